@@ -11,6 +11,10 @@ buffer) are resident in HBM before the timed region.  Synthetic transitions (SUR
 N > 1: one process per GPU (torch.distributed / RCCL); the global batch of 256 is sharded over
 ranks (strong scaling), every rank holds a replica of the replay buffer and the identical index
 stream, gradients (+ loss scalars) are all-reduced once per update (common.py:213-214 pmean).
+
+A plain run sets up, warms up, times --steps iterations and prints one JSON line (ms_per_step = one timed step);
+--dump-outputs DIR also writes what the last timed step computed.  --full adds everything else the line can carry
+(per-kernel timing and roofline, feature verification, CPU baseline, multi-GPU projection).
 """
 import argparse
 import itertools
@@ -103,17 +107,25 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--repeats", type=int, default=3,
-                    help="timed repetitions of --steps iterations (each bracketed by barrier + synchronize); the MEDIAN is reported")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline figure: per-kernel HIP-event timing and the roofline, "
+                         "the feature verification, the host enqueue cost, the CPU baseline, the multi-GPU projection, and 3 timed "
+                         "repetitions by default.  Off: set up, warm up, time --steps iterations once, print the result line")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="timed repetitions of --steps iterations (each bracketed by barrier + synchronize); the MEDIAN is reported "
+                         "(default: 1, with --full 3)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed to DIR/<name>.npy: the update's info scalars "
+                         "(float64), the trainable params and target params (float32) and a fixed sample of the Adam moments")
     ap.add_argument("--car", type=int, default=None, help="critic_actor_ratio (grad-steps per iteration); default: the workload's")
     ap.add_argument("--capacity", type=int, default=None, help="online buffer capacity (default 200000)")
     ap.add_argument("--fill", type=int, default=None, help="online buffer fill (default 20000)")
     ap.add_argument("--state-dim", type=int, default=24)
     ap.add_argument("--no-verify", action="store_true",
-                    help="skip the post-run check that the features the pipelined trunk produced (fused GroupNorm epilogues, update "
+                    help="--full: skip the post-run check that the features the pipelined trunk produced (fused GroupNorm epilogues, update "
                          "chain co-running) equal a serial re-encode with the un-fused elementwise passes")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0)
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="--full: time budget of the CPU baseline")
     ap.add_argument("--trunk", choices=["f16x3", "f32"], default="f16x3",
                     help="trunk conv arithmetic: split-fp16 MFMA (default, 1.3e-5 of fp64) or exact fp32 MFMA")
     ap.add_argument("--encoder", choices=["resnet-pretrained", "small"], default="resnet-pretrained",
@@ -155,6 +167,8 @@ def main():
     ap.add_argument("--emulate-world", type=int, default=0,
                     help="diagnostic: run ONE rank's share (B/world samples, no collective) of a world-size-N job")
     args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 3 if args.full else 1
     if args.workload == "sac_state":
         return sac_state_main(max(args.steps, 50))
     if args.workload == "actor_latency":
@@ -352,7 +366,9 @@ def main():
     global PROFILE_EVERY
     if args.steps * max(1, args.repeats) >= 320:
         PROFILE_EVERY = 16
-    _lib.check(_lib.lib().serl_profile_enable(0 if os.environ.get("SERL_BENCH_NOPROF") == "1" else PROFILE_EVERY))
+    # the per-kernel events feed the roofline: a plain run (no --full) times its steps without them
+    profiling = args.full and os.environ.get("SERL_BENCH_NOPROF") != "1"
+    _lib.check(_lib.lib().serl_profile_enable(PROFILE_EVERY if profiling else 0))
     _lib.check(_lib.lib().serl_profile_reset())
     coll["on"] = True
     dts = []
@@ -370,15 +386,19 @@ def main():
     prof = _lib.profile_read()
     _lib.check(_lib.lib().serl_profile_enable(0))
     torch.cuda.synchronize()
-    # host cost of enqueueing one iteration on empty queues (diagnostic: is the chain launch-bound?)
-    host_ms = []
-    for _ in range(5):
-        torch.cuda.synchronize()
-        h0 = time.perf_counter()
-        iteration()
-        host_ms.append((time.perf_counter() - h0) * 1e3)
-    torch.cuda.synchronize()
     info = core.read_info()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, core, info)
+    host_ms = []
+    if args.full:
+        # host cost of enqueueing one iteration on empty queues (diagnostic: is the chain launch-bound?)
+        for _ in range(5):
+            torch.cuda.synchronize()
+            h0 = time.perf_counter()
+            iteration()
+            host_ms.append((time.perf_counter() - h0) * 1e3)
+        torch.cuda.synchronize()
+        info = core.read_info()
     if not (farm and learner.role == "worker"):
         assert all(np.isfinite(v) for v in info.values()), info
     if world > 1:   # max over ranks, per repetition
@@ -388,8 +408,86 @@ def main():
     dt = float(np.median(dts))
     grad_steps = args.steps * car
     value = grad_steps / dt
-    verify = None if (args.no_verify or args.no_pipeline or args.trunk != "f16x3" or small or farm) else verify_features(learner, core, dbs, car)
+    verify = None if (not args.full or args.no_verify or args.no_pipeline or args.trunk != "f16x3" or small or farm) else verify_features(learner, core, dbs, car)
 
+    roofline = roofline_figures(prof, args, Bl, KEYS, S, A, small, dt, grad_steps) if args.full else None
+
+    out = {
+        "metric": f"learner grad-steps/sec (DrQ, bs{B}, {len(KEYS)}x128x128 img)" + (" [SmallEncoder]" if small else ""), "value": round(value, 3),
+        "unit": "grad-steps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(1e3 * dt / args.steps, 4), "higher_is_better": True, "scaling": "strong",
+        "vs_baseline": None,
+        "dtype": ("f32 (all GEMMs incl. the SmallEncoder convs as bf16x3: exact three-way bf16 split, six piece products, fp32 accumulate)" if small
+                  else "f32 (trunk convs as split-fp16 MFMA x3, fp32 accumulate; <=1e-6 vs fp64)" if args.trunk == "f16x3" else "f32"),
+        "data": "synthetic",
+        "config": {"workload": wl["name"].replace("ResNet-10 frozen trunk", "trainable SmallEncoder") if small else wl["name"], "workload_key": args.workload, "global_batch": B,
+                   "per_gpu_batch": Bl, "cameras": len(KEYS), "image_keys": list(KEYS), "image": [H, W, 3], "state_dim": S, "act_dim": A,
+                   "critic_actor_ratio": car, "utd_ratio": 1,
+                   "buffers": [{"capacity": c_, "fill": f_, "seed": s_, "samples_per_batch": n_} for c_, f_, s_, n_ in bufspec],
+                   "replay_capacity": bufspec[0][0], "replay_fill": bufspec[0][1], "parallelism": (f"trunk farm, {args.farm_role} role measured alone on one GPU" if args.farm_role else
+                                                                                                      f"trunk farm: 1 updater + {world - 1} trunk workers, features point to point" if farm else
+                                                                                                      f"dp{world}" + (f" (emulating 1 rank of dp{emu}, no collective)" if emu else "")), "grad_steps_per_step": car,
+                   "random_stream": ("jax.random threefry2x32 with the reference's key schedule: crop offsets, REDQ indices"
+                                     + (", policy noise, Dropout masks" if learner.device_noise == "threefry" else "; policy noise / Dropout masks hashed on the device")),
+                   "encoder": args.encoder, "trunk_passes_per_grad_step": 0 if small else 2, "trunk_arithmetic": "f32" if small else args.trunk,
+                   "schedule": "serial" if args.no_pipeline else (
+                       "trunk(i+1) overlapped with update(i) on a 2nd stream" + ("; gather(i+2) on a 3rd" if getattr(sched, "gather_stream", None) is not None else "")),
+                   # (every SERL_* switch set for this run: a variant line says so itself)
+                   "env_switches": {k: v for k, v in sorted(os.environ.items()) if k.startswith("SERL_")}},
+        "repeats": len(dts), "ms_per_step_runs": [round(1e3 * x / args.steps, 4) for x in dts],
+        "last_info": {k: round(float(v), 6) for k, v in info.items()},
+        "setup": {"replay_fill_s": round(fill_s, 2)},
+    }
+    if args.full:
+        out["roofline"] = roofline
+        out["host_enqueue_ms_per_iteration"] = round(min(host_ms), 4)
+    if dist is not None:
+        by_size = {}
+        for nbytes, e0, e1 in coll["timed"]:
+            by_size.setdefault(nbytes, []).append(e0.elapsed_time(e1) * 1e3)
+        out["collective"] = {
+            "backend": "nccl (RCCL)", "world_size": dist.get_world_size(), "launcher": "torch.distributed.run",
+            "all_reduces_per_step": coll["calls"] / max(args.steps * len(dts), 1),
+            "bytes_per_step": coll["bytes"] / max(args.steps * len(dts), 1),
+            "avg_us_by_bytes": {str(k): round(float(np.mean(v)), 2) for k, v in sorted(by_size.items())},
+            "overlap_reduce": args.overlap_reduce,
+            "note": ("per critic update two overlapped all-reduce(SUM) buckets on a communication stream -- [ensemble | Q head | proprio | "
+                     "loss scalars] issued while the encoder-head backward still runs, then [encoder heads] -- " if args.overlap_reduce == "on"
+                     else "per critic update ONE all-reduce(SUM) of [critic grads | loss scalars] on the update stream (no stream crossing; "
+                          "--overlap-reduce on = two buckets on a communication stream, measured slower at B/8) ")
+                    + "and one of [scalars | actor grads] per actor update; HIP events on the stream the collective is enqueued on, every 4th call"}
+    if verify is not None:
+        out["verify"] = verify
+    proj = scaling_projection() if args.full else None
+    if proj is not None and args.farm_role is None and not emu:
+        out["projection"] = proj
+    diag = os.environ.get("SERL_BENCH_DIAG") or ("hostprof" if os.environ.get("SERL_BENCH_HOSTPROF") == "1" else "") or (
+        f"farm-role-{args.farm_role}" if args.farm_role else "")
+    if diag:
+        # a diagnostic run is never a bench line: no `metric` / `value` / `unit` (SERL_BENCH_DIAG=noproduced runs updates that did
+        # not wait for their features -- its numbers time a wrong computation)
+        out = {"diagnostic": True, "diag": diag, "diagnostic_ms_per_step": out["ms_per_step"],
+               **{k: v for k, v in out.items() if k not in ("metric", "value", "unit", "ms_per_step", "vs_baseline", "higher_is_better")}}
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not diag:
+        out["cpu_baseline"] = cpu_baseline(args.cpu_seconds, KEYS, S, A, B)
+    # the JSON line must be the last thing on stdout: librccl prints its version banner through C stdio, which is
+    # block-buffered when stdout is a pipe/file and would otherwise surface after this line at exit -- every rank
+    # flushes before the final barrier, rank 0 prints after it
+    sys.stdout.flush()
+    try:
+        import ctypes
+        ctypes.CDLL(None).fflush(None)
+    except Exception:
+        pass
+    if dist is not None:
+        dist.barrier()
+        dist.destroy_process_group()
+    if rank == 0:
+        print(json.dumps(out), flush=True)
+
+
+def roofline_figures(prof, args, Bl, KEYS, S, A, small, dt, grad_steps):
+    """--full: the roofline of the dominant kernel family and of the whole step from the per-kernel HIP events of the timed region."""
     # ---- roofline of the dominant kernel family (implicit-GEMM convs of the frozen trunk)
     macs = conv_macs_per_image()
     n_img = 2 * len(KEYS) * Bl
@@ -512,77 +610,7 @@ def main():
     if "gather_crop" in per_kernel:
         roofline["sample_aug_hbm"] = {"bound": "hbm", "kernel": "gather_crop_rgb_kernel", "achieved": per_kernel["gather_crop"]["TBps"],
                                       "peak": PEAK_HBM, "unit": "TB/s", "frac": per_kernel["gather_crop"]["frac_hbm"]}
-
-    out = {
-        "metric": f"learner grad-steps/sec (DrQ, bs{B}, {len(KEYS)}x128x128 img)" + (" [SmallEncoder]" if small else ""), "value": round(value, 3),
-        "unit": "grad-steps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": round(1e3 * dt / args.steps, 4), "higher_is_better": True, "scaling": "strong",
-        "vs_baseline": None,
-        "dtype": ("f32 (all GEMMs incl. the SmallEncoder convs as bf16x3: exact three-way bf16 split, six piece products, fp32 accumulate)" if small
-                  else "f32 (trunk convs as split-fp16 MFMA x3, fp32 accumulate; <=1e-6 vs fp64)" if args.trunk == "f16x3" else "f32"),
-        "data": "synthetic",
-        "config": {"workload": wl["name"].replace("ResNet-10 frozen trunk", "trainable SmallEncoder") if small else wl["name"], "workload_key": args.workload, "global_batch": B,
-                   "per_gpu_batch": Bl, "cameras": len(KEYS), "image_keys": list(KEYS), "image": [H, W, 3], "state_dim": S, "act_dim": A,
-                   "critic_actor_ratio": car, "utd_ratio": 1,
-                   "buffers": [{"capacity": c_, "fill": f_, "seed": s_, "samples_per_batch": n_} for c_, f_, s_, n_ in bufspec],
-                   "replay_capacity": bufspec[0][0], "replay_fill": bufspec[0][1], "parallelism": (f"trunk farm, {args.farm_role} role measured alone on one GPU" if args.farm_role else
-                                                                                                      f"trunk farm: 1 updater + {world - 1} trunk workers, features point to point" if farm else
-                                                                                                      f"dp{world}" + (f" (emulating 1 rank of dp{emu}, no collective)" if emu else "")), "grad_steps_per_step": car,
-                   "random_stream": ("jax.random threefry2x32 with the reference's key schedule: crop offsets, REDQ indices"
-                                     + (", policy noise, Dropout masks" if learner.device_noise == "threefry" else "; policy noise / Dropout masks hashed on the device")),
-                   "encoder": args.encoder, "trunk_passes_per_grad_step": 0 if small else 2, "trunk_arithmetic": "f32" if small else args.trunk,
-                   "schedule": "serial" if args.no_pipeline else (
-                       "trunk(i+1) overlapped with update(i) on a 2nd stream" + ("; gather(i+2) on a 3rd" if getattr(sched, "gather_stream", None) is not None else "")),
-                   # (every SERL_* switch set for this run: a variant line says so itself)
-                   "env_switches": {k: v for k, v in sorted(os.environ.items()) if k.startswith("SERL_")}},
-        "roofline": roofline,
-        "repeats": len(dts), "ms_per_step_runs": [round(1e3 * x / args.steps, 4) for x in dts],
-        "last_info": {k: round(float(v), 6) for k, v in info.items()},
-        "host_enqueue_ms_per_iteration": round(min(host_ms), 4), "setup": {"replay_fill_s": round(fill_s, 2)},
-    }
-    if dist is not None:
-        by_size = {}
-        for nbytes, e0, e1 in coll["timed"]:
-            by_size.setdefault(nbytes, []).append(e0.elapsed_time(e1) * 1e3)
-        out["collective"] = {
-            "backend": "nccl (RCCL)", "world_size": dist.get_world_size(), "launcher": "torch.distributed.run",
-            "all_reduces_per_step": coll["calls"] / max(args.steps * len(dts), 1),
-            "bytes_per_step": coll["bytes"] / max(args.steps * len(dts), 1),
-            "avg_us_by_bytes": {str(k): round(float(np.mean(v)), 2) for k, v in sorted(by_size.items())},
-            "overlap_reduce": args.overlap_reduce,
-            "note": ("per critic update two overlapped all-reduce(SUM) buckets on a communication stream -- [ensemble | Q head | proprio | "
-                     "loss scalars] issued while the encoder-head backward still runs, then [encoder heads] -- " if args.overlap_reduce == "on"
-                     else "per critic update ONE all-reduce(SUM) of [critic grads | loss scalars] on the update stream (no stream crossing; "
-                          "--overlap-reduce on = two buckets on a communication stream, measured slower at B/8) ")
-                    + "and one of [scalars | actor grads] per actor update; HIP events on the stream the collective is enqueued on, every 4th call"}
-    if verify is not None:
-        out["verify"] = verify
-    proj = scaling_projection()
-    if proj is not None and args.farm_role is None and not emu:
-        out["projection"] = proj
-    diag = os.environ.get("SERL_BENCH_DIAG") or ("hostprof" if os.environ.get("SERL_BENCH_HOSTPROF") == "1" else "") or (
-        f"farm-role-{args.farm_role}" if args.farm_role else "")
-    if diag:
-        # a diagnostic run is never a bench line: no `metric` / `value` / `unit` (SERL_BENCH_DIAG=noproduced runs updates that did
-        # not wait for their features -- its numbers time a wrong computation)
-        out = {"diagnostic": True, "diag": diag, "diagnostic_ms_per_step": out["ms_per_step"],
-               **{k: v for k, v in out.items() if k not in ("metric", "value", "unit", "ms_per_step", "vs_baseline", "higher_is_better")}}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not diag:
-        out["cpu_baseline"] = cpu_baseline(args.cpu_seconds, KEYS, S, A, B)
-    # the JSON line must be the last thing on stdout: librccl prints its version banner through C stdio, which is
-    # block-buffered when stdout is a pipe/file and would otherwise surface after this line at exit -- every rank
-    # flushes before the final barrier, rank 0 prints after it
-    sys.stdout.flush()
-    try:
-        import ctypes
-        ctypes.CDLL(None).fflush(None)
-    except Exception:
-        pass
-    if dist is not None:
-        dist.barrier()
-        dist.destroy_process_group()
-    if rank == 0:
-        print(json.dumps(out), flush=True)
+    return roofline
 
 
 def small_encoder_flops_per_image(H=H, W=W):
@@ -620,6 +648,34 @@ def small_encoder_roofline(prof, per_kernel, Bl, n_cam):
             "note": "durations are HIP events around the whole pass (all launches of the four layers); achieved = executed bf16 MFMA rate "
                     "(6 piece products per fp32 product) against the dense bf16 peak; M is large and N = 32..256, K = 28..1153: these "
                     "GEMMs are bound by operand traffic, not by the matrix pipe"}
+
+
+DUMP_MOMENT_SAMPLE = 4096   # elements per leaf of each Adam moment written by --dump-outputs
+
+
+def dump_outputs(out_dir, core, info):
+    """--dump-outputs: what a caller of the timed path receives after its last step -- the update's info scalars and the train
+    state (params and target params of every trainable leaf in full, each Adam moment as a fixed sample of at most
+    DUMP_MOMENT_SAMPLE elements per leaf, the same indices in every run) -- as out_dir/<name>.npy, about 41 MB at the bench shape."""
+    os.makedirs(out_dir, exist_ok=True)
+
+    def put(name, arr):
+        np.save(os.path.join(out_dir, name.replace("/", ".") + ".npy"), arr)
+
+    for k, v in info.items():
+        put(f"info.{k}", np.asarray(v, np.float64))
+    leaves = [leaf for leaf in core.leaves if not leaf.startswith("trunk/")]   # the frozen trunk never changes
+    for section in ("params", "target_params"):
+        for leaf in leaves:
+            put(f"{section}/{leaf}", core.get(section, leaf).astype(np.float32))
+    for tx in ("actor", "critic", "temperature"):
+        for moment in ("mu", "nu"):
+            for leaf in leaves:
+                v = core.get(f"opt/{tx}/{moment}", leaf).astype(np.float32)
+                if v.size > DUMP_MOMENT_SAMPLE:
+                    idx = np.sort(np.random.default_rng(v.size).choice(v.size, DUMP_MOMENT_SAMPLE, replace=False))
+                    v = v[idx]
+                put(f"opt/{tx}/{moment}/{leaf}", v)
 
 
 def verify_features(learner, core, dbs, car, iters=12, tol=2e-6):

@@ -2,7 +2,7 @@
 # GPU box: same-call A/B of one environment switch.  usage: ab_env.sh OUT VAR "v1 v2 ..." ["bench args"] ; prints step time + selected kernel times
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/$1; mkdir -p $O; cd $R
 VAR=$2; VALS=$3; EXTRA=${4:-}
-NB="--no-cpu-baseline --no-verify --steps 100 --repeats 3 $EXTRA"
+NB="--full --no-cpu-baseline --no-verify --steps 100 --repeats 3 $EXTRA"
 for v in $VALS; do
   for m in "--no-pipeline" ""; do
     tag=${VAR}_${v}$(echo $m | tr -d ' -')

@@ -3,7 +3,7 @@
 # never shipped): 1 no epilogues, 2 no MFMAs, 4 no LDS fragment reads, 8 no DMA pieces.  Serial schedule, HIP-event time per launch.
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r06_call13; rm -rf $O; mkdir -p $O; cd $R
 NB="--no-cpu-baseline --no-verify --no-pipeline --steps 60 --repeats 2"
-run() { tag=$1; shift; timeout 200 python bench.py $NB "$@" > $O/$tag.json 2> $O/$tag.err; python -c "
+run() { tag=$1; shift; timeout 200 python bench.py --full $NB "$@" > $O/$tag.json 2> $O/$tag.err; python -c "
 import json
 try:
     d=json.load(open('$O/$tag.json')); pk=d['roofline']['per_kernel']

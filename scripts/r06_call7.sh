@@ -3,7 +3,7 @@
 # 16 no arrive-and-wait, 32 no statistics atomics, 64 no residual loads, 128 no final stores (48 = 16 + 32, 240 = all four).  Serial schedule.
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r06_call7; rm -rf $O; mkdir -p $O; cd $R
 NB="--no-cpu-baseline --no-verify --no-pipeline --steps 60 --repeats 2"
-run() { tag=$1; shift; timeout 200 python bench.py $NB "$@" > $O/$tag.json 2> $O/$tag.err; python -c "
+run() { tag=$1; shift; timeout 200 python bench.py --full $NB "$@" > $O/$tag.json 2> $O/$tag.err; python -c "
 import json
 try:
     d=json.load(open('$O/$tag.json')); pk=d['roofline']['per_kernel']

@@ -13,7 +13,7 @@ R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r06_evidence; rm -rf $O; mkdir -p $O
 echo "$C" > $O/commit.txt
 cd $R
 date +%s > $O/t0
-timeout 300 python bench.py > $O/bench.json 2> $O/bench.err
+timeout 300 python bench.py --full > $O/bench.json 2> $O/bench.err
 cd /tmp && export TMPDIR=/tmp
 PB="--no-cpu-baseline --no-verify --fill 3000 --steps 30 --warmup 5 --repeats 1"
 timeout 200 rocprofv3 --kernel-trace --stats -d $O/stats -o s -- python $R/bench.py $PB > $O/stats.log 2>&1
@@ -40,7 +40,7 @@ timeout 120 rocprofv3 --kernel-trace --output-format csv -d $O/trace_upd -o t --
 find $O -name '*.db' -delete; find $O -name '*.csv' -size +2M -delete
 cd $R
 date +%s > $O/t1
-NB="--no-cpu-baseline --steps 110 --repeats 3"
+NB="--full --no-cpu-baseline --steps 110 --repeats 3"
 timeout 150 python bench.py $NB --no-pipeline > $O/bench_serial.json 2> /dev/null
 for w in 2 4 8; do timeout 100 python bench.py $NB --emulate-world $w > $O/bench_emulate_world$w.json 2> /dev/null; done
 timeout 100 python bench.py $NB --farm-role worker > $O/bench_farm_worker.json 2> /dev/null

@@ -19,7 +19,7 @@ def _bench(*args, timeout=600):
 
 @pytest.mark.parametrize("overlap,n_ar", [("off", 2), ("on", 3)])
 def test_one_rank_through_the_launcher(gpu, overlap, n_ar):
-    r = _bench("--gpus", "1", "--force-launcher", "--overlap-reduce", overlap, *SMALL)
+    r = _bench("--gpus", "1", "--force-launcher", "--overlap-reduce", overlap, "--full", *SMALL)
     assert r.returncode == 0, r.stderr[-3000:]
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]
     out = json.loads(line)

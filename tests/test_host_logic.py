@@ -230,18 +230,12 @@ def _demo_files(tmp_path, n_files=2, per_file=3, D=14):
     return paths
 
 
-def _reference_functions(names):
-    """The named top-level functions of the reference's data/data_store.py, executed from where they lie (the module itself
-    imports agentlace, which is not installed; these functions only need pickle / numpy / copy)."""
-    import ast
-    path = "/root/reference/serl_launcher/serl_launcher/data/data_store.py"
-    if not os.path.exists(path):
-        pytest.skip("/root/reference not present")
-    tree = ast.parse(open(path).read())
-    mod = ast.Module([n for n in tree.body if isinstance(n, ast.FunctionDef) and n.name in names], type_ignores=[])
-    ns = {"DataStoreBase": object}
-    exec(compile(mod, path, "exec"), ns)
-    return [ns[n] for n in names]
+def _reference_outputs():
+    """What the reference's data/data_store.py populate_data_store / populate_data_store_with_z_axis_only inserted for
+    _demo_files (recorded by tests/golden/make_golden_live.py)."""
+    import pickle
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "live_populate_data_store.pkl"), "rb") as fh:
+        return pickle.load(fh)
 
 
 def _same_tree(a, b):
@@ -259,13 +253,12 @@ def test_populate_data_store_matches_the_reference(tmp_path, capsys):
     from serl_amd.data.data_store import populate_data_store, populate_data_store_with_z_axis_only
     from serl_amd.utils import launcher
     paths = _demo_files(tmp_path)
-    ref_plain, ref_z = _reference_functions(["populate_data_store", "populate_data_store_with_z_axis_only"])
-    for ours, ref in ((populate_data_store, ref_plain), (populate_data_store_with_z_axis_only, ref_z)):
-        a, b = _ListStore(), _ListStore()
+    ref = _reference_outputs()
+    for ours in (populate_data_store, populate_data_store_with_z_axis_only):
+        a, b = _ListStore(), ref[ours.__name__]
         assert ours(a, paths) is a
-        ref(b, paths)
         assert len(a) == len(b) == 6
-        for x, y in zip(a.items, b.items):
+        for x, y in zip(a.items, b):
             _same_tree(x, y)
     assert a.items[0]["observations"]["state"].shape == (1, 14 - 5)      # columns 4, 5, 7, 8, 9 dropped
     assert "Loaded 6 transitions." in capsys.readouterr().out

@@ -5,9 +5,12 @@
   /root/reference and runs it UNMODIFIED, in fp64, under stand-ins for its absent third-party libraries
   (oracle/jaxshim).  The oracle, fed the noise that run drew, must reproduce every info scalar and the whole final
   train state (params, target params, all three Adam states) to fp64 round-off.
-* when /root/reference is present (build container) the reference is also run live and compared directly.
+* tests/golden/live_*.{npz,json} were produced by tests/golden/make_golden_live.py from further runs of the reference's own code
+  (one update schedule per random stream, its random crop, its parameter tree); the tests below compare the oracle with them.
 """
 import glob
+import hashlib
+import json
 import os
 
 import numpy as np
@@ -17,7 +20,6 @@ import torch
 from oracle import drq_oracle as O
 from oracle import golden_update as G
 from oracle import ref_update_runner as RR
-from oracle import ref_update_shim as RS
 
 GOLDEN = sorted(glob.glob(os.path.join(os.path.dirname(__file__), "golden", "update_*.npz")))
 F64_TOL = 1e-9
@@ -78,75 +80,92 @@ def test_golden_fixtures_exist():
     assert len(GOLDEN) >= 8, "tests/golden/update_*.npz missing: run tests/golden/make_golden_update.py in the build container"
 
 
-needs_ref = pytest.mark.skipif(not RS.reference_available(), reason="/root/reference not present (GPU box)")
+
+class _Records(dict):
+    """npz-like view (`.files`, `[key]`) of a live_update_*.npz with its final-state records unpacked from final_data"""
+    @property
+    def files(self):
+        return list(self)
 
 
-@needs_ref
-def test_live_reference_matches_oracle():
-    """The reference itself, imported from /root/reference and run here, against the oracle (no fixture in between)."""
-    cfg = O.Config(image_keys=("wrist_1", "wrist_2"), H=64, W=64, S=19, A=7)     # the peg-insertion key names / dims
-    sched = [("critics",), ("high_utd", 2), ("critics",)]
-    res = RR.run_reference(cfg, 4, sched, param_seed=7, batch_seed=55)
-    st, infos = _run_oracle(cfg, res["steps"], 7)
-    for info, step in zip(infos, res["steps"]):
+def _live(name, monkeypatch):
+    """A reference run recorded by tests/golden/make_golden_live.py (the reference's own update code, fp64).  Its final-state
+    records use a smaller sample per leaf than oracle/golden_update.py's default: the comparison follows the recorded form."""
+    z = np.load(os.path.join(os.path.dirname(__file__), "golden", f"live_update_{name}.npz"))
+    rec = _Records((k, z[k]) for k in z.files if k not in ("final_index", "final_data"))
+    data, at = z["final_data"], 0
+    for key, n in json.loads(str(z["final_index"])):
+        rec[key] = data[at:at + n]
+        at += n
+    assert at == data.size
+    monkeypatch.setattr(G, "FULL_MAX", int(z["record_form"][0]))
+    monkeypatch.setattr(G, "N_SAMPLE", int(z["record_form"][1]))
+    return G.unpack(rec), rec
+
+
+def _assert_final_state(st, g, sections=None):
+    for sec, tree in _oracle_sections(st).items():
+        if sections is not None and sec not in sections:
+            continue
+        assert set(g["final"][sec]) == set(tree), sec
+        for name, t in tree.items():
+            e, how = G.leaf_compare(f"{sec}/{name}", g["final"][sec][name], t.numpy())
+            assert e <= F64_TOL, (sec, name, how, e)
+
+
+def test_live_reference_matches_oracle(monkeypatch):
+    """A reference run (peg-insertion key names / dims, critics / high_utd(2) / critics) against the oracle: every info
+    scalar, the optimizer counts and the whole final train state."""
+    g, z = _live("peg", monkeypatch)
+    cfg = g["cfg"]
+    assert cfg.image_keys == ("wrist_1", "wrist_2") and (cfg.H, cfg.W, cfg.S, cfg.A) == (64, 64, 19, 7) and g["B"] == 4
+    assert [s["kind"] for s in g["steps"]] == ["critics", "high_utd", "critics"]
+    st, infos = _run_oracle(cfg, g["steps"], 7)
+    for info, step in zip(infos, g["steps"]):
+        assert set(info) <= set(step["info"])
         for k, v in info.items():
             assert abs(v - step["info"][k]) <= F64_TOL * max(1.0, abs(step["info"][k])), (k, v, step["info"][k])
-    f = res["final"]
-    assert st.step == f["step"] == 5 and all(c == (5, 5) for c in f["count"].values())
-    for k in st.params:
-        for got, ref in ((st.params[k], f["params"][k]), (st.target[k], f["target"][k])):
-            assert np.abs(got.numpy().reshape(-1) - ref).max() <= F64_TOL * (np.abs(ref).max() + 1e-30), k
-        for tx in O.TX_NAMES:
-            for got, ref in ((st.opt[tx]["mu"][k], f["mu"][tx][k]), (st.opt[tx]["nu"][k], f["nu"][tx][k])):
-                assert np.abs(got.numpy().reshape(-1) - ref).max() <= F64_TOL * (np.abs(ref).max() + 1e-300), (tx, k)
+    assert st.step == g["meta"]["final_step"] == 5 and all(tuple(c) == (5, 5) for c in z["count"])
+    _assert_final_state(st, g)
     # frozen trunk: parameters untouched, target copy = EMA of identical values (drifts by round-off only)
     trunk, _ = O.init_params(cfg, 7)
-    assert np.array_equal(f["trunk_conv_init"], trunk["trunk/conv_init"].astype(np.float64).reshape(-1))
-    assert np.abs(f["trunk_conv_init_target"] - f["trunk_conv_init"]).max() < 1e-14
+    mine = np.ascontiguousarray(trunk["trunk/conv_init"].astype(np.float64).reshape(-1))
+    assert hashlib.sha256(mine.tobytes()).hexdigest() == str(z["trunk_conv_init_sha256"])
+    assert float(z["trunk_conv_init_target_drift"]) < 1e-14
 
 
-@needs_ref
 def test_live_reference_on_jax_key_chain(monkeypatch):
     """The same with the stand-in jax.random drawing through JAX's own threefry2x32 key chain (oracle/jaxshim/jax/threefry.py,
     pinned in tests/test_threefry_oracle.py): the reference's split / fold_in / randint / normal / bernoulli calls then consume
     the numbers a real JAX run draws for these keys; the oracle, fed the recorded draws, still agrees."""
-    monkeypatch.setenv("SERL_JAXSHIM_PRNG", "threefry")
-    cfg = O.Config(image_keys=("front",), H=64, W=64, S=7, A=4)
-    sched = [("critics",), ("high_utd", 1)]
-    res = RR.run_reference(cfg, 4, sched, param_seed=3, batch_seed=11)
-    st, infos = _run_oracle(cfg, res["steps"], 3)
-    for info, step in zip(infos, res["steps"]):
+    g, _ = _live("key_chain", monkeypatch)
+    cfg = g["cfg"]
+    assert g["meta"]["prng"] == "threefry" and cfg.image_keys == ("front",) and (cfg.S, cfg.A) == (7, 4)
+    st, infos = _run_oracle(cfg, g["steps"], 3)
+    for info, step in zip(infos, g["steps"]):
         for k, v in info.items():
             assert abs(v - step["info"][k]) <= F64_TOL * max(1.0, abs(step["info"][k])), (k, v, step["info"][k])
-    f = res["final"]
-    for k in st.params:
-        assert np.abs(st.params[k].numpy().reshape(-1) - f["params"][k]).max() <= F64_TOL * (np.abs(f["params"][k]).max() + 1e-30), k
+    _assert_final_state(st, g, sections=("params",))
 
 
-@needs_ref
 def test_reference_random_crop_equals_the_oracle_shift():
-    """vision/data_augmentations.py:7-36 (edge pad 4 + dynamic_slice) run from the reference == oracle random_shift."""
-    jax = RS.install(True)
-    import jax.numpy as jnp
-    from serl_launcher.vision.data_augmentations import batched_random_crop
+    """vision/data_augmentations.py:7-36 (edge pad 4 + dynamic_slice) as the reference computed it == oracle random_shift."""
     from oracle.replay_oracle import random_shift
+    z = np.load(os.path.join(os.path.dirname(__file__), "golden", "live_random_crop.npz"))
     img = np.random.default_rng(0).integers(0, 256, (6, 1, 24, 20, 3), dtype=np.uint8)
-    tape = jax.random.start_tape()
-    out = np.asarray(batched_random_crop(jnp.asarray(img), jax.random.PRNGKey(3), padding=4, num_batch_dims=2))
-    jax.random.stop_tape()
-    offs = np.stack([r["value"] for r in tape]).astype(np.int32)
+    out, offs = z["out"], z["offs"]
+    assert out.shape == img.shape
     assert offs.shape == (6, 2) and offs.min() >= 0 and offs.max() <= 8
     assert np.array_equal(out[:, 0], random_shift(img[:, 0], offs))
 
 
-@needs_ref
 def test_reference_parameter_tree_is_what_the_product_exports():
     """agent.state.params of the reference (built by its own make_drq_agent + load_resnet10_params on a synthetic
     pickle) has exactly the paths serl_amd/agents/flax_tree.py exports, the trunk only under the first camera."""
     from serl_amd.agents import flax_tree as FT
     cfg = O.Config(image_keys=("front", "wrist"), H=64, W=64, S=5, A=3)
-    res = RR.run_reference(cfg, 2, [], param_seed=1)
-    tree = res["final"]["param_tree"]
+    with open(os.path.join(os.path.dirname(__file__), "golden", "live_param_tree.json")) as fh:
+        tree = json.load(fh)
 
     def paths(t, pre=()):
         out = {}

@@ -1,12 +1,11 @@
-"""CPU: pins oracle/replay_oracle.py against the reference-generated golden fixtures and, when
-/root/reference is present, against the reference class itself."""
+"""CPU: pins oracle/replay_oracle.py against the reference-generated golden fixtures (tests/golden/make_golden_replay.py,
+tests/golden/make_golden_live.py)."""
 import itertools
 import os
 
 import numpy as np
 import pytest
 
-from oracle import ref_shim
 from oracle.replay_oracle import PCG64Py, ReplayOracle, concat_batches, random_shift, unpack
 from helpers import load_case, stream_for
 
@@ -34,26 +33,22 @@ def test_oracle_matches_golden(name):
             assert (b[f] == z[f"{f}_{s}"]).all()
 
 
-@pytest.mark.skipif(not ref_shim.reference_available(), reason="/root/reference not present")
 def test_oracle_matches_reference_live():
+    """The oracle against the reference's MemoryEfficientReplayBuffer as recorded by tests/golden/make_golden_live.py: the
+    validity mask after every insert and every packed sample."""
     from serl_amd.utils.synthetic import transition_stream
     keys, H, W, C, T, S, A, cap = ("a", "b"), 16, 16, 3, 1, 4, 2, 23
-    Ref = ref_shim.load_reference_buffer_cls()
-    osp, asp = ref_shim.make_spaces(keys, H, W, C, T, S, A)
-    ref = Ref(osp, asp, cap, pixel_keys=keys)
-    ref.seed(9)
+    g = np.load(os.path.join(os.path.dirname(__file__), "golden", "live_replay_packed.npz"))
     o = ReplayOracle(keys, H, W, C, T, S, A, cap)
     o.seed(9)
     for n, tr in enumerate(itertools.islice(transition_stream(keys, H, W, C, T, S, A, 5, 77), 120)):
-        ref.insert(tr)
         o.insert(tr)
-        assert (ref._is_correct_index == o.valid).all()
+        assert (g[f"valid_{n}"] == o.valid).all()
         if n % 7 == 6:
-            rb = ref.sample(8, pack_obs_and_next_obs=True)
             ob = o.sample(8)
             for k in keys:
-                assert (rb["observations"][k] == ob["observations"][k]).all()
-            assert (np.asarray(rb["rewards"]) == ob["rewards"]).all()
+                assert (g[f"obs_{k}_{n}"] == ob["observations"][k]).all()
+            assert (g[f"rewards_{n}"] == ob["rewards"]).all()
 
 
 def test_pcg64_restatement_matches_numpy():
@@ -123,21 +118,19 @@ def test_plain_oracle_matches_reference_golden(name):
             assert np.array_equal(b[f], g[f"{f}_{s}"]), (s, f)
 
 
-@pytest.mark.skipif(not ref_shim.reference_available(), reason="/root/reference not present")
 def test_plain_oracle_matches_live_reference():
+    """The plain oracle against the reference's ReplayBuffer as recorded by tests/golden/make_golden_live.py."""
     import itertools
     from oracle.replay_oracle import PlainReplayOracle
     from serl_amd.utils.synthetic import flat_stream
-    Ref = ref_shim.load_reference_plain_buffer_cls()
     S, A, cap = 7, 3, 41
-    ref = Ref(ref_shim.Box(-np.inf, np.inf, (S,), np.float32), ref_shim.Box(-1, 1, (A,), np.float32), cap)
+    g = np.load(os.path.join(os.path.dirname(__file__), "golden", "live_replay_plain.npz"))
     o = PlainReplayOracle(S, A, cap)
-    ref.seed(5); o.seed(5)
+    o.seed(5)
     for i, tr in enumerate(itertools.islice(flat_stream(S, A, 6, 99), 100)):
-        ref.insert(tr); o.insert(tr)
+        o.insert(tr)
         if i % 17 == 16:
-            b = ref.sample(13)
             idx = o.sample_indices(13)
             ob = o.gather(idx)
             for f in ("observations", "next_observations", "actions", "rewards", "masks", "dones"):
-                assert np.array_equal(np.asarray(b[f]), ob[f]), (i, f)
+                assert np.array_equal(g[f"{f}_{i}"], ob[f]), (i, f)
