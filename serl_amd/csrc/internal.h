@@ -27,19 +27,29 @@ struct TrunkDims {
 TrunkDims trunk_dims(int H, int W);
 
 constexpr int kSyncPerImage = 8, kSyncTickets = 16;   // tickets: 8 per launch (one per XCD)
-constexpr int kKsplitTiles = 1024;   // partial tiles (workgroups) a K-split conv launch may use: 16 MB of scratch
-// Which kernels the last split-fp16 pass selected (introspection for the parity tests: the shapes a data-parallel rank runs
-// choose other kernels than the full batch does).  kern: 'S' row-slab, 'D' LDS-DMA, 'R' register-staged implicit GEMM,
-// 0 = layer absent; cfg: tile configuration of launch_conv_f16x3; fused: GroupNorm epilogue inside the conv (1 exchange, 2 local).
+// Every launch decision of a split-fp16 pass, made by its first piece before anything launches (plan_pass, trunk_f16x3.hip) and
+// kept for the pieces that follow; also the introspection of the parity tests (the shapes a data-parallel rank runs choose
+// other kernels than the full batch does).
 struct TrunkPlan {
   int images = 0;
+  bool fuse = false; // the pass uses the fused GroupNorm epilogues (SERL_GN_FUSE and the one-fused-pass-at-a-time claim)
   int pool = 0;      // 0: separate GroupNorm + max-pool pass, 1: pooled in conv_init + pool_finish, 2: completed in conv_init
   int raw_b0 = 0;    // block 0 reads conv_init's raw pooled tensor (RAWIN)
-  struct L { char kern = 0; int cfg = 0, pmode = 0, fused = 0, ksplit = 1; } conv[kTrunkStages][3];
+  // kern: 'S' row-slab, 'D' LDS-DMA, 'R' register-staged implicit GEMM, 'F' projection computed by conv0's launch, 0 = layer
+  // absent; cfg: tile configuration (9 = the row-slab kernels); pmode: how a wave's rows relate to images (3: statistics by a
+  // separate kernel); fused: GroupNorm epilogue inside the conv (1 exchange, 2 local) -- 0 on a conv0 / conv1 means the separate
+  // gn_relu_split / block_out pass follows it
+  struct L {
+    char kern = 0;
+    int cfg = 0, pmode = 0, fused = 0;
+    int expected = 0, group = 0;   // FuseArgs of a fused launch
+    bool raw = false;              // 'S' on conv_init's raw pooled tensor (b0_conv0 of a raw_b0 pass)
+    bool proj = false;             // 'D' conv0: the block's projection rides on this launch
+    int stagger = 0;               // 'S': ConvArgsB::stagger
+  } conv[kTrunkStages][3];
 };
 struct TrunkWorkspace {
   TrunkPlan plan{};
-  bool fuse_pass = false;   // the pass in flight uses the fused GroupNorm epilogues (decided by its first piece)
   int max_images = 0;
   TrunkDims d{};
   float* raw_init = nullptr;  // [N][h0][w0][64]
@@ -47,10 +57,6 @@ struct TrunkWorkspace {
   struct B {
     float *raw0, *raw1, *rawp, *out, *norm0;
   } blk[kTrunkStages]{};
-  // K-split scratch of the small-M conv kernel (trunk_f16x3.hip): kKsplitTiles partial 64x64 tiles + one arrival counter per
-  // output tile (zero between launches: the last arriver re-zeroes its counter)
-  float* kslab = nullptr;
-  int* kctr = nullptr;
   double* stats = nullptr;  // 13 GN layers x [N][4][2]
   int* sync = nullptr;      // directly behind `stats` (one memset): 13 layers x (kSyncPerImage arrival counters per image + kSyncTickets ints)
   size_t stats_sync_bytes = 0;

@@ -455,8 +455,6 @@ static size_t trunk_layout(TrunkWorkspace* ws, uint8_t* base, int N, int H, int 
     blk[i].out = (float*)take(e);
     blk[i].norm0 = (float*)take(e);
   }
-  float* kslab = (float*)take((size_t)kKsplitTiles * 64 * 64 * 4);
-  int* kctr = (int*)take((size_t)kKsplitTiles * sizeof(int));
   const size_t stats_bytes = al256((size_t)kGnLayers * N * kGnGroups * 2 * sizeof(double));
   const size_t sync_bytes = (size_t)kGnLayers * ((size_t)N * kSyncPerImage + kSyncTickets) * sizeof(int);
   double* stats = (double*)take(stats_bytes + sync_bytes);
@@ -466,7 +464,6 @@ static size_t trunk_layout(TrunkWorkspace* ws, uint8_t* base, int N, int H, int 
     ws->max_images = N; ws->d = d; ws->raw_init = raw_init; ws->pool = pool;
     for (int i = 0; i < kTrunkStages; ++i) ws->blk[i] = blk[i];
     ws->stats = stats; ws->base = base; ws->bytes = off;
-    ws->kslab = kslab; ws->kctr = kctr;
   }
   return off;
 }
@@ -480,14 +477,6 @@ int trunk_workspace_bind(TrunkWorkspace& ws, void* mem, int max_images, int H, i
   SERL_REQUIRE(H >= 32 && W >= 32, "trunk needs images of at least 32x32 (got %dx%d)", H, W);
   trunk_layout(&ws, (uint8_t*)mem, max_images, H, W);
   return SERL_OK;
-}
-
-static GnRef gn_ref(const double* stats, const float* gamma, const float* beta, int P, int Cc) {
-  GnRef g{};
-  g.stats = stats; g.gamma = gamma; g.beta = beta;
-  g.inv_count = 1.0 / ((double)P * (Cc / kGnGroups));
-  g.gsize = Cc / kGnGroups;
-  return g;
 }
 
 static int launch_conv(const char* tag, const float* in, const float* w, float* out, double* stats, GnRef in_gn,
@@ -653,13 +642,9 @@ int trunk_forward(const TrunkWeights& w, TrunkWorkspace& ws, const uint8_t* fram
     const int l0 = 1 + 3 * i, l1 = 2 + 3 * i, lp = 3 + 3 * i;
     const TrunkWeights::Block& bw = w.blk[i];
     const bool has_proj = bw.proj != nullptr;
-    static const char* kTags[kTrunkStages][3] = {{"conv_igemm/b0_conv0", "conv_igemm/b0_conv1", "conv_igemm/b0_proj"},
-                                                  {"conv_igemm/b1_conv0", "conv_igemm/b1_conv1", "conv_igemm/b1_proj"},
-                                                  {"conv_igemm/b2_conv0", "conv_igemm/b2_conv1", "conv_igemm/b2_proj"},
-                                                  {"conv_igemm/b3_conv0", "conv_igemm/b3_conv1", "conv_igemm/b3_proj"}};
     auto conv = [&](int which, const float* in, const float* wf, float* out, double* st, GnRef g, int hi, int wi,
                     int ci, int ksz, int strd) -> int {
-      return launch_conv(kTags[i][which], in, wf, out, st, g, N, hi, wi, ci, Ho, Wo, f, ksz, strd, stream);
+      return launch_conv(kConvTags[i][which], in, wf, out, st, g, N, hi, wi, ci, Ho, Wo, f, ksz, strd, stream);
     };
     if ((rc = conv(0, x, bw.conv0, ws.blk[i].raw0, stats_of(l0), none, Hi, Wi, cin, 3, s))) return rc;
     if (has_proj)

@@ -61,6 +61,19 @@ struct GnRef {
   double inv_count;     // 1 / (P * C/4)
   int gsize;            // channels per group
 };
+// GroupNorm of a conv with Cc output channels over P pixels per image, statistics at `stats`
+static inline GnRef gn_ref(const double* stats, const float* gamma, const float* beta, int P, int Cc) {
+  GnRef g{};
+  g.stats = stats; g.gamma = gamma; g.beta = beta;
+  g.inv_count = 1.0 / ((double)P * (Cc / kGnGroups));
+  g.gsize = Cc / kGnGroups;
+  return g;
+}
+// profiler tags of the residual stages' convs: [stage][conv0, conv1, proj]
+inline constexpr const char* kConvTags[kTrunkStages][3] = {{"conv_igemm/b0_conv0", "conv_igemm/b0_conv1", "conv_igemm/b0_proj"},
+                                                          {"conv_igemm/b1_conv0", "conv_igemm/b1_conv1", "conv_igemm/b1_proj"},
+                                                          {"conv_igemm/b2_conv0", "conv_igemm/b2_conv1", "conv_igemm/b2_proj"},
+                                                          {"conv_igemm/b3_conv0", "conv_igemm/b3_conv1", "conv_igemm/b3_proj"}};
 
 __device__ __forceinline__ void gn_coef4(const GnRef& g, int n, int c, float4& sc, float4& sh) {
   const double* st = g.stats + ((size_t)n * kGnGroups + c / g.gsize) * 2;

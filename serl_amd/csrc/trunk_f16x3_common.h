@@ -27,7 +27,7 @@ constexpr float kLoScale = 2048.0f, kLoInv = 1.0f / 2048.0f;  // 2^11
 // workgroups already hold -- they finish without waiting for anybody -- or (b) for not-yet-taken tiles of the ONE image
 // per counter that straddles its next ticket; at most G - 1 workgroups per counter can wait in state (b), so as long as
 // more than 8 (G - 1) workgroups are resident, one of them is running or about to start and takes the missing tickets
-// (a workgroup whose own XCD's range is used up takes from the next XCD's counter).  The launcher checks that bound
+// (a workgroup whose own XCD's range is used up takes from the next XCD's counter).  The pass plan checks that bound
 // against the CUs the stream may use (resident_workgroups) and falls back to the separate elementwise pass otherwise;
 // the spin itself is bounded (trap) so a protocol error aborts the kernel instead of hanging the GPU.
 // Wave priority of the trunk's conv kernels (s_setprio 3).  In the pipelined step the frozen trunk's stream IS the critical path and the
@@ -63,13 +63,6 @@ struct ConvArgsB {
   const float* winv;    // [Cout] 1 / (per-output-channel weight scale)
   const uint16_t* wdma;  // LDS-DMA kernel: the planes in its piece order (pack_dma_order_f16x3) or nullptr
   int K;
-  // K-split of the small-M register-staged kernel (a rank's share of a data-parallel batch): `ksplit` workgroups per 64x64
-  // tile, each over a contiguous range of K chunks; partial tiles go to `kslab` [tile][split][4 waves][4 quads][64 lanes][4]
-  // (the accumulator registers as they are: 16-byte write-through stores) and the workgroup that arrives last at `kctr[tile]`
-  // adds them in split order and runs the ordinary epilogue (raw store + statistics)
-  int ksplit;
-  float* kslab;
-  int* kctr;
   // row-slab kernel, fused epilogue: the SECOND workgroup of every CU (block ids 256..511 of the first round) starts
   // `stagger` x s_sleep(127) late (before it takes its tile ticket), see the kernel
   int stagger;

@@ -25,20 +25,9 @@ struct ConvInitArgsB {
   int chunk;            // tiles per scheduling chunk (divides tiles_y * tiles_x)
   int* ticket;          // chunk ticket (zeroed per pass)
   int wprio;            // wave priority (s_setprio), see ConvArgsB
-  int ablate;           // TIMING EXPERIMENTS ONLY, compiled in with -DSERL_ABLATE (never in the shipped library; SERL_CINIT_ABLATE, results
-                        // are wrong): 1 no patch fill, 2 no MFMAs, 4 no pooling epilogue, 8 no pixel fetch
 };
 
 constexpr int kCbPatch = 37;     // input rows/cols per 16x16 output tile
-// phase ablation of conv_init for timing experiments: a compile-time `false` unless the library is built with -DSERL_ABLATE
-__device__ __forceinline__ bool c8_ablate(const ConvInitArgsB& a, int bit) {
-#ifdef SERL_ABLATE
-  return (a.ablate & bit) != 0;
-#else
-  (void)a; (void)bit;
-  return false;
-#endif
-}
 
 // POOL: relu(GN(.)) is monotone in the raw conv output with the sign of the channel's GroupNorm scale gamma (a frozen
 // parameter), so max_pool(relu(GN(x))) = relu(GN(extreme(x))) with extreme = max where gamma >= 0 and min where
@@ -166,7 +155,7 @@ __global__ __launch_bounds__(256, 2) void conv_init_u8_kernel(ConvInitArgsB a) {
 #pragma unroll
     for (int q = 0; q < 2; ++q) {
       const int t = tid + 256 * q;
-      if (t < kTasks && !c8_ablate(a, 1)) {
+      if (t < kTasks) {
         const int r = t / kGroups, g = t - r * kGroups;
         // bytes 0..11 = pixels 0..3 x (c0,c1,c2); patch column of pixel j = 4g - 1 + j (column -1 is not stored)
         const uint32_t d0 = pre[q][0], d1 = pre[q][1], d2 = pre[q][2];
@@ -190,7 +179,7 @@ __global__ __launch_bounds__(256, 2) void conv_init_u8_kernel(ConvInitArgsB a) {
     if (first_of_chunk) next_chunk = __builtin_amdgcn_readfirstlane(s_next_chunk);   // written before this tile's first barrier; scalar, so that
                                                                                       // everything derived from the tile index stays uniform
     // next tile's bytes (the first tile of the next chunk after the last one of this chunk), in flight under the MFMAs
-    if (!c8_ablate(a, 8)) SERL_C8_FETCH(min(tile + 1 < t_end ? tile + 1 : next_chunk * a.chunk, a.total_tiles - 1));
+    SERL_C8_FETCH(min(tile + 1 < t_end ? tile + 1 : next_chunk * a.chunk, a.total_tiles - 1));
     // POOL == 2: the neighbours' first column / first row (raw values written by this workgroup at earlier tiles), fetched HERE so
     // that their L2 round trip lies under the MFMAs.  Branch-free (a tile without that neighbour reads elsewhere and ignores the
     // values; `wave == 3` is a scalar branch): loads inside an exec-masked region get an `s_waitcnt vmcnt(0)` right behind them.
@@ -236,7 +225,6 @@ __global__ __launch_bounds__(256, 2) void conv_init_u8_kernel(ConvInitArgsB a) {
       for (int tn = 0; tn < 2; ++tn)
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[tm][tn][r] = 0.f;
-    if (!c8_ablate(a, 2))
 #pragma unroll
     for (int ks = 0; ks < kC8K / 16; ++ks) {
       const int aoff = (ks >> 1) * kC8Pitch + (ks & 1) * 32;   // kernel row ky = ks/2, k-blocks 2(ks&1) + lh
@@ -303,13 +291,6 @@ __global__ __launch_bounds__(256, 2) void conv_init_u8_kernel(ConvInitArgsB a) {
             q[tn] += v * v;
           }
         }
-    } else if (c8_ablate(a, 4)) {
-#pragma unroll
-      for (int tm = 0; tm < 2; ++tm)
-#pragma unroll
-        for (int r = 0; r < 16; ++r)
-#pragma unroll
-          for (int tn = 0; tn < 2; ++tn) { const float v = acc[tm][tn][r]; s[tn] += v; q[tn] += v * v; }
     } else {  // fused 3x3/2 max-pool (every tile is full)
 #pragma unroll
       for (int tm = 0; tm < 2; ++tm)
@@ -460,9 +441,6 @@ int launch_conv_init_f16x3(const uint8_t* img, PackedConvWeights w, float* out, 
   const int tpi = a.tiles_y * a.tiles_x;
   a.chunk = (pool_gamma && complete_pool) ? tpi : (tpi % 4 == 0 ? 4 : (tpi % 2 == 0 ? 2 : 1));
   a.ticket = ticket;
-#ifdef SERL_ABLATE
-  { const char* e = getenv("SERL_CINIT_ABLATE"); a.ablate = e ? atoi(e) : 0; }
-#endif
   // 2 persistent workgroups per CU (one per CU was measured 278 -> 377 us: issue-bound at two waves per SIMD)
   const int grid = std::min(a.total_tiles / a.chunk, 512);
   ProfScope prof("conv_init", stream);

@@ -1,5 +1,5 @@
 // Part of the split-fp16 trunk (trunk_f16x3.hip includes these in order; round 6 split the 2,600-line file by kernel family):
-// conv_igemm_f16x3_kernel: the register-staged implicit-GEMM conv (small M, odd shapes, K-split of a rank's share).
+// conv_igemm_f16x3_kernel: the register-staged implicit-GEMM conv (small M: a rank's share of a data-parallel batch, odd shapes).
 #pragma once
 #include "trunk_f16x3_common.h"
 
@@ -23,9 +23,7 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_f16x3_kernel(ConvArgsB ab) 
   extern __shared__ __attribute__((aligned(16))) uint8_t smemb[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave / WN, wn = wave % WN;
-  const int S = ab.ksplit > 1 ? ab.ksplit : 1;
-  const int gid = xcd_remap(blockIdx.x, gridDim.x);   // (a tile's splits are neighbours: same XCD, shared operands in L2)
-  const int id = gid / S, split = gid - id * S;
+  const int id = xcd_remap(blockIdx.x, gridDim.x);
   const int bn = id % a.tiles_n, bm = id / a.tiles_n;
   const int m0 = bm * BM, n0 = bn * BN;
   // per-thread im2col rows: element offset of the always-valid centre tap (pixel (oy*s, ox*s)) and a
@@ -49,16 +47,14 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_f16x3_kernel(ConvArgsB ab) 
       }
     }
   }
-  const int nchunks_all = a.KH * a.KW * (a.Cin >> 5);
-  const int cper = nchunks_all / S;                     // (the host picks S | nchunks_all)
-  const int cb = split * cper;                          // first chunk of this workgroup
-  const int nchunks = cb + cper;                        // one past its last chunk
+  const int nchunks = a.KH * a.KW * (a.Cin >> 5);
   // (native vector types: HIP's uint4 struct copies lower to memcpy and keep the arrays out of registers)
   u32x4 ra[AI], rb[BI], ra2[DEEP >= 2 ? AI : 1], rb2[DEEP >= 2 ? BI : 1], ra3[DEEP >= 3 ? AI : 1], rb3[DEEP >= 3 ? BI : 1];
   unsigned okmask = 0, okmask2 = 0, okmask3 = 0;
-  // chunk counters (chunks are visited strictly in order), started at chunk cb
-  const int cpt = a.Cin >> 5;
-  int l_tap = cb / cpt, l_ci0 = (cb - l_tap * cpt) << 5, l_ky = l_tap / a.KW, l_kx = l_tap - l_ky * a.KW;
+  // chunk counters (chunks are visited strictly in order).  Opaque to the compiler: with the start known to be chunk 0 hipcc
+  // schedules the single-buffered main loop (DEEP = 0) with four more VGPRs
+  int l_tap = 0, l_ci0 = 0, l_ky = 0, l_kx = 0;
+  asm volatile("" : "+s"(l_tap), "+s"(l_ci0), "+s"(l_ky), "+s"(l_kx));
 
 #define SERL_LOAD_CHUNK_(CIDX, RA, RB, OK)                                                                                \
   {                                                                                                            \
@@ -135,10 +131,10 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_f16x3_kernel(ConvArgsB ab) 
   }
   const int li = lane & 31, lh = lane >> 5;
   if (!DEEP) {
-    SERL_LOAD_CHUNK(cb);
-    SERL_STORE_CHUNK(cb & 1);
+    SERL_LOAD_CHUNK(0);
+    SERL_STORE_CHUNK(0);
     __syncthreads();
-    for (int c = cb; c < nchunks; ++c) {
+    for (int c = 0; c < nchunks; ++c) {
       const int buf = c & 1;
       SERL_LOAD_CHUNK(c + 1);  // (the last iteration re-reads its own chunk: the counters stop advancing)
       SERL_COMPUTE_CHUNK(buf);
@@ -147,11 +143,11 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_f16x3_kernel(ConvArgsB ab) 
     }
   } else {
     // register set (c mod DEEP) holds chunk c+1 while chunk c is computed; its loads were issued DEEP iterations ago
-    SERL_LOAD_CHUNK(cb);
-    SERL_STORE_CHUNK(cb & 1);
-    SERL_LOAD_CHUNK(cb + 1);
-    SERL_LOAD_CHUNK_(cb + 2, ra2, rb2, okmask2);
-    if (DEEP >= 3) SERL_LOAD_CHUNK_(cb + 3, ra3, rb3, okmask3);
+    SERL_LOAD_CHUNK(0);
+    SERL_STORE_CHUNK(0);
+    SERL_LOAD_CHUNK(1);
+    SERL_LOAD_CHUNK_(2, ra2, rb2, okmask2);
+    if (DEEP >= 3) SERL_LOAD_CHUNK_(3, ra3, rb3, okmask3);
     __syncthreads();
 #define SERL_DEEP_STEP(C, RA, RB, OK)                    \
   {                                                      \
@@ -160,7 +156,7 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_f16x3_kernel(ConvArgsB ab) 
     SERL_LOAD_CHUNK_((C) + 1 + DEEP, RA, RB, OK);        \
     __syncthreads();                                     \
   }
-    for (int c = cb; c < nchunks; c += DEEP) {
+    for (int c = 0; c < nchunks; c += DEEP) {
       SERL_DEEP_STEP(c, ra, rb, okmask);
       if (c + 1 < nchunks) SERL_DEEP_STEP(c + 1, ra2, rb2, okmask2);
       if (DEEP >= 3 && c + 2 < nchunks) SERL_DEEP_STEP(c + 2, ra3, rb3, okmask3);
@@ -183,55 +179,6 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_f16x3_kernel(ConvArgsB ab) 
     for (int tn = 0; tn < TN; ++tn)
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[tm][tn][r] = (acc[tm][tn][r] + accx[tm][tn][r] * kLoInv) * winv[tn];
-  if (S > 1) {
-    // K-split: publish this partial tile -- the accumulator registers as they are, four per 16-byte WRITE-THROUGH store (1 KB
-    // per wave instruction, contiguous) -- drain, take a ticket; the last arriver re-reads all partials IN SPLIT ORDER with
-    // L1-bypassing loads into the same registers and carries on below: the in-launch split-K recipe of
-    // cdna_hip_programming.md (no fence, no spinning: nobody waits).  (4-byte partial stores, round 4's first build, are one
-    // fabric write each and cost more than the K range saved: b3_conv1 85 -> 99 us.)
-    constexpr int kSc1 = 16;
-    constexpr int WAVE_FLOATS = TM * TN * 16 * 64;
-    const size_t tile_floats = (size_t)4 * WAVE_FLOATS;
-    // (ONE workgroup-uniform buffer descriptor for the tile's S partials; split, wave and lane go into the byte offset -- a
-    //  descriptor whose base depends on the wave index lands in VGPRs and hipcc wraps every access in a waterfall loop)
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(ab.kslab + (size_t)id * S * tile_floats, 0, 0x7fffffff, 0x00020000);
-    const int wl_off = (wave * WAVE_FLOATS + lane * 4) * 4;   // this lane's 16 bytes inside a quad block of its wave's region
-#pragma unroll
-    for (int tm = 0; tm < TM; ++tm)
-#pragma unroll
-      for (int tn = 0; tn < TN; ++tn)
-#pragma unroll
-        for (int q4 = 0; q4 < 4; ++q4) {
-          typedef float f32x4s_t __attribute__((ext_vector_type(4)));
-          const f32x4s_t vf = {acc[tm][tn][4 * q4], acc[tm][tn][4 * q4 + 1], acc[tm][tn][4 * q4 + 2], acc[tm][tn][4 * q4 + 3]};
-          __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, vf), rs, split * (int)(tile_floats * 4) + wl_off + ((tm * TN + tn) * 4 + q4) * 1024, 0, kSc1);
-        }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    int* flag = reinterpret_cast<int*>(smemb);   // (the operand LDS is idle: every wave passed the barrier above)
-    if (tid == 0) {
-      const int old = __hip_atomic_fetch_add(ab.kctr + id, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-      const int last = old == S - 1;
-      if (last) __hip_atomic_store(ab.kctr + id, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-      *flag = last;
-    }
-    __syncthreads();
-    if (!*flag) return;
-#pragma unroll
-    for (int tm = 0; tm < TM; ++tm)
-#pragma unroll
-      for (int tn = 0; tn < TN; ++tn)
-#pragma unroll
-        for (int q4 = 0; q4 < 4; ++q4) {
-          typedef float f32x4_t __attribute__((ext_vector_type(4)));
-          f32x4_t sum = {0.f, 0.f, 0.f, 0.f};
-          for (int sp = 0; sp < S; ++sp)
-            sum += __builtin_bit_cast(f32x4_t, __builtin_amdgcn_raw_buffer_load_b128(
-                       rs, sp * (int)(tile_floats * 4) + wl_off + ((tm * TN + tn) * 4 + q4) * 1024, 0, kSc1));
-#pragma unroll
-          for (int j = 0; j < 4; ++j) acc[tm][tn][4 * q4 + j] = sum[j];
-        }
-  }
 #pragma unroll
   for (int tm = 0; tm < TM; ++tm)
 #pragma unroll

@@ -33,24 +33,6 @@ def test_trunk_forward(gpu, H, W, n, mode):
     assert err < 5e-6, err
 
 
-@pytest.mark.parametrize("ksplit", [2, 4])
-def test_trunk_forward_with_the_opt_in_conv_k_split(gpu, ksplit, monkeypatch):
-    """SERL_CONV_KSPLIT: 2 / 4 workgroups per 64x64 tile of the small-M conv kernel, partial tiles summed by the last arriver
-    (trunk_f16x3.hip; a rank's share of a data-parallel batch).  Same 5e-6 bound, and the plan must show the split."""
-    monkeypatch.setenv("SERL_CONV_KSPLIT", str(ksplit))
-    for H, n in ((64, 6), (128, 70)):
-        cfg = O.Config(image_keys=("a",), H=H, W=H, S=4, A=2)
-        st, core = AH.make_pair(cfg, B=max(n, 4), trunk_mode="f16x3")
-        img = np.random.default_rng(1).integers(0, 256, (n, H, H, 3), dtype=np.uint8)
-        ref = O.trunk_forward(st.trunk, torch.tensor(img), torch.float64).numpy()
-        got = core.trunk_forward(torch.tensor(img, device="cuda")).cpu().numpy()
-        plan = core.trunk_plan()
-        assert any(len(v) == 5 and v[4] >= 2 for v in plan.values() if isinstance(v, tuple)), plan
-        err = AH.rel_err(got, ref)
-        print(f"trunk f16x3 {H}x{H} n={n} K-split {ksplit}: rel err vs fp64 = {err:.2e}")
-        assert err < 5e-6, err
-
-
 @pytest.mark.parametrize("n", [1024, 128])
 def test_fused_projection(gpu, n, monkeypatch):
     """Default since round 5 (SERL_PROJ_FUSE=0 = separate launch): a block's 1x1 stride-2 projection computed by conv0's workgroups (conv_dma_f16x3_kernel<.., PROJ = true>;
