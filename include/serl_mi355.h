@@ -352,6 +352,48 @@ int serl_classifier_get(serl_classifier* c, const char* leaf, float* host_out, i
 int serl_classifier_logits(serl_classifier* c, const uint8_t* dev_frames, int n, float* dev_logits, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Behaviour cloning (agents/continuous/bc.py, built by utils/launcher.py:26-47 with encoder_type="resnet-pretrained").
+ * One handle = BCAgent.state (params, one optax.adam(lr) state, step) + all activations; a separate handle so that
+ * serl_agent_cfg and the DrQ path stay as they are.  Policy(EncodingWrapper(use_proprio, enable_stacking) over the frozen
+ * trunk, MLP([256, 256], tanh, no LayerNorm, activate_final), heads mean / log_std, MultivariateNormalDiag (no tanh),
+ * std = clip(exp(log_std), std_min, std_max) * sqrt(temperature)).
+ * Leaves (flat fp32, HWIO kernels / [in][out] dense kernels): the trunk leaves of the agent ("trunk/..."),
+ * "enc/<k>/{sle, dense/kernel, dense/bias, ln/scale, ln/bias}" (frozen: behind stop_gradient, encoding.py:48-49 and
+ * actor_critic_nets.py:185), then the trainable "enc/proprio/{dense/kernel, dense/bias, ln/scale, ln/bias}",
+ * "actor/{w1, b1, w2, b2}", "actor/mean/{kernel,bias}", "actor/logstd/{kernel,bias}".  Sections: "params", "opt/mu",
+ * "opt/nu"; the moments of a frozen leaf read as zeros and may only be set to zeros.
+ * --------------------------------------------------------------------------------------------- */
+typedef struct serl_bc serl_bc;
+typedef struct {
+  int device, n_cam, H, W, state_dim, act_dim, max_batch;
+  float lr;                 /* optax.adam learning rate (bc.py:134) */
+  float dropout;            /* Dropout rate behind SpatialLearnedEmbeddings (resnet_v1.py:351) */
+  float std_min, std_max;   /* launcher.py:41-42 */
+} serl_bc_cfg;
+int serl_bc_create(const serl_bc_cfg* cfg, serl_bc** out);   /* BCAgent.create (bc.py:118-204) */
+int serl_bc_destroy(serl_bc* c);
+int serl_bc_num_leaves(serl_bc* c);
+int serl_bc_leaf_info(serl_bc* c, int i, char* name_out, int name_cap, int64_t* count, int* trainable);
+int serl_bc_set(serl_bc* c, const char* section, const char* leaf, const float* host, int64_t count);
+int serl_bc_get(serl_bc* c, const char* section, const char* leaf, float* host_out, int64_t count);
+int serl_bc_set_step(serl_bc* c, int64_t step);
+int64_t serl_bc_get_step(serl_bc* c);
+/* BCAgent.update (bc.py:37-77): frames[0] (the observations, [n_cam][batch][H][W][3]), state[0] and action of `batch`.
+ * The Dropout keep-masks of the forward pass (train=True) are dev_masks u8[n_cam][batch][4096], or, when NULL, drawn inside
+ * the SLE kernel as jax.random.bernoulli(key_c, 1 - dropout, (batch, 4096)) under host_mask_keys uint32[n_cam][2]. */
+int serl_bc_update(serl_bc* c, const serl_batch* batch, const uint8_t* dev_masks, const uint32_t* host_mask_keys, void* stream);
+/* info of the last update (bc.py:63-67): out[0] = actor_loss, out[1] = mse.  `out` is device or host memory; the copy is
+ * ordered on `stream` (synchronise it before reading host memory) */
+int serl_bc_read_info(serl_bc* c, float out[2], void* stream);
+/* BCAgent.sample_actions (bc.py:79-97), train=False: argmax -> the mean (no tanh); otherwise mean + std * eps with
+ * eps = dev_eps f32[n][A], or, when NULL, jax.random.normal(host_key, (n, A)).  dev_frames u8[n_cam][n][H][W][3],
+ * dev_state f32[n][S], dev_actions_out f32[n][A]. */
+int serl_bc_sample_actions(serl_bc* c, const uint8_t* dev_frames, const float* dev_state, int n, const float* dev_eps,
+                           const uint32_t* host_key, float temperature, int argmax, float* dev_actions_out, void* stream);
+/* BCAgent.get_debug_metrics (bc.py:99-116), train=False: per-sample mse[n], log_probs[n], pi_actions[n][A] (device) */
+int serl_bc_debug_metrics(serl_bc* c, const serl_batch* batch, float* dev_mse, float* dev_logp, float* dev_pi, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * JAX's PRNG (threefry2x32, non-partitionable; jax/_src/prng.py, jax/_src/random.py of jax 0.4.x) -- csrc/jaxrng.hip.
  * The reference learner draws its crop offsets (vision/data_augmentations.py:7-36), REDQ indices (agents/continuous/sac.py:150-157),
  * policy noise (sac.py:118-132,197-201,224-227) and Dropout masks from jax.random and advances `state.rng` as

@@ -27,6 +27,14 @@ TX_INDEX = {"actor": 0, "critic": 1, "temperature": 2}   # SERL_TX_*
 NET_BITS = {"critic": 1, "actor": 2, "temperature": 4}   # SERL_NET_*
 
 
+class SerlBcCfg(C.Structure):
+    _fields_ = [
+        ("device", C.c_int), ("n_cam", C.c_int), ("H", C.c_int), ("W", C.c_int), ("state_dim", C.c_int),
+        ("act_dim", C.c_int), ("max_batch", C.c_int),
+        ("lr", C.c_float), ("dropout", C.c_float), ("std_min", C.c_float), ("std_max", C.c_float),
+    ]
+
+
 class SerlNoise(C.Structure):
     _fields_ = [
         ("eps_next", C.c_void_p), ("mask_next", C.c_void_p), ("redq_idx", C.c_void_p),
@@ -80,6 +88,18 @@ def declare(lib):
         "serl_agent_debug_get": [vp, C.c_char_p, vp, i64],
         "serl_agent_trunk_plan": [vp, C.c_char_p, i32],
         "serl_agent_debug_set": [vp, C.c_char_p, vp, i64],
+        # behaviour cloning (csrc/bc.hip, serl_amd/agents/bc.py)
+        "serl_bc_create": [P(SerlBcCfg), P(vp)],
+        "serl_bc_destroy": [vp],
+        "serl_bc_num_leaves": [vp],
+        "serl_bc_leaf_info": [vp, i32, C.c_char_p, i32, P(i64), P(i32)],
+        "serl_bc_set": [vp, C.c_char_p, C.c_char_p, vp, i64],
+        "serl_bc_get": [vp, C.c_char_p, C.c_char_p, vp, i64],
+        "serl_bc_set_step": [vp, i64],
+        "serl_bc_update": [vp, P(SerlBatch), vp, vp, vp],
+        "serl_bc_read_info": [vp, vp, vp],
+        "serl_bc_sample_actions": [vp, vp, vp, i32, vp, vp, f32, i32, vp, vp],
+        "serl_bc_debug_metrics": [vp, P(SerlBatch), vp, vp, vp, vp],
     }
     for name, args in sigs.items():
         fn = getattr(lib, name)
@@ -89,3 +109,5 @@ def declare(lib):
     lib.serl_debug_chain_launches.restype = i64
     lib.serl_agent_get_step.argtypes = [vp]
     lib.serl_agent_get_step.restype = i64
+    lib.serl_bc_get_step.argtypes = [vp]
+    lib.serl_bc_get_step.restype = i64

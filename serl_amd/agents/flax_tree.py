@@ -111,6 +111,54 @@ def _state_paths():
     return m
 
 
+def bc_paths(image_keys):
+    """flat BC leaf (csrc/bc.hip) -> flax path in BCAgent.state.params (bc.py:118-204): Policy is `modules_actor`, its
+    EncodingWrapper `encoder` (per camera `encoder_<key>`, the proprio Dense_0 / LayerNorm_0), its MLP `network`
+    (Dense_0, Dense_1 -- no LayerNorm), the heads Dense_0 (mean) and Dense_1 (log_std); the shared frozen trunk sits under
+    the first camera in sorted-key order, as in DrQ."""
+    enc = ("modules_actor", "encoder")
+    m = {}
+    for leaf, sub in _trunk_paths().items():
+        m[leaf] = enc + (f"encoder_{trunk_owner(image_keys)}", "pretrained_encoder") + sub
+    for i, k in enumerate(image_keys):
+        e = enc + (f"encoder_{k}",)
+        m[f"enc/{i}/sle"] = e + ("SpatialLearnedEmbeddings_0", "kernel")
+        m[f"enc/{i}/dense/kernel"] = e + ("Dense_0", "kernel")
+        m[f"enc/{i}/dense/bias"] = e + ("Dense_0", "bias")
+        m[f"enc/{i}/ln/scale"] = e + ("LayerNorm_0", "scale")
+        m[f"enc/{i}/ln/bias"] = e + ("LayerNorm_0", "bias")
+    m["enc/proprio/dense/kernel"] = enc + ("Dense_0", "kernel")
+    m["enc/proprio/dense/bias"] = enc + ("Dense_0", "bias")
+    m["enc/proprio/ln/scale"] = enc + ("LayerNorm_0", "scale")
+    m["enc/proprio/ln/bias"] = enc + ("LayerNorm_0", "bias")
+    for j in (0, 1):
+        m[f"actor/w{j + 1}"] = ("modules_actor", "network", f"Dense_{j}", "kernel")
+        m[f"actor/b{j + 1}"] = ("modules_actor", "network", f"Dense_{j}", "bias")
+    m["actor/mean/kernel"] = ("modules_actor", "Dense_0", "kernel")
+    m["actor/mean/bias"] = ("modules_actor", "Dense_0", "bias")
+    m["actor/logstd/kernel"] = ("modules_actor", "Dense_1", "kernel")
+    m["actor/logstd/bias"] = ("modules_actor", "Dense_1", "bias")
+    return m
+
+
+def bc_shapes(image_keys, H, W, S, A, hidden=256, bottleneck=256, proprio_dim=64):
+    """flat BC leaf -> flax shape"""
+    from ..utils.init import feat_hw
+    fh, fw = feat_hw(H, W)
+    sh = dict(trunk_shapes())
+    for i in range(len(image_keys)):
+        sh[f"enc/{i}/sle"] = (fh, fw, 512, 8)
+        sh[f"enc/{i}/dense/kernel"] = (512 * 8, bottleneck)
+        sh[f"enc/{i}/dense/bias"] = sh[f"enc/{i}/ln/scale"] = sh[f"enc/{i}/ln/bias"] = (bottleneck,)
+    sh["enc/proprio/dense/kernel"] = (S, proprio_dim)
+    sh["enc/proprio/dense/bias"] = sh["enc/proprio/ln/scale"] = sh["enc/proprio/ln/bias"] = (proprio_dim,)
+    sh["actor/w1"], sh["actor/b1"] = (bottleneck * len(image_keys) + proprio_dim, hidden), (hidden,)
+    sh["actor/w2"], sh["actor/b2"] = (hidden, hidden), (hidden,)
+    sh["actor/mean/kernel"], sh["actor/mean/bias"] = (hidden, A), (A,)
+    sh["actor/logstd/kernel"], sh["actor/logstd/bias"] = (hidden, A), (A,)
+    return sh
+
+
 def trunk_owner(image_keys):
     """camera whose subtree holds the shared frozen trunk (first key in sorted order)."""
     return sorted(image_keys)[0]

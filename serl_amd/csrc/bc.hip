@@ -1,0 +1,607 @@
+// Behaviour cloning (serl_launcher/agents/continuous/bc.py, built by utils/launcher.py:26-47 with
+// encoder_type="resnet-pretrained"): parameter arena, update, inference and the serl_bc half of the C ABI.
+//   Policy(EncodingWrapper(use_proprio=True, enable_stacking=True), MLP([256, 256], tanh, no LayerNorm, activate_final),
+//          tanh_squash_distribution=False, std = clip(exp(log_std), 1e-5, 5) * sqrt(temperature))
+//   (networks/actor_critic_nets.py:167-227, networks/mlp.py, common/encoding.py:26-72)
+// Policy calls its encoder with stop_gradient=True, and EncodingWrapper stops the gradient of every image branch
+// (encoding.py:48-49): only the proprio Dense/LayerNorm, the two MLP layers and the two heads train.  The frozen trunk, the
+// SpatialLearnedEmbeddings and the bottleneck Dense/LayerNorm of every camera run forward only; their Adam moments are zero
+// forever (Adam with g = m = v = 0 leaves a parameter unchanged) and are produced on read instead of stored.
+// Reuses the trunk (trunk_f16x3.hip) and the encoder-head / GEMM / Adam kernels (heads.hip); new here: the bias + tanh slab
+// reduction of a plain Dense -> tanh layer, its backward, and the diagonal-Gaussian NLL head.
+#include <cmath>
+#include <string>
+#include <vector>
+
+#include "heads.h"
+#include "internal.h"
+#include "jaxrng.h"
+
+using namespace serl;
+
+namespace {
+struct BLeaf { std::string name; long off, count; bool train; };
+constexpr int kHidden = 256, kBottleneck = 256, kSleFeatures = 8, kProprio = 64, kMaxAct = 64;
+inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
+}  // namespace
+
+struct serl_bc {
+  serl_bc_cfg cfg{};
+  int HW = 0, D = 0, Eimg = 0, E = 0;
+  std::vector<BLeaf> leaves;   // trunk, cameras (frozen), then the trainable slice [t0, t0 + nt)
+  long n_params = 0, t0 = 0, nt = 0, cam_stride = 0;
+  long o_sle = 0, o_dW = 0, o_db = 0, o_lng = 0, o_lnb = 0;   // camera 0
+  long o_pW = 0, o_pb = 0, o_pg = 0, o_pbe = 0, o_w1 = 0, o_b1 = 0, o_w2 = 0, o_b2 = 0, o_Wm = 0, o_bm = 0, o_Ws = 0, o_bs = 0;
+  void* arena = nullptr;
+  float* params = nullptr;   // [n_params + 1]: the element behind the trainable slice is adam_ema's (unused) temperature slot
+  float *m = nullptr, *v = nullptr, *G = nullptr;   // [nt + 1], [nt + 1], [nt]: trainable slice only
+  TrunkWeights tw{};
+  TrunkWorkspace tws{};
+  TrunkPacked tpk{};
+  float *feats = nullptr, *f = nullptr, *slabs = nullptr, *enc = nullptr, *pxhat = nullptr, *prstd = nullptr;
+  float *h1 = nullptr, *h2 = nullptr, *mu = nullptr, *dhead = nullptr, *dpre1 = nullptr, *dpre2 = nullptr;
+  float *dprop = nullptr, *dpp = nullptr, *dgp = nullptr, *info = nullptr;
+  long slabs_cap = 0;
+  int64_t step = 0;
+};
+
+namespace {
+
+const BLeaf* find(const serl_bc* c, const char* name) {
+  for (const BLeaf& l : c->leaves)
+    if (l.name == name) return &l;
+  return nullptr;
+}
+
+void layout(serl_bc* c) {
+  const serl_bc_cfg& g = c->cfg;
+  const TrunkDims d = trunk_dims(g.H, g.W);
+  c->HW = d.h[5] * d.w[5];
+  c->D = 512 * kSleFeatures;
+  c->Eimg = kBottleneck * g.n_cam;
+  c->E = c->Eimg + kProprio;
+  long off = 0;
+  auto leaf = [&](const std::string& n, long cnt, bool train) {
+    c->leaves.push_back({n, off, cnt, train});
+    const long at = off;
+    off += cnt;
+    return at;
+  };
+  leaf("trunk/conv_init", 7 * 7 * 3 * 64, false);
+  leaf("trunk/norm_init/scale", 64, false);
+  leaf("trunk/norm_init/bias", 64, false);
+  int cin = 64;
+  for (int i = 0; i < kTrunkStages; ++i) {
+    const int f = kStageFilters[i];
+    const std::string p = "trunk/block" + std::to_string(i) + "/";
+    leaf(p + "conv0", 9L * cin * f, false); leaf(p + "gn0/scale", f, false); leaf(p + "gn0/bias", f, false);
+    leaf(p + "conv1", 9L * f * f, false); leaf(p + "gn1/scale", f, false); leaf(p + "gn1/bias", f, false);
+    if (kStageStride[i] != 1 || cin != f) {
+      leaf(p + "proj", (long)cin * f, false); leaf(p + "gnp/scale", f, false); leaf(p + "gnp/bias", f, false);
+    }
+    cin = f;
+  }
+  long cam0 = 0;
+  for (int k = 0; k < g.n_cam; ++k) {
+    const std::string p = "enc/" + std::to_string(k) + "/";
+    const long s = leaf(p + "sle", (long)c->HW * 512 * kSleFeatures, false);
+    const long dW = leaf(p + "dense/kernel", (long)c->D * kBottleneck, false);
+    const long db = leaf(p + "dense/bias", kBottleneck, false);
+    const long lg = leaf(p + "ln/scale", kBottleneck, false);
+    const long lb = leaf(p + "ln/bias", kBottleneck, false);
+    if (k == 0) { cam0 = s; c->o_sle = s; c->o_dW = dW; c->o_db = db; c->o_lng = lg; c->o_lnb = lb; }
+    if (k == 1) c->cam_stride = s - cam0;
+  }
+  if (g.n_cam == 1) c->cam_stride = off - cam0;
+  off = (off + 3) & ~3L;   // (16-byte aligned trainable slice)
+  c->t0 = off;
+  const long A = g.act_dim;
+  c->o_pW = leaf("enc/proprio/dense/kernel", (long)g.state_dim * kProprio, true);
+  c->o_pb = leaf("enc/proprio/dense/bias", kProprio, true);
+  c->o_pg = leaf("enc/proprio/ln/scale", kProprio, true);
+  c->o_pbe = leaf("enc/proprio/ln/bias", kProprio, true);
+  c->o_w1 = leaf("actor/w1", (long)c->E * kHidden, true);
+  c->o_b1 = leaf("actor/b1", kHidden, true);
+  c->o_w2 = leaf("actor/w2", (long)kHidden * kHidden, true);
+  c->o_b2 = leaf("actor/b2", kHidden, true);
+  c->o_Wm = leaf("actor/mean/kernel", kHidden * A, true);
+  c->o_bm = leaf("actor/mean/bias", A, true);
+  c->o_Ws = leaf("actor/logstd/kernel", kHidden * A, true);
+  c->o_bs = leaf("actor/logstd/bias", A, true);
+  c->nt = off - c->t0;
+  c->n_params = off;
+}
+
+int split_under(int M, int N, int groups, int smax) {   // K-split so that about 512 workgroups are in flight
+  const long tiles = (long)cdiv(M, 64) * cdiv(N, 64) * groups;
+  int s = smax;
+  while (s > 1 && tiles * s > 512) s >>= 1;
+  return s;
+}
+
+size_t carve(serl_bc* c, uint8_t* base) {
+  const serl_bc_cfg& g = c->cfg;
+  size_t off = 0;
+  auto take = [&](size_t bytes) {
+    uint8_t* p = base ? base + off : nullptr;
+    off += al256(bytes);
+    return p;
+  };
+  const long n = g.max_batch, A = g.act_dim;
+  c->params = (float*)take((size_t)(c->n_params + 1) * 4);
+  c->m = (float*)take((size_t)(c->nt + 1) * 4);
+  c->v = (float*)take((size_t)(c->nt + 1) * 4);
+  c->G = (float*)take((size_t)c->nt * 4);
+  c->info = (float*)take(2 * 4);
+  uint8_t* pk = take(trunk_packed_bytes());
+  uint8_t* ws = take(trunk_workspace_bytes(g.n_cam * g.max_batch, g.H, g.W));
+  c->feats = (float*)take((size_t)g.n_cam * n * c->HW * 512 * 4);
+  c->f = (float*)take((size_t)g.n_cam * n * c->D * 4);
+  c->slabs_cap = (long)std::max(32 * g.n_cam, 8) * n * kBottleneck;
+  c->slabs = (float*)take((size_t)c->slabs_cap * 4);
+  c->enc = (float*)take((size_t)n * c->E * 4);
+  c->pxhat = (float*)take((size_t)n * kProprio * 4);
+  c->prstd = (float*)take((size_t)n * 4);
+  c->h1 = (float*)take((size_t)n * kHidden * 4);
+  c->h2 = (float*)take((size_t)n * kHidden * 4);
+  c->mu = (float*)take((size_t)n * A * 4);
+  c->dhead = (float*)take((size_t)2 * n * A * 4);
+  c->dpre1 = (float*)take((size_t)n * kHidden * 4);
+  c->dpre2 = (float*)take((size_t)n * kHidden * 4);
+  c->dprop = (float*)take((size_t)n * kProprio * 4);
+  c->dpp = (float*)take((size_t)n * kProprio * 4);
+  c->dgp = (float*)take((size_t)n * kProprio * 4);
+  if (base) {
+    trunk_packed_bind(c->tpk, pk);
+    trunk_workspace_bind(c->tws, ws, g.n_cam * g.max_batch, g.H, g.W);
+    auto p = [&](const std::string& nm) -> const float* {
+      const BLeaf* l = find(c, nm.c_str());
+      return l ? c->params + l->off : nullptr;
+    };
+    c->tw.conv_init = p("trunk/conv_init");
+    c->tw.gn_init_s = p("trunk/norm_init/scale");
+    c->tw.gn_init_b = p("trunk/norm_init/bias");
+    for (int i = 0; i < kTrunkStages; ++i) {
+      const std::string q = "trunk/block" + std::to_string(i) + "/";
+      TrunkWeights::Block& b = c->tw.blk[i];
+      b.conv0 = p(q + "conv0"); b.gn0_s = p(q + "gn0/scale"); b.gn0_b = p(q + "gn0/bias");
+      b.conv1 = p(q + "conv1"); b.gn1_s = p(q + "gn1/scale"); b.gn1_b = p(q + "gn1/bias");
+      b.proj = p(q + "proj"); b.gnp_s = p(q + "gnp/scale"); b.gnp_b = p(q + "gnp/bias");
+    }
+  }
+  return off;
+}
+
+#define RC(x)            \
+  do {                   \
+    int _rc = (x);       \
+    if (_rc) return _rc; \
+  } while (0)
+
+// ---- new kernels ------------------------------------------------------------------------------
+// Plain Dense -> tanh (mlp.py:26-34 with use_layer_norm=False): y[r][c] = tanh(bias[c] + sum_s slab[s][r][c]), the K-split
+// GEMM's slabs reduced in index order.  Takes the place of the LayerNorm launch of the DrQ MLP layer.
+__global__ __launch_bounds__(256) void bc_dense_tanh_fwd_kernel(const float* slabs, int S, long sstride, const float* bias,
+                                                                 float* y, int rows, int N) {
+  const long e = (long)blockIdx.x * 256 + threadIdx.x;
+  if (e >= (long)rows * N) return;
+  const int col = (int)(e % N);
+  float acc = 0.f;
+  for (int s = 0; s < S; ++s) acc += slabs[(long)s * sstride + e];
+  y[e] = tanhf(acc + bias[col]);
+}
+
+// Its backward: the input gradient of the layer above arrives as `S` slabs (K-split / per-head products);
+// dpre = (sum_s slab[s]) * (1 - y^2).  The bias gradient is colsum3 mode 1 of dpre (deferred to the end of the step).
+__global__ __launch_bounds__(256) void bc_dense_tanh_bwd_kernel(const float* slabs, int S, long sstride, const float* y,
+                                                                 float* dpre, int rows, int N) {
+  const long e = (long)blockIdx.x * 256 + threadIdx.x;
+  if (e >= (long)rows * N) return;
+  float acc = 0.f;
+  for (int s = 0; s < S; ++s) acc += slabs[(long)s * sstride + e];
+  const float t = y[e];
+  dpre[e] = acc * (1.f - t * t);
+}
+
+// Diagonal-Gaussian head (distrax.MultivariateNormalDiag, actor_critic_nets.py:188-221 with tanh_squash_distribution=False):
+// mean = bias_m + sum of the mean slabs, log_std = bias_s + sum of the log-std slabs, std = clip(exp(log_std), lo, hi) * sqrt(T).
+// One workgroup; rows are strided over the threads and every batch sum is a fixed-order tree (deterministic).
+struct BcHeadArgs {
+  const float* slabs; int S; long sstride;   // [2 (mean, log_std)][S][B][A]
+  const float *bias_m, *bias_s;
+  int B, A; float std_min, std_max, temp;
+  const float* action;                        // [B][A] or nullptr
+  float* mu;                                  // [B][A] mode (or nullptr)
+  float *logp, *mse;                          // per-sample [B] (or nullptr)
+  float *dmu, *dls;                           // d(-mean log_prob) / d(mean, log_std) [B][A] (or nullptr)
+  float* info;                                // [2]: -mean(log_prob), mean(mse) (or nullptr)
+  float* act; const float* eps;               // act = mu (+ std * eps when `sample`)
+  int sample, tf; uint32_t tf_key[2];         // tf: eps[b][j] = jax.random.normal(tf_key, (B, A))[b][j]
+};
+__global__ __launch_bounds__(256) void bc_gauss_head_kernel(BcHeadArgs a) {
+  __shared__ float red[2][256];
+  const int tid = threadIdx.x;
+  const float half_log_2pi = 0.918938533204672742f;   // 0.5 * log(2 pi)
+  const float sq = sqrtf(a.temp);
+  float s_lp = 0.f, s_mse = 0.f;
+  for (int b = tid; b < a.B; b += 256) {
+    float lp = 0.f, se = 0.f;
+    for (int j = 0; j < a.A; ++j) {
+      const long e = (long)b * a.A + j;
+      float pm = 0.f, ps = 0.f;
+      for (int s = 0; s < a.S; ++s) {
+        pm += a.slabs[(long)s * a.sstride + e];
+        ps += a.slabs[(long)(a.S + s) * a.sstride + e];
+      }
+      const float mean = pm + a.bias_m[j], ls = ps + a.bias_s[j];
+      const float raw = expf(ls);
+      const float sd = fminf(fmaxf(raw, a.std_min), a.std_max) * sq;
+      if (a.mu) a.mu[e] = mean;
+      if (a.act) {
+        float out = mean;
+        if (a.sample) {
+          const float z = a.tf ? normal_from_bits(random_bits_at(a.tf_key[0], a.tf_key[1], (uint64_t)a.B * a.A, (uint64_t)e)) : a.eps[e];
+          out = mean + sd * z;
+        }
+        a.act[e] = out;
+      }
+      if (a.action) {
+        const float d = a.action[e] - mean;
+        const float z = d / sd;
+        lp += -0.5f * z * z - logf(sd) - half_log_2pi;
+        se += d * d;
+        // actor_loss = -mean_b sum_j log N(a | mean, sd): no gradient where the clip is active (as policy_dist_bwd)
+        if (a.dmu) a.dmu[e] = -(z / sd) / (float)a.B;
+        if (a.dls) a.dls[e] = (raw > a.std_min && raw < a.std_max) ? -(z * z - 1.f) / (float)a.B : 0.f;
+      }
+    }
+    if (a.action) {
+      if (a.logp) a.logp[b] = lp;
+      if (a.mse) a.mse[b] = se;
+      s_lp += lp;
+      s_mse += se;
+    }
+  }
+  if (!a.info) return;
+  red[0][tid] = s_lp;
+  red[1][tid] = s_mse;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if (tid < o) { red[0][tid] += red[0][tid + o]; red[1][tid] += red[1][tid + o]; }
+    __syncthreads();
+  }
+  if (tid == 0) {
+    a.info[0] = -red[0][0] / (float)a.B;
+    a.info[1] = red[1][0] / (float)a.B;
+  }
+}
+
+int dense_tanh_fwd(const float* slabs, int S, long sstride, const float* bias, float* y, int rows, int N, hipStream_t st) {
+  hipLaunchKernelGGL(bc_dense_tanh_fwd_kernel, dim3(cdiv((long)rows * N, 256)), dim3(256), 0, st, slabs, S, sstride, bias, y, rows, N);
+  SERL_HIP(hipGetLastError());
+  return SERL_OK;
+}
+
+int dense_tanh_bwd(const float* slabs, int S, long sstride, const float* y, float* dpre, int rows, int N, hipStream_t st) {
+  hipLaunchKernelGGL(bc_dense_tanh_bwd_kernel, dim3(cdiv((long)rows * N, 256)), dim3(256), 0, st, slabs, S, sstride, y, dpre, rows, N);
+  SERL_HIP(hipGetLastError());
+  return SERL_OK;
+}
+
+// ---- forward ---------------------------------------------------------------------------------
+// Policy forward (actor_critic_nets.py:179-190) on n observations up to the head GEMM's slabs: one frozen-trunk pass over the
+// n_cam * n images, SpatialLearnedEmbeddings (+ Dropout keep-mask: injected, drawn from per-camera jax.random keys, or none at
+// train=False) with the proprio branch riding on the same launch, bottleneck Dense + LayerNorm + tanh, the two Dense -> tanh
+// layers and the two heads.  Returns the head's K-split count.
+int forward(serl_bc* c, const uint8_t* frames, const float* state, int n, const uint8_t* mask, const uint32_t* mask_keys,
+            int* head_split, hipStream_t st) {
+  const serl_bc_cfg& g = c->cfg;
+  const float* P = c->params;
+  const int A = g.act_dim;
+  RC(trunk_forward(c->tw, c->tws, frames, g.n_cam * n, c->feats, st, &c->tpk));
+  SleFwdArgs sv{};
+  sv.x = c->feats; sv.K = P + c->o_sle; sv.mask = mask; sv.f = c->f;
+  if (!mask && mask_keys) {
+    sv.gen = 2;
+    for (int k = 0; k < g.n_cam; ++k) { sv.tf_key[k][0] = mask_keys[2 * k]; sv.tf_key[k][1] = mask_keys[2 * k + 1]; }
+    sv.tf_rows = n; sv.tf_row0 = 0;
+  }
+  ProprioArgs pv{};
+  pv.state = state; pv.W = P + c->o_pW; pv.b = P + c->o_pb; pv.gamma = P + c->o_pg; pv.beta = P + c->o_pbe;
+  pv.y = c->enc + c->Eimg; pv.ld_y = c->E; pv.xhat = c->pxhat; pv.rstd = c->prstd;
+  RC(sle_proprio_fwd_multi(&sv, &pv, 1, 1.0f - g.dropout, n, c->HW, 512, g.n_cam, (long)n * c->HW * 512, c->cam_stride,
+                           (long)n * c->D, (long)n * c->D, g.state_dim, st));
+  // bottleneck Dense (K-split) -> LayerNorm -> tanh per camera, side by side in enc
+  const int S0 = split_under(n, kBottleneck, g.n_cam, 32);
+  GemmDesc g0{};
+  g0.A = c->f; g0.sAm = c->D; g0.sAk = 1; g0.sAb = (long)n * c->D;
+  g0.B = P + c->o_dW; g0.sBk = kBottleneck; g0.sBn = 1; g0.sBb = c->cam_stride;
+  g0.C = c->slabs; g0.ldc = kBottleneck; g0.sCz = (long)n * kBottleneck;
+  g0.M = n; g0.N = kBottleneck; g0.K = c->D; g0.nbatch = g.n_cam; g0.splitk = S0;
+  RC(gemm_f32_multi(&g0, 1, st));
+  LnFwdArgs l0{};
+  l0.slabs = c->slabs; l0.S = S0; l0.slab_stride = g0.sCz;
+  l0.bias = P + c->o_db; l0.gamma = P + c->o_lng; l0.beta = P + c->o_lnb; l0.pstride = c->cam_stride;
+  l0.rows = g.n_cam * n; l0.rows_per_group = n;
+  l0.y = c->enc; l0.ld_y = c->E; l0.y_goff = kBottleneck;
+  RC(ln_tanh_fwd_multi(&l0, 1, kBottleneck, st));
+  // MLP: Dense(256) -> tanh, twice (activate_final)
+  const int S1 = split_under(n, kHidden, 1, 8);
+  GemmDesc g1{};
+  g1.A = c->enc; g1.sAm = c->E; g1.sAk = 1;
+  g1.B = P + c->o_w1; g1.sBk = kHidden; g1.sBn = 1;
+  g1.C = c->slabs; g1.ldc = kHidden; g1.sCz = (long)n * kHidden;
+  g1.M = n; g1.N = kHidden; g1.K = c->E; g1.nbatch = 1; g1.splitk = S1;
+  RC(gemm_f32_multi(&g1, 1, st));
+  RC(dense_tanh_fwd(c->slabs, S1, g1.sCz, P + c->o_b1, c->h1, n, kHidden, st));
+  const int S2 = split_under(n, kHidden, 1, 4);
+  GemmDesc g2 = g1;
+  g2.A = c->h1; g2.sAm = kHidden; g2.B = P + c->o_w2; g2.K = kHidden; g2.splitk = S2;
+  RC(gemm_f32_multi(&g2, 1, st));
+  RC(dense_tanh_fwd(c->slabs, S2, g2.sCz, P + c->o_b2, c->h2, n, kHidden, st));
+  // heads: Dense_0 (mean) and Dense_1 (log_std) as the two batches of one GEMM
+  const int S3 = 4;
+  GemmDesc g3{};
+  g3.A = c->h2; g3.sAm = kHidden; g3.sAk = 1; g3.sAb = 0;
+  g3.B = P + c->o_Wm; g3.sBk = A; g3.sBn = 1; g3.sBb = c->o_Ws - c->o_Wm;
+  g3.C = c->slabs; g3.ldc = A; g3.sCz = (long)n * A;
+  g3.M = n; g3.N = A; g3.K = kHidden; g3.nbatch = 2; g3.splitk = S3;
+  RC(gemm_f32_multi(&g3, 1, st));
+  *head_split = S3;
+  return SERL_OK;
+}
+
+BcHeadArgs head_args(serl_bc* c, int n, int S) {
+  BcHeadArgs h{};
+  h.slabs = c->slabs; h.S = S; h.sstride = (long)n * c->cfg.act_dim;
+  h.bias_m = c->params + c->o_bm; h.bias_s = c->params + c->o_bs;
+  h.B = n; h.A = c->cfg.act_dim; h.std_min = c->cfg.std_min; h.std_max = c->cfg.std_max; h.temp = 1.0f;
+  return h;
+}
+
+int launch_head(const BcHeadArgs& h, hipStream_t st) {
+  hipLaunchKernelGGL(bc_gauss_head_kernel, dim3(1), dim3(256), 0, st, h);
+  SERL_HIP(hipGetLastError());
+  return SERL_OK;
+}
+
+int check_batch(serl_bc* c, const serl_batch* b) {
+  const serl_bc_cfg& g = c->cfg;
+  SERL_REQUIRE(b && b->frames && b->state && b->action, "serl_batch has NULL members");
+  SERL_REQUIRE(b->batch >= 1 && b->batch <= g.max_batch, "batch %d not in [1,%d]", b->batch, g.max_batch);
+  SERL_REQUIRE(b->n_cam == g.n_cam && b->H == g.H && b->W == g.W && b->C == 3 && b->state_dim == g.state_dim &&
+                   b->act_dim == g.act_dim, "serl_batch shape does not match the BC agent");
+  return SERL_OK;
+}
+
+// (section, leaf) -> device pointer; *zero: a frozen leaf's Adam moment (always zero, not stored)
+int resolve(serl_bc* c, const char* section, const char* leaf, float** ptr, long* count, bool* zero) {
+  const BLeaf* l = find(c, leaf);
+  SERL_REQUIRE(l, "unknown BC leaf '%s'", leaf);
+  *count = l->count;
+  *zero = false;
+  const std::string s = section;
+  if (s == "params") { *ptr = c->params + l->off; return SERL_OK; }
+  SERL_REQUIRE(s == "opt/mu" || s == "opt/nu", "unknown BC section '%s' (params, opt/mu, opt/nu)", section);
+  if (!l->train) { *ptr = nullptr; *zero = true; return SERL_OK; }
+  *ptr = (s == "opt/mu" ? c->m : c->v) + (l->off - c->t0);
+  return SERL_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int serl_bc_create(const serl_bc_cfg* cfg, serl_bc** out) {
+  SERL_REQUIRE(cfg && out, "NULL argument");
+  SERL_REQUIRE(cfg->n_cam >= 1 && cfg->n_cam <= SERL_MAX_CAMS, "n_cam %d not in [1,%d]", cfg->n_cam, SERL_MAX_CAMS);
+  SERL_REQUIRE(cfg->H >= 32 && cfg->W >= 32 && cfg->max_batch >= 1, "bad BC shape");
+  SERL_REQUIRE(cfg->state_dim >= 1 && cfg->act_dim >= 1 && cfg->act_dim <= kMaxAct, "state_dim %d / act_dim %d unsupported",
+               cfg->state_dim, cfg->act_dim);
+  SERL_REQUIRE(cfg->dropout >= 0.f && cfg->dropout < 1.f && cfg->std_min > 0.f && cfg->std_max > cfg->std_min, "bad BC hyper-parameters");
+  SERL_HIP(hipSetDevice(cfg->device));
+  serl_bc* c = new serl_bc();
+  c->cfg = *cfg;
+  layout(c);
+  const size_t bytes = carve(c, nullptr);
+  if (hipMalloc(&c->arena, bytes) != hipSuccess) {
+    delete c;
+    serl::set_error("hipMalloc of %zu bytes failed", bytes);
+    return SERL_ERR_HIP;
+  }
+  SERL_HIP(hipMemset(c->arena, 0, bytes));
+  carve(c, (uint8_t*)c->arena);
+  *out = c;
+  return SERL_OK;
+}
+
+int serl_bc_destroy(serl_bc* c) {
+  if (!c) return SERL_OK;
+  if (c->arena) (void)hipFree(c->arena);
+  delete c;
+  return SERL_OK;
+}
+
+int serl_bc_num_leaves(serl_bc* c) { return c ? (int)c->leaves.size() : 0; }
+
+int serl_bc_leaf_info(serl_bc* c, int i, char* name_out, int name_cap, int64_t* count, int* trainable) {
+  SERL_REQUIRE(c && i >= 0 && i < (int)c->leaves.size(), "leaf index %d out of range", i);
+  const BLeaf& l = c->leaves[i];
+  if (name_out && name_cap > 0) snprintf(name_out, name_cap, "%s", l.name.c_str());
+  if (count) *count = l.count;
+  if (trainable) *trainable = l.train ? 1 : 0;
+  return SERL_OK;
+}
+
+int serl_bc_set(serl_bc* c, const char* section, const char* leaf, const float* host, int64_t count) {
+  SERL_REQUIRE(c && section && leaf && host, "NULL argument");
+  float* p = nullptr;
+  long n = 0;
+  bool zero = false;
+  RC(resolve(c, section, leaf, &p, &n, &zero));
+  SERL_REQUIRE(count == n, "leaf '%s' has %ld elements, got %ld", leaf, n, (long)count);
+  if (zero) {   // the moments of a frozen leaf are zero by construction
+    for (long i = 0; i < n; ++i) SERL_REQUIRE(host[i] == 0.f, "'%s' of the frozen leaf '%s' must be zero", section, leaf);
+    return SERL_OK;
+  }
+  SERL_HIP(hipSetDevice(c->cfg.device));
+  SERL_HIP(hipMemcpy(p, host, (size_t)n * 4, hipMemcpyHostToDevice));
+  if (std::string(leaf).rfind("trunk/", 0) == 0 && std::string(section) == "params") c->tpk.dirty = true;
+  return SERL_OK;
+}
+
+int serl_bc_get(serl_bc* c, const char* section, const char* leaf, float* host_out, int64_t count) {
+  SERL_REQUIRE(c && section && leaf && host_out, "NULL argument");
+  float* p = nullptr;
+  long n = 0;
+  bool zero = false;
+  RC(resolve(c, section, leaf, &p, &n, &zero));
+  SERL_REQUIRE(count == n, "leaf '%s' has %ld elements, got %ld", leaf, n, (long)count);
+  if (zero) {
+    for (long i = 0; i < n; ++i) host_out[i] = 0.f;
+    return SERL_OK;
+  }
+  SERL_HIP(hipSetDevice(c->cfg.device));
+  SERL_HIP(hipMemcpy(host_out, p, (size_t)n * 4, hipMemcpyDeviceToHost));
+  return SERL_OK;
+}
+
+int serl_bc_set_step(serl_bc* c, int64_t step) {
+  SERL_REQUIRE(c && step >= 0, "bad step");
+  c->step = step;
+  return SERL_OK;
+}
+
+int64_t serl_bc_get_step(serl_bc* c) { return c ? c->step : -1; }
+
+int serl_bc_update(serl_bc* c, const serl_batch* batch, const uint8_t* dev_masks, const uint32_t* host_mask_keys, void* stream) {
+  SERL_REQUIRE(c, "NULL BC agent");
+  RC(check_batch(c, batch));
+  SERL_REQUIRE(dev_masks || host_mask_keys, "the Dropout of the update needs keep-masks or jax.random keys");
+  const serl_bc_cfg& g = c->cfg;
+  SERL_HIP(hipSetDevice(g.device));
+  hipStream_t st = (hipStream_t)stream;
+  const int n = batch->batch, A = g.act_dim;
+  const float* P = c->params;
+  float* G = c->G - c->t0;   // G[o] = gradient of the trainable leaf at arena offset o
+  int S3 = 0;
+  RC(forward(c, batch->frames, batch->state, n, dev_masks, host_mask_keys, &S3, st));
+  // loss, info and the head gradients (bc.py:44-68)
+  BcHeadArgs h = head_args(c, n, S3);
+  h.action = batch->action; h.mu = c->mu;
+  h.dmu = c->dhead; h.dls = c->dhead + (long)n * A; h.info = c->info;
+  RC(launch_head(h, st));
+  // dh2 = dmu Wm^T + dls Ws^T: the two products as slabs, summed by the tanh backward of layer 2
+  GemmDesc gh{};
+  gh.A = c->dhead; gh.sAm = A; gh.sAk = 1; gh.sAb = (long)n * A;
+  gh.B = P + c->o_Wm; gh.sBk = 1; gh.sBn = A; gh.sBb = c->o_Ws - c->o_Wm;
+  gh.C = c->slabs; gh.ldc = kHidden; gh.sCz = (long)n * kHidden;
+  gh.M = n; gh.N = kHidden; gh.K = A; gh.nbatch = 2; gh.splitk = 1;
+  RC(gemm_f32_multi(&gh, 1, st));
+  RC(dense_tanh_bwd(c->slabs, 2, gh.sCz, c->h2, c->dpre2, n, kHidden, st));
+  // dh1 = dpre2 W2^T (K-split slabs) -> dpre1
+  const int S2 = split_under(n, kHidden, 1, 4);
+  GemmDesc gd{};
+  gd.A = c->dpre2; gd.sAm = kHidden; gd.sAk = 1;
+  gd.B = P + c->o_w2; gd.sBk = 1; gd.sBn = kHidden;
+  gd.C = c->slabs; gd.ldc = kHidden; gd.sCz = (long)n * kHidden;
+  gd.M = n; gd.N = kHidden; gd.K = kHidden; gd.nbatch = 1; gd.splitk = S2;
+  RC(gemm_f32_multi(&gd, 1, st));
+  RC(dense_tanh_bwd(c->slabs, S2, gd.sCz, c->h1, c->dpre1, n, kHidden, st));
+  // gradient of the proprio code only (the image codes are behind stop_gradient): dpre1 W1[Eimg:E]^T
+  GemmDesc gp{};
+  gp.A = c->dpre1; gp.sAm = kHidden; gp.sAk = 1;
+  gp.B = P + c->o_w1 + (long)c->Eimg * kHidden; gp.sBk = 1; gp.sBn = kHidden;
+  gp.C = c->dprop; gp.ldc = kProprio; gp.sCz = 0;
+  gp.M = n; gp.N = kProprio; gp.K = kHidden; gp.nbatch = 1; gp.splitk = 1;
+  RC(gemm_f32_multi(&gp, 1, st));
+  LnBwdArgs lb{};
+  lb.dy = c->dprop; lb.ld_dy = kProprio;
+  lb.y = c->enc + c->Eimg; lb.ld_y = c->E;
+  lb.xhat = c->pxhat; lb.rstd = c->prstd; lb.gamma = P + c->o_pg;
+  lb.rows = n; lb.rows_per_group = n;
+  lb.dx = c->dpp; lb.dg = c->dgp;
+  RC(ln_tanh_bwd(lb, kProprio, st));
+  // every parameter gradient: one column-sum launch and one grouped weight-gradient GEMM
+  const float* dmu = c->dhead;
+  const float* dls = c->dhead + (long)n * A;
+  const Colsum3Args cs[5] = {
+      {c->dpre1, nullptr, nullptr, 1, n, kHidden, nullptr, G + c->o_b1, nullptr, 0, 1},
+      {c->dpre2, nullptr, nullptr, 1, n, kHidden, nullptr, G + c->o_b2, nullptr, 0, 1},
+      {dmu, nullptr, nullptr, 1, n, A, nullptr, G + c->o_bm, nullptr, 0, 1},
+      {dls, nullptr, nullptr, 1, n, A, nullptr, G + c->o_bs, nullptr, 0, 1},
+      {c->dgp, c->pxhat, c->dpp, 1, n, kProprio, G + c->o_pg, G + c->o_pbe, G + c->o_pb, 0, 0},
+  };
+  RC(colsum3_multi(cs, 5, st));
+  auto wg = [&](const float* X, long ldx, const float* dY, long ldy, float* out, int Mx, int Ny) {
+    GemmDesc w{};
+    w.A = X; w.sAm = 1; w.sAk = ldx;
+    w.B = dY; w.sBk = ldy; w.sBn = 1;
+    w.C = out; w.ldc = Ny; w.sCz = 0;
+    w.M = Mx; w.N = Ny; w.K = n; w.nbatch = 1; w.splitk = 1;
+    return w;
+  };
+  const GemmDesc wgs[5] = {
+      wg(c->enc, c->E, c->dpre1, kHidden, G + c->o_w1, c->E, kHidden),
+      wg(c->h1, kHidden, c->dpre2, kHidden, G + c->o_w2, kHidden, kHidden),
+      wg(c->h2, kHidden, dmu, A, G + c->o_Wm, kHidden, A),
+      wg(c->h2, kHidden, dls, A, G + c->o_Ws, kHidden, A),
+      wg(batch->state, g.state_dim, c->dpp, kProprio, G + c->o_pW, g.state_dim, kProprio),
+  };
+  RC(gemm_f32_multi(wgs, 5, st));
+  // optax.adam(lr) over the trainable slice (bc.py:139 via common.py:170-220); one count, no schedule, no clip
+  const int64_t t = c->step + 1;
+  AdamArgs ad{};
+  ad.theta = c->params + c->t0; ad.theta_target = nullptr;
+  ad.P = c->nt + 1; ad.Pc = 0; ad.Pa0 = 0; ad.Pa1 = c->nt;
+  ad.g_actor = c->G; ad.m_a = c->m; ad.v_a = c->v;
+  ad.m_t = c->m + c->nt; ad.v_t = c->v + c->nt;   // the temperature slot adam_ema keeps at P - 1: never touched (g = m = v = 0)
+  ad.actor_on = 1;
+  ad.lr_a = g.lr;
+  ad.bc1 = 1.0f - powf(0.9f, (float)t);
+  ad.bc2 = 1.0f - powf(0.999f, (float)t);
+  RC(adam_ema(ad, st));
+  c->step = t;
+  return SERL_OK;
+}
+
+int serl_bc_read_info(serl_bc* c, float out[2], void* stream) {
+  SERL_REQUIRE(c && out, "NULL argument");
+  SERL_HIP(hipSetDevice(c->cfg.device));
+  SERL_HIP(hipMemcpyAsync(out, c->info, 2 * sizeof(float), hipMemcpyDefault, (hipStream_t)stream));
+  return SERL_OK;
+}
+
+int serl_bc_sample_actions(serl_bc* c, const uint8_t* dev_frames, const float* dev_state, int n, const float* dev_eps,
+                           const uint32_t* host_key, float temperature, int argmax, float* dev_actions_out, void* stream) {
+  SERL_REQUIRE(c && dev_frames && dev_state && dev_actions_out, "NULL argument");
+  SERL_REQUIRE(n >= 1 && n <= c->cfg.max_batch, "n = %d not in [1, max_batch = %d]", n, c->cfg.max_batch);
+  SERL_REQUIRE(argmax || dev_eps || host_key, "sampling needs eps or a jax.random key");
+  SERL_REQUIRE(temperature >= 0.f, "negative temperature");
+  SERL_HIP(hipSetDevice(c->cfg.device));
+  hipStream_t st = (hipStream_t)stream;
+  int S3 = 0;
+  RC(forward(c, dev_frames, dev_state, n, nullptr, nullptr, &S3, st));
+  BcHeadArgs h = head_args(c, n, S3);
+  h.temp = temperature;
+  h.act = dev_actions_out;
+  h.sample = argmax ? 0 : 1;
+  h.eps = dev_eps;
+  if (!argmax && !dev_eps) { h.tf = 1; h.tf_key[0] = host_key[0]; h.tf_key[1] = host_key[1]; }
+  return launch_head(h, st);
+}
+
+int serl_bc_debug_metrics(serl_bc* c, const serl_batch* batch, float* dev_mse, float* dev_logp, float* dev_pi, void* stream) {
+  SERL_REQUIRE(c && dev_mse && dev_logp && dev_pi, "NULL argument");
+  RC(check_batch(c, batch));
+  SERL_HIP(hipSetDevice(c->cfg.device));
+  hipStream_t st = (hipStream_t)stream;
+  const int n = batch->batch;
+  int S3 = 0;
+  RC(forward(c, batch->frames, batch->state, n, nullptr, nullptr, &S3, st));
+  BcHeadArgs h = head_args(c, n, S3);
+  h.action = batch->action; h.mu = dev_pi; h.logp = dev_logp; h.mse = dev_mse;
+  return launch_head(h, st);
+}
+
+}  // extern "C"

@@ -39,7 +39,19 @@ def _unpack_ext(code, data):
     return msgpack.ExtType(code, data)
 
 
+def _own_form(agent):
+    """A train state that writes / reads its own state-dict form (BCAgent's single-optimizer state, agents/bc.py), given
+    as the agent or as its `.state` -- or None."""
+    for x in (agent, getattr(agent, "state", None)):
+        if x is not None and hasattr(x, "state_dict") and hasattr(x, "load_state_dict"):
+            return x
+    return None
+
+
 def state_dict(agent) -> dict:
+    own = _own_form(agent)
+    if own is not None:
+        return own.state_dict()
     st = agent.state
     return {"step": np.int32(st.step), "params": st.params, "target_params": st.target_params,
             "opt_states": st.opt_states, "rng": st.rng}
@@ -123,6 +135,10 @@ def _find_adam_state(node):
 def load_state_dict(agent, sd: dict):
     """Loads any of {params, target_params, opt_states, step} (flax-layout trees, e.g. a restored checkpoint or
     `agent.state.replace(...)` arguments) into the agent's HBM arena."""
+    own = _own_form(agent)
+    if own is not None:
+        own.load_state_dict(sd)
+        return agent
     core, keys = agent.core, agent.image_keys
     etype = "small" if core.cfg.encoder_type == 1 else "resnet-pretrained"
     tp = theta_paths(keys, encoder_type=etype)
