@@ -330,7 +330,7 @@ int serl_agent_trunk_plan(serl_agent* a, char* out, int cap);
 int64_t serl_debug_chain_launches(void);
 
 /* ---------------------------------------------------------------------------------------------
- * Reward classifier, inference only (next-row N4; serl_launcher/networks/reward_classifier.py:16-113).
+ * Reward classifier (next-row N4; serl_launcher/networks/reward_classifier.py:16-113).
  * BinaryClassifier = EncodingWrapper(use_proprio=False) over the frozen ResNet-10 trunk (per camera:
  * SpatialLearnedEmbeddings(8) -> Dense(256) -> LayerNorm -> tanh, concatenated) -> Dense(256) -> [Dropout: identity at
  * train=False] -> LayerNorm -> ReLU -> Dense(1).  serl_classifier_logits is the function load_classifier_func
@@ -350,6 +350,34 @@ int serl_classifier_set(serl_classifier* c, const char* leaf, const float* host,
 int serl_classifier_get(serl_classifier* c, const char* leaf, float* host_out, int64_t count);
 /* dev_frames u8[n_cam][n][H][W][3] (device), n <= max_batch; dev_logits f32[n] (device) */
 int serl_classifier_logits(serl_classifier* c, const uint8_t* dev_frames, int n, float* dev_logits, void* stream);
+
+/* Training (examples/async_cable_route_drq/train_reward_classifier.py:122-137; the same file in async_bin_relocation_fwbw_drq),
+ * opt-in on the same handle and parameter arena.  serl_classifier_train_init replaces TrainState.create(tx=optax.adam(lr))
+ * (reward_classifier.py:62-66): it allocates the Adam moments and the gradient of the trainable leaves (every camera head and the
+ * classifier head; the trunk sits behind stop_gradient, resnet_v1.py:285-286, and its moments read as zeros) plus the
+ * activations of max_batch rows.  Only optax.adam's b1 = 0.9, b2 = 0.999, eps = 1e-8 are accepted.  Every other training entry
+ * point returns SERL_ERR_STATE on a handle without it, and SERL_ERR_INVALID for n > max_batch. */
+int serl_classifier_train_init(serl_classifier* c, int max_batch, float lr, float b1, float b2, float eps);
+/* One train_step (train_reward_classifier.py:122-137): dev_frames u8[n_cam][n][H][W][3] (device, already cropped),
+ * dev_labels f32[n] (device); loss = mean(sigmoid_binary_cross_entropy(logits(train=True), labels)), accuracy from a
+ * train=False forward of the same rows with the pre-update parameters, then one Adam step.  The two Dropout(0.1) layers use
+ * dev_masks (device u8: [n_cam][n][4096] for encoder_def/encoder_<k>/Dropout_0, then [n][256] for the root Dropout_0) or,
+ * when dev_masks is NULL, jax.random.bernoulli under host_mask_keys (host uint32[n_cam + 1][2]: the make_rng("dropout") keys
+ * of those layers, cameras first), drawn inside the kernels that consume them. */
+int serl_classifier_train_step(serl_classifier* c, const uint8_t* dev_frames, int n, const float* dev_labels,
+                               const uint8_t* dev_masks, const uint32_t* host_mask_keys, void* stream);
+/* apply_fn(..., train=True, rngs={"dropout": key}) (reward_classifier.py:20-28): train-mode logits, no update.  Same masks /
+ * keys as serl_classifier_train_step; dev_logits f32[n] (device). */
+int serl_classifier_train_forward(serl_classifier* c, const uint8_t* dev_frames, int n, const uint8_t* dev_masks,
+                                  const uint32_t* host_mask_keys, float* dev_logits, void* stream);
+/* (loss, train_accuracy) of the last step (train_reward_classifier.py:128,135); `out` device or host memory, copied on
+ * `stream` */
+int serl_classifier_read_train_info(serl_classifier* c, float out[2], void* stream);
+/* TrainState.step / opt_state[0].count, and the Adam moments ("opt/mu", "opt/nu") of one leaf (frozen leaves: zeros) */
+int serl_classifier_train_set_step(serl_classifier* c, int64_t step);
+int serl_classifier_train_get_step(serl_classifier* c, int64_t* step_out);
+int serl_classifier_train_set(serl_classifier* c, const char* section, const char* leaf, const float* host, int64_t count);
+int serl_classifier_train_get(serl_classifier* c, const char* section, const char* leaf, float* host_out, int64_t count);
 
 /* ---------------------------------------------------------------------------------------------
  * Behaviour cloning (agents/continuous/bc.py, built by utils/launcher.py:26-47 with encoder_type="resnet-pretrained").

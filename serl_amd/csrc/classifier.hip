@@ -1,20 +1,47 @@
-// Reward classifier, inference only (serl_launcher/networks/reward_classifier.py:16-113): the frozen ResNet-10 trunk
-// (split-fp16 MFMA convs, trunk_f16x3.hip) -> per camera SpatialLearnedEmbeddings -> Dense -> LayerNorm -> tanh
-// (vision/resnet_v1.py:81-116,324-376; common/encoding.py:26-72 with use_proprio=False) -> Dense(256) -> LayerNorm ->
-// ReLU -> Dense(1).  Dropout layers are the identity at train=False, which is the only mode load_classifier_func uses.
-// Same kernels as the agent's encoder heads (heads.hip); the last LayerNorm launch applies ReLU and the Dense(1) row-dot.
+// Reward classifier (serl_launcher/networks/reward_classifier.py:16-113): the frozen ResNet-10 trunk
+// (split-fp16 MFMA convs, trunk_f16x3.hip) -> per camera SpatialLearnedEmbeddings -> Dropout -> Dense -> LayerNorm -> tanh
+// (vision/resnet_v1.py:81-116,324-376; common/encoding.py:26-72 with use_proprio=False) -> Dense(256) -> Dropout -> LayerNorm ->
+// ReLU -> Dense(1).  Inference (load_classifier_func) runs train=False, where both Dropout layers are the identity: the same
+// kernels as the agent's encoder heads (heads.hip); the last LayerNorm launch applies ReLU and the Dense(1) row-dot.
+// Training (train_reward_classifier.py, bottom of this file) is opt-in on the same handle and parameter arena.
+#include <algorithm>
+#include <cmath>
 #include <string>
 #include <vector>
 
 #include "heads.h"
 #include "internal.h"
+#include "jaxrng.h"
 
 using namespace serl;
 
 namespace {
 struct CLeaf { std::string name; long off, count; };
-constexpr int kHidden = 256, kBottleneck = 256, kSleFeatures = 8;
+constexpr int kHidden = 256, kBottleneck = 256, kSleFeatures = 8, kSleSplit = 8;
 inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// Opt-in training workspace (serl_classifier_train_init): optax.adam's moments and the gradient of the trainable slice
+// [t0, n_params) -- every camera head and the classifier head; the frozen trunk has none -- plus the activations of a train
+// step over up to max_batch rows.  "Instance" 0 is the train=True forward, instance 1 the train=False forward of the same rows.
+struct ClsTrain {
+  int max_batch = 0;
+  float lr = 0.f;
+  int64_t step = 0;
+  void* arena = nullptr;
+  float *m = nullptr, *v = nullptr, *G = nullptr, *info = nullptr;   // [nt + 1], [nt + 1], [nt], [2]
+  TrunkWorkspace tws{};
+  float *feats = nullptr;                        // [n_cam][n][HW][512]
+  float *f = nullptr;                            // [2][n_cam][n][D]
+  float *slabs = nullptr;                        // K-split GEMM slabs of both instances
+  float *enc = nullptr;                          // [2][n][E]
+  float *xhat = nullptr, *rstd = nullptr;        // camera LayerNorms of instance 0: [n_cam * n][256], [n_cam * n]
+  float *logits = nullptr;                       // [2][n]
+  float *hxhat = nullptr, *hdg = nullptr, *dz = nullptr, *dw2in = nullptr;   // head rows [n][256]
+  float *dlogit = nullptr, *rowloss = nullptr, *rowcorr = nullptr;           // [n]
+  float *denc = nullptr, *dzc = nullptr, *dgc = nullptr, *df = nullptr, *sle_part = nullptr;
+  int* ctr = nullptr;
+  long slabs_cap = 0;
+};
 }  // namespace
 
 struct serl_classifier {
@@ -30,6 +57,8 @@ struct serl_classifier {
   TrunkPacked tpk{};
   float *feats = nullptr, *f = nullptr, *slabs = nullptr, *enc = nullptr, *h = nullptr;
   int split0 = 1, split1 = 1;
+  long t0 = 0, nt = 0;          // trainable slice: the camera heads and the classifier head (behind the trunk)
+  ClsTrain* tr = nullptr;       // nullptr: inference only
 };
 
 namespace {
@@ -84,6 +113,8 @@ void layout(serl_classifier* c) {
   c->o_w2 = leaf("head/dense1/kernel", kHidden);
   c->o_b2 = leaf("head/dense1/bias", 1);
   c->n_params = off;
+  c->t0 = c->o_sle;
+  c->nt = off - c->t0;
 }
 
 int split_under(int M, int N, int groups, int smax) {   // K-split so that about 512 workgroups are in flight
@@ -102,7 +133,7 @@ size_t carve(serl_classifier* c, uint8_t* base) {
     return p;
   };
   const long n = g.max_batch;
-  c->params = (float*)take((size_t)c->n_params * 4);
+  c->params = (float*)take((size_t)(c->n_params + 1) * 4);   // (+ the slot adam_ema keeps behind a slice: never read here)
   uint8_t* pk = take(trunk_packed_bytes());
   uint8_t* ws = take(trunk_workspace_bytes(g.max_batch, g.H, g.W));
   c->feats = (float*)take((size_t)g.n_cam * n * c->HW * 512 * 4);
@@ -157,6 +188,10 @@ int serl_classifier_create(const serl_classifier_cfg* cfg, serl_classifier** out
 
 int serl_classifier_destroy(serl_classifier* c) {
   if (!c) return SERL_OK;
+  if (c->tr) {
+    if (c->tr->arena) (void)hipFree(c->tr->arena);
+    delete c->tr;
+  }
   if (c->arena) (void)hipFree(c->arena);
   delete c;
   return SERL_OK;
@@ -239,6 +274,453 @@ int serl_classifier_logits(serl_classifier* c, const uint8_t* dev_frames, int n,
   l1.relu = 1;
   l1.dot_w = P + c->o_w2; l1.dot_b = P + c->o_b2; l1.dot_out = dev_logits;
   return ln_tanh_fwd_multi(&l1, 1, kHidden, st);
+}
+
+}  // extern "C"
+
+// =============================================================================================
+// Training (examples/async_cable_route_drq/train_reward_classifier.py:122-137, the same file in
+// async_bin_relocation_fwbw_drq): loss = mean(optax.sigmoid_binary_cross_entropy(logits_train, labels)) with both Dropout(0.1)
+// layers active (the camera heads' behind SpatialLearnedEmbeddings, resnet_v1.py:351-352, and the head's between Dense_0 and
+// LayerNorm_0, reward_classifier.py:23-24); train_accuracy = mean((sigmoid(logits_eval) >= 0.5) == labels) from a train=False
+// forward with the pre-update parameters; optax.adam(1e-4) over every leaf (reward_classifier.py:62-66).  The trunk sits behind
+// stop_gradient (resnet_v1.py:285-286): its gradient and moments are zero, so Adam leaves it as it is and only the slice
+// [t0, n_params) is stepped.  One frozen-trunk pass serves both forwards.
+// =============================================================================================
+namespace {
+
+#define RC(x)            \
+  do {                   \
+    int _rc = (x);       \
+    if (_rc) return _rc; \
+  } while (0)
+
+__device__ __forceinline__ float cls_softplus(float x) { return fmaxf(x, 0.f) + log1pf(expf(-fabsf(x))); }
+
+// One classifier-head row per wave (lane = four adjacent columns of the 256), instance = blockIdx.y (0: train, 1: eval):
+//   x = b1 + sum_s slab[s];  train: x = where(keep, x / 0.9, 0);  LayerNorm -> ReLU -> Dense(1) -> logit
+// With labels, the train instance also writes its BCE term, dlogit = (sigmoid(l) - y) / n and the backward through Dense(1),
+// ReLU, LayerNorm and the Dropout down to dz (the gradient of Dense_0's output) plus the per-row inputs of the column sums:
+// dg (-> d scale = sum dg * xhat, d bias = sum dg), dw2in = dlogit * h (-> dDense_1 kernel); the eval instance writes whether
+// sigmoid(l) >= 0.5 matches the label (fp32 sigmoid as jax.nn.sigmoid: a logit just below zero may round to 0.5).
+struct ClsHeadArgs {
+  const float* slabs; int S; long sstride, istride;   // instance i, split s: slabs + i * istride + s * sstride, [n][256]
+  const float *b1, *g1, *be1, *w2, *b2;
+  int n; float keep;
+  const uint8_t* mask;          // keep-mask u8 [n][256] of the train instance, or nullptr
+  int gen; uint32_t key[2];     // mask == nullptr && gen: jax.random.bernoulli(key, keep, (n, 256))
+  const float* labels;          // [n], or nullptr (forward only)
+  float* logits;                // [instances][n]
+  float *xhat, *dg, *dz, *dw2in, *dlogit, *rowloss, *rowcorr;
+};
+__global__ __launch_bounds__(256) void cls_head_kernel(ClsHeadArgs a) {
+  const int inst = blockIdx.y;
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (row >= a.n) return;
+  const bool train = inst == 0;
+  const float* sl = a.slabs + inst * a.istride + (long)row * kHidden;
+  float v[4];
+  bool keep[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int col = lane * 4 + j;
+    float x = a.b1[col];
+    for (int s = 0; s < a.S; ++s) x += sl[(long)s * a.sstride + col];
+    keep[j] = true;
+    if (train) {
+      const long e = (long)row * kHidden + col;
+      keep[j] = a.mask ? a.mask[e] != 0
+                       : (a.gen ? bits_to_unit(random_bits_at(a.key[0], a.key[1], (uint64_t)a.n * kHidden, (uint64_t)e)) < a.keep : true);
+      x = keep[j] ? x / a.keep : 0.f;
+    }
+    v[j] = x;
+  }
+  float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) { s1 += v[j]; s2 += v[j] * v[j]; }
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) { s1 += __shfl_xor(s1, off); s2 += __shfl_xor(s2, off); }
+  const float mean = s1 * (1.0f / kHidden), mean2 = s2 * (1.0f / kHidden);
+  const float rstd = rsqrtf(fmaxf(mean2 - mean * mean, 0.f) + 1e-6f);
+  float xh[4], pre[4], h[4], d = 0.f;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int col = lane * 4 + j;
+    xh[j] = (v[j] - mean) * rstd;
+    pre[j] = xh[j] * a.g1[col] + a.be1[col];
+    h[j] = fmaxf(pre[j], 0.f);
+    d += h[j] * a.w2[col];
+  }
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) d += __shfl_xor(d, off);
+  const float logit = d + a.b2[0];
+  if (lane == 0) a.logits[(long)inst * a.n + row] = logit;
+  if (!a.labels) return;
+  const float y = a.labels[row];
+  const float p = 1.f / (1.f + expf(-logit));
+  if (!train) {
+    if (lane == 0) a.rowcorr[row] = ((p >= 0.5f ? 1.f : 0.f) == y) ? 1.f : 0.f;
+    return;
+  }
+  const float dl = (p - y) / (float)a.n;
+  if (lane == 0) {   // optax.sigmoid_binary_cross_entropy = -y log_sigmoid(l) - (1 - y) log_sigmoid(-l)
+    a.rowloss[row] = y * cls_softplus(-logit) + (1.f - y) * cls_softplus(logit);
+    a.dlogit[row] = dl;
+  }
+  float dA[4], dxh[4];
+  s1 = 0.f; s2 = 0.f;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int col = lane * 4 + j;
+    dA[j] = pre[j] > 0.f ? dl * a.w2[col] : 0.f;
+    dxh[j] = dA[j] * a.g1[col];
+    s1 += dxh[j];
+    s2 += dxh[j] * xh[j];
+  }
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) { s1 += __shfl_xor(s1, off); s2 += __shfl_xor(s2, off); }
+  const float m1 = s1 * (1.0f / kHidden), m2 = s2 * (1.0f / kHidden);
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const long e = (long)row * kHidden + lane * 4 + j;
+    const float dx = rstd * (dxh[j] - m1 - xh[j] * m2);
+    a.dz[e] = keep[j] ? dx / a.keep : 0.f;
+    a.xhat[e] = xh[j];
+    a.dg[e] = dA[j];
+    a.dw2in[e] = dl * h[j];
+  }
+}
+
+// info[0] = mean of the BCE terms, info[1] = mean of the eval hits: one workgroup, 256 strided partial sums then a halving tree
+// (a fixed order: deterministic)
+__global__ __launch_bounds__(256) void cls_info_kernel(const float* rowloss, const float* rowcorr, int n, float* info) {
+  __shared__ float red[2][256];
+  const int tid = threadIdx.x;
+  float sl = 0.f, sc = 0.f;
+  for (int r = tid; r < n; r += 256) { sl += rowloss[r]; sc += rowcorr[r]; }
+  red[0][tid] = sl;
+  red[1][tid] = sc;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if (tid < o) { red[0][tid] += red[0][tid + o]; red[1][tid] += red[1][tid + o]; }
+    __syncthreads();
+  }
+  if (tid == 0) {
+    info[0] = red[0][0] / (float)n;
+    info[1] = red[1][0] / (float)n;
+  }
+}
+
+// Backward of the camera heads' Dropout (resnet_v1.py:352): df[cam][e] = where(keep, df / 0.9, 0) in place, e < n * 4096, the
+// keep-mask injected ([n_cam][n][4096]) or re-drawn from the camera's key exactly as the SLE forward drew it
+struct ClsDropArgs { float* df; long per_cam; const uint8_t* mask; uint32_t key[SERL_MAX_CAMS][2]; float keep; };
+__global__ __launch_bounds__(256) void cls_dropout_bwd_kernel(ClsDropArgs a) {
+  const long e = (long)blockIdx.x * 256 + threadIdx.x;
+  if (e >= a.per_cam) return;
+  const int cam = blockIdx.y;
+  const long i = (long)cam * a.per_cam + e;
+  const bool k = a.mask ? a.mask[i] != 0
+                        : bits_to_unit(random_bits_at(a.key[cam][0], a.key[cam][1], (uint64_t)a.per_cam, (uint64_t)e)) < a.keep;
+  a.df[i] = k ? a.df[i] / a.keep : 0.f;
+}
+
+size_t carve_train(serl_classifier* c, ClsTrain* t, uint8_t* base) {
+  const serl_classifier_cfg& g = c->cfg;
+  size_t off = 0;
+  auto take = [&](size_t bytes) {
+    uint8_t* p = base ? base + off : nullptr;
+    off += al256(bytes);
+    return p;
+  };
+  const long n = t->max_batch, nc = g.n_cam;
+  t->m = (float*)take((size_t)(c->nt + 1) * 4);
+  t->v = (float*)take((size_t)(c->nt + 1) * 4);
+  t->G = (float*)take((size_t)c->nt * 4);
+  t->info = (float*)take(2 * 4);
+  uint8_t* ws = take(trunk_workspace_bytes((int)(nc * n), g.H, g.W));
+  t->feats = (float*)take((size_t)nc * n * c->HW * 512 * 4);
+  t->f = (float*)take((size_t)2 * nc * n * c->D * 4);
+  t->slabs_cap = 2L * 32 * nc * n * kBottleneck;
+  t->slabs = (float*)take((size_t)t->slabs_cap * 4);
+  t->enc = (float*)take((size_t)2 * n * c->E * 4);
+  t->xhat = (float*)take((size_t)nc * n * kBottleneck * 4);
+  t->rstd = (float*)take((size_t)nc * n * 4);
+  t->logits = (float*)take((size_t)2 * n * 4);
+  t->hxhat = (float*)take((size_t)n * kHidden * 4);
+  t->hdg = (float*)take((size_t)n * kHidden * 4);
+  t->dz = (float*)take((size_t)n * kHidden * 4);
+  t->dw2in = (float*)take((size_t)n * kHidden * 4);
+  t->dlogit = (float*)take((size_t)n * 4);
+  t->rowloss = (float*)take((size_t)n * 4);
+  t->rowcorr = (float*)take((size_t)n * 4);
+  t->denc = (float*)take((size_t)n * c->E * 4);
+  t->dzc = (float*)take((size_t)nc * n * kBottleneck * 4);
+  t->dgc = (float*)take((size_t)nc * n * kBottleneck * 4);
+  t->df = (float*)take((size_t)nc * n * c->D * 4);
+  t->sle_part = (float*)take((size_t)nc * kSleSplit * c->HW * 512 * kSleFeatures * 4);
+  t->ctr = (int*)take((size_t)nc * c->HW * cdiv(512, 256) * 4);
+  if (base) trunk_workspace_bind(t->tws, ws, (int)(nc * n), g.H, g.W);
+  return off;
+}
+
+constexpr float kKeep = 0.9f;   // nn.Dropout(0.1): keep probability 1 - 0.1
+
+// The train=True forward (instance 0) and, with `eval`, the train=False forward (instance 1) of n cropped observations up to the
+// classifier-head kernel.  masks: u8 [n_cam][n][4096] then [n][256] (device) or nullptr; keys: host uint32 [n_cam + 1][2] -- the
+// make_rng("dropout") keys of encoder_def/encoder_<k>/Dropout_0 and of the root Dropout_0.
+int train_forward(serl_classifier* c, const uint8_t* frames, int n, const float* labels, const uint8_t* masks,
+                  const uint32_t* keys, bool eval, hipStream_t st) {
+  const serl_classifier_cfg& g = c->cfg;
+  ClsTrain* t = c->tr;
+  const float* P = c->params;
+  const int nc = g.n_cam, ni = eval ? 2 : 1;
+  const long nD = (long)n * c->D;
+  RC(trunk_forward(c->tw, t->tws, frames, nc * n, t->feats, st, &c->tpk));
+  // SpatialLearnedEmbeddings (+ Dropout keep-mask on instance 0) of both instances in one launch
+  SleFwdArgs sv[2] = {SleFwdArgs{}, SleFwdArgs{}};
+  for (int i = 0; i < ni; ++i) { sv[i].x = t->feats; sv[i].K = P + c->o_sle; sv[i].f = t->f + i * nc * nD; }
+  sv[0].mask = masks;
+  if (!masks) {
+    sv[0].gen = 2;
+    for (int k = 0; k < nc; ++k) { sv[0].tf_key[k][0] = keys[2 * k]; sv[0].tf_key[k][1] = keys[2 * k + 1]; }
+    sv[0].tf_rows = n; sv[0].tf_row0 = 0;
+  }
+  RC(sle_proprio_fwd_multi(sv, nullptr, ni, kKeep, n, c->HW, 512, nc, (long)n * c->HW * 512, c->cam_stride, nD, nD, 0, st));
+  // bottleneck Dense (K-split) -> LayerNorm -> tanh per camera, side by side in enc[i]
+  const int S0 = split_under(n, kBottleneck, nc * ni, 32);
+  GemmDesc g0[2];
+  LnFwdArgs l0[2];
+  for (int i = 0; i < ni; ++i) {
+    GemmDesc& d = g0[i];
+    d = GemmDesc{};
+    d.A = t->f + i * nc * nD; d.sAm = c->D; d.sAk = 1; d.sAb = nD;
+    d.B = P + c->o_dW; d.sBk = kBottleneck; d.sBn = 1; d.sBb = c->cam_stride;
+    d.C = t->slabs + (long)i * nc * S0 * n * kBottleneck; d.ldc = kBottleneck; d.sCz = (long)n * kBottleneck;
+    d.M = n; d.N = kBottleneck; d.K = c->D; d.nbatch = nc; d.splitk = S0;
+    LnFwdArgs& l = l0[i];
+    l = LnFwdArgs{};
+    l.slabs = d.C; l.S = S0; l.slab_stride = d.sCz;
+    l.bias = P + c->o_db; l.gamma = P + c->o_lng; l.beta = P + c->o_lnb; l.pstride = c->cam_stride;
+    l.rows = nc * n; l.rows_per_group = n;
+    l.y = t->enc + (long)i * n * c->E; l.ld_y = c->E; l.y_goff = kBottleneck;
+    if (i == 0) { l.xhat = t->xhat; l.rstd = t->rstd; }
+  }
+  RC(gemm_f32_multi(g0, ni, st));
+  RC(ln_tanh_fwd_multi(l0, ni, kBottleneck, st));
+  // classifier head: Dense_0 (K-split) of both instances, then the row kernel
+  const int S1 = split_under(n, kHidden, ni, 8);
+  GemmDesc g1[2];
+  for (int i = 0; i < ni; ++i) {
+    GemmDesc& d = g1[i];
+    d = GemmDesc{};
+    d.A = t->enc + (long)i * n * c->E; d.sAm = c->E; d.sAk = 1;
+    d.B = P + c->o_w1; d.sBk = kHidden; d.sBn = 1;
+    d.C = t->slabs + (long)i * S1 * n * kHidden; d.ldc = kHidden; d.sCz = (long)n * kHidden;
+    d.M = n; d.N = kHidden; d.K = c->E; d.nbatch = 1; d.splitk = S1;
+  }
+  RC(gemm_f32_multi(g1, ni, st));
+  ClsHeadArgs h{};
+  h.slabs = t->slabs; h.S = S1; h.sstride = (long)n * kHidden; h.istride = (long)S1 * n * kHidden;
+  h.b1 = P + c->o_b1; h.g1 = P + c->o_g1; h.be1 = P + c->o_be1; h.w2 = P + c->o_w2; h.b2 = P + c->o_b2;
+  h.n = n; h.keep = kKeep;
+  h.mask = masks ? masks + (long)nc * nD : nullptr;
+  if (!masks) { h.gen = 1; h.key[0] = keys[2 * nc]; h.key[1] = keys[2 * nc + 1]; }
+  h.labels = labels; h.logits = t->logits;
+  h.xhat = t->hxhat; h.dg = t->hdg; h.dz = t->dz; h.dw2in = t->dw2in; h.dlogit = t->dlogit; h.rowloss = t->rowloss; h.rowcorr = t->rowcorr;
+  hipLaunchKernelGGL(cls_head_kernel, dim3(cdiv(n, 4), ni), dim3(256), 0, st, h);
+  SERL_HIP(hipGetLastError());
+  return SERL_OK;
+}
+
+int check_train(serl_classifier* c, int n) {
+  SERL_REQUIRE(c, "NULL classifier");
+  if (!c->tr) {
+    serl::set_error("classifier training is not initialised (serl_classifier_train_init)");
+    return SERL_ERR_STATE;
+  }
+  SERL_REQUIRE(n >= 1 && n <= c->tr->max_batch, "n = %d not in [1, training max_batch = %d]", n, c->tr->max_batch);
+  return SERL_OK;
+}
+
+int resolve_moment(serl_classifier* c, const char* section, const char* leaf, float** ptr, long* count) {
+  SERL_REQUIRE(section && leaf, "NULL argument");
+  const CLeaf* l = find(c, leaf);
+  SERL_REQUIRE(l, "unknown classifier leaf '%s'", leaf);
+  const std::string s = section;
+  SERL_REQUIRE(s == "opt/mu" || s == "opt/nu", "unknown classifier section '%s' (opt/mu, opt/nu)", section);
+  *count = l->count;
+  *ptr = l->off < c->t0 ? nullptr : (s == "opt/mu" ? c->tr->m : c->tr->v) + (l->off - c->t0);   // nullptr: frozen, always zero
+  return SERL_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int serl_classifier_train_init(serl_classifier* c, int max_batch, float lr, float b1, float b2, float eps) {
+  SERL_REQUIRE(c, "NULL classifier");
+  SERL_REQUIRE(!c->tr, "classifier training is already initialised");
+  SERL_REQUIRE(max_batch >= 1 && lr > 0.f, "bad training max_batch %d / learning rate %g", max_batch, (double)lr);
+  SERL_REQUIRE(b1 == 0.9f && b2 == 0.999f && eps == 1e-8f, "only optax.adam's defaults b1 = 0.9, b2 = 0.999, eps = 1e-8 are implemented");
+  SERL_HIP(hipSetDevice(c->cfg.device));
+  ClsTrain* t = new ClsTrain();
+  t->max_batch = max_batch;
+  t->lr = lr;
+  const size_t bytes = carve_train(c, t, nullptr);
+  if (hipMalloc(&t->arena, bytes) != hipSuccess) {
+    delete t;
+    serl::set_error("hipMalloc of %zu bytes failed", bytes);
+    return SERL_ERR_HIP;
+  }
+  SERL_HIP(hipMemset(t->arena, 0, bytes));
+  carve_train(c, t, (uint8_t*)t->arena);
+  c->tr = t;
+  return SERL_OK;
+}
+
+int serl_classifier_train_forward(serl_classifier* c, const uint8_t* dev_frames, int n, const uint8_t* dev_masks,
+                                  const uint32_t* host_mask_keys, float* dev_logits, void* stream) {
+  RC(check_train(c, n));
+  SERL_REQUIRE(dev_frames && dev_logits && (dev_masks || host_mask_keys), "NULL argument (the Dropout needs keep-masks or keys)");
+  hipStream_t st = (hipStream_t)stream;
+  SERL_HIP(hipSetDevice(c->cfg.device));
+  RC(train_forward(c, dev_frames, n, nullptr, dev_masks, host_mask_keys, false, st));
+  SERL_HIP(hipMemcpyAsync(dev_logits, c->tr->logits, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
+  return SERL_OK;
+}
+
+int serl_classifier_train_step(serl_classifier* c, const uint8_t* dev_frames, int n, const float* dev_labels,
+                               const uint8_t* dev_masks, const uint32_t* host_mask_keys, void* stream) {
+  RC(check_train(c, n));
+  SERL_REQUIRE(dev_frames && dev_labels && (dev_masks || host_mask_keys), "NULL argument (the Dropout needs keep-masks or keys)");
+  const serl_classifier_cfg& g = c->cfg;
+  ClsTrain* t = c->tr;
+  hipStream_t st = (hipStream_t)stream;
+  SERL_HIP(hipSetDevice(g.device));
+  const float* P = c->params;
+  float* G = t->G - c->t0;   // G[o] = gradient of the leaf at arena offset o
+  const int nc = g.n_cam;
+  const long nD = (long)n * c->D;
+  RC(train_forward(c, dev_frames, n, dev_labels, dev_masks, host_mask_keys, true, st));
+  hipLaunchKernelGGL(cls_info_kernel, dim3(1), dim3(256), 0, st, t->rowloss, t->rowcorr, n, t->info);
+  SERL_HIP(hipGetLastError());
+  // d enc = dz W1^T
+  GemmDesc gi{};
+  gi.A = t->dz; gi.sAm = kHidden; gi.sAk = 1;
+  gi.B = P + c->o_w1; gi.sBk = 1; gi.sBn = kHidden;
+  gi.C = t->denc; gi.ldc = c->E; gi.sCz = 0;
+  gi.M = n; gi.N = c->E; gi.K = kHidden; gi.nbatch = 1; gi.splitk = 1;
+  RC(gemm_f32_multi(&gi, 1, st));
+  // camera heads: tanh + LayerNorm backward (all cameras), then d f = dzc W^T per camera
+  LnBwdArgs lb{};
+  lb.dy = t->denc; lb.ld_dy = c->E; lb.dy_goff = kBottleneck;
+  lb.y = t->enc; lb.ld_y = c->E; lb.y_goff = kBottleneck;
+  lb.xhat = t->xhat; lb.rstd = t->rstd; lb.gamma = P + c->o_lng; lb.pstride = c->cam_stride;
+  lb.rows = nc * n; lb.rows_per_group = n;
+  lb.dx = t->dzc; lb.dg = t->dgc;
+  RC(ln_tanh_bwd(lb, kBottleneck, st));
+  GemmDesc gf{};
+  gf.A = t->dzc; gf.sAm = kBottleneck; gf.sAk = 1; gf.sAb = (long)n * kBottleneck;
+  gf.B = P + c->o_dW; gf.sBk = 1; gf.sBn = kBottleneck; gf.sBb = c->cam_stride;
+  gf.C = t->df; gf.ldc = c->D; gf.sCz = nD;
+  gf.M = n; gf.N = c->D; gf.K = kBottleneck; gf.nbatch = nc; gf.splitk = 1;
+  RC(gemm_f32_multi(&gf, 1, st));
+  // through the camera Dropout, then the SpatialLearnedEmbeddings kernels' gradient (batch splits summed by the last arriver)
+  ClsDropArgs da{};
+  da.df = t->df; da.per_cam = nD; da.mask = dev_masks; da.keep = kKeep;
+  if (!dev_masks)
+    for (int k = 0; k < nc; ++k) { da.key[k][0] = host_mask_keys[2 * k]; da.key[k][1] = host_mask_keys[2 * k + 1]; }
+  hipLaunchKernelGGL(cls_dropout_bwd_kernel, dim3(cdiv(nD, 256), nc), dim3(256), 0, st, da);
+  SERL_HIP(hipGetLastError());
+  const long sle_n = (long)c->HW * 512 * kSleFeatures;
+  RC(sle_bwd_fused(t->feats, t->df, t->sle_part, n, c->HW, 512, kSleSplit, nc, (long)n * c->HW * 512, nD, kSleSplit * sle_n,
+                   G + c->o_sle, c->cam_stride, t->ctr, st));
+  // every other parameter gradient: one column-sum launch and one grouped weight-gradient GEMM
+  const Colsum3Args cs[4] = {
+      {t->hdg, t->hxhat, t->dz, 1, n, kHidden, G + c->o_g1, G + c->o_be1, G + c->o_b1, 0, 0},
+      {t->dw2in, nullptr, nullptr, 1, n, kHidden, nullptr, G + c->o_w2, nullptr, 0, 1},
+      {t->dlogit, nullptr, nullptr, 1, n, 1, nullptr, G + c->o_b2, nullptr, 0, 2},
+      {t->dgc, t->xhat, t->dzc, nc, n, kBottleneck, G + c->o_lng, G + c->o_lnb, G + c->o_db, c->cam_stride, 0},
+  };
+  RC(colsum3_multi(cs, 4, st));
+  GemmDesc wg[2] = {GemmDesc{}, GemmDesc{}};
+  wg[0].A = t->enc; wg[0].sAm = 1; wg[0].sAk = c->E;                     // dDense_0 = enc^T dz
+  wg[0].B = t->dz; wg[0].sBk = kHidden; wg[0].sBn = 1;
+  wg[0].C = G + c->o_w1; wg[0].ldc = kHidden; wg[0].sCz = 0;
+  wg[0].M = c->E; wg[0].N = kHidden; wg[0].K = n; wg[0].nbatch = 1; wg[0].splitk = 1;
+  wg[1].A = t->f; wg[1].sAm = 1; wg[1].sAk = c->D; wg[1].sAb = nD;      // per camera dDense = f^T dzc
+  wg[1].B = t->dzc; wg[1].sBk = kBottleneck; wg[1].sBn = 1; wg[1].sBb = (long)n * kBottleneck;
+  wg[1].C = G + c->o_dW; wg[1].ldc = kBottleneck; wg[1].sCz = c->cam_stride;
+  wg[1].M = c->D; wg[1].N = kBottleneck; wg[1].K = n; wg[1].nbatch = nc; wg[1].splitk = 1;
+  RC(gemm_f32_multi(wg, 2, st));
+  // optax.adam(lr) (reward_classifier.py:62-66) over the trainable slice
+  const int64_t step = t->step + 1;
+  AdamArgs ad{};
+  ad.theta = c->params + c->t0; ad.theta_target = nullptr;
+  ad.P = c->nt + 1; ad.Pc = 0; ad.Pa0 = 0; ad.Pa1 = c->nt;
+  ad.g_actor = t->G; ad.m_a = t->m; ad.v_a = t->v;
+  ad.m_t = t->m + c->nt; ad.v_t = t->v + c->nt;   // the temperature slot adam_ema keeps at P - 1: never touched (g = m = v = 0)
+  ad.actor_on = 1;
+  ad.lr_a = t->lr;
+  ad.bc1 = 1.0f - powf(0.9f, (float)step);
+  ad.bc2 = 1.0f - powf(0.999f, (float)step);
+  RC(adam_ema(ad, st));
+  t->step = step;
+  return SERL_OK;
+}
+
+int serl_classifier_read_train_info(serl_classifier* c, float out[2], void* stream) {
+  RC(check_train(c, 1));
+  SERL_REQUIRE(out, "NULL argument");
+  SERL_HIP(hipSetDevice(c->cfg.device));
+  SERL_HIP(hipMemcpyAsync(out, c->tr->info, 2 * sizeof(float), hipMemcpyDefault, (hipStream_t)stream));
+  return SERL_OK;
+}
+
+int serl_classifier_train_set_step(serl_classifier* c, int64_t step) {
+  RC(check_train(c, 1));
+  SERL_REQUIRE(step >= 0, "negative step");
+  c->tr->step = step;
+  return SERL_OK;
+}
+
+int serl_classifier_train_get_step(serl_classifier* c, int64_t* step_out) {
+  RC(check_train(c, 1));
+  SERL_REQUIRE(step_out, "NULL argument");
+  *step_out = c->tr->step;
+  return SERL_OK;
+}
+
+int serl_classifier_train_set(serl_classifier* c, const char* section, const char* leaf, const float* host, int64_t count) {
+  RC(check_train(c, 1));
+  SERL_REQUIRE(host, "NULL argument");
+  float* p = nullptr;
+  long n = 0;
+  RC(resolve_moment(c, section, leaf, &p, &n));
+  SERL_REQUIRE(count == n, "leaf '%s' has %ld elements, got %ld", leaf, n, (long)count);
+  if (!p) {   // the moments of a frozen leaf are zero by construction
+    for (long i = 0; i < n; ++i) SERL_REQUIRE(host[i] == 0.f, "'%s' of the frozen leaf '%s' must be zero", section, leaf);
+    return SERL_OK;
+  }
+  SERL_HIP(hipSetDevice(c->cfg.device));
+  SERL_HIP(hipMemcpy(p, host, (size_t)n * 4, hipMemcpyHostToDevice));
+  return SERL_OK;
+}
+
+int serl_classifier_train_get(serl_classifier* c, const char* section, const char* leaf, float* host_out, int64_t count) {
+  RC(check_train(c, 1));
+  SERL_REQUIRE(host_out, "NULL argument");
+  float* p = nullptr;
+  long n = 0;
+  RC(resolve_moment(c, section, leaf, &p, &n));
+  SERL_REQUIRE(count == n, "leaf '%s' has %ld elements, got %ld", leaf, n, (long)count);
+  if (!p) {
+    for (long i = 0; i < n; ++i) host_out[i] = 0.f;
+    return SERL_OK;
+  }
+  SERL_HIP(hipSetDevice(c->cfg.device));
+  SERL_HIP(hipMemcpy(host_out, p, (size_t)n * 4, hipMemcpyDeviceToHost));
+  return SERL_OK;
 }
 
 }  // extern "C"

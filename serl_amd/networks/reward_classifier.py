@@ -1,24 +1,29 @@
-"""Reward classifier, inference side, with the reference's names (serl_launcher/networks/reward_classifier.py):
+"""Reward classifier with the reference's names (serl_launcher/networks/reward_classifier.py and
+examples/async_cable_route_drq/train_reward_classifier.py):
 
     create_classifier(key, sample, image_keys, pretrained_encoder_path)   (:31-90)
     load_classifier_func(key, sample, image_keys, checkpoint_path, step)  (:93-113) -> func(obs) -> logits
+    train_step(state, batch, key) -> (state, loss, train_accuracy)       (train_reward_classifier.py:122-137)
+    train_reward_classifier(pos_buffer, neg_buffer, image_keys, ...)     (train_reward_classifier.py:54-172)
 
-The forward pass (frozen ResNet-10 trunk -> per camera SpatialLearnedEmbeddings / Dense / LayerNorm / tanh -> Dense(256)
--> LayerNorm -> ReLU -> Dense(1), Dropout = identity at train=False) runs in libserl_mi355.so (csrc/classifier.hip); no
-CPU fallback.  Training the classifier (examples/.../train_reward_classifier.py) is outside the hot path: checkpoints
-written by the reference's trainer are read here (flax msgpack layout, see utils/checkpoint.py).
+The forward pass (frozen ResNet-10 trunk -> per camera SpatialLearnedEmbeddings / Dropout / Dense / LayerNorm / tanh ->
+Dense(256) -> Dropout -> LayerNorm -> ReLU -> Dense(1)) and, for a classifier created with trainable=True, the train step
+(loss, backward, optax.adam) run in libserl_mi355.so (csrc/classifier.hip); no CPU fallback.  Checkpoints use the flax
+msgpack layout of the reference's TrainState (utils/checkpoint.py).
 """
 from __future__ import annotations
 
 import ctypes as C
 import os
 import pickle
+from collections import namedtuple
 from typing import Callable, Dict, List, Optional
 
 import numpy as np
 import torch
 
 from .. import _lib
+from .. import jaxrng as J
 from ..agents.flax_tree import _trunk_paths, trunk_from_flax, trunk_owner
 
 
@@ -38,6 +43,14 @@ def _declare(lib):
         "serl_classifier_set": [vp, C.c_char_p, vp, i64],
         "serl_classifier_get": [vp, C.c_char_p, vp, i64],
         "serl_classifier_logits": [vp, vp, i32, vp, vp],
+        "serl_classifier_train_init": [vp, i32, C.c_float, C.c_float, C.c_float, C.c_float],
+        "serl_classifier_train_step": [vp, vp, i32, vp, vp, vp, vp],
+        "serl_classifier_train_forward": [vp, vp, i32, vp, vp, vp, vp],
+        "serl_classifier_read_train_info": [vp, vp, vp],
+        "serl_classifier_train_set_step": [vp, i64],
+        "serl_classifier_train_get_step": [vp, C.POINTER(i64)],
+        "serl_classifier_train_set": [vp, C.c_char_p, C.c_char_p, vp, i64],
+        "serl_classifier_train_get": [vp, C.c_char_p, C.c_char_p, vp, i64],
     }
     for name, args in sigs.items():
         fn = getattr(lib, name)
@@ -55,11 +68,44 @@ _CAM_PATHS = {"sle": ("SpatialLearnedEmbeddings_0", "kernel"), "dense/kernel": (
               "dense/bias": ("Dense_0", "bias"), "ln/scale": ("LayerNorm_0", "scale"), "ln/bias": ("LayerNorm_0", "bias")}
 
 
-class Classifier:
-    """The role of the reference's `TrainState` for inference: `.params` (flax-layout tree) and
-    `.apply_fn({"params": params}, obs, train=False)`; parameters live in HBM."""
+# optax.adam's state (optax/_src/transform.py ScaleByAdamState; base.EmptyState of scale_by_learning_rate)
+ScaleByAdamState = namedtuple("ScaleByAdamState", ["count", "mu", "nu"])
+EmptyState = namedtuple("EmptyState", [])
 
-    def __init__(self, image_keys, H, W, max_batch=64, device=0):
+SLE_DIM = 512 * 8
+HIDDEN = 256
+
+
+def dropout_paths(image_keys) -> List[tuple]:
+    """Scope paths of the classifier's Dropout layers: encoder_def/encoder_<k>/Dropout_0 behind every camera's
+    SpatialLearnedEmbeddings (resnet_v1.py:352, shape (B, 4096)), then the root Dropout_0 (reward_classifier.py:24, (B, 256))."""
+    return [("encoder_def", f"encoder_{k}", "Dropout_0") for k in image_keys] + [("Dropout_0",)]
+
+
+def dropout_keys(key, image_keys) -> np.ndarray:
+    """uint32[n_cam + 1][2]: the keys make_rng("dropout") gives those layers under apply_fn(..., rngs={"dropout": key})"""
+    k = np.asarray(key, np.uint32).reshape(2)
+    return np.stack([J.flax_make_rng(k, p) for p in dropout_paths(image_keys)]).astype(np.uint32)
+
+
+def _stacked(frames):
+    """torch.stack(frames) -- without the copy when the cameras already lie back to back in one contiguous buffer
+    (train_reward_classifier's batches: views of one [n_cam][B][H][W][3] tensor)"""
+    f0 = frames[0]
+    step = f0.numel()
+    if all(f.is_contiguous() and f.shape == f0.shape and f.untyped_storage().data_ptr() == f0.untyped_storage().data_ptr()
+           and f.storage_offset() == f0.storage_offset() + i * step for i, f in enumerate(frames)):
+        return f0.as_strided((len(frames),) + tuple(f0.shape), (step,) + tuple(f0.stride()), f0.storage_offset())
+    return torch.stack(frames).contiguous()
+
+
+class Classifier:
+    """The role of the reference's `TrainState`: `.params` (flax-layout tree) and
+    `.apply_fn({"params": params}, obs, train=False)`; parameters live in HBM.  With trainable=True also `.step`,
+    `.opt_state` (optax.adam's (ScaleByAdamState(count, mu, nu), EmptyState()); the frozen trunk's moments are zeros),
+    apply_fn(..., train=True, rngs={"dropout": key}) and `train_step`."""
+
+    def __init__(self, image_keys, H, W, max_batch=64, device=0, trainable=False, learning_rate=1e-4):
         self.L = _lib.lib()
         _declare(self.L)
         self.image_keys = tuple(image_keys)
@@ -68,6 +114,9 @@ class Classifier:
         h = C.c_void_p()
         _lib.check(self.L.serl_classifier_create(C.byref(cfg), C.byref(h)))
         self._h = h
+        self.trainable = bool(trainable)
+        if self.trainable:   # TrainState.create(tx=optax.adam(learning_rate)) (reward_classifier.py:62-66)
+            _lib.check(self.L.serl_classifier_train_init(h, int(max_batch), float(learning_rate), 0.9, 0.999, 1e-8))
         self._counts = {}
         name = C.create_string_buffer(128)
         cnt = C.c_int64()
@@ -111,14 +160,27 @@ class Classifier:
             self._params_cache = self._export()
         return self._params_cache
 
-    def _export(self):
+    def _get(self, section, leaf):
+        if section == "params":
+            return self.get(leaf)
+        out = np.empty(self._counts[leaf], np.float32)
+        _lib.check(self.L.serl_classifier_train_get(self._h, section.encode(), leaf.encode(), out.ctypes.data_as(C.c_void_p), out.size))
+        return out
+
+    def _set(self, section, leaf, value):
+        if section == "params":
+            return self.set(leaf, value)
+        a = np.ascontiguousarray(np.asarray(value, np.float32).reshape(-1))
+        _lib.check(self.L.serl_classifier_train_set(self._h, section.encode(), leaf.encode(), a.ctypes.data_as(C.c_void_p), a.size))
+
+    def _export(self, section="params"):
         from ..utils.init import trunk_shapes
         tree = {"encoder_def": {}}
         tsh = trunk_shapes()
         for k in self.image_keys:
             sub = tree["encoder_def"].setdefault(f"encoder_{k}", {})
             for leaf, (mod, name) in _CAM_PATHS.items():
-                v = self.get(self._leaf(k, leaf))
+                v = self._get(section, self._leaf(k, leaf))
                 shape = {"sle": (-1, 512, 8), "dense/kernel": (4096, 256)}.get(leaf, (-1,))
                 if leaf == "sle":
                     hw = v.size // (512 * 8)
@@ -130,33 +192,145 @@ class Classifier:
             d = owner.setdefault("pretrained_encoder", {})
             for p in path[:-1]:
                 d = d.setdefault(p, {})
-            d[path[-1]] = self.get(leaf).reshape(tsh[leaf])
+            d[path[-1]] = self._get(section, leaf).reshape(tsh[leaf])
         E = 256 * len(self.image_keys)
         for leaf, (mod, name) in _HEAD_PATHS.items():
             shape = {"head/dense0/kernel": (E, 256), "head/dense1/kernel": (256, 1)}.get(leaf, (-1,))
-            tree.setdefault(mod, {})[name] = self.get(leaf).reshape(shape)
+            tree.setdefault(mod, {})[name] = self._get(section, leaf).reshape(shape)
         return tree
 
-    def load_params(self, tree):
-        """A BinaryClassifier parameter tree (e.g. the `params` entry of a checkpoint the reference's trainer wrote)."""
+    def load_params(self, tree, section="params"):
+        """A BinaryClassifier parameter tree (e.g. the `params` entry of a checkpoint the reference's trainer wrote); with
+        section "opt/mu" / "opt/nu" an Adam moment tree of the same layout."""
+        if section == "params":
+            self._params_cache = None
         enc = tree["encoder_def"]
         for k in self.image_keys:
             sub = enc[f"encoder_{k}"]
             for leaf, (mod, name) in _CAM_PATHS.items():
-                self.set(self._leaf(k, leaf), sub[mod][name])
+                self._set(section, self._leaf(k, leaf), sub[mod][name])
             if "pretrained_encoder" in sub:
                 for leaf, v in trunk_from_flax(sub["pretrained_encoder"]).items():
-                    self.set(leaf, v)
+                    self._set(section, leaf, v)
         for leaf, (mod, name) in _HEAD_PATHS.items():
-            self.set(leaf, tree[mod][name])
+            self._set(section, leaf, tree[mod][name])
         return self
 
     def replace(self, params=None, **kw):
-        if kw:
-            raise NotImplementedError(list(kw))
+        bad = set(kw) - ({"step", "opt_state"} if self.trainable else set())
+        if bad:
+            raise NotImplementedError(sorted(bad))
         if params is not None:
             self.load_params(params)
+        if kw:
+            self.load_state_dict(kw)
         return self
+
+    # ---- training state (flax TrainState fields, reward_classifier.py:61-66)
+    def _need_training(self):
+        if not self.trainable:
+            raise NotImplementedError("classifier training needs create_classifier(..., trainable=True)")
+
+    @property
+    def step(self) -> int:
+        self._need_training()
+        out = C.c_int64()
+        _lib.check(self.L.serl_classifier_train_get_step(self._h, C.byref(out)))
+        return int(out.value)
+
+    @property
+    def opt_state(self):
+        self._need_training()
+        return (ScaleByAdamState(np.int32(self.step), self._export("opt/mu"), self._export("opt/nu")), EmptyState())
+
+    def state_dict(self) -> dict:
+        """flax.serialization.to_state_dict(TrainState) -- what checkpoints.save_checkpoint stores: {step, params,
+        opt_state: {"0": {count, mu, nu}, "1": {}}} (apply_fn and tx are not pytree nodes)."""
+        adam, _ = self.opt_state
+        return {"step": np.int32(self.step), "params": self.params,
+                "opt_state": {"0": {"count": adam.count, "mu": adam.mu, "nu": adam.nu}, "1": {}}}
+
+    def load_state_dict(self, sd: dict):
+        self._need_training()
+        if sd.get("params") is not None:
+            self.load_params(sd["params"])
+        opt = sd.get("opt_state")
+        if opt is not None:
+            adam = opt[0] if isinstance(opt, (tuple, list)) else opt["0"]
+            mu, nu = (adam.mu, adam.nu) if hasattr(adam, "mu") else (adam["mu"], adam["nu"])
+            self.load_params(mu, "opt/mu")
+            self.load_params(nu, "opt/nu")
+        if sd.get("step") is not None:
+            _lib.check(self.L.serl_classifier_train_set_step(self._h, int(np.asarray(sd["step"]))))
+        return self
+
+    def _stream(self):
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _device_frames(self, observations):
+        """{image_key: u8 (T=1, H, W, 3) or (B, T=1, H, W, 3), host or device} -> (u8[n_cam][n][H][W][3] on the device, batched)"""
+        dev = torch.device("cuda", self.device)
+        frames, batched = [], None
+        for k in self.image_keys:
+            x = torch.as_tensor(observations[k])
+            if x.dtype != torch.uint8:
+                raise TypeError(f"observation '{k}' must be uint8 (got {x.dtype})")
+            batched = x.dim() == 5 if batched is None else batched
+            x = x if batched else x[None]
+            if x.shape[1] != 1:
+                raise NotImplementedError("frame stacking T > 1 is not supported")
+            frames.append(x[:, 0].to(dev))
+        return _stacked(frames), batched
+
+    def _dropout_args(self, n, key, masks, dev):
+        """(device keep-mask buffer or None, host keys) of the two Dropout layers.  masks: optional injected keep-masks
+        {image key: u8[n, 4096], "head": u8[n, 256]} (parity tests); by default they are drawn from `key` in the kernels."""
+        keys = np.ascontiguousarray(dropout_keys(np.zeros(2, np.uint32) if key is None else key, self.image_keys).reshape(-1))
+        if masks is None:
+            if key is None:
+                raise ValueError("train=True needs rngs={'dropout': key} or injected masks")
+            return None, keys
+        parts = [torch.as_tensor(np.asarray(masks[k], np.uint8)).reshape(-1) for k in self.image_keys]
+        parts.append(torch.as_tensor(np.asarray(masks["head"], np.uint8)).reshape(-1))
+        buf = torch.cat(parts).to(dev).contiguous()
+        if buf.numel() != n * (len(self.image_keys) * SLE_DIM + HIDDEN):
+            raise ValueError("injected Dropout masks must be u8[n, 4096] per camera and u8[n, 256] for 'head'")
+        return buf, keys
+
+    def train_logits(self, observations, key=None, masks=None) -> np.ndarray:
+        """apply_fn(..., train=True, rngs={"dropout": key}): logits with both Dropout layers active, no update -> (B, 1)"""
+        self._need_training()
+        fr, batched = self._device_frames(observations)
+        n = fr.shape[1]
+        mbuf, keys = self._dropout_args(n, key, masks, fr.device)
+        out = torch.empty((n,), dtype=torch.float32, device=fr.device)
+        _lib.check(self.L.serl_classifier_train_forward(self._h, C.c_void_p(fr.data_ptr()), n,
+                                                        None if mbuf is None else C.c_void_p(mbuf.data_ptr()),
+                                                        keys.ctypes.data_as(C.c_void_p), C.c_void_p(out.data_ptr()), self._stream()))
+        o = out.cpu().numpy().reshape(n, 1)
+        return o if batched else o[0]
+
+    def train_step(self, batch, key, masks=None):
+        """train_reward_classifier.py:122-137 on this classifier: batch = {"data": observations (B, 1, H, W, 3) u8 (host or
+        device), "labels": (B, 1)}.  Returns (self, loss, train_accuracy) -- 0-d device tensors, read when used."""
+        self._need_training()
+        fr, _ = self._device_frames(batch["data"])
+        n = fr.shape[1]
+        lab = batch["labels"]
+        lab = torch.as_tensor(lab if torch.is_tensor(lab) else np.asarray(lab, np.float32), dtype=torch.float32)
+        lab = lab.reshape(-1).to(fr.device).contiguous()
+        if lab.numel() != n:
+            raise ValueError(f"labels hold {lab.numel()} values for {n} observations")
+        mbuf, keys = self._dropout_args(n, key, masks, fr.device)
+        s = self._stream()
+        _lib.check(self.L.serl_classifier_train_step(self._h, C.c_void_p(fr.data_ptr()), n, C.c_void_p(lab.data_ptr()),
+                                                     None if mbuf is None else C.c_void_p(mbuf.data_ptr()),
+                                                     keys.ctypes.data_as(C.c_void_p), s))
+        info = torch.empty(2, dtype=torch.float32, device=fr.device)
+        _lib.check(self.L.serl_classifier_read_train_info(self._h, C.c_void_p(info.data_ptr()), s))
+        self._params_cache = None
+        self._inflight = (fr, lab, mbuf)   # (alive until the stream has consumed them)
+        return self, info[0], info[1]
 
     # ---- forward
     def logits(self, observations) -> np.ndarray:
@@ -185,25 +359,28 @@ class Classifier:
             out[lo:hi, 0] = d_out.cpu().numpy()
         return out if batched else out[0]
 
-    def apply_fn(self, variables, observations, train=False, **kw):
-        if train:
-            raise NotImplementedError("classifier training is outside the MI355X hot path")
+    def apply_fn(self, variables, observations, train=False, rngs=None, masks=None, **kw):
+        if train and not self.trainable:
+            raise NotImplementedError("classifier training needs create_classifier(..., trainable=True)")
         p = None if variables is None else variables.get("params")
         if p is not None and p is not self._params_cache:    # foreign parameters: load them first
             self.load_params(p)
+        if train:
+            return self.train_logits(observations, None if rngs is None else rngs.get("dropout"), masks)
         return self.logits(observations)
 
     _params_cache = None
 
 
 def create_classifier(key, sample: Dict, image_keys: List[str], pretrained_encoder_path: str = "./resnet10_params.pkl",
-                      max_batch: int = 64, device: int = 0) -> Classifier:
-    """reward_classifier.py:31-90: a freshly initialised classifier whose frozen trunk holds the pretrained ResNet-10."""
+                      max_batch: int = 64, device: int = 0, trainable: bool = False, learning_rate: float = 1e-4) -> Classifier:
+    """reward_classifier.py:31-90: a freshly initialised classifier whose frozen trunk holds the pretrained ResNet-10.
+    trainable=True adds optax.adam(learning_rate)'s state and the train step for batches of up to max_batch rows."""
     from ..utils import init as pinit
     first = np.asarray(sample[image_keys[0]])
     H, W = int(first.shape[-3]), int(first.shape[-2])
     seed = int(np.asarray(key).reshape(-1)[-1]) if not isinstance(key, int) else key
-    c = Classifier(image_keys, H, W, max_batch=max_batch, device=device)
+    c = Classifier(image_keys, H, W, max_batch=max_batch, device=device, trainable=trainable, learning_rate=learning_rate)
     for name, v in pinit.init_classifier(len(image_keys), H, W, seed).items():
         c.set(name, v)
     with open(pretrained_encoder_path, "rb") as f:
@@ -228,3 +405,71 @@ def load_classifier_func(key, sample: Dict, image_keys: List[str], checkpoint_pa
 def _blank_classifier(sample, image_keys):
     first = np.asarray(sample[image_keys[0]])
     return Classifier(image_keys, int(first.shape[-3]), int(first.shape[-2]))
+
+
+def train_step(state: Classifier, batch: Dict, key, masks=None):
+    """train_reward_classifier.py:122-137 (the jitted train_step): loss = mean(optax.sigmoid_binary_cross_entropy(
+    apply_fn(params, data, rngs={"dropout": key}, train=True), labels)), one optax.adam step, and train_accuracy =
+    mean((sigmoid(apply_fn(params, data, train=False)) >= 0.5) == labels) with the pre-update parameters.
+    Returns (state, loss, train_accuracy); state is updated in place."""
+    return state.train_step(batch, key, masks=masks)
+
+
+def _demo_sample(store, image_keys):
+    H, W, _ = store._img_shape
+    return {k: np.zeros((1, 1, H, W, 3), np.uint8) for k in image_keys}
+
+
+def train_reward_classifier(pos_buffer, neg_buffer, image_keys: List[str], *, batch_size: int = 256, num_epochs: int = 100,
+                            classifier_ckpt_path: Optional[str] = None, pretrained_encoder_path: str = "./resnet10_params.pkl",
+                            init_params: Optional[Dict[str, np.ndarray]] = None, device: int = 0, verbose: bool = True):
+    """The loop of train_reward_classifier.py:54-172 on the HBM data stores (MemoryEfficientReplayBufferDataStore filled with
+    positive / negative demos):
+      rng = PRNGKey(0); rng, _ = split(rng); one shape-only draw from each store (:101-105); rng, key = split(rng);
+      create_classifier(key, ...); per epoch: B/2 indices from each store, sample = concat(pos next_observations,
+      neg observations), rng, key = split(rng) -> batched_random_crop(sample, key, padding=4) (one key: every camera shifts
+      sample i by the same offset), labels [1]*B/2 + [0]*B/2, rng, key = split(rng) -> train_step;
+      at the end checkpoints.save_checkpoint(classifier_ckpt_path, classifier, step=num_epochs, overwrite=True).
+    The frames go from the stores to the trunk without leaving HBM (serl_rb_gather_crop does the gather and the crop).
+    init_params: optional flat leaves loaded over the fresh classifier (parity tests inject parameters).
+    Returns (classifier, log) with log = {"loss", "accuracy", "pos_idx", "neg_idx", "crop"} per epoch."""
+    from ..agents.batch import DeviceBatch
+    from ..data.data_store import gather_crop
+    image_keys = list(image_keys)
+    half = batch_size // 2
+    rng = J.prngkey(0)
+    rng, _ = J.split(rng)
+    pos_buffer.sample_indices(half)   # next(pos_iterator) / next(neg_iterator): shapes only, but they advance np_random
+    neg_buffer.sample_indices(half)
+    rng, key = J.split(rng)
+    classifier = create_classifier(key, _demo_sample(pos_buffer, image_keys), image_keys, pretrained_encoder_path,
+                                   max_batch=batch_size, device=device, trainable=True)
+    if init_params is not None:
+        classifier.load_flat(init_params)
+    H, W, Cc = pos_buffer._img_shape
+    dbs = [DeviceBatch(half, len(image_keys), H, W, Cc, s._S, s._A, device) for s in (pos_buffer, neg_buffer)]
+    labels = torch.cat([torch.ones(half), torch.zeros(half)]).to(torch.device("cuda", device))
+    log = {"loss": [], "accuracy": [], "pos_idx": [], "neg_idx": [], "crop": []}
+    pending = []
+    for epoch in range(num_epochs):
+        ip, ineg = pos_buffer.sample_indices(half), neg_buffer.sample_indices(half)
+        rng, key = J.split(rng)
+        crop = J.crop_offsets(key, 2 * half, padding=4)
+        gather_crop([(pos_buffer, ip)], None, crop[:half], dbs[0])     # positives: next_observations
+        gather_crop([(neg_buffer, ineg)], crop[half:], None, dbs[1])   # negatives: observations
+        frames = torch.cat([dbs[0].frames[1], dbs[1].frames[0]], dim=1)   # [n_cam][B][H][W][3]
+        rng, key = J.split(rng)
+        data = {k: frames[i][:, None] for i, k in enumerate(image_keys)}
+        classifier, loss, acc = train_step(classifier, {"data": data, "labels": labels}, key)
+        log["pos_idx"].append(ip)
+        log["neg_idx"].append(ineg)
+        log["crop"].append(crop)
+        pending.append((loss, acc))
+        if verbose:
+            print(f"Epoch: {epoch + 1}, Train Loss: {float(loss):.4f}, Train Accuracy: {float(acc):.4f}")
+    log["loss"] = [float(l) for l, _ in pending]
+    log["accuracy"] = [float(a) for _, a in pending]
+    if classifier_ckpt_path is not None:
+        from ..utils.checkpoint import save_checkpoint
+        save_checkpoint(classifier_ckpt_path, classifier, step=num_epochs, overwrite=True)
+    return classifier, log

@@ -40,8 +40,9 @@ def _unpack_ext(code, data):
 
 
 def _own_form(agent):
-    """A train state that writes / reads its own state-dict form (BCAgent's single-optimizer state, agents/bc.py), given
-    as the agent or as its `.state` -- or None."""
+    """A train state that writes / reads its own state-dict form (BCAgent's single-optimizer state, agents/bc.py; the
+    trainable reward classifier's flax TrainState, networks/reward_classifier.py), given as the agent or as its `.state`
+    -- or None."""
     for x in (agent, getattr(agent, "state", None)):
         if x is not None and hasattr(x, "state_dict") and hasattr(x, "load_state_dict"):
             return x
