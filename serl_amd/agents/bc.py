@@ -13,7 +13,6 @@ a learner started from the same seed draws the masks a JAX learner draws.
 from __future__ import annotations
 
 import ctypes as C
-from collections import namedtuple
 from typing import Dict, Iterable, Optional
 
 import numpy as np
@@ -24,11 +23,7 @@ from .. import jaxrng as J
 from .._lib_agent import SerlBcCfg
 from ..data.data_store import LazyBatch, gather_crop
 from .batch import DeviceBatch
-from .flax_tree import bc_paths, bc_shapes, trunk_from_flax
-
-# optax.adam's state (optax/_src/transform.py ScaleByAdamState; base.EmptyState of scale_by_learning_rate)
-ScaleByAdamState = namedtuple("ScaleByAdamState", ["count", "mu", "nu"])
-EmptyState = namedtuple("EmptyState", [])
+from .flax_tree import EmptyState, ScaleByAdamState, adam_moments, bc_paths, bc_shapes, trunk_from_flax
 
 SLE_DIM = 512 * 8
 
@@ -76,8 +71,7 @@ class BCTrainState:
             a._import("params", sd["params"])
         opt = sd.get("opt_states")
         if opt is not None:
-            adam = opt[0] if isinstance(opt, (tuple, list)) else opt["0"]
-            mu, nu = (adam.mu, adam.nu) if hasattr(adam, "mu") else (adam["mu"], adam["nu"])
+            mu, nu = adam_moments(opt)
             a._import("opt/mu", mu)
             a._import("opt/nu", nu)
         if sd.get("step") is not None:

@@ -12,11 +12,28 @@ install is available, so the alias switches below remain for the alternative rea
 """
 from __future__ import annotations
 
+from collections import namedtuple
 from typing import Dict
 
 import numpy as np
 
 from ..utils.init import STAGES, theta_shapes, trunk_shapes
+
+
+# optax.adam's state (optax/_src/transform.py ScaleByAdamState; base.EmptyState of scale_by_learning_rate)
+ScaleByAdamState = namedtuple("ScaleByAdamState", ["count", "mu", "nu"])
+EmptyState = namedtuple("EmptyState", [])
+
+# per-camera encoder head on the frozen trunk: leaf below enc/<i>/ -> path below encoder_<key>
+CAM_PATHS = {"sle": ("SpatialLearnedEmbeddings_0", "kernel"), "dense/kernel": ("Dense_0", "kernel"),
+             "dense/bias": ("Dense_0", "bias"), "ln/scale": ("LayerNorm_0", "scale"), "ln/bias": ("LayerNorm_0", "bias")}
+
+
+def adam_moments(opt):
+    """(mu, nu) of optax.adam's state, given as the (ScaleByAdamState, EmptyState) tuple or in its state-dict form
+    {"0": {"count", "mu", "nu"}, "1": {}}."""
+    adam = opt[0] if isinstance(opt, (tuple, list)) else opt["0"]
+    return (adam.mu, adam.nu) if hasattr(adam, "mu") else (adam["mu"], adam["nu"])
 
 
 def _put(tree, path, value):
@@ -121,12 +138,8 @@ def bc_paths(image_keys):
     for leaf, sub in _trunk_paths().items():
         m[leaf] = enc + (f"encoder_{trunk_owner(image_keys)}", "pretrained_encoder") + sub
     for i, k in enumerate(image_keys):
-        e = enc + (f"encoder_{k}",)
-        m[f"enc/{i}/sle"] = e + ("SpatialLearnedEmbeddings_0", "kernel")
-        m[f"enc/{i}/dense/kernel"] = e + ("Dense_0", "kernel")
-        m[f"enc/{i}/dense/bias"] = e + ("Dense_0", "bias")
-        m[f"enc/{i}/ln/scale"] = e + ("LayerNorm_0", "scale")
-        m[f"enc/{i}/ln/bias"] = e + ("LayerNorm_0", "bias")
+        for leaf, sub in CAM_PATHS.items():
+            m[f"enc/{i}/{leaf}"] = enc + (f"encoder_{k}",) + sub
     m["enc/proprio/dense/kernel"] = enc + ("Dense_0", "kernel")
     m["enc/proprio/dense/bias"] = enc + ("Dense_0", "bias")
     m["enc/proprio/ln/scale"] = enc + ("LayerNorm_0", "scale")

@@ -21,11 +21,6 @@ using namespace serl;
 
 namespace {
 
-struct Leaf {
-  std::string name;
-  long off, count;
-};
-
 struct CamOff { long sle, dW, db, lng, lnb, conv; };   // sle: resnet-pretrained, conv: SmallEncoder
 struct Offs {
   CamOff cam[SERL_MAX_CAMS];
@@ -81,6 +76,7 @@ struct serl_agent {
   Offs o{};
   std::vector<Leaf> theta_leaves, trunk_leaves;
   long trunk_count = 0;
+  TrunkOffsets to{};
   // device memory
   void* arena = nullptr;
   float *trunk = nullptr, *trunk_t = nullptr, *theta = nullptr, *theta_t = nullptr;
@@ -156,20 +152,6 @@ long pad64(long x) { return (x + 63) / 64 * 64; }
 // the parameter-gradient kernels of a phase are always deferred to the end of the phase (issuing them layer by layer was
 // measured 3 % slower at a per-rank batch of 32, equal at 256)
 
-size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
-
-struct Bump {
-  uint8_t* base;
-  size_t off = 0;
-  explicit Bump(void* b) : base((uint8_t*)b) {}
-  template <typename T>
-  T* take(size_t n) {
-    T* p = base ? (T*)(base + off) : nullptr;
-    off += al(n * sizeof(T));
-    return p;
-  }
-};
-
 void build_layout(serl_agent* a) {
   const serl_agent_cfg& c = a->cfg;
   const TrunkDims d = c.n_cam > 0 ? trunk_dims(c.H, c.W) : TrunkDims{};
@@ -180,12 +162,6 @@ void build_layout(serl_agent* a) {
   a->E = a->state_only ? c.state_dim : c.bottleneck * c.n_cam + c.proprio_dim;
   a->XA = a->E + c.act_dim;
   long off = 0;
-  auto leaf = [&](std::vector<Leaf>& v, const std::string& n, long cnt) {
-    v.push_back({n, off, cnt});
-    const long at = off;
-    off += cnt;
-    return at;
-  };
   Offs& o = a->o;
   std::vector<Leaf>& L = a->theta_leaves;
   const long Hd = c.hidden, A = c.act_dim, N = c.ensemble;
@@ -194,103 +170,60 @@ void build_layout(serl_agent* a) {
     if (a->small) {   // per layer [9*cin + 1][cout]: kernel (HWIO) immediately followed by the bias (small_encoder.hip)
       o.cam[k].conv = off;
       for (int l = 0; l < kSmallLayers; ++l) {
-        leaf(L, p + "conv" + std::to_string(l) + "/kernel", 9L * kSmallFeat[l] * kSmallFeat[l + 1]);
-        leaf(L, p + "conv" + std::to_string(l) + "/bias", kSmallFeat[l + 1]);
+        add_leaf(L, off, p + "conv" + std::to_string(l) + "/kernel", 9L * kSmallFeat[l] * kSmallFeat[l + 1]);
+        add_leaf(L, off, p + "conv" + std::to_string(l) + "/bias", kSmallFeat[l + 1]);
       }
       o.cam[k].sle = o.cam[k].conv;
     } else {
-      o.cam[k].sle = leaf(L, p + "sle", (long)a->HW * 512 * c.sle_features);
+      o.cam[k].sle = add_leaf(L, off, p + "sle", (long)a->HW * 512 * c.sle_features);
     }
-    o.cam[k].dW = leaf(L, p + "dense/kernel", (long)a->D * c.bottleneck);
-    o.cam[k].db = leaf(L, p + "dense/bias", c.bottleneck);
-    o.cam[k].lng = leaf(L, p + "ln/scale", c.bottleneck);
-    o.cam[k].lnb = leaf(L, p + "ln/bias", c.bottleneck);
+    o.cam[k].dW = add_leaf(L, off, p + "dense/kernel", (long)a->D * c.bottleneck);
+    o.cam[k].db = add_leaf(L, off, p + "dense/bias", c.bottleneck);
+    o.cam[k].lng = add_leaf(L, off, p + "ln/scale", c.bottleneck);
+    o.cam[k].lnb = add_leaf(L, off, p + "ln/bias", c.bottleneck);
   }
   o.cam_stride = c.n_cam > 1 ? o.cam[1].sle - o.cam[0].sle : off;
-  o.c_w1 = leaf(L, "critic/w1", N * a->XA * Hd);
-  o.c_b1 = leaf(L, "critic/b1", N * Hd);
-  o.c_g1 = leaf(L, "critic/ln1/scale", N * Hd);
-  o.c_be1 = leaf(L, "critic/ln1/bias", N * Hd);
-  o.c_w2 = leaf(L, "critic/w2", N * Hd * Hd);
-  o.c_b2 = leaf(L, "critic/b2", N * Hd);
-  o.c_g2 = leaf(L, "critic/ln2/scale", N * Hd);
-  o.c_be2 = leaf(L, "critic/ln2/bias", N * Hd);
+  o.c_w1 = add_leaf(L, off, "critic/w1", N * a->XA * Hd);
+  o.c_b1 = add_leaf(L, off, "critic/b1", N * Hd);
+  o.c_g1 = add_leaf(L, off, "critic/ln1/scale", N * Hd);
+  o.c_be1 = add_leaf(L, off, "critic/ln1/bias", N * Hd);
+  o.c_w2 = add_leaf(L, off, "critic/w2", N * Hd * Hd);
+  o.c_b2 = add_leaf(L, off, "critic/b2", N * Hd);
+  o.c_g2 = add_leaf(L, off, "critic/ln2/scale", N * Hd);
+  o.c_be2 = add_leaf(L, off, "critic/ln2/bias", N * Hd);
   // DrQ: one Dense(1) head shared by the ensemble (drq.py:201-207); state-only SAC: ensemblize vmaps the whole
   // Critic, so every member has its own head (actor_critic_nets.py:49-73,156-164)
-  o.c_hw = leaf(L, "critic/head/kernel", a->state_only ? N * Hd : Hd);
-  o.c_hb = leaf(L, "critic/head/bias", a->state_only ? N : 1);
+  o.c_hw = add_leaf(L, off, "critic/head/kernel", a->state_only ? N * Hd : Hd);
+  o.c_hb = add_leaf(L, off, "critic/head/bias", a->state_only ? N : 1);
   o.Pa0 = off;
   if (!a->state_only) {
-    o.p_W = leaf(L, "enc/proprio/dense/kernel", (long)c.state_dim * c.proprio_dim);
-    o.p_b = leaf(L, "enc/proprio/dense/bias", c.proprio_dim);
-    o.p_g = leaf(L, "enc/proprio/ln/scale", c.proprio_dim);
-    o.p_be = leaf(L, "enc/proprio/ln/bias", c.proprio_dim);
+    o.p_W = add_leaf(L, off, "enc/proprio/dense/kernel", (long)c.state_dim * c.proprio_dim);
+    o.p_b = add_leaf(L, off, "enc/proprio/dense/bias", c.proprio_dim);
+    o.p_g = add_leaf(L, off, "enc/proprio/ln/scale", c.proprio_dim);
+    o.p_be = add_leaf(L, off, "enc/proprio/ln/bias", c.proprio_dim);
   }
   o.Pc = off;
-  o.a_w1 = leaf(L, "actor/w1", (long)a->E * Hd);
-  o.a_b1 = leaf(L, "actor/b1", Hd);
-  o.a_g1 = leaf(L, "actor/ln1/scale", Hd);
-  o.a_be1 = leaf(L, "actor/ln1/bias", Hd);
-  o.a_w2 = leaf(L, "actor/w2", Hd * Hd);
-  o.a_b2 = leaf(L, "actor/b2", Hd);
-  o.a_g2 = leaf(L, "actor/ln2/scale", Hd);
-  o.a_be2 = leaf(L, "actor/ln2/bias", Hd);
-  o.a_Wm = leaf(L, "actor/mean/kernel", Hd * A);
-  o.a_bm = leaf(L, "actor/mean/bias", A);
-  o.a_Ws = leaf(L, "actor/logstd/kernel", Hd * A);
-  o.a_bs = leaf(L, "actor/logstd/bias", A);
+  o.a_w1 = add_leaf(L, off, "actor/w1", (long)a->E * Hd);
+  o.a_b1 = add_leaf(L, off, "actor/b1", Hd);
+  o.a_g1 = add_leaf(L, off, "actor/ln1/scale", Hd);
+  o.a_be1 = add_leaf(L, off, "actor/ln1/bias", Hd);
+  o.a_w2 = add_leaf(L, off, "actor/w2", Hd * Hd);
+  o.a_b2 = add_leaf(L, off, "actor/b2", Hd);
+  o.a_g2 = add_leaf(L, off, "actor/ln2/scale", Hd);
+  o.a_be2 = add_leaf(L, off, "actor/ln2/bias", Hd);
+  o.a_Wm = add_leaf(L, off, "actor/mean/kernel", Hd * A);
+  o.a_bm = add_leaf(L, off, "actor/mean/bias", A);
+  o.a_Ws = add_leaf(L, off, "actor/logstd/kernel", Hd * A);
+  o.a_bs = add_leaf(L, off, "actor/logstd/bias", A);
   o.Pa1 = off;
-  o.lam = leaf(L, "temp/lagrange", 1);
+  o.lam = add_leaf(L, off, "temp/lagrange", 1);
   o.P = off;
   // trunk
   off = 0;
   a->trunk_count = 0;
   if (a->state_only || a->small) return;   // no frozen trunk
-  std::vector<Leaf>& T = a->trunk_leaves;
-  leaf(T, "trunk/conv_init", 7 * 7 * 3 * 64);
-  leaf(T, "trunk/norm_init/scale", 64);
-  leaf(T, "trunk/norm_init/bias", 64);
-  int cin = 64;
-  for (int i = 0; i < kTrunkStages; ++i) {
-    const int f = kStageFilters[i];
-    const std::string p = "trunk/block" + std::to_string(i) + "/";
-    leaf(T, p + "conv0", 9L * cin * f);
-    leaf(T, p + "gn0/scale", f);
-    leaf(T, p + "gn0/bias", f);
-    leaf(T, p + "conv1", 9L * f * f);
-    leaf(T, p + "gn1/scale", f);
-    leaf(T, p + "gn1/bias", f);
-    if (kStageStride[i] != 1 || cin != f) {
-      leaf(T, p + "proj", (long)cin * f);
-      leaf(T, p + "gnp/scale", f);
-      leaf(T, p + "gnp/bias", f);
-    }
-    cin = f;
-  }
+  a->to = add_trunk_leaves(a->trunk_leaves, off);
   a->trunk_count = off;
-}
-
-const Leaf* find_leaf(const std::vector<Leaf>& v, const char* name) {
-  for (const Leaf& l : v)
-    if (l.name == name) return &l;
-  return nullptr;
-}
-
-void bind_trunk_weights(serl_agent* a) {
-  auto p = [&](const std::string& n) -> const float* {
-    const Leaf* l = find_leaf(a->trunk_leaves, n.c_str());
-    return l ? a->trunk + l->off : nullptr;
-  };
-  a->tw.conv_init = p("trunk/conv_init");
-  a->tw.gn_init_s = p("trunk/norm_init/scale");
-  a->tw.gn_init_b = p("trunk/norm_init/bias");
-  for (int i = 0; i < kTrunkStages; ++i) {
-    const std::string q = "trunk/block" + std::to_string(i) + "/";
-    TrunkWeights::Block& b = a->tw.blk[i];
-    b.conv0 = p(q + "conv0"); b.gn0_s = p(q + "gn0/scale"); b.gn0_b = p(q + "gn0/bias");
-    b.conv1 = p(q + "conv1"); b.gn1_s = p(q + "gn1/scale"); b.gn1_b = p(q + "gn1/bias");
-    b.proj = p(q + "proj"); b.gnp_s = p(q + "gnp/scale"); b.gnp_b = p(q + "gnp/bias");
-  }
 }
 
 // carve everything (pass 1 with base == nullptr measures)
@@ -377,12 +310,6 @@ size_t carve(serl_agent* a, void* base) {
   return b.off;
 }
 
-#define RC(x)            \
-  do {                   \
-    int _rc = (x);       \
-    if (_rc) return _rc; \
-  } while (0)
-
 // K-split of a GEMM launch: as deep as `smax` for latency when the problem is small, but never more
 // workgroups than the budget -- at large per-rank batches the update chain runs beside the trunk of the
 // next batch and every extra workgroup waits for a conv workgroup to retire.
@@ -390,10 +317,7 @@ size_t carve(serl_agent* a, void* base) {
 // agents (or sample_actions on another thread) never see each other's budget.
 int split_for(long agent_budget, int M, int N, int groups, int smax, long budget = 0) {
   if (budget <= 0) budget = agent_budget > 0 ? agent_budget : 512L;
-  const long tiles = (long)cdiv(M, 64) * cdiv(N, 64) * groups;
-  int s = smax;
-  while (s > 1 && tiles * s > budget) s >>= 1;
-  return s;
+  return split_under(M, N, groups, smax, budget);
 }
 
 // ---- EncodingWrapper forward on precomputed trunk features (encoding.py:26-72) ------------------
@@ -439,19 +363,9 @@ int encode_multi(serl_agent* a, const EncJob* jobs, int n, int off, int cnt, hip
     sv[i].K = j.P + o.cam[0].sle;
     sv[i].mask = j.mask ? j.mask + (long)off * a->D : nullptr;
     sv[i].f = e.f;
-    GemmDesc& g = gd[i];
-    g = GemmDesc{};
-    g.A = e.f; g.sAm = a->D; g.sAk = 1; g.sAb = (long)c.batch * a->D;
-    g.B = j.P + o.cam[0].dW; g.sBk = c.bottleneck; g.sBn = 1; g.sBb = o.cam_stride;
-    g.C = a->slabs_lane[i]; g.ldc = c.bottleneck; g.sCz = (long)cnt * c.bottleneck;
-    g.M = cnt; g.N = c.bottleneck; g.K = a->D; g.nbatch = c.n_cam; g.splitk = S;
-    LnFwdArgs& l = lv[i];
-    l = LnFwdArgs{};
-    l.slabs = a->slabs_lane[i]; l.S = S; l.slab_stride = g.sCz;
-    l.bias = j.P + o.cam[0].db; l.gamma = j.P + o.cam[0].lng; l.beta = j.P + o.cam[0].lnb; l.pstride = o.cam_stride;
-    l.rows = c.n_cam * cnt; l.rows_per_group = cnt;
-    l.y = e.enc; l.ld_y = e.ld; l.y_goff = c.bottleneck;
-    l.xhat = e.xhat; l.rstd = e.rstd;
+    cam_dense_ln_args(e.f, (long)c.batch * a->D, a->D, j.P + o.cam[0].dW, j.P + o.cam[0].db, j.P + o.cam[0].lng,
+                      j.P + o.cam[0].lnb, o.cam_stride, c.n_cam, cnt, c.bottleneck, S, a->slabs_lane[i], e.enc, e.ld, e.xhat,
+                      e.rstd, gd[i], lv[i]);
     ProprioArgs& pr = pv[i];
     pr = ProprioArgs{};
     pr.state = a->cur.state + ((long)j.which * Bfull + off) * c.state_dim;
@@ -466,10 +380,7 @@ int encode_multi(serl_agent* a, const EncJob* jobs, int n, int off, int cnt, hip
     for (int i = 0; i < n; ++i) {
       sv[i].gen = jobs[i].gen_mask; sv[i].seed = jobs[i].mask_seed;
       sv[i].row_offset = a->shard_off + off; sv[i].rows_global = a->shard_global ? a->shard_global : Bfull;
-      if (jobs[i].gen_mask == 2) {
-        for (int k = 0; k < c.n_cam; ++k) { sv[i].tf_key[k][0] = jobs[i].tf_key[2 * k]; sv[i].tf_key[k][1] = jobs[i].tf_key[2 * k + 1]; }
-        sv[i].tf_rows = jobs[i].tf_rows; sv[i].tf_row0 = jobs[i].tf_row0;
-      }
+      if (jobs[i].gen_mask == 2) sle_tf_masks(sv[i], jobs[i].tf_key, c.n_cam, jobs[i].tf_rows, jobs[i].tf_row0);
     }
   }
   if (a->small) {   // trainable conv stack + average pool per (parameter vector, observation side); no dropout (pool "avg")
@@ -993,16 +904,12 @@ int serl_agent_create(const serl_agent_cfg* cfg, serl_agent** out) {
   a->cfg = *cfg;
   { const char* e = getenv("SERL_CHAIN_FUSE"); a->fuse = !(e && e[0] == '0'); }
   build_layout(a);
-  const size_t bytes = carve(a, nullptr);
-  hipError_t e = hipMalloc(&a->arena, bytes);
-  if (e != hipSuccess) {
-    set_error("hipMalloc of %zu bytes for the agent arena failed: %s", bytes, hipGetErrorString(e));
+  if (int rc = alloc_zeroed(&a->arena, carve(a, nullptr), "agent arena")) {
     delete a;
-    return SERL_ERR_HIP;
+    return rc;
   }
   carve(a, a->arena);
-  SERL_HIP(hipMemset(a->arena, 0, bytes));
-  if (!a->state_only && !a->small) bind_trunk_weights(a);
+  if (!a->state_only && !a->small) a->tw = trunk_weights(a->trunk, a->to);
   *out = a;
   return SERL_OK;
 }
@@ -1039,11 +946,10 @@ static int flush_trunk_ema(serl_agent* a) {
   return SERL_OK;
 }
 
-// resolves (section, leaf) -> device pointer (nullptr = outside that optimizer's support)
-static int resolve(serl_agent* a, const char* section, const char* leaf, float** ptr, long* count, bool* zero) {
-  *zero = false;
-  const Leaf* t = find_leaf(a->trunk_leaves, leaf);
-  const Leaf* l = t ? t : find_leaf(a->theta_leaves, leaf);
+// resolves (section, leaf) -> device pointer (nullptr = outside that optimizer's support: exact zeros, as the gradient there)
+static int resolve(serl_agent* a, const char* section, const char* leaf, float** ptr, long* count) {
+  const Leaf* t = find(a->trunk_leaves, leaf);
+  const Leaf* l = t ? t : find(a->theta_leaves, leaf);
   SERL_REQUIRE(l != nullptr, "unknown leaf '%s'", leaf);
   *count = l->count;
   const std::string s(section);
@@ -1055,14 +961,13 @@ static int resolve(serl_agent* a, const char* section, const char* leaf, float**
   SERL_REQUIRE(s.rfind("opt/", 0) == 0 && (mu || nu), "unknown section '%s'", section);
   const std::string tx = s.substr(4, s.size() - 7);
   *ptr = nullptr;
-  *zero = true;  // exact zeros outside the support (the gradient there is always exactly zero)
   if (t) return SERL_OK;
   if (tx == "critic") {
-    if (l->off < o.Pc) { *ptr = (mu ? a->m_c : a->v_c) + l->off; *zero = false; }
+    if (l->off < o.Pc) *ptr = (mu ? a->m_c : a->v_c) + l->off;
   } else if (tx == "actor") {
-    if (l->off >= o.Pa0 && l->off < o.Pa1) { *ptr = (mu ? a->m_a : a->v_a) + (l->off - o.Pa0); *zero = false; }
+    if (l->off >= o.Pa0 && l->off < o.Pa1) *ptr = (mu ? a->m_a : a->v_a) + (l->off - o.Pa0);
   } else if (tx == "temperature") {
-    if (l->off == o.lam) { *ptr = mu ? a->m_t : a->v_t; *zero = false; }
+    if (l->off == o.lam) *ptr = mu ? a->m_t : a->v_t;
   } else {
     set_error("unknown optimizer '%s'", tx.c_str());
     return SERL_ERR_INVALID;
@@ -1070,36 +975,31 @@ static int resolve(serl_agent* a, const char* section, const char* leaf, float**
   return SERL_OK;
 }
 
+static constexpr const char* kOutsideSupport = "'%s' of '%s' lies outside the optimizer's support and must be zero";
+
 int serl_agent_set(serl_agent* a, const char* section, const char* leaf, const float* host, int64_t count) {
   SERL_REQUIRE(a && section && leaf && host, "NULL argument");
   SERL_HIP(hipSetDevice(a->cfg.device));
-  float* p; long n; bool zero;
-  int rc = resolve(a, section, leaf, &p, &n, &zero);
-  if (rc) return rc;
+  float* p; long n;
+  RC(resolve(a, section, leaf, &p, &n));
   SERL_REQUIRE(n == count, "leaf '%s' has %ld elements, got %lld", leaf, n, (long long)count);
   if (std::strncmp(leaf, "trunk/", 6) == 0) { SERL_HIP(hipDeviceSynchronize()); RC(flush_trunk_ema(a)); }   // pending EMA steps belong to the old values
-  if (zero) {
-    for (long i = 0; i < n; ++i)
-      SERL_REQUIRE(host[i] == 0.0f, "'%s' of '%s' lies outside the optimizer's support and must be zero", section, leaf);
-    return SERL_OK;
-  }
-  SERL_HIP(hipMemcpy(p, host, sizeof(float) * n, hipMemcpyHostToDevice));
-  if (std::strncmp(leaf, "trunk/", 6) == 0) a->tpk.dirty = true;
+  RC(leaf_copy(p, host, n, hipMemcpyHostToDevice, section, leaf, kOutsideSupport));
+  if (p && std::strncmp(leaf, "trunk/", 6) == 0) a->tpk.dirty = true;
   return SERL_OK;
 }
 
 int serl_agent_get(serl_agent* a, const char* section, const char* leaf, float* host_out, int64_t count) {
   SERL_REQUIRE(a && section && leaf && host_out, "NULL argument");
   SERL_HIP(hipSetDevice(a->cfg.device));
-  float* p; long n; bool zero;
-  int rc = resolve(a, section, leaf, &p, &n, &zero);
-  if (rc) return rc;
+  float* p; long n;
+  RC(resolve(a, section, leaf, &p, &n));
   SERL_REQUIRE(n == count, "leaf '%s' has %ld elements, got %lld", leaf, n, (long long)count);
-  if (zero) { std::memset(host_out, 0, sizeof(float) * n); return SERL_OK; }
-  SERL_HIP(hipDeviceSynchronize());
-  if (std::strncmp(leaf, "trunk/", 6) == 0 && std::strcmp(section, "target_params") == 0) RC(flush_trunk_ema(a));
-  SERL_HIP(hipMemcpy(host_out, p, sizeof(float) * n, hipMemcpyDeviceToHost));
-  return SERL_OK;
+  if (p) {
+    SERL_HIP(hipDeviceSynchronize());
+    if (std::strncmp(leaf, "trunk/", 6) == 0 && std::strcmp(section, "target_params") == 0) RC(flush_trunk_ema(a));
+  }
+  return leaf_copy(host_out, p, n, hipMemcpyDeviceToHost, section, leaf, kOutsideSupport);
 }
 
 int serl_agent_set_trunk_mode(serl_agent* a, int mode) {

@@ -14,23 +14,21 @@
 #include <vector>
 
 #include "heads.h"
-#include "internal.h"
 #include "jaxrng.h"
 
 using namespace serl;
 
 namespace {
-struct BLeaf { std::string name; long off, count; bool train; };
 constexpr int kHidden = 256, kBottleneck = 256, kSleFeatures = 8, kProprio = 64, kMaxAct = 64;
-inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
 }  // namespace
 
 struct serl_bc {
   serl_bc_cfg cfg{};
   int HW = 0, D = 0, Eimg = 0, E = 0;
-  std::vector<BLeaf> leaves;   // trunk, cameras (frozen), then the trainable slice [t0, t0 + nt)
-  long n_params = 0, t0 = 0, nt = 0, cam_stride = 0;
-  long o_sle = 0, o_dW = 0, o_db = 0, o_lng = 0, o_lnb = 0;   // camera 0
+  std::vector<Leaf> leaves;    // trunk, cameras (frozen), then the trainable slice [t0, t0 + nt)
+  long n_params = 0, t0 = 0, nt = 0;
+  TrunkOffsets to{};
+  CamHeadOffsets cam{};
   long o_pW = 0, o_pb = 0, o_pg = 0, o_pbe = 0, o_w1 = 0, o_b1 = 0, o_w2 = 0, o_b2 = 0, o_Wm = 0, o_bm = 0, o_Ws = 0, o_bs = 0;
   void* arena = nullptr;
   float* params = nullptr;   // [n_params + 1]: the element behind the trainable slice is adam_ema's (unused) temperature slot
@@ -47,12 +45,6 @@ struct serl_bc {
 
 namespace {
 
-const BLeaf* find(const serl_bc* c, const char* name) {
-  for (const BLeaf& l : c->leaves)
-    if (l.name == name) return &l;
-  return nullptr;
-}
-
 void layout(serl_bc* c) {
   const serl_bc_cfg& g = c->cfg;
   const TrunkDims d = trunk_dims(g.H, g.W);
@@ -60,123 +52,63 @@ void layout(serl_bc* c) {
   c->D = 512 * kSleFeatures;
   c->Eimg = kBottleneck * g.n_cam;
   c->E = c->Eimg + kProprio;
+  std::vector<Leaf>& L = c->leaves;
   long off = 0;
-  auto leaf = [&](const std::string& n, long cnt, bool train) {
-    c->leaves.push_back({n, off, cnt, train});
-    const long at = off;
-    off += cnt;
-    return at;
-  };
-  leaf("trunk/conv_init", 7 * 7 * 3 * 64, false);
-  leaf("trunk/norm_init/scale", 64, false);
-  leaf("trunk/norm_init/bias", 64, false);
-  int cin = 64;
-  for (int i = 0; i < kTrunkStages; ++i) {
-    const int f = kStageFilters[i];
-    const std::string p = "trunk/block" + std::to_string(i) + "/";
-    leaf(p + "conv0", 9L * cin * f, false); leaf(p + "gn0/scale", f, false); leaf(p + "gn0/bias", f, false);
-    leaf(p + "conv1", 9L * f * f, false); leaf(p + "gn1/scale", f, false); leaf(p + "gn1/bias", f, false);
-    if (kStageStride[i] != 1 || cin != f) {
-      leaf(p + "proj", (long)cin * f, false); leaf(p + "gnp/scale", f, false); leaf(p + "gnp/bias", f, false);
-    }
-    cin = f;
-  }
-  long cam0 = 0;
-  for (int k = 0; k < g.n_cam; ++k) {
-    const std::string p = "enc/" + std::to_string(k) + "/";
-    const long s = leaf(p + "sle", (long)c->HW * 512 * kSleFeatures, false);
-    const long dW = leaf(p + "dense/kernel", (long)c->D * kBottleneck, false);
-    const long db = leaf(p + "dense/bias", kBottleneck, false);
-    const long lg = leaf(p + "ln/scale", kBottleneck, false);
-    const long lb = leaf(p + "ln/bias", kBottleneck, false);
-    if (k == 0) { cam0 = s; c->o_sle = s; c->o_dW = dW; c->o_db = db; c->o_lng = lg; c->o_lnb = lb; }
-    if (k == 1) c->cam_stride = s - cam0;
-  }
-  if (g.n_cam == 1) c->cam_stride = off - cam0;
+  c->to = add_trunk_leaves(L, off);
+  c->cam = add_cam_head_leaves(L, off, g.n_cam, (long)c->HW * 512 * kSleFeatures, c->D, kBottleneck);
   off = (off + 3) & ~3L;   // (16-byte aligned trainable slice)
   c->t0 = off;
   const long A = g.act_dim;
-  c->o_pW = leaf("enc/proprio/dense/kernel", (long)g.state_dim * kProprio, true);
-  c->o_pb = leaf("enc/proprio/dense/bias", kProprio, true);
-  c->o_pg = leaf("enc/proprio/ln/scale", kProprio, true);
-  c->o_pbe = leaf("enc/proprio/ln/bias", kProprio, true);
-  c->o_w1 = leaf("actor/w1", (long)c->E * kHidden, true);
-  c->o_b1 = leaf("actor/b1", kHidden, true);
-  c->o_w2 = leaf("actor/w2", (long)kHidden * kHidden, true);
-  c->o_b2 = leaf("actor/b2", kHidden, true);
-  c->o_Wm = leaf("actor/mean/kernel", kHidden * A, true);
-  c->o_bm = leaf("actor/mean/bias", A, true);
-  c->o_Ws = leaf("actor/logstd/kernel", kHidden * A, true);
-  c->o_bs = leaf("actor/logstd/bias", A, true);
+  c->o_pW = add_leaf(L, off, "enc/proprio/dense/kernel", (long)g.state_dim * kProprio);
+  c->o_pb = add_leaf(L, off, "enc/proprio/dense/bias", kProprio);
+  c->o_pg = add_leaf(L, off, "enc/proprio/ln/scale", kProprio);
+  c->o_pbe = add_leaf(L, off, "enc/proprio/ln/bias", kProprio);
+  c->o_w1 = add_leaf(L, off, "actor/w1", (long)c->E * kHidden);
+  c->o_b1 = add_leaf(L, off, "actor/b1", kHidden);
+  c->o_w2 = add_leaf(L, off, "actor/w2", (long)kHidden * kHidden);
+  c->o_b2 = add_leaf(L, off, "actor/b2", kHidden);
+  c->o_Wm = add_leaf(L, off, "actor/mean/kernel", kHidden * A);
+  c->o_bm = add_leaf(L, off, "actor/mean/bias", A);
+  c->o_Ws = add_leaf(L, off, "actor/logstd/kernel", kHidden * A);
+  c->o_bs = add_leaf(L, off, "actor/logstd/bias", A);
   c->nt = off - c->t0;
   c->n_params = off;
 }
 
-int split_under(int M, int N, int groups, int smax) {   // K-split so that about 512 workgroups are in flight
-  const long tiles = (long)cdiv(M, 64) * cdiv(N, 64) * groups;
-  int s = smax;
-  while (s > 1 && tiles * s > 512) s >>= 1;
-  return s;
-}
-
 size_t carve(serl_bc* c, uint8_t* base) {
   const serl_bc_cfg& g = c->cfg;
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    uint8_t* p = base ? base + off : nullptr;
-    off += al256(bytes);
-    return p;
-  };
+  Bump b(base);
   const long n = g.max_batch, A = g.act_dim;
-  c->params = (float*)take((size_t)(c->n_params + 1) * 4);
-  c->m = (float*)take((size_t)(c->nt + 1) * 4);
-  c->v = (float*)take((size_t)(c->nt + 1) * 4);
-  c->G = (float*)take((size_t)c->nt * 4);
-  c->info = (float*)take(2 * 4);
-  uint8_t* pk = take(trunk_packed_bytes());
-  uint8_t* ws = take(trunk_workspace_bytes(g.n_cam * g.max_batch, g.H, g.W));
-  c->feats = (float*)take((size_t)g.n_cam * n * c->HW * 512 * 4);
-  c->f = (float*)take((size_t)g.n_cam * n * c->D * 4);
+  c->params = b.take<float>(c->n_params + 1);
+  c->m = b.take<float>(c->nt + 1);
+  c->v = b.take<float>(c->nt + 1);
+  c->G = b.take<float>(c->nt);
+  c->info = b.take<float>(2);
+  uint8_t* pk = b.take<uint8_t>(trunk_packed_bytes());
+  uint8_t* ws = b.take<uint8_t>(trunk_workspace_bytes(g.n_cam * g.max_batch, g.H, g.W));
+  c->feats = b.take<float>((size_t)g.n_cam * n * c->HW * 512);
+  c->f = b.take<float>((size_t)g.n_cam * n * c->D);
   c->slabs_cap = (long)std::max(32 * g.n_cam, 8) * n * kBottleneck;
-  c->slabs = (float*)take((size_t)c->slabs_cap * 4);
-  c->enc = (float*)take((size_t)n * c->E * 4);
-  c->pxhat = (float*)take((size_t)n * kProprio * 4);
-  c->prstd = (float*)take((size_t)n * 4);
-  c->h1 = (float*)take((size_t)n * kHidden * 4);
-  c->h2 = (float*)take((size_t)n * kHidden * 4);
-  c->mu = (float*)take((size_t)n * A * 4);
-  c->dhead = (float*)take((size_t)2 * n * A * 4);
-  c->dpre1 = (float*)take((size_t)n * kHidden * 4);
-  c->dpre2 = (float*)take((size_t)n * kHidden * 4);
-  c->dprop = (float*)take((size_t)n * kProprio * 4);
-  c->dpp = (float*)take((size_t)n * kProprio * 4);
-  c->dgp = (float*)take((size_t)n * kProprio * 4);
+  c->slabs = b.take<float>(c->slabs_cap);
+  c->enc = b.take<float>(n * c->E);
+  c->pxhat = b.take<float>(n * kProprio);
+  c->prstd = b.take<float>(n);
+  c->h1 = b.take<float>(n * kHidden);
+  c->h2 = b.take<float>(n * kHidden);
+  c->mu = b.take<float>(n * A);
+  c->dhead = b.take<float>(2 * n * A);
+  c->dpre1 = b.take<float>(n * kHidden);
+  c->dpre2 = b.take<float>(n * kHidden);
+  c->dprop = b.take<float>(n * kProprio);
+  c->dpp = b.take<float>(n * kProprio);
+  c->dgp = b.take<float>(n * kProprio);
   if (base) {
     trunk_packed_bind(c->tpk, pk);
     trunk_workspace_bind(c->tws, ws, g.n_cam * g.max_batch, g.H, g.W);
-    auto p = [&](const std::string& nm) -> const float* {
-      const BLeaf* l = find(c, nm.c_str());
-      return l ? c->params + l->off : nullptr;
-    };
-    c->tw.conv_init = p("trunk/conv_init");
-    c->tw.gn_init_s = p("trunk/norm_init/scale");
-    c->tw.gn_init_b = p("trunk/norm_init/bias");
-    for (int i = 0; i < kTrunkStages; ++i) {
-      const std::string q = "trunk/block" + std::to_string(i) + "/";
-      TrunkWeights::Block& b = c->tw.blk[i];
-      b.conv0 = p(q + "conv0"); b.gn0_s = p(q + "gn0/scale"); b.gn0_b = p(q + "gn0/bias");
-      b.conv1 = p(q + "conv1"); b.gn1_s = p(q + "gn1/scale"); b.gn1_b = p(q + "gn1/bias");
-      b.proj = p(q + "proj"); b.gnp_s = p(q + "gnp/scale"); b.gnp_b = p(q + "gnp/bias");
-    }
+    c->tw = trunk_weights(c->params, c->to);
   }
-  return off;
+  return b.off;
 }
-
-#define RC(x)            \
-  do {                   \
-    int _rc = (x);       \
-    if (_rc) return _rc; \
-  } while (0)
 
 // ---- new kernels ------------------------------------------------------------------------------
 // Plain Dense -> tanh (mlp.py:26-34 with use_layer_norm=False): y[r][c] = tanh(bias[c] + sum_s slab[s][r][c]), the K-split
@@ -300,30 +232,20 @@ int forward(serl_bc* c, const uint8_t* frames, const float* state, int n, const 
   const int A = g.act_dim;
   RC(trunk_forward(c->tw, c->tws, frames, g.n_cam * n, c->feats, st, &c->tpk));
   SleFwdArgs sv{};
-  sv.x = c->feats; sv.K = P + c->o_sle; sv.mask = mask; sv.f = c->f;
-  if (!mask && mask_keys) {
-    sv.gen = 2;
-    for (int k = 0; k < g.n_cam; ++k) { sv.tf_key[k][0] = mask_keys[2 * k]; sv.tf_key[k][1] = mask_keys[2 * k + 1]; }
-    sv.tf_rows = n; sv.tf_row0 = 0;
-  }
+  sv.x = c->feats; sv.K = P + c->cam.sle; sv.mask = mask; sv.f = c->f;
+  if (!mask && mask_keys) sle_tf_masks(sv, mask_keys, g.n_cam, n, 0);
   ProprioArgs pv{};
   pv.state = state; pv.W = P + c->o_pW; pv.b = P + c->o_pb; pv.gamma = P + c->o_pg; pv.beta = P + c->o_pbe;
   pv.y = c->enc + c->Eimg; pv.ld_y = c->E; pv.xhat = c->pxhat; pv.rstd = c->prstd;
-  RC(sle_proprio_fwd_multi(&sv, &pv, 1, 1.0f - g.dropout, n, c->HW, 512, g.n_cam, (long)n * c->HW * 512, c->cam_stride,
+  RC(sle_proprio_fwd_multi(&sv, &pv, 1, 1.0f - g.dropout, n, c->HW, 512, g.n_cam, (long)n * c->HW * 512, c->cam.stride,
                            (long)n * c->D, (long)n * c->D, g.state_dim, st));
   // bottleneck Dense (K-split) -> LayerNorm -> tanh per camera, side by side in enc
   const int S0 = split_under(n, kBottleneck, g.n_cam, 32);
-  GemmDesc g0{};
-  g0.A = c->f; g0.sAm = c->D; g0.sAk = 1; g0.sAb = (long)n * c->D;
-  g0.B = P + c->o_dW; g0.sBk = kBottleneck; g0.sBn = 1; g0.sBb = c->cam_stride;
-  g0.C = c->slabs; g0.ldc = kBottleneck; g0.sCz = (long)n * kBottleneck;
-  g0.M = n; g0.N = kBottleneck; g0.K = c->D; g0.nbatch = g.n_cam; g0.splitk = S0;
+  GemmDesc g0;
+  LnFwdArgs l0;
+  cam_dense_ln_args(c->f, (long)n * c->D, c->D, P + c->cam.dW, P + c->cam.db, P + c->cam.lng, P + c->cam.lnb, c->cam.stride,
+                    g.n_cam, n, kBottleneck, S0, c->slabs, c->enc, c->E, nullptr, nullptr, g0, l0);
   RC(gemm_f32_multi(&g0, 1, st));
-  LnFwdArgs l0{};
-  l0.slabs = c->slabs; l0.S = S0; l0.slab_stride = g0.sCz;
-  l0.bias = P + c->o_db; l0.gamma = P + c->o_lng; l0.beta = P + c->o_lnb; l0.pstride = c->cam_stride;
-  l0.rows = g.n_cam * n; l0.rows_per_group = n;
-  l0.y = c->enc; l0.ld_y = c->E; l0.y_goff = kBottleneck;
   RC(ln_tanh_fwd_multi(&l0, 1, kBottleneck, st));
   // MLP: Dense(256) -> tanh, twice (activate_final)
   const int S1 = split_under(n, kHidden, 1, 8);
@@ -374,19 +296,19 @@ int check_batch(serl_bc* c, const serl_batch* b) {
   return SERL_OK;
 }
 
-// (section, leaf) -> device pointer; *zero: a frozen leaf's Adam moment (always zero, not stored)
-int resolve(serl_bc* c, const char* section, const char* leaf, float** ptr, long* count, bool* zero) {
-  const BLeaf* l = find(c, leaf);
+// (section, leaf) -> device pointer; nullptr: a frozen leaf's Adam moment (always zero, not stored)
+int resolve(serl_bc* c, const char* section, const char* leaf, float** ptr, long* count) {
+  const Leaf* l = find(c->leaves, leaf);
   SERL_REQUIRE(l, "unknown BC leaf '%s'", leaf);
   *count = l->count;
-  *zero = false;
   const std::string s = section;
   if (s == "params") { *ptr = c->params + l->off; return SERL_OK; }
   SERL_REQUIRE(s == "opt/mu" || s == "opt/nu", "unknown BC section '%s' (params, opt/mu, opt/nu)", section);
-  if (!l->train) { *ptr = nullptr; *zero = true; return SERL_OK; }
-  *ptr = (s == "opt/mu" ? c->m : c->v) + (l->off - c->t0);
+  *ptr = l->off < c->t0 ? nullptr : (s == "opt/mu" ? c->m : c->v) + (l->off - c->t0);
   return SERL_OK;
 }
+
+constexpr const char* kFrozenMoment = "'%s' of the frozen leaf '%s' must be zero";
 
 }  // namespace
 
@@ -403,13 +325,10 @@ int serl_bc_create(const serl_bc_cfg* cfg, serl_bc** out) {
   serl_bc* c = new serl_bc();
   c->cfg = *cfg;
   layout(c);
-  const size_t bytes = carve(c, nullptr);
-  if (hipMalloc(&c->arena, bytes) != hipSuccess) {
+  if (int rc = alloc_zeroed(&c->arena, carve(c, nullptr), "BC arena")) {
     delete c;
-    serl::set_error("hipMalloc of %zu bytes failed", bytes);
-    return SERL_ERR_HIP;
+    return rc;
   }
-  SERL_HIP(hipMemset(c->arena, 0, bytes));
   carve(c, (uint8_t*)c->arena);
   *out = c;
   return SERL_OK;
@@ -426,10 +345,10 @@ int serl_bc_num_leaves(serl_bc* c) { return c ? (int)c->leaves.size() : 0; }
 
 int serl_bc_leaf_info(serl_bc* c, int i, char* name_out, int name_cap, int64_t* count, int* trainable) {
   SERL_REQUIRE(c && i >= 0 && i < (int)c->leaves.size(), "leaf index %d out of range", i);
-  const BLeaf& l = c->leaves[i];
+  const Leaf& l = c->leaves[i];
   if (name_out && name_cap > 0) snprintf(name_out, name_cap, "%s", l.name.c_str());
   if (count) *count = l.count;
-  if (trainable) *trainable = l.train ? 1 : 0;
+  if (trainable) *trainable = l.off >= c->t0 ? 1 : 0;
   return SERL_OK;
 }
 
@@ -437,15 +356,10 @@ int serl_bc_set(serl_bc* c, const char* section, const char* leaf, const float* 
   SERL_REQUIRE(c && section && leaf && host, "NULL argument");
   float* p = nullptr;
   long n = 0;
-  bool zero = false;
-  RC(resolve(c, section, leaf, &p, &n, &zero));
+  RC(resolve(c, section, leaf, &p, &n));
   SERL_REQUIRE(count == n, "leaf '%s' has %ld elements, got %ld", leaf, n, (long)count);
-  if (zero) {   // the moments of a frozen leaf are zero by construction
-    for (long i = 0; i < n; ++i) SERL_REQUIRE(host[i] == 0.f, "'%s' of the frozen leaf '%s' must be zero", section, leaf);
-    return SERL_OK;
-  }
   SERL_HIP(hipSetDevice(c->cfg.device));
-  SERL_HIP(hipMemcpy(p, host, (size_t)n * 4, hipMemcpyHostToDevice));
+  RC(leaf_copy(p, host, n, hipMemcpyHostToDevice, section, leaf, kFrozenMoment));
   if (std::string(leaf).rfind("trunk/", 0) == 0 && std::string(section) == "params") c->tpk.dirty = true;
   return SERL_OK;
 }
@@ -454,16 +368,10 @@ int serl_bc_get(serl_bc* c, const char* section, const char* leaf, float* host_o
   SERL_REQUIRE(c && section && leaf && host_out, "NULL argument");
   float* p = nullptr;
   long n = 0;
-  bool zero = false;
-  RC(resolve(c, section, leaf, &p, &n, &zero));
+  RC(resolve(c, section, leaf, &p, &n));
   SERL_REQUIRE(count == n, "leaf '%s' has %ld elements, got %ld", leaf, n, (long)count);
-  if (zero) {
-    for (long i = 0; i < n; ++i) host_out[i] = 0.f;
-    return SERL_OK;
-  }
   SERL_HIP(hipSetDevice(c->cfg.device));
-  SERL_HIP(hipMemcpy(host_out, p, (size_t)n * 4, hipMemcpyDeviceToHost));
-  return SERL_OK;
+  return leaf_copy(host_out, p, n, hipMemcpyDeviceToHost, section, leaf, kFrozenMoment);
 }
 
 int serl_bc_set_step(serl_bc* c, int64_t step) {
@@ -550,18 +458,8 @@ int serl_bc_update(serl_bc* c, const serl_batch* batch, const uint8_t* dev_masks
   };
   RC(gemm_f32_multi(wgs, 5, st));
   // optax.adam(lr) over the trainable slice (bc.py:139 via common.py:170-220); one count, no schedule, no clip
-  const int64_t t = c->step + 1;
-  AdamArgs ad{};
-  ad.theta = c->params + c->t0; ad.theta_target = nullptr;
-  ad.P = c->nt + 1; ad.Pc = 0; ad.Pa0 = 0; ad.Pa1 = c->nt;
-  ad.g_actor = c->G; ad.m_a = c->m; ad.v_a = c->v;
-  ad.m_t = c->m + c->nt; ad.v_t = c->v + c->nt;   // the temperature slot adam_ema keeps at P - 1: never touched (g = m = v = 0)
-  ad.actor_on = 1;
-  ad.lr_a = g.lr;
-  ad.bc1 = 1.0f - powf(0.9f, (float)t);
-  ad.bc2 = 1.0f - powf(0.999f, (float)t);
-  RC(adam_ema(ad, st));
-  c->step = t;
+  RC(adam_ema(adam_slice(c->params + c->t0, c->nt, c->G, c->m, c->v, g.lr, c->step + 1), st));
+  c->step += 1;
   return SERL_OK;
 }
 

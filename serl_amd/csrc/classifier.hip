@@ -10,15 +10,12 @@
 #include <vector>
 
 #include "heads.h"
-#include "internal.h"
 #include "jaxrng.h"
 
 using namespace serl;
 
 namespace {
-struct CLeaf { std::string name; long off, count; };
 constexpr int kHidden = 256, kBottleneck = 256, kSleFeatures = 8, kSleSplit = 8;
-inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 // Opt-in training workspace (serl_classifier_train_init): optax.adam's moments and the gradient of the trainable slice
 // [t0, n_params) -- every camera head and the classifier head; the frozen trunk has none -- plus the activations of a train
@@ -47,9 +44,11 @@ struct ClsTrain {
 struct serl_classifier {
   serl_classifier_cfg cfg{};
   int HW = 0, D = 0, E = 0;
-  std::vector<CLeaf> leaves;      // trunk leaves first, then the heads; offsets into `params`
-  long n_params = 0, cam_stride = 0;
-  long o_sle = 0, o_dW = 0, o_db = 0, o_lng = 0, o_lnb = 0, o_w1 = 0, o_b1 = 0, o_g1 = 0, o_be1 = 0, o_w2 = 0, o_b2 = 0;
+  std::vector<Leaf> leaves;       // trunk leaves first, then the heads; offsets into `params`
+  long n_params = 0;
+  TrunkOffsets to{};
+  CamHeadOffsets cam{};
+  long o_w1 = 0, o_b1 = 0, o_g1 = 0, o_be1 = 0, o_w2 = 0, o_b2 = 0;
   void* arena = nullptr;
   float* params = nullptr;
   TrunkWeights tw{};
@@ -63,103 +62,45 @@ struct serl_classifier {
 
 namespace {
 
-const CLeaf* find(const serl_classifier* c, const char* name) {
-  for (const CLeaf& l : c->leaves)
-    if (l.name == name) return &l;
-  return nullptr;
-}
-
 void layout(serl_classifier* c) {
   const serl_classifier_cfg& g = c->cfg;
   const TrunkDims d = trunk_dims(g.H, g.W);
   c->HW = d.h[5] * d.w[5];
   c->D = 512 * kSleFeatures;
   c->E = kBottleneck * g.n_cam;
+  std::vector<Leaf>& L = c->leaves;
   long off = 0;
-  auto leaf = [&](const std::string& n, long cnt) {
-    c->leaves.push_back({n, off, cnt});
-    const long at = off;
-    off += cnt;
-    return at;
-  };
-  leaf("trunk/conv_init", 7 * 7 * 3 * 64);
-  leaf("trunk/norm_init/scale", 64);
-  leaf("trunk/norm_init/bias", 64);
-  int cin = 64;
-  for (int i = 0; i < kTrunkStages; ++i) {
-    const int f = kStageFilters[i];
-    const std::string p = "trunk/block" + std::to_string(i) + "/";
-    leaf(p + "conv0", 9L * cin * f); leaf(p + "gn0/scale", f); leaf(p + "gn0/bias", f);
-    leaf(p + "conv1", 9L * f * f); leaf(p + "gn1/scale", f); leaf(p + "gn1/bias", f);
-    if (kStageStride[i] != 1 || cin != f) { leaf(p + "proj", (long)cin * f); leaf(p + "gnp/scale", f); leaf(p + "gnp/bias", f); }
-    cin = f;
-  }
-  long cam0 = 0;
-  for (int k = 0; k < g.n_cam; ++k) {
-    const std::string p = "enc/" + std::to_string(k) + "/";
-    const long s = leaf(p + "sle", (long)c->HW * 512 * kSleFeatures);
-    const long dW = leaf(p + "dense/kernel", (long)c->D * kBottleneck);
-    const long db = leaf(p + "dense/bias", kBottleneck);
-    const long lg = leaf(p + "ln/scale", kBottleneck);
-    const long lb = leaf(p + "ln/bias", kBottleneck);
-    if (k == 0) { cam0 = s; c->o_sle = s; c->o_dW = dW; c->o_db = db; c->o_lng = lg; c->o_lnb = lb; }
-    if (k == 1) c->cam_stride = s - cam0;
-  }
-  if (g.n_cam == 1) c->cam_stride = off - cam0;
-  c->o_w1 = leaf("head/dense0/kernel", (long)c->E * kHidden);
-  c->o_b1 = leaf("head/dense0/bias", kHidden);
-  c->o_g1 = leaf("head/ln/scale", kHidden);
-  c->o_be1 = leaf("head/ln/bias", kHidden);
-  c->o_w2 = leaf("head/dense1/kernel", kHidden);
-  c->o_b2 = leaf("head/dense1/bias", 1);
+  c->to = add_trunk_leaves(L, off);
+  c->cam = add_cam_head_leaves(L, off, g.n_cam, (long)c->HW * 512 * kSleFeatures, c->D, kBottleneck);
+  c->o_w1 = add_leaf(L, off, "head/dense0/kernel", (long)c->E * kHidden);
+  c->o_b1 = add_leaf(L, off, "head/dense0/bias", kHidden);
+  c->o_g1 = add_leaf(L, off, "head/ln/scale", kHidden);
+  c->o_be1 = add_leaf(L, off, "head/ln/bias", kHidden);
+  c->o_w2 = add_leaf(L, off, "head/dense1/kernel", kHidden);
+  c->o_b2 = add_leaf(L, off, "head/dense1/bias", 1);
   c->n_params = off;
-  c->t0 = c->o_sle;
+  c->t0 = c->cam.sle;
   c->nt = off - c->t0;
-}
-
-int split_under(int M, int N, int groups, int smax) {   // K-split so that about 512 workgroups are in flight
-  const long tiles = (long)((M + 63) / 64) * ((N + 63) / 64) * groups;
-  int s = smax;
-  while (s > 1 && tiles * s > 512) s >>= 1;
-  return s;
 }
 
 size_t carve(serl_classifier* c, uint8_t* base) {
   const serl_classifier_cfg& g = c->cfg;
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    uint8_t* p = base ? base + off : nullptr;
-    off += al256(bytes);
-    return p;
-  };
+  Bump b(base);
   const long n = g.max_batch;
-  c->params = (float*)take((size_t)(c->n_params + 1) * 4);   // (+ the slot adam_ema keeps behind a slice: never read here)
-  uint8_t* pk = take(trunk_packed_bytes());
-  uint8_t* ws = take(trunk_workspace_bytes(g.max_batch, g.H, g.W));
-  c->feats = (float*)take((size_t)g.n_cam * n * c->HW * 512 * 4);
-  c->f = (float*)take((size_t)g.n_cam * n * c->D * 4);
-  c->slabs = (float*)take((size_t)32 * g.n_cam * n * kBottleneck * 4);
-  c->enc = (float*)take((size_t)n * c->E * 4);
-  c->h = (float*)take((size_t)n * kHidden * 4);
+  c->params = b.take<float>(c->n_params + 1);   // (+ the slot adam_ema keeps behind a slice: never read here)
+  uint8_t* pk = b.take<uint8_t>(trunk_packed_bytes());
+  uint8_t* ws = b.take<uint8_t>(trunk_workspace_bytes(g.max_batch, g.H, g.W));
+  c->feats = b.take<float>((size_t)g.n_cam * n * c->HW * 512);
+  c->f = b.take<float>((size_t)g.n_cam * n * c->D);
+  c->slabs = b.take<float>((size_t)32 * g.n_cam * n * kBottleneck);
+  c->enc = b.take<float>(n * c->E);
+  c->h = b.take<float>(n * kHidden);
   if (base) {
     trunk_packed_bind(c->tpk, pk);
     trunk_workspace_bind(c->tws, ws, g.max_batch, g.H, g.W);
-    auto p = [&](const std::string& nm) -> const float* {
-      const CLeaf* l = find(c, nm.c_str());
-      return l ? c->params + l->off : nullptr;
-    };
-    c->tw.conv_init = p("trunk/conv_init");
-    c->tw.gn_init_s = p("trunk/norm_init/scale");
-    c->tw.gn_init_b = p("trunk/norm_init/bias");
-    for (int i = 0; i < kTrunkStages; ++i) {
-      const std::string q = "trunk/block" + std::to_string(i) + "/";
-      TrunkWeights::Block& b = c->tw.blk[i];
-      b.conv0 = p(q + "conv0"); b.gn0_s = p(q + "gn0/scale"); b.gn0_b = p(q + "gn0/bias");
-      b.conv1 = p(q + "conv1"); b.gn1_s = p(q + "gn1/scale"); b.gn1_b = p(q + "gn1/bias");
-      b.proj = p(q + "proj"); b.gnp_s = p(q + "gnp/scale"); b.gnp_b = p(q + "gnp/bias");
-    }
+    c->tw = trunk_weights(c->params, c->to);
   }
-  return off;
+  return b.off;
 }
 
 }  // namespace
@@ -174,13 +115,10 @@ int serl_classifier_create(const serl_classifier_cfg* cfg, serl_classifier** out
   serl_classifier* c = new serl_classifier();
   c->cfg = *cfg;
   layout(c);
-  const size_t bytes = carve(c, nullptr);
-  if (hipMalloc(&c->arena, bytes) != hipSuccess) {
+  if (int rc = alloc_zeroed(&c->arena, carve(c, nullptr), "classifier arena")) {
     delete c;
-    serl::set_error("hipMalloc of %zu bytes failed", bytes);
-    return SERL_ERR_HIP;
+    return rc;
   }
-  SERL_HIP(hipMemset(c->arena, 0, bytes));
   carve(c, (uint8_t*)c->arena);
   *out = c;
   return SERL_OK;
@@ -201,7 +139,7 @@ int serl_classifier_num_leaves(serl_classifier* c) { return c ? (int)c->leaves.s
 
 int serl_classifier_leaf_info(serl_classifier* c, int i, char* name_out, int name_cap, int64_t* count) {
   SERL_REQUIRE(c && i >= 0 && i < (int)c->leaves.size(), "leaf index %d out of range", i);
-  const CLeaf& l = c->leaves[i];
+  const Leaf& l = c->leaves[i];
   if (name_out && name_cap > 0) snprintf(name_out, name_cap, "%s", l.name.c_str());
   if (count) *count = l.count;
   return SERL_OK;
@@ -209,7 +147,7 @@ int serl_classifier_leaf_info(serl_classifier* c, int i, char* name_out, int nam
 
 int serl_classifier_set(serl_classifier* c, const char* leaf, const float* host, int64_t count) {
   SERL_REQUIRE(c && leaf && host, "NULL argument");
-  const CLeaf* l = find(c, leaf);
+  const Leaf* l = find(c->leaves, leaf);
   SERL_REQUIRE(l, "unknown classifier leaf '%s'", leaf);
   SERL_REQUIRE(count == l->count, "leaf '%s' has %ld elements, got %ld", leaf, l->count, (long)count);
   SERL_HIP(hipSetDevice(c->cfg.device));
@@ -220,7 +158,7 @@ int serl_classifier_set(serl_classifier* c, const char* leaf, const float* host,
 
 int serl_classifier_get(serl_classifier* c, const char* leaf, float* host_out, int64_t count) {
   SERL_REQUIRE(c && leaf && host_out, "NULL argument");
-  const CLeaf* l = find(c, leaf);
+  const Leaf* l = find(c->leaves, leaf);
   SERL_REQUIRE(l, "unknown classifier leaf '%s'", leaf);
   SERL_REQUIRE(count == l->count, "leaf '%s' has %ld elements, got %ld", leaf, l->count, (long)count);
   SERL_HIP(hipSetDevice(c->cfg.device));
@@ -236,28 +174,19 @@ int serl_classifier_logits(serl_classifier* c, const uint8_t* dev_frames, int n,
   SERL_HIP(hipSetDevice(g.device));
   const size_t fbytes = (size_t)g.H * g.W * 3;
   const long nmax = g.max_batch;
-  for (int k = 0; k < g.n_cam; ++k) {
-    int rc = trunk_forward(c->tw, c->tws, dev_frames + (size_t)k * n * fbytes, n, c->feats + (long)k * nmax * c->HW * 512, st, &c->tpk);
-    if (rc) return rc;
-  }
+  for (int k = 0; k < g.n_cam; ++k)
+    RC(trunk_forward(c->tw, c->tws, dev_frames + (size_t)k * n * fbytes, n, c->feats + (long)k * nmax * c->HW * 512, st, &c->tpk));
   const float* P = c->params;
   // per camera: SpatialLearnedEmbeddings -> Dense(256) (K-split GEMM) -> LayerNorm -> tanh, written side by side
-  SleFwdArgs sv{c->feats, P + c->o_sle, nullptr, c->f};
-  int rc = sle_fwd_multi(&sv, 1, 1.0f, n, c->HW, 512, g.n_cam, nmax * c->HW * 512, c->cam_stride, 0, nmax * c->D, st);
-  if (rc) return rc;
+  SleFwdArgs sv{c->feats, P + c->cam.sle, nullptr, c->f};
+  RC(sle_fwd_multi(&sv, 1, 1.0f, n, c->HW, 512, g.n_cam, nmax * c->HW * 512, c->cam.stride, 0, nmax * c->D, st));
   const int S0 = split_under(n, kBottleneck, g.n_cam, 32);
-  GemmDesc g0{};
-  g0.A = c->f; g0.sAm = c->D; g0.sAk = 1; g0.sAb = nmax * c->D;
-  g0.B = P + c->o_dW; g0.sBk = kBottleneck; g0.sBn = 1; g0.sBb = c->cam_stride;
-  g0.C = c->slabs; g0.ldc = kBottleneck; g0.sCz = (long)n * kBottleneck;
-  g0.M = n; g0.N = kBottleneck; g0.K = c->D; g0.nbatch = g.n_cam; g0.splitk = S0;
-  if ((rc = gemm_f32_multi(&g0, 1, st))) return rc;
-  LnFwdArgs l0{};
-  l0.slabs = c->slabs; l0.S = S0; l0.slab_stride = g0.sCz;
-  l0.bias = P + c->o_db; l0.gamma = P + c->o_lng; l0.beta = P + c->o_lnb; l0.pstride = c->cam_stride;
-  l0.rows = g.n_cam * n; l0.rows_per_group = n;
-  l0.y = c->enc; l0.ld_y = c->E; l0.y_goff = kBottleneck;
-  if ((rc = ln_tanh_fwd_multi(&l0, 1, kBottleneck, st))) return rc;
+  GemmDesc g0;
+  LnFwdArgs l0;
+  cam_dense_ln_args(c->f, nmax * c->D, c->D, P + c->cam.dW, P + c->cam.db, P + c->cam.lng, P + c->cam.lnb, c->cam.stride,
+                    g.n_cam, n, kBottleneck, S0, c->slabs, c->enc, c->E, nullptr, nullptr, g0, l0);
+  RC(gemm_f32_multi(&g0, 1, st));
+  RC(ln_tanh_fwd_multi(&l0, 1, kBottleneck, st));
   // Dense(256) -> LayerNorm -> ReLU -> Dense(1)
   const int S1 = split_under(n, kHidden, 1, 8);
   GemmDesc g1{};
@@ -265,7 +194,7 @@ int serl_classifier_logits(serl_classifier* c, const uint8_t* dev_frames, int n,
   g1.B = P + c->o_w1; g1.sBk = kHidden; g1.sBn = 1; g1.sBb = 0;
   g1.C = c->slabs; g1.ldc = kHidden; g1.sCz = (long)n * kHidden;
   g1.M = n; g1.N = kHidden; g1.K = c->E; g1.nbatch = 1; g1.splitk = S1;
-  if ((rc = gemm_f32_multi(&g1, 1, st))) return rc;
+  RC(gemm_f32_multi(&g1, 1, st));
   LnFwdArgs l1{};
   l1.slabs = c->slabs; l1.S = S1; l1.slab_stride = g1.sCz;
   l1.bias = P + c->o_b1; l1.gamma = P + c->o_g1; l1.beta = P + c->o_be1; l1.pstride = 0;
@@ -288,12 +217,6 @@ int serl_classifier_logits(serl_classifier* c, const uint8_t* dev_frames, int n,
 // [t0, n_params) is stepped.  One frozen-trunk pass serves both forwards.
 // =============================================================================================
 namespace {
-
-#define RC(x)            \
-  do {                   \
-    int _rc = (x);       \
-    if (_rc) return _rc; \
-  } while (0)
 
 __device__ __forceinline__ float cls_softplus(float x) { return fmaxf(x, 0.f) + log1pf(expf(-fabsf(x))); }
 
@@ -426,41 +349,36 @@ __global__ __launch_bounds__(256) void cls_dropout_bwd_kernel(ClsDropArgs a) {
 
 size_t carve_train(serl_classifier* c, ClsTrain* t, uint8_t* base) {
   const serl_classifier_cfg& g = c->cfg;
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    uint8_t* p = base ? base + off : nullptr;
-    off += al256(bytes);
-    return p;
-  };
+  Bump b(base);
   const long n = t->max_batch, nc = g.n_cam;
-  t->m = (float*)take((size_t)(c->nt + 1) * 4);
-  t->v = (float*)take((size_t)(c->nt + 1) * 4);
-  t->G = (float*)take((size_t)c->nt * 4);
-  t->info = (float*)take(2 * 4);
-  uint8_t* ws = take(trunk_workspace_bytes((int)(nc * n), g.H, g.W));
-  t->feats = (float*)take((size_t)nc * n * c->HW * 512 * 4);
-  t->f = (float*)take((size_t)2 * nc * n * c->D * 4);
+  t->m = b.take<float>(c->nt + 1);
+  t->v = b.take<float>(c->nt + 1);
+  t->G = b.take<float>(c->nt);
+  t->info = b.take<float>(2);
+  uint8_t* ws = b.take<uint8_t>(trunk_workspace_bytes((int)(nc * n), g.H, g.W));
+  t->feats = b.take<float>((size_t)nc * n * c->HW * 512);
+  t->f = b.take<float>((size_t)2 * nc * n * c->D);
   t->slabs_cap = 2L * 32 * nc * n * kBottleneck;
-  t->slabs = (float*)take((size_t)t->slabs_cap * 4);
-  t->enc = (float*)take((size_t)2 * n * c->E * 4);
-  t->xhat = (float*)take((size_t)nc * n * kBottleneck * 4);
-  t->rstd = (float*)take((size_t)nc * n * 4);
-  t->logits = (float*)take((size_t)2 * n * 4);
-  t->hxhat = (float*)take((size_t)n * kHidden * 4);
-  t->hdg = (float*)take((size_t)n * kHidden * 4);
-  t->dz = (float*)take((size_t)n * kHidden * 4);
-  t->dw2in = (float*)take((size_t)n * kHidden * 4);
-  t->dlogit = (float*)take((size_t)n * 4);
-  t->rowloss = (float*)take((size_t)n * 4);
-  t->rowcorr = (float*)take((size_t)n * 4);
-  t->denc = (float*)take((size_t)n * c->E * 4);
-  t->dzc = (float*)take((size_t)nc * n * kBottleneck * 4);
-  t->dgc = (float*)take((size_t)nc * n * kBottleneck * 4);
-  t->df = (float*)take((size_t)nc * n * c->D * 4);
-  t->sle_part = (float*)take((size_t)nc * kSleSplit * c->HW * 512 * kSleFeatures * 4);
-  t->ctr = (int*)take((size_t)nc * c->HW * cdiv(512, 256) * 4);
+  t->slabs = b.take<float>(t->slabs_cap);
+  t->enc = b.take<float>((size_t)2 * n * c->E);
+  t->xhat = b.take<float>((size_t)nc * n * kBottleneck);
+  t->rstd = b.take<float>((size_t)nc * n);
+  t->logits = b.take<float>((size_t)2 * n);
+  t->hxhat = b.take<float>((size_t)n * kHidden);
+  t->hdg = b.take<float>((size_t)n * kHidden);
+  t->dz = b.take<float>((size_t)n * kHidden);
+  t->dw2in = b.take<float>((size_t)n * kHidden);
+  t->dlogit = b.take<float>(n);
+  t->rowloss = b.take<float>(n);
+  t->rowcorr = b.take<float>(n);
+  t->denc = b.take<float>((size_t)n * c->E);
+  t->dzc = b.take<float>((size_t)nc * n * kBottleneck);
+  t->dgc = b.take<float>((size_t)nc * n * kBottleneck);
+  t->df = b.take<float>((size_t)nc * n * c->D);
+  t->sle_part = b.take<float>((size_t)nc * kSleSplit * c->HW * 512 * kSleFeatures);
+  t->ctr = b.take<int>((size_t)nc * c->HW * cdiv(512, 256));
   if (base) trunk_workspace_bind(t->tws, ws, (int)(nc * n), g.H, g.W);
-  return off;
+  return b.off;
 }
 
 constexpr float kKeep = 0.9f;   // nn.Dropout(0.1): keep probability 1 - 0.1
@@ -478,33 +396,18 @@ int train_forward(serl_classifier* c, const uint8_t* frames, int n, const float*
   RC(trunk_forward(c->tw, t->tws, frames, nc * n, t->feats, st, &c->tpk));
   // SpatialLearnedEmbeddings (+ Dropout keep-mask on instance 0) of both instances in one launch
   SleFwdArgs sv[2] = {SleFwdArgs{}, SleFwdArgs{}};
-  for (int i = 0; i < ni; ++i) { sv[i].x = t->feats; sv[i].K = P + c->o_sle; sv[i].f = t->f + i * nc * nD; }
+  for (int i = 0; i < ni; ++i) { sv[i].x = t->feats; sv[i].K = P + c->cam.sle; sv[i].f = t->f + i * nc * nD; }
   sv[0].mask = masks;
-  if (!masks) {
-    sv[0].gen = 2;
-    for (int k = 0; k < nc; ++k) { sv[0].tf_key[k][0] = keys[2 * k]; sv[0].tf_key[k][1] = keys[2 * k + 1]; }
-    sv[0].tf_rows = n; sv[0].tf_row0 = 0;
-  }
-  RC(sle_proprio_fwd_multi(sv, nullptr, ni, kKeep, n, c->HW, 512, nc, (long)n * c->HW * 512, c->cam_stride, nD, nD, 0, st));
+  if (!masks) sle_tf_masks(sv[0], keys, nc, n, 0);
+  RC(sle_proprio_fwd_multi(sv, nullptr, ni, kKeep, n, c->HW, 512, nc, (long)n * c->HW * 512, c->cam.stride, nD, nD, 0, st));
   // bottleneck Dense (K-split) -> LayerNorm -> tanh per camera, side by side in enc[i]
   const int S0 = split_under(n, kBottleneck, nc * ni, 32);
   GemmDesc g0[2];
   LnFwdArgs l0[2];
-  for (int i = 0; i < ni; ++i) {
-    GemmDesc& d = g0[i];
-    d = GemmDesc{};
-    d.A = t->f + i * nc * nD; d.sAm = c->D; d.sAk = 1; d.sAb = nD;
-    d.B = P + c->o_dW; d.sBk = kBottleneck; d.sBn = 1; d.sBb = c->cam_stride;
-    d.C = t->slabs + (long)i * nc * S0 * n * kBottleneck; d.ldc = kBottleneck; d.sCz = (long)n * kBottleneck;
-    d.M = n; d.N = kBottleneck; d.K = c->D; d.nbatch = nc; d.splitk = S0;
-    LnFwdArgs& l = l0[i];
-    l = LnFwdArgs{};
-    l.slabs = d.C; l.S = S0; l.slab_stride = d.sCz;
-    l.bias = P + c->o_db; l.gamma = P + c->o_lng; l.beta = P + c->o_lnb; l.pstride = c->cam_stride;
-    l.rows = nc * n; l.rows_per_group = n;
-    l.y = t->enc + (long)i * n * c->E; l.ld_y = c->E; l.y_goff = kBottleneck;
-    if (i == 0) { l.xhat = t->xhat; l.rstd = t->rstd; }
-  }
+  for (int i = 0; i < ni; ++i)
+    cam_dense_ln_args(t->f + i * nc * nD, nD, c->D, P + c->cam.dW, P + c->cam.db, P + c->cam.lng, P + c->cam.lnb, c->cam.stride,
+                      nc, n, kBottleneck, S0, t->slabs + (long)i * nc * S0 * n * kBottleneck, t->enc + (long)i * n * c->E, c->E,
+                      i == 0 ? t->xhat : nullptr, i == 0 ? t->rstd : nullptr, g0[i], l0[i]);
   RC(gemm_f32_multi(g0, ni, st));
   RC(ln_tanh_fwd_multi(l0, ni, kBottleneck, st));
   // classifier head: Dense_0 (K-split) of both instances, then the row kernel
@@ -544,7 +447,7 @@ int check_train(serl_classifier* c, int n) {
 
 int resolve_moment(serl_classifier* c, const char* section, const char* leaf, float** ptr, long* count) {
   SERL_REQUIRE(section && leaf, "NULL argument");
-  const CLeaf* l = find(c, leaf);
+  const Leaf* l = find(c->leaves, leaf);
   SERL_REQUIRE(l, "unknown classifier leaf '%s'", leaf);
   const std::string s = section;
   SERL_REQUIRE(s == "opt/mu" || s == "opt/nu", "unknown classifier section '%s' (opt/mu, opt/nu)", section);
@@ -552,6 +455,8 @@ int resolve_moment(serl_classifier* c, const char* section, const char* leaf, fl
   *ptr = l->off < c->t0 ? nullptr : (s == "opt/mu" ? c->tr->m : c->tr->v) + (l->off - c->t0);   // nullptr: frozen, always zero
   return SERL_OK;
 }
+
+constexpr const char* kFrozenMoment = "'%s' of the frozen leaf '%s' must be zero";
 
 }  // namespace
 
@@ -566,13 +471,10 @@ int serl_classifier_train_init(serl_classifier* c, int max_batch, float lr, floa
   ClsTrain* t = new ClsTrain();
   t->max_batch = max_batch;
   t->lr = lr;
-  const size_t bytes = carve_train(c, t, nullptr);
-  if (hipMalloc(&t->arena, bytes) != hipSuccess) {
+  if (int rc = alloc_zeroed(&t->arena, carve_train(c, t, nullptr), "classifier training arena")) {
     delete t;
-    serl::set_error("hipMalloc of %zu bytes failed", bytes);
-    return SERL_ERR_HIP;
+    return rc;
   }
-  SERL_HIP(hipMemset(t->arena, 0, bytes));
   carve_train(c, t, (uint8_t*)t->arena);
   c->tr = t;
   return SERL_OK;
@@ -615,13 +517,13 @@ int serl_classifier_train_step(serl_classifier* c, const uint8_t* dev_frames, in
   LnBwdArgs lb{};
   lb.dy = t->denc; lb.ld_dy = c->E; lb.dy_goff = kBottleneck;
   lb.y = t->enc; lb.ld_y = c->E; lb.y_goff = kBottleneck;
-  lb.xhat = t->xhat; lb.rstd = t->rstd; lb.gamma = P + c->o_lng; lb.pstride = c->cam_stride;
+  lb.xhat = t->xhat; lb.rstd = t->rstd; lb.gamma = P + c->cam.lng; lb.pstride = c->cam.stride;
   lb.rows = nc * n; lb.rows_per_group = n;
   lb.dx = t->dzc; lb.dg = t->dgc;
   RC(ln_tanh_bwd(lb, kBottleneck, st));
   GemmDesc gf{};
   gf.A = t->dzc; gf.sAm = kBottleneck; gf.sAk = 1; gf.sAb = (long)n * kBottleneck;
-  gf.B = P + c->o_dW; gf.sBk = 1; gf.sBn = kBottleneck; gf.sBb = c->cam_stride;
+  gf.B = P + c->cam.dW; gf.sBk = 1; gf.sBn = kBottleneck; gf.sBb = c->cam.stride;
   gf.C = t->df; gf.ldc = c->D; gf.sCz = nD;
   gf.M = n; gf.N = c->D; gf.K = kBottleneck; gf.nbatch = nc; gf.splitk = 1;
   RC(gemm_f32_multi(&gf, 1, st));
@@ -634,13 +536,13 @@ int serl_classifier_train_step(serl_classifier* c, const uint8_t* dev_frames, in
   SERL_HIP(hipGetLastError());
   const long sle_n = (long)c->HW * 512 * kSleFeatures;
   RC(sle_bwd_fused(t->feats, t->df, t->sle_part, n, c->HW, 512, kSleSplit, nc, (long)n * c->HW * 512, nD, kSleSplit * sle_n,
-                   G + c->o_sle, c->cam_stride, t->ctr, st));
+                   G + c->cam.sle, c->cam.stride, t->ctr, st));
   // every other parameter gradient: one column-sum launch and one grouped weight-gradient GEMM
   const Colsum3Args cs[4] = {
       {t->hdg, t->hxhat, t->dz, 1, n, kHidden, G + c->o_g1, G + c->o_be1, G + c->o_b1, 0, 0},
       {t->dw2in, nullptr, nullptr, 1, n, kHidden, nullptr, G + c->o_w2, nullptr, 0, 1},
       {t->dlogit, nullptr, nullptr, 1, n, 1, nullptr, G + c->o_b2, nullptr, 0, 2},
-      {t->dgc, t->xhat, t->dzc, nc, n, kBottleneck, G + c->o_lng, G + c->o_lnb, G + c->o_db, c->cam_stride, 0},
+      {t->dgc, t->xhat, t->dzc, nc, n, kBottleneck, G + c->cam.lng, G + c->cam.lnb, G + c->cam.db, c->cam.stride, 0},
   };
   RC(colsum3_multi(cs, 4, st));
   GemmDesc wg[2] = {GemmDesc{}, GemmDesc{}};
@@ -650,22 +552,12 @@ int serl_classifier_train_step(serl_classifier* c, const uint8_t* dev_frames, in
   wg[0].M = c->E; wg[0].N = kHidden; wg[0].K = n; wg[0].nbatch = 1; wg[0].splitk = 1;
   wg[1].A = t->f; wg[1].sAm = 1; wg[1].sAk = c->D; wg[1].sAb = nD;      // per camera dDense = f^T dzc
   wg[1].B = t->dzc; wg[1].sBk = kBottleneck; wg[1].sBn = 1; wg[1].sBb = (long)n * kBottleneck;
-  wg[1].C = G + c->o_dW; wg[1].ldc = kBottleneck; wg[1].sCz = c->cam_stride;
+  wg[1].C = G + c->cam.dW; wg[1].ldc = kBottleneck; wg[1].sCz = c->cam.stride;
   wg[1].M = c->D; wg[1].N = kBottleneck; wg[1].K = n; wg[1].nbatch = nc; wg[1].splitk = 1;
   RC(gemm_f32_multi(wg, 2, st));
   // optax.adam(lr) (reward_classifier.py:62-66) over the trainable slice
-  const int64_t step = t->step + 1;
-  AdamArgs ad{};
-  ad.theta = c->params + c->t0; ad.theta_target = nullptr;
-  ad.P = c->nt + 1; ad.Pc = 0; ad.Pa0 = 0; ad.Pa1 = c->nt;
-  ad.g_actor = t->G; ad.m_a = t->m; ad.v_a = t->v;
-  ad.m_t = t->m + c->nt; ad.v_t = t->v + c->nt;   // the temperature slot adam_ema keeps at P - 1: never touched (g = m = v = 0)
-  ad.actor_on = 1;
-  ad.lr_a = t->lr;
-  ad.bc1 = 1.0f - powf(0.9f, (float)step);
-  ad.bc2 = 1.0f - powf(0.999f, (float)step);
-  RC(adam_ema(ad, st));
-  t->step = step;
+  RC(adam_ema(adam_slice(c->params + c->t0, c->nt, t->G, t->m, t->v, t->lr, t->step + 1), st));
+  t->step += 1;
   return SERL_OK;
 }
 
@@ -698,13 +590,8 @@ int serl_classifier_train_set(serl_classifier* c, const char* section, const cha
   long n = 0;
   RC(resolve_moment(c, section, leaf, &p, &n));
   SERL_REQUIRE(count == n, "leaf '%s' has %ld elements, got %ld", leaf, n, (long)count);
-  if (!p) {   // the moments of a frozen leaf are zero by construction
-    for (long i = 0; i < n; ++i) SERL_REQUIRE(host[i] == 0.f, "'%s' of the frozen leaf '%s' must be zero", section, leaf);
-    return SERL_OK;
-  }
   SERL_HIP(hipSetDevice(c->cfg.device));
-  SERL_HIP(hipMemcpy(p, host, (size_t)n * 4, hipMemcpyHostToDevice));
-  return SERL_OK;
+  return leaf_copy(p, host, n, hipMemcpyHostToDevice, section, leaf, kFrozenMoment);
 }
 
 int serl_classifier_train_get(serl_classifier* c, const char* section, const char* leaf, float* host_out, int64_t count) {
@@ -714,13 +601,8 @@ int serl_classifier_train_get(serl_classifier* c, const char* section, const cha
   long n = 0;
   RC(resolve_moment(c, section, leaf, &p, &n));
   SERL_REQUIRE(count == n, "leaf '%s' has %ld elements, got %ld", leaf, n, (long)count);
-  if (!p) {
-    for (long i = 0; i < n; ++i) host_out[i] = 0.f;
-    return SERL_OK;
-  }
   SERL_HIP(hipSetDevice(c->cfg.device));
-  SERL_HIP(hipMemcpy(host_out, p, (size_t)n * 4, hipMemcpyDeviceToHost));
-  return SERL_OK;
+  return leaf_copy(host_out, p, n, hipMemcpyDeviceToHost, section, leaf, kFrozenMoment);
 }
 
 }  // extern "C"

@@ -30,6 +30,13 @@ void set_error(const char* fmt, ...);
     }                                  \
   } while (0)
 
+// returns a non-zero status of `x` to the caller
+#define RC(x)            \
+  do {                   \
+    int _rc = (x);       \
+    if (_rc) return _rc; \
+  } while (0)
+
 inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
 }  // namespace serl

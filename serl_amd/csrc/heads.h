@@ -1,5 +1,7 @@
 // Host-callable launchers of heads.hip (internal, not part of the C ABI).
 #pragma once
+#include <cmath>
+
 #include "internal.h"
 
 namespace serl {
@@ -125,6 +127,20 @@ struct AdamArgs {
   float info_w, inv_eb;
 };
 int adam_ema(const AdamArgs& a, hipStream_t stream);
+// optax.adam(lr) alone over a trainable slice theta[0, nt) (no schedule, clip or target), at update number `step` (1-based).
+// m / v hold nt + 1 floats: the last is the temperature slot adam_ema keeps at P - 1, never touched (g = m = v = 0).
+inline AdamArgs adam_slice(float* theta, long nt, const float* g, float* m, float* v, float lr, int64_t step) {
+  AdamArgs a{};
+  a.theta = theta; a.theta_target = nullptr;
+  a.P = nt + 1; a.Pc = 0; a.Pa0 = 0; a.Pa1 = nt;
+  a.g_actor = g; a.m_a = m; a.v_a = v;
+  a.m_t = m + nt; a.v_t = v + nt;
+  a.actor_on = 1;
+  a.lr_a = lr;
+  a.bc1 = 1.0f - powf(0.9f, (float)step);
+  a.bc2 = 1.0f - powf(0.999f, (float)step);
+  return a;
+}
 // `steps` target-EMA steps of frozen leaves in one pass (exactly the values `steps` adam_ema launches would have left)
 int frozen_ema(const float* frozen, float* frozen_target, long n, float tau, long steps, hipStream_t stream);
 // out[0] = sum g_critic^2 over [0, nc), out[1] = sum g_actor^2 over [0, na) (deterministic single-block reduction)
@@ -134,5 +150,53 @@ int grad_norm2(const float* g_critic, long nc, const float* g_actor, long na, fl
 // batch-sharded job draws the same noise for a sample whichever rank owns it (rows_global == 0: local == global)
 struct NoiseJob { void* out; long n; uint64_t seed; int kind; float keep; long rows_local, rows_global, row_offset, row_elems; };
 int gen_noise_multi(const NoiseJob* v, int n, hipStream_t stream);
+
+
+// ---- the per-camera encoder head on the frozen trunk (resnet_v1.py:324-376, encoding.py:26-72): SpatialLearnedEmbeddings ->
+// Dense -> LayerNorm -> tanh.  Offsets of camera 0's leaves; camera k's sit k * stride floats further.
+struct CamHeadOffsets { long sle, dW, db, lng, lnb, stride; };
+// Appends enc/<k>/{sle, dense/kernel, dense/bias, ln/scale, ln/bias} of n_cam cameras at `off`, which moves behind them:
+// sle_count floats of SpatialLearnedEmbeddings kernel, a [D][N] Dense, and LayerNorm of width N.
+inline CamHeadOffsets add_cam_head_leaves(std::vector<Leaf>& v, long& off, int n_cam, long sle_count, long D, long N) {
+  CamHeadOffsets o{};
+  for (int k = 0; k < n_cam; ++k) {
+    const std::string p = "enc/" + std::to_string(k) + "/";
+    const long s = add_leaf(v, off, p + "sle", sle_count);
+    const long dW = add_leaf(v, off, p + "dense/kernel", D * N);
+    const long db = add_leaf(v, off, p + "dense/bias", N);
+    const long lg = add_leaf(v, off, p + "ln/scale", N);
+    const long lb = add_leaf(v, off, p + "ln/bias", N);
+    if (k == 0) o = CamHeadOffsets{s, dW, db, lg, lb, off - s};
+  }
+  return o;
+}
+
+// The GEMM + LayerNorm launch pair of one instance of the Dense -> LayerNorm -> tanh layer over `cams` cameras.  Camera k reads
+// [rows][K] inputs at f + k * f_cstride, its parameters k * cam_stride floats behind W / bias / gamma / beta, and writes columns
+// k * N.. of y (row stride ld_y).  The GEMM leaves S K-split slabs per camera at `slabs` ([cam][split][rows][N]), which the
+// LayerNorm launch sums.  xhat / rstd: the statistics a backward pass reads, or nullptr.
+inline void cam_dense_ln_args(const float* f, long f_cstride, int K, const float* W, const float* bias, const float* gamma,
+                              const float* beta, long cam_stride, int cams, int rows, int N, int S, float* slabs, float* y,
+                              long ld_y, float* xhat, float* rstd, GemmDesc& g, LnFwdArgs& l) {
+  g = GemmDesc{};
+  g.A = f; g.sAm = K; g.sAk = 1; g.sAb = f_cstride;
+  g.B = W; g.sBk = N; g.sBn = 1; g.sBb = cam_stride;
+  g.C = slabs; g.ldc = N; g.sCz = (long)rows * N;
+  g.M = rows; g.N = N; g.K = K; g.nbatch = cams; g.splitk = S;
+  l = LnFwdArgs{};
+  l.slabs = slabs; l.S = S; l.slab_stride = g.sCz;
+  l.bias = bias; l.gamma = gamma; l.beta = beta; l.pstride = cam_stride;
+  l.rows = cams * rows; l.rows_per_group = rows;
+  l.y = y; l.ld_y = ld_y; l.y_goff = N;
+  l.xhat = xhat; l.rstd = rstd;
+}
+
+// Dropout keep-masks of the SpatialLearnedEmbeddings launch drawn from host jax.random keys [n_cam][2]: rows row0.. of
+// jax.random.bernoulli(key, keep, (rows, D)) per camera.
+inline void sle_tf_masks(SleFwdArgs& s, const uint32_t* keys, int n_cam, long rows, long row0) {
+  s.gen = 2;
+  for (int k = 0; k < n_cam; ++k) { s.tf_key[k][0] = keys[2 * k]; s.tf_key[k][1] = keys[2 * k + 1]; }
+  s.tf_rows = rows; s.tf_row0 = row0;
+}
 
 }  // namespace serl

@@ -1,6 +1,7 @@
 // Internal (non-ABI) interfaces between the translation units of libserl_mi355.so.
 #pragma once
 #include "common.h"
+#include "param_arena.h"
 
 namespace serl {
 
@@ -19,6 +20,18 @@ struct TrunkWeights {  // device pointers into the agent's parameter arena (HWIO
     const float *conv0, *gn0_s, *gn0_b, *conv1, *gn1_s, *gn1_b, *proj, *gnp_s, *gnp_b;
   } blk[kTrunkStages];
 };
+
+// Offsets of the trunk's leaves in a flat parameter vector; -1 for the projection of a block that has none.
+struct TrunkOffsets {
+  long conv_init, gn_init_s, gn_init_b;
+  struct Block {
+    long conv0, gn0_s, gn0_b, conv1, gn1_s, gn1_b, proj, gnp_s, gnp_b;
+  } blk[kTrunkStages];
+};
+// Appends the trunk's leaves (trunk/conv_init ... trunk/block3/gnp/bias) at `off`, which moves behind them.
+TrunkOffsets add_trunk_leaves(std::vector<Leaf>& leaves, long& off);
+// The trunk's weights in the parameter vector at `params` (nullptr where the offset is -1).
+TrunkWeights trunk_weights(const float* params, const TrunkOffsets& o);
 
 struct TrunkDims {
   int H, W;            // input image

@@ -40,29 +40,27 @@ long small_conv_params() { return small_conv_offset(kSmallLayers); }
 constexpr int kConv0Chunks = 1024, kSmallMaxCams = 4;   // layer 0's weight gradient: row chunks per camera / cameras
 static int ldk(int l) { return (9 * kSmallFeat[l] + 1 + 3) & ~3; }   // row pitch of col_l: K + 1 rounded up to 4 floats
 static long rows_of(const SmallDims& d, int l, long n_img) { return n_img * d.h[l + 1] * d.w[l + 1]; }
-static size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 static size_t carve(SmallWorkspace& ws, uint8_t* base, int max_images, int H, int W) {
   ws.d = small_dims(H, W);
   ws.max_images = max_images;
-  size_t off = 0;
-  auto take = [&](size_t floats) { float* p = base ? (float*)(base + off) : nullptr; off += al256(floats * 4); return p; };
+  Bump b(base);
   long max_act = 0, max_col = 0;
   for (int l = 0; l < kSmallLayers; ++l) {
     const long r = rows_of(ws.d, l, max_images);
-    if (l > 0) ws.tab[l] = reinterpret_cast<int*>(take((size_t)r));
-    ws.act[l] = take((size_t)r * kSmallFeat[l + 1]);
+    if (l > 0) ws.tab[l] = b.take<int>(r);
+    ws.act[l] = b.take<float>((size_t)r * kSmallFeat[l + 1]);
     max_act = std::max(max_act, r * kSmallFeat[l + 1]);
     if (l > 0) max_col = std::max(max_col, r * ldk(l));
   }
   ws.tab_ready = false;
-  ws.dact = take(max_act);
-  ws.dact2 = take(max_act);
-  ws.dcol = take(max_col);
+  ws.dact = b.take<float>(max_act);
+  ws.dact2 = b.take<float>(max_act);
+  ws.dcol = b.take<float>(max_col);
   ws.slabs_cap = std::max(64L * (9 * 128 + 1) * 256, (long)kConv0Chunks * kSmallMaxCams * 28 * 32);   // up to 64 K-slices of the largest [K+1][cout] gradient / layer 0's row chunks
-  ws.slabs = take(ws.slabs_cap);
-  ws.bytes = off;
-  return off;
+  ws.slabs = b.take<float>(ws.slabs_cap);
+  ws.bytes = b.off;
+  return b.off;
 }
 size_t small_workspace_bytes(int max_images, int H, int W) {
   SmallWorkspace t;

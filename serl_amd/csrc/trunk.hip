@@ -433,39 +433,73 @@ TrunkDims trunk_dims(int H, int W) {
   return d;
 }
 
-constexpr int kGnLayers = 1 + 3 * kTrunkStages;
-static inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
+TrunkOffsets add_trunk_leaves(std::vector<Leaf>& v, long& off) {
+  TrunkOffsets o{};
+  o.conv_init = add_leaf(v, off, "trunk/conv_init", 7 * 7 * 3 * 64);
+  o.gn_init_s = add_leaf(v, off, "trunk/norm_init/scale", 64);
+  o.gn_init_b = add_leaf(v, off, "trunk/norm_init/bias", 64);
+  int cin = 64;
+  for (int i = 0; i < kTrunkStages; ++i) {
+    const int f = kStageFilters[i];
+    const std::string p = "trunk/block" + std::to_string(i) + "/";
+    TrunkOffsets::Block& b = o.blk[i];
+    b.conv0 = add_leaf(v, off, p + "conv0", 9L * cin * f);
+    b.gn0_s = add_leaf(v, off, p + "gn0/scale", f);
+    b.gn0_b = add_leaf(v, off, p + "gn0/bias", f);
+    b.conv1 = add_leaf(v, off, p + "conv1", 9L * f * f);
+    b.gn1_s = add_leaf(v, off, p + "gn1/scale", f);
+    b.gn1_b = add_leaf(v, off, p + "gn1/bias", f);
+    b.proj = b.gnp_s = b.gnp_b = -1;
+    if (kStageStride[i] != 1 || cin != f) {
+      b.proj = add_leaf(v, off, p + "proj", (long)cin * f);
+      b.gnp_s = add_leaf(v, off, p + "gnp/scale", f);
+      b.gnp_b = add_leaf(v, off, p + "gnp/bias", f);
+    }
+    cin = f;
+  }
+  return o;
+}
 
+TrunkWeights trunk_weights(const float* params, const TrunkOffsets& o) {
+  auto p = [&](long off) { return off < 0 ? nullptr : params + off; };
+  TrunkWeights w{};
+  w.conv_init = p(o.conv_init); w.gn_init_s = p(o.gn_init_s); w.gn_init_b = p(o.gn_init_b);
+  for (int i = 0; i < kTrunkStages; ++i) {
+    const TrunkOffsets::Block& s = o.blk[i];
+    TrunkWeights::Block& b = w.blk[i];
+    b.conv0 = p(s.conv0); b.gn0_s = p(s.gn0_s); b.gn0_b = p(s.gn0_b);
+    b.conv1 = p(s.conv1); b.gn1_s = p(s.gn1_s); b.gn1_b = p(s.gn1_b);
+    b.proj = p(s.proj); b.gnp_s = p(s.gnp_s); b.gnp_b = p(s.gnp_b);
+  }
+  return w;
+}
+
+constexpr int kGnLayers = 1 + 3 * kTrunkStages;
 static size_t trunk_layout(TrunkWorkspace* ws, uint8_t* base, int N, int H, int W) {
   const TrunkDims d = trunk_dims(H, W);
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    uint8_t* p = base ? base + off : nullptr;
-    off += al256(bytes);
-    return p;
-  };
-  float* raw_init = (float*)take((size_t)N * d.h[0] * d.w[0] * 64 * 4);
-  float* pool = (float*)take((size_t)N * d.h[1] * d.w[1] * 64 * 4);
+  Bump b(base);
+  float* raw_init = b.take<float>((size_t)N * d.h[0] * d.w[0] * 64);
+  float* pool = b.take<float>((size_t)N * d.h[1] * d.w[1] * 64);
   TrunkWorkspace::B blk[kTrunkStages];
   for (int i = 0; i < kTrunkStages; ++i) {
-    const size_t e = (size_t)N * d.h[2 + i] * d.w[2 + i] * kStageFilters[i] * 4;
-    blk[i].raw0 = (float*)take(e);
-    blk[i].raw1 = (float*)take(e);
-    blk[i].rawp = (float*)take(e);
-    blk[i].out = (float*)take(e);
-    blk[i].norm0 = (float*)take(e);
+    const size_t e = (size_t)N * d.h[2 + i] * d.w[2 + i] * kStageFilters[i];
+    blk[i].raw0 = b.take<float>(e);
+    blk[i].raw1 = b.take<float>(e);
+    blk[i].rawp = b.take<float>(e);
+    blk[i].out = b.take<float>(e);
+    blk[i].norm0 = b.take<float>(e);
   }
   const size_t stats_bytes = al256((size_t)kGnLayers * N * kGnGroups * 2 * sizeof(double));
   const size_t sync_bytes = (size_t)kGnLayers * ((size_t)N * kSyncPerImage + kSyncTickets) * sizeof(int);
-  double* stats = (double*)take(stats_bytes + sync_bytes);
+  double* stats = (double*)b.take<uint8_t>(stats_bytes + sync_bytes);
   if (ws) {
     ws->sync = base ? (int*)(base + ((uint8_t*)stats - base) + stats_bytes) : nullptr;
     ws->stats_sync_bytes = stats_bytes + sync_bytes;
     ws->max_images = N; ws->d = d; ws->raw_init = raw_init; ws->pool = pool;
     for (int i = 0; i < kTrunkStages; ++i) ws->blk[i] = blk[i];
-    ws->stats = stats; ws->base = base; ws->bytes = off;
+    ws->stats = stats; ws->base = base; ws->bytes = b.off;
   }
-  return off;
+  return b.off;
 }
 
 size_t trunk_workspace_bytes(int max_images, int H, int W) {

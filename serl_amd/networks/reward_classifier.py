@@ -16,7 +16,6 @@ from __future__ import annotations
 import ctypes as C
 import os
 import pickle
-from collections import namedtuple
 from typing import Callable, Dict, List, Optional
 
 import numpy as np
@@ -24,7 +23,8 @@ import torch
 
 from .. import _lib
 from .. import jaxrng as J
-from ..agents.flax_tree import _trunk_paths, trunk_from_flax, trunk_owner
+from ..agents.flax_tree import CAM_PATHS as _CAM_PATHS
+from ..agents.flax_tree import EmptyState, ScaleByAdamState, _trunk_paths, adam_moments, trunk_from_flax, trunk_owner
 
 
 class SerlClassifierCfg(C.Structure):
@@ -64,13 +64,6 @@ _HEAD_PATHS = {   # flat leaf -> path in BinaryClassifier's parameter tree (flax
     "head/ln/scale": ("LayerNorm_0", "scale"), "head/ln/bias": ("LayerNorm_0", "bias"),
     "head/dense1/kernel": ("Dense_1", "kernel"), "head/dense1/bias": ("Dense_1", "bias"),
 }
-_CAM_PATHS = {"sle": ("SpatialLearnedEmbeddings_0", "kernel"), "dense/kernel": ("Dense_0", "kernel"),
-              "dense/bias": ("Dense_0", "bias"), "ln/scale": ("LayerNorm_0", "scale"), "ln/bias": ("LayerNorm_0", "bias")}
-
-
-# optax.adam's state (optax/_src/transform.py ScaleByAdamState; base.EmptyState of scale_by_learning_rate)
-ScaleByAdamState = namedtuple("ScaleByAdamState", ["count", "mu", "nu"])
-EmptyState = namedtuple("EmptyState", [])
 
 SLE_DIM = 512 * 8
 HIDDEN = 256
@@ -256,8 +249,7 @@ class Classifier:
             self.load_params(sd["params"])
         opt = sd.get("opt_state")
         if opt is not None:
-            adam = opt[0] if isinstance(opt, (tuple, list)) else opt["0"]
-            mu, nu = (adam.mu, adam.nu) if hasattr(adam, "mu") else (adam["mu"], adam["nu"])
+            mu, nu = adam_moments(opt)
             self.load_params(mu, "opt/mu")
             self.load_params(nu, "opt/nu")
         if sd.get("step") is not None:
