@@ -29,50 +29,43 @@ class SerlBatch(C.Structure):
     ]
 
 
+vp, i32, i64, u64, u32, f32, P = C.c_void_p, C.c_int, C.c_int64, C.c_uint64, C.c_uint32, C.c_float, C.POINTER
+
+# function -> argtypes; every function returns an int status unless RESTYPES says otherwise.  The agent, BC and classifier
+# handles are declared in _lib_agent.py; tests/test_bindings.py checks both tables against include/serl_mi355.h.
+SIGNATURES = {
+    "serl_last_error": [],
+    "serl_version": [],
+    "serl_device_count": [],
+    "serl_rb_create": [i32, i64, i32, i32, i32, i32, i32, i32, i32, P(vp)],
+    "serl_rb_destroy": [vp],
+    "serl_rb_seed": [vp, u64, u64, u64, u64, i32, u32],
+    "serl_rb_rng_state": [vp, P(u64), P(i32), P(u32)],
+    "serl_rb_insert": [vp, P(vp), P(vp), vp, vp, vp, f32, f32, i32],
+    "serl_rb_len": [vp],
+    "serl_rb_insert_index": [vp],
+    "serl_rb_valid_mask": [vp, vp],
+    "serl_rb_sample_indices": [vp, i32, vp],
+    "serl_rb_gather_packed": [vp, vp, i32, P(vp), vp, vp, vp, vp, vp, vp, vp],
+    "serl_rb_gather_crop": [P(vp), i32, P(vp), P(i32), vp, vp, P(SerlBatch), vp],
+    "serl_crop_packed": [i32, P(vp), i32, i32, i32, i32, i32, vp, vp, vp, vp],
+    "serl_profile_enable": [i32],
+    "serl_profile_reset": [],
+    "serl_profile_read": [i32, vp, vp, vp, P(i32)],
+    # JAX's PRNG (csrc/jaxrng.hip; serl_amd/jaxrng.py)
+    "serl_jax_prngkey": [u64, P(u32)],
+    "serl_jax_split": [P(u32), i32, P(u32)],
+    "serl_jax_fold_in": [P(u32), u32, P(u32)],
+    "serl_jax_random_bits": [P(u32), i64, P(u32)],
+    "serl_jax_randint": [P(u32), i64, i32, i32, P(i32)],
+    "serl_jax_normal_host": [P(u32), i64, P(f32)],
+    "serl_jax_crop_offsets": [P(u32), i32, i32, P(i32)],
+    "serl_jax_update_keys": [P(u32), i32, i32, i32, i32, vp],
+    "serl_jax_fill": [i32, vp, i32, vp],
+}
+RESTYPES = {"serl_last_error": C.c_char_p, "serl_rb_len": i64, "serl_rb_insert_index": i64}
+
 _lib = None
-
-
-def _declare(lib):
-    vp, i32, i64, u64, u32, f32 = C.c_void_p, C.c_int, C.c_int64, C.c_uint64, C.c_uint32, C.c_float
-    P = C.POINTER
-    lib.serl_last_error.restype = C.c_char_p
-    lib.serl_last_error.argtypes = []
-    lib.serl_version.restype = i32
-    lib.serl_device_count.restype = i32
-    sigs = {
-        "serl_rb_create": [i32, i64, i32, i32, i32, i32, i32, i32, i32, P(vp)],
-        "serl_rb_destroy": [vp],
-        "serl_rb_seed": [vp, u64, u64, u64, u64, i32, u32],
-        "serl_rb_rng_state": [vp, P(u64), P(i32), P(u32)],
-        "serl_rb_insert": [vp, P(vp), P(vp), vp, vp, vp, f32, f32, i32],
-        "serl_rb_valid_mask": [vp, vp],
-        "serl_rb_sample_indices": [vp, i32, vp],
-        "serl_rb_gather_packed": [vp, vp, i32, P(vp), vp, vp, vp, vp, vp, vp, vp],
-        "serl_rb_gather_crop": [P(vp), i32, P(vp), P(i32), vp, vp, P(SerlBatch), vp],
-        "serl_crop_packed": [i32, P(vp), i32, i32, i32, i32, i32, vp, vp, vp, vp],
-        "serl_profile_enable": [i32],
-        "serl_profile_reset": [],
-        "serl_profile_read": [i32, vp, vp, vp, P(i32)],
-        # JAX's PRNG (csrc/jaxrng.hip; serl_amd/jaxrng.py)
-        "serl_jax_prngkey": [u64, P(u32)],
-        "serl_jax_split": [P(u32), i32, P(u32)],
-        "serl_jax_fold_in": [P(u32), u32, P(u32)],
-        "serl_jax_random_bits": [P(u32), i64, P(u32)],
-        "serl_jax_randint": [P(u32), i64, i32, i32, P(i32)],
-        "serl_jax_normal_host": [P(u32), i64, P(f32)],
-        "serl_jax_crop_offsets": [P(u32), i32, i32, P(i32)],
-        "serl_jax_update_keys": [P(u32), i32, i32, i32, i32, vp],
-        "serl_jax_fill": [i32, vp, i32, vp],
-    }
-    for name, args in sigs.items():
-        fn = getattr(lib, name)
-        fn.argtypes = args
-        fn.restype = i32
-    for name in ("serl_rb_len", "serl_rb_insert_index"):
-        fn = getattr(lib, name)
-        fn.argtypes = [vp]
-        fn.restype = i64
-    return sigs
 
 
 def lib():
@@ -82,19 +75,14 @@ def lib():
             raise SerlError(
                 f"{LIB_PATH} not found: build it with `python -m serl_amd.build` "
                 "(hipcc --offload-arch=gfx950). There is no CPU fallback.")
-        _lib = C.CDLL(LIB_PATH)
-        _declare(_lib)
-        _declare_agent(_lib)
-    return _lib
-
-
-def _declare_agent(lib):
-    """Agent entry points (declared in a second step so replay-only builds still load)."""
-    try:
         from . import _lib_agent
-    except ImportError:
-        return
-    _lib_agent.declare(lib)
+        L = C.CDLL(LIB_PATH)
+        for sigs, restypes in ((SIGNATURES, RESTYPES), (_lib_agent.SIGNATURES, _lib_agent.RESTYPES)):
+            for name, args in sigs.items():
+                fn = getattr(L, name)
+                fn.argtypes, fn.restype = args, restypes.get(name, i32)
+        _lib = L
+    return _lib
 
 
 def check(status: int):
@@ -119,9 +107,13 @@ def profile_read(max_entries=64):
 
 
 def exported_symbols():
-    """Names declared in include/serl_mi355.h (parsed), for the symbol-presence test."""
+    """{name: parameter count} of every function include/serl_mi355.h declares (parsed), for the ABI tests."""
     import re
     hdr = os.path.join(_HERE, "..", "include", "serl_mi355.h")
     txt = open(hdr).read()
     txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    return sorted(set(re.findall(r"\b(serl_[a-z0-9_]+)\s*\(", txt)))
+    out = {}
+    for name, params in re.findall(r"\b(serl_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", txt):
+        params = params.strip()
+        out[name] = 0 if params in ("", "void") else params.count(",") + 1
+    return out

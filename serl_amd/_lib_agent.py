@@ -1,7 +1,8 @@
-"""ctypes declarations of the agent half of the C ABI (include/serl_mi355.h)."""
+"""ctypes declarations of the handle half of the C ABI (include/serl_mi355.h): the agent, BC and reward-classifier
+handles.  _lib.lib() applies SIGNATURES / RESTYPES once, when it loads the library."""
 import ctypes as C
 
-from ._lib import SerlBatch
+from ._lib import P, SerlBatch, f32, i32, i64, vp
 
 
 class SerlAgentCfg(C.Structure):
@@ -35,6 +36,10 @@ class SerlBcCfg(C.Structure):
     ]
 
 
+class SerlClassifierCfg(C.Structure):
+    _fields_ = [("device", C.c_int), ("n_cam", C.c_int), ("H", C.c_int), ("W", C.c_int), ("max_batch", C.c_int)]
+
+
 class SerlNoise(C.Structure):
     _fields_ = [
         ("eps_next", C.c_void_p), ("mask_next", C.c_void_p), ("redq_idx", C.c_void_p),
@@ -52,62 +57,70 @@ class SerlInfo(C.Structure):
         "temperature_loss", "actor_lr", "critic_lr", "temperature_lr")]
 
 
-def declare(lib):
-    vp, i32, i64, f32 = C.c_void_p, C.c_int, C.c_int64, C.c_float
-    P = C.POINTER
-    sigs = {
-        "serl_agent_create": [P(SerlAgentCfg), P(vp)],
-        "serl_agent_destroy": [vp],
-        "serl_agent_num_leaves": [vp],
-        "serl_agent_leaf_info": [vp, i32, C.c_char_p, i32, P(i64)],
-        "serl_agent_set": [vp, C.c_char_p, C.c_char_p, vp, i64],
-        "serl_agent_get": [vp, C.c_char_p, C.c_char_p, vp, i64],
-        "serl_agent_set_step": [vp, i64],
-        "serl_agent_set_trunk_mode": [vp, i32],
-        "serl_agent_set_chain_budget": [vp, i32],
-        "serl_agent_update_critics": [vp, P(SerlBatch), P(SerlNoise), vp],
-        "serl_agent_update_high_utd": [vp, P(SerlBatch), i32, P(SerlNoise), vp],
-        "serl_agent_read_info": [vp, P(SerlInfo), vp],
-        "serl_agent_encode": [vp, P(SerlBatch), vp],
-        "serl_agent_encode_slot": [vp, P(SerlBatch), i32, vp],
-        "serl_agent_encode_slot_range": [vp, P(SerlBatch), i32, i32, i32, vp],
-        "serl_agent_select_slot": [vp, i32],
-        "serl_agent_slot_features": [vp, i32, P(vp), P(i64)],
-        "serl_agent_bind_slot": [vp, P(SerlBatch), i32],
-        "serl_agent_critic_grads": [vp, i32, i32, i32, P(SerlNoise), i32, vp],
-        "serl_agent_critic_grads_bucketed": [vp, i32, i32, i32, P(SerlNoise), i32, vp, vp],
-        "serl_agent_grad_bucket": [vp, i32, P(vp), P(i64)],
-        "serl_agent_actor_grads": [vp, i32, P(SerlNoise), vp],
-        "serl_agent_apply": [vp, i32, f32, vp],
-        "serl_agent_update": [vp, P(SerlBatch), i32, P(SerlNoise), vp],
-        "serl_agent_begin_update": [vp, vp],
-        "serl_agent_set_shard": [vp, i64, i64],
-        "serl_agent_grad_view": [vp, i32, P(vp), P(i64)],
-        "serl_agent_sample_actions": [vp, vp, vp, i32, vp, vp, vp],
-        "serl_agent_trunk_forward": [vp, vp, i32, vp, vp],
-        "serl_agent_debug_get": [vp, C.c_char_p, vp, i64],
-        "serl_agent_trunk_plan": [vp, C.c_char_p, i32],
-        "serl_agent_debug_set": [vp, C.c_char_p, vp, i64],
-        # behaviour cloning (csrc/bc.hip, serl_amd/agents/bc.py)
-        "serl_bc_create": [P(SerlBcCfg), P(vp)],
-        "serl_bc_destroy": [vp],
-        "serl_bc_num_leaves": [vp],
-        "serl_bc_leaf_info": [vp, i32, C.c_char_p, i32, P(i64), P(i32)],
-        "serl_bc_set": [vp, C.c_char_p, C.c_char_p, vp, i64],
-        "serl_bc_get": [vp, C.c_char_p, C.c_char_p, vp, i64],
-        "serl_bc_set_step": [vp, i64],
-        "serl_bc_update": [vp, P(SerlBatch), vp, vp, vp],
-        "serl_bc_read_info": [vp, vp, vp],
-        "serl_bc_sample_actions": [vp, vp, vp, i32, vp, vp, f32, i32, vp, vp],
-        "serl_bc_debug_metrics": [vp, P(SerlBatch), vp, vp, vp, vp],
-    }
-    for name, args in sigs.items():
-        fn = getattr(lib, name)
-        fn.argtypes = args
-        fn.restype = i32
-    lib.serl_debug_chain_launches.argtypes = []
-    lib.serl_debug_chain_launches.restype = i64
-    lib.serl_agent_get_step.argtypes = [vp]
-    lib.serl_agent_get_step.restype = i64
-    lib.serl_bc_get_step.argtypes = [vp]
-    lib.serl_bc_get_step.restype = i64
+# function -> argtypes (int status unless RESTYPES says otherwise)
+SIGNATURES = {
+    "serl_agent_create": [P(SerlAgentCfg), P(vp)],
+    "serl_agent_destroy": [vp],
+    "serl_agent_num_leaves": [vp],
+    "serl_agent_leaf_info": [vp, i32, C.c_char_p, i32, P(i64)],
+    "serl_agent_set": [vp, C.c_char_p, C.c_char_p, vp, i64],
+    "serl_agent_get": [vp, C.c_char_p, C.c_char_p, vp, i64],
+    "serl_agent_set_step": [vp, i64],
+    "serl_agent_set_trunk_mode": [vp, i32],
+    "serl_agent_set_chain_budget": [vp, i32],
+    "serl_agent_get_step": [vp],
+    "serl_agent_update_critics": [vp, P(SerlBatch), P(SerlNoise), vp],
+    "serl_agent_update_high_utd": [vp, P(SerlBatch), i32, P(SerlNoise), vp],
+    "serl_agent_read_info": [vp, P(SerlInfo), vp],
+    "serl_agent_encode": [vp, P(SerlBatch), vp],
+    "serl_agent_encode_slot": [vp, P(SerlBatch), i32, vp],
+    "serl_agent_encode_slot_range": [vp, P(SerlBatch), i32, i32, i32, vp],
+    "serl_agent_select_slot": [vp, i32],
+    "serl_agent_slot_features": [vp, i32, P(vp), P(i64)],
+    "serl_agent_bind_slot": [vp, P(SerlBatch), i32],
+    "serl_agent_critic_grads": [vp, i32, i32, i32, P(SerlNoise), i32, vp],
+    "serl_agent_critic_grads_bucketed": [vp, i32, i32, i32, P(SerlNoise), i32, vp, vp],
+    "serl_agent_grad_bucket": [vp, i32, P(vp), P(i64)],
+    "serl_agent_actor_grads": [vp, i32, P(SerlNoise), vp],
+    "serl_agent_apply": [vp, i32, f32, vp],
+    "serl_agent_update": [vp, P(SerlBatch), i32, P(SerlNoise), vp],
+    "serl_agent_begin_update": [vp, vp],
+    "serl_agent_set_shard": [vp, i64, i64],
+    "serl_agent_grad_view": [vp, i32, P(vp), P(i64)],
+    "serl_agent_sample_actions": [vp, vp, vp, i32, vp, vp, vp],
+    "serl_agent_trunk_forward": [vp, vp, i32, vp, vp],
+    "serl_agent_debug_get": [vp, C.c_char_p, vp, i64],
+    "serl_agent_trunk_plan": [vp, C.c_char_p, i32],
+    "serl_agent_debug_set": [vp, C.c_char_p, vp, i64],
+    "serl_debug_chain_launches": [],
+    # behaviour cloning (csrc/bc.hip, serl_amd/agents/bc.py)
+    "serl_bc_create": [P(SerlBcCfg), P(vp)],
+    "serl_bc_destroy": [vp],
+    "serl_bc_num_leaves": [vp],
+    "serl_bc_leaf_info": [vp, i32, C.c_char_p, i32, P(i64), P(i32)],
+    "serl_bc_set": [vp, C.c_char_p, C.c_char_p, vp, i64],
+    "serl_bc_get": [vp, C.c_char_p, C.c_char_p, vp, i64],
+    "serl_bc_set_step": [vp, i64],
+    "serl_bc_get_step": [vp],
+    "serl_bc_update": [vp, P(SerlBatch), vp, vp, vp],
+    "serl_bc_read_info": [vp, vp, vp],
+    "serl_bc_sample_actions": [vp, vp, vp, i32, vp, vp, f32, i32, vp, vp],
+    "serl_bc_debug_metrics": [vp, P(SerlBatch), vp, vp, vp, vp],
+    # reward classifier (csrc/classifier.hip, serl_amd/networks/reward_classifier.py)
+    "serl_classifier_create": [P(SerlClassifierCfg), P(vp)],
+    "serl_classifier_destroy": [vp],
+    "serl_classifier_num_leaves": [vp],
+    "serl_classifier_leaf_info": [vp, i32, C.c_char_p, i32, P(i64)],
+    "serl_classifier_set": [vp, C.c_char_p, vp, i64],
+    "serl_classifier_get": [vp, C.c_char_p, vp, i64],
+    "serl_classifier_logits": [vp, vp, i32, vp, vp],
+    "serl_classifier_train_init": [vp, i32, f32, f32, f32, f32],
+    "serl_classifier_train_step": [vp, vp, i32, vp, vp, vp, vp],
+    "serl_classifier_train_forward": [vp, vp, i32, vp, vp, vp, vp],
+    "serl_classifier_read_train_info": [vp, vp, vp],
+    "serl_classifier_train_set_step": [vp, i64],
+    "serl_classifier_train_get_step": [vp, P(i64)],
+    "serl_classifier_train_set": [vp, C.c_char_p, C.c_char_p, vp, i64],
+    "serl_classifier_train_get": [vp, C.c_char_p, C.c_char_p, vp, i64],
+}
+RESTYPES = {"serl_agent_get_step": i64, "serl_bc_get_step": i64, "serl_debug_chain_launches": i64}

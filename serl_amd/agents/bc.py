@@ -20,18 +20,24 @@ import torch
 
 from .. import _lib
 from .. import jaxrng as J
+from .._handle import Handle, LazyInfo
 from .._lib_agent import SerlBcCfg
 from ..data.data_store import LazyBatch, gather_crop
 from .batch import DeviceBatch
-from .flax_tree import EmptyState, ScaleByAdamState, adam_moments, bc_paths, bc_shapes, trunk_from_flax
+from .flax_tree import AdamTrainState, bc_paths, bc_shapes, leaves_from_tree, trunk_from_flax, tree_from_leaves
 
 SLE_DIM = 512 * 8
 
 
-class BCTrainState:
+class BCTrainState(AdamTrainState):
     """agent.state: JaxRLTrainState-shaped (common.py:81-114), materialised from HBM on access.  BC has ONE optimizer
     over the whole tree, so `opt_states` is optax.adam's tuple (ScaleByAdamState(count, mu, nu), EmptyState()); the
     moments of every frozen leaf are exact zeros.  target_params equals params (BC never updates a target)."""
+
+    fields = ("step", "params", "target_params", "opt_states", "rng")
+    opt_field = "opt_states"
+    replace_error = TypeError
+    opt_states = property(AdamTrainState.adam_state)
 
     def __init__(self, agent):
         self._a = agent
@@ -40,112 +46,73 @@ class BCTrainState:
     def step(self):
         return int(self._a.L.serl_bc_get_step(self._a._h))
 
+    def _set_step(self, step):
+        _lib.check(self._a.L.serl_bc_set_step(self._a._h, step))
+
     @property
     def params(self):
-        return self._a._export("params")
+        return self._export("params")
 
     @property
     def target_params(self):
         return self.params
 
     @property
-    def opt_states(self):
-        a = self._a
-        return (ScaleByAdamState(np.int32(self.step), a._export("opt/mu"), a._export("opt/nu")), EmptyState())
-
-    @property
     def rng(self):
         return self._a._rng_key.copy()
 
-    def state_dict(self) -> dict:
-        """flax.serialization.to_state_dict form (what flax checkpoints store): tuples become {'0', '1', ...} and
-        NamedTuples dicts of their fields."""
-        adam, _ = self.opt_states
-        params = self.params
-        return {"step": np.int32(self.step), "params": params, "target_params": params,
-                "opt_states": {"0": {"count": adam.count, "mu": adam.mu, "nu": adam.nu}, "1": {}}, "rng": self.rng}
-
     def load_state_dict(self, sd: dict):
-        a = self._a
-        if sd.get("params") is not None:
-            a._import("params", sd["params"])
-        opt = sd.get("opt_states")
-        if opt is not None:
-            mu, nu = adam_moments(opt)
-            a._import("opt/mu", mu)
-            a._import("opt/nu", nu)
-        if sd.get("step") is not None:
-            _lib.check(a.L.serl_bc_set_step(a._h, int(np.asarray(sd["step"]))))
+        super().load_state_dict(sd)
         if sd.get("rng") is not None:
-            a._rng_key = np.asarray(sd["rng"], np.uint32).reshape(2).copy()
-        return a
+            self._a._rng_key = np.asarray(sd["rng"], np.uint32).reshape(2).copy()
+        return self._a
 
-    def replace(self, **kw):
-        bad = set(kw) - {"params", "target_params", "opt_states", "step", "rng"}
-        if bad:
-            raise TypeError(f"unknown TrainState fields: {sorted(bad)}")
-        self.load_state_dict(kw)
-        return self
+    def _export(self, section):
+        a = self._a
+        return tree_from_leaves(bc_paths(a.image_keys), bc_shapes(a.image_keys, a.H, a.W, a.S, a.A),
+                                lambda leaf: a.get(section, leaf))
+
+    def _import(self, tree, section):
+        a = self._a
+        paths = bc_paths(a.image_keys)
+        for leaf, v in leaves_from_tree(paths, tree):
+            v = np.asarray(v, np.float32)
+            if section != "params" and not a._trainable[leaf]:
+                if np.any(v):
+                    raise ValueError(f"{section} of the frozen leaf {'/'.join(paths[leaf])} is not zero")
+                continue
+            a.set(section, leaf, v)
 
 
-class _Info:
+class _Info(LazyInfo):
     """The info dict of one update: {'actor_loss', 'mse'}, copied on the device when the update is issued and read on
     first access (no host synchronisation per step)."""
 
     def __init__(self, dev):
-        self._dev, self._vals = dev, None
+        self._dev = dev
 
-    def _resolve(self):
-        if self._vals is None:
-            v = self._dev.cpu().numpy()
-            self._vals = {"actor_loss": float(v[0]), "mse": float(v[1])}
-        return self._vals
+    def _read(self):
+        v = self._dev.cpu().numpy()
+        return {"actor_loss": float(v[0]), "mse": float(v[1])}
 
-    def __getitem__(self, k):
-        return self._resolve()[k]
-
-    def items(self):
-        return self._resolve().items()
-
-    def keys(self):
-        return self._resolve().keys()
-
-    def __iter__(self):
-        return iter(self._resolve())
-
-    def __len__(self):
+    def __len__(self):   # known without reading the device
         return 2
 
-    def __repr__(self):
-        return repr(self._resolve())
 
+class BCAgent(Handle):
+    prefix = "serl_bc"
 
-class BCAgent:
     def __init__(self, image_keys, H, W, state_dim, act_dim, *, seed_key, max_batch=256, learning_rate=3e-4, device=0,
                  dropout=0.1, std_min=1e-5, std_max=5.0):
-        self.L = _lib.lib()
         self.image_keys = tuple(image_keys)
         self.H, self.W, self.S, self.A, self.max_batch, self.device = H, W, state_dim, act_dim, max_batch, device
         self.config = {"image_keys": self.image_keys}
-        cfg = SerlBcCfg(device, len(self.image_keys), H, W, state_dim, act_dim, max_batch, learning_rate, dropout, std_min, std_max)
-        h = C.c_void_p()
-        _lib.check(self.L.serl_bc_create(C.byref(cfg), C.byref(h)))
-        self._h = h
-        self._counts, self._trainable = {}, {}
-        name, cnt, tr = C.create_string_buffer(128), C.c_int64(), C.c_int()
-        for i in range(self.L.serl_bc_num_leaves(h)):
-            _lib.check(self.L.serl_bc_leaf_info(h, i, name, 128, C.byref(cnt), C.byref(tr)))
-            self._counts[name.value.decode()] = cnt.value
-            self._trainable[name.value.decode()] = bool(tr.value)
+        super().__init__(SerlBcCfg(device, len(self.image_keys), H, W, state_dim, act_dim, max_batch, learning_rate, dropout,
+                                   std_min, std_max))
         # BCAgent.create (bc.py:194-202): rng, init_rng = split(rng); rng, create_rng = split(rng); state.rng = create_rng
         self._rng_key = J.split(J.split(np.asarray(seed_key, np.uint32))[0])[1]
         self._db: Optional[DeviceBatch] = None
         self.state = BCTrainState(self)
-
-    def __del__(self):
-        h, self._h = getattr(self, "_h", None), None
-        if h:
-            self.L.serl_bc_destroy(h)
 
     # ------------------------------------------------------------------ construction (bc.py:118-204)
     @classmethod
@@ -183,15 +150,6 @@ class BCAgent:
         return agent
 
     # ------------------------------------------------------------------ flat leaves
-    def set(self, section, leaf, value):
-        a = np.ascontiguousarray(np.asarray(value, np.float32).reshape(-1))
-        _lib.check(self.L.serl_bc_set(self._h, section.encode(), leaf.encode(), a.ctypes.data_as(C.c_void_p), a.size))
-
-    def get(self, section, leaf):
-        out = np.empty(self._counts[leaf], np.float32)
-        _lib.check(self.L.serl_bc_get(self._h, section.encode(), leaf.encode(), out.ctypes.data_as(C.c_void_p), out.size))
-        return out
-
     def leaves(self, trainable: Optional[bool] = None):
         return [k for k in self._counts if trainable is None or self._trainable[k] == trainable]
 
@@ -209,32 +167,7 @@ class BCAgent:
         """utils/train_utils.py:69-130 on the BC tree: the pickle's {conv_init, norm_init, ResNetBlock_i} into the trunk."""
         return self.load_flat(trunk_from_flax(pretrained))
 
-    def _export(self, section):
-        tree: Dict = {}
-        shapes = bc_shapes(self.image_keys, self.H, self.W, self.S, self.A)
-        for leaf, path in bc_paths(self.image_keys).items():
-            d = tree
-            for p in path[:-1]:
-                d = d.setdefault(p, {})
-            d[path[-1]] = self.get(section, leaf).reshape(shapes[leaf])
-        return tree
-
-    def _import(self, section, tree):
-        for leaf, path in bc_paths(self.image_keys).items():
-            d = tree
-            for p in path:
-                d = d[p]
-            v = np.asarray(d, np.float32)
-            if section != "params" and not self._trainable[leaf]:
-                if np.any(v):
-                    raise ValueError(f"{section} of the frozen leaf {'/'.join(path)} is not zero")
-                continue
-            self.set(section, leaf, v)
-
     # ------------------------------------------------------------------ batches
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
     def _device_batch(self, B):
         if B > self.max_batch:
             raise ValueError(f"batch {B} > max_batch {self.max_batch} (BCAgent.create(batch_size=...))")

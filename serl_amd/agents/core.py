@@ -8,13 +8,16 @@ import numpy as np
 import torch
 
 from .. import _lib
+from .._handle import Handle
 from .._lib_agent import NET_BITS, TX_INDEX, SerlAgentCfg, SerlInfo, SerlNoise
 
 APPLY_CRITIC, APPLY_ACTOR_TEMP = 1, 6   # SERL_NET_CRITIC, SERL_NET_ACTOR | SERL_NET_TEMPERATURE
 TX_NAMES = ("actor", "critic", "temperature")
 
 
-class AgentCore:
+class AgentCore(Handle):
+    prefix = "serl_agent"
+
     def __init__(self, *, device=0, n_cam, H, W, state_dim, act_dim, batch, ensemble=10, hidden=256,
                  bottleneck=256, sle_features=8, proprio_dim=64, warmup_steps=0, discount=0.96,
                  tau=0.005, lr=3e-4, dropout=0.1, std_min=1e-5, std_max=5.0, target_entropy=None,
@@ -48,39 +51,15 @@ class AgentCore:
                 self.cfg.tx_weight_decay_on[i], self.cfg.tx_weight_decay[i] = 1, float(kw["weight_decay"])
             if kw.get("clip_grad_norm") is not None:
                 self.cfg.tx_clip_norm[i] = float(kw["clip_grad_norm"])
-        self._h = C.c_void_p()
-        self.L = _lib.lib()
-        _lib.check(self.L.serl_agent_create(C.byref(self.cfg), C.byref(self._h)))
         self.device = torch.device("cuda", device)
-        self.leaves = {}
-        buf = C.create_string_buffer(128)
-        cnt = C.c_int64()
-        for i in range(self.L.serl_agent_num_leaves(self._h)):
-            _lib.check(self.L.serl_agent_leaf_info(self._h, i, buf, 128, C.byref(cnt)))
-            self.leaves[buf.value.decode()] = int(cnt.value)
+        super().__init__(self.cfg)
         self._keep = None
 
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h is not None and h.value:
-            try:
-                self.L.serl_agent_destroy(h)
-            except Exception:
-                pass
-            self._h = C.c_void_p()
-
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
     # ---- parameters ------------------------------------------------------------------------
-    def set(self, section: str, leaf: str, value):
-        v = np.ascontiguousarray(np.asarray(value, dtype=np.float32).reshape(-1))
-        _lib.check(self.L.serl_agent_set(self._h, section.encode(), leaf.encode(), v.ctypes.data, v.size))
-
-    def get(self, section: str, leaf: str) -> np.ndarray:
-        out = np.empty(self.leaves[leaf], np.float32)
-        _lib.check(self.L.serl_agent_get(self._h, section.encode(), leaf.encode(), out.ctypes.data, out.size))
-        return out
+    @property
+    def leaves(self) -> Dict[str, int]:
+        """{leaf: element count}"""
+        return self._counts
 
     def set_trunk_mode(self, mode: str):
         """'f32' = exact fp32 MFMA convs, 'f16x3' = split-fp16 convs (default)."""

@@ -20,6 +20,7 @@ from ..data.data_store import LazyBatch, gather_crop
 from ..utils import init as pinit
 from .. import _lib
 from .. import jaxrng as J
+from .._handle import LazyInfo
 from .batch import DeviceBatch
 from .core import APPLY_ACTOR_TEMP, APPLY_CRITIC, TX_NAMES, AgentCore
 from .flax_tree import export_tree
@@ -38,44 +39,30 @@ def lr_schedule(kw: dict, count: int) -> float:
     return peak
 
 
-class PendingInfo:
+class PendingInfo(LazyInfo):
     """Info dict of the LAST update call; reading it synchronises the stream (the reference's jitted
     update returns device arrays that are also only materialised when logged)."""
 
     def __init__(self, agent, kind, serial):
-        self._agent, self._kind, self._serial, self._val = agent, kind, serial, None
+        self._agent, self._kind, self._serial = agent, kind, serial
 
-    def resolve(self) -> dict:
-        if self._val is None:
-            if self._agent._update_serial != self._serial:
-                raise RuntimeError("info of an older update was overwritten; read it before the next update")
-            r = self._agent.core.read_info()
-            lr = {f"{n}_lr": r[f"{n}_lr"] for n in TX_NAMES}
-            if isinstance(self._kind, frozenset):   # SACAgent.update: an info dict per network, {} for the skipped ones
-                nets = self._kind
-                out = {"critic": {k: r[k] for k in ("critic_loss", "predicted_qs", "target_qs")} if "critic" in nets else {},
-                       "actor": {k: r[k] for k in ("actor_loss", "temperature", "entropy")} if "actor" in nets else {},
-                       "temperature": {"temperature_loss": r["temperature_loss"]} if "temperature" in nets else {}}
-            else:
-                out = {"critic": {k: r[k] for k in ("critic_loss", "predicted_qs", "target_qs")}}
-                if self._kind == "high_utd":
-                    out["actor"] = {k: r[k] for k in ("actor_loss", "temperature", "entropy")}
-                    out["temperature"] = {"temperature_loss": r["temperature_loss"]}
-            out.update(lr)
-            self._val = out
-        return self._val
-
-    def __getitem__(self, k):
-        return self.resolve()[k]
-
-    def items(self):
-        return self.resolve().items()
-
-    def keys(self):
-        return self.resolve().keys()
-
-    def __repr__(self):
-        return repr(self.resolve())
+    def _read(self) -> dict:
+        if self._agent._update_serial != self._serial:
+            raise RuntimeError("info of an older update was overwritten; read it before the next update")
+        r = self._agent.core.read_info()
+        lr = {f"{n}_lr": r[f"{n}_lr"] for n in TX_NAMES}
+        if isinstance(self._kind, frozenset):   # SACAgent.update: an info dict per network, {} for the skipped ones
+            nets = self._kind
+            out = {"critic": {k: r[k] for k in ("critic_loss", "predicted_qs", "target_qs")} if "critic" in nets else {},
+                   "actor": {k: r[k] for k in ("actor_loss", "temperature", "entropy")} if "actor" in nets else {},
+                   "temperature": {"temperature_loss": r["temperature_loss"]} if "temperature" in nets else {}}
+        else:
+            out = {"critic": {k: r[k] for k in ("critic_loss", "predicted_qs", "target_qs")}}
+            if self._kind == "high_utd":
+                out["actor"] = {k: r[k] for k in ("actor_loss", "temperature", "entropy")}
+                out["temperature"] = {"temperature_loss": r["temperature_loss"]}
+        out.update(lr)
+        return out
 
 
 class TrainStateView:

@@ -36,11 +36,77 @@ def adam_moments(opt):
     return (adam.mu, adam.nu) if hasattr(adam, "mu") else (adam["mu"], adam["nu"])
 
 
-def _put(tree, path, value):
-    d = tree
-    for p in path[:-1]:
-        d = d.setdefault(p, {})
-    d[path[-1]] = value
+class AdamTrainState:
+    """TrainState fields of a handle trained by ONE optax.adam over its whole parameter tree (BC, the trainable reward
+    classifier): the optax tuple (ScaleByAdamState(count, mu, nu), EmptyState()) -- the moments of a frozen leaf are
+    exact zeros --, flax's state-dict form and `replace`.  `fields` are the TrainState's fields in flax's order and
+    `opt_field` the one that holds the optax tuple; the class provides `step`, `params` (and `rng` when it is a field),
+    `_export(section)` / `_import(tree, section)` of the trees "params", "opt/mu", "opt/nu" and `_set_step(step)`."""
+
+    fields = ("step", "params", "opt_state")
+    opt_field = "opt_state"
+    replace_error = NotImplementedError
+
+    def adam_state(self):
+        return (ScaleByAdamState(np.int32(self.step), self._export("opt/mu"), self._export("opt/nu")), EmptyState())
+
+    def state_dict(self) -> dict:
+        """flax.serialization.to_state_dict form (what flax checkpoints store): tuples become {'0', '1', ...} and
+        NamedTuples dicts of their fields; target_params, where it is a field, equals params."""
+        adam, _ = self.adam_state()
+        params = self.params
+        sd = {"step": np.int32(self.step), "params": params, "target_params": params,
+              self.opt_field: {"0": {"count": adam.count, "mu": adam.mu, "nu": adam.nu}, "1": {}}}
+        if "rng" in self.fields:
+            sd["rng"] = self.rng
+        return {f: sd[f] for f in self.fields}
+
+    def load_state_dict(self, sd: dict):
+        if sd.get("params") is not None:
+            self._import(sd["params"], "params")
+        opt = sd.get(self.opt_field)
+        if opt is not None:
+            mu, nu = adam_moments(opt)
+            self._import(mu, "opt/mu")
+            self._import(nu, "opt/nu")
+        if sd.get("step") is not None:
+            self._set_step(int(np.asarray(sd["step"])))
+        return self
+
+    def replace(self, **kw):
+        bad = set(kw) - set(self.fields)
+        if bad:
+            raise self.replace_error(f"unknown TrainState fields: {sorted(bad)}")
+        self.load_state_dict(kw)
+        return self
+
+
+def _aliases(path):
+    """the paths of one leaf: theta_paths lists aliases, the other tables give one path"""
+    return path if isinstance(path, list) else [path]
+
+
+def tree_from_leaves(paths, shapes, get) -> Dict:
+    """{leaf: path} table -> nested dict holding get(leaf).reshape(shapes[leaf]) at the leaf's path (one array at
+    every alias)."""
+    tree: Dict = {}
+    for leaf, path in paths.items():
+        v = get(leaf).reshape(shapes[leaf])
+        for p in _aliases(path):
+            d = tree
+            for k in p[:-1]:
+                d = d.setdefault(k, {})
+            d[p[-1]] = v
+    return tree
+
+
+def leaves_from_tree(paths, tree):
+    """{leaf: path} table, nested dict -> (leaf, the value at its (first) path)"""
+    for leaf, path in paths.items():
+        d = tree
+        for k in _aliases(path)[0]:
+            d = d[k]
+        yield leaf, d
 
 
 def _trunk_paths():
@@ -154,15 +220,21 @@ def bc_paths(image_keys):
     return m
 
 
-def bc_shapes(image_keys, H, W, S, A, hidden=256, bottleneck=256, proprio_dim=64):
-    """flat BC leaf -> flax shape"""
+def _camera_shapes(n_cam, H, W, bottleneck):
+    """flat leaf -> flax shape of the per-camera heads on the frozen trunk (enc/<i>/...)"""
     from ..utils.init import feat_hw
     fh, fw = feat_hw(H, W)
-    sh = dict(trunk_shapes())
-    for i in range(len(image_keys)):
+    sh = {}
+    for i in range(n_cam):
         sh[f"enc/{i}/sle"] = (fh, fw, 512, 8)
         sh[f"enc/{i}/dense/kernel"] = (512 * 8, bottleneck)
         sh[f"enc/{i}/dense/bias"] = sh[f"enc/{i}/ln/scale"] = sh[f"enc/{i}/ln/bias"] = (bottleneck,)
+    return sh
+
+
+def bc_shapes(image_keys, H, W, S, A, hidden=256, bottleneck=256, proprio_dim=64):
+    """flat BC leaf -> flax shape"""
+    sh = dict(trunk_shapes(), **_camera_shapes(len(image_keys), H, W, bottleneck))
     sh["enc/proprio/dense/kernel"] = (S, proprio_dim)
     sh["enc/proprio/dense/bias"] = sh["enc/proprio/ln/scale"] = sh["enc/proprio/ln/bias"] = (proprio_dim,)
     sh["actor/w1"], sh["actor/b1"] = (bottleneck * len(image_keys) + proprio_dim, hidden), (hidden,)
@@ -183,37 +255,25 @@ def export_tree(core, section: str, image_keys, duplicate_encoder_under_critic: 
     cfg = core.cfg
     etype = "small" if cfg.encoder_type == 1 else "resnet-pretrained"
     shapes = theta_shapes(cfg.n_cam, cfg.H, cfg.W, cfg.state_dim, cfg.act_dim, ensemble=cfg.ensemble, encoder_type=etype)
-    tree: Dict = {}
-    for leaf, paths in theta_paths(image_keys, critic_mlp_name, etype).items():
-        v = core.get(section, leaf).reshape(shapes[leaf])
-        for p in paths:
-            _put(tree, p, v)
-            if duplicate_encoder_under_critic and p[:2] == ("modules_actor", "encoder"):
-                _put(tree, ("modules_critic",) + p[1:], v)
-    tshapes = trunk_shapes()
-    for leaf, sub in (_trunk_paths() if (cfg.n_cam and etype != "small") else {}).items():
-        v = core.get(section, leaf).reshape(tshapes[leaf])
+    shapes.update(trunk_shapes())
+    paths = theta_paths(image_keys, critic_mlp_name, etype)
+    if cfg.n_cam and etype != "small":
         # ONE frozen trunk: drq.py:165-176 passes the same `pretrained_encoder` module to every camera's
         # PreTrainedResNetEncoder, flax adopts a shared module once -- under the first camera in sorted-key order --
         # which is why train_utils.py:118-123 guards with `if "pretrained_encoder" in new_encoder_params`
         owners = image_keys if trunk_under_every_camera else (trunk_owner(image_keys),)
-        for k in owners:
-            _put(tree, ("modules_actor", "encoder", f"encoder_{k}", "pretrained_encoder") + sub, v)
-            if duplicate_encoder_under_critic:
-                _put(tree, ("modules_critic", "encoder", f"encoder_{k}", "pretrained_encoder") + sub, v)
-    return tree
+        for leaf, sub in _trunk_paths().items():
+            paths[leaf] = [("modules_actor", "encoder", f"encoder_{k}", "pretrained_encoder") + sub for k in owners]
+    if duplicate_encoder_under_critic:
+        for leaf, ps in paths.items():
+            paths[leaf] = [q for p in ps
+                           for q in ([p, ("modules_critic",) + p[1:]] if p[:2] == ("modules_actor", "encoder") else [p])]
+    return tree_from_leaves(paths, shapes, lambda leaf: core.get(section, leaf))
 
 
 def trunk_from_flax(pretrained: Dict) -> Dict[str, np.ndarray]:
     """resnet10_params.pkl tree -> flat leaves.  Top-level keys are matched by name and a top-level key the pickle
     does not hold keeps its current value (train_utils.py:124-127: `for k in new_encoder_params: if k in encoder_params`);
     a top-level key that is present must hold the whole sub-tree."""
-    out = {}
-    for leaf, sub in _trunk_paths().items():
-        if sub[0] not in pretrained:
-            continue
-        d = pretrained
-        for p in sub:
-            d = d[p]
-        out[leaf] = np.asarray(d, np.float32)
-    return out
+    present = {leaf: sub for leaf, sub in _trunk_paths().items() if sub[0] in pretrained}
+    return {leaf: np.asarray(v, np.float32) for leaf, v in leaves_from_tree(present, pretrained)}

@@ -23,40 +23,13 @@ import torch
 
 from .. import _lib
 from .. import jaxrng as J
+from .._handle import Handle
+from .._lib_agent import SerlClassifierCfg
 from ..agents.flax_tree import CAM_PATHS as _CAM_PATHS
-from ..agents.flax_tree import EmptyState, ScaleByAdamState, _trunk_paths, adam_moments, trunk_from_flax, trunk_owner
-
-
-class SerlClassifierCfg(C.Structure):
-    _fields_ = [("device", C.c_int), ("n_cam", C.c_int), ("H", C.c_int), ("W", C.c_int), ("max_batch", C.c_int)]
-
-
-def _declare(lib):
-    if getattr(lib, "_serl_classifier_declared", False):
-        return
-    vp, i32, i64 = C.c_void_p, C.c_int, C.c_int64
-    sigs = {
-        "serl_classifier_create": [C.POINTER(SerlClassifierCfg), C.POINTER(vp)],
-        "serl_classifier_destroy": [vp],
-        "serl_classifier_num_leaves": [vp],
-        "serl_classifier_leaf_info": [vp, i32, C.c_char_p, i32, C.POINTER(i64)],
-        "serl_classifier_set": [vp, C.c_char_p, vp, i64],
-        "serl_classifier_get": [vp, C.c_char_p, vp, i64],
-        "serl_classifier_logits": [vp, vp, i32, vp, vp],
-        "serl_classifier_train_init": [vp, i32, C.c_float, C.c_float, C.c_float, C.c_float],
-        "serl_classifier_train_step": [vp, vp, i32, vp, vp, vp, vp],
-        "serl_classifier_train_forward": [vp, vp, i32, vp, vp, vp, vp],
-        "serl_classifier_read_train_info": [vp, vp, vp],
-        "serl_classifier_train_set_step": [vp, i64],
-        "serl_classifier_train_get_step": [vp, C.POINTER(i64)],
-        "serl_classifier_train_set": [vp, C.c_char_p, C.c_char_p, vp, i64],
-        "serl_classifier_train_get": [vp, C.c_char_p, C.c_char_p, vp, i64],
-    }
-    for name, args in sigs.items():
-        fn = getattr(lib, name)
-        fn.argtypes = args
-        fn.restype = i32
-    lib._serl_classifier_declared = True
+from ..agents.flax_tree import (AdamTrainState, _camera_shapes, _trunk_paths, leaves_from_tree, tree_from_leaves,
+                                trunk_from_flax, trunk_owner)
+from ..agents.flax_tree import EmptyState, ScaleByAdamState  # noqa: F401  (the types `opt_state` holds, importable from here)
+from ..utils.init import trunk_shapes
 
 
 _HEAD_PATHS = {   # flat leaf -> path in BinaryClassifier's parameter tree (flax auto-names, reward_classifier.py:20-28)
@@ -67,6 +40,27 @@ _HEAD_PATHS = {   # flat leaf -> path in BinaryClassifier's parameter tree (flax
 
 SLE_DIM = 512 * 8
 HIDDEN = 256
+
+
+def _tree_paths(image_keys):
+    """flat leaf -> path in the parameter tree: the camera heads under encoder_def/encoder_<key>, the ONE shared frozen
+    trunk under the first camera in sorted-key order (:37-51), the classifier head at the root."""
+    m = {}
+    for i, k in enumerate(image_keys):
+        for leaf, sub in _CAM_PATHS.items():
+            m[f"enc/{i}/{leaf}"] = ("encoder_def", f"encoder_{k}") + sub
+    for leaf, sub in _trunk_paths().items():
+        m[leaf] = ("encoder_def", f"encoder_{trunk_owner(image_keys)}", "pretrained_encoder") + sub
+    return {**m, **_HEAD_PATHS}
+
+
+def _tree_shapes(image_keys, H, W):
+    """flat leaf -> flax shape"""
+    sh = dict(trunk_shapes(), **_camera_shapes(len(image_keys), H, W, 256))
+    sh["head/dense0/kernel"], sh["head/dense0/bias"] = (256 * len(image_keys), HIDDEN), (HIDDEN,)
+    sh["head/ln/scale"] = sh["head/ln/bias"] = (HIDDEN,)
+    sh["head/dense1/kernel"], sh["head/dense1/bias"] = (HIDDEN, 1), (1,)
+    return sh
 
 
 def dropout_paths(image_keys) -> List[tuple]:
@@ -92,46 +86,38 @@ def _stacked(frames):
     return torch.stack(frames).contiguous()
 
 
-class Classifier:
+class Classifier(Handle, AdamTrainState):
     """The role of the reference's `TrainState`: `.params` (flax-layout tree) and
     `.apply_fn({"params": params}, obs, train=False)`; parameters live in HBM.  With trainable=True also `.step`,
     `.opt_state` (optax.adam's (ScaleByAdamState(count, mu, nu), EmptyState()); the frozen trunk's moments are zeros),
     apply_fn(..., train=True, rngs={"dropout": key}) and `train_step`."""
 
+    prefix = "serl_classifier"
+    opt_state = property(AdamTrainState.adam_state)
+
     def __init__(self, image_keys, H, W, max_batch=64, device=0, trainable=False, learning_rate=1e-4):
-        self.L = _lib.lib()
-        _declare(self.L)
         self.image_keys = tuple(image_keys)
         self.H, self.W, self.max_batch, self.device = H, W, max_batch, device
-        cfg = SerlClassifierCfg(device, len(self.image_keys), H, W, max_batch)
-        h = C.c_void_p()
-        _lib.check(self.L.serl_classifier_create(C.byref(cfg), C.byref(h)))
-        self._h = h
+        super().__init__(SerlClassifierCfg(device, len(self.image_keys), H, W, max_batch))
         self.trainable = bool(trainable)
         if self.trainable:   # TrainState.create(tx=optax.adam(learning_rate)) (reward_classifier.py:62-66)
-            _lib.check(self.L.serl_classifier_train_init(h, int(max_batch), float(learning_rate), 0.9, 0.999, 1e-8))
-        self._counts = {}
-        name = C.create_string_buffer(128)
-        cnt = C.c_int64()
-        for i in range(self.L.serl_classifier_num_leaves(h)):
-            _lib.check(self.L.serl_classifier_leaf_info(h, i, name, 128, C.byref(cnt)))
-            self._counts[name.value.decode()] = cnt.value
+            _lib.check(self.L.serl_classifier_train_init(self._h, int(max_batch), float(learning_rate), 0.9, 0.999, 1e-8))
 
-    def __del__(self):
-        h, self._h = getattr(self, "_h", None), None
-        if h:
-            self.L.serl_classifier_destroy(h)
+    # ---- flat leaves: the public set / get address the parameters, _set / _get any section ("params", "opt/mu", "opt/nu")
+    _set, _get = Handle.set, Handle.get
 
-    # ---- flat leaves
     def set(self, leaf, value):
-        a = np.ascontiguousarray(np.asarray(value, np.float32).reshape(-1))
-        self._params_cache = None
-        _lib.check(self.L.serl_classifier_set(self._h, leaf.encode(), a.ctypes.data_as(C.c_void_p), a.size))
+        self._set("params", leaf, value)
 
     def get(self, leaf):
-        out = np.empty(self._counts[leaf], np.float32)
-        _lib.check(self.L.serl_classifier_get(self._h, leaf.encode(), out.ctypes.data_as(C.c_void_p), out.size))
-        return out
+        return self._get("params", leaf)
+
+    def _leaf_call(self, op, section, leaf, data, count):
+        if section != "params":   # the Adam moments of the training state
+            return super()._leaf_call("train_" + op, section, leaf, data, count)
+        if op == "set":
+            self._params_cache = None
+        return self._fn(op)(self._h, leaf.encode(), data, count)
 
     def _leaf(self, k, leaf):
         return f"enc/{self.image_keys.index(k)}/{leaf}"
@@ -153,71 +139,32 @@ class Classifier:
             self._params_cache = self._export()
         return self._params_cache
 
-    def _get(self, section, leaf):
-        if section == "params":
-            return self.get(leaf)
-        out = np.empty(self._counts[leaf], np.float32)
-        _lib.check(self.L.serl_classifier_train_get(self._h, section.encode(), leaf.encode(), out.ctypes.data_as(C.c_void_p), out.size))
-        return out
-
-    def _set(self, section, leaf, value):
-        if section == "params":
-            return self.set(leaf, value)
-        a = np.ascontiguousarray(np.asarray(value, np.float32).reshape(-1))
-        _lib.check(self.L.serl_classifier_train_set(self._h, section.encode(), leaf.encode(), a.ctypes.data_as(C.c_void_p), a.size))
-
     def _export(self, section="params"):
-        from ..utils.init import trunk_shapes
-        tree = {"encoder_def": {}}
-        tsh = trunk_shapes()
-        for k in self.image_keys:
-            sub = tree["encoder_def"].setdefault(f"encoder_{k}", {})
-            for leaf, (mod, name) in _CAM_PATHS.items():
-                v = self._get(section, self._leaf(k, leaf))
-                shape = {"sle": (-1, 512, 8), "dense/kernel": (4096, 256)}.get(leaf, (-1,))
-                if leaf == "sle":
-                    hw = v.size // (512 * 8)
-                    side = int(round(hw ** 0.5))
-                    shape = (side, hw // side, 512, 8)
-                sub.setdefault(mod, {})[name] = v.reshape(shape)
-        owner = tree["encoder_def"][f"encoder_{trunk_owner(self.image_keys)}"]   # ONE shared frozen trunk (:37-51)
-        for leaf, path in _trunk_paths().items():
-            d = owner.setdefault("pretrained_encoder", {})
-            for p in path[:-1]:
-                d = d.setdefault(p, {})
-            d[path[-1]] = self._get(section, leaf).reshape(tsh[leaf])
-        E = 256 * len(self.image_keys)
-        for leaf, (mod, name) in _HEAD_PATHS.items():
-            shape = {"head/dense0/kernel": (E, 256), "head/dense1/kernel": (256, 1)}.get(leaf, (-1,))
-            tree.setdefault(mod, {})[name] = self._get(section, leaf).reshape(shape)
-        return tree
+        return tree_from_leaves(_tree_paths(self.image_keys), _tree_shapes(self.image_keys, self.H, self.W),
+                                lambda leaf: self._get(section, leaf))
 
     def load_params(self, tree, section="params"):
         """A BinaryClassifier parameter tree (e.g. the `params` entry of a checkpoint the reference's trainer wrote); with
         section "opt/mu" / "opt/nu" an Adam moment tree of the same layout."""
-        if section == "params":
-            self._params_cache = None
-        enc = tree["encoder_def"]
-        for k in self.image_keys:
-            sub = enc[f"encoder_{k}"]
-            for leaf, (mod, name) in _CAM_PATHS.items():
-                self._set(section, self._leaf(k, leaf), sub[mod][name])
+        trunk = _trunk_paths()
+        heads = {leaf: p for leaf, p in _tree_paths(self.image_keys).items() if leaf not in trunk}
+        for leaf, v in leaves_from_tree(heads, tree):
+            self._set(section, leaf, v)
+        for k in self.image_keys:   # the shared trunk, under whichever camera holds it
+            sub = tree["encoder_def"][f"encoder_{k}"]
             if "pretrained_encoder" in sub:
                 for leaf, v in trunk_from_flax(sub["pretrained_encoder"]).items():
                     self._set(section, leaf, v)
-        for leaf, (mod, name) in _HEAD_PATHS.items():
-            self._set(section, leaf, tree[mod][name])
         return self
 
+    _import = load_params
+
     def replace(self, params=None, **kw):
-        bad = set(kw) - ({"step", "opt_state"} if self.trainable else set())
-        if bad:
-            raise NotImplementedError(sorted(bad))
-        if params is not None:
-            self.load_params(params)
-        if kw:
-            self.load_state_dict(kw)
-        return self
+        """flax TrainState.replace; an inference-only classifier takes `params` only."""
+        if not kw:
+            return self if params is None else self.load_params(params)
+        self._need_training()
+        return super().replace(params=params, **kw)
 
     # ---- training state (flax TrainState fields, reward_classifier.py:61-66)
     def _need_training(self):
@@ -231,33 +178,12 @@ class Classifier:
         _lib.check(self.L.serl_classifier_train_get_step(self._h, C.byref(out)))
         return int(out.value)
 
-    @property
-    def opt_state(self):
-        self._need_training()
-        return (ScaleByAdamState(np.int32(self.step), self._export("opt/mu"), self._export("opt/nu")), EmptyState())
-
-    def state_dict(self) -> dict:
-        """flax.serialization.to_state_dict(TrainState) -- what checkpoints.save_checkpoint stores: {step, params,
-        opt_state: {"0": {count, mu, nu}, "1": {}}} (apply_fn and tx are not pytree nodes)."""
-        adam, _ = self.opt_state
-        return {"step": np.int32(self.step), "params": self.params,
-                "opt_state": {"0": {"count": adam.count, "mu": adam.mu, "nu": adam.nu}, "1": {}}}
+    def _set_step(self, step):
+        _lib.check(self.L.serl_classifier_train_set_step(self._h, step))
 
     def load_state_dict(self, sd: dict):
         self._need_training()
-        if sd.get("params") is not None:
-            self.load_params(sd["params"])
-        opt = sd.get("opt_state")
-        if opt is not None:
-            mu, nu = adam_moments(opt)
-            self.load_params(mu, "opt/mu")
-            self.load_params(nu, "opt/nu")
-        if sd.get("step") is not None:
-            _lib.check(self.L.serl_classifier_train_set_step(self._h, int(np.asarray(sd["step"]))))
-        return self
-
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        return super().load_state_dict(sd)
 
     def _device_frames(self, observations):
         """{image_key: u8 (T=1, H, W, 3) or (B, T=1, H, W, 3), host or device} -> (u8[n_cam][n][H][W][3] on the device, batched)"""

@@ -20,7 +20,7 @@ import msgpack
 import numpy as np
 
 from ..agents.core import TX_NAMES
-from ..agents.flax_tree import theta_paths, trunk_owner, _trunk_paths
+from ..agents.flax_tree import leaves_from_tree, theta_paths, trunk_owner, _trunk_paths
 
 _EXT_NDARRAY = 1
 
@@ -80,12 +80,6 @@ def latest_checkpoint(ckpt_dir: str, prefix: str = "checkpoint_") -> Optional[st
         return None
     steps = [int(m.group(1)) for m in (re.fullmatch(re.escape(prefix) + r"(\d+)", n) for n in os.listdir(ckpt_dir)) if m]
     return os.path.join(ckpt_dir, f"{prefix}{max(steps)}") if steps else None
-
-
-def _walk(tree, path):
-    for p in path:
-        tree = tree[p]
-    return tree
 
 
 def restore_checkpoint(ckpt_dir_or_file: str, agent, step: Optional[int] = None, prefix: str = "checkpoint_"):
@@ -148,29 +142,28 @@ def load_state_dict(agent, sd: dict):
         tree = sd.get(section)
         if tree is None:
             continue
-        for leaf, paths in tp.items():
-            core.set(section, leaf, _walk(tree, paths[0]))
+        for leaf, v in leaves_from_tree(tp, tree):
+            core.set(section, leaf, v)
         if trunk:
             # Where flax puts the ONE shared frozen trunk is derived from its adoption rule (first camera in sorted-key
             # order) and unverified against a real flax install: accept it under any camera, like
             # reward_classifier.load_params and the reference's own `if "pretrained_encoder" in ...` guard do
-            enc = _walk(tree, ("modules_actor", "encoder"))
+            enc = tree["modules_actor"]["encoder"]
             owners = [k for k in [trunk_owner(keys)] + sorted(keys) if "pretrained_encoder" in enc.get(f"encoder_{k}", {})]
             if not owners:
                 raise KeyError(f"'{section}' holds no pretrained_encoder under any of encoder_{{{', '.join(sorted(keys))}}}")
             root = enc[f"encoder_{owners[0]}"]["pretrained_encoder"]
-            for leaf, sub in trunk.items():
-                core.set(section, leaf, _walk(root, sub))
+            for leaf, v in leaves_from_tree(trunk, root):
+                core.set(section, leaf, v)
     if sd.get("opt_states") is not None:
         for tx in TX_NAMES:
             adam = _find_adam_state(sd["opt_states"][tx])
             if adam is None:
                 raise KeyError(f"opt_states['{tx}'] holds no ScaleByAdamState (mu / nu)")
             for mom in ("mu", "nu"):
-                tree = adam[mom]
-                for leaf, paths in tp.items():
+                for leaf, v in leaves_from_tree(tp, adam[mom]):
                     # leaves outside the optimizer's support are exact zeros; the C ABI accepts (and checks) them
-                    core.set(f"opt/{tx}/{mom}", leaf, np.asarray(_walk(tree, paths[0]), np.float32))
+                    core.set(f"opt/{tx}/{mom}", leaf, np.asarray(v, np.float32))
     if sd.get("step") is not None:
         core.step = int(np.asarray(sd["step"]))
     return agent
