@@ -474,6 +474,25 @@ typedef struct serl_jax_job {
   void* out;            /* device */
 } serl_jax_job;
 int serl_jax_fill(int device, const serl_jax_job* jobs, int n, void* stream);
+/* Parameter initialisers (jax.nn.initializers.variance_scaling's draws, jax/_src/random.py of jax 0.4.x): job i writes the
+ * whole flat f32 array of `count` elements that one call returns, times `scale` (float32 ops, in this order):
+ *   SERL_JAX_INIT_UNIFORM           jax.random.uniform(key, shape, f32, minval, maxval) * scale
+ *   SERL_JAX_INIT_TRUNCATED_NORMAL  jax.random.truncated_normal(key, minval, maxval, shape, f32) * scale
+ *   SERL_JAX_INIT_NORMAL            jax.random.normal(key, shape, f32) * scale            (minval / maxval unused)
+ * erf is XLA's float32 rational approximation, erf_inv XLA's ErfInv32 with log1p rounded from double precision, so that
+ * device and host results agree bit for bit.  serl_jax_init_fill: one launch per 64 jobs on `stream`, `out` in device memory;
+ * serl_jax_init_host: one job on the host, `out` in host memory. */
+enum { SERL_JAX_INIT_UNIFORM = 0, SERL_JAX_INIT_TRUNCATED_NORMAL = 1, SERL_JAX_INIT_NORMAL = 2 };
+typedef struct serl_jax_init_job {
+  uint32_t key[2];
+  int32_t kind;
+  float minval, maxval;  /* uniform: [minval, maxval); truncated normal: the bounds (lower, upper) */
+  float scale;
+  int64_t count;
+  void* out;
+} serl_jax_init_job;
+int serl_jax_init_fill(int device, const serl_jax_init_job* jobs, int n, void* stream);
+int serl_jax_init_host(const serl_jax_init_job* job);
 
 #ifdef __cplusplus
 }

@@ -62,6 +62,8 @@ SIGNATURES = {
     "serl_jax_crop_offsets": [P(u32), i32, i32, P(i32)],
     "serl_jax_update_keys": [P(u32), i32, i32, i32, i32, vp],
     "serl_jax_fill": [i32, vp, i32, vp],
+    "serl_jax_init_fill": [i32, vp, i32, vp],
+    "serl_jax_init_host": [vp],
 }
 RESTYPES = {"serl_last_error": C.c_char_p, "serl_rb_len": i64, "serl_rb_insert_index": i64}
 

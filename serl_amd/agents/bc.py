@@ -118,11 +118,15 @@ class BCAgent(Handle):
     @classmethod
     def create(cls, rng, observations, actions, encoder_type: str = "small", image_keys: Iterable[str] = ("image",),
                use_proprio: bool = False, network_kwargs: dict = None, policy_kwargs: dict = None,
-               learning_rate: float = 3e-4, batch_size: int = 256, device: int = 0, param_seed: Optional[int] = None):
+               learning_rate: float = 3e-4, batch_size: int = 256, device: int = 0, param_seed: Optional[int] = None,
+               param_init: str = "numpy"):
         """`rng`: a jax.random key (uint32[2]) or an int seed.  Only the frozen pretrained ResNet-10 encoder is served.
         As for DrQAgent.create_drq, the trunk keeps its initialiser's values until the caller runs
         utils.train_utils.load_resnet10_params(agent, image_keys) (the reference calls it at the end of create, bc.py:200-203,
-        and downloads the pickle when it is absent; there is no download here)."""
+        and downloads the pickle when it is absent; there is no download here).
+        param_init: "numpy" (default) or "reference" (the reference's own initialisers and keys from `rng`, utils/init_ref.py)."""
+        from ..utils import init_ref
+        reference = init_ref.check_param_init(param_init)
         if encoder_type != "resnet-pretrained":
             raise ValueError(f"encoder_type {encoder_type!r}: only 'resnet-pretrained' is implemented for BC on this library")
         if not use_proprio:
@@ -145,7 +149,10 @@ class BCAgent(Handle):
         from ..utils.init import init_theta, init_trunk
         seed = int(key[1]) if param_seed is None else param_seed
         agent.load_flat(init_trunk(seed))
-        theta = init_theta(len(image_keys), H, W, S, A, seed=seed)
+        if reference:
+            theta = init_ref.bc_reference(image_keys, H, W, S, A, key, device=device)
+        else:
+            theta = init_theta(len(image_keys), H, W, S, A, seed=seed)
         agent.load_flat({k: v for k, v in theta.items() if k in agent._counts})
         return agent
 
@@ -282,11 +289,12 @@ class BCAgent(Handle):
 
 
 def make_bc_agent(seed, sample_obs, sample_action, image_keys=("image",), encoder_type="resnet-pretrained",
-                  batch_size=256, device=0):
+                  batch_size=256, device=0, param_init="numpy"):
     """launcher.py:26-47 (hyper-parameters copied from there).  The reference's default encoder_type "small" raises at this
     reference commit; only "resnet-pretrained" is served here."""
     return BCAgent.create(
         J.prngkey(seed), sample_obs, sample_action,
         network_kwargs={"activations": "tanh", "use_layer_norm": False, "hidden_dims": [256, 256]},
         policy_kwargs={"tanh_squash_distribution": False, "std_parameterization": "exp", "std_min": 1e-5, "std_max": 5},
-        use_proprio=True, encoder_type=encoder_type, image_keys=image_keys, batch_size=batch_size, device=device)
+        use_proprio=True, encoder_type=encoder_type, image_keys=image_keys, batch_size=batch_size, device=device,
+        param_init=param_init)

@@ -18,6 +18,7 @@ import torch
 
 from ..data.data_store import LazyBatch, gather_crop
 from ..utils import init as pinit
+from ..utils import init_ref
 from .. import _lib
 from .. import jaxrng as J
 from .._handle import LazyInfo
@@ -167,10 +168,12 @@ class DrQAgent:
                    target_entropy: Optional[float] = None, backup_entropy: bool = False,
                    batch_size: int = 256, device: int = 0, learning_rate: float = 3e-4,
                    actor_optimizer_kwargs: dict = None, critic_optimizer_kwargs: dict = None,
-                   temperature_optimizer_kwargs: dict = None, **kwargs):
+                   temperature_optimizer_kwargs: dict = None, param_init: str = "numpy", **kwargs):
         """drq.py:104-242.  Only the configuration the reference's examples run is built natively:
         encoder_type="resnet-pretrained", use_proprio=True, REDQ subsample 2, tanh-squashed
-        exp-parameterised policy, LayerNorm+tanh 256x256 MLPs (utils/launcher.py:79-116)."""
+        exp-parameterised policy, LayerNorm+tanh 256x256 MLPs (utils/launcher.py:79-116).
+        param_init: "numpy" (default) draws the trainable leaves from host NumPy streams seeded by `rng`; "reference" draws them
+        as the reference's model_def.init(init_rng) does (utils/init_ref.py); the frozen trunk is the same either way."""
         if encoder_type not in ("resnet-pretrained", "small"):
             # drq.py:155-167 also has "resnet" (trainable ResNet-10, never selected by an example: not built)
             raise NotImplementedError(f"Unknown encoder type: {encoder_type}")
@@ -200,8 +203,12 @@ class DrQAgent:
                          std_max=pk.get("std_max", 10.0), target_entropy=target_entropy, seed=seed,
                          optimizers={k: {"warmup_steps": 0, **v} for k, v in opts.items()}, encoder_type=encoder_type,
                          critic_subsample_size=critic_subsample_size, backup_entropy=backup_entropy)
-        theta = pinit.init_theta(len(image_keys), H, W, S, A, seed=seed, temperature_init=temperature_init,
-                                 ensemble=critic_ensemble_size, encoder_type=encoder_type)
+        if init_ref.check_param_init(param_init):
+            theta = init_ref.theta_reference(image_keys, H, W, S, A, rng, ensemble=critic_ensemble_size, encoder_type=encoder_type,
+                                             temperature_init=temperature_init, device=device)
+        else:
+            theta = pinit.init_theta(len(image_keys), H, W, S, A, seed=seed, temperature_init=temperature_init,
+                                     ensemble=critic_ensemble_size, encoder_type=encoder_type)
         trunk = pinit.init_trunk(seed=seed) if encoder_type == "resnet-pretrained" else {}
         for sec in ("params", "target_params"):  # JaxRLTrainState.create(target_params=params)
             core.load_flat(sec, theta)
@@ -211,6 +218,8 @@ class DrQAgent:
                       target_entropy=target_entropy, backup_entropy=backup_entropy, image_keys=image_keys)
         agent = cls(core, image_keys, config, seed)
         agent._opts = {k: {"warmup_steps": 0, **v} for k, v in opts.items()}
+        if param_init == "reference":
+            agent._rng_key = init_ref.create_rng_of(rng)
         return agent
 
     def lr_at(self, count, tx="critic"):

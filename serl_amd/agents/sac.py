@@ -15,6 +15,7 @@ import torch
 
 from ..data.data_store import LazyBatch, gather_crop
 from ..utils import init as pinit
+from ..utils import init_ref
 from .batch import DeviceBatch
 from .core import AgentCore
 from .drq import DrQAgent
@@ -30,9 +31,11 @@ class SACAgent(DrQAgent):
                       discount: float = 0.95, soft_target_update_rate: float = 0.005,
                       target_entropy: Optional[float] = None, backup_entropy: bool = False,
                       actor_optimizer_kwargs: dict = None, critic_optimizer_kwargs: dict = None,
-                      temperature_optimizer_kwargs: dict = None, batch_size: int = 256, device: int = 0, **kwargs):
+                      temperature_optimizer_kwargs: dict = None, batch_size: int = 256, device: int = 0, param_init: str = "numpy",
+                      **kwargs):
         """sac.py:486-542 -> create (:323-400).  Built natively: the configuration of utils/launcher.py:50-76
-        (REDQ subsample 2, tanh-squashed exp-parameterised policy, LayerNorm+tanh 256x256 MLPs)."""
+        (REDQ subsample 2, tanh-squashed exp-parameterised policy, LayerNorm+tanh 256x256 MLPs).
+        param_init: "numpy" (default) or "reference" (the reference's own initialisers and keys, utils/init_ref.py)."""
         pk = policy_kwargs or {}
         if pk.get("std_parameterization", "exp") != "exp" or not pk.get("tanh_squash_distribution", True):
             raise NotImplementedError("policy must be tanh-squashed with std_parameterization='exp'")
@@ -54,7 +57,11 @@ class SACAgent(DrQAgent):
                          std_max=pk.get("std_max", 10.0), target_entropy=target_entropy, seed=seed,
                          optimizers={"actor": ao, "critic": co, "temperature": {"warmup_steps": 0, **to}},
                          critic_subsample_size=critic_subsample_size, backup_entropy=backup_entropy)
-        theta = pinit.init_theta(0, 0, 0, S, A, seed=seed, temperature_init=temperature_init, ensemble=critic_ensemble_size)
+        if init_ref.check_param_init(param_init):
+            theta = init_ref.theta_reference((), 0, 0, S, A, rng, ensemble=critic_ensemble_size, temperature_init=temperature_init,
+                                             device=device)
+        else:
+            theta = pinit.init_theta(0, 0, 0, S, A, seed=seed, temperature_init=temperature_init, ensemble=critic_ensemble_size)
         for sec in ("params", "target_params"):
             core.load_flat(sec, theta)
         config = dict(critic_ensemble_size=critic_ensemble_size, critic_subsample_size=critic_subsample_size,
@@ -62,6 +69,8 @@ class SACAgent(DrQAgent):
                       target_entropy=target_entropy, backup_entropy=backup_entropy)
         agent = cls(core, (), config, seed)
         agent._opts = {"actor": ao, "critic": co, "temperature": {"warmup_steps": 0, **to}}
+        if param_init == "reference":
+            agent._rng_key = init_ref.create_rng_of(rng)
         return agent
 
     # ------------------------------------------------------------------ batches (flat observations, no augmentation)

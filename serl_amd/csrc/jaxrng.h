@@ -72,5 +72,72 @@ __host__ __device__ __forceinline__ float normal_from_bits(uint32_t b) {
   return 1.41421354f * erfinv32(u);                    // np.float32(np.sqrt(2))
 }
 
+// ---- parameter initialisers (serl_jax_init_*).  Float contraction is off: every product and sum rounds to float32 on its own,
+// as XLA evaluates them, and the host and device builds give the same bits.
+
+// XLA's float32 erf (xla/client/lib/math.cc ErfImpl32 / chlo's materializeErfApproximationF32): x clamped to [-4, 4], then
+// x * P(x^2) / Q(x^2) by Horner's rule
+__host__ __device__ __forceinline__ float erf32(float x) {
+#pragma clang fp contract(off)
+  x = fminf(fmaxf(x, -4.0f), 4.0f);
+  const float x2 = x * x;
+  float p = -2.72614225801306e-10f;
+  p = p * x2 + 2.77068142495902e-08f;
+  p = p * x2 + -2.10102402082508e-06f;
+  p = p * x2 + -5.69250639462346e-05f;
+  p = p * x2 + -7.34990630326855e-04f;
+  p = p * x2 + -2.95459980854025e-03f;
+  p = p * x2 + -1.60960333262415e-02f;
+  float q = -1.45660718464996e-05f;
+  q = q * x2 + -2.13374055278905e-04f;
+  q = q * x2 + -1.68282697438203e-03f;
+  q = q * x2 + -7.37332916720468e-03f;
+  q = q * x2 + -1.42647390514189e-02f;
+  return (x * p) / q;
+}
+
+// erfinv32 with log1p taken in double precision and rounded to float32: the host's and the device's float log1p differ in the
+// last bit, the rounded double agrees (up to a double-rounding tie, ~2^-29 per element)
+__host__ __device__ __forceinline__ float erfinv32_init(float x) {
+#pragma clang fp contract(off)
+  float w = -(float)log1p((double)(-(x * x)));
+  const bool lt = w < 5.0f;
+  w = lt ? w - 2.5f : sqrtf(w) - 3.0f;
+  float p = lt ? 2.81022636e-08f : -0.000200214257f;
+  p = (lt ? 3.43273939e-07f : 0.000100950558f) + p * w;
+  p = (lt ? -3.5233877e-06f : 0.00134934322f) + p * w;
+  p = (lt ? -4.39150654e-06f : -0.00367342844f) + p * w;
+  p = (lt ? 0.00021858087f : 0.00573950773f) + p * w;
+  p = (lt ? -0.00125372503f : -0.0076224613f) + p * w;
+  p = (lt ? -0.00417768164f : 0.00943887047f) + p * w;
+  p = (lt ? 0.246640727f : 1.00167406f) + p * w;
+  p = (lt ? 1.50140941f : 2.83297682f) + p * w;
+  return fabsf(x) == 1.0f ? x * INFINITY : p * x;
+}
+
+// jax.random.uniform's element: 23 mantissa bits -> [1, 2) - 1, then max(lo, u * (hi - lo) + lo)
+__host__ __device__ __forceinline__ float uniform_from_bits(uint32_t b, float lo, float hi) {
+#pragma clang fp contract(off)
+  const float u = bits_to_unit(b) * (hi - lo) + lo;
+  return fmaxf(lo, u);
+}
+
+// one element of a parameter initialiser's draw (SERL_JAX_INIT_*), times scale
+__host__ __device__ __forceinline__ float init_from_bits(uint32_t b, int kind, float lo, float hi, float scale) {
+#pragma clang fp contract(off)
+  const float sqrt2 = 1.41421354f;                     // np.float32(np.sqrt(2))
+  float v;
+  if (kind == 0) {                                     // uniform
+    v = uniform_from_bits(b, lo, hi);
+  } else if (kind == 1) {                              // truncated_normal: uniform on [erf(lo/sqrt2), erf(hi/sqrt2)), then
+    const float a = erf32(lo / sqrt2), c = erf32(hi / sqrt2);   // sqrt2 * erf_inv, clipped to the open interval (lo, hi)
+    v = sqrt2 * erfinv32_init(uniform_from_bits(b, a, c));
+    v = fminf(fmaxf(v, nextafterf(lo, INFINITY)), nextafterf(hi, -INFINITY));
+  } else {                                             // normal
+    v = sqrt2 * erfinv32_init(uniform_from_bits(b, -0.99999994f, 1.0f));
+  }
+  return v * scale;
+}
+
 
 }  // namespace serl

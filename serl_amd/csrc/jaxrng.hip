@@ -48,6 +48,25 @@ __global__ __launch_bounds__(256) void jax_fill_kernel(JaxJobs jobs) {
   }
 }
 
+constexpr int kMaxInitJobs = 64;
+struct JaxInitJobs { serl_jax_init_job j[kMaxInitJobs]; long start[kMaxInitJobs + 1]; int n; };
+
+// parameter initialisers: one thread per output element over every job of the launch (element i of its job's flat array)
+__global__ __launch_bounds__(256) void jax_init_fill_kernel(JaxInitJobs jobs) {
+  const long t = (long)blockIdx.x * 256 + threadIdx.x;
+  if (t >= jobs.start[jobs.n]) return;
+  int k = 0;
+  while (k + 1 < jobs.n && t >= jobs.start[k + 1]) ++k;
+  const serl_jax_init_job& j = jobs.j[k];
+  const long i = t - jobs.start[k];
+  const uint32_t b = random_bits_at(j.key[0], j.key[1], (uint64_t)j.count, (uint64_t)i);
+  static_cast<float*>(j.out)[i] = init_from_bits(b, j.kind, j.minval, j.maxval, j.scale);
+}
+
+static bool init_job_ok(const serl_jax_init_job& j) {
+  return j.out && j.count >= 0 && (j.kind == SERL_JAX_INIT_UNIFORM || j.kind == SERL_JAX_INIT_TRUNCATED_NORMAL || j.kind == SERL_JAX_INIT_NORMAL);
+}
+
 static void split_host(const uint32_t key[2], int num, uint32_t* out /* [num][2] */) {
   const uint64_t n = 2ull * (uint64_t)num;
   for (uint64_t e = 0; e < n; ++e) out[e] = random_bits_at(key[0], key[1], n, e);
@@ -182,6 +201,34 @@ int serl_jax_fill(int device, const serl_jax_job* jobs, int n, void* stream) {
   jj.n = n;
   if (tot == 0) return SERL_OK;
   hipLaunchKernelGGL(serl::jax_fill_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, (hipStream_t)stream, jj);
+  SERL_HIP(hipGetLastError());
+  return SERL_OK;
+}
+
+int serl_jax_init_host(const serl_jax_init_job* job) {
+  SERL_REQUIRE(job && serl::init_job_ok(*job), "bad init job");
+  const serl_jax_init_job& j = *job;
+  float* out = static_cast<float*>(j.out);
+  for (int64_t e = 0; e < j.count; ++e)
+    out[e] = serl::init_from_bits(serl::random_bits_at(j.key[0], j.key[1], (uint64_t)j.count, (uint64_t)e), j.kind, j.minval, j.maxval, j.scale);
+  return SERL_OK;
+}
+
+int serl_jax_init_fill(int device, const serl_jax_init_job* jobs, int n, void* stream) {
+  SERL_REQUIRE(jobs && n >= 1 && n <= serl::kMaxInitJobs, "1..64 init jobs per launch");
+  SERL_HIP(hipSetDevice(device));
+  serl::JaxInitJobs jj{};
+  long tot = 0;
+  for (int i = 0; i < n; ++i) {
+    SERL_REQUIRE(serl::init_job_ok(jobs[i]), "bad init job %d", i);
+    jj.j[i] = jobs[i];
+    jj.start[i] = tot;
+    tot += jobs[i].count;
+  }
+  jj.start[n] = tot;
+  jj.n = n;
+  if (tot == 0) return SERL_OK;
+  hipLaunchKernelGGL(serl::jax_init_fill_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, (hipStream_t)stream, jj);
   SERL_HIP(hipGetLastError());
   return SERL_OK;
 }

@@ -166,3 +166,39 @@ def fill(device: int, jobs: Iterable[_Job], stream) -> None:
         part = jobs[i:i + 16]
         arr = (_Job * len(part))(*part)
         _lib.check(_lib.lib().serl_jax_fill(int(device), arr, len(part), stream))
+
+
+# ---- parameter initialisers (serl_jax_init_fill / serl_jax_init_host; include/serl_mi355.h)
+INIT_UNIFORM, INIT_TRUNCATED_NORMAL, INIT_NORMAL = 0, 1, 2
+MAX_INIT_JOBS = 64
+
+
+class _InitJob(C.Structure):
+    _fields_ = [("key", C.c_uint32 * 2), ("kind", C.c_int32), ("minval", C.c_float), ("maxval", C.c_float), ("scale", C.c_float),
+                ("count", C.c_int64), ("out", C.c_void_p)]
+
+
+def init_job(kind: int, key, count: int, out_ptr: int, minval: float = 0.0, maxval: float = 1.0, scale: float = 1.0) -> _InitJob:
+    k = _key(key)
+    j = _InitJob()
+    j.key[0], j.key[1] = int(k[0]), int(k[1])
+    j.kind, j.minval, j.maxval, j.scale = int(kind), float(minval), float(maxval), float(scale)
+    j.count, j.out = int(count), C.c_void_p(int(out_ptr))
+    return j
+
+
+def init_fill(device: int, jobs: Iterable[_InitJob], stream) -> None:
+    """One launch (per 64 jobs) writing every job's whole initialiser draw into device memory on `stream`."""
+    jobs = list(jobs)
+    for i in range(0, len(jobs), MAX_INIT_JOBS):
+        part = jobs[i:i + MAX_INIT_JOBS]
+        arr = (_InitJob * len(part))(*part)
+        _lib.check(_lib.lib().serl_jax_init_fill(int(device), arr, len(part), stream))
+
+
+def init_host(kind: int, key, count: int, minval: float = 0.0, maxval: float = 1.0, scale: float = 1.0) -> np.ndarray:
+    """The same draw evaluated by the library's host code -> float32[count]"""
+    out = np.zeros(int(count), np.float32)
+    j = init_job(kind, key, count, out.ctypes.data, minval, maxval, scale)
+    _lib.check(_lib.lib().serl_jax_init_host(C.byref(j)))
+    return out

@@ -291,15 +291,21 @@ class Classifier(Handle, AdamTrainState):
 
 
 def create_classifier(key, sample: Dict, image_keys: List[str], pretrained_encoder_path: str = "./resnet10_params.pkl",
-                      max_batch: int = 64, device: int = 0, trainable: bool = False, learning_rate: float = 1e-4) -> Classifier:
+                      max_batch: int = 64, device: int = 0, trainable: bool = False, learning_rate: float = 1e-4,
+                      param_init: str = "numpy") -> Classifier:
     """reward_classifier.py:31-90: a freshly initialised classifier whose frozen trunk holds the pretrained ResNet-10.
-    trainable=True adds optax.adam(learning_rate)'s state and the train step for batches of up to max_batch rows."""
+    trainable=True adds optax.adam(learning_rate)'s state and the train step for batches of up to max_batch rows.
+    param_init: "numpy" (default) or "reference" (classifier_def.init(key, sample)'s keys and initialisers, utils/init_ref.py)."""
     from ..utils import init as pinit
+    from ..utils import init_ref
+    reference = init_ref.check_param_init(param_init)
     first = np.asarray(sample[image_keys[0]])
     H, W = int(first.shape[-3]), int(first.shape[-2])
     seed = int(np.asarray(key).reshape(-1)[-1]) if not isinstance(key, int) else key
     c = Classifier(image_keys, H, W, max_batch=max_batch, device=device, trainable=trainable, learning_rate=learning_rate)
-    for name, v in pinit.init_classifier(len(image_keys), H, W, seed).items():
+    theta = init_ref.classifier_reference(image_keys, H, W, key, device=device) if reference else \
+        pinit.init_classifier(len(image_keys), H, W, seed)
+    for name, v in theta.items():
         c.set(name, v)
     with open(pretrained_encoder_path, "rb") as f:
         encoder_params = pickle.load(f)

@@ -5,6 +5,9 @@ overwrites the ResNet-10 trunk with weights downloaded at run time (utils/train_
 Neither flax nor the network is available here, so the trunk gets seeded synthetic weights of the
 same tree/shape; real weights are loaded with DrQAgent.load_trunk_params().
 Leaf names/shapes = the flat arena of libserl_mi355.so, camera index instead of key.
+The trainable leaves here come from host NumPy streams seeded by the integer seed: the default (param_init="numpy") of every
+constructor.  param_init="reference" draws the same leaves as the reference's model_def.init(init_rng) does, from jax.random's
+threefry stream under flax's per-module keys (utils/init_ref.py); the trunk comes from init_trunk either way.
 """
 from __future__ import annotations
 

@@ -10,9 +10,10 @@ from ..transport.endpoint import make_trainer_config  # noqa: F401  (launcher.py
 
 
 def make_drq_agent(seed, sample_obs, sample_action, image_keys=("image",), encoder_type="small",
-                   discount=0.96, batch_size=256, device=0, **create_kwargs):
+                   discount=0.96, batch_size=256, device=0, param_init="numpy", **create_kwargs):
     """launcher.py:79-116 (hyper-parameters copied from there).  `create_kwargs` (e.g. critic_optimizer_kwargs) are
-    passed on to DrQAgent.create_drq, whose signature has them in the reference too (drq.py:34-43)."""
+    passed on to DrQAgent.create_drq, whose signature has them in the reference too (drq.py:34-43).  param_init="reference"
+    initialises the parameters from the seed as the reference does (utils/init_ref.py)."""
     kw = dict(backup_entropy=False, critic_ensemble_size=10, critic_subsample_size=2)   # launcher.py:111-114
     kw.update(create_kwargs)
     return DrQAgent.create_drq(
@@ -20,11 +21,13 @@ def make_drq_agent(seed, sample_obs, sample_action, image_keys=("image",), encod
         policy_kwargs={"tanh_squash_distribution": True, "std_parameterization": "exp", "std_min": 1e-5, "std_max": 5},
         critic_network_kwargs={"activations": "tanh", "use_layer_norm": True, "hidden_dims": [256, 256]},
         policy_network_kwargs={"activations": "tanh", "use_layer_norm": True, "hidden_dims": [256, 256]},
-        temperature_init=1e-2, discount=discount, batch_size=batch_size, device=device, **kw)
+        temperature_init=1e-2, discount=discount, batch_size=batch_size, device=device, param_init=param_init, **kw)
 
 
-def make_sac_agent(seed, sample_obs, sample_action, discount=0.99, batch_size=256, device=0, **create_kwargs):
-    """launcher.py:50-76 (hyper-parameters copied from there; optimizer defaults from sac.py:333-343)."""
+def make_sac_agent(seed, sample_obs, sample_action, discount=0.99, batch_size=256, device=0, param_init="numpy",
+                   **create_kwargs):
+    """launcher.py:50-76 (hyper-parameters copied from there; optimizer defaults from sac.py:333-343).  param_init as for
+    make_drq_agent."""
     kw = dict(backup_entropy=False, critic_ensemble_size=10, critic_subsample_size=2)   # launcher.py:70-73
     kw.update(create_kwargs)
     return SACAgent.create_states(
@@ -32,7 +35,7 @@ def make_sac_agent(seed, sample_obs, sample_action, discount=0.99, batch_size=25
         policy_kwargs={"tanh_squash_distribution": True, "std_parameterization": "exp", "std_min": 1e-5, "std_max": 5},
         critic_network_kwargs={"activations": "tanh", "use_layer_norm": True, "hidden_dims": [256, 256]},
         policy_network_kwargs={"activations": "tanh", "use_layer_norm": True, "hidden_dims": [256, 256]},
-        temperature_init=1e-2, discount=discount, batch_size=batch_size, device=device, **kw)
+        temperature_init=1e-2, discount=discount, batch_size=batch_size, device=device, param_init=param_init, **kw)
 
 
 def make_replay_buffer(env, capacity: int = 1000000, rlds_logger_path: Optional[str] = None,

@@ -1,0 +1,142 @@
+"""GPU: param_init="reference".  The public constructors (make_drq_agent / make_sac_agent / make_bc_agent / create_classifier) start
+from the parameters and state.rng the reference's own create code gives for the same seed (tests/golden/init_*.npz, bit for bit,
+drawn on the device by serl_jax_init_fill), and from that state -- nothing injected -- one update agrees with the reference's
+within the golden-update tolerances of tests/test_golden_update_gpu.py.  The device draws equal the host twins element for
+element on a full-size critic ensemble kernel."""
+import os
+import pickle
+
+import numpy as np
+import pytest
+import torch
+
+import init_golden_helpers as IG
+from oracle import golden_update as G
+from oracle import ref_update_runner as RR
+from serl_amd import jaxrng as J
+from serl_amd.utils import init as pinit
+from serl_amd.utils import init_ref as IR
+from test_golden_update_gpu import _check_draws, _ref_batch
+
+pytestmark = pytest.mark.gpu
+TOL = 1e-4
+AGENT_CASES = [p for p in IG.GOLDEN if IG.case_name(p).startswith(("drq", "sac"))]
+
+
+def _make(cfg, B):
+    from serl_amd.utils.launcher import make_drq_agent, make_sac_agent
+    if cfg.state_only:
+        opt = {f"{tx}_optimizer_kwargs": kw for tx, kw in (("actor", {"warmup_steps": cfg.warmup}),
+                                                          ("critic", {"warmup_steps": cfg.warmup}), ("temperature", {}))}
+        return make_sac_agent(0, np.zeros((cfg.S,), np.float32), np.zeros((cfg.A,), np.float32), discount=cfg.discount,
+                              batch_size=B, param_init="reference", **opt)
+    obs = {k: np.zeros((1, cfg.H, cfg.W, 3), np.uint8) for k in cfg.image_keys}
+    obs["state"] = np.zeros((1, cfg.S), np.float32)
+    return make_drq_agent(0, obs, np.zeros((cfg.A,), np.float32), image_keys=cfg.image_keys, encoder_type=cfg.encoder_type,
+                          discount=cfg.discount, batch_size=B, param_init="reference")
+
+
+@pytest.mark.parametrize("path", AGENT_CASES, ids=IG.case_name)
+def test_reference_init_then_one_update_matches_the_reference(gpu, path, monkeypatch):
+    monkeypatch.setattr(G, "N_SAMPLE", IG.N_SAMPLE)
+    npz, cfg, recs, _ = IG.load(path)
+    g = G.unpack(npz)
+    B = g["B"]
+    agent = _make(cfg, B)
+    core = agent.core
+    # step 0: parameters and target parameters equal the reference's initial parameters bit for bit, moments are zero,
+    # state.rng is create_rng
+    bad = [m for n in sorted(recs) for sec in ("params", "target_params") for m in [IG.mismatch(n, recs[n], core.get(sec, n))] if m]
+    assert not bad, bad
+    for n in recs:
+        for tx in ("critic", "actor", "temperature"):
+            assert not core.get(f"opt/{tx}/mu", n).any() and not core.get(f"opt/{tx}/nu", n).any()
+    assert [int(v) for v in agent.state.rng] == g["meta"]["rng0"] == [int(v) for v in npz["init_rng"]]
+    if cfg.image_keys and cfg.encoder_type != "small":      # the frozen trunk keeps init_trunk's values (the golden's pickle)
+        assert np.array_equal(core.get("params", "trunk/conv_init"), pinit.init_trunk(0)["trunk/conv_init"].reshape(-1))
+    # one update from that state, every draw from state.rng
+    n_steps = 0
+    for step in g["steps"]:
+        crops = None
+        if "crop_obs" in step["noise"]:
+            crops = (step["noise"]["crop_obs"].astype(np.int32), step["noise"]["crop_next"].astype(np.int32))
+        batch = _ref_batch(cfg, step["batch"])
+        if step["kind"] == "critics":
+            agent, info = agent.update_critics(batch)
+            flat = dict(info["critic"])
+            n_steps += 1
+        else:
+            agent, info = agent.update_high_utd(batch, utd_ratio=step["utd"])
+            flat = {**info["critic"], **info["actor"], **info["temperature"]}
+            n_steps += step["utd"] + 1
+        _check_draws(agent, cfg, B, step, step["noise"], crops)
+        for tx in ("actor", "critic", "temperature"):
+            flat[f"{tx}_lr"] = info[f"{tx}_lr"]
+        for k, r in step["info"].items():
+            assert abs(flat[k] - r) < TOL * max(1.0, abs(r)), (step["kind"], k, flat[k], r)
+    assert agent.state.step == g["meta"]["final_step"] == n_steps
+    assert [int(v) for v in agent.state.rng] == g["meta"]["rng_final"]
+    worst = 0.0
+    for name, (gname, _) in recs.items():
+        for tx in ("critic", "actor", "temperature"):
+            for mom in ("mu", "nu"):
+                err, scale = G.leaf_errors(f"{mom}_{tx}/{gname}", g["final"][f"{mom}_{tx}"][gname], core.get(f"opt/{tx}/{mom}", name))
+                if scale < 1e-200:
+                    assert err.max() == 0.0, (tx, mom, name)
+                    continue
+                worst = max(worst, err.max() / scale)
+                assert err.max() / scale < 3 * TOL, (tx, mom, name, err.max() / scale)   # the seed-only bound of the update goldens
+        for sec, gsec in (("params", "params"), ("target_params", "target")):
+            err, scale = G.leaf_errors(f"{gsec}/{gname}", g["final"][gsec][gname], core.get(sec, name))
+            assert float(np.quantile(err, 0.999)) / scale < TOL, (sec, name)
+            lr = 3e-4
+            assert err.max() <= 2.1 * lr * n_steps * (cfg.tau * n_steps if sec == "target_params" else 1.0) + TOL * scale, (sec, name)
+    print(f"{IG.case_name(path)}: reference init + {n_steps} update(s): Adam moments {worst:.1e}")
+
+
+def test_bc_reference_init(gpu):
+    from serl_amd.agents.bc import make_bc_agent
+    path = [p for p in IG.GOLDEN if IG.case_name(p).startswith("bc")][0]
+    npz, cfg, recs, _ = IG.load(path)
+    obs = {k: np.zeros((1, cfg.H, cfg.W, 3), np.uint8) for k in cfg.image_keys}
+    obs["state"] = np.zeros((1, cfg.S), np.float32)
+    agent = make_bc_agent(0, obs, np.zeros((cfg.A,), np.float32), image_keys=cfg.image_keys, batch_size=8, param_init="reference")
+    bad = [m for n in sorted(recs) for m in [IG.mismatch(n, recs[n], agent.get("params", n))] if m]
+    assert not bad, bad
+    assert np.array_equal(agent.state.rng, npz["init_rng"])
+    # the default is unchanged: host NumPy streams
+    base = make_bc_agent(0, obs, np.zeros((cfg.A,), np.float32), image_keys=cfg.image_keys, batch_size=8)
+    want = pinit.init_theta(len(cfg.image_keys), cfg.H, cfg.W, cfg.S, cfg.A, seed=0)
+    assert np.array_equal(base.get("params", "actor/w1"), want["actor/w1"].reshape(-1))
+
+
+def test_classifier_reference_init(gpu, tmp_path):
+    from serl_amd.networks.reward_classifier import create_classifier
+    path = [p for p in IG.GOLDEN if IG.case_name(p) == "classifier"][0]
+    _, cfg, recs, _ = IG.load(path)
+    pkl = os.path.join(tmp_path, "resnet10_params.pkl")
+    with open(pkl, "wb") as f:
+        pickle.dump(RR.pretrained_pickle_tree(pinit.init_trunk(0)), f)
+    sample = {k: np.zeros((1, 1, cfg.H, cfg.W, 3), np.uint8) for k in cfg.image_keys}
+    c = create_classifier(J.prngkey(0), sample, list(cfg.image_keys), pretrained_encoder_path=pkl, param_init="reference")
+    bad = [m for n in sorted(recs) for m in [IG.mismatch(n, recs[n], c.get(n))] if m]
+    assert not bad, bad
+
+
+def test_device_draws_equal_host_twins_on_a_critic_ensemble_kernel(gpu):
+    """582 x 256 per member, 10 members (the timed DrQ critic's first kernel) and a truncated normal of 4096 x 256 (the camera
+    bottleneck Dense): every element of the device draw equals the host twin's."""
+    init_rng = IR.init_rng_of(J.prngkey(3))
+    leaves = [IR.Leaf("critic/w1", ("modules_critic", "network", "Dense_0"), 1, IR.XAVIER_UNIFORM, (10, 582, 256), 10),
+              IR.Leaf("enc/0/dense/kernel", ("modules_actor", "encoder", "encoder_a", "Dense_0"), 1, IR.LECUN_NORMAL, (4096, 256))]
+    dev = IR.draw(leaves, init_rng, device=0)
+    host = IR.draw_host(leaves, init_rng)
+    for lf in leaves:
+        got = dev[lf.name].cpu().numpy()
+        diff = np.flatnonzero(got.view(np.uint32).reshape(-1) != host[lf.name].view(np.uint32).reshape(-1))
+        assert diff.size == 0, (lf.name, diff.size, diff[:5])
+    n = J.init_host(J.INIT_NORMAL, init_rng, 100003, scale=0.5)
+    t = torch.empty(100003, dtype=torch.float32, device="cuda")
+    J.init_fill(0, [J.init_job(J.INIT_NORMAL, init_rng, 100003, t.data_ptr(), scale=0.5)], torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    assert np.array_equal(t.cpu().numpy().view(np.uint32), n.view(np.uint32))
