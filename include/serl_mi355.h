@@ -55,7 +55,9 @@ int serl_profile_read(int max_entries, char* names, double* total_ms, int64_t* c
 typedef struct serl_rb serl_rb;
 
 /* MemoryEfficientReplayBuffer.__init__ (memory_efficient_replay_buffer.py:13-51) +
- * ReplayBuffer.__init__ (replay_buffer.py:41-66). num_stack = T (frames per observation). */
+ * ReplayBuffer.__init__ (replay_buffer.py:41-66). num_stack = T (frames per observation).
+ * LIMIT: image rows are whole 16-byte vectors, W * C % 16 == 0 (with C = 3: W a multiple of 16; H is free) -- any other
+ * width is refused here with SERL_ERR_INVALID ("W*C (...) must be a multiple of 16 bytes"). */
 int serl_rb_create(int device, int64_t capacity, int n_cam, int H, int W, int C, int num_stack,
                    int state_dim, int act_dim, serl_rb** out);
 int serl_rb_destroy(serl_rb* rb);
@@ -122,7 +124,8 @@ int serl_rb_gather_crop(serl_rb* const* rbs, int n_rb, int64_t* const* host_idx,
                         const int32_t* host_crop_next, const serl_batch* out, void* stream);
 
 /* _unpack + random shift on an already-gathered packed batch (train_utils.py:44-66,
- * data_augmentations.py:7-36): dev_packed[c] u8[batch][2][H][W][C] -> out->frames. */
+ * data_augmentations.py:7-36): dev_packed[c] u8[batch][2][H][W][C] -> out->frames.  Same LIMIT as serl_rb_create:
+ * W * C % 16 == 0, refused otherwise (the agents themselves take any H, W >= 32 through serl_batch). */
 int serl_crop_packed(int device, const uint8_t* const* dev_packed, int n_cam, int batch, int H,
                      int W, int C, const int32_t* host_crop_obs, const int32_t* host_crop_next,
                      uint8_t* dev_frames_out, void* stream);
@@ -320,10 +323,12 @@ int serl_agent_trunk_forward(serl_agent* a, const uint8_t* dev_frames, int n, fl
 int serl_agent_debug_get(serl_agent* a, const char* what, float* host_out, int64_t count);
 /* inject gradients / scalars ("g_critic", "g_actor", "scalars") before serl_agent_apply: optimizer tests */
 int serl_agent_debug_set(serl_agent* a, const char* what, const float* host, int64_t count);
-/* Which kernels the LAST split-fp16 trunk pass selected, as text ("images=128 pool=1 raw_b0=0 b0_conv0=S/1/0/f1 ...":
- * layer=kernel/tile-config/statistics-mode/f<fused epilogue>; kernel S = row-slab, D = LDS-DMA, R = register-staged implicit
- * GEMM).  The per-rank shapes of a data-parallel job (resnet_v1.py:260-269 at N = B/8 images) pick other kernels than the
- * full batch; the parity tests assert which path they exercised. */
+/* Which kernels the LAST split-fp16 trunk pass selected, as text ("images=128 pool=1 raw_b0=0 b0_conv0=S/1/0/f1/p1x1 ...":
+ * layer=kernel/tile-config/statistics-mode/f<fused epilogue>/p<low-side SAME pad of the rows>x<of the columns>; kernel S =
+ * row-slab, D = LDS-DMA, R = register-staged implicit GEMM, F = projection computed by conv0's launch).  Image extents that
+ * are not powers of two pick other pads and kernels than 64 / 128 do, and the per-rank shapes of a data-parallel job
+ * (resnet_v1.py:260-269 at N = B/8 images) pick other kernels than the full batch; the parity tests assert which path they
+ * exercised.  A buffer the text (about 350 bytes) does not fit in is refused with SERL_ERR_INVALID, never truncated. */
 int serl_agent_trunk_plan(serl_agent* a, char* out, int cap);
 /* Number of update-chain kernels (everything but the frozen trunk, the SmallEncoder convs and the replay kernels) launched
  * since the library was loaded: the tests pin the launch count of an update_critics + update_high_utd pair (sac.py:243-299). */

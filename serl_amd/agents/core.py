@@ -232,15 +232,16 @@ class AgentCore(Handle):
 
 
     def trunk_plan(self) -> dict:
-        """Kernels the last split-fp16 trunk pass selected: {"images", "pool", "raw_b0", "<layer>": (kernel, cfg, pmode, fused)}."""
-        buf = C.create_string_buffer(512)
-        _lib.check(self.L.serl_agent_trunk_plan(self._h, buf, 512))
+        """Kernels the last split-fp16 trunk pass selected: {"images", "pool", "raw_b0", "<layer>": (kernel, cfg, pmode, fused,
+        (low-side SAME pad of the rows, of the columns))}."""
+        buf = C.create_string_buffer(2048)      # (the library refuses a buffer the text does not fit in)
+        _lib.check(self.L.serl_agent_trunk_plan(self._h, buf, 2048))
         out = {}
         for tok in buf.value.decode().split():
             k, v = tok.split("=")
             if "/" in v:
-                kern, cfg, pm, fz = v.split("/")
-                out[k] = (kern, int(cfg), int(pm), int(fz[1:]))
+                kern, cfg, pm, fz, pd = v.split("/")
+                out[k] = (kern, int(cfg), int(pm), int(fz[1:]), tuple(int(v) for v in pd[1:].split("x")))
             else:
                 out[k] = int(v)
         return out

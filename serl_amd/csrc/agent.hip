@@ -1504,8 +1504,9 @@ int serl_agent_trunk_plan(serl_agent* a, char* out, int cap) {
       const TrunkPlan::L& l = p.conv[i][k];
       if (!l.kern) continue;
       s += " b" + std::to_string(i) + "_" + kNames[k] + "=" + std::string(1, l.kern) + "/" + std::to_string(l.cfg) + "/" +
-           std::to_string(l.pmode) + "/f" + std::to_string(l.fused);
+           std::to_string(l.pmode) + "/f" + std::to_string(l.fused) + "/p" + std::to_string(l.pad) + "x" + std::to_string(l.padw);
     }
+  SERL_REQUIRE((int)s.size() < cap, "the plan text takes %d bytes, the buffer holds %d", (int)s.size() + 1, cap);
   snprintf(out, cap, "%s", s.c_str());
   return SERL_OK;
 }

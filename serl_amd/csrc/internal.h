@@ -59,6 +59,7 @@ struct TrunkPlan {
     bool raw = false;              // 'S' on conv_init's raw pooled tensor (b0_conv0 of a raw_b0 pass)
     bool proj = false;             // 'D' conv0: the block's projection rides on this launch
     int stagger = 0;               // 'S': ConvArgsB::stagger
+    int pad = 0, padw = 0;         // the conv's low-side ("SAME") padding in rows / columns, as conv_geom derived it
   } conv[kTrunkStages][3];
 };
 struct TrunkWorkspace {

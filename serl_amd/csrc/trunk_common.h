@@ -6,6 +6,10 @@ namespace serl {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
+// Low-side -inf padding of the 3x3 stride-2 "SAME" max-pool along one axis (resnet_v1.py:259): XLA puts total / 2 on the low side,
+// total = max((out - 1) * 2 + 3 - in, 0) -- 0 over an even extent, 1 (a line above / left of the map) over an odd one.
+__device__ __forceinline__ int pool_pad_lo(int in, int out) { return max((out - 1) * 2 + 3 - in, 0) >> 1; }
+
 // ---------------------------------------------------------------------------------------------
 // XCD-aware bijective workgroup remap (8 XCDs, block b is dispatched to XCD b % 8): gives every
 // XCD a contiguous range of tile ids so tiles that share A rows / weights hit the same L2.

@@ -116,6 +116,7 @@ static TrunkPlan::L plan_conv(const ConvArgs& a, bool dma, bool zero_page, bool 
     l.kern = 'R'; l.cfg = cfg;
   }
   l.pmode = pmode;
+  l.pad = a.pad; l.padw = a.padw;
   return l;
 }
 

@@ -119,14 +119,15 @@ __global__ __launch_bounds__(256) void gn_relu_maxpool_split_kernel(const float*
   float4 s, h;
   gn_coef4(gn, n, c4 * 4, s, h);
   float4 m = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
+  const int pt = pool_pad_lo(Hi, Ho), pl = pool_pad_lo(Wi, Wo);
 #pragma unroll
   for (int dy = 0; dy < 3; ++dy) {
-    const int iy = oy * 2 + dy;
-    if (iy >= Hi) continue;
+    const int iy = oy * 2 - pt + dy;
+    if (iy < 0 || iy >= Hi) continue;
 #pragma unroll
     for (int dx = 0; dx < 3; ++dx) {
-      const int ix = ox * 2 + dx;
-      if (ix >= Wi) continue;
+      const int ix = ox * 2 - pl + dx;
+      if (ix < 0 || ix >= Wi) continue;
       const float4 v = *reinterpret_cast<const float4*>(x + (((size_t)n * Hi + iy) * Wi + ix) * Cc + c4 * 4);
       m.x = fmaxf(m.x, fmaxf(v.x * s.x + h.x, 0.f));
       m.y = fmaxf(m.y, fmaxf(v.y * s.y + h.y, 0.f));

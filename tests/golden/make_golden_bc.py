@@ -52,6 +52,8 @@ CASES = {
     "bc_64_seq": (O.Config(image_keys=("front", "wrist"), H=64, W=64, S=5, A=3), 8, 5),
     # one camera
     "bc_one_cam": (O.Config(image_keys=("image",), H=64, W=64, S=7, A=4), 6, 1),
+    # 84x84: a 3x3 feature map behind stride-2 convs padded (1, 1) in stages 1 and 2 (tests/shape_edges.py)
+    "bc_84": (O.Config(image_keys=("front", "wrist"), H=84, W=84, S=5, A=3), 8, 1),
     # the timed shape: B = 256, two 128x128 cameras, S = 24, A = 6
     "bc_128": (O.Config(image_keys=("front", "wrist"), H=128, W=128, S=24, A=6), 256, 1),
     # the reference's own random stream (jax.random's threefry): masks / eps are drawn from the keys, nothing injected

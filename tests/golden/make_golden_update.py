@@ -24,6 +24,10 @@ CASES = {
     "drq_128": (O.Config(image_keys=("front", "wrist"), H=128, W=128, S=24, A=6), 4, [("critics",), ("high_utd", 1)]),
     # one camera (the literal BASELINE.json configs[1] wording), non-square
     "drq_one_cam": (O.Config(image_keys=("image",), H=128, W=64, S=7, A=4), 6, [("high_utd", 1), ("critics",)]),
+    # 84 rows x 96 columns, one camera: a 3x3 feature map behind stride-2 convs whose row pad is (1, 1) and column pad (0, 1) in
+    # stages 1 and 2 (tests/shape_edges.py).  96 wide because the packed batch goes through the replay crop, whose rows are
+    # whole 16-byte vectors (W * 3 % 16 == 0, include/serl_mi355.h); the height is free
+    "drq_84x96": (O.Config(image_keys=("wrist",), H=84, W=96, S=5, A=3), 4, [("high_utd", 2)]),
     # SACAgent.update (sac.py:243-299) with the default networks_to_update (all three losses at the same parameters, one
     # optimizer step) and other subsets
     "drq_update_subsets": (O.Config(image_keys=("front", "wrist"), H=64, W=64, S=5, A=3), 6,

@@ -35,7 +35,7 @@ def _flat_shapes(tree, prefix=()):
     return {"/".join(prefix): tuple(tree)}
 
 
-@pytest.mark.parametrize("name", ["bc_64", "bc_one_cam", "bc_128"])
+@pytest.mark.parametrize("name", ["bc_64", "bc_one_cam", "bc_128", "bc_84"])
 def test_bc_tree_paths_and_shapes_match_reference(name):
     from serl_amd.agents.flax_tree import bc_paths, bc_shapes
     d, meta, cfg = _golden(name)
@@ -103,7 +103,7 @@ def _np_bc(theta, enc, act, std_min=1e-5, std_max=5.0):
     return loss, mse, g
 
 
-@pytest.mark.parametrize("name", ["bc_64", "bc_one_cam"])
+@pytest.mark.parametrize("name", ["bc_64", "bc_one_cam", "bc_84"])
 def test_numpy_restatement_reproduces_golden_loss_and_gradients(name):
     from oracle.ref_update_runner import synth_packed_batch
     d, meta, cfg = _golden(name)

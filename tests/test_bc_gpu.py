@@ -73,7 +73,7 @@ def _frozen(agent):
     return {leaf: agent.get("params", leaf) for leaf in agent.leaves(trainable=False)}
 
 
-@pytest.mark.parametrize("name", ["bc_64", "bc_one_cam", "bc_128", "bc_64_seq"])
+@pytest.mark.parametrize("name", ["bc_64", "bc_one_cam", "bc_128", "bc_64_seq", "bc_84"])
 def test_update_matches_reference_with_injected_masks(gpu, name):
     d, meta, cfg = _golden(name)
     B = meta["B"]
@@ -123,7 +123,7 @@ def _close(got, ref, tol=2e-4):
     assert err < tol, err
 
 
-@pytest.mark.parametrize("name", ["bc_64", "bc_one_cam", "bc_64_threefry"])
+@pytest.mark.parametrize("name", ["bc_64", "bc_one_cam", "bc_64_threefry", "bc_84"])
 def test_inference_matches_reference(gpu, name):
     d, meta, cfg = _golden(name)
     B = meta["B"]

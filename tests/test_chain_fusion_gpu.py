@@ -58,9 +58,12 @@ def _assert_state_bits(cfg, fused, plain, what, leaves=None):
             assert _bits_equal(fused.get(sec, k), plain.get(sec, k)), (what, sec, k)
 
 
-@pytest.mark.parametrize("shape", ["bench", "small", "odd"])
+@pytest.mark.parametrize("shape", ["bench", "small", "odd", "1cam_84_A64_E17_B65", "4cam_100x80_A33_B7"])
 def test_fused_chain_is_bit_identical_to_the_unfused_chain(gpu, shape):
-    if shape == "bench":
+    if shape[0].isdigit():    # rows of the edge-dimension table (tests/shape_edges.py): A = 64 / 33, 3x3 / 4x3 SLE, 17 members x 65 rows, 4 cameras
+        import shape_edges as SE
+        cfg, B, _ = SE.update_config(next(c for c in SE.UPDATE_CASES if c[0] == shape))
+    elif shape == "bench":
         cfg, B = O.Config(image_keys=("front", "wrist"), H=128, W=128, S=24, A=6), 256
     elif shape == "small":     # a rank's share of an 8-GPU job: half-empty 64-row tiles, deep K-splits
         cfg, B = O.Config(image_keys=("front", "wrist"), H=128, W=128, S=24, A=6), 32
