@@ -429,15 +429,10 @@ int dense_ln_tanh_multi(serl_agent* a, const DenseJob* jobs, int n, int groups, 
   LnFwdArgs lv[3];
   for (int i = 0; i < n; ++i) {
     const DenseJob& j = jobs[i];
-    GemmDesc& g = gd[i];
-    g = GemmDesc{};
-    g.A = j.X; g.sAm = j.ldx; g.sAk = 1; g.sAb = j.x_gstride;
-    g.B = j.W; g.sBk = Hd; g.sBn = 1; g.sBb = j.w_gstride;
-    g.C = a->slabs_lane[i]; g.ldc = Hd; g.sCz = (long)rows_per_group * Hd;
-    g.M = rows_per_group; g.N = Hd; g.K = K; g.nbatch = groups; g.splitk = splitk;
+    gd[i] = gemm_fwd(j.X, j.ldx, j.x_gstride, j.W, j.w_gstride, a->slabs_lane[i], groups, rows_per_group, Hd, K, splitk);
     LnFwdArgs& l = lv[i];
     l = LnFwdArgs{};
-    l.slabs = a->slabs_lane[i]; l.S = splitk; l.slab_stride = g.sCz;
+    l.slabs = a->slabs_lane[i]; l.S = splitk; l.slab_stride = gd[i].sCz;
     l.bias = j.bias; l.gamma = j.gamma; l.beta = j.beta; l.pstride = j.p_gstride;
     l.rows = groups * rows_per_group; l.rows_per_group = rows_per_group;
     l.y = j.y; l.ld_y = Hd; l.y_goff = (long)rows_per_group * Hd;
@@ -477,12 +472,7 @@ int policy_fwd_multi(serl_agent* a, const PolJob* jobs, int n, int cnt, hipStrea
                      pb.m.h1, pb.m.xh1, pb.m.rs1, nullptr, nullptr, nullptr};
     d2[i] = DenseJob{pb.m.h1, Hd, 0, P + o.a_w2, 0, P + o.a_b2, P + o.a_g2, P + o.a_be2, 0,
                      pb.m.h2, pb.m.xh2, pb.m.rs2, nullptr, nullptr, nullptr};
-    GemmDesc& g = gd[i];
-    g = GemmDesc{};
-    g.A = pb.m.h2; g.sAm = Hd; g.sAk = 1; g.sAb = 0;
-    g.B = P + o.a_Wm; g.sBk = A; g.sBn = 1; g.sBb = o.a_Ws - o.a_Wm;
-    g.C = a->slabs_lane[i]; g.ldc = A; g.sCz = (long)cnt * A;
-    g.M = cnt; g.N = A; g.K = Hd; g.nbatch = 2; g.splitk = 4;
+    gd[i] = gemm_fwd(pb.m.h2, Hd, 0, P + o.a_Wm, o.a_Ws - o.a_Wm, a->slabs_lane[i], 2, cnt, A, Hd, 4);   // (mean, log_std) as two groups
     pv[i] = PolicyDistArgs{};
     pv[i].slabs = a->slabs_lane[i]; pv[i].S = 4; pv[i].bias_mean = P + o.a_bm; pv[i].bias_ls = P + o.a_bs; pv[i].pre = pb.pre;
     pv[i].eps = j.eps; pv[i].act = j.act_out; pv[i].ld_act = j.ld_act; pv[i].logp = pb.logp; pv[i].std_out = pb.std;
@@ -540,6 +530,17 @@ int critic_fwd_multi(serl_agent* a, const CritJob* jobs, int n, int cnt, hipStre
   return dense_ln_tanh_multi(a, d2, n, N, cnt, Hd, 2, st);
 }
 
+LnBwdArgs ln_bwd_args(const float* dy, long ld_dy, long dy_goff, const float* y, long ld_y, long y_goff, const float* xhat,
+                      const float* rstd, const float* gamma, long p_gstride, int groups, int rows_per_group, float* dpre, float* dg) {
+  LnBwdArgs l{};
+  l.dy = dy; l.ld_dy = ld_dy; l.dy_goff = dy_goff;
+  l.y = y; l.ld_y = ld_y; l.y_goff = y_goff;
+  l.xhat = xhat; l.rstd = rstd; l.gamma = gamma; l.pstride = p_gstride;
+  l.rows = groups * rows_per_group; l.rows_per_group = rows_per_group;
+  l.dx = dpre; l.dg = dg;
+  return l;
+}
+
 // backward of one Dense->LN->tanh layer.  dy: [groups*rows][Hd] gradient wrt the layer output.
 // Produces dpre (a->da*) and, if G != nullptr, parameter gradients into G at the given offsets
 // (W grads are written directly by the GEMM: splitk == 1).
@@ -548,12 +549,7 @@ int dense_ln_tanh_bwd(serl_agent* a, const float* dy, long ld_dy, long dy_goff, 
                       int groups, int rows_per_group, int D, float* dpre, float* dg, float* G, long g_off,
                       long be_off, long b_off, long pg_gstride, hipStream_t st, const float* dq = nullptr,
                       const float* dq_w = nullptr, float dq_const = 0.f, long dq_w_gstride = 0, const LossArgs* loss = nullptr) {
-  LnBwdArgs l{};
-  l.dy = dy; l.ld_dy = ld_dy; l.dy_goff = dy_goff;
-  l.y = y; l.ld_y = ld_y; l.y_goff = y_goff;
-  l.xhat = xhat; l.rstd = rstd; l.gamma = gamma; l.pstride = p_gstride;
-  l.rows = groups * rows_per_group; l.rows_per_group = rows_per_group;
-  l.dx = dpre; l.dg = dg;
+  LnBwdArgs l = ln_bwd_args(dy, ld_dy, dy_goff, y, ld_y, y_goff, xhat, rstd, gamma, p_gstride, groups, rows_per_group, dpre, dg);
   l.dq = dq; l.dq_w = dq_w; l.dq_const = dq_const; l.dq_w_gstride = dq_w_gstride;
   if (loss) {   // the critic loss rides on this launch and every row derives its dQ from the loss arguments (no critic_loss launch)
     l.D = D; l.dq_inline = 1;
@@ -579,11 +575,7 @@ int flush_param_grads(serl_agent* a, hipStream_t st) {
 // C[g] = X[g]^T * dY[g]  (weight gradient, written directly)   X: [rows][K-dim as M], dY: [rows][N]
 int wgrad(serl_agent* a, const float* X, long ldx, long x_gstride, const float* dY, long ldy, long dy_gstride, float* out,
           long ldo, long out_gstride, int groups, int Mx, int Ny, int rows, hipStream_t st) {
-  GemmDesc g{};
-  g.A = X; g.sAm = 1; g.sAk = ldx; g.sAb = x_gstride;
-  g.B = dY; g.sBk = ldy; g.sBn = 1; g.sBb = dy_gstride;
-  g.C = out; g.ldc = ldo; g.sCz = out_gstride;
-  g.M = Mx; g.N = Ny; g.K = rows; g.nbatch = groups; g.splitk = 1;
+  const GemmDesc g = gemm_wgrad(X, ldx, x_gstride, dY, ldy, dy_gstride, out, ldo, out_gstride, groups, Mx, Ny, rows);
   if (a->pg_defer && a->pg_nwg < kMaxGemmGroups) {
     a->pg_wg[a->pg_nwg++] = g;  // issued by flush_param_grads
     return SERL_OK;
@@ -594,89 +586,86 @@ int wgrad(serl_agent* a, const float* X, long ldx, long x_gstride, const float* 
 // dX[g] = dY[g] * W[g]^T   (input gradient)   W: [Kin][Nout] row-major
 int igrad(const float* dY, long ldy, long dy_gstride, const float* W, long ldw, long w_gstride, float* out,
           long ldo, long out_zstride, int groups, int rows, int Kin, int Nout, hipStream_t st) {
-  GemmDesc g{};
-  g.A = dY; g.sAm = ldy; g.sAk = 1; g.sAb = dy_gstride;
-  g.B = W; g.sBk = 1; g.sBn = ldw; g.sBb = w_gstride;
-  g.C = out; g.ldc = ldo; g.sCz = out_zstride;
-  g.M = rows; g.N = Kin; g.K = Nout; g.nbatch = groups; g.splitk = 1;
-  return gemm_f32(g, st);
+  return gemm_f32(gemm_igrad(dY, ldy, dy_gstride, W, ldw, w_gstride, out, ldo, out_zstride, groups, rows, Kin, Nout), st);
 }
 
-// dX = sum_g dY[g] * W[g]^T: the per-group products go to padded scratch slabs and the last workgroup to arrive at an output
-// tile adds them in group order (heads.hip, kEpiReduce) -- igrad + reduce_slabs in one launch
+// ---- the places where the two schedules of the update chain differ: a->fuse is read here and in
+// policy_fwd_multi / encode_multi, nowhere in the phases themselves ----------------------------------------------------------
+
+// dX = sum_g dY[g] * W[g]^T.  Fused: the per-group products go to padded scratch slabs and the last workgroup to arrive at an
+// output tile adds them in group order (heads.hip, kEpiReduce).  Else: the products as slabs, then reduce_slabs.
 int igrad_sum(serl_agent* a, const float* dY, long ldy, long dy_gstride, const float* W, long ldw, long w_gstride, float* out,
               long ldo, int groups, int rows, int Kin, int Nout, hipStream_t st) {
-  GemmDesc g{};
-  g.A = dY; g.sAm = ldy; g.sAk = 1; g.sAb = dy_gstride;
-  g.B = W; g.sBk = 1; g.sBn = ldw; g.sBb = w_gstride;
-  g.C = a->slabs; g.ldc = pad64(Kin); g.sCz = pad64(rows) * g.ldc;
-  g.M = rows; g.N = Kin; g.K = Nout; g.nbatch = groups; g.splitk = 1;
+  if (!a->fuse) {
+    RC(igrad(dY, ldy, dy_gstride, W, ldw, w_gstride, a->slabs, Kin, (long)rows * Kin, groups, rows, Kin, Nout, st));
+    return reduce_slabs(a->slabs, groups, (long)rows * Kin, 1, rows, Kin, nullptr, 0, out, ldo, 0, false, st);
+  }
+  const long ldc = pad64(Kin);
+  GemmDesc g = gemm_igrad(dY, ldy, dy_gstride, W, ldw, w_gstride, a->slabs, ldc, pad64(rows) * ldc, groups, rows, Kin, Nout);
   g.epi = kEpiReduce; g.zred = groups; g.ctr = a->ctr; g.out = out; g.ld_out = ldo; g.out_gstride = 0;
   SERL_REQUIRE((long)cdiv(rows, 64) * cdiv(Kin, 64) <= kCtrPerLane && groups * g.sCz <= a->slabs_cap, "input gradient exceeds the fused epilogue's scratch");
   return gemm_f32(g, st);
 }
 
-// Critic backward from dq [ens][cnt] down to dx [cnt][E+A]; parameter grads into Gc when `pg`.
-// dq: [ens][cnt] gradient wrt Q, or nullptr with the constant `dq_const` for every element (actor loss)
-int critic_bwd(serl_agent* a, const float* P, CritBuf& cb, int cnt, bool pg, hipStream_t st, const float* dq,
-               float dq_const, const LossArgs* loss = nullptr) {
+// Gradient of the critic's head kernel: dw[j] = sum_{e,b} dq h2 for the shared head, dw[e][j] = sum_b dq[e][b] h2[e][b][j] with
+// one head per member (state-only SAC): dq as one row [1][K] times h2.  A K above 1024 is split.  Fused: a deferred GEMM whose
+// slabs the last arriver sums.  Else: the GEMM now, then reduce_slabs.  (M = 1: hand-filled, sAm is the schedule's own.)
+int head_kernel_grad(serl_agent* a, CritBuf& cb, int cnt, hipStream_t st) {
+  const int Hd = a->cfg.hidden, N = a->cfg.ensemble;
+  const int groups = a->state_only ? N : 1, K = a->state_only ? cnt : N * cnt, split = K <= 1024 ? 1 : (a->state_only ? 4 : 8);
+  float* out = a->Gc + a->o.c_hw;
+  GemmDesc g{};
+  g.A = a->dq; g.sAm = a->fuse ? 1 : 0; g.sAk = 1; g.sAb = a->state_only ? cnt : 0;
+  g.B = cb.m.h2; g.sBk = Hd; g.sBn = 1; g.sBb = a->state_only ? (long)cnt * Hd : 0;
+  g.C = split == 1 ? out : a->slabs; g.ldc = Hd; g.sCz = Hd;   // (short K: written in place)
+  g.M = 1; g.N = Hd; g.K = K; g.nbatch = groups; g.splitk = split;
+  if (!a->fuse) {
+    RC(gemm_f32(g, st));
+    return split == 1 ? SERL_OK : reduce_slabs(a->slabs, split, Hd, groups, 1, Hd, nullptr, 0, out, Hd, a->state_only ? Hd : 0, false, st);
+  }
+  if (split > 1) {
+    g.sCz = 64L * Hd;
+    g.epi = kEpiReduce; g.zred = split; g.ctr = a->ctr; g.out = out; g.ld_out = Hd; g.out_gstride = Hd;
+    SERL_REQUIRE((long)groups * split * g.sCz <= a->slabs_cap && groups * cdiv(Hd, 64) <= kCtrPerLane, "head gradient exceeds the scratch");
+  }
+  SERL_REQUIRE(a->pg_defer && a->pg_nwg < kMaxGemmGroups, "no room for the deferred head-gradient GEMM");
+  a->pg_wg[a->pg_nwg++] = g;
+  return SERL_OK;
+}
+
+// REDQ target + critic loss (sac.py:142-191).  Fused: *rider = the arguments, for the LayerNorm-backward launch that consumes
+// dQ to carry as a rider workgroup.  Else: the critic_loss launch, no rider.
+int critic_loss_or_rider(serl_agent* a, const LossArgs& L, hipStream_t st, const LossArgs** rider) {
+  *rider = nullptr;
+  if (a->fuse) { *rider = &L; return SERL_OK; }
+  return critic_loss(L.qt, L.q, L.reward, L.mask, L.sel, L.E, L.B, L.discount, L.inv_norm, L.y_out, L.dq, L.scalars, L.dbias, st,
+                     L.per_member != 0, L.logp_next, L.alpha);
+}
+
+// Gradient of the policy's head biases (mean, log_std): the column sums of dpre.  Fused: a job of the phase's deferred
+// column-sum launch.  Else: a colsum launch.
+int head_bias_grad(serl_agent* a, int cnt, float* out, long out_gstride, hipStream_t st) {
+  const int A = a->cfg.act_dim;
+  if (!a->fuse) return colsum(a->dpre, nullptr, 2, cnt, A, out, out_gstride, false, st);
+  SERL_REQUIRE(a->pg_ncs < kMaxColsum, "no room for the head-bias gradient job");
+  a->pg_cs[a->pg_ncs++] = Colsum3Args{a->dpre, nullptr, nullptr, 2, cnt, A, nullptr, out, nullptr, out_gstride, 1};
+  return SERL_OK;
+}
+
+// Critic backward down to dx [cnt][E+A]; parameter grads into Gc when `pg`.  The gradient wrt Q [ens][cnt] is the dq of the
+// critic loss `loss` (critic phase), or the constant `dq_const` for every element (actor loss, loss == nullptr).
+int critic_bwd(serl_agent* a, const float* P, CritBuf& cb, int cnt, bool pg, hipStream_t st, const LossArgs* loss, float dq_const) {
   const serl_agent_cfg& c = a->cfg;
   const Offs& o = a->o;
   const int Hd = c.hidden, N = c.ensemble;
   float* G = pg ? a->Gc : nullptr;
-  if (a->fuse) {
-    if (pg) {   // head kernel gradient: a deferred GEMM; a long K is split and the slabs are summed by the last arriver
-      GemmDesc g{};
-      const int groups = a->state_only ? N : 1, K = a->state_only ? cnt : N * cnt, split = K <= 1024 ? 1 : (a->state_only ? 4 : 8);
-      g.A = a->dq; g.sAm = 1; g.sAk = 1; g.sAb = a->state_only ? cnt : 0;   // one row: dq as [1][K]
-      g.B = cb.m.h2; g.sBk = Hd; g.sBn = 1; g.sBb = a->state_only ? (long)cnt * Hd : 0;
-      g.M = 1; g.N = Hd; g.K = K; g.nbatch = groups; g.splitk = split;
-      if (split == 1) { g.C = a->Gc + o.c_hw; g.ldc = Hd; g.sCz = Hd; }
-      else {
-        g.C = a->slabs; g.ldc = Hd; g.sCz = 64L * Hd;
-        g.epi = kEpiReduce; g.zred = split; g.ctr = a->ctr; g.out = a->Gc + o.c_hw; g.ld_out = Hd; g.out_gstride = Hd;
-        SERL_REQUIRE((long)groups * split * g.sCz <= a->slabs_cap && groups * cdiv(Hd, 64) <= kCtrPerLane, "head gradient exceeds the scratch");
-      }
-      SERL_REQUIRE(a->pg_defer && a->pg_nwg < kMaxGemmGroups, "no room for the deferred head-gradient GEMM");
-      a->pg_wg[a->pg_nwg++] = g;
-    }
-    RC(dense_ln_tanh_bwd(a, nullptr, Hd, (long)cnt * Hd, cb.m.h2, Hd, (long)cnt * Hd, cb.m.xh2, cb.m.rs2, P + o.c_g2, Hd,
-                         N, cnt, Hd, a->da2, a->dg2, G, o.c_g2, o.c_be2, o.c_b2, Hd, st, dq, P + o.c_hw, dq_const,
-                         a->state_only ? Hd : 0, loss));
-    if (pg)
-      RC(wgrad(a, cb.m.h1, Hd, (long)cnt * Hd, a->da2, Hd, (long)cnt * Hd, a->Gc + o.c_w2, Hd, (long)Hd * Hd, N, Hd, Hd,
-               cnt, st));
-    RC(igrad(a->da2, Hd, (long)cnt * Hd, P + o.c_w2, Hd, (long)Hd * Hd, a->dh1, Hd, (long)cnt * Hd, N, cnt, Hd, Hd, st));
-    RC(dense_ln_tanh_bwd(a, a->dh1, Hd, (long)cnt * Hd, cb.m.h1, Hd, (long)cnt * Hd, cb.m.xh1, cb.m.rs1, P + o.c_g1, Hd,
-                         N, cnt, Hd, a->da1, a->dg1, G, o.c_g1, o.c_be1, o.c_b1, Hd, st));
-    if (pg)
-      RC(wgrad(a, cb.x, a->XA, 0, a->da1, Hd, (long)cnt * Hd, a->Gc + o.c_w1, Hd, (long)a->XA * Hd, N, a->XA, Hd, cnt, st));
-    // dx = sum_e da1[e] * W1[e]^T, the ensemble sum inside the GEMM launch
-    return igrad_sum(a, a->da1, Hd, (long)cnt * Hd, P + o.c_w1, Hd, (long)a->XA * Hd, a->dx, a->XA, N, cnt, a->XA, Hd, st);
-  }
-  if (pg && !a->state_only) {  // shared head kernel: dw[j] = sum_{e,b} dq*h2
-    GemmDesc g{};
-    g.A = a->dq; g.sAm = 0; g.sAk = 1; g.sAb = 0;
-    g.B = cb.m.h2; g.sBk = Hd; g.sBn = 1; g.sBb = 0;
-    const bool direct = N * cnt <= 1024;  // short K: written in place, no K-split slabs to reduce
-    g.C = direct ? a->Gc + o.c_hw : a->slabs; g.ldc = Hd; g.sCz = Hd;
-    g.M = 1; g.N = Hd; g.K = N * cnt; g.nbatch = 1; g.splitk = direct ? 1 : 8;
-    RC(gemm_f32(g, st));
-    if (!direct) RC(reduce_slabs(a->slabs, 8, Hd, 1, 1, Hd, nullptr, 0, a->Gc + o.c_hw, Hd, 0, false, st));
-  } else if (pg) {  // one head per member: dw[e][j] = sum_b dq[e][b]*h2[e][b][j]
-    GemmDesc g{};
-    g.A = a->dq; g.sAm = 0; g.sAk = 1; g.sAb = cnt;
-    g.B = cb.m.h2; g.sBk = Hd; g.sBn = 1; g.sBb = (long)cnt * Hd;
-    const bool direct = cnt <= 1024;
-    g.C = direct ? a->Gc + o.c_hw : a->slabs; g.ldc = Hd; g.sCz = Hd;
-    g.M = 1; g.N = Hd; g.K = cnt; g.nbatch = N; g.splitk = direct ? 1 : 4;
-    RC(gemm_f32(g, st));
-    if (!direct) RC(reduce_slabs(a->slabs, 4, Hd, N, 1, Hd, nullptr, 0, a->Gc + o.c_hw, Hd, Hd, false, st));
-  }
-  // gradient through the shared head dh2 = dq (x) w is formed inside the LN backward kernel (rank-1 mode)
+  const LossArgs* rider = nullptr;
+  if (loss) RC(critic_loss_or_rider(a, *loss, st, &rider));
+  if (pg) RC(head_kernel_grad(a, cb, cnt, st));
+  // gradient through the head dh2 = dq (x) w is formed inside the LN backward kernel (rank-1 mode)
   RC(dense_ln_tanh_bwd(a, nullptr, Hd, (long)cnt * Hd, cb.m.h2, Hd, (long)cnt * Hd, cb.m.xh2, cb.m.rs2, P + o.c_g2, Hd,
-                       N, cnt, Hd, a->da2, a->dg2, G, o.c_g2, o.c_be2, o.c_b2, Hd, st, dq, P + o.c_hw, dq_const,
-                       a->state_only ? Hd : 0));
+                       N, cnt, Hd, a->da2, a->dg2, G, o.c_g2, o.c_be2, o.c_b2, Hd, st, loss ? loss->dq : nullptr, P + o.c_hw, dq_const,
+                       a->state_only ? Hd : 0, rider));
   if (pg)
     RC(wgrad(a, cb.m.h1, Hd, (long)cnt * Hd, a->da2, Hd, (long)cnt * Hd, a->Gc + o.c_w2, Hd, (long)Hd * Hd, N, Hd, Hd,
              cnt, st));
@@ -686,41 +675,8 @@ int critic_bwd(serl_agent* a, const float* P, CritBuf& cb, int cnt, bool pg, hip
   if (pg)
     RC(wgrad(a, cb.x, a->XA, 0, a->da1, Hd, (long)cnt * Hd, a->Gc + o.c_w1, Hd, (long)a->XA * Hd, N, a->XA, Hd, cnt, st));
   // dx = sum_e da1[e] * W1[e]^T
-  RC(igrad(a->da1, Hd, (long)cnt * Hd, P + o.c_w1, Hd, (long)a->XA * Hd, a->slabs, a->XA, (long)cnt * a->XA, N, cnt,
-           a->XA, Hd, st));
-  return reduce_slabs(a->slabs, N, (long)cnt * a->XA, 1, cnt, a->XA, nullptr, 0, a->dx, a->XA, 0, false, st);
+  return igrad_sum(a, a->da1, Hd, (long)cnt * Hd, P + o.c_w1, Hd, (long)a->XA * Hd, a->dx, a->XA, N, cnt, a->XA, Hd, st);
 }
-
-// Encoder-head backward for the critic path: d_enc = dx[:, :E] -> camera heads (SLE kernel, Dense,
-// LayerNorm) and the proprio branch, into Gc.
-int encode_bwd_critic(serl_agent* a, const float* P, EncBuf& e, int off, int cnt, hipStream_t st) {
-  const serl_agent_cfg& c = a->cfg;
-  const Offs& o = a->o;
-  const int Bn = c.bottleneck;
-  RC(dense_ln_tanh_bwd(a, a->dx, a->XA, Bn, e.enc, e.ld, Bn, e.xhat, e.rstd, P + o.cam[0].lng, o.cam_stride,
-                       c.n_cam, cnt, Bn, a->dz, a->dgz, a->Gc, o.cam[0].lng, o.cam[0].lnb, o.cam[0].db,
-                       o.cam_stride, st));
-  RC(wgrad(a, e.f, a->D, (long)c.batch * a->D, a->dz, Bn, (long)cnt * Bn, a->Gc + o.cam[0].dW, Bn, o.cam_stride,
-           c.n_cam, a->D, Bn, cnt, st));
-  RC(igrad(a->dz, Bn, (long)cnt * Bn, P + o.cam[0].dW, Bn, o.cam_stride, a->df, a->D, (long)cnt * a->D, c.n_cam, cnt,
-           a->D, Bn, st));
-  if (a->small)   // through the average pool and the four convs of the forward pass that ran last (theta at observations)
-    return small_backward(a->sws, P, o.cam[0].conv, o.cam_stride, c.n_cam, cnt, a->df, (long)cnt * a->D, a->Gc, st);
-  const long sle_n = (long)a->HW * 512 * c.sle_features;
-  {  // dK of every camera: one partial-sum launch (grid.z = camera x batch split) + one reduction
-    const float* x = a->feats + (long)off * a->HW * 512;
-    RC(sle_bwd(x, a->df, a->sle_part, cnt, a->HW, 512, kSleSplit, c.n_cam, (long)c.batch * a->HW * 512,
-               (long)cnt * a->D, (long)kSleSplit * sle_n, st));
-    RC(reduce_slabs(a->sle_part, kSleSplit, sle_n, c.n_cam, 1, (int)sle_n, nullptr, 0, a->Gc + o.cam[0].sle, sle_n,
-                    o.cam_stride, false, st));
-  }
-  return SERL_OK;
-}
-
-// Fused chain: the critic path's backward below dx in one piece -- the LayerNorm backward of the camera heads (width 256) and of
-// the proprio branch (width 64) share ONE launch, the SpatialLearnedEmbeddings gradient sums its batch splits itself
-// (sle_bwd_fused), every parameter gradient is deferred.  `event_bucket0`: see serl_agent_critic_grads_bucketed.
-int enc_proprio_bwd_critic_fused(serl_agent* a, const float* P, EncBuf& e, int off, int cnt, hipStream_t st, void* event_bucket0);
 
 // proprio-branch backward: dy = gradient wrt the proprio code (ld/offset given), into G (Gc or Ga)
 int proprio_bwd(serl_agent* a, const float* P, const float* dy, long ld_dy, const float* y, long ld_y, EncBuf& e,
@@ -734,68 +690,57 @@ int proprio_bwd(serl_agent* a, const float* P, const float* dy, long ld_dy, cons
   return wgrad(a, s, c.state_dim, 0, a->dp, Pd, 0, G + (o.p_W - base_off), Pd, 0, 1, c.state_dim, Pd, cnt, st);
 }
 
-int enc_proprio_bwd_critic_fused(serl_agent* a, const float* P, EncBuf& e, int off, int cnt, hipStream_t st, void* event_bucket0) {
+// The critic path's backward below dx: d_enc = dx[:, :E] -> the proprio branch and the camera heads (LayerNorm, Dense, SLE
+// kernel or the SmallEncoder's convs), into Gc.  `event_bucket0`: see serl_agent_critic_grads_bucketed.
+// Fused: the LayerNorm backward of the camera heads (width 256) and of the proprio branch (width 64) share ONE launch in front
+// of the event, and the SpatialLearnedEmbeddings gradient sums its batch splits itself (sle_bwd_fused).  Else: the proprio
+// LayerNorm backward in front of the event, the camera heads' behind it, sle_bwd + reduce_slabs.
+int enc_bwd_critic(serl_agent* a, const float* P, EncBuf& e, int off, int cnt, hipStream_t st, void* event_bucket0) {
   const serl_agent_cfg& c = a->cfg;
   const Offs& o = a->o;
   const int Bn = c.bottleneck, Pd = c.proprio_dim;
   const long pc = (long)c.n_cam * Bn;
-  LnBwdArgs lb[2] = {LnBwdArgs{}, LnBwdArgs{}};
-  LnBwdArgs& h = lb[0];   // camera heads
-  h.dy = a->dx; h.ld_dy = a->XA; h.dy_goff = Bn;
-  h.y = e.enc; h.ld_y = e.ld; h.y_goff = Bn;
-  h.xhat = e.xhat; h.rstd = e.rstd; h.gamma = P + o.cam[0].lng; h.pstride = o.cam_stride;
-  h.rows = c.n_cam * cnt; h.rows_per_group = cnt; h.dx = a->dz; h.dg = a->dgz; h.D = Bn;
-  LnBwdArgs& q = lb[1];   // proprio branch
-  q.dy = a->dx + pc; q.ld_dy = a->XA; q.dy_goff = 0;
-  q.y = e.enc + pc; q.ld_y = e.ld; q.y_goff = 0;
-  q.xhat = e.pxhat; q.rstd = e.prstd; q.gamma = P + o.p_g; q.pstride = 0;
-  q.rows = cnt; q.rows_per_group = cnt; q.dx = a->dp; q.dg = a->dgp; q.D = Pd;
-  RC(ln_tanh_bwd_multi(lb, 2, LossArgs{}, st));
-  SERL_REQUIRE(a->pg_defer && a->pg_ncs + 2 <= kMaxColsum, "no room for the deferred LayerNorm gradients");
-  a->pg_cs[a->pg_ncs++] = Colsum3Args{a->dgp, e.pxhat, a->dp, 1, cnt, Pd, a->Gc + o.p_g, a->Gc + o.p_be, a->Gc + o.p_b, 0, 0};
-  a->pg_cs[a->pg_ncs++] = Colsum3Args{a->dgz, e.xhat, a->dz, c.n_cam, cnt, Bn, a->Gc + o.cam[0].lng, a->Gc + o.cam[0].lnb,
-                                      a->Gc + o.cam[0].db, o.cam_stride, 0};
-  const float* s = a->cur.state + (long)off * c.state_dim;
-  RC(wgrad(a, s, c.state_dim, 0, a->dp, Pd, 0, a->Gc + o.p_W, Pd, 0, 1, c.state_dim, Pd, cnt, st));
-  if (event_bucket0) {   // bucket 0 (ensemble | head | proprio | scalars) is final once these deferred jobs have run
+  if (a->fuse && !a->state_only) {
+    LnBwdArgs lb[2] = {ln_bwd_args(a->dx, a->XA, Bn, e.enc, e.ld, Bn, e.xhat, e.rstd, P + o.cam[0].lng, o.cam_stride, c.n_cam, cnt, a->dz, a->dgz),
+                       ln_bwd_args(a->dx + pc, a->XA, 0, e.enc + pc, e.ld, 0, e.pxhat, e.prstd, P + o.p_g, 0, 1, cnt, a->dp, a->dgp)};
+    lb[0].D = Bn; lb[1].D = Pd;
+    RC(ln_tanh_bwd_multi(lb, 2, LossArgs{}, st));
+    SERL_REQUIRE(a->pg_defer && a->pg_ncs + 2 <= kMaxColsum, "no room for the deferred LayerNorm gradients");
+    a->pg_cs[a->pg_ncs++] = Colsum3Args{a->dgp, e.pxhat, a->dp, 1, cnt, Pd, a->Gc + o.p_g, a->Gc + o.p_be, a->Gc + o.p_b, 0, 0};
+    a->pg_cs[a->pg_ncs++] = Colsum3Args{a->dgz, e.xhat, a->dz, c.n_cam, cnt, Bn, a->Gc + o.cam[0].lng, a->Gc + o.cam[0].lnb,
+                                        a->Gc + o.cam[0].db, o.cam_stride, 0};
+    const float* s = a->cur.state + (long)off * c.state_dim;
+    RC(wgrad(a, s, c.state_dim, 0, a->dp, Pd, 0, a->Gc + o.p_W, Pd, 0, 1, c.state_dim, Pd, cnt, st));
+  } else if (!a->state_only) {
+    RC(proprio_bwd(a, P, a->dx + pc, a->XA, e.enc + pc, e.ld, e, 0, off, cnt, a->Gc, 0, st));
+  }
+  if (event_bucket0) {   // bucket 0 (ensemble | head | proprio | scalars) is final once the jobs deferred so far have run
     RC(flush_param_grads(a, st));
     SERL_HIP(hipEventRecord((hipEvent_t)event_bucket0, st));
   }
+  if (a->state_only) return SERL_OK;
+  if (!a->fuse)
+    RC(dense_ln_tanh_bwd(a, a->dx, a->XA, Bn, e.enc, e.ld, Bn, e.xhat, e.rstd, P + o.cam[0].lng, o.cam_stride,
+                         c.n_cam, cnt, Bn, a->dz, a->dgz, a->Gc, o.cam[0].lng, o.cam[0].lnb, o.cam[0].db,
+                         o.cam_stride, st));
   RC(wgrad(a, e.f, a->D, (long)c.batch * a->D, a->dz, Bn, (long)cnt * Bn, a->Gc + o.cam[0].dW, Bn, o.cam_stride,
            c.n_cam, a->D, Bn, cnt, st));
   RC(igrad(a->dz, Bn, (long)cnt * Bn, P + o.cam[0].dW, Bn, o.cam_stride, a->df, a->D, (long)cnt * a->D, c.n_cam, cnt,
            a->D, Bn, st));
-  if (a->small) return small_backward(a->sws, P, o.cam[0].conv, o.cam_stride, c.n_cam, cnt, a->df, (long)cnt * a->D, a->Gc, st);
+  if (a->small)   // through the average pool and the four convs of the forward pass that ran last (theta at observations)
+    return small_backward(a->sws, P, o.cam[0].conv, o.cam_stride, c.n_cam, cnt, a->df, (long)cnt * a->D, a->Gc, st);
+  // dK of every camera: partial sums over batch splits (grid.z = camera x batch split), summed by the last arriver or a reduction
   const long sle_n = (long)a->HW * 512 * c.sle_features;
   const float* x = a->feats + (long)off * a->HW * 512;
-  SERL_REQUIRE((long)c.n_cam * a->HW * 2 <= kCtrPerLane, "SLE gradient exceeds the arrival counters");
-  return sle_bwd_fused(x, a->df, a->sle_part, cnt, a->HW, 512, kSleSplit, c.n_cam, (long)c.batch * a->HW * 512, (long)cnt * a->D,
-                       (long)kSleSplit * sle_n, a->Gc + o.cam[0].sle, o.cam_stride, a->ctr, st);
-}
-
-// Noise of one update phase: caller-provided tensors are used as they are (parity mode), missing ones are
-// generated on the device -- all of them by ONE launch (NoiseBatch::flush).
-struct NoiseBatch {
-  NoiseJob jobs[kMaxMulti];
-  int n = 0;
-  int flush(hipStream_t st) { return n ? gen_noise_multi(jobs, n, st) : SERL_OK; }
-};
-void fetch_noise(serl_agent* a, NoiseBatch& nb, const float* given_eps, const uint8_t* given_mask, int slot,
-                 int cnt_total, const float** eps, const uint8_t** mask) {
-  const serl_agent_cfg& c = a->cfg;
-  if (given_eps) *eps = given_eps;
-  else {
-    nb.jobs[nb.n++] = NoiseJob{a->eps_buf[slot], (long)cnt_total * c.act_dim, c.seed ^ (0xA5A5ull + 7919ull * (++a->noise_ctr)), 0, 0.f,
-                               cnt_total, a->shard_global, a->shard_off, c.act_dim};
-    *eps = a->eps_buf[slot];
+  if (a->fuse) {
+    SERL_REQUIRE((long)c.n_cam * a->HW * 2 <= kCtrPerLane, "SLE gradient exceeds the arrival counters");
+    return sle_bwd_fused(x, a->df, a->sle_part, cnt, a->HW, 512, kSleSplit, c.n_cam, (long)c.batch * a->HW * 512, (long)cnt * a->D,
+                         (long)kSleSplit * sle_n, a->Gc + o.cam[0].sle, o.cam_stride, a->ctr, st);
   }
-  if (given_mask || a->state_only || a->small) *mask = a->small ? nullptr : given_mask;  // (no dropout without the SLE branch)
-  else {
-    nb.jobs[nb.n++] = NoiseJob{a->mask_buf[slot], (long)c.n_cam * cnt_total * a->D,
-                               c.seed ^ (0x5A5Aull + 104729ull * (++a->noise_ctr)), 1, 1.0f - c.dropout,
-                               cnt_total, a->shard_global, a->shard_off, a->D};
-    *mask = a->mask_buf[slot];
-  }
+  RC(sle_bwd(x, a->df, a->sle_part, cnt, a->HW, 512, kSleSplit, c.n_cam, (long)c.batch * a->HW * 512,
+             (long)cnt * a->D, (long)kSleSplit * sle_n, st));
+  return reduce_slabs(a->sle_part, kSleSplit, sle_n, c.n_cam, 1, (int)sle_n, nullptr, 0, a->Gc + o.cam[0].sle, sle_n,
+                      o.cam_stride, false, st);
 }
 
 // rows of the GLOBAL (mini)batch in front of this rank's `cnt` rows (serl_agent_set_shard: this rank owns rows shard_off.. of a
@@ -804,60 +749,79 @@ static long tf_row0_of(const serl_agent* a, int cnt) {
   return a->shard_global ? (a->shard_off * (long)cnt) / std::max<long>(a->cur.batch, 1) : 0;
 }
 
-// One-launch-per-operation chain (SERL_CHAIN_FUSE=0) with jax.random KEYS instead of tensors: the draws are materialised in the
-// agent's noise buffers by serl_jax_fill (rows [off, off + cnt) of the buffers = rows tf_row0.. of the global arrays) and then
-// taken as given tensors.  *eps / *mask are replaced only where the caller gave a key and no tensor.
-int jax_noise_tensors(serl_agent* a, const uint32_t* key_eps, const uint32_t* key_mask, int slot, int off, int cnt, long global_count,
-                      hipStream_t st, const float** eps, const uint8_t** mask) {
-  const serl_agent_cfg& c = a->cfg;
-  serl_jax_job jobs[1 + SERL_MAX_CAMS];
-  int n = 0;
-  const long row0 = tf_row0_of(a, cnt);
-  if (key_eps && !*eps) {
-    serl_jax_job& j = jobs[n++];
-    j = serl_jax_job{};
-    j.key[0] = key_eps[0]; j.key[1] = key_eps[1]; j.kind = SERL_JAX_NORMAL;
-    j.n_total = global_count * c.act_dim; j.first = row0 * c.act_dim; j.count = (long)cnt * c.act_dim;
-    j.out = a->eps_buf[slot] + (long)off * c.act_dim;
-    *eps = a->eps_buf[slot];
-  }
-  if (key_mask && !*mask && !a->state_only && !a->small) {
-    for (int k = 0; k < c.n_cam; ++k) {
-      serl_jax_job& j = jobs[n++];
-      j = serl_jax_job{};
-      j.key[0] = key_mask[2 * k]; j.key[1] = key_mask[2 * k + 1]; j.kind = SERL_JAX_BERNOULLI_U8; j.p = 1.0f - c.dropout;
-      j.n_total = global_count * a->D; j.first = row0 * a->D; j.count = (long)cnt * a->D;
-      j.out = a->mask_buf[slot] + ((long)k * a->cur.batch + off) * a->D;
-    }
-    *mask = a->mask_buf[slot];
-  }
-  return n ? serl_jax_fill(c.device, jobs, n, (void*)st) : SERL_OK;
-}
-
-// Fused chain: nothing is generated ahead of time.  Missing normal draws are hashed inside the policy-head epilogue (same
-// stream as gen_noise: seed and global-row indexing unchanged) and kept in eps_buf[slot]; a missing Dropout mask is hashed
-// inside the SLE kernel.  The seeds advance exactly as fetch_noise advances them.
-// key_eps / key_mask (serl_noise key_*, host words; nullptr = none): jax.random keys of the draws -- used where the tensor is absent.
-struct FusedNoise {
-  const float* eps; float* eps_out; uint64_t eps_seed; const uint8_t* mask; int gen_mask; uint64_t mask_seed;
-  const uint32_t* tf_eps; const uint32_t* tf_mask;
+// Noise of one policy evaluation and of the encoder pass that feeds it: the normal draws eps [B][A] and the Dropout keep-mask
+// [n_cam][B][D].  Each is a caller-provided tensor (parity mode), drawn from a jax.random key (serl_noise key_*, host words), or
+// hashed from a seed of the agent's own stream -- in that order of preference.
+struct PhaseNoise {
+  const float* eps; float* eps_out;        // eps == nullptr: drawn into eps_out from tf_eps, or else from eps_seed
+  const uint32_t* tf_eps; uint64_t eps_seed;
+  const uint8_t* mask; uint8_t* mask_out;  // mask == nullptr: gen_mask 0 = no Dropout, 1 = hashed from mask_seed, 2 = drawn from tf_mask
+  int gen_mask; const uint32_t* tf_mask; uint64_t mask_seed;
 };
-FusedNoise fetch_noise_fused(serl_agent* a, const float* given_eps, const uint8_t* given_mask, int slot,
-                             const uint32_t* key_eps = nullptr, const uint32_t* key_mask = nullptr) {
+// The one place that advances the agent's noise stream: a seed is taken for eps, then for the mask, where neither tensor nor key
+// is given (no Dropout without the SLE branch).  Buffers of `slot`.
+PhaseNoise draw_noise(serl_agent* a, const float* given_eps, const uint8_t* given_mask, int slot, const uint32_t* key_eps,
+                      const uint32_t* key_mask) {
   const serl_agent_cfg& c = a->cfg;
-  FusedNoise f{};
-  f.eps = given_eps;
-  f.eps_out = a->eps_buf[slot];
+  PhaseNoise z{};
+  z.eps = given_eps; z.eps_out = a->eps_buf[slot];
+  z.mask_out = a->mask_buf[slot];
   if (!given_eps) {
-    if (key_eps) f.tf_eps = key_eps;
-    else f.eps_seed = c.seed ^ (0xA5A5ull + 7919ull * (++a->noise_ctr));
+    if (key_eps) z.tf_eps = key_eps;
+    else z.eps_seed = c.seed ^ (0xA5A5ull + 7919ull * (++a->noise_ctr));
   }
-  if (given_mask || a->state_only || a->small) f.mask = a->small ? nullptr : given_mask;
-  else if (key_mask) { f.gen_mask = 2; f.tf_mask = key_mask; }
-  else { f.gen_mask = 1; f.mask_seed = c.seed ^ (0x5A5Aull + 104729ull * (++a->noise_ctr)); }
-  return f;
+  if (given_mask || a->state_only || a->small) z.mask = a->small ? nullptr : given_mask;
+  else if (key_mask) { z.gen_mask = 2; z.tf_mask = key_mask; }
+  else { z.gen_mask = 1; z.mask_seed = c.seed ^ (0x5A5Aull + 104729ull * (++a->noise_ctr)); }
+  return z;
 }
-
+// Fused: nothing is generated ahead of time -- missing normal draws are made inside the policy-head epilogue and kept in eps_out,
+// a missing Dropout mask inside the SLE kernel.  Else: the n descriptors of a phase are materialised first and left as given
+// tensors: key draws by serl_jax_fill (rows [off, off + cnt) of the buffers = rows tf_row0.. of the global arrays), seeded ones
+// for the whole batch by ONE gen_noise_multi launch (same hash: seed and global-row indexing as in the fused kernels).
+int materialise_noise(serl_agent* a, PhaseNoise* v, int n, int off, int cnt, long global_count, hipStream_t st) {
+  if (a->fuse) return SERL_OK;
+  const serl_agent_cfg& c = a->cfg;
+  const long rows = a->cur.batch, row0 = tf_row0_of(a, cnt);
+  NoiseJob gen[kMaxMulti];
+  int ngen = 0;
+  for (int i = 0; i < n; ++i) {
+    PhaseNoise& z = v[i];
+    serl_jax_job jobs[1 + SERL_MAX_CAMS];
+    int nj = 0;
+    if (!z.eps && z.tf_eps) {
+      serl_jax_job& j = jobs[nj++];
+      j = serl_jax_job{};
+      j.key[0] = z.tf_eps[0]; j.key[1] = z.tf_eps[1]; j.kind = SERL_JAX_NORMAL;
+      j.n_total = global_count * c.act_dim; j.first = row0 * c.act_dim; j.count = (long)cnt * c.act_dim;
+      j.out = z.eps_out + (long)off * c.act_dim;
+    } else if (!z.eps) {
+      gen[ngen++] = NoiseJob{z.eps_out, rows * c.act_dim, z.eps_seed, 0, 0.f, rows, a->shard_global, a->shard_off, c.act_dim};
+    }
+    for (int k = 0; k < c.n_cam && z.gen_mask == 2; ++k) {
+      serl_jax_job& j = jobs[nj++];
+      j = serl_jax_job{};
+      j.key[0] = z.tf_mask[2 * k]; j.key[1] = z.tf_mask[2 * k + 1]; j.kind = SERL_JAX_BERNOULLI_U8; j.p = 1.0f - c.dropout;
+      j.n_total = global_count * a->D; j.first = row0 * a->D; j.count = (long)cnt * a->D;
+      j.out = z.mask_out + ((long)k * rows + off) * a->D;
+    }
+    if (z.gen_mask == 1)
+      gen[ngen++] = NoiseJob{z.mask_out, (long)c.n_cam * rows * a->D, z.mask_seed, 1, 1.0f - c.dropout, rows, a->shard_global, a->shard_off, a->D};
+    if (nj) RC(serl_jax_fill(c.device, jobs, nj, (void*)st));
+    z = PhaseNoise{z.eps ? z.eps : z.eps_out, z.eps_out, nullptr, 0, z.gen_mask ? z.mask_out : z.mask, z.mask_out, 0, nullptr, 0};
+  }
+  return ngen ? gen_noise_multi(gen, ngen, st) : SERL_OK;
+}
+// hands the noise of a phase's rows [off, off + cnt) (= rows tf_row0_of.. of the global_count rows a key draws) to its jobs
+void set_noise(const serl_agent* a, EncJob& e, PolJob& p, const PhaseNoise& z, long off, int cnt, long global_count) {
+  const int A = a->cfg.act_dim;
+  const long tf_row0 = tf_row0_of(a, cnt);
+  e.mask = z.mask; e.gen_mask = z.gen_mask; e.mask_seed = z.mask_seed;
+  e.tf_key = z.tf_mask; e.tf_rows = global_count; e.tf_row0 = tf_row0;
+  p.eps = z.eps ? z.eps + off * A : nullptr;
+  p.eps_out = z.eps_out + off * A; p.eps_seed = z.eps_seed; p.eps_row0 = a->shard_off + off;
+  p.tf_key = z.tf_eps; p.tf_rows = global_count; p.tf_row0 = tf_row0;
+}
 
 // learning rate of optimizer `tx` at `count` (optimizers.py:14-30): warm-up -> constant, or warm-up -> cosine decay
 float lr_at(const serl_agent_cfg& c, int64_t count, int tx) {
@@ -1161,74 +1125,30 @@ int serl_agent_critic_grads_bucketed(serl_agent* a, int off, int cnt, int global
   a->pg_ncs = a->pg_nwg = 0;
   a->pg_defer = true;
   const int A = c.act_dim;
-  if (a->fuse) {
-    const FusedNoise fz = fetch_noise_fused(a, noise ? noise->eps_next : nullptr, noise ? noise->mask_next : nullptr, 0,
-                                            noise && noise->key_eps_next ? noise->key_eps_next + 2 * redq_row : nullptr,
-                                            noise && noise->key_mask_next ? noise->key_mask_next + 2 * c.n_cam * redq_row : nullptr);
-    const long tf_row0 = tf_row0_of(a, cnt);
-    EncJob ej[3] = {{a->theta, 1, fz.mask, &a->encP, nullptr, nullptr},
-                    {a->theta_t, 1, nullptr, &a->encT, nullptr, nullptr},
-                    {a->theta, 0, nullptr, &a->encO, a->cur.action + (long)off * A, a->crit.x + a->E}};
-    ej[0].gen_mask = fz.gen_mask; ej[0].mask_seed = fz.mask_seed;
-    ej[0].tf_key = fz.tf_mask; ej[0].tf_rows = global_count; ej[0].tf_row0 = tf_row0;
-    RC(encode_multi(a, ej, 3, off, cnt, st));
-    PolJob pj{a->theta, &a->pol, a->encP.enc, a->encP.ld, fz.eps ? fz.eps + (long)off * A : nullptr, a->critT.x + a->E, a->XA, nullptr,
-              c.backup_entropy ? a->aux + X_ALPHA : nullptr};
-    pj.eps_out = fz.eps_out + (long)off * A; pj.eps_seed = fz.eps_seed; pj.eps_row0 = a->shard_off + off;
-    pj.tf_key = fz.tf_eps; pj.tf_rows = global_count; pj.tf_row0 = tf_row0;
-    RC(policy_fwd_multi(a, &pj, 1, cnt, st));
-    const CritJob cj[2] = {{a->theta_t, &a->critT}, {a->theta, &a->crit}};
-    RC(critic_fwd_multi(a, cj, 2, cnt, st));
-    // REDQ target + loss: a rider workgroup of the LayerNorm-backward launch that consumes dQ (no critic_loss launch)
-    const LossArgs L{1, a->critT.q, a->crit.q, a->cur.reward + off, a->cur.mask + off, sel, c.ensemble, cnt, c.discount,
-                     1.0f / ((float)c.ensemble * (float)global_count), a->ytgt, a->dq, a->SC, a->Gc + o.c_hb, a->state_only ? 1 : 0,
-                     c.backup_entropy ? a->pol.logp : nullptr, c.backup_entropy ? a->aux + X_ALPHA : nullptr};
-    SERL_REQUIRE(!a->state_only || c.ensemble <= 16, "per-member head bias supports ensembles of at most 16");
-    RC(critic_bwd(a, a->theta, a->crit, cnt, true, st, a->dq, 0.f, &L));
-    if (!a->state_only) RC(enc_proprio_bwd_critic_fused(a, a->theta, a->encO, off, cnt, st, event_bucket0));
-    else if (event_bucket0) {
-      RC(flush_param_grads(a, st));
-      SERL_HIP(hipEventRecord((hipEvent_t)event_bucket0, st));
-    }
-    RC(flush_param_grads(a, st));
-    a->last_global = global_count;
-    return SERL_OK;
-  }
-  const float* eps; const uint8_t* mask;
-  NoiseBatch nb;
-  const float* g_eps = noise ? noise->eps_next : nullptr;
-  const uint8_t* g_mask = noise ? noise->mask_next : nullptr;
-  RC(jax_noise_tensors(a, noise && noise->key_eps_next ? noise->key_eps_next + 2 * redq_row : nullptr,
-                       noise && noise->key_mask_next ? noise->key_mask_next + 2 * c.n_cam * redq_row : nullptr, 0, off, cnt, global_count,
-                       st, &g_eps, &g_mask));
-  fetch_noise(a, nb, g_eps, g_mask, 0, a->cur.batch, &eps, &mask);
-  RC(nb.flush(st));
+  PhaseNoise nz = draw_noise(a, noise ? noise->eps_next : nullptr, noise ? noise->mask_next : nullptr, 0,
+                             noise && noise->key_eps_next ? noise->key_eps_next + 2 * redq_row : nullptr,
+                             noise && noise->key_mask_next ? noise->key_mask_next + 2 * c.n_cam * redq_row : nullptr);
+  RC(materialise_noise(a, &nz, 1, off, cnt, global_count, st));
   // the three encoder passes of the critic loss in one set of launches: online policy input at next_obs
   // (dropout), target-critic input at next_obs (target_params, train=False), online-critic input at obs
   // (train=False; the batch's actions ride along into [enc | action])
-  const EncJob ej[3] = {{a->theta, 1, mask, &a->encP, nullptr, nullptr},
-                        {a->theta_t, 1, nullptr, &a->encT, nullptr, nullptr},
-                        {a->theta, 0, nullptr, &a->encO, a->cur.action + (long)off * A, a->crit.x + a->E}};
-  RC(encode_multi(a, ej, 3, off, cnt, st));
+  EncJob ej[3] = {{a->theta, 1, nullptr, &a->encP, nullptr, nullptr},
+                  {a->theta_t, 1, nullptr, &a->encT, nullptr, nullptr},
+                  {a->theta, 0, nullptr, &a->encO, a->cur.action + (long)off * A, a->crit.x + a->E}};
   // backup_entropy (sac.py:174-176) needs alpha = softplus(lagrange) of the online parameters next to the per-sample log-probs
-  const PolJob pj{a->theta, &a->pol, a->encP.enc, a->encP.ld, eps + (long)off * A, a->critT.x + a->E, a->XA, nullptr,
-                  c.backup_entropy ? a->aux + X_ALPHA : nullptr};
+  PolJob pj{a->theta, &a->pol, a->encP.enc, a->encP.ld, nullptr, a->critT.x + a->E, a->XA, nullptr,
+            c.backup_entropy ? a->aux + X_ALPHA : nullptr};
+  set_noise(a, ej[0], pj, nz, off, cnt, global_count);
+  RC(encode_multi(a, ej, 3, off, cnt, st));
   RC(policy_fwd_multi(a, &pj, 1, cnt, st));
   const CritJob cj[2] = {{a->theta_t, &a->critT}, {a->theta, &a->crit}};  // target and online ensembles together
   RC(critic_fwd_multi(a, cj, 2, cnt, st));
-  const float inv_norm = 1.0f / ((float)c.ensemble * (float)global_count);
-  RC(critic_loss(a->critT.q, a->crit.q, a->cur.reward + off, a->cur.mask + off, sel, c.ensemble, cnt, c.discount,
-                 inv_norm, a->ytgt, a->dq, a->SC, a->Gc + o.c_hb, st, a->state_only,
-                 c.backup_entropy ? a->pol.logp : nullptr, c.backup_entropy ? a->aux + X_ALPHA : nullptr));
-  RC(critic_bwd(a, a->theta, a->crit, cnt, true, st, a->dq, 0.f));
-  if (!a->state_only)
-    RC(proprio_bwd(a, a->theta, a->dx + (long)c.n_cam * c.bottleneck, a->XA, a->crit.x + (long)c.n_cam * c.bottleneck,
-                   a->XA, a->encO, 0, off, cnt, a->Gc, 0, st));
-  if (event_bucket0) {   // bucket 0 (ensemble | head | proprio | scalars) is final here: publish it before the encoder heads
-    RC(flush_param_grads(a, st));
-    SERL_HIP(hipEventRecord((hipEvent_t)event_bucket0, st));
-  }
-  if (!a->state_only) RC(encode_bwd_critic(a, a->theta, a->encO, off, cnt, st));
+  const LossArgs L{1, a->critT.q, a->crit.q, a->cur.reward + off, a->cur.mask + off, sel, c.ensemble, cnt, c.discount,
+                   1.0f / ((float)c.ensemble * (float)global_count), a->ytgt, a->dq, a->SC, a->Gc + o.c_hb, a->state_only ? 1 : 0,
+                   c.backup_entropy ? a->pol.logp : nullptr, c.backup_entropy ? a->aux + X_ALPHA : nullptr};
+  SERL_REQUIRE(!a->state_only || c.ensemble <= 16, "per-member head bias supports ensembles of at most 16");
+  RC(critic_bwd(a, a->theta, a->crit, cnt, true, st, &L, 0.f));
+  RC(enc_bwd_critic(a, a->theta, a->encO, off, cnt, st, event_bucket0));
   RC(flush_param_grads(a, st));
   a->last_global = global_count;
   return SERL_OK;
@@ -1244,107 +1164,52 @@ int serl_agent_actor_grads(serl_agent* a, int global_count, const serl_noise* no
   SERL_REQUIRE(global_count >= cnt, "global_count < local batch");
   a->pg_ncs = a->pg_nwg = 0;
   a->pg_defer = true;
-  const float* eps_pi; const uint8_t* mask_pi; const float* eps_t; const uint8_t* mask_t;
-  hipStream_t s0 = st;
-  if (a->fuse) {
-    const FusedNoise fp = fetch_noise_fused(a, noise ? noise->eps_pi : nullptr, noise ? noise->mask_obs_pi : nullptr, 1,
-                                            noise ? noise->key_eps_pi : nullptr, noise ? noise->key_mask_obs_pi : nullptr);
-    const FusedNoise ft = fetch_noise_fused(a, noise ? noise->eps_temp : nullptr, noise ? noise->mask_next_temp : nullptr, 2,
-                                            noise ? noise->key_eps_temp : nullptr, noise ? noise->key_mask_next_temp : nullptr);
-    const long tf_row0 = tf_row0_of(a, cnt);
-    EncJob ej[3] = {{a->theta, 1, ft.mask, &a->encT, nullptr, nullptr},
-                    {a->theta, 0, nullptr, &a->encO, nullptr, nullptr},
-                    {a->theta, 0, fp.mask, &a->encP, nullptr, nullptr}};
-    ej[0].gen_mask = ft.gen_mask; ej[0].mask_seed = ft.mask_seed;
-    ej[2].gen_mask = fp.gen_mask; ej[2].mask_seed = fp.mask_seed;
-    ej[0].tf_key = ft.tf_mask; ej[0].tf_rows = global_count; ej[0].tf_row0 = tf_row0;
-    ej[2].tf_key = fp.tf_mask; ej[2].tf_rows = global_count; ej[2].tf_row0 = tf_row0;
-    RC(encode_multi(a, ej, 3, 0, cnt, s0));
-    PolJob pj[2] = {{a->theta, &a->polT, a->encT.enc, a->encT.ld, ft.eps, a->act_tmp, A, a->SC + S_LOGP_NEXT, a->aux + X_ALPHA},
-                    {a->theta, &a->pol, a->encP.enc, a->encP.ld, fp.eps, a->crit.x + a->E, a->XA, a->SC + S_LOGP, nullptr}};
-    pj[0].eps_out = ft.eps_out; pj[0].eps_seed = ft.eps_seed; pj[0].eps_row0 = a->shard_off;
-    pj[1].eps_out = fp.eps_out; pj[1].eps_seed = fp.eps_seed; pj[1].eps_row0 = a->shard_off;
-    pj[0].tf_key = ft.tf_eps; pj[0].tf_rows = global_count; pj[0].tf_row0 = tf_row0;
-    pj[1].tf_key = fp.tf_eps; pj[1].tf_rows = global_count; pj[1].tf_row0 = tf_row0;
-    RC(policy_fwd_multi(a, pj, 2, cnt, s0));
-    eps_pi = fp.eps ? fp.eps : fp.eps_out;   // (the backward reads the draws the head epilogue used)
-    const CritJob cj{a->theta, &a->crit};
-    RC(critic_fwd_multi(a, &cj, 1, cnt, s0));
-    RC(critic_bwd(a, a->theta, a->crit, cnt, false, s0, nullptr, -1.0f / ((float)c.ensemble * (float)global_count)));
-    RC(policy_dist_bwd(a->dx + a->E, a->XA, a->crit.x + a->E, a->XA, a->pol.pre, a->pol.std, eps_pi, a->aux + X_ALPHA,
-                       1.0f / (float)global_count, cnt, A, c.std_min, c.std_max, a->dpre, a->crit.q, c.ensemble,
-                       a->SC + S_QPI, s0));
-    const long hs = o.a_Ws - o.a_Wm;
-    float* Ga = a->Ga;
-    const long b0 = o.Pa0;
-    RC(wgrad(a, a->pol.m.h2, Hd, 0, a->dpre, A, (long)cnt * A, Ga + (o.a_Wm - b0), A, hs, 2, Hd, A, cnt, s0));
-    SERL_REQUIRE(a->pg_ncs < kMaxColsum, "no room for the head-bias gradient job");
-    a->pg_cs[a->pg_ncs++] = Colsum3Args{a->dpre, nullptr, nullptr, 2, cnt, A, nullptr, Ga + (o.a_bm - b0), nullptr, hs, 1};
-    // dh2 = dmean W_mean^T + dlog_std W_logstd^T: both products and their sum in one launch
-    RC(igrad_sum(a, a->dpre, A, (long)cnt * A, a->theta + o.a_Wm, A, hs, a->dh2, Hd, 2, cnt, Hd, A, s0));
-    RC(dense_ln_tanh_bwd(a, a->dh2, Hd, 0, a->pol.m.h2, Hd, 0, a->pol.m.xh2, a->pol.m.rs2, a->theta + o.a_g2, 0, 1, cnt, Hd,
-                         a->da2, a->dg2, Ga, o.a_g2 - b0, o.a_be2 - b0, o.a_b2 - b0, 0, s0));
-    RC(wgrad(a, a->pol.m.h1, Hd, 0, a->da2, Hd, 0, Ga + (o.a_w2 - b0), Hd, 0, 1, Hd, Hd, cnt, s0));
-    RC(igrad(a->da2, Hd, 0, a->theta + o.a_w2, Hd, 0, a->dh1, Hd, 0, 1, cnt, Hd, Hd, s0));
-    RC(dense_ln_tanh_bwd(a, a->dh1, Hd, 0, a->pol.m.h1, Hd, 0, a->pol.m.xh1, a->pol.m.rs1, a->theta + o.a_g1, 0, 1, cnt, Hd,
-                         a->da1, a->dg1, Ga, o.a_g1 - b0, o.a_be1 - b0, o.a_b1 - b0, 0, s0));
-    RC(wgrad(a, a->encP.enc, a->encP.ld, 0, a->da1, Hd, 0, Ga + (o.a_w1 - b0), Hd, 0, 1, a->E, Hd, cnt, s0));
-    if (!a->state_only) {
-      const long pc = (long)c.n_cam * c.bottleneck;
-      RC(igrad(a->da1, Hd, 0, a->theta + o.a_w1 + pc * Hd, Hd, 0, a->dprop_y, c.proprio_dim, 0, 1, cnt, c.proprio_dim, Hd, s0));
-      RC(proprio_bwd(a, a->theta, a->dprop_y, c.proprio_dim, a->encP.enc + pc, a->encP.ld, a->encP, 0, 0, cnt, Ga, b0, s0));
-    }
-    RC(flush_param_grads(a, s0));
-    a->last_global = global_count;
-    return SERL_OK;
-  }
-  NoiseBatch nb;
-  const float* g_eps_pi = noise ? noise->eps_pi : nullptr; const uint8_t* g_mask_pi = noise ? noise->mask_obs_pi : nullptr;
-  const float* g_eps_t = noise ? noise->eps_temp : nullptr; const uint8_t* g_mask_t = noise ? noise->mask_next_temp : nullptr;
-  RC(jax_noise_tensors(a, noise ? noise->key_eps_pi : nullptr, noise ? noise->key_mask_obs_pi : nullptr, 1, 0, cnt, global_count, st,
-                       &g_eps_pi, &g_mask_pi));
-  RC(jax_noise_tensors(a, noise ? noise->key_eps_temp : nullptr, noise ? noise->key_mask_next_temp : nullptr, 2, 0, cnt, global_count, st,
-                       &g_eps_t, &g_mask_t));
-  fetch_noise(a, nb, g_eps_pi, g_mask_pi, 1, cnt, &eps_pi, &mask_pi);
-  fetch_noise(a, nb, g_eps_t, g_mask_t, 2, cnt, &eps_t, &mask_t);
-  RC(nb.flush(st));
+  enum { PI = 0, TEMP = 1 };   // noise of the policy loss (slot 1) and of the temperature loss (slot 2), drawn in this order
+  PhaseNoise nz[2] = {draw_noise(a, noise ? noise->eps_pi : nullptr, noise ? noise->mask_obs_pi : nullptr, 1,
+                                 noise ? noise->key_eps_pi : nullptr, noise ? noise->key_mask_obs_pi : nullptr),
+                      draw_noise(a, noise ? noise->eps_temp : nullptr, noise ? noise->mask_next_temp : nullptr, 2,
+                                 noise ? noise->key_eps_temp : nullptr, noise ? noise->key_mask_next_temp : nullptr)};
+  RC(materialise_noise(a, nz, 2, 0, cnt, global_count, st));
   // encoder passes of the actor step in one set of launches: temperature loss input (next_obs, dropout;
   // sac.py:223-234), critic-side encoding of obs (train=False), policy input at obs (dropout; sac.py:193-221)
-  const EncJob ej[3] = {{a->theta, 1, mask_t, &a->encT, nullptr, nullptr},
-                        {a->theta, 0, nullptr, &a->encO, nullptr, nullptr},
-                        {a->theta, 0, mask_pi, &a->encP, nullptr, nullptr}};
-  RC(encode_multi(a, ej, 3, 0, cnt, s0));
-  const PolJob pj[2] = {{a->theta, &a->polT, a->encT.enc, a->encT.ld, eps_t, a->act_tmp, A, a->SC + S_LOGP_NEXT, a->aux + X_ALPHA},
-                        {a->theta, &a->pol, a->encP.enc, a->encP.ld, eps_pi, a->crit.x + a->E, a->XA, a->SC + S_LOGP, nullptr}};
-  RC(policy_fwd_multi(a, pj, 2, cnt, s0));
+  EncJob ej[3] = {{a->theta, 1, nullptr, &a->encT, nullptr, nullptr},
+                  {a->theta, 0, nullptr, &a->encO, nullptr, nullptr},
+                  {a->theta, 0, nullptr, &a->encP, nullptr, nullptr}};
+  PolJob pj[2] = {{a->theta, &a->polT, a->encT.enc, a->encT.ld, nullptr, a->act_tmp, A, a->SC + S_LOGP_NEXT, a->aux + X_ALPHA},
+                  {a->theta, &a->pol, a->encP.enc, a->encP.ld, nullptr, a->crit.x + a->E, a->XA, a->SC + S_LOGP, nullptr}};
+  set_noise(a, ej[0], pj[0], nz[TEMP], 0, cnt, global_count);
+  set_noise(a, ej[2], pj[1], nz[PI], 0, cnt, global_count);
+  RC(encode_multi(a, ej, 3, 0, cnt, st));
+  RC(policy_fwd_multi(a, pj, 2, cnt, st));
+  const float* eps_pi = nz[PI].eps ? nz[PI].eps : nz[PI].eps_out;   // (the backward reads the draws the head used)
   const CritJob cj{a->theta, &a->crit};
-  RC(critic_fwd_multi(a, &cj, 1, cnt, s0));
-  RC(critic_bwd(a, a->theta, a->crit, cnt, false, s0, nullptr, -1.0f / ((float)c.ensemble * (float)global_count)));
+  RC(critic_fwd_multi(a, &cj, 1, cnt, st));
+  RC(critic_bwd(a, a->theta, a->crit, cnt, false, st, nullptr, -1.0f / ((float)c.ensemble * (float)global_count)));
   RC(policy_dist_bwd(a->dx + a->E, a->XA, a->crit.x + a->E, a->XA, a->pol.pre, a->pol.std, eps_pi, a->aux + X_ALPHA,
                      1.0f / (float)global_count, cnt, A, c.std_min, c.std_max, a->dpre, a->crit.q, c.ensemble,
-                     a->SC + S_QPI, s0));
-  // policy heads (mean, log_std): nbatch = 2 with uniform stride; parameter gradients off the critical chain
+                     a->SC + S_QPI, st));
+  // policy heads (mean, log_std): two groups with uniform stride; parameter gradients off the critical chain
   const long hs = o.a_Ws - o.a_Wm;
   float* Ga = a->Ga;
   const long b0 = o.Pa0;
-  RC(wgrad(a, a->pol.m.h2, Hd, 0, a->dpre, A, (long)cnt * A, Ga + (o.a_Wm - b0), A, hs, 2, Hd, A, cnt, s0));
-  RC(colsum(a->dpre, nullptr, 2, cnt, A, Ga + (o.a_bm - b0), hs, false, s0));
-  RC(igrad(a->dpre, A, (long)cnt * A, a->theta + o.a_Wm, A, hs, a->slabs, Hd, (long)cnt * Hd, 2, cnt, Hd, A, s0));
-  RC(reduce_slabs(a->slabs, 2, (long)cnt * Hd, 1, cnt, Hd, nullptr, 0, a->dh2, Hd, 0, false, s0));
+  RC(wgrad(a, a->pol.m.h2, Hd, 0, a->dpre, A, (long)cnt * A, Ga + (o.a_Wm - b0), A, hs, 2, Hd, A, cnt, st));
+  RC(head_bias_grad(a, cnt, Ga + (o.a_bm - b0), hs, st));
+  // dh2 = dmean W_mean^T + dlog_std W_logstd^T
+  RC(igrad_sum(a, a->dpre, A, (long)cnt * A, a->theta + o.a_Wm, A, hs, a->dh2, Hd, 2, cnt, Hd, A, st));
   RC(dense_ln_tanh_bwd(a, a->dh2, Hd, 0, a->pol.m.h2, Hd, 0, a->pol.m.xh2, a->pol.m.rs2, a->theta + o.a_g2, 0, 1, cnt, Hd,
-                       a->da2, a->dg2, Ga, o.a_g2 - b0, o.a_be2 - b0, o.a_b2 - b0, 0, s0));
-  RC(wgrad(a, a->pol.m.h1, Hd, 0, a->da2, Hd, 0, Ga + (o.a_w2 - b0), Hd, 0, 1, Hd, Hd, cnt, s0));
-  RC(igrad(a->da2, Hd, 0, a->theta + o.a_w2, Hd, 0, a->dh1, Hd, 0, 1, cnt, Hd, Hd, s0));
+                       a->da2, a->dg2, Ga, o.a_g2 - b0, o.a_be2 - b0, o.a_b2 - b0, 0, st));
+  RC(wgrad(a, a->pol.m.h1, Hd, 0, a->da2, Hd, 0, Ga + (o.a_w2 - b0), Hd, 0, 1, Hd, Hd, cnt, st));
+  RC(igrad(a->da2, Hd, 0, a->theta + o.a_w2, Hd, 0, a->dh1, Hd, 0, 1, cnt, Hd, Hd, st));
   RC(dense_ln_tanh_bwd(a, a->dh1, Hd, 0, a->pol.m.h1, Hd, 0, a->pol.m.xh1, a->pol.m.rs1, a->theta + o.a_g1, 0, 1, cnt, Hd,
-                       a->da1, a->dg1, Ga, o.a_g1 - b0, o.a_be1 - b0, o.a_b1 - b0, 0, s0));
-  RC(wgrad(a, a->encP.enc, a->encP.ld, 0, a->da1, Hd, 0, Ga + (o.a_w1 - b0), Hd, 0, 1, a->E, Hd, cnt, s0));
+                       a->da1, a->dg1, Ga, o.a_g1 - b0, o.a_be1 - b0, o.a_b1 - b0, 0, st));
+  RC(wgrad(a, a->encP.enc, a->encP.ld, 0, a->da1, Hd, 0, Ga + (o.a_w1 - b0), Hd, 0, 1, a->E, Hd, cnt, st));
   // image codes are stop-gradiented (encoding.py:48-49); only the proprio slice of d_enc is needed
   if (!a->state_only) {
     const long pc = (long)c.n_cam * c.bottleneck;
-    RC(igrad(a->da1, Hd, 0, a->theta + o.a_w1 + pc * Hd, Hd, 0, a->dprop_y, c.proprio_dim, 0, 1, cnt, c.proprio_dim, Hd, s0));
-    RC(proprio_bwd(a, a->theta, a->dprop_y, c.proprio_dim, a->encP.enc + pc, a->encP.ld, a->encP, 0, 0, cnt, Ga, b0, s0));
+    RC(igrad(a->da1, Hd, 0, a->theta + o.a_w1 + pc * Hd, Hd, 0, a->dprop_y, c.proprio_dim, 0, 1, cnt, c.proprio_dim, Hd, st));
+    RC(proprio_bwd(a, a->theta, a->dprop_y, c.proprio_dim, a->encP.enc + pc, a->encP.ld, a->encP, 0, 0, cnt, Ga, b0, st));
   }
-  RC(flush_param_grads(a, s0));
+  RC(flush_param_grads(a, st));
   a->last_global = global_count;
   return SERL_OK;
 }

@@ -32,7 +32,7 @@ struct serl_bc {
   long o_pW = 0, o_pb = 0, o_pg = 0, o_pbe = 0, o_w1 = 0, o_b1 = 0, o_w2 = 0, o_b2 = 0, o_Wm = 0, o_bm = 0, o_Ws = 0, o_bs = 0;
   void* arena = nullptr;
   float* params = nullptr;   // [n_params + 1]: the element behind the trainable slice is adam_ema's (unused) temperature slot
-  float *m = nullptr, *v = nullptr, *G = nullptr;   // [nt + 1], [nt + 1], [nt]: trainable slice only
+  AdamSlice opt{};           // moments, gradient and update count of the trainable slice
   TrunkWeights tw{};
   TrunkWorkspace tws{};
   TrunkPacked tpk{};
@@ -40,7 +40,6 @@ struct serl_bc {
   float *h1 = nullptr, *h2 = nullptr, *mu = nullptr, *dhead = nullptr, *dpre1 = nullptr, *dpre2 = nullptr;
   float *dprop = nullptr, *dpp = nullptr, *dgp = nullptr, *info = nullptr;
   long slabs_cap = 0;
-  int64_t step = 0;
 };
 
 namespace {
@@ -80,9 +79,7 @@ size_t carve(serl_bc* c, uint8_t* base) {
   Bump b(base);
   const long n = g.max_batch, A = g.act_dim;
   c->params = b.take<float>(c->n_params + 1);
-  c->m = b.take<float>(c->nt + 1);
-  c->v = b.take<float>(c->nt + 1);
-  c->G = b.take<float>(c->nt);
+  c->opt.carve(b, c->t0, c->nt);
   c->info = b.take<float>(2);
   uint8_t* pk = b.take<uint8_t>(trunk_packed_bytes());
   uint8_t* ws = b.take<uint8_t>(trunk_workspace_bytes(g.n_cam * g.max_batch, g.H, g.W));
@@ -249,25 +246,16 @@ int forward(serl_bc* c, const uint8_t* frames, const float* state, int n, const 
   RC(ln_tanh_fwd_multi(&l0, 1, kBottleneck, st));
   // MLP: Dense(256) -> tanh, twice (activate_final)
   const int S1 = split_under(n, kHidden, 1, 8);
-  GemmDesc g1{};
-  g1.A = c->enc; g1.sAm = c->E; g1.sAk = 1;
-  g1.B = P + c->o_w1; g1.sBk = kHidden; g1.sBn = 1;
-  g1.C = c->slabs; g1.ldc = kHidden; g1.sCz = (long)n * kHidden;
-  g1.M = n; g1.N = kHidden; g1.K = c->E; g1.nbatch = 1; g1.splitk = S1;
+  const GemmDesc g1 = gemm_fwd(c->enc, c->E, 0, P + c->o_w1, 0, c->slabs, 1, n, kHidden, c->E, S1);
   RC(gemm_f32_multi(&g1, 1, st));
   RC(dense_tanh_fwd(c->slabs, S1, g1.sCz, P + c->o_b1, c->h1, n, kHidden, st));
   const int S2 = split_under(n, kHidden, 1, 4);
-  GemmDesc g2 = g1;
-  g2.A = c->h1; g2.sAm = kHidden; g2.B = P + c->o_w2; g2.K = kHidden; g2.splitk = S2;
+  const GemmDesc g2 = gemm_fwd(c->h1, kHidden, 0, P + c->o_w2, 0, c->slabs, 1, n, kHidden, kHidden, S2);
   RC(gemm_f32_multi(&g2, 1, st));
   RC(dense_tanh_fwd(c->slabs, S2, g2.sCz, P + c->o_b2, c->h2, n, kHidden, st));
   // heads: Dense_0 (mean) and Dense_1 (log_std) as the two batches of one GEMM
   const int S3 = 4;
-  GemmDesc g3{};
-  g3.A = c->h2; g3.sAm = kHidden; g3.sAk = 1; g3.sAb = 0;
-  g3.B = P + c->o_Wm; g3.sBk = A; g3.sBn = 1; g3.sBb = c->o_Ws - c->o_Wm;
-  g3.C = c->slabs; g3.ldc = A; g3.sCz = (long)n * A;
-  g3.M = n; g3.N = A; g3.K = kHidden; g3.nbatch = 2; g3.splitk = S3;
+  const GemmDesc g3 = gemm_fwd(c->h2, kHidden, 0, P + c->o_Wm, c->o_Ws - c->o_Wm, c->slabs, 2, n, A, kHidden, S3);
   RC(gemm_f32_multi(&g3, 1, st));
   *head_split = S3;
   return SERL_OK;
@@ -301,14 +289,10 @@ int resolve(serl_bc* c, const char* section, const char* leaf, float** ptr, long
   const Leaf* l = find(c->leaves, leaf);
   SERL_REQUIRE(l, "unknown BC leaf '%s'", leaf);
   *count = l->count;
-  const std::string s = section;
-  if (s == "params") { *ptr = c->params + l->off; return SERL_OK; }
-  SERL_REQUIRE(s == "opt/mu" || s == "opt/nu", "unknown BC section '%s' (params, opt/mu, opt/nu)", section);
-  *ptr = l->off < c->t0 ? nullptr : (s == "opt/mu" ? c->m : c->v) + (l->off - c->t0);
+  if (std::string(section) == "params") { *ptr = c->params + l->off; return SERL_OK; }
+  SERL_REQUIRE(c->opt.moment(section, *l, ptr), "unknown BC section '%s' (params, opt/mu, opt/nu)", section);
   return SERL_OK;
 }
-
-constexpr const char* kFrozenMoment = "'%s' of the frozen leaf '%s' must be zero";
 
 }  // namespace
 
@@ -376,11 +360,11 @@ int serl_bc_get(serl_bc* c, const char* section, const char* leaf, float* host_o
 
 int serl_bc_set_step(serl_bc* c, int64_t step) {
   SERL_REQUIRE(c && step >= 0, "bad step");
-  c->step = step;
+  c->opt.step = step;
   return SERL_OK;
 }
 
-int64_t serl_bc_get_step(serl_bc* c) { return c ? c->step : -1; }
+int64_t serl_bc_get_step(serl_bc* c) { return c ? c->opt.step : -1; }
 
 int serl_bc_update(serl_bc* c, const serl_batch* batch, const uint8_t* dev_masks, const uint32_t* host_mask_keys, void* stream) {
   SERL_REQUIRE(c, "NULL BC agent");
@@ -391,7 +375,7 @@ int serl_bc_update(serl_bc* c, const serl_batch* batch, const uint8_t* dev_masks
   hipStream_t st = (hipStream_t)stream;
   const int n = batch->batch, A = g.act_dim;
   const float* P = c->params;
-  float* G = c->G - c->t0;   // G[o] = gradient of the trainable leaf at arena offset o
+  float* G = c->opt.grad();   // G[o] = gradient of the trainable leaf at arena offset o
   int S3 = 0;
   RC(forward(c, batch->frames, batch->state, n, dev_masks, host_mask_keys, &S3, st));
   // loss, info and the head gradients (bc.py:44-68)
@@ -400,28 +384,16 @@ int serl_bc_update(serl_bc* c, const serl_batch* batch, const uint8_t* dev_masks
   h.dmu = c->dhead; h.dls = c->dhead + (long)n * A; h.info = c->info;
   RC(launch_head(h, st));
   // dh2 = dmu Wm^T + dls Ws^T: the two products as slabs, summed by the tanh backward of layer 2
-  GemmDesc gh{};
-  gh.A = c->dhead; gh.sAm = A; gh.sAk = 1; gh.sAb = (long)n * A;
-  gh.B = P + c->o_Wm; gh.sBk = 1; gh.sBn = A; gh.sBb = c->o_Ws - c->o_Wm;
-  gh.C = c->slabs; gh.ldc = kHidden; gh.sCz = (long)n * kHidden;
-  gh.M = n; gh.N = kHidden; gh.K = A; gh.nbatch = 2; gh.splitk = 1;
+  const GemmDesc gh = gemm_igrad(c->dhead, A, (long)n * A, P + c->o_Wm, A, c->o_Ws - c->o_Wm, c->slabs, kHidden, (long)n * kHidden, 2, n, kHidden, A);
   RC(gemm_f32_multi(&gh, 1, st));
   RC(dense_tanh_bwd(c->slabs, 2, gh.sCz, c->h2, c->dpre2, n, kHidden, st));
   // dh1 = dpre2 W2^T (K-split slabs) -> dpre1
   const int S2 = split_under(n, kHidden, 1, 4);
-  GemmDesc gd{};
-  gd.A = c->dpre2; gd.sAm = kHidden; gd.sAk = 1;
-  gd.B = P + c->o_w2; gd.sBk = 1; gd.sBn = kHidden;
-  gd.C = c->slabs; gd.ldc = kHidden; gd.sCz = (long)n * kHidden;
-  gd.M = n; gd.N = kHidden; gd.K = kHidden; gd.nbatch = 1; gd.splitk = S2;
+  const GemmDesc gd = gemm_igrad(c->dpre2, kHidden, 0, P + c->o_w2, kHidden, 0, c->slabs, kHidden, (long)n * kHidden, 1, n, kHidden, kHidden, S2);
   RC(gemm_f32_multi(&gd, 1, st));
   RC(dense_tanh_bwd(c->slabs, S2, gd.sCz, c->h1, c->dpre1, n, kHidden, st));
   // gradient of the proprio code only (the image codes are behind stop_gradient): dpre1 W1[Eimg:E]^T
-  GemmDesc gp{};
-  gp.A = c->dpre1; gp.sAm = kHidden; gp.sAk = 1;
-  gp.B = P + c->o_w1 + (long)c->Eimg * kHidden; gp.sBk = 1; gp.sBn = kHidden;
-  gp.C = c->dprop; gp.ldc = kProprio; gp.sCz = 0;
-  gp.M = n; gp.N = kProprio; gp.K = kHidden; gp.nbatch = 1; gp.splitk = 1;
+  const GemmDesc gp = gemm_igrad(c->dpre1, kHidden, 0, P + c->o_w1 + (long)c->Eimg * kHidden, kHidden, 0, c->dprop, kProprio, 0, 1, n, kProprio, kHidden);
   RC(gemm_f32_multi(&gp, 1, st));
   LnBwdArgs lb{};
   lb.dy = c->dprop; lb.ld_dy = kProprio;
@@ -442,12 +414,7 @@ int serl_bc_update(serl_bc* c, const serl_batch* batch, const uint8_t* dev_masks
   };
   RC(colsum3_multi(cs, 5, st));
   auto wg = [&](const float* X, long ldx, const float* dY, long ldy, float* out, int Mx, int Ny) {
-    GemmDesc w{};
-    w.A = X; w.sAm = 1; w.sAk = ldx;
-    w.B = dY; w.sBk = ldy; w.sBn = 1;
-    w.C = out; w.ldc = Ny; w.sCz = 0;
-    w.M = Mx; w.N = Ny; w.K = n; w.nbatch = 1; w.splitk = 1;
-    return w;
+    return gemm_wgrad(X, ldx, 0, dY, ldy, 0, out, Ny, 0, 1, Mx, Ny, n);
   };
   const GemmDesc wgs[5] = {
       wg(c->enc, c->E, c->dpre1, kHidden, G + c->o_w1, c->E, kHidden),
@@ -458,9 +425,7 @@ int serl_bc_update(serl_bc* c, const serl_batch* batch, const uint8_t* dev_masks
   };
   RC(gemm_f32_multi(wgs, 5, st));
   // optax.adam(lr) over the trainable slice (bc.py:139 via common.py:170-220); one count, no schedule, no clip
-  RC(adam_ema(adam_slice(c->params + c->t0, c->nt, c->G, c->m, c->v, g.lr, c->step + 1), st));
-  c->step += 1;
-  return SERL_OK;
+  return c->opt.apply(c->params, g.lr, st);
 }
 
 int serl_bc_read_info(serl_bc* c, float out[2], void* stream) {

@@ -23,9 +23,9 @@ constexpr int kHidden = 256, kBottleneck = 256, kSleFeatures = 8, kSleSplit = 8;
 struct ClsTrain {
   int max_batch = 0;
   float lr = 0.f;
-  int64_t step = 0;
   void* arena = nullptr;
-  float *m = nullptr, *v = nullptr, *G = nullptr, *info = nullptr;   // [nt + 1], [nt + 1], [nt], [2]
+  AdamSlice opt{};                               // moments, gradient and update count of the trainable slice
+  float *info = nullptr;                         // [2]
   TrunkWorkspace tws{};
   float *feats = nullptr;                        // [n_cam][n][HW][512]
   float *f = nullptr;                            // [2][n_cam][n][D]
@@ -189,11 +189,7 @@ int serl_classifier_logits(serl_classifier* c, const uint8_t* dev_frames, int n,
   RC(ln_tanh_fwd_multi(&l0, 1, kBottleneck, st));
   // Dense(256) -> LayerNorm -> ReLU -> Dense(1)
   const int S1 = split_under(n, kHidden, 1, 8);
-  GemmDesc g1{};
-  g1.A = c->enc; g1.sAm = c->E; g1.sAk = 1; g1.sAb = 0;
-  g1.B = P + c->o_w1; g1.sBk = kHidden; g1.sBn = 1; g1.sBb = 0;
-  g1.C = c->slabs; g1.ldc = kHidden; g1.sCz = (long)n * kHidden;
-  g1.M = n; g1.N = kHidden; g1.K = c->E; g1.nbatch = 1; g1.splitk = S1;
+  const GemmDesc g1 = gemm_fwd(c->enc, c->E, 0, P + c->o_w1, 0, c->slabs, 1, n, kHidden, c->E, S1);
   RC(gemm_f32_multi(&g1, 1, st));
   LnFwdArgs l1{};
   l1.slabs = c->slabs; l1.S = S1; l1.slab_stride = g1.sCz;
@@ -351,9 +347,7 @@ size_t carve_train(serl_classifier* c, ClsTrain* t, uint8_t* base) {
   const serl_classifier_cfg& g = c->cfg;
   Bump b(base);
   const long n = t->max_batch, nc = g.n_cam;
-  t->m = b.take<float>(c->nt + 1);
-  t->v = b.take<float>(c->nt + 1);
-  t->G = b.take<float>(c->nt);
+  t->opt.carve(b, c->t0, c->nt);
   t->info = b.take<float>(2);
   uint8_t* ws = b.take<uint8_t>(trunk_workspace_bytes((int)(nc * n), g.H, g.W));
   t->feats = b.take<float>((size_t)nc * n * c->HW * 512);
@@ -413,14 +407,8 @@ int train_forward(serl_classifier* c, const uint8_t* frames, int n, const float*
   // classifier head: Dense_0 (K-split) of both instances, then the row kernel
   const int S1 = split_under(n, kHidden, ni, 8);
   GemmDesc g1[2];
-  for (int i = 0; i < ni; ++i) {
-    GemmDesc& d = g1[i];
-    d = GemmDesc{};
-    d.A = t->enc + (long)i * n * c->E; d.sAm = c->E; d.sAk = 1;
-    d.B = P + c->o_w1; d.sBk = kHidden; d.sBn = 1;
-    d.C = t->slabs + (long)i * S1 * n * kHidden; d.ldc = kHidden; d.sCz = (long)n * kHidden;
-    d.M = n; d.N = kHidden; d.K = c->E; d.nbatch = 1; d.splitk = S1;
-  }
+  for (int i = 0; i < ni; ++i)
+    g1[i] = gemm_fwd(t->enc + (long)i * n * c->E, c->E, 0, P + c->o_w1, 0, t->slabs + (long)i * S1 * n * kHidden, 1, n, kHidden, c->E, S1);
   RC(gemm_f32_multi(g1, ni, st));
   ClsHeadArgs h{};
   h.slabs = t->slabs; h.S = S1; h.sstride = (long)n * kHidden; h.istride = (long)S1 * n * kHidden;
@@ -449,14 +437,10 @@ int resolve_moment(serl_classifier* c, const char* section, const char* leaf, fl
   SERL_REQUIRE(section && leaf, "NULL argument");
   const Leaf* l = find(c->leaves, leaf);
   SERL_REQUIRE(l, "unknown classifier leaf '%s'", leaf);
-  const std::string s = section;
-  SERL_REQUIRE(s == "opt/mu" || s == "opt/nu", "unknown classifier section '%s' (opt/mu, opt/nu)", section);
   *count = l->count;
-  *ptr = l->off < c->t0 ? nullptr : (s == "opt/mu" ? c->tr->m : c->tr->v) + (l->off - c->t0);   // nullptr: frozen, always zero
+  SERL_REQUIRE(c->tr->opt.moment(section, *l, ptr), "unknown classifier section '%s' (opt/mu, opt/nu)", section);
   return SERL_OK;
 }
-
-constexpr const char* kFrozenMoment = "'%s' of the frozen leaf '%s' must be zero";
 
 }  // namespace
 
@@ -500,18 +484,14 @@ int serl_classifier_train_step(serl_classifier* c, const uint8_t* dev_frames, in
   hipStream_t st = (hipStream_t)stream;
   SERL_HIP(hipSetDevice(g.device));
   const float* P = c->params;
-  float* G = t->G - c->t0;   // G[o] = gradient of the leaf at arena offset o
+  float* G = t->opt.grad();   // G[o] = gradient of the leaf at arena offset o
   const int nc = g.n_cam;
   const long nD = (long)n * c->D;
   RC(train_forward(c, dev_frames, n, dev_labels, dev_masks, host_mask_keys, true, st));
   hipLaunchKernelGGL(cls_info_kernel, dim3(1), dim3(256), 0, st, t->rowloss, t->rowcorr, n, t->info);
   SERL_HIP(hipGetLastError());
   // d enc = dz W1^T
-  GemmDesc gi{};
-  gi.A = t->dz; gi.sAm = kHidden; gi.sAk = 1;
-  gi.B = P + c->o_w1; gi.sBk = 1; gi.sBn = kHidden;
-  gi.C = t->denc; gi.ldc = c->E; gi.sCz = 0;
-  gi.M = n; gi.N = c->E; gi.K = kHidden; gi.nbatch = 1; gi.splitk = 1;
+  const GemmDesc gi = gemm_igrad(t->dz, kHidden, 0, P + c->o_w1, kHidden, 0, t->denc, c->E, 0, 1, n, c->E, kHidden);
   RC(gemm_f32_multi(&gi, 1, st));
   // camera heads: tanh + LayerNorm backward (all cameras), then d f = dzc W^T per camera
   LnBwdArgs lb{};
@@ -521,11 +501,7 @@ int serl_classifier_train_step(serl_classifier* c, const uint8_t* dev_frames, in
   lb.rows = nc * n; lb.rows_per_group = n;
   lb.dx = t->dzc; lb.dg = t->dgc;
   RC(ln_tanh_bwd(lb, kBottleneck, st));
-  GemmDesc gf{};
-  gf.A = t->dzc; gf.sAm = kBottleneck; gf.sAk = 1; gf.sAb = (long)n * kBottleneck;
-  gf.B = P + c->cam.dW; gf.sBk = 1; gf.sBn = kBottleneck; gf.sBb = c->cam.stride;
-  gf.C = t->df; gf.ldc = c->D; gf.sCz = nD;
-  gf.M = n; gf.N = c->D; gf.K = kBottleneck; gf.nbatch = nc; gf.splitk = 1;
+  const GemmDesc gf = gemm_igrad(t->dzc, kBottleneck, (long)n * kBottleneck, P + c->cam.dW, kBottleneck, c->cam.stride, t->df, c->D, nD, nc, n, c->D, kBottleneck);
   RC(gemm_f32_multi(&gf, 1, st));
   // through the camera Dropout, then the SpatialLearnedEmbeddings kernels' gradient (batch splits summed by the last arriver)
   ClsDropArgs da{};
@@ -545,20 +521,14 @@ int serl_classifier_train_step(serl_classifier* c, const uint8_t* dev_frames, in
       {t->dgc, t->xhat, t->dzc, nc, n, kBottleneck, G + c->cam.lng, G + c->cam.lnb, G + c->cam.db, c->cam.stride, 0},
   };
   RC(colsum3_multi(cs, 4, st));
-  GemmDesc wg[2] = {GemmDesc{}, GemmDesc{}};
-  wg[0].A = t->enc; wg[0].sAm = 1; wg[0].sAk = c->E;                     // dDense_0 = enc^T dz
-  wg[0].B = t->dz; wg[0].sBk = kHidden; wg[0].sBn = 1;
-  wg[0].C = G + c->o_w1; wg[0].ldc = kHidden; wg[0].sCz = 0;
-  wg[0].M = c->E; wg[0].N = kHidden; wg[0].K = n; wg[0].nbatch = 1; wg[0].splitk = 1;
-  wg[1].A = t->f; wg[1].sAm = 1; wg[1].sAk = c->D; wg[1].sAb = nD;      // per camera dDense = f^T dzc
-  wg[1].B = t->dzc; wg[1].sBk = kBottleneck; wg[1].sBn = 1; wg[1].sBb = (long)n * kBottleneck;
-  wg[1].C = G + c->cam.dW; wg[1].ldc = kBottleneck; wg[1].sCz = c->cam.stride;
-  wg[1].M = c->D; wg[1].N = kBottleneck; wg[1].K = n; wg[1].nbatch = nc; wg[1].splitk = 1;
+  const GemmDesc wg[2] = {
+      gemm_wgrad(t->enc, c->E, 0, t->dz, kHidden, 0, G + c->o_w1, kHidden, 0, 1, c->E, kHidden, n),   // dDense_0 = enc^T dz
+      gemm_wgrad(t->f, c->D, nD, t->dzc, kBottleneck, (long)n * kBottleneck, G + c->cam.dW, kBottleneck, c->cam.stride, nc, c->D,
+                 kBottleneck, n),                                                                      // per camera dDense = f^T dzc
+  };
   RC(gemm_f32_multi(wg, 2, st));
   // optax.adam(lr) (reward_classifier.py:62-66) over the trainable slice
-  RC(adam_ema(adam_slice(c->params + c->t0, c->nt, t->G, t->m, t->v, t->lr, t->step + 1), st));
-  t->step += 1;
-  return SERL_OK;
+  return t->opt.apply(c->params, t->lr, st);
 }
 
 int serl_classifier_read_train_info(serl_classifier* c, float out[2], void* stream) {
@@ -572,14 +542,14 @@ int serl_classifier_read_train_info(serl_classifier* c, float out[2], void* stre
 int serl_classifier_train_set_step(serl_classifier* c, int64_t step) {
   RC(check_train(c, 1));
   SERL_REQUIRE(step >= 0, "negative step");
-  c->tr->step = step;
+  c->tr->opt.step = step;
   return SERL_OK;
 }
 
 int serl_classifier_train_get_step(serl_classifier* c, int64_t* step_out) {
   RC(check_train(c, 1));
   SERL_REQUIRE(step_out, "NULL argument");
-  *step_out = c->tr->step;
+  *step_out = c->tr->opt.step;
   return SERL_OK;
 }
 

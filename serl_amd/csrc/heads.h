@@ -141,6 +141,34 @@ inline AdamArgs adam_slice(float* theta, long nt, const float* g, float* m, floa
   a.bc2 = 1.0f - powf(0.999f, (float)step);
   return a;
 }
+// optax.adam(lr) over the trainable slice [t0, t0 + nt) of a parameter vector whose leaves in front of t0 are frozen (BC, the
+// reward classifier): the moments and the gradient of the slice alone, and the update count.  A frozen leaf's moments are zero
+// forever (Adam with g = m = v = 0 leaves a parameter unchanged): not stored, produced on read (leaf_copy).
+constexpr const char* kFrozenMoment = "'%s' of the frozen leaf '%s' must be zero";
+struct AdamSlice {
+  long t0 = 0, nt = 0;
+  float *m = nullptr, *v = nullptr, *G = nullptr;   // [nt + 1], [nt + 1], [nt]
+  int64_t step = 0;
+  void carve(Bump& b, long t0_, long nt_) {
+    t0 = t0_; nt = nt_;
+    m = b.take<float>(nt + 1);
+    v = b.take<float>(nt + 1);
+    G = b.take<float>(nt);
+  }
+  float* grad() const { return G - t0; }   // grad()[o] = gradient of the trainable leaf at arena offset o
+  // section "opt/mu" / "opt/nu" (anything else: false) -> *ptr = that moment of leaf `l`, nullptr for a frozen leaf
+  bool moment(const char* section, const Leaf& l, float** ptr) const {
+    const std::string s = section;
+    if (s != "opt/mu" && s != "opt/nu") return false;
+    *ptr = l.off < t0 ? nullptr : (s == "opt/mu" ? m : v) + (l.off - t0);
+    return true;
+  }
+  int apply(float* params, float lr, hipStream_t stream) {   // one update of params[t0, t0 + nt) from G
+    RC(adam_ema(adam_slice(params + t0, nt, G, m, v, lr, step + 1), stream));
+    step += 1;
+    return SERL_OK;
+  }
+};
 // `steps` target-EMA steps of frozen leaves in one pass (exactly the values `steps` adam_ema launches would have left)
 int frozen_ema(const float* frozen, float* frozen_target, long n, float tau, long steps, hipStream_t stream);
 // out[0] = sum g_critic^2 over [0, nc), out[1] = sum g_actor^2 over [0, na) (deterministic single-block reduction)
@@ -171,6 +199,41 @@ inline CamHeadOffsets add_cam_head_leaves(std::vector<Leaf>& v, long& off, int n
   return o;
 }
 
+// ---- the three GEMM forms of a Dense layer, for `groups` independent (input, kernel) pairs `*_gs` floats apart ------------------
+// Forward Y = X W as `splitk` K-split slabs: X [rows][K] (row stride ldx), W [K][N] row-major; the slab of (group g, split s) is
+// the [rows][N] block g * splitk + s behind `slabs`.
+inline GemmDesc gemm_fwd(const float* X, long ldx, long x_gs, const float* W, long w_gs, float* slabs, int groups, int rows, int N,
+                         int K, int splitk) {
+  GemmDesc g{};
+  g.A = X; g.sAm = ldx; g.sAk = 1; g.sAb = x_gs;
+  g.B = W; g.sBk = N; g.sBn = 1; g.sBb = w_gs;
+  g.C = slabs; g.ldc = N; g.sCz = (long)rows * N;
+  g.M = rows; g.N = N; g.K = K; g.nbatch = groups; g.splitk = splitk;
+  return g;
+}
+// Input gradient dX = dY W^T: dY [rows][Nout] (row stride ldy), W [Kin][Nout] (row stride ldw); block z (= group * splitk + split)
+// of the result lands at out + z * out_zs with row stride ldo.
+inline GemmDesc gemm_igrad(const float* dY, long ldy, long dy_gs, const float* W, long ldw, long w_gs, float* out, long ldo,
+                           long out_zs, int groups, int rows, int Kin, int Nout, int splitk = 1) {
+  GemmDesc g{};
+  g.A = dY; g.sAm = ldy; g.sAk = 1; g.sAb = dy_gs;
+  g.B = W; g.sBk = 1; g.sBn = ldw; g.sBb = w_gs;
+  g.C = out; g.ldc = ldo; g.sCz = out_zs;
+  g.M = rows; g.N = Kin; g.K = Nout; g.nbatch = groups; g.splitk = splitk;
+  return g;
+}
+// Weight gradient dW = X^T dY, written in place: X [rows][Mx] (row stride ldx), dY [rows][Ny] (row stride ldy), group g's
+// [Mx][Ny] result (row stride ldo) at out + g * out_gs.
+inline GemmDesc gemm_wgrad(const float* X, long ldx, long x_gs, const float* dY, long ldy, long dy_gs, float* out, long ldo,
+                           long out_gs, int groups, int Mx, int Ny, int rows) {
+  GemmDesc g{};
+  g.A = X; g.sAm = 1; g.sAk = ldx; g.sAb = x_gs;
+  g.B = dY; g.sBk = ldy; g.sBn = 1; g.sBb = dy_gs;
+  g.C = out; g.ldc = ldo; g.sCz = out_gs;
+  g.M = Mx; g.N = Ny; g.K = rows; g.nbatch = groups; g.splitk = 1;
+  return g;
+}
+
 // The GEMM + LayerNorm launch pair of one instance of the Dense -> LayerNorm -> tanh layer over `cams` cameras.  Camera k reads
 // [rows][K] inputs at f + k * f_cstride, its parameters k * cam_stride floats behind W / bias / gamma / beta, and writes columns
 // k * N.. of y (row stride ld_y).  The GEMM leaves S K-split slabs per camera at `slabs` ([cam][split][rows][N]), which the
@@ -178,11 +241,7 @@ inline CamHeadOffsets add_cam_head_leaves(std::vector<Leaf>& v, long& off, int n
 inline void cam_dense_ln_args(const float* f, long f_cstride, int K, const float* W, const float* bias, const float* gamma,
                               const float* beta, long cam_stride, int cams, int rows, int N, int S, float* slabs, float* y,
                               long ld_y, float* xhat, float* rstd, GemmDesc& g, LnFwdArgs& l) {
-  g = GemmDesc{};
-  g.A = f; g.sAm = K; g.sAk = 1; g.sAb = f_cstride;
-  g.B = W; g.sBk = N; g.sBn = 1; g.sBb = cam_stride;
-  g.C = slabs; g.ldc = N; g.sCz = (long)rows * N;
-  g.M = rows; g.N = N; g.K = K; g.nbatch = cams; g.splitk = S;
+  g = gemm_fwd(f, K, f_cstride, W, cam_stride, slabs, cams, rows, N, K, S);
   l = LnFwdArgs{};
   l.slabs = slabs; l.S = S; l.slab_stride = g.sCz;
   l.bias = bias; l.gamma = gamma; l.beta = beta; l.pstride = cam_stride;

@@ -410,11 +410,8 @@ int small_backward(SmallWorkspace& ws, const float* P, long conv_off, long cam_s
     }
     if (l == 0) break;   // the pixels need no gradient
     {  // dcol_cam = dy_cam x kernel_cam^T  (the ones column has no input below it)
-      GemmDesc g{};
-      g.A = dy; g.sAm = cout; g.sAk = 1; g.sAb = rows_cam * cout;
-      g.B = P + conv_off + small_conv_offset(l); g.sBk = 1; g.sBn = cout; g.sBb = cam_stride;
-      g.C = ws.dcol; g.ldc = pitch; g.sCz = rows_cam * pitch;
-      g.M = (int)rows_cam; g.N = K - 1; g.K = cout; g.nbatch = n_cam; g.splitk = 1;
+      const GemmDesc g = gemm_igrad(dy, cout, rows_cam * cout, P + conv_off + small_conv_offset(l), cout, cam_stride, ws.dcol, pitch,
+                                    rows_cam * pitch, n_cam, (int)rows_cam, K - 1, cout);
       int rc = gemm_f32(g, stream);
       if (rc) return rc;
     }

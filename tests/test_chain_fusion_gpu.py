@@ -1,6 +1,7 @@
 """The last-arriver fusion of the update chain (serl_amd/csrc/heads.hip "last-arriver epilogues"; reference math: agents/continuous/
 sac.py:134-234, common/common.py:136-221, networks/mlp.py:10-32) against the SAME chain with one launch per operation
-(SERL_CHAIN_FUSE=0, the round-3 schedule):
+(SERL_CHAIN_FUSE=0, the round-3 schedule; agent.hip issues both from one body per phase, and DESIGN.md section 4b lists the six
+places where they differ):
 
 * the fused epilogues sum slabs in the order the separate kernels did, so on identical (injected) noise every gradient, loss
   scalar, parameter and Adam moment must agree TO THE BIT -- any visibility bug of the slab hand-off (a stale or torn slab)

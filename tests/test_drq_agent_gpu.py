@@ -352,7 +352,7 @@ def test_draws_inside_the_kernels_equal_the_materialised_draws(gpu, monkeypatch,
     agent.noise_form = "tensors", as tensors filled by one serl_jax_fill launch (bit-exact against the oracle's jax.random in
     tests/test_jaxrng.py).  Same keys, same elements of the same arrays: parameters and info must agree TO THE BIT, for minibatch
     windows of a UTD = 2 update too, on the fused chain and on the one-launch-per-operation chain (which materialises key draws
-    itself: agent.hip jax_noise_tensors)."""
+    itself: agent.hip materialise_noise)."""
     import numpy as np
     import torch
     from serl_amd.utils.launcher import make_drq_agent
