@@ -26,6 +26,7 @@ class SerlAgentCfg(C.Structure):
 
 TX_INDEX = {"actor": 0, "critic": 1, "temperature": 2}   # SERL_TX_*
 NET_BITS = {"critic": 1, "actor": 2, "temperature": 4}   # SERL_NET_*
+APPLY_CRITIC, APPLY_ACTOR_TEMP = NET_BITS["critic"], NET_BITS["actor"] | NET_BITS["temperature"]   # SERL_APPLY_*
 
 
 class SerlBcCfg(C.Structure):

@@ -109,8 +109,7 @@ class BCAgent(Handle):
         self.config = {"image_keys": self.image_keys}
         super().__init__(SerlBcCfg(device, len(self.image_keys), H, W, state_dim, act_dim, max_batch, learning_rate, dropout,
                                    std_min, std_max))
-        # BCAgent.create (bc.py:194-202): rng, init_rng = split(rng); rng, create_rng = split(rng); state.rng = create_rng
-        self._rng_key = J.split(J.split(np.asarray(seed_key, np.uint32))[0])[1]
+        self._rng_key = J.create_rng(seed_key)    # BCAgent.create (bc.py:194-202)
         self._db: Optional[DeviceBatch] = None
         self.state = BCTrainState(self)
 

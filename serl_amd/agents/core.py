@@ -9,9 +9,8 @@ import torch
 
 from .. import _lib
 from .._handle import Handle
-from .._lib_agent import NET_BITS, TX_INDEX, SerlAgentCfg, SerlInfo, SerlNoise
+from .._lib_agent import APPLY_ACTOR_TEMP, APPLY_CRITIC, NET_BITS, TX_INDEX, SerlAgentCfg, SerlInfo, SerlNoise  # noqa: F401
 
-APPLY_CRITIC, APPLY_ACTOR_TEMP = 1, 6   # SERL_NET_CRITIC, SERL_NET_ACTOR | SERL_NET_TEMPERATURE
 TX_NAMES = ("actor", "critic", "temperature")
 
 

@@ -22,6 +22,7 @@ from ..utils import init_ref
 from .. import _lib
 from .. import jaxrng as J
 from .._handle import LazyInfo
+from ..call_noise import CallNoise
 from .batch import DeviceBatch
 from .core import APPLY_ACTOR_TEMP, APPLY_CRITIC, TX_NAMES, AgentCore
 from .flax_tree import export_tree
@@ -139,13 +140,11 @@ class DrQAgent:
         self.rng_impl = "threefry"
         # how the threefry draws reach the kernels: "keys" = the kernels draw them in place from the call's keys (no noise tensors,
         # no extra launch); "tensors" = one serl_jax_fill launch per call materialises them (bit-identical results:
-        # tests/test_drq_agent_gpu.py; the tensors can then be inspected -- agent._noise_bufs)
+        # tests/test_drq_agent_gpu.py; the tensors can then be inspected -- agent._noise_bufs); serl_amd/call_noise.py builds both
         self.noise_form = "keys"
-        # state.rng as create_drq / create leave it (drq.py:69-84, sac.py:355-372): rng = PRNGKey(seed); rng, init_rng = split(rng);
-        # rng, create_rng = split(rng); JaxRLTrainState.create(rng=create_rng)
-        self._rng_key = J.split(J.split(J.prngkey(seed))[0])[1]
+        self._rng_key = J.create_rng(seed)     # state.rng as create_drq / create leave it (drq.py:69-84, sac.py:355-372)
         self.last_draws = {}     # what the last update call drew from its keys (crop offsets, REDQ indices): parity tests read it
-        self._noise_bufs = {}
+        self._call_noise = CallNoise(core, self.image_keys, self.last_draws)
         self._batch: Optional[DeviceBatch] = None
         self._update_serial = 0
         self.state = TrainStateView(self)
@@ -219,7 +218,7 @@ class DrQAgent:
         agent = cls(core, image_keys, config, seed)
         agent._opts = {k: {"warmup_steps": 0, **v} for k, v in opts.items()}
         if param_init == "reference":
-            agent._rng_key = init_ref.create_rng_of(rng)
+            agent._rng_key = J.create_rng(rng)
         return agent
 
     def lr_at(self, count, tx="critic"):
@@ -263,27 +262,7 @@ class DrQAgent:
             co = self._np_rng.integers(0, 9, size=(B, 2)).astype(np.int32)
             cn = self._np_rng.integers(0, 9, size=(B, 2)).astype(np.int32)
             return co, cn
-        k = J.split(self._rng_key if rng is None else rng, 3)
-        return J.crop_offsets(k[1], B, 4), J.crop_offsets(k[2], B, 4)
-
-    def _jax_keys(self, keys, n_cam, want_critic, want_actor):
-        """serl_noise with KEYS only: every draw happens inside the kernel that consumes it (heads.hip: Dropout mask in the
-        SpatialLearnedEmbeddings kernel, normals in the policy-head epilogue); REDQ indices are host integers."""
-        c, noise = self.core.cfg, {}
-        cam_keys = lambda k: np.stack([J.flax_make_rng(k, J.dropout_path(cam), 1) for cam in self.image_keys[:n_cam]])  # noqa: E731
-        if want_critic and keys.n_critic:
-            m = int(c.critic_subsample_size)
-            noise["key_eps_next"] = np.stack(keys.k_next_action)
-            if n_cam:
-                noise["key_mask_next"] = np.stack([cam_keys(k) for k in keys.k_next_action])
-            if m > 0:
-                noise["redq_idx"] = np.stack([J.randint(k, m, 0, c.ensemble) for k in keys.k_subsample]).astype(np.int32)
-                self.last_draws["redq_idx"] = noise["redq_idx"].copy()
-        if want_actor and keys.has_actor_temp:
-            noise["key_eps_pi"], noise["key_eps_temp"] = keys.k_sample, keys.k_temp
-            if n_cam:
-                noise["key_mask_obs_pi"], noise["key_mask_next_temp"] = cam_keys(keys.k_policy), cam_keys(keys.k_temp)
-        return noise
+        return J.crop_pair(self._rng_key if rng is None else rng, B)
 
     # ------------------------------------------------------------------ the reference's random stream for one call
     def _call_keys(self, n_critic, has_actor_temp, drq_aug=None, combined=False):
@@ -292,58 +271,21 @@ class DrQAgent:
             return None
         return J.UpdateKeys(self._rng_key, self._DRQ_AUG if drq_aug is None else drq_aug, n_critic, has_actor_temp, combined)
 
-    def _finish_call(self, keys):
+    @property
+    def _noise_bufs(self):
+        """{batch: the noise tensors of the last call} under noise_form = "tensors" (serl_amd/call_noise.py)"""
+        return self._call_noise.bufs
+
+    def _run_call(self, keys, kind, noise, rows, run, **want):
+        """What every update method ends with: the call's noise -- the injected one, else drawn from the call's keys (None with
+        the device-hashed stream) -- goes to `run`; state.rng then advances as the reference's and the info becomes readable."""
+        if noise is None and keys is not None:
+            noise = self._call_noise.build(keys, rows, self.noise_form, **want)
+        run(noise)
         if keys is not None:
             self._rng_key = keys.rng_out.copy()
-
-    def _jax_noise(self, keys, B, want_critic=True, want_actor=True):
-        """The noise tensors of one call, filled on the device from the call's keys (ONE launch): for critic update i over the
-        minibatch rows [i*mb, (i+1)*mb) the next-action sample and the policy encoder's Dropout masks of sac.py:118-132, the
-        REDQ subsample (host integers, sac.py:150-157); for the actor + temperature update the samples / masks of sac.py:197-201 and
-        :224-227.  Shapes are the reference's ((mb, A) normals, one (mb, 4096) mask per camera from that camera's Dropout key)."""
-        c = self.core.cfg
-        dev, A = self.core.device, c.act_dim
-        n_cam = c.n_cam if c.encoder_type == 0 else 0          # (the SmallEncoder path has no Dropout: pooling "avg")
-        D = 512 * c.sle_features
-        if self.noise_form == "keys":
-            return self._jax_keys(keys, n_cam, want_critic, want_actor)
-        nb = self._noise_bufs.get(B)
-        if nb is None:
-            nb = {k: torch.empty((B, A), dtype=torch.float32, device=dev) for k in ("eps_next", "eps_pi", "eps_temp")}
-            if n_cam:
-                nb.update({k: torch.empty((n_cam, B, D), dtype=torch.uint8, device=dev) for k in ("mask_next", "mask_obs_pi", "mask_next_temp")})
-            self._noise_bufs = {B: nb}
-        keep = 1.0 - float(c.dropout)
-        jobs, noise = [], {}
-
-        def masks(name, key, row0, rows):
-            for ci, cam in enumerate(self.image_keys[:n_cam]):
-                jobs.append(J.job(J.BERNOULLI_U8, J.flax_make_rng(key, J.dropout_path(cam), 1), rows * D,
-                                  nb[name].data_ptr() + (ci * B + row0) * D, p=keep))
-            if n_cam:
-                noise[name] = nb[name]
-
-        if want_critic and keys.n_critic:
-            mb = B // keys.n_critic
-            m = int(c.critic_subsample_size)
-            redq = np.zeros((keys.n_critic, max(m, 1)), np.int32)
-            for i in range(keys.n_critic):
-                jobs.append(J.job(J.NORMAL, keys.k_next_action[i], mb * A, nb["eps_next"].data_ptr() + i * mb * A * 4))
-                masks("mask_next", keys.k_next_action[i], i * mb, mb)
-                if m > 0:
-                    redq[i] = J.randint(keys.k_subsample[i], m, 0, c.ensemble)
-            noise["eps_next"] = nb["eps_next"]
-            if m > 0:
-                noise["redq_idx"] = redq
-                self.last_draws["redq_idx"] = redq.copy()
-        if want_actor and keys.has_actor_temp:
-            jobs.append(J.job(J.NORMAL, keys.k_sample, B * A, nb["eps_pi"].data_ptr()))
-            masks("mask_obs_pi", keys.k_policy, 0, B)
-            jobs.append(J.job(J.NORMAL, keys.k_temp, B * A, nb["eps_temp"].data_ptr()))
-            masks("mask_next_temp", keys.k_temp, 0, B)
-            noise["eps_pi"], noise["eps_temp"] = nb["eps_pi"], nb["eps_temp"]
-        J.fill(c.device, jobs, self.core._stream())
-        return noise
+        self._update_serial += 1
+        return self, PendingInfo(self, kind, self._update_serial)
 
     def prepare(self, batch, crops=None) -> DeviceBatch:
         """sample-gather [+ concat_batches] + _unpack + random-shift crop -> DeviceBatch."""
@@ -476,21 +418,17 @@ class DrQAgent:
         keys = self._call_keys(1, False)
         if self._can_prefetch(batch, crops):
             slot, db = self._acquire(batch, None if keys is None else keys.rng_out)
-            if noise is None and keys is not None:
-                noise = self._jax_noise(keys, db.batch)
-            self.core.begin_update()
-            self.core.critic_grads(0, db.batch, db.batch, noise)
-            self.core.apply(APPLY_CRITIC)
-            self._sched.consumed(slot)
+
+            def run(noise):
+                self.core.begin_update()
+                self.core.critic_grads(0, db.batch, db.batch, noise)
+                self.core.apply(APPLY_CRITIC)
+                self._sched.consumed(slot)
         else:
             db = self.prepare(batch, crops)
             self._sync_side_stream()
-            if noise is None and keys is not None:
-                noise = self._jax_noise(keys, db.batch)
-            self.core.update_critics(db, noise)
-        self._finish_call(keys)
-        self._update_serial += 1
-        return self, PendingInfo(self, "critics", self._update_serial)
+            run = lambda noise: self.core.update_critics(db, noise)  # noqa: E731
+        return self._run_call(keys, "critics", noise, db.batch, run)
 
     def update_high_utd(self, batch, *, utd_ratio: int, pmap_axis: Optional[str] = None, noise=None, crops=None):
         """drq.py:255-294 -> sac.py:544-596."""
@@ -499,27 +437,23 @@ class DrQAgent:
             B = batch.batch_size
             assert B % utd_ratio == 0, f"Batch size {B} must be divisible by UTD ratio {utd_ratio}"  # sac.py:561-563
             slot, db = self._acquire(batch, None if keys is None else keys.rng_out)
-            if noise is None and keys is not None:
-                noise = self._jax_noise(keys, B)
-            mb = B // utd_ratio
-            self.core.begin_update()
-            for i in range(utd_ratio):
-                self.core.critic_grads(i * mb, mb, mb, noise, i)
-                self.core.apply(APPLY_CRITIC, 1.0 / utd_ratio)
-            self.core.actor_grads(B, noise)
-            self.core.apply(APPLY_ACTOR_TEMP)
-            self._sched.consumed(slot)
+
+            def run(noise):
+                mb = B // utd_ratio
+                self.core.begin_update()
+                for i in range(utd_ratio):
+                    self.core.critic_grads(i * mb, mb, mb, noise, i)
+                    self.core.apply(APPLY_CRITIC, 1.0 / utd_ratio)
+                self.core.actor_grads(B, noise)
+                self.core.apply(APPLY_ACTOR_TEMP)
+                self._sched.consumed(slot)
         else:
             db = self.prepare(batch, crops)
             assert db.batch % utd_ratio == 0, \
                 f"Batch size {db.batch} must be divisible by UTD ratio {utd_ratio}"  # sac.py:561-563
             self._sync_side_stream()
-            if noise is None and keys is not None:
-                noise = self._jax_noise(keys, db.batch)
-            self.core.update_high_utd(db, utd_ratio, noise)
-        self._finish_call(keys)
-        self._update_serial += 1
-        return self, PendingInfo(self, "high_utd", self._update_serial)
+            run = lambda noise: self.core.update_high_utd(db, utd_ratio, noise)  # noqa: E731
+        return self._run_call(keys, "high_utd", noise, db.batch, run)
 
     def update(self, batch, *, pmap_axis: str = None,
                networks_to_update: FrozenSet[str] = frozenset({"actor", "critic", "temperature"}), noise=None):
@@ -539,12 +473,8 @@ class DrQAgent:
         nets = set(networks_to_update)
         crit, act = "critic" in nets, bool(nets & {"actor", "temperature"})
         keys = self._call_keys(1 if crit else 0, act, drq_aug=False, combined=crit and act)
-        if noise is None and keys is not None:
-            noise = self._jax_noise(keys, db.batch, want_critic=crit, want_actor=act)
-        self.core.update(db, tuple(networks_to_update), noise)
-        self._finish_call(keys)
-        self._update_serial += 1
-        return self, PendingInfo(self, frozenset(networks_to_update), self._update_serial)
+        return self._run_call(keys, frozenset(networks_to_update), noise, db.batch,
+                              lambda noise: self.core.update(db, tuple(networks_to_update), noise), want_critic=crit, want_actor=act)
 
     # ------------------------------------------------------------------ acting
     def sample_actions(self, observations, *, seed=None, argmax: bool = False, **kwargs):

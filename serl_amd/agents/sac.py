@@ -16,6 +16,7 @@ import torch
 from ..data.data_store import LazyBatch, gather_crop
 from ..utils import init as pinit
 from ..utils import init_ref
+from .. import jaxrng as J
 from .batch import DeviceBatch
 from .core import AgentCore
 from .drq import DrQAgent
@@ -70,7 +71,7 @@ class SACAgent(DrQAgent):
         agent = cls(core, (), config, seed)
         agent._opts = {"actor": ao, "critic": co, "temperature": {"warmup_steps": 0, **to}}
         if param_init == "reference":
-            agent._rng_key = init_ref.create_rng_of(rng)
+            agent._rng_key = J.create_rng(rng)
         return agent
 
     # ------------------------------------------------------------------ batches (flat observations, no augmentation)

@@ -98,6 +98,20 @@ def crop_offsets(key, frames: int, padding: int = 4) -> np.ndarray:
     return out
 
 
+def create_rng(seed_or_key) -> np.ndarray:
+    """state.rng as the reference's create paths leave it (drq.py:69-84, sac.py:355-372, bc.py:194-202), from an int seed
+    (PRNGKey(seed)) or a key: rng, init_rng = split(rng); rng, create_rng = split(rng); TrainState.create(rng=create_rng)"""
+    key = prngkey(int(seed_or_key)) if np.ndim(seed_or_key) == 0 else _key(seed_or_key)
+    return split(split(key)[0])[1]
+
+
+def crop_pair(rng, frames: int):
+    """(crop_obs, crop_next) of a DrQ call that enters with state.rng = `rng`: rng, obs_rng, next_obs_rng = split(rng, 3)
+    (drq.py:276-281,307-308), one batched_random_crop draw each (padding 4)"""
+    k = split(rng, 3)
+    return crop_offsets(k[1], frames, 4), crop_offsets(k[2], frames, 4)
+
+
 class UpdateKeys:
     """Every key one learner call derives from state.rng (serl_jax_update_keys; order documented in the header)."""
 

@@ -26,7 +26,9 @@ from typing import List, Sequence, Tuple
 
 import numpy as np
 
-APPLY_CRITIC, APPLY_ACTOR_TEMP = 1, 6   # SERL_NET_CRITIC, SERL_NET_ACTOR | SERL_NET_TEMPERATURE
+from . import jaxrng as J
+from ._lib_agent import APPLY_ACTOR_TEMP, APPLY_CRITIC  # noqa: F401
+from .call_noise import CallNoise
 
 
 def shard_parts(parts: Sequence[Tuple[object, np.ndarray]], rank: int, world: int):
@@ -170,17 +172,14 @@ class DataParallelLearner:
         self.all_reduce = all_reduce
         self.ensemble = ensemble
         self.sched = schedule or SerialSchedule()
-        # the reference's random stream, identical on all ranks (same seed): state.rng as create_drq leaves it (drq.py:69-84)
-        from . import jaxrng as J
-        self._J = J
-        self._rng = J.split(J.split(J.prngkey(seed))[0])[1]
+        self._rng = J.create_rng(seed)   # the reference's random stream, identical on all ranks (same seed)
         self._keys = None            # keys of the call in progress
         self.image_keys = tuple(image_keys) if image_keys is not None else None
         assert device_noise in ("hash", "threefry")
         self.device_noise = device_noise if (self.image_keys is not None and hasattr(core, "cfg")) else "hash"
-        self._nbuf = None
         self.noise_form = "keys"     # "keys": drawn inside the consuming kernels; "tensors": one serl_jax_fill launch per update
         self.last_draws = {}
+        self._call_noise = CallNoise(core, self.image_keys, self.last_draws, ensemble)
         self._gv = {}
         self._pending = None   # slot of the prefetched (sampled + gathered + encoded) batch
         self.force_reduce = False   # diagnostic: issue the collectives even with one rank
@@ -211,10 +210,10 @@ class DataParallelLearner:
         if self.world > 1 or self.force_reduce:
             self.all_reduce(self._view(which))
 
-    def _produce(self, rng):
-        """Sample one global batch (identical index/crop streams on all ranks), materialise this rank's
-        slice and run the frozen trunk on it -- on the side stream when pipelining.  `rng`: state.rng at the entry of the call
-        that will consume this batch (rng, obs_rng, next_obs_rng = split(rng, 3), drq.py:276-277,307-308)."""
+    def _sample(self, rng, crops=True):
+        """-> (slot, parts, crop_obs, crop_next): the next pipeline slot, one global batch's indices (identical index / crop
+        streams on all ranks) and, unless crops is False, its crop offsets.  `rng`: state.rng at the entry of the call that
+        will consume this batch (rng, obs_rng, next_obs_rng = split(rng, 3), drq.py:276-277,307-308)."""
         slot = self._next_slot
         self._next_slot = (slot + 1) % self.sched.slots
         # replicated stores (serl_amd/data/replicated.py): every rank applies the same actor transitions here, i.e. at
@@ -223,9 +222,16 @@ class DataParallelLearner:
             if hasattr(buf, "step_barrier"):
                 buf.step_barrier()
         parts = [(b, b.sample_indices(n)) for b, n in zip(self.buffers, self.batch_sizes)]
-        k3 = self._J.split(rng, 3)
-        co, cn = self._J.crop_offsets(k3[1], self.B, 4), self._J.crop_offsets(k3[2], self.B, 4)
+        if not crops:
+            return slot, parts, None, None
+        co, cn = J.crop_pair(rng, self.B)
         self.last_draws["crops"] = (co, cn)
+        return slot, parts, co, cn
+
+    def _produce(self, rng):
+        """Sample one global batch, materialise this rank's slice and run the frozen trunk on it -- on the side stream when
+        pipelining."""
+        slot, parts, co, cn = self._sample(rng)
         local, (lo, hi) = shard_parts(parts, self.rank, self.world)
         self.sched.wait_consumed(slot)
         split = getattr(self.sched, "update_after_stage", None)
@@ -253,54 +259,8 @@ class DataParallelLearner:
 
     def _noise(self, critic: bool):
         """this rank's rows of the call's jax.random draws (device_noise = "threefry"), REDQ indices always"""
-        J, keys = self._J, self._keys
-        noise = {}
-        if critic:
-            noise["redq_idx"] = J.randint(keys.k_subsample[0], 2, 0, self.ensemble).reshape(1, 2)
-            self.last_draws["redq_idx"] = noise["redq_idx"]
-        if self.device_noise != "threefry":
-            return noise if critic else None
-        if self.noise_form == "keys":      # the kernels draw this rank's rows of the global arrays themselves (serl_agent_set_shard)
-            c = self.core.cfg
-            n_cam = c.n_cam if c.encoder_type == 0 else 0
-            cam = lambda k: np.stack([J.flax_make_rng(k, J.dropout_path(x), 1) for x in self.image_keys[:n_cam]])  # noqa: E731
-            if critic:
-                noise["key_eps_next"] = keys.k_next_action[0]
-                if n_cam:
-                    noise["key_mask_next"] = cam(keys.k_next_action[0])
-            else:
-                noise["key_eps_pi"], noise["key_eps_temp"] = keys.k_sample, keys.k_temp
-                if n_cam:
-                    noise["key_mask_obs_pi"], noise["key_mask_next_temp"] = cam(keys.k_policy), cam(keys.k_temp)
-            return noise
-        import torch
-        c = self.core.cfg
-        A, D, Bl, B, lo = c.act_dim, 512 * c.sle_features, self.Bl, self.B, self.rank * self.Bl
-        n_cam = c.n_cam if c.encoder_type == 0 else 0
-        if self._nbuf is None:
-            dev = self.core.device
-            self._nbuf = {k: torch.empty((Bl, A), dtype=torch.float32, device=dev) for k in ("eps_next", "eps_pi", "eps_temp")}
-            if n_cam:
-                self._nbuf.update({k: torch.empty((n_cam, Bl, D), dtype=torch.uint8, device=dev)
-                                   for k in ("mask_next", "mask_obs_pi", "mask_next_temp")})
-        nb, jobs, keep = self._nbuf, [], 1.0 - float(c.dropout)
-
-        def draws(eps_name, eps_key, mask_name, mask_key):
-            jobs.append(J.job(J.NORMAL, eps_key, B * A, nb[eps_name].data_ptr(), first=lo * A, count=Bl * A))
-            noise[eps_name] = nb[eps_name]
-            for ci, cam in enumerate(self.image_keys[:n_cam]):
-                jobs.append(J.job(J.BERNOULLI_U8, J.flax_make_rng(mask_key, J.dropout_path(cam), 1), B * D,
-                                  nb[mask_name].data_ptr() + ci * Bl * D, first=lo * D, count=Bl * D, p=keep))
-            if n_cam:
-                noise[mask_name] = nb[mask_name]
-
-        if critic:
-            draws("eps_next", keys.k_next_action[0], "mask_next", keys.k_next_action[0])
-        else:
-            draws("eps_pi", keys.k_sample, "mask_obs_pi", keys.k_policy)
-            draws("eps_temp", keys.k_temp, "mask_next_temp", keys.k_temp)
-        J.fill(c.device, jobs, self.core._stream())
-        return noise
+        return self._call_noise.build(self._keys, self.Bl, self.noise_form, want_critic=critic, want_actor=not critic,
+                                      shard=(self.rank * self.Bl, self.B), device_draws=self.device_noise == "threefry")
 
     def _critic(self):
         noise = self._noise(True)
@@ -333,7 +293,7 @@ class DataParallelLearner:
 
     def update_critics(self):
         """DrQAgent.update_critics over the global batch (one grad-step)."""
-        self._keys = self._J.UpdateKeys(self._rng, True, 1, False)
+        self._keys = J.UpdateKeys(self._rng, True, 1, False)
         with self.sched.main():
             slot = self._acquire()
             self._critic()
@@ -342,7 +302,7 @@ class DataParallelLearner:
 
     def update_high_utd(self):
         """DrQAgent.update_high_utd(utd_ratio=1): critic step, then actor+temperature on the same batch."""
-        self._keys = self._J.UpdateKeys(self._rng, True, 1, True)
+        self._keys = J.UpdateKeys(self._rng, True, 1, True)
         with self.sched.main():
             slot = self._acquire()
             self._critic()
@@ -403,19 +363,12 @@ class TrunkFarmLearner(DataParallelLearner):
 
     # every rank walks the same sequence of batches; what it does with batch t depends on its role
     def _produce(self, rng):
-        slot = self._next_slot
-        self._next_slot = (slot + 1) % self.sched.slots
         t = self._t
         self._t += 1
-        for buf in self.buffers:
-            if hasattr(buf, "step_barrier"):
-                buf.step_barrier()
-        parts = [(b, b.sample_indices(n)) for b, n in zip(self.buffers, self.batch_sizes)]     # (keeps every rank's index stream in step)
-        k3 = self._J.split(rng, 3)
-        if self.role == "worker" and self.owner(t) != self.farm_rank and self.farm_world > 1:
+        mine = not (self.role == "worker" and self.owner(t) != self.farm_rank and self.farm_world > 1)
+        slot, parts, co, cn = self._sample(rng, crops=mine)     # (the indices are drawn either way: every rank's stream stays in step)
+        if not mine:
             return slot                                                       # another worker's batch
-        co, cn = self._J.crop_offsets(k3[1], self.B, 4), self._J.crop_offsets(k3[2], self.B, 4)
-        self.last_draws["crops"] = (co, cn)
         self.sched.wait_consumed(slot)
         with self.sched.side():
             db = self.sched.gathered(slot, lambda: self.gather(parts, co, cn, slot))
@@ -446,7 +399,7 @@ class TrunkFarmLearner(DataParallelLearner):
 
     def _worker_step(self, has_actor):
         """a worker's share of one learner call: the key bookkeeping of the call and, if it owns the batch, its pass"""
-        self._keys = self._J.UpdateKeys(self._rng, True, 1, has_actor)
+        self._keys = J.UpdateKeys(self._rng, True, 1, has_actor)
         slot = self._pending if self._pending is not None else self._produce(self._keys.rng_in)
         self._pending = None
         if self.sched.slots > 1:

@@ -191,9 +191,7 @@ def init_rng_of(rng) -> np.ndarray:
     return J.split(rng)[1]
 
 
-def create_rng_of(rng) -> np.ndarray:
-    """state.rng the create paths leave: rng, init_rng = split(rng); rng, create_rng = split(rng) -> create_rng"""
-    return J.split(J.split(reference_key(rng))[0])[1]
+create_rng_of = J.create_rng       # state.rng the create paths leave, from an int seed or a key
 
 
 def reference_key(rng) -> np.ndarray:

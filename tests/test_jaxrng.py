@@ -99,6 +99,19 @@ def test_crop_offsets_follow_batched_random_crop():
         assert got.min() >= 0 and got.max() <= 8
 
 
+def test_create_rng_and_crop_pair_are_the_chains_they_name():
+    """state.rng after create (rng, init_rng = split(rng); rng, create_rng = split(rng)) and the crop keys of a DrQ call
+    (rng, obs_rng, next_obs_rng = split(rng, 3)), shared by the agents and the learners"""
+    for seed in (0, 3, 2**31 + 7):
+        rng = J.split(J.split(J.prngkey(seed))[0])[1]
+        assert np.array_equal(J.create_rng(seed), rng)
+        assert np.array_equal(J.create_rng(J.prngkey(seed)), rng)                   # a key is taken as it is
+        co, cn = J.crop_pair(rng, 7)
+        k = J.split(rng, 3)
+        assert np.array_equal(co, J.crop_offsets(k[1], 7, 4)) and np.array_equal(cn, J.crop_offsets(k[2], 7, 4))
+        assert co.shape == cn.shape == (7, 2) and not np.array_equal(co, cn)
+
+
 def test_host_normals_are_within_a_few_ulps_of_the_oracle():
     k = T.PRNGKey(7)
     for n in (1, 6, 1537):
