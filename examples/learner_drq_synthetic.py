@@ -9,6 +9,10 @@ client.update / request / recv_network_callback); real ZeroMQ is used when pyzmq
 Only the import lines differ from the reference script: make_drq_agent / make_replay_buffer / concat_batches come
 from serl_amd, `lazy=True` lets gather + concat + unpack + random-shift crop fuse into the update, and checkpoints
 go through serl_amd.utils.checkpoint (flax's file layout).
+
+Stopping and continuing:  --run_dir DIR --save_every N  saves the run state (the agent's checkpoint, state.rng included, plus a
+snapshot of both replay stores) every N steps; the same command with  --resume  continues from the latest one: the demo store
+is not filled again and the online store already holds what the actor had sent.
 """
 import argparse
 import itertools
@@ -21,7 +25,7 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from serl_amd.transport import QueuedDataStore, TrainerClient, TrainerServer, make_trainer_config  # noqa: E402
-from serl_amd.utils.checkpoint import save_checkpoint  # noqa: E402
+from serl_amd.utils.checkpoint import restore_run, save_checkpoint, save_run  # noqa: E402
 from serl_amd.utils.launcher import make_drq_agent, make_replay_buffer  # noqa: E402
 from serl_amd.utils.synthetic import transition_stream  # noqa: E402
 from serl_amd.utils.train_utils import concat_batches  # noqa: E402
@@ -51,7 +55,11 @@ def main():
     ap.add_argument("--log_period", type=int, default=20)
     ap.add_argument("--steps_per_update", type=int, default=30)      # async_drq_sim.py:60
     ap.add_argument("--port", type=int, default=5488)
+    ap.add_argument("--run_dir", default=None, help="directory of the run state (save_run / restore_run)")
+    ap.add_argument("--save_every", type=int, default=0, help="save the run state every N steps (needs --run_dir)")
+    ap.add_argument("--resume", action="store_true", help="continue from the latest run state in --run_dir")
     a = ap.parse_args()
+    assert a.run_dir or not (a.save_every or a.resume), "--save_every / --resume need --run_dir"
 
     env = _Env()
     agent = make_drq_agent(seed=42, sample_obs={"front": np.zeros((1, H, W, 3), np.uint8), "wrist": np.zeros((1, H, W, 3), np.uint8),
@@ -60,8 +68,13 @@ def main():
                            batch_size=a.batch_size)
     replay_buffer = make_replay_buffer(env, capacity=200000, type="memory_efficient_replay_buffer", image_keys=KEYS)
     demo_buffer = make_replay_buffer(env, capacity=10000, type="memory_efficient_replay_buffer", image_keys=KEYS)
-    for tr in itertools.islice(transition_stream(KEYS, H, W, 3, 1, S, A, 100, 99), 2000):   # 20 demo trajectories
-        demo_buffer.insert(tr)
+    stores, update_steps = {"replay": replay_buffer, "demo": demo_buffer}, 0
+    if a.resume:
+        update_steps = restore_run(a.run_dir, agent, stores)
+        print(f"resumed at {update_steps} grad-steps: replay size {len(replay_buffer)}, demo size {len(demo_buffer)}", flush=True)
+    else:
+        for tr in itertools.islice(transition_stream(KEYS, H, W, 3, 1, S, A, 100, 99), 2000):   # 20 demo trajectories
+            demo_buffer.insert(tr)
 
     # ---- learner endpoint (async_drq_sim.py:202-212)
     stats_log = []
@@ -103,7 +116,7 @@ def main():
 
     half = {"batch_size": a.batch_size // 2, "pack_obs_and_next_obs": True, "lazy": True}
     replay_iterator, demo_iterator = replay_buffer.get_iterator(sample_args=half), demo_buffer.get_iterator(sample_args=half)
-    t0, update_steps = time.time(), 0
+    t0, steps_before = time.time(), update_steps
     for step in range(a.steps):
         for _ in range(a.critic_actor_ratio - 1):                        # async_drq_sim.py:266-281
             batch = concat_batches(next(replay_iterator), next(demo_iterator), axis=0)
@@ -118,9 +131,11 @@ def main():
             info = update_info.resolve()                                 # synchronises; the reference logs to wandb here
             print(f"step {step:5d} updates {update_steps:6d} critic_loss {info['critic']['critic_loss']:.4f} "
                   f"actor_loss {info['actor']['actor_loss']:.4f} temperature {info['actor']['temperature']:.4f} "
-                  f"{update_steps / (time.time() - t0):.1f} grad-steps/s", flush=True)
+                  f"{(update_steps - steps_before) / (time.time() - t0):.1f} grad-steps/s", flush=True)
         if a.checkpoint_path and a.checkpoint_period and step and step % a.checkpoint_period == 0:
             save_checkpoint(a.checkpoint_path, agent, step=update_steps, keep=20)   # :303-307
+        if a.save_every and step and step % a.save_every == 0:
+            save_run(a.run_dir, agent, stores, step=update_steps, keep=2)
     stop_actor.set()
     actor_thread.join(timeout=10)
     time.sleep(0.2)

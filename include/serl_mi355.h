@@ -81,6 +81,45 @@ int serl_rb_insert(serl_rb* rb, const uint8_t* const* obs_frames,
 int64_t serl_rb_len(serl_rb* rb);          /* ReplayBuffer.__len__ (replay_buffer.py:68-69) */
 int64_t serl_rb_insert_index(serl_rb* rb); /* latest_data_id (data_store.py:138-140) */
 int serl_rb_valid_mask(serl_rb* rb, uint8_t* host_out /* [capacity] */);
+/* Slot writes ever made: every ReplayBuffer.insert of the reference (replay_buffer.py:71-75), i.e. each time the write head
+ * advances -- a transition's own slot, an episode's first-frame slots and the wrap re-inserts all count.  insert_index ==
+ * count % capacity, and unlike insert_index it never wraps, so "the slots written since count c" is the ring range
+ * [c % capacity, count % capacity) as long as count - c < capacity. */
+int64_t serl_rb_insert_count(serl_rb* rb);
+
+/* ---- Snapshot of a store (run resume).  Everything in a store that is state rather than workspace: the geometry, the ring
+ * bookkeeping, the sampler's PCG64, the valid mask, and the frames and records of the slots. */
+typedef struct serl_rb_meta {
+  int64_t capacity;
+  int32_t n_cam, H, W, C, T, S, A, rec_len;  /* rec_len = 2*T*S + A + 3 floats per record */
+  int64_t size, insert_index, insert_count;
+  int32_t first;                             /* the next insert opens an episode (writes first-frame slots) */
+  int32_t rng_seeded;
+  uint64_t rng_state_inc[4];                 /* as serl_rb_rng_state */
+  int32_t rng_has_uint32;
+  uint32_t rng_uinteger;
+} serl_rb_meta;
+/* One consistent reading of all of the above (under the store's mutex: never between the slot writes of one insert). */
+int serl_rb_export_meta(serl_rb* rb, serl_rb_meta* out);
+/* Copies the n_slots slots slot_begin, slot_begin + 1, ... (mod capacity: the range may run over the end of the ring) to host
+ * memory, in that order: host_frames[c] u8[n_slots][H*W*C] per camera (NULL for a store without cameras), host_records
+ * f32[n_slots][rec_len], and -- when host_valid is not NULL -- the WHOLE valid mask u8[capacity]: an insert changes the mask of
+ * slots other than the one it writes (look-ahead invalidation, first-frame slots, the wrap re-insert), so a saver may keep
+ * frames incrementally but must rewrite the mask whole.  0 <= slot_begin < capacity, 0 <= n_slots <= capacity.
+ * Ordering: the call first waits for the copies of the last insert, then reads device memory in chunks through pinned staging
+ * on the store's copy stream.  While it runs, inserts into the store (and other exports / imports) WAIT -- every insert is
+ * either wholly in the result or not at all; index draws and gathers on any stream proceed (they only read). */
+int serl_rb_export_slots(serl_rb* rb, int64_t slot_begin, int64_t n_slots, uint8_t* const* host_frames,
+                         float* host_records, uint8_t* host_valid);
+/* The inverse.  serl_rb_import_meta sets the bookkeeping and the generator; the geometry in `meta` (capacity, n_cam, H, W, C, T,
+ * S, A, rec_len) must be the store's own, and size / insert_index / insert_count consistent with it, else SERL_ERR_INVALID and
+ * the store is untouched.  serl_rb_import_slots writes a slot range (same layout and limits as the export; host_valid, when not
+ * NULL, replaces the whole mask) host -> HBM in chunks through pinned staging, after the gathers in flight that may read those
+ * slots, and refreshes the host mirror of the records that the wrap re-insert reads.  It holds the store's mutex throughout and
+ * returns when the copies have completed: nothing else touches the store meanwhile. */
+int serl_rb_import_meta(serl_rb* rb, const serl_rb_meta* meta);
+int serl_rb_import_slots(serl_rb* rb, int64_t slot_begin, int64_t n_slots, const uint8_t* const* host_frames,
+                         const float* host_records, const uint8_t* host_valid);
 
 /* index draw + rejection loop (memory_efficient_replay_buffer.py:111-122): bit-exact with
  * numpy Generator(PCG64).integers.  host_idx_out: int64[batch]. */

@@ -29,6 +29,18 @@ class SerlBatch(C.Structure):
     ]
 
 
+class SerlRbMeta(C.Structure):   # serl_rb_meta
+    _fields_ = [
+        ("capacity", C.c_int64),
+        ("n_cam", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("C", C.c_int32), ("T", C.c_int32), ("S", C.c_int32),
+        ("A", C.c_int32), ("rec_len", C.c_int32),
+        ("size", C.c_int64), ("insert_index", C.c_int64), ("insert_count", C.c_int64),
+        ("first", C.c_int32), ("rng_seeded", C.c_int32),
+        ("rng_state_inc", C.c_uint64 * 4),
+        ("rng_has_uint32", C.c_int32), ("rng_uinteger", C.c_uint32),
+    ]
+
+
 vp, i32, i64, u64, u32, f32, P = C.c_void_p, C.c_int, C.c_int64, C.c_uint64, C.c_uint32, C.c_float, C.POINTER
 
 # function -> argtypes; every function returns an int status unless RESTYPES says otherwise.  The agent, BC and classifier
@@ -45,6 +57,12 @@ SIGNATURES = {
     "serl_rb_len": [vp],
     "serl_rb_insert_index": [vp],
     "serl_rb_valid_mask": [vp, vp],
+    "serl_rb_insert_count": [vp],
+    # snapshot of a store (run resume; serl_amd/data/data_store.py save_snapshot / restore_snapshot)
+    "serl_rb_export_meta": [vp, P(SerlRbMeta)],
+    "serl_rb_export_slots": [vp, i64, i64, P(vp), vp, vp],
+    "serl_rb_import_meta": [vp, P(SerlRbMeta)],
+    "serl_rb_import_slots": [vp, i64, i64, P(vp), vp, vp],
     "serl_rb_sample_indices": [vp, i32, vp],
     "serl_rb_gather_packed": [vp, vp, i32, P(vp), vp, vp, vp, vp, vp, vp, vp],
     "serl_rb_gather_crop": [P(vp), i32, P(vp), P(i32), vp, vp, P(SerlBatch), vp],
@@ -65,7 +83,7 @@ SIGNATURES = {
     "serl_jax_init_fill": [i32, vp, i32, vp],
     "serl_jax_init_host": [vp],
 }
-RESTYPES = {"serl_last_error": C.c_char_p, "serl_rb_len": i64, "serl_rb_insert_index": i64}
+RESTYPES = {"serl_last_error": C.c_char_p, "serl_rb_len": i64, "serl_rb_insert_index": i64, "serl_rb_insert_count": i64}
 
 _lib = None
 

@@ -6,6 +6,7 @@
 // Device side: one fused kernel = sample gather + concat_batches + _unpack + DrQ random shift
 // (K2+K3+K4).  It is HBM-bound u8 traffic: every source frame row is pulled once with 16-byte
 // coalesced loads into LDS, shifted/clamped out of LDS, and written once with 16-byte stores.
+#include <condition_variable>
 #include <cstring>
 #include <mutex>
 #include <vector>
@@ -70,6 +71,7 @@ struct Pcg64 {
 constexpr int kRing = 8;           // staging slots for per-call index/crop parameters
 constexpr int kInsRing = 32;       // pinned staging slots for inserted transitions (one slot write each)
 constexpr int kRowsPerBlock = 32;  // output rows per workgroup in the gather/crop kernel
+constexpr size_t kXferChunk = (size_t)8 << 20;  // bytes per pinned staging buffer of the snapshot export / import (two of them)
 
 }  // namespace serl
 
@@ -85,9 +87,16 @@ struct serl_rb {
   std::vector<uint8_t> valid;
   std::vector<float> rec_host;  // host mirror of the records (needed for the wrap re-insert)
   int64_t size = 0, insert_index = 0;
+  int64_t insert_count = 0;  // slot writes ever made (insert_index == insert_count % cap)
   bool first = true;
   serl::Pcg64 rng;
   std::mutex mu;
+  // snapshot export (serl_rb_export_slots): while `busy`, inserts and other exports / imports wait on `idle` with the mutex
+  // released -- index draws and gathers only take the mutex and go on.  The two pinned staging buffers are made at the first use.
+  std::condition_variable idle;
+  bool busy = false;
+  uint8_t* xfer_host = nullptr;
+  hipEvent_t xfer_done[2] = {nullptr, nullptr};
   // stream/event plumbing
   hipStream_t copy_stream = nullptr;
   // one "last gather" event per stream that gathers from this buffer (the learner's update stream, its prefetch side
@@ -454,6 +463,7 @@ static int write_slot(serl_rb* rb, int64_t i, const uint8_t* const* frames_host,
   SERL_HIP(hipEventRecord(rb->ins_done[s], rb->copy_stream));
   rb->ins_used[s] = true;
   rb->insert_index = (i + 1) % rb->cap;
+  rb->insert_count += 1;
   rb->size = rb->size + 1 < rb->cap ? rb->size + 1 : rb->cap;
   return SERL_OK;
 }
@@ -471,6 +481,7 @@ static int copy_slot_to_head(serl_rb* rb, int64_t src) {
                             rb->frames[c] + (size_t)src * rb->frame_bytes, rb->frame_bytes,
                             hipMemcpyDeviceToDevice, rb->copy_stream));
   rb->insert_index = (i + 1) % rb->cap;
+  rb->insert_count += 1;
   rb->size = rb->size + 1 < rb->cap ? rb->size + 1 : rb->cap;
   return SERL_OK;
 }
@@ -507,6 +518,82 @@ static int stage_params(serl_rb* rb, const void* const* srcs, const size_t* size
   *dev_out = d;
   rb->stage_used[s] = true;
   return s;
+}
+
+
+// ---------------------------------------------------------------------------------------------
+// snapshot export / import: HBM <-> ordinary host memory in chunks through two pinned buffers on the copy stream
+// ---------------------------------------------------------------------------------------------
+static int xfer_init(serl_rb* rb) {
+  if (!rb->xfer_host) SERL_HIP(hipHostMalloc((void**)&rb->xfer_host, 2 * kXferChunk, hipHostMallocDefault));
+  for (int k = 0; k < 2; ++k)
+    if (!rb->xfer_done[k]) SERL_HIP(hipEventCreateWithFlags(&rb->xfer_done[k], hipEventDisableTiming));
+  return SERL_OK;
+}
+// Chunk i goes through buffer i & 1; chunk i + 1 is in flight while chunk i is copied out of its buffer.
+static int staged_d2h(serl_rb* rb, uint8_t* dst, const uint8_t* dev_src, size_t bytes) {
+  const size_t n = (bytes + kXferChunk - 1) / kXferChunk;
+  for (size_t i = 0; i <= n; ++i) {
+    if (i < n) {
+      const size_t off = i * kXferChunk, len = bytes - off < kXferChunk ? bytes - off : kXferChunk;
+      SERL_HIP(hipMemcpyAsync(rb->xfer_host + (i & 1) * kXferChunk, dev_src + off, len, hipMemcpyDeviceToHost, rb->copy_stream));
+      SERL_HIP(hipEventRecord(rb->xfer_done[i & 1], rb->copy_stream));
+    }
+    if (i >= 1) {
+      const size_t off = (i - 1) * kXferChunk, len = bytes - off < kXferChunk ? bytes - off : kXferChunk;
+      SERL_HIP(hipEventSynchronize(rb->xfer_done[(i - 1) & 1]));
+      std::memcpy(dst + off, rb->xfer_host + ((i - 1) & 1) * kXferChunk, len);
+    }
+  }
+  return SERL_OK;
+}
+// A buffer is refilled once the copy that last read it has completed (an event never recorded counts as complete); the caller
+// synchronises the copy stream at the end.
+static int staged_h2d(serl_rb* rb, uint8_t* dev_dst, const uint8_t* src, size_t bytes) {
+  const size_t n = (bytes + kXferChunk - 1) / kXferChunk;
+  for (size_t i = 0; i < n; ++i) {
+    const size_t off = i * kXferChunk, len = bytes - off < kXferChunk ? bytes - off : kXferChunk;
+    uint8_t* h = rb->xfer_host + (i & 1) * kXferChunk;
+    SERL_HIP(hipEventSynchronize(rb->xfer_done[i & 1]));
+    std::memcpy(h, src + off, len);
+    SERL_HIP(hipMemcpyAsync(dev_dst + off, h, len, hipMemcpyHostToDevice, rb->copy_stream));
+    SERL_HIP(hipEventRecord(rb->xfer_done[i & 1], rb->copy_stream));
+  }
+  return SERL_OK;
+}
+// The ring range [slot_begin, slot_begin + n_slots) mod cap as at most two runs of consecutive slots: (first slot, slots, position
+// of the run in the caller's arrays).
+struct SlotRun { int64_t slot, n, at; };
+static int slot_runs(const serl_rb* rb, int64_t slot_begin, int64_t n_slots, SlotRun runs[2]) {
+  const int64_t head = n_slots < rb->cap - slot_begin ? n_slots : rb->cap - slot_begin;
+  int k = 0;
+  if (head > 0) runs[k++] = SlotRun{slot_begin, head, 0};
+  if (n_slots - head > 0) runs[k++] = SlotRun{0, n_slots - head, head};
+  return k;
+}
+static int check_slot_range(const serl_rb* rb, int64_t slot_begin, int64_t n_slots, const uint8_t* const* frames, const void* records) {
+  SERL_REQUIRE(slot_begin >= 0 && slot_begin < rb->cap, "slot_begin %lld not in [0,%lld)", (long long)slot_begin, (long long)rb->cap);
+  SERL_REQUIRE(n_slots >= 0 && n_slots <= rb->cap, "n_slots %lld not in [0,%lld]", (long long)n_slots, (long long)rb->cap);
+  if (n_slots == 0) return SERL_OK;
+  SERL_REQUIRE(records && (rb->n_cam == 0 || frames), "NULL argument");
+  for (int c = 0; c < rb->n_cam; ++c) SERL_REQUIRE(frames[c], "frames[%d] is NULL", c);
+  return SERL_OK;
+}
+// the device reads of an export; the store is marked busy, the mutex is NOT held
+static int export_copies(serl_rb* rb, int64_t slot_begin, int64_t n_slots, uint8_t* const* host_frames, float* host_records) {
+  SERL_HIP(hipSetDevice(rb->device));
+  SERL_HIP(hipEventSynchronize(rb->last_insert));  // the copies of the last insert (the copy stream orders the reads behind them too)
+  SlotRun runs[2];
+  const int nr = slot_runs(rb, slot_begin, n_slots, runs);
+  const size_t rec_bytes = sizeof(float) * rb->rec_len;
+  for (int r = 0; r < nr; ++r) {
+    RC(staged_d2h(rb, reinterpret_cast<uint8_t*>(host_records) + (size_t)runs[r].at * rec_bytes,
+                  reinterpret_cast<const uint8_t*>(rb->rec) + (size_t)runs[r].slot * rec_bytes, (size_t)runs[r].n * rec_bytes));
+    for (int c = 0; c < rb->n_cam; ++c)
+      RC(staged_d2h(rb, host_frames[c] + (size_t)runs[r].at * rb->frame_bytes, rb->frames[c] + (size_t)runs[r].slot * rb->frame_bytes,
+                    (size_t)runs[r].n * rb->frame_bytes));
+  }
+  return SERL_OK;
 }
 
 }  // namespace serl
@@ -583,6 +670,9 @@ int serl_rb_destroy(serl_rb* rb) {
     if (rb->gather_ev[k]) (void)hipEventDestroy(rb->gather_ev[k]);
   if (rb->last_insert) (void)hipEventDestroy(rb->last_insert);
   if (rb->ins_host) (void)hipHostFree(rb->ins_host);
+  if (rb->xfer_host) (void)hipHostFree(rb->xfer_host);
+  for (int k = 0; k < 2; ++k)
+    if (rb->xfer_done[k]) (void)hipEventDestroy(rb->xfer_done[k]);
   for (int s = 0; s < kInsRing; ++s)
     if (rb->ins_done[s]) (void)hipEventDestroy(rb->ins_done[s]);
   if (rb->copy_stream) (void)hipStreamDestroy(rb->copy_stream);
@@ -619,7 +709,8 @@ int serl_rb_insert(serl_rb* rb, const uint8_t* const* obs_frames, const uint8_t*
                    float mask, int done) {
   SERL_REQUIRE(rb && state && next_state && action, "NULL argument");
   SERL_REQUIRE(rb->n_cam == 0 || (obs_frames && next_frames), "NULL frames");
-  std::lock_guard<std::mutex> g(rb->mu);
+  std::unique_lock<std::mutex> g(rb->mu);
+  rb->idle.wait(g, [rb] { return !rb->busy; });  // a snapshot export is reading the slots
   SERL_HIP(hipSetDevice(rb->device));
   int rc = order_after_gathers(rb);  // never overwrite a slot an in-flight gather may still read
   if (rc) return rc;
@@ -676,10 +767,111 @@ int64_t serl_rb_insert_index(serl_rb* rb) {
   std::lock_guard<std::mutex> g(rb->mu);
   return rb->insert_index;
 }
+int64_t serl_rb_insert_count(serl_rb* rb) {
+  if (!rb) return -1;
+  std::lock_guard<std::mutex> g(rb->mu);
+  return rb->insert_count;
+}
 int serl_rb_valid_mask(serl_rb* rb, uint8_t* host_out) {
   SERL_REQUIRE(rb && host_out, "NULL argument");
   std::lock_guard<std::mutex> g(rb->mu);
   std::memcpy(host_out, rb->valid.data(), (size_t)rb->cap);
+  return SERL_OK;
+}
+
+int serl_rb_export_meta(serl_rb* rb, serl_rb_meta* out) {
+  SERL_REQUIRE(rb && out, "NULL argument");
+  std::lock_guard<std::mutex> g(rb->mu);
+  std::memset(out, 0, sizeof(*out));
+  out->capacity = rb->cap;
+  out->n_cam = rb->n_cam; out->H = rb->H; out->W = rb->W; out->C = rb->C; out->T = rb->T; out->S = rb->S; out->A = rb->A;
+  out->rec_len = rb->rec_len;
+  out->size = rb->size; out->insert_index = rb->insert_index; out->insert_count = rb->insert_count;
+  out->first = rb->first ? 1 : 0;
+  out->rng_seeded = rb->rng.seeded ? 1 : 0;
+  out->rng_state_inc[0] = (uint64_t)(rb->rng.state >> 64);
+  out->rng_state_inc[1] = (uint64_t)rb->rng.state;
+  out->rng_state_inc[2] = (uint64_t)(rb->rng.inc >> 64);
+  out->rng_state_inc[3] = (uint64_t)rb->rng.inc;
+  out->rng_has_uint32 = rb->rng.has_uint32;
+  out->rng_uinteger = rb->rng.uinteger;
+  return SERL_OK;
+}
+
+int serl_rb_export_slots(serl_rb* rb, int64_t slot_begin, int64_t n_slots, uint8_t* const* host_frames, float* host_records,
+                         uint8_t* host_valid) {
+  SERL_REQUIRE(rb, "rb is NULL");
+  int rc = check_slot_range(rb, slot_begin, n_slots, host_frames, host_records);
+  if (rc) return rc;
+  {
+    std::unique_lock<std::mutex> g(rb->mu);
+    rb->idle.wait(g, [rb] { return !rb->busy; });
+    SERL_HIP(hipSetDevice(rb->device));
+    if ((rc = xfer_init(rb))) return rc;
+    // the mask belongs to the same instant as the slots: no insert runs between here and the end of the copies
+    if (host_valid) std::memcpy(host_valid, rb->valid.data(), (size_t)rb->cap);
+    rb->busy = true;
+  }
+  // mutex released: sample_indices and gathers go on; inserts wait on `idle`
+  rc = export_copies(rb, slot_begin, n_slots, host_frames, host_records);
+  {
+    std::lock_guard<std::mutex> g(rb->mu);
+    rb->busy = false;
+  }
+  rb->idle.notify_all();
+  return rc;
+}
+
+int serl_rb_import_meta(serl_rb* rb, const serl_rb_meta* m) {
+  SERL_REQUIRE(rb && m, "NULL argument");
+  std::unique_lock<std::mutex> g(rb->mu);
+  rb->idle.wait(g, [rb] { return !rb->busy; });
+  SERL_REQUIRE(m->capacity == rb->cap && m->n_cam == rb->n_cam && m->H == rb->H && m->W == rb->W && m->C == rb->C && m->T == rb->T &&
+                   m->S == rb->S && m->A == rb->A && m->rec_len == rb->rec_len,
+               "snapshot geometry (capacity %lld, %d cameras %dx%dx%d, T %d, S %d, A %d) is not the store's (capacity %lld, %d cameras "
+               "%dx%dx%d, T %d, S %d, A %d)", (long long)m->capacity, m->n_cam, m->H, m->W, m->C, m->T, m->S, m->A, (long long)rb->cap,
+               rb->n_cam, rb->H, rb->W, rb->C, rb->T, rb->S, rb->A);
+  SERL_REQUIRE(m->insert_count >= 0 && m->insert_index == m->insert_count % rb->cap &&
+                   m->size == (m->insert_count < rb->cap ? m->insert_count : rb->cap),
+               "inconsistent bookkeeping: size %lld, insert_index %lld, insert_count %lld at capacity %lld", (long long)m->size,
+               (long long)m->insert_index, (long long)m->insert_count, (long long)rb->cap);
+  rb->size = m->size;
+  rb->insert_index = m->insert_index;
+  rb->insert_count = m->insert_count;
+  rb->first = m->first != 0;
+  if (m->rng_seeded) {
+    rb->rng.state = ((unsigned __int128)m->rng_state_inc[0] << 64) | m->rng_state_inc[1];
+    rb->rng.inc = ((unsigned __int128)m->rng_state_inc[2] << 64) | m->rng_state_inc[3];
+    rb->rng.has_uint32 = m->rng_has_uint32;
+    rb->rng.uinteger = m->rng_uinteger;
+    rb->rng.seeded = true;
+  }
+  return SERL_OK;
+}
+
+int serl_rb_import_slots(serl_rb* rb, int64_t slot_begin, int64_t n_slots, const uint8_t* const* host_frames,
+                         const float* host_records, const uint8_t* host_valid) {
+  SERL_REQUIRE(rb, "rb is NULL");
+  int rc = check_slot_range(rb, slot_begin, n_slots, host_frames, host_records);
+  if (rc) return rc;
+  std::unique_lock<std::mutex> g(rb->mu);
+  rb->idle.wait(g, [rb] { return !rb->busy; });
+  SERL_HIP(hipSetDevice(rb->device));
+  if ((rc = xfer_init(rb))) return rc;
+  if ((rc = order_after_gathers(rb))) return rc;  // as an insert: never overwrite a slot an in-flight gather may still read
+  SlotRun runs[2];
+  const int nr = slot_runs(rb, slot_begin, n_slots, runs);
+  const size_t rec_bytes = sizeof(float) * rb->rec_len;
+  for (int r = 0; r < nr; ++r) {
+    const uint8_t* rec_src = reinterpret_cast<const uint8_t*>(host_records) + (size_t)runs[r].at * rec_bytes;
+    std::memcpy(&rb->rec_host[(size_t)runs[r].slot * rb->rec_len], rec_src, (size_t)runs[r].n * rec_bytes);
+    RC(staged_h2d(rb, reinterpret_cast<uint8_t*>(rb->rec) + (size_t)runs[r].slot * rec_bytes, rec_src, (size_t)runs[r].n * rec_bytes));
+    for (int c = 0; c < rb->n_cam; ++c)
+      RC(staged_h2d(rb, rb->frames[c] + (size_t)runs[r].slot * rb->frame_bytes, host_frames[c] + (size_t)runs[r].at * rb->frame_bytes,
+                    (size_t)runs[r].n * rb->frame_bytes));
+  }
+  if (host_valid) std::memcpy(rb->valid.data(), host_valid, (size_t)rb->cap);
+  SERL_HIP(hipStreamSynchronize(rb->copy_stream));  // the slots are in HBM when the call returns: a later gather needs no wait
   return SERL_OK;
 }
 

@@ -15,12 +15,14 @@ from __future__ import annotations
 
 import collections
 import ctypes as C
+import threading
 from typing import Iterable, Optional
 
 import numpy as np
 import torch
 
 from .. import _lib
+from . import snapshot as _snap
 from ..transport.endpoint import DataStoreBase
 
 
@@ -122,6 +124,7 @@ class MemoryEfficientReplayBufferDataStore(DataStoreBase):
                                              self._num_stack, self._S, self._A, C.byref(self._h)))
         self._np_random = None
         self._seed = None
+        self._lock = threading.Lock()   # insert() against the device -> host phase of save_snapshot()
 
     def __del__(self):
         h = getattr(self, "_h", None)
@@ -181,9 +184,10 @@ class MemoryEfficientReplayBufferDataStore(DataStoreBase):
         nst = np.ascontiguousarray(nobs["state"], dtype=np.float32).reshape(-1)
         act = np.ascontiguousarray(data_dict["actions"], dtype=np.float32).reshape(-1)
         assert st.size == T * self._S and nst.size == T * self._S and act.size == self._A
-        _lib.check(_lib.lib().serl_rb_insert(
-            self._h, obs_p, next_p, st.ctypes.data, nst.ctypes.data, act.ctypes.data,
-            float(data_dict["rewards"]), float(data_dict["masks"]), int(bool(data_dict["dones"]))))
+        with self._lock:
+            _lib.check(_lib.lib().serl_rb_insert(
+                self._h, obs_p, next_p, st.ctypes.data, nst.ctypes.data, act.ctypes.data,
+                float(data_dict["rewards"]), float(data_dict["masks"]), int(bool(data_dict["dones"]))))
 
     # -- index draw (memory_efficient_replay_buffer.py:111-122)
     def sample_indices(self, batch_size: int) -> np.ndarray:
@@ -255,6 +259,99 @@ class MemoryEfficientReplayBufferDataStore(DataStoreBase):
     def handle(self):
         return self._h
 
+    # -- snapshot / restore (run resume; file form: serl_amd/data/snapshot.py)
+    def insert_count(self) -> int:
+        """Slot writes ever made (serl_rb_insert_count): unlike latest_data_id() it does not wrap."""
+        return int(_lib.lib().serl_rb_insert_count(self._h))
+
+    def rng_state(self) -> dict:
+        """The sampler's PCG64 in numpy's terms: {"state", "inc", "has_uint32", "uinteger"}."""
+        return _meta_state(self._meta())["rng"]
+
+    def _meta(self):
+        m = _lib.SerlRbMeta()
+        _lib.check(_lib.lib().serl_rb_export_meta(self._h, C.byref(m)))
+        return m
+
+    def save_snapshot(self, path: str, incremental: bool = False) -> dict:
+        """Writes the store (slots, valid mask, ring bookkeeping, sampler state) into the directory `path` and returns the
+        manifest.  incremental=True extends the snapshot already in `path` -- which must be an earlier snapshot of THIS store's
+        history -- by one segment holding the slots written since; with no usable snapshot there, or a whole ring of slot writes
+        since, it saves everything.  Inserts wait while HBM is copied to host buffers (sampling and gathers go on) and run again
+        while the files are written; a save that dies leaves the previous snapshot in `path` readable."""
+        self._ensure_seeded()   # a snapshot always carries a generator state
+        base = None
+        if incremental:
+            try:
+                base = _snap.read_manifest(path)
+            except ValueError:
+                base = None
+        n_cam = len(self.pixel_keys)
+        with self._lock:
+            m = self._meta()
+            geometry, state = _meta_geometry(m), _meta_state(m)
+            count, cap = state["count"], geometry["capacity"]
+            if base is not None and base["geometry"] == geometry and 0 <= count - base["count"] < cap:
+                first_count = base["count"]
+            else:
+                base, first_count = None, max(0, count - cap)
+            n = count - first_count
+            frames = [np.empty((n, m.H, m.W, m.C), np.uint8) for _ in range(n_cam)]
+            records = np.empty((n, m.rec_len), np.float32)
+            valid = np.empty(cap, np.uint8)
+            fp = (C.c_void_p * max(n_cam, 1))(*[f.ctypes.data for f in frames])
+            _lib.check(_lib.lib().serl_rb_export_slots(self._h, first_count % cap, n, fp if n_cam else None,
+                                                       records.ctypes.data, valid.ctypes.data))
+        state["seed"] = self._seed
+        return _snap.write_snapshot(path, geometry, state, valid, first_count, frames, records, base)
+
+    def check_snapshot(self, path: str) -> dict:
+        """Checks the snapshot in `path` against this store WITHOUT loading anything: the manifest's form and geometry, and the
+        length and checksum of every file.  Returns the manifest; ValueError names the bad file."""
+        manifest = _snap.read_manifest(path, _meta_geometry(self._meta()))
+        _snap.verify_snapshot(path, manifest)
+        return manifest
+
+    def restore_snapshot(self, path: str, manifest: Optional[dict] = None) -> dict:
+        """Loads the snapshot in `path` into this (already constructed) store of the same geometry and returns its manifest.
+        Every file is checked first: a truncated or missing file, a checksum or a geometry mismatch raises ValueError naming the
+        file, and the store keeps its contents.  `manifest`: what check_snapshot(path) returned just before (the files are then
+        not read a second time for their checksums)."""
+        if manifest is None:
+            manifest = self.check_snapshot(path)
+        valid = _snap.load_valid(path, manifest)
+        m = _lib.SerlRbMeta(**{k: manifest["geometry"][k] for k in _snap.GEOMETRY_KEYS})
+        m.size, m.insert_index, m.insert_count, m.first = manifest["size"], manifest["insert_index"], manifest["count"], int(manifest["first"])
+        s, inc, mask = int(manifest["rng"]["state"]), int(manifest["rng"]["inc"]), (1 << 64) - 1
+        m.rng_seeded, m.rng_has_uint32, m.rng_uinteger = 1, manifest["rng"]["has_uint32"], manifest["rng"]["uinteger"]
+        m.rng_state_inc[:] = [s >> 64, s & mask, inc >> 64, inc & mask]
+        n_cam = len(self.pixel_keys)
+        with self._lock:
+            _lib.check(_lib.lib().serl_rb_import_meta(self._h, C.byref(m)))
+            for seg in manifest["segments"]:
+                frames, records = _snap.load_segment(path, manifest, seg)
+                fp = (C.c_void_p * max(n_cam, 1))(*[f.ctypes.data for f in frames])
+                _lib.check(_lib.lib().serl_rb_import_slots(self._h, seg["slot_begin"], seg["n_slots"], fp if n_cam else None,
+                                                           records.ctypes.data, None))
+            _lib.check(_lib.lib().serl_rb_import_slots(self._h, 0, 0, None, None, valid.ctypes.data))
+        # the generator is the snapshot's: _ensure_seeded() must not draw a fresh OS-entropy seed over it
+        self._seed = int(manifest["seed"]) if manifest.get("seed") not in (None, "None") else 0
+        self._np_random = np.random.Generator(np.random.PCG64())
+        self._np_random.bit_generator.state = {"bit_generator": "PCG64", "state": {"state": s, "inc": inc},
+                                               "has_uint32": manifest["rng"]["has_uint32"], "uinteger": manifest["rng"]["uinteger"]}
+        return manifest
+
+
+def _meta_geometry(m) -> dict:
+    return {k: int(getattr(m, k)) for k in _snap.GEOMETRY_KEYS}
+
+
+def _meta_state(m) -> dict:
+    st = m.rng_state_inc
+    return {"size": int(m.size), "insert_index": int(m.insert_index), "count": int(m.insert_count), "first": bool(m.first),
+            "rng": {"state": (st[0] << 64) | st[1], "inc": (st[2] << 64) | st[3], "has_uint32": int(m.rng_has_uint32),
+                    "uinteger": int(m.rng_uinteger)}}
+
 
 class ReplayBufferDataStore(MemoryEfficientReplayBufferDataStore):
     """Drop-in for the reference's plain `ReplayBufferDataStore` (data_store.py:27-80) of flat observations
@@ -279,6 +376,7 @@ class ReplayBufferDataStore(MemoryEfficientReplayBufferDataStore):
         _lib.check(_lib.lib().serl_rb_create(device, self._capacity, 0, 0, 0, 0, 1, self._S, self._A, C.byref(self._h)))
         self._np_random = None
         self._seed = None
+        self._lock = threading.Lock()   # insert() against the device -> host phase of save_snapshot()
 
     def insert(self, data):  # replay_buffer.py:71-75 under the data store's lock (data_store.py:44-46)
         data_dict = data
@@ -286,9 +384,10 @@ class ReplayBufferDataStore(MemoryEfficientReplayBufferDataStore):
         nst = np.ascontiguousarray(data_dict["next_observations"], dtype=np.float32).reshape(-1)
         act = np.ascontiguousarray(data_dict["actions"], dtype=np.float32).reshape(-1)
         assert st.size == self._S and nst.size == self._S and act.size == self._A
-        _lib.check(_lib.lib().serl_rb_insert(
-            self._h, None, None, st.ctypes.data, nst.ctypes.data, act.ctypes.data,
-            float(data_dict["rewards"]), float(data_dict["masks"]), int(bool(data_dict["dones"]))))
+        with self._lock:
+            _lib.check(_lib.lib().serl_rb_insert(
+                self._h, None, None, st.ctypes.data, nst.ctypes.data, act.ctypes.data,
+                float(data_dict["rewards"]), float(data_dict["masks"]), int(bool(data_dict["dones"]))))
 
     def gather(self, indx: np.ndarray, stream=None):
         indx = np.ascontiguousarray(indx, dtype=np.int64)

@@ -38,7 +38,11 @@ _REG, _FLUSH, _CLOSE = 0, 1, 2
 
 class ReplicatedDataStore:
     """Wraps one rank's replica `store` (anything with insert(transition); the HBM stores of data_store.py in
-    production).  Everything except insert / step_barrier / flush / close is forwarded to the replica."""
+    production).  Everything except insert / step_barrier / flush / close is forwarded to the replica.
+
+    Run resume is out of scope here: save_snapshot / restore_snapshot reach the replica like any forwarded name, but they know
+    nothing of the transitions still pending or in the inbox, nor of the message indices the ranks agree on, so a multi-rank
+    job cannot be stopped and continued through them."""
 
     def __init__(self, store, rank: int, world: int, group=None, lag: int = 2, timeout_s: float = 120.0):
         self._store, self.rank, self.world = store, int(rank), int(world)

@@ -14,6 +14,7 @@ from __future__ import annotations
 
 import os
 import re
+import shutil
 from typing import Optional
 
 import msgpack
@@ -82,8 +83,10 @@ def latest_checkpoint(ckpt_dir: str, prefix: str = "checkpoint_") -> Optional[st
     return os.path.join(ckpt_dir, f"{prefix}{max(steps)}") if steps else None
 
 
-def restore_checkpoint(ckpt_dir_or_file: str, agent, step: Optional[int] = None, prefix: str = "checkpoint_"):
-    """Loads params / target_params / Adam moments / step back into the agent's HBM arena."""
+def restore_checkpoint(ckpt_dir_or_file: str, agent, step: Optional[int] = None, prefix: str = "checkpoint_",
+                       restore_rng: bool = False):
+    """Loads params / target_params / Adam moments / step back into the agent's HBM arena; with restore_rng=True also
+    `state.rng` (see load_state_dict)."""
     path = ckpt_dir_or_file
     if os.path.isdir(path):
         path = os.path.join(path, f"{prefix}{step}") if step is not None else latest_checkpoint(path, prefix)
@@ -91,7 +94,7 @@ def restore_checkpoint(ckpt_dir_or_file: str, agent, step: Optional[int] = None,
             return agent  # flax returns the target unchanged when there is nothing to restore
     with open(path, "rb") as f:
         sd = msgpack.unpackb(f.read(), ext_hook=_unpack_ext, raw=False, strict_map_key=False)
-    return load_state_dict(agent, sd)
+    return load_state_dict(agent, sd, restore_rng=restore_rng)
 
 
 def read_checkpoint_tree(ckpt_dir_or_file: str, step: Optional[int] = None, prefix: str = "checkpoint_") -> dict:
@@ -127,9 +130,13 @@ def _find_adam_state(node):
     return None
 
 
-def load_state_dict(agent, sd: dict):
+def load_state_dict(agent, sd: dict, restore_rng: bool = False):
     """Loads any of {params, target_params, opt_states, step} (flax-layout trees, e.g. a restored checkpoint or
-    `agent.state.replace(...)` arguments) into the agent's HBM arena."""
+    `agent.state.replace(...)` arguments) into the agent's HBM arena.  restore_rng=True also takes `state.rng` from `sd["rng"]`
+    (DrQAgent / SACAgent): crop offsets, REDQ indices, policy normals and Dropout masks all derive from it, so only then does the
+    agent CONTINUE the run the state was saved from.  Off by default: a restored agent keeps the rng it was created with, as
+    before.  Agents with their own state-dict form decide themselves and ignore the flag: BCAgent's form carries `rng` and
+    restores it whenever it is present; the reward classifier's TrainState has no rng (its Dropout keys come from the caller)."""
     own = _own_form(agent)
     if own is not None:
         own.load_state_dict(sd)
@@ -166,4 +173,109 @@ def load_state_dict(agent, sd: dict):
                     core.set(f"opt/{tx}/{mom}", leaf, np.asarray(v, np.float32))
     if sd.get("step") is not None:
         core.step = int(np.asarray(sd["step"]))
+    if restore_rng:
+        if sd.get("rng") is None:
+            raise KeyError("restore_rng=True, but the state dict holds no 'rng'")
+        agent._rng_key = np.asarray(sd["rng"], np.uint32).reshape(2).copy()
     return agent
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# Run state: the agent's checkpoint plus one snapshot directory per replay store (serl_amd/data/snapshot.py), so that a learner
+# process can be stopped and continued.  <run_dir>/checkpoint_<step> is the agent (format unchanged);
+# <run_dir>/store_<name>_<step>/ is the store `name` at that step.
+# ---------------------------------------------------------------------------------------------------------------------------
+def _store_dir(run_dir: str, name: str, step: int) -> str:
+    return os.path.join(run_dir, f"store_{name}_{step}")
+
+
+def _store_steps(run_dir: str, name: str):
+    ms = (re.fullmatch(r"store_" + re.escape(name) + r"_(\d+)", n) for n in os.listdir(run_dir))
+    return sorted(int(m.group(1)) for m in ms if m)
+
+
+def _link_snapshot(src: str, dst: str) -> bool:
+    """Hard-links the files of the snapshot in `src` into the new directory `dst` (and copies its manifest), so that an
+    incremental save into `dst` extends it without copying a byte and pruning `src` later frees nothing `dst` needs.  False
+    (and `dst` left empty) where there is no readable snapshot or the file system has no hard links."""
+    from ..data import snapshot as snap
+    try:
+        m = snap.read_manifest(src)
+        os.makedirs(dst, exist_ok=True)
+        for e in [m["valid"]] + m["segments"]:
+            if not os.path.exists(os.path.join(dst, e["file"])):
+                os.link(os.path.join(src, e["file"]), os.path.join(dst, e["file"]))
+        shutil.copyfile(os.path.join(src, snap.MANIFEST), os.path.join(dst, snap.MANIFEST + ".tmp"))
+        os.replace(os.path.join(dst, snap.MANIFEST + ".tmp"), os.path.join(dst, snap.MANIFEST))
+        return True
+    except (ValueError, OSError):
+        shutil.rmtree(dst, ignore_errors=True)
+        return False
+
+
+def _complete_steps(run_dir: str):
+    """steps that have a `checkpoint_<step>` file: only these were saved to the end"""
+    ms = (re.fullmatch(r"checkpoint_(\d+)", n) for n in os.listdir(run_dir))
+    return sorted(int(m.group(1)) for m in ms if m)
+
+
+def save_run(run_dir: str, agent, stores: dict, step: int, keep: int = 1) -> str:
+    """Saves the agent (`checkpoint_<step>`, as save_checkpoint) and every store of `stores` ({name: data store}) into `run_dir`.
+    The checkpoint file is written LAST: a step is COMPLETE once it exists.  A store's snapshot extends the one of the latest
+    complete earlier step where there is one (only the slots written since are copied out of HBM and written); store directories
+    of steps without a checkpoint file -- a save that died, whose slots a resumed run never wrote -- are removed first and never
+    extended.  A step's directory is built under a temporary name and renamed, so saving a complete step again keeps its old
+    snapshot until the new one is whole.  The `keep` most recent steps stay, as for checkpoints.  `run_dir` belongs to ONE run:
+    its stores' history is what the incremental saves extend, and nothing else may write `checkpoint_<n>` files into it.  Call
+    it from the learner thread between updates; inserts from other threads wait only while a store's slots are copied to host
+    memory."""
+    os.makedirs(run_dir, exist_ok=True)
+    for name in stores:
+        if not re.fullmatch(r"[A-Za-z0-9._-]+", name):
+            raise ValueError(f"store name {name!r}: letters, digits, '.', '_' and '-' only")
+    complete = _complete_steps(run_dir)
+    for n in os.listdir(run_dir):
+        m = re.fullmatch(r"store_.+_(\d+)(\.tmp)?", n)
+        if m and (m.group(2) or int(m.group(1)) not in complete):
+            shutil.rmtree(os.path.join(run_dir, n), ignore_errors=True)
+    earlier = [s for s in complete if s < step]
+    for name, store in stores.items():
+        dst = _store_dir(run_dir, name, step)
+        tmp = dst + ".tmp"
+        linked = bool(earlier) and _link_snapshot(_store_dir(run_dir, name, earlier[-1]), tmp)
+        store.save_snapshot(tmp, incremental=linked)
+        if os.path.exists(dst):
+            shutil.rmtree(dst)
+        os.rename(tmp, dst)
+    path = save_checkpoint(run_dir, agent, step, keep=keep, overwrite=True)
+    kept = set(_complete_steps(run_dir))
+    for name in stores:
+        for s in _store_steps(run_dir, name):
+            if s not in kept:
+                shutil.rmtree(_store_dir(run_dir, name, s), ignore_errors=True)
+    return path
+
+
+def restore_run(run_dir: str, agent, stores: dict, step: Optional[int] = None) -> int:
+    """Restores what save_run wrote into an agent and stores constructed as for the original run (same configuration and
+    geometry), `state.rng` and the stores' sampler states included, and returns the step: the given `step`, or the newest
+    complete step whose store snapshots all check (a newer one that does not is passed over).  Every snapshot -- manifest,
+    geometry against its store, length and checksum of every file -- is checked before anything is loaded: ValueError (naming
+    the bad file) leaves agent and stores untouched."""
+    if not os.path.isdir(run_dir):
+        raise FileNotFoundError(f"no checkpoint_<step> file in {run_dir}")
+    candidates = [step] if step is not None else _complete_steps(run_dir)[::-1]
+    if not candidates or (step is not None and not os.path.isfile(os.path.join(run_dir, f"checkpoint_{step}"))):
+        raise FileNotFoundError(f"no checkpoint_<step> file in {run_dir}" if step is None else os.path.join(run_dir, f"checkpoint_{step}"))
+    first_error = None
+    for s in candidates:
+        try:
+            manifests = {name: store.check_snapshot(_store_dir(run_dir, name, s)) for name, store in stores.items()}
+        except ValueError as e:
+            first_error = first_error or e
+            continue
+        restore_checkpoint(os.path.join(run_dir, f"checkpoint_{s}"), agent, restore_rng=True)
+        for name, store in stores.items():
+            store.restore_snapshot(_store_dir(run_dir, name, s), manifest=manifests[name])
+        return s
+    raise first_error
