@@ -1,18 +1,19 @@
 // HBM-resident memory-efficient replay buffer for SERL on MI355X (gfx950).
 //
-// Host side: slot bookkeeping identical to the reference's MemoryEfficientReplayBuffer
-// (serl_launcher/data/memory_efficient_replay_buffer.py:53-89) and a bit-exact PCG64/Lemire index
-// sampler (numpy Generator.integers; memory_efficient_replay_buffer.py:111-122).
+// Host side: replay_index.h holds the reference's slot bookkeeping and index sampler (no HIP, tested on the CPU); this
+// file stages host data through pinned rings, orders the streams and launches the kernels.
 // Device side: one fused kernel = sample gather + concat_batches + _unpack + DrQ random shift
 // (K2+K3+K4).  It is HBM-bound u8 traffic: every source frame row is pulled once with 16-byte
 // coalesced loads into LDS, shifted/clamped out of LDS, and written once with 16-byte stores.
 #include <condition_variable>
 #include <cstring>
+#include <memory>
 #include <mutex>
 #include <vector>
 
 #include "common.h"
 #include "prof.h"
+#include "replay_index.h"
 
 namespace serl {
 
@@ -24,72 +25,60 @@ void set_error(const char* fmt, ...) {
   va_end(ap);
 }
 
-// ---------------------------------------------------------------------------------------------
-// PCG64 XSL-RR 128/64 with numpy's buffered next_uint32 and Lemire bounded draws.
-// ---------------------------------------------------------------------------------------------
-struct Pcg64 {
-  unsigned __int128 state = 0, inc = 0;
-  int has_uint32 = 0;
-  uint32_t uinteger = 0;
-  bool seeded = false;
-
-  uint64_t next64() {
-    const unsigned __int128 mult =
-        ((unsigned __int128)0x2360ED051FC65DA4ULL << 64) | 0x4385DF649FCCF645ULL;
-    state = state * mult + inc;
-    uint64_t hi = (uint64_t)(state >> 64), lo = (uint64_t)state;
-    uint64_t x = hi ^ lo;
-    unsigned r = (unsigned)(state >> 122);
-    return (x >> r) | (x << ((64 - r) & 63));
-  }
-  uint32_t next32() {
-    if (has_uint32) {
-      has_uint32 = 0;
-      return uinteger;
-    }
-    uint64_t v = next64();
-    has_uint32 = 1;
-    uinteger = (uint32_t)(v >> 32);
-    return (uint32_t)v;
-  }
-  // Generator.integers(n), 0 < n < 2^32 - 1 (numpy buffered_bounded_lemire_uint32)
-  uint32_t bounded(uint32_t n) {
-    if (n == 1) return 0;
-    uint64_t m = (uint64_t)next32() * n;
-    uint32_t l = (uint32_t)m;
-    if (l < n) {
-      uint32_t t = (0xFFFFFFFFu - (n - 1)) % n;
-      while (l < t) {
-        m = (uint64_t)next32() * n;
-        l = (uint32_t)m;
-      }
-    }
-    return (uint32_t)(m >> 32);
-  }
-};
-
 constexpr int kRing = 8;           // staging slots for per-call index/crop parameters
 constexpr int kInsRing = 32;       // pinned staging slots for inserted transitions (one slot write each)
 constexpr int kRowsPerBlock = 32;  // output rows per workgroup in the gather/crop kernel
 constexpr size_t kXferChunk = (size_t)8 << 20;  // bytes per pinned staging buffer of the snapshot export / import (two of them)
 
+// A ring of `n` pinned host slots (and, if asked for, as many device slots) with one event per slot.  acquire() hands out the
+// next slot, first waiting for the work that last used it if the ring has wrapped; mark() records that work's end.  The owner
+// serialises the calls (a mutex), so the slot between an acquire and its mark is `cur`.
+struct StageRing {
+  uint8_t* host = nullptr;
+  uint8_t* dev = nullptr;
+  size_t slot_bytes = 0;
+  int n = 0, next = 0, cur = 0;
+  hipEvent_t done[kInsRing] = {nullptr};
+  bool used[kInsRing] = {false};
+
+  int init(int n_slots, size_t bytes, bool with_dev) {
+    n = n_slots; slot_bytes = bytes;
+    SERL_HIP(hipHostMalloc((void**)&host, slot_bytes * n, hipHostMallocDefault));
+    if (with_dev) SERL_HIP(hipMalloc((void**)&dev, slot_bytes * n));
+    for (int s = 0; s < n; ++s) SERL_HIP(hipEventCreateWithFlags(&done[s], hipEventDisableTiming));
+    return SERL_OK;
+  }
+  void destroy() {  // tolerates a half-built ring
+    if (host) (void)hipHostFree(host);
+    if (dev) (void)hipFree(dev);
+    for (int s = 0; s < kInsRing; ++s)
+      if (done[s]) (void)hipEventDestroy(done[s]);
+  }
+  int acquire() {
+    cur = next;
+    next = (cur + 1) % n;
+    if (used[cur]) SERL_HIP(hipEventSynchronize(done[cur]));  // ring wrapped: that work is long done
+    return SERL_OK;
+  }
+  int mark(hipStream_t stream) {
+    SERL_HIP(hipEventRecord(done[cur], stream));
+    used[cur] = true;
+    return SERL_OK;
+  }
+  uint8_t* h() const { return host + (size_t)cur * slot_bytes; }
+  uint8_t* d() const { return dev + (size_t)cur * slot_bytes; }
+};
+
 }  // namespace serl
 
 struct serl_rb {
   int device = 0;
-  int64_t cap = 0;
   int n_cam = 0, H = 0, W = 0, C = 0, T = 1, S = 0, A = 0;
   int rec_len = 0;  // floats per record: [state T*S | next_state T*S | action A | reward | mask | done]
   size_t frame_bytes = 0;
   uint8_t* frames[SERL_MAX_CAMS] = {nullptr};  // device, [cap][H*W*C] each
   float* rec = nullptr;                        // device, [cap][rec_len]
-  // host bookkeeping (memory_efficient_replay_buffer.py)
-  std::vector<uint8_t> valid;
-  std::vector<float> rec_host;  // host mirror of the records (needed for the wrap re-insert)
-  int64_t size = 0, insert_index = 0;
-  int64_t insert_count = 0;  // slot writes ever made (insert_index == insert_count % cap)
-  bool first = true;
-  serl::Pcg64 rng;
+  serl::ReplayIndex ix;  // host bookkeeping (memory_efficient_replay_buffer.py); guarded by `mu`
   std::mutex mu;
   // snapshot export (serl_rb_export_slots): while `busy`, inserts and other exports / imports wait on `idle` with the mutex
   // released -- index draws and gathers only take the mutex and go on.  The two pinned staging buffers are made at the first use.
@@ -108,23 +97,13 @@ struct serl_rb {
   bool gather_pend[kGatherStreams] = {false, false, false, false};
   int gather_rr = 0;
   bool gather_pending = false;
-  // inserts are staged through a pinned ring and copied asynchronously on copy_stream: the caller's thread (the
-  // actor-facing server thread of data_store.py:104-106) holds the mutex for a host memcpy only, never for a stream
-  // synchronisation, so it cannot stall the learner thread's sample_indices / gather
-  uint8_t* ins_host = nullptr;
-  size_t ins_slot_bytes = 0;
-  hipEvent_t ins_done[serl::kInsRing] = {nullptr};
-  bool ins_used[serl::kInsRing] = {false};
-  int ins_next = 0;
+  // inserts are staged through a pinned ring (slot = padded record + one frame per camera) and copied asynchronously on
+  // copy_stream: the caller's thread (the actor-facing server thread of data_store.py:104-106) holds the mutex for a host
+  // memcpy only, never for a stream synchronisation, so it cannot stall the learner thread's sample_indices / gather
+  serl::StageRing ins;
   hipEvent_t last_insert = nullptr;
   bool insert_pending = false;
-  // per-call parameter staging (pinned host + device), ring of kRing slots
-  uint8_t* stage_host = nullptr;
-  uint8_t* stage_dev = nullptr;
-  size_t stage_slot_bytes = 0;
-  hipEvent_t stage_done[serl::kRing] = {nullptr};
-  bool stage_used[serl::kRing] = {false};
-  int stage_next = 0;
+  serl::StageRing stage;  // per-call parameter staging (pinned host + device)
 };
 
 namespace serl {
@@ -152,6 +131,54 @@ struct GatherArgs {
   const uint8_t* packed[SERL_MAX_CAMS];
   int from_packed;
 };
+
+struct PackedArgs {
+  const uint8_t* frames[SERL_MAX_CAMS];
+  const float* rec;
+  const int64_t* idx;
+  int batch, n_cam, T, TS, A, rec_len;
+  int64_t cap;
+  size_t fbytes;
+  uint8_t* out_frames[SERL_MAX_CAMS];  // [batch][T+1][fbytes]
+  float *out_state, *out_next_state, *out_action, *out_reward, *out_mask;
+  uint8_t* out_done;
+  int n_frame_blocks, vec_per_block;
+};
+
+// Frame t of the T+1 frame window of slot idx[j]: slots idx-T .. idx.  numpy wraps a negative window index to
+// cap - T + (idx - T) (reference quirk for a valid slot below T, see oracle/replay_oracle.py gather()).
+__device__ __forceinline__ const uint8_t* window_frame(const uint8_t* frames, const int64_t* idx, int j, int T, int64_t cap, int t,
+                                                       size_t fbytes) {
+  int64_t start = idx[j] - T;
+  if (start < 0) start += cap - T;
+  return frames + (size_t)(start + t) * fbytes;
+}
+// source frame of (which, cam, sample i): which 0 = observation frame (slot idx-1), 1 = next frame (slot idx); T == 1 here.
+// Samples [0,count0) come from buffer 0, the rest from buffer 1.
+__device__ __forceinline__ const uint8_t* source_frame(const GatherArgs& a, int which, int cam, int i, size_t fbytes) {
+  if (a.from_packed) return a.packed[cam] + ((size_t)i * 2 + which) * fbytes;
+  const int buf = (i < a.count0) ? 0 : 1;
+  return window_frame(a.frames[buf][cam], a.idx[buf], buf == 0 ? i : i - a.count0, 1, a.cap[buf], which, fbytes);
+}
+// (dy, dx) of sample i; without a table it is the identity crop (4, 4)
+__device__ __forceinline__ int2 crop_offset(const int32_t* crop, int i) {
+  return make_int2(crop ? crop[2 * i] : 4, crop ? crop[2 * i + 1] : 4);
+}
+// frame workgroup -> (part of the frame, sample, camera, which), part fastest; with the source frame and the shift (sy, sx)
+struct FrameJob { int part, i, cam, which, sy, sx; const uint8_t* src; };
+__device__ __forceinline__ FrameJob frame_job(const GatherArgs& a, int parts, size_t fbytes) {
+  FrameJob j;
+  int bid = blockIdx.x;
+  j.part = bid % parts; bid /= parts;
+  j.i = bid % a.batch; bid /= a.batch;
+  j.cam = bid % a.n_cam;
+  j.which = bid / a.n_cam;
+  j.src = source_frame(a, j.which, j.cam, j.i, fbytes);
+  const int2 c = crop_offset(j.which == 0 ? a.crop_obs : a.crop_next, j.i);
+  j.sy = c.x - 4;
+  j.sx = c.y - 4;
+  return j;
+}
 
 // Shift one output row out of an LDS-staged source row.  rowb = W*C bytes (multiple of 16).
 // Interior 16-byte chunks: 5 aligned dword LDS reads + v_alignbyte; edge chunks (where the shift
@@ -190,16 +217,22 @@ __device__ __forceinline__ uint4 shifted_chunk(const uint8_t* srow, int q, int s
   return r;
 }
 
-// record gather: one thread per (sample, float of the record)
-__device__ __forceinline__ void gather_record(const GatherArgs& a, int e) {
+// the record of sample i
+__device__ __forceinline__ const float* record_row(const GatherArgs& a, int i) {
+  const int buf = (i < a.count0) ? 0 : 1;
+  return a.rec[buf] + (size_t)a.idx[buf][buf == 0 ? i : i - a.count0] * a.rec_len;
+}
+__device__ __forceinline__ const float* record_row(const PackedArgs& a, int i) { return a.rec + (size_t)a.idx[i] * a.rec_len; }
+
+// record gather: one thread per (sample, float of the record).  S = floats of a state; next states go to out_next_state
+template <class Args>
+__device__ __forceinline__ void gather_record(const Args& a, int e, int S, float* out_next_state) {
   const int i = e / a.rec_len, f = e - i * a.rec_len;
   if (i >= a.batch) return;
-  const int buf = (i < a.count0) ? 0 : 1;
-  const int64_t slot = a.idx[buf][buf == 0 ? i : i - a.count0];
-  const float v = a.rec[buf][(size_t)slot * a.rec_len + f];
-  const int S = a.S, A = a.A;
+  const float v = record_row(a, i)[f];
+  const int A = a.A;
   if (f < S) a.out_state[(size_t)i * S + f] = v;
-  else if (f < 2 * S) a.out_state[((size_t)a.batch + i) * S + (f - S)] = v;
+  else if (f < 2 * S) out_next_state[(size_t)i * S + (f - S)] = v;
   else if (f < 2 * S + A) a.out_action[(size_t)i * A + (f - 2 * S)] = v;
   else if (f == 2 * S + A) a.out_reward[i] = v;
   else if (f == 2 * S + A + 1) a.out_mask[i] = v;
@@ -213,49 +246,27 @@ __global__ __launch_bounds__(256) void gather_crop_kernel(GatherArgs a) {
   const int rowb = a.W * a.C;        // bytes per row
   const int lds_stride = rowb + 16;  // 16B pad: the 5th dword of the last chunk stays in bounds
   if ((int)blockIdx.x < a.n_frame_blocks) {
-    const int chunks = (a.H + kRowsPerBlock - 1) / kRowsPerBlock;
-    int bid = blockIdx.x;
-    const int rc = bid % chunks;
-    bid /= chunks;
-    const int i = bid % a.batch;
-    bid /= a.batch;
-    const int cam = bid % a.n_cam;
-    const int which = bid / a.n_cam;  // 0 = observation frame (slot idx-1), 1 = next frame (slot idx)
-    const int buf = (i < a.count0) ? 0 : 1;
     const size_t fbytes = (size_t)a.H * rowb;
-    const uint8_t* src;
-    if (a.from_packed) {
-      src = a.packed[cam] + ((size_t)i * 2 + which) * fbytes;
-    } else {
-      // window start = idx - T; numpy wraps a negative window index to cap - T + (idx - T)
-      // (reference quirk for a valid slot 0, see oracle/replay_oracle.py gather()).  T == 1 here.
-      int64_t start = a.idx[buf][buf == 0 ? i : i - a.count0] - 1;
-      if (start < 0) start += a.cap[buf] - 1;
-      src = a.frames[buf][cam] + (size_t)(start + which) * fbytes;
-    }
-    const int32_t* crop = which == 0 ? a.crop_obs : a.crop_next;
-    const int dy = crop ? crop[2 * i] : 4, dx = crop ? crop[2 * i + 1] : 4;
-    const int sy = dy - 4, sx = dx - 4;
-    const int h0 = rc * kRowsPerBlock;
+    const FrameJob j = frame_job(a, (a.H + kRowsPerBlock - 1) / kRowsPerBlock, fbytes);
+    const int h0 = j.part * kRowsPerBlock;
     const int nrows = min(kRowsPerBlock, a.H - h0);
     const int vec_per_row = rowb / 16;
     // stage: LDS row r <- source row clamp(h0 + r + sy)
     for (int v = tid; v < nrows * vec_per_row; v += 256) {
       const int r = v / vec_per_row, q = v - r * vec_per_row;
-      const int sh = min(max(h0 + r + sy, 0), a.H - 1);
-      const uint4 val = *reinterpret_cast<const uint4*>(src + (size_t)sh * rowb + q * 16);
+      const int sh = min(max(h0 + r + j.sy, 0), a.H - 1);
+      const uint4 val = *reinterpret_cast<const uint4*>(j.src + (size_t)sh * rowb + q * 16);
       *reinterpret_cast<uint4*>(lds + r * lds_stride + q * 16) = val;
     }
     __syncthreads();
-    uint8_t* dst = a.out_frames + (((size_t)which * a.n_cam + cam) * a.batch + i) * fbytes +
-                   (size_t)h0 * rowb;
+    uint8_t* dst = a.out_frames + (((size_t)j.which * a.n_cam + j.cam) * a.batch + j.i) * fbytes + (size_t)h0 * rowb;
     for (int v = tid; v < nrows * vec_per_row; v += 256) {
       const int r = v / vec_per_row, q = v - r * vec_per_row;
-      const uint4 val = shifted_chunk<CT>(lds + r * lds_stride, q, sx, a.W, a.C);
+      const uint4 val = shifted_chunk<CT>(lds + r * lds_stride, q, j.sx, a.W, a.C);
       *reinterpret_cast<uint4*>(dst + (size_t)r * rowb + q * 16) = val;
     }
   } else if (!a.from_packed) {
-    gather_record(a, (blockIdx.x - a.n_frame_blocks) * 256 + tid);
+    gather_record(a, (blockIdx.x - a.n_frame_blocks) * 256 + tid, a.S, a.out_state + (size_t)a.batch * a.S);
   }
 }
 
@@ -275,28 +286,11 @@ __global__ __launch_bounds__(256) void gather_crop_rgb_kernel(GatherArgs a) {
   const int vec_per_row = rowb >> 4;
   const int nvec = a.H * vec_per_row;
   if ((int)blockIdx.x < a.n_frame_blocks) {
-    const int parts = (nvec + 256 * kDirectVec - 1) / (256 * kDirectVec);
-    int bid = blockIdx.x;
-    const int part = bid % parts;
-    bid /= parts;
-    const int i = bid % a.batch;
-    bid /= a.batch;
-    const int cam = bid % a.n_cam;
-    const int which = bid / a.n_cam;
-    const int buf = (i < a.count0) ? 0 : 1;
     const size_t fbytes = (size_t)a.H * rowb;
-    const uint8_t* src;
-    if (a.from_packed) {
-      src = a.packed[cam] + ((size_t)i * 2 + which) * fbytes;
-    } else {
-      int64_t start = a.idx[buf][buf == 0 ? i : i - a.count0] - 1;
-      if (start < 0) start += a.cap[buf] - 1;  // numpy negative window index (reference quirk, see gather_crop_kernel)
-      src = a.frames[buf][cam] + (size_t)(start + which) * fbytes;
-    }
-    const int32_t* crop = which == 0 ? a.crop_obs : a.crop_next;
-    const int dy = crop ? crop[2 * i] : 4, dx = crop ? crop[2 * i + 1] : 4;
-    const int sy = dy - 4, sx3 = (dx - 4) * 3;
-    uint8_t* dst = a.out_frames + (((size_t)which * a.n_cam + cam) * a.batch + i) * fbytes;
+    const FrameJob job = frame_job(a, (nvec + 256 * kDirectVec - 1) / (256 * kDirectVec), fbytes);
+    const int part = job.part, sy = job.sy, sx3 = job.sx * 3;
+    const uint8_t* src = job.src;
+    uint8_t* dst = a.out_frames + (((size_t)job.which * a.n_cam + job.cam) * a.batch + job.i) * fbytes;
     unsigned __int128 val[kDirectVec];
     int shl[kDirectVec], shr[kDirectVec];
 #pragma unroll
@@ -341,22 +335,9 @@ __global__ __launch_bounds__(256) void gather_crop_rgb_kernel(GatherArgs a) {
       }
     }
   } else if (!a.from_packed) {
-    gather_record(a, (blockIdx.x - a.n_frame_blocks) * 256 + tid);
+    gather_record(a, (blockIdx.x - a.n_frame_blocks) * 256 + tid, a.S, a.out_state + (size_t)a.batch * a.S);
   }
 }
-
-struct PackedArgs {
-  const uint8_t* frames[SERL_MAX_CAMS];
-  const float* rec;
-  const int64_t* idx;
-  int batch, n_cam, T, TS, A, rec_len;
-  int64_t cap;
-  size_t fbytes;
-  uint8_t* out_frames[SERL_MAX_CAMS];  // [batch][T+1][fbytes]
-  float *out_state, *out_next_state, *out_action, *out_reward, *out_mask;
-  uint8_t* out_done;
-  int n_frame_blocks, vec_per_block;
-};
 
 // sample(pack_obs_and_next_obs=True): straight 16B-vector copy of slots idx-T..idx per camera
 __global__ __launch_bounds__(256) void gather_packed_kernel(PackedArgs a) {
@@ -370,26 +351,13 @@ __global__ __launch_bounds__(256) void gather_packed_kernel(PackedArgs a) {
     bid /= (a.T + 1);
     const int i = bid % a.batch;
     const int cam = bid / a.batch;
-    int64_t start = a.idx[i] - a.T;
-    if (start < 0) start += a.cap - a.T;  // numpy negative window index (reference quirk)
-    const int64_t slot = start + t;
-    const uint4* src = reinterpret_cast<const uint4*>(a.frames[cam] + (size_t)slot * a.fbytes);
+    const uint4* src = reinterpret_cast<const uint4*>(window_frame(a.frames[cam], a.idx, i, a.T, a.cap, t, a.fbytes));
     uint4* dst = reinterpret_cast<uint4*>(a.out_frames[cam] + ((size_t)i * (a.T + 1) + t) * a.fbytes);
     const int nvec = (int)(a.fbytes / 16);
     const int v0 = part * a.vec_per_block;
     for (int v = v0 + tid; v < min(v0 + a.vec_per_block, nvec); v += 256) dst[v] = src[v];
   } else {
-    const int e = (blockIdx.x - a.n_frame_blocks) * 256 + tid;
-    const int i = e / a.rec_len, f = e - i * a.rec_len;
-    if (i >= a.batch) return;
-    const float v = a.rec[(size_t)a.idx[i] * a.rec_len + f];
-    const int S = a.TS, A = a.A;
-    if (f < S) a.out_state[(size_t)i * S + f] = v;
-    else if (f < 2 * S) a.out_next_state[(size_t)i * S + (f - S)] = v;
-    else if (f < 2 * S + A) a.out_action[(size_t)i * A + (f - 2 * S)] = v;
-    else if (f == 2 * S + A) a.out_reward[i] = v;
-    else if (f == 2 * S + A + 1) a.out_mask[i] = v;
-    else a.out_done[i] = (uint8_t)(v != 0.0f);
+    gather_record(a, (blockIdx.x - a.n_frame_blocks) * 256 + tid, a.TS, a.out_next_state);
   }
 }
 
@@ -447,11 +415,8 @@ static int order_after_inserts(serl_rb* rb, hipStream_t stream) {
 
 // writes slot `i` (record + one frame per camera) host -> HBM through the pinned ring.  Caller holds rb->mu.
 static int write_slot(serl_rb* rb, int64_t i, const uint8_t* const* frames_host, const float* rec) {
-  std::memcpy(&rb->rec_host[(size_t)i * rb->rec_len], rec, sizeof(float) * rb->rec_len);
-  const int s = rb->ins_next;
-  rb->ins_next = (s + 1) % kInsRing;
-  if (rb->ins_used[s]) SERL_HIP(hipEventSynchronize(rb->ins_done[s]));  // ring wrapped: that copy is long done
-  uint8_t* h = rb->ins_host + (size_t)s * rb->ins_slot_bytes;
+  RC(rb->ins.acquire());
+  uint8_t* h = rb->ins.h();
   const size_t rec_bytes = sizeof(float) * rb->rec_len;
   std::memcpy(h, rec, rec_bytes);
   const size_t f0 = (rec_bytes + 255) & ~(size_t)255;
@@ -460,29 +425,17 @@ static int write_slot(serl_rb* rb, int64_t i, const uint8_t* const* frames_host,
   for (int c = 0; c < rb->n_cam; ++c)
     SERL_HIP(hipMemcpyAsync(rb->frames[c] + (size_t)i * rb->frame_bytes, h + f0 + (size_t)c * rb->frame_bytes,
                             rb->frame_bytes, hipMemcpyHostToDevice, rb->copy_stream));
-  SERL_HIP(hipEventRecord(rb->ins_done[s], rb->copy_stream));
-  rb->ins_used[s] = true;
-  rb->insert_index = (i + 1) % rb->cap;
-  rb->insert_count += 1;
-  rb->size = rb->size + 1 < rb->cap ? rb->size + 1 : rb->cap;
-  return SERL_OK;
+  return rb->ins.mark(rb->copy_stream);
 }
 
-// device->device copy of slot src to the write head (wrap re-insert,
-// memory_efficient_replay_buffer.py:54-59).  Caller holds rb->mu.
-static int copy_slot_to_head(serl_rb* rb, int64_t src) {
-  const int64_t i = rb->insert_index;
-  std::memmove(&rb->rec_host[(size_t)i * rb->rec_len], &rb->rec_host[(size_t)src * rb->rec_len],
-               sizeof(float) * rb->rec_len);
+// device->device copy of slot src to slot i (wrap re-insert, memory_efficient_replay_buffer.py:54-59).  Caller holds rb->mu.
+static int copy_slot(serl_rb* rb, int64_t i, int64_t src) {
   SERL_HIP(hipMemcpyAsync(rb->rec + (size_t)i * rb->rec_len, rb->rec + (size_t)src * rb->rec_len,
                           sizeof(float) * rb->rec_len, hipMemcpyDeviceToDevice, rb->copy_stream));
   for (int c = 0; c < rb->n_cam; ++c)
     SERL_HIP(hipMemcpyAsync(rb->frames[c] + (size_t)i * rb->frame_bytes,
                             rb->frames[c] + (size_t)src * rb->frame_bytes, rb->frame_bytes,
                             hipMemcpyDeviceToDevice, rb->copy_stream));
-  rb->insert_index = (i + 1) % rb->cap;
-  rb->insert_count += 1;
-  rb->size = rb->size + 1 < rb->cap ? rb->size + 1 : rb->cap;
   return SERL_OK;
 }
 
@@ -493,33 +446,39 @@ static int finish_insert(serl_rb* rb) {
   return SERL_OK;
 }
 
-// reserve a staging slot, copy `bytes` of host parameters into pinned memory and enqueue the H2D
-// copy on `stream`.  Returns the device address of the slot.
-static int stage_params(serl_rb* rb, const void* const* srcs, const size_t* sizes, int n,
+// lays `n` host sources out at 16-byte alignment in a slot of `ring` (a NULL source keeps its place and is not copied) and
+// enqueues ONE H2D copy of the slot on `stream`; *dev_out is the slot's device address, offsets[k] where source k lies in it.
+// A total beyond the slot is refused before a slot is taken or a byte copied.  The caller launches, then ring.mark(stream).
+static int stage_params(StageRing& ring, const void* const* srcs, const size_t* sizes, int n,
                         hipStream_t stream, uint8_t** dev_out, size_t* offsets) {
-  const int s = rb->stage_next;
-  rb->stage_next = (s + 1) % kRing;
-  if (rb->stage_used[s]) SERL_HIP(hipEventSynchronize(rb->stage_done[s]));
-  uint8_t* h = rb->stage_host + (size_t)s * rb->stage_slot_bytes;
-  size_t off = 0;
+  size_t total = 0;
   for (int k = 0; k < n; ++k) {
-    offsets[k] = off;
-    if (srcs[k]) std::memcpy(h + off, srcs[k], sizes[k]);
-    off += (sizes[k] + 15) & ~(size_t)15;
-    if (off > rb->stage_slot_bytes) {
-      set_error("batch too large for the staging slot (%zu > %zu bytes)", off, rb->stage_slot_bytes);
-      return SERL_ERR_INVALID;
-    }
+    offsets[k] = total;
+    total += (sizes[k] + 15) & ~(size_t)15;
   }
-  uint8_t* d = rb->stage_dev + (size_t)s * rb->stage_slot_bytes;
+  SERL_REQUIRE(total <= ring.slot_bytes, "batch too large for the staging slot (%zu > %zu bytes)", total, ring.slot_bytes);
+  RC(ring.acquire());
+  for (int k = 0; k < n; ++k)
+    if (srcs[k]) std::memcpy(ring.h() + offsets[k], srcs[k], sizes[k]);
   // (round 5: letting the gather kernel read the pinned host slot itself -- no copy command on the stream -- left the step
   //  unchanged, 2.5225 / 2.5198 -> 2.5221 / 2.5239 ms: the idle time in front of a pass is not the copy's, profiles/README.md)
-  SERL_HIP(hipMemcpyAsync(d, h, off, hipMemcpyHostToDevice, stream));
-  *dev_out = d;
-  rb->stage_used[s] = true;
-  return s;
+  SERL_HIP(hipMemcpyAsync(ring.d(), ring.h(), total, hipMemcpyHostToDevice, stream));
+  *dev_out = ring.d();
+  return SERL_OK;
 }
 
+// what a gather checks of its indices: in range, and stale ones re-drawn in place (ReplayIndex::revalidate).  Caller holds rb->mu.
+static int check_and_revalidate(serl_rb* rb, int64_t* idx, int n) {
+  int bad = 0;
+  if (rb->ix.check_indices(idx, n, &bad) != IndexStatus::kOk) {
+    set_error("index %lld out of range [0,%lld)", (long long)idx[bad], (long long)rb->ix.size);
+    return SERL_ERR_INVALID;
+  }
+  const IndexStatus st = rb->ix.revalidate(idx, n);
+  SERL_REQUIRE(st != IndexStatus::kNotSeeded, "replay buffer RNG not seeded");
+  SERL_REQUIRE(st != IndexStatus::kRedrawExhausted, "no valid slot found while re-drawing a stale index");
+  return SERL_OK;
+}
 
 // ---------------------------------------------------------------------------------------------
 // snapshot export / import: HBM <-> ordinary host memory in chunks through two pinned buffers on the copy stream
@@ -561,19 +520,9 @@ static int staged_h2d(serl_rb* rb, uint8_t* dev_dst, const uint8_t* src, size_t 
   }
   return SERL_OK;
 }
-// The ring range [slot_begin, slot_begin + n_slots) mod cap as at most two runs of consecutive slots: (first slot, slots, position
-// of the run in the caller's arrays).
-struct SlotRun { int64_t slot, n, at; };
-static int slot_runs(const serl_rb* rb, int64_t slot_begin, int64_t n_slots, SlotRun runs[2]) {
-  const int64_t head = n_slots < rb->cap - slot_begin ? n_slots : rb->cap - slot_begin;
-  int k = 0;
-  if (head > 0) runs[k++] = SlotRun{slot_begin, head, 0};
-  if (n_slots - head > 0) runs[k++] = SlotRun{0, n_slots - head, head};
-  return k;
-}
 static int check_slot_range(const serl_rb* rb, int64_t slot_begin, int64_t n_slots, const uint8_t* const* frames, const void* records) {
-  SERL_REQUIRE(slot_begin >= 0 && slot_begin < rb->cap, "slot_begin %lld not in [0,%lld)", (long long)slot_begin, (long long)rb->cap);
-  SERL_REQUIRE(n_slots >= 0 && n_slots <= rb->cap, "n_slots %lld not in [0,%lld]", (long long)n_slots, (long long)rb->cap);
+  SERL_REQUIRE(slot_begin >= 0 && slot_begin < rb->ix.cap, "slot_begin %lld not in [0,%lld)", (long long)slot_begin, (long long)rb->ix.cap);
+  SERL_REQUIRE(n_slots >= 0 && n_slots <= rb->ix.cap, "n_slots %lld not in [0,%lld]", (long long)n_slots, (long long)rb->ix.cap);
   if (n_slots == 0) return SERL_OK;
   SERL_REQUIRE(records && (rb->n_cam == 0 || frames), "NULL argument");
   for (int c = 0; c < rb->n_cam; ++c) SERL_REQUIRE(frames[c], "frames[%d] is NULL", c);
@@ -584,7 +533,7 @@ static int export_copies(serl_rb* rb, int64_t slot_begin, int64_t n_slots, uint8
   SERL_HIP(hipSetDevice(rb->device));
   SERL_HIP(hipEventSynchronize(rb->last_insert));  // the copies of the last insert (the copy stream orders the reads behind them too)
   SlotRun runs[2];
-  const int nr = slot_runs(rb, slot_begin, n_slots, runs);
+  const int nr = rb->ix.slot_runs(slot_begin, n_slots, runs);
   const size_t rec_bytes = sizeof(float) * rb->rec_len;
   for (int r = 0; r < nr; ++r) {
     RC(staged_d2h(rb, reinterpret_cast<uint8_t*>(host_records) + (size_t)runs[r].at * rec_bytes,
@@ -621,21 +570,19 @@ int serl_rb_create(int device, int64_t capacity, int n_cam, int H, int W, int C,
   SERL_REQUIRE(n_cam == 0 || ((size_t)W * C) % 16 == 0, "W*C (%d) must be a multiple of 16 bytes", W * C);
   SERL_REQUIRE((n_cam == 0 || H >= 1) && state_dim >= 1 && act_dim >= 1, "bad dims");
   SERL_HIP(hipSetDevice(device));
-  serl_rb* rb = new serl_rb();
+  // one owner until the end: every failure below frees what was built (serl_rb_destroy tolerates a half-built store)
+  std::unique_ptr<serl_rb, int (*)(serl_rb*)> rb(new serl_rb(), serl_rb_destroy);
   rb->device = device;
-  rb->cap = capacity;
   rb->n_cam = n_cam;
   rb->H = H; rb->W = W; rb->C = C; rb->T = num_stack; rb->S = state_dim; rb->A = act_dim;
   rb->rec_len = 2 * num_stack * state_dim + act_dim + 3;
   rb->frame_bytes = (size_t)H * W * C;
-  rb->valid.assign((size_t)capacity, 0);
-  rb->rec_host.assign((size_t)capacity * rb->rec_len, 0.0f);
+  rb->ix.init(capacity, n_cam > 0, num_stack);
   for (int c = 0; c < n_cam; ++c) {
     hipError_t e = hipMalloc((void**)&rb->frames[c], (size_t)capacity * rb->frame_bytes);
     if (e != hipSuccess) {
       set_error("hipMalloc of %zu bytes for camera %d failed: %s", (size_t)capacity * rb->frame_bytes,
                 c, hipGetErrorString(e));
-      serl_rb_destroy(rb);
       return SERL_ERR_HIP;
     }
   }
@@ -643,15 +590,9 @@ int serl_rb_create(int device, int64_t capacity, int n_cam, int H, int W, int C,
   SERL_HIP(hipStreamCreateWithFlags(&rb->copy_stream, hipStreamNonBlocking));
   for (int k = 0; k < serl_rb::kGatherStreams; ++k) SERL_HIP(hipEventCreateWithFlags(&rb->gather_ev[k], hipEventDisableTiming));
   SERL_HIP(hipEventCreateWithFlags(&rb->last_insert, hipEventDisableTiming));
-  rb->ins_slot_bytes = ((sizeof(float) * rb->rec_len + 255) & ~(size_t)255) + (size_t)n_cam * rb->frame_bytes;
-  SERL_HIP(hipHostMalloc((void**)&rb->ins_host, rb->ins_slot_bytes * kInsRing, hipHostMallocDefault));
-  for (int s = 0; s < kInsRing; ++s) SERL_HIP(hipEventCreateWithFlags(&rb->ins_done[s], hipEventDisableTiming));
-  rb->stage_slot_bytes = 1 << 16;  // idx (8B) + 2 crops (16B) per sample: up to ~2700 samples
-  SERL_HIP(hipHostMalloc((void**)&rb->stage_host, rb->stage_slot_bytes * kRing, hipHostMallocDefault));
-  SERL_HIP(hipMalloc((void**)&rb->stage_dev, rb->stage_slot_bytes * kRing));
-  for (int s = 0; s < kRing; ++s)
-    SERL_HIP(hipEventCreateWithFlags(&rb->stage_done[s], hipEventDisableTiming));
-  *out = rb;
+  RC(rb->ins.init(kInsRing, ((sizeof(float) * rb->rec_len + 255) & ~(size_t)255) + (size_t)n_cam * rb->frame_bytes, false));
+  RC(rb->stage.init(kRing, 1 << 16, true));  // idx (8B) + 2 crops (16B) per sample: up to ~2700 samples
+  *out = rb.release();
   return SERL_OK;
 }
 
@@ -662,19 +603,14 @@ int serl_rb_destroy(serl_rb* rb) {
   for (int c = 0; c < SERL_MAX_CAMS; ++c)
     if (rb->frames[c]) (void)hipFree(rb->frames[c]);
   if (rb->rec) (void)hipFree(rb->rec);
-  if (rb->stage_host) (void)hipHostFree(rb->stage_host);
-  if (rb->stage_dev) (void)hipFree(rb->stage_dev);
-  for (int s = 0; s < kRing; ++s)
-    if (rb->stage_done[s]) (void)hipEventDestroy(rb->stage_done[s]);
+  rb->stage.destroy();
   for (int k = 0; k < serl_rb::kGatherStreams; ++k)
     if (rb->gather_ev[k]) (void)hipEventDestroy(rb->gather_ev[k]);
   if (rb->last_insert) (void)hipEventDestroy(rb->last_insert);
-  if (rb->ins_host) (void)hipHostFree(rb->ins_host);
+  rb->ins.destroy();
   if (rb->xfer_host) (void)hipHostFree(rb->xfer_host);
   for (int k = 0; k < 2; ++k)
     if (rb->xfer_done[k]) (void)hipEventDestroy(rb->xfer_done[k]);
-  for (int s = 0; s < kInsRing; ++s)
-    if (rb->ins_done[s]) (void)hipEventDestroy(rb->ins_done[s]);
   if (rb->copy_stream) (void)hipStreamDestroy(rb->copy_stream);
   delete rb;
   return SERL_OK;
@@ -684,23 +620,17 @@ int serl_rb_seed(serl_rb* rb, uint64_t state_hi, uint64_t state_lo, uint64_t inc
                  uint64_t inc_lo, int has_uint32, uint32_t uinteger) {
   SERL_REQUIRE(rb, "rb is NULL");
   std::lock_guard<std::mutex> g(rb->mu);
-  rb->rng.state = ((unsigned __int128)state_hi << 64) | state_lo;
-  rb->rng.inc = ((unsigned __int128)inc_hi << 64) | inc_lo;
-  rb->rng.has_uint32 = has_uint32;
-  rb->rng.uinteger = uinteger;
-  rb->rng.seeded = true;
+  const uint64_t words[4] = {state_hi, state_lo, inc_hi, inc_lo};
+  rb->ix.rng.set(words, has_uint32, uinteger);
   return SERL_OK;
 }
 
 int serl_rb_rng_state(serl_rb* rb, uint64_t out[4], int* has_uint32, uint32_t* uinteger) {
   SERL_REQUIRE(rb && out && has_uint32 && uinteger, "NULL argument");
   std::lock_guard<std::mutex> g(rb->mu);
-  out[0] = (uint64_t)(rb->rng.state >> 64);
-  out[1] = (uint64_t)rb->rng.state;
-  out[2] = (uint64_t)(rb->rng.inc >> 64);
-  out[3] = (uint64_t)rb->rng.inc;
-  *has_uint32 = rb->rng.has_uint32;
-  *uinteger = rb->rng.uinteger;
+  rb->ix.rng.get(out);
+  *has_uint32 = rb->ix.rng.has_uint32;
+  *uinteger = rb->ix.rng.uinteger;
   return SERL_OK;
 }
 
@@ -712,28 +642,8 @@ int serl_rb_insert(serl_rb* rb, const uint8_t* const* obs_frames, const uint8_t*
   std::unique_lock<std::mutex> g(rb->mu);
   rb->idle.wait(g, [rb] { return !rb->busy; });  // a snapshot export is reading the slots
   SERL_HIP(hipSetDevice(rb->device));
-  int rc = order_after_gathers(rb);  // never overwrite a slot an in-flight gather may still read
-  if (rc) return rc;
-  const int T = rb->T, TS = rb->T * rb->S;
-  if (rb->n_cam == 0) {  // ReplayBuffer.insert (replay_buffer.py:71-75): write at the head, advance, no bookkeeping
-    std::vector<float> r0(rb->rec_len);
-    std::memcpy(r0.data(), state, sizeof(float) * TS);
-    std::memcpy(r0.data() + TS, next_state, sizeof(float) * TS);
-    std::memcpy(r0.data() + 2 * TS, action, sizeof(float) * rb->A);
-    r0[2 * TS + rb->A] = reward;
-    r0[2 * TS + rb->A + 1] = mask;
-    r0[2 * TS + rb->A + 2] = done ? 1.0f : 0.0f;
-    rb->valid[rb->insert_index] = 1;
-    if ((rc = write_slot(rb, rb->insert_index, nullptr, r0.data()))) return rc;
-    return finish_insert(rb);
-  }
-  // wrap: re-insert the last T slots at the head as invalid (py:54-59)
-  if (rb->insert_index == 0 && rb->cap == rb->size && !rb->first) {
-    for (int64_t src = rb->size - T; src < rb->size; ++src) {
-      rb->valid[rb->insert_index] = 0;
-      if ((rc = copy_slot_to_head(rb, src))) return rc;
-    }
-  }
+  RC(order_after_gathers(rb));  // never overwrite a slot an in-flight gather may still read
+  const int TS = rb->T * rb->S;
   std::vector<float> rec(rb->rec_len);
   std::memcpy(rec.data(), state, sizeof(float) * TS);
   std::memcpy(rec.data() + TS, next_state, sizeof(float) * TS);
@@ -742,40 +652,37 @@ int serl_rb_insert(serl_rb* rb, const uint8_t* const* obs_frames, const uint8_t*
   rec[2 * TS + rb->A + 1] = mask;
   rec[2 * TS + rb->A + 2] = done ? 1.0f : 0.0f;
   const uint8_t* fr[SERL_MAX_CAMS];
-  if (rb->first) {  // episode start: T invalid "first-frame" slots holding the obs frames (py:71-77)
-    for (int t = 0; t < T; ++t) {
-      for (int c = 0; c < rb->n_cam; ++c) fr[c] = obs_frames[c] + (size_t)t * rb->frame_bytes;
-      rb->valid[rb->insert_index] = 0;
-      if ((rc = write_slot(rb, rb->insert_index, fr, rec.data()))) return rc;
+  for (const SlotOp& op : rb->ix.plan_insert(done != 0)) {
+    if (op.kind == SlotOp::kCopy) {
+      RC(copy_slot(rb, op.dst, op.arg));
+    } else {
+      const uint8_t* const* from = op.kind == SlotOp::kObsFrame ? obs_frames : next_frames;
+      for (int c = 0; c < rb->n_cam; ++c) fr[c] = from[c] + (size_t)op.arg * rb->frame_bytes;
+      RC(write_slot(rb, op.dst, fr, rec.data()));
     }
   }
-  for (int c = 0; c < rb->n_cam; ++c) fr[c] = next_frames[c] + (size_t)(T - 1) * rb->frame_bytes;
-  rb->first = done != 0;
-  rb->valid[rb->insert_index] = 1;
-  if ((rc = write_slot(rb, rb->insert_index, fr, rec.data()))) return rc;
-  for (int t = 0; t < T; ++t) rb->valid[(rb->insert_index + t) % rb->size] = 0;  // py:87-89
   return finish_insert(rb);
 }
 
 int64_t serl_rb_len(serl_rb* rb) {
   if (!rb) return -1;
   std::lock_guard<std::mutex> g(rb->mu);
-  return rb->size;
+  return rb->ix.size;
 }
 int64_t serl_rb_insert_index(serl_rb* rb) {
   if (!rb) return -1;
   std::lock_guard<std::mutex> g(rb->mu);
-  return rb->insert_index;
+  return rb->ix.insert_index;
 }
 int64_t serl_rb_insert_count(serl_rb* rb) {
   if (!rb) return -1;
   std::lock_guard<std::mutex> g(rb->mu);
-  return rb->insert_count;
+  return rb->ix.insert_count;
 }
 int serl_rb_valid_mask(serl_rb* rb, uint8_t* host_out) {
   SERL_REQUIRE(rb && host_out, "NULL argument");
   std::lock_guard<std::mutex> g(rb->mu);
-  std::memcpy(host_out, rb->valid.data(), (size_t)rb->cap);
+  std::memcpy(host_out, rb->ix.valid.data(), (size_t)rb->ix.cap);
   return SERL_OK;
 }
 
@@ -783,37 +690,33 @@ int serl_rb_export_meta(serl_rb* rb, serl_rb_meta* out) {
   SERL_REQUIRE(rb && out, "NULL argument");
   std::lock_guard<std::mutex> g(rb->mu);
   std::memset(out, 0, sizeof(*out));
-  out->capacity = rb->cap;
+  out->capacity = rb->ix.cap;
   out->n_cam = rb->n_cam; out->H = rb->H; out->W = rb->W; out->C = rb->C; out->T = rb->T; out->S = rb->S; out->A = rb->A;
   out->rec_len = rb->rec_len;
-  out->size = rb->size; out->insert_index = rb->insert_index; out->insert_count = rb->insert_count;
-  out->first = rb->first ? 1 : 0;
-  out->rng_seeded = rb->rng.seeded ? 1 : 0;
-  out->rng_state_inc[0] = (uint64_t)(rb->rng.state >> 64);
-  out->rng_state_inc[1] = (uint64_t)rb->rng.state;
-  out->rng_state_inc[2] = (uint64_t)(rb->rng.inc >> 64);
-  out->rng_state_inc[3] = (uint64_t)rb->rng.inc;
-  out->rng_has_uint32 = rb->rng.has_uint32;
-  out->rng_uinteger = rb->rng.uinteger;
+  out->size = rb->ix.size; out->insert_index = rb->ix.insert_index; out->insert_count = rb->ix.insert_count;
+  out->first = rb->ix.first ? 1 : 0;
+  out->rng_seeded = rb->ix.rng.seeded ? 1 : 0;
+  rb->ix.rng.get(out->rng_state_inc);
+  out->rng_has_uint32 = rb->ix.rng.has_uint32;
+  out->rng_uinteger = rb->ix.rng.uinteger;
   return SERL_OK;
 }
 
 int serl_rb_export_slots(serl_rb* rb, int64_t slot_begin, int64_t n_slots, uint8_t* const* host_frames, float* host_records,
                          uint8_t* host_valid) {
   SERL_REQUIRE(rb, "rb is NULL");
-  int rc = check_slot_range(rb, slot_begin, n_slots, host_frames, host_records);
-  if (rc) return rc;
+  RC(check_slot_range(rb, slot_begin, n_slots, host_frames, host_records));
   {
     std::unique_lock<std::mutex> g(rb->mu);
     rb->idle.wait(g, [rb] { return !rb->busy; });
     SERL_HIP(hipSetDevice(rb->device));
-    if ((rc = xfer_init(rb))) return rc;
+    RC(xfer_init(rb));
     // the mask belongs to the same instant as the slots: no insert runs between here and the end of the copies
-    if (host_valid) std::memcpy(host_valid, rb->valid.data(), (size_t)rb->cap);
+    if (host_valid) std::memcpy(host_valid, rb->ix.valid.data(), (size_t)rb->ix.cap);
     rb->busy = true;
   }
   // mutex released: sample_indices and gathers go on; inserts wait on `idle`
-  rc = export_copies(rb, slot_begin, n_slots, host_frames, host_records);
+  const int rc = export_copies(rb, slot_begin, n_slots, host_frames, host_records);
   {
     std::lock_guard<std::mutex> g(rb->mu);
     rb->busy = false;
@@ -826,51 +729,38 @@ int serl_rb_import_meta(serl_rb* rb, const serl_rb_meta* m) {
   SERL_REQUIRE(rb && m, "NULL argument");
   std::unique_lock<std::mutex> g(rb->mu);
   rb->idle.wait(g, [rb] { return !rb->busy; });
-  SERL_REQUIRE(m->capacity == rb->cap && m->n_cam == rb->n_cam && m->H == rb->H && m->W == rb->W && m->C == rb->C && m->T == rb->T &&
+  SERL_REQUIRE(m->capacity == rb->ix.cap && m->n_cam == rb->n_cam && m->H == rb->H && m->W == rb->W && m->C == rb->C && m->T == rb->T &&
                    m->S == rb->S && m->A == rb->A && m->rec_len == rb->rec_len,
                "snapshot geometry (capacity %lld, %d cameras %dx%dx%d, T %d, S %d, A %d) is not the store's (capacity %lld, %d cameras "
-               "%dx%dx%d, T %d, S %d, A %d)", (long long)m->capacity, m->n_cam, m->H, m->W, m->C, m->T, m->S, m->A, (long long)rb->cap,
+               "%dx%dx%d, T %d, S %d, A %d)", (long long)m->capacity, m->n_cam, m->H, m->W, m->C, m->T, m->S, m->A, (long long)rb->ix.cap,
                rb->n_cam, rb->H, rb->W, rb->C, rb->T, rb->S, rb->A);
-  SERL_REQUIRE(m->insert_count >= 0 && m->insert_index == m->insert_count % rb->cap &&
-                   m->size == (m->insert_count < rb->cap ? m->insert_count : rb->cap),
+  SERL_REQUIRE(rb->ix.restore(m->size, m->insert_index, m->insert_count, m->first != 0) == IndexStatus::kOk,
                "inconsistent bookkeeping: size %lld, insert_index %lld, insert_count %lld at capacity %lld", (long long)m->size,
-               (long long)m->insert_index, (long long)m->insert_count, (long long)rb->cap);
-  rb->size = m->size;
-  rb->insert_index = m->insert_index;
-  rb->insert_count = m->insert_count;
-  rb->first = m->first != 0;
-  if (m->rng_seeded) {
-    rb->rng.state = ((unsigned __int128)m->rng_state_inc[0] << 64) | m->rng_state_inc[1];
-    rb->rng.inc = ((unsigned __int128)m->rng_state_inc[2] << 64) | m->rng_state_inc[3];
-    rb->rng.has_uint32 = m->rng_has_uint32;
-    rb->rng.uinteger = m->rng_uinteger;
-    rb->rng.seeded = true;
-  }
+               (long long)m->insert_index, (long long)m->insert_count, (long long)rb->ix.cap);
+  if (m->rng_seeded) rb->ix.rng.set(m->rng_state_inc, m->rng_has_uint32, m->rng_uinteger);
   return SERL_OK;
 }
 
 int serl_rb_import_slots(serl_rb* rb, int64_t slot_begin, int64_t n_slots, const uint8_t* const* host_frames,
                          const float* host_records, const uint8_t* host_valid) {
   SERL_REQUIRE(rb, "rb is NULL");
-  int rc = check_slot_range(rb, slot_begin, n_slots, host_frames, host_records);
-  if (rc) return rc;
+  RC(check_slot_range(rb, slot_begin, n_slots, host_frames, host_records));
   std::unique_lock<std::mutex> g(rb->mu);
   rb->idle.wait(g, [rb] { return !rb->busy; });
   SERL_HIP(hipSetDevice(rb->device));
-  if ((rc = xfer_init(rb))) return rc;
-  if ((rc = order_after_gathers(rb))) return rc;  // as an insert: never overwrite a slot an in-flight gather may still read
+  RC(xfer_init(rb));
+  RC(order_after_gathers(rb));  // as an insert: never overwrite a slot an in-flight gather may still read
   SlotRun runs[2];
-  const int nr = slot_runs(rb, slot_begin, n_slots, runs);
+  const int nr = rb->ix.slot_runs(slot_begin, n_slots, runs);
   const size_t rec_bytes = sizeof(float) * rb->rec_len;
   for (int r = 0; r < nr; ++r) {
     const uint8_t* rec_src = reinterpret_cast<const uint8_t*>(host_records) + (size_t)runs[r].at * rec_bytes;
-    std::memcpy(&rb->rec_host[(size_t)runs[r].slot * rb->rec_len], rec_src, (size_t)runs[r].n * rec_bytes);
     RC(staged_h2d(rb, reinterpret_cast<uint8_t*>(rb->rec) + (size_t)runs[r].slot * rec_bytes, rec_src, (size_t)runs[r].n * rec_bytes));
     for (int c = 0; c < rb->n_cam; ++c)
       RC(staged_h2d(rb, rb->frames[c] + (size_t)runs[r].slot * rb->frame_bytes, host_frames[c] + (size_t)runs[r].at * rb->frame_bytes,
                     (size_t)runs[r].n * rb->frame_bytes));
   }
-  if (host_valid) std::memcpy(rb->valid.data(), host_valid, (size_t)rb->cap);
+  if (host_valid) std::memcpy(rb->ix.valid.data(), host_valid, (size_t)rb->ix.cap);
   SERL_HIP(hipStreamSynchronize(rb->copy_stream));  // the slots are in HBM when the call returns: a later gather needs no wait
   return SERL_OK;
 }
@@ -879,60 +769,12 @@ int serl_rb_sample_indices(serl_rb* rb, int batch, int64_t* host_idx_out) {
   SERL_REQUIRE(rb && host_idx_out, "NULL argument");
   SERL_REQUIRE(batch >= 0, "negative batch");
   std::lock_guard<std::mutex> g(rb->mu);
-  if (!rb->rng.seeded) {
-    set_error("replay buffer RNG not seeded: call serl_rb_seed first");
-    return SERL_ERR_STATE;
-  }
-  if (batch > 0 && rb->size <= 0) {
-    set_error("cannot sample from an empty replay buffer");
-    return SERL_ERR_STATE;
-  }
-  const uint32_t n = (uint32_t)rb->size;
-  if (batch > 0) {
-    bool any = false;
-    for (int64_t i = 0; i < rb->size && !any; ++i) any = rb->valid[i];
-    if (!any) {
-      set_error("replay buffer holds no valid transition");
-      return SERL_ERR_STATE;
-    }
-  }
-  for (int i = 0; i < batch; ++i) host_idx_out[i] = rb->rng.bounded(n);  // integers(len, size=B)
-  for (int i = 0; i < batch; ++i)
-    while (!rb->valid[host_idx_out[i]]) host_idx_out[i] = rb->rng.bounded(n);  // rejection loop
-  return SERL_OK;
-}
-
-// The reference holds one lock across index draw and gather (data_store.py:108-111); here they are two calls (the
-// lazy / prefetched path), so an insert in between may have invalidated a drawn slot (the look-ahead invalidation of
-// memory_efficient_replay_buffer.py:87-89, a new episode's first-frame slot, the wrap re-insert).  A slot that is still
-// valid pairs with slot-1 consistently (writes are sequential), so validity is the whole check: stale indices are
-// re-drawn from the buffer's generator under the lock, exactly as the rejection loop would have.  `out` stays empty
-// when nothing changed.  Caller holds rb->mu.
-// An index drawn before an insert invalidated its slot is re-drawn here, IN PLACE: the caller's array then describes the
-// batch that is actually gathered (index-keyed bookkeeping and determinism checks stay valid).
-static int revalidate(serl_rb* rb, int64_t* idx, int n) {
-  if (rb->n_cam == 0) return SERL_OK;   // plain ReplayBuffer: every slot below `size` is valid
-  for (int i = 0; i < n; ++i) {
-    if (rb->valid[idx[i]]) continue;
-    SERL_REQUIRE(rb->rng.seeded, "replay buffer RNG not seeded");
-    const uint32_t sz = (uint32_t)rb->size;
-    int guard = 0;
-    do {
-      idx[i] = rb->rng.bounded(sz);
-      SERL_REQUIRE(++guard < (1 << 24), "no valid slot found while re-drawing a stale index");
-    } while (!rb->valid[idx[i]]);
-  }
-  return SERL_OK;
-}
-
-static int check_indices(serl_rb* rb, const int64_t* idx, int n) {
-  for (int i = 0; i < n; ++i) {
-    if (idx[i] < 0 || idx[i] >= rb->size) {
-      set_error("index %lld out of range [0,%lld)", (long long)idx[i], (long long)rb->size);
-      return SERL_ERR_INVALID;
-    }
-  }
-  return SERL_OK;
+  const IndexStatus st = rb->ix.sample(batch, host_idx_out);
+  if (st == IndexStatus::kOk) return SERL_OK;
+  set_error("%s", st == IndexStatus::kNotSeeded ? "replay buffer RNG not seeded: call serl_rb_seed first"
+                  : st == IndexStatus::kEmpty   ? "cannot sample from an empty replay buffer"
+                                                : "replay buffer holds no valid transition");
+  return SERL_ERR_STATE;
 }
 
 int serl_rb_gather_packed(serl_rb* rb, int64_t* host_idx, int batch,
@@ -944,15 +786,12 @@ int serl_rb_gather_packed(serl_rb* rb, int64_t* host_idx, int batch,
   hipStream_t stream = (hipStream_t)stream_;
   std::lock_guard<std::mutex> g(rb->mu);
   SERL_HIP(hipSetDevice(rb->device));
-  int rc = check_indices(rb, host_idx, batch);
-  if (rc) return rc;
-  if ((rc = revalidate(rb, host_idx, batch))) return rc;
-  if ((rc = order_after_inserts(rb, stream))) return rc;
+  RC(check_and_revalidate(rb, host_idx, batch));
+  RC(order_after_inserts(rb, stream));
   const void* srcs[1] = {host_idx};
   size_t sizes[1] = {sizeof(int64_t) * (size_t)batch}, offs[1];
   uint8_t* dparams;
-  int slot = stage_params(rb, srcs, sizes, 1, stream, &dparams, offs);
-  if (slot < 0) return slot;
+  RC(stage_params(rb->stage, srcs, sizes, 1, stream, &dparams, offs));
   PackedArgs a{};
   for (int c = 0; c < rb->n_cam; ++c) {
     a.frames[c] = rb->frames[c];
@@ -961,7 +800,7 @@ int serl_rb_gather_packed(serl_rb* rb, int64_t* host_idx, int batch,
   a.rec = rb->rec;
   a.idx = reinterpret_cast<const int64_t*>(dparams + offs[0]);
   a.batch = batch; a.n_cam = rb->n_cam; a.T = rb->T; a.TS = rb->T * rb->S; a.A = rb->A;
-  a.rec_len = rb->rec_len; a.fbytes = rb->frame_bytes; a.cap = rb->cap;
+  a.rec_len = rb->rec_len; a.fbytes = rb->frame_bytes; a.cap = rb->ix.cap;
   a.out_state = dev_state_out; a.out_next_state = dev_next_state_out; a.out_action = dev_action_out;
   a.out_reward = dev_reward_out; a.out_mask = dev_mask_out; a.out_done = dev_done_out;
   a.vec_per_block = 256 * 4;
@@ -970,8 +809,15 @@ int serl_rb_gather_packed(serl_rb* rb, int64_t* host_idx, int batch,
   const int rec_blocks = dev_state_out ? cdiv((long)batch * rb->rec_len, 256) : 0;
   hipLaunchKernelGGL(gather_packed_kernel, dim3(a.n_frame_blocks + rec_blocks), dim3(256), 0, stream, a);
   SERL_HIP(hipGetLastError());
-  SERL_HIP(hipEventRecord(rb->stage_done[slot], stream));
+  RC(rb->stage.mark(stream));
   return note_gather(rb, stream);
+}
+
+// a table of (dy, dx) per sample, or none
+static int check_crops(const int32_t* crop, int batch) {
+  if (crop)
+    for (int i = 0; i < 2 * batch; ++i) SERL_REQUIRE(crop[i] >= 0 && crop[i] <= 8, "crop offset %d out of [0,8]", crop[i]);
+  return SERL_OK;
 }
 
 static int launch_gather_crop(GatherArgs& a, hipStream_t stream) {
@@ -1017,12 +863,8 @@ int serl_rb_gather_crop(serl_rb* const* rbs, int n_rb, int64_t* const* host_idx,
                    out->state_dim == r0->S && out->act_dim == r0->A, "serl_batch shape mismatch");
   SERL_REQUIRE((out->frames || r0->n_cam == 0) && out->state && out->action && out->reward && out->mask && out->done,
                "serl_batch has NULL outputs");
-  for (int k = 0; k < 2; ++k) {
-    const int32_t* cr = k ? host_crop_next : host_crop_obs;
-    if (cr)
-      for (int i = 0; i < 2 * total; ++i)
-        SERL_REQUIRE(cr[i] >= 0 && cr[i] <= 8, "crop offset %d out of [0,8]", cr[i]);
-  }
+  RC(check_crops(host_crop_obs, total));
+  RC(check_crops(host_crop_next, total));
   // lock all buffers (fixed order) while we read bookkeeping and enqueue
   std::unique_lock<std::mutex> l0(rbs[0]->mu, std::defer_lock), l1;
   if (n_rb == 2 && rbs[1] != rbs[0]) {
@@ -1032,28 +874,21 @@ int serl_rb_gather_crop(serl_rb* const* rbs, int n_rb, int64_t* const* host_idx,
     l0.lock();
   }
   SERL_HIP(hipSetDevice(r0->device));
-  const int64_t* use_idx[SERL_MAX_BUFFERS] = {nullptr};
   for (int b = 0; b < n_rb; ++b) {
-    int rc = check_indices(rbs[b], host_idx[b], counts[b]);
-    if (rc) return rc;
-    if ((rc = revalidate(rbs[b], host_idx[b], counts[b]))) return rc;
-    use_idx[b] = host_idx[b];
-    if ((rc = order_after_inserts(rbs[b], stream))) return rc;
+    RC(check_and_revalidate(rbs[b], host_idx[b], counts[b]));
+    RC(order_after_inserts(rbs[b], stream));
   }
-  const void* srcs[4] = {use_idx[0], n_rb > 1 ? use_idx[1] : nullptr, host_crop_obs, host_crop_next};
-  size_t sizes[4] = {sizeof(int64_t) * (size_t)counts[0],
-                     n_rb > 1 ? sizeof(int64_t) * (size_t)counts[1] : 0,
-                     host_crop_obs ? sizeof(int32_t) * 2 * (size_t)total : 0,
-                     host_crop_next ? sizeof(int32_t) * 2 * (size_t)total : 0};
-  size_t offs[4];
+  const size_t cbytes = sizeof(int32_t) * 2 * (size_t)total;
+  const void* srcs[4] = {host_idx[0], n_rb > 1 ? host_idx[1] : nullptr, host_crop_obs, host_crop_next};
+  size_t sizes[4] = {sizeof(int64_t) * (size_t)counts[0], n_rb > 1 ? sizeof(int64_t) * (size_t)counts[1] : 0,
+                     host_crop_obs ? cbytes : 0, host_crop_next ? cbytes : 0}, offs[4];
   uint8_t* dparams;
-  int slot = stage_params(r0, srcs, sizes, 4, stream, &dparams, offs);
-  if (slot < 0) return slot;
+  RC(stage_params(r0->stage, srcs, sizes, 4, stream, &dparams, offs));
   GatherArgs a{};
   for (int b = 0; b < n_rb; ++b) {
     for (int c = 0; c < r0->n_cam; ++c) a.frames[b][c] = rbs[b]->frames[c];
     a.rec[b] = rbs[b]->rec;
-    a.cap[b] = rbs[b]->cap;
+    a.cap[b] = rbs[b]->ix.cap;
     a.idx[b] = reinterpret_cast<const int64_t*>(dparams + offs[b]);
   }
   a.count0 = counts[0];
@@ -1064,30 +899,14 @@ int serl_rb_gather_crop(serl_rb* const* rbs, int n_rb, int64_t* const* host_idx,
   a.out_frames = out->frames; a.out_state = out->state; a.out_action = out->action;
   a.out_reward = out->reward; a.out_mask = out->mask; a.out_done = out->done;
   a.from_packed = 0;
-  int rc = launch_gather_crop(a, stream);
-  if (rc) return rc;
-  SERL_HIP(hipEventRecord(r0->stage_done[slot], stream));
-  for (int b = 0; b < n_rb; ++b) {
-    int rc2 = note_gather(rbs[b], stream);
-    if (rc2) return rc2;
-  }
+  RC(launch_gather_crop(a, stream));
+  RC(r0->stage.mark(stream));
+  for (int b = 0; b < n_rb; ++b) RC(note_gather(rbs[b], stream));
   return SERL_OK;
 }
 
-// Standalone crop needs its own parameter staging (no buffer handle): a small static pool.
-namespace {
-struct CropStage {
-  std::mutex mu;
-  int device = -1;
-  uint8_t* host = nullptr;
-  uint8_t* dev = nullptr;
-  hipEvent_t done[serl::kRing] = {nullptr};
-  bool used[serl::kRing] = {false};
-  int next = 0;
-  size_t slot_bytes = 1 << 16;
-};
-CropStage g_crop;
-}  // namespace
+// Standalone crop needs its own parameter staging (no buffer handle): one static ring, made at the first call.
+static struct { std::mutex mu; int device = -1; StageRing ring; } g_crop;
 
 int serl_crop_packed(int device, const uint8_t* const* dev_packed, int n_cam, int batch, int H,
                      int W, int C, const int32_t* host_crop_obs, const int32_t* host_crop_next,
@@ -1100,42 +919,26 @@ int serl_crop_packed(int device, const uint8_t* const* dev_packed, int n_cam, in
   SERL_HIP(hipSetDevice(device));
   if (g_crop.device != device) {
     SERL_REQUIRE(g_crop.device == -1, "serl_crop_packed is bound to device %d", g_crop.device);
-    SERL_HIP(hipHostMalloc((void**)&g_crop.host, g_crop.slot_bytes * kRing, hipHostMallocDefault));
-    SERL_HIP(hipMalloc((void**)&g_crop.dev, g_crop.slot_bytes * kRing));
-    for (int s = 0; s < kRing; ++s)
-      SERL_HIP(hipEventCreateWithFlags(&g_crop.done[s], hipEventDisableTiming));
+    RC(g_crop.ring.init(kRing, 1 << 16, true));
     g_crop.device = device;
   }
+  RC(check_crops(host_crop_obs, batch));  // every check comes before a staging slot is taken
+  RC(check_crops(host_crop_next, batch));
   const size_t cbytes = sizeof(int32_t) * 2 * (size_t)batch;
-  const size_t coff = (cbytes + 15) & ~(size_t)15;
-  SERL_REQUIRE(2 * coff <= g_crop.slot_bytes, "batch too large");
-  const int s = g_crop.next;
-  g_crop.next = (s + 1) % kRing;
-  if (g_crop.used[s]) SERL_HIP(hipEventSynchronize(g_crop.done[s]));
-  uint8_t* h = g_crop.host + (size_t)s * g_crop.slot_bytes;
-  uint8_t* d = g_crop.dev + (size_t)s * g_crop.slot_bytes;
-  for (int k = 0; k < 2; ++k) {
-    const int32_t* cr = k ? host_crop_next : host_crop_obs;
-    if (cr) {
-      for (int i = 0; i < 2 * batch; ++i)
-        SERL_REQUIRE(cr[i] >= 0 && cr[i] <= 8, "crop offset %d out of [0,8]", cr[i]);
-      std::memcpy(h + k * coff, cr, cbytes);
-    }
-  }
-  SERL_HIP(hipMemcpyAsync(d, h, 2 * coff, hipMemcpyHostToDevice, stream));
-  g_crop.used[s] = true;
+  const void* srcs[2] = {host_crop_obs, host_crop_next};
+  size_t sizes[2] = {cbytes, cbytes}, offs[2];  // both tables keep their place in the slot, given or not
+  uint8_t* d;
+  RC(stage_params(g_crop.ring, srcs, sizes, 2, stream, &d, offs));
   GatherArgs a{};
   for (int c = 0; c < n_cam; ++c) a.packed[c] = dev_packed[c];
   a.from_packed = 1;
   a.count0 = batch;
   a.batch = batch; a.n_cam = n_cam; a.H = H; a.W = W; a.C = C;
-  a.crop_obs = host_crop_obs ? reinterpret_cast<const int32_t*>(d) : nullptr;
-  a.crop_next = host_crop_next ? reinterpret_cast<const int32_t*>(d + coff) : nullptr;
+  a.crop_obs = host_crop_obs ? reinterpret_cast<const int32_t*>(d + offs[0]) : nullptr;
+  a.crop_next = host_crop_next ? reinterpret_cast<const int32_t*>(d + offs[1]) : nullptr;
   a.out_frames = dev_frames_out;
-  int rc = launch_gather_crop(a, stream);
-  if (rc) return rc;
-  SERL_HIP(hipEventRecord(g_crop.done[s], stream));
-  return SERL_OK;
+  RC(launch_gather_crop(a, stream));
+  return g_crop.ring.mark(stream);
 }
 
 }  // extern "C"

@@ -157,6 +157,50 @@ def test_error_behaviour(gpu):
         rb.gather(np.array([999], np.int64))
 
 
+def test_refused_gather_leaves_store_intact(gpu):
+    """A gather whose indices exceed the 64 KiB parameter slot (8200 x 8 bytes) is refused on the host before a byte is staged
+    or a kernel launched; the nine gathers after it -- one more than the staging ring has slots -- are still exact."""
+    import ctypes as C
+    from serl_amd import _lib
+    from serl_amd.data.data_store import MemoryEfficientReplayBufferDataStore
+    from serl_amd.utils.synthetic import transition_stream
+    keys, H, W, Cc, S, A, cap = ("img",), 4, 16, 1, 2, 2, 64
+    osp, asp = make_spaces(keys, H, W, Cc, 1, S, A)
+    rb = MemoryEfficientReplayBufferDataStore(osp, asp, cap, image_keys=keys)
+    o = ReplayOracle(keys, H, W, Cc, 1, S, A, cap)
+    rb.seed(5)
+    o.seed(5)
+    for tr in itertools.islice(transition_stream(keys, H, W, Cc, 1, S, A, 7, 99), 40):
+        rb.insert(tr)
+        o.insert(tr)
+    B = 8200
+    drawn = rb.sample_indices(16)
+    assert (drawn == o.sample_indices(16)).all()
+    idx = np.resize(drawn, B).astype(np.int64)   # valid, repeated
+    dev = torch.device("cuda", 0)
+    fr = torch.empty((B, 2, H, W, Cc), dtype=torch.uint8, device=dev)
+    st, nst, act = (torch.empty((B, 2), dtype=torch.float32, device=dev) for _ in range(3))
+    rew, msk = torch.empty(B, dtype=torch.float32, device=dev), torch.empty(B, dtype=torch.float32, device=dev)
+    done = torch.empty(B, dtype=torch.uint8, device=dev)
+    rc = _lib.lib().serl_rb_gather_packed(
+        rb.handle, idx.ctypes.data, B, (C.c_void_p * 1)(fr.data_ptr()), st.data_ptr(), nst.data_ptr(), act.data_ptr(),
+        rew.data_ptr(), msk.data_ptr(), done.data_ptr(), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+    assert rc == -1   # SERL_ERR_INVALID
+    assert b"batch too large for the staging slot" in _lib.lib().serl_last_error()
+    for _ in range(9):
+        i = rb.sample_indices(16)
+        assert (i == o.sample_indices(16)).all()
+        b, ob = rb.gather(i), o.gather(i)
+        torch.cuda.synchronize()
+        assert (b["observations"]["img"].cpu().numpy() == ob["observations"]["img"]).all()
+        assert (b["observations"]["state"].cpu().numpy() == ob["observations"]["state"]).all()
+        assert (b["next_observations"]["state"].cpu().numpy() == ob["next_observations"]["state"]).all()
+        assert (b["actions"].cpu().numpy() == ob["actions"]).all()
+        assert (b["rewards"].cpu().numpy() == ob["rewards"]).all()
+        assert (b["masks"].cpu().numpy() == ob["masks"]).all()
+        assert (b["dones"].cpu().numpy() == ob["dones"]).all()
+
+
 def test_full_size_properties(gpu):
     """BASELINE shape (2 cams 128x128x3, S=24, A=6, B=256): identity crop == packed gather,
     byte checksum of checksums, and crop-by-rows equivalence."""
