@@ -394,6 +394,43 @@ int serl_classifier_set(serl_classifier* c, const char* leaf, const float* host,
 int serl_classifier_get(serl_classifier* c, const char* leaf, float* host_out, int64_t count);
 /* dev_frames u8[n_cam][n][H][W][3] (device), n <= max_batch; dev_logits f32[n] (device) */
 int serl_classifier_logits(serl_classifier* c, const uint8_t* dev_frames, int n, float* dev_logits, void* stream);
+/* The same logits from frozen-trunk features that already exist (serl_classifier_logits = the trunk, then this): per camera
+ * SpatialLearnedEmbeddings -> Dense -> LayerNorm -> tanh, then the head.  Classifier camera k reads the n feature maps
+ * f32[n][h*w][512] at dev_feats + cam_of[k] * cam_stride_floats (cam_of: host int[n_cam], any order, entries may
+ * repeat; every entry >= 0, and the caller guarantees that each camera it names lies inside the buffer at dev_feats: the
+ * function knows neither how many cameras the buffer holds nor its size, and reads where the entry points). */
+int serl_classifier_logits_from_features(serl_classifier* c, const float* dev_feats, int64_t cam_stride_floats, const int* cam_of,
+                                         int n, float* dev_logits, void* stream);
+
+/* Reward labelling inside the DrQ update: the part of VICEAgent that changes what the critic learns from
+ * (agents/continuous/vice.py:546 in update_critics, :594 in update_high_utd):
+ *     rewards = (sigmoid(classifier(augmented next_obs, train=False)) >= 0.5) * 1.0
+ * computed once per call over the whole batch and used in place of the stored rewards.  SACAgent.update is not overridden by
+ * VICE and keeps the stored rewards (serl_agent_update).  mixup, label smoothing and the gradient penalty of update_vice are
+ * not built; the classifier is trained by serl_classifier_train_step.
+ * serl_agent_set_reward_classifier attaches `c` (NULL detaches).  cam_of: host int[classifier n_cam], the agent camera each
+ * classifier camera reads.  Refused: a state-only agent, a camera index the agent lacks, another image size or device, a
+ * classifier max_batch below the agent's batch.  *mode_out (may be NULL) = SERL_LABEL_FEATURES when the agent has a frozen
+ * trunk whose every leaf is bit-identical to the classifier's (compared here, once): the classifier's head then runs on the
+ * trunk features of the augmented next observations that the agent's slot already holds; else SERL_LABEL_FRAMES: the
+ * classifier's own trunk runs on the batch's augmented next frames.  Both handles count the trunk leaves set on them; a trunk
+ * leaf set on either after the attach makes the next labelling fail with SERL_ERR_STATE until the classifier is attached
+ * again.  The handle is borrowed: it must outlive the attachment.  Labelling reads the classifier's parameters and uses its
+ * scratch on the update's stream; a serl_classifier_train_step or serl_classifier_logits on another stream is the caller's to order. */
+#define SERL_LABEL_NONE 0
+#define SERL_LABEL_FEATURES 1
+#define SERL_LABEL_FRAMES 2
+int serl_agent_set_reward_classifier(serl_agent* a, serl_classifier* c, const int* cam_of, int* mode_out);
+/* Labels the selected batch (vice.py:594): label[i] = 1 / (1 + expf(-logit_i)) >= 0.5f in fp32, into a buffer of the agent;
+ * the critic phases that follow read it instead of the batch's rewards, until another batch is selected.  The batch and the
+ * replay store are not written.  serl_agent_update_critics / _update_high_utd call it themselves when a classifier is attached;
+ * a phase-API caller does, after serl_agent_select_slot / serl_agent_encode (serl_agent_critic_grads refuses otherwise).  Under
+ * serl_agent_set_shard a rank labels its own rows.  No random number is drawn (train=False). */
+int serl_agent_label_rewards(serl_agent* a, void* stream);
+int serl_agent_reward_label_rows(serl_agent* a);   /* rows of the last labelling (0: none yet) */
+/* Labels, logits (host f32[rows of the last labelling], rows <= cfg.batch) and the mean label (vice.py:609 "vice_rewards") of the
+ * last labelling; NULL members are skipped.  Synchronises `stream`. */
+int serl_agent_read_reward_labels(serl_agent* a, float* host_labels, float* host_logits, float* mean_out, void* stream);
 
 /* Training (examples/async_cable_route_drq/train_reward_classifier.py:122-137; the same file in async_bin_relocation_fwbw_drq),
  * opt-in on the same handle and parameter arena.  serl_classifier_train_init replaces TrainState.create(tx=optax.adam(lr))

@@ -115,6 +115,12 @@ SIGNATURES = {
     "serl_classifier_set": [vp, C.c_char_p, vp, i64],
     "serl_classifier_get": [vp, C.c_char_p, vp, i64],
     "serl_classifier_logits": [vp, vp, i32, vp, vp],
+    "serl_classifier_logits_from_features": [vp, vp, i64, P(i32), i32, vp, vp],
+    # reward labelling inside the DrQ update (vice.py:546,594)
+    "serl_agent_set_reward_classifier": [vp, vp, P(i32), P(i32)],
+    "serl_agent_label_rewards": [vp, vp],
+    "serl_agent_reward_label_rows": [vp],
+    "serl_agent_read_reward_labels": [vp, vp, vp, P(f32), vp],
     "serl_classifier_train_init": [vp, i32, f32, f32, f32, f32],
     "serl_classifier_train_step": [vp, vp, i32, vp, vp, vp, vp],
     "serl_classifier_train_forward": [vp, vp, i32, vp, vp, vp, vp],

@@ -138,6 +138,32 @@ class AgentCore(Handle):
         _lib.check(self.L.serl_agent_read_info(self._h, C.byref(info), self._stream()))
         return {n: getattr(info, n) for n, _ in SerlInfo._fields_}
 
+    # ---- reward labelling inside update_critics / update_high_utd (vice.py:546,594) ---------
+    reward_classifier = None      # the attached classifier handle (kept alive here: the library borrows it)
+    reward_label_mode = None      # None | "features" (head on the slot's trunk features) | "frames" (the classifier's own trunk)
+
+    def set_reward_classifier(self, classifier, cam_of=()):
+        """classifier: a serl_classifier Handle, None detaches; cam_of[k] = the agent camera classifier camera k reads."""
+        mode = C.c_int()
+        if classifier is None:
+            _lib.check(self.L.serl_agent_set_reward_classifier(self._h, None, None, C.byref(mode)))
+        else:
+            _lib.check(self.L.serl_agent_set_reward_classifier(self._h, classifier._h, (C.c_int * len(cam_of))(*cam_of), C.byref(mode)))
+        self.reward_classifier = classifier
+        self.reward_label_mode = {0: None, 1: "features", 2: "frames"}[mode.value]
+        return self.reward_label_mode
+
+    def label_rewards(self):
+        """Phase API: label the selected batch (after select_slot / encode); the critic phases then read the labels."""
+        _lib.check(self.L.serl_agent_label_rewards(self._h, self._stream()))
+
+    def read_reward_labels(self):
+        """-> (labels f32[rows], logits f32[rows], mean label) of the last labelling; synchronises the stream."""
+        n = int(self.L.serl_agent_reward_label_rows(self._h))
+        lab, lg, mean = np.empty(max(n, 1), np.float32), np.empty(max(n, 1), np.float32), C.c_float()
+        _lib.check(self.L.serl_agent_read_reward_labels(self._h, lab.ctypes.data, lg.ctypes.data, C.byref(mean), self._stream()))
+        return lab[:n], lg[:n], float(mean.value)
+
     # ---- data-parallel phases --------------------------------------------------------------
     def set_shard(self, global_offset: int, global_batch: int):
         """This agent's batches are rows [global_offset, ...) of a global batch: device noise is indexed globally."""

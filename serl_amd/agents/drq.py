@@ -45,8 +45,8 @@ class PendingInfo(LazyInfo):
     """Info dict of the LAST update call; reading it synchronises the stream (the reference's jitted
     update returns device arrays that are also only materialised when logged)."""
 
-    def __init__(self, agent, kind, serial):
-        self._agent, self._kind, self._serial = agent, kind, serial
+    def __init__(self, agent, kind, serial, labelled=False):
+        self._agent, self._kind, self._serial, self._labelled = agent, kind, serial, labelled
 
     def _read(self) -> dict:
         if self._agent._update_serial != self._serial:
@@ -63,6 +63,8 @@ class PendingInfo(LazyInfo):
             if self._kind == "high_utd":
                 out["actor"] = {k: r[k] for k in ("actor_loss", "temperature", "entropy")}
                 out["temperature"] = {"temperature_loss": r["temperature_loss"]}
+                if self._labelled:     # vice.py:609: info["vice_rewards"] = rewards.mean()
+                    out["vice_rewards"] = self._agent.core.read_reward_labels()[2]
         out.update(lr)
         return out
 
@@ -247,6 +249,52 @@ class DrQAgent:
             raise TypeError("state must be a flax-layout dict (params / target_params / opt_states / step) or agent.state")
         return self
 
+    # ------------------------------------------------------------------ learned rewards (vice.py:546,594)
+    def set_reward_classifier(self, classifier, image_keys=None):
+        """Label rewards at update time, as VICEAgent.update_critics / update_high_utd do (vice.py:546,594): with a classifier
+        attached (serl_amd.networks.reward_classifier.Classifier; None detaches) those two calls replace the batch's rewards by
+        (sigmoid(classifier(augmented next_obs, train=False)) >= 0.5) * 1.0, once per call over the whole batch; `update` keeps the
+        stored rewards (VICE does not override it).  Neither the caller's batch nor the replay store is written, and no random
+        number is drawn.  update_high_utd's info gains "vice_rewards", the mean label (vice.py:609).
+        image_keys: the agent camera each classifier camera reads, by name, in the classifier's camera order (default: the
+        classifier's own image_keys) -- a subset of the agent's, in any order.
+        The classifier's head runs on the frozen-trunk features the update already holds when both trunks are bit-identical
+        (reward_label_mode "features", compared here), else its own trunk runs on the augmented next frames ("frames").  Setting a
+        trunk leaf on either side afterwards (load_trunk_params) makes the next labelled update raise until this is called again.
+        Train the classifier with its train_step between updates, on the stream the updates run on."""
+        if classifier is None:
+            self.core.set_reward_classifier(None)
+            return self
+        if not self.image_keys:
+            raise _lib.SerlError("a state-only agent has no frames for a reward classifier to label")
+        keys = tuple(classifier.image_keys if image_keys is None else image_keys)
+        if len(keys) != len(classifier.image_keys):
+            raise _lib.SerlError(f"the classifier has {len(classifier.image_keys)} cameras, image_keys names {len(keys)}")
+        lacking = [k for k in keys if k not in self.image_keys]
+        if lacking:
+            raise _lib.SerlError(f"the reward classifier reads {lacking}, which are not among the agent's image_keys {self.image_keys}")
+        self.core.set_reward_classifier(classifier, [self.image_keys.index(k) for k in keys])
+        return self
+
+    @property
+    def reward_classifier(self):
+        return self.core.reward_classifier
+
+    @property
+    def reward_label_mode(self):
+        """None (no classifier attached), "features" or "frames": see set_reward_classifier"""
+        return self.core.reward_label_mode
+
+    def last_reward_labels(self):
+        """(labels, logits) f32[batch] of the last labelled update, rows in batch order; synchronises the stream"""
+        lab, lg, _ = self.core.read_reward_labels()
+        return lab, lg
+
+    def _label_slot(self):
+        """the label phase of the pipelined path: the slot is selected, its features (or frames) are ready"""
+        if self.core.reward_classifier is not None:
+            self.core.label_rewards()
+
     # ------------------------------------------------------------------ batches
     def _device_batch(self, B):
         c = self.core.cfg
@@ -285,7 +333,8 @@ class DrQAgent:
         if keys is not None:
             self._rng_key = keys.rng_out.copy()
         self._update_serial += 1
-        return self, PendingInfo(self, kind, self._update_serial)
+        labelled = kind in ("critics", "high_utd") and self.core.reward_classifier is not None
+        return self, PendingInfo(self, kind, self._update_serial, labelled)
 
     def prepare(self, batch, crops=None) -> DeviceBatch:
         """sample-gather [+ concat_batches] + _unpack + random-shift crop -> DeviceBatch."""
@@ -420,6 +469,7 @@ class DrQAgent:
             slot, db = self._acquire(batch, None if keys is None else keys.rng_out)
 
             def run(noise):
+                self._label_slot()
                 self.core.begin_update()
                 self.core.critic_grads(0, db.batch, db.batch, noise)
                 self.core.apply(APPLY_CRITIC)
@@ -440,6 +490,7 @@ class DrQAgent:
 
             def run(noise):
                 mb = B // utd_ratio
+                self._label_slot()
                 self.core.begin_update()
                 for i in range(utd_ratio):
                     self.core.critic_grads(i * mb, mb, mb, noise, i)

@@ -142,6 +142,20 @@ struct serl_agent {
   int pg_ncs = 0;
   GemmDesc pg_wg[kMaxGemmGroups];
   int pg_nwg = 0;
+  // Reward labelling (vice.py:546,594): with a reward classifier attached, update_critics / update_high_utd replace the batch's
+  // rewards by (sigmoid(classifier(augmented next_obs, train=False)) >= 0.5), computed once per call into `labels`; the critic
+  // loss then reads `labels` instead of cur.reward (`labelled`, cleared when another batch is selected).  label_mode
+  // SERL_LABEL_FEATURES: the classifier's head runs on the slot's pass-1 trunk features (the trunks were bit-identical at
+  // attach); SERL_LABEL_FRAMES: the classifier's own trunk runs on the batch's next frames.  The handle is borrowed.
+  serl_classifier* cls = nullptr;
+  int cls_cam[SERL_MAX_CAMS] = {0, 0, 0, 0};   // classifier camera k reads agent camera cls_cam[k]
+  int label_mode = SERL_LABEL_NONE;
+  int64_t trunk_gen = 0;                       // bumped by every trunk leaf set on this agent
+  int64_t attach_gen = 0, attach_cls_gen = 0;  // both generations when the classifier was attached
+  float *labels = nullptr, *label_logits = nullptr, *label_mean = nullptr;   // [batch], [batch], [1]
+  int* label_ctr = nullptr;
+  int label_n = 0;                             // rows of the last labelling
+  bool labelled = false, label_exempt = false; // exempt: SACAgent.update, which VICE does not override
 };
 
 namespace {
@@ -296,6 +310,8 @@ size_t carve(serl_agent* a, void* base) {
   }
   a->act_tmp = b.take<float>(B * A);
   a->ctr = b.take<int>((long)kCtrPerLane * kCtrLanes);
+  a->labels = b.take<float>(B); a->label_logits = b.take<float>(B); a->label_mean = b.take<float>(1);
+  a->label_ctr = b.take<int>(1);
   if (a->small) {
     void* smem = b.take<uint8_t>(small_workspace_bytes(c.n_cam * c.batch, c.H, c.W));
     if (base) small_workspace_bind(a->sws, smem, c.n_cam * c.batch, c.H, c.W);
@@ -949,7 +965,10 @@ int serl_agent_set(serl_agent* a, const char* section, const char* leaf, const f
   SERL_REQUIRE(n == count, "leaf '%s' has %ld elements, got %lld", leaf, n, (long long)count);
   if (std::strncmp(leaf, "trunk/", 6) == 0) { SERL_HIP(hipDeviceSynchronize()); RC(flush_trunk_ema(a)); }   // pending EMA steps belong to the old values
   RC(leaf_copy(p, host, n, hipMemcpyHostToDevice, section, leaf, kOutsideSupport));
-  if (p && std::strncmp(leaf, "trunk/", 6) == 0) a->tpk.dirty = true;
+  if (p && std::strncmp(leaf, "trunk/", 6) == 0) {
+    a->tpk.dirty = true;
+    a->trunk_gen += 1;   // (a reward classifier attached on equal trunks is stale now: check_label_fresh)
+  }
   return SERL_OK;
 }
 
@@ -1058,6 +1077,7 @@ int serl_agent_select_slot(serl_agent* a, int slot) {
   a->feats = a->feats_slot[slot];
   a->cur = a->cur_slot[slot];
   a->has_batch = true;
+  a->labelled = a->label_exempt = false;   // this batch's rewards are its own until serl_agent_label_rewards runs
   return SERL_OK;
 }
 
@@ -1083,6 +1103,99 @@ int serl_agent_set_shard(serl_agent* a, int64_t global_offset, int64_t global_ba
   return SERL_OK;
 }
 
+// ---- reward labelling (vice.py:546,594) -----------------------------------------------------------------------------------
+// A trunk leaf set on either handle since the attach may have made the trunks differ: the shared-feature path would then label
+// from features the classifier's own trunk does not produce.  Refused until the caller attaches again (which compares anew).
+static int check_label_fresh(serl_agent* a) {
+  if (!a->cls) return SERL_OK;
+  const bool mine = a->trunk_gen != a->attach_gen, theirs = classifier_view(a->cls).trunk_gen != a->attach_cls_gen;
+  if (mine || theirs) {
+    set_error("stale reward-classifier attachment: a trunk leaf of the %s was set after serl_agent_set_reward_classifier; attach again",
+              mine ? "agent" : "classifier");
+    return SERL_ERR_STATE;
+  }
+  return SERL_OK;
+}
+
+int serl_agent_set_reward_classifier(serl_agent* a, serl_classifier* cls, const int* cam_of, int* mode_out) {
+  SERL_REQUIRE(a, "NULL agent");
+  if (!cls) {
+    a->cls = nullptr;
+    a->label_mode = SERL_LABEL_NONE;
+    a->labelled = false;
+    if (mode_out) *mode_out = SERL_LABEL_NONE;
+    return SERL_OK;
+  }
+  SERL_REQUIRE(cam_of, "NULL camera map");
+  const serl_agent_cfg& c = a->cfg;
+  SERL_REQUIRE(!a->state_only, "a state-only agent has no frames for a reward classifier to label");
+  const ClassifierView v = classifier_view(cls);
+  SERL_REQUIRE(v.cfg.device == c.device, "the classifier lives on device %d, the agent on %d", v.cfg.device, c.device);
+  for (int k = 0; k < v.cfg.n_cam; ++k)
+    SERL_REQUIRE(cam_of[k] >= 0 && cam_of[k] < c.n_cam, "classifier camera %d maps to agent camera %d, the agent has %d", k, cam_of[k], c.n_cam);
+  SERL_REQUIRE(v.cfg.H == c.H && v.cfg.W == c.W, "the classifier takes %dx%d images, the agent %dx%d", v.cfg.H, v.cfg.W, c.H, c.W);
+  SERL_REQUIRE(v.cfg.max_batch >= c.batch, "classifier max_batch %d is below the agent's batch %d", v.cfg.max_batch, c.batch);
+  SERL_HIP(hipSetDevice(c.device));
+  int mode = SERL_LABEL_FRAMES;
+  if (!a->small && v.trunk_count == a->trunk_count) {   // shared features only where every trunk leaf is bit-identical
+    SERL_HIP(hipDeviceSynchronize());
+    std::vector<float> mine(a->trunk_count), theirs(a->trunk_count);
+    SERL_HIP(hipMemcpy(mine.data(), a->trunk, sizeof(float) * mine.size(), hipMemcpyDeviceToHost));
+    SERL_HIP(hipMemcpy(theirs.data(), v.trunk, sizeof(float) * theirs.size(), hipMemcpyDeviceToHost));
+    if (std::memcmp(mine.data(), theirs.data(), sizeof(float) * mine.size()) == 0) mode = SERL_LABEL_FEATURES;
+  }
+  a->cls = cls;
+  for (int k = 0; k < v.cfg.n_cam; ++k) a->cls_cam[k] = cam_of[k];
+  a->label_mode = mode;
+  a->attach_gen = a->trunk_gen;
+  a->attach_cls_gen = v.trunk_gen;
+  a->labelled = false;
+  if (mode_out) *mode_out = mode;
+  return SERL_OK;
+}
+
+int serl_agent_label_rewards(serl_agent* a, void* stream) {
+  SERL_REQUIRE(a && a->has_batch, "serl_agent_encode / serl_agent_select_slot must run first");
+  if (!a->cls) {
+    set_error("no reward classifier is attached (serl_agent_set_reward_classifier)");
+    return SERL_ERR_STATE;
+  }
+  RC(check_label_fresh(a));
+  const serl_agent_cfg& c = a->cfg;
+  hipStream_t st = (hipStream_t)stream;
+  SERL_HIP(hipSetDevice(c.device));
+  const int n = a->cur.batch, nc = classifier_view(a->cls).cfg.n_cam;
+  SERL_HIP(hipMemsetAsync(a->label_ctr, 0, sizeof(int), st));
+  if (a->label_mode == SERL_LABEL_FEATURES) {   // pass 1 of the slot: the augmented next observations, camera stride = cfg.batch maps
+    const long cam_stride = (long)c.batch * a->HW * 512;
+    RC(classifier_label(a->cls, a->feats + c.n_cam * cam_stride, cam_stride, a->cls_cam, nullptr, n, a->labels, a->label_logits,
+                        a->label_mean, a->label_ctr, st));
+  } else {
+    const size_t fbytes = (size_t)c.H * c.W * 3;
+    const uint8_t* cams[SERL_MAX_CAMS];
+    for (int k = 0; k < nc; ++k) cams[k] = a->cur.frames + ((size_t)(c.n_cam + a->cls_cam[k]) * n) * fbytes;   // frames[1][camera]
+    RC(classifier_label(a->cls, nullptr, 0, nullptr, cams, n, a->labels, a->label_logits, a->label_mean, a->label_ctr, st));
+  }
+  a->label_n = n;
+  a->labelled = true;
+  return SERL_OK;
+}
+
+int serl_agent_reward_label_rows(serl_agent* a) { return a ? a->label_n : -1; }
+
+int serl_agent_read_reward_labels(serl_agent* a, float* host_labels, float* host_logits, float* mean_out, void* stream) {
+  SERL_REQUIRE(a, "NULL agent");
+  SERL_REQUIRE(a->label_n > 0, "no rewards were labelled yet");
+  hipStream_t st = (hipStream_t)stream;
+  SERL_HIP(hipSetDevice(a->cfg.device));
+  const size_t bytes = sizeof(float) * a->label_n;
+  if (host_labels) SERL_HIP(hipMemcpyAsync(host_labels, a->labels, bytes, hipMemcpyDeviceToHost, st));
+  if (host_logits) SERL_HIP(hipMemcpyAsync(host_logits, a->label_logits, bytes, hipMemcpyDeviceToHost, st));
+  if (mean_out) SERL_HIP(hipMemcpyAsync(mean_out, a->label_mean, sizeof(float), hipMemcpyDeviceToHost, st));
+  SERL_HIP(hipStreamSynchronize(st));
+  return SERL_OK;
+}
+
 int serl_agent_critic_grads(serl_agent* a, int off, int cnt, int global_count, const serl_noise* noise,
                             int redq_row, void* stream) {
   return serl_agent_critic_grads_bucketed(a, off, cnt, global_count, noise, redq_row, stream, nullptr);
@@ -1101,6 +1214,10 @@ int serl_agent_critic_grads_bucketed(serl_agent* a, int off, int cnt, int global
                                      int redq_row, void* stream, void* event_bucket0) {
   SERL_REQUIRE(a && a->has_batch, "serl_agent_encode must run first");
   SERL_REQUIRE(off >= 0 && cnt >= 1 && off + cnt <= a->cur.batch && global_count >= cnt, "bad minibatch range");
+  if (a->cls && !a->labelled && !a->label_exempt) {
+    set_error("a reward classifier is attached: serl_agent_label_rewards must follow serl_agent_select_slot (vice.py:594)");
+    return SERL_ERR_STATE;
+  }
   const serl_agent_cfg& c = a->cfg;
   const Offs& o = a->o;
   hipStream_t st = (hipStream_t)stream;
@@ -1143,7 +1260,8 @@ int serl_agent_critic_grads_bucketed(serl_agent* a, int off, int cnt, int global
   RC(policy_fwd_multi(a, &pj, 1, cnt, st));
   const CritJob cj[2] = {{a->theta_t, &a->critT}, {a->theta, &a->crit}};  // target and online ensembles together
   RC(critic_fwd_multi(a, cj, 2, cnt, st));
-  const LossArgs L{1, a->critT.q, a->crit.q, a->cur.reward + off, a->cur.mask + off, sel, c.ensemble, cnt, c.discount,
+  const float* reward = a->labelled ? a->labels : a->cur.reward;   // vice.py:594: the labels stand in for the stored rewards
+  const LossArgs L{1, a->critT.q, a->crit.q, reward + off, a->cur.mask + off, sel, c.ensemble, cnt, c.discount,
                    1.0f / ((float)c.ensemble * (float)global_count), a->ytgt, a->dq, a->SC, a->Gc + o.c_hb, a->state_only ? 1 : 0,
                    c.backup_entropy ? a->pol.logp : nullptr, c.backup_entropy ? a->aux + X_ALPHA : nullptr};
   SERL_REQUIRE(!a->state_only || c.ensemble <= 16, "per-member head bias supports ensembles of at most 16");
@@ -1280,14 +1398,18 @@ int serl_agent_update(serl_agent* a, const serl_batch* batch, int nets, const se
   SERL_REQUIRE(nets >= 1 && nets <= 7, "Invalid gradient steps: %d", nets);   // sac.py:272-274
   RC(serl_agent_begin_update(a, stream));
   RC(serl_agent_encode(a, batch, stream));
+  a->label_exempt = true;   // SACAgent.update keeps the stored rewards: VICE overrides update_critics / update_high_utd only
   if (nets & SERL_NET_CRITIC) RC(serl_agent_critic_grads(a, 0, batch->batch, batch->batch, noise, 0, stream));
   if (nets & (SERL_NET_ACTOR | SERL_NET_TEMPERATURE)) RC(serl_agent_actor_grads(a, batch->batch, noise, stream));
   return serl_agent_apply(a, nets, 1.0f, stream);
 }
 
 int serl_agent_update_critics(serl_agent* a, const serl_batch* batch, const serl_noise* noise, void* stream) {
+  SERL_REQUIRE(a, "NULL agent");
+  RC(check_label_fresh(a));
   RC(serl_agent_begin_update(a, stream));
   RC(serl_agent_encode(a, batch, stream));
+  if (a->cls) RC(serl_agent_label_rewards(a, stream));
   RC(serl_agent_critic_grads(a, 0, batch->batch, batch->batch, noise, 0, stream));
   return serl_agent_apply(a, SERL_APPLY_CRITIC, 1.0f, stream);
 }
@@ -1297,8 +1419,10 @@ int serl_agent_update_high_utd(serl_agent* a, const serl_batch* batch, int utd_r
   SERL_REQUIRE(a && batch, "NULL argument");
   SERL_REQUIRE(utd_ratio >= 1 && batch->batch % utd_ratio == 0,
                "Batch size %d must be divisible by UTD ratio %d", batch->batch, utd_ratio);  // sac.py:561-563
+  RC(check_label_fresh(a));
   RC(serl_agent_begin_update(a, stream));
   RC(serl_agent_encode(a, batch, stream));
+  if (a->cls) RC(serl_agent_label_rewards(a, stream));   // once, over the whole batch, before the first minibatch (vice.py:594)
   const int mb = batch->batch / utd_ratio;
   for (int i = 0; i < utd_ratio; ++i) {
     RC(serl_agent_critic_grads(a, i * mb, mb, mb, noise, i, stream));

@@ -58,6 +58,7 @@ struct serl_classifier {
   int split0 = 1, split1 = 1;
   long t0 = 0, nt = 0;          // trainable slice: the camera heads and the classifier head (behind the trunk)
   ClsTrain* tr = nullptr;       // nullptr: inference only
+  int64_t trunk_gen = 0;        // bumped by every trunk leaf set: an agent that labels with this classifier notices (agent.hip)
 };
 
 namespace {
@@ -103,7 +104,89 @@ size_t carve(serl_classifier* c, uint8_t* base) {
   return b.off;
 }
 
+// The frozen trunk on n frames per camera (camera k: u8[n][H][W][3] at cams[k]) -> c->feats [n_cam][max_batch][HW][512]
+int own_trunk(serl_classifier* c, const uint8_t* const* cams, int n, hipStream_t st) {
+  const long nmax = c->cfg.max_batch;
+  for (int k = 0; k < c->cfg.n_cam; ++k)
+    RC(trunk_forward(c->tw, c->tws, cams[k], n, c->feats + (long)k * nmax * c->HW * 512, st, &c->tpk));
+  return SERL_OK;
+}
+
+// Everything between the trunk and the head's LayerNorm, on trunk features that already exist: camera k reads
+// feats + cam_of[k] * cam_stride ([n][HW][512]).  Per camera SpatialLearnedEmbeddings -> Dense(256) (K-split GEMM) -> LayerNorm ->
+// tanh, written side by side, then Dense_0 as *S1 K-split slabs [S1][n][256] in c->slabs.
+int head_slabs(serl_classifier* c, const float* feats, long cam_stride, const int* cam_of, int n, hipStream_t st, int* S1_out) {
+  const serl_classifier_cfg& g = c->cfg;
+  SERL_REQUIRE(n >= 1 && n <= g.max_batch, "n = %d not in [1, max_batch = %d]", n, g.max_batch);
+  SERL_REQUIRE(cam_stride >= (long)n * c->HW * 512, "camera stride %ld holds fewer than n = %d feature maps", cam_stride, n);
+  bool affine = true;   // cam_of[k] = cam_of[0] + k * d: the cameras' features are one (possibly negative) stride apart
+  for (int k = 0; k < g.n_cam; ++k) {
+    SERL_REQUIRE(cam_of[k] >= 0, "negative camera index");
+    if (k >= 2 && cam_of[k] - cam_of[k - 1] != cam_of[1] - cam_of[0]) affine = false;
+  }
+  const float* P = c->params;
+  const long nmax = g.max_batch;
+  if (affine) {
+    const long d = g.n_cam > 1 ? cam_of[1] - cam_of[0] : 0;
+    SleFwdArgs sv{feats + cam_of[0] * cam_stride, P + c->cam.sle, nullptr, c->f};
+    RC(sle_fwd_multi(&sv, 1, 1.0f, n, c->HW, 512, g.n_cam, d * cam_stride, c->cam.stride, 0, nmax * c->D, st));
+  } else {
+    for (int k = 0; k < g.n_cam; ++k) {
+      SleFwdArgs sv{feats + cam_of[k] * cam_stride, P + c->cam.sle + k * c->cam.stride, nullptr, c->f + k * nmax * c->D};
+      RC(sle_fwd_multi(&sv, 1, 1.0f, n, c->HW, 512, 1, 0, 0, 0, 0, st));
+    }
+  }
+  const int S0 = split_under(n, kBottleneck, g.n_cam, 32);
+  GemmDesc g0;
+  LnFwdArgs l0;
+  cam_dense_ln_args(c->f, nmax * c->D, c->D, P + c->cam.dW, P + c->cam.db, P + c->cam.lng, P + c->cam.lnb, c->cam.stride,
+                    g.n_cam, n, kBottleneck, S0, c->slabs, c->enc, c->E, nullptr, nullptr, g0, l0);
+  RC(gemm_f32_multi(&g0, 1, st));
+  RC(ln_tanh_fwd_multi(&l0, 1, kBottleneck, st));
+  const int S1 = split_under(n, kHidden, 1, 8);
+  const GemmDesc g1 = gemm_fwd(c->enc, c->E, 0, P + c->o_w1, 0, c->slabs, 1, n, kHidden, c->E, S1);
+  RC(gemm_f32_multi(&g1, 1, st));
+  *S1_out = S1;
+  return SERL_OK;
+}
+
+// The head's last launch on Dense_0's slabs: LayerNorm -> ReLU -> Dense(1), logits to dev_logits
+LnFwdArgs head_ln_args(serl_classifier* c, int S1, int n, float* dev_logits) {
+  const float* P = c->params;
+  LnFwdArgs l1{};
+  l1.slabs = c->slabs; l1.S = S1; l1.slab_stride = (long)n * kHidden;
+  l1.bias = P + c->o_b1; l1.gamma = P + c->o_g1; l1.beta = P + c->o_be1; l1.pstride = 0;
+  l1.rows = n; l1.rows_per_group = n;
+  l1.y = c->h; l1.ld_y = kHidden; l1.y_goff = 0;
+  l1.relu = 1;
+  l1.dot_w = P + c->o_w2; l1.dot_b = P + c->o_b2; l1.dot_out = dev_logits;
+  return l1;
+}
+
 }  // namespace
+
+// ---- the classifier as the agent's reward labeller sees it (internal.h) -------------------------------------------------------
+namespace serl {
+
+ClassifierView classifier_view(const serl_classifier* c) {
+  return ClassifierView{c->cfg, c->params, c->t0, c->trunk_gen};   // (the trunk's leaves lie in front of the first camera head)
+}
+
+int classifier_label(serl_classifier* c, const float* feats, long cam_stride, const int* cam_of, const uint8_t* const* cam_frames,
+                     int n, float* label, float* logit, float* mean, int* ctr, hipStream_t st) {
+  const serl_classifier_cfg& g = c->cfg;
+  SERL_REQUIRE(n >= 1 && n <= g.max_batch, "n = %d not in [1, classifier max_batch = %d]", n, g.max_batch);
+  int ident[SERL_MAX_CAMS] = {0, 1, 2, 3};
+  if (cam_frames) {   // own-trunk path: the classifier's trunk on the frames, then its features in camera order
+    RC(own_trunk(c, cam_frames, n, st));
+    feats = c->feats; cam_stride = (long)g.max_batch * c->HW * 512; cam_of = ident;
+  }
+  int S1 = 0;
+  RC(head_slabs(c, feats, cam_stride, cam_of, n, st, &S1));
+  return label_rows(head_ln_args(c, S1, n, logit), label, mean, ctr, st);
+}
+
+}  // namespace serl
 
 extern "C" {
 
@@ -152,7 +235,10 @@ int serl_classifier_set(serl_classifier* c, const char* leaf, const float* host,
   SERL_REQUIRE(count == l->count, "leaf '%s' has %ld elements, got %ld", leaf, l->count, (long)count);
   SERL_HIP(hipSetDevice(c->cfg.device));
   SERL_HIP(hipMemcpy(c->params + l->off, host, (size_t)count * 4, hipMemcpyHostToDevice));
-  if (l->name.rfind("trunk/", 0) == 0) c->tpk.dirty = true;   // fp16 planes are re-packed on the next forward
+  if (l->name.rfind("trunk/", 0) == 0) {
+    c->tpk.dirty = true;   // fp16 planes are re-packed on the next forward
+    c->trunk_gen += 1;
+  }
   return SERL_OK;
 }
 
@@ -172,32 +258,22 @@ int serl_classifier_logits(serl_classifier* c, const uint8_t* dev_frames, int n,
   SERL_REQUIRE(n >= 1 && n <= g.max_batch, "n = %d not in [1, max_batch = %d]", n, g.max_batch);
   hipStream_t st = (hipStream_t)stream;
   SERL_HIP(hipSetDevice(g.device));
-  const size_t fbytes = (size_t)g.H * g.W * 3;
-  const long nmax = g.max_batch;
-  for (int k = 0; k < g.n_cam; ++k)
-    RC(trunk_forward(c->tw, c->tws, dev_frames + (size_t)k * n * fbytes, n, c->feats + (long)k * nmax * c->HW * 512, st, &c->tpk));
-  const float* P = c->params;
-  // per camera: SpatialLearnedEmbeddings -> Dense(256) (K-split GEMM) -> LayerNorm -> tanh, written side by side
-  SleFwdArgs sv{c->feats, P + c->cam.sle, nullptr, c->f};
-  RC(sle_fwd_multi(&sv, 1, 1.0f, n, c->HW, 512, g.n_cam, nmax * c->HW * 512, c->cam.stride, 0, nmax * c->D, st));
-  const int S0 = split_under(n, kBottleneck, g.n_cam, 32);
-  GemmDesc g0;
-  LnFwdArgs l0;
-  cam_dense_ln_args(c->f, nmax * c->D, c->D, P + c->cam.dW, P + c->cam.db, P + c->cam.lng, P + c->cam.lnb, c->cam.stride,
-                    g.n_cam, n, kBottleneck, S0, c->slabs, c->enc, c->E, nullptr, nullptr, g0, l0);
-  RC(gemm_f32_multi(&g0, 1, st));
-  RC(ln_tanh_fwd_multi(&l0, 1, kBottleneck, st));
-  // Dense(256) -> LayerNorm -> ReLU -> Dense(1)
-  const int S1 = split_under(n, kHidden, 1, 8);
-  const GemmDesc g1 = gemm_fwd(c->enc, c->E, 0, P + c->o_w1, 0, c->slabs, 1, n, kHidden, c->E, S1);
-  RC(gemm_f32_multi(&g1, 1, st));
-  LnFwdArgs l1{};
-  l1.slabs = c->slabs; l1.S = S1; l1.slab_stride = g1.sCz;
-  l1.bias = P + c->o_b1; l1.gamma = P + c->o_g1; l1.beta = P + c->o_be1; l1.pstride = 0;
-  l1.rows = n; l1.rows_per_group = n;
-  l1.y = c->h; l1.ld_y = kHidden; l1.y_goff = 0;
-  l1.relu = 1;
-  l1.dot_w = P + c->o_w2; l1.dot_b = P + c->o_b2; l1.dot_out = dev_logits;
+  const uint8_t* cams[SERL_MAX_CAMS];
+  for (int k = 0; k < g.n_cam; ++k) cams[k] = dev_frames + (size_t)k * n * g.H * g.W * 3;
+  RC(own_trunk(c, cams, n, st));
+  int cam_of[SERL_MAX_CAMS];
+  for (int k = 0; k < g.n_cam; ++k) cam_of[k] = k;
+  return serl_classifier_logits_from_features(c, c->feats, (int64_t)g.max_batch * c->HW * 512, cam_of, n, dev_logits, stream);
+}
+
+int serl_classifier_logits_from_features(serl_classifier* c, const float* dev_feats, int64_t cam_stride_floats, const int* cam_of,
+                                         int n, float* dev_logits, void* stream) {
+  SERL_REQUIRE(c && dev_feats && cam_of && dev_logits, "NULL argument");
+  hipStream_t st = (hipStream_t)stream;
+  SERL_HIP(hipSetDevice(c->cfg.device));
+  int S1 = 0;
+  RC(head_slabs(c, dev_feats, cam_stride_floats, cam_of, n, st, &S1));
+  const LnFwdArgs l1 = head_ln_args(c, S1, n, dev_logits);
   return ln_tanh_fwd_multi(&l1, 1, kHidden, st);
 }
 

@@ -22,6 +22,10 @@ int reduce_slabs(const float* slabs, int S, long slab_stride, int groups, int ro
                  hipStream_t stream, float scale = 1.0f);
 
 int ln_tanh_fwd_multi(const LnFwdArgs* a, int n, int D, hipStream_t stream);
+// One width-256 ReLU instance with a row-dot (the reward classifier's head), closed for reward labelling: dot_out = logits,
+// label[row] = sigmoid(logit) >= 0.5, mean[0] = the labels' mean, summed in a fixed order inside the launch (ctr: one zeroed
+// arrival counter)
+int label_rows(const LnFwdArgs& a, float* label, float* mean, int* ctr, hipStream_t stream);
 
 // REDQ target + critic loss as a rider workgroup of the LayerNorm-backward launch that consumes dQ (sac.py:142-191)
 struct RedqSel { int n; int idx[16]; };

@@ -193,8 +193,9 @@ __device__ __forceinline__ float hash_normal(uint64_t seed, uint64_t i) {
 // LayerNorm(eps 1e-6, fast variance) + tanh of ONE row of 256 by one wave (mlp.py:24-31, resnet_v1.py:371-374, encoding.py:66-68):
 // pre = bias[g] + sum_s slab[s][row] (slabs read in index order);  y = tanh(gamma[g]*xhat + beta[g]).  LIVE: the slabs were
 // written by other workgroups of THIS launch (sc1 loads); otherwise plain loads (the separate ln_tanh_fwd kernel).
+// Returns the fused row-dot (dot_out's value, in every lane; 0 without one).
 template <bool LIVE>
-__device__ __forceinline__ void ln_tanh_row256(const LnFwdArgs& a, int row, int lane) {
+__device__ __forceinline__ float ln_tanh_row256(const LnFwdArgs& a, int row, int lane) {
   constexpr int D = 256;
   const int grp = row / a.rows_per_group;
   const long lrow = row - grp * a.rows_per_group;
@@ -241,8 +242,10 @@ __device__ __forceinline__ void ln_tanh_row256(const LnFwdArgs& a, int row, int 
   if (a.dot_out) {
 #pragma unroll
     for (int off = 1; off < 64; off <<= 1) d += __shfl_xor(d, off);
-    if (lane == 0) a.dot_out[row] = d + a.dot_b[(long)grp * a.dot_b_gstride];
+    d += a.dot_b[(long)grp * a.dot_b_gstride];
+    if (lane == 0) a.dot_out[row] = d;
   }
+  return d;
 }
 
 // tanh-Gaussian head of rows [r0, r1) from the head GEMM's slabs (actor_critic_nets.py:179-272): one thread per (row, action)
@@ -858,6 +861,40 @@ __global__ __launch_bounds__(256) void ln_tanh_fwd_kernel(Multi<LnFwdArgs> mv) {
     for (int off = 1; off < 64; off <<= 1) d += __shfl_xor(d, off);
     if (lane == 0) a.dot_out[row] = d + a.dot_b[(long)grp * a.dot_b_gstride];
   }
+}
+
+// The reward classifier's head closed for labelling (vice.py:546,594: rewards = (sigmoid(classifier(next_obs)) >= 0.5) * 1.0): the
+// LayerNorm -> ReLU -> Dense(1) row of ln_tanh_row256 (one row per wave; the logit goes to a.dot_out as in the train=False
+// forward), then p = 1 / (1 + expf(-logit)) in fp32 (as jax.nn.sigmoid: a logit just below zero may round to 0.5) and
+// label = p >= 0.5f.  The mean label is taken inside the launch by the workgroup that arrives last (arrive_is_last: write-through
+// label stores, every wave drains, one ticket; the labels are read back past the L1): 256 strided partial sums in row order, then
+// a halving tree -- a fixed order, whichever workgroup is last.  Rows >= a.rows of the last workgroup compute nothing but arrive.
+__global__ __launch_bounds__(256) void label_rows_kernel(LnFwdArgs a, float* label, float* mean, int* ctr) {
+  __shared__ float red[256 + 1];   // partial sums and, behind them, the "I am last" flag (one LDS object)
+  const int tid = threadIdx.x, row = blockIdx.x * 4 + (tid >> 6), lane = tid & 63;
+  const __amdgpu_buffer_rsrc_t lab = rsrc_of(label);
+  if (row < a.rows) {
+    const float logit = ln_tanh_row256<false>(a, row, lane);
+    const float p = 1.f / (1.f + expf(-logit));
+    if (lane == 0) __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, p >= 0.5f ? 1.f : 0.f), lab, row * 4, 0, kSc1);
+  }
+  if (!arrive_is_last(ctr, (int)gridDim.x, reinterpret_cast<int*>(&red[256]))) return;
+  float s = 0.f;
+  for (int r = tid; r < a.rows; r += 256) s += ld1_sc1(lab, r);
+  red[tid] = s;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if (tid < o) red[tid] += red[tid + o];
+    __syncthreads();
+  }
+  if (tid == 0) mean[0] = red[0] / (float)a.rows;
+}
+
+int label_rows(const LnFwdArgs& a, float* label, float* mean, int* ctr, hipStream_t stream) {
+  SERL_REQUIRE(a.rows >= 1 && a.rows == a.rows_per_group && a.relu && a.dot_out && label && mean && ctr, "bad label launch");
+  SERL_LAUNCH_CHAIN(label_rows_kernel, dim3(cdiv(a.rows, 4)), dim3(256), 0, stream, a, label, mean, ctr);
+  SERL_HIP(hipGetLastError());
+  return SERL_OK;
 }
 
 int ln_tanh_fwd_multi(const LnFwdArgs* as, int n, int D, hipStream_t stream) {

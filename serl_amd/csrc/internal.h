@@ -163,4 +163,19 @@ struct GemmDesc {
 };
 int gemm_f32(const GemmDesc& g, hipStream_t stream);
 
+// --------------------------------------------------------------------------------------------
+// the reward classifier as the agent's reward labelling sees it (classifier.hip; vice.py:546,594)
+// --------------------------------------------------------------------------------------------
+struct ClassifierView {
+  serl_classifier_cfg cfg;
+  const float* trunk; long trunk_count;   // device: the frozen trunk's leaves, in add_trunk_leaves order
+  int64_t trunk_gen;                      // number of trunk leaves set so far
+};
+ClassifierView classifier_view(const serl_classifier* c);
+// label[i] = sigmoid(logit[i]) >= 0.5 of n rows, train=False, and mean[0] = their mean (device f32[n], [n], [1]; ctr: one zeroed
+// arrival counter).  cam_frames == nullptr: the head on trunk features that exist -- classifier camera k reads
+// feats + cam_of[k] * cam_stride ([n][h*w][512]).  Else the classifier's own trunk first, on cam_frames[k] (u8[n][H][W][3]).
+int classifier_label(serl_classifier* c, const float* feats, long cam_stride, const int* cam_of, const uint8_t* const* cam_frames,
+                     int n, float* label, float* logit, float* mean, int* ctr, hipStream_t stream);
+
 }  // namespace serl

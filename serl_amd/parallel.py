@@ -262,8 +262,26 @@ class DataParallelLearner:
         return self._call_noise.build(self._keys, self.Bl, self.noise_form, want_critic=critic, want_actor=not critic,
                                       shard=(self.rank * self.Bl, self.B), device_draws=self.device_noise == "threefry")
 
+    def _label(self):
+        """With a reward classifier attached to the core (AgentCore.set_reward_classifier) this rank labels its rows of the
+        selected batch (vice.py:546,594) and the critic phase reads the labels."""
+        if getattr(self.core, "reward_classifier", None) is not None:
+            self.core.label_rewards()
+
+    def vice_rewards(self) -> float:
+        """info["vice_rewards"] of vice.py:609 for the last labelled call: the mean label over the GLOBAL batch (the ranks hold
+        equal shares, so the mean of their means).  Synchronises."""
+        mean = self.core.read_reward_labels()[2]
+        if self.world > 1:
+            import torch
+            t = torch.tensor([mean], dtype=torch.float32, device=self.core.device)
+            self.all_reduce(t)
+            mean = float(t[0]) / self.world
+        return mean
+
     def _critic(self):
         noise = self._noise(True)
+        self._label()
         self.core.begin_update()
         if self._overlap and (self.world > 1 or self.force_reduce):
             self._critic_overlapped(noise)
@@ -352,11 +370,17 @@ class TrunkFarmLearner(DataParallelLearner):
             # order).  Nothing co-runs with the chain on this rank, so deeper splits pay: same call, updater alone, 512 -> 0.7406,
             # 1024 -> 0.7054, 2048 -> 0.7099, 4096 -> 0.7236 ms per step (profiles/r05_scaling_pieces.txt); bench.py passes 1024.
             core.set_chain_budget(0 if chain_budget is None else int(chain_budget))
+        self._label()
         self._t = 0                  # global batch counter (identical on every rank)
         self._recv_pending = {}      # slot -> handle
 
     def owner(self, t):
         return 1 + (t % self.n_workers)
+
+    def _label(self):
+        # (the updater never sees the frames and the workers hold no classifier: DESIGN.md section 5b)
+        if getattr(self.core, "reward_classifier", None) is not None:
+            raise NotImplementedError("the trunk farm does not label rewards: detach the reward classifier or use DataParallelLearner")
 
     def _reduce(self, which):
         pass        # one rank holds the parameters and sees the whole batch: there is no gradient to reduce
