@@ -139,8 +139,10 @@ int serl_rb_gather_packed(serl_rb* rb, int64_t* host_idx, int batch,
 
 /* Device batch consumed by the agent: the result of sample -> [concat_batches] -> _unpack ->
  * random-shift crop.  All pointers are device addresses owned by the caller.
- *   frames : u8 [2 (0=obs,1=next)][n_cam][batch][H][W][C]   (T==1)
- *   state  : f32[2][batch][S]
+ *   frames : u8 [2 (0=obs,1=next)][n_cam][batch][T][H][W][C]   (frame-planar: frame t of a stack is a whole H*W*C image)
+ *   state  : f32[2][batch][state_dim], state_dim = T * S (the T proprio vectors of a stack, oldest first)
+ * T = num_stack (0 means 1, so a zero-initialised struct describes the single-frame batch it always did).  Observation frame
+ * t is frame t of the packed T+1 window and next-observation frame t is frame t+1 (utils/train_utils.py:53-64).
  */
 typedef struct serl_batch {
   int batch, n_cam, H, W, C, state_dim, act_dim;
@@ -150,14 +152,17 @@ typedef struct serl_batch {
   float* reward;
   float* mask;
   uint8_t* done;
+  int num_stack;           /* T: frames per observation; 0 = 1 */
 } serl_batch;
 
 /* Fused sample-gather + concat_batches + _unpack + DrQ random shift (K2+K3+K4 of SURVEY.md):
  * memory_efficient_replay_buffer.py:126-164 + utils/train_utils.py:16-31,44-66 +
  * vision/data_augmentations.py:7-36 + agents/continuous/drq.py:244-253 (same offsets for every
  * camera).  Samples [0,counts[0]) come from rbs[0], the next counts[1] from rbs[1] (RLPD 50/50).
- * host_crop_obs / host_crop_next: int32[batch][2] = (dy,dx) in [0,8]; NULL = no shift (4,4).
- * host_idx[b]: IN/OUT like serl_rb_gather_packed's (stale indices are re-drawn in place). */
+ * host_crop_obs / host_crop_next: int32[batch*T][2] = (dy,dx) in [0,8], entry b*T + t for frame t of sample b (every frame of
+ * a stack has its own offset: batched_random_crop with num_batch_dims=2 splits its key B*T ways); NULL = no shift (4,4).
+ * host_idx[b]: IN/OUT like serl_rb_gather_packed's (stale indices are re-drawn in place).
+ * Stores with num_stack T > 1 need out->num_stack == T and out->state_dim == T * S (SERL_ERR_INVALID otherwise). */
 int serl_rb_gather_crop(serl_rb* const* rbs, int n_rb, int64_t* const* host_idx,
                         const int* counts, const int32_t* host_crop_obs,
                         const int32_t* host_crop_next, const serl_batch* out, void* stream);
@@ -168,6 +173,12 @@ int serl_rb_gather_crop(serl_rb* const* rbs, int n_rb, int64_t* const* host_idx,
 int serl_crop_packed(int device, const uint8_t* const* dev_packed, int n_cam, int batch, int H,
                      int W, int C, const int32_t* host_crop_obs, const int32_t* host_crop_next,
                      uint8_t* dev_frames_out, void* stream);
+/* The same for frame stacks: dev_packed[c] u8[batch][T+1][H][W][C] -> dev_frames_out u8[2][n_cam][batch][T][H][W][C], observation
+ * frame t = packed frame t, next frame t = packed frame t+1; crop tables int32[batch*T][2] (entry b*T + t), NULL = no shift.
+ * 1 <= num_stack <= 4.  serl_crop_packed is this function with num_stack == 1. */
+int serl_crop_packed_stacked(int device, const uint8_t* const* dev_packed, int n_cam, int batch, int num_stack, int H,
+                             int W, int C, const int32_t* host_crop_obs, const int32_t* host_crop_next,
+                             uint8_t* dev_frames_out, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * DrQ / SAC agent  (agents/continuous/drq.py, agents/continuous/sac.py, common/common.py)
@@ -220,6 +231,12 @@ typedef struct serl_agent_cfg {
   int critic_subsample_size; /* sac.py:150-161: 0 = 2 (utils/launcher.py), -1 = None (minimum over all members), else 1..16 */
   int backup_entropy;        /* sac.py:174-176: target_q -= alpha * log pi(a'|s') */
   int tx_lr_set[3];          /* != 0: tx_lr[t] was given explicitly and is honoured even when it is 0 */
+  /* T, frames per observation (0 = 1; at most 4).  EncodingWrapper(enable_stacking=True) folds a stack into the channels
+   * (common/encoding.py:39-44,58-64: "B T H W C -> B H W (T C)", "B T S -> B (T S)"), so the SmallEncoder's first kernel is
+   * (3,3,3T,32) with input channel t*3 + c = channel c of frame t, and state_dim above is the FLATTENED width T * S.
+   * T > 1 is served for SERL_ENCODER_SMALL only: the pretrained ResNet-10's conv_init kernel is (7,7,3,64) and cannot be
+   * applied to 3T channels (SERL_ERR_UNSUPPORTED). */
+  int num_stack;
 } serl_agent_cfg;
 #define SERL_ENCODER_RESNET_PRETRAINED 0
 #define SERL_ENCODER_SMALL 1
@@ -352,7 +369,7 @@ int serl_agent_set_shard(serl_agent* a, int64_t global_offset, int64_t global_ba
 int serl_agent_grad_view(serl_agent* a, int which, float** dev_ptr, int64_t* count);
 
 /* SACAgent.sample_actions (sac.py:301-320): policy forward with train=False on `n` observations
- * (frames u8[n_cam][n][H][W][3], state f32[n][S], both device); eps f32[n][A] device or NULL for
+ * (frames u8[n_cam][n][T][H][W][3], state f32[n][T*S], both device; T = cfg.num_stack); eps f32[n][A] device or NULL for
  * argmax (= distribution mode).  out_actions f32[n][A] device. */
 int serl_agent_sample_actions(serl_agent* a, const uint8_t* dev_frames, const float* dev_state, int n,
                               const float* dev_eps, float* dev_out_actions, void* stream);
@@ -410,7 +427,7 @@ int serl_classifier_logits_from_features(serl_classifier* c, const float* dev_fe
  * not built; the classifier is trained by serl_classifier_train_step.
  * serl_agent_set_reward_classifier attaches `c` (NULL detaches).  cam_of: host int[classifier n_cam], the agent camera each
  * classifier camera reads.  Refused: a state-only agent, a camera index the agent lacks, another image size or device, a
- * classifier max_batch below the agent's batch.  *mode_out (may be NULL) = SERL_LABEL_FEATURES when the agent has a frozen
+ * classifier max_batch below the agent's batch, an agent with num_stack > 1 (the classifier reads single frames).  *mode_out (may be NULL) = SERL_LABEL_FEATURES when the agent has a frozen
  * trunk whose every leaf is bit-identical to the classifier's (compared here, once): the classifier's head then runs on the
  * trunk features of the augmented next observations that the agent's slot already holds; else SERL_LABEL_FRAMES: the
  * classifier's own trunk runs on the batch's augmented next frames.  Both handles count the trunk leaves set on them; a trunk

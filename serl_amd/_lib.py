@@ -26,6 +26,7 @@ class SerlBatch(C.Structure):
         ("state_dim", C.c_int), ("act_dim", C.c_int),
         ("frames", C.c_void_p), ("state", C.c_void_p), ("action", C.c_void_p),
         ("reward", C.c_void_p), ("mask", C.c_void_p), ("done", C.c_void_p),
+        ("num_stack", C.c_int),   # T, frames per observation; 0 = 1
     ]
 
 
@@ -67,6 +68,7 @@ SIGNATURES = {
     "serl_rb_gather_packed": [vp, vp, i32, P(vp), vp, vp, vp, vp, vp, vp, vp],
     "serl_rb_gather_crop": [P(vp), i32, P(vp), P(i32), vp, vp, P(SerlBatch), vp],
     "serl_crop_packed": [i32, P(vp), i32, i32, i32, i32, i32, vp, vp, vp, vp],
+    "serl_crop_packed_stacked": [i32, P(vp), i32, i32, i32, i32, i32, i32, vp, vp, vp, vp],
     "serl_profile_enable": [i32],
     "serl_profile_reset": [],
     "serl_profile_read": [i32, vp, vp, vp, P(i32)],

@@ -21,6 +21,7 @@ class SerlAgentCfg(C.Structure):
         ("critic_subsample_size", C.c_int),   # 0 = 2, -1 = None (all members), else 1..16
         ("backup_entropy", C.c_int),
         ("tx_lr_set", C.c_int * 3),   # != 0: tx_lr[t] given explicitly (0.0 is a valid optax learning rate)
+        ("num_stack", C.c_int),   # T, frames per observation (0 = 1); state_dim is then the flattened width T * S
     ]
 
 

@@ -21,9 +21,10 @@ class AgentCore(Handle):
                  bottleneck=256, sle_features=8, proprio_dim=64, warmup_steps=0, discount=0.96,
                  tau=0.005, lr=3e-4, dropout=0.1, std_min=1e-5, std_max=5.0, target_entropy=None,
                  seed=0, temp_warmup_steps=-1, optimizers=None, encoder_type="resnet-pretrained",
-                 critic_subsample_size=2, backup_entropy=False):
+                 critic_subsample_size=2, backup_entropy=False, num_stack=1):
         """optimizers: optional {"actor"|"critic"|"temperature": make_optimizer kwargs (common/optimizers.py:6-13:
-        learning_rate, warmup_steps, cosine_decay_steps, weight_decay, clip_grad_norm)} overriding lr / warmup_steps."""
+        learning_rate, warmup_steps, cosine_decay_steps, weight_decay, clip_grad_norm)} overriding lr / warmup_steps.
+        num_stack: T, frames per observation (SmallEncoder only); state_dim is then the flattened width T * S."""
         if target_entropy is None:
             target_entropy = -act_dim / 2
         self.cfg = SerlAgentCfg(device, n_cam, H, W, state_dim, act_dim, batch, ensemble, hidden,
@@ -35,6 +36,7 @@ class AgentCore(Handle):
             raise ValueError(f"critic_subsample_size must be None or in [1, 16] (got {critic_subsample_size})")
         self.cfg.critic_subsample_size = -1 if critic_subsample_size is None else int(critic_subsample_size)
         self.cfg.backup_entropy = 1 if backup_entropy else 0
+        self.cfg.num_stack = int(num_stack)
         for name, kw in (optimizers or {}).items():
             i = TX_INDEX[name]
             bad = set(kw) - {"learning_rate", "warmup_steps", "cosine_decay_steps", "weight_decay", "clip_grad_norm"}

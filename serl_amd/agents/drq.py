@@ -133,6 +133,7 @@ class DrQAgent:
         self.core = core
         self.image_keys = tuple(image_keys)
         self.config = config
+        self.num_stack = max(int(core.cfg.num_stack), 1)     # T, frames per observation (ChunkingWrapper(obs_horizon=T))
         self._np_rng = np.random.Generator(np.random.PCG64(np.random.SeedSequence([seed, 0xD1CE])))
         # RANDOMNESS.  "threefry" (default): the reference's own stream -- crop offsets, REDQ indices, policy noise and Dropout
         # masks are drawn from jax.random's threefry2x32 with the reference's key schedule (serl_amd/jaxrng.py), and `state.rng`
@@ -173,6 +174,10 @@ class DrQAgent:
         """drq.py:104-242.  Only the configuration the reference's examples run is built natively:
         encoder_type="resnet-pretrained", use_proprio=True, REDQ subsample 2, tanh-squashed
         exp-parameterised policy, LayerNorm+tanh 256x256 MLPs (utils/launcher.py:79-116).
+        Frame stacks: the sample observation carries T = observations[image_key].shape[0] frames and a (T, S) state, as
+        ChunkingWrapper(obs_horizon=T) produces them; EncodingWrapper(enable_stacking=True) folds them into the channels and the
+        proprio width (common/encoding.py:39-44,58-64).  T in 1..4 with encoder_type="small"; the pretrained ResNet-10 cannot take
+        a stack (its conv_init kernel has 3 input channels).
         param_init: "numpy" (default) draws the trainable leaves from host NumPy streams seeded by `rng`; "reference" draws them
         as the reference's model_def.init(init_rng) does (utils/init_ref.py); the frozen trunk is the same either way."""
         if encoder_type not in ("resnet-pretrained", "small"):
@@ -190,7 +195,18 @@ class DrQAgent:
         image_keys = tuple(image_keys)
         img = np.asarray(observations[image_keys[0]])
         H, W = img.shape[-3], img.shape[-2]
-        S = int(np.asarray(observations["state"]).shape[-1])
+        st0 = np.asarray(observations["state"])
+        T = int(img.shape[-4]) if img.ndim >= 4 else 1
+        if T > 1:
+            if st0.ndim < 2 or st0.shape[-2] != T:
+                raise ValueError(f"observations[{image_keys[0]!r}] stacks {T} frames, observations['state'] has shape {st0.shape}: "
+                                 f"expected ({T}, S)")
+            if encoder_type == "resnet-pretrained":
+                raise NotImplementedError(
+                    f"num_stack {T} with encoder_type='resnet-pretrained': the stack is folded into {3 * T} channels "
+                    "(common/encoding.py:39-44) and the pretrained ResNet-10's conv_init kernel (7,7,3,64) takes 3; "
+                    "use encoder_type='small'")
+        S = int(st0.shape[-1]) * T      # the proprio Dense's input: "B T S -> B (T S)" (common/encoding.py:58-64)
         A = int(np.asarray(actions).shape[-1])
         if target_entropy is None:
             target_entropy = -A / 2  # drq.py:88-89
@@ -203,13 +219,13 @@ class DrQAgent:
                          tau=soft_target_update_rate, lr=learning_rate, std_min=pk.get("std_min", 1e-5),
                          std_max=pk.get("std_max", 10.0), target_entropy=target_entropy, seed=seed,
                          optimizers={k: {"warmup_steps": 0, **v} for k, v in opts.items()}, encoder_type=encoder_type,
-                         critic_subsample_size=critic_subsample_size, backup_entropy=backup_entropy)
+                         critic_subsample_size=critic_subsample_size, backup_entropy=backup_entropy, num_stack=T)
         if init_ref.check_param_init(param_init):
             theta = init_ref.theta_reference(image_keys, H, W, S, A, rng, ensemble=critic_ensemble_size, encoder_type=encoder_type,
-                                             temperature_init=temperature_init, device=device)
+                                             temperature_init=temperature_init, device=device, num_stack=T)
         else:
             theta = pinit.init_theta(len(image_keys), H, W, S, A, seed=seed, temperature_init=temperature_init,
-                                     ensemble=critic_ensemble_size, encoder_type=encoder_type)
+                                     ensemble=critic_ensemble_size, encoder_type=encoder_type, num_stack=T)
         trunk = pinit.init_trunk(seed=seed) if encoder_type == "resnet-pretrained" else {}
         for sec in ("params", "target_params"):  # JaxRLTrainState.create(target_params=params)
             core.load_flat(sec, theta)
@@ -299,18 +315,20 @@ class DrQAgent:
     def _device_batch(self, B):
         c = self.core.cfg
         if self._batch is None or self._batch.batch != B:
-            self._batch = DeviceBatch(B, c.n_cam, c.H, c.W, 3, c.state_dim, c.act_dim, c.device)
+            self._batch = DeviceBatch(B, c.n_cam, c.H, c.W, 3, c.state_dim, c.act_dim, c.device, self.num_stack)
         return self._batch
 
     def _draw_crops(self, B, rng=None):
         """data_augmentation_fn (drq.py:244-253): one (dy, dx) in [0, 8] per frame, the SAME for every camera; obs and next_obs
-        use independent keys (drq.py:279-281).  `rng`: state.rng at the entry of the call that consumes the batch (None: the
+        use independent keys (drq.py:279-281).  A stack of T frames draws B*T offsets per stream, entry b*T + t for frame t of
+        sample b: batched_random_crop(num_batch_dims=2) flattens to B*T images and splits its key B*T ways.  `rng`: state.rng at the entry of the call that consumes the batch (None: the
         current one) -- rng, obs_rng, next_obs_rng = split(rng, 3); offsets = batched_random_crop's (data_augmentations.py:22-36)."""
+        n = B * self.num_stack
         if self.rng_impl != "threefry":
-            co = self._np_rng.integers(0, 9, size=(B, 2)).astype(np.int32)
-            cn = self._np_rng.integers(0, 9, size=(B, 2)).astype(np.int32)
+            co = self._np_rng.integers(0, 9, size=(n, 2)).astype(np.int32)
+            cn = self._np_rng.integers(0, 9, size=(n, 2)).astype(np.int32)
             return co, cn
-        return J.crop_pair(self._rng_key if rng is None else rng, B)
+        return J.crop_pair(self._rng_key if rng is None else rng, n)
 
     # ------------------------------------------------------------------ the reference's random stream for one call
     def _call_keys(self, n_critic, has_actor_temp, drq_aug=None, combined=False):
@@ -342,6 +360,9 @@ class DrQAgent:
             return batch
         if isinstance(batch, LazyBatch):
             B = batch.batch_size
+            if self.core.cfg.n_cam > 0 and batch.num_stack != self.num_stack:
+                raise ValueError(f"the batch comes from a store of stacks of {batch.num_stack} frames, this agent was built for "
+                                 f"num_stack {self.num_stack}")
             out = self._device_batch(B)
             co, cn = crops if crops is not None else self._draw_crops(B)
             self.last_draws["crop_obs"], self.last_draws["crop_next"] = co, cn
@@ -354,19 +375,26 @@ class DrQAgent:
         out = self._device_batch(B)
         co, cn = crops if crops is not None else self._draw_crops(B)
         self.last_draws["crop_obs"], self.last_draws["crop_next"] = co, cn
-        keep, ptrs = [], (C.c_void_p * len(self.image_keys))()
+        keep, ptrs, T = [], (C.c_void_p * len(self.image_keys))(), self.num_stack
         for i, k in enumerate(self.image_keys):
-            if k in nobs:  # unpacked: re-pack [B,2,H,W,C] (train_utils._unpack inverse)
+            if k in nobs and T == 1:  # unpacked: re-pack [B,2,H,W,C] (train_utils._unpack inverse)
                 p = torch.cat([obs[k], nobs[k]], dim=1).contiguous()
+            elif k in nobs:           # unpacked stacks [B,T,...]: the window is obs frames 0..T-1 + the last next frame
+                if not torch.equal(obs[k][:, 1:], nobs[k][:, :-1]):
+                    raise ValueError(f"observations[{k!r}][:, 1:] differs from next_observations[{k!r}][:, :-1]: not the two "
+                                     "views of one packed window (train_utils._unpack)")
+                p = torch.cat([obs[k][:, :T], nobs[k][:, -1:]], dim=1).contiguous()
             else:
                 p = obs[k].contiguous()
-            assert p.shape[1] == 2, "only num_stack == 1 (T=1) is supported"
+            if p.shape[1] != T + 1:
+                raise ValueError(f"a packed window of {p.shape[1]} frames under {k!r}: this agent was built for num_stack {T} "
+                                 f"({T + 1} frames)")
             keep.append(p)
             ptrs[i] = p.data_ptr()
         c = self.core.cfg
         s = torch.cuda.current_stream(self.core.device).cuda_stream
-        _lib.check(_lib.lib().serl_crop_packed(c.device, ptrs, c.n_cam, B, c.H, c.W, 3, co.ctypes.data,
-                                               cn.ctypes.data, out.frames.data_ptr(), C.c_void_p(s)))
+        _lib.check(_lib.lib().serl_crop_packed_stacked(c.device, ptrs, c.n_cam, B, T, c.H, c.W, 3, co.ctypes.data,
+                                                       cn.ctypes.data, out.frames.data_ptr(), C.c_void_p(s)))
         out.state[0].copy_(obs["state"].reshape(B, -1))
         out.state[1].copy_(nobs["state"].reshape(B, -1))
         out.action.copy_(batch["actions"])
@@ -392,7 +420,7 @@ class DrQAgent:
                 self._sched.side_stream.synchronize()
                 if getattr(self._sched, "gather_stream", None) is not None:
                     self._sched.gather_stream.synchronize()
-            self._slot_batches[slot] = DeviceBatch(B, c.n_cam, c.H, c.W, 3, c.state_dim, c.act_dim, c.device)
+            self._slot_batches[slot] = DeviceBatch(B, c.n_cam, c.H, c.W, 3, c.state_dim, c.act_dim, c.device, self.num_stack)
         return self._slot_batches[slot]
 
     def _produce(self, batch: LazyBatch, slot, db, rng=None):
@@ -518,7 +546,7 @@ class DrQAgent:
             db = batch
         else:  # identity crop (offset 4 = centre of the 9 shifts): the batch is taken as already augmented
             n = batch.batch_size if isinstance(batch, LazyBatch) else int(batch["rewards"].shape[0])
-            db = self.prepare(batch, crops=(np.full((n, 2), 4, np.int32),) * 2)
+            db = self.prepare(batch, crops=(np.full((n * self.num_stack, 2), 4, np.int32),) * 2)
         self._sync_side_stream()
         # SACAgent.update (sac.py:243-299): no augmentation split; every selected loss takes its key from ONE 4-way split
         nets = set(networks_to_update)
@@ -529,14 +557,16 @@ class DrQAgent:
 
     # ------------------------------------------------------------------ acting
     def sample_actions(self, observations, *, seed=None, argmax: bool = False, **kwargs):
-        """sac.py:301-320: policy forward with train=False; sample (external seed) or mode."""
+        """sac.py:301-320: policy forward with train=False; sample (external seed) or mode.  Observations are (T, H, W, 3) frames
+        and a (T, S) state per sample (T = num_stack; the T axis of a single-frame agent may be missing), batched or not."""
         if argmax:
             assert seed is None, "Cannot specify seed when sampling deterministically"
         c = self.core.cfg
         st = np.asarray(observations["state"], np.float32)
         batched = st.ndim == 3
         n = st.shape[0] if batched else 1
-        frames = np.stack([np.asarray(observations[k], np.uint8).reshape(n, c.H, c.W, 3) for k in self.image_keys])
+        fshape = (n,) + ((self.num_stack,) if self.num_stack > 1 else ()) + (c.H, c.W, 3)
+        frames = np.stack([np.asarray(observations[k], np.uint8).reshape(fshape) for k in self.image_keys])
         self._sync_side_stream()
         f = torch.from_numpy(frames).to(self.core.device)
         s = torch.from_numpy(st.reshape(n, -1)).to(self.core.device)

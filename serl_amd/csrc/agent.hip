@@ -184,7 +184,8 @@ void build_layout(serl_agent* a) {
     if (a->small) {   // per layer [9*cin + 1][cout]: kernel (HWIO) immediately followed by the bias (small_encoder.hip)
       o.cam[k].conv = off;
       for (int l = 0; l < kSmallLayers; ++l) {
-        add_leaf(L, off, p + "conv" + std::to_string(l) + "/kernel", 9L * kSmallFeat[l] * kSmallFeat[l + 1]);
+        // (layer 0 of a stacked agent takes the T frames as 3T channels: kernel (3,3,3T,32), common/encoding.py:39-44)
+        add_leaf(L, off, p + "conv" + std::to_string(l) + "/kernel", 9L * kSmallFeat[l] * (l == 0 ? c.num_stack : 1) * kSmallFeat[l + 1]);
         add_leaf(L, off, p + "conv" + std::to_string(l) + "/bias", kSmallFeat[l + 1]);
       }
       o.cam[k].sle = o.cam[k].conv;
@@ -313,8 +314,8 @@ size_t carve(serl_agent* a, void* base) {
   a->labels = b.take<float>(B); a->label_logits = b.take<float>(B); a->label_mean = b.take<float>(1);
   a->label_ctr = b.take<int>(1);
   if (a->small) {
-    void* smem = b.take<uint8_t>(small_workspace_bytes(c.n_cam * c.batch, c.H, c.W));
-    if (base) small_workspace_bind(a->sws, smem, c.n_cam * c.batch, c.H, c.W);
+    void* smem = b.take<uint8_t>(small_workspace_bytes(c.n_cam * c.batch, c.H, c.W, c.num_stack));
+    if (base) small_workspace_bind(a->sws, smem, c.n_cam * c.batch, c.H, c.W, c.num_stack);
   } else if (!a->state_only) {
     const int nimg = 2 * c.n_cam * c.batch;
     void* tmem = b.take<uint8_t>(trunk_workspace_bytes(nimg, c.H, c.W));
@@ -410,7 +411,7 @@ int encode_multi(serl_agent* a, const EncJob* jobs, int n, int off, int cnt, hip
       for (int k = i + 1; k < n; ++k)
         if (jobs[k].P == j.P && jobs[k].which == j.which) dup = k;
       if (dup >= 0) { gd[i].A = jobs[dup].e->f; continue; }
-      const uint8_t* fr = a->cur.frames + (((size_t)j.which * c.n_cam) * Bfull + off) * fbytes;
+      const uint8_t* fr = a->cur.frames + (((size_t)j.which * c.n_cam) * Bfull + off) * c.num_stack * fbytes;   // an image = T frames
       RC(small_forward(a->sws, j.P, o.cam[0].conv, o.cam_stride, fr, Bfull, c.n_cam, cnt, j.e->f, (long)c.batch * a->D, st));
     }
   } else if (a->fuse) {   // channel-blocked SLE (+ hashed Dropout mask) with the proprio branch as extra workgroups of the launch
@@ -868,6 +869,16 @@ int serl_agent_create(const serl_agent_cfg* cfg, serl_agent** out) {
   SERL_REQUIRE(cfg->proprio_dim == 64, "proprio_dim must be 64");
   SERL_REQUIRE(cfg->sle_features == 8, "sle_features must be 8");
   SERL_REQUIRE(cfg->batch >= 1 && cfg->ensemble >= 2 && cfg->state_dim >= 1 && cfg->act_dim >= 1 && cfg->act_dim <= 64, "bad dims");
+  const int num_stack = cfg->num_stack > 0 ? cfg->num_stack : 1;   // 0 = 1: a zero-initialised field keeps its meaning
+  SERL_REQUIRE(cfg->num_stack >= 0 && num_stack <= kSmallMaxStack, "num_stack %d not in [1,%d]", cfg->num_stack, kSmallMaxStack);
+  if (num_stack > 1 && cfg->n_cam > 0 && cfg->encoder_type == SERL_ENCODER_RESNET_PRETRAINED) {
+    set_error("num_stack %d with the pretrained ResNet-10: its conv_init kernel is (7,7,3,64), 3 input channels, and cannot be applied "
+              "to the %d channels of a folded stack (common/encoding.py:39-44); frame stacks are served with SERL_ENCODER_SMALL", num_stack, 3 * num_stack);
+    return SERL_ERR_UNSUPPORTED;
+  }
+  SERL_REQUIRE(num_stack == 1 || cfg->n_cam > 0, "num_stack %d on a state-only agent: its state path has no stacking wrapper", num_stack);
+  SERL_REQUIRE(cfg->state_dim % num_stack == 0, "state_dim %d is not num_stack %d proprio vectors (state_dim is the flattened width T * S)",
+               cfg->state_dim, num_stack);
   for (int t = 0; t < 3; ++t) {
     // adamw decays EVERY leaf of the tree the optimizer is given (common.py:142-147 passes the full params), i.e. it
     // would un-freeze the pretrained trunk and make the online and target trunks differ, which the two-pass trunk
@@ -882,6 +893,7 @@ int serl_agent_create(const serl_agent_cfg* cfg, serl_agent** out) {
   SERL_HIP(hipSetDevice(cfg->device));
   serl_agent* a = new serl_agent();
   a->cfg = *cfg;
+  a->cfg.num_stack = num_stack;
   { const char* e = getenv("SERL_CHAIN_FUSE"); a->fuse = !(e && e[0] == '0'); }
   build_layout(a);
   if (int rc = alloc_zeroed(&a->arena, carve(a, nullptr), "agent arena")) {
@@ -1017,6 +1029,8 @@ static int check_batch(serl_agent* a, const serl_batch* b) {
   SERL_REQUIRE(b->batch >= 1 && b->batch <= c.batch, "batch %d not in [1,%d]", b->batch, c.batch);
   SERL_REQUIRE(b->n_cam == c.n_cam && (c.n_cam == 0 || (b->H == c.H && b->W == c.W && b->C == 3)) &&
                    b->state_dim == c.state_dim && b->act_dim == c.act_dim, "serl_batch shape does not match the agent");
+  SERL_REQUIRE((b->num_stack > 0 ? b->num_stack : 1) == c.num_stack, "serl_batch.num_stack %d does not match the agent's num_stack %d",
+               b->num_stack > 0 ? b->num_stack : 1, c.num_stack);
   return SERL_OK;
 }
 
@@ -1129,6 +1143,8 @@ int serl_agent_set_reward_classifier(serl_agent* a, serl_classifier* cls, const 
   SERL_REQUIRE(cam_of, "NULL camera map");
   const serl_agent_cfg& c = a->cfg;
   SERL_REQUIRE(!a->state_only, "a state-only agent has no frames for a reward classifier to label");
+  SERL_REQUIRE(c.num_stack == 1, "the reward classifier reads single frames (its pretrained conv_init takes 3 channels): an agent with num_stack %d "
+               "cannot be labelled by it", c.num_stack);
   const ClassifierView v = classifier_view(cls);
   SERL_REQUIRE(v.cfg.device == c.device, "the classifier lives on device %d, the agent on %d", v.cfg.device, c.device);
   for (int k = 0; k < v.cfg.n_cam; ++k)
@@ -1533,6 +1549,8 @@ int serl_agent_debug_get(serl_agent* a, const char* what, float* host_out, int64
   else if (w == "feats") { p = a->feats; n = 2L * c.n_cam * c.batch * a->HW * 512; }
   else if (w == "logp") { p = a->pol.logp; n = c.batch; }
   else if (w == "dx") { p = a->dx; n = (long)c.batch * a->XA; }
+  // SmallEncoder layer 0's ReLU output of the LAST encoder pass, [n_cam][images of that pass][h1][w1][32]
+  else if (w == "small_act0" && a->small) { p = a->sws.act[0]; n = (long)c.n_cam * c.batch * a->sws.d.h[1] * a->sws.d.w[1] * kSmallFeat[1]; }
   else { set_error("unknown debug tap '%s'", what); return SERL_ERR_INVALID; }
   SERL_REQUIRE(count <= n && count > 0, "tap '%s' holds %ld floats, asked for %lld", what, n, (long long)count);
   SERL_HIP(hipDeviceSynchronize());

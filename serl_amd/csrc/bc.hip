@@ -281,6 +281,7 @@ int check_batch(serl_bc* c, const serl_batch* b) {
   SERL_REQUIRE(b->batch >= 1 && b->batch <= g.max_batch, "batch %d not in [1,%d]", b->batch, g.max_batch);
   SERL_REQUIRE(b->n_cam == g.n_cam && b->H == g.H && b->W == g.W && b->C == 3 && b->state_dim == g.state_dim &&
                    b->act_dim == g.act_dim, "serl_batch shape does not match the BC agent");
+  SERL_REQUIRE(b->num_stack <= 1, "the BC agent takes single-frame observations (serl_batch.num_stack %d)", b->num_stack);
   return SERL_OK;
 }
 

@@ -5,6 +5,7 @@
 // Device side: one fused kernel = sample gather + concat_batches + _unpack + DrQ random shift
 // (K2+K3+K4).  It is HBM-bound u8 traffic: every source frame row is pulled once with 16-byte
 // coalesced loads into LDS, shifted/clamped out of LDS, and written once with 16-byte stores.
+#include <algorithm>
 #include <condition_variable>
 #include <cstring>
 #include <memory>
@@ -14,6 +15,7 @@
 #include "common.h"
 #include "prof.h"
 #include "replay_index.h"
+#include "stack_index.h"
 
 namespace serl {
 
@@ -28,6 +30,7 @@ void set_error(const char* fmt, ...) {
 constexpr int kRing = 8;           // staging slots for per-call index/crop parameters
 constexpr int kInsRing = 32;       // pinned staging slots for inserted transitions (one slot write each)
 constexpr int kRowsPerBlock = 32;  // output rows per workgroup in the gather/crop kernel
+constexpr int kMaxStack = 4;       // most frames per observation the crop kernels and the agent serve (serl_agent_cfg.num_stack)
 constexpr size_t kXferChunk = (size_t)8 << 20;  // bytes per pinned staging buffer of the snapshot export / import (two of them)
 
 // A ring of `n` pinned host slots (and, if asked for, as many device slots) with one event per slot.  acquire() hands out the
@@ -117,17 +120,18 @@ struct GatherArgs {
   const int64_t* idx[SERL_MAX_BUFFERS];  // device, per buffer
   int64_t cap[SERL_MAX_BUFFERS];
   int count0;                            // samples [0,count0) come from buffer 0
-  int batch, n_cam, H, W, C, S, A, rec_len;
-  const int32_t* crop_obs;   // device [batch][2] or nullptr
-  const int32_t* crop_next;  // device [batch][2] or nullptr
-  uint8_t* out_frames;       // [2][n_cam][batch][H][W][C]
+  int batch, n_cam, H, W, C, S, A, rec_len;   // S = floats of one observation's state (T * state_dim of the store)
+  int T;                     // frames per observation (num_stack)
+  const int32_t* crop_obs;   // device [batch*T][2] or nullptr
+  const int32_t* crop_next;  // device [batch*T][2] or nullptr
+  uint8_t* out_frames;       // [2][n_cam][batch][T][H][W][C]
   float* out_state;          // [2][batch][S]
   float* out_action;         // [batch][A]
   float* out_reward;
   float* out_mask;
   uint8_t* out_done;
   int n_frame_blocks;
-  // packed mode (serl_crop_packed): source is dev_packed[c] u8[batch][2][H][W][C]
+  // packed mode (serl_crop_packed_stacked): source is dev_packed[c] u8[batch][T+1][H][W][C]
   const uint8_t* packed[SERL_MAX_CAMS];
   int from_packed;
 };
@@ -149,32 +153,30 @@ struct PackedArgs {
 // cap - T + (idx - T) (reference quirk for a valid slot below T, see oracle/replay_oracle.py gather()).
 __device__ __forceinline__ const uint8_t* window_frame(const uint8_t* frames, const int64_t* idx, int j, int T, int64_t cap, int t,
                                                        size_t fbytes) {
-  int64_t start = idx[j] - T;
-  if (start < 0) start += cap - T;
-  return frames + (size_t)(start + t) * fbytes;
+  return frames + (size_t)window_slot(idx[j], T, cap, t) * fbytes;
 }
-// source frame of (which, cam, sample i): which 0 = observation frame (slot idx-1), 1 = next frame (slot idx); T == 1 here.
+// source frame of (which, cam, sample i, stack frame t): frame which + t of the T+1 window (train_utils.py:53-64: observation =
+// frames 0..T-1, next observation = frames 1..T; T == 1: slot idx-1 and slot idx).
 // Samples [0,count0) come from buffer 0, the rest from buffer 1.
-__device__ __forceinline__ const uint8_t* source_frame(const GatherArgs& a, int which, int cam, int i, size_t fbytes) {
-  if (a.from_packed) return a.packed[cam] + ((size_t)i * 2 + which) * fbytes;
-  const int buf = (i < a.count0) ? 0 : 1;
-  return window_frame(a.frames[buf][cam], a.idx[buf], buf == 0 ? i : i - a.count0, 1, a.cap[buf], which, fbytes);
+__device__ __forceinline__ const uint8_t* source_frame(const GatherArgs& a, const StackJob& j, size_t fbytes) {
+  if (a.from_packed) return a.packed[j.cam] + (size_t)stack_packed_frame(j, a.T) * fbytes;
+  const int buf = (j.i < a.count0) ? 0 : 1;
+  return window_frame(a.frames[buf][j.cam], a.idx[buf], buf == 0 ? j.i : j.i - a.count0, a.T, a.cap[buf], j.which + j.t, fbytes);
 }
-// (dy, dx) of sample i; without a table it is the identity crop (4, 4)
+// (dy, dx) of frame i (= sample * T + stack frame); without a table it is the identity crop (4, 4)
 __device__ __forceinline__ int2 crop_offset(const int32_t* crop, int i) {
   return make_int2(crop ? crop[2 * i] : 4, crop ? crop[2 * i + 1] : 4);
 }
-// frame workgroup -> (part of the frame, sample, camera, which), part fastest; with the source frame and the shift (sy, sx)
-struct FrameJob { int part, i, cam, which, sy, sx; const uint8_t* src; };
+// frame workgroup -> (part of the frame, stack frame, sample, camera, which) (stack_index.h), with the source frame, the shift
+// (sy, sx) and the frame's place in out_frames
+struct FrameJob { int part, which, sy, sx; const uint8_t* src; size_t dst_frame; };
 __device__ __forceinline__ FrameJob frame_job(const GatherArgs& a, int parts, size_t fbytes) {
+  const StackJob s = stack_job((int)blockIdx.x, parts, a.T, a.batch, a.n_cam);
   FrameJob j;
-  int bid = blockIdx.x;
-  j.part = bid % parts; bid /= parts;
-  j.i = bid % a.batch; bid /= a.batch;
-  j.cam = bid % a.n_cam;
-  j.which = bid / a.n_cam;
-  j.src = source_frame(a, j.which, j.cam, j.i, fbytes);
-  const int2 c = crop_offset(j.which == 0 ? a.crop_obs : a.crop_next, j.i);
+  j.part = s.part; j.which = s.which;
+  j.src = source_frame(a, s, fbytes);
+  j.dst_frame = (size_t)stack_dst_frame(s, a.T, a.batch, a.n_cam);
+  const int2 c = crop_offset(j.which == 0 ? a.crop_obs : a.crop_next, stack_crop_entry(s, a.T));
   j.sy = c.x - 4;
   j.sx = c.y - 4;
   return j;
@@ -259,7 +261,7 @@ __global__ __launch_bounds__(256) void gather_crop_kernel(GatherArgs a) {
       *reinterpret_cast<uint4*>(lds + r * lds_stride + q * 16) = val;
     }
     __syncthreads();
-    uint8_t* dst = a.out_frames + (((size_t)j.which * a.n_cam + j.cam) * a.batch + j.i) * fbytes + (size_t)h0 * rowb;
+    uint8_t* dst = a.out_frames + j.dst_frame * fbytes + (size_t)h0 * rowb;
     for (int v = tid; v < nrows * vec_per_row; v += 256) {
       const int r = v / vec_per_row, q = v - r * vec_per_row;
       const uint4 val = shifted_chunk<CT>(lds + r * lds_stride, q, j.sx, a.W, a.C);
@@ -290,7 +292,7 @@ __global__ __launch_bounds__(256) void gather_crop_rgb_kernel(GatherArgs a) {
     const FrameJob job = frame_job(a, (nvec + 256 * kDirectVec - 1) / (256 * kDirectVec), fbytes);
     const int part = job.part, sy = job.sy, sx3 = job.sx * 3;
     const uint8_t* src = job.src;
-    uint8_t* dst = a.out_frames + (((size_t)job.which * a.n_cam + job.cam) * a.batch + job.i) * fbytes;
+    uint8_t* dst = a.out_frames + job.dst_frame * fbytes;
     unsigned __int128 val[kDirectVec];
     int shl[kDirectVec], shr[kDirectVec];
 #pragma unroll
@@ -591,7 +593,7 @@ int serl_rb_create(int device, int64_t capacity, int n_cam, int H, int W, int C,
   for (int k = 0; k < serl_rb::kGatherStreams; ++k) SERL_HIP(hipEventCreateWithFlags(&rb->gather_ev[k], hipEventDisableTiming));
   SERL_HIP(hipEventCreateWithFlags(&rb->last_insert, hipEventDisableTiming));
   RC(rb->ins.init(kInsRing, ((sizeof(float) * rb->rec_len + 255) & ~(size_t)255) + (size_t)n_cam * rb->frame_bytes, false));
-  RC(rb->stage.init(kRing, 1 << 16, true));  // idx (8B) + 2 crops (16B) per sample: up to ~2700 samples
+  RC(rb->stage.init(kRing, (size_t)(1 << 16) * std::min(num_stack, kMaxStack), true));  // idx (8B) + 2 crops (16B per frame) per sample: up to ~2700 samples
   *out = rb.release();
   return SERL_OK;
 }
@@ -813,10 +815,17 @@ int serl_rb_gather_packed(serl_rb* rb, int64_t* host_idx, int batch,
   return note_gather(rb, stream);
 }
 
-// a table of (dy, dx) per sample, or none
+// a table of (dy, dx) per frame, or none
 static int check_crops(const int32_t* crop, int batch) {
   if (crop)
     for (int i = 0; i < 2 * batch; ++i) SERL_REQUIRE(crop[i] >= 0 && crop[i] <= 8, "crop offset %d out of [0,8]", crop[i]);
+  return SERL_OK;
+}
+
+static int set_frame_blocks(GatherArgs& a, int parts) {
+  const int64_t n = stack_frame_blocks(parts, a.T, a.batch, a.n_cam);
+  SERL_REQUIRE(n + cdiv((long)a.batch * a.rec_len, 256) < (1LL << 31), "gather+crop of %d x %d frames needs too many workgroups", a.batch, a.T);
+  a.n_frame_blocks = (int)n;
   return SERL_OK;
 }
 
@@ -825,13 +834,13 @@ static int launch_gather_crop(GatherArgs& a, hipStream_t stream) {
   ProfScope prof("gather_crop", stream);
   if (a.C == 3 && (a.W * 3) % 16 == 0 && a.W * 3 >= 32) {   // RGB rows of whole 16-byte vectors: the LDS-free kernel
     const int nvec = a.H * (a.W * 3 / 16);
-    a.n_frame_blocks = 2 * a.n_cam * a.batch * cdiv(nvec, 256 * kDirectVec);
+    RC(set_frame_blocks(a, cdiv(nvec, 256 * kDirectVec)));
     hipLaunchKernelGGL(gather_crop_rgb_kernel, dim3(a.n_frame_blocks + rec_blocks), dim3(256), 0, stream, a);
     SERL_HIP(hipGetLastError());
     return SERL_OK;
   }
   const int chunks = cdiv(a.H, kRowsPerBlock);
-  a.n_frame_blocks = 2 * a.n_cam * a.batch * chunks;
+  RC(set_frame_blocks(a, chunks));
   const size_t lds = (size_t)kRowsPerBlock * ((size_t)a.W * a.C + 16);
   if (a.C == 3) hipLaunchKernelGGL(gather_crop_kernel<3>, dim3(a.n_frame_blocks + rec_blocks), dim3(256), lds, stream, a);
   else hipLaunchKernelGGL(gather_crop_kernel<0>, dim3(a.n_frame_blocks + rec_blocks), dim3(256), lds, stream, a);
@@ -847,7 +856,9 @@ int serl_rb_gather_crop(serl_rb* const* rbs, int n_rb, int64_t* const* host_idx,
   hipStream_t stream = (hipStream_t)stream_;
   serl_rb* r0 = rbs[0];
   SERL_REQUIRE(r0, "rbs[0] is NULL");
-  SERL_REQUIRE(r0->T == 1, "fused gather+crop supports num_stack == 1 (got %d)", r0->T);
+  const int T = r0->T, out_T = out->num_stack > 0 ? out->num_stack : 1;
+  SERL_REQUIRE(T >= 1 && T <= kMaxStack, "fused gather+crop supports num_stack 1..%d (the store has %d)", kMaxStack, T);
+  SERL_REQUIRE(out_T == T, "the store holds stacks of %d frames, serl_batch.num_stack is %d", T, out_T);
   int total = 0;
   for (int b = 0; b < n_rb; ++b) {
     SERL_REQUIRE(rbs[b] && host_idx[b], "NULL buffer/index");
@@ -860,11 +871,11 @@ int serl_rb_gather_crop(serl_rb* const* rbs, int n_rb, int64_t* const* host_idx,
   }
   SERL_REQUIRE(total == out->batch && total > 0, "counts sum %d != batch %d", total, out->batch);
   SERL_REQUIRE(out->n_cam == r0->n_cam && (r0->n_cam == 0 || (out->H == r0->H && out->W == r0->W && out->C == r0->C)) &&
-                   out->state_dim == r0->S && out->act_dim == r0->A, "serl_batch shape mismatch");
+                   out->state_dim == T * r0->S && out->act_dim == r0->A, "serl_batch shape mismatch");
   SERL_REQUIRE((out->frames || r0->n_cam == 0) && out->state && out->action && out->reward && out->mask && out->done,
                "serl_batch has NULL outputs");
-  RC(check_crops(host_crop_obs, total));
-  RC(check_crops(host_crop_next, total));
+  RC(check_crops(host_crop_obs, total * T));
+  RC(check_crops(host_crop_next, total * T));
   // lock all buffers (fixed order) while we read bookkeeping and enqueue
   std::unique_lock<std::mutex> l0(rbs[0]->mu, std::defer_lock), l1;
   if (n_rb == 2 && rbs[1] != rbs[0]) {
@@ -878,7 +889,7 @@ int serl_rb_gather_crop(serl_rb* const* rbs, int n_rb, int64_t* const* host_idx,
     RC(check_and_revalidate(rbs[b], host_idx[b], counts[b]));
     RC(order_after_inserts(rbs[b], stream));
   }
-  const size_t cbytes = sizeof(int32_t) * 2 * (size_t)total;
+  const size_t cbytes = sizeof(int32_t) * 2 * (size_t)total * T;
   const void* srcs[4] = {host_idx[0], n_rb > 1 ? host_idx[1] : nullptr, host_crop_obs, host_crop_next};
   size_t sizes[4] = {sizeof(int64_t) * (size_t)counts[0], n_rb > 1 ? sizeof(int64_t) * (size_t)counts[1] : 0,
                      host_crop_obs ? cbytes : 0, host_crop_next ? cbytes : 0}, offs[4];
@@ -892,7 +903,7 @@ int serl_rb_gather_crop(serl_rb* const* rbs, int n_rb, int64_t* const* host_idx,
     a.idx[b] = reinterpret_cast<const int64_t*>(dparams + offs[b]);
   }
   a.count0 = counts[0];
-  a.batch = total; a.n_cam = r0->n_cam; a.H = r0->H; a.W = r0->W; a.C = r0->C; a.S = r0->S; a.A = r0->A;
+  a.batch = total; a.n_cam = r0->n_cam; a.H = r0->H; a.W = r0->W; a.C = r0->C; a.S = T * r0->S; a.A = r0->A; a.T = T;
   a.rec_len = r0->rec_len;
   a.crop_obs = host_crop_obs ? reinterpret_cast<const int32_t*>(dparams + offs[2]) : nullptr;
   a.crop_next = host_crop_next ? reinterpret_cast<const int32_t*>(dparams + offs[3]) : nullptr;
@@ -911,8 +922,16 @@ static struct { std::mutex mu; int device = -1; StageRing ring; } g_crop;
 int serl_crop_packed(int device, const uint8_t* const* dev_packed, int n_cam, int batch, int H,
                      int W, int C, const int32_t* host_crop_obs, const int32_t* host_crop_next,
                      uint8_t* dev_frames_out, void* stream_) {
+  return serl_crop_packed_stacked(device, dev_packed, n_cam, batch, 1, H, W, C, host_crop_obs, host_crop_next, dev_frames_out, stream_);
+}
+
+int serl_crop_packed_stacked(int device, const uint8_t* const* dev_packed, int n_cam, int batch, int num_stack, int H,
+                             int W, int C, const int32_t* host_crop_obs, const int32_t* host_crop_next,
+                             uint8_t* dev_frames_out, void* stream_) {
   SERL_REQUIRE(dev_packed && dev_frames_out, "NULL argument");
   SERL_REQUIRE(n_cam >= 1 && n_cam <= SERL_MAX_CAMS && batch > 0, "bad n_cam/batch");
+  SERL_REQUIRE(num_stack >= 1 && num_stack <= kMaxStack, "num_stack %d not in [1,%d]", num_stack, kMaxStack);
+  const int T = num_stack;
   SERL_REQUIRE(((size_t)W * C) % 16 == 0, "W*C (%d) must be a multiple of 16 bytes", W * C);
   hipStream_t stream = (hipStream_t)stream_;
   std::lock_guard<std::mutex> g(g_crop.mu);
@@ -922,9 +941,9 @@ int serl_crop_packed(int device, const uint8_t* const* dev_packed, int n_cam, in
     RC(g_crop.ring.init(kRing, 1 << 16, true));
     g_crop.device = device;
   }
-  RC(check_crops(host_crop_obs, batch));  // every check comes before a staging slot is taken
-  RC(check_crops(host_crop_next, batch));
-  const size_t cbytes = sizeof(int32_t) * 2 * (size_t)batch;
+  RC(check_crops(host_crop_obs, batch * T));  // every check comes before a staging slot is taken
+  RC(check_crops(host_crop_next, batch * T));
+  const size_t cbytes = sizeof(int32_t) * 2 * (size_t)batch * T;
   const void* srcs[2] = {host_crop_obs, host_crop_next};
   size_t sizes[2] = {cbytes, cbytes}, offs[2];  // both tables keep their place in the slot, given or not
   uint8_t* d;
@@ -933,7 +952,7 @@ int serl_crop_packed(int device, const uint8_t* const* dev_packed, int n_cam, in
   for (int c = 0; c < n_cam; ++c) a.packed[c] = dev_packed[c];
   a.from_packed = 1;
   a.count0 = batch;
-  a.batch = batch; a.n_cam = n_cam; a.H = H; a.W = W; a.C = C;
+  a.batch = batch; a.n_cam = n_cam; a.H = H; a.W = W; a.C = C; a.T = T;
   a.crop_obs = host_crop_obs ? reinterpret_cast<const int32_t*>(d + offs[0]) : nullptr;
   a.crop_next = host_crop_next ? reinterpret_cast<const int32_t*>(d + offs[1]) : nullptr;
   a.out_frames = dev_frames_out;

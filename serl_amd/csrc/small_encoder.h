@@ -14,13 +14,16 @@ struct SmallDims {
   int h[kSmallLayers + 1], w[kSmallLayers + 1];   // [0] = input, [l+1] = output of conv l
 };
 SmallDims small_dims(int H, int W);
-// floats of one camera's conv stack in the parameter arena: per layer [9*cin + 1][cout] = kernel (HWIO) then bias
-long small_conv_params();
-long small_conv_offset(int layer);   // offset of layer's kernel inside that block
+constexpr int kSmallMaxStack = 4;   // most frames per observation (serl_agent_cfg.num_stack)
+// floats of one camera's conv stack in the parameter arena: per layer [9*cin + 1][cout] = kernel (HWIO) then bias.  With a
+// stack of T frames folded into the channels (common/encoding.py:39-44) layer 0 has cin = 3T.
+long small_conv_params(int T = 1);
+long small_conv_offset(int layer, int T = 1);   // offset of layer's kernel inside that block
 
 struct SmallWorkspace {
   SmallDims d{};
-  int max_images = 0;             // images per pass (all cameras together)
+  int max_images = 0;             // images per pass (all cameras together); an image is a stack of T frames
+  int T = 1;                      // frames per image, folded into layer 0's input channels
   float* col[kSmallLayers]{};     // (unused since round 4: layer 0 reads the u8 frames directly)
   int* tab[kSmallLayers]{};       // layers 1..3: offset of every im2col row's patch in the layer's NHWC input (implicit GEMM)
   bool tab_ready = false;
@@ -35,10 +38,11 @@ struct SmallWorkspace {
   long last_frame_cam_stride = 0;
   size_t bytes = 0;
 };
-size_t small_workspace_bytes(int max_images, int H, int W);
-int small_workspace_bind(SmallWorkspace& ws, void* mem, int max_images, int H, int W);
+size_t small_workspace_bytes(int max_images, int H, int W, int T = 1);
+int small_workspace_bind(SmallWorkspace& ws, void* mem, int max_images, int H, int W, int T = 1);
 
-// frames: u8, image i of camera c at frames + (c * frame_cam_stride + i) * H*W*3 (device); P + cam*cam_stride + conv_off
+// frames: u8, frame t of image i of camera c at frames + ((c * frame_cam_stride + i) * T + t) * H*W*3 (device; T as bound,
+// frame-planar: layer 0 reads the T frames where they lie, no folded copy is made); P + cam*cam_stride + conv_off
 // = that camera's conv parameters.  pooled: [n_cam][pooled_cam_stride / 256 rows][256] -- rows [0, n) of every camera
 // block are written.
 int small_forward(SmallWorkspace& ws, const float* P, long conv_off, long cam_stride, const uint8_t* frames,

@@ -30,20 +30,21 @@ SmallDims small_dims(int H, int W) {
   }
   return d;
 }
-long small_conv_offset(int layer) {
+long small_conv_offset(int layer, int T) {
   long off = 0;
-  for (int l = 0; l < layer; ++l) off += (9L * kSmallFeat[l] + 1) * kSmallFeat[l + 1];
+  for (int l = 0; l < layer; ++l) off += (9L * kSmallFeat[l] * (l == 0 ? T : 1) + 1) * kSmallFeat[l + 1];
   return off;
 }
-long small_conv_params() { return small_conv_offset(kSmallLayers); }
+long small_conv_params(int T) { return small_conv_offset(kSmallLayers, T); }
 
 constexpr int kConv0Chunks = 1024, kSmallMaxCams = 4;   // layer 0's weight gradient: row chunks per camera / cameras
 static int ldk(int l) { return (9 * kSmallFeat[l] + 1 + 3) & ~3; }   // row pitch of col_l: K + 1 rounded up to 4 floats
 static long rows_of(const SmallDims& d, int l, long n_img) { return n_img * d.h[l + 1] * d.w[l + 1]; }
 
-static size_t carve(SmallWorkspace& ws, uint8_t* base, int max_images, int H, int W) {
+static size_t carve(SmallWorkspace& ws, uint8_t* base, int max_images, int H, int W, int T) {
   ws.d = small_dims(H, W);
   ws.max_images = max_images;
+  ws.T = T;
   Bump b(base);
   long max_act = 0, max_col = 0;
   for (int l = 0; l < kSmallLayers; ++l) {
@@ -57,17 +58,18 @@ static size_t carve(SmallWorkspace& ws, uint8_t* base, int max_images, int H, in
   ws.dact = b.take<float>(max_act);
   ws.dact2 = b.take<float>(max_act);
   ws.dcol = b.take<float>(max_col);
-  ws.slabs_cap = std::max(64L * (9 * 128 + 1) * 256, (long)kConv0Chunks * kSmallMaxCams * 28 * 32);   // up to 64 K-slices of the largest [K+1][cout] gradient / layer 0's row chunks
+  ws.slabs_cap = std::max(64L * (9 * 128 + 1) * 256, (long)kConv0Chunks * kSmallMaxCams * (27 * T + 1) * 32);   // up to 64 K-slices of the largest [K+1][cout] gradient / layer 0's row chunks
   ws.slabs = b.take<float>(ws.slabs_cap);
   ws.bytes = b.off;
   return b.off;
 }
-size_t small_workspace_bytes(int max_images, int H, int W) {
+size_t small_workspace_bytes(int max_images, int H, int W, int T) {
   SmallWorkspace t;
-  return carve(t, nullptr, max_images, H, W);
+  return carve(t, nullptr, max_images, H, W, T);
 }
-int small_workspace_bind(SmallWorkspace& ws, void* mem, int max_images, int H, int W) {
-  carve(ws, (uint8_t*)mem, max_images, H, W);
+int small_workspace_bind(SmallWorkspace& ws, void* mem, int max_images, int H, int W, int T) {
+  SERL_REQUIRE(T >= 1 && T <= kSmallMaxStack, "SmallEncoder: num_stack %d not in [1,%d]", T, kSmallMaxStack);
+  carve(ws, (uint8_t*)mem, max_images, H, W, T);
   return SERL_OK;
 }
 
@@ -212,6 +214,140 @@ __global__ __launch_bounds__(256) void small_conv0_wgrad_kernel(const uint8_t* f
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Layer 0 on a STACK of T frames (T = 2..4; EncodingWrapper folds "B T H W C -> B H W (T C)", common/encoding.py:39-44): the
+// kernel is (3,3,3T,32), flax row (ky*3 + kx)*3T + t*3 + c, and input channel t*3 + c is channel c of frame t.  The frames stay
+// where the crop kernel wrote them (frame-planar u8[image][T][H][W][3]): a thread walks the T frames with the same three 8-byte
+// + three 1-byte loads per frame as the single-frame kernel above, which remains the T == 1 path.  Addresses are clamped, every
+// load is issued unconditionally and the result selected afterwards.
+// ---------------------------------------------------------------------------------------------
+template <int T>
+__global__ __launch_bounds__(256) void small_conv0_stack_fwd_kernel(const uint8_t* frames, const float* P, long cam_stride, float* act,
+                                                                   long rows_cam, long frame_cam_stride, int hi, int wi, int ho,
+                                                                   int wo) {
+  constexpr int KR = 27 * T + 1;   // parameter rows: 27T taps + the bias
+  __shared__ float Ws[KR * 32];
+  __shared__ float lut[256];
+  const int cam = blockIdx.y, tid = threadIdx.x;
+  const float* Wg = P + (long)cam * cam_stride;
+  for (int i = tid; i < KR * 32; i += 256) Ws[i] = Wg[i];
+  lut[tid] = (float)tid / 255.0f;
+  __syncthreads();
+  const long e = (long)blockIdx.x * 256 + tid;
+  const long m_raw = e >> 2, m = min(m_raw, rows_cam - 1);   // (rows past the end re-read the last row and store nothing)
+  const int cg = (int)(e & 3) * 8;
+  const long n = m / ((long)ho * wo);
+  const int rem = (int)(m - n * (long)ho * wo), oy = rem / wo, ox = rem - oy * wo;
+  const size_t fbytes = (size_t)hi * wi * 3;
+  const uint8_t* px = frames + (((size_t)cam * frame_cam_stride + n) * T) * fbytes + ((size_t)(2 * oy) * wi + 2 * ox) * 3;
+  unsigned long long lo[T][3];
+  unsigned b8[T][3];
+#pragma unroll
+  for (int t = 0; t < T; ++t)
+#pragma unroll
+    for (int ky = 0; ky < 3; ++ky) {
+      const uint8_t* q = px + t * fbytes + (size_t)ky * wi * 3;
+      lo[t][ky] = reinterpret_cast<const U64Unaligned*>(q)->v;
+      b8[t][ky] = q[8];
+    }
+  float acc[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) acc[j] = Ws[27 * T * 32 + cg + j];
+#pragma unroll
+  for (int ky = 0; ky < 3; ++ky)
+#pragma unroll
+    for (int kx = 0; kx < 3; ++kx)
+#pragma unroll
+      for (int t = 0; t < T; ++t)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+          const int b = kx * 3 + c;   // byte of the 9-byte patch row
+          const float x = lut[b < 8 ? (unsigned)((lo[t][ky] >> (8 * b)) & 0xffu) : b8[t][ky]];
+          const float* w = Ws + (((ky * 3 + kx) * T + t) * 3 + c) * 32 + cg;
+#pragma unroll
+          for (int j = 0; j < 8; ++j) acc[j] += x * w[j];
+        }
+  if (m_raw < rows_cam) {
+    float* o = act + ((long)cam * rows_cam + m) * 32 + cg;
+    *reinterpret_cast<float4*>(o) = make_float4(fmaxf(acc[0], 0.f), fmaxf(acc[1], 0.f), fmaxf(acc[2], 0.f), fmaxf(acc[3], 0.f));
+    *reinterpret_cast<float4*>(o + 4) = make_float4(fmaxf(acc[4], 0.f), fmaxf(acc[5], 0.f), fmaxf(acc[6], 0.f), fmaxf(acc[7], 0.f));
+  }
+}
+
+// Layer 0's parameter gradient for a stack of T frames, on the exact fp32 matrix pipe like small_conv0_wgrad_kernel: ONE
+// 32 x 32 accumulator per frame t -- lane l supplies A_t[i = l & 31][k = l >> 5] = patch value i = ky*9 + kx*3 + c of frame t of
+// row k (i = 27: the ones column, in tile 0 only; beyond: zero) -- and the one loaded dy operand B feeds the T MFMAs of a row
+// pair, so dy is read once.  Tile t's row i goes to flax row (i / 3) * 3T + t*3 + i % 3 of the partial, tile 0's row 27 to the
+// bias row 27T.  Same fixed-order wave reduction (one tile at a time through LDS) and chunk reduction as the single-frame kernel.
+template <int T>
+__global__ __launch_bounds__(256) void small_conv0_stack_wgrad_kernel(const uint8_t* frames, const float* dy, float* part, long rows_cam,
+                                                                     long frame_cam_stride, int hi, int wi, int ho, int wo, int chunks) {
+  constexpr int KR = 27 * T + 1;
+  __shared__ float lut[256];
+  __shared__ float red[3][32 * 32];
+  const int cam = blockIdx.y, chunk = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  lut[tid] = (float)tid / 255.0f;
+  __syncthreads();
+  const long per = ((rows_cam + chunks - 1) / chunks + 7) & ~7L;       // rows per workgroup, a multiple of 8 (2 per MFMA x 4 waves)
+  const long r0 = (long)chunk * per, r1 = min(rows_cam, r0 + per);
+  const int i = lane & 31, kk = lane >> 5;
+  const int poff = i < 27 ? (i / 9) * wi * 3 + (i % 9) : 0;            // byte offset of patch value i inside the patch
+  f32x16s acc[T];
+#pragma unroll
+  for (int t = 0; t < T; ++t)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
+  long m = r0 + 2 * wave + kk;
+  const long hw = (long)ho * wo;
+  long n = min(m, rows_cam - 1) / hw;
+  int rem = (int)(min(m, rows_cam - 1) - n * hw), oy = rem / wo, ox = rem - oy * wo;
+  const size_t fbytes = (size_t)hi * wi * 3;
+  const uint8_t* img = frames + (size_t)cam * frame_cam_stride * T * fbytes + poff;
+  const float* dyc = dy + (long)cam * rows_cam * 32 + i;
+  constexpr int U = 4;   // row pairs in flight: U * (T + 1) loads per lane before their U * T MFMAs
+  while (m - kk < r1) {   // (wave-uniform: both half-waves advance together)
+    float a[T][U], b[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const bool ok = m < r1;
+      const size_t pix = ok ? ((size_t)n * T * hi + 2 * oy) * (size_t)wi * 3 + (size_t)(2 * ox) * 3 : 0;   // clamped: frame 0's first byte
+#pragma unroll
+      for (int t = 0; t < T; ++t) {
+        const float v = lut[img[pix + (ok ? t * fbytes : 0)]];
+        a[t][u] = (ok && i < 27) ? v : ((ok && i == 27 && t == 0) ? 1.0f : 0.f);
+      }
+      const float d = dyc[(ok ? m : r0) * 32];
+      b[u] = ok ? d : 0.f;
+      m += 8; ox += 8;
+      while (ox >= wo) { ox -= wo; if (++oy >= ho) { oy = 0; ++n; } }
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+#pragma unroll
+      for (int t = 0; t < T; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[t][u], b[u], acc[t], 0, 0, 0);
+  }
+  // C layout: acc[t][r] = D_t[row (r & 3) + 8 (r >> 2) + 4 kk][col i]; waves 1..3 hand a tile over, wave 0 adds in wave order
+  float* o = part + ((long)cam * chunks + chunk) * KR * 32;
+#pragma unroll
+  for (int t = 0; t < T; ++t) {
+    if (wave > 0) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) red[wave - 1][((r & 3) + 8 * (r >> 2) + 4 * kk) * 32 + i] = acc[t][r];
+    }
+    __syncthreads();
+    if (wave == 0) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int row = (r & 3) + 8 * (r >> 2) + 4 * kk;
+        const float v = ((acc[t][r] + red[0][row * 32 + i]) + red[1][row * 32 + i]) + red[2][row * 32 + i];
+        if (row < 27) o[((row / 3) * 3 * T + t * 3 + row % 3) * 32 + i] = v;
+        else if (row == 27 && t == 0) o[27 * T * 32 + i] = v;
+      }
+    }
+    __syncthreads();
+  }
+}
+
 // out[cam][e] = sum over the S per-workgroup partials part[cam][s][e], in a fixed order: sixteen waves take the partials
 // s = w, w + 16, ... each, then wave 0 adds the sixteen sums in wave order (deterministic; the generic reduce_slabs walks all S
 // one after the other: 60 us for 256 partials)
@@ -336,8 +472,22 @@ int small_forward(SmallWorkspace& ws, const float* P, long conv_off, long cam_st
     GemmDesc g{};   // act[cam] = relu(col[cam] ([rows_cam][K+1]) x [kernel ; bias]_cam ([K+1][cout]))
     if (l == 0) {   // directly on the u8 frames, fp32 FMAs (no im2col matrix, no GEMM)
       SERL_REQUIRE(n_cam <= kSmallMaxCams, "SmallEncoder: at most %d cameras", kSmallMaxCams);
-      hipLaunchKernelGGL(small_conv0_fwd_kernel, dim3(cdiv(rows_cam * 4, 256), n_cam), dim3(256), 0, stream, frames,
-                         P + conv_off, cam_stride, ws.act[0], rows_cam, n, frame_cam_stride, d.h[0], d.w[0], d.h[1], d.w[1]);
+      const dim3 grid(cdiv(rows_cam * 4, 256), n_cam);
+      ProfScope prof0("small_conv0_fwd", stream);   // (inside small_encoder_fwd: layer 0 alone, for scripts/measure_frame_stack.py)
+#define SERL_CONV0_STACK_FWD(TT)                                                                                                  \
+  hipLaunchKernelGGL(small_conv0_stack_fwd_kernel<TT>, grid, dim3(256), 0, stream, frames, P + conv_off, cam_stride, ws.act[0], \
+                     rows_cam, frame_cam_stride, d.h[0], d.w[0], d.h[1], d.w[1])
+      switch (ws.T) {
+        case 1:
+          hipLaunchKernelGGL(small_conv0_fwd_kernel, grid, dim3(256), 0, stream, frames,
+                             P + conv_off, cam_stride, ws.act[0], rows_cam, n, frame_cam_stride, d.h[0], d.w[0], d.h[1], d.w[1]);
+          break;
+        case 2: SERL_CONV0_STACK_FWD(2); break;
+        case 3: SERL_CONV0_STACK_FWD(3); break;
+        case 4: SERL_CONV0_STACK_FWD(4); break;
+        default: SERL_REQUIRE(false, "SmallEncoder: num_stack %d not in [1,%d]", ws.T, kSmallMaxStack);
+      }
+#undef SERL_CONV0_STACK_FWD
       SERL_HIP(hipGetLastError());
       ws.last_frames = frames; ws.last_frame_cam_stride = frame_cam_stride;
       (void)rows; (void)pitch;
@@ -346,7 +496,7 @@ int small_forward(SmallWorkspace& ws, const float* P, long conv_off, long cam_st
       g.A = ws.act[l - 1]; g.sAm = 0; g.sAk = 1; g.sAb = 0;
       g.gtab = ws.tab[l]; g.gseg = 3 * cin; g.gkbias = 9 * cin; g.gpitch = (long)d.w[l] * cin;
     }
-    g.B = P + conv_off + small_conv_offset(l); g.sBk = cout; g.sBn = 1; g.sBb = cam_stride;
+    g.B = P + conv_off + small_conv_offset(l, ws.T); g.sBk = cout; g.sBn = 1; g.sBb = cam_stride;
     g.C = ws.act[l]; g.ldc = cout; g.sCz = rows_cam * cout;
     g.M = (int)rows_cam; g.N = cout; g.K = K; g.nbatch = n_cam; g.splitk = 1; g.relu = 1;
     int rc = gemm_f32(g, stream);
@@ -376,10 +526,25 @@ int small_backward(SmallWorkspace& ws, const float* P, long conv_off, long cam_s
     if (l == 0) {   // straight from the u8 frames of the forward pass: per-chunk partial sums, added in chunk order
       SERL_REQUIRE(ws.last_frames != nullptr, "small_backward without a forward pass");
       const int chunks = (int)std::min<long>(kConv0Chunks, std::max<long>(1, rows_cam / 256));   // one workgroup per chunk (latency-bound: many)
-      hipLaunchKernelGGL(small_conv0_wgrad_kernel, dim3(chunks, n_cam), dim3(256), 0, stream, ws.last_frames, dy, ws.slabs, rows_cam, n,
-                         ws.last_frame_cam_stride, d.h[0], d.w[0], d.h[1], d.w[1], chunks);
+      const int n_elem = (27 * ws.T + 1) * 32;
+      ProfScope prof0("small_conv0_wgrad", stream);   // (inside small_encoder_bwd: layer 0's two launches)
+      SERL_REQUIRE((long)chunks * n_cam * n_elem <= ws.slabs_cap, "SmallEncoder: layer 0's partials exceed the workspace");
+#define SERL_CONV0_STACK_WGRAD(TT)                                                                                                 \
+  hipLaunchKernelGGL(small_conv0_stack_wgrad_kernel<TT>, dim3(chunks, n_cam), dim3(256), 0, stream, ws.last_frames, dy, ws.slabs, \
+                     rows_cam, ws.last_frame_cam_stride, d.h[0], d.w[0], d.h[1], d.w[1], chunks)
+      switch (ws.T) {
+        case 1:
+          hipLaunchKernelGGL(small_conv0_wgrad_kernel, dim3(chunks, n_cam), dim3(256), 0, stream, ws.last_frames, dy, ws.slabs, rows_cam, n,
+                             ws.last_frame_cam_stride, d.h[0], d.w[0], d.h[1], d.w[1], chunks);
+          break;
+        case 2: SERL_CONV0_STACK_WGRAD(2); break;
+        case 3: SERL_CONV0_STACK_WGRAD(3); break;
+        case 4: SERL_CONV0_STACK_WGRAD(4); break;
+        default: SERL_REQUIRE(false, "SmallEncoder: num_stack %d not in [1,%d]", ws.T, kSmallMaxStack);
+      }
+#undef SERL_CONV0_STACK_WGRAD
       SERL_HIP(hipGetLastError());
-      hipLaunchKernelGGL(small_reduce_chunks_kernel, dim3(cdiv(28 * 32, 64), n_cam), dim3(1024), 0, stream, ws.slabs, chunks, 28 * 32,
+      hipLaunchKernelGGL(small_reduce_chunks_kernel, dim3(cdiv(n_elem, 64), n_cam), dim3(1024), 0, stream, ws.slabs, chunks, n_elem,
                          G + conv_off, cam_stride);
       SERL_HIP(hipGetLastError());
       break;   // the pixels need no gradient
@@ -395,7 +560,7 @@ int small_backward(SmallWorkspace& ws, const float* P, long conv_off, long cam_s
       }
       g.B = dy; g.sBk = cout; g.sBn = 1; g.sBb = rows_cam * cout;
       g.M = K; g.N = cout; g.K = (int)rows_cam; g.nbatch = n_cam; g.splitk = S;
-      float* out = G + conv_off + small_conv_offset(l);
+      float* out = G + conv_off + small_conv_offset(l, ws.T);
       if (S == 1) {
         g.C = out; g.ldc = cout; g.sCz = cam_stride;
         int rc = gemm_f32(g, stream);
@@ -410,7 +575,7 @@ int small_backward(SmallWorkspace& ws, const float* P, long conv_off, long cam_s
     }
     if (l == 0) break;   // the pixels need no gradient
     {  // dcol_cam = dy_cam x kernel_cam^T  (the ones column has no input below it)
-      const GemmDesc g = gemm_igrad(dy, cout, rows_cam * cout, P + conv_off + small_conv_offset(l), cout, cam_stride, ws.dcol, pitch,
+      const GemmDesc g = gemm_igrad(dy, cout, rows_cam * cout, P + conv_off + small_conv_offset(l, ws.T), cout, cam_stride, ws.dcol, pitch,
                                     rows_cam * pitch, n_cam, (int)rows_cam, K - 1, cout);
       int rc = gemm_f32(g, stream);
       if (rc) return rc;

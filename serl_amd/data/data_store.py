@@ -48,6 +48,11 @@ class LazyBatch:
     def batch_size(self):
         return sum(len(ix) for _, ix in self.parts)
 
+    @property
+    def num_stack(self):
+        """T, frames per observation of the stores the batch was drawn from"""
+        return int(getattr(self.parts[0][0], "_num_stack", 1) or 1)
+
     def materialize(self):
         out = None
         for buf, ix in self.parts:

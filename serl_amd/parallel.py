@@ -168,6 +168,8 @@ class DataParallelLearner:
         self.rank, self.world = rank, world
         self.B = sum(batch_sizes)
         assert self.B % world == 0
+        # T, frames per observation (AgentCore num_stack): a batch of B samples draws B*T crop offsets per stream, entry b*T + t
+        self.T = max(int(getattr(getattr(core, "cfg", None), "num_stack", 1) or 1), 1)
         self.Bl = self.B // world
         self.all_reduce = all_reduce
         self.ensemble = ensemble
@@ -224,7 +226,7 @@ class DataParallelLearner:
         parts = [(b, b.sample_indices(n)) for b, n in zip(self.buffers, self.batch_sizes)]
         if not crops:
             return slot, parts, None, None
-        co, cn = J.crop_pair(rng, self.B)
+        co, cn = J.crop_pair(rng, self.B * self.T)
         self.last_draws["crops"] = (co, cn)
         return slot, parts, co, cn
 
@@ -236,7 +238,7 @@ class DataParallelLearner:
         self.sched.wait_consumed(slot)
         split = getattr(self.sched, "update_after_stage", None)
         with self.sched.side():
-            db = self.sched.gathered(slot, lambda: self.gather(local, co[lo:hi], cn[lo:hi], slot))
+            db = self.sched.gathered(slot, lambda: self.gather(local, co[lo * self.T:hi * self.T], cn[lo * self.T:hi * self.T], slot))
             if split is None or not hasattr(self.core, "encode_slot_range"):
                 self.core.encode_slot(db, slot)
             else:   # two pieces with an event between them (see TorchPipelineSchedule)

@@ -48,7 +48,9 @@ SMALL_FEATURES = (3, 32, 64, 128, 256)   # SmallEncoder(features=(32, 64, 128, 2
 
 
 def theta_shapes(n_cam, H, W, S, A, ensemble=10, hidden=256, bottleneck=256, sle_features=8, proprio_dim=64,
-                 encoder_type="resnet-pretrained"):
+                 encoder_type="resnet-pretrained", num_stack=1):
+    """S: the proprio Dense's input width -- T * S for a stack of T = num_stack frames, which EncodingWrapper folds into the
+    channels ("B T H W C -> B H W (T C)", common/encoding.py:39-44): the SmallEncoder's first kernel is then (3,3,3T,32)."""
     if n_cam == 0:   # state-only SAC (SACAgent.create_states, sac.py:486-542): no encoder, per-member Q heads
         N, Hd = ensemble, hidden
         return {
@@ -67,7 +69,7 @@ def theta_shapes(n_cam, H, W, S, A, ensemble=10, hidden=256, bottleneck=256, sle
     for k in range(n_cam):
         if encoder_type == "small":    # 4 x Conv(3x3, stride 2, VALID) with bias, then mean-pool -> Dense(256)
             for l in range(4):
-                sh[f"enc/{k}/conv{l}/kernel"] = (3, 3, SMALL_FEATURES[l], SMALL_FEATURES[l + 1])
+                sh[f"enc/{k}/conv{l}/kernel"] = (3, 3, SMALL_FEATURES[l] * (num_stack if l == 0 else 1), SMALL_FEATURES[l + 1])
                 sh[f"enc/{k}/conv{l}/bias"] = (SMALL_FEATURES[l + 1],)
             sh[f"enc/{k}/dense/kernel"] = (SMALL_FEATURES[4], bottleneck)
         else:
