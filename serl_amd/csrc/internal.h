@@ -1,6 +1,7 @@
 // Internal (non-ABI) interfaces between the translation units of libserl_mi355.so.
 #pragma once
 #include "common.h"
+#include "gn_exchange.h"
 #include "param_arena.h"
 
 namespace serl {
@@ -39,7 +40,8 @@ struct TrunkDims {
 };
 TrunkDims trunk_dims(int H, int W);
 
-constexpr int kSyncPerImage = 8, kSyncTickets = 16;   // tickets: 8 per launch (one per XCD)
+constexpr int kSyncTickets = 16;   // ints per layer; tickets: 8 per launch (one per XCD)
+constexpr int kGnLayers = 1 + 3 * kTrunkStages;   // conv_init, then (conv0, conv1, projection) per stage
 // Every launch decision of a split-fp16 pass, made by its first piece before anything launches (plan_pass, trunk_f16x3.hip) and
 // kept for the pieces that follow; also the introspection of the parity tests (the shapes a data-parallel rank runs choose
 // other kernels than the full batch does).
@@ -72,8 +74,14 @@ struct TrunkWorkspace {
     float *raw0, *raw1, *rawp, *out, *norm0;
   } blk[kTrunkStages]{};
   double* stats = nullptr;  // 13 GN layers x [N][4][2]
-  int* sync = nullptr;      // directly behind `stats` (one memset): 13 layers x (kSyncPerImage arrival counters per image + kSyncTickets ints)
+  int* tickets = nullptr;   // directly behind `stats` (zeroed together, every pass): 13 layers x kSyncTickets ints
   size_t stats_sync_bytes = 0;
+  // statistics exchange of the fused GroupNorm epilogues (gn_exchange.h): one 256-byte record per tile that can take part, per layer
+  // at record rec_off[layer]; never zeroed between passes -- granules carry the pass `epoch` (0: no pass yet, the first one zeroes)
+  uint64_t* rec = nullptr;
+  size_t rec_bytes = 0;
+  size_t rec_off[kGnLayers] = {};
+  uint32_t epoch = 0;
   void* base = nullptr;     // single allocation backing everything above
   size_t bytes = 0;
 };

@@ -477,7 +477,6 @@ TrunkWeights trunk_weights(const float* params, const TrunkOffsets& o) {
   return w;
 }
 
-constexpr int kGnLayers = 1 + 3 * kTrunkStages;
 static size_t trunk_layout(TrunkWorkspace* ws, uint8_t* base, int N, int H, int W) {
   const TrunkDims d = trunk_dims(H, W);
   Bump b(base);
@@ -493,11 +492,22 @@ static size_t trunk_layout(TrunkWorkspace* ws, uint8_t* base, int N, int H, int 
     blk[i].norm0 = b.take<float>(e);
   }
   const size_t stats_bytes = al256((size_t)kGnLayers * N * kGnGroups * 2 * sizeof(double));
-  const size_t sync_bytes = (size_t)kGnLayers * ((size_t)N * kSyncPerImage + kSyncTickets) * sizeof(int);
+  const size_t sync_bytes = al256((size_t)kGnLayers * kSyncTickets * sizeof(int));
   double* stats = (double*)b.take<uint8_t>(stats_bytes + sync_bytes);
+  // exchange records of conv0 / conv1 of every stage (a projection never has a fused epilogue)
+  size_t rec_off[kGnLayers] = {}, nrec = 0;
+  for (int i = 0; i < kTrunkStages; ++i)
+    for (int k = 0; k < 2; ++k) {
+      rec_off[1 + 3 * i + k] = nrec;
+      nrec += (size_t)N * gnx_records_per_image(d.h[2 + i] * d.w[2 + i], kStageFilters[i]);
+    }
+  const size_t rec_bytes = al256(nrec * kGnxRecordBytes);
+  uint64_t* rec = (uint64_t*)b.take<uint8_t>(rec_bytes);
   if (ws) {
-    ws->sync = base ? (int*)(base + ((uint8_t*)stats - base) + stats_bytes) : nullptr;
+    ws->tickets = base ? (int*)(base + ((uint8_t*)stats - base) + stats_bytes) : nullptr;
     ws->stats_sync_bytes = stats_bytes + sync_bytes;
+    ws->rec = rec; ws->rec_bytes = rec_bytes; ws->epoch = 0;
+    for (int l = 0; l < kGnLayers; ++l) ws->rec_off[l] = rec_off[l];
     ws->max_images = N; ws->d = d; ws->raw_init = raw_init; ws->pool = pool;
     for (int i = 0; i < kTrunkStages; ++i) ws->blk[i] = blk[i];
     ws->stats = stats; ws->base = base; ws->bytes = b.off;

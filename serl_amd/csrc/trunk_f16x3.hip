@@ -61,7 +61,7 @@ static ConvArgs conv_geom(const TrunkDims& d, int N, int i, int k) {
 
 // shapes the row-slab kernel takes: stride-1 3x3 convs with 64 or 128 output channels on 32- or 16-pixel-wide maps
 static bool rowslab_shape_ok(const ConvArgs& a) {
-  return a.KH == 3 && a.stride == 1 && a.Cout <= 128 && a.Cout / 64 <= kSyncPerImage && a.Cin % 16 == 0 && a.Hi == a.Ho &&
+  return a.KH == 3 && a.stride == 1 && a.Cout <= 128 && a.Cin % 16 == 0 && a.Hi == a.Ho &&
          a.Wi == a.Wo && (a.Wo == 32 || a.Wo == 16) && a.Ho % (256 / a.Wo) == 0 && (long)a.N * a.Hi * a.Wi * a.Cin < (1L << 31);
 }
 // the fused epilogue's wait needs more than 8 (G - 1) co-resident workgroups (see FuseArgs); demand twice that of the
@@ -93,7 +93,9 @@ static TrunkPlan::L plan_conv(const ConvArgs& a, bool dma, bool zero_page, bool 
   if (slab_ok) {
     l.kern = 'S'; l.cfg = 9; l.raw = raw;
     const int tiles_n = a.Cout / 64;
-    if (fuse && a.P % 256 == 0 && fused_can_wait(resident, a.P / 256 * tiles_n)) {
+    if (fuse && a.P == 256) {
+      l.fused = 2;   // LOCAL: a 256 x 64 tile = one whole image over complete groups, nothing to exchange and nobody to wait for
+    } else if (fuse && a.P % 256 == 0 && fused_can_wait(resident, a.P / 256 * tiles_n)) {
       l.fused = 1; l.expected = a.P / 256; l.group = a.P / 256 * tiles_n;
     }
     // anti-phase start: 5 x s_sleep(127) ~ 20 us ~ half a tile of the stage-0 convs.  Same-call A/B (profiles/r04_ab_rs_stagger.txt):
@@ -103,7 +105,8 @@ static TrunkPlan::L plan_conv(const ConvArgs& a, bool dma, bool zero_page, bool 
     l.kern = 'D'; l.cfg = cfg;
     const int tn = cfg == 0 ? 2 : 1, tiles_n = a.Cout / (64 * tn);
     if (pmode == 1 && cfg == 4) pmode = 3;
-    if (fuse && pmode == 0 && a.P % 128 == 0 && tiles_n <= kSyncPerImage && fused_can_wait(resident, a.P / 128 * tiles_n)) {
+    // (the exchange is among the row tiles of ONE column tile: a GroupNorm group must not be wider than the tile)
+    if (fuse && pmode == 0 && a.P % 128 == 0 && a.Cout / kGnGroups <= 64 * tn && fused_can_wait(resident, a.P / 128 * tiles_n)) {
       l.fused = 1; l.expected = a.P / 128; l.group = a.P / 128 * tiles_n;
     } else if (fuse && pmode == 0 && a.P == 64 && a.M % 128 == 0 && tn == 2 && a.Cout / kGnGroups == 64) {
       l.fused = 2;   // LOCAL: a wave = one (image, group), no exchange
@@ -225,8 +228,9 @@ static int launch_conv_f16x3(const char* tag, const TrunkPlan::L& l, const ConvA
   return SERL_OK;
 }
 
-// Zeroes the statistics / arrival counters / tickets of a pass with SYSTEM-scope (write-through, sc0 sc1) 16-byte stores.
-// Everything that touches these words afterwards is a memory-side atomic (stats_flush, fused_arrive_and_wait, fused_tile),
+// Zeroes the statistics (of the unfused layers: a fused launch writes none) and the tickets of a pass -- and, before a workspace's
+// first pass, its exchange records -- with SYSTEM-scope (write-through, sc0 sc1) 16-byte stores.
+// Everything that touches these words afterwards is a memory-side access (stats_flush, fused_tile, gnx_publish / gnx_collect),
 // so the zeroes must be AT the memory side too and no cache may keep a copy: a plain-store zeroing kernel (round 2, reverted
 // after one unexplained parity failure) leaves the zeroed lines dirty in the L2 of whichever XCD ran the store until that
 // L2 writes them back -- ordered against the next kernel only by the launch boundary's cache maintenance, i.e. outside the
@@ -291,22 +295,30 @@ int trunk_forward_f16x3(const TrunkWeights& w, TrunkWorkspace& ws, TrunkPacked& 
                                          w.blk[3].proj != nullptr};
     const int resident = fuse ? resident_workgroups(stream) : 0;   // (only the fused epilogues wait for other workgroups)
     if ((rc = plan_pass(ws.plan, d, N, pk, has_proj, resident, fuse, !(pf && pf[0] == '0')))) return rc;
-    // statistics + arrival counters + tickets
-    if (ws.stats_sync_bytes % 16 == 0 && ws.stats_sync_bytes < ((size_t)1 << 31)) {
-      const long n16 = (long)(ws.stats_sync_bytes / 16);
-      hipLaunchKernelGGL(zero_sys_kernel, dim3((unsigned)std::min<long>(cdiv(n16, 256), 512)), dim3(256), 0, stream, (void*)ws.stats, n16);
-      SERL_HIP(hipGetLastError());
-    } else {
-      SERL_HIP(hipMemsetAsync(ws.stats, 0, ws.stats_sync_bytes, stream));
-    }
+    auto zero_sys = [&](void* p, size_t bytes) -> int {
+      for (size_t off = 0; off < bytes; off += (size_t)1 << 30) {   // (32-bit buffer offsets: 1 GiB per launch)
+        const long n16 = (long)(std::min(bytes - off, (size_t)1 << 30) / 16);
+        hipLaunchKernelGGL(zero_sys_kernel, dim3((unsigned)std::min<long>(cdiv(n16, 256), 512)), dim3(256), 0, stream,
+                           (void*)((uint8_t*)p + off), n16);
+        SERL_HIP(hipGetLastError());
+      }
+      return SERL_OK;
+    };
+    // statistics + tickets (both regions are multiples of 256 bytes: trunk_layout)
+    if ((rc = zero_sys(ws.stats, ws.stats_sync_bytes))) return rc;
+    // the pass epoch = the tag of this pass's granules (gn_exchange.h); the records are zeroed only when the rule says so
+    const GnxEpoch ep = gnx_next_epoch(ws.epoch);
+    if (ep.clear && (rc = zero_sys(ws.rec, ws.rec_bytes))) return rc;
+    ws.epoch = ep.epoch;
   } else {
     SERL_REQUIRE(plan.images == N, "trunk pass piece over %d images continues a pass planned for %d", N, plan.images);
   }
   auto fuse_of = [&](int layer, int mode) {
     FuseArgs f{};
     f.mode = mode;
-    f.sync = ws.sync + (size_t)layer * ((size_t)ws.max_images * kSyncPerImage + kSyncTickets);
-    f.ticket = f.sync + (size_t)ws.max_images * kSyncPerImage;
+    f.ticket = ws.tickets + (size_t)layer * kSyncTickets;
+    f.rec = ws.rec + ws.rec_off[layer] * kGnxGranules;
+    f.epoch = ws.epoch;
     return f;
   };
   const GnRef gn_init = gn_ref(stats_of(0), w.gn_init_s, w.gn_init_b, d.h[0] * d.w[0], 64);

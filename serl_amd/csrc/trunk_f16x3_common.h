@@ -1,12 +1,13 @@
 // Part of the split-fp16 trunk (trunk_f16x3.hip includes these in order; round 6 split the 2,600-line file by kernel family):
 // shared by every split-fp16 trunk kernel: argument structs, the hi / lo' split, LDS swizzle, the tile tickets and the
-// arrive-and-wait of the fused GroupNorm epilogues, the C-layout fused store (register-staged and LDS-DMA kernels).
+// statistics exchange of the fused GroupNorm epilogues, the C-layout fused store (register-staged and LDS-DMA kernels).
 #pragma once
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
 
+#include "gn_exchange.h"
 #include "prof.h"
 #include "trunk_common.h"
 
@@ -18,9 +19,10 @@ typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 constexpr float kLoScale = 2048.0f, kLoInv = 1.0f / 2048.0f;  // 2^11
 
 // GroupNorm (+ residual) + ReLU + split8 re-layout in the PRODUCING conv's epilogue (mode != 0) instead of a separate
-// elementwise pass over the raw fp32 tensor.  GroupNorm needs the statistics of the whole image, which G = 2..8 workgroups
-// produce: each adds its partial sums (fp64 atomics, as before), then bumps an arrival counter of the image and waits
-// until all of the image's workgroups have arrived.
+// elementwise pass over the raw fp32 tensor.  GroupNorm needs the statistics of the whole image.  Where a tile IS a whole image
+// over complete groups (or a wave's block is: LOCAL, expected == 0) they are taken inside the workgroup and nothing leaves it.
+// Otherwise G = 2..8 workgroups produce them: each PUBLISHES its partial sums as one record of data-tagged granules and reads the
+// records of the image's other tiles until every granule carries this pass's tag (gnx_publish / gnx_collect below, gn_exchange.h).
 // FORWARD PROGRESS.  Tiles are handed out by atomic TICKETS taken when a workgroup starts running (fused_tile): one
 // counter per XCD, each covering a contiguous range of whole images, so the G tiles of an image carry CONSECUTIVE tickets
 // of one counter (and are fetched through one L2).  A waiting workgroup therefore waits (a) for tiles that running
@@ -42,12 +44,14 @@ static int trunk_wave_prio(long images) { return images >= 512 ? 2 : 0; }
 
 struct FuseArgs {
   int mode;                 // 0 off; 1 relu(GN(y)); 2 relu(GN(y) + res_split); 3 relu(GN(y) + GN_res(res_raw))
-  int expected;             // arrivals per counter; 0 = LOCAL: a wave's 64 rows x 64 columns are exactly one (image, group), no
-                            // workgroup exchanges anything (P == 64 and Cout / 4 == 64: stage 2) -- no ticket, no wait
-  int* sync;                // [image][tiles_n] arrival counters, zeroed with the statistics
-  int* ticket;              // [8] per-XCD tile counters, zeroed with the statistics
+  int expected;             // row tiles per image = records a tile's statistics are summed from; 0 = LOCAL: the statistics of an
+                            // (image, group) lie inside one workgroup (a whole-image row-slab tile; a wave's 64 x 64 block in stage 2;
+                            // eight whole images per tile in stage 3) -- no ticket, no record, no wait
+  uint64_t* rec;            // this layer's records [tile][kGnxGranules] (gn_exchange.h); written and read with system-scope accesses only
+  uint32_t epoch;           // tag of this pass's granules, never 0
+  int* ticket;              // [8] per-XCD tile counters, zeroed per pass
   int group;                // G: tiles (workgroups) per image -- tickets of one image are consecutive
-  GnRef gn;                 // this conv's statistics (being produced), scale, bias
+  GnRef gn;                 // this conv's scale, bias and 1 / count (a fused launch writes no statistics: nothing reads them)
   GnRef res_gn;             // mode 3: the projection's GroupNorm (complete: that conv ran before)
   const uint8_t* res_split; // mode 2: the block input (split8)
   const float* res_raw;     // mode 3: raw projection output
@@ -131,41 +135,108 @@ __device__ __forceinline__ int fused_tile(const FuseArgs& fz, int ntiles) {
   return s_tile;
 }
 
-// Ordering without cache maintenance: the statistics, the arrival counters and the tickets are only ever touched by
-// SYSTEM-scope atomics (sc1: performed at the memory side, past the 8 per-XCD L2s -- an image's workgroups can sit on
-// different XCDs, and agent-scope atomics performed in one XCD's L2 reached the others late: 1e-4 errors at 1024 images),
-// and pollers read the statistics with system-scope atomic loads, so there is no cached copy anywhere that an L2
-// write-back / L1 invalidate would have to refresh (an agent-scope ACQUIRE in the polling loop invalidates caches on every
-// poll: measured 4x slower convs).  What remains is the ORDER "statistics performed before the arrival is performed":
-//   * the statistics atomics are RETURNING atomics whose results are consumed (stats_flush): a wave passes the
-//     s_waitcnt in front of the barrier below only when the memory side has answered, i.e. performed, each of them.
-//     (A NO-RETURN atomic leaves vmcnt when the L2 has ACCEPTED it -- trunk_common.h -- which is why the round-2
-//     no-return variant lost sums at 1024 images.)
-//   * the barrier orders every wave's (performed) statistics before thread 0 issues the arrival atomic.
-// In HIP memory-model terms the arrival is the release and the poll that sees `expected` the acquire; relaxed atomics
-// are enough here because every location involved is accessed with memory-side atomics only -- this rests on the measured
-// gfx950 behaviour above (tests/test_agent_gpu.py::test_fused_groupnorm_epilogue_is_race_free_*), not on the language model.
-__device__ __forceinline__ void fused_arrive_and_wait(int* ctr, int expected) {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    __hip_atomic_fetch_add(ctr, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    // (the bound turns a protocol error into a kernel abort instead of a hung GPU; a real wait is a few microseconds)
-    for (int spins = 0; __hip_atomic_load(ctr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) < expected; ++spins) {
+// THE EXCHANGE.  What a tile hands to the other tiles of its image is 16 or 32 fp32 partial sums.  Each travels as a GRANULE: one
+// naturally aligned 8-byte {value, tag} written by ONE system-scope store (global_store_dwordx2 sc0 sc1: write-through, past the 8
+// per-XCD L2s -- an image's workgroups can sit on different XCDs) and read by system-scope loads (global_load_dwordx2 sc0 sc1:
+// never served from a CU's L1).  The data is its own flag: a reader that sees this pass's tag in a granule has, from the same
+// load, the value that was stored with it, so the protocol needs NO ordering between memory operations -- no returning atomics,
+// no drain before a flag, no arrival counter, no separate statistics loads: a tile publishes and does not wait for its store,
+// and the last arriver's peers are complete one load round trip after its store lands.  That an aligned 8-byte store is never
+// observed torn is MEASURED gfx950 behaviour (ROCm 7.2), not an architectural guarantee; the reproducibility test of
+// tests/test_gn_exchange_gpu.py (bit-identical passes under uneven load) is what a torn or stale granule would break.
+// Tags are the workspace's pass epoch (gn_exchange.h: never 0, records zeroed before the first pass and at the wrap), every tile
+// has a record of its own per layer, so nothing is zeroed between passes and nothing is reused within one.
+// The statistics are what they were -- the fp64 sum of the same per-wave fp32 partials -- but in a FIXED order (a granule's
+// values over the image's tiles in tile order, then the waves, then a group's segments in channel order), where the fp64
+// atomics they replace added in arrival order: every pass over the same frames now gives the same bits.
+//
+// LAYOUT 0: row-slab tile, four waves over the SAME 64 channels, s_part[wave][segment * 2 + stat] (4 segments of 16 channels);
+// LAYOUT TN = 1 / 2: LDS-DMA tile, wave = wm * 2 + wn over columns wn * 32 TN .., s_part[wave][(tn * 2 + segment) * 2 + stat].
+template <int LAYOUT>
+struct GnxShape {
+  static constexpr int NP = LAYOUT == 0 ? 8 : 4 * LAYOUT;    // partials per wave
+  static constexpr int NG = 4 * NP;                          // granules of a record in use
+  static constexpr int NSEG = LAYOUT == 0 ? 4 : 4 * LAYOUT;  // 16-channel segments of the tile
+  static constexpr int NC = LAYOUT == 0 ? 4 : 2;             // waves that hold rows of one segment
+  static_assert(NG <= kGnxGranules, "a record holds the tile's partials");
+  // granule of the c-th contributing wave of tile segment `seg`
+  __device__ static __forceinline__ int granule(int c, int seg, int stat) {
+    if (LAYOUT == 0) return c * NP + seg * 2 + stat;
+    const int per_wave = 2 * LAYOUT, wn = seg / per_wave, j = seg - wn * per_wave;
+    return (c * 2 + wn) * NP + j * 2 + stat;
+  }
+};
+typedef __attribute__((address_space(1))) unsigned long long gnx_u64;
+
+// gnx_publish + gnx_collect are called by every thread of the workgroup BEHIND the barrier that completed s_part (the tile's NG
+// partials, wave-major); only wave 0 touches memory in them.  Publish: wave 0 stores the record of tile `tile` and does not wait
+// for it.  Collect (as late as the caller has other work to issue): wave 0 polls the image's other records and leaves mean / rstd
+// of every 16-channel segment of the tile (channels n0 + 16 seg ..) in s_mr; the closing barrier hands them to all waves.
+// The spin is bounded (trap): a protocol error aborts the kernel instead of hanging the GPU; a real wait is a few microseconds.
+template <int LAYOUT>
+__device__ __forceinline__ void gnx_publish(const FuseArgs& fz, int tile, int wave, int lane, const float* s_part) {
+  using S = GnxShape<LAYOUT>;
+  if (wave == 0 && lane < S::NG)
+    __hip_atomic_store((gnx_u64*)fz.rec + (size_t)tile * kGnxGranules + lane,
+                       (unsigned long long)gnx_pack(__builtin_bit_cast(uint32_t, s_part[lane]), fz.epoch), __ATOMIC_RELAXED,
+                       __HIP_MEMORY_SCOPE_SYSTEM);
+}
+template <int LAYOUT>
+__device__ __forceinline__ void gnx_collect(const FuseArgs& fz, int tile, int tiles_n, int n0, int wave, int lane, const float* s_part,
+                                            float (*s_mr)[2]) {
+  using S = GnxShape<LAYOUT>;
+  __shared__ double s_acc[S::NG];
+  if (wave == 0) {
+    gnx_u64* const rec = (gnx_u64*)fz.rec;
+    const GnxPeers pr = gnx_peers(tile, fz.expected, tiles_n);
+    const int gl = lane & (S::NG - 1);   // (lanes past NG repeat granules: same lines, no extra traffic, no divergence)
+    const float mine = s_part[gl];
+    double acc;
+    for (int spins = 0;; ++spins) {
+      bool ok = true;
+      acc = 0.0;
+      for (int p0 = 0; p0 < pr.count; p0 += 4) {   // four records' loads in flight together
+        unsigned long long x[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          x[k] = gnx_pack(__builtin_bit_cast(uint32_t, mine), fz.epoch);   // (its own partials come from LDS, not from memory)
+          if (p0 + k < pr.count && p0 + k != pr.self)
+            x[k] = __hip_atomic_load(rec + (size_t)(pr.first + (long)(p0 + k) * pr.stride) * kGnxGranules + gl, __ATOMIC_RELAXED,
+                                     __HIP_MEMORY_SCOPE_SYSTEM);
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+          if (p0 + k < pr.count) {
+            ok = ok && gnx_tag(x[k]) == fz.epoch;
+            acc += (double)__builtin_bit_cast(float, gnx_value(x[k]));
+          }
+      }
+      if (__all(ok)) break;
       __builtin_amdgcn_s_sleep(4);
       if (spins > (1 << 22)) __builtin_trap();
+    }
+    if (lane < S::NG) s_acc[gl] = acc;
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");   // (this wave's LDS writes before its own reads below)
+    __builtin_amdgcn_wave_barrier();
+    if (lane < S::NSEG) {
+      const int gsize = fz.gn.gsize, g = (n0 + 16 * lane) / gsize;
+      double s = 0.0, q = 0.0;
+      for (int seg = 0; seg < S::NSEG; ++seg)
+        if ((n0 + 16 * seg) / gsize == g)
+          for (int c = 0; c < S::NC; ++c) { s += s_acc[S::granule(c, seg, 0)]; q += s_acc[S::granule(c, seg, 1)]; }
+      const double mean = s * fz.gn.inv_count, m2 = q * fz.gn.inv_count;
+      const float var = fmaxf((float)(m2 - mean * mean), 0.f);
+      s_mr[lane][0] = (float)mean;
+      s_mr[lane][1] = rsqrtf(var + 1e-5f);
     }
   }
   __syncthreads();
 }
 
-// gn_coef4 for one channel; LIVE: the statistics were written by other workgroups of this launch (read at L2)
-template <bool LIVE>
+// GroupNorm scale / shift of one channel from the COMPLETE statistics of an earlier launch
 __device__ __forceinline__ void gn_coef1(const GnRef& g, int n, int c, float& sc, float& sh) {
   const double* st = g.stats + ((size_t)n * kGnGroups + c / g.gsize) * 2;
-  const double s0 = LIVE ? __hip_atomic_load(st, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) : st[0];
-  const double s1 = LIVE ? __hip_atomic_load(st + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) : st[1];
-  const double mean = s0 * g.inv_count, m2 = s1 * g.inv_count;
+  const double mean = st[0] * g.inv_count, m2 = st[1] * g.inv_count;
   const float var = fmaxf((float)(m2 - mean * mean), 0.f);
   const float rstd = rsqrtf(var + 1e-5f), mf = (float)mean;
   sc = g.gamma[c] * rstd;
@@ -211,12 +282,14 @@ __device__ __forceinline__ void fused_load_residual(const ConvArgsB& ab, FusedRe
     }
 }
 
+// The statistics come from the caller (taken inside the workgroup, LOCAL, or out of gnx_collect): mean[] / rstd[] hold one value per
+// slot, and with PER_TN one per (32-column block tn, slot) at [tn * NSLOT + slot] -- a wave's 64 columns span two 32-channel groups.
 // NSLOT = 4 (stage 3, images of 16 pixels): the wave's 64 rows are FOUR images, slot s = rows 16 s .. 16 s + 15 = image n_img + s, each with
-// its own statistics (local_mean / local_rstd then point at NSLOT values); NSLOT = 1: the whole block lies in image n_img.
-template <int TM, int TN, int NSLOT = 1>
+// its own statistics; NSLOT = 1: the whole block lies in image n_img.
+template <int TM, int TN, int NSLOT = 1, bool PER_TN = false>
 __device__ __forceinline__ void fused_gn_store(const ConvArgsB& ab, const f32x16 (&acc)[TM][TN],
                                                const FusedResidual<TM, TN>& res, int n_img, int wrow0, int col0, int li, int lh,
-                                               bool local = false, const float* local_mean = nullptr, const float* local_rstd = nullptr) {
+                                               const float* mean, const float* rstd) {
   const FuseArgs& fz = ab.fz;
   const int Cout = ab.c.Cout;
   const bool odd = li & 1;
@@ -231,13 +304,10 @@ __device__ __forceinline__ void fused_gn_store(const ConvArgsB& ab, const f32x16
 #pragma unroll
     for (int sl = 0; sl < NSLOT; ++sl) {
       rss[sl] = 0.f; rhs[sl] = 0.f;
-      if (local) {   // statistics of this wave's (or, NSLOT = 4, this workgroup's) own block = the whole (image, group)
-        scs[sl] = fz.gn.gamma[c] * local_rstd[sl];
-        shs[sl] = fz.gn.beta[c] - local_mean[sl] * scs[sl];
-      } else {
-        gn_coef1<true>(fz.gn, n_img + sl, c, scs[sl], shs[sl]);
-      }
-      if (fz.mode >= 3) gn_coef1<false>(fz.res_gn, n_img + sl, c, rss[sl], rhs[sl]);
+      const int si = (PER_TN ? tn * NSLOT : 0) + sl;
+      scs[sl] = fz.gn.gamma[c] * rstd[si];
+      shs[sl] = fz.gn.beta[c] - mean[si] * scs[sl];
+      if (fz.mode >= 3) gn_coef1(fz.res_gn, n_img + sl, c, rss[sl], rhs[sl]);
     }
     const int cbyte = (c & ~7) * 4 + (odd ? 16 : 0) + (c & 6) * 2;
 #pragma unroll

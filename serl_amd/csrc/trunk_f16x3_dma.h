@@ -39,7 +39,10 @@ __device__ __forceinline__ void dma_tile_epilogue(const ConvArgsB& ab, f32x16 (&
         }
       }
   }
-  if (PMODE != 3 && !(ab.fz.mode && !ab.fz.expected)) {   // (LOCAL fused mode keeps its statistics in the wave)
+  // Statistics for a LATER kernel: unfused launches only (a fused launch keeps its statistics in the workgroup or exchanges records,
+  // and nothing reads a.stats of a fused layer).  (PMODE 1 / 2: a fused launch there is always LOCAL, `expected` is 0 -- the test stays
+  // in its earlier form because without it the compiler gives the stage-3 kernel 256 registers and spills.)
+  if (PMODE != 3 && !(ab.fz.mode && (PMODE == 0 || !ab.fz.expected))) {
     const int gsize = a.Cout / kGnGroups;
     constexpr int ROWS = PMODE == 0 ? WROWS : (PMODE == 1 ? 32 : 16);
     constexpr int NSLOT = WROWS / ROWS;
@@ -63,14 +66,41 @@ __device__ __forceinline__ void dma_tile_epilogue(const ConvArgsB& ab, f32x16 (&
               q += v * v;
             }
           }
-        stats_flush(s, q, stp, n0 + wn * WCOLS + tn * 32 + li, gsize, valid, ab.fz.mode != 0);   // (unfused: a later kernel reads them)
+        stats_flush(s, q, stp, n0 + wn * WCOLS + tn * 32 + li, gsize, valid, false);   // (a later kernel reads them)
       }
     }
   }
   if (PMODE == 0 && ab.fz.mode && ab.fz.expected) {   // the launcher guarantees P % BM == 0: the whole tile lies in one image
-    const int n_img = m0 / a.P;
-    fused_arrive_and_wait(ab.fz.sync + n_img * a.tiles_n + bn, ab.fz.expected);
-    fused_gn_store<TM, TN>(ab, acc, fres, n_img, wrow0, n0 + wn * WCOLS, li, lh);
+    // The image's P / 128 row tiles exchange their statistics (gnx_publish / gnx_collect, trunk_f16x3_common.h): every wave leaves its partial
+    // sums per 16-channel segment in LDS, wave 0 publishes them as the tile's record and collects the other tiles' records.
+    __shared__ float s_part[4][4 * TN];   // [wave = wm * 2 + wn][(tn * 2 + 16-channel segment) * 2 + {sum, sumsq}]
+    __shared__ float s_mr[4 * TN][2];     // [segment of the tile][mean, rstd]
+    const int n_img = m0 / a.P, wave = wm * 2 + wn, lane = lh * 32 + li;
+#pragma unroll
+    for (int tn = 0; tn < TN; ++tn) {
+      float s = 0.f, q = 0.f;
+#pragma unroll
+      for (int tm = 0; tm < TM; ++tm)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) { const float v = acc[tm][tn][r]; s += v; q += v * v; }
+#pragma unroll
+      for (int off = 1; off < 16; off <<= 1) { s += __shfl_xor(s, off); q += __shfl_xor(q, off); }
+      s += __shfl_xor(s, 32);
+      q += __shfl_xor(q, 32);
+      if ((lane & 15) == 0 && lane < 32) {
+        s_part[wave][(tn * 2 + (lane >> 4)) * 2] = s;
+        s_part[wave][(tn * 2 + (lane >> 4)) * 2 + 1] = q;
+      }
+    }
+    __syncthreads();
+    const int tile_id = (m0 / 128) * a.tiles_n + bn;
+    gnx_publish<TN>(ab.fz, tile_id, wave, lane, &s_part[0][0]);
+    gnx_collect<TN>(ab.fz, tile_id, a.tiles_n, n0, wave, lane, &s_part[0][0], s_mr);
+    // (a group is at least 32 channels here -- Cout >= 128 -- so both segments of a 32-column block share their statistics)
+    float lmean[TN], lrstd[TN];
+#pragma unroll
+    for (int tn = 0; tn < TN; ++tn) { lmean[tn] = s_mr[wn * 2 * TN + tn * 2][0]; lrstd[tn] = s_mr[wn * 2 * TN + tn * 2][1]; }
+    fused_gn_store<TM, TN, 1, true>(ab, acc, fres, n_img, wrow0, n0 + wn * WCOLS, li, lh, lmean, lrstd);
   } else if (PMODE == 0 && ab.fz.mode) {              // LOCAL: this wave's block is one whole (image, group)
     double s = 0.0, q = 0.0;
 #pragma unroll
@@ -87,7 +117,7 @@ __device__ __forceinline__ void dma_tile_epilogue(const ConvArgsB& ab, f32x16 (&
     const double mean = s * ab.fz.gn.inv_count, m2 = q * ab.fz.gn.inv_count;
     const float var = fmaxf((float)(m2 - mean * mean), 0.f);
     const float lmean = (float)mean, lrstd = rsqrtf(var + 1e-5f);
-    fused_gn_store<TM, TN>(ab, acc, fres, wrow0 / a.P, wrow0, n0 + wn * WCOLS, li, lh, true, &lmean, &lrstd);
+    fused_gn_store<TM, TN>(ab, acc, fres, wrow0 / a.P, wrow0, n0 + wn * WCOLS, li, lh, &lmean, &lrstd);
   } else if (PMODE == 2 && ab.fz.mode) {
     // LOCAL, stage 3 (round 6): images of 16 pixels, 128 channels per group.  The workgroup's 128 x 128 tile holds EIGHT whole images of ONE
     // group; a wave holds four of them (16-row slots) over half the group's channels, so the statistics of an (image, group) are this wave's
@@ -121,7 +151,7 @@ __device__ __forceinline__ void dma_tile_epilogue(const ConvArgsB& ab, f32x16 (&
       const float var = fmaxf((float)(m2 - mean * mean), 0.f);
       lmean[sl] = (float)mean; lrstd[sl] = rsqrtf(var + 1e-5f);
     }
-    fused_gn_store<TM, TN, 4>(ab, acc, fres, wrow0 / a.P, wrow0, n0 + wn * WCOLS, li, lh, true, lmean, lrstd);
+    fused_gn_store<TM, TN, 4>(ab, acc, fres, wrow0 / a.P, wrow0, n0 + wn * WCOLS, li, lh, lmean, lrstd);
   }
 }
 

@@ -57,9 +57,10 @@ __device__ __forceinline__ void rowtile_epilogue(const ConvArgsB& ab, f32x16 (&a
 // 16 KB per wave, and reads it back with a lane owning EIGHT consecutive channels of a row: the residual arrives as two 16-byte
 // loads, the split8 record (16 bytes of hi halves + 16 bytes of lo' halves) leaves as two 16-byte stores, eight lanes cover a
 // row's 256 contiguous bytes -- 16 + 16 wide memory instructions per lane instead of 64 + 64 narrow ones, no lane exchange.
-// Same arithmetic per element as fused_gn_store.  Statistics, arrival and wait are unchanged (taken from the registers first).
+// Same arithmetic per element as fused_gn_store.  The statistics are taken from the registers first; `tile` = the tile's number in the
+// launch (its record, gn_exchange.h).
 __device__ __forceinline__ void rowtile_epilogue_t(const ConvArgsB& ab, f32x16 (&acc)[2][2], f32x16 (&accx)[2][2], int m0, int n0,
-                                                   int n_img, int wave, int lane, int sync_idx, uint8_t* lds) {
+                                                   int n_img, int wave, int lane, int tile_id, uint8_t* lds) {
   const ConvArgs& a = ab.c;
   const FuseArgs& fz = ab.fz;
   constexpr int TM = 2, TN = 2, WROWS = 64;
@@ -75,42 +76,32 @@ __device__ __forceinline__ void rowtile_epilogue_t(const ConvArgsB& ab, f32x16 (
     for (int tn = 0; tn < TN; ++tn)
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[tm][tn][r] = (acc[tm][tn][r] + accx[tm][tn][r] * kLoInv) * winv[tn];
-  {
-    // Statistics: the four waves of the tile cover the SAME 64 channels of the SAME image, so their partial sums are added in the
-    // workgroup first (through LDS, in wave order, in fp64) and ONE wave issues the returning atomics: 8 per tile instead of 32.  The
-    // atomics are contended at the memory side -- 4 tiles x 4 waves x 8 on the eight (sum, sumsq) words of an image -- and the timing
-    // ablation without them ran the stage-0 convs 22-37 us shorter; issuing a wave's four at once instead of two and two made the
-    // kernels SLOWER (profiles/README.md round 6), fewer of them is what helps.  Ordering as before: the results are consumed before
-    // the barrier in front of the arrival (fused_arrive_and_wait).
-    __shared__ float s_part[4][8];   // [wave][(tn * 2 + 16-channel segment) * 2 + {sum, sumsq}]
-    const int gsize = a.Cout / kGnGroups;
-    double* stp = a.stats + (size_t)n_img * kGnGroups * 2;
+  // Statistics: the four waves of the tile cover the SAME 64 channels of the SAME image; each leaves its partial sums per 16-channel
+  // segment in s_part.  LOCAL (fz.expected == 0): the tile is a whole image, its 64 channels are complete GroupNorm groups and s_part
+  // is all any lane needs -- nothing leaves the workgroup.  Else wave 0 publishes s_part as the tile's record, at once, and collects
+  // the image's other records behind the residual prefetch (gnx_publish / gnx_collect, trunk_f16x3_common.h).  a.stats stays untouched either way.
+  const bool local = fz.expected == 0;
+  const int gsize = a.Cout / kGnGroups;
+  __shared__ float s_part[4][8];   // [wave][(tn * 2 + 16-channel segment) * 2 + {sum, sumsq}]
+  __shared__ float s_mr[4][2];     // exchange: [segment][mean, rstd]
 #pragma unroll
-    for (int tn = 0; tn < TN; ++tn) {
-      float s = 0.f, q = 0.f;
+  for (int tn = 0; tn < TN; ++tn) {
+    float s = 0.f, q = 0.f;
 #pragma unroll
-      for (int tm = 0; tm < TM; ++tm)
+    for (int tm = 0; tm < TM; ++tm)
 #pragma unroll
-        for (int r = 0; r < 16; ++r) { const float v = acc[tm][tn][r]; s += v; q += v * v; }
+      for (int r = 0; r < 16; ++r) { const float v = acc[tm][tn][r]; s += v; q += v * v; }
 #pragma unroll
-      for (int off = 1; off < 16; off <<= 1) { s += __shfl_xor(s, off); q += __shfl_xor(q, off); }
-      s += __shfl_xor(s, 32);
-      q += __shfl_xor(q, 32);
-      if ((lane & 15) == 0 && lane < 32) {
-        s_part[wave][(tn * 2 + (lane >> 4)) * 2] = s;
-        s_part[wave][(tn * 2 + (lane >> 4)) * 2 + 1] = q;
-      }
-    }
-    __syncthreads();
-    if (wave == 0 && lane < 4) {   // lane = tn * 2 + segment
-      const double ss = (((double)s_part[0][2 * lane] + (double)s_part[1][2 * lane]) + (double)s_part[2][2 * lane]) + (double)s_part[3][2 * lane];
-      const double qq = (((double)s_part[0][2 * lane + 1] + (double)s_part[1][2 * lane + 1]) + (double)s_part[2][2 * lane + 1]) + (double)s_part[3][2 * lane + 1];
-      const int g = (n0 + 16 * lane) / gsize;
-      const double o0 = __hip_atomic_fetch_add(&stp[2 * g], ss, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-      const double o1 = __hip_atomic_fetch_add(&stp[2 * g + 1], qq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-      asm volatile("" ::"v"(o0), "v"(o1));
+    for (int off = 1; off < 16; off <<= 1) { s += __shfl_xor(s, off); q += __shfl_xor(q, off); }
+    s += __shfl_xor(s, 32);
+    q += __shfl_xor(q, 32);
+    if ((lane & 15) == 0 && lane < 32) {
+      s_part[wave][(tn * 2 + (lane >> 4)) * 2] = s;
+      s_part[wave][(tn * 2 + (lane >> 4)) * 2 + 1] = q;
     }
   }
+  __syncthreads();
+  if (!local) gnx_publish<0>(fz, tile_id, wave, lane, &s_part[0][0]);
   // the wave's tile -> LDS [row][64 floats] (every wave passed the main loop's last barrier: the operand buffers are idle)
   float* tile = reinterpret_cast<float*>(lds) + wave * (64 * 64);
 #pragma unroll
@@ -133,20 +124,31 @@ __device__ __forceinline__ void rowtile_epilogue_t(const ConvArgsB& ab, f32x16 (
       rres[p][1] = *reinterpret_cast<const u32x4*>(q + 16);
     }
   }
-  fused_arrive_and_wait(fz.sync + sync_idx, fz.expected);
   float sc[8], sh[8], rs[8], rh[8];
   {
-    const double* st = fz.gn.stats + ((size_t)n_img * kGnGroups + c0 / fz.gn.gsize) * 2;   // (8 consecutive channels: one group)
-    const double s0 = __hip_atomic_load(st, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    const double s1 = __hip_atomic_load(st + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    const double mean = s0 * fz.gn.inv_count, m2 = s1 * fz.gn.inv_count;
-    const float var = fmaxf((float)(m2 - mean * mean), 0.f);
-    const float rstd = rsqrtf(var + 1e-5f), mf = (float)mean;
+    float rstd, mf;
+    if (local) {
+      // this lane's group = nseg 16-channel segments of s_part (1 at 64 output channels, 2 at 128): each segment's four partials are
+      // added in wave order and the segments in channel order, in fp64
+      const int nseg = gsize >> 4, seg0 = (8 * g8 / gsize) * nseg;
+      double s0 = 0.0, s1 = 0.0;
+      for (int j = 0; j < nseg; ++j) {
+        const int k = 2 * (seg0 + j);
+        s0 += (((double)s_part[0][k] + (double)s_part[1][k]) + (double)s_part[2][k]) + (double)s_part[3][k];
+        s1 += (((double)s_part[0][k + 1] + (double)s_part[1][k + 1]) + (double)s_part[2][k + 1]) + (double)s_part[3][k + 1];
+      }
+      const double mean = s0 * fz.gn.inv_count, m2 = s1 * fz.gn.inv_count;
+      const float var = fmaxf((float)(m2 - mean * mean), 0.f);
+      rstd = rsqrtf(var + 1e-5f); mf = (float)mean;
+    } else {
+      gnx_collect<0>(fz, tile_id, a.tiles_n, n0, wave, lane, &s_part[0][0], s_mr);
+      mf = s_mr[g8 >> 1][0]; rstd = s_mr[g8 >> 1][1];   // (8 consecutive channels: one segment)
+    }
 #pragma unroll
     for (int j = 0; j < 8; ++j) { sc[j] = fz.gn.gamma[c0 + j] * rstd; sh[j] = fz.gn.beta[c0 + j] - mf * sc[j]; rs[j] = 0.f; rh[j] = 0.f; }
     if (fz.mode >= 3) {
 #pragma unroll
-      for (int j = 0; j < 8; ++j) gn_coef1<false>(fz.res_gn, n_img, c0 + j, rs[j], rh[j]);
+      for (int j = 0; j < 8; ++j) gn_coef1(fz.res_gn, n_img, c0 + j, rs[j], rh[j]);
     }
   }
   uint8_t* out_base = fz.out_split + (size_t)wrow0 * rowb + c0 * 4;
@@ -242,7 +244,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_rowslab_f16x3_kernel(ConvArgsB
   if (ab.wprio) __builtin_amdgcn_s_setprio(3);
   if (ab.stagger > 0 && blockIdx.x >= 256u && blockIdx.x < 512u)
     for (int i = 0; i < ab.stagger; ++i) __builtin_amdgcn_s_sleep(127);
-  const int id = ab.fz.mode ? fused_tile(ab.fz, gridDim.x) : xcd_remap((int)blockIdx.x, gridDim.x);
+  const int id = (ab.fz.mode && ab.fz.expected) ? fused_tile(ab.fz, gridDim.x) : xcd_remap((int)blockIdx.x, gridDim.x);
   const int bn = id % a.tiles_n, bm = id / a.tiles_n;   // 64-channel column tiles of one row tile are neighbours (shared slab in L2)
   const int m0 = bm * BM, n0 = bn * BN;
   const int n_img = m0 / a.P, oy0 = (m0 - n_img * a.P) / a.Wo;
@@ -251,7 +253,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_rowslab_f16x3_kernel(ConvArgsB
   int rbase[3][AJ];        // element offset of unit (part, j) of a slab at channel group 0 (clamped into the image)
   unsigned okbits = 0;     // bit part*AJ + j: the unit's pixel lies inside the image (else it is stored as zeros)
   __shared__ float s_gn[2][128];   // GroupNorm scale / shift per input channel of this tile's image
-  if (tid < a.Cin) gn_coef1<false>(a.in_gn, n_img, tid, s_gn[0][tid], s_gn[1][tid]);
+  if (tid < a.Cin) gn_coef1(a.in_gn, n_img, tid, s_gn[0][tid], s_gn[1][tid]);
 #pragma unroll
   for (int part = 0; part < 3; ++part) {   // (pixel, k-half) = part * 256 + tid; both staging registers belong to it
     const int v = part * 256 + tid, pix = v >> 1, kh = v & 1;
@@ -381,7 +383,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_rowslab_f16x3_kernel(ConvArgsB
 #undef SERL_RS_LOADS
 #undef SERL_RS_STORES
 #undef SERL_RS_COMPUTE
-  rowtile_epilogue_t(ab, acc, accx, m0, n0, n_img, wave, lane, n_img * a.tiles_n + bn, smemb);
+  rowtile_epilogue_t(ab, acc, accx, m0, n0, n_img, wave, lane, id, smemb);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -416,7 +418,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_slabdma_f16x3_kernel(ConvArgsB
   if (ab.wprio) __builtin_amdgcn_s_setprio(3);
   if (ab.stagger > 0 && blockIdx.x >= 256u && blockIdx.x < 512u)   // anti-phase start, see conv3x3_rowslab_f16x3_kernel
     for (int i = 0; i < ab.stagger; ++i) __builtin_amdgcn_s_sleep(127);
-  const int id = ab.fz.mode ? fused_tile(ab.fz, gridDim.x) : xcd_remap((int)blockIdx.x, gridDim.x);
+  const int id = (ab.fz.mode && ab.fz.expected) ? fused_tile(ab.fz, gridDim.x) : xcd_remap((int)blockIdx.x, gridDim.x);
   const int bn = id % a.tiles_n, bm = id / a.tiles_n;
   const int m0 = bm * BM, n0 = bn * BN;
   const int n_img = m0 / a.P, oy0 = (m0 - n_img * a.P) / a.Wo;
@@ -522,7 +524,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_slabdma_f16x3_kernel(ConvArgsB
   }
 #undef SERL_SD_SLAB
 #undef SERL_SD_W
-  if (EPT) rowtile_epilogue_t(ab, acc, accx, m0, n0, n_img, wave, lane, n_img * a.tiles_n + bn, smemb);
+  if (EPT) rowtile_epilogue_t(ab, acc, accx, m0, n0, n_img, wave, lane, id, smemb);
   else rowtile_epilogue(ab, acc, accx, m0, n0, n_img, wave, li, lh);
 }
 
