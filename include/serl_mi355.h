@@ -72,11 +72,31 @@ int serl_rb_rng_state(serl_rb* rb, uint64_t out_state_inc[4], int* has_uint32, u
 /* MemoryEfficientReplayBuffer.insert (memory_efficient_replay_buffer.py:53-89), thread-safe like
  * MemoryEfficientReplayBufferDataStore.insert (data_store.py:104-106).
  * obs_frames[c] / next_frames[c]: host u8[T][H][W][C] for camera c; state/next_state: host
- * f32[T*S]; action: host f32[A]. */
+ * f32[T*S]; action: host f32[A].  A NULL array, table or table entry is SERL_ERR_INVALID (the entries are checked since the
+ * argument checks are shared with serl_rb_insert_batch). */
 int serl_rb_insert(serl_rb* rb, const uint8_t* const* obs_frames,
                    const uint8_t* const* next_frames, const float* state,
                    const float* next_state, const float* action, float reward, float mask,
                    int done);
+
+/* n calls of serl_rb_insert, in order, with byte-identical results (frames, records, valid mask, size, insert_index,
+ * insert_count, first; the sampler's generator is not touched) -- what an actor's message or a file of demonstrations brings.
+ * obs_frames / next_frames: [n * n_cam] host pointers, entry i*n_cam + c -> u8[T][H][W][C] (NULL tables for a store without
+ * cameras); state, next_state f32[n][T*S]; action f32[n][A]; reward, mask f32[n]; done u8[n].
+ * Every argument is checked before anything is inserted: n < 0, a NULL array or a NULL table entry is SERL_ERR_INVALID and leaves
+ * the store untouched; n == 0 succeeds and does nothing.  The slot writes are staged in slots of 2 MB and go to HBM with ONE
+ * host-to-device copy and ONE kernel launch per staging slot, whatever the number of cameras (a payload that wraps the ring or
+ * overwrites its own slots takes a few more launches).  The store's mutex is released between transitions only: another thread's
+ * index draw, gather or snapshot export sees each transition wholly or not at all.  Where it releases the mutex the call stands
+ * back, for at most 100 us, while an index draw or a gather of another thread waits for it: inserts yield priority to readers.
+ * "Untouched" covers the argument checks only: a HIP error in the middle of a payload (SERL_ERR_HIP) leaves the bookkeeping and
+ * serl_rb_insert_stats advanced for transitions whose data may not have reached HBM, exactly as a HIP error inside
+ * serl_rb_insert does -- such a store is to be discarded. */
+int serl_rb_insert_batch(serl_rb* rb, int n, const uint8_t* const* obs_frames, const uint8_t* const* next_frames,
+                         const float* state, const float* next_state, const float* action,
+                         const float* reward, const float* mask, const uint8_t* done);
+/* out = { transitions inserted, serl_rb_insert_batch calls, H2D copies enqueued by inserts, kernel launches enqueued by inserts } */
+int serl_rb_insert_stats(serl_rb* rb, int64_t out[4]);
 
 int64_t serl_rb_len(serl_rb* rb);          /* ReplayBuffer.__len__ (replay_buffer.py:68-69) */
 int64_t serl_rb_insert_index(serl_rb* rb); /* latest_data_id (data_store.py:138-140) */

@@ -55,6 +55,8 @@ SIGNATURES = {
     "serl_rb_seed": [vp, u64, u64, u64, u64, i32, u32],
     "serl_rb_rng_state": [vp, P(u64), P(i32), P(u32)],
     "serl_rb_insert": [vp, P(vp), P(vp), vp, vp, vp, f32, f32, i32],
+    "serl_rb_insert_batch": [vp, i32, P(vp), P(vp), vp, vp, vp, vp, vp, vp],
+    "serl_rb_insert_stats": [vp, P(i64)],
     "serl_rb_len": [vp],
     "serl_rb_insert_index": [vp],
     "serl_rb_valid_mask": [vp, vp],

@@ -6,14 +6,18 @@
 // (K2+K3+K4).  It is HBM-bound u8 traffic: every source frame row is pulled once with 16-byte
 // coalesced loads into LDS, shifted/clamped out of LDS, and written once with 16-byte stores.
 #include <algorithm>
+#include <atomic>
+#include <chrono>
 #include <condition_variable>
 #include <cstring>
 #include <memory>
 #include <mutex>
+#include <thread>
 #include <vector>
 
 #include "common.h"
 #include "prof.h"
+#include "replay_batch.h"
 #include "replay_index.h"
 #include "stack_index.h"
 
@@ -32,6 +36,9 @@ constexpr int kInsRing = 32;       // pinned staging slots for inserted transiti
 constexpr int kRowsPerBlock = 32;  // output rows per workgroup in the gather/crop kernel
 constexpr int kMaxStack = 4;       // most frames per observation the crop kernels and the agent serve (serl_agent_cfg.num_stack)
 constexpr size_t kXferChunk = (size_t)8 << 20;  // bytes per pinned staging buffer of the snapshot export / import (two of them)
+constexpr int kBatRing = 2;                     // staging slots of the batched insert, pinned and device: one launch each
+constexpr size_t kBatBudget = (size_t)2 << 20;  // bytes per such slot (it always holds at least one entry)
+constexpr int kHandOverUs = 100;                // longest a batched insert stands back for waiting readers between two groups
 
 // A ring of `n` pinned host slots (and, if asked for, as many device slots) with one event per slot.  acquire() hands out the
 // next slot, first waiting for the work that last used it if the ring has wrapped; mark() records that work's end.  The owner
@@ -107,6 +114,19 @@ struct serl_rb {
   hipEvent_t last_insert = nullptr;
   bool insert_pending = false;
   serl::StageRing stage;  // per-call parameter staging (pinned host + device)
+  // batched inserts (serl_rb_insert_batch): replay_batch.h groups the slot operations of a payload into launches; a launch is
+  // staged in one slot of `bat` -- its entries (one slot write each, laid out like a slot of `ins`: the record padded to
+  // rec_pad bytes, then one frame per camera), then its op table -- and costs one H2D copy and one insert_scatter_kernel on
+  // copy_stream.  The ring is made at the first batched call.
+  size_t rec_pad = 0, entry_bytes = 0;
+  serl::StageRing bat;
+  bool bat_taken = false;  // the launch being built has its slot of `bat`
+  serl::BatchPlan plan;
+  int64_t stats[4] = {0, 0, 0, 0};  // serl_rb_insert_stats
+  // index draws and gathers that wait for `mu` or hold it (Reader below).  Between two of its groups a batched insert stands
+  // back while this is not zero, for at most kHandOverUs: unlocking alone lets nobody in, the inserting thread has the mutex
+  // back before a thread it woke gets to run.  The wait is bounded, so readers that overlap without end cannot starve inserts.
+  std::atomic<int> readers{0};
 };
 
 namespace serl {
@@ -363,9 +383,72 @@ __global__ __launch_bounds__(256) void gather_packed_kernel(PackedArgs a) {
   }
 }
 
+// Batched insert: executes the op table of one launch (replay_batch.h), in no defined order.  A frame workgroup moves one
+// (op, camera, 16 KB part) of frame bytes into the store, from the launch's staging entries or -- copy ops, the wrap re-insert --
+// from another slot of the store; each thread issues its four 16-byte loads before its first store, as gather_crop_rgb_kernel
+// does.  The workgroups after them move the records, one thread per (op, float).
+struct ScatterArgs {
+  uint8_t* frames[SERL_MAX_CAMS];
+  float* rec;
+  const uint8_t* entries;  // device copy of the launch's staging entries
+  const BatchOp* ops;
+  int n_ops, n_cam, parts, rec_len, n_frame_blocks;
+  size_t fbytes, entry_bytes, rec_pad;
+};
+
+__global__ __launch_bounds__(256) void insert_scatter_kernel(ScatterArgs a) {
+  const int tid = threadIdx.x;
+  if ((int)blockIdx.x < a.n_frame_blocks) {
+    int bid = blockIdx.x;
+    const int part = bid % a.parts;
+    bid /= a.parts;
+    const int cam = bid % a.n_cam;
+    const BatchOp op = a.ops[bid / a.n_cam];
+    const uint8_t* src = op.kind == SlotOp::kCopy ? a.frames[cam] + (size_t)op.src * a.fbytes
+                                                  : a.entries + (size_t)op.src * a.entry_bytes + a.rec_pad + (size_t)cam * a.fbytes;
+    uint8_t* dst = a.frames[cam] + (size_t)op.dst * a.fbytes;
+    const int nvec = (int)(a.fbytes / 16);
+    uint4 val[kDirectVec];
+#pragma unroll
+    for (int j = 0; j < kDirectVec; ++j) {
+      const int v = min((part * kDirectVec + j) * 256 + tid, nvec - 1);
+      val[j] = *reinterpret_cast<const uint4*>(src + (size_t)v * 16);
+    }
+#pragma unroll
+    for (int j = 0; j < kDirectVec; ++j) {
+      const int v = (part * kDirectVec + j) * 256 + tid;
+      if (v < nvec) *reinterpret_cast<uint4*>(dst + (size_t)v * 16) = val[j];
+    }
+  } else {
+    const int e = ((int)blockIdx.x - a.n_frame_blocks) * 256 + tid;
+    const int o = e / a.rec_len, f = e - o * a.rec_len;
+    if (o >= a.n_ops) return;
+    const BatchOp op = a.ops[o];
+    const float* src = op.kind == SlotOp::kCopy ? a.rec + (size_t)op.src * a.rec_len
+                                                : reinterpret_cast<const float*>(a.entries + (size_t)op.src * a.entry_bytes);
+    a.rec[(size_t)op.dst * a.rec_len + f] = src[f];
+  }
+}
+
 // ---------------------------------------------------------------------------------------------
 // host helpers
 // ---------------------------------------------------------------------------------------------
+// Declared in front of the lock of an index draw or a gather, so that it counts from before the wait for the mutex until after
+// its release.
+struct Reader {
+  serl_rb* rbs[SERL_MAX_BUFFERS] = {nullptr};
+  explicit Reader(serl_rb* a, serl_rb* b = nullptr) : rbs{a, b} {
+    for (serl_rb* rb : rbs)
+      if (rb) rb->readers.fetch_add(1);
+  }
+  ~Reader() {
+    for (serl_rb* rb : rbs)
+      if (rb) rb->readers.fetch_sub(1);
+  }
+  Reader(const Reader&) = delete;
+  Reader& operator=(const Reader&) = delete;
+};
+
 // An insert must not overwrite a slot that an in-flight gather may still read: the copy stream waits (on the device)
 // for the last enqueued gather.  Caller holds rb->mu.
 static int order_after_gathers(serl_rb* rb) {
@@ -421,12 +504,13 @@ static int write_slot(serl_rb* rb, int64_t i, const uint8_t* const* frames_host,
   uint8_t* h = rb->ins.h();
   const size_t rec_bytes = sizeof(float) * rb->rec_len;
   std::memcpy(h, rec, rec_bytes);
-  const size_t f0 = (rec_bytes + 255) & ~(size_t)255;
+  const size_t f0 = rb->rec_pad;
   for (int c = 0; c < rb->n_cam; ++c) std::memcpy(h + f0 + (size_t)c * rb->frame_bytes, frames_host[c], rb->frame_bytes);
   SERL_HIP(hipMemcpyAsync(rb->rec + (size_t)i * rb->rec_len, h, rec_bytes, hipMemcpyHostToDevice, rb->copy_stream));
   for (int c = 0; c < rb->n_cam; ++c)
     SERL_HIP(hipMemcpyAsync(rb->frames[c] + (size_t)i * rb->frame_bytes, h + f0 + (size_t)c * rb->frame_bytes,
                             rb->frame_bytes, hipMemcpyHostToDevice, rb->copy_stream));
+  rb->stats[2] += rb->n_cam + 1;
   return rb->ins.mark(rb->copy_stream);
 }
 
@@ -446,6 +530,94 @@ static int finish_insert(serl_rb* rb) {
   SERL_HIP(hipEventRecord(rb->last_insert, rb->copy_stream));
   rb->insert_pending = true;
   return SERL_OK;
+}
+
+// what both insert entry points check of their arguments: `n` transitions, frame tables of n * n_cam host pointers
+static int check_insert_args(const serl_rb* rb, int64_t n, const uint8_t* const* obs_frames, const uint8_t* const* next_frames,
+                             const float* state, const float* next_state, const float* action) {
+  SERL_REQUIRE(rb && state && next_state && action, "NULL argument");
+  SERL_REQUIRE(rb->n_cam == 0 || (obs_frames && next_frames), "NULL frames");
+  for (int64_t k = 0; k < n * rb->n_cam; ++k)
+    SERL_REQUIRE(obs_frames[k] && next_frames[k], "a frame pointer of transition %lld, camera %d is NULL", (long long)(k / rb->n_cam),
+                 (int)(k % rb->n_cam));
+  return SERL_OK;
+}
+// the record of a transition: [state T*S | next_state T*S | action A | reward | mask | done]
+static void pack_record(const serl_rb* rb, float* rec, const float* state, const float* next_state, const float* action, float reward,
+                        float mask, bool done) {
+  const int TS = rb->T * rb->S;
+  std::memcpy(rec, state, sizeof(float) * TS);
+  std::memcpy(rec + TS, next_state, sizeof(float) * TS);
+  std::memcpy(rec + 2 * TS, action, sizeof(float) * rb->A);
+  rec[2 * TS + rb->A] = reward;
+  rec[2 * TS + rb->A + 1] = mask;
+  rec[2 * TS + rb->A + 2] = done ? 1.0f : 0.0f;
+}
+
+// ---- batched insert.  The caller holds rb->mu throughout.
+// The staging ring of the launches, made at the first batched call: a slot holds as many entries as fit kBatBudget with their
+// places in the op table (at least one), and the table's places for the copies of a wrap.
+static int batch_init(serl_rb* rb) {
+  if (rb->bat.n) return SERL_OK;
+  const size_t per_entry = rb->entry_bytes + sizeof(BatchOp), fixed = sizeof(BatchOp) * (size_t)rb->T;
+  const size_t entries = std::min<size_t>(std::max<size_t>((kBatBudget - std::min(fixed, kBatBudget)) / per_entry, 1), 1 << 20);
+  rb->plan.init(rb->ix.cap, rb->T, (int)entries);
+  const int rc = rb->bat.init(kBatRing, entries * rb->entry_bytes + sizeof(BatchOp) * (size_t)rb->plan.max_ops, true);
+  if (rc != SERL_OK) {  // nothing half-built stays behind: the next call tries again
+    rb->bat.destroy();
+    rb->bat = StageRing();
+  }
+  return rc;
+}
+// the launch being built gets its staging slot when it first needs one
+static int take_batch_slot(serl_rb* rb) {
+  if (!rb->bat_taken) RC(rb->bat.acquire());
+  rb->bat_taken = true;
+  return SERL_OK;
+}
+struct BatchSource {  // the arguments of serl_rb_insert_batch
+  const uint8_t* const* obs_frames;
+  const uint8_t* const* next_frames;
+  const float *state, *next_state, *action, *reward, *mask;
+  const uint8_t* done;
+};
+// fills the staging entry of write op `op` from its transition
+static int fill_entry(serl_rb* rb, const BatchOp& op, const BatchSource& in) {
+  RC(take_batch_slot(rb));
+  uint8_t* e = rb->bat.h() + (size_t)op.src * rb->entry_bytes;
+  const size_t tr = (size_t)op.tr, TS = (size_t)rb->T * rb->S;
+  pack_record(rb, reinterpret_cast<float*>(e), in.state + tr * TS, in.next_state + tr * TS, in.action + tr * rb->A, in.reward[tr],
+              in.mask[tr], in.done[tr] != 0);
+  const uint8_t* const* from = (op.kind == SlotOp::kObsFrame ? in.obs_frames : in.next_frames) + tr * rb->n_cam;
+  for (int c = 0; c < rb->n_cam; ++c)
+    std::memcpy(e + rb->rec_pad + (size_t)c * rb->frame_bytes, from[c] + (size_t)op.frame * rb->frame_bytes, rb->frame_bytes);
+  return SERL_OK;
+}
+// runs the launch built in rb->plan: ONE H2D copy of its entries and its op table (which lies behind the last entry used), ONE
+// kernel
+static int run_launch(serl_rb* rb) {
+  const BatchPlan& p = rb->plan;
+  RC(take_batch_slot(rb));  // (a launch of copies only has no entry)
+  const size_t table_at = (size_t)p.entries * rb->entry_bytes, table_bytes = sizeof(BatchOp) * p.ops.size();
+  std::memcpy(rb->bat.h() + table_at, p.ops.data(), table_bytes);
+  SERL_HIP(hipMemcpyAsync(rb->bat.d(), rb->bat.h(), table_at + table_bytes, hipMemcpyHostToDevice, rb->copy_stream));
+  ScatterArgs a{};
+  for (int c = 0; c < rb->n_cam; ++c) a.frames[c] = rb->frames[c];
+  a.rec = rb->rec;
+  a.entries = rb->bat.d();
+  a.ops = reinterpret_cast<const BatchOp*>(rb->bat.d() + table_at);
+  a.n_ops = (int)p.ops.size(); a.n_cam = rb->n_cam; a.rec_len = rb->rec_len;
+  a.fbytes = rb->frame_bytes; a.entry_bytes = rb->entry_bytes; a.rec_pad = rb->rec_pad;
+  a.parts = cdiv((long)(rb->frame_bytes / 16), 256 * kDirectVec);
+  const int64_t frame_blocks = (int64_t)a.n_ops * rb->n_cam * a.parts, rec_blocks = cdiv((long)a.n_ops * rb->rec_len, 256);
+  SERL_REQUIRE(frame_blocks + rec_blocks < (1LL << 31), "a launch of %d slot operations needs too many workgroups", a.n_ops);
+  a.n_frame_blocks = (int)frame_blocks;
+  hipLaunchKernelGGL(insert_scatter_kernel, dim3((unsigned)(frame_blocks + rec_blocks)), dim3(256), 0, rb->copy_stream, a);
+  SERL_HIP(hipGetLastError());
+  rb->bat_taken = false;
+  rb->stats[2] += 1;
+  rb->stats[3] += 1;
+  return rb->bat.mark(rb->copy_stream);
 }
 
 // lays `n` host sources out at 16-byte alignment in a slot of `ring` (a NULL source keeps its place and is not copied) and
@@ -579,6 +751,8 @@ int serl_rb_create(int device, int64_t capacity, int n_cam, int H, int W, int C,
   rb->H = H; rb->W = W; rb->C = C; rb->T = num_stack; rb->S = state_dim; rb->A = act_dim;
   rb->rec_len = 2 * num_stack * state_dim + act_dim + 3;
   rb->frame_bytes = (size_t)H * W * C;
+  rb->rec_pad = (sizeof(float) * rb->rec_len + 255) & ~(size_t)255;
+  rb->entry_bytes = rb->rec_pad + (size_t)n_cam * rb->frame_bytes;
   rb->ix.init(capacity, n_cam > 0, num_stack);
   for (int c = 0; c < n_cam; ++c) {
     hipError_t e = hipMalloc((void**)&rb->frames[c], (size_t)capacity * rb->frame_bytes);
@@ -592,7 +766,7 @@ int serl_rb_create(int device, int64_t capacity, int n_cam, int H, int W, int C,
   SERL_HIP(hipStreamCreateWithFlags(&rb->copy_stream, hipStreamNonBlocking));
   for (int k = 0; k < serl_rb::kGatherStreams; ++k) SERL_HIP(hipEventCreateWithFlags(&rb->gather_ev[k], hipEventDisableTiming));
   SERL_HIP(hipEventCreateWithFlags(&rb->last_insert, hipEventDisableTiming));
-  RC(rb->ins.init(kInsRing, ((sizeof(float) * rb->rec_len + 255) & ~(size_t)255) + (size_t)n_cam * rb->frame_bytes, false));
+  RC(rb->ins.init(kInsRing, rb->entry_bytes, false));
   RC(rb->stage.init(kRing, (size_t)(1 << 16) * std::min(num_stack, kMaxStack), true));  // idx (8B) + 2 crops (16B per frame) per sample: up to ~2700 samples
   *out = rb.release();
   return SERL_OK;
@@ -610,6 +784,7 @@ int serl_rb_destroy(serl_rb* rb) {
     if (rb->gather_ev[k]) (void)hipEventDestroy(rb->gather_ev[k]);
   if (rb->last_insert) (void)hipEventDestroy(rb->last_insert);
   rb->ins.destroy();
+  rb->bat.destroy();
   if (rb->xfer_host) (void)hipHostFree(rb->xfer_host);
   for (int k = 0; k < 2; ++k)
     if (rb->xfer_done[k]) (void)hipEventDestroy(rb->xfer_done[k]);
@@ -639,20 +814,14 @@ int serl_rb_rng_state(serl_rb* rb, uint64_t out[4], int* has_uint32, uint32_t* u
 int serl_rb_insert(serl_rb* rb, const uint8_t* const* obs_frames, const uint8_t* const* next_frames,
                    const float* state, const float* next_state, const float* action, float reward,
                    float mask, int done) {
-  SERL_REQUIRE(rb && state && next_state && action, "NULL argument");
-  SERL_REQUIRE(rb->n_cam == 0 || (obs_frames && next_frames), "NULL frames");
+  RC(check_insert_args(rb, 1, obs_frames, next_frames, state, next_state, action));
   std::unique_lock<std::mutex> g(rb->mu);
   rb->idle.wait(g, [rb] { return !rb->busy; });  // a snapshot export is reading the slots
   SERL_HIP(hipSetDevice(rb->device));
   RC(order_after_gathers(rb));  // never overwrite a slot an in-flight gather may still read
-  const int TS = rb->T * rb->S;
   std::vector<float> rec(rb->rec_len);
-  std::memcpy(rec.data(), state, sizeof(float) * TS);
-  std::memcpy(rec.data() + TS, next_state, sizeof(float) * TS);
-  std::memcpy(rec.data() + 2 * TS, action, sizeof(float) * rb->A);
-  rec[2 * TS + rb->A] = reward;
-  rec[2 * TS + rb->A + 1] = mask;
-  rec[2 * TS + rb->A + 2] = done ? 1.0f : 0.0f;
+  pack_record(rb, rec.data(), state, next_state, action, reward, mask, done != 0);
+  rb->stats[0] += 1;
   const uint8_t* fr[SERL_MAX_CAMS];
   for (const SlotOp& op : rb->ix.plan_insert(done != 0)) {
     if (op.kind == SlotOp::kCopy) {
@@ -664,6 +833,60 @@ int serl_rb_insert(serl_rb* rb, const uint8_t* const* obs_frames, const uint8_t*
     }
   }
   return finish_insert(rb);
+}
+
+// The transitions go in under the mutex in groups: a group is as many whole transitions as one staging slot is sure to hold
+// (a launch is also cut wherever replay_batch.h says so, inside a transition if need be, with the mutex kept).  Per group: wait
+// for a snapshot export to end, order the copy stream behind the gathers in flight, plan, fill the pinned slot, enqueue, record
+// last_insert.  The mutex is released between groups only, so every transition is wholly in a snapshot export or not in it, and
+// never across a stream synchronisation other than StageRing::acquire waiting for its own slot of two launches ago.
+int serl_rb_insert_batch(serl_rb* rb, int n, const uint8_t* const* obs_frames, const uint8_t* const* next_frames, const float* state,
+                         const float* next_state, const float* action, const float* reward, const float* mask, const uint8_t* done) {
+  SERL_REQUIRE(rb, "rb is NULL");
+  SERL_REQUIRE(n >= 0, "negative transition count %d", n);
+  if (n == 0) return SERL_OK;
+  RC(check_insert_args(rb, n, obs_frames, next_frames, state, next_state, action));
+  SERL_REQUIRE(reward && mask && done, "NULL argument");
+  const BatchSource in{obs_frames, next_frames, state, next_state, action, reward, mask, done};
+  std::unique_lock<std::mutex> g(rb->mu);
+  SERL_HIP(hipSetDevice(rb->device));
+  RC(batch_init(rb));
+  rb->plan.clear();  // (a call that failed half way may have left a launch behind)
+  rb->bat_taken = false;
+  rb->stats[1] += 1;
+  bool group_open = false;
+  for (int i = 0; i < n; ++i) {
+    if (!group_open) {
+      rb->idle.wait(g, [rb] { return !rb->busy; });  // a snapshot export is reading the slots
+      RC(order_after_gathers(rb));                    // never overwrite a slot an in-flight gather may still read
+      group_open = true;
+    }
+    for (const SlotOp& op : rb->ix.plan_insert(done[i] != 0)) {
+      RC(rb->plan.push(op, i, [rb] { return run_launch(rb); }));
+      if (op.kind != SlotOp::kCopy) RC(fill_entry(rb, rb->plan.ops.back(), in));
+    }
+    rb->stats[0] += 1;
+    if (i + 1 == n || !rb->plan.room_for_transition()) {
+      RC(run_launch(rb));
+      rb->plan.clear();
+      RC(finish_insert(rb));
+      if (i + 1 < n) {  // let the index draws and gathers that wait for the mutex in
+        g.unlock();
+        const auto give_up = std::chrono::steady_clock::now() + std::chrono::microseconds(kHandOverUs);
+        while (rb->readers.load(std::memory_order_relaxed) > 0 && std::chrono::steady_clock::now() < give_up) std::this_thread::yield();
+        g.lock();
+        group_open = false;
+      }
+    }
+  }
+  return SERL_OK;
+}
+
+int serl_rb_insert_stats(serl_rb* rb, int64_t out[4]) {
+  SERL_REQUIRE(rb && out, "NULL argument");
+  std::lock_guard<std::mutex> g(rb->mu);
+  std::memcpy(out, rb->stats, sizeof(rb->stats));
+  return SERL_OK;
 }
 
 int64_t serl_rb_len(serl_rb* rb) {
@@ -770,6 +993,7 @@ int serl_rb_import_slots(serl_rb* rb, int64_t slot_begin, int64_t n_slots, const
 int serl_rb_sample_indices(serl_rb* rb, int batch, int64_t* host_idx_out) {
   SERL_REQUIRE(rb && host_idx_out, "NULL argument");
   SERL_REQUIRE(batch >= 0, "negative batch");
+  Reader reader(rb);
   std::lock_guard<std::mutex> g(rb->mu);
   const IndexStatus st = rb->ix.sample(batch, host_idx_out);
   if (st == IndexStatus::kOk) return SERL_OK;
@@ -786,6 +1010,7 @@ int serl_rb_gather_packed(serl_rb* rb, int64_t* host_idx, int batch,
   SERL_REQUIRE(rb && host_idx && (dev_frames_out || rb->n_cam == 0), "NULL argument");
   SERL_REQUIRE(batch > 0, "batch must be positive");
   hipStream_t stream = (hipStream_t)stream_;
+  Reader reader(rb);
   std::lock_guard<std::mutex> g(rb->mu);
   SERL_HIP(hipSetDevice(rb->device));
   RC(check_and_revalidate(rb, host_idx, batch));
@@ -877,6 +1102,7 @@ int serl_rb_gather_crop(serl_rb* const* rbs, int n_rb, int64_t* const* host_idx,
   RC(check_crops(host_crop_obs, total * T));
   RC(check_crops(host_crop_next, total * T));
   // lock all buffers (fixed order) while we read bookkeeping and enqueue
+  Reader reader(rbs[0], n_rb == 2 && rbs[1] != rbs[0] ? rbs[1] : nullptr);
   std::unique_lock<std::mutex> l0(rbs[0]->mu, std::defer_lock), l1;
   if (n_rb == 2 && rbs[1] != rbs[0]) {
     l1 = std::unique_lock<std::mutex>(rbs[1]->mu, std::defer_lock);

@@ -15,6 +15,7 @@ from __future__ import annotations
 
 import collections
 import ctypes as C
+import itertools
 import threading
 from typing import Iterable, Optional
 
@@ -171,28 +172,64 @@ class MemoryEfficientReplayBufferDataStore(DataStoreBase):
         return out.astype(bool)
 
     # -- insert (memory_efficient_replay_buffer.py:53-89; thread-safe, data_store.py:104-106)
-    def insert(self, data):   # (the reference's data stores name the transition `data`, data_store.py:104)
-        data_dict = data
+    def _checked(self, data_dict):
+        """-> (observation frames per camera, next frames per camera, state, next state, action) of one transition as contiguous
+        arrays of the store's types, their shapes checked."""
         obs, nobs = data_dict["observations"], data_dict["next_observations"]
-        n = len(self.pixel_keys)
-        keep = []
-        obs_p, next_p = (C.c_void_p * n)(), (C.c_void_p * n)()
         T = self._num_stack
-        for i, k in enumerate(self.pixel_keys):
+        fo, fn = [], []
+        for k in self.pixel_keys:
             a = np.ascontiguousarray(obs[k], dtype=np.uint8)
             b = np.ascontiguousarray(nobs[k], dtype=np.uint8)
             assert a.shape == (T,) + tuple(self._img_shape), (k, a.shape)
             assert b.shape == a.shape, (k, b.shape)
-            keep += [a, b]
-            obs_p[i], next_p[i] = a.ctypes.data, b.ctypes.data
+            fo.append(a)
+            fn.append(b)
         st = np.ascontiguousarray(obs["state"], dtype=np.float32).reshape(-1)
         nst = np.ascontiguousarray(nobs["state"], dtype=np.float32).reshape(-1)
         act = np.ascontiguousarray(data_dict["actions"], dtype=np.float32).reshape(-1)
         assert st.size == T * self._S and nst.size == T * self._S and act.size == self._A
+        return fo, fn, st, nst, act
+
+    def insert(self, data):   # (the reference's data stores name the transition `data`, data_store.py:104)
+        fo, fn, st, nst, act = self._checked(data)
+        n = len(self.pixel_keys)
+        obs_p = (C.c_void_p * n)(*[a.ctypes.data for a in fo]) if n else None
+        next_p = (C.c_void_p * n)(*[b.ctypes.data for b in fn]) if n else None
         with self._lock:
             _lib.check(_lib.lib().serl_rb_insert(
                 self._h, obs_p, next_p, st.ctypes.data, nst.ctypes.data, act.ctypes.data,
-                float(data_dict["rewards"]), float(data_dict["masks"]), int(bool(data_dict["dones"]))))
+                float(data["rewards"]), float(data["masks"]), int(bool(data["dones"]))))
+
+    def batch_insert(self, batch_data):
+        """insert() of every transition of `batch_data`, in order, as ONE library call (serl_rb_insert_batch: one host-to-device
+        copy and one kernel launch per 2 MB of slot writes instead of n_cam + 1 copies per slot write) -- what TrainerServer does
+        with an actor's message.  Every transition is checked before the first is inserted."""
+        batch = list(batch_data)
+        if len(batch) <= 1:
+            for d in batch:
+                self.insert(d)
+            return
+        checked = [self._checked(d) for d in batch]
+        n, n_cam = len(batch), len(self.pixel_keys)
+        obs_p = next_p = None
+        if n_cam:   # pointer tables straight from each transition's arrays (`checked` keeps them alive): entry i * n_cam + c
+            obs_p = (C.c_void_p * (n * n_cam))(*[a.ctypes.data for c in checked for a in c[0]])
+            next_p = (C.c_void_p * (n * n_cam))(*[b.ctypes.data for c in checked for b in c[1]])
+        st, nst, act = (np.stack([c[j] for c in checked]) for j in (2, 3, 4))
+        rew = np.array([float(d["rewards"]) for d in batch], np.float32)
+        msk = np.array([float(d["masks"]) for d in batch], np.float32)
+        done = np.array([bool(d["dones"]) for d in batch], np.uint8)
+        with self._lock:
+            _lib.check(_lib.lib().serl_rb_insert_batch(self._h, n, obs_p, next_p, st.ctypes.data, nst.ctypes.data, act.ctypes.data,
+                                                       rew.ctypes.data, msk.ctypes.data, done.ctypes.data))
+
+    def insert_stats(self) -> dict:
+        """What the inserts into this store have cost so far (serl_rb_insert_stats): transitions inserted, batch_insert library
+        calls, host-to-device copies and kernel launches enqueued."""
+        out = (C.c_int64 * 4)()
+        _lib.check(_lib.lib().serl_rb_insert_stats(self._h, out))
+        return dict(zip(("transitions", "batch_calls", "h2d_copies", "launches"), (int(v) for v in out)))
 
     # -- index draw (memory_efficient_replay_buffer.py:111-122)
     def sample_indices(self, batch_size: int) -> np.ndarray:
@@ -383,16 +420,14 @@ class ReplayBufferDataStore(MemoryEfficientReplayBufferDataStore):
         self._seed = None
         self._lock = threading.Lock()   # insert() against the device -> host phase of save_snapshot()
 
-    def insert(self, data):  # replay_buffer.py:71-75 under the data store's lock (data_store.py:44-46)
-        data_dict = data
+    # insert (replay_buffer.py:71-75 under the data store's lock, data_store.py:44-46), batch_insert and insert_stats are the
+    # parent's: a transition of this store has no frames
+    def _checked(self, data_dict):
         st = np.ascontiguousarray(data_dict["observations"], dtype=np.float32).reshape(-1)
         nst = np.ascontiguousarray(data_dict["next_observations"], dtype=np.float32).reshape(-1)
         act = np.ascontiguousarray(data_dict["actions"], dtype=np.float32).reshape(-1)
         assert st.size == self._S and nst.size == self._S and act.size == self._A
-        with self._lock:
-            _lib.check(_lib.lib().serl_rb_insert(
-                self._h, None, None, st.ctypes.data, nst.ctypes.data, act.ctypes.data,
-                float(data_dict["rewards"]), float(data_dict["masks"]), int(bool(data_dict["dones"]))))
+        return [], [], st, nst, act
 
     def gather(self, indx: np.ndarray, stream=None):
         indx = np.ascontiguousarray(indx, dtype=np.int64)
@@ -451,11 +486,24 @@ def _demo_transitions(demos_path):
             yield transition
 
 
+def _insert_in_chunks(data_store, transitions, chunk=256):
+    """The transitions go into `data_store` in order: through batch_insert, `chunk` at a time, if the store has one."""
+    if not hasattr(data_store, "batch_insert"):
+        for transition in transitions:
+            data_store.insert(transition)
+        return
+    it = iter(transitions)
+    while True:
+        part = list(itertools.islice(it, chunk))
+        if not part:
+            return
+        data_store.batch_insert(part)
+
+
 def populate_data_store(data_store, demos_path):
     """data_store.py:147-163: insert every transition of the demonstration pickles into `data_store` (any object with
     insert() and __len__: the HBM stores above or a QueuedDataStore) and return it."""
-    for transition in _demo_transitions(demos_path):
-        data_store.insert(transition)
+    _insert_in_chunks(data_store, _demo_transitions(demos_path))
     print(f"Loaded {len(data_store)} transitions.")
     return data_store
 
@@ -470,11 +518,13 @@ def _z_axis_only(state: np.ndarray) -> np.ndarray:
 def populate_data_store_with_z_axis_only(data_store, demos_path):
     """data_store.py:166-196: as populate_data_store, with the x / y coordinates removed from both observations' state
     (the caller's transitions are not modified)."""
-    for transition in _demo_transitions(demos_path):
-        t = dict(transition)
-        for side in ("observations", "next_observations"):
-            t[side] = dict(transition[side])
-            t[side]["state"] = _z_axis_only(transition[side]["state"])
-        data_store.insert(t)
+    def z_only():
+        for transition in _demo_transitions(demos_path):
+            t = dict(transition)
+            for side in ("observations", "next_observations"):
+                t[side] = dict(transition[side])
+                t[side]["state"] = _z_axis_only(transition[side]["state"])
+            yield t
+    _insert_in_chunks(data_store, z_only())
     print(f"Loaded {len(data_store)} transitions.")
     return data_store

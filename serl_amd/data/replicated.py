@@ -153,9 +153,13 @@ class ReplicatedDataStore:
             self._applied = pos + 1
             for k_, i_, _ in todo:
                 self._done[k_] = max(self._done[k_], i_)
-        for _, _, trs in todo:
-            for tr in trs:
-                self._store.insert(tr)
+        batch_insert = getattr(self._store, "batch_insert", None)
+        for _, _, trs in todo:   # a batch boundary's transitions stay together and in order
+            if batch_insert is not None and trs:
+                batch_insert(trs)
+            else:
+                for tr in trs:
+                    self._store.insert(tr)
         # applied messages are dropped so the inbox does not grow with the run
         with self._cv:
             drop = self._applied
