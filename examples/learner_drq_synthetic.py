@@ -24,6 +24,7 @@ import time
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from serl_amd.agents.drq import DrQAgent  # noqa: E402
 from serl_amd.transport import QueuedDataStore, TrainerClient, TrainerServer, make_trainer_config  # noqa: E402
 from serl_amd.utils.checkpoint import restore_run, save_checkpoint, save_run  # noqa: E402
 from serl_amd.utils.launcher import make_drq_agent, make_replay_buffer  # noqa: E402
@@ -58,14 +59,26 @@ def main():
     ap.add_argument("--run_dir", default=None, help="directory of the run state (save_run / restore_run)")
     ap.add_argument("--save_every", type=int, default=0, help="save the run state every N steps (needs --run_dir)")
     ap.add_argument("--resume", action="store_true", help="continue from the latest run state in --run_dir")
+    ap.add_argument("--hidden", type=int, default=256,
+                    help="width h of the critic's and the policy's MLPs (hidden_dims=[h, h]): a multiple of 64 in [64, 1024]")
     a = ap.parse_args()
     assert a.run_dir or not (a.save_every or a.resume), "--save_every / --resume need --run_dir"
 
     env = _Env()
-    agent = make_drq_agent(seed=42, sample_obs={"front": np.zeros((1, H, W, 3), np.uint8), "wrist": np.zeros((1, H, W, 3), np.uint8),
-                                                "state": np.zeros((1, S), np.float32)},
-                           sample_action=np.zeros((A,), np.float32), image_keys=KEYS, encoder_type="resnet-pretrained",
-                           batch_size=a.batch_size)
+    sample_obs = {"front": np.zeros((1, H, W, 3), np.uint8), "wrist": np.zeros((1, H, W, 3), np.uint8),
+                  "state": np.zeros((1, S), np.float32)}
+    if a.hidden == 256:
+        agent = make_drq_agent(seed=42, sample_obs=sample_obs, sample_action=np.zeros((A,), np.float32), image_keys=KEYS,
+                               encoder_type="resnet-pretrained", batch_size=a.batch_size)
+    else:
+        # make_drq_agent has no width argument (launcher.py:79-116 writes hidden_dims into the call): another width goes to
+        # create_drq as it does in the reference, with the launcher's other hyper-parameters
+        mlp = {"activations": "tanh", "use_layer_norm": True, "hidden_dims": [a.hidden, a.hidden]}
+        agent = DrQAgent.create_drq(
+            42, sample_obs, np.zeros((A,), np.float32), encoder_type="resnet-pretrained", use_proprio=True, image_keys=KEYS,
+            policy_kwargs={"tanh_squash_distribution": True, "std_parameterization": "exp", "std_min": 1e-5, "std_max": 5},
+            critic_network_kwargs=mlp, policy_network_kwargs=dict(mlp), temperature_init=1e-2, discount=0.96,
+            backup_entropy=False, critic_ensemble_size=10, critic_subsample_size=2, batch_size=a.batch_size)
     replay_buffer = make_replay_buffer(env, capacity=200000, type="memory_efficient_replay_buffer", image_keys=KEYS)
     demo_buffer = make_replay_buffer(env, capacity=10000, type="memory_efficient_replay_buffer", image_keys=KEYS)
     stores, update_steps = {"replay": replay_buffer, "demo": demo_buffer}, 0

@@ -216,8 +216,9 @@ typedef struct serl_agent_cfg {
   int state_dim, act_dim;
   int batch;               /* max samples per update call on THIS rank */
   int ensemble;            /* critic_ensemble_size (10) */
-  int hidden;              /* MLP width (256) */
-  int bottleneck;          /* encoder bottleneck_dim (256) */
+  int hidden;              /* width of the critic's and the policy's two MLP layers, hidden_dims = [hidden, hidden]: a multiple of
+                              64 in [64, 1024] (256 in the launcher's configurations); anything else is SERL_ERR_INVALID */
+  int bottleneck;          /* encoder bottleneck_dim: 256 (create_drq fixes it), anything else is SERL_ERR_INVALID */
   int sle_features;        /* num_spatial_blocks (8) */
   int proprio_dim;         /* proprio_latent_dim (64) */
   int warmup_steps;        /* optimizers.py:23-30: actor and critic optimizers (0 for DrQ, 2000 for make_sac_agent) */

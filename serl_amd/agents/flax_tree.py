@@ -254,8 +254,8 @@ def export_tree(core, section: str, image_keys, duplicate_encoder_under_critic: 
     """Nested dict of np.float32 arrays in flax layout (HWIO convs, (in,out) dense, ensemble axis 0)."""
     cfg = core.cfg
     etype = "small" if cfg.encoder_type == 1 else "resnet-pretrained"
-    shapes = theta_shapes(cfg.n_cam, cfg.H, cfg.W, cfg.state_dim, cfg.act_dim, ensemble=cfg.ensemble, encoder_type=etype,
-                          num_stack=max(cfg.num_stack, 1))
+    shapes = theta_shapes(cfg.n_cam, cfg.H, cfg.W, cfg.state_dim, cfg.act_dim, ensemble=cfg.ensemble, hidden=cfg.hidden,
+                          encoder_type=etype, num_stack=max(cfg.num_stack, 1))
     shapes.update(trunk_shapes())
     paths = theta_paths(image_keys, critic_mlp_name, etype)
     if cfg.n_cam and etype != "small":

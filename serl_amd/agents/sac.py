@@ -35,14 +35,13 @@ class SACAgent(DrQAgent):
                       temperature_optimizer_kwargs: dict = None, batch_size: int = 256, device: int = 0, param_init: str = "numpy",
                       **kwargs):
         """sac.py:486-542 -> create (:323-400).  Built natively: the configuration of utils/launcher.py:50-76
-        (REDQ subsample 2, tanh-squashed exp-parameterised policy, LayerNorm+tanh 256x256 MLPs).
+        (REDQ subsample 2, tanh-squashed exp-parameterised policy, LayerNorm+tanh 256x256 MLPs); hidden_dims=[h, h] in both
+        network kwargs selects another width h, a multiple of 64 in [64, 1024].
         param_init: "numpy" (default) or "reference" (the reference's own initialisers and keys, utils/init_ref.py)."""
         pk = policy_kwargs or {}
         if pk.get("std_parameterization", "exp") != "exp" or not pk.get("tanh_squash_distribution", True):
             raise NotImplementedError("policy must be tanh-squashed with std_parameterization='exp'")
-        for nk in (critic_network_kwargs or {}, policy_network_kwargs or {}):
-            if list(nk.get("hidden_dims", [256, 256])) != [256, 256] or not nk.get("use_layer_norm", True):
-                raise NotImplementedError("MLPs must be [256,256] with LayerNorm")
+        hidden = pinit.mlp_hidden_width(critic_network_kwargs, policy_network_kwargs)
         ao = {"learning_rate": 3e-4, "warmup_steps": 2000, **(actor_optimizer_kwargs or {})}     # sac.py:333-336
         co = {"learning_rate": 3e-4, "warmup_steps": 2000, **(critic_optimizer_kwargs or {})}    # sac.py:337-340
         to = {"learning_rate": 3e-4, **(temperature_optimizer_kwargs or {})}                     # sac.py:341-343
@@ -57,12 +56,13 @@ class SACAgent(DrQAgent):
                          temp_warmup_steps=int(to.get("warmup_steps", 0)), std_min=pk.get("std_min", 1e-5),
                          std_max=pk.get("std_max", 10.0), target_entropy=target_entropy, seed=seed,
                          optimizers={"actor": ao, "critic": co, "temperature": {"warmup_steps": 0, **to}},
-                         critic_subsample_size=critic_subsample_size, backup_entropy=backup_entropy)
+                         critic_subsample_size=critic_subsample_size, backup_entropy=backup_entropy, hidden=hidden)
         if init_ref.check_param_init(param_init):
             theta = init_ref.theta_reference((), 0, 0, S, A, rng, ensemble=critic_ensemble_size, temperature_init=temperature_init,
-                                             device=device)
+                                             device=device, hidden=hidden)
         else:
-            theta = pinit.init_theta(0, 0, 0, S, A, seed=seed, temperature_init=temperature_init, ensemble=critic_ensemble_size)
+            theta = pinit.init_theta(0, 0, 0, S, A, seed=seed, temperature_init=temperature_init, ensemble=critic_ensemble_size,
+                                     hidden=hidden)
         for sec in ("params", "target_params"):
             core.load_flat(sec, theta)
         config = dict(critic_ensemble_size=critic_ensemble_size, critic_subsample_size=critic_subsample_size,

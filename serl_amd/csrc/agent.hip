@@ -34,14 +34,14 @@ struct Offs {
 
 struct EncBuf {     // activations of one EncodingWrapper forward
   float* f;         // [n_cam][B][D] SLE output (after dropout)
-  float* xhat;      // [n_cam*B][256]
+  float* xhat;      // [n_cam*B][bottleneck]
   float* rstd;      // [n_cam*B]
-  float* pxhat;     // [B][64]
+  float* pxhat;     // [B][proprio_dim]
   float* prstd;     // [B]
   float* enc;       // [B][ld] output slice base
   long ld;
 };
-struct MlpBuf {  // 2-layer LN/tanh MLP activations (ensemble: rows = E*B)
+struct MlpBuf {  // 2-layer LN/tanh MLP activations, [rows][hidden] and [rows] (ensemble: rows = E*B)
   float *h1, *xh1, *rs1, *h2, *xh2, *rs2;
 };
 struct CritBuf {
@@ -289,7 +289,10 @@ size_t carve(serl_agent* a, void* base) {
     mlp(pbuf->m, B);
     pbuf->pre = b.take<float>(2 * B * A); pbuf->std = b.take<float>(B * A); pbuf->logp = b.take<float>(B);
   }
-  // (fused epilogues keep whole 64x64 slab tiles: rows and columns padded to 64)
+  // (fused epilogues keep whole 64x64 slab tiles: rows and columns padded to 64).  The terms, in order: the camera heads' K-split
+  // (32 slices), the critic's input gradient summed over members, a policy layer (K-split <= 8), a critic layer (K-split <= 4 per
+  // member) and the shared head's gradient (K-split 8, 64 padded rows); every user checks its own need against slabs_cap with the
+  // numbers in the message (hidden = 1024 x 16 members x 65 rows: tests/test_mlp_widths_gpu.py)
   const long Bp = pad64(B);
   long cap = std::max<long>({(long)c.n_cam * 32 * Bp * c.bottleneck, N * Bp * pad64(a->XA), 8 * Bp * Hd, 4 * N * Bp * Hd, 16L * 64 * Hd});
   a->slabs_cap = cap;
@@ -442,6 +445,9 @@ int dense_ln_tanh_multi(serl_agent* a, const DenseJob* jobs, int n, int groups, 
   const int Hd = a->cfg.hidden;
   SERL_REQUIRE(n >= 1 && n <= 3, "bad dense instance count");
   splitk = split_for(a->split_budget, rows_per_group, Hd, groups * n, splitk);
+  SERL_REQUIRE((long)groups * splitk * rows_per_group * Hd <= a->slabs_cap,
+               "Dense layer: %d groups x %d K-splits x %d rows x width %d exceeds the slab scratch of %ld floats", groups, splitk,
+               rows_per_group, Hd, a->slabs_cap);
   GemmDesc gd[3];
   LnFwdArgs lv[3];
   for (int i = 0; i < n; ++i) {
@@ -620,7 +626,9 @@ int igrad_sum(serl_agent* a, const float* dY, long ldy, long dy_gstride, const f
   const long ldc = pad64(Kin);
   GemmDesc g = gemm_igrad(dY, ldy, dy_gstride, W, ldw, w_gstride, a->slabs, ldc, pad64(rows) * ldc, groups, rows, Kin, Nout);
   g.epi = kEpiReduce; g.zred = groups; g.ctr = a->ctr; g.out = out; g.ld_out = ldo; g.out_gstride = 0;
-  SERL_REQUIRE((long)cdiv(rows, 64) * cdiv(Kin, 64) <= kCtrPerLane && groups * g.sCz <= a->slabs_cap, "input gradient exceeds the fused epilogue's scratch");
+  SERL_REQUIRE((long)cdiv(rows, 64) * cdiv(Kin, 64) <= kCtrPerLane && groups * g.sCz <= a->slabs_cap,
+               "input gradient: %d groups x %d rows x %d columns exceeds the fused epilogue's slab scratch of %ld floats, or its tiles the %d "
+               "arrival counters", groups, rows, Kin, a->slabs_cap, kCtrPerLane);
   return gemm_f32(g, st);
 }
 
@@ -643,7 +651,9 @@ int head_kernel_grad(serl_agent* a, CritBuf& cb, int cnt, hipStream_t st) {
   if (split > 1) {
     g.sCz = 64L * Hd;
     g.epi = kEpiReduce; g.zred = split; g.ctr = a->ctr; g.out = out; g.ld_out = Hd; g.out_gstride = Hd;
-    SERL_REQUIRE((long)groups * split * g.sCz <= a->slabs_cap && groups * cdiv(Hd, 64) <= kCtrPerLane, "head gradient exceeds the scratch");
+    SERL_REQUIRE((long)groups * split * g.sCz <= a->slabs_cap && groups * cdiv(Hd, 64) <= kCtrPerLane,
+                 "head gradient: %d groups x %d K-splits x 64 rows x width %d exceeds the slab scratch of %ld floats, or its %d tiles the %d "
+                 "arrival counters", groups, split, Hd, a->slabs_cap, groups * cdiv(Hd, 64), kCtrPerLane);
   }
   SERL_REQUIRE(a->pg_defer && a->pg_nwg < kMaxGemmGroups, "no room for the deferred head-gradient GEMM");
   a->pg_wg[a->pg_nwg++] = g;
@@ -865,7 +875,10 @@ int serl_agent_create(const serl_agent_cfg* cfg, serl_agent** out) {
   SERL_REQUIRE(cfg->encoder_type == SERL_ENCODER_RESNET_PRETRAINED || cfg->encoder_type == SERL_ENCODER_SMALL,
                "Unknown encoder type: %d", cfg->encoder_type);
   SERL_REQUIRE(cfg->n_cam > 0 || cfg->ensemble <= 16, "state-only SAC supports ensembles of at most 16");
-  SERL_REQUIRE(cfg->hidden == 256 && cfg->bottleneck == 256, "hidden/bottleneck must be 256 (got %d/%d)", cfg->hidden, cfg->bottleneck);
+  // one wave owns a LayerNorm row and a lane holds hidden / 64 of its columns, 16 at the most (heads.hip)
+  SERL_REQUIRE(cfg->hidden >= 64 && cfg->hidden <= 1024 && cfg->hidden % 64 == 0,
+               "hidden must be a multiple of 64 in [64, 1024] (got %d): the width of the critic's and the policy's two MLP layers", cfg->hidden);
+  SERL_REQUIRE(cfg->bottleneck == 256, "bottleneck must be 256 (got %d): the reference fixes bottleneck_dim=256 in create_drq", cfg->bottleneck);
   SERL_REQUIRE(cfg->proprio_dim == 64, "proprio_dim must be 64");
   SERL_REQUIRE(cfg->sle_features == 8, "sle_features must be 8");
   SERL_REQUIRE(cfg->batch >= 1 && cfg->ensemble >= 2 && cfg->state_dim >= 1 && cfg->act_dim >= 1 && cfg->act_dim <= 64, "bad dims");

@@ -248,6 +248,62 @@ __device__ __forceinline__ float ln_tanh_row256(const LnFwdArgs& a, int row, int
   return d;
 }
 
+// The same row at ANY width D = 64 * VPL (the MLPs' hidden width, serl_agent_cfg.hidden: 64 .. 1024): one wave still owns the
+// row, a lane holds VPL of its columns.  Lane-to-column layout: STRIDED -- lane l holds columns l, l + 64, ..., l + 64 (VPL - 1).
+// Every load / store instruction of the wave then covers 64 consecutive floats (256 bytes, two whole cache lines) whatever VPL
+// is; the blocked layout of the 256 form (lane l holds columns 4 l .. 4 l + 3 as one 16-byte access) has no counterpart at
+// VPL = 3 or 5, where a lane's block is 12 or 20 bytes and a 4-byte access per column would stride the wave over the row.
+// Same arithmetic as the 256 form: bias, then the slabs in index order; fast variance; a lane sums its columns in ascending
+// order, then the xor butterfly.  Widths 64 and 256 keep their own kernels (ln_tanh_fwd_kernel<1|4>) and never come here.
+// LIVE as in the 256 form (sc1 loads of slabs written inside this launch); like there, no launch instantiates it today.
+// (Multiples of 256 could take 16-byte accesses in a blocked-by-256 layout; one layout serves every width until a width other
+// than 256 has a speed target.)
+template <int VPL, bool LIVE>
+__device__ __forceinline__ float ln_tanh_row(const LnFwdArgs& a, int row, int lane) {
+  constexpr int D = 64 * VPL;
+  const int grp = row / a.rows_per_group;
+  const long lrow = row - grp * a.rows_per_group;
+  const long base = (long)grp * a.S * a.slab_stride + lrow * D + lane;
+  const long pb = (long)grp * a.pstride + lane;
+  const __amdgpu_buffer_rsrc_t rs = rsrc_of(a.slabs);
+  float v[VPL];
+#pragma unroll
+  for (int j = 0; j < VPL; ++j) v[j] = a.bias ? a.bias[pb + 64 * j] : 0.f;
+#pragma unroll 2
+  for (int s = 0; s < a.S; ++s) {   // 2 VPL independent reads in flight, added in index order
+    const long o = base + (long)s * a.slab_stride;
+#pragma unroll
+    for (int j = 0; j < VPL; ++j) v[j] += LIVE ? ld1_sc1(rs, o + 64 * j) : a.slabs[o + 64 * j];
+  }
+  float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+  for (int j = 0; j < VPL; ++j) { s1 += v[j]; s2 += v[j] * v[j]; }
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) { s1 += __shfl_xor(s1, off); s2 += __shfl_xor(s2, off); }
+  const float mean = s1 * (1.0f / D), mean2 = s2 * (1.0f / D);
+  const float var = fmaxf(mean2 - mean * mean, 0.f);
+  const float rstd = rsqrtf(var + 1e-6f);
+  float d = 0.f;
+#pragma unroll
+  for (int j = 0; j < VPL; ++j) {
+    const int col = lane + 64 * j;
+    const float xh = (v[j] - mean) * rstd;
+    const float pre = xh * a.gamma[pb + 64 * j] + a.beta[pb + 64 * j];
+    const float y = a.relu ? fmaxf(pre, 0.f) : tanhf(pre);
+    a.y[lrow * a.ld_y + (long)grp * a.y_goff + col] = y;
+    if (a.xhat) a.xhat[(long)row * D + col] = xh;
+    if (a.dot_out) d += y * a.dot_w[(long)grp * a.dot_gstride + col];
+  }
+  if (a.rstd && lane == 0) a.rstd[row] = rstd;
+  if (a.dot_out) {
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) d += __shfl_xor(d, off);
+    d += a.dot_b[(long)grp * a.dot_b_gstride];
+    if (lane == 0) a.dot_out[row] = d;
+  }
+  return d;
+}
+
 // tanh-Gaussian head of rows [r0, r1) from the head GEMM's slabs (actor_critic_nets.py:179-272): one thread per (row, action)
 template <bool LIVE>
 __device__ __forceinline__ void policy_dist_rows(const PolicyDistArgs& v, int r0, int r1, int tid, int nthreads) {
@@ -897,15 +953,40 @@ int label_rows(const LnFwdArgs& a, float* label, float* mean, int* ctr, hipStrea
   return SERL_OK;
 }
 
+// the width-generic row (ln_tanh_row: strided columns) with the grid of ln_tanh_fwd_kernel: four rows per workgroup
+template <int VPL>
+__global__ __launch_bounds__(256) void ln_tanh_fwd_wide_kernel(Multi<LnFwdArgs> mv) {
+  const LnFwdArgs& a = mv.v[blockIdx.y];
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (row >= a.rows) return;
+  ln_tanh_row<VPL, false>(a, row, lane);
+}
+
+// The widths the LayerNorm rows serve: one wave per row, D / 64 columns per lane, at most 16.  64 and 256 have kernels of their
+// own (the encoder's proprio and bottleneck LayerNorms, and the MLPs at the default width); every other width takes
+// K<D / 64> of the width-generic family K.
+#define SERL_LN_WIDTH_OK(D) ((D) >= 64 && (D) <= 1024 && (D) % 64 == 0)
+#define SERL_LN_WIDE_CASE(K, V, ...) case V: SERL_LAUNCH_CHAIN(K<V>, __VA_ARGS__); break;
+#define SERL_LN_WIDE_LAUNCH(K, D, ...)                                                                                   \
+  switch ((D) / 64) {                                                                                                     \
+    SERL_LN_WIDE_CASE(K, 2, __VA_ARGS__) SERL_LN_WIDE_CASE(K, 3, __VA_ARGS__) SERL_LN_WIDE_CASE(K, 5, __VA_ARGS__)       \
+    SERL_LN_WIDE_CASE(K, 6, __VA_ARGS__) SERL_LN_WIDE_CASE(K, 7, __VA_ARGS__) SERL_LN_WIDE_CASE(K, 8, __VA_ARGS__)       \
+    SERL_LN_WIDE_CASE(K, 9, __VA_ARGS__) SERL_LN_WIDE_CASE(K, 10, __VA_ARGS__) SERL_LN_WIDE_CASE(K, 11, __VA_ARGS__)     \
+    SERL_LN_WIDE_CASE(K, 12, __VA_ARGS__) SERL_LN_WIDE_CASE(K, 13, __VA_ARGS__) SERL_LN_WIDE_CASE(K, 14, __VA_ARGS__)    \
+    SERL_LN_WIDE_CASE(K, 15, __VA_ARGS__) SERL_LN_WIDE_CASE(K, 16, __VA_ARGS__)                                          \
+    default: serl::set_error("LayerNorm width %d has no width-generic kernel", (int)(D)); return SERL_ERR_INVALID;       \
+  }
+
 int ln_tanh_fwd_multi(const LnFwdArgs* as, int n, int D, hipStream_t stream) {
-  SERL_REQUIRE(D == 256 || D == 64, "LayerNorm width %d unsupported (64 or 256)", D);
+  SERL_REQUIRE(SERL_LN_WIDTH_OK(D), "LayerNorm width %d unsupported (a multiple of 64 in [64, 1024])", D);
   SERL_REQUIRE(n >= 1 && n <= kMaxMulti, "bad instance count %d", n);
   Multi<LnFwdArgs> mv{};
   int rows = 0;
   for (int i = 0; i < n; ++i) { mv.v[i] = as[i]; rows = std::max(rows, as[i].rows); }
   dim3 grid(cdiv(rows, 4), n);
   if (D == 256) SERL_LAUNCH_CHAIN(ln_tanh_fwd_kernel<4>, grid, dim3(256), 0, stream, mv);
-  else SERL_LAUNCH_CHAIN(ln_tanh_fwd_kernel<1>, grid, dim3(256), 0, stream, mv);
+  else if (D == 64) SERL_LAUNCH_CHAIN(ln_tanh_fwd_kernel<1>, grid, dim3(256), 0, stream, mv);
+  else SERL_LN_WIDE_LAUNCH(ln_tanh_fwd_wide_kernel, D, grid, dim3(256), 0, stream, mv)
   SERL_HIP(hipGetLastError());
   return SERL_OK;
 }
@@ -945,7 +1026,12 @@ __global__ __launch_bounds__(256) void ln_tanh_bwd_kernel(LnBwdArgs a) {
 }
 
 int ln_tanh_bwd(const LnBwdArgs& a, int D, hipStream_t stream) {
-  SERL_REQUIRE(D == 256 || D == 64, "LayerNorm width %d unsupported (64 or 256)", D);
+  SERL_REQUIRE(SERL_LN_WIDTH_OK(D), "LayerNorm width %d unsupported (a multiple of 64 in [64, 1024])", D);
+  if (D != 256 && D != 64) {   // the width-generic rows: one instance of ln_tanh_bwd_multi's launch, no rider
+    LnBwdArgs w = a;
+    w.D = D; w.dq_inline = 0;
+    return ln_tanh_bwd_multi(&w, 1, LossArgs{}, stream);
+  }
   dim3 grid(cdiv(a.rows, 4));
   if (D == 256) SERL_LAUNCH_CHAIN(ln_tanh_bwd_kernel<4>, grid, dim3(256), 0, stream, a);
   else SERL_LAUNCH_CHAIN(ln_tanh_bwd_kernel<1>, grid, dim3(256), 0, stream, a);
@@ -1064,18 +1150,71 @@ __global__ __launch_bounds__(256) void ln_tanh_bwd_multi_kernel(Multi<LnBwdArgs>
   else ln_tanh_bwd_row<1>(a, loss, row, lane);
 }
 
+// ln_tanh_bwd_row at any width D = 64 * VPL, with the strided lane-to-column layout of ln_tanh_row (lane l holds columns
+// l + 64 j: 256 consecutive bytes per wave access at every width); a lane sums its columns in ascending order
+template <int VPL>
+__device__ __forceinline__ void ln_tanh_bwd_row_wide(const LnBwdArgs& a, const LossArgs& L, int row, int lane) {
+  const int grp = row / a.rows_per_group;
+  constexpr int D = VPL * 64;
+  float dg[VPL], dxh[VPL], xh[VPL];
+  float s1 = 0.f, s2 = 0.f;
+  const long lr = row - grp * a.rows_per_group;
+  float dqr = 0.f;
+  if (a.dq_w) dqr = a.dq_inline ? 2.f * (L.q[row] - redq_target(L, (int)lr)) * L.inv_norm : (a.dq ? a.dq[row] : a.dq_const);
+#pragma unroll
+  for (int j = 0; j < VPL; ++j) {
+    const int col = lane + 64 * j;
+    const float y = a.y[lr * a.ld_y + (long)grp * a.y_goff + col];
+    const float dy = a.dq_w ? dqr * a.dq_w[(long)grp * a.dq_w_gstride + col] : a.dy[lr * a.ld_dy + (long)grp * a.dy_goff + col];
+    dg[j] = dy * (1.f - y * y);
+    xh[j] = a.xhat[(long)row * D + col];
+    dxh[j] = dg[j] * a.gamma[(long)grp * a.pstride + col];
+    s1 += dxh[j];
+    s2 += dxh[j] * xh[j];
+  }
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) { s1 += __shfl_xor(s1, off); s2 += __shfl_xor(s2, off); }
+  const float m1 = s1 * (1.0f / D), m2 = s2 * (1.0f / D), rstd = a.rstd[row];
+#pragma unroll
+  for (int j = 0; j < VPL; ++j) {
+    const int col = lane + 64 * j;
+    a.dx[(long)row * D + col] = rstd * (dxh[j] - m1 - xh[j] * m2);
+    a.dg[(long)row * D + col] = dg[j];
+  }
+}
+
+// ln_tanh_bwd_multi_kernel for instances that all have the width 64 * VPL (the MLP layers at a hidden width other than 256)
+template <int VPL>
+__global__ __launch_bounds__(256) void ln_tanh_bwd_multi_wide_kernel(Multi<LnBwdArgs> mv, LossArgs loss) {
+  __shared__ float red[4][256];
+  if (loss.on && blockIdx.y == 0 && blockIdx.x == gridDim.x - 1) { critic_loss_body(loss, red); return; }
+  const LnBwdArgs& a = mv.v[blockIdx.y];
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (row >= a.rows) return;
+  ln_tanh_bwd_row_wide<VPL>(a, loss, row, lane);
+}
+
 int ln_tanh_bwd_multi(const LnBwdArgs* as, int n, const LossArgs& loss, hipStream_t stream) {
   SERL_REQUIRE(n >= 1 && n <= kMaxMulti, "bad instance count %d", n);
   Multi<LnBwdArgs> mv{};
   int rows = 0;
+  bool wide = false;
   for (int i = 0; i < n; ++i) {
-    SERL_REQUIRE(as[i].D == 256 || as[i].D == 64, "LayerNorm width %d unsupported (64 or 256)", as[i].D);
+    SERL_REQUIRE(SERL_LN_WIDTH_OK(as[i].D), "LayerNorm width %d unsupported (a multiple of 64 in [64, 1024])", as[i].D);
     SERL_REQUIRE(!as[i].dq_inline || (loss.on && as[i].dq_w && as[i].rows == loss.E * loss.B && as[i].rows_per_group == loss.B),
                  "inline dQ needs the loss arguments of the launch");
     mv.v[i] = as[i];
     rows = std::max(rows, as[i].rows);
+    wide = wide || (as[i].D != 256 && as[i].D != 64);
   }
-  SERL_LAUNCH_CHAIN(ln_tanh_bwd_multi_kernel, dim3(cdiv(rows, 4) + (loss.on ? 1 : 0), n), dim3(256), 0, stream, mv, loss);
+  const dim3 grid(cdiv(rows, 4) + (loss.on ? 1 : 0), n);
+  if (wide) {   // (64 and 256 may share a launch -- the encoder heads; any other width comes from one MLP layer and is alone)
+    for (int i = 1; i < n; ++i)
+      SERL_REQUIRE(as[i].D == as[0].D, "LayerNorm widths %d and %d in one launch: widths other than 64 and 256 do not mix", as[0].D, as[i].D);
+    SERL_LN_WIDE_LAUNCH(ln_tanh_bwd_multi_wide_kernel, as[0].D, grid, dim3(256), 0, stream, mv, loss)
+  } else {
+    SERL_LAUNCH_CHAIN(ln_tanh_bwd_multi_kernel, grid, dim3(256), 0, stream, mv, loss);
+  }
   SERL_HIP(hipGetLastError());
   return SERL_OK;
 }

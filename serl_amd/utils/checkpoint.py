@@ -145,12 +145,12 @@ def load_state_dict(agent, sd: dict, restore_rng: bool = False):
     etype = "small" if core.cfg.encoder_type == 1 else "resnet-pretrained"
     tp = theta_paths(keys, encoder_type=etype)
     trunk = _trunk_paths() if (keys and etype != "small") else {}   # state-only / SmallEncoder agents have no frozen trunk
+    todo = []      # (section, leaf, array): everything is sized against the agent's leaves before the first one is written
     for section in ("params", "target_params"):
         tree = sd.get(section)
         if tree is None:
             continue
-        for leaf, v in leaves_from_tree(tp, tree):
-            core.set(section, leaf, v)
+        todo += [(section, leaf, v) for leaf, v in leaves_from_tree(tp, tree)]
         if trunk:
             # Where flax puts the ONE shared frozen trunk is derived from its adoption rule (first camera in sorted-key
             # order) and unverified against a real flax install: accept it under any camera, like
@@ -160,17 +160,25 @@ def load_state_dict(agent, sd: dict, restore_rng: bool = False):
             if not owners:
                 raise KeyError(f"'{section}' holds no pretrained_encoder under any of encoder_{{{', '.join(sorted(keys))}}}")
             root = enc[f"encoder_{owners[0]}"]["pretrained_encoder"]
-            for leaf, v in leaves_from_tree(trunk, root):
-                core.set(section, leaf, v)
+            todo += [(section, leaf, v) for leaf, v in leaves_from_tree(trunk, root)]
     if sd.get("opt_states") is not None:
         for tx in TX_NAMES:
             adam = _find_adam_state(sd["opt_states"][tx])
             if adam is None:
                 raise KeyError(f"opt_states['{tx}'] holds no ScaleByAdamState (mu / nu)")
             for mom in ("mu", "nu"):
-                for leaf, v in leaves_from_tree(tp, adam[mom]):
-                    # leaves outside the optimizer's support are exact zeros; the C ABI accepts (and checks) them
-                    core.set(f"opt/{tx}/{mom}", leaf, np.asarray(v, np.float32))
+                # leaves outside the optimizer's support are exact zeros; the C ABI accepts (and checks) them
+                todo += [(f"opt/{tx}/{mom}", leaf, np.asarray(v, np.float32)) for leaf, v in leaves_from_tree(tp, adam[mom])]
+    # A state saved by an agent of another geometry (MLP width, ensemble, action or state dimension) is refused whole: a leaf
+    # that does not depend on the differing dimension would otherwise be overwritten before the first mismatch is met
+    counts = getattr(core, "leaves", {})
+    for section, leaf, v in todo:
+        have, got = counts.get(leaf), int(np.size(v))
+        if have is not None and have != got:
+            raise ValueError(f"{section}: leaf '{leaf}' has {have} elements in this agent, the state holds {got} "
+                             f"(shape {tuple(np.shape(v))}); nothing was loaded")
+    for section, leaf, v in todo:
+        core.set(section, leaf, v)
     if sd.get("step") is not None:
         core.step = int(np.asarray(sd["step"]))
     if restore_rng:

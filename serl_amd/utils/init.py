@@ -47,6 +47,31 @@ def feat_hw(H, W):
 SMALL_FEATURES = (3, 32, 64, 128, 256)   # SmallEncoder(features=(32, 64, 128, 256)) on RGB (drq.py:140-151)
 
 
+HIDDEN_WIDTHS = tuple(range(64, 1025, 64))   # serl_agent_cfg.hidden: one wave per LayerNorm row, hidden / 64 columns per lane
+
+
+def mlp_hidden_width(critic_network_kwargs=None, policy_network_kwargs=None) -> int:
+    """The one width h of the critic's and the policy's MLPs from the reference's `critic_network_kwargs` /
+    `policy_network_kwargs` (hidden_dims=[h, h], LayerNorm, default [256, 256]).  Served: two layers of the same width, the same
+    in both networks, a multiple of 64 from 64 to 1024; anything else raises NotImplementedError."""
+    served = "served: hidden_dims=[h, h] with LayerNorm, h a multiple of 64 in [64, 1024], the same h for critic and policy"
+    widths = []
+    for which, nk in (("critic_network_kwargs", critic_network_kwargs or {}), ("policy_network_kwargs", policy_network_kwargs or {})):
+        if not nk.get("use_layer_norm", True):
+            raise NotImplementedError(f"{which}: use_layer_norm=False ({served})")
+        dims = [int(d) for d in nk.get("hidden_dims", [256, 256])]
+        if len(dims) != 2:
+            raise NotImplementedError(f"{which}: hidden_dims={dims} has {len(dims)} layers ({served})")
+        if dims[0] != dims[1]:
+            raise NotImplementedError(f"{which}: hidden_dims={dims} has two different layer widths ({served})")
+        if dims[0] not in HIDDEN_WIDTHS:
+            raise NotImplementedError(f"{which}: width {dims[0]} is off the grid ({served})")
+        widths.append(dims[0])
+    if widths[0] != widths[1]:
+        raise NotImplementedError(f"critic width {widths[0]} and policy width {widths[1]} differ ({served})")
+    return widths[0]
+
+
 def theta_shapes(n_cam, H, W, S, A, ensemble=10, hidden=256, bottleneck=256, sle_features=8, proprio_dim=64,
                  encoder_type="resnet-pretrained", num_stack=1):
     """S: the proprio Dense's input width -- T * S for a stack of T = num_stack frames, which EncodingWrapper folds into the

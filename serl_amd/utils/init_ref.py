@@ -82,10 +82,13 @@ def _init_of(name, shape):
     return XAVIER_UNIFORM
 
 
-def theta_leaves(image_keys: Sequence[str], H, W, S, A, ensemble=10, encoder_type="resnet-pretrained", num_stack=1) -> List[Leaf]:
-    """The trainable leaves of DrQAgent.create_drq (image_keys non-empty) or SACAgent.create_states (image_keys empty)."""
+def theta_leaves(image_keys: Sequence[str], H, W, S, A, ensemble=10, encoder_type="resnet-pretrained", num_stack=1,
+                 hidden=256) -> List[Leaf]:
+    """The trainable leaves of DrQAgent.create_drq (image_keys non-empty) or SACAgent.create_states (image_keys empty);
+    hidden: the MLPs' width (hidden_dims=[hidden, hidden])."""
     from ..agents.flax_tree import theta_paths
-    shapes = theta_shapes(len(image_keys), H, W, S, A, ensemble=ensemble, encoder_type=encoder_type, num_stack=num_stack)
+    shapes = theta_shapes(len(image_keys), H, W, S, A, ensemble=ensemble, hidden=hidden, encoder_type=encoder_type,
+                          num_stack=num_stack)
     paths = theta_paths(tuple(image_keys), encoder_type=encoder_type)
     # the vmapped module: DrQ ensemblizes the critic's MLP (drq.py:206-209), state SAC the whole Critic (sac.py:516-517)
     vm = ("modules_critic", "network") if image_keys else ("modules_critic",)
@@ -211,11 +214,12 @@ def draw_flat(leaves: Sequence[Leaf], init_rng, device: Optional[int] = 0, tempe
 
 
 def theta_reference(image_keys, H, W, S, A, rng, ensemble=10, encoder_type="resnet-pretrained", temperature_init=1.0,
-                    device: Optional[int] = 0, num_stack=1) -> Dict[str, np.ndarray]:
+                    device: Optional[int] = 0, num_stack=1, hidden=256) -> Dict[str, np.ndarray]:
     """init_theta's leaves as the reference's DrQ / state-SAC create path draws them from `rng` (drq.py:69, sac.py:368).
-    S is the flattened proprio width T * S of a stack of T = num_stack frames; the widened leaves draw with their real fan-in."""
-    return draw_flat(theta_leaves(image_keys, H, W, S, A, ensemble, encoder_type, num_stack), init_rng_of(reference_key(rng)), device,
-                     temperature_init)
+    S is the flattened proprio width T * S of a stack of T = num_stack frames; the widened leaves draw with their real fan-in.
+    hidden: the MLPs' width; its leaves draw with the fans of that width."""
+    return draw_flat(theta_leaves(image_keys, H, W, S, A, ensemble, encoder_type, num_stack, hidden), init_rng_of(reference_key(rng)),
+                     device, temperature_init)
 
 
 def bc_reference(image_keys, H, W, S, A, rng, device: Optional[int] = 0) -> Dict[str, np.ndarray]:
