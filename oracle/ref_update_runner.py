@@ -248,9 +248,14 @@ def synth_flat_batch(cfg, B, seed):
             "reward": (rng.random(B) < 0.3).astype(np.float32), "mask": (rng.random(B) < 0.9).astype(np.float32)}
 
 
-def run_reference(cfg: O.Config, B: int, schedule, param_seed=42, batch_seed=100, float64=True):
+def run_reference(cfg: O.Config, B: int, schedule, param_seed=42, batch_seed=100, float64=True, theta_transform=None,
+                  batch_transform=None, target_transform=None):
     """schedule: list of ("critics",), ("high_utd", utd_ratio) or ("update", (network names...)) -- the last one is
     SACAgent.update on an un-augmented batch.  cfg.image_keys == (): the state-only agent of make_sac_agent.
+    theta_transform(theta, cfg) -> theta: applied to O.init_params' leaves before they are patched into the reference agent
+    (params and target_params); target_transform(theta, cfg) -> theta: the target copy, from the transformed leaves;
+    batch_transform(pb, step) -> pb: applied to the synthetic sample of schedule item `step`.  All three default to None = the
+    run every update_*.npz was recorded from.
     Returns dict(steps=[...], final=...)."""
     assert R.reference_available(), "/root/reference is not present"
     jax = R.install(float64)
@@ -258,6 +263,8 @@ def run_reference(cfg: O.Config, B: int, schedule, param_seed=42, batch_seed=100
     from flax.core.frozen_dict import freeze
 
     trunk, theta = O.init_params(cfg, param_seed)
+    if theta_transform is not None:
+        theta = theta_transform(theta, cfg)
     agent = _make_reference_agent(jax, jnp, cfg, trunk)
     assert agent.config["critic_ensemble_size"] == cfg.ensemble and agent.config["critic_subsample_size"] == cfg.subsample
     assert abs(agent.config["soft_target_update_rate"] - cfg.tau) < 1e-12 and abs(agent.config["target_entropy"] - cfg.target_entropy) < 1e-12
@@ -275,7 +282,13 @@ def run_reference(cfg: O.Config, B: int, schedule, param_seed=42, batch_seed=100
         val = np.asarray(theta[name], np.float64 if float64 else np.float32).reshape(tuple(cur.shape))
         _set(params, path, jnp.asarray(val))
     params = jax.tree_map(lambda a: jnp.asarray(np.asarray(a)), params)
-    agent = agent.replace(state=agent.state.replace(params=params, target_params=params))
+    target_params = params
+    if target_transform is not None:
+        target_params = jax.tree_map(lambda a: a, params)
+        for name, val in target_transform(theta, cfg).items():
+            cur = _get(target_params, paths[name])
+            _set(target_params, paths[name], jnp.asarray(np.asarray(val, np.float64 if float64 else np.float32).reshape(tuple(cur.shape))))
+    agent = agent.replace(state=agent.state.replace(params=params, target_params=target_params))
 
     rng0 = [int(v) & 0xFFFFFFFF for v in np.asarray(agent.state.rng).reshape(-1)]   # state.rng as the reference's factory left it
     steps = []
@@ -284,6 +297,8 @@ def run_reference(cfg: O.Config, B: int, schedule, param_seed=42, batch_seed=100
         utd = item[1] if kind == "high_utd" else 1
         nets = tuple(item[1]) if kind == "update" else ()
         pb = synth_flat_batch(cfg, B, batch_seed + i) if cfg.state_only else synth_packed_batch(cfg, B, batch_seed + i)
+        if batch_transform is not None:
+            pb = batch_transform(pb, i)
         if cfg.state_only:
             batch = freeze({"observations": jnp.asarray(pb["state"][:, 0]), "next_observations": jnp.asarray(pb["next_state"][:, 0]),
                             "actions": jnp.asarray(pb["action"]), "rewards": jnp.asarray(pb["reward"]),

@@ -187,6 +187,13 @@ def test_hip_update_matches_the_reference_golden_at_width(gpu, name, monkeypatch
     for sec in ("params", "target_params"):
         agent.core.load_flat(sec, trunk)
         agent.core.load_flat(sec, {AH.product_name(k, cfg.image_keys): v for k, v in theta.items()})
+    _replay_golden(agent, g, f"widths_update_{name}")
+
+
+def _replay_golden(agent, g, label):
+    """the recorded schedule of a reference golden through an agent that holds the run's initial parameters (injected noise), with
+    the comparisons and bounds of tests/test_golden_update_gpu.py; also used by tests/test_trained_regime_gpu.py"""
+    cfg, B = g["cfg"], g["B"]
     n_steps = 0
     for i, step in enumerate(g["steps"]):
         noise = AH.noise_to_device(cfg, {k: (v.astype(np.float32) if k.startswith("eps") else v) for k, v in step["noise"].items()
@@ -237,7 +244,7 @@ def test_hip_update_matches_the_reference_golden_at_width(gpu, name, monkeypatch
             assert bulk < TOL, (sec, leaf_name, bulk)
             bound = 2.1 * lr_max * n_steps * (cfg.tau * n_steps if sec == "target_params" else 1.0) + TOL * scale
             assert err.max() <= bound, (sec, leaf_name, err.max(), bound)
-    print(f"widths_update_{name}: HIP vs reference golden: Adam moments {worst_m:.1e}, params (99.9 pct) {worst_p:.1e}")
+    print(f"{label}: HIP vs reference golden: Adam moments {worst_m:.1e}, params (99.9 pct) {worst_p:.1e}")
 
 
 def test_reference_init_then_one_update_matches_the_reference_at_width_128(gpu, monkeypatch):
