@@ -259,6 +259,9 @@ typedef struct serl_agent_cfg {
    * applied to 3T channels (SERL_ERR_UNSUPPORTED). */
   int num_stack;
 } serl_agent_cfg;
+#define SERL_STD_EXP 0
+#define SERL_STD_SOFTPLUS 1
+#define SERL_STD_UNIFORM 2
 #define SERL_ENCODER_RESNET_PRETRAINED 0
 #define SERL_ENCODER_SMALL 1
 #define SERL_TX_ACTOR 0
@@ -266,6 +269,16 @@ typedef struct serl_agent_cfg {
 #define SERL_TX_TEMPERATURE 2
 
 int serl_agent_create(const serl_agent_cfg* cfg, serl_agent** out);
+/* serl_agent_create with another policy distribution (actor_critic_nets.py:167-227).  serl_agent_create is this function with
+ * (SERL_STD_EXP, 0): exp + tanh, what utils/launcher.py configures -- serl_agent_cfg itself is unchanged and describes the agent it
+ * always did.  Any other value of the two arguments is SERL_ERR_INVALID, the message naming the argument and the value.
+ *   std_param: SERL_STD_EXP      std = clip(exp(Dense_1(h)), std_min, std_max)
+ *              SERL_STD_SOFTPLUS std = clip(softplus(Dense_1(h)), std_min, std_max)
+ *              SERL_STD_UNIFORM  std = clip(exp(log_stds), std_min, std_max): one trainable vector of act_dim floats shared by
+ *                                all rows, leaf actor/log_stds in place of actor/logstd/{kernel,bias} (create_drq's own default)
+ *   no_tanh:   0 = distrax Tanh bijector on the Gaussian; 1 = tanh_squash_distribution=False: the plain Gaussian -- actions are
+ *              unbounded, log pi has no log-det term, and the mode is the mean */
+int serl_agent_create_policy(const serl_agent_cfg* cfg, int std_param, int no_tanh, serl_agent** out);
 int serl_agent_destroy(serl_agent* a);
 
 /* Parameter tree access (flat leaf names, see DESIGN.md "parameter arena"; the Python shim maps

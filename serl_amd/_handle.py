@@ -19,7 +19,7 @@ class Handle:
     def __init__(self, cfg):
         self.L = _lib.lib()
         self._h = C.c_void_p()
-        _lib.check(self._fn("create")(C.byref(cfg), C.byref(self._h)))
+        _lib.check(self._create(cfg))
         self._counts, self._trainable = {}, {}   # leaf -> element count / trainable (where leaf_info reports it)
         leaf_info = self._fn("leaf_info")
         name, cnt, tr = C.create_string_buffer(128), C.c_int64(), C.c_int()
@@ -29,6 +29,10 @@ class Handle:
             self._counts[name.value.decode()] = cnt.value
             if flag:
                 self._trainable[name.value.decode()] = bool(tr.value)
+
+    def _create(self, cfg):
+        """<prefix>_create(cfg, &handle) -> status; a subclass with another constructor overrides it"""
+        return self._fn("create")(C.byref(cfg), C.byref(self._h))
 
     def __del__(self):
         h, self._h = getattr(self, "_h", None), None

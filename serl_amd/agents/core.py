@@ -11,6 +11,8 @@ from .. import _lib
 from .._handle import Handle
 from .._lib_agent import APPLY_ACTOR_TEMP, APPLY_CRITIC, NET_BITS, TX_INDEX, SerlAgentCfg, SerlInfo, SerlNoise  # noqa: F401
 
+from ..utils.init import STD_PARAMETERIZATIONS
+
 TX_NAMES = ("actor", "critic", "temperature")
 
 
@@ -21,10 +23,12 @@ class AgentCore(Handle):
                  bottleneck=256, sle_features=8, proprio_dim=64, warmup_steps=0, discount=0.96,
                  tau=0.005, lr=3e-4, dropout=0.1, std_min=1e-5, std_max=5.0, target_entropy=None,
                  seed=0, temp_warmup_steps=-1, optimizers=None, encoder_type="resnet-pretrained",
-                 critic_subsample_size=2, backup_entropy=False, num_stack=1):
+                 critic_subsample_size=2, backup_entropy=False, num_stack=1, std_parameterization="exp",
+                 tanh_squash_distribution=True):
         """optimizers: optional {"actor"|"critic"|"temperature": make_optimizer kwargs (common/optimizers.py:6-13:
         learning_rate, warmup_steps, cosine_decay_steps, weight_decay, clip_grad_norm)} overriding lr / warmup_steps.
-        num_stack: T, frames per observation (SmallEncoder only); state_dim is then the flattened width T * S."""
+        num_stack: T, frames per observation (SmallEncoder only); state_dim is then the flattened width T * S.
+        std_parameterization / tanh_squash_distribution: the policy distribution (Policy's kwargs of the same names)."""
         if target_entropy is None:
             target_entropy = -act_dim / 2
         self.cfg = SerlAgentCfg(device, n_cam, H, W, state_dim, act_dim, batch, ensemble, hidden,
@@ -37,6 +41,10 @@ class AgentCore(Handle):
         self.cfg.critic_subsample_size = -1 if critic_subsample_size is None else int(critic_subsample_size)
         self.cfg.backup_entropy = 1 if backup_entropy else 0
         self.cfg.num_stack = int(num_stack)
+        # the policy distribution is no field of serl_agent_cfg: it goes to serl_agent_create_policy (_create)
+        self.std_parameterization = std_parameterization
+        self.tanh_squash_distribution = bool(tanh_squash_distribution)
+        self._std_param = STD_PARAMETERIZATIONS.index(std_parameterization)
         for name, kw in (optimizers or {}).items():
             i = TX_INDEX[name]
             bad = set(kw) - {"learning_rate", "warmup_steps", "cosine_decay_steps", "weight_decay", "clip_grad_norm"}
@@ -55,6 +63,9 @@ class AgentCore(Handle):
         self.device = torch.device("cuda", device)
         super().__init__(self.cfg)
         self._keep = None
+
+    def _create(self, cfg):
+        return self.L.serl_agent_create_policy(C.byref(cfg), self._std_param, 0 if self.tanh_squash_distribution else 1, C.byref(self._h))
 
     # ---- parameters ------------------------------------------------------------------------
     @property

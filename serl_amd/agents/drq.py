@@ -175,6 +175,9 @@ class DrQAgent:
         encoder_type="resnet-pretrained", use_proprio=True, REDQ subsample 2, tanh-squashed
         exp-parameterised policy, LayerNorm+tanh MLPs (utils/launcher.py:79-116) -- 256x256 there; critic_network_kwargs /
         policy_network_kwargs may give hidden_dims=[h, h], h a multiple of 64 in [64, 1024], the same in both.
+        policy_kwargs: std_parameterization "exp", "softplus" or "uniform" (one trainable log_stds vector, no Dense_1) and
+        tanh_squash_distribution True or False all run in the head kernels; "fixed" is refused.  A key that is absent, or
+        policy_kwargs=None, means the launcher's value ("exp", True).
         Frame stacks: the sample observation carries T = observations[image_key].shape[0] frames and a (T, S) state, as
         ChunkingWrapper(obs_horizon=T) produces them; EncodingWrapper(enable_stacking=True) folds them into the channels and the
         proprio width (common/encoding.py:39-44,58-64).  T in 1..4 with encoder_type="small"; the pretrained ResNet-10 cannot take
@@ -187,8 +190,7 @@ class DrQAgent:
         if not use_proprio:
             raise NotImplementedError("only use_proprio=True")
         pk = policy_kwargs or {}
-        if pk.get("std_parameterization", "exp") != "exp" or not pk.get("tanh_squash_distribution", True):
-            raise NotImplementedError("policy must be tanh-squashed with std_parameterization='exp'")
+        std_param, squash = pinit.policy_mode(pk)
         hidden = pinit.mlp_hidden_width(critic_network_kwargs, policy_network_kwargs)
         seed = int(np.asarray(rng).reshape(-1)[-1]) if not isinstance(rng, int) else rng
         image_keys = tuple(image_keys)
@@ -219,13 +221,15 @@ class DrQAgent:
                          std_max=pk.get("std_max", 10.0), target_entropy=target_entropy, seed=seed,
                          optimizers={k: {"warmup_steps": 0, **v} for k, v in opts.items()}, encoder_type=encoder_type,
                          critic_subsample_size=critic_subsample_size, backup_entropy=backup_entropy, num_stack=T,
-                         hidden=hidden)
+                         hidden=hidden, std_parameterization=std_param, tanh_squash_distribution=squash)
         if init_ref.check_param_init(param_init):
             theta = init_ref.theta_reference(image_keys, H, W, S, A, rng, ensemble=critic_ensemble_size, encoder_type=encoder_type,
-                                             temperature_init=temperature_init, device=device, num_stack=T, hidden=hidden)
+                                             temperature_init=temperature_init, device=device, num_stack=T, hidden=hidden,
+                                             std_parameterization=std_param)
         else:
             theta = pinit.init_theta(len(image_keys), H, W, S, A, seed=seed, temperature_init=temperature_init,
-                                     ensemble=critic_ensemble_size, encoder_type=encoder_type, num_stack=T, hidden=hidden)
+                                     ensemble=critic_ensemble_size, encoder_type=encoder_type, num_stack=T, hidden=hidden,
+                                     std_parameterization=std_param)
         trunk = pinit.init_trunk(seed=seed) if encoder_type == "resnet-pretrained" else {}
         for sec in ("params", "target_params"):  # JaxRLTrainState.create(target_params=params)
             core.load_flat(sec, theta)

@@ -130,14 +130,27 @@ def _trunk_paths():
     return m
 
 
-def theta_paths(image_keys, critic_mlp_name="network", encoder_type="resnet-pretrained"):
+def _policy_std_paths(std_parameterization):
+    """the leaves behind the policy's mean head: Dense_1, or Policy's own `log_stds` parameter with "uniform"
+    (actor_critic_nets.py:199-201: self.param("log_stds", zeros, (action_dim,)))"""
+    if std_parameterization == "uniform":
+        return {"actor/log_stds": [("modules_actor", "log_stds")]}
+    return {"actor/logstd/kernel": [("modules_actor", "Dense_1", "kernel")], "actor/logstd/bias": [("modules_actor", "Dense_1", "bias")]}
+
+
+def std_parameterization_of(core) -> str:
+    """the std parameterisation an AgentCore was created with (a handle without the attribute is the "exp" agent)"""
+    return getattr(core, "std_parameterization", "exp")
+
+
+def theta_paths(image_keys, critic_mlp_name="network", encoder_type="resnet-pretrained", std_parameterization="exp"):
     """flat trainable leaf -> list of flax paths (aliases)."""
     enc = ("modules_actor", "encoder")
     m = {}
     if len(image_keys) == 0:
         # SACAgent.create_states: Policy(encoder=None, network=MLP) and ensemblize(Critic(encoder=None, network=MLP))
         # -- the vmapped Critic keeps its module names, every leaf gains a leading ensemble axis (sac.py:516-524)
-        return _state_paths()
+        return _state_paths(std_parameterization)
     for i, k in enumerate(image_keys):
         e = enc + (f"encoder_{k}",)
         if encoder_type == "small":   # SmallEncoder (small_encoders.py:9-55): Conv_0..3 {kernel, bias}
@@ -170,13 +183,12 @@ def theta_paths(image_keys, critic_mlp_name="network", encoder_type="resnet-pret
         m[f"actor/ln{j}/bias"] = [a + (f"LayerNorm_{n}", "bias")]
     m["actor/mean/kernel"] = [("modules_actor", "Dense_0", "kernel")]
     m["actor/mean/bias"] = [("modules_actor", "Dense_0", "bias")]
-    m["actor/logstd/kernel"] = [("modules_actor", "Dense_1", "kernel")]
-    m["actor/logstd/bias"] = [("modules_actor", "Dense_1", "bias")]
+    m.update(_policy_std_paths(std_parameterization))
     m["temp/lagrange"] = [("modules_temperature", "lagrange")]
     return m
 
 
-def _state_paths():
+def _state_paths(std_parameterization="exp"):
     m = {}
     for mod, pre in (("modules_critic", "critic"), ("modules_actor", "actor")):
         for j, n in ((1, 0), (2, 1)):
@@ -188,8 +200,7 @@ def _state_paths():
     m["critic/head/bias"] = [("modules_critic", "Dense_0", "bias")]
     m["actor/mean/kernel"] = [("modules_actor", "Dense_0", "kernel")]
     m["actor/mean/bias"] = [("modules_actor", "Dense_0", "bias")]
-    m["actor/logstd/kernel"] = [("modules_actor", "Dense_1", "kernel")]
-    m["actor/logstd/bias"] = [("modules_actor", "Dense_1", "bias")]
+    m.update(_policy_std_paths(std_parameterization))
     m["temp/lagrange"] = [("modules_temperature", "lagrange")]
     return m
 
@@ -255,9 +266,9 @@ def export_tree(core, section: str, image_keys, duplicate_encoder_under_critic: 
     cfg = core.cfg
     etype = "small" if cfg.encoder_type == 1 else "resnet-pretrained"
     shapes = theta_shapes(cfg.n_cam, cfg.H, cfg.W, cfg.state_dim, cfg.act_dim, ensemble=cfg.ensemble, hidden=cfg.hidden,
-                          encoder_type=etype, num_stack=max(cfg.num_stack, 1))
+                          encoder_type=etype, num_stack=max(cfg.num_stack, 1), std_parameterization=std_parameterization_of(core))
     shapes.update(trunk_shapes())
-    paths = theta_paths(image_keys, critic_mlp_name, etype)
+    paths = theta_paths(image_keys, critic_mlp_name, etype, std_parameterization_of(core))
     if cfg.n_cam and etype != "small":
         # ONE frozen trunk: drq.py:165-176 passes the same `pretrained_encoder` module to every camera's
         # PreTrainedResNetEncoder, flax adopts a shared module once -- under the first camera in sorted-key order --

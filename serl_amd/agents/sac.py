@@ -36,11 +36,11 @@ class SACAgent(DrQAgent):
                       **kwargs):
         """sac.py:486-542 -> create (:323-400).  Built natively: the configuration of utils/launcher.py:50-76
         (REDQ subsample 2, tanh-squashed exp-parameterised policy, LayerNorm+tanh 256x256 MLPs); hidden_dims=[h, h] in both
-        network kwargs selects another width h, a multiple of 64 in [64, 1024].
+        network kwargs selects another width h, a multiple of 64 in [64, 1024].  policy_kwargs: std_parameterization "exp",
+        "softplus" or "uniform" and tanh_squash_distribution True or False run in the head kernels ("fixed" is refused).
         param_init: "numpy" (default) or "reference" (the reference's own initialisers and keys, utils/init_ref.py)."""
         pk = policy_kwargs or {}
-        if pk.get("std_parameterization", "exp") != "exp" or not pk.get("tanh_squash_distribution", True):
-            raise NotImplementedError("policy must be tanh-squashed with std_parameterization='exp'")
+        std_param, squash = pinit.policy_mode(pk)
         hidden = pinit.mlp_hidden_width(critic_network_kwargs, policy_network_kwargs)
         ao = {"learning_rate": 3e-4, "warmup_steps": 2000, **(actor_optimizer_kwargs or {})}     # sac.py:333-336
         co = {"learning_rate": 3e-4, "warmup_steps": 2000, **(critic_optimizer_kwargs or {})}    # sac.py:337-340
@@ -56,13 +56,14 @@ class SACAgent(DrQAgent):
                          temp_warmup_steps=int(to.get("warmup_steps", 0)), std_min=pk.get("std_min", 1e-5),
                          std_max=pk.get("std_max", 10.0), target_entropy=target_entropy, seed=seed,
                          optimizers={"actor": ao, "critic": co, "temperature": {"warmup_steps": 0, **to}},
-                         critic_subsample_size=critic_subsample_size, backup_entropy=backup_entropy, hidden=hidden)
+                         critic_subsample_size=critic_subsample_size, backup_entropy=backup_entropy, hidden=hidden,
+                         std_parameterization=std_param, tanh_squash_distribution=squash)
         if init_ref.check_param_init(param_init):
             theta = init_ref.theta_reference((), 0, 0, S, A, rng, ensemble=critic_ensemble_size, temperature_init=temperature_init,
-                                             device=device, hidden=hidden)
+                                             device=device, hidden=hidden, std_parameterization=std_param)
         else:
             theta = pinit.init_theta(0, 0, 0, S, A, seed=seed, temperature_init=temperature_init, ensemble=critic_ensemble_size,
-                                     hidden=hidden)
+                                     hidden=hidden, std_parameterization=std_param)
         for sec in ("params", "target_params"):
             core.load_flat(sec, theta)
         config = dict(critic_ensemble_size=critic_ensemble_size, critic_subsample_size=critic_subsample_size,

@@ -27,7 +27,7 @@ struct Offs {
   long cam_stride;
   long c_w1, c_b1, c_g1, c_be1, c_w2, c_b2, c_g2, c_be2, c_hw, c_hb;
   long p_W, p_b, p_g, p_be;
-  long a_w1, a_b1, a_g1, a_be1, a_w2, a_b2, a_g2, a_be2, a_Wm, a_bm, a_Ws, a_bs;
+  long a_w1, a_b1, a_g1, a_be1, a_w2, a_b2, a_g2, a_be2, a_Wm, a_bm, a_Ws, a_bs;   // kPolUniform: a_bs = actor/log_stds, no a_Ws
   long lam;
   long P, Pc, Pa0, Pa1;
 };
@@ -72,6 +72,9 @@ struct serl_agent {
   int E = 0, D = 0, HW = 0, XA = 0;  // enc dim, sle dim, feature pixels, E + A
   bool state_only = false;           // n_cam == 0: SACAgent.create_states
   bool small = false;                // encoder_type == "small": trainable SmallEncoder instead of the frozen trunk
+  int std_param = SERL_STD_EXP, no_tanh = 0;   // the arguments of serl_agent_create_policy
+  int pol_mode = kPolExp;            // ... as the head kernels take them
+  int head_groups = 2;               // Dense layers of the policy head: (mean, log_std), or the mean alone with kPolUniform
   SmallWorkspace sws{};
   Offs o{};
   std::vector<Leaf> theta_leaves, trunk_leaves;
@@ -228,8 +231,15 @@ void build_layout(serl_agent* a) {
   o.a_be2 = add_leaf(L, off, "actor/ln2/bias", Hd);
   o.a_Wm = add_leaf(L, off, "actor/mean/kernel", Hd * A);
   o.a_bm = add_leaf(L, off, "actor/mean/bias", A);
-  o.a_Ws = add_leaf(L, off, "actor/logstd/kernel", Hd * A);
-  o.a_bs = add_leaf(L, off, "actor/logstd/bias", A);
+  a->pol_mode = a->std_param | (a->no_tanh ? kPolNoTanh : 0);
+  a->head_groups = a->std_param == SERL_STD_UNIFORM ? 1 : 2;
+  if (a->head_groups == 1) {   // one log-std vector shared by all rows (actor_critic_nets.py:199-201), directly behind the mean's bias
+    o.a_Ws = -1;
+    o.a_bs = add_leaf(L, off, "actor/log_stds", A);
+  } else {
+    o.a_Ws = add_leaf(L, off, "actor/logstd/kernel", Hd * A);
+    o.a_bs = add_leaf(L, off, "actor/logstd/bias", A);
+  }
   o.Pa1 = off;
   o.lam = add_leaf(L, off, "temp/lagrange", 1);
   o.P = off;
@@ -495,8 +505,10 @@ int policy_fwd_multi(serl_agent* a, const PolJob* jobs, int n, int cnt, hipStrea
                      pb.m.h1, pb.m.xh1, pb.m.rs1, nullptr, nullptr, nullptr};
     d2[i] = DenseJob{pb.m.h1, Hd, 0, P + o.a_w2, 0, P + o.a_b2, P + o.a_g2, P + o.a_be2, 0,
                      pb.m.h2, pb.m.xh2, pb.m.rs2, nullptr, nullptr, nullptr};
-    gd[i] = gemm_fwd(pb.m.h2, Hd, 0, P + o.a_Wm, o.a_Ws - o.a_Wm, a->slabs_lane[i], 2, cnt, A, Hd, 4);   // (mean, log_std) as two groups
+    // (mean, log_std) as two groups; the mean alone when log_stds is a parameter vector (the stride is then unused)
+    gd[i] = gemm_fwd(pb.m.h2, Hd, 0, P + o.a_Wm, o.a_bs - o.a_bm, a->slabs_lane[i], a->head_groups, cnt, A, Hd, 4);
     pv[i] = PolicyDistArgs{};
+    pv[i].mode = a->pol_mode;
     pv[i].slabs = a->slabs_lane[i]; pv[i].S = 4; pv[i].bias_mean = P + o.a_bm; pv[i].bias_ls = P + o.a_bs; pv[i].pre = pb.pre;
     pv[i].eps = j.eps; pv[i].act = j.act_out; pv[i].ld_act = j.ld_act; pv[i].logp = pb.logp; pv[i].std_out = pb.std;
     pv[i].sum_logp = j.sum_logp; pv[i].lam = P + o.lam; pv[i].alpha_out = j.alpha_out;
@@ -671,6 +683,8 @@ int critic_loss_or_rider(serl_agent* a, const LossArgs& L, hipStream_t st, const
 
 // Gradient of the policy's head biases (mean, log_std): the column sums of dpre.  Fused: a job of the phase's deferred
 // column-sum launch.  Else: a colsum launch.
+// (kPolUniform: the second slab of dpre is the per-row gradient of the shared log_stds, whose leaf sits out_gstride = A behind
+// the mean's bias: the same two column sums.)
 int head_bias_grad(serl_agent* a, int cnt, float* out, long out_gstride, hipStream_t st) {
   const int A = a->cfg.act_dim;
   if (!a->fuse) return colsum(a->dpre, nullptr, 2, cnt, A, out, out_gstride, false, st);
@@ -868,7 +882,9 @@ float lr_at(const serl_agent_cfg& c, int64_t count, int tx) {
 
 extern "C" {
 
-int serl_agent_create(const serl_agent_cfg* cfg, serl_agent** out) {
+int serl_agent_create(const serl_agent_cfg* cfg, serl_agent** out) { return serl_agent_create_policy(cfg, SERL_STD_EXP, 0, out); }
+
+int serl_agent_create_policy(const serl_agent_cfg* cfg, int std_param, int no_tanh, serl_agent** out) {
   SERL_REQUIRE(cfg && out, "NULL argument");
   SERL_REQUIRE(cfg->n_cam >= 0 && cfg->n_cam <= SERL_MAX_CAMS, "n_cam %d not in [0,%d]", cfg->n_cam, SERL_MAX_CAMS);
   SERL_REQUIRE(cfg->n_cam == 0 || (cfg->H >= 32 && cfg->W >= 32), "images must be at least 32x32");
@@ -890,6 +906,9 @@ int serl_agent_create(const serl_agent_cfg* cfg, serl_agent** out) {
     return SERL_ERR_UNSUPPORTED;
   }
   SERL_REQUIRE(num_stack == 1 || cfg->n_cam > 0, "num_stack %d on a state-only agent: its state path has no stacking wrapper", num_stack);
+  SERL_REQUIRE(std_param >= SERL_STD_EXP && std_param <= SERL_STD_UNIFORM,
+               "std_param %d is not SERL_STD_EXP (0), SERL_STD_SOFTPLUS (1) or SERL_STD_UNIFORM (2)", std_param);
+  SERL_REQUIRE(no_tanh == 0 || no_tanh == 1, "no_tanh %d is not 0 (tanh-squashed) or 1 (plain Gaussian)", no_tanh);
   SERL_REQUIRE(cfg->state_dim % num_stack == 0, "state_dim %d is not num_stack %d proprio vectors (state_dim is the flattened width T * S)",
                cfg->state_dim, num_stack);
   for (int t = 0; t < 3; ++t) {
@@ -907,6 +926,7 @@ int serl_agent_create(const serl_agent_cfg* cfg, serl_agent** out) {
   serl_agent* a = new serl_agent();
   a->cfg = *cfg;
   a->cfg.num_stack = num_stack;
+  a->std_param = std_param; a->no_tanh = no_tanh;
   { const char* e = getenv("SERL_CHAIN_FUSE"); a->fuse = !(e && e[0] == '0'); }
   build_layout(a);
   if (int rc = alloc_zeroed(&a->arena, carve(a, nullptr), "agent arena")) {
@@ -1334,15 +1354,17 @@ int serl_agent_actor_grads(serl_agent* a, int global_count, const serl_noise* no
   RC(critic_bwd(a, a->theta, a->crit, cnt, false, st, nullptr, -1.0f / ((float)c.ensemble * (float)global_count)));
   RC(policy_dist_bwd(a->dx + a->E, a->XA, a->crit.x + a->E, a->XA, a->pol.pre, a->pol.std, eps_pi, a->aux + X_ALPHA,
                      1.0f / (float)global_count, cnt, A, c.std_min, c.std_max, a->dpre, a->crit.q, c.ensemble,
-                     a->SC + S_QPI, st));
-  // policy heads (mean, log_std): two groups with uniform stride; parameter gradients off the critical chain
-  const long hs = o.a_Ws - o.a_Wm;
+                     a->SC + S_QPI, st, a->pol_mode));
+  // policy heads (mean, log_std): two groups with uniform stride; parameter gradients off the critical chain.  kPolUniform: one
+  // group, and hs = A is the distance from the mean's bias to log_stds
+  const long hs = o.a_bs - o.a_bm;
+  const int hg = a->head_groups;
   float* Ga = a->Ga;
   const long b0 = o.Pa0;
-  RC(wgrad(a, a->pol.m.h2, Hd, 0, a->dpre, A, (long)cnt * A, Ga + (o.a_Wm - b0), A, hs, 2, Hd, A, cnt, st));
+  RC(wgrad(a, a->pol.m.h2, Hd, 0, a->dpre, A, (long)cnt * A, Ga + (o.a_Wm - b0), A, hs, hg, Hd, A, cnt, st));
   RC(head_bias_grad(a, cnt, Ga + (o.a_bm - b0), hs, st));
-  // dh2 = dmean W_mean^T + dlog_std W_logstd^T
-  RC(igrad_sum(a, a->dpre, A, (long)cnt * A, a->theta + o.a_Wm, A, hs, a->dh2, Hd, 2, cnt, Hd, A, st));
+  // dh2 = dmean W_mean^T + dlog_std W_logstd^T (no second term when the log-std has no Dense)
+  RC(igrad_sum(a, a->dpre, A, (long)cnt * A, a->theta + o.a_Wm, A, hs, a->dh2, Hd, hg, cnt, Hd, A, st));
   RC(dense_ln_tanh_bwd(a, a->dh2, Hd, 0, a->pol.m.h2, Hd, 0, a->pol.m.xh2, a->pol.m.rs2, a->theta + o.a_g2, 0, 1, cnt, Hd,
                        a->da2, a->dg2, Ga, o.a_g2 - b0, o.a_be2 - b0, o.a_b2 - b0, 0, st));
   RC(wgrad(a, a->pol.m.h1, Hd, 0, a->da2, Hd, 0, Ga + (o.a_w2 - b0), Hd, 0, 1, Hd, Hd, cnt, st));
@@ -1497,7 +1519,7 @@ int serl_agent_sample_actions(serl_agent* a, const uint8_t* dev_frames, const fl
   a->cur.frames = const_cast<uint8_t*>(dev_frames);   // (the SmallEncoder reads the pixels in encode_multi)
   const EncJob ej{a->theta, 0, nullptr, &a->encP, nullptr, nullptr};  // train=False: no dropout
   RC(encode_multi(a, &ej, 1, 0, n, st));
-  if (!dev_eps) {  // argmax -> mode = tanh(mean): zero noise
+  if (!dev_eps) {  // argmax -> mode = tanh(mean), or the mean itself without the squash: zero noise
     RC(fill(a->eps_buf[0], 0.f, (long)n * c.act_dim, st));
     dev_eps = a->eps_buf[0];
   }

@@ -304,8 +304,16 @@ __device__ __forceinline__ float ln_tanh_row(const LnFwdArgs& a, int row, int la
   return d;
 }
 
-// tanh-Gaussian head of rows [r0, r1) from the head GEMM's slabs (actor_critic_nets.py:179-272): one thread per (row, action)
-template <bool LIVE>
+// The raw standard deviation of a std parameterisation (actor_critic_nets.py:196-211) before the clip to [std_min, std_max]
+template <int MODE>
+__device__ __forceinline__ float policy_std_raw(float ls) {
+  return (MODE & kPolStdMask) == kPolSoftplus ? softplusf(ls) : expf(ls);
+}
+
+// Gaussian head of rows [r0, r1) from the head GEMM's slabs (actor_critic_nets.py:179-272): one thread per (row, action).
+// MODE (internal.h, kPol*): the std parameterisation, and whether the sample goes through tanh.  kPolUniform: the head GEMM has
+// no log-std group -- `ls` is the shared log_stds vector (bias_ls) alone and no second slab is read.
+template <bool LIVE, int MODE>
 __device__ __forceinline__ void policy_dist_rows(const PolicyDistArgs& v, int r0, int r1, int tid, int nthreads) {
   const int A = v.A, B = v.B;
   const __amdgpu_buffer_rsrc_t rs = rsrc_of(v.slabs);
@@ -315,7 +323,7 @@ __device__ __forceinline__ void policy_dist_rows(const PolicyDistArgs& v, int r0
     for (int sp = 0; sp < v.S; ++sp) {   // K-split slabs of the head GEMM: [mean | log_std][split][rows][ld]
       const long o0 = (long)sp * v.slab_stride + (long)b * v.slab_ld + j, o1 = o0 + (long)v.S * v.slab_stride;
       mean += LIVE ? ld1_sc1(rs, o0) : v.slabs[o0];
-      ls += LIVE ? ld1_sc1(rs, o1) : v.slabs[o1];
+      if ((MODE & kPolStdMask) != kPolUniform) ls += LIVE ? ld1_sc1(rs, o1) : v.slabs[o1];
     }
     float ep;
     if (v.eps) ep = v.eps[(long)b * A + j];
@@ -327,13 +335,15 @@ __device__ __forceinline__ void policy_dist_rows(const PolicyDistArgs& v, int r0
     }
     v.pre[(long)b * A + j] = mean;
     v.pre[((long)B + b) * A + j] = ls;
-    const float sd = fminf(fmaxf(expf(ls), v.std_min), v.std_max);
+    const float sd = fminf(fmaxf(policy_std_raw<MODE>(ls), v.std_min), v.std_max);
     const float u = mean + sd * ep;
-    v.act[(long)b * v.ld_act + j] = tanhf(u);
+    v.act[(long)b * v.ld_act + j] = (MODE & kPolNoTanh) ? u : tanhf(u);
     v.std_out[(long)b * A + j] = sd;
   }
 }
-// logp[b] = sum_j(-eps^2/2 - log std - log(2pi)/2) - sum_j 2(log2 - u - softplus(-2u)), in j order (one thread per row)
+// logp[b] = sum_j(-eps^2/2 - log std - log(2pi)/2) - sum_j 2(log2 - u - softplus(-2u)), in j order (one thread per row); the
+// second sum is the Tanh bijector's log-determinant, absent with kPolNoTanh
+template <int MODE>
 __device__ __forceinline__ void policy_logp_rows(const PolicyDistArgs& v, int r0, int r1, int tid, int nthreads) {
   const int A = v.A;
   for (int b = r0 + tid; b < r1; b += nthreads) {
@@ -341,18 +351,38 @@ __device__ __forceinline__ void policy_logp_rows(const PolicyDistArgs& v, int r0
     for (int j = 0; j < A; ++j) {
       const float e = v.eps ? v.eps[(long)b * A + j] : v.eps_out[(long)b * A + j];
       const float sd = v.std_out[(long)b * A + j];
-      const float u = v.pre[(long)b * A + j] + sd * e;
       lp += -0.5f * e * e - logf(sd) - 0.91893853320467274f;
-      lp -= 2.f * (0.69314718055994531f - u - softplusf(-2.f * u));
+      if (!(MODE & kPolNoTanh)) {
+        const float u = v.pre[(long)b * A + j] + sd * e;
+        lp -= 2.f * (0.69314718055994531f - u - softplusf(-2.f * u));
+      }
     }
     v.logp[b] = lp;
   }
 }
+template <int MODE>
+__device__ __forceinline__ void policy_tile(const PolicyDistArgs& v, int r0, int r1, int tid) {
+  policy_dist_rows<true, MODE>(v, r0, r1, tid, 256);
+  __syncthreads();   // (this workgroup's own global writes of pre / std / eps, read back below)
+  policy_logp_rows<MODE>(v, r0, r1, tid, 256);
+}
+// X(MODE) for the compile-time constant equal to `mode`; `bad` for a value that is no mode
+#define SERL_POLICY_MODE_SWITCH(mode, X, bad)                                  \
+  switch (mode) {                                                              \
+    case kPolExp: X(kPolExp); break;                                           \
+    case kPolSoftplus: X(kPolSoftplus); break;                                 \
+    case kPolUniform: X(kPolUniform); break;                                   \
+    case kPolExp | kPolNoTanh: X(kPolExp | kPolNoTanh); break;                 \
+    case kPolSoftplus | kPolNoTanh: X(kPolSoftplus | kPolNoTanh); break;       \
+    case kPolUniform | kPolNoTanh: X(kPolUniform | kPolNoTanh); break;         \
+    default: bad;                                                              \
+  }
 
 // the epilogue proper; `lds` = the kernel's operand LDS (>= kEpiScratch floats + 1 int), idle after the K loop.
 // (A LayerNorm + tanh reducer -- the last arriver of a 64-row tile normalising its rows -- existed in round 4: bit-identical, and
 // slower in every schedule than the separate LayerNorm launch that spreads the rows over the chip; removed, numbers in
 // profiles/README.md.)
+template <bool ALT>
 __device__ __forceinline__ void gemm_epilogue(const GemmDesc& g, const f32x16& acc, float* C, int z, int batch, int m0, int n0,
                                               float* lds, int tid) {
   store_tile_sc1(C, g.ldc, m0, n0, acc, lds, tid);
@@ -376,9 +406,15 @@ __device__ __forceinline__ void gemm_epilogue(const GemmDesc& g, const f32x16& a
   } else {   // kEpiPolicy
     if (!arrive_is_last(g.ctr + blockIdx.y, g.nbatch * g.splitk * tiles_n, flag)) return;
     const int r_end = min(m0 + kGBM, g.M);
-    policy_dist_rows<true>(g.pd, m0, r_end, tid, 256);
-    __syncthreads();   // (this workgroup's own global writes of pre / std / eps, read back below)
-    policy_logp_rows(g.pd, m0, r_end, tid, 256);
+    // ALT: the instantiations gemm_f32_multi launches for a head of another distribution than kPolExp; every other kernel holds
+    // the kPolExp rows alone, the code it always held
+    if (!ALT) {
+      policy_tile<kPolExp>(g.pd, m0, r_end, tid);
+    } else {
+#define SERL_X(M) policy_tile<M>(g.pd, m0, r_end, tid)
+      SERL_POLICY_MODE_SWITCH(g.pd.mode, SERL_X, break)
+#undef SERL_X
+    }
     if (blockIdx.y == 0 && tid == 0 && g.pd.alpha_out) g.pd.alpha_out[0] = softplusf(g.pd.lam[0]);
   }
 }
@@ -391,7 +427,7 @@ struct GemmMulti {
   int n;
 };
 
-template <bool A_KFAST, bool B_KFAST>
+template <bool A_KFAST, bool B_KFAST, bool ALT = false>
 __global__ __launch_bounds__(256) void gemm_f32_kernel(GemmMulti mm) {
   static_assert(2 * kGTile >= kEpiScratch + 4, "the epilogue's transpose scratch lives in the operand LDS");
   __shared__ __attribute__((aligned(16))) float ABf[2 * kGTile];
@@ -436,7 +472,7 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(GemmMulti mm) {
       __syncthreads();
     }
   }
-  if (g.epi) { gemm_epilogue(g, acc, C, z, batch, m0, n0, As, tid); return; }
+  if (g.epi) { gemm_epilogue<ALT>(g, acc, C, z, batch, m0, n0, As, tid); return; }
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
     const int m = m0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
@@ -663,7 +699,7 @@ struct XLoader {
 // (131 KB) conv workgroups instead of waiting for one of them to retire and taking its place.
 // GATHER: the SmallEncoder's implicit-GEMM operand (GemmDesc::gtab) is compiled in -- a separate instantiation, because a
 // run-time "gather or not" inside the chunk loop makes every loaded value a phi and hipcc then waits right behind each load
-template <bool A_KFAST, bool B_KFAST, int BK, bool GATHER = false>
+template <bool A_KFAST, bool B_KFAST, int BK, bool GATHER = false, bool ALT = false>
 __global__ __launch_bounds__(256) void gemm_bf16x3_kernel(GemmMulti mm) {
   constexpr int kPlane = kGBM * BK * 2;
   static_assert(6 * kPlane >= (kEpiScratch + 4) * 4, "the epilogue's transpose scratch lives in the operand LDS");
@@ -731,7 +767,7 @@ __global__ __launch_bounds__(256) void gemm_bf16x3_kernel(GemmMulti mm) {
       }
     }
   }
-  if (g.epi) { gemm_epilogue(g, acc, C, z, batch, m0, n0, reinterpret_cast<float*>(AB), tid); return; }
+  if (g.epi) { gemm_epilogue<ALT>(g, acc, C, z, batch, m0, n0, reinterpret_cast<float*>(AB), tid); return; }
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
     const int m = m0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
@@ -814,6 +850,18 @@ int gemm_f32_multi(const GemmDesc* gs, int n, hipStream_t stream) {
   bool any_epi = false;
   for (int i = 0; i < n; ++i) any_epi = any_epi || gs[i].epi != kEpiNone;
   SERL_REQUIRE(!any_epi || vec, "epilogue GEMMs need a vector layout");
+  // a policy head of another distribution than kPolExp: its own instantiation (the head GEMM's operand layout), see gemm_epilogue
+  bool alt = false;
+  for (int i = 0; i < n; ++i) alt = alt || (gs[i].epi == kEpiPolicy && gs[i].pd.mode != kPolExp);
+  if (alt) {
+    for (int i = 0; i < n; ++i)
+      SERL_REQUIRE(gs[i].epi == kEpiPolicy && gs[i].pd.mode == gs[0].pd.mode && !gs[i].gtab, "a policy-head launch mixes distributions or kinds of GEMM");
+    SERL_REQUIRE(a_k && b_n, "the policy head's GEMM reads row-major activations and a row-major kernel");
+    if (!exact) SERL_LAUNCH_CHAIN((gemm_bf16x3_kernel<true, false, 16, false, true>), grid, dim3(256), 0, stream, mm);
+    else SERL_LAUNCH_CHAIN((gemm_f32_kernel<true, false, true>), grid, dim3(256), 0, stream, mm);
+    SERL_HIP(hipGetLastError());
+    return SERL_OK;
+  }
   if (vec && (!exact || gather)) {   // BK = 16 (12 KB of LDS); BK = 32 (24 KB) was measured 30 us per step slower next to the trunk pass
     bool any_tab = false;
     for (int i = 0; i < n; ++i) any_tab = any_tab || gs[i].gtab != nullptr;
@@ -1608,11 +1656,13 @@ int critic_loss(const float* qt, const float* q, const float* reward, const floa
 }
 
 // =============================================================================================
-// tanh-Gaussian policy head (actor_critic_nets.py:179-272, distrax MultivariateNormalDiag + Tanh)
+// Gaussian policy head (actor_critic_nets.py:179-272, distrax MultivariateNormalDiag [+ Tanh])
 //   std = clip(exp(log_std), std_min, std_max); u = mean + std*eps; a = tanh(u)
 //   logp = sum_j(-eps^2/2 - log std - log(2pi)/2) - sum_j 2(log2 - u - softplus(-2u))
-// pre: [2][B][A] (mean slab, log_std slab; biases already added)
+// pre: [2][B][A] (mean slab, log_std slab; biases already added).  MODE: see policy_dist_rows (kPolSoftplus: std from
+// softplus; kPolUniform: log_std = bias_ls for every row, one slab group; kPolNoTanh: a = u and no second sum)
 // =============================================================================================
+template <int MODE>
 __global__ void policy_dist_fwd_kernel(Multi<PolicyDistArgs> mv, int B, int A, float std_min, float std_max) {
   const PolicyDistArgs& v = mv.v[blockIdx.x];  // one workgroup per instance
   __shared__ float red[256];
@@ -1623,17 +1673,17 @@ __global__ void policy_dist_fwd_kernel(Multi<PolicyDistArgs> mv, int B, int A, f
       float mean = v.bias_mean[j], ls = v.bias_ls[j];
       for (int sp = 0; sp < v.S; ++sp) {  // K-split slabs of the head GEMM: [mean | log_std][split][B][A]
         mean += v.slabs[((long)sp * B + b) * A + j];
-        ls += v.slabs[(((long)v.S + sp) * B + b) * A + j];
+        if ((MODE & kPolStdMask) != kPolUniform) ls += v.slabs[(((long)v.S + sp) * B + b) * A + j];
       }
       const float e = v.eps[(long)b * A + j];
       v.pre[(long)b * A + j] = mean;
       v.pre[((long)B + b) * A + j] = ls;
-      const float sd = fminf(fmaxf(expf(ls), std_min), std_max);
+      const float sd = fminf(fmaxf(policy_std_raw<MODE>(ls), std_min), std_max);
       const float u = mean + sd * e;
-      v.act[(long)b * v.ld_act + j] = tanhf(u);
+      v.act[(long)b * v.ld_act + j] = (MODE & kPolNoTanh) ? u : tanhf(u);
       v.std_out[(long)b * A + j] = sd;
       lp += -0.5f * e * e - logf(sd) - 0.91893853320467274f;
-      lp -= 2.f * (0.69314718055994531f - u - softplusf(-2.f * u));
+      if (!(MODE & kPolNoTanh)) lp -= 2.f * (0.69314718055994531f - u - softplusf(-2.f * u));
     }
     v.logp[b] = lp;
     local += lp;
@@ -1651,8 +1701,13 @@ __global__ void policy_dist_fwd_kernel(Multi<PolicyDistArgs> mv, int B, int A, f
 int policy_dist_fwd_multi(const PolicyDistArgs* vs, int n, int B, int A, float std_min, float std_max, hipStream_t stream) {
   SERL_REQUIRE(n >= 1 && n <= kMaxMulti, "bad instance count %d", n);
   Multi<PolicyDistArgs> mv{};
-  for (int i = 0; i < n; ++i) mv.v[i] = vs[i];
-  SERL_LAUNCH_CHAIN(policy_dist_fwd_kernel, dim3(n), dim3(256), 0, stream, mv, B, A, std_min, std_max);
+  for (int i = 0; i < n; ++i) {
+    mv.v[i] = vs[i];
+    SERL_REQUIRE(vs[i].mode == vs[0].mode, "the policy heads of one launch share a distribution mode");
+  }
+#define SERL_X(M) SERL_LAUNCH_CHAIN(policy_dist_fwd_kernel<M>, dim3(n), dim3(256), 0, stream, mv, B, A, std_min, std_max)
+  SERL_POLICY_MODE_SWITCH(vs[0].mode, SERL_X, SERL_REQUIRE(false, "bad policy distribution mode %d", vs[0].mode))
+#undef SERL_X
   SERL_HIP(hipGetLastError());
   return SERL_OK;
 }
@@ -1682,6 +1737,10 @@ int proprio_fwd_multi(const ProprioArgs* vs, int n, int S, int rows, hipStream_t
 //   G_u = dL/da*(1-a^2) + c_lp*2a   (d logp/du = 2 tanh u);  dmean = G_u;
 //   dstd = G_u*eps - c_lp/std;  dlog_std = dstd*std if std_min < exp(ls) < std_max else 0
 // dpre: [2][B][A].  c_lp = dL/dlogp (device scalar *alpha times coef).
+// MODE (see policy_dist_rows): kPolNoTanh: G_u = dL/da; kPolSoftplus: dlog_std = dstd * sigmoid(ls) under the same gate on
+// softplus(ls); kPolUniform: ls is the shared log_stds vector (as the forward left it in pre) and the column sums of the second
+// slab -- the sums that make the log-std bias gradient -- are the gradient of log_stds.
+template <int MODE>
 __global__ void policy_dist_bwd_kernel(const float* da, long ld_da, const float* act, long ld_act,
                                        const float* pre, const float* stdv, const float* eps,
                                        const float* alpha, float coef, int B, int A, float std_min,
@@ -1707,21 +1766,29 @@ __global__ void policy_dist_bwd_kernel(const float* da, long ld_da, const float*
   if (e >= B * A) return;
   const int b = e / A, j = e - b * A;
   const float c_lp = alpha[0] * coef;
-  const float a = act[(long)b * ld_act + j];
-  const float gu = da[(long)b * ld_da + j] * (1.f - a * a) + c_lp * 2.f * a;
+  float gu = da[(long)b * ld_da + j];
+  if (!(MODE & kPolNoTanh)) {
+    const float a = act[(long)b * ld_act + j];
+    gu = gu * (1.f - a * a) + c_lp * 2.f * a;
+  }
   const float sd = stdv[e];
-  const float raw = expf(pre[((long)B + b) * A + j]);
+  const float ls = pre[((long)B + b) * A + j];
+  const float raw = policy_std_raw<MODE>(ls);
   const float dstd = gu * eps[e] - c_lp / sd;
   dpre[e] = gu;
-  dpre[(long)B * A + e] = (raw > std_min && raw < std_max) ? dstd * sd : 0.f;
+  const float draw = (MODE & kPolStdMask) == kPolSoftplus ? 1.f / (1.f + expf(-ls)) : sd;   // d raw / d ls (exp: raw == sd inside the clip)
+  dpre[(long)B * A + e] = (raw > std_min && raw < std_max) ? dstd * draw : 0.f;
 }
 
 int policy_dist_bwd(const float* da, long ld_da, const float* act, long ld_act, const float* pre,
                     const float* stdv, const float* eps, const float* alpha, float coef, int B, int A,
                     float std_min, float std_max, float* dpre, const float* q, int E, float* qmean_out,
-                    hipStream_t stream) {
-  SERL_LAUNCH_CHAIN(policy_dist_bwd_kernel, dim3(cdiv(B * A, 256) + 1), dim3(256), 0, stream, da, ld_da, act,
-                     ld_act, pre, stdv, eps, alpha, coef, B, A, std_min, std_max, dpre, q, E, qmean_out);
+                    hipStream_t stream, int mode) {
+#define SERL_X(M)                                                                                                            \
+  SERL_LAUNCH_CHAIN(policy_dist_bwd_kernel<M>, dim3(cdiv(B * A, 256) + 1), dim3(256), 0, stream, da, ld_da, act, ld_act, pre, \
+                    stdv, eps, alpha, coef, B, A, std_min, std_max, dpre, q, E, qmean_out)
+  SERL_POLICY_MODE_SWITCH(mode, SERL_X, SERL_REQUIRE(false, "bad policy distribution mode %d", mode))
+#undef SERL_X
   SERL_HIP(hipGetLastError());
   return SERL_OK;
 }

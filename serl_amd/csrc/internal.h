@@ -122,9 +122,12 @@ struct LnFwdArgs {
   long dot_gstride, dot_b_gstride;  // 0: one head shared by all groups (DrQ critic); else per-group heads (ensemblized Critic)
   int relu;              // 0: tanh (the MLPs / encoder heads); 1: ReLU (BinaryClassifier, reward_classifier.py:24-26)
 };
+// The policy distribution of an agent (serl_agent_create_policy's std_param / no_tanh) as the head kernels take it, a template parameter:
+// the std parameterisation in the low bits, kPolNoTanh on top.  kPolExp (0) is the tanh-Gaussian with std = exp(log_std).
+enum { kPolExp = 0, kPolSoftplus = 1, kPolUniform = 2, kPolStdMask = 3, kPolNoTanh = 4 };
 // tanh-Gaussian policy head: slabs = raw head GEMM outputs (mean, log_std); biases added here, result kept in `pre`
 struct PolicyDistArgs {
-  const float* slabs; int S;  // head GEMM output [mean | log_std][S K-splits][B][A]
+  const float* slabs; int S;  // head GEMM output [mean | log_std][S K-splits][B][A]; kPolUniform: [mean] alone, bias_ls = log_stds
   const float* bias_mean; const float* bias_ls; float* pre; const float* eps;
   float* act; long ld_act; float* logp; float* std_out; float* sum_logp;
   const float* lam; float* alpha_out;  // optional rider: alpha_out[0] = softplus(lam[0])
@@ -133,6 +136,7 @@ struct PolicyDistArgs {
   int B, A; float std_min, std_max; long slab_ld, slab_stride;
   // tf != 0 (and eps == nullptr): the draws are jax.random.normal(tf_key, (tf_rows, A))[tf_row0 + b][j] instead of the hash (jaxrng.h)
   int tf; uint32_t tf_key[2]; long tf_rows, tf_row0;
+  int mode;   // kPol*
 };
 
 // Epilogues of the update chain's GEMMs ("last-arriver" fusion, heads.hip): a launch boundary between a K-split GEMM and the

@@ -21,7 +21,7 @@ import msgpack
 import numpy as np
 
 from ..agents.core import TX_NAMES
-from ..agents.flax_tree import leaves_from_tree, theta_paths, trunk_owner, _trunk_paths
+from ..agents.flax_tree import leaves_from_tree, std_parameterization_of, theta_paths, trunk_owner, _trunk_paths
 
 _EXT_NDARRAY = 1
 
@@ -130,6 +130,17 @@ def _find_adam_state(node):
     return None
 
 
+STD_LEAVES = ("actor/logstd/kernel", "actor/logstd/bias", "actor/log_stds")
+
+
+def _absent(tree, path) -> bool:
+    for k in path:
+        if not isinstance(tree, dict) or k not in tree:
+            return True
+        tree = tree[k]
+    return False
+
+
 def load_state_dict(agent, sd: dict, restore_rng: bool = False):
     """Loads any of {params, target_params, opt_states, step} (flax-layout trees, e.g. a restored checkpoint or
     `agent.state.replace(...)` arguments) into the agent's HBM arena.  restore_rng=True also takes `state.rng` from `sd["rng"]`
@@ -143,14 +154,22 @@ def load_state_dict(agent, sd: dict, restore_rng: bool = False):
         return agent
     core, keys = agent.core, agent.image_keys
     etype = "small" if core.cfg.encoder_type == 1 else "resnet-pretrained"
-    tp = theta_paths(keys, encoder_type=etype)
+    tp = theta_paths(keys, encoder_type=etype, std_parameterization=std_parameterization_of(core))
     trunk = _trunk_paths() if (keys and etype != "small") else {}   # state-only / SmallEncoder agents have no frozen trunk
     todo = []      # (section, leaf, array): everything is sized against the agent's leaves before the first one is written
+
+    def leaves_of(tree):
+        # The policy's std leaves are the ones whose PRESENCE is geometry (std_parameterization "uniform": log_stds, else
+        # Dense_1): a tree of the other kind holds nothing at their paths, which the size check below reports as 0 elements
+        for leaf in STD_LEAVES:
+            if leaf in tp and _absent(tree, tp[leaf][0]):
+                yield leaf, np.zeros((0,), np.float32)
+        yield from leaves_from_tree({leaf: p for leaf, p in tp.items() if leaf not in STD_LEAVES or not _absent(tree, p[0])}, tree)
     for section in ("params", "target_params"):
         tree = sd.get(section)
         if tree is None:
             continue
-        todo += [(section, leaf, v) for leaf, v in leaves_from_tree(tp, tree)]
+        todo += [(section, leaf, v) for leaf, v in leaves_of(tree)]
         if trunk:
             # Where flax puts the ONE shared frozen trunk is derived from its adoption rule (first camera in sorted-key
             # order) and unverified against a real flax install: accept it under any camera, like
@@ -168,8 +187,8 @@ def load_state_dict(agent, sd: dict, restore_rng: bool = False):
                 raise KeyError(f"opt_states['{tx}'] holds no ScaleByAdamState (mu / nu)")
             for mom in ("mu", "nu"):
                 # leaves outside the optimizer's support are exact zeros; the C ABI accepts (and checks) them
-                todo += [(f"opt/{tx}/{mom}", leaf, np.asarray(v, np.float32)) for leaf, v in leaves_from_tree(tp, adam[mom])]
-    # A state saved by an agent of another geometry (MLP width, ensemble, action or state dimension) is refused whole: a leaf
+                todo += [(f"opt/{tx}/{mom}", leaf, np.asarray(v, np.float32)) for leaf, v in leaves_of(adam[mom])]
+    # A state saved by an agent of another geometry (MLP width, ensemble, action or state dimension, std leaves) is refused whole: a leaf
     # that does not depend on the differing dimension would otherwise be overwritten before the first mismatch is met
     counts = getattr(core, "leaves", {})
     for section, leaf, v in todo:

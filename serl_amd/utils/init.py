@@ -72,10 +72,37 @@ def mlp_hidden_width(critic_network_kwargs=None, policy_network_kwargs=None) -> 
     return widths[0]
 
 
+STD_PARAMETERIZATIONS = ("exp", "softplus", "uniform")   # serl_agent_create_policy's std_param (actor_critic_nets.py:196-211); "fixed" is not served
+
+
+def policy_mode(policy_kwargs=None):
+    """(std_parameterization, tanh_squash_distribution) of the reference's `policy_kwargs`.  An absent key means what
+    utils/launcher.py writes down ("exp", True), as it always did here -- also for policy_kwargs=None, where create_drq's own
+    default dict would say "uniform": pass it to get it.  Anything the head kernels do not serve raises NotImplementedError."""
+    pk = policy_kwargs or {}
+    std = pk.get("std_parameterization", "exp")
+    if std not in STD_PARAMETERIZATIONS:
+        raise NotImplementedError(f"std_parameterization={std!r}: served are {STD_PARAMETERIZATIONS} (no 'fixed' / fixed_std)")
+    if pk.get("fixed_std") is not None:
+        raise NotImplementedError("policy_kwargs['fixed_std'] is not served")
+    return std, bool(pk.get("tanh_squash_distribution", True))
+
+
+def _policy_std_shapes(Hd, A, std_parameterization):
+    """The leaves behind the policy's mean head: Dense_1 (log-std or softplus pre-activation), or with "uniform" the one
+    `log_stds` vector shared by all rows (actor_critic_nets.py:199-201)."""
+    if std_parameterization not in STD_PARAMETERIZATIONS:
+        raise NotImplementedError(f"std_parameterization={std_parameterization!r}")
+    if std_parameterization == "uniform":
+        return {"actor/log_stds": (A,)}
+    return {"actor/logstd/kernel": (Hd, A), "actor/logstd/bias": (A,)}
+
+
 def theta_shapes(n_cam, H, W, S, A, ensemble=10, hidden=256, bottleneck=256, sle_features=8, proprio_dim=64,
-                 encoder_type="resnet-pretrained", num_stack=1):
+                 encoder_type="resnet-pretrained", num_stack=1, std_parameterization="exp"):
     """S: the proprio Dense's input width -- T * S for a stack of T = num_stack frames, which EncodingWrapper folds into the
-    channels ("B T H W C -> B H W (T C)", common/encoding.py:39-44): the SmallEncoder's first kernel is then (3,3,3T,32)."""
+    channels ("B T H W C -> B H W (T C)", common/encoding.py:39-44): the SmallEncoder's first kernel is then (3,3,3T,32).
+    std_parameterization="uniform": actor/log_stds (A,) in place of actor/logstd/{kernel,bias}."""
     if n_cam == 0:   # state-only SAC (SACAgent.create_states, sac.py:486-542): no encoder, per-member Q heads
         N, Hd = ensemble, hidden
         return {
@@ -85,7 +112,7 @@ def theta_shapes(n_cam, H, W, S, A, ensemble=10, hidden=256, bottleneck=256, sle
             "actor/w1": (S, Hd), "actor/b1": (Hd,), "actor/ln1/scale": (Hd,), "actor/ln1/bias": (Hd,),
             "actor/w2": (Hd, Hd), "actor/b2": (Hd,), "actor/ln2/scale": (Hd,), "actor/ln2/bias": (Hd,),
             "actor/mean/kernel": (Hd, A), "actor/mean/bias": (A,),
-            "actor/logstd/kernel": (Hd, A), "actor/logstd/bias": (A,),
+            **_policy_std_shapes(Hd, A, std_parameterization),
             "temp/lagrange": (),
         }
     fh, fw = feat_hw(H, W)
@@ -113,7 +140,7 @@ def theta_shapes(n_cam, H, W, S, A, ensemble=10, hidden=256, bottleneck=256, sle
         "actor/w1": (E, Hd), "actor/b1": (Hd,), "actor/ln1/scale": (Hd,), "actor/ln1/bias": (Hd,),
         "actor/w2": (Hd, Hd), "actor/b2": (Hd,), "actor/ln2/scale": (Hd,), "actor/ln2/bias": (Hd,),
         "actor/mean/kernel": (Hd, A), "actor/mean/bias": (A,),
-        "actor/logstd/kernel": (Hd, A), "actor/logstd/bias": (A,),
+        **_policy_std_shapes(Hd, A, std_parameterization),
         "temp/lagrange": (),
     })
     return sh

@@ -73,8 +73,8 @@ def _counter(pname):
 def _init_of(name, shape):
     if name.endswith("/scale"):
         return ONES
-    if name.endswith("bias") or name.startswith("critic/b") or name.startswith("actor/b"):
-        return ZEROS
+    if name.endswith("bias") or name.startswith("critic/b") or name.startswith("actor/b") or name == "actor/log_stds":
+        return ZEROS    # (log_stds: nn.initializers.zeros, actor_critic_nets.py:199-201 -- no draw, no key consumed)
     if name == "temp/lagrange":
         return LAGRANGE
     if name.endswith("/sle") or "/conv" in name or (name.startswith("enc/") and "proprio" not in name) or name.startswith("head/"):
@@ -83,13 +83,15 @@ def _init_of(name, shape):
 
 
 def theta_leaves(image_keys: Sequence[str], H, W, S, A, ensemble=10, encoder_type="resnet-pretrained", num_stack=1,
-                 hidden=256) -> List[Leaf]:
+                 hidden=256, std_parameterization="exp") -> List[Leaf]:
     """The trainable leaves of DrQAgent.create_drq (image_keys non-empty) or SACAgent.create_states (image_keys empty);
-    hidden: the MLPs' width (hidden_dims=[hidden, hidden])."""
+    hidden: the MLPs' width (hidden_dims=[hidden, hidden]).  std_parameterization="uniform": the zero-initialised log_stds
+    vector in place of Dense_1; every other leaf keeps its key (a flax key depends on the module's path and the scope's own
+    counter, not on its siblings), so the rest of the tree is bit-identical to the "exp" agent's."""
     from ..agents.flax_tree import theta_paths
     shapes = theta_shapes(len(image_keys), H, W, S, A, ensemble=ensemble, hidden=hidden, encoder_type=encoder_type,
-                          num_stack=num_stack)
-    paths = theta_paths(tuple(image_keys), encoder_type=encoder_type)
+                          num_stack=num_stack, std_parameterization=std_parameterization)
+    paths = theta_paths(tuple(image_keys), encoder_type=encoder_type, std_parameterization=std_parameterization)
     # the vmapped module: DrQ ensemblizes the critic's MLP (drq.py:206-209), state SAC the whole Critic (sac.py:516-517)
     vm = ("modules_critic", "network") if image_keys else ("modules_critic",)
     out = []
@@ -214,11 +216,12 @@ def draw_flat(leaves: Sequence[Leaf], init_rng, device: Optional[int] = 0, tempe
 
 
 def theta_reference(image_keys, H, W, S, A, rng, ensemble=10, encoder_type="resnet-pretrained", temperature_init=1.0,
-                    device: Optional[int] = 0, num_stack=1, hidden=256) -> Dict[str, np.ndarray]:
+                    device: Optional[int] = 0, num_stack=1, hidden=256, std_parameterization="exp") -> Dict[str, np.ndarray]:
     """init_theta's leaves as the reference's DrQ / state-SAC create path draws them from `rng` (drq.py:69, sac.py:368).
     S is the flattened proprio width T * S of a stack of T = num_stack frames; the widened leaves draw with their real fan-in.
     hidden: the MLPs' width; its leaves draw with the fans of that width."""
-    return draw_flat(theta_leaves(image_keys, H, W, S, A, ensemble, encoder_type, num_stack, hidden), init_rng_of(reference_key(rng)),
+    return draw_flat(theta_leaves(image_keys, H, W, S, A, ensemble, encoder_type, num_stack, hidden, std_parameterization),
+                     init_rng_of(reference_key(rng)),
                      device, temperature_init)
 
 

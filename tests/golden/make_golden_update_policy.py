@@ -1,0 +1,133 @@
+"""Generates the policy-distribution fixtures: the REFERENCE's own SACAgent / DrQAgent (serl_launcher/agents/continuous/{sac,drq}.py,
+networks/actor_critic_nets.py:167-227), imported unmodified from its checkout and run under the stand-ins of oracle/jaxshim in fp64,
+with a policy distribution other than the launcher's ("exp" + tanh).  Run in the build container (needs the reference):
+    python tests/golden/make_golden_update_policy.py [name ...]
+
+The launcher factories write their own policy_kwargs into create_states / create_drq (utils/launcher.py:50-116), so the two create
+functions are wrapped AT RUN TIME, as make_golden_update_widths.py wraps them for hidden_dims: the wrapper overrides
+std_parameterization / tanh_squash_distribution in the `policy_kwargs` the factory passes.  For "uniform" the run's leaf table
+(oracle.ref_update_runner.theta_flax_paths, looked up at run time) is replaced by tests/policy_modes.flax_paths: no
+modules_actor/Dense_1, and ("modules_actor", "log_stds") instead.  Nothing under oracle/ changes.
+
+  policy_update_sac_state_{softplus,gauss,uniform,uniform_gauss}.npz   S = 10, A = 5, 72 rows; high_utd 2, update, high_utd 1
+  policy_update_drq_uniform.npz                                        one camera 64x64, S = 5, A = 3, 6 rows; critics, high_utd 2
+  policy_trained_sac_state_{softplus,uniform}.npz                      the state-only schedule from policy_modes.mode_theta's
+      "trained" leaves: one std column below std_min in every row, one above std_max in every row, the rest inside
+
+Every file records under meta["policy"] the distribution, the regime and what the reference's parameter tree holds in place of the
+log-std leaves.  For the trained files, SACAgent.forward_policy is wrapped to read `.stddev()` of every distribution the update code
+builds: per evaluation and action column the fraction of rows clipped low / high is asserted (at least one column low in all rows,
+one high in all rows, two unclipped in all rows) and stored as policy_clip_low / policy_clip_high [evaluation][A].
+
+The file names do not start with "update_": tests/test_reference_update.py and tests/test_golden_update_gpu.py run every
+update_*.npz through the launcher's distribution.  tests/test_policy_modes_{cpu,gpu}.py read these files.
+"""
+import contextlib
+import json
+import os
+import sys
+
+import numpy as np
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(os.path.dirname(HERE))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(HERE))
+from oracle import golden_update as G  # noqa: E402
+from oracle import ref_update_runner as RR  # noqa: E402
+from oracle import ref_update_shim as R  # noqa: E402
+import policy_modes as PM  # noqa: E402
+
+ONLY = [a for a in sys.argv[1:] if not a.startswith("-")]
+
+
+@contextlib.contextmanager
+def reference_policy(cfg, std, squash, stddevs):
+    """create_states / create_drq with this distribution, the run's leaf table for it, and every forward_policy's stddev recorded"""
+    R.install(True)
+    from jax._core import raw
+    from serl_launcher.agents.continuous.drq import DrQAgent
+    from serl_launcher.agents.continuous.sac import SACAgent
+    saved = []
+    for target, name in ((SACAgent, "create_states"), (DrQAgent, "create_drq")):
+        cm = target.__dict__[name]
+        saved.append((target, name, cm))
+
+        def patched(cls, *a, _orig=cm.__func__, **k):
+            assert "policy_kwargs" in k, "the factory no longer passes policy_kwargs by keyword"
+            k["policy_kwargs"] = {**k["policy_kwargs"], "std_parameterization": std, "tanh_squash_distribution": squash}
+            return _orig(cls, *a, **k)
+        setattr(target, name, classmethod(patched))
+    fp = SACAgent.__dict__["forward_policy"]
+    saved.append((SACAgent, "forward_policy", fp))
+
+    def forward_policy(self, *a, _orig=fp, **k):
+        dist = _orig(self, *a, **k)
+        base = dist.distribution if squash else dist     # (the tanh distribution's own stddev() is tanh of the Gaussian's)
+        stddevs.append(np.asarray(raw(base.stddev()).detach().cpu().numpy(), np.float64))
+        return dist
+    SACAgent.forward_policy = forward_policy
+    paths = RR.theta_flax_paths
+    RR.theta_flax_paths = lambda c: PM.flax_paths(c, std)
+    try:
+        yield
+    finally:
+        RR.theta_flax_paths = paths
+        for target, name, cm in saved:
+            setattr(target, name, cm)
+
+
+def check_tree(tree, std):
+    """the mode took effect: the reference's own parameter tree says so -> what it holds behind the mean head"""
+    actor = tree["modules_actor"]
+    if std == "uniform":
+        assert "log_stds" in actor and "Dense_1" not in actor, sorted(actor)
+        assert tuple(actor["log_stds"]) == tuple(actor["Dense_0"]["bias"]), actor["log_stds"]
+        return "log_stds"
+    assert "Dense_1" in actor and "log_stds" not in actor, sorted(actor)
+    return "Dense_1"
+
+
+def clip_fractions(cfg, stddevs):
+    """-> (low, high) [evaluation][A]: fraction of rows whose std sits on std_min / std_max; asserts the fixture's condition"""
+    low = np.stack([(s == cfg.std_min).mean(axis=0) for s in stddevs])
+    high = np.stack([(s == cfg.std_max).mean(axis=0) for s in stddevs])
+    for i, (lo, hi) in enumerate(zip(low, high)):
+        assert (lo == 1.0).sum() >= 1, ("no column clipped low in all rows", i, lo)
+        assert (hi == 1.0).sum() >= 1, ("no column clipped high in all rows", i, hi)
+        assert ((lo == 0.0) & (hi == 0.0)).sum() >= 2, ("fewer than two columns unclipped in all rows", i, lo, hi)
+    return low, high
+
+
+def main():
+    for name, (cfg, B, sched, (std, squash), regime, n_sample) in PM.GOLDEN.items():
+        if ONLY and name not in ONLY:
+            continue
+        os.environ.pop("SERL_JAXSHIM_PRNG", None)
+        G.N_SAMPLE = n_sample
+        stddevs = []
+        with reference_policy(cfg, std, squash, stddevs):
+            res = RR.run_reference(cfg, B, sched, PM.PARAM_SEED, PM.BATCH_SEED,
+                                   theta_transform=lambda th, c: PM.mode_theta(th, c, std, regime))
+        holds = check_tree(res["final"]["param_tree"], std)
+        assert set(res["final"]["params"]) == set(PM.leaf_names(cfg, std))
+        assert stddevs and all(s.shape[-1] == cfg.A for s in stddevs)
+        res["prng"] = "philox"
+        rec = G.pack(res, PM.PARAM_SEED, PM.BATCH_SEED)
+        meta = json.loads(str(rec["meta"]))
+        meta["policy"] = {"std_parameterization": std, "tanh_squash_distribution": squash, "regime": regime, "std_leaves": holds,
+                          "transform": "policy_modes.mode_theta", "log_stds_seed": PM.LOG_STDS_SEED, "clip_cycle": list(PM.CLIP_CYCLE),
+                          "policy_evaluations": len(stddevs)}
+        if regime == "trained":
+            rec["policy_clip_low"], rec["policy_clip_high"] = clip_fractions(cfg, stddevs)
+        rec["meta"] = np.array(json.dumps(meta))
+        path = PM.golden_path(name)
+        np.savez_compressed(path, policy_n_sample=np.int64(n_sample), **rec)
+        size = os.path.getsize(path)
+        assert size < 1 << 20, (path, size)
+        print(name, "->", path, f"{size / 1e6:.2f} MB", "final step", res["final"]["step"],
+              {k: round(v, 6) for k, v in res["steps"][-1]["info"].items()})
+
+
+if __name__ == "__main__":
+    main()
