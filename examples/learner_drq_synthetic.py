@@ -61,19 +61,21 @@ def main():
     ap.add_argument("--resume", action="store_true", help="continue from the latest run state in --run_dir")
     ap.add_argument("--hidden", type=int, default=256,
                     help="width h of the critic's and the policy's MLPs (hidden_dims=[h, h]): a multiple of 64 in [64, 1024]")
+    ap.add_argument("--activation", choices=["tanh", "relu", "swish"], default="tanh",
+                    help="activation of the critic's and the policy's MLPs (the launcher writes tanh)")
     a = ap.parse_args()
     assert a.run_dir or not (a.save_every or a.resume), "--save_every / --resume need --run_dir"
 
     env = _Env()
     sample_obs = {"front": np.zeros((1, H, W, 3), np.uint8), "wrist": np.zeros((1, H, W, 3), np.uint8),
                   "state": np.zeros((1, S), np.float32)}
-    if a.hidden == 256:
+    if a.hidden == 256 and a.activation == "tanh":
         agent = make_drq_agent(seed=42, sample_obs=sample_obs, sample_action=np.zeros((A,), np.float32), image_keys=KEYS,
                                encoder_type="resnet-pretrained", batch_size=a.batch_size)
     else:
-        # make_drq_agent has no width argument (launcher.py:79-116 writes hidden_dims into the call): another width goes to
-        # create_drq as it does in the reference, with the launcher's other hyper-parameters
-        mlp = {"activations": "tanh", "use_layer_norm": True, "hidden_dims": [a.hidden, a.hidden]}
+        # make_drq_agent has no width or activation argument (launcher.py:79-116 writes hidden_dims and nn.tanh into the call):
+        # other ones go to create_drq as they do in the reference, with the launcher's other hyper-parameters
+        mlp = {"activations": a.activation, "use_layer_norm": True, "hidden_dims": [a.hidden, a.hidden]}
         agent = DrQAgent.create_drq(
             42, sample_obs, np.zeros((A,), np.float32), encoder_type="resnet-pretrained", use_proprio=True, image_keys=KEYS,
             policy_kwargs={"tanh_squash_distribution": True, "std_parameterization": "exp", "std_min": 1e-5, "std_max": 5},

@@ -262,6 +262,9 @@ typedef struct serl_agent_cfg {
 #define SERL_STD_EXP 0
 #define SERL_STD_SOFTPLUS 1
 #define SERL_STD_UNIFORM 2
+#define SERL_ACT_TANH 0
+#define SERL_ACT_RELU 1
+#define SERL_ACT_SWISH 2
 #define SERL_ENCODER_RESNET_PRETRAINED 0
 #define SERL_ENCODER_SMALL 1
 #define SERL_TX_ACTOR 0
@@ -279,6 +282,15 @@ int serl_agent_create(const serl_agent_cfg* cfg, serl_agent** out);
  *   no_tanh:   0 = distrax Tanh bijector on the Gaussian; 1 = tanh_squash_distribution=False: the plain Gaussian -- actions are
  *              unbounded, log pi has no log-det term, and the mode is the mean */
 int serl_agent_create_policy(const serl_agent_cfg* cfg, int std_param, int no_tanh, serl_agent** out);
+/* serl_agent_create_policy with another activation in the critic's and the policy's MLP (networks/mlp.py:19-31: `activations`
+ * behind every LayerNorm; the two networks take theirs from separate kwargs, so the codes are independent).  serl_agent_create_policy
+ * is this function with (SERL_ACT_TANH, SERL_ACT_TANH), what utils/launcher.py writes.  Any other code is SERL_ERR_INVALID, the
+ * message naming the served set.  An activation owns no parameter: leaves, optimizer state and checkpoints are the same for all.
+ * The encoder's bottleneck and proprio rows keep tanh (resnet_v1.py:371-374, encoding.py:66-68).
+ *   SERL_ACT_TANH   y = tanh(p)
+ *   SERL_ACT_RELU   y = max(p, 0), gradient 0 at p = 0 (jax.nn.relu)
+ *   SERL_ACT_SWISH  y = p * sigmoid(p) (flax.linen.swish = silu, mlp.py's own default) */
+int serl_agent_create_mlp(const serl_agent_cfg* cfg, int std_param, int no_tanh, int critic_act, int policy_act, serl_agent** out);
 int serl_agent_destroy(serl_agent* a);
 
 /* Parameter tree access (flat leaf names, see DESIGN.md "parameter arena"; the Python shim maps

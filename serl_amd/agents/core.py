@@ -11,7 +11,7 @@ from .. import _lib
 from .._handle import Handle
 from .._lib_agent import APPLY_ACTOR_TEMP, APPLY_CRITIC, NET_BITS, TX_INDEX, SerlAgentCfg, SerlInfo, SerlNoise  # noqa: F401
 
-from ..utils.init import STD_PARAMETERIZATIONS
+from ..utils.init import MLP_ACTIVATIONS, STD_PARAMETERIZATIONS
 
 TX_NAMES = ("actor", "critic", "temperature")
 
@@ -24,11 +24,12 @@ class AgentCore(Handle):
                  tau=0.005, lr=3e-4, dropout=0.1, std_min=1e-5, std_max=5.0, target_entropy=None,
                  seed=0, temp_warmup_steps=-1, optimizers=None, encoder_type="resnet-pretrained",
                  critic_subsample_size=2, backup_entropy=False, num_stack=1, std_parameterization="exp",
-                 tanh_squash_distribution=True):
+                 tanh_squash_distribution=True, critic_activation="tanh", policy_activation="tanh"):
         """optimizers: optional {"actor"|"critic"|"temperature": make_optimizer kwargs (common/optimizers.py:6-13:
         learning_rate, warmup_steps, cosine_decay_steps, weight_decay, clip_grad_norm)} overriding lr / warmup_steps.
         num_stack: T, frames per observation (SmallEncoder only); state_dim is then the flattened width T * S.
-        std_parameterization / tanh_squash_distribution: the policy distribution (Policy's kwargs of the same names)."""
+        std_parameterization / tanh_squash_distribution: the policy distribution (Policy's kwargs of the same names).
+        critic_activation / policy_activation: one of MLP_ACTIVATIONS each (MLP's `activations`, utils.init.mlp_activations)."""
         if target_entropy is None:
             target_entropy = -act_dim / 2
         self.cfg = SerlAgentCfg(device, n_cam, H, W, state_dim, act_dim, batch, ensemble, hidden,
@@ -45,6 +46,9 @@ class AgentCore(Handle):
         self.std_parameterization = std_parameterization
         self.tanh_squash_distribution = bool(tanh_squash_distribution)
         self._std_param = STD_PARAMETERIZATIONS.index(std_parameterization)
+        # ... nor are the MLP activations: serl_agent_create_mlp
+        self.critic_activation, self.policy_activation = critic_activation, policy_activation
+        self._acts = (MLP_ACTIVATIONS.index(critic_activation), MLP_ACTIVATIONS.index(policy_activation))
         for name, kw in (optimizers or {}).items():
             i = TX_INDEX[name]
             bad = set(kw) - {"learning_rate", "warmup_steps", "cosine_decay_steps", "weight_decay", "clip_grad_norm"}
@@ -65,7 +69,8 @@ class AgentCore(Handle):
         self._keep = None
 
     def _create(self, cfg):
-        return self.L.serl_agent_create_policy(C.byref(cfg), self._std_param, 0 if self.tanh_squash_distribution else 1, C.byref(self._h))
+        return self.L.serl_agent_create_mlp(C.byref(cfg), self._std_param, 0 if self.tanh_squash_distribution else 1, *self._acts,
+                                            C.byref(self._h))
 
     # ---- parameters ------------------------------------------------------------------------
     @property

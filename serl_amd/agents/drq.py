@@ -174,7 +174,9 @@ class DrQAgent:
         """drq.py:104-242.  Only the configuration the reference's examples run is built natively:
         encoder_type="resnet-pretrained", use_proprio=True, REDQ subsample 2, tanh-squashed
         exp-parameterised policy, LayerNorm+tanh MLPs (utils/launcher.py:79-116) -- 256x256 there; critic_network_kwargs /
-        policy_network_kwargs may give hidden_dims=[h, h], h a multiple of 64 in [64, 1024], the same in both.
+        policy_network_kwargs may give hidden_dims=[h, h], h a multiple of 64 in [64, 1024], the same in both, and
+        activations "tanh" (when absent), "relu" or "swish" / "silu", by name or as a callable of that name, chosen per network
+        (mlp.py:19-31); other activations and a positive dropout_rate are refused.
         policy_kwargs: std_parameterization "exp", "softplus" or "uniform" (one trainable log_stds vector, no Dense_1) and
         tanh_squash_distribution True or False all run in the head kernels; "fixed" is refused.  A key that is absent, or
         policy_kwargs=None, means the launcher's value ("exp", True).
@@ -192,6 +194,7 @@ class DrQAgent:
         pk = policy_kwargs or {}
         std_param, squash = pinit.policy_mode(pk)
         hidden = pinit.mlp_hidden_width(critic_network_kwargs, policy_network_kwargs)
+        critic_act, policy_act = pinit.mlp_activations(critic_network_kwargs, policy_network_kwargs)
         seed = int(np.asarray(rng).reshape(-1)[-1]) if not isinstance(rng, int) else rng
         image_keys = tuple(image_keys)
         img = np.asarray(observations[image_keys[0]])
@@ -221,7 +224,8 @@ class DrQAgent:
                          std_max=pk.get("std_max", 10.0), target_entropy=target_entropy, seed=seed,
                          optimizers={k: {"warmup_steps": 0, **v} for k, v in opts.items()}, encoder_type=encoder_type,
                          critic_subsample_size=critic_subsample_size, backup_entropy=backup_entropy, num_stack=T,
-                         hidden=hidden, std_parameterization=std_param, tanh_squash_distribution=squash)
+                         hidden=hidden, std_parameterization=std_param, tanh_squash_distribution=squash,
+                         critic_activation=critic_act, policy_activation=policy_act)
         if init_ref.check_param_init(param_init):
             theta = init_ref.theta_reference(image_keys, H, W, S, A, rng, ensemble=critic_ensemble_size, encoder_type=encoder_type,
                                              temperature_init=temperature_init, device=device, num_stack=T, hidden=hidden,
@@ -236,7 +240,8 @@ class DrQAgent:
             core.load_flat(sec, trunk)
         config = dict(critic_ensemble_size=critic_ensemble_size, critic_subsample_size=critic_subsample_size,
                       discount=discount, soft_target_update_rate=soft_target_update_rate,
-                      target_entropy=target_entropy, backup_entropy=backup_entropy, image_keys=image_keys)
+                      target_entropy=target_entropy, backup_entropy=backup_entropy, image_keys=image_keys,
+                      critic_activation=critic_act, policy_activation=policy_act)
         agent = cls(core, image_keys, config, seed)
         agent._opts = {k: {"warmup_steps": 0, **v} for k, v in opts.items()}
         if param_init == "reference":

@@ -75,6 +75,7 @@ struct serl_agent {
   int std_param = SERL_STD_EXP, no_tanh = 0;   // the arguments of serl_agent_create_policy
   int pol_mode = kPolExp;            // ... as the head kernels take them
   int head_groups = 2;               // Dense layers of the policy head: (mean, log_std), or the mean alone with kPolUniform
+  int critic_act = kActTanh, policy_act = kActTanh;   // serl_agent_create_mlp: the activation of each MLP's two LayerNorm rows (kAct*)
   SmallWorkspace sws{};
   Offs o{};
   std::vector<Leaf> theta_leaves, trunk_leaves;
@@ -440,7 +441,7 @@ int encode_multi(serl_agent* a, const EncJob* jobs, int n, int off, int cnt, hip
   return proprio_fwd_multi(pv, n, c.state_dim, cnt, st);
 }
 
-// generic Dense -> LN -> tanh layer on `rows_per_group` rows for `groups` parameter groups, for n independent
+// generic Dense -> LN -> activation (act: kAct*, the network's) layer on `rows_per_group` rows for `groups` parameter groups, for n independent
 // instances with identical shapes (instance i: operands of job i, split-K scratch slabs_lane[i])
 struct DenseJob {
   const float* X; long ldx, x_gstride;
@@ -450,7 +451,7 @@ struct DenseJob {
   const float *dot_w, *dot_b; float* dot_out;  // optional fused row-dot (critic head)
   long dot_gstride = 0, dot_b_gstride = 0;      // per-group heads (state-only SAC) or 0 = shared
 };
-int dense_ln_tanh_multi(serl_agent* a, const DenseJob* jobs, int n, int groups, int rows_per_group, int K, int splitk,
+int dense_ln_tanh_multi(serl_agent* a, const DenseJob* jobs, int n, int groups, int rows_per_group, int K, int splitk, int act,
                         hipStream_t st) {
   const int Hd = a->cfg.hidden;
   SERL_REQUIRE(n >= 1 && n <= 3, "bad dense instance count");
@@ -472,6 +473,7 @@ int dense_ln_tanh_multi(serl_agent* a, const DenseJob* jobs, int n, int groups, 
     l.xhat = j.xhat; l.rstd = j.rstd;
     l.dot_w = j.dot_w; l.dot_b = j.dot_b; l.dot_out = j.dot_out;
     l.dot_gstride = j.dot_gstride; l.dot_b_gstride = j.dot_b_gstride;
+    l.act = act;
   }
   RC(gemm_f32_multi(gd, n, st));
   return ln_tanh_fwd_multi(lv, n, Hd, st);
@@ -513,8 +515,8 @@ int policy_fwd_multi(serl_agent* a, const PolJob* jobs, int n, int cnt, hipStrea
     pv[i].eps = j.eps; pv[i].act = j.act_out; pv[i].ld_act = j.ld_act; pv[i].logp = pb.logp; pv[i].std_out = pb.std;
     pv[i].sum_logp = j.sum_logp; pv[i].lam = P + o.lam; pv[i].alpha_out = j.alpha_out;
   }
-  RC(dense_ln_tanh_multi(a, d1, n, 1, cnt, a->E, 8, st));
-  RC(dense_ln_tanh_multi(a, d2, n, 1, cnt, Hd, 4, st));
+  RC(dense_ln_tanh_multi(a, d1, n, 1, cnt, a->E, 8, a->policy_act, st));
+  RC(dense_ln_tanh_multi(a, d2, n, 1, cnt, Hd, 4, a->policy_act, st));
   if (a->fuse) {   // the tanh-Gaussian head inside the head GEMM: last arriver of every 64-row tile (heads.hip, kEpiPolicy)
     SERL_REQUIRE(A <= 64, "the fused policy-head epilogue holds one 64-wide slab row per sample (act_dim %d)", A);
     SERL_REQUIRE(cdiv(cnt, 64) <= kCtrPerLane && 8 * pad64(cnt) * 64 <= a->slabs_cap, "policy head exceeds the fused epilogue's scratch");
@@ -561,8 +563,8 @@ int critic_fwd_multi(serl_agent* a, const CritJob* jobs, int n, int cnt, hipStre
     d2[i].dot_gstride = a->state_only ? Hd : 0;
     d2[i].dot_b_gstride = a->state_only ? 1 : 0;
   }
-  RC(dense_ln_tanh_multi(a, d1, n, N, cnt, a->XA, 4, st));
-  return dense_ln_tanh_multi(a, d2, n, N, cnt, Hd, 2, st);
+  RC(dense_ln_tanh_multi(a, d1, n, N, cnt, a->XA, 4, a->critic_act, st));
+  return dense_ln_tanh_multi(a, d2, n, N, cnt, Hd, 2, a->critic_act, st);
 }
 
 LnBwdArgs ln_bwd_args(const float* dy, long ld_dy, long dy_goff, const float* y, long ld_y, long y_goff, const float* xhat,
@@ -576,16 +578,18 @@ LnBwdArgs ln_bwd_args(const float* dy, long ld_dy, long dy_goff, const float* y,
   return l;
 }
 
-// backward of one Dense->LN->tanh layer.  dy: [groups*rows][Hd] gradient wrt the layer output.
+// backward of one Dense->LN->activation layer (act: kAct*; beta: the forward's, read by the swish backward alone).
+// dy: [groups*rows][Hd] gradient wrt the layer output.
 // Produces dpre (a->da*) and, if G != nullptr, parameter gradients into G at the given offsets
 // (W grads are written directly by the GEMM: splitk == 1).
 int dense_ln_tanh_bwd(serl_agent* a, const float* dy, long ld_dy, long dy_goff, const float* y, long ld_y,
-                      long y_goff, const float* xhat, const float* rstd, const float* gamma, long p_gstride,
+                      long y_goff, const float* xhat, const float* rstd, const float* gamma, const float* beta, int act, long p_gstride,
                       int groups, int rows_per_group, int D, float* dpre, float* dg, float* G, long g_off,
                       long be_off, long b_off, long pg_gstride, hipStream_t st, const float* dq = nullptr,
                       const float* dq_w = nullptr, float dq_const = 0.f, long dq_w_gstride = 0, const LossArgs* loss = nullptr) {
   LnBwdArgs l = ln_bwd_args(dy, ld_dy, dy_goff, y, ld_y, y_goff, xhat, rstd, gamma, p_gstride, groups, rows_per_group, dpre, dg);
   l.dq = dq; l.dq_w = dq_w; l.dq_const = dq_const; l.dq_w_gstride = dq_w_gstride;
+  l.act = act; l.beta = beta;
   if (loss) {   // the critic loss rides on this launch and every row derives its dQ from the loss arguments (no critic_loss launch)
     l.D = D; l.dq_inline = 1;
     RC(ln_tanh_bwd_multi(&l, 1, *loss, st));
@@ -704,14 +708,14 @@ int critic_bwd(serl_agent* a, const float* P, CritBuf& cb, int cnt, bool pg, hip
   if (loss) RC(critic_loss_or_rider(a, *loss, st, &rider));
   if (pg) RC(head_kernel_grad(a, cb, cnt, st));
   // gradient through the head dh2 = dq (x) w is formed inside the LN backward kernel (rank-1 mode)
-  RC(dense_ln_tanh_bwd(a, nullptr, Hd, (long)cnt * Hd, cb.m.h2, Hd, (long)cnt * Hd, cb.m.xh2, cb.m.rs2, P + o.c_g2, Hd,
+  RC(dense_ln_tanh_bwd(a, nullptr, Hd, (long)cnt * Hd, cb.m.h2, Hd, (long)cnt * Hd, cb.m.xh2, cb.m.rs2, P + o.c_g2, P + o.c_be2, a->critic_act, Hd,
                        N, cnt, Hd, a->da2, a->dg2, G, o.c_g2, o.c_be2, o.c_b2, Hd, st, loss ? loss->dq : nullptr, P + o.c_hw, dq_const,
                        a->state_only ? Hd : 0, rider));
   if (pg)
     RC(wgrad(a, cb.m.h1, Hd, (long)cnt * Hd, a->da2, Hd, (long)cnt * Hd, a->Gc + o.c_w2, Hd, (long)Hd * Hd, N, Hd, Hd,
              cnt, st));
   RC(igrad(a->da2, Hd, (long)cnt * Hd, P + o.c_w2, Hd, (long)Hd * Hd, a->dh1, Hd, (long)cnt * Hd, N, cnt, Hd, Hd, st));
-  RC(dense_ln_tanh_bwd(a, a->dh1, Hd, (long)cnt * Hd, cb.m.h1, Hd, (long)cnt * Hd, cb.m.xh1, cb.m.rs1, P + o.c_g1, Hd,
+  RC(dense_ln_tanh_bwd(a, a->dh1, Hd, (long)cnt * Hd, cb.m.h1, Hd, (long)cnt * Hd, cb.m.xh1, cb.m.rs1, P + o.c_g1, P + o.c_be1, a->critic_act, Hd,
                        N, cnt, Hd, a->da1, a->dg1, G, o.c_g1, o.c_be1, o.c_b1, Hd, st));
   if (pg)
     RC(wgrad(a, cb.x, a->XA, 0, a->da1, Hd, (long)cnt * Hd, a->Gc + o.c_w1, Hd, (long)a->XA * Hd, N, a->XA, Hd, cnt, st));
@@ -725,7 +729,7 @@ int proprio_bwd(serl_agent* a, const float* P, const float* dy, long ld_dy, cons
   const serl_agent_cfg& c = a->cfg;
   const Offs& o = a->o;
   const int Pd = c.proprio_dim;
-  RC(dense_ln_tanh_bwd(a, dy, ld_dy, 0, y, ld_y, 0, e.pxhat, e.prstd, P + o.p_g, 0, 1, cnt, Pd, a->dp, a->dgp, G,
+  RC(dense_ln_tanh_bwd(a, dy, ld_dy, 0, y, ld_y, 0, e.pxhat, e.prstd, P + o.p_g, nullptr, kActTanh, 0, 1, cnt, Pd, a->dp, a->dgp, G,
                        o.p_g - base_off, o.p_be - base_off, o.p_b - base_off, 0, st));
   const float* s = a->cur.state + ((long)which * a->cur.batch + off) * c.state_dim;
   return wgrad(a, s, c.state_dim, 0, a->dp, Pd, 0, G + (o.p_W - base_off), Pd, 0, 1, c.state_dim, Pd, cnt, st);
@@ -761,7 +765,7 @@ int enc_bwd_critic(serl_agent* a, const float* P, EncBuf& e, int off, int cnt, h
   }
   if (a->state_only) return SERL_OK;
   if (!a->fuse)
-    RC(dense_ln_tanh_bwd(a, a->dx, a->XA, Bn, e.enc, e.ld, Bn, e.xhat, e.rstd, P + o.cam[0].lng, o.cam_stride,
+    RC(dense_ln_tanh_bwd(a, a->dx, a->XA, Bn, e.enc, e.ld, Bn, e.xhat, e.rstd, P + o.cam[0].lng, nullptr, kActTanh, o.cam_stride,
                          c.n_cam, cnt, Bn, a->dz, a->dgz, a->Gc, o.cam[0].lng, o.cam[0].lnb, o.cam[0].db,
                          o.cam_stride, st));
   RC(wgrad(a, e.f, a->D, (long)c.batch * a->D, a->dz, Bn, (long)cnt * Bn, a->Gc + o.cam[0].dW, Bn, o.cam_stride,
@@ -885,6 +889,12 @@ extern "C" {
 int serl_agent_create(const serl_agent_cfg* cfg, serl_agent** out) { return serl_agent_create_policy(cfg, SERL_STD_EXP, 0, out); }
 
 int serl_agent_create_policy(const serl_agent_cfg* cfg, int std_param, int no_tanh, serl_agent** out) {
+  return serl_agent_create_mlp(cfg, std_param, no_tanh, SERL_ACT_TANH, SERL_ACT_TANH, out);
+}
+
+// mlp.py:19-31: MLP applies `activations` (a callable, or the name of one in flax.linen) behind every LayerNorm; the critic and the
+// policy get theirs from two separate kwargs dicts, so the two codes are independent.
+int serl_agent_create_mlp(const serl_agent_cfg* cfg, int std_param, int no_tanh, int critic_act, int policy_act, serl_agent** out) {
   SERL_REQUIRE(cfg && out, "NULL argument");
   SERL_REQUIRE(cfg->n_cam >= 0 && cfg->n_cam <= SERL_MAX_CAMS, "n_cam %d not in [0,%d]", cfg->n_cam, SERL_MAX_CAMS);
   SERL_REQUIRE(cfg->n_cam == 0 || (cfg->H >= 32 && cfg->W >= 32), "images must be at least 32x32");
@@ -909,6 +919,8 @@ int serl_agent_create_policy(const serl_agent_cfg* cfg, int std_param, int no_ta
   SERL_REQUIRE(std_param >= SERL_STD_EXP && std_param <= SERL_STD_UNIFORM,
                "std_param %d is not SERL_STD_EXP (0), SERL_STD_SOFTPLUS (1) or SERL_STD_UNIFORM (2)", std_param);
   SERL_REQUIRE(no_tanh == 0 || no_tanh == 1, "no_tanh %d is not 0 (tanh-squashed) or 1 (plain Gaussian)", no_tanh);
+  SERL_REQUIRE(critic_act >= 0 && critic_act < kActCount, "critic_act %d: served are SERL_ACT_TANH (0), SERL_ACT_RELU (1) and SERL_ACT_SWISH (2)", critic_act);
+  SERL_REQUIRE(policy_act >= 0 && policy_act < kActCount, "policy_act %d: served are SERL_ACT_TANH (0), SERL_ACT_RELU (1) and SERL_ACT_SWISH (2)", policy_act);
   SERL_REQUIRE(cfg->state_dim % num_stack == 0, "state_dim %d is not num_stack %d proprio vectors (state_dim is the flattened width T * S)",
                cfg->state_dim, num_stack);
   for (int t = 0; t < 3; ++t) {
@@ -927,6 +939,7 @@ int serl_agent_create_policy(const serl_agent_cfg* cfg, int std_param, int no_ta
   a->cfg = *cfg;
   a->cfg.num_stack = num_stack;
   a->std_param = std_param; a->no_tanh = no_tanh;
+  a->critic_act = critic_act; a->policy_act = policy_act;
   { const char* e = getenv("SERL_CHAIN_FUSE"); a->fuse = !(e && e[0] == '0'); }
   build_layout(a);
   if (int rc = alloc_zeroed(&a->arena, carve(a, nullptr), "agent arena")) {
@@ -1365,11 +1378,11 @@ int serl_agent_actor_grads(serl_agent* a, int global_count, const serl_noise* no
   RC(head_bias_grad(a, cnt, Ga + (o.a_bm - b0), hs, st));
   // dh2 = dmean W_mean^T + dlog_std W_logstd^T (no second term when the log-std has no Dense)
   RC(igrad_sum(a, a->dpre, A, (long)cnt * A, a->theta + o.a_Wm, A, hs, a->dh2, Hd, hg, cnt, Hd, A, st));
-  RC(dense_ln_tanh_bwd(a, a->dh2, Hd, 0, a->pol.m.h2, Hd, 0, a->pol.m.xh2, a->pol.m.rs2, a->theta + o.a_g2, 0, 1, cnt, Hd,
+  RC(dense_ln_tanh_bwd(a, a->dh2, Hd, 0, a->pol.m.h2, Hd, 0, a->pol.m.xh2, a->pol.m.rs2, a->theta + o.a_g2, a->theta + o.a_be2, a->policy_act, 0, 1, cnt, Hd,
                        a->da2, a->dg2, Ga, o.a_g2 - b0, o.a_be2 - b0, o.a_b2 - b0, 0, st));
   RC(wgrad(a, a->pol.m.h1, Hd, 0, a->da2, Hd, 0, Ga + (o.a_w2 - b0), Hd, 0, 1, Hd, Hd, cnt, st));
   RC(igrad(a->da2, Hd, 0, a->theta + o.a_w2, Hd, 0, a->dh1, Hd, 0, 1, cnt, Hd, Hd, st));
-  RC(dense_ln_tanh_bwd(a, a->dh1, Hd, 0, a->pol.m.h1, Hd, 0, a->pol.m.xh1, a->pol.m.rs1, a->theta + o.a_g1, 0, 1, cnt, Hd,
+  RC(dense_ln_tanh_bwd(a, a->dh1, Hd, 0, a->pol.m.h1, Hd, 0, a->pol.m.xh1, a->pol.m.rs1, a->theta + o.a_g1, a->theta + o.a_be1, a->policy_act, 0, 1, cnt, Hd,
                        a->da1, a->dg1, Ga, o.a_g1 - b0, o.a_be1 - b0, o.a_b1 - b0, 0, st));
   RC(wgrad(a, a->encP.enc, a->encP.ld, 0, a->da1, Hd, 0, Ga + (o.a_w1 - b0), Hd, 0, 1, a->E, Hd, cnt, st));
   // image codes are stop-gradiented (encoding.py:48-49); only the proprio slice of d_enc is needed

@@ -158,7 +158,7 @@ LnFwdArgs head_ln_args(serl_classifier* c, int S1, int n, float* dev_logits) {
   l1.bias = P + c->o_b1; l1.gamma = P + c->o_g1; l1.beta = P + c->o_be1; l1.pstride = 0;
   l1.rows = n; l1.rows_per_group = n;
   l1.y = c->h; l1.ld_y = kHidden; l1.y_goff = 0;
-  l1.relu = 1;
+  l1.act = kActRelu;
   l1.dot_w = P + c->o_w2; l1.dot_b = P + c->o_b2; l1.dot_out = dev_logits;
   return l1;
 }

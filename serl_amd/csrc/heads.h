@@ -45,7 +45,9 @@ struct LnBwdArgs {
   const float* gamma; long pstride;
   int rows, rows_per_group;
   float* dx;  // [rows][D] gradient wrt the pre-activation
-  float* dg;  // [rows][D] dy*(1-y^2)  (-> dbeta = colsum(dg), dgamma = colsum(dg*xhat))
+  float* dg;  // [rows][D] dy * act'(pre): dy*(1-y^2) for tanh  (-> dbeta = colsum(dg), dgamma = colsum(dg*xhat))
+  int act;            // kAct* of the forward row (per instance, uniform over a wave)
+  const float* beta;  // kActSwish only: the forward's beta (addressed like gamma), to recompute pre = gamma*xhat + beta
   int D;          // ln_tanh_bwd_multi only: the row width, a multiple of 64 in [64, 1024]
   int dq_inline;  // ln_tanh_bwd_multi, rank-1 mode: dq[row] = 2 (q - y) inv_norm computed from the LossArgs of the launch
 };

@@ -190,6 +190,52 @@ __device__ __forceinline__ float hash_normal(uint64_t seed, uint64_t i) {
   return sqrtf(-2.f * logf(u1)) * cosf(6.283185307179586f * u2);
 }
 
+// The activation of a LayerNorm row, and what multiplies dy in its backward (mlp.py:19-31).  `act` (kAct*) is a field of the launch's
+// instance, so the branch is uniform over the wave -- a scalar compare and branch, no exec masking (no lane takes another way) --
+// and the rows take it ONCE, over all the columns a lane holds: the tanh path then runs the instructions it always ran.
+// swish(p) = p * sigmoid(p) with sigmoid from e = exp(-|p|) in (0, 1]: 1 / (1 + e) for p >= 0, e / (1 + e) below.  No exponent
+// overflows and nothing is NaN at any finite p; at p -> -inf both e and swish go to -0.  Two quarter-rate instructions per
+// element (v_exp_f32, v_rcp_f32; 1 ulp each), fewer than tanhf spends.
+__device__ __forceinline__ float sigmoid_stable(float p) {
+  const float e = __expf(-fabsf(p));
+  const float r = __builtin_amdgcn_rcpf(1.f + e);
+  return p >= 0.f ? r : e * r;
+}
+template <int N>
+__device__ __forceinline__ void ln_activate(int act, float (&v)[N]) {   // in place: pre-activations -> y
+  if (act == kActTanh) {
+#pragma unroll
+    for (int j = 0; j < N; ++j) v[j] = tanhf(v[j]);
+  } else if (act == kActRelu) {
+#pragma unroll
+    for (int j = 0; j < N; ++j) v[j] = fmaxf(v[j], 0.f);
+  } else {
+#pragma unroll
+    for (int j = 0; j < N; ++j) v[j] *= sigmoid_stable(v[j]);
+  }
+}
+// dg[j] = dy[j] * act'(pre[j]) in place (dg holds dy on entry).  tanh: 1 - y^2.  ReLU: y > 0 -- the gradient AT 0 is 0, as
+// jax.nn.relu's.  swish: sigma(p) + y (1 - sigma(p)) with p = gam * xh + beta recomputed (pbeta: the lane's first beta, its
+// columns BSTRIDE floats apart: beta + boff; beta is nullptr on the other paths, so the pointer is formed on this one alone).
+template <int N, int BSTRIDE>
+__device__ __forceinline__ void ln_act_grad(int act, float (&dg)[N], const float (&y)[N], const float (&xh)[N], const float (&gam)[N],
+                                            const float* beta, long boff) {
+  if (act == kActTanh) {
+#pragma unroll
+    for (int j = 0; j < N; ++j) dg[j] *= 1.f - y[j] * y[j];
+  } else if (act == kActRelu) {
+#pragma unroll
+    for (int j = 0; j < N; ++j) dg[j] = y[j] > 0.f ? dg[j] : 0.f;
+  } else {
+    const float* pbeta = beta + boff;
+#pragma unroll
+    for (int j = 0; j < N; ++j) {
+      const float sg = sigmoid_stable(xh[j] * gam[j] + pbeta[j * BSTRIDE]);
+      dg[j] *= sg + y[j] * (1.f - sg);
+    }
+  }
+}
+
 // LayerNorm(eps 1e-6, fast variance) + tanh of ONE row of 256 by one wave (mlp.py:24-31, resnet_v1.py:371-374, encoding.py:66-68):
 // pre = bias[g] + sum_s slab[s][row] (slabs read in index order);  y = tanh(gamma[g]*xhat + beta[g]).  LIVE: the slabs were
 // written by other workgroups of THIS launch (sc1 loads); otherwise plain loads (the separate ln_tanh_fwd kernel).
@@ -227,16 +273,20 @@ __device__ __forceinline__ float ln_tanh_row256(const LnFwdArgs& a, int row, int
   const float mean = s1 * (1.0f / D), mean2 = s2 * (1.0f / D);
   const float var = fmaxf(mean2 - mean * mean, 0.f);
   const float rstd = rsqrtf(var + 1e-6f);
-  float d = 0.f;
+  float d = 0.f, y[4];
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     const int col = lane * 4 + j;
     const float xh = (v[j] - mean) * rstd;
-    const float pre = xh * a.gamma[(long)grp * a.pstride + col] + a.beta[(long)grp * a.pstride + col];
-    const float y = a.relu ? fmaxf(pre, 0.f) : tanhf(pre);
-    a.y[lrow * a.ld_y + (long)grp * a.y_goff + col] = y;
+    y[j] = xh * a.gamma[(long)grp * a.pstride + col] + a.beta[(long)grp * a.pstride + col];
     if (a.xhat) a.xhat[(long)row * D + col] = xh;
-    if (a.dot_out) d += y * a.dot_w[(long)grp * a.dot_gstride + col];
+  }
+  ln_activate(a.act, y);
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int col = lane * 4 + j;
+    a.y[lrow * a.ld_y + (long)grp * a.y_goff + col] = y[j];
+    if (a.dot_out) d += y[j] * a.dot_w[(long)grp * a.dot_gstride + col];
   }
   if (a.rstd && lane == 0) a.rstd[row] = rstd;
   if (a.dot_out) {
@@ -285,14 +335,17 @@ __device__ __forceinline__ float ln_tanh_row(const LnFwdArgs& a, int row, int la
   const float rstd = rsqrtf(var + 1e-6f);
   float d = 0.f;
 #pragma unroll
+  for (int j = 0; j < VPL; ++j) {   // v: the row's values, then its pre-activations, then y
+    const float xh = (v[j] - mean) * rstd;
+    v[j] = xh * a.gamma[pb + 64 * j] + a.beta[pb + 64 * j];
+    if (a.xhat) a.xhat[(long)row * D + lane + 64 * j] = xh;
+  }
+  ln_activate(a.act, v);
+#pragma unroll
   for (int j = 0; j < VPL; ++j) {
     const int col = lane + 64 * j;
-    const float xh = (v[j] - mean) * rstd;
-    const float pre = xh * a.gamma[pb + 64 * j] + a.beta[pb + 64 * j];
-    const float y = a.relu ? fmaxf(pre, 0.f) : tanhf(pre);
-    a.y[lrow * a.ld_y + (long)grp * a.y_goff + col] = y;
-    if (a.xhat) a.xhat[(long)row * D + col] = xh;
-    if (a.dot_out) d += y * a.dot_w[(long)grp * a.dot_gstride + col];
+    a.y[lrow * a.ld_y + (long)grp * a.y_goff + col] = v[j];
+    if (a.dot_out) d += v[j] * a.dot_w[(long)grp * a.dot_gstride + col];
   }
   if (a.rstd && lane == 0) a.rstd[row] = rstd;
   if (a.dot_out) {
@@ -950,14 +1003,18 @@ __global__ __launch_bounds__(256) void ln_tanh_fwd_kernel(Multi<LnFwdArgs> mv) {
   const float rstd = rsqrtf(var + 1e-6f);
   float d = 0.f;
 #pragma unroll
-  for (int j = 0; j < VPL; ++j) {
+  for (int j = 0; j < VPL; ++j) {   // v: the row's values, then its pre-activations, then y
     const int col = lane * VPL + j;
     const float xh = (v[j] - mean) * rstd;
-    const float pre = xh * a.gamma[(long)grp * a.pstride + col] + a.beta[(long)grp * a.pstride + col];
-    const float y = a.relu ? fmaxf(pre, 0.f) : tanhf(pre);
-    a.y[(long)(row - grp * a.rows_per_group) * a.ld_y + (long)grp * a.y_goff + col] = y;
+    v[j] = xh * a.gamma[(long)grp * a.pstride + col] + a.beta[(long)grp * a.pstride + col];
     if (a.xhat) a.xhat[(long)row * D + col] = xh;
-    if (a.dot_out) d += y * a.dot_w[(long)grp * a.dot_gstride + col];
+  }
+  ln_activate(a.act, v);
+#pragma unroll
+  for (int j = 0; j < VPL; ++j) {
+    const int col = lane * VPL + j;
+    a.y[(long)(row - grp * a.rows_per_group) * a.ld_y + (long)grp * a.y_goff + col] = v[j];
+    if (a.dot_out) d += v[j] * a.dot_w[(long)grp * a.dot_gstride + col];
   }
   if (a.rstd && lane == 0) a.rstd[row] = rstd;
   if (a.dot_out) {
@@ -995,7 +1052,7 @@ __global__ __launch_bounds__(256) void label_rows_kernel(LnFwdArgs a, float* lab
 }
 
 int label_rows(const LnFwdArgs& a, float* label, float* mean, int* ctr, hipStream_t stream) {
-  SERL_REQUIRE(a.rows >= 1 && a.rows == a.rows_per_group && a.relu && a.dot_out && label && mean && ctr, "bad label launch");
+  SERL_REQUIRE(a.rows >= 1 && a.rows == a.rows_per_group && a.act == kActRelu && a.dot_out && label && mean && ctr, "bad label launch");
   SERL_LAUNCH_CHAIN(label_rows_kernel, dim3(cdiv(a.rows, 4)), dim3(256), 0, stream, a, label, mean, ctr);
   SERL_HIP(hipGetLastError());
   return SERL_OK;
@@ -1030,7 +1087,11 @@ int ln_tanh_fwd_multi(const LnFwdArgs* as, int n, int D, hipStream_t stream) {
   SERL_REQUIRE(n >= 1 && n <= kMaxMulti, "bad instance count %d", n);
   Multi<LnFwdArgs> mv{};
   int rows = 0;
-  for (int i = 0; i < n; ++i) { mv.v[i] = as[i]; rows = std::max(rows, as[i].rows); }
+  for (int i = 0; i < n; ++i) {
+    SERL_REQUIRE(as[i].act >= 0 && as[i].act < kActCount, "LayerNorm row: activation code %d is not tanh (0), relu (1) or swish (2)", as[i].act);
+    mv.v[i] = as[i];
+    rows = std::max(rows, as[i].rows);
+  }
   dim3 grid(cdiv(rows, 4), n);
   if (D == 256) SERL_LAUNCH_CHAIN(ln_tanh_fwd_kernel<4>, grid, dim3(256), 0, stream, mv);
   else if (D == 64) SERL_LAUNCH_CHAIN(ln_tanh_fwd_kernel<1>, grid, dim3(256), 0, stream, mv);
@@ -1039,26 +1100,30 @@ int ln_tanh_fwd_multi(const LnFwdArgs* as, int n, int D, hipStream_t stream) {
   return SERL_OK;
 }
 
-// backward of y = tanh(gamma*xhat + beta), xhat = (x-mean)*rstd:
-//   dg = dy*(1-y^2);  dxhat = dg*gamma;  dx = rstd*(dxhat - mean(dxhat) - xhat*mean(dxhat*xhat))
+// backward of y = act(gamma*xhat + beta), xhat = (x-mean)*rstd:
+//   dg = dy*act'(pre) (ln_act_grad; tanh: dy*(1-y^2));  dxhat = dg*gamma;  dx = rstd*(dxhat - mean(dxhat) - xhat*mean(dxhat*xhat))
 template <int VPL>
 __global__ __launch_bounds__(256) void ln_tanh_bwd_kernel(LnBwdArgs a) {
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (row >= a.rows) return;
   const int grp = row / a.rows_per_group;
   constexpr int D = VPL * 64;
-  float dg[VPL], dxh[VPL], xh[VPL];
+  float dg[VPL], dxh[VPL], xh[VPL], y[VPL], gam[VPL];
   float s1 = 0.f, s2 = 0.f;
 #pragma unroll
   for (int j = 0; j < VPL; ++j) {
     const int col = lane * VPL + j;
     const long lr = row - grp * a.rows_per_group;
-    const float y = a.y[lr * a.ld_y + (long)grp * a.y_goff + col];
-    const float dy = a.dq_w ? (a.dq ? a.dq[row] : a.dq_const) * a.dq_w[(long)grp * a.dq_w_gstride + col]
-                            : a.dy[lr * a.ld_dy + (long)grp * a.dy_goff + col];
-    dg[j] = dy * (1.f - y * y);
+    y[j] = a.y[lr * a.ld_y + (long)grp * a.y_goff + col];
+    dg[j] = a.dq_w ? (a.dq ? a.dq[row] : a.dq_const) * a.dq_w[(long)grp * a.dq_w_gstride + col]
+                   : a.dy[lr * a.ld_dy + (long)grp * a.dy_goff + col];
     xh[j] = a.xhat[(long)row * D + col];
-    dxh[j] = dg[j] * a.gamma[(long)grp * a.pstride + col];
+    gam[j] = a.gamma[(long)grp * a.pstride + col];
+  }
+  ln_act_grad<VPL, 1>(a.act, dg, y, xh, gam, a.beta, (long)grp * a.pstride + lane * VPL);
+#pragma unroll
+  for (int j = 0; j < VPL; ++j) {
+    dxh[j] = dg[j] * gam[j];
     s1 += dxh[j];
     s2 += dxh[j] * xh[j];
   }
@@ -1073,8 +1138,14 @@ __global__ __launch_bounds__(256) void ln_tanh_bwd_kernel(LnBwdArgs a) {
   }
 }
 
+// (the swish backward recomputes its pre-activation: it reads beta where the forward did)
+#define SERL_LN_BWD_ACT_OK(a)                                                                                             \
+  SERL_REQUIRE((a).act >= 0 && (a).act < kActCount && ((a).act != kActSwish || (a).beta),                                 \
+               "LayerNorm backward: activation code %d is not tanh (0), relu (1) or swish (2), or swish without beta", (a).act)
+
 int ln_tanh_bwd(const LnBwdArgs& a, int D, hipStream_t stream) {
   SERL_REQUIRE(SERL_LN_WIDTH_OK(D), "LayerNorm width %d unsupported (a multiple of 64 in [64, 1024])", D);
+  SERL_LN_BWD_ACT_OK(a);
   if (D != 256 && D != 64) {   // the width-generic rows: one instance of ln_tanh_bwd_multi's launch, no rider
     LnBwdArgs w = a;
     w.D = D; w.dq_inline = 0;
@@ -1160,7 +1231,7 @@ template <int VPL>
 __device__ __forceinline__ void ln_tanh_bwd_row(const LnBwdArgs& a, const LossArgs& L, int row, int lane) {
   const int grp = row / a.rows_per_group;
   constexpr int D = VPL * 64;
-  float dg[VPL], dxh[VPL], xh[VPL];
+  float dg[VPL], dxh[VPL], xh[VPL], y[VPL], gam[VPL];
   float s1 = 0.f, s2 = 0.f;
   const long lr = row - grp * a.rows_per_group;
   float dqr = 0.f;
@@ -1168,11 +1239,15 @@ __device__ __forceinline__ void ln_tanh_bwd_row(const LnBwdArgs& a, const LossAr
 #pragma unroll
   for (int j = 0; j < VPL; ++j) {
     const int col = lane * VPL + j;
-    const float y = a.y[lr * a.ld_y + (long)grp * a.y_goff + col];
-    const float dy = a.dq_w ? dqr * a.dq_w[(long)grp * a.dq_w_gstride + col] : a.dy[lr * a.ld_dy + (long)grp * a.dy_goff + col];
-    dg[j] = dy * (1.f - y * y);
+    y[j] = a.y[lr * a.ld_y + (long)grp * a.y_goff + col];
+    dg[j] = a.dq_w ? dqr * a.dq_w[(long)grp * a.dq_w_gstride + col] : a.dy[lr * a.ld_dy + (long)grp * a.dy_goff + col];
     xh[j] = a.xhat[(long)row * D + col];
-    dxh[j] = dg[j] * a.gamma[(long)grp * a.pstride + col];
+    gam[j] = a.gamma[(long)grp * a.pstride + col];
+  }
+  ln_act_grad<VPL, 1>(a.act, dg, y, xh, gam, a.beta, (long)grp * a.pstride + lane * VPL);
+#pragma unroll
+  for (int j = 0; j < VPL; ++j) {
+    dxh[j] = dg[j] * gam[j];
     s1 += dxh[j];
     s2 += dxh[j] * xh[j];
   }
@@ -1204,7 +1279,7 @@ template <int VPL>
 __device__ __forceinline__ void ln_tanh_bwd_row_wide(const LnBwdArgs& a, const LossArgs& L, int row, int lane) {
   const int grp = row / a.rows_per_group;
   constexpr int D = VPL * 64;
-  float dg[VPL], dxh[VPL], xh[VPL];
+  float dg[VPL], dxh[VPL], xh[VPL], y[VPL], gam[VPL];
   float s1 = 0.f, s2 = 0.f;
   const long lr = row - grp * a.rows_per_group;
   float dqr = 0.f;
@@ -1212,11 +1287,15 @@ __device__ __forceinline__ void ln_tanh_bwd_row_wide(const LnBwdArgs& a, const L
 #pragma unroll
   for (int j = 0; j < VPL; ++j) {
     const int col = lane + 64 * j;
-    const float y = a.y[lr * a.ld_y + (long)grp * a.y_goff + col];
-    const float dy = a.dq_w ? dqr * a.dq_w[(long)grp * a.dq_w_gstride + col] : a.dy[lr * a.ld_dy + (long)grp * a.dy_goff + col];
-    dg[j] = dy * (1.f - y * y);
+    y[j] = a.y[lr * a.ld_y + (long)grp * a.y_goff + col];
+    dg[j] = a.dq_w ? dqr * a.dq_w[(long)grp * a.dq_w_gstride + col] : a.dy[lr * a.ld_dy + (long)grp * a.dy_goff + col];
     xh[j] = a.xhat[(long)row * D + col];
-    dxh[j] = dg[j] * a.gamma[(long)grp * a.pstride + col];
+    gam[j] = a.gamma[(long)grp * a.pstride + col];
+  }
+  ln_act_grad<VPL, 64>(a.act, dg, y, xh, gam, a.beta, (long)grp * a.pstride + lane);
+#pragma unroll
+  for (int j = 0; j < VPL; ++j) {
+    dxh[j] = dg[j] * gam[j];
     s1 += dxh[j];
     s2 += dxh[j] * xh[j];
   }
@@ -1251,6 +1330,7 @@ int ln_tanh_bwd_multi(const LnBwdArgs* as, int n, const LossArgs& loss, hipStrea
     SERL_REQUIRE(SERL_LN_WIDTH_OK(as[i].D), "LayerNorm width %d unsupported (a multiple of 64 in [64, 1024])", as[i].D);
     SERL_REQUIRE(!as[i].dq_inline || (loss.on && as[i].dq_w && as[i].rows == loss.E * loss.B && as[i].rows_per_group == loss.B),
                  "inline dQ needs the loss arguments of the launch");
+    SERL_LN_BWD_ACT_OK(as[i]);
     mv.v[i] = as[i];
     rows = std::max(rows, as[i].rows);
     wide = wide || (as[i].D != 256 && as[i].D != 64);

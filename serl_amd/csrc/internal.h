@@ -120,8 +120,12 @@ struct LnFwdArgs {
   // optional fused row-dot (critic head, actor_critic_nets.py:65-73): dot_out[row] = sum_col y*dot_w + dot_b[0]
   const float* dot_w; const float* dot_b; float* dot_out;
   long dot_gstride, dot_b_gstride;  // 0: one head shared by all groups (DrQ critic); else per-group heads (ensemblized Critic)
-  int relu;              // 0: tanh (the MLPs / encoder heads); 1: ReLU (BinaryClassifier, reward_classifier.py:24-26)
+  int act;               // kAct*: the row's activation, per instance (one launch may mix them) and uniform over a wave
 };
+// The activation behind a LayerNorm row (mlp.py:19-31: `activations`, a callable or the name of one in flax.linen).  tanh: the MLPs
+// as utils/launcher.py configures them, and always the encoder heads; ReLU: also the BinaryClassifier (reward_classifier.py:24-26);
+// swish = silu: x * sigmoid(x), mlp.py's own default.  The values are serl_agent_create_mlp's critic_act / policy_act.
+enum { kActTanh = 0, kActRelu = 1, kActSwish = 2, kActCount = 3 };
 // The policy distribution of an agent (serl_agent_create_policy's std_param / no_tanh) as the head kernels take it, a template parameter:
 // the std parameterisation in the low bits, kPolNoTanh on top.  kPolExp (0) is the tanh-Gaussian with std = exp(log_std).
 enum { kPolExp = 0, kPolSoftplus = 1, kPolUniform = 2, kPolStdMask = 3, kPolNoTanh = 4 };

@@ -72,6 +72,30 @@ def mlp_hidden_width(critic_network_kwargs=None, policy_network_kwargs=None) -> 
     return widths[0]
 
 
+MLP_ACTIVATIONS = ("tanh", "relu", "swish")   # serl_agent_create_mlp's critic_act / policy_act (SERL_ACT_*), in code order
+_ACTIVATION_NAMES = {"tanh": "tanh", "relu": "relu", "swish": "swish", "silu": "swish"}   # flax.linen.silu is swish
+
+
+def mlp_activations(critic_network_kwargs=None, policy_network_kwargs=None):
+    """(critic, policy): the `activations` of the reference's MLP (networks/mlp.py:19-31) from its two network kwargs, each one
+    of MLP_ACTIVATIONS.  Accepted: the strings "tanh", "relu", "swish", "silu" (mlp.py resolves a string as getattr(nn, name)) and
+    any callable whose __name__ is one of them (nn.tanh, jax.nn.relu, ...).  An absent key means what utils/launcher.py writes,
+    tanh -- not mlp.py's own default, swish: pass it to get it.  Anything else, and a positive dropout_rate (mlp.py:28-31: not
+    built in the MLP rows), raises NotImplementedError from the arguments alone."""
+    served = 'served: activations "tanh", "relu", "swish" (= "silu") by name or as a callable of that __name__, dropout_rate None or 0'
+    out = []
+    for which, nk in (("critic_network_kwargs", critic_network_kwargs or {}), ("policy_network_kwargs", policy_network_kwargs or {})):
+        act = nk.get("activations", "tanh")
+        name = act if isinstance(act, str) else getattr(act, "__name__", None) if callable(act) else None
+        if not isinstance(name, str) or name not in _ACTIVATION_NAMES:
+            raise NotImplementedError(f"{which}: activations={act!r} ({served})")
+        rate = nk.get("dropout_rate")
+        if rate is not None and not (isinstance(rate, (int, float)) and rate <= 0):
+            raise NotImplementedError(f"{which}: dropout_rate={rate!r} ({served})")
+        out.append(_ACTIVATION_NAMES[name])
+    return tuple(out)
+
+
 STD_PARAMETERIZATIONS = ("exp", "softplus", "uniform")   # serl_agent_create_policy's std_param (actor_critic_nets.py:196-211); "fixed" is not served
 
 

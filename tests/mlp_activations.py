@@ -1,0 +1,228 @@
+"""Shared by tests/test_mlp_activations_cpu.py, tests/test_mlp_activations_gpu.py and tests/golden/make_golden_update_activations.py:
+the activations of the critic's and the policy's MLP beside the launcher's tanh (networks/mlp.py:19-31; the critic_act / policy_act
+arguments of serl_agent_create_mlp), the table of the act_*.npz fixtures, the parameters each fixture's run starts from, and a
+float64 restatement of the two MLPs that takes the activation as a parameter: oracle.drq_oracle's policy_head and critic_forward,
+replaced at run time (`oracle_activations`), so that the oracle's own update code -- and autograd for the backward -- runs on it."""
+import contextlib
+import json
+import os
+
+import numpy as np
+import torch
+
+from oracle import drq_oracle as O
+from oracle import golden_update as G
+import trained_regime as TR
+
+GOLDEN_DIR = os.path.join(os.path.dirname(__file__), "golden")
+PARAM_SEED, BATCH_SEED = 42, 100
+KINK_MIN = 1e-4        # the smallest |pre-activation| a relu comparison may contain (see `Recorder`)
+KINK_SEEDS = 10
+
+TORCH_ACT = {"tanh": torch.tanh, "relu": torch.relu, "swish": lambda x: x * torch.sigmoid(x)}
+NEW_ACTS = ("swish", "relu")
+
+
+def network_kwargs(act, h=256):
+    """the launcher's critic_network_kwargs / policy_network_kwargs (utils/launcher.py:50-116) with another activation"""
+    return {"activations": act, "use_layer_norm": True, "hidden_dims": [h, h]}
+
+
+_STATE = dict(image_keys=(), S=10, A=5, discount=0.99, temp_warmup=0)
+_STATE_SCHED = [("high_utd", 2), ("update", ("actor", "critic", "temperature")), ("high_utd", 1)]
+# name -> (oracle Config, rows, schedule, (critic activation, policy activation), regime, sampled elements per large leaf).
+# State-only: B = 72 = two 64-row head tiles, the second ragged, divisible by the UTD; A = 5 is odd.
+GOLDEN = {
+    "update_sac_state_swish": (O.Config(warmup=2000, **_STATE), 72, _STATE_SCHED, ("swish", "swish"), "init", 1024),
+    "update_sac_state_relu": (O.Config(warmup=2000, **_STATE), 72, _STATE_SCHED, ("relu", "relu"), "kink_margin", 1024),
+    "update_sac_state_mixed": (O.Config(warmup=2000, **_STATE), 72, _STATE_SCHED, ("relu", "swish"), "kink_margin", 1024),
+    "trained_sac_state_swish": (O.Config(warmup=4, **_STATE), 72, _STATE_SCHED, ("swish", "swish"), "trained", 1024),
+    "update_drq_swish": (O.Config(image_keys=("image",), H=64, W=64, S=5, A=3), 6, [("critics",), ("high_utd", 2)],
+                         ("swish", "swish"), "init", 1024),
+}
+
+
+MARGIN_SEED = 23
+SAFE_SCALE, SAFE_BIAS, LIVE_BIAS, SAFE_REACH = 0.05, 1.0, 0.3, 0.8
+
+
+def safe_scale(D):
+    """the LayerNorm scale of a safe column at width D: |scale * xhat| <= SAFE_REACH = 0.8 < SAFE_BIAS whatever the row, since
+    |xhat| <= sqrt(D - 1).  SAFE_SCALE = 0.05 up to width 257 (0.05 sqrt(255) = 0.798), 0.8 / sqrt(D - 1) above (0.025 at 1024)."""
+    return min(SAFE_SCALE, SAFE_REACH / float(np.sqrt(D - 1)))
+
+
+GOLDEN_LIVE = 4      # live columns per LayerNorm vector in the relu fixtures
+
+
+def kink_margin(theta, seed=MARGIN_SEED, n_live=GOLDEN_LIVE):
+    """LayerNorm leaves of the four MLP layers under which a run CAN keep every relu pre-activation KINK_MIN away from 0.  With
+    O.init_params' leaves (scale ~ 1, bias ~ 0) a pre-activation has density 0.4 at 0 and a run of the fixtures' schedule evaluates
+    8e6 of them: the smallest is 1e-7 whatever the batch seed.  Here every LayerNorm vector (every member's, in the critic) keeps
+    n_live live columns -- scale 1, bias LIVE_BIAS: the sign changes from row to row, the unit is off in about 40 % of the rows --
+    and all other columns are safe: scale safe_scale(D), bias +-SAFE_BIAS by a seeded coin, so |pre| >= 0.2 in every row: on in
+    every row, or off in every row (output and gradient exactly 0).  Only the live pre-activations can come near 0, and there are
+    few enough of them (1.4e5 in a fixture's run with GOLDEN_LIVE = 4 live columns) for a batch seed to keep them all KINK_MIN
+    away: with ONE live column 19 (relu) and 18 (mixed) of the batch seeds 100, 116, ..., 564 did; what the generator found with
+    four is in each file's meta (batch_seed, seeds_tried)."""
+    rng = np.random.default_rng(seed)
+    out = {k: np.array(v, np.float32) for k, v in theta.items()}
+    for net in ("critic", "actor"):
+        for ln in ("ln1", "ln2"):
+            sc, bi = out[f"{net}/{ln}/scale"], out[f"{net}/{ln}/bias"]
+            D = sc.shape[-1]
+            rows_sc, rows_bi = sc.reshape(-1, D), bi.reshape(-1, D)     # (views: one row per member)
+            for r in range(rows_sc.shape[0]):
+                live = rng.choice(D, size=n_live, replace=False)
+                rows_sc[r, :] = safe_scale(D)
+                rows_bi[r, :] = np.where(rng.random(D) < 0.5, SAFE_BIAS, -SAFE_BIAS)
+                rows_sc[r, live], rows_bi[r, live] = 1.0, LIVE_BIAS
+    return out
+
+
+def act_theta(theta, cfg, regime):
+    """O.init_params' leaves -> the leaves a fixture's run starts from (oracle names), float32.  "trained": trained_regime.trained_like
+    (lagrange 0.5): LayerNorm scales up to 3 in front of the activation.  "kink_margin": kink_margin above (the relu fixtures)."""
+    if regime == "trained":
+        return TR.trained_like(theta, cfg, lam=0.5)
+    if regime == "kink_margin":
+        return kink_margin(theta)
+    assert regime == "init", regime
+    return {k: np.array(v, np.float32) for k, v in theta.items()}
+
+
+def golden_path(name):
+    return os.path.join(GOLDEN_DIR, f"act_{name}.npz")
+
+
+def load_golden(name, monkeypatch=None):
+    """-> (G.unpack of tests/golden/act_<name>.npz, its meta["activations"], the npz)"""
+    z = np.load(golden_path(name))
+    if monkeypatch is not None:
+        monkeypatch.setattr(G, "N_SAMPLE", int(z["act_n_sample"]))
+    meta = json.loads(str(z["meta"]))
+    return (G.unpack(z) if monkeypatch is not None else None), meta["activations"], z
+
+
+def initial_leaves(name):
+    """-> (trunk, theta) the run of fixture `name` started from, oracle names"""
+    cfg, _, _, _, regime, _ = GOLDEN[name]
+    trunk, theta = O.init_params(cfg, PARAM_SEED)
+    return trunk, act_theta(theta, cfg, regime)
+
+
+class Kink(Exception):
+    """a pre-activation closer to 0 than a Recorder's floor; args[0] = its absolute value"""
+
+
+class Recorder:
+    """What an activation saw: per evaluation (one call) the smallest and the largest |pre-activation|.  ReLU's kink: an fp32 run
+    may put a pre-activation on the other side of 0 than the fp64 one, which flips a gradient term; a relu comparison counts only
+    where every evaluation stayed KINK_MIN away from 0 -- a condition on the inputs, checked on the fp64 side alone."""
+
+    def __init__(self, floor=None):
+        """floor: raise Kink at the first evaluation that comes closer to 0 (a seed search need not finish a run that is out)"""
+        self.floor = floor
+        self.reset()
+
+    def reset(self):
+        self.min_abs, self.max_abs, self._off, self._live = [], [], 0, 0
+
+    @property
+    def off_fraction(self):
+        """over the columns whose sign differed between the rows of an evaluation: the fraction of entries below 0"""
+        return self._off / self._live if self._live else None
+
+    def see(self, x):
+        rows = x.shape[-2] if x.dim() > 1 else 1      # (a factory's init pass hands over one observation)
+        neg = (x.detach().reshape(-1, rows, x.shape[-1]) < 0).to(torch.float64)      # [member, row, column]
+        mixed = (neg.mean(1) > 0) & (neg.mean(1) < 1)
+        self._off += int((neg * mixed[:, None, :]).sum())
+        self._live += int(mixed.sum()) * neg.shape[1]
+        a = x.detach().abs()
+        self.min_abs.append(float(a.min()))
+        self.max_abs.append(float(a.max()))
+        if self.floor is not None and self.min_abs[-1] < self.floor:
+            raise Kink(self.min_abs[-1])
+
+    @property
+    def kink_free(self):
+        return bool(self.min_abs) and min(self.min_abs) >= KINK_MIN
+
+
+# ---- float64 restatement of the two MLPs -----------------------------------------------------------------------------------------
+def policy_features(th, enc, act):
+    """the policy's two LayerNorm + activation layers -> h2 (mlp.py:19-31)"""
+    h = act(O.layer_norm(enc @ th["actor/w1"] + th["actor/b1"], th["actor/ln1/scale"], th["actor/ln1/bias"]))
+    return act(O.layer_norm(h @ th["actor/w2"] + th["actor/b2"], th["actor/ln2/scale"], th["actor/ln2/bias"]))
+
+
+def policy_head(th, cfg, enc, act):
+    """O.policy_head (exp std, the launcher's) with the MLP's activation given -> (mean, clipped std)"""
+    h = policy_features(th, enc, act)
+    mean = h @ th["actor/mean/kernel"] + th["actor/mean/bias"]
+    log_std = h @ th["actor/logstd/kernel"] + th["actor/logstd/bias"]
+    return mean, torch.clamp(torch.exp(log_std), cfg.std_min, cfg.std_max)
+
+
+def critic_forward(th, cfg, enc, action, act):
+    """O.critic_forward with the MLP's activation given -> Q [ensemble, B]"""
+    x = torch.cat([enc, action], dim=-1)
+    h = torch.einsum("bi,eio->ebo", x, th["critic/w1"]) + th["critic/b1"][:, None, :]
+    h = act(O.layer_norm(h, th["critic/ln1/scale"][:, None, :], th["critic/ln1/bias"][:, None, :]))
+    h = torch.einsum("ebi,eio->ebo", h, th["critic/w2"]) + th["critic/b2"][:, None, :]
+    h = act(O.layer_norm(h, th["critic/ln2/scale"][:, None, :], th["critic/ln2/bias"][:, None, :]))
+    if cfg.state_only:
+        return torch.einsum("ebi,eio->ebo", h, th["critic/head/kernel"]).squeeze(-1) + th["critic/head/bias"][:, None]
+    return (h @ th["critic/head/kernel"]).squeeze(-1) + th["critic/head/bias"]
+
+
+def recorded(name, rec):
+    """TORCH_ACT[name] reporting every pre-activation tensor to the Recorder"""
+    fn = TORCH_ACT[name]
+
+    def act(x):
+        rec.see(x)
+        return fn(x)
+    return act
+
+
+@contextlib.contextmanager
+def oracle_activations(critic, policy, recs=None):
+    """oracle.drq_oracle with the critic's MLP on activation `critic` and the policy's on `policy` (names of TORCH_ACT): its
+    policy_head / critic_forward replaced for the duration, so update_critics / update_high_utd / update run on them.
+    recs: {"critic": Recorder, "policy": Recorder} that see every pre-activation of their network."""
+    ca = recorded(critic, recs["critic"]) if recs else TORCH_ACT[critic]
+    pa = recorded(policy, recs["policy"]) if recs else TORCH_ACT[policy]
+    saved = O.policy_head, O.critic_forward
+    O.policy_head = lambda th, cfg, enc: policy_head(th, cfg, enc, pa)
+    O.critic_forward = lambda th, cfg, enc, action: critic_forward(th, cfg, enc, action, ca)
+    try:
+        yield
+    finally:
+        O.policy_head, O.critic_forward = saved
+
+
+def core_with(cfg, B, critic, policy, theta, trunk=None, fuse=None):
+    """AgentCore with these activations holding `theta` (oracle names) in params and target_params"""
+    import agent_helpers as AH
+    from serl_amd.agents.core import AgentCore
+    old = os.environ.get("SERL_CHAIN_FUSE")
+    try:
+        if fuse is not None:
+            os.environ["SERL_CHAIN_FUSE"] = "1" if fuse else "0"
+        core = AgentCore(encoder_type=cfg.encoder_type, n_cam=cfg.n_cam, H=cfg.H, W=cfg.W, state_dim=cfg.S, act_dim=cfg.A, batch=B,
+                         ensemble=cfg.ensemble, hidden=cfg.hidden, discount=cfg.discount, tau=cfg.tau, lr=cfg.lr,
+                         warmup_steps=cfg.warmup, dropout=cfg.dropout, std_min=cfg.std_min, std_max=cfg.std_max,
+                         target_entropy=cfg.target_entropy, seed=0,
+                         temp_warmup_steps=-1 if cfg.temp_warmup is None else cfg.temp_warmup,
+                         critic_activation=critic, policy_activation=policy)
+    finally:
+        if old is None:
+            os.environ.pop("SERL_CHAIN_FUSE", None)
+        else:
+            os.environ["SERL_CHAIN_FUSE"] = old
+    for sec in ("params", "target_params"):
+        core.load_flat(sec, trunk or {})
+        core.load_flat(sec, {AH.product_name(k, cfg.image_keys): v for k, v in theta.items()})
+    return core
