@@ -22,20 +22,20 @@ def _proj_vec(n, salt):
     return r.integers(0, 2, n).astype(np.float64) * 2.0 - 1.0
 
 
-def _sample_idx(n, salt):
+def _sample_idx(n, salt, size=N_SAMPLE):
     r = np.random.Generator(np.random.PCG64(np.random.SeedSequence([n, salt, 7])))
-    return np.sort(r.choice(n, size=N_SAMPLE, replace=False))
+    return np.sort(r.choice(n, size=size, replace=False))
 
 
 def _salt(name):
     return zlib.crc32(name.encode())
 
 
-def leaf_record(name, v):
+def leaf_record(name, v, n_sample=N_SAMPLE, full_max=FULL_MAX):
     v = np.asarray(v, np.float64).reshape(-1)
-    if v.size <= FULL_MAX:
+    if v.size <= full_max:
         return {"full": v}
-    idx = _sample_idx(v.size, _salt(name))
+    idx = _sample_idx(v.size, _salt(name), n_sample)
     return {"stat": np.array([v.sum(), (v * v).sum(), (v * _proj_vec(v.size, _salt(name))).sum()]), "val": v[idx]}
 
 
@@ -47,8 +47,8 @@ def leaf_compare(name, rec, got):
         assert got.size == ref.size, (name, got.size, ref.size)
         scale = np.abs(ref).max() + 1e-300
         return float(np.abs(got - ref).max() / scale), "full"
-    idx = _sample_idx(got.size, _salt(name))
     ref = rec["val"]
+    idx = _sample_idx(got.size, _salt(name), ref.size)      # (the sample count a file was written with is in its records)
     scale = np.abs(ref).max() + 1e-300
     e_val = float(np.abs(got[idx] - ref).max() / scale)
     st = np.array([got.sum(), (got * got).sum(), (got * _proj_vec(got.size, _salt(name))).sum()])
@@ -83,7 +83,7 @@ def shape_tree(t):
     return list(np.shape(t))
 
 
-def pack(res, param_seed, batch_seed):
+def pack(res, param_seed, batch_seed, n_sample=N_SAMPLE, full_max=FULL_MAX):
     cfg = res["cfg"]
     out = {"meta": np.array(json.dumps({"cfg": cfg_to_dict(cfg), "B": res["B"],
                                         "schedule": [[s[0]] + [list(x) if isinstance(x, (tuple, list)) else x for x in s[1:]] for s in res["schedule"]],
@@ -112,7 +112,7 @@ def pack(res, param_seed, batch_seed):
         secs[f"mu_{tx}"], secs[f"nu_{tx}"] = f["mu"][tx], f["nu"][tx]
     for sec, tree in secs.items():
         for name, v in tree.items():
-            for kind, arr in leaf_record(f"{sec}/{name}", v).items():
+            for kind, arr in leaf_record(f"{sec}/{name}", v, n_sample, full_max).items():
                 out[f"f_{sec}|{name}|{kind}"] = arr
     return out
 
@@ -161,6 +161,6 @@ def leaf_errors(name, rec, got):
     if "full" in rec:
         ref, g = rec["full"], got
     else:
-        ref, g = rec["val"], got[_sample_idx(got.size, _salt(name))]
+        ref, g = rec["val"], got[_sample_idx(got.size, _salt(name), rec["val"].size)]
     scale = np.abs(ref).max() + 1e-300
     return np.abs(g - ref), scale

@@ -1,4 +1,7 @@
 """Helpers for the agent parity tests: build the same agent in the oracle and in the HIP library."""
+import contextlib
+import os
+
 import numpy as np
 import torch
 
@@ -12,22 +15,52 @@ def product_name(name, image_keys):
     return "/".join(parts)
 
 
-def make_pair(cfg: O.Config, B, dtype=torch.float64, seed=42, agent_seed=0, trunk_mode=None):
-    """-> (oracle TrainState, AgentCore) holding identical parameters."""
+@contextlib.contextmanager
+def chain_fuse(fuse):
+    """SERL_CHAIN_FUSE 1 / 0 (fuse True / False) for the duration; None leaves the default chain.  The switch is read when an
+    agent is created."""
+    if fuse is None:
+        yield
+        return
+    old = os.environ.get("SERL_CHAIN_FUSE")
+    os.environ["SERL_CHAIN_FUSE"] = "1" if fuse else "0"
+    try:
+        yield
+    finally:
+        os.environ.pop("SERL_CHAIN_FUSE")
+        if old is not None:
+            os.environ.update(SERL_CHAIN_FUSE=old)
+
+
+def make_core(cfg: O.Config, B, *, fuse=None, trunk_mode=None, agent_seed=0, **agent_kwargs):
+    """-> the AgentCore of an oracle Config; agent_kwargs: what a Config does not hold (std_parameterization,
+    tanh_squash_distribution, critic_activation, policy_activation).  fuse: see chain_fuse."""
     from serl_amd.agents.core import AgentCore
-    trunk, theta = O.init_params(cfg, seed)
-    st = O.TrainState(cfg, trunk, theta, dtype)
-    core = AgentCore(encoder_type=cfg.encoder_type, n_cam=cfg.n_cam, H=cfg.H, W=cfg.W, state_dim=cfg.S, act_dim=cfg.A, batch=B,
-                     ensemble=cfg.ensemble, discount=cfg.discount, tau=cfg.tau, lr=cfg.lr,
-                     warmup_steps=cfg.warmup, dropout=cfg.dropout, std_min=cfg.std_min, std_max=cfg.std_max,
-                     target_entropy=cfg.target_entropy, seed=agent_seed,
-                     temp_warmup_steps=-1 if cfg.temp_warmup is None else cfg.temp_warmup)
+    with chain_fuse(fuse):
+        core = AgentCore(encoder_type=cfg.encoder_type, n_cam=cfg.n_cam, H=cfg.H, W=cfg.W, state_dim=cfg.S, act_dim=cfg.A, batch=B,
+                         ensemble=cfg.ensemble, hidden=cfg.hidden, discount=cfg.discount, tau=cfg.tau, lr=cfg.lr,
+                         warmup_steps=cfg.warmup, dropout=cfg.dropout, std_min=cfg.std_min, std_max=cfg.std_max,
+                         target_entropy=cfg.target_entropy, seed=agent_seed,
+                         temp_warmup_steps=-1 if cfg.temp_warmup is None else cfg.temp_warmup,
+                         critic_subsample_size=cfg.subsample, backup_entropy=cfg.backup_entropy, **agent_kwargs)
     if trunk_mode is not None:
         core.set_trunk_mode(trunk_mode)
-    for sec in ("params", "target_params"):
-        core.load_flat(sec, trunk)
-        core.load_flat(sec, {product_name(k, cfg.image_keys): v for k, v in theta.items()})
-    return st, core
+    return core
+
+
+def load_leaves(core, cfg, trunk, theta, target=None):
+    """trunk and theta (oracle names) into params and target_params; target: other leaves for the target copy.  -> core"""
+    for sec, th in (("params", theta), ("target_params", theta if target is None else target)):
+        core.load_flat(sec, trunk or {})
+        core.load_flat(sec, {product_name(k, cfg.image_keys): v for k, v in th.items()})
+    return core
+
+
+def make_pair(cfg: O.Config, B, dtype=torch.float64, seed=42, agent_seed=0, trunk_mode=None, fuse=None):
+    """-> (oracle TrainState, AgentCore) holding identical parameters."""
+    trunk, theta = O.init_params(cfg, seed)
+    core = make_core(cfg, B, fuse=fuse, trunk_mode=trunk_mode, agent_seed=agent_seed)
+    return O.TrainState(cfg, trunk, theta, dtype), load_leaves(core, cfg, trunk, theta)
 
 
 _FRAMES = {}

@@ -32,7 +32,7 @@ from oracle import ref_update_runner as RR  # noqa: E402
 from oracle import ref_update_shim as R  # noqa: E402
 
 SEED, BATCH_SEED = 0, 100
-G.N_SAMPLE = 512     # sampled elements per large leaf (make_golden_update.py keeps 2048): every file stays well under 1 MiB
+N_SAMPLE = 512     # sampled elements per large leaf (make_golden_update.py keeps 2048): every file stays well under 1 MiB
 CASES = {   # name: (config, batch rows, schedule); schedule None = parameters and state.rng only
     "drq_64": (O.Config(image_keys=("front", "wrist"), H=64, W=64, S=5, A=3), 8, [("high_utd", 1)]),
     "drq_small": (O.Config(image_keys=("front", "wrist"), H=64, W=64, S=5, A=3, encoder_type="small"), 8, [("high_utd", 1)]),
@@ -223,9 +223,9 @@ def run_agent_case(cfg, B, sched):
     finally:
         RR._make_reference_agent, O.init_params = orig_make, orig_init
     res["prng"] = "threefry"
-    rec = G.pack(res, SEED, BATCH_SEED)
+    rec = G.pack(res, SEED, BATCH_SEED, n_sample=N_SAMPLE)
     for name, v in captured.items():
-        for k, a in G.leaf_record(name, v).items():
+        for k, a in G.leaf_record(name, v, N_SAMPLE).items():
             rec[f"init/{name}/{k}"] = a
         rec[f"init_shape/{name}"] = np.asarray(v.shape, np.int64)
     rec["init_rng"] = np.asarray(meta["rng"], np.uint32)
@@ -282,7 +282,7 @@ def run_classifier_case(cfg):
 
 def _init_records(rec, leaves):
     for name, v in leaves.items():
-        for k, a in G.leaf_record(name, v).items():
+        for k, a in G.leaf_record(name, v, N_SAMPLE).items():
             rec[f"init/{name}/{k}"] = a
         rec[f"init_shape/{name}"] = np.asarray(v.shape, np.int64)
     return rec

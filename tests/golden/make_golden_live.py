@@ -47,7 +47,6 @@ FULL_MAX, N_SAMPLE = 256, 256
 
 
 def update_runs():
-    G.FULL_MAX, G.N_SAMPLE = FULL_MAX, N_SAMPLE
     for name, (cfg, B, sched, pseed, bseed, prng) in UPDATE_CASES.items():
         if prng == "threefry":
             os.environ["SERL_JAXSHIM_PRNG"] = "threefry"
@@ -55,7 +54,7 @@ def update_runs():
             os.environ.pop("SERL_JAXSHIM_PRNG", None)
         res = RR.run_reference(cfg, B, sched, pseed, bseed)
         res["prng"] = os.environ.pop("SERL_JAXSHIM_PRNG", "philox")
-        rec = G.pack(res, pseed, bseed)
+        rec = G.pack(res, pseed, bseed, n_sample=N_SAMPLE, full_max=FULL_MAX)
         f = res["final"]
         rec["record_form"] = np.array([FULL_MAX, N_SAMPLE], np.int64)
         rec["count"] = np.array([f["count"][tx] for tx in O.TX_NAMES], np.int64)

@@ -27,20 +27,18 @@ do not start with "update_": tests/test_reference_update.py and tests/test_golde
 launcher's tanh.  tests/test_mlp_activations_{cpu,gpu}.py read these files.
 """
 import contextlib
-import json
 import os
 import sys
-
-import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.dirname(HERE))
-from oracle import golden_update as G  # noqa: E402
 from oracle import ref_update_runner as RR  # noqa: E402
 from oracle import ref_update_shim as R  # noqa: E402
+import golden_replay as GR  # noqa: E402
 import mlp_activations as MA  # noqa: E402
+import variant_recorder as VR  # noqa: E402
 
 ONLY = [a for a in sys.argv[1:] if not a.startswith("-")]
 SEED_STEP = 16
@@ -54,8 +52,6 @@ def reference_activations(critic, policy, recs, floors):
     R.install(True)
     import jax.nn
     from jax._core import raw
-    from serl_launcher.agents.continuous.drq import DrQAgent
-    from serl_launcher.agents.continuous.sac import SACAgent
 
     def recording(name, rec):
         fn = getattr(jax.nn, name)
@@ -65,22 +61,11 @@ def reference_activations(critic, policy, recs, floors):
             return fn(x)
         activation.__name__ = name
         return activation
-    acts = {"critic_network_kwargs": recording(critic, recs["critic"]), "policy_network_kwargs": recording(policy, recs["policy"])}
-    saved = []
-    for target, name in ((SACAgent, "create_states"), (DrQAgent, "create_drq")):
-        cm = target.__dict__[name]
-        saved.append((target, name, cm))
-
-        def patched(cls, *a, _orig=cm.__func__, **k):
-            for nk, act in acts.items():
-                assert nk in k, f"the factory no longer passes {nk} by keyword"
-                k[nk] = {**k[nk], "activations": act}
-            return _orig(cls, *a, **k)
-        setattr(target, name, classmethod(patched))
+    acts = {"critic_network_kwargs": {"activations": recording(critic, recs["critic"])},
+            "policy_network_kwargs": {"activations": recording(policy, recs["policy"])}}
     # the factory's model_def.init runs both networks on zero observations (pre-activation = the LayerNorm bias = 0 everywhere):
     # what the recorders saw until the agent exists is no evaluation of the run
     make = RR._make_reference_agent
-    saved.append((RR, "_make_reference_agent", make))
 
     def make_and_forget(*a, **k):
         agent = make(*a, **k)
@@ -92,10 +77,10 @@ def reference_activations(critic, policy, recs, floors):
         return agent
     RR._make_reference_agent = make_and_forget
     try:
-        yield
+        with VR.reference_create_overrides(acts):
+            yield
     finally:
-        for target, name, cm in saved:
-            setattr(target, name, cm)
+        RR._make_reference_agent = make
 
 
 def main():
@@ -103,15 +88,14 @@ def main():
         if ONLY and name not in ONLY:
             continue
         os.environ.pop("SERL_JAXSHIM_PRNG", None)
-        G.N_SAMPLE = n_sample
         relu = [w for w, a in (("critic", critic), ("policy", policy)) if a == "relu"]
         tried = []
         for k in range(MAX_SEEDS if relu else 1):
-            batch_seed = MA.BATCH_SEED + SEED_STEP * k
+            batch_seed = GR.BATCH_SEED + SEED_STEP * k
             recs = {"critic": MA.Recorder(), "policy": MA.Recorder()}
             try:
                 with reference_activations(critic, policy, recs, {w: MA.KINK_MIN for w in relu}):
-                    res = RR.run_reference(cfg, B, sched, MA.PARAM_SEED, batch_seed,
+                    res = RR.run_reference(cfg, B, sched, GR.PARAM_SEED, batch_seed,
                                            theta_transform=lambda th, c: MA.act_theta(th, c, regime))
             except MA.Kink as e:      # this seed is out at its first evaluation inside the margin: the next one
                 tried.append((batch_seed, e.args[0]))
@@ -128,24 +112,16 @@ def main():
         if relu:      # the run crossed the kink: the live units were on in some rows and off in others
             frac = {w: recs[w].off_fraction for w in relu}
             print(name, "seeds tried", len(tried), "live-unit rows off:", frac)
-        res["prng"] = "philox"
-        rec = G.pack(res, MA.PARAM_SEED, batch_seed)
-        meta = json.loads(str(rec["meta"]))
-        meta["activations"] = {"critic": critic, "policy": policy, "regime": regime, "transform": "mlp_activations.act_theta",
-                               "batch_seed": batch_seed, "relu_min_abs_pre": kink, "seeds_tried": len(tried), "margin_seed": MA.MARGIN_SEED,
-                               "relu_off_fraction": {w: recs[w].off_fraction for w in relu},
-                               "evaluations": {w: len(recs[w].min_abs) for w in recs},
-                               "min_abs_pre": {w: min(recs[w].min_abs) for w in recs},
-                               "max_abs_pre": {w: max(recs[w].max_abs) for w in recs}}
+        meta = {"critic": critic, "policy": policy, "regime": regime, "transform": "mlp_activations.act_theta",
+                "batch_seed": batch_seed, "relu_min_abs_pre": kink, "seeds_tried": len(tried), "margin_seed": MA.MARGIN_SEED,
+                "relu_off_fraction": {w: recs[w].off_fraction for w in relu},
+                "evaluations": {w: len(recs[w].min_abs) for w in recs},
+                "min_abs_pre": {w: min(recs[w].min_abs) for w in recs},
+                "max_abs_pre": {w: max(recs[w].max_abs) for w in recs}}
         if regime == "trained":     # swish's saturated branch: sigmoid's exponent reaches ten and more
-            assert max(meta["activations"]["max_abs_pre"].values()) >= 10.0, meta["activations"]["max_abs_pre"]
-        rec["meta"] = np.array(json.dumps(meta))
-        path = MA.golden_path(name)
-        np.savez_compressed(path, act_n_sample=np.int64(n_sample), **rec)
-        size = os.path.getsize(path)
-        assert size < 1 << 20, (path, size)
-        print(name, "->", path, f"{size / 1e6:.2f} MB", "final step", res["final"]["step"], meta["activations"],
-              {k: round(v, 6) for k, v in res["steps"][-1]["info"].items()})
+            assert max(meta["max_abs_pre"].values()) >= 10.0, meta["max_abs_pre"]
+        VR.write(GR.variant_path("act", name), res, GR.PARAM_SEED, batch_seed, n_sample_key="act_n_sample", n_sample=n_sample,
+                 meta_key="activations", meta=meta)
 
 
 if __name__ == "__main__":

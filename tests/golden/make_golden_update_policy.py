@@ -23,7 +23,6 @@ The file names do not start with "update_": tests/test_reference_update.py and t
 update_*.npz through the launcher's distribution.  tests/test_policy_modes_{cpu,gpu}.py read these files.
 """
 import contextlib
-import json
 import os
 import sys
 
@@ -33,10 +32,10 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.dirname(HERE))
-from oracle import golden_update as G  # noqa: E402
 from oracle import ref_update_runner as RR  # noqa: E402
-from oracle import ref_update_shim as R  # noqa: E402
+import golden_replay as GR  # noqa: E402
 import policy_modes as PM  # noqa: E402
+import variant_recorder as VR  # noqa: E402
 
 ONLY = [a for a in sys.argv[1:] if not a.startswith("-")]
 
@@ -44,37 +43,23 @@ ONLY = [a for a in sys.argv[1:] if not a.startswith("-")]
 @contextlib.contextmanager
 def reference_policy(cfg, std, squash, stddevs):
     """create_states / create_drq with this distribution, the run's leaf table for it, and every forward_policy's stddev recorded"""
-    R.install(True)
-    from jax._core import raw
-    from serl_launcher.agents.continuous.drq import DrQAgent
-    from serl_launcher.agents.continuous.sac import SACAgent
-    saved = []
-    for target, name in ((SACAgent, "create_states"), (DrQAgent, "create_drq")):
-        cm = target.__dict__[name]
-        saved.append((target, name, cm))
+    with VR.reference_create_overrides({"policy_kwargs": {"std_parameterization": std, "tanh_squash_distribution": squash}}):
+        from jax._core import raw
+        from serl_launcher.agents.continuous.sac import SACAgent
+        fp = SACAgent.__dict__["forward_policy"]
 
-        def patched(cls, *a, _orig=cm.__func__, **k):
-            assert "policy_kwargs" in k, "the factory no longer passes policy_kwargs by keyword"
-            k["policy_kwargs"] = {**k["policy_kwargs"], "std_parameterization": std, "tanh_squash_distribution": squash}
-            return _orig(cls, *a, **k)
-        setattr(target, name, classmethod(patched))
-    fp = SACAgent.__dict__["forward_policy"]
-    saved.append((SACAgent, "forward_policy", fp))
-
-    def forward_policy(self, *a, _orig=fp, **k):
-        dist = _orig(self, *a, **k)
-        base = dist.distribution if squash else dist     # (the tanh distribution's own stddev() is tanh of the Gaussian's)
-        stddevs.append(np.asarray(raw(base.stddev()).detach().cpu().numpy(), np.float64))
-        return dist
-    SACAgent.forward_policy = forward_policy
-    paths = RR.theta_flax_paths
-    RR.theta_flax_paths = lambda c: PM.flax_paths(c, std)
-    try:
-        yield
-    finally:
-        RR.theta_flax_paths = paths
-        for target, name, cm in saved:
-            setattr(target, name, cm)
+        def forward_policy(self, *a, _orig=fp, **k):
+            dist = _orig(self, *a, **k)
+            base = dist.distribution if squash else dist     # (the tanh distribution's own stddev() is tanh of the Gaussian's)
+            stddevs.append(np.asarray(raw(base.stddev()).detach().cpu().numpy(), np.float64))
+            return dist
+        SACAgent.forward_policy = forward_policy
+        paths = RR.theta_flax_paths
+        RR.theta_flax_paths = lambda c: PM.flax_paths(c, std)
+        try:
+            yield
+        finally:
+            RR.theta_flax_paths, SACAgent.forward_policy = paths, fp
 
 
 def check_tree(tree, std):
@@ -104,29 +89,19 @@ def main():
         if ONLY and name not in ONLY:
             continue
         os.environ.pop("SERL_JAXSHIM_PRNG", None)
-        G.N_SAMPLE = n_sample
         stddevs = []
         with reference_policy(cfg, std, squash, stddevs):
-            res = RR.run_reference(cfg, B, sched, PM.PARAM_SEED, PM.BATCH_SEED,
+            res = RR.run_reference(cfg, B, sched, GR.PARAM_SEED, GR.BATCH_SEED,
                                    theta_transform=lambda th, c: PM.mode_theta(th, c, std, regime))
         holds = check_tree(res["final"]["param_tree"], std)
         assert set(res["final"]["params"]) == set(PM.leaf_names(cfg, std))
         assert stddevs and all(s.shape[-1] == cfg.A for s in stddevs)
-        res["prng"] = "philox"
-        rec = G.pack(res, PM.PARAM_SEED, PM.BATCH_SEED)
-        meta = json.loads(str(rec["meta"]))
-        meta["policy"] = {"std_parameterization": std, "tanh_squash_distribution": squash, "regime": regime, "std_leaves": holds,
-                          "transform": "policy_modes.mode_theta", "log_stds_seed": PM.LOG_STDS_SEED, "clip_cycle": list(PM.CLIP_CYCLE),
-                          "policy_evaluations": len(stddevs)}
-        if regime == "trained":
-            rec["policy_clip_low"], rec["policy_clip_high"] = clip_fractions(cfg, stddevs)
-        rec["meta"] = np.array(json.dumps(meta))
-        path = PM.golden_path(name)
-        np.savez_compressed(path, policy_n_sample=np.int64(n_sample), **rec)
-        size = os.path.getsize(path)
-        assert size < 1 << 20, (path, size)
-        print(name, "->", path, f"{size / 1e6:.2f} MB", "final step", res["final"]["step"],
-              {k: round(v, 6) for k, v in res["steps"][-1]["info"].items()})
+        meta = {"std_parameterization": std, "tanh_squash_distribution": squash, "regime": regime, "std_leaves": holds,
+                "transform": "policy_modes.mode_theta", "log_stds_seed": PM.LOG_STDS_SEED, "clip_cycle": list(PM.CLIP_CYCLE),
+                "policy_evaluations": len(stddevs)}
+        extra = dict(zip(("policy_clip_low", "policy_clip_high"), clip_fractions(cfg, stddevs))) if regime == "trained" else None
+        VR.write(GR.variant_path("policy", name), res, GR.PARAM_SEED, GR.BATCH_SEED, n_sample_key="policy_n_sample", n_sample=n_sample,
+                 meta_key="policy", meta=meta, extra=extra)
 
 
 if __name__ == "__main__":

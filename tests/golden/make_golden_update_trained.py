@@ -18,20 +18,17 @@ lagrange value and the mask mode, and the readers (trained_regime.update_golden)
 The file names do not start with "update_": tests/test_reference_update.py and tests/test_golden_update_gpu.py run every
 update_*.npz from O.init_params(param_seed) alone.  tests/test_trained_regime_{cpu,gpu}.py read these files.
 """
-import json
 import os
 import sys
-
-import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.dirname(HERE))
 from oracle import drq_oracle as O  # noqa: E402
-from oracle import golden_update as G  # noqa: E402
 from oracle import ref_update_runner as RR  # noqa: E402
 import trained_regime as TR  # noqa: E402
+import variant_recorder as VR  # noqa: E402
 
 PARAM_SEED, BATCH_SEED = 42, 100
 SCHEDULE = [("critics",), ("high_utd", 2), ("update", ("actor", "critic", "temperature")), ("critics",)]
@@ -51,23 +48,14 @@ def main():
         if ONLY and name not in ONLY:
             continue
         os.environ.pop("SERL_JAXSHIM_PRNG", None)
-        G.N_SAMPLE = n_sample
         res = RR.run_reference(cfg, B, SCHEDULE_STATE if cfg.state_only else SCHEDULE, PARAM_SEED, BATCH_SEED,
                                theta_transform=lambda th, c: TR.trained_like(th, c, lam=lam),
                                target_transform=TR.perturb_target, batch_transform=TR.golden_batch_transform(mode))
-        res["prng"] = "philox"
-        rec = G.pack(res, PARAM_SEED, BATCH_SEED)
-        meta = json.loads(str(rec["meta"]))
-        meta["trained"] = {"transform": "trained_like", "seed": TR.TRANSFORM_SEED, "target_transform": "perturb_target",
-                           "target_seed": TR.TARGET_SEED, "batch_transform": "harden_batch", "batch_seed": TR.BATCH_SEED,
-                           "lam": lam, "mask_mode": mode}
-        rec["meta"] = np.array(json.dumps(meta))
-        path = os.path.join(HERE, f"trained_update_{name}.npz")
-        np.savez_compressed(path, trained_n_sample=np.int64(n_sample), **rec)
-        size = os.path.getsize(path)
-        assert size < 1 << 20, (path, size)
-        print(name, "->", path, f"{size / 1e6:.2f} MB", "final step", res["final"]["step"],
-              {k: round(v, 6) for k, v in res["steps"][-1]["info"].items()})
+        meta = {"transform": "trained_like", "seed": TR.TRANSFORM_SEED, "target_transform": "perturb_target",
+                "target_seed": TR.TARGET_SEED, "batch_transform": "harden_batch", "batch_seed": TR.BATCH_SEED,
+                "lam": lam, "mask_mode": mode}
+        VR.write(os.path.join(HERE, f"trained_update_{name}.npz"), res, PARAM_SEED, BATCH_SEED, n_sample_key="trained_n_sample",
+                 n_sample=n_sample, meta_key="trained", meta=meta)
 
 
 if __name__ == "__main__":

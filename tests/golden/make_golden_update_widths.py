@@ -17,7 +17,6 @@ The file names do not start with "update_" / "init_": tests/test_reference_updat
 tests/test_init_reference_{cpu,gpu}.py run every update_*.npz / init_*.npz through the launcher factories, which build width 256.
 tests/test_mlp_widths_{cpu,gpu}.py read these files.
 """
-import contextlib
 import importlib.util
 import os
 import sys
@@ -30,12 +29,12 @@ sys.path.insert(0, ROOT)
 from oracle import drq_oracle as O  # noqa: E402
 from oracle import golden_update as G  # noqa: E402
 from oracle import ref_update_runner as RR  # noqa: E402
-from oracle import ref_update_shim as R  # noqa: E402
+import variant_recorder as VR  # noqa: E402
 
 PARAM_SEED, BATCH_SEED = 42, 100
 # name: (config, batch rows, schedule, sampled elements per large leaf).  make_golden_update.py keeps 2048 samples; the pixel case
-# keeps 1024 so that the file stays under 1 MiB.  Every file records its count as "widths_n_sample" (the readers set
-# oracle.golden_update.N_SAMPLE from it, as tests/init_golden_helpers.py does for init_*.npz).
+# keeps 1024 so that the file stays under 1 MiB.  Every file records its count as "widths_n_sample" (the readers take it from
+# the records themselves).
 UPDATE_CASES = {
     "sac_state_w128": (O.Config(image_keys=(), S=10, A=4, discount=0.99, warmup=2000, temp_warmup=0, hidden=128), 8,
                        [("high_utd", 2), ("update", ("actor", "critic", "temperature")), ("high_utd", 1)], 2048),
@@ -47,28 +46,9 @@ INIT_CASES = {
 ONLY = [a for a in sys.argv[1:] if not a.startswith("-")]
 
 
-@contextlib.contextmanager
 def reference_width(h):
     """SACAgent.create_states / DrQAgent.create_drq called with hidden_dims=[h, h] whatever the caller passes"""
-    R.install(True)
-    from serl_launcher.agents.continuous.drq import DrQAgent
-    from serl_launcher.agents.continuous.sac import SACAgent
-    saved = []
-    for target, name in ((SACAgent, "create_states"), (DrQAgent, "create_drq")):
-        cm = target.__dict__[name]
-        saved.append((target, name, cm))
-
-        def patched(cls, *a, _orig=cm.__func__, **k):
-            for nk in ("critic_network_kwargs", "policy_network_kwargs"):
-                assert nk in k, f"the factory no longer passes {nk} by keyword"
-                k[nk] = {**k[nk], "hidden_dims": [h, h]}
-            return _orig(cls, *a, **k)
-        setattr(target, name, classmethod(patched))
-    try:
-        yield
-    finally:
-        for target, name, cm in saved:
-            setattr(target, name, cm)
+    return VR.reference_create_overrides({nk: {"hidden_dims": [h, h]} for nk in ("critic_network_kwargs", "policy_network_kwargs")})
 
 
 def _check_width(res_tree, cfg):
@@ -82,25 +62,21 @@ def main():
         if ONLY and f"update_{name}" not in ONLY:
             continue
         os.environ.pop("SERL_JAXSHIM_PRNG", None)
-        G.N_SAMPLE = n_sample
         with reference_width(cfg.hidden):
             res = RR.run_reference(cfg, B, sched, PARAM_SEED, BATCH_SEED)
         _check_width(res["final"]["param_tree"], cfg)
-        res["prng"] = "philox"
-        path = os.path.join(HERE, f"widths_update_{name}.npz")
-        np.savez_compressed(path, widths_n_sample=np.int64(n_sample), **G.pack(res, PARAM_SEED, BATCH_SEED))
-        print(name, "->", path, f"{os.path.getsize(path) / 1e6:.2f} MB", "final step", res["final"]["step"],
-              {k: round(v, 6) for k, v in res["steps"][-1]["info"].items()})
+        VR.write(os.path.join(HERE, f"widths_update_{name}.npz"), res, PARAM_SEED, BATCH_SEED, n_sample_key="widths_n_sample",
+                 n_sample=n_sample)
     for name, (cfg, B, sched) in INIT_CASES.items():
         if ONLY and f"init_{name}" not in ONLY:
             continue
         spec = importlib.util.spec_from_file_location("make_golden_init", os.path.join(HERE, "make_golden_init.py"))
         mi = importlib.util.module_from_spec(spec)
-        spec.loader.exec_module(mi)          # sets SERL_JAXSHIM_PRNG=threefry and G.N_SAMPLE = 512, as for init_*.npz
+        spec.loader.exec_module(mi)          # sets SERL_JAXSHIM_PRNG=threefry; records mi.N_SAMPLE = 512 samples, as for init_*.npz
         with reference_width(cfg.hidden):
             rec = mi.run_agent_case(cfg, B, sched)
         assert tuple(rec["init_shape/actor/w2"]) == (cfg.hidden, cfg.hidden), rec["init_shape/actor/w2"]
-        rec["widths_n_sample"] = np.int64(G.N_SAMPLE)
+        rec["widths_n_sample"] = np.int64(mi.N_SAMPLE)
         rec["init_cfg"] = np.frombuffer(repr(G.cfg_to_dict(cfg)).encode(), np.uint8)
         path = os.path.join(HERE, f"widths_init_{name}.npz")
         np.savez_compressed(path, **rec)

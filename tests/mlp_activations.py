@@ -4,18 +4,14 @@ arguments of serl_agent_create_mlp), the table of the act_*.npz fixtures, the pa
 float64 restatement of the two MLPs that takes the activation as a parameter: oracle.drq_oracle's policy_head and critic_forward,
 replaced at run time (`oracle_activations`), so that the oracle's own update code -- and autograd for the backward -- runs on it."""
 import contextlib
-import json
-import os
 
 import numpy as np
 import torch
 
 from oracle import drq_oracle as O
-from oracle import golden_update as G
+import golden_replay as GR
 import trained_regime as TR
 
-GOLDEN_DIR = os.path.join(os.path.dirname(__file__), "golden")
-PARAM_SEED, BATCH_SEED = 42, 100
 KINK_MIN = 1e-4        # the smallest |pre-activation| a relu comparison may contain (see `Recorder`)
 KINK_SEEDS = 10
 
@@ -28,15 +24,13 @@ def network_kwargs(act, h=256):
     return {"activations": act, "use_layer_norm": True, "hidden_dims": [h, h]}
 
 
-_STATE = dict(image_keys=(), S=10, A=5, discount=0.99, temp_warmup=0)
-_STATE_SCHED = [("high_utd", 2), ("update", ("actor", "critic", "temperature")), ("high_utd", 1)]
 # name -> (oracle Config, rows, schedule, (critic activation, policy activation), regime, sampled elements per large leaf).
-# State-only: B = 72 = two 64-row head tiles, the second ragged, divisible by the UTD; A = 5 is odd.
+# State-only: golden_replay's shared shape.
 GOLDEN = {
-    "update_sac_state_swish": (O.Config(warmup=2000, **_STATE), 72, _STATE_SCHED, ("swish", "swish"), "init", 1024),
-    "update_sac_state_relu": (O.Config(warmup=2000, **_STATE), 72, _STATE_SCHED, ("relu", "relu"), "kink_margin", 1024),
-    "update_sac_state_mixed": (O.Config(warmup=2000, **_STATE), 72, _STATE_SCHED, ("relu", "swish"), "kink_margin", 1024),
-    "trained_sac_state_swish": (O.Config(warmup=4, **_STATE), 72, _STATE_SCHED, ("swish", "swish"), "trained", 1024),
+    "update_sac_state_swish": (O.Config(warmup=2000, **GR.STATE), 72, GR.STATE_SCHED, ("swish", "swish"), "init", 1024),
+    "update_sac_state_relu": (O.Config(warmup=2000, **GR.STATE), 72, GR.STATE_SCHED, ("relu", "relu"), "kink_margin", 1024),
+    "update_sac_state_mixed": (O.Config(warmup=2000, **GR.STATE), 72, GR.STATE_SCHED, ("relu", "swish"), "kink_margin", 1024),
+    "trained_sac_state_swish": (O.Config(warmup=4, **GR.STATE), 72, GR.STATE_SCHED, ("swish", "swish"), "trained", 1024),
     "update_drq_swish": (O.Config(image_keys=("image",), H=64, W=64, S=5, A=3), 6, [("critics",), ("high_utd", 2)],
                          ("swish", "swish"), "init", 1024),
 }
@@ -91,24 +85,10 @@ def act_theta(theta, cfg, regime):
     return {k: np.array(v, np.float32) for k, v in theta.items()}
 
 
-def golden_path(name):
-    return os.path.join(GOLDEN_DIR, f"act_{name}.npz")
-
-
-def load_golden(name, monkeypatch=None):
-    """-> (G.unpack of tests/golden/act_<name>.npz, its meta["activations"], the npz)"""
-    z = np.load(golden_path(name))
-    if monkeypatch is not None:
-        monkeypatch.setattr(G, "N_SAMPLE", int(z["act_n_sample"]))
-    meta = json.loads(str(z["meta"]))
-    return (G.unpack(z) if monkeypatch is not None else None), meta["activations"], z
-
-
 def initial_leaves(name):
     """-> (trunk, theta) the run of fixture `name` started from, oracle names"""
     cfg, _, _, _, regime, _ = GOLDEN[name]
-    trunk, theta = O.init_params(cfg, PARAM_SEED)
-    return trunk, act_theta(theta, cfg, regime)
+    return GR.initial_leaves(cfg, lambda theta, c: act_theta(theta, c, regime))
 
 
 class Kink(Exception):
@@ -201,28 +181,3 @@ def oracle_activations(critic, policy, recs=None):
         yield
     finally:
         O.policy_head, O.critic_forward = saved
-
-
-def core_with(cfg, B, critic, policy, theta, trunk=None, fuse=None):
-    """AgentCore with these activations holding `theta` (oracle names) in params and target_params"""
-    import agent_helpers as AH
-    from serl_amd.agents.core import AgentCore
-    old = os.environ.get("SERL_CHAIN_FUSE")
-    try:
-        if fuse is not None:
-            os.environ["SERL_CHAIN_FUSE"] = "1" if fuse else "0"
-        core = AgentCore(encoder_type=cfg.encoder_type, n_cam=cfg.n_cam, H=cfg.H, W=cfg.W, state_dim=cfg.S, act_dim=cfg.A, batch=B,
-                         ensemble=cfg.ensemble, hidden=cfg.hidden, discount=cfg.discount, tau=cfg.tau, lr=cfg.lr,
-                         warmup_steps=cfg.warmup, dropout=cfg.dropout, std_min=cfg.std_min, std_max=cfg.std_max,
-                         target_entropy=cfg.target_entropy, seed=0,
-                         temp_warmup_steps=-1 if cfg.temp_warmup is None else cfg.temp_warmup,
-                         critic_activation=critic, policy_activation=policy)
-    finally:
-        if old is None:
-            os.environ.pop("SERL_CHAIN_FUSE", None)
-        else:
-            os.environ["SERL_CHAIN_FUSE"] = old
-    for sec in ("params", "target_params"):
-        core.load_flat(sec, trunk or {})
-        core.load_flat(sec, {AH.product_name(k, cfg.image_keys): v for k, v in theta.items()})
-    return core

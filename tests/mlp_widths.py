@@ -1,15 +1,13 @@
 """Shared by tests/test_mlp_widths_cpu.py and tests/test_mlp_widths_gpu.py: the table of MLP widths (serl_agent_cfg.hidden,
-hidden_dims=[h, h]) the parity tests run, the agent pair at a width, and the readers of tests/golden/widths_*.npz
-(tests/golden/make_golden_update_widths.py)."""
+hidden_dims=[h, h]) the parity tests run, the reference's create calls at a width, and the reader of
+tests/golden/widths_init_*.npz (tests/golden/make_golden_update_widths.py; widths_update_*.npz: golden_replay.load_variant)."""
 import ast
 import os
 
 import numpy as np
-import torch
 
 from oracle import drq_oracle as O
 from oracle import golden_update as G
-import agent_helpers as AH
 
 GOLDEN_DIR = os.path.join(os.path.dirname(__file__), "golden")
 UPDATE_GOLDEN = ("sac_state_w128", "drq_w320")
@@ -47,48 +45,12 @@ def case_config(case):
     return config(hidden, kind, ensemble), B, utd
 
 
-def pair(cfg, B, fuse=None, trunk_mode=None):
-    """AH.make_pair plus hidden=cfg.hidden -> (oracle TrainState, AgentCore) holding identical parameters.  fuse: None = the
-    default chain, True / False = SERL_CHAIN_FUSE 1 / 0 (the switch is read when an agent is created)."""
-    from serl_amd.agents.core import AgentCore
-    trunk, theta = O.init_params(cfg, 42)
-    st = O.TrainState(cfg, trunk, theta, torch.float64)
-    old = os.environ.get("SERL_CHAIN_FUSE")
-    try:
-        if fuse is not None:
-            os.environ["SERL_CHAIN_FUSE"] = "1" if fuse else "0"
-        core = AgentCore(encoder_type=cfg.encoder_type, n_cam=cfg.n_cam, H=cfg.H, W=cfg.W, state_dim=cfg.S, act_dim=cfg.A, batch=B,
-                         ensemble=cfg.ensemble, hidden=cfg.hidden, discount=cfg.discount, tau=cfg.tau, lr=cfg.lr,
-                         warmup_steps=cfg.warmup, dropout=cfg.dropout, std_min=cfg.std_min, std_max=cfg.std_max,
-                         target_entropy=cfg.target_entropy, seed=0,
-                         temp_warmup_steps=-1 if cfg.temp_warmup is None else cfg.temp_warmup)
-    finally:
-        if old is None:
-            os.environ.pop("SERL_CHAIN_FUSE", None)
-        else:
-            os.environ["SERL_CHAIN_FUSE"] = old
-    if trunk_mode is not None:
-        core.set_trunk_mode(trunk_mode)
-    for sec in ("params", "target_params"):
-        core.load_flat(sec, trunk)
-        core.load_flat(sec, {AH.product_name(k, cfg.image_keys): v for k, v in theta.items()})
-    return st, core
-
-
-def update_golden(name, monkeypatch):
-    """G.unpack of tests/golden/widths_update_<name>.npz, read with the sample count the file was written with"""
-    z = np.load(os.path.join(GOLDEN_DIR, f"widths_update_{name}.npz"))
-    monkeypatch.setattr(G, "N_SAMPLE", int(z["widths_n_sample"]))
-    return G.unpack(z)
-
-
-def init_golden(monkeypatch):
+def init_golden():
     """tests/golden/widths_init_sac_state_w128.npz in the form of init_golden_helpers.load: (npz, cfg, {leaf: (name, record)},
-    {leaf: shape}); oracle.golden_update.N_SAMPLE follows the file."""
+    {leaf: shape})"""
     import init_golden_helpers as IG
     z = np.load(os.path.join(GOLDEN_DIR, f"widths_init_{INIT_GOLDEN}.npz"))
     assert int(z["widths_n_sample"]) == IG.N_SAMPLE
-    monkeypatch.setattr(G, "N_SAMPLE", IG.N_SAMPLE)
     cfg = G.cfg_from_dict(ast.literal_eval(bytes(z["init_cfg"]).decode()))
     leaves = {}
     for k in z.files:

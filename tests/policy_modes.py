@@ -2,20 +2,17 @@
 policy distributions beside the launcher's (std_parameterization "exp" / "softplus" / "uniform" x tanh_squash_distribution True /
 False; the std_param / no_tanh arguments of serl_agent_create_policy), the table of the policy_*.npz fixtures, the parameters each fixture's run starts from,
 and a float64 restatement of the policy head (actor_critic_nets.py:189-227, distrax MultivariateNormalDiag [+ Tanh])."""
-import json
 import math
-import os
 
 import numpy as np
 import torch
 
 from oracle import drq_oracle as O
-from oracle import golden_update as G
 import agent_helpers as AH
+import golden_replay as GR
 import trained_regime as TR
 
-GOLDEN_DIR = os.path.join(os.path.dirname(__file__), "golden")
-PARAM_SEED, BATCH_SEED, LOG_STDS_SEED = 42, 100, 17
+LOG_STDS_SEED = 17
 
 # (std_parameterization, tanh_squash_distribution); the first is what utils/launcher.py writes down and every other test runs
 DEFAULT_MODE = ("exp", True)
@@ -34,19 +31,17 @@ def policy_kwargs(std, squash):
 # by a few tenths: the bias decides.
 CLIP_CYCLE = (-14.0, -3.0, 0.5, 7.0)
 
-_STATE = dict(image_keys=(), S=10, A=5, discount=0.99, temp_warmup=0)
-_STATE_SCHED = [("high_utd", 2), ("update", ("actor", "critic", "temperature")), ("high_utd", 1)]
-# name -> (oracle Config, rows, schedule, (std, squash), regime, sampled elements per large leaf).  State-only: B = 72 = two 64-row
-# head tiles, the second ragged, divisible by the UTD; A = 5 is odd.  The pixel case is create_drq's own default pair.
+# name -> (oracle Config, rows, schedule, (std, squash), regime, sampled elements per large leaf).  State-only: golden_replay's
+# shared shape.  The pixel case is create_drq's own default pair.
 GOLDEN = {
-    "update_sac_state_softplus": (O.Config(warmup=2000, **_STATE), 72, _STATE_SCHED, ("softplus", True), "init", 1024),
-    "update_sac_state_gauss": (O.Config(warmup=2000, **_STATE), 72, _STATE_SCHED, ("exp", False), "init", 1024),
-    "update_sac_state_uniform": (O.Config(warmup=2000, **_STATE), 72, _STATE_SCHED, ("uniform", True), "init", 1024),
-    "update_sac_state_uniform_gauss": (O.Config(warmup=2000, **_STATE), 72, _STATE_SCHED, ("uniform", False), "init", 1024),
+    "update_sac_state_softplus": (O.Config(warmup=2000, **GR.STATE), 72, GR.STATE_SCHED, ("softplus", True), "init", 1024),
+    "update_sac_state_gauss": (O.Config(warmup=2000, **GR.STATE), 72, GR.STATE_SCHED, ("exp", False), "init", 1024),
+    "update_sac_state_uniform": (O.Config(warmup=2000, **GR.STATE), 72, GR.STATE_SCHED, ("uniform", True), "init", 1024),
+    "update_sac_state_uniform_gauss": (O.Config(warmup=2000, **GR.STATE), 72, GR.STATE_SCHED, ("uniform", False), "init", 1024),
     "update_drq_uniform": (O.Config(image_keys=("image",), H=64, W=64, S=5, A=3), 6, [("critics",), ("high_utd", 2)],
                            ("uniform", True), "init", 1024),
-    "trained_sac_state_softplus": (O.Config(warmup=4, **_STATE), 72, _STATE_SCHED, ("softplus", True), "trained", 1024),
-    "trained_sac_state_uniform": (O.Config(warmup=4, **_STATE), 72, _STATE_SCHED, ("uniform", True), "trained", 1024),
+    "trained_sac_state_softplus": (O.Config(warmup=4, **GR.STATE), 72, GR.STATE_SCHED, ("softplus", True), "trained", 1024),
+    "trained_sac_state_uniform": (O.Config(warmup=4, **GR.STATE), 72, GR.STATE_SCHED, ("uniform", True), "trained", 1024),
 }
 STD_DENSE = ("actor/logstd/kernel", "actor/logstd/bias")
 
@@ -86,24 +81,10 @@ def flax_paths(cfg, std):
     return {k: prod[AH.product_name(k, cfg.image_keys)][0] for k in leaf_names(cfg, std)}
 
 
-def golden_path(name):
-    return os.path.join(GOLDEN_DIR, f"policy_{name}.npz")
-
-
-def load_golden(name, monkeypatch=None):
-    """-> (G.unpack of tests/golden/policy_<name>.npz, its meta["policy"], the npz)"""
-    z = np.load(golden_path(name))
-    if monkeypatch is not None:
-        monkeypatch.setattr(G, "N_SAMPLE", int(z["policy_n_sample"]))
-    meta = json.loads(str(z["meta"]))
-    return (G.unpack(z) if monkeypatch is not None else None), meta["policy"], z
-
-
 def initial_leaves(name):
     """-> (trunk, theta) the run of fixture `name` started from, oracle names"""
     cfg, _, _, (std, _), regime, _ = GOLDEN[name]
-    trunk, theta = O.init_params(cfg, PARAM_SEED)
-    return trunk, mode_theta(theta, cfg, std, regime)
+    return GR.initial_leaves(cfg, lambda theta, c: mode_theta(theta, c, std, regime))
 
 
 def tree_has(tree, path):
@@ -140,28 +121,3 @@ def sample_and_log_prob(mean, sd, eps, squash):
     if not squash:
         return u, lp
     return torch.tanh(u), lp - (2.0 * (math.log(2.0) - u - torch.nn.functional.softplus(-2.0 * u))).sum(-1)
-
-
-def core_with(cfg, B, std, squash, theta, trunk=None, fuse=None, target=None):
-    """AgentCore of this distribution holding `theta` (oracle names) in params and target_params.  fuse: None = the default
-    chain, True / False = SERL_CHAIN_FUSE 1 / 0 (read when an agent is created)."""
-    from serl_amd.agents.core import AgentCore
-    old = os.environ.get("SERL_CHAIN_FUSE")
-    try:
-        if fuse is not None:
-            os.environ["SERL_CHAIN_FUSE"] = "1" if fuse else "0"
-        core = AgentCore(encoder_type=cfg.encoder_type, n_cam=cfg.n_cam, H=cfg.H, W=cfg.W, state_dim=cfg.S, act_dim=cfg.A, batch=B,
-                         ensemble=cfg.ensemble, hidden=cfg.hidden, discount=cfg.discount, tau=cfg.tau, lr=cfg.lr,
-                         warmup_steps=cfg.warmup, dropout=cfg.dropout, std_min=cfg.std_min, std_max=cfg.std_max,
-                         target_entropy=cfg.target_entropy, seed=0,
-                         temp_warmup_steps=-1 if cfg.temp_warmup is None else cfg.temp_warmup,
-                         std_parameterization=std, tanh_squash_distribution=squash)
-    finally:
-        if old is None:
-            os.environ.pop("SERL_CHAIN_FUSE", None)
-        else:
-            os.environ["SERL_CHAIN_FUSE"] = old
-    for sec in ("params", "target_params"):
-        core.load_flat(sec, trunk or {})
-        core.load_flat(sec, {AH.product_name(k, cfg.image_keys): v for k, v in theta.items()})
-    return core

@@ -25,16 +25,7 @@ pytestmark = pytest.mark.gpu
 
 def _core(cfg, B, fuse, **kw):
     """an agent with the given chain variant (the switch is read when an agent is created)"""
-    old = {k: os.environ.get(k) for k in ("SERL_CHAIN_FUSE",)}
-    try:
-        os.environ["SERL_CHAIN_FUSE"] = "1" if fuse else "0"
-        return AH.make_pair(cfg, B, **kw)[1]
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
+    return AH.make_pair(cfg, B, fuse=fuse, **kw)[1]
 
 
 def _pair(cfg, B, **kw):

@@ -16,7 +16,7 @@ from oracle import ref_update_runner as RR
 from serl_amd import jaxrng as J
 from serl_amd.utils import init as pinit
 from serl_amd.utils import init_ref as IR
-from test_golden_update_gpu import _check_draws, _ref_batch
+from golden_replay import check_draws, ref_batch
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-4
@@ -37,8 +37,7 @@ def _make(cfg, B):
 
 
 @pytest.mark.parametrize("path", AGENT_CASES, ids=IG.case_name)
-def test_reference_init_then_one_update_matches_the_reference(gpu, path, monkeypatch):
-    monkeypatch.setattr(G, "N_SAMPLE", IG.N_SAMPLE)
+def test_reference_init_then_one_update_matches_the_reference(gpu, path):
     npz, cfg, recs, _ = IG.load(path)
     g = G.unpack(npz)
     B = g["B"]
@@ -60,7 +59,7 @@ def test_reference_init_then_one_update_matches_the_reference(gpu, path, monkeyp
         crops = None
         if "crop_obs" in step["noise"]:
             crops = (step["noise"]["crop_obs"].astype(np.int32), step["noise"]["crop_next"].astype(np.int32))
-        batch = _ref_batch(cfg, step["batch"])
+        batch = ref_batch(cfg, step["batch"])
         if step["kind"] == "critics":
             agent, info = agent.update_critics(batch)
             flat = dict(info["critic"])
@@ -69,7 +68,7 @@ def test_reference_init_then_one_update_matches_the_reference(gpu, path, monkeyp
             agent, info = agent.update_high_utd(batch, utd_ratio=step["utd"])
             flat = {**info["critic"], **info["actor"], **info["temperature"]}
             n_steps += step["utd"] + 1
-        _check_draws(agent, cfg, B, step, step["noise"], crops)
+        check_draws(agent, cfg, B, step, step["noise"], crops)
         for tx in ("actor", "critic", "temperature"):
             flat[f"{tx}_lr"] = info[f"{tx}_lr"]
         for k, r in step["info"].items():

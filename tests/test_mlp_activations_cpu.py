@@ -26,6 +26,7 @@ import torch
 from oracle import drq_oracle as O
 from oracle import golden_update as G
 from oracle import ref_update_runner as RR
+import golden_replay as GR
 import mlp_activations as MA
 import mlp_widths as MW
 from serl_amd.utils import init as pinit
@@ -36,15 +37,16 @@ SERVED = 'served: activations "tanh", "relu", "swish" (= "silu") by name or as a
 
 
 def _need_golden(name):
-    assert os.path.exists(MA.golden_path(name)), f"{os.path.basename(MA.golden_path(name))} is not recorded"
+    assert os.path.exists(GR.variant_path("act", name)), f"act_{name}.npz is not recorded"
 
 
 # ---- the restatement against the reference's own runs ----------------------------------------------------------------------------
 @pytest.mark.parametrize("name", list(MA.GOLDEN))
-def test_restated_mlps_reproduce_the_reference_golden(name, monkeypatch):
+def test_restated_mlps_reproduce_the_reference_golden(name):
     _need_golden(name)
     cfg, B, sched, (critic, policy), regime, n_sample = MA.GOLDEN[name]
-    g, act, z = MA.load_golden(name, monkeypatch)
+    g, meta, z = GR.load_variant("act", name)
+    act = meta["activations"]
     assert (act["critic"], act["policy"], act["regime"]) == (critic, policy, regime) and int(z["act_n_sample"]) == n_sample
     assert g["B"] == B and [s["kind"] for s in g["steps"]] == [s[0] for s in sched] and g["meta"]["batch_seed"] == act["batch_seed"]
     if "relu" in (critic, policy):      # the fixture's condition, as the generator recorded it; and the kink was crossed
@@ -86,11 +88,11 @@ def test_restated_mlps_reproduce_the_reference_golden(name, monkeypatch):
     print(f"act_{name}: restated MLPs vs reference golden, worst {worst:.1e}")
 
 
-@pytest.mark.parametrize("name", [n for n in MA.GOLDEN if os.path.exists(MA.golden_path(n))])
-def test_golden_differs_from_the_tanh_run(name, monkeypatch):
+@pytest.mark.parametrize("name", [n for n in MA.GOLDEN if os.path.exists(GR.variant_path("act", n))])
+def test_golden_differs_from_the_tanh_run(name):
     """the activation took effect in the reference: the oracle's own tanh MLPs do NOT reproduce the first step's critic loss
     (a missing fixture fails in the test above)"""
-    g, act, _ = MA.load_golden(name, monkeypatch)
+    g = GR.load_variant("act", name)[0]
     trunk, theta = MA.initial_leaves(name)
     st = O.TrainState(g["cfg"], trunk, theta, torch.float64)
     step = g["steps"][0]
@@ -212,7 +214,7 @@ def test_create_mlp_is_declared_exported_and_bound():
 
 def test_golden_files_stay_out_of_the_update_sweeps_and_under_the_size_limit():
     for name in MA.GOLDEN:
-        path = MA.golden_path(name)
+        path = GR.variant_path("act", name)
         assert os.path.basename(path).startswith("act_")
         if os.path.exists(path):
             assert os.path.getsize(path) < 1 << 20
@@ -223,7 +225,7 @@ def test_golden_files_stay_out_of_the_update_sweeps_and_under_the_size_limit():
 def test_kink_margin_leaves_are_what_the_relu_fixtures_started_from():
     cfg = MA.GOLDEN["update_sac_state_relu"][0]
     _, th = MA.initial_leaves("update_sac_state_relu")
-    _, base = O.init_params(cfg, MA.PARAM_SEED)
+    _, base = O.init_params(cfg, GR.PARAM_SEED)
     for k, v in th.items():
         if k.split("/")[-2] in ("ln1", "ln2"):
             rows = v.reshape(-1, v.shape[-1])

@@ -2,7 +2,7 @@
 field of LnFwdArgs / LnBwdArgs in serl_amd/csrc/heads.hip: ln_activate, ln_act_grad).
 
 * the reference's own update code with another activation (tests/golden/act_*.npz, injected noise) through
-  tests/test_policy_modes_gpu.py::_replay: its comparisons, its TOL;
+  tests/golden_replay.py::replay: its comparisons, its TOL;
 * the three row layouts (width 64, blocked 256, strided 2..16 columns per lane) against the restated oracle of
   tests/mlp_activations.py: swish and relu at hidden 64, 192, 256 and 1024, 8 rows x 10 members, and 72 rows at 192 -- one
   update_critics and one update_high_utd(1) each, every gradient leaf, the info scalars, the state;
@@ -26,44 +26,30 @@ import torch
 
 from oracle import drq_oracle as O
 import agent_helpers as AH
+import golden_replay as GR
 import mlp_activations as MA
 import mlp_widths as MW
 from test_agent_gpu import TOL, _compare_state
 from test_mlp_activations_cpu import _need_golden
 from test_mlp_widths_gpu import _Figures, _flat_batch, _grads, _info
-from test_policy_modes_gpu import _replay
 
 pytestmark = pytest.mark.gpu
 
 
 # ---- the reference's own code with another activation ----------------------------------------------------------------------------
-def _golden_agent(cfg, B, critic, policy):
-    opt = {}
-    if cfg.opt or cfg.state_only:
-        sched = O.TrainState(cfg, {}, {}, torch.float64)
-        opt = {f"{tx}_optimizer_kwargs": {k: v for k, v in sched.tx_opt(tx).items() if v is not None} for tx in O.TX_NAMES}
-    nk = dict(critic_network_kwargs=MA.network_kwargs(critic, cfg.hidden), policy_network_kwargs=MA.network_kwargs(policy, cfg.hidden))
-    if cfg.state_only:
-        return MW.sac_agent(cfg.hidden, B=B, S=cfg.S, A=cfg.A, discount=cfg.discount, **nk, **opt)
-    return MW.drq_agent(cfg.hidden, cfg.image_keys, cfg.H, cfg.W, cfg.S, cfg.A, B=B, encoder_type=cfg.encoder_type,
-                        discount=cfg.discount, **nk, **opt)
-
-
 @pytest.mark.parametrize("name", list(MA.GOLDEN))
-def test_hip_update_matches_the_reference_golden_with_activation(gpu, name, monkeypatch):
+def test_hip_update_matches_the_reference_golden_with_activation(gpu, name):
     _need_golden(name)
-    g, act, _ = MA.load_golden(name, monkeypatch)
+    g, meta, _ = GR.load_variant("act", name)
     cfg, B = g["cfg"], g["B"]
-    critic, policy = act["critic"], act["policy"]
+    critic, policy = meta["activations"]["critic"], meta["activations"]["policy"]
     assert (critic, policy) == MA.GOLDEN[name][3] and B == MA.GOLDEN[name][1]
-    agent = _golden_agent(cfg, B, critic, policy)
+    agent = GR.reference_agent(cfg, B, critic_network_kwargs=MA.network_kwargs(critic, cfg.hidden),
+                               policy_network_kwargs=MA.network_kwargs(policy, cfg.hidden))
     assert (agent.config["critic_activation"], agent.config["policy_activation"]) == (critic, policy)
     assert (agent.core.critic_activation, agent.core.policy_activation) == (critic, policy)
-    trunk, theta = MA.initial_leaves(name)
-    for sec in ("params", "target_params"):
-        agent.core.load_flat(sec, trunk)
-        agent.core.load_flat(sec, {AH.product_name(k, cfg.image_keys): v for k, v in theta.items()})
-    _replay(agent, g, list(O.trainable_param_shapes(cfg)), f"act_{name}")
+    AH.load_leaves(agent.core, cfg, *MA.initial_leaves(name))
+    GR.replay(agent, g, label=f"act_{name}")
     assert agent.core.debug("ctr_nonzero", 1)[0] == 0
 
 
@@ -79,6 +65,11 @@ PAIRS = [("swish", "swish"), ("relu", "relu"), ("relu", "swish"), ("swish", "rel
 
 def _row_cfg(hidden):
     return O.Config(image_keys=(), S=10, A=3, discount=0.99, hidden=hidden, ensemble=10)
+
+
+def _core(cfg, B, critic, policy, theta):
+    """AgentCore with these activations holding `theta` (oracle names) in params and target_params"""
+    return AH.load_leaves(AH.make_core(cfg, B, critic_activation=critic, policy_activation=policy), cfg, None, theta)
 
 
 @functools.lru_cache(maxsize=None)
@@ -115,7 +106,7 @@ def _compare_rows(case, critic, policy, margin):
     if k is None:
         pytest.skip(f"{label} {critic}/{policy}: no batch seed among {MA.KINK_SEEDS} keeps every relu pre-activation {margin:g} away from 0 "
                     f"(seed index, the first evaluation's minimum inside the margin): {[(i, float(f'{m:.2g}')) for i, m in side]}")
-    core = MA.core_with(cfg, B, critic, policy, side["theta"])
+    core = _core(cfg, B, critic, policy, side["theta"])
     assert core.cfg.hidden == hidden
     fig = _Figures(f"{label} critic={critic} policy={policy} seed {k}")
     core.update_critics(AH.batch_to_device(cfg, side["b1"]), AH.noise_to_device(cfg, side["n1"]))
@@ -146,7 +137,7 @@ def test_a_tanh_row_case_fails_against_the_swish_oracle(gpu):
     label, hidden, B = ROWS[0]
     cfg = _row_cfg(hidden)
     _, side = _oracle_side(hidden, B, "swish", "swish", MA.KINK_MIN)
-    core = MA.core_with(cfg, B, "tanh", "tanh", side["theta"])
+    core = _core(cfg, B, "tanh", "tanh", side["theta"])
     core.update_critics(AH.batch_to_device(cfg, side["b1"]), AH.noise_to_device(cfg, side["n1"]))
     assert AH.rel_err(core.debug("q", cfg.ensemble * B).reshape(cfg.ensemble, B), side["aux1"]["q"].numpy()) > 100 * TOL
 
@@ -158,9 +149,8 @@ def test_sample_actions_of_a_swish_agent_match_the_restated_policy(gpu, hidden):
     agent = MW.sac_agent(hidden, seed=3, B=B, S=S, A=A, critic_network_kwargs=MA.network_kwargs("relu", hidden),
                          policy_network_kwargs=MA.network_kwargs("swish", hidden))
     cfg = O.Config(image_keys=(), S=S, A=A, discount=0.99, hidden=hidden)
-    theta = MA.act_theta(O.init_params(cfg, MA.PARAM_SEED)[1], cfg, "trained")      # (LayerNorm scales up to 3: swish is not near-linear)
-    for sec in ("params", "target_params"):
-        agent.core.load_flat(sec, {AH.product_name(k, ()): v for k, v in theta.items()})
+    theta = MA.act_theta(O.init_params(cfg, GR.PARAM_SEED)[1], cfg, "trained")      # (LayerNorm scales up to 3: swish is not near-linear)
+    AH.load_leaves(agent.core, cfg, None, theta)
     state = np.random.default_rng(6).standard_normal((B, S)).astype(np.float32)
     th = O.to_torch(theta, torch.float64)
     mean, sd = MA.policy_head(th, cfg, torch.tensor(state, dtype=torch.float64), MA.TORCH_ACT["swish"])
@@ -203,8 +193,7 @@ def test_tanh_through_create_mlp_is_bit_identical_to_serl_agent_create(gpu, hidd
     assert new._acts == (0, 0)
     b, noise = AH.synth_batch(cfg, B, seed=5), O.make_noise(cfg, B, seed=9, utd_ratio=2)
     for core in (old, new):
-        for sec in ("params", "target_params"):
-            core.load_flat(sec, {AH.product_name(k, ()): v for k, v in theta.items()})
+        AH.load_leaves(core, cfg, None, theta)
         core.update_high_utd(AH.batch_to_device(cfg, b), 2, AH.noise_to_device(cfg, noise))
     assert old.step == new.step == 3 and old.read_info() == new.read_info()
     want = _bits(old)

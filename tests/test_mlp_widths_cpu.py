@@ -15,6 +15,7 @@ import torch
 
 from oracle import drq_oracle as O
 from oracle import golden_update as G
+import golden_replay as GR
 import init_golden_helpers as IG
 import mlp_widths as MW
 from serl_amd.agents import flax_tree as FT
@@ -24,8 +25,8 @@ from test_reference_update import F64_TOL, _oracle_sections, _run_oracle
 
 
 @pytest.mark.parametrize("name", MW.UPDATE_GOLDEN)
-def test_oracle_reproduces_the_reference_golden_at_other_widths(name, monkeypatch):
-    g = MW.update_golden(name, monkeypatch)
+def test_oracle_reproduces_the_reference_golden_at_other_widths(name):
+    g = GR.load_variant("widths_update", name)[0]
     cfg = g["cfg"]
     assert cfg.hidden == int(name.rsplit("_w", 1)[1])
     assert g["meta"]["param_tree"]["modules_actor"]["network"]["Dense_1"]["kernel"] == [cfg.hidden, cfg.hidden]
@@ -45,8 +46,8 @@ def test_oracle_reproduces_the_reference_golden_at_other_widths(name, monkeypatc
     print(f"widths_update_{name}: oracle vs reference golden, worst {worst:.1e}")
 
 
-def test_host_twins_equal_the_reference_initial_params_at_width_128(monkeypatch):
-    z, cfg, recs, shapes = MW.init_golden(monkeypatch)
+def test_host_twins_equal_the_reference_initial_params_at_width_128():
+    z, cfg, recs, shapes = MW.init_golden()
     assert cfg.hidden == 128 and shapes["actor/w2"] == (128, 128) and shapes["critic/w1"] == (cfg.ensemble, cfg.S + cfg.A, 128)
     got = IR.theta_reference(cfg.image_keys, cfg.H, cfg.W, cfg.S, cfg.A, 0, ensemble=cfg.ensemble, encoder_type=cfg.encoder_type,
                              temperature_init=1e-2, device=None, hidden=cfg.hidden)
@@ -101,8 +102,8 @@ class _ShapeCore:
 
 @pytest.mark.parametrize("name", MW.UPDATE_GOLDEN)
 @pytest.mark.parametrize("h", [64, 320, 1024])
-def test_shapes_paths_and_export_follow_the_width(name, h, monkeypatch):
-    g = MW.update_golden(name, monkeypatch)
+def test_shapes_paths_and_export_follow_the_width(name, h):
+    g = GR.load_variant("widths_update", name)[0]
     cfg = g["cfg"]
     want = _at_width(g["meta"]["param_tree"], cfg.hidden, h)
     shapes = pinit.theta_shapes(cfg.n_cam, cfg.H, cfg.W, cfg.S, cfg.A, ensemble=cfg.ensemble, hidden=h, encoder_type=cfg.encoder_type)

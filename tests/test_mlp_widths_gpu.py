@@ -18,11 +18,11 @@ import torch
 from oracle import drq_oracle as O
 from oracle import golden_update as G
 import agent_helpers as AH
+import golden_replay as GR
 import init_golden_helpers as IG
 import mlp_widths as MW
 from test_agent_gpu import TOL, _compare_state
 from test_chain_fusion_gpu import _assert_state_bits, _bits_equal, _launches
-from test_golden_update_gpu import _check_draws, _ref_batch
 
 pytestmark = pytest.mark.gpu
 
@@ -61,7 +61,7 @@ def _info(fig, got, info, names):
 @pytest.mark.parametrize("case", MW.CASES, ids=MW.IDS)
 def test_update_critics_matches_the_oracle_at_width(gpu, case):
     cfg, B, _ = MW.case_config(case)
-    st, core = MW.pair(cfg, B)
+    st, core = AH.make_pair(cfg, B)
     assert core.cfg.hidden == cfg.hidden == case[1] and core.leaves["actor/w2"] == cfg.hidden * cfg.hidden
     b = AH.synth_batch(cfg, B, seed=3)
     noise = O.make_noise(cfg, B, seed=7)
@@ -86,7 +86,7 @@ _UTD = [(c, 1) for c in MW.CASES] + [(c, c[5]) for c in MW.CASES if c[5] > 1]
 def test_update_high_utd_matches_the_oracle_at_width(gpu, case, utd):
     cfg, B, _ = MW.case_config(case)
     assert B % utd == 0
-    st, core = MW.pair(cfg, B)
+    st, core = AH.make_pair(cfg, B)
     b = AH.synth_batch(cfg, B, seed=4)
     noise = O.make_noise(cfg, B, seed=8, utd_ratio=utd)
     info, aux = O.update_high_utd(st, AH.batch_to_torch(b, torch.float64), O.noise_to_torch(noise, torch.float64), utd)
@@ -103,7 +103,7 @@ def test_update_high_utd_matches_the_oracle_at_width(gpu, case, utd):
 @pytest.mark.parametrize("case", MW.CASES, ids=MW.IDS)
 def test_sample_actions_match_the_oracle_at_width(gpu, case):
     cfg, B, _ = MW.case_config(case)
-    st, core = MW.pair(cfg, B)
+    st, core = AH.make_pair(cfg, B)
     b = AH.synth_batch(cfg, B, seed=6)
     frames = torch.tensor(np.stack([b["obs"][k] for k in cfg.image_keys]), device="cuda") if cfg.image_keys else None
     state = torch.tensor(b["state"], device="cuda")
@@ -124,7 +124,7 @@ def test_sample_actions_match_the_oracle_at_width(gpu, case):
                          ids=["w192_frozen_B65", "w1024_frozen_B7", "w1024_state_B65_E16"])
 def test_fused_chain_is_bit_identical_to_the_unfused_chain_at_width(gpu, h, kind, B, ensemble):
     cfg = MW.config(h, kind, ensemble)
-    fused, plain = MW.pair(cfg, B, fuse=True)[1], MW.pair(cfg, B, fuse=False)[1]
+    fused, plain = AH.make_pair(cfg, B, fuse=True)[1], AH.make_pair(cfg, B, fuse=False)[1]
     sl, _ = AH.leaf_slices(cfg)
     pc = sl.get("enc/proprio/ln/bias", sl["critic/head/bias"])[1]
     pa0, pa1 = sl.get("enc/proprio/dense/kernel", sl["actor/w1"])[0], sl["actor/logstd/bias"][1]
@@ -153,7 +153,7 @@ def test_fused_chain_is_bit_identical_to_the_unfused_chain_at_width(gpu, h, kind
     # ... and exactly what the same agent launches at 256 (state-only agents have no encoder launches: compared, not pinned)
     cfg256 = MW.config(256, kind, ensemble)
     for name, fuse in (("fused", True), ("plain", False)):
-        core = MW.pair(cfg256, B, fuse=fuse)[1]
+        core = AH.make_pair(cfg256, B, fuse=fuse)[1]
         db, dn = AH.batch_to_device(cfg256, AH.synth_batch(cfg256, B, seed=301)), AH.noise_to_device(cfg256, O.make_noise(cfg256, B, seed=401, utd_ratio=1))
         torch.cuda.synchronize()
         l0 = _launches()
@@ -165,95 +165,24 @@ def test_fused_chain_is_bit_identical_to_the_unfused_chain_at_width(gpu, h, kind
 
 
 # ---- the reference's own code at other widths ------------------------------------------------------------------------------------
-def _golden_agent(cfg, B, param_init="numpy"):
-    opt = {}
-    if cfg.opt or cfg.state_only:
-        sched = O.TrainState(cfg, {}, {}, torch.float64)
-        opt = {f"{tx}_optimizer_kwargs": {k: v for k, v in sched.tx_opt(tx).items() if v is not None} for tx in O.TX_NAMES}
-    if cfg.state_only:
-        return MW.sac_agent(cfg.hidden, B=B, S=cfg.S, A=cfg.A, discount=cfg.discount, param_init=param_init, **opt)
-    return MW.drq_agent(cfg.hidden, cfg.image_keys, cfg.H, cfg.W, cfg.S, cfg.A, B=B, encoder_type=cfg.encoder_type,
-                        discount=cfg.discount, param_init=param_init, **opt)
-
-
 @pytest.mark.parametrize("name", MW.UPDATE_GOLDEN)
-def test_hip_update_matches_the_reference_golden_at_width(gpu, name, monkeypatch):
+def test_hip_update_matches_the_reference_golden_at_width(gpu, name):
     """tests/test_golden_update_gpu.py::test_hip_update_matches_the_reference_golden on widths_update_<name>.npz (injected noise)"""
-    g = MW.update_golden(name, monkeypatch)
-    cfg, B = g["cfg"], g["B"]
-    agent = _golden_agent(cfg, B)
+    g = GR.load_variant("widths_update", name)[0]
+    cfg = g["cfg"]
+    agent = GR.reference_agent(cfg, g["B"])
     assert agent.core.cfg.hidden == cfg.hidden
-    trunk, theta = O.init_params(cfg, g["meta"]["param_seed"])
-    for sec in ("params", "target_params"):
-        agent.core.load_flat(sec, trunk)
-        agent.core.load_flat(sec, {AH.product_name(k, cfg.image_keys): v for k, v in theta.items()})
-    _replay_golden(agent, g, f"widths_update_{name}")
+    AH.load_leaves(agent.core, cfg, *O.init_params(cfg, g["meta"]["param_seed"]))
+    GR.replay(agent, g, label=f"widths_update_{name}")
+    assert agent.core.debug("ctr_nonzero", 1)[0] == 0
 
 
-def _replay_golden(agent, g, label):
-    """the recorded schedule of a reference golden through an agent that holds the run's initial parameters (injected noise), with
-    the comparisons and bounds of tests/test_golden_update_gpu.py; also used by tests/test_trained_regime_gpu.py"""
-    cfg, B = g["cfg"], g["B"]
-    n_steps = 0
-    for i, step in enumerate(g["steps"]):
-        noise = AH.noise_to_device(cfg, {k: (v.astype(np.float32) if k.startswith("eps") else v) for k, v in step["noise"].items()
-                                         if not k.startswith("crop")})
-        crops = None
-        if "crop_obs" in step["noise"]:
-            crops = (step["noise"]["crop_obs"].astype(np.int32), step["noise"]["crop_next"].astype(np.int32))
-        batch = _ref_batch(cfg, step["batch"], unpacked=step["kind"] == "update")
-        if step["kind"] == "critics":
-            agent, info = agent.update_critics(batch, noise=noise, crops=crops)
-            flat = dict(info["critic"])
-            n_steps += 1
-        elif step["kind"] == "high_utd":
-            agent, info = agent.update_high_utd(batch, utd_ratio=step["utd"], noise=noise, crops=crops)
-            flat = {**info["critic"], **info["actor"], **info["temperature"]}
-            n_steps += step["utd"] + 1
-        else:
-            agent, info = agent.update(batch, networks_to_update=frozenset(step["nets"]), noise=noise)
-            flat = {**info["critic"], **info["actor"], **info["temperature"]}
-            n_steps += 1
-        for tx in ("actor", "critic", "temperature"):
-            flat[f"{tx}_lr"] = info[f"{tx}_lr"]
-        for k, r in step["info"].items():
-            assert abs(flat[k] - r) < TOL * max(1.0, abs(r)), (i, step["kind"], k, flat[k], r)
-    assert agent.state.step == g["meta"]["final_step"] == n_steps
-    assert G.shape_tree(agent.state.params) == g["meta"]["param_tree"]
-    assert G.shape_tree(agent.state.target_params) == g["meta"]["param_tree"]
-    assert G.shape_tree(agent.state.opt_states) == g["meta"]["opt_state_tree"]
-    core = agent.core
-    worst_m, worst_p = 0.0, 0.0
-    lr_max = max([cfg.lr] + [kw.get("learning_rate", cfg.lr) for kw in (cfg.opt or {}).values()])
-    for leaf_name in O.trainable_param_shapes(cfg):
-        leaf = AH.product_name(leaf_name, cfg.image_keys)
-        for tx in ("critic", "actor", "temperature"):
-            for mom, sec in (("mu", f"opt/{tx}/mu"), ("nu", f"opt/{tx}/nu")):
-                rec = g["final"][f"{mom}_{tx}"][leaf_name]
-                err, scale = G.leaf_errors(f"{mom}_{tx}/{leaf_name}", rec, core.get(sec, leaf))
-                if scale < 1e-200:
-                    assert err.max() == 0.0, (tx, mom, leaf_name)
-                    continue
-                worst_m = max(worst_m, err.max() / scale)
-                tol = TOL if err.size >= 64 else 3 * TOL      # (the bound of test_golden_update_gpu.py for a handful of elements)
-                assert err.max() / scale < tol, (tx, mom, leaf_name, err.max() / scale)
-        for sec, gsec in (("params", "params"), ("target_params", "target")):
-            err, scale = G.leaf_errors(f"{gsec}/{leaf_name}", g["final"][gsec][leaf_name], core.get(sec, leaf))
-            bulk = float(np.quantile(err, 0.999)) / scale
-            worst_p = max(worst_p, bulk)
-            assert bulk < TOL, (sec, leaf_name, bulk)
-            bound = 2.1 * lr_max * n_steps * (cfg.tau * n_steps if sec == "target_params" else 1.0) + TOL * scale
-            assert err.max() <= bound, (sec, leaf_name, err.max(), bound)
-    print(f"{label}: HIP vs reference golden: Adam moments {worst_m:.1e}, params (99.9 pct) {worst_p:.1e}")
-
-
-def test_reference_init_then_one_update_matches_the_reference_at_width_128(gpu, monkeypatch):
+def test_reference_init_then_one_update_matches_the_reference_at_width_128(gpu):
     """tests/test_init_reference_gpu.py::test_reference_init_then_one_update_matches_the_reference on widths_init_sac_state_w128.npz:
     from the seed only, param_init="reference" """
-    npz, cfg, recs, _ = MW.init_golden(monkeypatch)
+    npz, cfg, recs, _ = MW.init_golden()
     g = G.unpack(npz)
-    B = g["B"]
-    agent = _golden_agent(cfg, B, param_init="reference")
+    agent = GR.reference_agent(cfg, g["B"], param_init="reference")
     core = agent.core
     assert core.cfg.hidden == 128
     bad = [m for n in sorted(recs) for sec in ("params", "target_params") for m in [IG.mismatch(n, recs[n], core.get(sec, n))] if m]
@@ -262,36 +191,8 @@ def test_reference_init_then_one_update_matches_the_reference_at_width_128(gpu, 
         for tx in ("critic", "actor", "temperature"):
             assert not core.get(f"opt/{tx}/mu", n).any() and not core.get(f"opt/{tx}/nu", n).any()
     assert [int(v) for v in agent.state.rng] == g["meta"]["rng0"] == [int(v) for v in npz["init_rng"]]
-    n_steps = 0
-    for step in g["steps"]:
-        batch = _ref_batch(cfg, step["batch"])
-        assert step["kind"] == "high_utd"
-        agent, info = agent.update_high_utd(batch, utd_ratio=step["utd"])
-        flat = {**info["critic"], **info["actor"], **info["temperature"]}
-        n_steps += step["utd"] + 1
-        _check_draws(agent, cfg, B, step, step["noise"], None)
-        for tx in ("actor", "critic", "temperature"):
-            flat[f"{tx}_lr"] = info[f"{tx}_lr"]
-        for k, r in step["info"].items():
-            assert abs(flat[k] - r) < TOL * max(1.0, abs(r)), (step["kind"], k, flat[k], r)
-    assert agent.state.step == g["meta"]["final_step"] == n_steps
-    assert [int(v) for v in agent.state.rng] == g["meta"]["rng_final"]
-    worst = 0.0
-    for name, (gname, _) in recs.items():
-        for tx in ("critic", "actor", "temperature"):
-            for mom in ("mu", "nu"):
-                err, scale = G.leaf_errors(f"{mom}_{tx}/{gname}", g["final"][f"{mom}_{tx}"][gname], core.get(f"opt/{tx}/{mom}", name))
-                if scale < 1e-200:
-                    assert err.max() == 0.0, (tx, mom, name)
-                    continue
-                worst = max(worst, err.max() / scale)
-                assert err.max() / scale < 3 * TOL, (tx, mom, name, err.max() / scale)   # the seed-only bound of the update goldens
-        for sec, gsec in (("params", "params"), ("target_params", "target")):
-            err, scale = G.leaf_errors(f"{gsec}/{gname}", g["final"][gsec][gname], core.get(sec, name))
-            assert float(np.quantile(err, 0.999)) / scale < TOL, (sec, name)
-            lr = 3e-4
-            assert err.max() <= 2.1 * lr * n_steps * (cfg.tau * n_steps if sec == "target_params" else 1.0) + TOL * scale, (sec, name)
-    print(f"widths_init_sac_state_w128: reference init + {n_steps} update(s): Adam moments {worst:.1e}")
+    assert [s["kind"] for s in g["steps"]] == ["high_utd"] and set(recs) == set(O.trainable_param_shapes(cfg))
+    GR.replay(agent, g, seed_only=True, label="widths_init_sac_state_w128")     # (cfg.lr = the 3e-4 of the init goldens' bound)
 
 
 # ---- data-parallel split, checkpoints, the C ABI's refusals --------------------------------------------------------------------
@@ -300,7 +201,7 @@ def test_dp_split_equals_full_batch_at_width_192(gpu):
     global count) sum to the full-batch gradient"""
     cfg = MW.config(192, "frozen", 10)
     B = 16
-    _, core = MW.pair(cfg, B)
+    _, core = AH.make_pair(cfg, B)
     b = AH.synth_batch(cfg, B, seed=5)
     noise = AH.noise_to_device(cfg, O.make_noise(cfg, B, seed=9))
     db = AH.batch_to_device(cfg, b)

@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 from oracle import drq_oracle as O
+import golden_replay as GR
 import policy_modes as PM
 
 from serl_amd.agents import flax_tree as FT
@@ -23,11 +24,10 @@ def _leaf_paths(tree, prefix=()):
 @pytest.mark.parametrize("name", list(PM.GOLDEN))
 def test_golden_records_the_mode_the_reference_ran(name):
     cfg, B, sched, (std, squash), regime, n_sample = PM.GOLDEN[name]
-    _, pol, z = PM.load_golden(name)
+    _, meta, z = GR.load_variant("policy", name)
+    pol = meta["policy"]
     assert (pol["std_parameterization"], pol["tanh_squash_distribution"], pol["regime"]) == (std, squash, regime)
     assert int(z["policy_n_sample"]) == n_sample and pol["clip_cycle"] == list(PM.CLIP_CYCLE) and pol["log_stds_seed"] == PM.LOG_STDS_SEED
-    import json
-    meta = json.loads(str(z["meta"]))
     assert meta["B"] == B and [s[0] for s in meta["schedule"]] == [s[0] for s in sched]
     actor = meta["param_tree"]["modules_actor"]
     if std == "uniform":
@@ -48,10 +48,8 @@ def test_golden_records_the_mode_the_reference_ran(name):
 
 @pytest.mark.parametrize("name", [n for n in PM.GOLDEN if PM.GOLDEN[n][3][0] == "uniform"])
 def test_flax_paths_of_a_uniform_agent_equal_the_recorded_tree(name):
-    import json
     cfg = PM.GOLDEN[name][0]
-    _, _, z = PM.load_golden(name)
-    tree = json.loads(str(z["meta"]))["param_tree"]
+    tree = GR.load_variant("policy", name)[1]["param_tree"]
     etype = cfg.encoder_type
     paths = FT.theta_paths(cfg.image_keys, encoder_type=etype, std_parameterization="uniform")
     shapes = pinit.theta_shapes(cfg.n_cam, cfg.H, cfg.W, cfg.S, cfg.A, ensemble=cfg.ensemble, hidden=cfg.hidden, encoder_type=etype,

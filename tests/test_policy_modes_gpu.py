@@ -2,7 +2,7 @@
 Gaussian (serl_agent_create_policy's std_param / no_tanh; the MODE template parameter of the head kernels in serl_amd/csrc/heads.hip).
 
 * the reference's own update code in every new mode (tests/golden/policy_*.npz, injected noise) with the comparisons and bounds of
-  tests/test_mlp_widths_gpu.py::_replay_golden, walked over the agent's own leaves (a uniform agent has actor/log_stds and no
+  tests/golden_replay.py::replay, walked over the agent's own leaves (a uniform agent has actor/log_stds and no
   log-std Dense), at 72 rows (two head tiles, the second ragged) and A = 5; two of them in the regime where whole std columns clip;
 * sample_actions, mode and injected noise, against the float64 restatement of tests/policy_modes.py;
 * the fused chain against the one-launch-per-operation chain bit for bit at hidden = 192, 65 rows, and a uniform agent's launch count
@@ -16,113 +16,43 @@ import pytest
 import torch
 
 from oracle import drq_oracle as O
-from oracle import golden_update as G
 import agent_helpers as AH
+import golden_replay as GR
 import mlp_widths as MW
 import policy_modes as PM
 from test_agent_gpu import TOL
 from test_chain_fusion_gpu import _assert_state_bits, _bits_equal, _launches
-from test_golden_update_gpu import _ref_batch
 from test_mlp_widths_gpu import _all_bits, _flat_batch
 
 pytestmark = pytest.mark.gpu
 
 
 # ---- the reference's own code in every new mode ----------------------------------------------------------------------------------
-def _golden_agent(cfg, B, std, squash):
-    opt = {}
-    if cfg.opt or cfg.state_only:
-        sched = O.TrainState(cfg, {}, {}, torch.float64)
-        opt = {f"{tx}_optimizer_kwargs": {k: v for k, v in sched.tx_opt(tx).items() if v is not None} for tx in O.TX_NAMES}
-    pk = PM.policy_kwargs(std, squash)
-    if cfg.state_only:
-        return MW.sac_agent(cfg.hidden, B=B, S=cfg.S, A=cfg.A, discount=cfg.discount, policy_kwargs=pk, **opt)
-    return MW.drq_agent(cfg.hidden, cfg.image_keys, cfg.H, cfg.W, cfg.S, cfg.A, B=B, encoder_type=cfg.encoder_type,
-                        discount=cfg.discount, policy_kwargs=pk, **opt)
-
-
-def _replay(agent, g, leaf_names, label):
-    """tests/test_mlp_widths_gpu.py::_replay_golden with the leaves to compare given by the caller: same comparisons, same bounds"""
-    cfg, B = g["cfg"], g["B"]
-    n_steps = 0
-    for i, step in enumerate(g["steps"]):
-        noise = AH.noise_to_device(cfg, {k: (v.astype(np.float32) if k.startswith("eps") else v) for k, v in step["noise"].items()
-                                         if not k.startswith("crop")})
-        crops = None
-        if "crop_obs" in step["noise"]:
-            crops = (step["noise"]["crop_obs"].astype(np.int32), step["noise"]["crop_next"].astype(np.int32))
-        batch = _ref_batch(cfg, step["batch"], unpacked=step["kind"] == "update")
-        if step["kind"] == "critics":
-            agent, info = agent.update_critics(batch, noise=noise, crops=crops)
-            flat = dict(info["critic"])
-            n_steps += 1
-        elif step["kind"] == "high_utd":
-            agent, info = agent.update_high_utd(batch, utd_ratio=step["utd"], noise=noise, crops=crops)
-            flat = {**info["critic"], **info["actor"], **info["temperature"]}
-            n_steps += step["utd"] + 1
-        else:
-            agent, info = agent.update(batch, networks_to_update=frozenset(step["nets"]), noise=noise)
-            flat = {**info["critic"], **info["actor"], **info["temperature"]}
-            n_steps += 1
-        for tx in ("actor", "critic", "temperature"):
-            flat[f"{tx}_lr"] = info[f"{tx}_lr"]
-        for k, r in step["info"].items():
-            print(f"{label}: step {i} {step['kind']} info {k}: {flat[k]:.8g} vs {r:.8g}")
-            assert abs(flat[k] - r) < TOL * max(1.0, abs(r)), (i, step["kind"], k, flat[k], r)
-    assert agent.state.step == g["meta"]["final_step"] == n_steps
-    assert G.shape_tree(agent.state.params) == g["meta"]["param_tree"]
-    assert G.shape_tree(agent.state.target_params) == g["meta"]["param_tree"]
-    assert G.shape_tree(agent.state.opt_states) == g["meta"]["opt_state_tree"]
-    core = agent.core
-    assert {AH.product_name(k, cfg.image_keys) for k in leaf_names} == {k for k in core.leaves if not k.startswith("trunk/")}
-    worst_m, worst_p = 0.0, 0.0
-    lr_max = max([cfg.lr] + [kw.get("learning_rate", cfg.lr) for kw in (cfg.opt or {}).values()])
-    for leaf_name in leaf_names:
-        leaf = AH.product_name(leaf_name, cfg.image_keys)
-        for tx in ("critic", "actor", "temperature"):
-            for mom, sec in (("mu", f"opt/{tx}/mu"), ("nu", f"opt/{tx}/nu")):
-                rec = g["final"][f"{mom}_{tx}"][leaf_name]
-                err, scale = G.leaf_errors(f"{mom}_{tx}/{leaf_name}", rec, core.get(sec, leaf))
-                if scale < 1e-200:
-                    assert err.max() == 0.0, (tx, mom, leaf_name)
-                    continue
-                worst_m = max(worst_m, err.max() / scale)
-                tol = TOL if err.size >= 64 else 3 * TOL      # (a handful of elements: actor/log_stds among them)
-                if leaf_name.startswith("actor/") and tx == "actor" and err.size < 64:
-                    print(f"{label}: {mom}_{tx} {leaf_name}: {err.max() / scale:.2e}")
-                assert err.max() / scale < tol, (tx, mom, leaf_name, err.max() / scale)
-        for sec, gsec in (("params", "params"), ("target_params", "target")):
-            err, scale = G.leaf_errors(f"{gsec}/{leaf_name}", g["final"][gsec][leaf_name], core.get(sec, leaf))
-            bulk = float(np.quantile(err, 0.999)) / scale
-            worst_p = max(worst_p, bulk)
-            assert bulk < TOL, (sec, leaf_name, bulk)
-            bound = 2.1 * lr_max * n_steps * (cfg.tau * n_steps if sec == "target_params" else 1.0) + TOL * scale
-            assert err.max() <= bound, (sec, leaf_name, err.max(), bound)
-    print(f"{label}: HIP vs reference golden: Adam moments {worst_m:.1e}, params (99.9 pct) {worst_p:.1e}")
-
-
 @pytest.mark.parametrize("name", list(PM.GOLDEN))
-def test_hip_update_matches_the_reference_golden_in_mode(gpu, name, monkeypatch):
-    g, pol, _ = PM.load_golden(name, monkeypatch)
+def test_hip_update_matches_the_reference_golden_in_mode(gpu, name):
+    g, meta, _ = GR.load_variant("policy", name)
     cfg, B = g["cfg"], g["B"]
-    std, squash = pol["std_parameterization"], pol["tanh_squash_distribution"]
+    std, squash = meta["policy"]["std_parameterization"], meta["policy"]["tanh_squash_distribution"]
     assert (std, squash) == PM.GOLDEN[name][3] and B == PM.GOLDEN[name][1]
-    agent = _golden_agent(cfg, B, std, squash)
+    agent = GR.reference_agent(cfg, B, policy_kwargs=PM.policy_kwargs(std, squash))
     assert ("actor/log_stds" in agent.core.leaves) == (std == "uniform") == ("actor/logstd/kernel" not in agent.core.leaves)
-    trunk, theta = PM.initial_leaves(name)
-    for sec in ("params", "target_params"):
-        agent.core.load_flat(sec, trunk)
-        agent.core.load_flat(sec, {AH.product_name(k, cfg.image_keys): v for k, v in theta.items()})
-    _replay(agent, g, PM.leaf_names(cfg, std), f"policy_{name}")
+    AH.load_leaves(agent.core, cfg, *PM.initial_leaves(name))
+    GR.replay(agent, g, leaf_names=PM.leaf_names(cfg, std), label=f"policy_{name}")
     assert agent.core.debug("ctr_nonzero", 1)[0] == 0
 
 
 # ---- sample_actions ------------------------------------------------------------------------------------------------------------
+def _core(cfg, B, std, squash, theta, trunk=None, fuse=None):
+    """AgentCore of this distribution holding `theta` (oracle names) in params and target_params"""
+    core = AH.make_core(cfg, B, fuse=fuse, std_parameterization=std, tanh_squash_distribution=squash)
+    return AH.load_leaves(core, cfg, trunk, theta)
+
+
 @pytest.mark.parametrize("std,squash", [PM.DEFAULT_MODE] + PM.NEW_MODES, ids=["exp"] + PM.MODE_IDS)
 def test_sample_actions_match_the_float64_head_in_mode(gpu, std, squash):
     cfg, B = O.Config(image_keys=(), S=10, A=5, discount=0.99), 72
-    theta = PM.mode_theta(O.init_params(cfg, PM.PARAM_SEED)[1], cfg, std, "init")
-    core = PM.core_with(cfg, B, std, squash, theta)
+    theta = PM.mode_theta(O.init_params(cfg, GR.PARAM_SEED)[1], cfg, std, "init")
+    core = _core(cfg, B, std, squash, theta)
     rng = np.random.default_rng(6)
     state = rng.standard_normal((B, cfg.S)).astype(np.float32)
     eps = (2.0 * rng.standard_normal((B, cfg.A))).astype(np.float32)      # (wide enough that unsquashed samples leave [-1, 1])
@@ -172,9 +102,9 @@ _FUSE_CASES = [(s, t, "state") for s, t in PM.NEW_MODES] + [("uniform", True, "f
 @pytest.mark.parametrize("std,squash,kind", _FUSE_CASES, ids=[f"{i}-state" for i in PM.MODE_IDS] + ["uniform-frozen"])
 def test_fused_chain_is_bit_identical_to_the_unfused_chain_in_mode(gpu, std, squash, kind):
     cfg, B = MW.config(192, kind, 10), 65
-    trunk, theta0 = O.init_params(cfg, PM.PARAM_SEED)
+    trunk, theta0 = O.init_params(cfg, GR.PARAM_SEED)
     theta = PM.mode_theta(theta0, cfg, std, "init")
-    fused, plain = (PM.core_with(cfg, B, std, squash, theta, trunk, fuse=f) for f in (True, False))
+    fused, plain = (_core(cfg, B, std, squash, theta, trunk, fuse=f) for f in (True, False))
     sl = _spans(fused)
     last_actor = "actor/log_stds" if std == "uniform" else "actor/logstd/bias"
     pc = sl.get("enc/proprio/ln/bias", sl["critic/head/bias"])[1]
@@ -195,7 +125,7 @@ def test_fused_chain_is_bit_identical_to_the_unfused_chain_in_mode(gpu, std, squ
         _assert_state_bits(cfg, fused, plain, (std, squash, it))
     # a uniform agent's head is one GEMM group less, never a launch more: against the exp agent at the same shape
     for name, fuse in (("fused", True), ("plain", False)):
-        ref = PM.core_with(cfg, B, "exp", True, theta0, trunk, fuse=fuse)
+        ref = _core(cfg, B, "exp", True, theta0, trunk, fuse=fuse)
         n_exp = _pair_launches(ref, cfg, B, AH.synth_batch(cfg, B, seed=301), O.make_noise(cfg, B, seed=401, utd_ratio=1))
         print(f"{std} squash={squash} {kind}: {name} chain launches per critic + actor pair {n_pair[name]}, exp agent {n_exp}")
         assert n_pair[name] <= n_exp, (name, n_pair[name], n_exp)

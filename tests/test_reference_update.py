@@ -80,6 +80,27 @@ def test_golden_fixtures_exist():
     assert len(GOLDEN) >= 8, "tests/golden/update_*.npz missing: run tests/golden/make_golden_update.py in the build container"
 
 
+def test_sampled_records_hold_the_count_their_file_states():
+    """every committed file written by oracle.golden_update.pack: the sample count it states (its *_n_sample key, record_form[1],
+    or, where it stores none, its generator's constant) is the size of every sampled record in it -- the size the readers
+    (G.leaf_compare, G.leaf_errors) draw their indices with"""
+    import init_golden_helpers as IG
+    seen = 0
+    for path in sorted(glob.glob(os.path.join(os.path.dirname(__file__), "golden", "*.npz"))):
+        name = os.path.basename(path)
+        if not name.startswith(("update_", "init_", "live_update_", "widths_", "trained_update_", "policy_", "act_")):
+            continue
+        z = np.load(path)
+        sizes = {k: z[k].size for k in z.files if k.endswith(("|val", "/val"))}
+        if "final_index" in z.files:
+            sizes.update({k: n for k, n in json.loads(str(z["final_index"])) if k.endswith("|val")})
+        stated = [int(z[k]) for k in z.files if k.endswith("_n_sample")] + ([int(z["record_form"][1])] if "record_form" in z.files else [])
+        stated = stated or [IG.N_SAMPLE if name.startswith("init_") else G.N_SAMPLE]
+        assert len(stated) == 1 and sizes and set(sizes.values()) == {stated[0]}, (name, stated, sorted(set(sizes.values())))
+        seen += 1
+    assert seen >= len(GOLDEN) + 20, seen
+
+
 
 class _Records(dict):
     """npz-like view (`.files`, `[key]`) of a live_update_*.npz with its final-state records unpacked from final_data"""
@@ -88,9 +109,9 @@ class _Records(dict):
         return list(self)
 
 
-def _live(name, monkeypatch):
+def _live(name):
     """A reference run recorded by tests/golden/make_golden_live.py (the reference's own update code, fp64).  Its final-state
-    records use a smaller sample per leaf than oracle/golden_update.py's default: the comparison follows the recorded form."""
+    records use a smaller sample per leaf than oracle/golden_update.py's default: the comparison follows each record's size."""
     z = np.load(os.path.join(os.path.dirname(__file__), "golden", f"live_update_{name}.npz"))
     rec = _Records((k, z[k]) for k in z.files if k not in ("final_index", "final_data"))
     data, at = z["final_data"], 0
@@ -98,8 +119,6 @@ def _live(name, monkeypatch):
         rec[key] = data[at:at + n]
         at += n
     assert at == data.size
-    monkeypatch.setattr(G, "FULL_MAX", int(z["record_form"][0]))
-    monkeypatch.setattr(G, "N_SAMPLE", int(z["record_form"][1]))
     return G.unpack(rec), rec
 
 
@@ -113,10 +132,10 @@ def _assert_final_state(st, g, sections=None):
             assert e <= F64_TOL, (sec, name, how, e)
 
 
-def test_live_reference_matches_oracle(monkeypatch):
+def test_live_reference_matches_oracle():
     """A reference run (peg-insertion key names / dims, critics / high_utd(2) / critics) against the oracle: every info
     scalar, the optimizer counts and the whole final train state."""
-    g, z = _live("peg", monkeypatch)
+    g, z = _live("peg")
     cfg = g["cfg"]
     assert cfg.image_keys == ("wrist_1", "wrist_2") and (cfg.H, cfg.W, cfg.S, cfg.A) == (64, 64, 19, 7) and g["B"] == 4
     assert [s["kind"] for s in g["steps"]] == ["critics", "high_utd", "critics"]
@@ -134,11 +153,11 @@ def test_live_reference_matches_oracle(monkeypatch):
     assert float(z["trunk_conv_init_target_drift"]) < 1e-14
 
 
-def test_live_reference_on_jax_key_chain(monkeypatch):
+def test_live_reference_on_jax_key_chain():
     """The same with the stand-in jax.random drawing through JAX's own threefry2x32 key chain (oracle/jaxshim/jax/threefry.py,
     pinned in tests/test_threefry_oracle.py): the reference's split / fold_in / randint / normal / bernoulli calls then consume
     the numbers a real JAX run draws for these keys; the oracle, fed the recorded draws, still agrees."""
-    g, _ = _live("key_chain", monkeypatch)
+    g, _ = _live("key_chain")
     cfg = g["cfg"]
     assert g["meta"]["prng"] == "threefry" and cfg.image_keys == ("front",) and (cfg.S, cfg.A) == (7, 4)
     st, infos = _run_oracle(cfg, g["steps"], 3)

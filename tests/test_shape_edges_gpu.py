@@ -103,23 +103,6 @@ def test_trunk_full_batch_and_per_rank_kernels_at_84_and_96(gpu, H, n, monkeypat
 
 
 # ---- update chain ------------------------------------------------------------------------------------------------------------
-def _pair(cfg, B, trunk_mode=None):
-    """AH.make_pair plus the two creation arguments it does not pass on (critic_subsample_size, backup_entropy)."""
-    from serl_amd.agents.core import AgentCore
-    trunk, theta = O.init_params(cfg, 42)
-    st = O.TrainState(cfg, trunk, theta, torch.float64)
-    core = AgentCore(encoder_type=cfg.encoder_type, n_cam=cfg.n_cam, H=cfg.H, W=cfg.W, state_dim=cfg.S, act_dim=cfg.A, batch=B,
-                     ensemble=cfg.ensemble, discount=cfg.discount, tau=cfg.tau, lr=cfg.lr, warmup_steps=cfg.warmup,
-                     dropout=cfg.dropout, std_min=cfg.std_min, std_max=cfg.std_max, target_entropy=cfg.target_entropy, seed=0,
-                     temp_warmup_steps=-1, critic_subsample_size=cfg.subsample, backup_entropy=cfg.backup_entropy)
-    if trunk_mode is not None:
-        core.set_trunk_mode(trunk_mode)
-    for sec in ("params", "target_params"):
-        core.load_flat(sec, trunk)
-        core.load_flat(sec, {AH.product_name(k, cfg.image_keys): v for k, v in theta.items()})
-    return st, core
-
-
 class _Figures:
     """every figure of a case is printed before the first assertion fails, so one run shows all of them"""
 
@@ -156,7 +139,7 @@ _FROZEN = [c for c in SE.UPDATE_CASES if c[2] == "resnet-pretrained"]
 
 def _critics(case, mode):
     cfg, B, _ = SE.update_config(case)
-    st, core = _pair(cfg, B, trunk_mode=mode)
+    st, core = AH.make_pair(cfg, B, trunk_mode=mode)
     b = AH.synth_batch(cfg, B, seed=3)
     noise = O.make_noise(cfg, B, seed=7)
     info, aux = O.update_critics(st, AH.batch_to_torch(b, torch.float64), O.noise_to_torch(noise, torch.float64))
@@ -190,7 +173,7 @@ _UTD = [(c, 1) for c in SE.UPDATE_CASES] + [(c, c[10]) for c in SE.UPDATE_CASES 
 @pytest.mark.parametrize("case,utd", _UTD, ids=[f"{c[0]}-utd{u}" for c, u in _UTD])
 def test_update_high_utd_at_edge_dimensions(gpu, case, utd):
     cfg, B, _ = SE.update_config(case)
-    st, core = _pair(cfg, B)
+    st, core = AH.make_pair(cfg, B)
     b = AH.synth_batch(cfg, B, seed=4)
     noise = O.make_noise(cfg, B, seed=8, utd_ratio=utd)
     info, aux = O.update_high_utd(st, AH.batch_to_torch(b, torch.float64), O.noise_to_torch(noise, torch.float64), utd)
@@ -207,7 +190,7 @@ def test_update_high_utd_at_edge_dimensions(gpu, case, utd):
 @pytest.mark.parametrize("case", SE.UPDATE_CASES, ids=_IDS)
 def test_sample_actions_at_edge_dimensions(gpu, case):
     cfg, B, _ = SE.update_config(case)
-    st, core = _pair(cfg, B)
+    st, core = AH.make_pair(cfg, B)
     b = AH.synth_batch(cfg, B, seed=6)
     frames = torch.tensor(np.stack([b["obs"][k] for k in cfg.image_keys]), device="cuda") if cfg.image_keys else None
     state = torch.tensor(b["state"], device="cuda")
@@ -335,7 +318,7 @@ def test_replay_crop_update_at_84x96(gpu):
         assert (out.state[0].cpu().numpy() == ob["observations"]["state"][:, 0]).all()
         assert (out.action.cpu().numpy() == ob["actions"]).all() and (out.reward.cpu().numpy() == ob["rewards"]).all()
     cfg = O.Config(image_keys=keys, H=H, W=W, S=S, A=A)
-    st, core = _pair(cfg, B)
+    st, core = AH.make_pair(cfg, B)
     b = {"obs": {k: fr[0, c] for c, k in enumerate(keys)}, "next": {k: fr[1, c] for c, k in enumerate(keys)},
          "state": out.state[0].cpu().numpy(), "next_state": out.state[1].cpu().numpy(), "action": out.action.cpu().numpy(),
          "reward": out.reward.cpu().numpy(), "mask": out.mask.cpu().numpy()}

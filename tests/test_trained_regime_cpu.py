@@ -102,9 +102,9 @@ def _run_oracle(g, theta, target, trunk):
 
 
 @pytest.mark.parametrize("name", TR.UPDATE_GOLDEN)
-def test_oracle_reproduces_the_reference_golden_in_the_regime(name, monkeypatch):
+def test_oracle_reproduces_the_reference_golden_in_the_regime(name):
     """tests/test_reference_update.py::test_oracle_reproduces_the_reference_golden on trained_update_<name>.npz"""
-    g, theta, target, trunk = TR.update_golden(name, monkeypatch)
+    g, theta, target, trunk = TR.update_golden(name)
     cfg = g["cfg"]
     assert cfg.A >= 4 and [s["kind"] for s in g["steps"]] == ([("update" if cfg.state_only else "critics"), "high_utd", "update",
                                                                ("update" if cfg.state_only else "critics")])

@@ -25,10 +25,10 @@ import torch
 
 from oracle import drq_oracle as O
 import agent_helpers as AH
+import golden_replay as GR
 import trained_regime as TR
 from test_agent_gpu import TOL, _check_grads, _compare_state
 from test_chain_fusion_gpu import _assert_state_bits, _bits_equal
-from test_mlp_widths_gpu import _golden_agent, _replay_golden
 
 pytestmark = pytest.mark.gpu
 FUSE = [pytest.param(True, id="fused"), pytest.param(False, id="unfused")]
@@ -206,10 +206,10 @@ def test_sample_actions_match_the_oracle_in_the_regime(gpu, case):
 
 
 @pytest.mark.parametrize("name", TR.UPDATE_GOLDEN)
-def test_hip_update_matches_the_reference_golden_in_the_regime(gpu, name, monkeypatch):
+def test_hip_update_matches_the_reference_golden_in_the_regime(gpu, name):
     """tests/test_golden_update_gpu.py::test_hip_update_matches_the_reference_golden on trained_update_<name>.npz (injected noise)"""
-    g, theta, target, trunk = TR.update_golden(name, monkeypatch)
-    cfg = g["cfg"]
-    agent = _golden_agent(cfg, g["B"])
-    TR.load_core(agent.core, cfg, trunk, theta, target)
-    _replay_golden(agent, g, f"trained_update_{name}")
+    g, theta, target, trunk = TR.update_golden(name)
+    agent = GR.reference_agent(g["cfg"], g["B"])
+    AH.load_leaves(agent.core, g["cfg"], trunk, theta, target)
+    GR.replay(agent, g, label=f"trained_update_{name}")
+    assert agent.core.debug("ctr_nonzero", 1)[0] == 0

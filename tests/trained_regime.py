@@ -7,16 +7,13 @@ and stored actions at exactly +-1, with a target copy that differs from the onli
 
 The recipe is fixed by hand and its conditions are asserted on the fp64 oracle alone (tests/test_trained_regime_cpu.py): if a
 change of the recipe breaks one of them, the recipe is what changes."""
-import os
-
 import numpy as np
 import torch
 
 from oracle import drq_oracle as O
-from oracle import golden_update as G
 import agent_helpers as AH
+import golden_replay as GR
 
-GOLDEN_DIR = os.path.join(os.path.dirname(__file__), "golden")
 UPDATE_GOLDEN = ("sac_state_A4", "drq_64_A5")
 
 LOGSTD_CYCLE = (-14.0, -3.0, 0.5, 3.0)     # column j % 4: below log(std_min) = -11.5 | inside | inside | above log(std_max) = 1.61
@@ -105,35 +102,12 @@ def oracle_state(cfg, lam, dtype=torch.float64, mean_cycle=MEAN_CYCLE, param_see
     return st
 
 
-def load_core(core, cfg, trunk, theta, target):
-    for sec, th in (("params", theta), ("target_params", target)):
-        core.load_flat(sec, trunk)
-        core.load_flat(sec, {AH.product_name(k, cfg.image_keys): v for k, v in th.items()})
-
-
 def pair(cfg, B, lam, fuse=None, mean_cycle=MEAN_CYCLE):
-    """mlp_widths.pair in the trained regime -> (oracle TrainState, AgentCore): trained_like parameters in both, perturb_target in
+    """AH.make_pair in the trained regime -> (oracle TrainState, AgentCore): trained_like parameters in both, perturb_target in
     both target copies.  fuse: None = the default chain, True / False = SERL_CHAIN_FUSE 1 / 0."""
-    from serl_amd.agents.core import AgentCore
     trunk, theta, target = theta_pair(cfg, lam, mean_cycle)
-    st = oracle_state(cfg, lam, torch.float64, mean_cycle)
-    old = os.environ.get("SERL_CHAIN_FUSE")
-    try:
-        if fuse is not None:
-            os.environ["SERL_CHAIN_FUSE"] = "1" if fuse else "0"
-        core = AgentCore(encoder_type=cfg.encoder_type, n_cam=cfg.n_cam, H=cfg.H, W=cfg.W, state_dim=cfg.S, act_dim=cfg.A, batch=B,
-                         ensemble=cfg.ensemble, hidden=cfg.hidden, discount=cfg.discount, tau=cfg.tau, lr=cfg.lr,
-                         warmup_steps=cfg.warmup, dropout=cfg.dropout, std_min=cfg.std_min, std_max=cfg.std_max,
-                         target_entropy=cfg.target_entropy, seed=0,
-                         temp_warmup_steps=-1 if cfg.temp_warmup is None else cfg.temp_warmup,
-                         critic_subsample_size=cfg.subsample, backup_entropy=cfg.backup_entropy)
-    finally:
-        if old is None:
-            os.environ.pop("SERL_CHAIN_FUSE", None)
-        else:
-            os.environ["SERL_CHAIN_FUSE"] = old
-    load_core(core, cfg, trunk, theta, target)
-    return st, core
+    core = AH.load_leaves(AH.make_core(cfg, B, fuse=fuse), cfg, trunk, theta, target)
+    return oracle_state(cfg, lam, torch.float64, mean_cycle), core
 
 
 def _state(A, hidden=256, **kw):
@@ -176,13 +150,11 @@ def golden_batch_transform(mode):
     return transform
 
 
-def update_golden(name, monkeypatch):
-    """G.unpack of tests/golden/trained_update_<name>.npz with the recorded sample count, its batches hardened as the generator
-    hardened them -> (golden, online theta, target theta, trunk)"""
-    z = np.load(os.path.join(GOLDEN_DIR, f"trained_update_{name}.npz"))
-    monkeypatch.setattr(G, "N_SAMPLE", int(z["trained_n_sample"]))
-    g = G.unpack(z)
-    tr = g["meta"]["trained"]
+def update_golden(name):
+    """tests/golden/trained_update_<name>.npz, its batches hardened as the generator hardened them -> (golden, online theta,
+    target theta, trunk)"""
+    g, meta, _ = GR.load_variant("trained_update", name)
+    tr = meta["trained"]
     assert tr["transform"] == "trained_like" and tr["seed"] == TRANSFORM_SEED and tr["target_seed"] == TARGET_SEED
     bt = golden_batch_transform(tr["mask_mode"])
     for i, step in enumerate(g["steps"]):
