@@ -436,7 +436,7 @@ int encode_multi(serl_agent* a, const EncJob* jobs, int n, int off, int cnt, hip
                      Bfull * a->D, (long)c.batch * a->D, st));
   }
   RC(gemm_f32_multi(gd, n, st));
-  RC(ln_tanh_fwd_multi(lv, n, c.bottleneck, st));
+  RC(ln_fwd_multi(lv, n, c.bottleneck, st));
   if (a->fuse && !a->small) return SERL_OK;   // (the proprio branch rode on the SLE launch)
   return proprio_fwd_multi(pv, n, c.state_dim, cnt, st);
 }
@@ -451,8 +451,8 @@ struct DenseJob {
   const float *dot_w, *dot_b; float* dot_out;  // optional fused row-dot (critic head)
   long dot_gstride = 0, dot_b_gstride = 0;      // per-group heads (state-only SAC) or 0 = shared
 };
-int dense_ln_tanh_multi(serl_agent* a, const DenseJob* jobs, int n, int groups, int rows_per_group, int K, int splitk, int act,
-                        hipStream_t st) {
+int dense_ln_multi(serl_agent* a, const DenseJob* jobs, int n, int groups, int rows_per_group, int K, int splitk, int act,
+                   hipStream_t st) {
   const int Hd = a->cfg.hidden;
   SERL_REQUIRE(n >= 1 && n <= 3, "bad dense instance count");
   splitk = split_for(a->split_budget, rows_per_group, Hd, groups * n, splitk);
@@ -476,7 +476,7 @@ int dense_ln_tanh_multi(serl_agent* a, const DenseJob* jobs, int n, int groups, 
     l.act = act;
   }
   RC(gemm_f32_multi(gd, n, st));
-  return ln_tanh_fwd_multi(lv, n, Hd, st);
+  return ln_fwd_multi(lv, n, Hd, st);
 }
 
 // Policy forward + tanh-Gaussian sample (actor_critic_nets.py:179-227) for n independent inputs
@@ -515,8 +515,8 @@ int policy_fwd_multi(serl_agent* a, const PolJob* jobs, int n, int cnt, hipStrea
     pv[i].eps = j.eps; pv[i].act = j.act_out; pv[i].ld_act = j.ld_act; pv[i].logp = pb.logp; pv[i].std_out = pb.std;
     pv[i].sum_logp = j.sum_logp; pv[i].lam = P + o.lam; pv[i].alpha_out = j.alpha_out;
   }
-  RC(dense_ln_tanh_multi(a, d1, n, 1, cnt, a->E, 8, a->policy_act, st));
-  RC(dense_ln_tanh_multi(a, d2, n, 1, cnt, Hd, 4, a->policy_act, st));
+  RC(dense_ln_multi(a, d1, n, 1, cnt, a->E, 8, a->policy_act, st));
+  RC(dense_ln_multi(a, d2, n, 1, cnt, Hd, 4, a->policy_act, st));
   if (a->fuse) {   // the tanh-Gaussian head inside the head GEMM: last arriver of every 64-row tile (heads.hip, kEpiPolicy)
     SERL_REQUIRE(A <= 64, "the fused policy-head epilogue holds one 64-wide slab row per sample (act_dim %d)", A);
     SERL_REQUIRE(cdiv(cnt, 64) <= kCtrPerLane && 8 * pad64(cnt) * 64 <= a->slabs_cap, "policy head exceeds the fused epilogue's scratch");
@@ -563,17 +563,18 @@ int critic_fwd_multi(serl_agent* a, const CritJob* jobs, int n, int cnt, hipStre
     d2[i].dot_gstride = a->state_only ? Hd : 0;
     d2[i].dot_b_gstride = a->state_only ? 1 : 0;
   }
-  RC(dense_ln_tanh_multi(a, d1, n, N, cnt, a->XA, 4, a->critic_act, st));
-  return dense_ln_tanh_multi(a, d2, n, N, cnt, Hd, 2, a->critic_act, st);
+  RC(dense_ln_multi(a, d1, n, N, cnt, a->XA, 4, a->critic_act, st));
+  return dense_ln_multi(a, d2, n, N, cnt, Hd, 2, a->critic_act, st);
 }
 
 LnBwdArgs ln_bwd_args(const float* dy, long ld_dy, long dy_goff, const float* y, long ld_y, long y_goff, const float* xhat,
-                      const float* rstd, const float* gamma, long p_gstride, int groups, int rows_per_group, float* dpre, float* dg) {
+                      const float* rstd, const float* gamma, long p_gstride, int groups, int rows_per_group, int D, float* dpre,
+                      float* dg) {
   LnBwdArgs l{};
   l.dy = dy; l.ld_dy = ld_dy; l.dy_goff = dy_goff;
   l.y = y; l.ld_y = ld_y; l.y_goff = y_goff;
   l.xhat = xhat; l.rstd = rstd; l.gamma = gamma; l.pstride = p_gstride;
-  l.rows = groups * rows_per_group; l.rows_per_group = rows_per_group;
+  l.rows = groups * rows_per_group; l.rows_per_group = rows_per_group; l.D = D;
   l.dx = dpre; l.dg = dg;
   return l;
 }
@@ -582,19 +583,19 @@ LnBwdArgs ln_bwd_args(const float* dy, long ld_dy, long dy_goff, const float* y,
 // dy: [groups*rows][Hd] gradient wrt the layer output.
 // Produces dpre (a->da*) and, if G != nullptr, parameter gradients into G at the given offsets
 // (W grads are written directly by the GEMM: splitk == 1).
-int dense_ln_tanh_bwd(serl_agent* a, const float* dy, long ld_dy, long dy_goff, const float* y, long ld_y,
-                      long y_goff, const float* xhat, const float* rstd, const float* gamma, const float* beta, int act, long p_gstride,
-                      int groups, int rows_per_group, int D, float* dpre, float* dg, float* G, long g_off,
-                      long be_off, long b_off, long pg_gstride, hipStream_t st, const float* dq = nullptr,
-                      const float* dq_w = nullptr, float dq_const = 0.f, long dq_w_gstride = 0, const LossArgs* loss = nullptr) {
-  LnBwdArgs l = ln_bwd_args(dy, ld_dy, dy_goff, y, ld_y, y_goff, xhat, rstd, gamma, p_gstride, groups, rows_per_group, dpre, dg);
+int dense_ln_bwd(serl_agent* a, const float* dy, long ld_dy, long dy_goff, const float* y, long ld_y,
+                 long y_goff, const float* xhat, const float* rstd, const float* gamma, const float* beta, int act, long p_gstride,
+                 int groups, int rows_per_group, int D, float* dpre, float* dg, float* G, long g_off,
+                 long be_off, long b_off, long pg_gstride, hipStream_t st, const float* dq = nullptr,
+                 const float* dq_w = nullptr, float dq_const = 0.f, long dq_w_gstride = 0, const LossArgs* loss = nullptr) {
+  LnBwdArgs l = ln_bwd_args(dy, ld_dy, dy_goff, y, ld_y, y_goff, xhat, rstd, gamma, p_gstride, groups, rows_per_group, D, dpre, dg);
   l.dq = dq; l.dq_w = dq_w; l.dq_const = dq_const; l.dq_w_gstride = dq_w_gstride;
   l.act = act; l.beta = beta;
   if (loss) {   // the critic loss rides on this launch and every row derives its dQ from the loss arguments (no critic_loss launch)
-    l.D = D; l.dq_inline = 1;
-    RC(ln_tanh_bwd_multi(&l, 1, *loss, st));
+    l.dq_inline = 1;
+    RC(ln_bwd_multi(&l, 1, *loss, st));
   } else {
-    RC(ln_tanh_bwd(l, D, st));
+    RC(ln_bwd(l, st));
   }
   if (G && a->pg_defer && a->pg_ncs < kMaxColsum) {
     a->pg_cs[a->pg_ncs++] = Colsum3Args{dg, xhat, dpre, groups, rows_per_group, D, G + g_off, G + be_off, G + b_off, pg_gstride, 0};
@@ -708,15 +709,15 @@ int critic_bwd(serl_agent* a, const float* P, CritBuf& cb, int cnt, bool pg, hip
   if (loss) RC(critic_loss_or_rider(a, *loss, st, &rider));
   if (pg) RC(head_kernel_grad(a, cb, cnt, st));
   // gradient through the head dh2 = dq (x) w is formed inside the LN backward kernel (rank-1 mode)
-  RC(dense_ln_tanh_bwd(a, nullptr, Hd, (long)cnt * Hd, cb.m.h2, Hd, (long)cnt * Hd, cb.m.xh2, cb.m.rs2, P + o.c_g2, P + o.c_be2, a->critic_act, Hd,
-                       N, cnt, Hd, a->da2, a->dg2, G, o.c_g2, o.c_be2, o.c_b2, Hd, st, loss ? loss->dq : nullptr, P + o.c_hw, dq_const,
-                       a->state_only ? Hd : 0, rider));
+  RC(dense_ln_bwd(a, nullptr, Hd, (long)cnt * Hd, cb.m.h2, Hd, (long)cnt * Hd, cb.m.xh2, cb.m.rs2, P + o.c_g2, P + o.c_be2, a->critic_act, Hd,
+                  N, cnt, Hd, a->da2, a->dg2, G, o.c_g2, o.c_be2, o.c_b2, Hd, st, loss ? loss->dq : nullptr, P + o.c_hw, dq_const,
+                  a->state_only ? Hd : 0, rider));
   if (pg)
     RC(wgrad(a, cb.m.h1, Hd, (long)cnt * Hd, a->da2, Hd, (long)cnt * Hd, a->Gc + o.c_w2, Hd, (long)Hd * Hd, N, Hd, Hd,
              cnt, st));
   RC(igrad(a->da2, Hd, (long)cnt * Hd, P + o.c_w2, Hd, (long)Hd * Hd, a->dh1, Hd, (long)cnt * Hd, N, cnt, Hd, Hd, st));
-  RC(dense_ln_tanh_bwd(a, a->dh1, Hd, (long)cnt * Hd, cb.m.h1, Hd, (long)cnt * Hd, cb.m.xh1, cb.m.rs1, P + o.c_g1, P + o.c_be1, a->critic_act, Hd,
-                       N, cnt, Hd, a->da1, a->dg1, G, o.c_g1, o.c_be1, o.c_b1, Hd, st));
+  RC(dense_ln_bwd(a, a->dh1, Hd, (long)cnt * Hd, cb.m.h1, Hd, (long)cnt * Hd, cb.m.xh1, cb.m.rs1, P + o.c_g1, P + o.c_be1, a->critic_act, Hd,
+                  N, cnt, Hd, a->da1, a->dg1, G, o.c_g1, o.c_be1, o.c_b1, Hd, st));
   if (pg)
     RC(wgrad(a, cb.x, a->XA, 0, a->da1, Hd, (long)cnt * Hd, a->Gc + o.c_w1, Hd, (long)a->XA * Hd, N, a->XA, Hd, cnt, st));
   // dx = sum_e da1[e] * W1[e]^T
@@ -729,8 +730,8 @@ int proprio_bwd(serl_agent* a, const float* P, const float* dy, long ld_dy, cons
   const serl_agent_cfg& c = a->cfg;
   const Offs& o = a->o;
   const int Pd = c.proprio_dim;
-  RC(dense_ln_tanh_bwd(a, dy, ld_dy, 0, y, ld_y, 0, e.pxhat, e.prstd, P + o.p_g, nullptr, kActTanh, 0, 1, cnt, Pd, a->dp, a->dgp, G,
-                       o.p_g - base_off, o.p_be - base_off, o.p_b - base_off, 0, st));
+  RC(dense_ln_bwd(a, dy, ld_dy, 0, y, ld_y, 0, e.pxhat, e.prstd, P + o.p_g, nullptr, kActTanh, 0, 1, cnt, Pd, a->dp, a->dgp, G,
+                  o.p_g - base_off, o.p_be - base_off, o.p_b - base_off, 0, st));
   const float* s = a->cur.state + ((long)which * a->cur.batch + off) * c.state_dim;
   return wgrad(a, s, c.state_dim, 0, a->dp, Pd, 0, G + (o.p_W - base_off), Pd, 0, 1, c.state_dim, Pd, cnt, st);
 }
@@ -746,10 +747,9 @@ int enc_bwd_critic(serl_agent* a, const float* P, EncBuf& e, int off, int cnt, h
   const int Bn = c.bottleneck, Pd = c.proprio_dim;
   const long pc = (long)c.n_cam * Bn;
   if (a->fuse && !a->state_only) {
-    LnBwdArgs lb[2] = {ln_bwd_args(a->dx, a->XA, Bn, e.enc, e.ld, Bn, e.xhat, e.rstd, P + o.cam[0].lng, o.cam_stride, c.n_cam, cnt, a->dz, a->dgz),
-                       ln_bwd_args(a->dx + pc, a->XA, 0, e.enc + pc, e.ld, 0, e.pxhat, e.prstd, P + o.p_g, 0, 1, cnt, a->dp, a->dgp)};
-    lb[0].D = Bn; lb[1].D = Pd;
-    RC(ln_tanh_bwd_multi(lb, 2, LossArgs{}, st));
+    LnBwdArgs lb[2] = {ln_bwd_args(a->dx, a->XA, Bn, e.enc, e.ld, Bn, e.xhat, e.rstd, P + o.cam[0].lng, o.cam_stride, c.n_cam, cnt, Bn, a->dz, a->dgz),
+                       ln_bwd_args(a->dx + pc, a->XA, 0, e.enc + pc, e.ld, 0, e.pxhat, e.prstd, P + o.p_g, 0, 1, cnt, Pd, a->dp, a->dgp)};
+    RC(ln_bwd_multi(lb, 2, LossArgs{}, st));
     SERL_REQUIRE(a->pg_defer && a->pg_ncs + 2 <= kMaxColsum, "no room for the deferred LayerNorm gradients");
     a->pg_cs[a->pg_ncs++] = Colsum3Args{a->dgp, e.pxhat, a->dp, 1, cnt, Pd, a->Gc + o.p_g, a->Gc + o.p_be, a->Gc + o.p_b, 0, 0};
     a->pg_cs[a->pg_ncs++] = Colsum3Args{a->dgz, e.xhat, a->dz, c.n_cam, cnt, Bn, a->Gc + o.cam[0].lng, a->Gc + o.cam[0].lnb,
@@ -765,9 +765,9 @@ int enc_bwd_critic(serl_agent* a, const float* P, EncBuf& e, int off, int cnt, h
   }
   if (a->state_only) return SERL_OK;
   if (!a->fuse)
-    RC(dense_ln_tanh_bwd(a, a->dx, a->XA, Bn, e.enc, e.ld, Bn, e.xhat, e.rstd, P + o.cam[0].lng, nullptr, kActTanh, o.cam_stride,
-                         c.n_cam, cnt, Bn, a->dz, a->dgz, a->Gc, o.cam[0].lng, o.cam[0].lnb, o.cam[0].db,
-                         o.cam_stride, st));
+    RC(dense_ln_bwd(a, a->dx, a->XA, Bn, e.enc, e.ld, Bn, e.xhat, e.rstd, P + o.cam[0].lng, nullptr, kActTanh, o.cam_stride,
+                    c.n_cam, cnt, Bn, a->dz, a->dgz, a->Gc, o.cam[0].lng, o.cam[0].lnb, o.cam[0].db,
+                    o.cam_stride, st));
   RC(wgrad(a, e.f, a->D, (long)c.batch * a->D, a->dz, Bn, (long)cnt * Bn, a->Gc + o.cam[0].dW, Bn, o.cam_stride,
            c.n_cam, a->D, Bn, cnt, st));
   RC(igrad(a->dz, Bn, (long)cnt * Bn, P + o.cam[0].dW, Bn, o.cam_stride, a->df, a->D, (long)cnt * a->D, c.n_cam, cnt,
@@ -1378,12 +1378,12 @@ int serl_agent_actor_grads(serl_agent* a, int global_count, const serl_noise* no
   RC(head_bias_grad(a, cnt, Ga + (o.a_bm - b0), hs, st));
   // dh2 = dmean W_mean^T + dlog_std W_logstd^T (no second term when the log-std has no Dense)
   RC(igrad_sum(a, a->dpre, A, (long)cnt * A, a->theta + o.a_Wm, A, hs, a->dh2, Hd, hg, cnt, Hd, A, st));
-  RC(dense_ln_tanh_bwd(a, a->dh2, Hd, 0, a->pol.m.h2, Hd, 0, a->pol.m.xh2, a->pol.m.rs2, a->theta + o.a_g2, a->theta + o.a_be2, a->policy_act, 0, 1, cnt, Hd,
-                       a->da2, a->dg2, Ga, o.a_g2 - b0, o.a_be2 - b0, o.a_b2 - b0, 0, st));
+  RC(dense_ln_bwd(a, a->dh2, Hd, 0, a->pol.m.h2, Hd, 0, a->pol.m.xh2, a->pol.m.rs2, a->theta + o.a_g2, a->theta + o.a_be2, a->policy_act, 0, 1, cnt, Hd,
+                  a->da2, a->dg2, Ga, o.a_g2 - b0, o.a_be2 - b0, o.a_b2 - b0, 0, st));
   RC(wgrad(a, a->pol.m.h1, Hd, 0, a->da2, Hd, 0, Ga + (o.a_w2 - b0), Hd, 0, 1, Hd, Hd, cnt, st));
   RC(igrad(a->da2, Hd, 0, a->theta + o.a_w2, Hd, 0, a->dh1, Hd, 0, 1, cnt, Hd, Hd, st));
-  RC(dense_ln_tanh_bwd(a, a->dh1, Hd, 0, a->pol.m.h1, Hd, 0, a->pol.m.xh1, a->pol.m.rs1, a->theta + o.a_g1, a->theta + o.a_be1, a->policy_act, 0, 1, cnt, Hd,
-                       a->da1, a->dg1, Ga, o.a_g1 - b0, o.a_be1 - b0, o.a_b1 - b0, 0, st));
+  RC(dense_ln_bwd(a, a->dh1, Hd, 0, a->pol.m.h1, Hd, 0, a->pol.m.xh1, a->pol.m.rs1, a->theta + o.a_g1, a->theta + o.a_be1, a->policy_act, 0, 1, cnt, Hd,
+                  a->da1, a->dg1, Ga, o.a_g1 - b0, o.a_be1 - b0, o.a_b1 - b0, 0, st));
   RC(wgrad(a, a->encP.enc, a->encP.ld, 0, a->da1, Hd, 0, Ga + (o.a_w1 - b0), Hd, 0, 1, a->E, Hd, cnt, st));
   // image codes are stop-gradiented (encoding.py:48-49); only the proprio slice of d_enc is needed
   if (!a->state_only) {

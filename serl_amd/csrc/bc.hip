@@ -243,7 +243,7 @@ int forward(serl_bc* c, const uint8_t* frames, const float* state, int n, const 
   cam_dense_ln_args(c->f, (long)n * c->D, c->D, P + c->cam.dW, P + c->cam.db, P + c->cam.lng, P + c->cam.lnb, c->cam.stride,
                     g.n_cam, n, kBottleneck, S0, c->slabs, c->enc, c->E, nullptr, nullptr, g0, l0);
   RC(gemm_f32_multi(&g0, 1, st));
-  RC(ln_tanh_fwd_multi(&l0, 1, kBottleneck, st));
+  RC(ln_fwd_multi(&l0, 1, kBottleneck, st));
   // MLP: Dense(256) -> tanh, twice (activate_final)
   const int S1 = split_under(n, kHidden, 1, 8);
   const GemmDesc g1 = gemm_fwd(c->enc, c->E, 0, P + c->o_w1, 0, c->slabs, 1, n, kHidden, c->E, S1);
@@ -400,9 +400,9 @@ int serl_bc_update(serl_bc* c, const serl_batch* batch, const uint8_t* dev_masks
   lb.dy = c->dprop; lb.ld_dy = kProprio;
   lb.y = c->enc + c->Eimg; lb.ld_y = c->E;
   lb.xhat = c->pxhat; lb.rstd = c->prstd; lb.gamma = P + c->o_pg;
-  lb.rows = n; lb.rows_per_group = n;
+  lb.rows = n; lb.rows_per_group = n; lb.D = kProprio;
   lb.dx = c->dpp; lb.dg = c->dgp;
-  RC(ln_tanh_bwd(lb, kProprio, st));
+  RC(ln_bwd(lb, st));
   // every parameter gradient: one column-sum launch and one grouped weight-gradient GEMM
   const float* dmu = c->dhead;
   const float* dls = c->dhead + (long)n * A;

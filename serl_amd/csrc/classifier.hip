@@ -11,6 +11,7 @@
 
 #include "heads.h"
 #include "jaxrng.h"
+#include "ln_stats.h"
 
 using namespace serl;
 
@@ -142,7 +143,7 @@ int head_slabs(serl_classifier* c, const float* feats, long cam_stride, const in
   cam_dense_ln_args(c->f, nmax * c->D, c->D, P + c->cam.dW, P + c->cam.db, P + c->cam.lng, P + c->cam.lnb, c->cam.stride,
                     g.n_cam, n, kBottleneck, S0, c->slabs, c->enc, c->E, nullptr, nullptr, g0, l0);
   RC(gemm_f32_multi(&g0, 1, st));
-  RC(ln_tanh_fwd_multi(&l0, 1, kBottleneck, st));
+  RC(ln_fwd_multi(&l0, 1, kBottleneck, st));
   const int S1 = split_under(n, kHidden, 1, 8);
   const GemmDesc g1 = gemm_fwd(c->enc, c->E, 0, P + c->o_w1, 0, c->slabs, 1, n, kHidden, c->E, S1);
   RC(gemm_f32_multi(&g1, 1, st));
@@ -274,7 +275,7 @@ int serl_classifier_logits_from_features(serl_classifier* c, const float* dev_fe
   int S1 = 0;
   RC(head_slabs(c, dev_feats, cam_stride_floats, cam_of, n, st, &S1));
   const LnFwdArgs l1 = head_ln_args(c, S1, n, dev_logits);
-  return ln_tanh_fwd_multi(&l1, 1, kHidden, st);
+  return ln_fwd_multi(&l1, 1, kHidden, st);
 }
 
 }  // extern "C"
@@ -333,10 +334,9 @@ __global__ __launch_bounds__(256) void cls_head_kernel(ClsHeadArgs a) {
   float s1 = 0.f, s2 = 0.f;
 #pragma unroll
   for (int j = 0; j < 4; ++j) { s1 += v[j]; s2 += v[j] * v[j]; }
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) { s1 += __shfl_xor(s1, off); s2 += __shfl_xor(s2, off); }
-  const float mean = s1 * (1.0f / kHidden), mean2 = s2 * (1.0f / kHidden);
-  const float rstd = rsqrtf(fmaxf(mean2 - mean * mean, 0.f) + 1e-6f);
+  wave_sum2(s1, s2);
+  float mean, rstd;
+  ln_mean_rstd<kHidden>(s1, s2, mean, rstd);
   float xh[4], pre[4], h[4], d = 0.f;
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
@@ -372,8 +372,7 @@ __global__ __launch_bounds__(256) void cls_head_kernel(ClsHeadArgs a) {
     s1 += dxh[j];
     s2 += dxh[j] * xh[j];
   }
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) { s1 += __shfl_xor(s1, off); s2 += __shfl_xor(s2, off); }
+  wave_sum2(s1, s2);
   const float m1 = s1 * (1.0f / kHidden), m2 = s2 * (1.0f / kHidden);
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
@@ -479,7 +478,7 @@ int train_forward(serl_classifier* c, const uint8_t* frames, int n, const float*
                       nc, n, kBottleneck, S0, t->slabs + (long)i * nc * S0 * n * kBottleneck, t->enc + (long)i * n * c->E, c->E,
                       i == 0 ? t->xhat : nullptr, i == 0 ? t->rstd : nullptr, g0[i], l0[i]);
   RC(gemm_f32_multi(g0, ni, st));
-  RC(ln_tanh_fwd_multi(l0, ni, kBottleneck, st));
+  RC(ln_fwd_multi(l0, ni, kBottleneck, st));
   // classifier head: Dense_0 (K-split) of both instances, then the row kernel
   const int S1 = split_under(n, kHidden, ni, 8);
   GemmDesc g1[2];
@@ -574,9 +573,9 @@ int serl_classifier_train_step(serl_classifier* c, const uint8_t* dev_frames, in
   lb.dy = t->denc; lb.ld_dy = c->E; lb.dy_goff = kBottleneck;
   lb.y = t->enc; lb.ld_y = c->E; lb.y_goff = kBottleneck;
   lb.xhat = t->xhat; lb.rstd = t->rstd; lb.gamma = P + c->cam.lng; lb.pstride = c->cam.stride;
-  lb.rows = nc * n; lb.rows_per_group = n;
+  lb.rows = nc * n; lb.rows_per_group = n; lb.D = kBottleneck;
   lb.dx = t->dzc; lb.dg = t->dgc;
-  RC(ln_tanh_bwd(lb, kBottleneck, st));
+  RC(ln_bwd(lb, st));
   const GemmDesc gf = gemm_igrad(t->dzc, kBottleneck, (long)n * kBottleneck, P + c->cam.dW, kBottleneck, c->cam.stride, t->df, c->D, nD, nc, n, c->D, kBottleneck);
   RC(gemm_f32_multi(&gf, 1, st));
   // through the camera Dropout, then the SpatialLearnedEmbeddings kernels' gradient (batch splits summed by the last arriver)

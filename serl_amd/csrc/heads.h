@@ -22,7 +22,7 @@ int reduce_slabs(const float* slabs, int S, long slab_stride, int groups, int ro
                  hipStream_t stream, float scale = 1.0f);
 
 // D: the row width of every instance, a multiple of 64 in [64, 1024] (one wave per row, D / 64 columns per lane)
-int ln_tanh_fwd_multi(const LnFwdArgs* a, int n, int D, hipStream_t stream);
+int ln_fwd_multi(const LnFwdArgs* a, int n, int D, hipStream_t stream);
 // One width-256 ReLU instance with a row-dot (the reward classifier's head), closed for reward labelling: dot_out = logits,
 // label[row] = sigmoid(logit) >= 0.5, mean[0] = the labels' mean, summed in a fixed order inside the launch (ctr: one zeroed
 // arrival counter)
@@ -48,13 +48,14 @@ struct LnBwdArgs {
   float* dg;  // [rows][D] dy * act'(pre): dy*(1-y^2) for tanh  (-> dbeta = colsum(dg), dgamma = colsum(dg*xhat))
   int act;            // kAct* of the forward row (per instance, uniform over a wave)
   const float* beta;  // kActSwish only: the forward's beta (addressed like gamma), to recompute pre = gamma*xhat + beta
-  int D;          // ln_tanh_bwd_multi only: the row width, a multiple of 64 in [64, 1024]
-  int dq_inline;  // ln_tanh_bwd_multi, rank-1 mode: dq[row] = 2 (q - y) inv_norm computed from the LossArgs of the launch
+  int D;          // the row width, a multiple of 64 in [64, 1024]
+  int dq_inline;  // rank-1 mode: dq[row] = 2 (q - y) inv_norm computed from the LossArgs of the launch
 };
-int ln_tanh_bwd(const LnBwdArgs& a, int D, hipStream_t stream);
 // up to kMaxMulti LayerNorm backward passes in one launch (+ the critic-loss rider when loss.on).  Widths 64 and 256 may share a
-// launch (the encoder heads); any other width (an MLP layer at hidden != 256) must be the width of every instance.
-int ln_tanh_bwd_multi(const LnBwdArgs* a, int n, const LossArgs& loss, hipStream_t stream);
+// launch (the encoder heads); any other width (an MLP layer at hidden != 256) must be the width of every instance.  One
+// instance of width 64 or 256 without a rider takes a launch of its own kind with one LnBwdArgs for arguments.
+int ln_bwd_multi(const LnBwdArgs* a, int n, const LossArgs& loss, hipStream_t stream);
+inline int ln_bwd(const LnBwdArgs& a, hipStream_t stream) { return ln_bwd_multi(&a, 1, LossArgs{}, stream); }
 
 int colsum(const float* X, const float* Y, int groups, int rows_per_group, int D, float* out,
            long out_gstride, bool accumulate, hipStream_t stream);

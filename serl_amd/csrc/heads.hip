@@ -7,6 +7,7 @@
 
 #include "heads.h"
 #include "jaxrng.h"
+#include "ln_stats.h"
 #include "prof.h"
 
 namespace serl {
@@ -32,7 +33,7 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 // ds_write_b128 and a fragment is four conflict-free ds_read_b32 (consecutive lanes = consecutive rows).  Round 2
 // transposed such operands on the way into LDS with scalar stores at a 36-float row pitch: 8 lanes per bank,
 // SQ_LDS_BANK_CONFLICT / SQ_LDS_IDX_ACTIVE = 0.62 for gemm_f32_kernel<true, false> (profiles/r02_mfma_counters.json).
-// Edges are zero-filled; slabs are summed by the consumer (reduce_slabs / ln_tanh_fwd), which keeps the
+// Edges are zero-filled; slabs are summed by the consumer (reduce_slabs / ln_fwd_kernel), which keeps the
 // K-split deterministic.  Arbitrary element strides fall back to gemm_f32_strided_kernel.
 // =============================================================================================
 constexpr int kGBM = 64, kGBN = 64, kGBK = 32, kGP = 36, kGPT = 68;
@@ -118,7 +119,7 @@ struct OperandLoader {
 //     counter with a returning memory-side atomic;
 //   * the workgroup that draws the last ticket re-zeroes the counter and reads every slab of the tile with sc1 loads (served
 //     past its own L1: no acquire fence / invalidate needed) IN INDEX ORDER -- the same order the separate reduce_slabs /
-//     ln_tanh_fwd kernels summed in, so fused and un-fused results are bit-identical (tests assert exact equality).
+//     ln_fwd kernels summed in, so fused and un-fused results are bit-identical (tests assert exact equality).
 // This is the "in-launch split-K reduction" recipe of cdna_hip_programming.md (sc1 stores + drain + barrier + relaxed
 // ticket; sc1 loads on the reducer): correct for any placement of a tile's workgroups over CUs / XCDs, no spinning (nobody
 // waits for anybody), no cache maintenance next to the co-running trunk pass.  The MFMA accumulator layout gives a lane one
@@ -236,114 +237,78 @@ __device__ __forceinline__ void ln_act_grad(int act, float (&dg)[N], const float
   }
 }
 
-// LayerNorm(eps 1e-6, fast variance) + tanh of ONE row of 256 by one wave (mlp.py:24-31, resnet_v1.py:371-374, encoding.py:66-68):
-// pre = bias[g] + sum_s slab[s][row] (slabs read in index order);  y = tanh(gamma[g]*xhat + beta[g]).  LIVE: the slabs were
-// written by other workgroups of THIS launch (sc1 loads); otherwise plain loads (the separate ln_tanh_fwd kernel).
-// Returns the fused row-dot (dot_out's value, in every lane; 0 without one).
-template <bool LIVE>
-__device__ __forceinline__ float ln_tanh_row256(const LnFwdArgs& a, int row, int lane) {
-  constexpr int D = 256;
-  const int grp = row / a.rows_per_group;
-  const long lrow = row - grp * a.rows_per_group;
-  const long base = (long)grp * a.S * a.slab_stride + lrow * D + lane * 4;
-  const __amdgpu_buffer_rsrc_t rs = rsrc_of(a.slabs);
-  float4 acc4 = a.bias ? *reinterpret_cast<const float4*>(a.bias + (long)grp * a.pstride + lane * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
-  auto slab = [&](int s) -> f32x4 {
-    if (LIVE) return ld_sc1(rs, base + (long)s * a.slab_stride);
-    return *reinterpret_cast<const f32x4*>(a.slabs + base + (long)s * a.slab_stride);
-  };
-  int s = 0;
-  for (; s + 4 <= a.S; s += 4) {   // 4 independent slab reads in flight, added in index order
-    const f32x4 x0 = slab(s), x1 = slab(s + 1), x2 = slab(s + 2), x3 = slab(s + 3);
-    acc4.x += x0[0]; acc4.y += x0[1]; acc4.z += x0[2]; acc4.w += x0[3];
-    acc4.x += x1[0]; acc4.y += x1[1]; acc4.z += x1[2]; acc4.w += x1[3];
-    acc4.x += x2[0]; acc4.y += x2[1]; acc4.z += x2[2]; acc4.w += x2[3];
-    acc4.x += x3[0]; acc4.y += x3[1]; acc4.z += x3[2]; acc4.w += x3[3];
-  }
-  for (; s < a.S; ++s) {
-    const f32x4 x0 = slab(s);
-    acc4.x += x0[0]; acc4.y += x0[1]; acc4.z += x0[2]; acc4.w += x0[3];
-  }
-  const float v[4] = {acc4.x, acc4.y, acc4.z, acc4.w};
-  float s1 = 0.f, s2 = 0.f;
+// LayerNorm(eps 1e-6, fast variance) + activation of ONE row of width D = 64 * VPL by one wave (mlp.py:24-31,
+// resnet_v1.py:371-374, encoding.py:66-68): a lane holds VPL of the row's columns, 64 .. 1024 columns in all.
+//   pre = bias[g] + sum_s slab[s][row] (slabs read in index order);  y = act(gamma[g]*xhat + beta[g])  (act: LnFwdArgs::act)
+// Lane-to-column layout.  STRIDED: lane l holds columns l, l + 64, ..., l + 64 (VPL - 1); every load / store instruction of the
+// wave then covers 64 consecutive floats (256 bytes, two whole cache lines) whatever VPL is.  BLOCKED (width 256 alone, VPL == 4):
+// lane l holds columns 4 l .. 4 l + 3, its bias and slab values one 16-byte access each; a block of 12 or 20 bytes (VPL = 3 or 5)
+// has no such access, and a 4-byte access per column would stride the wave over the row.  (Multiples of 256 could take 16-byte
+// accesses in a blocked-by-256 layout; the strided layout serves every other width until one of them has a speed target.)
+// Same arithmetic in both: bias, then the slabs in index order; a lane sums its columns in ascending order, then the xor
+// butterfly.  Fused and one-per-operation schedules compare bit for bit (tests assert exact equality).
+// A lane's column j is ln_col0(lane) + kLnStep * j.
+template <int VPL, bool BLOCKED>
+__device__ __forceinline__ int ln_col0(int lane) { return BLOCKED ? lane * VPL : lane; }
+template <bool BLOCKED>
+constexpr int kLnStep = BLOCKED ? 1 : 64;
+// The row's values in a lane: v[j] = bias[pb + kLnStep j] (0 without a bias) + sum_s slabs[base + s slab_stride + kLnStep j], the
+// slabs added in index order.  A blocked lane asks for its 16 bytes as such -- the compiler cannot prove their alignment and
+// would not merge four scalar loads -- and keeps four slab reads in flight (unrolled by hand: the compiler's own unrolling by 4
+// takes 6 VGPRs more); a strided lane keeps 2 VPL reads in flight.
+template <int VPL, bool BLOCKED>
+__device__ __forceinline__ void ln_gather(const LnFwdArgs& a, long base, long pb, float (&v)[VPL]) {
+  if constexpr (BLOCKED) {
+    static_assert(VPL == 4, "the blocked layout is one 16-byte access per lane");
+    auto slab = [&](int s) { return *reinterpret_cast<const f32x4*>(a.slabs + base + (long)s * a.slab_stride); };
+    f32x4 acc = a.bias ? *reinterpret_cast<const f32x4*>(a.bias + pb) : (f32x4){0.f, 0.f, 0.f, 0.f};
+    int s = 0;
+    for (; s + 4 <= a.S; s += 4) {
+      const f32x4 x0 = slab(s), x1 = slab(s + 1), x2 = slab(s + 2), x3 = slab(s + 3);
+      acc += x0; acc += x1; acc += x2; acc += x3;
+    }
+    for (; s < a.S; ++s) acc += slab(s);
 #pragma unroll
-  for (int j = 0; j < 4; ++j) { s1 += v[j]; s2 += v[j] * v[j]; }
+    for (int j = 0; j < 4; ++j) v[j] = acc[j];
+  } else {
 #pragma unroll
-  for (int off = 1; off < 64; off <<= 1) { s1 += __shfl_xor(s1, off); s2 += __shfl_xor(s2, off); }
-  const float mean = s1 * (1.0f / D), mean2 = s2 * (1.0f / D);
-  const float var = fmaxf(mean2 - mean * mean, 0.f);
-  const float rstd = rsqrtf(var + 1e-6f);
-  float d = 0.f, y[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const int col = lane * 4 + j;
-    const float xh = (v[j] - mean) * rstd;
-    y[j] = xh * a.gamma[(long)grp * a.pstride + col] + a.beta[(long)grp * a.pstride + col];
-    if (a.xhat) a.xhat[(long)row * D + col] = xh;
-  }
-  ln_activate(a.act, y);
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const int col = lane * 4 + j;
-    a.y[lrow * a.ld_y + (long)grp * a.y_goff + col] = y[j];
-    if (a.dot_out) d += y[j] * a.dot_w[(long)grp * a.dot_gstride + col];
-  }
-  if (a.rstd && lane == 0) a.rstd[row] = rstd;
-  if (a.dot_out) {
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) d += __shfl_xor(d, off);
-    d += a.dot_b[(long)grp * a.dot_b_gstride];
-    if (lane == 0) a.dot_out[row] = d;
-  }
-  return d;
-}
-
-// The same row at ANY width D = 64 * VPL (the MLPs' hidden width, serl_agent_cfg.hidden: 64 .. 1024): one wave still owns the
-// row, a lane holds VPL of its columns.  Lane-to-column layout: STRIDED -- lane l holds columns l, l + 64, ..., l + 64 (VPL - 1).
-// Every load / store instruction of the wave then covers 64 consecutive floats (256 bytes, two whole cache lines) whatever VPL
-// is; the blocked layout of the 256 form (lane l holds columns 4 l .. 4 l + 3 as one 16-byte access) has no counterpart at
-// VPL = 3 or 5, where a lane's block is 12 or 20 bytes and a 4-byte access per column would stride the wave over the row.
-// Same arithmetic as the 256 form: bias, then the slabs in index order; fast variance; a lane sums its columns in ascending
-// order, then the xor butterfly.  Widths 64 and 256 keep their own kernels (ln_tanh_fwd_kernel<1|4>) and never come here.
-// LIVE as in the 256 form (sc1 loads of slabs written inside this launch); like there, no launch instantiates it today.
-// (Multiples of 256 could take 16-byte accesses in a blocked-by-256 layout; one layout serves every width until a width other
-// than 256 has a speed target.)
-template <int VPL, bool LIVE>
-__device__ __forceinline__ float ln_tanh_row(const LnFwdArgs& a, int row, int lane) {
-  constexpr int D = 64 * VPL;
-  const int grp = row / a.rows_per_group;
-  const long lrow = row - grp * a.rows_per_group;
-  const long base = (long)grp * a.S * a.slab_stride + lrow * D + lane;
-  const long pb = (long)grp * a.pstride + lane;
-  const __amdgpu_buffer_rsrc_t rs = rsrc_of(a.slabs);
-  float v[VPL];
-#pragma unroll
-  for (int j = 0; j < VPL; ++j) v[j] = a.bias ? a.bias[pb + 64 * j] : 0.f;
+    for (int j = 0; j < VPL; ++j) v[j] = a.bias ? a.bias[pb + 64 * j] : 0.f;
 #pragma unroll 2
-  for (int s = 0; s < a.S; ++s) {   // 2 VPL independent reads in flight, added in index order
-    const long o = base + (long)s * a.slab_stride;
+    for (int s = 0; s < a.S; ++s) {
+      const long o = base + (long)s * a.slab_stride;
 #pragma unroll
-    for (int j = 0; j < VPL; ++j) v[j] += LIVE ? ld1_sc1(rs, o + 64 * j) : a.slabs[o + 64 * j];
+      for (int j = 0; j < VPL; ++j) v[j] += a.slabs[o + 64 * j];
+    }
   }
+}
+// Returns the fused row-dot (dot_out's value, in every lane; 0 without one).
+template <int VPL, bool BLOCKED>
+__device__ __forceinline__ float ln_row(const LnFwdArgs& a, int row, int lane) {
+  constexpr int D = 64 * VPL, kStep = kLnStep<BLOCKED>;
+  const int grp = row / a.rows_per_group;
+  const long lrow = row - grp * a.rows_per_group;
+  const int c0 = ln_col0<VPL, BLOCKED>(lane);
+  const long base = (long)grp * a.S * a.slab_stride + lrow * D + c0;
+  const long pb = (long)grp * a.pstride + c0;
+  float v[VPL];
+  ln_gather<VPL, BLOCKED>(a, base, pb, v);
   float s1 = 0.f, s2 = 0.f;
 #pragma unroll
   for (int j = 0; j < VPL; ++j) { s1 += v[j]; s2 += v[j] * v[j]; }
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) { s1 += __shfl_xor(s1, off); s2 += __shfl_xor(s2, off); }
-  const float mean = s1 * (1.0f / D), mean2 = s2 * (1.0f / D);
-  const float var = fmaxf(mean2 - mean * mean, 0.f);
-  const float rstd = rsqrtf(var + 1e-6f);
+  wave_sum2(s1, s2);
+  float mean, rstd;
+  ln_mean_rstd<D>(s1, s2, mean, rstd);
   float d = 0.f;
 #pragma unroll
   for (int j = 0; j < VPL; ++j) {   // v: the row's values, then its pre-activations, then y
     const float xh = (v[j] - mean) * rstd;
-    v[j] = xh * a.gamma[pb + 64 * j] + a.beta[pb + 64 * j];
-    if (a.xhat) a.xhat[(long)row * D + lane + 64 * j] = xh;
+    v[j] = xh * a.gamma[pb + kStep * j] + a.beta[pb + kStep * j];
+    if (a.xhat) a.xhat[(long)row * D + c0 + kStep * j] = xh;
   }
   ln_activate(a.act, v);
 #pragma unroll
   for (int j = 0; j < VPL; ++j) {
-    const int col = lane + 64 * j;
+    const int col = c0 + kStep * j;
     a.y[lrow * a.ld_y + (long)grp * a.y_goff + col] = v[j];
     if (a.dot_out) d += v[j] * a.dot_w[(long)grp * a.dot_gstride + col];
   }
@@ -973,59 +938,18 @@ int reduce_slabs(const float* slabs, int S, long slab_stride, int groups, int ro
 }
 
 // =============================================================================================
-// LayerNorm(eps 1e-6, fast variance) + tanh, one wave per row.   mlp.py:24-31, resnet_v1.py:371-374,
-// encoding.py:66-68.   pre = bias[g] + sum_s slab[s][row];  y = tanh(gamma[g]*xhat + beta[g])
+// LayerNorm(eps 1e-6, fast variance) + activation, one wave per row (ln_row), four rows per workgroup.
 // =============================================================================================
-template <int VPL>
-__global__ __launch_bounds__(256) void ln_tanh_fwd_kernel(Multi<LnFwdArgs> mv) {
+template <int VPL, bool BLOCKED>
+__global__ __launch_bounds__(256) void ln_fwd_kernel(Multi<LnFwdArgs> mv) {
   const LnFwdArgs& a = mv.v[blockIdx.y];  // blockIdx.y = independent instance (variant)
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (row >= a.rows) return;
-  if (VPL == 4) { ln_tanh_row256<false>(a, row, lane); return; }   // (the same code the fused GEMM epilogue runs)
-  const int grp = row / a.rows_per_group;
-  constexpr int D = VPL * 64;
-  float v[VPL];
-#pragma unroll
-  for (int j = 0; j < VPL; ++j) {
-    const int col = lane * VPL + j;
-    float x = a.bias ? a.bias[(long)grp * a.pstride + col] : 0.f;
-    for (int s = 0; s < a.S; ++s)
-      x += a.slabs[(long)(grp * a.S + s) * a.slab_stride + (long)(row - grp * a.rows_per_group) * D + col];
-    v[j] = x;
-  }
-  float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-  for (int j = 0; j < VPL; ++j) { s1 += v[j]; s2 += v[j] * v[j]; }
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) { s1 += __shfl_xor(s1, off); s2 += __shfl_xor(s2, off); }
-  const float mean = s1 * (1.0f / D), mean2 = s2 * (1.0f / D);
-  const float var = fmaxf(mean2 - mean * mean, 0.f);
-  const float rstd = rsqrtf(var + 1e-6f);
-  float d = 0.f;
-#pragma unroll
-  for (int j = 0; j < VPL; ++j) {   // v: the row's values, then its pre-activations, then y
-    const int col = lane * VPL + j;
-    const float xh = (v[j] - mean) * rstd;
-    v[j] = xh * a.gamma[(long)grp * a.pstride + col] + a.beta[(long)grp * a.pstride + col];
-    if (a.xhat) a.xhat[(long)row * D + col] = xh;
-  }
-  ln_activate(a.act, v);
-#pragma unroll
-  for (int j = 0; j < VPL; ++j) {
-    const int col = lane * VPL + j;
-    a.y[(long)(row - grp * a.rows_per_group) * a.ld_y + (long)grp * a.y_goff + col] = v[j];
-    if (a.dot_out) d += v[j] * a.dot_w[(long)grp * a.dot_gstride + col];
-  }
-  if (a.rstd && lane == 0) a.rstd[row] = rstd;
-  if (a.dot_out) {
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) d += __shfl_xor(d, off);
-    if (lane == 0) a.dot_out[row] = d + a.dot_b[(long)grp * a.dot_b_gstride];
-  }
+  ln_row<VPL, BLOCKED>(a, row, lane);
 }
 
 // The reward classifier's head closed for labelling (vice.py:546,594: rewards = (sigmoid(classifier(next_obs)) >= 0.5) * 1.0): the
-// LayerNorm -> ReLU -> Dense(1) row of ln_tanh_row256 (one row per wave; the logit goes to a.dot_out as in the train=False
+// LayerNorm -> ReLU -> Dense(1) row of ln_row at width 256 (one row per wave; the logit goes to a.dot_out as in the train=False
 // forward), then p = 1 / (1 + expf(-logit)) in fp32 (as jax.nn.sigmoid: a logit just below zero may round to 0.5) and
 // label = p >= 0.5f.  The mean label is taken inside the launch by the workgroup that arrives last (arrive_is_last: write-through
 // label stores, every wave drains, one ticket; the labels are read back past the L1): 256 strided partial sums in row order, then
@@ -1035,7 +959,7 @@ __global__ __launch_bounds__(256) void label_rows_kernel(LnFwdArgs a, float* lab
   const int tid = threadIdx.x, row = blockIdx.x * 4 + (tid >> 6), lane = tid & 63;
   const __amdgpu_buffer_rsrc_t lab = rsrc_of(label);
   if (row < a.rows) {
-    const float logit = ln_tanh_row256<false>(a, row, lane);
+    const float logit = ln_row<4, true>(a, row, lane);
     const float p = 1.f / (1.f + expf(-logit));
     if (lane == 0) __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, p >= 0.5f ? 1.f : 0.f), lab, row * 4, 0, kSc1);
   }
@@ -1058,31 +982,24 @@ int label_rows(const LnFwdArgs& a, float* label, float* mean, int* ctr, hipStrea
   return SERL_OK;
 }
 
-// the width-generic row (ln_tanh_row: strided columns) with the grid of ln_tanh_fwd_kernel: four rows per workgroup
-template <int VPL>
-__global__ __launch_bounds__(256) void ln_tanh_fwd_wide_kernel(Multi<LnFwdArgs> mv) {
-  const LnFwdArgs& a = mv.v[blockIdx.y];
-  const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-  if (row >= a.rows) return;
-  ln_tanh_row<VPL, false>(a, row, lane);
-}
-
-// The widths the LayerNorm rows serve: one wave per row, D / 64 columns per lane, at most 16.  64 and 256 have kernels of their
-// own (the encoder's proprio and bottleneck LayerNorms, and the MLPs at the default width); every other width takes
-// K<D / 64> of the width-generic family K.
+// The widths the LayerNorm rows serve: one wave per row, D / 64 columns per lane, at most 16.  The launch of a width: K64 at 64
+// and K256 at 256 (the encoder's proprio and bottleneck LayerNorms, and the MLPs at the default width), the strided K<D / 64, false>
+// at every other.
 #define SERL_LN_WIDTH_OK(D) ((D) >= 64 && (D) <= 1024 && (D) % 64 == 0)
-#define SERL_LN_WIDE_CASE(K, V, ...) case V: SERL_LAUNCH_CHAIN(K<V>, __VA_ARGS__); break;
-#define SERL_LN_WIDE_LAUNCH(K, D, ...)                                                                                   \
+#define SERL_LN_CASE(V, K, ...) case V: SERL_LAUNCH_CHAIN(K, __VA_ARGS__); break;
+#define SERL_LN_STRIDED(V, K, ...) SERL_LN_CASE(V, (K<V, false>), __VA_ARGS__)
+#define SERL_LN_LAUNCH(D, K64, K256, K, ...)                                                                              \
   switch ((D) / 64) {                                                                                                     \
-    SERL_LN_WIDE_CASE(K, 2, __VA_ARGS__) SERL_LN_WIDE_CASE(K, 3, __VA_ARGS__) SERL_LN_WIDE_CASE(K, 5, __VA_ARGS__)       \
-    SERL_LN_WIDE_CASE(K, 6, __VA_ARGS__) SERL_LN_WIDE_CASE(K, 7, __VA_ARGS__) SERL_LN_WIDE_CASE(K, 8, __VA_ARGS__)       \
-    SERL_LN_WIDE_CASE(K, 9, __VA_ARGS__) SERL_LN_WIDE_CASE(K, 10, __VA_ARGS__) SERL_LN_WIDE_CASE(K, 11, __VA_ARGS__)     \
-    SERL_LN_WIDE_CASE(K, 12, __VA_ARGS__) SERL_LN_WIDE_CASE(K, 13, __VA_ARGS__) SERL_LN_WIDE_CASE(K, 14, __VA_ARGS__)    \
-    SERL_LN_WIDE_CASE(K, 15, __VA_ARGS__) SERL_LN_WIDE_CASE(K, 16, __VA_ARGS__)                                          \
-    default: serl::set_error("LayerNorm width %d has no width-generic kernel", (int)(D)); return SERL_ERR_INVALID;       \
+    SERL_LN_CASE(1, K64, __VA_ARGS__) SERL_LN_CASE(4, K256, __VA_ARGS__)                                                  \
+    SERL_LN_STRIDED(2, K, __VA_ARGS__) SERL_LN_STRIDED(3, K, __VA_ARGS__) SERL_LN_STRIDED(5, K, __VA_ARGS__)              \
+    SERL_LN_STRIDED(6, K, __VA_ARGS__) SERL_LN_STRIDED(7, K, __VA_ARGS__) SERL_LN_STRIDED(8, K, __VA_ARGS__)              \
+    SERL_LN_STRIDED(9, K, __VA_ARGS__) SERL_LN_STRIDED(10, K, __VA_ARGS__) SERL_LN_STRIDED(11, K, __VA_ARGS__)            \
+    SERL_LN_STRIDED(12, K, __VA_ARGS__) SERL_LN_STRIDED(13, K, __VA_ARGS__) SERL_LN_STRIDED(14, K, __VA_ARGS__)           \
+    SERL_LN_STRIDED(15, K, __VA_ARGS__) SERL_LN_STRIDED(16, K, __VA_ARGS__)                                               \
+    default: serl::set_error("LayerNorm width %d has no kernel", (int)(D)); return SERL_ERR_INVALID;                      \
   }
 
-int ln_tanh_fwd_multi(const LnFwdArgs* as, int n, int D, hipStream_t stream) {
+int ln_fwd_multi(const LnFwdArgs* as, int n, int D, hipStream_t stream) {
   SERL_REQUIRE(SERL_LN_WIDTH_OK(D), "LayerNorm width %d unsupported (a multiple of 64 in [64, 1024])", D);
   SERL_REQUIRE(n >= 1 && n <= kMaxMulti, "bad instance count %d", n);
   Multi<LnFwdArgs> mv{};
@@ -1093,67 +1010,7 @@ int ln_tanh_fwd_multi(const LnFwdArgs* as, int n, int D, hipStream_t stream) {
     rows = std::max(rows, as[i].rows);
   }
   dim3 grid(cdiv(rows, 4), n);
-  if (D == 256) SERL_LAUNCH_CHAIN(ln_tanh_fwd_kernel<4>, grid, dim3(256), 0, stream, mv);
-  else if (D == 64) SERL_LAUNCH_CHAIN(ln_tanh_fwd_kernel<1>, grid, dim3(256), 0, stream, mv);
-  else SERL_LN_WIDE_LAUNCH(ln_tanh_fwd_wide_kernel, D, grid, dim3(256), 0, stream, mv)
-  SERL_HIP(hipGetLastError());
-  return SERL_OK;
-}
-
-// backward of y = act(gamma*xhat + beta), xhat = (x-mean)*rstd:
-//   dg = dy*act'(pre) (ln_act_grad; tanh: dy*(1-y^2));  dxhat = dg*gamma;  dx = rstd*(dxhat - mean(dxhat) - xhat*mean(dxhat*xhat))
-template <int VPL>
-__global__ __launch_bounds__(256) void ln_tanh_bwd_kernel(LnBwdArgs a) {
-  const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-  if (row >= a.rows) return;
-  const int grp = row / a.rows_per_group;
-  constexpr int D = VPL * 64;
-  float dg[VPL], dxh[VPL], xh[VPL], y[VPL], gam[VPL];
-  float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-  for (int j = 0; j < VPL; ++j) {
-    const int col = lane * VPL + j;
-    const long lr = row - grp * a.rows_per_group;
-    y[j] = a.y[lr * a.ld_y + (long)grp * a.y_goff + col];
-    dg[j] = a.dq_w ? (a.dq ? a.dq[row] : a.dq_const) * a.dq_w[(long)grp * a.dq_w_gstride + col]
-                   : a.dy[lr * a.ld_dy + (long)grp * a.dy_goff + col];
-    xh[j] = a.xhat[(long)row * D + col];
-    gam[j] = a.gamma[(long)grp * a.pstride + col];
-  }
-  ln_act_grad<VPL, 1>(a.act, dg, y, xh, gam, a.beta, (long)grp * a.pstride + lane * VPL);
-#pragma unroll
-  for (int j = 0; j < VPL; ++j) {
-    dxh[j] = dg[j] * gam[j];
-    s1 += dxh[j];
-    s2 += dxh[j] * xh[j];
-  }
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) { s1 += __shfl_xor(s1, off); s2 += __shfl_xor(s2, off); }
-  const float m1 = s1 * (1.0f / D), m2 = s2 * (1.0f / D), rstd = a.rstd[row];
-#pragma unroll
-  for (int j = 0; j < VPL; ++j) {
-    const int col = lane * VPL + j;
-    a.dx[(long)row * D + col] = rstd * (dxh[j] - m1 - xh[j] * m2);
-    a.dg[(long)row * D + col] = dg[j];
-  }
-}
-
-// (the swish backward recomputes its pre-activation: it reads beta where the forward did)
-#define SERL_LN_BWD_ACT_OK(a)                                                                                             \
-  SERL_REQUIRE((a).act >= 0 && (a).act < kActCount && ((a).act != kActSwish || (a).beta),                                 \
-               "LayerNorm backward: activation code %d is not tanh (0), relu (1) or swish (2), or swish without beta", (a).act)
-
-int ln_tanh_bwd(const LnBwdArgs& a, int D, hipStream_t stream) {
-  SERL_REQUIRE(SERL_LN_WIDTH_OK(D), "LayerNorm width %d unsupported (a multiple of 64 in [64, 1024])", D);
-  SERL_LN_BWD_ACT_OK(a);
-  if (D != 256 && D != 64) {   // the width-generic rows: one instance of ln_tanh_bwd_multi's launch, no rider
-    LnBwdArgs w = a;
-    w.D = D; w.dq_inline = 0;
-    return ln_tanh_bwd_multi(&w, 1, LossArgs{}, stream);
-  }
-  dim3 grid(cdiv(a.rows, 4));
-  if (D == 256) SERL_LAUNCH_CHAIN(ln_tanh_bwd_kernel<4>, grid, dim3(256), 0, stream, a);
-  else SERL_LAUNCH_CHAIN(ln_tanh_bwd_kernel<1>, grid, dim3(256), 0, stream, a);
+  SERL_LN_LAUNCH(D, (ln_fwd_kernel<1, false>), (ln_fwd_kernel<4, true>), ln_fwd_kernel, grid, dim3(256), 0, stream, mv)
   SERL_HIP(hipGetLastError());
   return SERL_OK;
 }
@@ -1227,122 +1084,93 @@ __device__ void critic_loss_body(const LossArgs& L, float (*red)[256]) {
   }
 }
 
-template <int VPL>
-__device__ __forceinline__ void ln_tanh_bwd_row(const LnBwdArgs& a, const LossArgs& L, int row, int lane) {
+// backward of ONE row of y = act(gamma*xhat + beta), xhat = (x-mean)*rstd, by one wave, in the lane-to-column layout of ln_row:
+//   dg = dy*act'(pre) (ln_act_grad; tanh: dy*(1-y^2));  dxhat = dg*gamma;  dx = rstd*(dxhat - mean(dxhat) - xhat*mean(dxhat*xhat))
+// a lane sums its columns in ascending order, then the xor butterfly.  L: the launch's critic loss, read by a dq_inline row alone.
+template <int VPL, bool BLOCKED>
+__device__ __forceinline__ void ln_bwd_row(const LnBwdArgs& a, const LossArgs& L, int row, int lane) {
   const int grp = row / a.rows_per_group;
   constexpr int D = VPL * 64;
   float dg[VPL], dxh[VPL], xh[VPL], y[VPL], gam[VPL];
   float s1 = 0.f, s2 = 0.f;
   const long lr = row - grp * a.rows_per_group;
+  const int c0 = ln_col0<VPL, BLOCKED>(lane);
   float dqr = 0.f;
   if (a.dq_w) dqr = a.dq_inline ? 2.f * (L.q[row] - redq_target(L, (int)lr)) * L.inv_norm : (a.dq ? a.dq[row] : a.dq_const);
 #pragma unroll
   for (int j = 0; j < VPL; ++j) {
-    const int col = lane * VPL + j;
+    const int col = c0 + kLnStep<BLOCKED> * j;
     y[j] = a.y[lr * a.ld_y + (long)grp * a.y_goff + col];
     dg[j] = a.dq_w ? dqr * a.dq_w[(long)grp * a.dq_w_gstride + col] : a.dy[lr * a.ld_dy + (long)grp * a.dy_goff + col];
     xh[j] = a.xhat[(long)row * D + col];
     gam[j] = a.gamma[(long)grp * a.pstride + col];
   }
-  ln_act_grad<VPL, 1>(a.act, dg, y, xh, gam, a.beta, (long)grp * a.pstride + lane * VPL);
+  ln_act_grad<VPL, BLOCKED ? 1 : 64>(a.act, dg, y, xh, gam, a.beta, (long)grp * a.pstride + c0);
 #pragma unroll
   for (int j = 0; j < VPL; ++j) {
     dxh[j] = dg[j] * gam[j];
     s1 += dxh[j];
     s2 += dxh[j] * xh[j];
   }
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) { s1 += __shfl_xor(s1, off); s2 += __shfl_xor(s2, off); }
+  wave_sum2(s1, s2);
   const float m1 = s1 * (1.0f / D), m2 = s2 * (1.0f / D), rstd = a.rstd[row];
 #pragma unroll
   for (int j = 0; j < VPL; ++j) {
-    const int col = lane * VPL + j;
+    const int col = c0 + kLnStep<BLOCKED> * j;
     a.dx[(long)row * D + col] = rstd * (dxh[j] - m1 - xh[j] * m2);
     a.dg[(long)row * D + col] = dg[j];
   }
 }
 
-// blockIdx.y = instance (its own width); the LAST workgroup of instance 0 is the critic-loss rider when loss.on
-__global__ __launch_bounds__(256) void ln_tanh_bwd_multi_kernel(Multi<LnBwdArgs> mv, LossArgs loss) {
+// A LayerNorm-backward launch: blockIdx.y = instance, one wave per row, four rows per workgroup; the LAST workgroup of instance 0
+// is the critic-loss rider when loss.on.  VPL > 0: every instance has the width 64 * VPL (the MLP layers at a hidden width other
+// than 256).  VPL == 0: instances of width 256 or 64, each its own (the encoder heads: the cameras' bottleneck and the proprio
+// branch in one launch; and the MLP layers at the default width).
+constexpr int kLnMixed = 0;
+template <int VPL, bool BLOCKED>
+__global__ __launch_bounds__(256) void ln_bwd_kernel(Multi<LnBwdArgs> mv, LossArgs loss) {
   __shared__ float red[4][256];
   if (loss.on && blockIdx.y == 0 && blockIdx.x == gridDim.x - 1) { critic_loss_body(loss, red); return; }
   const LnBwdArgs& a = mv.v[blockIdx.y];
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (row >= a.rows) return;
-  if (a.D == 256) ln_tanh_bwd_row<4>(a, loss, row, lane);
-  else ln_tanh_bwd_row<1>(a, loss, row, lane);
+  if constexpr (VPL != kLnMixed) ln_bwd_row<VPL, BLOCKED>(a, loss, row, lane);
+  else if (a.D == 256) ln_bwd_row<4, true>(a, loss, row, lane);
+  else ln_bwd_row<1, false>(a, loss, row, lane);
 }
 
-// ln_tanh_bwd_row at any width D = 64 * VPL, with the strided lane-to-column layout of ln_tanh_row (lane l holds columns
-// l + 64 j: 256 consecutive bytes per wave access at every width); a lane sums its columns in ascending order
-template <int VPL>
-__device__ __forceinline__ void ln_tanh_bwd_row_wide(const LnBwdArgs& a, const LossArgs& L, int row, int lane) {
-  const int grp = row / a.rows_per_group;
-  constexpr int D = VPL * 64;
-  float dg[VPL], dxh[VPL], xh[VPL], y[VPL], gam[VPL];
-  float s1 = 0.f, s2 = 0.f;
-  const long lr = row - grp * a.rows_per_group;
-  float dqr = 0.f;
-  if (a.dq_w) dqr = a.dq_inline ? 2.f * (L.q[row] - redq_target(L, (int)lr)) * L.inv_norm : (a.dq ? a.dq[row] : a.dq_const);
-#pragma unroll
-  for (int j = 0; j < VPL; ++j) {
-    const int col = lane + 64 * j;
-    y[j] = a.y[lr * a.ld_y + (long)grp * a.y_goff + col];
-    dg[j] = a.dq_w ? dqr * a.dq_w[(long)grp * a.dq_w_gstride + col] : a.dy[lr * a.ld_dy + (long)grp * a.dy_goff + col];
-    xh[j] = a.xhat[(long)row * D + col];
-    gam[j] = a.gamma[(long)grp * a.pstride + col];
-  }
-  ln_act_grad<VPL, 64>(a.act, dg, y, xh, gam, a.beta, (long)grp * a.pstride + lane);
-#pragma unroll
-  for (int j = 0; j < VPL; ++j) {
-    dxh[j] = dg[j] * gam[j];
-    s1 += dxh[j];
-    s2 += dxh[j] * xh[j];
-  }
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) { s1 += __shfl_xor(s1, off); s2 += __shfl_xor(s2, off); }
-  const float m1 = s1 * (1.0f / D), m2 = s2 * (1.0f / D), rstd = a.rstd[row];
-#pragma unroll
-  for (int j = 0; j < VPL; ++j) {
-    const int col = lane + 64 * j;
-    a.dx[(long)row * D + col] = rstd * (dxh[j] - m1 - xh[j] * m2);
-    a.dg[(long)row * D + col] = dg[j];
-  }
-}
-
-// ln_tanh_bwd_multi_kernel for instances that all have the width 64 * VPL (the MLP layers at a hidden width other than 256)
-template <int VPL>
-__global__ __launch_bounds__(256) void ln_tanh_bwd_multi_wide_kernel(Multi<LnBwdArgs> mv, LossArgs loss) {
-  __shared__ float red[4][256];
-  if (loss.on && blockIdx.y == 0 && blockIdx.x == gridDim.x - 1) { critic_loss_body(loss, red); return; }
-  const LnBwdArgs& a = mv.v[blockIdx.y];
+// One instance of a default width without a rider (most LayerNorm backward launches of the default agent, BC, the classifier):
+// the same row behind a launch that carries one LnBwdArgs (ln_bwd_kernel's arguments are four of them and the loss).  Measured:
+// with ln_bwd_kernel in its place the update step is 0.36 % slower (profiles/README.md).
+template <int VPL, bool BLOCKED>
+__global__ __launch_bounds__(256) void ln_bwd_one_kernel(LnBwdArgs a) {
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (row >= a.rows) return;
-  ln_tanh_bwd_row_wide<VPL>(a, loss, row, lane);
+  ln_bwd_row<VPL, BLOCKED>(a, LossArgs{}, row, lane);   // (no dq_inline without a loss: ln_bwd_multi checks)
 }
 
-int ln_tanh_bwd_multi(const LnBwdArgs* as, int n, const LossArgs& loss, hipStream_t stream) {
+int ln_bwd_multi(const LnBwdArgs* as, int n, const LossArgs& loss, hipStream_t stream) {
   SERL_REQUIRE(n >= 1 && n <= kMaxMulti, "bad instance count %d", n);
   Multi<LnBwdArgs> mv{};
   int rows = 0;
-  bool wide = false;
+  const auto mixes = [](int D) { return D == 64 || D == 256; };
   for (int i = 0; i < n; ++i) {
     SERL_REQUIRE(SERL_LN_WIDTH_OK(as[i].D), "LayerNorm width %d unsupported (a multiple of 64 in [64, 1024])", as[i].D);
     SERL_REQUIRE(!as[i].dq_inline || (loss.on && as[i].dq_w && as[i].rows == loss.E * loss.B && as[i].rows_per_group == loss.B),
                  "inline dQ needs the loss arguments of the launch");
-    SERL_LN_BWD_ACT_OK(as[i]);
+    // (the swish backward recomputes its pre-activation: it reads beta where the forward did)
+    SERL_REQUIRE(as[i].act >= 0 && as[i].act < kActCount && (as[i].act != kActSwish || as[i].beta),
+                 "LayerNorm backward: activation code %d is not tanh (0), relu (1) or swish (2), or swish without beta", as[i].act);
     mv.v[i] = as[i];
     rows = std::max(rows, as[i].rows);
-    wide = wide || (as[i].D != 256 && as[i].D != 64);
+    // (64 and 256 may share a launch -- the encoder heads; any other width comes from one MLP layer and is alone)
+    SERL_REQUIRE(as[i].D == as[0].D || (mixes(as[i].D) && mixes(as[0].D)),
+                 "LayerNorm widths %d and %d in one launch: widths other than 64 and 256 do not mix", as[0].D, as[i].D);
   }
   const dim3 grid(cdiv(rows, 4) + (loss.on ? 1 : 0), n);
-  if (wide) {   // (64 and 256 may share a launch -- the encoder heads; any other width comes from one MLP layer and is alone)
-    for (int i = 1; i < n; ++i)
-      SERL_REQUIRE(as[i].D == as[0].D, "LayerNorm widths %d and %d in one launch: widths other than 64 and 256 do not mix", as[0].D, as[i].D);
-    SERL_LN_WIDE_LAUNCH(ln_tanh_bwd_multi_wide_kernel, as[0].D, grid, dim3(256), 0, stream, mv, loss)
-  } else {
-    SERL_LAUNCH_CHAIN(ln_tanh_bwd_multi_kernel, grid, dim3(256), 0, stream, mv, loss);
-  }
+  if (n == 1 && !loss.on && as[0].D == 256) SERL_LAUNCH_CHAIN((ln_bwd_one_kernel<4, true>), grid, dim3(256), 0, stream, as[0]);
+  else if (n == 1 && !loss.on && as[0].D == 64) SERL_LAUNCH_CHAIN((ln_bwd_one_kernel<1, false>), grid, dim3(256), 0, stream, as[0]);
+  else SERL_LN_LAUNCH(as[0].D, (ln_bwd_kernel<kLnMixed, false>), (ln_bwd_kernel<kLnMixed, false>), ln_bwd_kernel, grid, dim3(256), 0, stream, mv, loss)
   SERL_HIP(hipGetLastError());
   return SERL_OK;
 }
@@ -1518,10 +1346,10 @@ __device__ __forceinline__ void proprio_row(const ProprioArgs& a, int S, int row
     for (; s < cnt; ++s) v += __shfl(mine, s) * a.W[(s0 + s) * 64 + lane];
   }
   float s1 = v, s2 = v * v;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) { s1 += __shfl_xor(s1, off); s2 += __shfl_xor(s2, off); }
-  const float mean = s1 * (1.0f / 64), var = fmaxf(s2 * (1.0f / 64) - mean * mean, 0.f);
-  const float rstd = rsqrtf(var + 1e-6f), xh = (v - mean) * rstd;
+  wave_sum2(s1, s2);
+  float mean, rstd;
+  ln_mean_rstd<64>(s1, s2, mean, rstd);
+  const float xh = (v - mean) * rstd;
   a.y[(long)row * a.ld_y + lane] = tanhf(xh * a.gamma[lane] + a.beta[lane]);
   if (a.xhat) a.xhat[(long)row * 64 + lane] = xh;
   if (a.rstd && lane == 0) a.rstd[row] = rstd;

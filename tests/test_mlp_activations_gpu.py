@@ -54,7 +54,7 @@ def test_hip_update_matches_the_reference_golden_with_activation(gpu, name):
 
 
 # ---- the three row layouts against the restated oracle ---------------------------------------------------------------------------
-# (id, hidden, rows): 64 = the width-64 kernel; 256 = the blocked rows; 192 / 1024 = the strided rows at 3 and 16 columns per lane.
+# (id, hidden, rows): 256 = the blocked rows (ln_row<4, true>); 64 / 192 / 1024 = the strided rows at 1, 3 and 16 columns per lane.
 # 8 rows = two LayerNorm workgroups per member; 72 rows = two 64-row GEMM tiles, the second ragged.
 ROWS = [("w64_B8", 64, 8), ("w192_B8", 192, 8), ("w256_B8", 256, 8), ("w1024_B8", 1024, 8), ("w192_B72", 192, 72)]
 
