@@ -31,15 +31,15 @@ def host_crop(frames, offsets, padding=4):
     return out
 
 
-def features(params, image_keys, frames):
-    """frames {k: u8 [B, H, W, 3]} -> {k: fp64 trunk features [B, h, w, 512]} (frozen: computed once per batch)"""
-    tp = {k: torch.tensor(np.asarray(v), dtype=torch.float64) for k, v in params.items() if k.startswith("trunk/")}
+def features(params, image_keys, frames, dtype=torch.float64):
+    """frames {k: u8 [B, H, W, 3]} -> {k: trunk features [B, h, w, 512] in `dtype`} (frozen: computed once per batch)"""
+    tp = {k: torch.tensor(np.asarray(v), dtype=dtype) for k, v in params.items() if k.startswith("trunk/")}
     with torch.no_grad():
-        return {k: O.trunk_forward(tp, torch.as_tensor(np.ascontiguousarray(frames[k])), torch.float64) for k in image_keys}
+        return {k: O.trunk_forward(tp, torch.as_tensor(np.ascontiguousarray(frames[k])), dtype) for k in image_keys}
 
 
-def forward(th, image_keys, feats, masks=None):
-    """reward_classifier.py:20-28; masks None = train=False (both Dropout layers are the identity)"""
+def hidden(th, image_keys, feats, masks=None):
+    """reward_classifier.py:20-26, up to the ReLU; masks None = train=False (both Dropout layers are the identity)"""
     codes = []
     for k in image_keys:
         f = O.sle(feats[k], th[f"enc/{k}/sle"])                                   # resnet_v1.py:341-349
@@ -51,8 +51,12 @@ def forward(th, image_keys, feats, masks=None):
     x = x @ th["head/dense0/kernel"] + th["head/dense0/bias"]                     # reward_classifier.py:23
     if masks is not None:                                                         # :24 Dropout before the LayerNorm
         x = torch.where(torch.as_tensor(masks["head"]).bool(), x / KEEP, torch.zeros_like(x))
-    x = torch.relu(O.layer_norm(x, th["head/ln/scale"], th["head/ln/bias"]))
-    return x @ th["head/dense1/kernel"] + th["head/dense1/bias"]
+    return torch.relu(O.layer_norm(x, th["head/ln/scale"], th["head/ln/bias"]))
+
+
+def forward(th, image_keys, feats, masks=None):
+    """reward_classifier.py:20-28"""
+    return hidden(th, image_keys, feats, masks) @ th["head/dense1/kernel"] + th["head/dense1/bias"]
 
 
 def sigmoid_bce(logits, labels):
@@ -61,10 +65,11 @@ def sigmoid_bce(logits, labels):
 
 
 class State:
-    """params / mu / nu as fp64 numpy flat dicts (moments of the trainable leaves only), step"""
+    """params / mu / nu as fp64 numpy flat dicts (moments of the trainable leaves only), step.  dtype: the precision train_step
+    computes the forward, the loss and the gradients in (float32 = the yardstick of what plain fp32 attains)"""
 
-    def __init__(self, params, image_keys, lr=1e-4):
-        self.keys = tuple(image_keys)
+    def __init__(self, params, image_keys, lr=1e-4, dtype=torch.float64):
+        self.keys, self.dtype = tuple(image_keys), dtype
         self.params = {k: np.asarray(v, np.float64).copy() for k, v in params.items()}
         self.mu = {k: np.zeros_like(self.params[k]) for k in trainable(self.keys)}
         self.nu = {k: np.zeros_like(self.params[k]) for k in trainable(self.keys)}
@@ -74,23 +79,23 @@ class State:
 
 def train_step(st: State, feats, labels, masks):
     """One train_step: -> (loss, accuracy, eval logits, grads); st is updated (optax.adam(lr), b1 0.9, b2 0.999, eps 1e-8)"""
-    th = {k: torch.tensor(st.params[k].reshape(st.shapes[k]), dtype=torch.float64, requires_grad=True) for k in trainable(st.keys)}
-    y = torch.as_tensor(np.asarray(labels, np.float64).reshape(-1, 1))
+    th = {k: torch.tensor(st.params[k].reshape(st.shapes[k]), dtype=st.dtype, requires_grad=True) for k in trainable(st.keys)}
+    y = torch.as_tensor(np.asarray(labels, np.float64).reshape(-1, 1)).to(st.dtype)
     logits = forward(th, st.keys, feats, masks)
     loss = sigmoid_bce(logits, y).mean()
     grads = torch.autograd.grad(loss, [th[k] for k in trainable(st.keys)])
     with torch.no_grad():
         ev = forward(th, st.keys, feats, None)
-        acc = ((torch.sigmoid(ev) >= 0.5).double() == y).double().mean()
+        acc = ((torch.sigmoid(ev) >= 0.5).to(st.dtype) == y).double().mean()
     st.step += 1
     t = st.step
     g_out = {}
     for k, g in zip(trainable(st.keys), grads):
-        g = g.detach().numpy().reshape(-1)
+        g = g.detach().double().numpy().reshape(-1)
         g_out[k] = g
         st.mu[k] = 0.9 * st.mu[k].reshape(-1) + 0.1 * g
         st.nu[k] = 0.999 * st.nu[k].reshape(-1) + 0.001 * g * g
         mh = st.mu[k] / (1.0 - 0.9 ** t)
         nh = st.nu[k] / (1.0 - 0.999 ** t)
         st.params[k] = st.params[k].reshape(-1) - st.lr * mh / (np.sqrt(nh) + 1e-8)
-    return float(loss.detach()), float(acc), ev.detach().numpy(), g_out
+    return float(loss.detach()), float(acc), ev.detach().double().numpy(), g_out

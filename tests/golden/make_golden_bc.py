@@ -11,6 +11,11 @@ CRC-guarded).  Recorded: the Dropout keep-masks and normals the run drew (from t
 SERL_JAXSHIM_PRNG=threefry they are jax.random's own), the info dicts, state.rng, the final trainable params and Adam
 moments (golden_update.leaf_record: full or sampled), the parameter / optimizer-state tree, the encoder output of the first
 update (for the fp64 NumPy restatement in tests/test_bc_cpu.py), and sample_actions / get_debug_metrics on a fresh batch.
+
+A case may carry the hooks oracle.ref_update_runner.run_reference has: theta_transform(theta, cfg) -> theta on the leaves before
+they are patched into the reference agent, and batch_transform(pb, step) -> pb on every synthetic sample (step = the number of
+updates for the inference batch).  bc_regime_64 and bc_regime_sat_64 use them to run the reference's BCAgent in the trained regime of
+tests/learner_regimes.py (std clipped on both sides in whole columns, saturated tanh, hardened batches).
 """
 import json
 import os
@@ -23,6 +28,7 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
 from oracle import drq_oracle as O  # noqa: E402
 from oracle import golden_update as G  # noqa: E402
 from oracle import ref_update_runner as RR  # noqa: E402
@@ -58,7 +64,25 @@ CASES = {
     "bc_128": (O.Config(image_keys=("front", "wrist"), H=128, W=128, S=24, A=6), 256, 1),
     # the reference's own random stream (jax.random's threefry): masks / eps are drawn from the keys, nothing injected
     "bc_64_threefry": (O.Config(image_keys=("front", "wrist"), H=64, W=64, S=5, A=3), 8, 2),
+    # the trained regime (tests/learner_regimes.py: BC_GOLDEN, BC_CFG, BC_B): two updates at A = 5, both clips binding in whole columns
+    "bc_regime_64": (O.Config(image_keys=("front", "wrist"), H=64, W=64, S=5, A=5), 8, 2),
+    # ... one update with hidden tanh units at exactly +-1 in fp32 as well (BC_GOLDEN_SAT: compared on infos and moments only)
+    "bc_regime_sat_64": (O.Config(image_keys=("front", "wrist"), H=64, W=64, S=5, A=5), 8, 1),
 }
+
+
+def hooks(name, cfg):
+    """-> (theta_transform, batch_transform, what meta["regime"] says of them) of a case; built only for the case that has them"""
+    if not name.startswith("bc_regime_"):
+        return None, None, None
+    import learner_regimes as LR
+    sat_bias = LR.BC_GOLDEN_SAT_BIASES[name]
+    assert cfg == LR.BC_CFG
+    return (LR.bc_golden_theta_transform(sat_bias), LR.bc_golden_batch_transform(cfg, PARAM_SEED, sat_bias),
+            {"transform": "bc_trained_like", "which": "both", "seed": LR.BC_SEED, "sat_bias": list(sat_bias),
+             "batch_transform": "harden_bc_batch", "batch_seed": LR.BC_BATCH_SEED})
+
+
 ONLY = [a for a in sys.argv[1:] if not a.startswith("-")]
 
 
@@ -136,13 +160,15 @@ def _masks(tape, cfg, rows, ctx_prefix):
     return out
 
 
-def run_case(cfg, B, n_steps, prng):
+def run_case(cfg, B, n_steps, prng, theta_transform=None, batch_transform=None, regime=None):
     jax = R.install(True)
     import jax.numpy as jnp
     from flax.core.frozen_dict import freeze
     import torch
 
     trunk, theta = theta_of(cfg, PARAM_SEED)
+    if theta_transform is not None:
+        theta = theta_transform(theta, cfg)
     agent = _make_agent(jax, jnp, cfg, trunk)
     params = jax.tree_map(lambda a: a, agent.state.params)
     first = sorted(cfg.image_keys)[0]
@@ -166,6 +192,8 @@ def run_case(cfg, B, n_steps, prng):
     infos = []
     for i in range(n_steps):
         pb = RR.synth_packed_batch(cfg, B, BATCH_SEED + i)
+        if batch_transform is not None:
+            pb = batch_transform(pb, i)
         batch = RR._to_reference_batch(jnp, freeze, pb, cfg)
         for k, v in pb["frames"].items():
             rec[f"s{i}_crc_{k}"] = np.uint32(zlib.crc32(v.tobytes()))
@@ -210,6 +238,8 @@ def run_case(cfg, B, n_steps, prng):
 
     # inference on a fresh batch, train=False
     pb = RR.synth_packed_batch(cfg, B, INFER_SEED)
+    if batch_transform is not None:
+        pb = batch_transform(pb, n_steps)
     for k, v in pb["frames"].items():
         rec[f"inf_crc_{k}"] = np.uint32(zlib.crc32(v.tobytes()))
     obs = {k: jnp.asarray(v[:, :1]) for k, v in pb["frames"].items()}
@@ -235,6 +265,8 @@ def run_case(cfg, B, n_steps, prng):
             "rng_final": [int(v) & 0xFFFFFFFF for v in np.asarray(st.rng).reshape(-1)], "final_step": int(np.asarray(st.step)),
             "param_paths": param_paths, "param_tree": _shapes(dict(st.params)),
             "opt_state": _opt_state_form(jax, st.opt_states), "info_keys": sorted(infos[0])}
+    if regime is not None:
+        meta["regime"] = regime
     rec["meta"] = np.array(json.dumps(meta))
     return rec
 
@@ -270,7 +302,7 @@ def main():
             os.environ["SERL_JAXSHIM_PRNG"] = "threefry"
         else:
             os.environ.pop("SERL_JAXSHIM_PRNG", None)
-        rec = run_case(cfg, B, n, os.environ.get("SERL_JAXSHIM_PRNG", "philox"))
+        rec = run_case(cfg, B, n, os.environ.get("SERL_JAXSHIM_PRNG", "philox"), *hooks(name, cfg))
         os.environ.pop("SERL_JAXSHIM_PRNG", None)
         path = os.path.join(out_dir, f"{name}.npz")
         np.savez_compressed(path, **rec)

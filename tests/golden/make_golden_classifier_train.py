@@ -15,6 +15,11 @@ Recorded per epoch: the keys of the chain (crop and train step), the Dropout kee
 scope paths), loss and train_accuracy, and the eval logits; at the end the trainable params and Adam moments
 (golden_update.leaf_record), the TrainState tree paths / shapes and the optimizer-state form, and the first two cropped
 frames of camera 0 in epoch 0.
+
+A case may carry two hooks: a frame builder (keys, H, W, B, epochs) -> [frames of epoch e] in place of the seeded noise, and a
+parameter transform (keys, H, W, param seed, [cropped frames of epoch e]) -> params in place of make_params alone.
+regime_one_cam_64 uses them to run the loop in the regime of tests/learner_regimes.py: structured frames and a hand-built head whose
+logits span both signs from below 1 to beyond 90.
 """
 import json
 import os
@@ -26,6 +31,7 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
 os.environ["SERL_JAXSHIM_PRNG"] = "threefry"
 from oracle import ref_update_shim as R   # noqa: E402
 
@@ -40,7 +46,19 @@ from serl_launcher.vision.data_augmentations import batched_random_crop   # noqa
 
 # name: (image keys, H, W, batch, epochs, param seed, data seed)
 CASES = {"two_cams_128": (("front", "wrist"), 128, 128, 8, 3, 21, 500),
-         "one_cam_64": (("image",), 64, 64, 6, 3, 22, 600)}
+         "one_cam_64": (("image",), 64, 64, 6, 3, 22, 600),
+         # the regime of tests/learner_regimes.py (CLS_GOLDEN, CLS_KEYS, CLS_H, CLS_W, CLS_GOLDEN_B, CLS_PARAM_SEED); no data seed: its frames are built
+         "regime_one_cam_64": (("image",), 64, 64, 6, 2, 23, 0)}
+
+
+def hooks(name, case):
+    """-> (frame builder, parameter transform, what meta["regime"] says of them) of a case; built only for the case that has them"""
+    if name != "regime_one_cam_64":
+        return None, None, None
+    import learner_regimes as LR
+    assert name == LR.CLS_GOLDEN and case[:4] == (LR.CLS_KEYS, LR.CLS_H, LR.CLS_W, LR.CLS_GOLDEN_B) and case[5] == LR.CLS_PARAM_SEED
+    return (LR.cls_golden_frames, LR.cls_golden_params,
+            {"frames": "cls_golden_frames", "params": "cls_golden_params", "targets": list(LR.CLS_GOLDEN_TARGETS)})
 
 
 def sigmoid_binary_cross_entropy(logits, labels):
@@ -85,7 +103,7 @@ def leaf_paths(keys):
     return out
 
 
-def run_case(keys, H, W, B, epochs, pseed, dseed):
+def run_case(keys, H, W, B, epochs, pseed, dseed, frames_fn=None, params_fn=None, regime=None):
     params0 = CO.make_params(keys, H, W, pseed)
     d = tempfile.mkdtemp()
     pkl = os.path.join(d, "resnet10_params.pkl")
@@ -102,6 +120,16 @@ def run_case(keys, H, W, B, epochs, pseed, dseed):
     hw = (H // 32) * (W // 32)
     side = int(round(hw ** 0.5))
     paths = leaf_paths(keys)
+    data_rng = np.random.default_rng(dseed)
+    all_frames = frames_fn(keys, H, W, B, epochs) if frames_fn else [epoch_frames(data_rng, keys, B, H, W) for _ in range(epochs)]
+    if params_fn is not None:   # the crops the loop below will draw: the same key chain, walked ahead on a copy
+        r, cropped = rng, []
+        for e in range(epochs):
+            r, ck = jax.random.split(r)
+            r, _ = jax.random.split(r)
+            cropped.append({k: np.asarray(batched_random_crop(jnp.asarray(v), ck, padding=4, num_batch_dims=2)).astype(np.uint8)[:, 0]
+                            for k, v in all_frames[e].items()})
+        params0 = params_fn(keys, H, W, pseed, cropped)
     for name, path in paths.items():
         v = params0[name]
         if name.endswith("/sle"):
@@ -125,10 +153,9 @@ def run_case(keys, H, W, B, epochs, pseed, dseed):
         train_accuracy = jnp.mean((jax.nn.sigmoid(logits) >= 0.5) == batch["labels"])
         return state.apply_gradients(grads=grads), loss, train_accuracy, logits
 
-    data_rng = np.random.default_rng(dseed)
     rec["rng0"] = ints(rng)
     for e in range(epochs):
-        frames = epoch_frames(data_rng, keys, B, H, W)   # [pos next_observations; neg observations]
+        frames = all_frames[e]   # [pos next_observations; neg observations]
         rng, key = jax.random.split(rng)
         rec[f"e{e}_crop_key"] = ints(key)
         cropped = {k: batched_random_crop(jnp.asarray(v), key, padding=4, num_batch_dims=2) for k, v in frames.items()}
@@ -168,6 +195,8 @@ def run_case(keys, H, W, B, epochs, pseed, dseed):
                 assert not np.any(np.asarray(v)), p
     meta = {"image_keys": list(keys), "H": H, "W": W, "B": B, "epochs": epochs, "param_seed": pseed, "data_seed": dseed,
             "final_step": int(np.asarray(st.step)), "opt_state": opt_form, "lr": 1e-4}
+    if regime is not None:
+        meta["regime"] = regime
     rec["meta"] = np.array(json.dumps(meta))
     return rec
 
@@ -184,7 +213,7 @@ def main():
     for name, case in CASES.items():
         if only and name not in only:
             continue
-        rec = run_case(*case)
+        rec = run_case(*case, *hooks(name, case))
         path = os.path.join(out_dir, f"classifier_train_{name}.npz")
         np.savez_compressed(path, **rec)
         meta = json.loads(str(rec["meta"]))
