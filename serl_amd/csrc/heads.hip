@@ -1358,15 +1358,18 @@ __device__ __forceinline__ void proprio_row(const ProprioArgs& a, int S, int row
 }
 
 // SpatialLearnedEmbeddings, channel-blocked: a workgroup = 256 channels x kSleNb samples.  The embedding kernel K
-// ([HW][C][8]: 256 KB per camera at 4x4x512) is read ONCE per workgroup, four pixels at a time into registers, instead of
+// ([HW][C][8]: 256 KB per camera at 4x4x512) is read ONCE per workgroup, kPx pixels at a time into registers, instead of
 // once per sample (round 3: 393 MB of L2 reads per update phase, 30 us alone / 160-190 us next to the trunk pass); every
 // sample's 8 outputs stay in registers across the pixel loop (same hw-ascending sum as before: bit-identical).  The Dropout(0.1)
 // keep-mask (resnet_v1.py:351), when not supplied, is hashed from (seed, camera, GLOBAL sample, channel): three 64-bit hashes
 // give the eight 24-bit uniforms of a thread's eight outputs -- no mask tensor, no gen_noise launch.  Workgroups past the SLE
 // range run the proprio branch of the same instance (camera 0 only): one launch instead of two.
-// kSleNb samples per workgroup; a rank's share of a data-parallel batch (<= 64 samples) takes 2, which keeps 4x more workgroups
-// in flight (96 workgroups of 8 samples each took 64 us next to the trunk pass at 32 samples)
-template <int kSleNb>
+// kSleNb samples per workgroup; a rank's share of a data-parallel batch (<= 64 samples) takes 2 samples x 4 pixels (64 VGPRs), which
+// keeps more workgroups in flight (96 workgroups of 8 samples each took 64 us next to the trunk pass at 32 samples).  Larger
+// batches take 4 samples x 2 pixels: 32 sums + 16 embedding values + 8 pixels = 62 VGPRs, so a wave fits into the 80 registers per
+// SIMD that two resident trunk workgroups leave (scripts/kernel_resources.py).  The 8 x 4 form this replaces took 150 and fitted
+// beside no trunk kernel; alone it was no faster (31 / 37 us per launch at B = 256 against 26 / 34, profiles/README.md).
+template <int kSleNb, int kPx>
 __global__ __launch_bounds__(256) void sle_proprio_fwd_kernel(Multi<SleFwdArgs> mv, Multi<ProprioArgs> pv, int has_proprio,
                                                               float keep_scale, unsigned keep_thr, float keep_p, int N, int HW, int Cc,
                                                               long xs, long ks, long ms, long fs, int S, int nb_sle) {
@@ -1388,23 +1391,23 @@ __global__ __launch_bounds__(256) void sle_proprio_fwd_kernel(Multi<SleFwdArgs> 
   for (int s = 0; s < kSleNb; ++s)
 #pragma unroll
     for (int j = 0; j < 8; ++j) acc[s][j] = 0.f;
-  for (int hw0 = 0; hw0 < HW; hw0 += 4) {
-    float4 k0[4], k1[4];
+  for (int hw0 = 0; hw0 < HW; hw0 += kPx) {
+    float4 k0[kPx], k1[kPx];
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
+    for (int i = 0; i < kPx; ++i) {
       const int hw = min(hw0 + i, HW - 1);
       k0[i] = *reinterpret_cast<const float4*>(K + (long)hw * Cc * 8);
       k1[i] = *reinterpret_cast<const float4*>(K + (long)hw * Cc * 8 + 4);
     }
     // (no branch on the sample count: samples past the end re-read the last one and are never stored -- a branch per sample kept
     //  the compiler from issuing the 32 pixel loads of a chunk together: 48 us against 36 for the un-blocked kernel)
-    float xv[kSleNb][4];
+    float xv[kSleNb][kPx];
 #pragma unroll
     for (int s = 0; s < kSleNb; ++s)
 #pragma unroll
-      for (int i = 0; i < 4; ++i) xv[s][i] = x[((long)min(s, ns - 1) * HW + min(hw0 + i, HW - 1)) * Cc];
+      for (int i = 0; i < kPx; ++i) xv[s][i] = x[((long)min(s, ns - 1) * HW + min(hw0 + i, HW - 1)) * Cc];
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
+    for (int i = 0; i < kPx; ++i) {
       if (hw0 + i < HW) {   // (uniform; pixels past HW must not touch the sums)
 #pragma unroll
         for (int s = 0; s < kSleNb; ++s) {
@@ -1453,13 +1456,14 @@ int sle_proprio_fwd_multi(const SleFwdArgs* vs, const ProprioArgs* ps, int n, fl
     mv.v[i] = vs[i];
     if (ps) { pv.v[i] = ps[i]; SERL_REQUIRE(!ps[i].copy_dst || ps[i].copy_cols <= 64, "copy_cols > 64"); }
   }
-  const int nb = N <= 64 ? 2 : 8;
+  // (block sizes: see the kernel; tests/test_sle_block_gpu.py holds its row counts to the 4)
+  const int nb = N <= 64 ? 2 : 4;
   const int nb_sle = cdiv(Cc, 256) * cdiv(N, nb), nb_prop = ps ? cdiv(N, 4) : 0;
   if (nb == 2)
-    SERL_LAUNCH_CHAIN(sle_proprio_fwd_kernel<2>, dim3(nb_sle + nb_prop, groups, n), dim3(256), 0, stream, mv, pv, ps ? 1 : 0,
+    SERL_LAUNCH_CHAIN((sle_proprio_fwd_kernel<2, 4>), dim3(nb_sle + nb_prop, groups, n), dim3(256), 0, stream, mv, pv, ps ? 1 : 0,
                       1.0f / keep, (unsigned)(keep * 16777216.0f), keep, N, HW, Cc, x_gs, k_gs, mask_gs, f_gs, state_dim, nb_sle);
   else
-    SERL_LAUNCH_CHAIN(sle_proprio_fwd_kernel<8>, dim3(nb_sle + nb_prop, groups, n), dim3(256), 0, stream, mv, pv, ps ? 1 : 0,
+    SERL_LAUNCH_CHAIN((sle_proprio_fwd_kernel<4, 2>), dim3(nb_sle + nb_prop, groups, n), dim3(256), 0, stream, mv, pv, ps ? 1 : 0,
                       1.0f / keep, (unsigned)(keep * 16777216.0f), keep, N, HW, Cc, x_gs, k_gs, mask_gs, f_gs, state_dim, nb_sle);
   SERL_HIP(hipGetLastError());
   return SERL_OK;

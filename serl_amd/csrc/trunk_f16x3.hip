@@ -189,6 +189,8 @@ static int launch_conv_f16x3(const char* tag, const TrunkPlan::L& l, const ConvA
   ab.wprio = trunk_wave_prio(a.N);
   ab.stagger = l.stagger;
   if (l.fused) { ab.fz = fz; ab.fz.expected = l.expected; ab.fz.group = l.group; }
+  // (the projection kernels are compiled without the residual epilogues: conv_dma_f16x3_kernel)
+  SERL_REQUIRE(!l.proj || ab.fz.mode < 2, "%s: a conv with a fused projection cannot take a residual (mode %d)", tag, (int)ab.fz.mode);
   {
     ProfScope prof(tag, stream);
     if (l.kern == 'S') {

@@ -238,9 +238,18 @@ __device__ __forceinline__ void dma_proj_epilogue(const ConvArgsB& ab, const Con
 typedef __attribute__((address_space(3))) void lds_void_t;
 typedef __attribute__((address_space(1))) const void gbl_void_t;
 
+// Registers: 216 per lane at the most (VGPR + AGPR; on gfx90a and later the attribute counts the unified file in halves, 108 = 216),
+// so that two resident workgroups leave 80 per SIMD -- one wave of an update-chain GEMM (scripts/kernel_resources.py, DESIGN.md
+// sections 4 and 8).  The forms without the projection need 208-212 and are not touched by the cap; the 128 x 128 forms with the
+// projection reach 218-219 without it (224 allocated: 64 left, room for the chain's small kernels but not for its GEMMs, and the
+// pipelined step was 1.2 % SLOWER than with nothing beside them) and fit under it without scratch because they are compiled
+// without the residual epilogues (below; 215, profiles/ring_proj_isa.txt).
 template <int TN, int PMODE, bool PROJ = false>
-__global__ __launch_bounds__(256, 2) void conv_dma_f16x3_kernel(ConvArgsB ab, const uint8_t* zero_page, ConvProjB pj) {
+__global__ __launch_bounds__(256, 2) __attribute__((amdgpu_num_vgpr(108))) void conv_dma_f16x3_kernel(ConvArgsB ab, const uint8_t* zero_page, ConvProjB pj) {
   static_assert(!PROJ || PMODE != 3, "the fused projection takes its statistics in the kernel");
+  // A projection rides on a block's conv0 only, whose epilogue has no residual operand (launch_conv_f16x3 refuses another mode): the
+  // residual forms of dma_tile_epilogue, 64 loaded values beside the 64 of the tile, are not compiled into the projection kernels
+  if constexpr (PROJ) __builtin_assume(ab.fz.mode < 2);
   constexpr int NS = 4;
   const ConvArgs& a = ab.c;
   constexpr int TM = 2, WROWS = 64, WCOLS = 32 * TN, BM = 128, BN = 2 * WCOLS;
@@ -256,38 +265,41 @@ __global__ __launch_bounds__(256, 2) void conv_dma_f16x3_kernel(ConvArgsB ab, co
   const int bn = id % a.tiles_n, bm = id / a.tiles_n;
   const int m0 = bm * BM, n0 = bn * BN;
   const int ntaps = a.KH * a.KW;
+  // This lane's K-loop state is a function of the lane index alone: the A pieces' row bases and tap masks (piece_state), the
+  // fragment offsets (frag_state) and the zero page unit.  With a fused projection it is worked out again behind the projection's
+  // epilogue from an opaque copy of the lane index, so that none of it stays in registers across that epilogue
   unsigned rbase[A_PIECES], rmask[A_PIECES];
   const uint8_t* in_bytes = reinterpret_cast<const uint8_t*>(a.in);
+  auto piece_state = [&](int ln) {
 #pragma unroll
-  for (int q = 0; q < A_PIECES; ++q) {
-    const int row = (q * 4 + wave) * 16 + (lane >> 2);
-    const int u = (lane & 3) ^ ((row >> 2) & 3);
-    const int m = m0 + row;
-    rbase[q] = 0; rmask[q] = 0;
-    if (m < a.M) {
-      const int n = m / a.P, rem = m - n * a.P;
-      const int oy = rem / a.Wo, ox = rem - oy * a.Wo;
-      rbase[q] = (unsigned)((((long)(n * a.Hi + oy * a.stride) * a.Wi + ox * a.stride) * a.Cin) * 4 + u * 16);
-      for (int t = 0; t < ntaps; ++t) {
-        const int iy = oy * a.stride - a.pad + t / a.KW, ix = ox * a.stride - a.padw + t % a.KW;
-        if ((unsigned)iy < (unsigned)a.Hi && (unsigned)ix < (unsigned)a.Wi) rmask[q] |= 1u << t;
+    for (int q = 0; q < A_PIECES; ++q) {
+      const int row = (q * 4 + wave) * 16 + (ln >> 2);
+      const int u = (ln & 3) ^ ((row >> 2) & 3);
+      const int m = m0 + row;
+      rbase[q] = 0; rmask[q] = 0;
+      if (m < a.M) {
+        const int n = m / a.P, rem = m - n * a.P;
+        const int oy = rem / a.Wo, ox = rem - oy * a.Wo;
+        rbase[q] = (unsigned)((((long)(n * a.Hi + oy * a.stride) * a.Wi + ox * a.stride) * a.Cin) * 4 + u * 16);
+        for (int t = 0; t < ntaps; ++t) {
+          const int iy = oy * a.stride - a.pad + t / a.KW, ix = ox * a.stride - a.padw + t % a.KW;
+          if ((unsigned)iy < (unsigned)a.Hi && (unsigned)ix < (unsigned)a.Wi) rmask[q] |= 1u << t;
+        }
       }
     }
-  }
+  };
+  piece_state(lane);
   const int nslots = ntaps * (a.Cin >> 4);
   // The K loop below (SERL_RING_RUN) runs over one operand set: `run_nslots` slots of `run_kw`-wide kernel rows with the weight
-  // pieces at wsrc.  Normally once; with a fused projection (PROJ) first over the projection's K = Cin (tap (0, 0) only).
+  // pieces at wbase.  Normally once; with a fused projection (PROJ) first over the projection's K = Cin (tap (0, 0) only).
   // (PROJ is a separate instantiation: the kernels without it compile to the same code as before the projection existed)
   constexpr bool with_proj = PROJ;
   int run_nslots = with_proj ? (a.Cin >> 4) : nslots, run_kw = with_proj ? 1 : a.KW;
-  // weight pieces (ring-order copy: 4 KB per (64-row block, slot), swizzle baked in): this lane's 16 bytes of piece q
-  const uint8_t* wsrc[B_PIECES];
-#pragma unroll
-  for (int q = 0; q < B_PIECES; ++q) {
-    const int prow = (q * 4 + wave) * 16 + (lane >> 2);
-    wsrc[q] = reinterpret_cast<const uint8_t*>(with_proj ? pj.wdma : ab.wdma) + (size_t)((n0 + prow) >> 6) * run_nslots * 4096 +
-              ((prow & 63) << 6) + ((lane & 3) << 4);
-  }
+  // weight pieces (ring-order copy: 4 KB per (64-row block, slot), swizzle baked in).  Piece q covers the rows of 64-row block
+  // n0 / 64 + q, so the block and the slot are uniform: a piece's address is a scalar base plus this lane's 16 bytes within a 4 KB
+  // piece, the same for every piece -- one VGPR where a 64-bit pointer per piece took 2 * B_PIECES
+  const uint8_t* wbase = reinterpret_cast<const uint8_t*>(with_proj ? pj.wdma : ab.wdma) + (size_t)(n0 >> 6) * run_nslots * 4096;
+  const unsigned wlane = ((wave * 16 + (lane >> 2)) << 6) + ((lane & 3) << 4);
   int l_tap = 0, l_ky = 0, l_kx = 0, l_ci0 = 0, l_slot = 0;   // counters of the next slot to latch (strictly in order)
   const uint8_t* zp = zero_page + (lane & 3) * 16;
   int nx_tap = 0, nx_toff = 0, nx_k = 0, nx_ring = 0;
@@ -301,7 +313,7 @@ __global__ __launch_bounds__(256, 2) void conv_dma_f16x3_kernel(ConvArgsB ab, co
       __builtin_amdgcn_global_load_lds((gbl_void_t*)src, (lds_void_t*)(st_ + (q * 4 + wave) * 1024), 16, 0, 0); \
     } else {                                                                                                   \
       const int q = (PI) >= A_PIECES ? (PI) - A_PIECES : 0;                                                    \
-      __builtin_amdgcn_global_load_lds((gbl_void_t*)(wsrc[q] + (size_t)nx_k * 4096),                           \
+      __builtin_amdgcn_global_load_lds((gbl_void_t*)(wbase + ((size_t)q * run_nslots + nx_k) * 4096 + wlane),   \
                                        (lds_void_t*)(st_ + A_BYTES + (q * 4 + wave) * 1024), 16, 0, 0);        \
     }                                                                                                          \
   }
@@ -323,31 +335,31 @@ __global__ __launch_bounds__(256, 2) void conv_dma_f16x3_kernel(ConvArgsB ab, co
     for (int tn = 0; tn < TN; ++tn)
 #pragma unroll
       for (int r = 0; r < 16; ++r) { acc[tm][tn][r] = 0.f; accx[tm][tn][r] = 0.f; }
-  const int li = lane & 31, lh = lane >> 5;
-  int ahi_off[TM], alo_off[TM], bhi_off[TN], blo_off[TN];
-#pragma unroll
-  for (int tm = 0; tm < TM; ++tm) {
-    const int row = wm * WROWS + tm * 32 + li, sw = (row >> 2) & 3;
-    ahi_off[tm] = row * 64 + (((2 * lh) ^ sw) << 4);
-    alo_off[tm] = row * 64 + (((2 * lh + 1) ^ sw) << 4);
-  }
-#pragma unroll
-  for (int tn = 0; tn < TN; ++tn) {
-    const int row = wn * WCOLS + tn * 32 + li, sw = (row >> 2) & 3;
-    bhi_off[tn] = A_BYTES + row * 64 + ((lh ^ sw) << 4);
-    blo_off[tn] = A_BYTES + row * 64 + (((2 + lh) ^ sw) << 4);
-  }
+  int li = lane & 31, lh = lane >> 5;
+  // fragment offsets of tile 0; tile t of either operand lies 32 rows = 2048 bytes further on with the same swizzle
+  // ((row >> 2) & 3 does not change over 32 rows): an immediate offset of the read instead of a register per tile
+  int ahi_off, alo_off, bhi_off, blo_off;
+  auto frag_state = [&](int ln) {
+    const int li_ = ln & 31, lh_ = ln >> 5;
+    const int arow = wm * WROWS + li_, asw = (arow >> 2) & 3;
+    ahi_off = arow * 64 + (((2 * lh_) ^ asw) << 4);
+    alo_off = arow * 64 + (((2 * lh_ + 1) ^ asw) << 4);
+    const int brow = wn * WCOLS + li_, bsw = (brow >> 2) & 3;
+    bhi_off = A_BYTES + brow * 64 + ((lh_ ^ bsw) << 4);
+    blo_off = A_BYTES + brow * 64 + (((2 + lh_) ^ bsw) << 4);
+  };
+  frag_state(lane);
   constexpr int GROUPS = TM * TN;
   f16x8 fa[2][2 * TM], fb[2][2 * TN];   // [register set][hi/lo per tile]
 #define SERL_RING_READ(SET, ST)                                                                \
   {                                                                                            \
     _Pragma("unroll") for (int tm = 0; tm < TM; ++tm) {                                        \
-      fa[SET][2 * tm] = *reinterpret_cast<const f16x8*>((ST) + ahi_off[tm]);                   \
-      fa[SET][2 * tm + 1] = *reinterpret_cast<const f16x8*>((ST) + alo_off[tm]);               \
+      fa[SET][2 * tm] = *reinterpret_cast<const f16x8*>((ST) + ahi_off + tm * 2048);                   \
+      fa[SET][2 * tm + 1] = *reinterpret_cast<const f16x8*>((ST) + alo_off + tm * 2048);               \
     }                                                                                          \
     _Pragma("unroll") for (int tn = 0; tn < TN; ++tn) {                                        \
-      fb[SET][2 * tn] = *reinterpret_cast<const f16x8*>((ST) + bhi_off[tn]);                   \
-      fb[SET][2 * tn + 1] = *reinterpret_cast<const f16x8*>((ST) + blo_off[tn]);               \
+      fb[SET][2 * tn] = *reinterpret_cast<const f16x8*>((ST) + bhi_off + tn * 2048);                   \
+      fb[SET][2 * tn + 1] = *reinterpret_cast<const f16x8*>((ST) + blo_off + tn * 2048);               \
     }                                                                                          \
   }
   // iteration c: slot c is in register set CUR; slot c + 1 must have landed (slots c + 2, c + 3 may be in flight) and every
@@ -356,10 +368,10 @@ __global__ __launch_bounds__(256, 2) void conv_dma_f16x3_kernel(ConvArgsB ab, co
   {                                                                                            \
     if ((I) < 2 * TM) {                                                                        \
       const int tm_ = (I) >> 1;                                                                \
-      fa[SET][I] = *reinterpret_cast<const f16x8*>((ST) + (((I) & 1) ? alo_off[tm_ < TM ? tm_ : 0] : ahi_off[tm_ < TM ? tm_ : 0])); \
+      fa[SET][I] = *reinterpret_cast<const f16x8*>((ST) + (((I) & 1) ? alo_off : ahi_off) + tm_ * 2048); \
     } else {                                                                                   \
       const int j_ = (I) - 2 * TM, tn_ = j_ >> 1;                                              \
-      fb[SET][j_ < 2 * TN ? j_ : 0] = *reinterpret_cast<const f16x8*>((ST) + ((j_ & 1) ? blo_off[tn_ < TN ? tn_ : 0] : bhi_off[tn_ < TN ? tn_ : 0])); \
+      fb[SET][j_ < 2 * TN ? j_ : 0] = *reinterpret_cast<const f16x8*>((ST) + ((j_ & 1) ? blo_off : bhi_off) + tn_ * 2048); \
     }                                                                                          \
   }
   // iteration c: slot c is in register set CUR; slot c + 1 must have landed (slots c + 2, c + 3 may be in flight) and every
@@ -411,7 +423,15 @@ __global__ __launch_bounds__(256, 2) void conv_dma_f16x3_kernel(ConvArgsB ab, co
   if constexpr (PROJ) {
     {   // the projection's tile first: K = Cin at conv0's tap (0, 0) -- launcher: stride 2, pad 0, 3x3
       SERL_RING_RUN();
-      dma_proj_epilogue<TN, PMODE>(ab, pj, acc, accx, m0, n0, wm, wn, li, lh);
+      // The projection's epilogue and conv0's index the tile the same way.  Handed the same li / lh, the compiler keeps what they
+      // have in common (row numbers, image indices, output offsets: ~40 VGPRs and 60 SGPRs) alive across conv0's whole ring run
+      // -- 256 VGPRs and a spill where the kernel without the projection takes 213.  Each epilogue gets lane indices of its own
+      // that the optimiser cannot see through.
+      {
+        int li_p = li, lh_p = lh;
+        asm volatile("" : "+v"(li_p), "+v"(lh_p));
+        dma_proj_epilogue<TN, PMODE>(ab, pj, acc, accx, m0, n0, wm, wn, li_p, lh_p);
+      }
 #pragma unroll
       for (int tm = 0; tm < TM; ++tm)
 #pragma unroll
@@ -423,14 +443,20 @@ __global__ __launch_bounds__(256, 2) void conv_dma_f16x3_kernel(ConvArgsB ab, co
       asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
       asm volatile("s_barrier" ::: "memory");
       run_nslots = nslots; run_kw = a.KW;
-#pragma unroll
-      for (int q = 0; q < B_PIECES; ++q) {
-        const int prow = (q * 4 + wave) * 16 + (lane >> 2);
-        wsrc[q] = reinterpret_cast<const uint8_t*>(ab.wdma) + (size_t)((n0 + prow) >> 6) * nslots * 4096 + ((prow & 63) << 6) + ((lane & 3) << 4);
-      }
+      int ln = lane;
+      asm volatile("" : "+v"(ln));
+      piece_state(ln);
+      frag_state(ln);
+      zp = zero_page + (ln & 3) * 16;
+      wbase = reinterpret_cast<const uint8_t*>(ab.wdma) + (size_t)(n0 >> 6) * nslots * 4096;
     }
   }
   SERL_RING_RUN();
+  if constexpr (PROJ) {   // (behind the ring run: nothing of conv0's epilogue is worked out ahead of it)
+    int le = lane;
+    asm volatile("" : "+v"(le));
+    li = le & 31; lh = le >> 5;
+  }
 #undef SERL_RING_RUN
 #undef SERL_RING_ITER
 #undef SERL_RING_READ
