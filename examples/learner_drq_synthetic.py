@@ -13,6 +13,12 @@ go through serl_amd.utils.checkpoint (flax's file layout).
 Stopping and continuing:  --run_dir DIR --save_every N  saves the run state (the agent's checkpoint, state.rng included, plus a
 snapshot of both replay stores) every N steps; the same command with  --resume  continues from the latest one: the demo store
 is not filled again and the online store already holds what the actor had sent.
+
+Publishing:  --publish sync  (default) is the reference's line, server.publish_network(agent.state.params): one blocking copy per
+leaf, pickle, LZ4 and send on the training thread.  --publish snapshot  is server.publish_network(agent.snapshot): the server takes
+the snapshot -- one kernel launch on the update stream --, the copy to pinned host memory and the encoding happen behind the
+learner's back, a publisher that falls behind drops a network instead of stalling the learner, and parameters that have gone NaN
+are never sent; with --checkpoint_path the checkpoints are then taken from a three-section snapshot too.
 """
 import argparse
 import itertools
@@ -61,6 +67,8 @@ def main():
     ap.add_argument("--resume", action="store_true", help="continue from the latest run state in --run_dir")
     ap.add_argument("--hidden", type=int, default=256,
                     help="width h of the critic's and the policy's MLPs (hidden_dims=[h, h]): a multiple of 64 in [64, 1024]")
+    ap.add_argument("--publish", choices=["sync", "snapshot"], default="sync",
+                    help="sync: publish_network(agent.state.params) on the training thread; snapshot: publish_network(agent.snapshot)")
     ap.add_argument("--activation", choices=["tanh", "relu", "swish"], default="tanh",
                     help="activation of the critic's and the policy's MLPs (the launcher writes tanh)")
     a = ap.parse_args()
@@ -141,14 +149,18 @@ def main():
         agent, update_info = agent.update_high_utd(batch, utd_ratio=1)   # :283-292
         update_steps += 1
         if step > 0 and step % a.steps_per_update == 0:                  # :295-297
-            server.publish_network(agent.state.params)
+            server.publish_network(agent.snapshot if a.publish == "snapshot" else agent.state.params)
         if step % a.log_period == 0:
             info = update_info.resolve()                                 # synchronises; the reference logs to wandb here
             print(f"step {step:5d} updates {update_steps:6d} critic_loss {info['critic']['critic_loss']:.4f} "
                   f"actor_loss {info['actor']['actor_loss']:.4f} temperature {info['actor']['temperature']:.4f} "
                   f"{(update_steps - steps_before) / (time.time() - t0):.1f} grad-steps/s", flush=True)
         if a.checkpoint_path and a.checkpoint_period and step and step % a.checkpoint_period == 0:
-            save_checkpoint(a.checkpoint_path, agent, step=update_steps, keep=20)   # :303-307
+            if a.publish == "snapshot":     # the copy leaves the device behind the next updates; the file is written from pinned memory
+                with agent.snapshot(("params", "target_params", "opt_states"), slots=1) as snap:
+                    save_checkpoint(a.checkpoint_path, snap, step=snap.step, keep=20)
+            else:
+                save_checkpoint(a.checkpoint_path, agent, step=update_steps, keep=20)   # :303-307
         if a.save_every and step and step % a.save_every == 0:
             save_run(a.run_dir, agent, stores, step=update_steps, keep=2)
     stop_actor.set()
@@ -157,7 +169,15 @@ def main():
     server.stop()
     print(f"done: {update_steps} grad-steps; transport: {server.transport}; server stats {server.stats}; "
           f"actor received {len(networks)} networks {networks[-1] if networks else None}; replay size {len(replay_buffer)}", flush=True)
+    encode_s = list(server.encode_seconds)
+    if encode_s:
+        print(f"publisher thread: {len(encode_s)} encodes, median {1e3 * float(np.median(encode_s)):.1f} ms, "
+              f"max {1e3 * max(encode_s):.1f} ms each (pickle + LZ4)", flush=True)
     assert server.stats["transitions"] >= a.training_starts and len(networks) >= 1 and stats_log
+    if a.publish == "snapshot":     # every snapshot handed over was sent or, when a newer one overtook it, dropped -- none was lost
+        handed = sum(1 for step in range(1, a.steps) if step % a.steps_per_update == 0)
+        assert server.stats["published"] - 1 + server.stats.get("publish_dropped", 0) == handed, server.stats
+        assert "publish_refused_nonfinite" not in server.stats, server.stats
 
 
 if __name__ == "__main__":

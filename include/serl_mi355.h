@@ -312,6 +312,54 @@ int serl_agent_set_trunk_mode(serl_agent* a, int mode);
 int serl_agent_set_chain_budget(serl_agent* a, int workgroups);
 int64_t serl_agent_get_step(serl_agent* a);
 
+/* Parameter snapshots (csrc/snapshot.hip).  The reference's learner sends its parameters to the actor every 30 iterations and
+ * writes a checkpoint every few thousand (examples/async_drq_sim/async_drq_sim.py:229,295-307); serl_agent_get serves that with one
+ * blocking copy per leaf.  A serl_snapshot handle takes a CONSISTENT copy of the selected sections in one kernel launch on the
+ * update stream and moves it to pinned host memory on a stream of its own: what was enqueued on `stream` before the take is in
+ * the snapshot, what is enqueued after it is not and may start as soon as the pack kernel is done.
+ *   sections  SERL_SNAP_PARAMS | SERL_SNAP_TARGET | SERL_SNAP_OPT: "params", "target_params", and "opt/<tx>/mu" + "opt/<tx>/nu"
+ *             of the three optimizers.  A moment outside its optimizer's support reads as zeros, as with serl_agent_get.
+ *   slots     1..4 snapshots that can be held at once.  A slot is held from take until release.
+ * take / ready / wait / info / leaf / release may be called from any thread (slot states sit behind a mutex in the handle; take
+ * never waits for a reader).  create and destroy belong to the thread that owns the agent, like every serl_agent_* call (the
+ * agent's count of live handles is not locked), and destroy must not run while another thread is inside a call on the handle.
+ * SERL_ERR_STATE: take with every slot held -- or released while its copy to the host was still running, a slot is never
+ * overwritten under a copy -- or with a stream of another device (nothing is enqueued then); info / leaf before the slot's copy
+ * is complete; any call on a slot that holds nothing.
+ * An agent with a live snapshot handle cannot be destroyed: serl_agent_destroy returns SERL_ERR_STATE and leaves the agent as it
+ * was; destroy the snapshot handles first. */
+typedef struct serl_snapshot serl_snapshot;
+#define SERL_SNAP_PARAMS 1
+#define SERL_SNAP_TARGET 2
+#define SERL_SNAP_OPT 4
+typedef struct serl_snapshot_meta {
+  int64_t step;          /* serl_agent_get_step at the take */
+  int64_t trunk_gen;     /* trunk leaves set on the agent up to the take */
+  int64_t bytes;         /* bytes one take copies to the host (header + every contiguous run, each padded to 16 bytes) */
+  int64_t nonfinite[3];  /* Inf / NaN values found while packing, per section: [params, target_params, opt] (0 where not selected) */
+  int sections, slots;   /* as created */
+} serl_snapshot_meta;
+/* async_drq_sim.py:229,295-307.  Resolves every (section, leaf) once, merges the device ranges into their maximal contiguous runs
+ * and allocates, per slot, a device staging buffer and its pinned host twin; one copy stream and two events per slot. */
+int serl_snapshot_create(serl_agent* a, int sections, int slots, serl_snapshot** out);
+/* async_drq_sim.py:295-297,303-307.  Returns without waiting for the device.  On `stream` (the stream the agent's updates run
+ * on): a memset of the slot's counters, ONE snapshot_pack_kernel launch, an event; on the handle's copy stream: a wait on that
+ * event, one copy of the whole slot to its pinned buffer, a second event.  *slot_out is the slot now held. */
+int serl_snapshot_take(serl_snapshot* s, void* stream, int* slot_out);
+/* async_drq_sim.py:295-297.  1 = the slot's copy is complete, 0 = not yet (never blocks), negative = status. */
+int serl_snapshot_ready(serl_snapshot* s, int slot);
+/* async_drq_sim.py:295-297.  Blocks the calling thread (not the device, and no other thread's take) until the copy is complete. */
+int serl_snapshot_wait(serl_snapshot* s, int slot);
+/* async_drq_sim.py:295-307.  What the slot holds; refused before its copy is complete. */
+int serl_snapshot_info(serl_snapshot* s, int slot, serl_snapshot_meta* out);
+/* async_drq_sim.py:229,295-307.  *host_out points INTO the slot's pinned buffer (read-only for the caller; shared zeros for a
+ * moment outside its optimizer's support) and is valid until serl_snapshot_release; refused before the copy is complete. */
+int serl_snapshot_leaf(serl_snapshot* s, int slot, const char* section, const char* leaf, const float** host_out, int64_t* count);
+/* async_drq_sim.py:295-307.  The slot may be taken again (once its copy, if still running, has ended). */
+int serl_snapshot_release(serl_snapshot* s, int slot);
+/* async_drq_sim.py:295-307.  Waits for what the handle has in flight, frees it; the agent can be destroyed again. */
+int serl_snapshot_destroy(serl_snapshot* s);
+
 /* Explicit randomness (parity mode).  All pointers are DEVICE addresses; NULL members (or a NULL
  * struct) are generated on the device from cfg.seed.  Shapes use the batch of the call:
  *   eps_*  f32[batch][act_dim];  mask_* u8[n_cam][batch][512*sle_features] keep-masks (1 = keep)

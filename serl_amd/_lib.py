@@ -17,7 +17,7 @@ MAX_BUFFERS = 2
 
 
 class SerlError(RuntimeError):
-    pass
+    status = None     # the library's status code (SERL_ERR_*) where the error came from a call of it
 
 
 class SerlBatch(C.Structure):
@@ -112,7 +112,9 @@ def lib():
 def check(status: int):
     if status != 0:
         msg = lib().serl_last_error()
-        raise SerlError(f"libserl_mi355 status {status}: {msg.decode() if msg else '?'}")
+        e = SerlError(f"libserl_mi355 status {status}: {msg.decode() if msg else '?'}")
+        e.status = status
+        raise e
 
 
 def profile_read(max_entries=64):

@@ -59,6 +59,13 @@ class SerlInfo(C.Structure):
         "temperature_loss", "actor_lr", "critic_lr", "temperature_lr")]
 
 
+class SerlSnapshotMeta(C.Structure):   # serl_snapshot_meta
+    _fields_ = [("step", C.c_int64), ("trunk_gen", C.c_int64), ("bytes", C.c_int64), ("nonfinite", C.c_int64 * 3),
+                ("sections", C.c_int), ("slots", C.c_int)]
+
+
+SNAP_BITS = {"params": 1, "target_params": 2, "opt_states": 4}   # SERL_SNAP_*, by the TrainState field each bit fills
+
 # function -> argtypes (int status unless RESTYPES says otherwise)
 SIGNATURES = {
     "serl_agent_create": [P(SerlAgentCfg), P(vp)],
@@ -97,6 +104,15 @@ SIGNATURES = {
     "serl_agent_trunk_plan": [vp, C.c_char_p, i32],
     "serl_agent_debug_set": [vp, C.c_char_p, vp, i64],
     "serl_debug_chain_launches": [],
+    # parameter snapshots (csrc/snapshot.hip, serl_amd/agents/snapshot.py)
+    "serl_snapshot_create": [vp, i32, i32, P(vp)],
+    "serl_snapshot_take": [vp, vp, P(i32)],
+    "serl_snapshot_ready": [vp, i32],
+    "serl_snapshot_wait": [vp, i32],
+    "serl_snapshot_info": [vp, i32, P(SerlSnapshotMeta)],
+    "serl_snapshot_leaf": [vp, i32, C.c_char_p, C.c_char_p, P(P(f32)), P(i64)],
+    "serl_snapshot_release": [vp, i32],
+    "serl_snapshot_destroy": [vp],
     # behaviour cloning (csrc/bc.hip, serl_amd/agents/bc.py)
     "serl_bc_create": [P(SerlBcCfg), P(vp)],
     "serl_bc_destroy": [vp],

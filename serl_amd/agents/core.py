@@ -67,6 +67,13 @@ class AgentCore(Handle):
         self.device = torch.device("cuda", device)
         super().__init__(self.cfg)
         self._keep = None
+        self._snapshots = {}    # (SERL_SNAP_* mask, slots) -> agents/snapshot.py SnapshotHandle
+
+    def __del__(self):
+        # the library refuses to destroy an agent that has live snapshot handles
+        for h in getattr(self, "_snapshots", {}).values():
+            h.close()
+        super().__del__()
 
     def _create(self, cfg):
         return self.L.serl_agent_create_mlp(C.byref(cfg), self._std_param, 0 if self.tanh_squash_distribution else 1, *self._acts,

@@ -69,6 +69,28 @@ class PendingInfo(LazyInfo):
         return out
 
 
+def opt_states_tree(agent, step, export) -> dict:
+    """{tx: InjectHyperparamsState} in flax's state-dict form (flax.serialization.to_state_dict: NamedTuples become
+    dicts of their fields, tuples dicts keyed '0', '1', ...).  Each reference tx is
+    optax.inject_hyperparams(chain([clip_by_global_norm], adam | adamw)) (common/optimizers.py:32-56):
+      {count, hyperparams: {learning_rate}, inner_state: {'0': <clip: {}>?, '<k>': {'0': {count, mu, nu}, '1': {} ...}}}
+    (non-numeric hyper-parameters such as weight_decay=None are not stored by optax).  `step`: the count and the point of the
+    learning-rate schedule; export(section) -> the flax tree of "opt/<tx>/mu" / "opt/<tx>/nu"."""
+    out = {}
+    step = np.int32(step)
+    for tx in TX_NAMES:
+        kw = agent._opts.get(tx, {})
+        adam = {"count": step, "mu": export(f"opt/{tx}/mu"), "nu": export(f"opt/{tx}/nu")}
+        # optax.adam = chain(scale_by_adam, scale_by_learning_rate); adamw adds add_decayed_weights in between
+        inner_adam = {"0": adam, "1": {}} if kw.get("weight_decay") is None else {"0": adam, "1": {}, "2": {}}
+        stages = ([{}] if kw.get("clip_grad_norm") is not None else []) + [inner_adam]
+        hp = {"learning_rate": np.float32(agent.lr_at(int(step), tx))}
+        if kw.get("weight_decay") is not None:
+            hp["weight_decay"] = np.float32(kw["weight_decay"])
+        out[tx] = {"count": step, "hyperparams": hp, "inner_state": {str(i): s for i, s in enumerate(stages)}}
+    return out
+
+
 class TrainStateView:
     """agent.state: JaxRLTrainState-shaped, materialised from HBM on access (common.py:81-114)."""
 
@@ -89,25 +111,7 @@ class TrainStateView:
 
     @property
     def opt_states(self):
-        """{tx: InjectHyperparamsState} in flax's state-dict form (flax.serialization.to_state_dict: NamedTuples become
-        dicts of their fields, tuples dicts keyed '0', '1', ...).  Each reference tx is
-        optax.inject_hyperparams(chain([clip_by_global_norm], adam | adamw)) (common/optimizers.py:32-56):
-          {count, hyperparams: {learning_rate}, inner_state: {'0': <clip: {}>?, '<k>': {'0': {count, mu, nu}, '1': {} ...}}}
-        (non-numeric hyper-parameters such as weight_decay=None are not stored by optax)."""
-        out = {}
-        step = np.int32(self._a.core.step)
-        for tx in TX_NAMES:
-            kw = self._a._opts.get(tx, {})
-            adam = {"count": step, "mu": export_tree(self._a.core, f"opt/{tx}/mu", self._a.image_keys),
-                    "nu": export_tree(self._a.core, f"opt/{tx}/nu", self._a.image_keys)}
-            # optax.adam = chain(scale_by_adam, scale_by_learning_rate); adamw adds add_decayed_weights in between
-            inner_adam = {"0": adam, "1": {}} if kw.get("weight_decay") is None else {"0": adam, "1": {}, "2": {}}
-            stages = ([{}] if kw.get("clip_grad_norm") is not None else []) + [inner_adam]
-            hp = {"learning_rate": np.float32(self._a.lr_at(int(step), tx))}
-            if kw.get("weight_decay") is not None:
-                hp["weight_decay"] = np.float32(kw["weight_decay"])
-            out[tx] = {"count": step, "hyperparams": hp, "inner_state": {str(i): s for i, s in enumerate(stages)}}
-        return out
+        return opt_states_tree(self._a, self._a.core.step, lambda section: export_tree(self._a.core, section, self._a.image_keys))
 
     @property
     def rng(self):
@@ -247,6 +251,19 @@ class DrQAgent:
         if param_init == "reference":
             agent._rng_key = J.create_rng(rng)
         return agent
+
+    def snapshot(self, sections=("params",), slots=3):
+        """A consistent copy of the selected TrainState fields ("params", "target_params", "opt_states") as they are once every
+        update enqueued so far has run, taken in one kernel launch on the stream the updates run on and moved to pinned host
+        memory behind the learner's back: agents/snapshot.py StateSnapshot.  Returns at once; the updates that follow are not in
+        it and do not wait for the copy.  `slots` snapshots (1..4) of one choice of sections can be held at a time -- with every
+        slot held the call raises SerlError (status -3); 3, the default, is what publishing needs: one with the publisher thread,
+        one queued behind it, one being taken.  The handle is created at the first call and reused by later calls with the same
+        arguments.
+            server.publish_network(agent.snapshot)      # async_drq_sim.py:295-297; the server takes it: never raises when behind
+            save_checkpoint(path, agent.snapshot(("params", "target_params", "opt_states")), step=...)   # :303-307"""
+        from .snapshot import take_snapshot
+        return take_snapshot(self, sections, slots)
 
     def lr_at(self, count, tx="critic"):
         """optimizers.py:14-30: warm-up -> constant, or warm-up -> cosine decay."""

@@ -261,8 +261,10 @@ def trunk_owner(image_keys):
 
 
 def export_tree(core, section: str, image_keys, duplicate_encoder_under_critic: bool = False,
-                critic_mlp_name: str = "network", trunk_under_every_camera: bool = False) -> Dict:
-    """Nested dict of np.float32 arrays in flax layout (HWIO convs, (in,out) dense, ensemble axis 0)."""
+                critic_mlp_name: str = "network", trunk_under_every_camera: bool = False, get=None) -> Dict:
+    """Nested dict of np.float32 arrays in flax layout (HWIO convs, (in,out) dense, ensemble axis 0).  get(section, leaf) -> the
+    leaf's flat values; None = core.get, a copy out of HBM (a StateSnapshot passes views into its pinned buffer)."""
+    get = core.get if get is None else get
     cfg = core.cfg
     etype = "small" if cfg.encoder_type == 1 else "resnet-pretrained"
     shapes = theta_shapes(cfg.n_cam, cfg.H, cfg.W, cfg.state_dim, cfg.act_dim, ensemble=cfg.ensemble, hidden=cfg.hidden,
@@ -280,7 +282,7 @@ def export_tree(core, section: str, image_keys, duplicate_encoder_under_critic: 
         for leaf, ps in paths.items():
             paths[leaf] = [q for p in ps
                            for q in ([p, ("modules_critic",) + p[1:]] if p[:2] == ("modules_actor", "encoder") else [p])]
-    return tree_from_leaves(paths, shapes, lambda leaf: core.get(section, leaf))
+    return tree_from_leaves(paths, shapes, lambda leaf: get(section, leaf))
 
 
 def trunk_from_flax(pretrained: Dict) -> Dict[str, np.ndarray]:

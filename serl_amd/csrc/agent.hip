@@ -160,6 +160,7 @@ struct serl_agent {
   int* label_ctr = nullptr;
   int label_n = 0;                             // rows of the last labelling
   bool labelled = false, label_exempt = false; // exempt: SACAgent.update, which VICE does not override
+  int snapshots = 0;                           // live serl_snapshot handles (snapshot.hip): serl_agent_destroy is refused while > 0
 };
 
 namespace {
@@ -954,6 +955,10 @@ int serl_agent_create_mlp(const serl_agent_cfg* cfg, int std_param, int no_tanh,
 
 int serl_agent_destroy(serl_agent* a) {
   if (!a) return SERL_OK;
+  if (a->snapshots > 0) {   // their staging slots hold pointers into the arena freed below
+    set_error("the agent has %d live snapshot handle(s): serl_snapshot_destroy them first", a->snapshots);
+    return SERL_ERR_STATE;
+  }
   (void)hipSetDevice(a->cfg.device);
   (void)hipDeviceSynchronize();
   if (a->arena) (void)hipFree(a->arena);
@@ -1012,6 +1017,21 @@ static int resolve(serl_agent* a, const char* section, const char* leaf, float**
   }
   return SERL_OK;
 }
+
+}  // extern "C"
+// ---- the agent as a snapshot handle sees it (internal.h; snapshot.hip) ----
+namespace serl {
+int agent_resolve(serl_agent* a, const char* section, const char* leaf, float** ptr, long* count) { return resolve(a, section, leaf, ptr, count); }
+int agent_device(const serl_agent* a) { return a->cfg.device; }
+int64_t agent_trunk_gen(const serl_agent* a) { return a->trunk_gen; }
+void agent_snapshot_count(serl_agent* a, int delta) { a->snapshots += delta; }
+int agent_flush_target_trunk(serl_agent* a, hipStream_t stream) {
+  if (a->trunk_ema_pending > 0 && a->trunk_count > 0) RC(frozen_ema(a->trunk, a->trunk_t, a->trunk_count, a->cfg.tau, a->trunk_ema_pending, stream));
+  a->trunk_ema_pending = 0;
+  return SERL_OK;
+}
+}  // namespace serl
+extern "C" {
 
 static constexpr const char* kOutsideSupport = "'%s' of '%s' lies outside the optimizer's support and must be zero";
 

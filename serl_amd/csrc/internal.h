@@ -194,4 +194,16 @@ ClassifierView classifier_view(const serl_classifier* c);
 int classifier_label(serl_classifier* c, const float* feats, long cam_stride, const int* cam_of, const uint8_t* const* cam_frames,
                      int n, float* label, float* logit, float* mean, int* ctr, hipStream_t stream);
 
+// --------------------------------------------------------------------------------------------
+// the agent as a snapshot handle sees it (agent.hip; snapshot.hip)
+// --------------------------------------------------------------------------------------------
+// serl_agent_get's resolver: (section, leaf) -> device range; *ptr == nullptr for a moment outside its optimizer's support
+int agent_resolve(serl_agent* a, const char* section, const char* leaf, float** ptr, long* count);
+int agent_device(const serl_agent* a);
+int64_t agent_trunk_gen(const serl_agent* a);
+void agent_snapshot_count(serl_agent* a, int delta);   // live snapshot handles: serl_agent_destroy is refused while there are any
+// Enqueues the deferred target-EMA steps of the frozen trunk (serl_agent::trunk_ema_pending) on `stream`, without waiting: the
+// target trunk a snapshot packs behind it on the same stream is the one serl_agent_get would read.
+int agent_flush_target_trunk(serl_agent* a, hipStream_t stream);
+
 }  // namespace serl

@@ -2,6 +2,7 @@
 from __future__ import annotations
 
 import hashlib
+import logging
 import pickle
 import queue
 import threading
@@ -184,6 +185,12 @@ class TrainerServer:
         self.data_stores: Dict[str, DataStoreBase] = {}
         self._thread, self._stop = None, threading.Event()
         self.stats = {"datastore_msgs": 0, "transitions": 0, "requests": 0, "published": 0}
+        # snapshots handed to publish_network: one publisher thread (started at the first), a queue one deep, the newest wins
+        self._pub_cv = threading.Condition()
+        self._pub_send = threading.Lock()      # the PUB socket is used by the caller's thread (dicts) and the publisher thread
+        self._pub_next, self._pub_thread = None, None
+        self._stats_lock = threading.Lock()    # counters that more than one thread increments (_count)
+        self.encode_seconds = deque(maxlen=256)   # wall time of each encode on the publisher thread (pickle holds the GIL for its part)
 
     def register_data_store(self, name: str, data_store: DataStoreBase):
         self.data_stores[name] = data_store
@@ -232,7 +239,7 @@ class TrainerServer:
                 try:
                     reply = self.handle(decode(frame))
                 except Exception as e:  # noqa: BLE001
-                    self.stats["errors"] = self.stats.get("errors", 0) + 1
+                    self._count("errors")
                     reply = {"success": False, "message": repr(e)}
                 rep.send(encode(reply))
         rep.close(0)
@@ -254,17 +261,107 @@ class TrainerServer:
         else:
             target()
 
-    def publish_network(self, params: dict):
-        """Broadcast the learner's parameters (a flax-layout tree of numpy arrays) to every actor."""
-        frame = encode(params)
-        if self.transport == "loopback":
-            _Loopback.publish(self.config.broadcast_port, frame)
-        else:
-            self._pub.send(frame)
-        self.stats["published"] += 1
+    def publish_network(self, params):
+        """Broadcast the learner's parameters to every actor.  `params` is one of
+        * a flax-layout tree of numpy arrays: encoded and sent before the call returns;
+        * a StateSnapshot (`agent.snapshot()`; any object whose TYPE has wait / params / finite / release -- the attributes are
+          looked up on the type, because reading `snapshot.params` would wait for the copy on the caller's thread, so an object
+          that carries them as instance attributes only is taken for a tree and pickled whole): the call returns at once and the
+          publisher thread waits for the snapshot's copy, checks that it is finite, encodes `snapshot.params`, sends and releases it;
+        * a callable that TAKES the snapshot (`agent.snapshot`, or a lambda around it): the snapshot still queued, if any, is
+          released first and the callable is called then, so a publisher that has fallen behind never makes the learner fail.  If
+          the take still finds every slot held (an error with `status == -3`, SerlError's SERL_ERR_STATE), this network is the
+          one that is dropped and counted; the call returns normally.
+        The publisher's queue is one deep and the newest wins, as on a PUB socket an actor only ever wants the latest network: a
+        snapshot still waiting when the next arrives, or at stop(), is released unsent (stats["publish_dropped"]).  A snapshot
+        that holds Inf or NaN is never sent (stats["publish_refused_nonfinite"], and a warning naming step and section).  Both
+        counters appear in `stats` when first incremented.  `encode_seconds` holds the wall time of the publisher's encodes."""
+        if all(hasattr(type(params), n) for n in ("wait", "params", "finite", "release")):
+            return self._publish_snapshot(params)
+        if callable(params):
+            self._drop_queued()
+            try:
+                snap = params()
+            except RuntimeError as e:
+                if getattr(e, "status", None) != -3:
+                    raise
+                self._count("publish_dropped")      # every slot is with the publisher or still being copied: skip this network
+                return
+            return self._publish_snapshot(snap)
+        self._broadcast(encode(params))
+
+    def _broadcast(self, frame: bytes):
+        with self._pub_send:
+            if self.transport == "loopback":
+                _Loopback.publish(self.config.broadcast_port, frame)
+            else:
+                self._pub.send(frame)
+            self.stats["published"] += 1
+
+    def _count(self, key):
+        with self._stats_lock:
+            self.stats[key] = self.stats.get(key, 0) + 1
+
+    def _drop_queued(self, replacement=None):
+        """puts `replacement` (or nothing) into the one-deep queue; what was waiting there is released unsent and counted"""
+        with self._pub_cv:
+            dropped, self._pub_next = self._pub_next, replacement
+            if replacement is not None:
+                self._pub_cv.notify()
+        if dropped is not None:
+            dropped.release()
+            self._count("publish_dropped")
+
+    def _publish_snapshot(self, snap):
+        with self._pub_cv:
+            if self._stop.is_set():
+                raise RuntimeError("publish_network on a stopped TrainerServer")
+            if self._pub_thread is None:
+                self._pub_thread = threading.Thread(target=self._publisher, name="TrainerServer-publish", daemon=True)
+                self._pub_thread.start()
+        self._drop_queued(snap)
+
+    def _publisher(self):
+        log = logging.getLogger(__name__)
+        while True:
+            with self._pub_cv:
+                while self._pub_next is None and not self._stop.is_set():
+                    self._pub_cv.wait()
+                if self._stop.is_set():
+                    return           # (stop() releases what is still queued)
+                snap, self._pub_next = self._pub_next, None
+            try:
+                snap.wait()
+                if not snap.finite:
+                    self._count("publish_refused_nonfinite")
+                    bad = {k: v for k, v in dict(getattr(snap, "nonfinite", {})).items() if v}
+                    log.warning("network of step %s not published: non-finite values in %s", getattr(snap, "step", "?"), bad or "it")
+                else:
+                    tree, t0 = snap.params, time.perf_counter()
+                    try:
+                        frame = encode(tree)
+                    finally:
+                        self.encode_seconds.append(time.perf_counter() - t0)
+                    self._broadcast(frame)
+            except Exception as e:  # noqa: BLE001  (a failing snapshot must not end the thread: the next one may be fine)
+                self._count("errors")
+                log.warning("publishing the network of step %s failed: %r", getattr(snap, "step", "?"), e)
+            finally:
+                try:
+                    snap.release()
+                except Exception as e:  # noqa: BLE001
+                    log.warning("releasing the snapshot of step %s failed: %r", getattr(snap, "step", "?"), e)
 
     def stop(self):
         self._stop.set()
+        with self._pub_cv:
+            queued, self._pub_next = self._pub_next, None
+            self._pub_cv.notify_all()
+        if queued is not None:      # never picked up: released unsent, counted like one that a newer snapshot overtook
+            queued.release()
+            self._count("publish_dropped")
+        if self._pub_thread is not None:
+            self._pub_thread.join(timeout=5)
         if self._thread is not None:
             self._thread.join(timeout=5)
         if self.transport == "loopback":

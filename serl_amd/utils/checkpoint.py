@@ -60,6 +60,12 @@ def state_dict(agent) -> dict:
 
 
 def save_checkpoint(ckpt_dir: str, agent, step: int, prefix: str = "checkpoint_", keep: int = 1, overwrite: bool = False) -> str:
+    """`agent`: an agent, or a StateSnapshot of all three sections (agent.snapshot(("params", "target_params", "opt_states")),
+    agents/snapshot.py), which writes the file the agent would have written at the snapshot's step.  A snapshot that holds Inf or
+    NaN values is refused before any file is touched: a diverged run does not overwrite its last good checkpoint."""
+    if getattr(agent, "finite", True) is False:
+        raise ValueError(f"the snapshot of step {getattr(agent, 'step', '?')} holds non-finite values {getattr(agent, 'nonfinite', {})}: "
+                         f"no checkpoint written, {ckpt_dir} is left as it was")
     os.makedirs(ckpt_dir, exist_ok=True)
     path = os.path.join(ckpt_dir, f"{prefix}{step}")
     if os.path.exists(path) and not overwrite:
