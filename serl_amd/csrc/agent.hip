@@ -14,20 +14,18 @@
 #include <string>
 #include <vector>
 
-#include "heads.h"
+#include "dense_layer.h"
 #include "small_encoder.h"
 
 using namespace serl;
 
 namespace {
 
-struct CamOff { long sle, dW, db, lng, lnb, conv; };   // sle: resnet-pretrained, conv: SmallEncoder
 struct Offs {
-  CamOff cam[SERL_MAX_CAMS];
-  long cam_stride;
-  long c_w1, c_b1, c_g1, c_be1, c_w2, c_b2, c_g2, c_be2, c_hw, c_hb;
-  long p_W, p_b, p_g, p_be;
-  long a_w1, a_b1, a_g1, a_be1, a_w2, a_b2, a_g2, a_be2, a_Wm, a_bm, a_Ws, a_bs;   // kPolUniform: a_bs = actor/log_stds, no a_Ws
+  long enc0, cam_stride;   // camera 0's first leaf (SpatialLearnedEmbeddings kernel, or the SmallEncoder's first conv); camera k's sit k * cam_stride further
+  DenseLn cam, prop, c1, c2, a1, a2;   // the Dense -> LayerNorm -> activation layers: camera bottleneck, proprio branch, critic and policy MLPs
+  long c_hw, c_hb;
+  long a_Wm, a_bm, a_Ws, a_bs;   // kPolUniform: a_bs = actor/log_stds, no a_Ws
   long lam;
   long P, Pc, Pa0, Pa1;
 };
@@ -41,9 +39,9 @@ struct EncBuf {     // activations of one EncodingWrapper forward
   float* enc;       // [B][ld] output slice base
   long ld;
 };
-struct MlpBuf {  // 2-layer LN/tanh MLP activations, [rows][hidden] and [rows] (ensemble: rows = E*B)
-  float *h1, *xh1, *rs1, *h2, *xh2, *rs2;
-};
+struct LayerBuf { float *h, *xhat, *rstd; };   // a layer's output [rows][hidden], normalised pre-activation and 1/std [rows]
+struct MlpBuf { LayerBuf l1, l2; };             // 2-layer MLP activations (ensemble: rows = E*B)
+struct GradBuf { float *dy, *dpre, *dg; };      // a layer's backward scratch: DenseLnGrad's three tensors
 struct CritBuf {
   float* x;  // [B][E+A]
   MlpBuf m;
@@ -114,9 +112,8 @@ struct serl_agent {
   float* slabs = nullptr; long slabs_cap = 0;  // GEMM split-K scratch (== slabs_lane[0])
   float* slabs_lane[3] = {nullptr, nullptr, nullptr};  // one per instance of a multi-instance launch
   float *dq = nullptr, *ytgt = nullptr;
-  float *dh2 = nullptr, *da2 = nullptr, *dg2 = nullptr, *dh1 = nullptr, *da1 = nullptr, *dg1 = nullptr;
-  float *dx = nullptr, *dz = nullptr, *dgz = nullptr, *df = nullptr, *sle_part = nullptr;
-  float *dp = nullptr, *dgp = nullptr, *dpre = nullptr, *dprop_y = nullptr;
+  GradBuf s2{}, s1{}, scam{}, sprop{};   // MLP layers 2 and 1 (critic and policy in turn), camera bottleneck (dy lies in dx), proprio branch
+  float *dx = nullptr, *df = nullptr, *sle_part = nullptr, *dpre = nullptr;
   float *eps_buf[3] = {nullptr, nullptr, nullptr};
   uint8_t* mask_buf[3] = {nullptr, nullptr, nullptr};
   float* act_tmp = nullptr;  // [B][A] sample_actions scratch
@@ -183,54 +180,31 @@ void build_layout(serl_agent* a) {
   long off = 0;
   Offs& o = a->o;
   std::vector<Leaf>& L = a->theta_leaves;
-  const long Hd = c.hidden, A = c.act_dim, N = c.ensemble;
-  for (int k = 0; k < c.n_cam; ++k) {
-    const std::string p = "enc/" + std::to_string(k) + "/";
-    if (a->small) {   // per layer [9*cin + 1][cout]: kernel (HWIO) immediately followed by the bias (small_encoder.hip)
-      o.cam[k].conv = off;
-      for (int l = 0; l < kSmallLayers; ++l) {
-        // (layer 0 of a stacked agent takes the T frames as 3T channels: kernel (3,3,3T,32), common/encoding.py:39-44)
-        add_leaf(L, off, p + "conv" + std::to_string(l) + "/kernel", 9L * kSmallFeat[l] * (l == 0 ? c.num_stack : 1) * kSmallFeat[l + 1]);
-        add_leaf(L, off, p + "conv" + std::to_string(l) + "/bias", kSmallFeat[l + 1]);
-      }
-      o.cam[k].sle = o.cam[k].conv;
-    } else {
-      o.cam[k].sle = add_leaf(L, off, p + "sle", (long)a->HW * 512 * c.sle_features);
+  const int Hd = c.hidden, N = c.ensemble;
+  const long A = c.act_dim;
+  const CamHeadOffsets ch = add_cam_head_leaves(L, off, c.n_cam, a->D, c.bottleneck, [&](const std::string& p) {
+    if (!a->small) { add_leaf(L, off, p + "sle", (long)a->HW * 512 * c.sle_features); return; }
+    for (int l = 0; l < kSmallLayers; ++l) {   // per layer [9*cin + 1][cout]: kernel (HWIO) immediately followed by the bias (small_encoder.hip)
+      // (layer 0 of a stacked agent takes the T frames as 3T channels: kernel (3,3,3T,32), common/encoding.py:39-44)
+      add_leaf(L, off, p + "conv" + std::to_string(l) + "/kernel", 9L * kSmallFeat[l] * (l == 0 ? c.num_stack : 1) * kSmallFeat[l + 1]);
+      add_leaf(L, off, p + "conv" + std::to_string(l) + "/bias", kSmallFeat[l + 1]);
     }
-    o.cam[k].dW = add_leaf(L, off, p + "dense/kernel", (long)a->D * c.bottleneck);
-    o.cam[k].db = add_leaf(L, off, p + "dense/bias", c.bottleneck);
-    o.cam[k].lng = add_leaf(L, off, p + "ln/scale", c.bottleneck);
-    o.cam[k].lnb = add_leaf(L, off, p + "ln/bias", c.bottleneck);
-  }
-  o.cam_stride = c.n_cam > 1 ? o.cam[1].sle - o.cam[0].sle : off;
-  o.c_w1 = add_leaf(L, off, "critic/w1", N * a->XA * Hd);
-  o.c_b1 = add_leaf(L, off, "critic/b1", N * Hd);
-  o.c_g1 = add_leaf(L, off, "critic/ln1/scale", N * Hd);
-  o.c_be1 = add_leaf(L, off, "critic/ln1/bias", N * Hd);
-  o.c_w2 = add_leaf(L, off, "critic/w2", N * Hd * Hd);
-  o.c_b2 = add_leaf(L, off, "critic/b2", N * Hd);
-  o.c_g2 = add_leaf(L, off, "critic/ln2/scale", N * Hd);
-  o.c_be2 = add_leaf(L, off, "critic/ln2/bias", N * Hd);
+  });
+  o.enc0 = ch.first; o.cam_stride = ch.stride; o.cam = ch.dense;
+  o.c1 = add_dense_ln_leaves(L, off, "critic/w1", "critic/b1", "critic/ln1", N, a->XA, Hd, a->critic_act);
+  o.c2 = add_dense_ln_leaves(L, off, "critic/w2", "critic/b2", "critic/ln2", N, Hd, Hd, a->critic_act);
   // DrQ: one Dense(1) head shared by the ensemble (drq.py:201-207); state-only SAC: ensemblize vmaps the whole
   // Critic, so every member has its own head (actor_critic_nets.py:49-73,156-164)
   o.c_hw = add_leaf(L, off, "critic/head/kernel", a->state_only ? N * Hd : Hd);
   o.c_hb = add_leaf(L, off, "critic/head/bias", a->state_only ? N : 1);
   o.Pa0 = off;
   if (!a->state_only) {
-    o.p_W = add_leaf(L, off, "enc/proprio/dense/kernel", (long)c.state_dim * c.proprio_dim);
-    o.p_b = add_leaf(L, off, "enc/proprio/dense/bias", c.proprio_dim);
-    o.p_g = add_leaf(L, off, "enc/proprio/ln/scale", c.proprio_dim);
-    o.p_be = add_leaf(L, off, "enc/proprio/ln/bias", c.proprio_dim);
+    o.prop = add_dense_ln_leaves(L, off, "enc/proprio/dense/kernel", "enc/proprio/dense/bias", "enc/proprio/ln", 1, c.state_dim,
+                                 c.proprio_dim, kActTanh);
   }
   o.Pc = off;
-  o.a_w1 = add_leaf(L, off, "actor/w1", (long)a->E * Hd);
-  o.a_b1 = add_leaf(L, off, "actor/b1", Hd);
-  o.a_g1 = add_leaf(L, off, "actor/ln1/scale", Hd);
-  o.a_be1 = add_leaf(L, off, "actor/ln1/bias", Hd);
-  o.a_w2 = add_leaf(L, off, "actor/w2", Hd * Hd);
-  o.a_b2 = add_leaf(L, off, "actor/b2", Hd);
-  o.a_g2 = add_leaf(L, off, "actor/ln2/scale", Hd);
-  o.a_be2 = add_leaf(L, off, "actor/ln2/bias", Hd);
+  o.a1 = add_dense_ln_leaves(L, off, "actor/w1", "actor/b1", "actor/ln1", 1, a->E, Hd, a->policy_act);
+  o.a2 = add_dense_ln_leaves(L, off, "actor/w2", "actor/b2", "actor/ln2", 1, Hd, Hd, a->policy_act);
   o.a_Wm = add_leaf(L, off, "actor/mean/kernel", Hd * A);
   o.a_bm = add_leaf(L, off, "actor/mean/bias", A);
   a->pol_mode = a->std_param | (a->no_tanh ? kPolNoTanh : 0);
@@ -286,8 +260,7 @@ size_t carve(serl_agent* a, void* base) {
   float* encP_out = b.take<float>(B * a->E);
   a->encP.enc = encP_out; a->encP.ld = a->E;
   auto mlp = [&](MlpBuf& m, long rows) {
-    m.h1 = b.take<float>(rows * Hd); m.xh1 = b.take<float>(rows * Hd); m.rs1 = b.take<float>(rows);
-    m.h2 = b.take<float>(rows * Hd); m.xh2 = b.take<float>(rows * Hd); m.rs2 = b.take<float>(rows);
+    for (LayerBuf* l : {&m.l1, &m.l2}) { l->h = b.take<float>(rows * Hd); l->xhat = b.take<float>(rows * Hd); l->rstd = b.take<float>(rows); }
   };
   auto crit = [&](CritBuf& cb) {
     cb.x = b.take<float>(B * a->XA);
@@ -311,15 +284,14 @@ size_t carve(serl_agent* a, void* base) {
   for (int k = 0; k < 3; ++k) a->slabs_lane[k] = b.take<float>(cap);
   a->slabs = a->slabs_lane[0];
   a->dq = b.take<float>(N * B); a->ytgt = b.take<float>(B);
-  a->dh2 = b.take<float>(N * B * Hd); a->da2 = b.take<float>(N * B * Hd); a->dg2 = b.take<float>(N * B * Hd);
-  a->dh1 = b.take<float>(N * B * Hd); a->da1 = b.take<float>(N * B * Hd); a->dg1 = b.take<float>(N * B * Hd);
+  for (GradBuf* s : {&a->s2, &a->s1}) { s->dy = b.take<float>(N * B * Hd); s->dpre = b.take<float>(N * B * Hd); s->dg = b.take<float>(N * B * Hd); }
   a->dx = b.take<float>(B * a->XA);
-  a->dz = b.take<float>((long)c.n_cam * B * c.bottleneck);
-  a->dgz = b.take<float>((long)c.n_cam * B * c.bottleneck);
+  a->scam.dpre = b.take<float>((long)c.n_cam * B * c.bottleneck);
+  a->scam.dg = b.take<float>((long)c.n_cam * B * c.bottleneck);
   a->df = b.take<float>((long)c.n_cam * B * a->D);
   a->sle_part = b.take<float>((long)c.n_cam * kSleSplit * a->HW * 512 * c.sle_features);
-  a->dp = b.take<float>(B * c.proprio_dim); a->dgp = b.take<float>(B * c.proprio_dim);
-  a->dpre = b.take<float>(2 * B * A); a->dprop_y = b.take<float>(B * c.proprio_dim);
+  a->sprop.dpre = b.take<float>(B * c.proprio_dim); a->sprop.dg = b.take<float>(B * c.proprio_dim);
+  a->dpre = b.take<float>(2 * B * A); a->sprop.dy = b.take<float>(B * c.proprio_dim);
   for (int k = 0; k < 3; ++k) {
     a->eps_buf[k] = b.take<float>(B * A);
     a->mask_buf[k] = b.take<uint8_t>((long)c.n_cam * B * a->D);
@@ -367,6 +339,14 @@ struct EncJob {
   uint64_t mask_seed = 0;      // 2 = jax.random.bernoulli(tf_key[camera], keep, (tf_rows, D)) rows tf_row0.. (serl_noise key_mask_*)
   const uint32_t* tf_key = nullptr; long tf_rows = 0, tf_row0 = 0;
 };
+// The tensors of the two encoder layers in one EncodingWrapper pass: every camera reads its own block of f and writes its
+// columns of the code; the proprio branch reads `state` and writes the columns behind the cameras'.
+DenseLnIo cam_io(const serl_agent* a, const EncBuf& e) {
+  return DenseLnIo{e.f, a->D, (long)a->cfg.batch * a->D, e.enc, e.ld, a->cfg.bottleneck, e.xhat, e.rstd};
+}
+DenseLnIo prop_io(const serl_agent* a, const EncBuf& e, const float* state) {
+  return DenseLnIo{state, a->cfg.state_dim, 0, e.enc + (long)a->cfg.n_cam * a->cfg.bottleneck, e.ld, 0, e.pxhat, e.prstd};
+}
 int encode_multi(serl_agent* a, const EncJob* jobs, int n, int off, int cnt, hipStream_t st) {
   const serl_agent_cfg& c = a->cfg;
   const Offs& o = a->o;
@@ -392,17 +372,13 @@ int encode_multi(serl_agent* a, const EncJob* jobs, int n, int off, int cnt, hip
     EncBuf& e = *j.e;
     sv[i] = SleFwdArgs{};
     sv[i].x = a->feats + (((long)j.which * c.n_cam) * c.batch + off) * a->HW * 512;
-    sv[i].K = j.P + o.cam[0].sle;
+    sv[i].K = j.P + o.enc0;
     sv[i].mask = j.mask ? j.mask + (long)off * a->D : nullptr;
     sv[i].f = e.f;
-    cam_dense_ln_args(e.f, (long)c.batch * a->D, a->D, j.P + o.cam[0].dW, j.P + o.cam[0].db, j.P + o.cam[0].lng,
-                      j.P + o.cam[0].lnb, o.cam_stride, c.n_cam, cnt, c.bottleneck, S, a->slabs_lane[i], e.enc, e.ld, e.xhat,
-                      e.rstd, gd[i], lv[i]);
+    gd[i] = layer_fwd(o.cam, j.P, cam_io(a, e), cnt, a->slabs_lane[i], S);
+    lv[i] = layer_ln_fwd(o.cam, j.P, cam_io(a, e), cnt, gd[i]);
     ProprioArgs& pr = pv[i];
-    pr = ProprioArgs{};
-    pr.state = a->cur.state + ((long)j.which * Bfull + off) * c.state_dim;
-    pr.W = j.P + o.p_W; pr.b = j.P + o.p_b; pr.gamma = j.P + o.p_g; pr.beta = j.P + o.p_be;
-    pr.y = e.enc + (long)c.n_cam * c.bottleneck; pr.ld_y = e.ld; pr.xhat = e.pxhat; pr.rstd = e.prstd;
+    pr = layer_row_fwd(o.prop, j.P, prop_io(a, e, a->cur.state + ((long)j.which * Bfull + off) * c.state_dim));
     if (j.act_dst) {
       pr.copy_src = j.act_src; pr.ld_copy_src = c.act_dim; pr.copy_dst = j.act_dst; pr.ld_copy_dst = a->XA;
       pr.copy_cols = c.act_dim;
@@ -427,7 +403,7 @@ int encode_multi(serl_agent* a, const EncJob* jobs, int n, int off, int cnt, hip
         if (jobs[k].P == j.P && jobs[k].which == j.which) dup = k;
       if (dup >= 0) { gd[i].A = jobs[dup].e->f; continue; }
       const uint8_t* fr = a->cur.frames + (((size_t)j.which * c.n_cam) * Bfull + off) * c.num_stack * fbytes;   // an image = T frames
-      RC(small_forward(a->sws, j.P, o.cam[0].conv, o.cam_stride, fr, Bfull, c.n_cam, cnt, j.e->f, (long)c.batch * a->D, st));
+      RC(small_forward(a->sws, j.P, o.enc0, o.cam_stride, fr, Bfull, c.n_cam, cnt, j.e->f, (long)c.batch * a->D, st));
     }
   } else if (a->fuse) {   // channel-blocked SLE (+ hashed Dropout mask) with the proprio branch as extra workgroups of the launch
     RC(sle_proprio_fwd_multi(sv, pv, n, 1.0f - c.dropout, cnt, a->HW, 512, c.n_cam, (long)c.batch * a->HW * 512, o.cam_stride,
@@ -442,42 +418,39 @@ int encode_multi(serl_agent* a, const EncJob* jobs, int n, int off, int cnt, hip
   return proprio_fwd_multi(pv, n, c.state_dim, cnt, st);
 }
 
-// generic Dense -> LN -> activation (act: kAct*, the network's) layer on `rows_per_group` rows for `groups` parameter groups, for n independent
-// instances with identical shapes (instance i: operands of job i, split-K scratch slabs_lane[i])
-struct DenseJob {
-  const float* X; long ldx, x_gstride;
-  const float* W; long w_gstride;
-  const float *bias, *gamma, *beta; long p_gstride;
-  float *y, *xhat, *rstd;
-  const float *dot_w, *dot_b; float* dot_out;  // optional fused row-dot (critic head)
-  long dot_gstride = 0, dot_b_gstride = 0;      // per-group heads (state-only SAC) or 0 = shared
-};
-int dense_ln_multi(serl_agent* a, const DenseJob* jobs, int n, int groups, int rows_per_group, int K, int splitk, int act,
-                   hipStream_t st) {
-  const int Hd = a->cfg.hidden;
+// The tensors of an MLP layer on `rows` rows per group: output and statistics in `b`, one [rows][N] block per group ...
+DenseLnIo mlp_io(const DenseLn& L, const float* x, long ldx, const LayerBuf& b, int rows) {   // ... on one input shared by the groups
+  return DenseLnIo{x, ldx, 0, b.h, L.N, (long)rows * L.N, b.xhat, b.rstd};
+}
+DenseLnIo mlp_io(const DenseLn& L, const LayerBuf& below, const LayerBuf& b, int rows) {   // ... every group on its block of the layer below
+  return DenseLnIo{below.h, L.K, L.groups > 1 ? (long)rows * L.K : 0, b.h, L.N, (long)rows * L.N, b.xhat, b.rstd};
+}
+// ... and of its backward pass: dy arrives in the layer's own scratch (dy_here), or is formed inside the LayerNorm backward
+DenseLnGrad mlp_grad(const DenseLn& L, const GradBuf& s, int rows, bool dy_here = true) {
+  return DenseLnGrad{dy_here ? s.dy : nullptr, L.N, (long)rows * L.N, s.dpre, s.dg};
+}
+
+// Layer L forward on `rows` rows per group for n independent instances of identical shape (instance i: parameters and tensors of
+// job i, split-K scratch slabs_lane[i]): one grouped GEMM launch, K-split `smax` deep at the most, and one LayerNorm launch.
+struct RowDot { const float *w, *b; float* out; long w_gs, b_gs; };   // rider of the LayerNorm launch: out[row] = y . w + b (critic head); *_gs: per-group heads, 0 = shared
+struct LayerJob { const float* P; DenseLnIo t; RowDot dot; };
+int dense_ln_multi(serl_agent* a, const DenseLn& L, const LayerJob* jobs, int n, int rows, int smax, hipStream_t st) {
   SERL_REQUIRE(n >= 1 && n <= 3, "bad dense instance count");
-  splitk = split_for(a->split_budget, rows_per_group, Hd, groups * n, splitk);
-  SERL_REQUIRE((long)groups * splitk * rows_per_group * Hd <= a->slabs_cap,
-               "Dense layer: %d groups x %d K-splits x %d rows x width %d exceeds the slab scratch of %ld floats", groups, splitk,
-               rows_per_group, Hd, a->slabs_cap);
+  const int splitk = split_for(a->split_budget, rows, L.N, L.groups * n, smax);
+  SERL_REQUIRE((long)L.groups * splitk * rows * L.N <= a->slabs_cap,
+               "Dense layer: %d groups x %d K-splits x %d rows x width %d exceeds the slab scratch of %ld floats", L.groups, splitk,
+               rows, L.N, a->slabs_cap);
   GemmDesc gd[3];
   LnFwdArgs lv[3];
   for (int i = 0; i < n; ++i) {
-    const DenseJob& j = jobs[i];
-    gd[i] = gemm_fwd(j.X, j.ldx, j.x_gstride, j.W, j.w_gstride, a->slabs_lane[i], groups, rows_per_group, Hd, K, splitk);
-    LnFwdArgs& l = lv[i];
-    l = LnFwdArgs{};
-    l.slabs = a->slabs_lane[i]; l.S = splitk; l.slab_stride = gd[i].sCz;
-    l.bias = j.bias; l.gamma = j.gamma; l.beta = j.beta; l.pstride = j.p_gstride;
-    l.rows = groups * rows_per_group; l.rows_per_group = rows_per_group;
-    l.y = j.y; l.ld_y = Hd; l.y_goff = (long)rows_per_group * Hd;
-    l.xhat = j.xhat; l.rstd = j.rstd;
-    l.dot_w = j.dot_w; l.dot_b = j.dot_b; l.dot_out = j.dot_out;
-    l.dot_gstride = j.dot_gstride; l.dot_b_gstride = j.dot_b_gstride;
-    l.act = act;
+    const LayerJob& j = jobs[i];
+    gd[i] = layer_fwd(L, j.P, j.t, rows, a->slabs_lane[i], splitk);
+    lv[i] = layer_ln_fwd(L, j.P, j.t, rows, gd[i]);
+    lv[i].dot_w = j.dot.w; lv[i].dot_b = j.dot.b; lv[i].dot_out = j.dot.out;
+    lv[i].dot_gstride = j.dot.w_gs; lv[i].dot_b_gstride = j.dot.b_gs;
   }
   RC(gemm_f32_multi(gd, n, st));
-  return ln_fwd_multi(lv, n, Hd, st);
+  return ln_fwd_multi(lv, n, L.N, st);
 }
 
 // Policy forward + tanh-Gaussian sample (actor_critic_nets.py:179-227) for n independent inputs
@@ -497,27 +470,26 @@ int policy_fwd_multi(serl_agent* a, const PolJob* jobs, int n, int cnt, hipStrea
   const Offs& o = a->o;
   const int Hd = c.hidden, A = c.act_dim;
   SERL_REQUIRE(n >= 1 && n <= 3, "bad policy instance count");
-  DenseJob d1[3], d2[3];
+  LayerJob d1[3], d2[3];
   GemmDesc gd[3];
   PolicyDistArgs pv[3];
   for (int i = 0; i < n; ++i) {
     const PolJob& j = jobs[i];
     const float* P = j.P;
     PolBuf& pb = *j.pb;
-    d1[i] = DenseJob{j.enc, j.ld_enc, 0, P + o.a_w1, 0, P + o.a_b1, P + o.a_g1, P + o.a_be1, 0,
-                     pb.m.h1, pb.m.xh1, pb.m.rs1, nullptr, nullptr, nullptr};
-    d2[i] = DenseJob{pb.m.h1, Hd, 0, P + o.a_w2, 0, P + o.a_b2, P + o.a_g2, P + o.a_be2, 0,
-                     pb.m.h2, pb.m.xh2, pb.m.rs2, nullptr, nullptr, nullptr};
-    // (mean, log_std) as two groups; the mean alone when log_stds is a parameter vector (the stride is then unused)
-    gd[i] = gemm_fwd(pb.m.h2, Hd, 0, P + o.a_Wm, o.a_bs - o.a_bm, a->slabs_lane[i], a->head_groups, cnt, A, Hd, 4);
+    d1[i] = LayerJob{P, mlp_io(o.a1, j.enc, j.ld_enc, pb.m.l1, cnt), {}};
+    d2[i] = LayerJob{P, mlp_io(o.a2, pb.m.l1, pb.m.l2, cnt), {}};
+    // The head is no layer of the six (no LayerNorm): (mean, log_std) as two groups of one GEMM, the mean alone when log_stds is
+    // a parameter vector (the stride is then unused)
+    gd[i] = gemm_fwd(pb.m.l2.h, Hd, 0, P + o.a_Wm, o.a_bs - o.a_bm, a->slabs_lane[i], a->head_groups, cnt, A, Hd, 4);
     pv[i] = PolicyDistArgs{};
     pv[i].mode = a->pol_mode;
     pv[i].slabs = a->slabs_lane[i]; pv[i].S = 4; pv[i].bias_mean = P + o.a_bm; pv[i].bias_ls = P + o.a_bs; pv[i].pre = pb.pre;
     pv[i].eps = j.eps; pv[i].act = j.act_out; pv[i].ld_act = j.ld_act; pv[i].logp = pb.logp; pv[i].std_out = pb.std;
     pv[i].sum_logp = j.sum_logp; pv[i].lam = P + o.lam; pv[i].alpha_out = j.alpha_out;
   }
-  RC(dense_ln_multi(a, d1, n, 1, cnt, a->E, 8, a->policy_act, st));
-  RC(dense_ln_multi(a, d2, n, 1, cnt, Hd, 4, a->policy_act, st));
+  RC(dense_ln_multi(a, o.a1, d1, n, cnt, 8, st));
+  RC(dense_ln_multi(a, o.a2, d2, n, cnt, 4, st));
   if (a->fuse) {   // the tanh-Gaussian head inside the head GEMM: last arriver of every 64-row tile (heads.hip, kEpiPolicy)
     SERL_REQUIRE(A <= 64, "the fused policy-head epilogue holds one 64-wide slab row per sample (act_dim %d)", A);
     SERL_REQUIRE(cdiv(cnt, 64) <= kCtrPerLane && 8 * pad64(cnt) * 64 <= a->slabs_cap, "policy head exceeds the fused epilogue's scratch");
@@ -551,59 +523,17 @@ struct CritJob { const float* P; CritBuf* cb; };
 int critic_fwd_multi(serl_agent* a, const CritJob* jobs, int n, int cnt, hipStream_t st) {
   const serl_agent_cfg& c = a->cfg;
   const Offs& o = a->o;
-  const int Hd = c.hidden, N = c.ensemble;
   SERL_REQUIRE(n >= 1 && n <= 3, "bad critic instance count");
-  DenseJob d1[3], d2[3];
+  LayerJob d1[3], d2[3];
   for (int i = 0; i < n; ++i) {
     const float* P = jobs[i].P;
     CritBuf& cb = *jobs[i].cb;
-    d1[i] = DenseJob{cb.x, a->XA, 0, P + o.c_w1, (long)a->XA * Hd, P + o.c_b1, P + o.c_g1, P + o.c_be1, Hd,
-                     cb.m.h1, cb.m.xh1, cb.m.rs1, nullptr, nullptr, nullptr};
-    d2[i] = DenseJob{cb.m.h1, Hd, (long)cnt * Hd, P + o.c_w2, (long)Hd * Hd, P + o.c_b2, P + o.c_g2, P + o.c_be2, Hd,
-                     cb.m.h2, cb.m.xh2, cb.m.rs2, P + o.c_hw, P + o.c_hb, cb.q};
-    d2[i].dot_gstride = a->state_only ? Hd : 0;
-    d2[i].dot_b_gstride = a->state_only ? 1 : 0;
+    d1[i] = LayerJob{P, mlp_io(o.c1, cb.x, a->XA, cb.m.l1, cnt), {}};
+    d2[i] = LayerJob{P, mlp_io(o.c2, cb.m.l1, cb.m.l2, cnt),
+                     RowDot{P + o.c_hw, P + o.c_hb, cb.q, a->state_only ? c.hidden : 0, a->state_only ? 1 : 0}};
   }
-  RC(dense_ln_multi(a, d1, n, N, cnt, a->XA, 4, a->critic_act, st));
-  return dense_ln_multi(a, d2, n, N, cnt, Hd, 2, a->critic_act, st);
-}
-
-LnBwdArgs ln_bwd_args(const float* dy, long ld_dy, long dy_goff, const float* y, long ld_y, long y_goff, const float* xhat,
-                      const float* rstd, const float* gamma, long p_gstride, int groups, int rows_per_group, int D, float* dpre,
-                      float* dg) {
-  LnBwdArgs l{};
-  l.dy = dy; l.ld_dy = ld_dy; l.dy_goff = dy_goff;
-  l.y = y; l.ld_y = ld_y; l.y_goff = y_goff;
-  l.xhat = xhat; l.rstd = rstd; l.gamma = gamma; l.pstride = p_gstride;
-  l.rows = groups * rows_per_group; l.rows_per_group = rows_per_group; l.D = D;
-  l.dx = dpre; l.dg = dg;
-  return l;
-}
-
-// backward of one Dense->LN->activation layer (act: kAct*; beta: the forward's, read by the swish backward alone).
-// dy: [groups*rows][Hd] gradient wrt the layer output.
-// Produces dpre (a->da*) and, if G != nullptr, parameter gradients into G at the given offsets
-// (W grads are written directly by the GEMM: splitk == 1).
-int dense_ln_bwd(serl_agent* a, const float* dy, long ld_dy, long dy_goff, const float* y, long ld_y,
-                 long y_goff, const float* xhat, const float* rstd, const float* gamma, const float* beta, int act, long p_gstride,
-                 int groups, int rows_per_group, int D, float* dpre, float* dg, float* G, long g_off,
-                 long be_off, long b_off, long pg_gstride, hipStream_t st, const float* dq = nullptr,
-                 const float* dq_w = nullptr, float dq_const = 0.f, long dq_w_gstride = 0, const LossArgs* loss = nullptr) {
-  LnBwdArgs l = ln_bwd_args(dy, ld_dy, dy_goff, y, ld_y, y_goff, xhat, rstd, gamma, p_gstride, groups, rows_per_group, D, dpre, dg);
-  l.dq = dq; l.dq_w = dq_w; l.dq_const = dq_const; l.dq_w_gstride = dq_w_gstride;
-  l.act = act; l.beta = beta;
-  if (loss) {   // the critic loss rides on this launch and every row derives its dQ from the loss arguments (no critic_loss launch)
-    l.dq_inline = 1;
-    RC(ln_bwd_multi(&l, 1, *loss, st));
-  } else {
-    RC(ln_bwd(l, st));
-  }
-  if (G && a->pg_defer && a->pg_ncs < kMaxColsum) {
-    a->pg_cs[a->pg_ncs++] = Colsum3Args{dg, xhat, dpre, groups, rows_per_group, D, G + g_off, G + be_off, G + b_off, pg_gstride, 0};
-  } else if (G) {
-    RC(colsum3(dg, xhat, dpre, groups, rows_per_group, D, G + g_off, G + be_off, G + b_off, pg_gstride, st));
-  }
-  return SERL_OK;
+  RC(dense_ln_multi(a, o.c1, d1, n, cnt, 4, st));
+  return dense_ln_multi(a, o.c2, d2, n, cnt, 2, st);
 }
 
 int flush_param_grads(serl_agent* a, hipStream_t st) {
@@ -613,10 +543,8 @@ int flush_param_grads(serl_agent* a, hipStream_t st) {
   return SERL_OK;
 }
 
-// C[g] = X[g]^T * dY[g]  (weight gradient, written directly)   X: [rows][K-dim as M], dY: [rows][N]
-int wgrad(serl_agent* a, const float* X, long ldx, long x_gstride, const float* dY, long ldy, long dy_gstride, float* out,
-          long ldo, long out_gstride, int groups, int Mx, int Ny, int rows, hipStream_t st) {
-  const GemmDesc g = gemm_wgrad(X, ldx, x_gstride, dY, ldy, dy_gstride, out, ldo, out_gstride, groups, Mx, Ny, rows);
+// A weight-gradient GEMM (written in place: splitk == 1): a job of the phase's deferred launch, or issued now
+int wgrad(serl_agent* a, const GemmDesc& g, hipStream_t st) {
   if (a->pg_defer && a->pg_nwg < kMaxGemmGroups) {
     a->pg_wg[a->pg_nwg++] = g;  // issued by flush_param_grads
     return SERL_OK;
@@ -624,25 +552,43 @@ int wgrad(serl_agent* a, const float* X, long ldx, long x_gstride, const float* 
   return gemm_f32(g, st);
 }
 
-// dX[g] = dY[g] * W[g]^T   (input gradient)   W: [Kin][Nout] row-major
-int igrad(const float* dY, long ldy, long dy_gstride, const float* W, long ldw, long w_gstride, float* out,
-          long ldo, long out_zstride, int groups, int rows, int Kin, int Nout, hipStream_t st) {
-  return gemm_f32(gemm_igrad(dY, ldy, dy_gstride, W, ldw, w_gstride, out, ldo, out_zstride, groups, rows, Kin, Nout), st);
+// Backward of layer L through activation and LayerNorm: dpre and dg from dy, and with G (a gradient vector indexed like P) the
+// gradients of its bias, scale and shift (a column-sum job) and of its kernel.  `head`: the riders of the critic's layer 2.
+struct HeadDq {   // dy[row][col] = dq[row] * w[col] formed in the launch (rank-1); dq from `dq`, else from the `loss` rider, else dq_const
+  const float* dq; const float* w; float dq_const; long w_gs; const LossArgs* loss;
+};
+int dense_ln_bwd(serl_agent* a, const DenseLn& L, const float* P, const DenseLnIo& t, const DenseLnGrad& d, int rows, float* G,
+                 hipStream_t st, const HeadDq* head = nullptr) {
+  LnBwdArgs l = layer_ln_bwd(L, P, t, d, rows);
+  if (head) { l.dq = head->dq; l.dq_w = head->w; l.dq_const = head->dq_const; l.dq_w_gstride = head->w_gs; }
+  if (head && head->loss) {   // the critic loss rides on this launch and every row derives its dQ from the loss arguments (no critic_loss launch)
+    l.dq_inline = 1;
+    RC(ln_bwd_multi(&l, 1, *head->loss, st));
+  } else {
+    RC(ln_bwd(l, st));
+  }
+  if (!G) return SERL_OK;
+  const Colsum3Args cs = layer_colsum(L, t, d, rows, G);
+  if (a->pg_defer && a->pg_ncs < kMaxColsum) a->pg_cs[a->pg_ncs++] = cs;
+  else RC(colsum3_multi(&cs, 1, st));
+  return wgrad(a, layer_wgrad(L, t, d, rows, G), st);
 }
 
 // ---- the places where the two schedules of the update chain differ: a->fuse is read here and in
 // policy_fwd_multi / encode_multi, nowhere in the phases themselves ----------------------------------------------------------
 
-// dX = sum_g dY[g] * W[g]^T.  Fused: the per-group products go to padded scratch slabs and the last workgroup to arrive at an
-// output tile adds them in group order (heads.hip, kEpiReduce).  Else: the products as slabs, then reduce_slabs.
-int igrad_sum(serl_agent* a, const float* dY, long ldy, long dy_gstride, const float* W, long ldw, long w_gstride, float* out,
-              long ldo, int groups, int rows, int Kin, int Nout, hipStream_t st) {
+// dX = sum_g dY[g] * W[g]^T: `g` is the input-gradient GEMM (layer_igrad / gemm_igrad) without a place to land, which this
+// gives it.  Fused: the per-group products go to padded scratch slabs and the last workgroup to arrive at an output tile adds
+// them in group order (heads.hip, kEpiReduce).  Else: the products as slabs, then reduce_slabs.
+int igrad_sum(serl_agent* a, GemmDesc g, float* out, long ldo, hipStream_t st) {
+  const int groups = g.nbatch, rows = g.M, Kin = g.N;
+  g.C = a->slabs;
   if (!a->fuse) {
-    RC(igrad(dY, ldy, dy_gstride, W, ldw, w_gstride, a->slabs, Kin, (long)rows * Kin, groups, rows, Kin, Nout, st));
+    g.ldc = Kin; g.sCz = (long)rows * Kin;
+    RC(gemm_f32(g, st));
     return reduce_slabs(a->slabs, groups, (long)rows * Kin, 1, rows, Kin, nullptr, 0, out, ldo, 0, false, st);
   }
-  const long ldc = pad64(Kin);
-  GemmDesc g = gemm_igrad(dY, ldy, dy_gstride, W, ldw, w_gstride, a->slabs, ldc, pad64(rows) * ldc, groups, rows, Kin, Nout);
+  g.ldc = pad64(Kin); g.sCz = pad64(rows) * g.ldc;
   g.epi = kEpiReduce; g.zred = groups; g.ctr = a->ctr; g.out = out; g.ld_out = ldo; g.out_gstride = 0;
   SERL_REQUIRE((long)cdiv(rows, 64) * cdiv(Kin, 64) <= kCtrPerLane && groups * g.sCz <= a->slabs_cap,
                "input gradient: %d groups x %d rows x %d columns exceeds the fused epilogue's slab scratch of %ld floats, or its tiles the %d "
@@ -659,7 +605,7 @@ int head_kernel_grad(serl_agent* a, CritBuf& cb, int cnt, hipStream_t st) {
   float* out = a->Gc + a->o.c_hw;
   GemmDesc g{};
   g.A = a->dq; g.sAm = a->fuse ? 1 : 0; g.sAk = 1; g.sAb = a->state_only ? cnt : 0;
-  g.B = cb.m.h2; g.sBk = Hd; g.sBn = 1; g.sBb = a->state_only ? (long)cnt * Hd : 0;
+  g.B = cb.m.l2.h; g.sBk = Hd; g.sBn = 1; g.sBb = a->state_only ? (long)cnt * Hd : 0;
   g.C = split == 1 ? out : a->slabs; g.ldc = Hd; g.sCz = Hd;   // (short K: written in place)
   g.M = 1; g.N = Hd; g.K = K; g.nbatch = groups; g.splitk = split;
   if (!a->fuse) {
@@ -704,37 +650,18 @@ int head_bias_grad(serl_agent* a, int cnt, float* out, long out_gstride, hipStre
 int critic_bwd(serl_agent* a, const float* P, CritBuf& cb, int cnt, bool pg, hipStream_t st, const LossArgs* loss, float dq_const) {
   const serl_agent_cfg& c = a->cfg;
   const Offs& o = a->o;
-  const int Hd = c.hidden, N = c.ensemble;
   float* G = pg ? a->Gc : nullptr;
   const LossArgs* rider = nullptr;
   if (loss) RC(critic_loss_or_rider(a, *loss, st, &rider));
   if (pg) RC(head_kernel_grad(a, cb, cnt, st));
-  // gradient through the head dh2 = dq (x) w is formed inside the LN backward kernel (rank-1 mode)
-  RC(dense_ln_bwd(a, nullptr, Hd, (long)cnt * Hd, cb.m.h2, Hd, (long)cnt * Hd, cb.m.xh2, cb.m.rs2, P + o.c_g2, P + o.c_be2, a->critic_act, Hd,
-                  N, cnt, Hd, a->da2, a->dg2, G, o.c_g2, o.c_be2, o.c_b2, Hd, st, loss ? loss->dq : nullptr, P + o.c_hw, dq_const,
-                  a->state_only ? Hd : 0, rider));
-  if (pg)
-    RC(wgrad(a, cb.m.h1, Hd, (long)cnt * Hd, a->da2, Hd, (long)cnt * Hd, a->Gc + o.c_w2, Hd, (long)Hd * Hd, N, Hd, Hd,
-             cnt, st));
-  RC(igrad(a->da2, Hd, (long)cnt * Hd, P + o.c_w2, Hd, (long)Hd * Hd, a->dh1, Hd, (long)cnt * Hd, N, cnt, Hd, Hd, st));
-  RC(dense_ln_bwd(a, a->dh1, Hd, (long)cnt * Hd, cb.m.h1, Hd, (long)cnt * Hd, cb.m.xh1, cb.m.rs1, P + o.c_g1, P + o.c_be1, a->critic_act, Hd,
-                  N, cnt, Hd, a->da1, a->dg1, G, o.c_g1, o.c_be1, o.c_b1, Hd, st));
-  if (pg)
-    RC(wgrad(a, cb.x, a->XA, 0, a->da1, Hd, (long)cnt * Hd, a->Gc + o.c_w1, Hd, (long)a->XA * Hd, N, a->XA, Hd, cnt, st));
+  const DenseLnGrad d2 = mlp_grad(o.c2, a->s2, cnt, false), d1 = mlp_grad(o.c1, a->s1, cnt);
+  // layer 2: the gradient through the head dh2 = dq (x) w is formed inside the LN backward kernel (rank-1 mode)
+  const HeadDq head{loss ? loss->dq : nullptr, P + o.c_hw, dq_const, a->state_only ? c.hidden : 0, rider};
+  RC(dense_ln_bwd(a, o.c2, P, mlp_io(o.c2, cb.m.l1, cb.m.l2, cnt), d2, cnt, G, st, &head));
+  RC(gemm_f32(layer_igrad(o.c2, P, d2, cnt, d1), st));
+  RC(dense_ln_bwd(a, o.c1, P, mlp_io(o.c1, cb.x, a->XA, cb.m.l1, cnt), d1, cnt, G, st));
   // dx = sum_e da1[e] * W1[e]^T
-  return igrad_sum(a, a->da1, Hd, (long)cnt * Hd, P + o.c_w1, Hd, (long)a->XA * Hd, a->dx, a->XA, N, cnt, a->XA, Hd, st);
-}
-
-// proprio-branch backward: dy = gradient wrt the proprio code (ld/offset given), into G (Gc or Ga)
-int proprio_bwd(serl_agent* a, const float* P, const float* dy, long ld_dy, const float* y, long ld_y, EncBuf& e,
-                int which, int off, int cnt, float* G, long base_off, hipStream_t st) {
-  const serl_agent_cfg& c = a->cfg;
-  const Offs& o = a->o;
-  const int Pd = c.proprio_dim;
-  RC(dense_ln_bwd(a, dy, ld_dy, 0, y, ld_y, 0, e.pxhat, e.prstd, P + o.p_g, nullptr, kActTanh, 0, 1, cnt, Pd, a->dp, a->dgp, G,
-                  o.p_g - base_off, o.p_be - base_off, o.p_b - base_off, 0, st));
-  const float* s = a->cur.state + ((long)which * a->cur.batch + off) * c.state_dim;
-  return wgrad(a, s, c.state_dim, 0, a->dp, Pd, 0, G + (o.p_W - base_off), Pd, 0, 1, c.state_dim, Pd, cnt, st);
+  return igrad_sum(a, layer_igrad(o.c1, P, d1, cnt, nullptr, 0, 0), a->dx, a->XA, st);
 }
 
 // The critic path's backward below dx: d_enc = dx[:, :E] -> the proprio branch and the camera heads (LayerNorm, Dense, SLE
@@ -745,47 +672,41 @@ int proprio_bwd(serl_agent* a, const float* P, const float* dy, long ld_dy, cons
 int enc_bwd_critic(serl_agent* a, const float* P, EncBuf& e, int off, int cnt, hipStream_t st, void* event_bucket0) {
   const serl_agent_cfg& c = a->cfg;
   const Offs& o = a->o;
-  const int Bn = c.bottleneck, Pd = c.proprio_dim;
-  const long pc = (long)c.n_cam * Bn;
+  // both layers read their dy where the critic's backward left it: the cameras' column slices of dx, the proprio columns behind
+  const DenseLnIo tc = cam_io(a, e), tp = prop_io(a, e, a->cur.state + (long)off * c.state_dim);
+  const DenseLnGrad dc{a->dx, a->XA, o.cam.N, a->scam.dpre, a->scam.dg};
+  const DenseLnGrad dp{a->dx + (long)c.n_cam * o.cam.N, a->XA, 0, a->sprop.dpre, a->sprop.dg};
   if (a->fuse && !a->state_only) {
-    LnBwdArgs lb[2] = {ln_bwd_args(a->dx, a->XA, Bn, e.enc, e.ld, Bn, e.xhat, e.rstd, P + o.cam[0].lng, o.cam_stride, c.n_cam, cnt, Bn, a->dz, a->dgz),
-                       ln_bwd_args(a->dx + pc, a->XA, 0, e.enc + pc, e.ld, 0, e.pxhat, e.prstd, P + o.p_g, 0, 1, cnt, Pd, a->dp, a->dgp)};
+    LnBwdArgs lb[2] = {layer_ln_bwd(o.cam, P, tc, dc, cnt), layer_ln_bwd(o.prop, P, tp, dp, cnt)};
     RC(ln_bwd_multi(lb, 2, LossArgs{}, st));
     SERL_REQUIRE(a->pg_defer && a->pg_ncs + 2 <= kMaxColsum, "no room for the deferred LayerNorm gradients");
-    a->pg_cs[a->pg_ncs++] = Colsum3Args{a->dgp, e.pxhat, a->dp, 1, cnt, Pd, a->Gc + o.p_g, a->Gc + o.p_be, a->Gc + o.p_b, 0, 0};
-    a->pg_cs[a->pg_ncs++] = Colsum3Args{a->dgz, e.xhat, a->dz, c.n_cam, cnt, Bn, a->Gc + o.cam[0].lng, a->Gc + o.cam[0].lnb,
-                                        a->Gc + o.cam[0].db, o.cam_stride, 0};
-    const float* s = a->cur.state + (long)off * c.state_dim;
-    RC(wgrad(a, s, c.state_dim, 0, a->dp, Pd, 0, a->Gc + o.p_W, Pd, 0, 1, c.state_dim, Pd, cnt, st));
+    a->pg_cs[a->pg_ncs++] = layer_colsum(o.prop, tp, dp, cnt, a->Gc);
+    a->pg_cs[a->pg_ncs++] = layer_colsum(o.cam, tc, dc, cnt, a->Gc);
+    RC(wgrad(a, layer_wgrad(o.prop, tp, dp, cnt, a->Gc), st));
   } else if (!a->state_only) {
-    RC(proprio_bwd(a, P, a->dx + pc, a->XA, e.enc + pc, e.ld, e, 0, off, cnt, a->Gc, 0, st));
+    RC(dense_ln_bwd(a, o.prop, P, tp, dp, cnt, a->Gc, st));
   }
   if (event_bucket0) {   // bucket 0 (ensemble | head | proprio | scalars) is final once the jobs deferred so far have run
     RC(flush_param_grads(a, st));
     SERL_HIP(hipEventRecord((hipEvent_t)event_bucket0, st));
   }
   if (a->state_only) return SERL_OK;
-  if (!a->fuse)
-    RC(dense_ln_bwd(a, a->dx, a->XA, Bn, e.enc, e.ld, Bn, e.xhat, e.rstd, P + o.cam[0].lng, nullptr, kActTanh, o.cam_stride,
-                    c.n_cam, cnt, Bn, a->dz, a->dgz, a->Gc, o.cam[0].lng, o.cam[0].lnb, o.cam[0].db,
-                    o.cam_stride, st));
-  RC(wgrad(a, e.f, a->D, (long)c.batch * a->D, a->dz, Bn, (long)cnt * Bn, a->Gc + o.cam[0].dW, Bn, o.cam_stride,
-           c.n_cam, a->D, Bn, cnt, st));
-  RC(igrad(a->dz, Bn, (long)cnt * Bn, P + o.cam[0].dW, Bn, o.cam_stride, a->df, a->D, (long)cnt * a->D, c.n_cam, cnt,
-           a->D, Bn, st));
+  if (a->fuse) RC(wgrad(a, layer_wgrad(o.cam, tc, dc, cnt, a->Gc), st));
+  else RC(dense_ln_bwd(a, o.cam, P, tc, dc, cnt, a->Gc, st));
+  RC(gemm_f32(layer_igrad(o.cam, P, dc, cnt, a->df, a->D, (long)cnt * a->D), st));
   if (a->small)   // through the average pool and the four convs of the forward pass that ran last (theta at observations)
-    return small_backward(a->sws, P, o.cam[0].conv, o.cam_stride, c.n_cam, cnt, a->df, (long)cnt * a->D, a->Gc, st);
+    return small_backward(a->sws, P, o.enc0, o.cam_stride, c.n_cam, cnt, a->df, (long)cnt * a->D, a->Gc, st);
   // dK of every camera: partial sums over batch splits (grid.z = camera x batch split), summed by the last arriver or a reduction
   const long sle_n = (long)a->HW * 512 * c.sle_features;
   const float* x = a->feats + (long)off * a->HW * 512;
   if (a->fuse) {
     SERL_REQUIRE((long)c.n_cam * a->HW * 2 <= kCtrPerLane, "SLE gradient exceeds the arrival counters");
     return sle_bwd_fused(x, a->df, a->sle_part, cnt, a->HW, 512, kSleSplit, c.n_cam, (long)c.batch * a->HW * 512, (long)cnt * a->D,
-                         (long)kSleSplit * sle_n, a->Gc + o.cam[0].sle, o.cam_stride, a->ctr, st);
+                         (long)kSleSplit * sle_n, a->Gc + o.enc0, o.cam_stride, a->ctr, st);
   }
   RC(sle_bwd(x, a->df, a->sle_part, cnt, a->HW, 512, kSleSplit, c.n_cam, (long)c.batch * a->HW * 512,
              (long)cnt * a->D, (long)kSleSplit * sle_n, st));
-  return reduce_slabs(a->sle_part, kSleSplit, sle_n, c.n_cam, 1, (int)sle_n, nullptr, 0, a->Gc + o.cam[0].sle, sle_n,
+  return reduce_slabs(a->sle_part, kSleSplit, sle_n, c.n_cam, 1, (int)sle_n, nullptr, 0, a->Gc + o.enc0, sle_n,
                       o.cam_stride, false, st);
 }
 
@@ -1287,8 +1208,8 @@ int serl_agent_grad_bucket(serl_agent* a, int bucket, float** dev_ptr, int64_t* 
   SERL_REQUIRE(a && dev_ptr && count, "NULL argument");
   SERL_REQUIRE(bucket == 0 || bucket == 1, "bucket must be 0 or 1");
   const Offs& o = a->o;
-  if (bucket == 0) { *dev_ptr = a->Gc + o.c_w1; *count = (o.Pc - o.c_w1) + kScalars; }
-  else { *dev_ptr = a->Gc; *count = o.c_w1; }
+  if (bucket == 0) { *dev_ptr = a->Gc + o.c1.W; *count = (o.Pc - o.c1.W) + kScalars; }
+  else { *dev_ptr = a->Gc; *count = o.c1.W; }
   return SERL_OK;
 }
 
@@ -1392,24 +1313,25 @@ int serl_agent_actor_grads(serl_agent* a, int global_count, const serl_noise* no
   // group, and hs = A is the distance from the mean's bias to log_stds
   const long hs = o.a_bs - o.a_bm;
   const int hg = a->head_groups;
-  float* Ga = a->Ga;
-  const long b0 = o.Pa0;
-  RC(wgrad(a, a->pol.m.h2, Hd, 0, a->dpre, A, (long)cnt * A, Ga + (o.a_Wm - b0), A, hs, hg, Hd, A, cnt, st));
-  RC(head_bias_grad(a, cnt, Ga + (o.a_bm - b0), hs, st));
+  float* Ga = a->Ga - o.Pa0;   // Ga[o] = gradient of the actor-tx leaf at parameter offset o
+  const float* P = a->theta;
+  const DenseLnIo t2 = mlp_io(o.a2, a->pol.m.l1, a->pol.m.l2, cnt), t1 = mlp_io(o.a1, a->encP.enc, a->encP.ld, a->pol.m.l1, cnt);
+  const DenseLnGrad d2 = mlp_grad(o.a2, a->s2, cnt), d1 = mlp_grad(o.a1, a->s1, cnt);
+  // (the head is no layer of the six -- no LayerNorm, mean and log_std as groups: its three GEMM forms are written out)
+  RC(wgrad(a, gemm_wgrad(t2.y, Hd, 0, a->dpre, A, (long)cnt * A, Ga + o.a_Wm, A, hs, hg, Hd, A, cnt), st));
+  RC(head_bias_grad(a, cnt, Ga + o.a_bm, hs, st));
   // dh2 = dmean W_mean^T + dlog_std W_logstd^T (no second term when the log-std has no Dense)
-  RC(igrad_sum(a, a->dpre, A, (long)cnt * A, a->theta + o.a_Wm, A, hs, a->dh2, Hd, hg, cnt, Hd, A, st));
-  RC(dense_ln_bwd(a, a->dh2, Hd, 0, a->pol.m.h2, Hd, 0, a->pol.m.xh2, a->pol.m.rs2, a->theta + o.a_g2, a->theta + o.a_be2, a->policy_act, 0, 1, cnt, Hd,
-                  a->da2, a->dg2, Ga, o.a_g2 - b0, o.a_be2 - b0, o.a_b2 - b0, 0, st));
-  RC(wgrad(a, a->pol.m.h1, Hd, 0, a->da2, Hd, 0, Ga + (o.a_w2 - b0), Hd, 0, 1, Hd, Hd, cnt, st));
-  RC(igrad(a->da2, Hd, 0, a->theta + o.a_w2, Hd, 0, a->dh1, Hd, 0, 1, cnt, Hd, Hd, st));
-  RC(dense_ln_bwd(a, a->dh1, Hd, 0, a->pol.m.h1, Hd, 0, a->pol.m.xh1, a->pol.m.rs1, a->theta + o.a_g1, a->theta + o.a_be1, a->policy_act, 0, 1, cnt, Hd,
-                  a->da1, a->dg1, Ga, o.a_g1 - b0, o.a_be1 - b0, o.a_b1 - b0, 0, st));
-  RC(wgrad(a, a->encP.enc, a->encP.ld, 0, a->da1, Hd, 0, Ga + (o.a_w1 - b0), Hd, 0, 1, a->E, Hd, cnt, st));
-  // image codes are stop-gradiented (encoding.py:48-49); only the proprio slice of d_enc is needed
+  RC(igrad_sum(a, gemm_igrad(a->dpre, A, (long)cnt * A, P + o.a_Wm, A, hs, nullptr, 0, 0, hg, cnt, Hd, A), d2.dy, d2.ld_dy, st));
+  RC(dense_ln_bwd(a, o.a2, P, t2, d2, cnt, Ga, st));
+  RC(gemm_f32(layer_igrad(o.a2, P, d2, cnt, d1), st));
+  RC(dense_ln_bwd(a, o.a1, P, t1, d1, cnt, Ga, st));
+  // image codes are stop-gradiented (encoding.py:48-49); only the proprio slice of d_enc is needed: the rows of W1 that the
+  // proprio columns multiply, a slice of layer 1's kernel and therefore written out
   if (!a->state_only) {
-    const long pc = (long)c.n_cam * c.bottleneck;
-    RC(igrad(a->da1, Hd, 0, a->theta + o.a_w1 + pc * Hd, Hd, 0, a->dprop_y, c.proprio_dim, 0, 1, cnt, c.proprio_dim, Hd, st));
-    RC(proprio_bwd(a, a->theta, a->dprop_y, c.proprio_dim, a->encP.enc + pc, a->encP.ld, a->encP, 0, 0, cnt, Ga, b0, st));
+    const DenseLnGrad dp{a->sprop.dy, o.prop.N, 0, a->sprop.dpre, a->sprop.dg};
+    RC(gemm_f32(gemm_igrad(d1.dpre, o.a1.N, 0, P + o.a1.W + (long)c.n_cam * o.cam.N * o.a1.N, o.a1.N, 0, dp.dy, dp.ld_dy, 0, 1, cnt,
+                           o.prop.N, o.a1.N), st));
+    RC(dense_ln_bwd(a, o.prop, P, prop_io(a, a->encP, a->cur.state), dp, cnt, Ga, st));
   }
   RC(flush_param_grads(a, st));
   a->last_global = global_count;

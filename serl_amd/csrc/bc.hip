@@ -13,7 +13,7 @@
 #include <string>
 #include <vector>
 
-#include "heads.h"
+#include "dense_layer.h"
 #include "jaxrng.h"
 
 using namespace serl;
@@ -29,7 +29,8 @@ struct serl_bc {
   long n_params = 0, t0 = 0, nt = 0;
   TrunkOffsets to{};
   CamHeadOffsets cam{};
-  long o_pW = 0, o_pb = 0, o_pg = 0, o_pbe = 0, o_w1 = 0, o_b1 = 0, o_w2 = 0, o_b2 = 0, o_Wm = 0, o_bm = 0, o_Ws = 0, o_bs = 0;
+  DenseLn prop{};   // the proprio branch
+  long o_w1 = 0, o_b1 = 0, o_w2 = 0, o_b2 = 0, o_Wm = 0, o_bm = 0, o_Ws = 0, o_bs = 0;
   void* arena = nullptr;
   float* params = nullptr;   // [n_params + 1]: the element behind the trainable slice is adam_ema's (unused) temperature slot
   AdamSlice opt{};           // moments, gradient and update count of the trainable slice
@@ -54,14 +55,11 @@ void layout(serl_bc* c) {
   std::vector<Leaf>& L = c->leaves;
   long off = 0;
   c->to = add_trunk_leaves(L, off);
-  c->cam = add_cam_head_leaves(L, off, g.n_cam, (long)c->HW * 512 * kSleFeatures, c->D, kBottleneck);
+  c->cam = add_cam_head_leaves(L, off, g.n_cam, c->D, kBottleneck, [&](const std::string& p) { add_leaf(L, off, p + "sle", (long)c->HW * 512 * kSleFeatures); });
   off = (off + 3) & ~3L;   // (16-byte aligned trainable slice)
   c->t0 = off;
   const long A = g.act_dim;
-  c->o_pW = add_leaf(L, off, "enc/proprio/dense/kernel", (long)g.state_dim * kProprio);
-  c->o_pb = add_leaf(L, off, "enc/proprio/dense/bias", kProprio);
-  c->o_pg = add_leaf(L, off, "enc/proprio/ln/scale", kProprio);
-  c->o_pbe = add_leaf(L, off, "enc/proprio/ln/bias", kProprio);
+  c->prop = add_dense_ln_leaves(L, off, "enc/proprio/dense/kernel", "enc/proprio/dense/bias", "enc/proprio/ln", 1, g.state_dim, kProprio, kActTanh);
   c->o_w1 = add_leaf(L, off, "actor/w1", (long)c->E * kHidden);
   c->o_b1 = add_leaf(L, off, "actor/b1", kHidden);
   c->o_w2 = add_leaf(L, off, "actor/w2", (long)kHidden * kHidden);
@@ -222,6 +220,11 @@ int dense_tanh_bwd(const float* slabs, int S, long sstride, const float* y, floa
 // n_cam * n images, SpatialLearnedEmbeddings (+ Dropout keep-mask: injected, drawn from per-camera jax.random keys, or none at
 // train=False) with the proprio branch riding on the same launch, bottleneck Dense + LayerNorm + tanh, the two Dense -> tanh
 // layers and the two heads.  Returns the head's K-split count.
+// the proprio branch's tensors: reads `state`, writes the columns of the code behind the cameras'
+DenseLnIo prop_io(const serl_bc* c, const float* state) {
+  return DenseLnIo{state, c->cfg.state_dim, 0, c->enc + c->Eimg, c->E, 0, c->pxhat, c->prstd};
+}
+
 int forward(serl_bc* c, const uint8_t* frames, const float* state, int n, const uint8_t* mask, const uint32_t* mask_keys,
             int* head_split, hipStream_t st) {
   const serl_bc_cfg& g = c->cfg;
@@ -229,22 +232,19 @@ int forward(serl_bc* c, const uint8_t* frames, const float* state, int n, const 
   const int A = g.act_dim;
   RC(trunk_forward(c->tw, c->tws, frames, g.n_cam * n, c->feats, st, &c->tpk));
   SleFwdArgs sv{};
-  sv.x = c->feats; sv.K = P + c->cam.sle; sv.mask = mask; sv.f = c->f;
+  sv.x = c->feats; sv.K = P + c->cam.first; sv.mask = mask; sv.f = c->f;
   if (!mask && mask_keys) sle_tf_masks(sv, mask_keys, g.n_cam, n, 0);
-  ProprioArgs pv{};
-  pv.state = state; pv.W = P + c->o_pW; pv.b = P + c->o_pb; pv.gamma = P + c->o_pg; pv.beta = P + c->o_pbe;
-  pv.y = c->enc + c->Eimg; pv.ld_y = c->E; pv.xhat = c->pxhat; pv.rstd = c->prstd;
+  const ProprioArgs pv = layer_row_fwd(c->prop, P, prop_io(c, state));
   RC(sle_proprio_fwd_multi(&sv, &pv, 1, 1.0f - g.dropout, n, c->HW, 512, g.n_cam, (long)n * c->HW * 512, c->cam.stride,
                            (long)n * c->D, (long)n * c->D, g.state_dim, st));
   // bottleneck Dense (K-split) -> LayerNorm -> tanh per camera, side by side in enc
   const int S0 = split_under(n, kBottleneck, g.n_cam, 32);
-  GemmDesc g0;
-  LnFwdArgs l0;
-  cam_dense_ln_args(c->f, (long)n * c->D, c->D, P + c->cam.dW, P + c->cam.db, P + c->cam.lng, P + c->cam.lnb, c->cam.stride,
-                    g.n_cam, n, kBottleneck, S0, c->slabs, c->enc, c->E, nullptr, nullptr, g0, l0);
+  const DenseLnIo tc{c->f, c->D, (long)n * c->D, c->enc, c->E, kBottleneck, nullptr, nullptr};
+  const GemmDesc g0 = layer_fwd(c->cam.dense, P, tc, n, c->slabs, S0);
+  const LnFwdArgs l0 = layer_ln_fwd(c->cam.dense, P, tc, n, g0);
   RC(gemm_f32_multi(&g0, 1, st));
   RC(ln_fwd_multi(&l0, 1, kBottleneck, st));
-  // MLP: Dense(256) -> tanh, twice (activate_final)
+  // MLP: Dense(256) -> tanh, twice (activate_final) -- no LayerNorm, so not the DenseLn layer: GEMM forms written out
   const int S1 = split_under(n, kHidden, 1, 8);
   const GemmDesc g1 = gemm_fwd(c->enc, c->E, 0, P + c->o_w1, 0, c->slabs, 1, n, kHidden, c->E, S1);
   RC(gemm_f32_multi(&g1, 1, st));
@@ -396,13 +396,9 @@ int serl_bc_update(serl_bc* c, const serl_batch* batch, const uint8_t* dev_masks
   // gradient of the proprio code only (the image codes are behind stop_gradient): dpre1 W1[Eimg:E]^T
   const GemmDesc gp = gemm_igrad(c->dpre1, kHidden, 0, P + c->o_w1 + (long)c->Eimg * kHidden, kHidden, 0, c->dprop, kProprio, 0, 1, n, kProprio, kHidden);
   RC(gemm_f32_multi(&gp, 1, st));
-  LnBwdArgs lb{};
-  lb.dy = c->dprop; lb.ld_dy = kProprio;
-  lb.y = c->enc + c->Eimg; lb.ld_y = c->E;
-  lb.xhat = c->pxhat; lb.rstd = c->prstd; lb.gamma = P + c->o_pg;
-  lb.rows = n; lb.rows_per_group = n; lb.D = kProprio;
-  lb.dx = c->dpp; lb.dg = c->dgp;
-  RC(ln_bwd(lb, st));
+  const DenseLnIo tp = prop_io(c, batch->state);
+  const DenseLnGrad dp{c->dprop, kProprio, 0, c->dpp, c->dgp};
+  RC(ln_bwd(layer_ln_bwd(c->prop, P, tp, dp, n), st));
   // every parameter gradient: one column-sum launch and one grouped weight-gradient GEMM
   const float* dmu = c->dhead;
   const float* dls = c->dhead + (long)n * A;
@@ -411,7 +407,7 @@ int serl_bc_update(serl_bc* c, const serl_batch* batch, const uint8_t* dev_masks
       {c->dpre2, nullptr, nullptr, 1, n, kHidden, nullptr, G + c->o_b2, nullptr, 0, 1},
       {dmu, nullptr, nullptr, 1, n, A, nullptr, G + c->o_bm, nullptr, 0, 1},
       {dls, nullptr, nullptr, 1, n, A, nullptr, G + c->o_bs, nullptr, 0, 1},
-      {c->dgp, c->pxhat, c->dpp, 1, n, kProprio, G + c->o_pg, G + c->o_pbe, G + c->o_pb, 0, 0},
+      layer_colsum(c->prop, tp, dp, n, G),
   };
   RC(colsum3_multi(cs, 5, st));
   auto wg = [&](const float* X, long ldx, const float* dY, long ldy, float* out, int Mx, int Ny) {
@@ -422,7 +418,7 @@ int serl_bc_update(serl_bc* c, const serl_batch* batch, const uint8_t* dev_masks
       wg(c->h1, kHidden, c->dpre2, kHidden, G + c->o_w2, kHidden, kHidden),
       wg(c->h2, kHidden, dmu, A, G + c->o_Wm, kHidden, A),
       wg(c->h2, kHidden, dls, A, G + c->o_Ws, kHidden, A),
-      wg(batch->state, g.state_dim, c->dpp, kProprio, G + c->o_pW, g.state_dim, kProprio),
+      layer_wgrad(c->prop, tp, dp, n, G),
   };
   RC(gemm_f32_multi(wgs, 5, st));
   // optax.adam(lr) over the trainable slice (bc.py:139 via common.py:170-220); one count, no schedule, no clip

@@ -9,7 +9,7 @@
 #include <string>
 #include <vector>
 
-#include "heads.h"
+#include "dense_layer.h"
 #include "jaxrng.h"
 #include "ln_stats.h"
 
@@ -73,7 +73,7 @@ void layout(serl_classifier* c) {
   std::vector<Leaf>& L = c->leaves;
   long off = 0;
   c->to = add_trunk_leaves(L, off);
-  c->cam = add_cam_head_leaves(L, off, g.n_cam, (long)c->HW * 512 * kSleFeatures, c->D, kBottleneck);
+  c->cam = add_cam_head_leaves(L, off, g.n_cam, c->D, kBottleneck, [&](const std::string& p) { add_leaf(L, off, p + "sle", (long)c->HW * 512 * kSleFeatures); });
   c->o_w1 = add_leaf(L, off, "head/dense0/kernel", (long)c->E * kHidden);
   c->o_b1 = add_leaf(L, off, "head/dense0/bias", kHidden);
   c->o_g1 = add_leaf(L, off, "head/ln/scale", kHidden);
@@ -81,7 +81,7 @@ void layout(serl_classifier* c) {
   c->o_w2 = add_leaf(L, off, "head/dense1/kernel", kHidden);
   c->o_b2 = add_leaf(L, off, "head/dense1/bias", 1);
   c->n_params = off;
-  c->t0 = c->cam.sle;
+  c->t0 = c->cam.first;
   c->nt = off - c->t0;
 }
 
@@ -129,22 +129,22 @@ int head_slabs(serl_classifier* c, const float* feats, long cam_stride, const in
   const long nmax = g.max_batch;
   if (affine) {
     const long d = g.n_cam > 1 ? cam_of[1] - cam_of[0] : 0;
-    SleFwdArgs sv{feats + cam_of[0] * cam_stride, P + c->cam.sle, nullptr, c->f};
+    SleFwdArgs sv{feats + cam_of[0] * cam_stride, P + c->cam.first, nullptr, c->f};
     RC(sle_fwd_multi(&sv, 1, 1.0f, n, c->HW, 512, g.n_cam, d * cam_stride, c->cam.stride, 0, nmax * c->D, st));
   } else {
     for (int k = 0; k < g.n_cam; ++k) {
-      SleFwdArgs sv{feats + cam_of[k] * cam_stride, P + c->cam.sle + k * c->cam.stride, nullptr, c->f + k * nmax * c->D};
+      SleFwdArgs sv{feats + cam_of[k] * cam_stride, P + c->cam.first + k * c->cam.stride, nullptr, c->f + k * nmax * c->D};
       RC(sle_fwd_multi(&sv, 1, 1.0f, n, c->HW, 512, 1, 0, 0, 0, 0, st));
     }
   }
   const int S0 = split_under(n, kBottleneck, g.n_cam, 32);
-  GemmDesc g0;
-  LnFwdArgs l0;
-  cam_dense_ln_args(c->f, nmax * c->D, c->D, P + c->cam.dW, P + c->cam.db, P + c->cam.lng, P + c->cam.lnb, c->cam.stride,
-                    g.n_cam, n, kBottleneck, S0, c->slabs, c->enc, c->E, nullptr, nullptr, g0, l0);
+  const DenseLnIo tc{c->f, c->D, nmax * c->D, c->enc, c->E, kBottleneck, nullptr, nullptr};
+  const GemmDesc g0 = layer_fwd(c->cam.dense, P, tc, n, c->slabs, S0);
+  const LnFwdArgs l0 = layer_ln_fwd(c->cam.dense, P, tc, n, g0);
   RC(gemm_f32_multi(&g0, 1, st));
   RC(ln_fwd_multi(&l0, 1, kBottleneck, st));
   const int S1 = split_under(n, kHidden, 1, 8);
+  // (Dense_0 feeds a Dropout in front of its LayerNorm when training, so its slabs go to label_rows / cls_head_kernel: written out)
   const GemmDesc g1 = gemm_fwd(c->enc, c->E, 0, P + c->o_w1, 0, c->slabs, 1, n, kHidden, c->E, S1);
   RC(gemm_f32_multi(&g1, 1, st));
   *S1_out = S1;
@@ -455,6 +455,13 @@ constexpr float kKeep = 0.9f;   // nn.Dropout(0.1): keep probability 1 - 0.1
 // The train=True forward (instance 0) and, with `eval`, the train=False forward (instance 1) of n cropped observations up to the
 // classifier-head kernel.  masks: u8 [n_cam][n][4096] then [n][256] (device) or nullptr; keys: host uint32 [n_cam + 1][2] -- the
 // make_rng("dropout") keys of encoder_def/encoder_<k>/Dropout_0 and of the root Dropout_0.
+// the camera layer's tensors of instance i: the train instance alone keeps the statistics its backward reads
+DenseLnIo train_cam_io(const serl_classifier* c, int n, int i) {
+  const ClsTrain* t = c->tr;
+  const long nD = (long)n * c->D;
+  return DenseLnIo{t->f + i * c->cfg.n_cam * nD, c->D, nD, t->enc + (long)i * n * c->E, c->E, kBottleneck, i ? nullptr : t->xhat, i ? nullptr : t->rstd};
+}
+
 int train_forward(serl_classifier* c, const uint8_t* frames, int n, const float* labels, const uint8_t* masks,
                   const uint32_t* keys, bool eval, hipStream_t st) {
   const serl_classifier_cfg& g = c->cfg;
@@ -465,7 +472,7 @@ int train_forward(serl_classifier* c, const uint8_t* frames, int n, const float*
   RC(trunk_forward(c->tw, t->tws, frames, nc * n, t->feats, st, &c->tpk));
   // SpatialLearnedEmbeddings (+ Dropout keep-mask on instance 0) of both instances in one launch
   SleFwdArgs sv[2] = {SleFwdArgs{}, SleFwdArgs{}};
-  for (int i = 0; i < ni; ++i) { sv[i].x = t->feats; sv[i].K = P + c->cam.sle; sv[i].f = t->f + i * nc * nD; }
+  for (int i = 0; i < ni; ++i) { sv[i].x = t->feats; sv[i].K = P + c->cam.first; sv[i].f = t->f + i * nc * nD; }
   sv[0].mask = masks;
   if (!masks) sle_tf_masks(sv[0], keys, nc, n, 0);
   RC(sle_proprio_fwd_multi(sv, nullptr, ni, kKeep, n, c->HW, 512, nc, (long)n * c->HW * 512, c->cam.stride, nD, nD, 0, st));
@@ -473,10 +480,10 @@ int train_forward(serl_classifier* c, const uint8_t* frames, int n, const float*
   const int S0 = split_under(n, kBottleneck, nc * ni, 32);
   GemmDesc g0[2];
   LnFwdArgs l0[2];
-  for (int i = 0; i < ni; ++i)
-    cam_dense_ln_args(t->f + i * nc * nD, nD, c->D, P + c->cam.dW, P + c->cam.db, P + c->cam.lng, P + c->cam.lnb, c->cam.stride,
-                      nc, n, kBottleneck, S0, t->slabs + (long)i * nc * S0 * n * kBottleneck, t->enc + (long)i * n * c->E, c->E,
-                      i == 0 ? t->xhat : nullptr, i == 0 ? t->rstd : nullptr, g0[i], l0[i]);
+  for (int i = 0; i < ni; ++i) {
+    g0[i] = layer_fwd(c->cam.dense, P, train_cam_io(c, n, i), n, t->slabs + (long)i * nc * S0 * n * kBottleneck, S0);
+    l0[i] = layer_ln_fwd(c->cam.dense, P, train_cam_io(c, n, i), n, g0[i]);
+  }
   RC(gemm_f32_multi(g0, ni, st));
   RC(ln_fwd_multi(l0, ni, kBottleneck, st));
   // classifier head: Dense_0 (K-split) of both instances, then the row kernel
@@ -569,14 +576,11 @@ int serl_classifier_train_step(serl_classifier* c, const uint8_t* dev_frames, in
   const GemmDesc gi = gemm_igrad(t->dz, kHidden, 0, P + c->o_w1, kHidden, 0, t->denc, c->E, 0, 1, n, c->E, kHidden);
   RC(gemm_f32_multi(&gi, 1, st));
   // camera heads: tanh + LayerNorm backward (all cameras), then d f = dzc W^T per camera
-  LnBwdArgs lb{};
-  lb.dy = t->denc; lb.ld_dy = c->E; lb.dy_goff = kBottleneck;
-  lb.y = t->enc; lb.ld_y = c->E; lb.y_goff = kBottleneck;
-  lb.xhat = t->xhat; lb.rstd = t->rstd; lb.gamma = P + c->cam.lng; lb.pstride = c->cam.stride;
-  lb.rows = nc * n; lb.rows_per_group = n; lb.D = kBottleneck;
-  lb.dx = t->dzc; lb.dg = t->dgc;
-  RC(ln_bwd(lb, st));
-  const GemmDesc gf = gemm_igrad(t->dzc, kBottleneck, (long)n * kBottleneck, P + c->cam.dW, kBottleneck, c->cam.stride, t->df, c->D, nD, nc, n, c->D, kBottleneck);
+  const DenseLn& cam = c->cam.dense;
+  const DenseLnIo tc = train_cam_io(c, n, 0);
+  const DenseLnGrad dc{t->denc, c->E, kBottleneck, t->dzc, t->dgc};
+  RC(ln_bwd(layer_ln_bwd(cam, P, tc, dc, n), st));
+  const GemmDesc gf = layer_igrad(cam, P, dc, n, t->df, c->D, nD);
   RC(gemm_f32_multi(&gf, 1, st));
   // through the camera Dropout, then the SpatialLearnedEmbeddings kernels' gradient (batch splits summed by the last arriver)
   ClsDropArgs da{};
@@ -587,19 +591,18 @@ int serl_classifier_train_step(serl_classifier* c, const uint8_t* dev_frames, in
   SERL_HIP(hipGetLastError());
   const long sle_n = (long)c->HW * 512 * kSleFeatures;
   RC(sle_bwd_fused(t->feats, t->df, t->sle_part, n, c->HW, 512, kSleSplit, nc, (long)n * c->HW * 512, nD, kSleSplit * sle_n,
-                   G + c->cam.sle, c->cam.stride, t->ctr, st));
+                   G + c->cam.first, c->cam.stride, t->ctr, st));
   // every other parameter gradient: one column-sum launch and one grouped weight-gradient GEMM
   const Colsum3Args cs[4] = {
       {t->hdg, t->hxhat, t->dz, 1, n, kHidden, G + c->o_g1, G + c->o_be1, G + c->o_b1, 0, 0},
       {t->dw2in, nullptr, nullptr, 1, n, kHidden, nullptr, G + c->o_w2, nullptr, 0, 1},
       {t->dlogit, nullptr, nullptr, 1, n, 1, nullptr, G + c->o_b2, nullptr, 0, 2},
-      {t->dgc, t->xhat, t->dzc, nc, n, kBottleneck, G + c->cam.lng, G + c->cam.lnb, G + c->cam.db, c->cam.stride, 0},
+      layer_colsum(cam, tc, dc, n, G),
   };
   RC(colsum3_multi(cs, 4, st));
   const GemmDesc wg[2] = {
       gemm_wgrad(t->enc, c->E, 0, t->dz, kHidden, 0, G + c->o_w1, kHidden, 0, 1, c->E, kHidden, n),   // dDense_0 = enc^T dz
-      gemm_wgrad(t->f, c->D, nD, t->dzc, kBottleneck, (long)n * kBottleneck, G + c->cam.dW, kBottleneck, c->cam.stride, nc, c->D,
-                 kBottleneck, n),                                                                      // per camera dDense = f^T dzc
+      layer_wgrad(cam, tc, dc, n, G),                                                                  // per camera dDense = f^T dzc
   };
   RC(gemm_f32_multi(wg, 2, st));
   // optax.adam(lr) (reward_classifier.py:62-66) over the trainable slice

@@ -188,26 +188,6 @@ int grad_norm2(const float* g_critic, long nc, const float* g_actor, long na, fl
 struct NoiseJob { void* out; long n; uint64_t seed; int kind; float keep; long rows_local, rows_global, row_offset, row_elems; };
 int gen_noise_multi(const NoiseJob* v, int n, hipStream_t stream);
 
-
-// ---- the per-camera encoder head on the frozen trunk (resnet_v1.py:324-376, encoding.py:26-72): SpatialLearnedEmbeddings ->
-// Dense -> LayerNorm -> tanh.  Offsets of camera 0's leaves; camera k's sit k * stride floats further.
-struct CamHeadOffsets { long sle, dW, db, lng, lnb, stride; };
-// Appends enc/<k>/{sle, dense/kernel, dense/bias, ln/scale, ln/bias} of n_cam cameras at `off`, which moves behind them:
-// sle_count floats of SpatialLearnedEmbeddings kernel, a [D][N] Dense, and LayerNorm of width N.
-inline CamHeadOffsets add_cam_head_leaves(std::vector<Leaf>& v, long& off, int n_cam, long sle_count, long D, long N) {
-  CamHeadOffsets o{};
-  for (int k = 0; k < n_cam; ++k) {
-    const std::string p = "enc/" + std::to_string(k) + "/";
-    const long s = add_leaf(v, off, p + "sle", sle_count);
-    const long dW = add_leaf(v, off, p + "dense/kernel", D * N);
-    const long db = add_leaf(v, off, p + "dense/bias", N);
-    const long lg = add_leaf(v, off, p + "ln/scale", N);
-    const long lb = add_leaf(v, off, p + "ln/bias", N);
-    if (k == 0) o = CamHeadOffsets{s, dW, db, lg, lb, off - s};
-  }
-  return o;
-}
-
 // ---- the three GEMM forms of a Dense layer, for `groups` independent (input, kernel) pairs `*_gs` floats apart ------------------
 // Forward Y = X W as `splitk` K-split slabs: X [rows][K] (row stride ldx), W [K][N] row-major; the slab of (group g, split s) is
 // the [rows][N] block g * splitk + s behind `slabs`.
@@ -241,22 +221,6 @@ inline GemmDesc gemm_wgrad(const float* X, long ldx, long x_gs, const float* dY,
   g.C = out; g.ldc = ldo; g.sCz = out_gs;
   g.M = Mx; g.N = Ny; g.K = rows; g.nbatch = groups; g.splitk = 1;
   return g;
-}
-
-// The GEMM + LayerNorm launch pair of one instance of the Dense -> LayerNorm -> tanh layer over `cams` cameras.  Camera k reads
-// [rows][K] inputs at f + k * f_cstride, its parameters k * cam_stride floats behind W / bias / gamma / beta, and writes columns
-// k * N.. of y (row stride ld_y).  The GEMM leaves S K-split slabs per camera at `slabs` ([cam][split][rows][N]), which the
-// LayerNorm launch sums.  xhat / rstd: the statistics a backward pass reads, or nullptr.
-inline void cam_dense_ln_args(const float* f, long f_cstride, int K, const float* W, const float* bias, const float* gamma,
-                              const float* beta, long cam_stride, int cams, int rows, int N, int S, float* slabs, float* y,
-                              long ld_y, float* xhat, float* rstd, GemmDesc& g, LnFwdArgs& l) {
-  g = gemm_fwd(f, K, f_cstride, W, cam_stride, slabs, cams, rows, N, K, S);
-  l = LnFwdArgs{};
-  l.slabs = slabs; l.S = S; l.slab_stride = g.sCz;
-  l.bias = bias; l.gamma = gamma; l.beta = beta; l.pstride = cam_stride;
-  l.rows = cams * rows; l.rows_per_group = rows;
-  l.y = y; l.ld_y = ld_y; l.y_goff = N;
-  l.xhat = xhat; l.rstd = rstd;
 }
 
 // Dropout keep-masks of the SpatialLearnedEmbeddings launch drawn from host jax.random keys [n_cam][2]: rows row0.. of
