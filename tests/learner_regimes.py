@@ -368,3 +368,23 @@ def cls_edge(row):
         labels = (np.arange(B) % 2 == 0).astype(np.float32)
         _EDGE[name] = (keys, p, structured_frames(keys, EDGE_HW, EDGE_HW, B, 43 + B), labels, masks)
     return _EDGE[name]
+
+
+# ---- the HIP learners of a table row (GPU tests) -----------------------------------------------------------------------------------
+def bc_agent(cfg, B, trunk, theta):
+    from serl_amd import jaxrng as J
+    from serl_amd.agents.bc import BCAgent
+    agent = BCAgent(cfg.image_keys, cfg.H, cfg.W, cfg.S, cfg.A, seed_key=J.prngkey(0), max_batch=B)
+    agent.load_flat(trunk)
+    agent.load_flat(theta)
+    return agent
+
+
+def bc_batch(frames, state, action):
+    t = lambda a: torch.tensor(np.ascontiguousarray(a), device="cuda")  # noqa: E731
+    return {"observations": dict({k: t(v) for k, v in frames.items()}, state=t(state)), "actions": t(action)}
+
+
+def classifier(keys, H, W, params, max_batch, lr=1e-4):
+    from serl_amd.networks.reward_classifier import Classifier
+    return Classifier(keys, H, W, max_batch=max_batch, trainable=True, learning_rate=lr).load_flat(params)

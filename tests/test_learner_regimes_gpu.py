@@ -39,18 +39,7 @@ TOL = 1e-4
 
 
 # ---- behaviour cloning ---------------------------------------------------------------------------------------------------------------------
-def _bc_agent(cfg, B, trunk, theta):
-    from serl_amd import jaxrng as J
-    from serl_amd.agents.bc import BCAgent
-    agent = BCAgent(cfg.image_keys, cfg.H, cfg.W, cfg.S, cfg.A, seed_key=J.prngkey(0), max_batch=B)
-    agent.load_flat(trunk)
-    agent.load_flat(theta)
-    return agent
-
-
-def _bc_batch(frames, state, action):
-    t = lambda a: torch.tensor(np.ascontiguousarray(a), device="cuda")  # noqa: E731
-    return {"observations": dict({k: t(v) for k, v in frames.items()}, state=t(state)), "actions": t(action)}
+_bc_agent, _bc_batch = LR.bc_agent, LR.bc_batch
 
 
 def _obs(inp):
@@ -239,9 +228,7 @@ def test_bc_drawn_masks_equal_injected_masks_beyond_one_trip(gpu):
 
 
 # ---- reward classifier -----------------------------------------------------------------------------------------------------------------
-def _classifier(keys, H, W, params, max_batch, lr=1e-4):
-    from serl_amd.networks.reward_classifier import Classifier
-    return Classifier(keys, H, W, max_batch=max_batch, trainable=True, learning_rate=lr).load_flat(params)
+_classifier = LR.classifier
 
 
 def _name(keys, leaf):
