@@ -71,6 +71,9 @@ def main():
                     help="sync: publish_network(agent.state.params) on the training thread; snapshot: publish_network(agent.snapshot)")
     ap.add_argument("--activation", choices=["tanh", "relu", "swish"], default="tanh",
                     help="activation of the critic's and the policy's MLPs (the launcher writes tanh)")
+    ap.add_argument("--eval-every", dest="eval_every", type=int, default=0,
+                    help="every K steps print the ensemble's mean Q on a demo batch and the mean log-prob of its actions "
+                         "(agent.evaluate_batch: read-only for the agent; the extra sample advances the demo store's sampler)")
     a = ap.parse_args()
     assert a.run_dir or not (a.save_every or a.resume), "--save_every / --resume need --run_dir"
 
@@ -155,6 +158,14 @@ def main():
             print(f"step {step:5d} updates {update_steps:6d} critic_loss {info['critic']['critic_loss']:.4f} "
                   f"actor_loss {info['actor']['actor_loss']:.4f} temperature {info['actor']['temperature']:.4f} "
                   f"{(update_steps - steps_before) / (time.time() - t0):.1f} grad-steps/s", flush=True)
+        if a.eval_every and step % a.eval_every == 0:
+            # "does the critic overestimate on the demonstrations, how likely are their actions?" -- forward_critic /
+            # forward_policy(train=False).log_prob in the reference; a stored action at exactly +-1 has no finite log-prob
+            ev = agent.evaluate_batch(demo_buffer.sample(min(a.batch_size, 64), pack_obs_and_next_obs=True, lazy=True))
+            lp = ev["log_prob"][np.isfinite(ev["log_prob"])]
+            print(f"step {step:5d} demo batch: mean Q {ev['q'].mean():.4f} (target copy {ev['q_target'].mean():.4f}) "
+                  f"mean log-prob of its actions {lp.mean() if lp.size else float('nan'):.4f} over {lp.size}/{ev['log_prob'].size} "
+                  f"rows inside (-1, 1); mean std {ev['std'].mean():.4f}", flush=True)
         if a.checkpoint_path and a.checkpoint_period and step and step % a.checkpoint_period == 0:
             if a.publish == "snapshot":     # the copy leaves the device behind the next updates; the file is written from pinned memory
                 with agent.snapshot(("params", "target_params", "opt_states"), slots=1) as snap:

@@ -468,6 +468,36 @@ int serl_agent_grad_view(serl_agent* a, int which, float** dev_ptr, int64_t* cou
 int serl_agent_sample_actions(serl_agent* a, const uint8_t* dev_frames, const float* dev_state, int n,
                               const float* dev_eps, float* dev_out_actions, void* stream);
 
+/* ---- Read-only evaluation: what the trained networks think, without a step -------------------------------------------------
+ * The three entries below read the parameters and leave every piece of training state as it was: no byte of the online or
+ * target parameters, the Adam moments, the step counter, the agent's noise counter, the reward-label state, or the three
+ * pipeline slots (their trunk features and batch bindings) is written.  They use the scratch feature slot of
+ * serl_agent_sample_actions, the activations, the gradient scratch and an info accumulator of their own; the next update
+ * starts with serl_agent_begin_update as always.  They share the trunk workspace with serl_agent_encode_slot: order them
+ * behind a trunk pass in flight on another stream, as for serl_agent_sample_actions.  No Dropout (train=False) in the first two.
+ * Refused with SERL_ERR_INVALID, the message naming the argument and the value: n outside [1, cfg.batch]; dev_logp_out without
+ * dev_actions; NULL dev_frames on an agent with cameras (a state-only agent, n_cam == 0, takes NULL). */
+/* forward_critic(obs, actions, train=False) (sac.py:33-55); target != 0: with target_params (sac.py:57-69).
+ * frames u8[n_cam][n][T][H][W][3], state f32[n][T*S], actions f32[n][A], all device, 1 <= n <= cfg.batch;
+ * q_out f32[ensemble][n] device. */
+int serl_agent_eval_q(serl_agent* a, const uint8_t* dev_frames, const float* dev_state, const float* dev_actions,
+                      int n, int target, float* dev_q_out, void* stream);
+/* forward_policy(obs, train=False) (sac.py:71-91): loc, scale_diag, mode, and log_prob(dev_actions) when given.
+ * Any output pointer may be NULL; dev_logp_out requires dev_actions.  mean, std, mode f32[n][A], logp f32[n], device.
+ * Under the tanh squash log_prob follows distrax's Transformed.log_prob with the Tanh bijector: u = atanh(a),
+ * sum_j [log N(u_j; loc_j, scale_j) - 2 (log 2 - u_j - softplus(-2 u_j))]; without it, the diagonal Gaussian's log-density.
+ * An action component with |a| >= 1 has no finite atanh: that row's log_prob is not finite, here as in the reference, and is
+ * NOT clamped -- stored gripper commands of exactly +-1 are common; clip them to the open interval before asking. */
+int serl_agent_eval_policy(serl_agent* a, const uint8_t* dev_frames, const float* dev_state, const float* dev_actions,
+                           int n, float* dev_mean_out, float* dev_std_out, float* dev_mode_out, float* dev_logp_out,
+                           void* stream);
+/* loss_fns(batch) evaluated, not applied (sac.py:134-241): the critic, actor and temperature phases of
+ * serl_agent_update on `batch` with `noise`, WITHOUT serl_agent_apply.  host_out gets the seven loss scalars and the
+ * three learning rates an update at the current step would report (synchronises `stream`).  The scalars are bit for bit those
+ * of the serl_agent_update(batch, all three networks, noise) that follows; like that call it keeps the stored rewards when a
+ * reward classifier is attached. */
+int serl_agent_eval_losses(serl_agent* a, const serl_batch* batch, const serl_noise* noise, serl_info* host_out, void* stream);
+
 /* Debug / test taps (device->host copies of internal activations). */
 int serl_agent_trunk_forward(serl_agent* a, const uint8_t* dev_frames, int n, float* dev_feats_out, void* stream);
 int serl_agent_debug_get(serl_agent* a, const char* what, float* host_out, int64_t count);

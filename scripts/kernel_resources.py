@@ -54,6 +54,9 @@ CHAIN = [
     ("critic_loss_kernel", 80),
     ("colsum3_kernel", 80),
     ("adam_ema_kernel", 80),
+    # read-only evaluation (serl_agent_eval_policy): launched on the update stream, possibly beside a prefetching trunk pass
+    ("policy_stats_kernel<0>", 80),
+    ("policy_stats_kernel<1>", 80),
 ]
 
 

@@ -99,6 +99,10 @@ SIGNATURES = {
     "serl_agent_set_shard": [vp, i64, i64],
     "serl_agent_grad_view": [vp, i32, P(vp), P(i64)],
     "serl_agent_sample_actions": [vp, vp, vp, i32, vp, vp, vp],
+    # read-only evaluation: forward_critic / forward_target_critic, forward_policy, loss_fns without the step
+    "serl_agent_eval_q": [vp, vp, vp, vp, i32, i32, vp, vp],
+    "serl_agent_eval_policy": [vp, vp, vp, vp, i32, vp, vp, vp, vp, vp],
+    "serl_agent_eval_losses": [vp, P(SerlBatch), P(SerlNoise), P(SerlInfo), vp],
     "serl_agent_trunk_forward": [vp, vp, i32, vp, vp],
     "serl_agent_debug_get": [vp, C.c_char_p, vp, i64],
     "serl_agent_trunk_plan": [vp, C.c_char_p, i32],

@@ -275,6 +275,41 @@ class AgentCore(Handle):
             None if eps is None else eps.contiguous().data_ptr(), out.data_ptr(), self._stream()))
         return out
 
+    # ---- read-only evaluation (serl_mi355.h: no byte of the training state is written) ---------
+    @staticmethod
+    def _ptr(t):
+        return None if t is None else t.contiguous().data_ptr()
+
+    def eval_q(self, frames_u8, state, actions, target=False) -> torch.Tensor:
+        """forward_critic(obs, actions, train=False), or with target_params -> f32[ensemble, n] (device).  frames_u8
+        u8[n_cam, n, (T,) H, W, 3] or None (state-only), state f32[n, T*S], actions f32[n, A]: device tensors, n <= cfg.batch."""
+        n = state.shape[0]
+        out = torch.empty((self.cfg.ensemble, n), dtype=torch.float32, device=self.device)
+        keep = [None if frames_u8 is None else frames_u8.contiguous(), state.contiguous(), actions.contiguous()]
+        _lib.check(self.L.serl_agent_eval_q(self._h, self._ptr(keep[0]), keep[1].data_ptr(), keep[2].data_ptr(), n,
+                                            1 if target else 0, out.data_ptr(), self._stream()))
+        return out
+
+    def eval_policy(self, frames_u8, state, actions=None) -> Dict[str, torch.Tensor]:
+        """forward_policy(obs, train=False) -> {"mean": loc, "std": scale_diag, "mode"} f32[n, A] and, with actions,
+        "log_prob" f32[n] (device).  A row whose action has a component |a| >= 1 under the tanh squash is not finite."""
+        n, A = state.shape[0], self.cfg.act_dim
+        out = {k: torch.empty((n, A), dtype=torch.float32, device=self.device) for k in ("mean", "std", "mode")}
+        if actions is not None:
+            out["log_prob"] = torch.empty((n,), dtype=torch.float32, device=self.device)
+        keep = [None if frames_u8 is None else frames_u8.contiguous(), state.contiguous(),
+                None if actions is None else actions.contiguous()]
+        _lib.check(self.L.serl_agent_eval_policy(self._h, self._ptr(keep[0]), keep[1].data_ptr(), self._ptr(keep[2]), n,
+                                                 out["mean"].data_ptr(), out["std"].data_ptr(), out["mode"].data_ptr(),
+                                                 self._ptr(out.get("log_prob")), self._stream()))
+        return out
+
+    def eval_losses(self, batch, noise=None) -> dict:
+        """loss_fns(batch) evaluated, not applied: the scalars and learning rates update(batch, noise=noise) would report."""
+        info = SerlInfo()
+        _lib.check(self.L.serl_agent_eval_losses(self._h, C.byref(batch.cstruct), self._noise(noise), C.byref(info), self._stream()))
+        return {n: getattr(info, n) for n, _ in SerlInfo._fields_}
+
     def debug(self, what: str, count: int) -> np.ndarray:
         out = np.empty(count, np.float32)
         _lib.check(self.L.serl_agent_debug_get(self._h, what.encode(), out.ctypes.data, count))

@@ -600,6 +600,103 @@ class DrQAgent:
         a = self.core.sample_actions(f, s, eps).cpu().numpy()
         return a if batched else a[0]
 
+    # ------------------------------------------------------------------ read-only evaluation
+    # What the trained networks think, without a step: the reference's forward_critic / forward_target_critic (sac.py:33-69),
+    # forward_policy(obs, train=False) with .distribution.loc / .scale_diag / .mode() / .log_prob(a) (sac.py:71-91) and
+    # loss_fns(batch) (sac.py:134-241).  None of these calls changes params, target_params, opt_states, step or state.rng, and an
+    # update that follows computes what it would have computed without them.
+    def _eval_obs(self, observations):
+        """host observations in the forms sample_actions accepts -> (frames u8[n_cam, n, (T,) H, W, 3] device, state f32[n, T*S]
+        device, n, batched)"""
+        c = self.core.cfg
+        st = np.asarray(observations["state"], np.float32)
+        # (n, T, S) is a batch, (T, S) one observation; a single-frame agent may drop the T axis: (n, S) with n > 1 is then a batch
+        batched = st.ndim == 3 or (self.num_stack == 1 and st.ndim == 2 and st.shape[0] > 1)
+        n = st.shape[0] if batched else 1
+        fshape = (n,) + ((self.num_stack,) if self.num_stack > 1 else ()) + (c.H, c.W, 3)
+        frames = np.stack([np.asarray(observations[k], np.uint8).reshape(fshape) for k in self.image_keys])
+        return torch.from_numpy(frames).to(self.core.device), torch.from_numpy(st.reshape(n, -1)).to(self.core.device), n, batched
+
+    def _eval_actions(self, actions, n):
+        a = np.asarray(actions, np.float32).reshape(n, self.core.cfg.act_dim)
+        return torch.from_numpy(a).to(self.core.device)
+
+    def _chunks(self, n):
+        """n > cfg.batch is served in chunks of cfg.batch rows"""
+        B = int(self.core.cfg.batch)
+        return [(lo, min(lo + B, n)) for lo in range(0, n, B)]
+
+    def _q_dev(self, f, s, a, target):
+        return torch.cat([self.core.eval_q(None if f is None else f[:, lo:hi], s[lo:hi], a[lo:hi], target)
+                          for lo, hi in self._chunks(s.shape[0])], dim=1)
+
+    def _policy_dev(self, f, s, a):
+        parts = [self.core.eval_policy(None if f is None else f[:, lo:hi], s[lo:hi], None if a is None else a[lo:hi])
+                 for lo, hi in self._chunks(s.shape[0])]
+        return {k: torch.cat([p[k] for p in parts], dim=0) for k in parts[0]}
+
+    def q_values(self, observations, actions, *, target: bool = False) -> np.ndarray:
+        """forward_critic(observations, actions, train=False) -- with target=True forward_target_critic -> f32[ensemble, n]
+        (n = 1 for a single observation)."""
+        self._sync_side_stream()
+        f, s, n, _ = self._eval_obs(observations)
+        return self._q_dev(f, s, self._eval_actions(actions, n), target).cpu().numpy()
+
+    def policy_stats(self, observations, actions=None) -> dict:
+        """forward_policy(observations, train=False) -> {"mean": .distribution.loc, "std": .scale_diag, "mode": .mode()} [n, A]
+        (without the leading axis for a single observation) and, with `actions`, "log_prob": .log_prob(actions) [n].
+        Under the tanh squash an action with a component of exactly +-1 (stored gripper commands often are) has no finite
+        atanh and its log_prob is not finite, as in the reference: nothing is clamped here."""
+        self._sync_side_stream()
+        f, s, n, batched = self._eval_obs(observations)
+        out = self._policy_dev(f, s, None if actions is None else self._eval_actions(actions, n))
+        out = {k: v.cpu().numpy() for k, v in out.items()}
+        return out if batched else {k: v[0] for k, v in out.items()}
+
+    def evaluate_batch(self, batch, *, side: str = "observations") -> dict:
+        """The four questions on a replay batch (what `update` takes: a host dict, a DeviceBatch or a LazyBatch of the store --
+        gathered in HBM, never through the host) -> {"q", "q_target": [ensemble, B], "mean", "std", "mode": [B, A], "log_prob":
+        [B]} at the batch's observations, or with side="next_observations" at its next observations, with the batch's actions.
+        Frames are taken as already augmented (the identity crop of `update`)."""
+        if side not in ("observations", "next_observations"):
+            raise ValueError(f"side must be 'observations' or 'next_observations' (got {side!r})")
+        if isinstance(batch, DeviceBatch):
+            db = batch
+        else:
+            n = batch.batch_size if isinstance(batch, LazyBatch) else int(batch["rewards"].shape[0])
+            db = self.prepare(batch, crops=(np.full((n * self.num_stack, 2), 4, np.int32),) * 2)
+        self._sync_side_stream()
+        w = 0 if side == "observations" else 1
+        f = db.frames[w] if self.core.cfg.n_cam > 0 else None
+        s, a = db.state[w], db.action
+        out = {"q": self._q_dev(f, s, a, False), "q_target": self._q_dev(f, s, a, True), **self._policy_dev(f, s, a)}
+        return {k: v.cpu().numpy() for k, v in out.items()}
+
+    def evaluate_losses(self, batch, *, noise=None, rng=None) -> dict:
+        """loss_fns(batch) evaluated and not applied: the nested info dict `update(batch)` returns -- critic / actor /
+        temperature losses and the three learning rates -- at the current parameters, bit for bit what an `update` issued right
+        after it with the same noise reports.  noise: explicit draws as in the update calls; rng: a jax.random key to derive
+        the call's keys from; with neither they are derived from state.rng, which does not advance."""
+        if isinstance(batch, DeviceBatch):
+            db = batch
+        else:
+            n = batch.batch_size if isinstance(batch, LazyBatch) else int(batch["rewards"].shape[0])
+            db = self.prepare(batch, crops=(np.full((n * self.num_stack, 2), 4, np.int32),) * 2)
+        self._sync_side_stream()
+        if noise is None and self.rng_impl == "threefry":
+            key = self._rng_key if rng is None else np.asarray(rng, np.uint32)
+            keys = J.UpdateKeys(key, False, 1, True, True)       # the split of update() with all three networks
+            drawn = dict(self.last_draws)     # (last_draws records what the last UPDATE drew: put back below)
+            noise = self._call_noise.build(keys, db.batch, self.noise_form, want_critic=True, want_actor=True)
+            self.last_draws.clear()
+            self.last_draws.update(drawn)
+        r = self.core.eval_losses(db, noise)
+        out = {"critic": {k: r[k] for k in ("critic_loss", "predicted_qs", "target_qs")},
+               "actor": {k: r[k] for k in ("actor_loss", "temperature", "entropy")},
+               "temperature": {"temperature_loss": r["temperature_loss"]}}
+        out.update({f"{n}_lr": r[f"{n}_lr"] for n in TX_NAMES})
+        return out
+
     def _action_noise(self, seed, n):
         """dist.sample(seed=seed) of sac.py:316-320: distrax draws jax.random.normal(seed, (1,) + batch + (A,))."""
         assert seed is not None, "Must specify rng when sampling"

@@ -103,6 +103,13 @@ class SACAgent(DrQAgent):
     def update_critics(self, batch, **kw):
         raise AttributeError("SACAgent has no update_critics (drq.py:296-328 is DrQ-only); use update(networks_to_update={'critic'})")
 
+    def _eval_obs(self, observations):
+        """flat observations, (S,) or (n, S), as sample_actions takes them -> (None, state f32[n, S] device, n, batched)"""
+        st = np.asarray(observations, np.float32)
+        batched = st.ndim == 2
+        n = st.shape[0] if batched else 1
+        return None, torch.from_numpy(st.reshape(n, -1)).to(self.core.device), n, batched
+
     def sample_actions(self, observations, *, seed=None, argmax: bool = False, **kwargs):
         """sac.py:301-320."""
         if argmax:

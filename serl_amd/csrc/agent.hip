@@ -86,6 +86,7 @@ struct serl_agent {
   float* G = nullptr;  // [Gc (Pc) | scalars (32) | Ga (Pa1-Pa0)]
   float *Gc = nullptr, *SC = nullptr, *Ga = nullptr;
   float* info_acc = nullptr;  // [I_N]
+  float* eval_info = nullptr; // [I_N] the same scalars as serl_agent_eval_losses forms them: an update's info is never overwritten
   float* aux = nullptr;       // [X_N]
   TrunkWeights tw{};
   TrunkWorkspace tws{};
@@ -103,7 +104,7 @@ struct serl_agent {
   int* ctr = nullptr;   // arrival counters: kCtrLanes ranges of kCtrPerLane (zero between launches)
   float* feats = nullptr;  // current slot: [2][n_cam][B][HW][512]
   static constexpr int kSlots = 3;                                  // pipelined update batches in flight (see serl_mi355.h)
-  float* feats_slot[kSlots + 1] = {nullptr, nullptr, nullptr, nullptr};   // 0..kSlots-1: update batches, kSlots: sample_actions
+  float* feats_slot[kSlots + 1] = {nullptr, nullptr, nullptr, nullptr};   // 0..kSlots-1: update batches, kSlots: sample_actions and the read-only evaluations
   serl_batch cur_slot[kSlots]{};
   bool slot_valid[kSlots] = {false, false, false};
   EncBuf encP{}, encT{}, encO{};
@@ -245,8 +246,9 @@ size_t carve(serl_agent* a, void* base) {
   a->info_acc = b.take<float>(8);
   a->aux = b.take<float>(X_N);
   const size_t persistent = b.off;  // zero-initialised region ends here
+  // (the scratch slot holds both observation sides too: serl_agent_eval_losses runs a whole batch through it)
   for (int k = 0; k <= serl_agent::kSlots; ++k)
-    a->feats_slot[k] = b.take<float>((k < serl_agent::kSlots ? 2L : 1L) * c.n_cam * B * a->HW * 512);   // (HW = 0 without a trunk)
+    a->feats_slot[k] = b.take<float>(2L * c.n_cam * B * a->HW * 512);   // (HW = 0 without a trunk)
   a->feats = a->feats_slot[0];
   auto enc = [&](EncBuf& e) {
     e.f = b.take<float>((long)c.n_cam * B * a->D);
@@ -300,6 +302,7 @@ size_t carve(serl_agent* a, void* base) {
   a->ctr = b.take<int>((long)kCtrPerLane * kCtrLanes);
   a->labels = b.take<float>(B); a->label_logits = b.take<float>(B); a->label_mean = b.take<float>(1);
   a->label_ctr = b.take<int>(1);
+  a->eval_info = b.take<float>(8);
   if (a->small) {
     void* smem = b.take<uint8_t>(small_workspace_bytes(c.n_cam * c.batch, c.H, c.W, c.num_stack));
     if (base) small_workspace_bind(a->sws, smem, c.n_cam * c.batch, c.H, c.W, c.num_stack);
@@ -1021,6 +1024,8 @@ static int check_batch(serl_agent* a, const serl_batch* b) {
   return SERL_OK;
 }
 
+static int trunk_pass(serl_agent* a, const serl_batch* batch, float* feats, int stage_begin, int stage_end, hipStream_t st);
+
 int serl_agent_encode_slot(serl_agent* a, const serl_batch* batch, int slot, void* stream) {
   return serl_agent_encode_slot_range(a, batch, slot, -1, kTrunkStages - 1, stream);
 }
@@ -1035,7 +1040,11 @@ int serl_agent_encode_slot_range(serl_agent* a, const serl_batch* batch, int slo
   hipStream_t st = (hipStream_t)stream;
   a->cur_slot[slot] = *batch;
   a->slot_valid[slot] = true;
-  float* feats = a->feats_slot[slot];
+  return trunk_pass(a, batch, a->feats_slot[slot], stage_begin, stage_end, st);
+}
+
+// The frozen trunk on both observation sides of `batch` into `feats` ([2][n_cam][cfg.batch] feature maps)
+static int trunk_pass(serl_agent* a, const serl_batch* batch, float* feats, int stage_begin, int stage_end, hipStream_t st) {
   const serl_agent_cfg& c = a->cfg;
   const int B = batch->batch;
   const size_t fbytes = (size_t)c.H * c.W * 3;
@@ -1452,6 +1461,53 @@ int serl_agent_read_info(serl_agent* a, serl_info* out, void* stream) {
   return SERL_OK;
 }
 
+// ---- acting and read-only evaluation (serl_mi355.h): forwards on observations that are no update batch ---------------------------
+// What the forward helpers read of the agent's host-side training state is swapped for the evaluation's own view and put back
+// when the scope ends, on every path out: the batch binding, the feature slot, the reward-label flags, the loss normaliser and
+// the noise counter.  Device memory: the evaluations write activations, gradient scratch, the scratch feature slot and eval_info
+// only -- nothing a later update reads before it has rewritten it.
+struct EvalScope {
+  serl_agent* a;
+  serl_batch cur; bool has_batch, labelled, label_exempt; float* feats; int last_global; uint64_t noise_ctr;
+  explicit EvalScope(serl_agent* a_)
+      : a(a_), cur(a_->cur), has_batch(a_->has_batch), labelled(a_->labelled), label_exempt(a_->label_exempt), feats(a_->feats),
+        last_global(a_->last_global), noise_ctr(a_->noise_ctr) {
+    a->feats = a->feats_slot[serl_agent::kSlots];
+  }
+  ~EvalScope() {
+    a->cur = cur; a->has_batch = has_batch; a->labelled = labelled; a->label_exempt = label_exempt; a->feats = feats;
+    a->last_global = last_global; a->noise_ctr = noise_ctr;
+    a->pg_ncs = a->pg_nwg = 0;
+  }
+};
+
+static int eval_check(serl_agent* a, const uint8_t* dev_frames, const float* dev_state, int n) {
+  SERL_REQUIRE(a, "NULL agent");
+  const serl_agent_cfg& c = a->cfg;
+  SERL_REQUIRE(n >= 1 && n <= c.batch, "n %d not in [1,%d]", n, c.batch);
+  SERL_REQUIRE(dev_frames || c.n_cam == 0, "dev_frames is NULL on an agent with %d camera(s)", c.n_cam);
+  SERL_REQUIRE(dev_state, "dev_state is NULL");
+  return SERL_OK;
+}
+
+// The trunk on [n_cam][n] images into the scratch slot, then one EncodingWrapper pass with parameters P, train=False (no Dropout),
+// into `e`; the state goes through a temporary serl_batch view (with `act_src` the actions ride into [enc | action] at act_dst).
+// Inside an EvalScope.
+static int eval_encode(serl_agent* a, const uint8_t* dev_frames, const float* dev_state, int n, const float* P, EncBuf* e,
+                       const float* act_src, float* act_dst, hipStream_t st) {
+  const serl_agent_cfg& c = a->cfg;
+  const size_t fbytes = (size_t)c.H * c.W * 3;
+  for (int k = 0; k < c.n_cam && !a->small; ++k)
+    RC(trunk_forward(a->tw, a->tws, dev_frames + (size_t)k * n * fbytes, n, a->feats + ((long)k * c.batch) * a->HW * 512, st,
+                     a->trunk_mode ? &a->tpk : nullptr));
+  a->cur = serl_batch{};
+  a->cur.batch = n;
+  a->cur.state = const_cast<float*>(dev_state);
+  a->cur.frames = const_cast<uint8_t*>(dev_frames);   // (the SmallEncoder reads the pixels in encode_multi)
+  const EncJob ej{P, 0, nullptr, e, act_src, act_dst};
+  return encode_multi(a, &ej, 1, 0, n, st);
+}
+
 int serl_agent_sample_actions(serl_agent* a, const uint8_t* dev_frames, const float* dev_state, int n,
                               const float* dev_eps, float* dev_out_actions, void* stream) {
   SERL_REQUIRE(a && dev_state && dev_out_actions, "NULL argument");
@@ -1460,30 +1516,95 @@ int serl_agent_sample_actions(serl_agent* a, const uint8_t* dev_frames, const fl
   SERL_REQUIRE(n >= 1 && n <= c.batch, "n %d not in [1,%d]", n, c.batch);
   hipStream_t st = (hipStream_t)stream;
   SERL_HIP(hipSetDevice(c.device));
-  // trunk on [n_cam][n] images -> feats slot 0; state goes through a temporary serl_batch view
-  const size_t fbytes = (size_t)c.H * c.W * 3;
-  for (int k = 0; k < c.n_cam && !a->small; ++k)
-    RC(trunk_forward(a->tw, a->tws, dev_frames + (size_t)k * n * fbytes, n, a->feats_slot[serl_agent::kSlots] + ((long)k * c.batch) * a->HW * 512, st, a->trunk_mode ? &a->tpk : nullptr));
-  serl_batch saved = a->cur;
-  const bool had = a->has_batch;
-  float* saved_feats = a->feats;
-  a->feats = a->feats_slot[serl_agent::kSlots];
-  a->cur = serl_batch{};
-  a->cur.batch = n;
-  a->cur.state = const_cast<float*>(dev_state);
-  a->cur.frames = const_cast<uint8_t*>(dev_frames);   // (the SmallEncoder reads the pixels in encode_multi)
-  const EncJob ej{a->theta, 0, nullptr, &a->encP, nullptr, nullptr};  // train=False: no dropout
-  RC(encode_multi(a, &ej, 1, 0, n, st));
+  EvalScope scope(a);
+  RC(eval_encode(a, dev_frames, dev_state, n, a->theta, &a->encP, nullptr, nullptr, st));
   if (!dev_eps) {  // argmax -> mode = tanh(mean), or the mean itself without the squash: zero noise
     RC(fill(a->eps_buf[0], 0.f, (long)n * c.act_dim, st));
     dev_eps = a->eps_buf[0];
   }
   PolJob pj{a->theta, &a->pol, a->encP.enc, a->encP.ld, dev_eps, dev_out_actions, c.act_dim, nullptr, nullptr};
   pj.eps_out = a->eps_buf[0];
-  RC(policy_fwd_multi(a, &pj, 1, n, st));
-  a->cur = saved;
-  a->has_batch = had;
-  a->feats = saved_feats;
+  return policy_fwd_multi(a, &pj, 1, n, st);
+}
+
+int serl_agent_eval_q(serl_agent* a, const uint8_t* dev_frames, const float* dev_state, const float* dev_actions,
+                      int n, int target, float* dev_q_out, void* stream) {
+  RC(eval_check(a, dev_frames, dev_state, n));
+  SERL_REQUIRE(dev_actions && dev_q_out, "dev_actions or dev_q_out is NULL");
+  const serl_agent_cfg& c = a->cfg;
+  hipStream_t st = (hipStream_t)stream;
+  SERL_HIP(hipSetDevice(c.device));
+  EvalScope scope(a);
+  // the target copy goes through the target buffers of the critic phase, the online one through the online buffers
+  const float* P = target ? a->theta_t : a->theta;
+  CritBuf& cb = target ? a->critT : a->crit;
+  RC(eval_encode(a, dev_frames, dev_state, n, P, target ? &a->encT : &a->encO, dev_actions, cb.x + a->E, st));
+  const CritJob cj{P, &cb};
+  RC(critic_fwd_multi(a, &cj, 1, n, st));
+  SERL_HIP(hipMemcpyAsync(dev_q_out, cb.q, sizeof(float) * c.ensemble * n, hipMemcpyDeviceToDevice, st));   // [ensemble][n]
+  return SERL_OK;
+}
+
+int serl_agent_eval_policy(serl_agent* a, const uint8_t* dev_frames, const float* dev_state, const float* dev_actions,
+                           int n, float* dev_mean_out, float* dev_std_out, float* dev_mode_out, float* dev_logp_out,
+                           void* stream) {
+  RC(eval_check(a, dev_frames, dev_state, n));
+  SERL_REQUIRE(!dev_logp_out || dev_actions, "dev_logp_out is given and dev_actions is NULL: a log-density needs the actions");
+  const serl_agent_cfg& c = a->cfg;
+  const Offs& o = a->o;
+  hipStream_t st = (hipStream_t)stream;
+  SERL_HIP(hipSetDevice(c.device));
+  EvalScope scope(a);
+  const float* P = a->theta;
+  RC(eval_encode(a, dev_frames, dev_state, n, P, &a->encP, nullptr, nullptr, st));
+  // the policy MLP as policy_fwd_multi runs it; the head always as a plain K-split GEMM whose slabs policy_stats_kernel reads
+  // (whatever a->fuse says: the fused epilogue samples, and this call draws nothing)
+  PolBuf& pb = a->pol;
+  const LayerJob d1{P, mlp_io(o.a1, a->encP.enc, a->encP.ld, pb.m.l1, n), {}}, d2{P, mlp_io(o.a2, pb.m.l1, pb.m.l2, n), {}};
+  RC(dense_ln_multi(a, o.a1, &d1, 1, n, 8, st));
+  RC(dense_ln_multi(a, o.a2, &d2, 1, n, 4, st));
+  const GemmDesc g = gemm_fwd(pb.m.l2.h, c.hidden, 0, P + o.a_Wm, o.a_bs - o.a_bm, a->slabs_lane[0], a->head_groups, n, c.act_dim,
+                              c.hidden, 4);
+  SERL_REQUIRE((long)a->head_groups * 4 * n * c.act_dim <= a->slabs_cap, "policy head exceeds the slab scratch");
+  RC(gemm_f32_multi(&g, 1, st));
+  PolicyStatsArgs v{};
+  v.slabs = a->slabs_lane[0]; v.S = 4; v.bias_mean = P + o.a_bm; v.bias_ls = P + o.a_bs; v.act = dev_actions;
+  v.mean = dev_mean_out; v.std = dev_std_out; v.mode_out = dev_mode_out; v.logp = dev_logp_out;
+  v.rows = n; v.A = c.act_dim; v.std_min = c.std_min; v.std_max = c.std_max; v.mode = a->pol_mode;
+  return policy_stats(v, st);
+}
+
+int serl_agent_eval_losses(serl_agent* a, const serl_batch* batch, const serl_noise* noise, serl_info* host_out, void* stream) {
+  SERL_REQUIRE(a && batch && host_out, "NULL argument");
+  RC(check_batch(a, batch));
+  const serl_agent_cfg& c = a->cfg;
+  hipStream_t st = (hipStream_t)stream;
+  SERL_HIP(hipSetDevice(c.device));
+  EvalScope scope(a);
+  // serl_agent_update's encode without a slot: both sides of the batch through the trunk into the scratch slot, no binding
+  RC(trunk_pass(a, batch, a->feats, -1, kTrunkStages - 1, st));
+  a->cur = *batch;
+  a->has_batch = true;
+  a->labelled = false; a->label_exempt = true;   // SACAgent.update keeps the stored rewards
+  RC(serl_agent_critic_grads(a, 0, batch->batch, batch->batch, noise, 0, stream));
+  RC(serl_agent_actor_grads(a, batch->batch, noise, stream));
+  // the info rider of serl_agent_apply(all three networks) with its arguments, alone
+  AdamArgs ad{};
+  ad.info_mode = 3; ad.info_reset = 1;
+  ad.scalars = a->SC; ad.alpha = a->aux + X_ALPHA; ad.info_acc = a->eval_info;
+  ad.info_w = 1.0f;
+  ad.target_entropy = c.target_entropy;
+  ad.inv_batch = a->last_global > 0 ? 1.0f / (float)a->last_global : 0.f;
+  ad.inv_eb = a->last_global > 0 ? 1.0f / ((float)c.ensemble * (float)a->last_global) : 0.f;
+  RC(adam_info_only(ad, st));
+  float acc[I_N];
+  SERL_HIP(hipMemcpyAsync(acc, a->eval_info, sizeof(acc), hipMemcpyDeviceToHost, st));
+  SERL_HIP(hipStreamSynchronize(st));
+  host_out->critic_loss = acc[I_CL]; host_out->predicted_qs = acc[I_PQ]; host_out->target_qs = acc[I_TQ];
+  host_out->actor_loss = acc[I_AL]; host_out->temperature = acc[I_TEMP]; host_out->entropy = acc[I_ENT];
+  host_out->temperature_loss = acc[I_TL];
+  host_out->actor_lr = lr_at(c, a->step, SERL_TX_ACTOR); host_out->critic_lr = lr_at(c, a->step, SERL_TX_CRITIC);
+  host_out->temperature_lr = lr_at(c, a->step, SERL_TX_TEMPERATURE);
   return SERL_OK;
 }
 
@@ -1538,6 +1659,7 @@ int serl_agent_debug_get(serl_agent* a, const char* what, float* host_out, int64
   else if (w == "x_target") { p = a->critT.x; n = (long)c.batch * a->XA; }
   else if (w == "feats") { p = a->feats; n = 2L * c.n_cam * c.batch * a->HW * 512; }
   else if (w == "logp") { p = a->pol.logp; n = c.batch; }
+  else if (w == "std") { p = a->pol.std; n = (long)c.batch * c.act_dim; }   // clipped std [rows][A] of the last policy evaluation in `pol`
   else if (w == "dx") { p = a->dx; n = (long)c.batch * a->XA; }
   // SmallEncoder layer 0's ReLU output of the LAST encoder pass, [n_cam][images of that pass][h1][w1][32]
   else if (w == "small_act0" && a->small) { p = a->sws.act[0]; n = (long)c.n_cam * c.batch * a->sws.d.h[1] * a->sws.d.w[1] * kSmallFeat[1]; }

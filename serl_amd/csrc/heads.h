@@ -96,6 +96,17 @@ int critic_loss(const float* qt, const float* q, const float* reward, const floa
                 int B, float discount, float inv_norm, float* y_out, float* dq, float* scalars, float* dbias,
                 hipStream_t stream, bool per_member_bias = false, const float* logp_next = nullptr, const float* alpha = nullptr);
 int policy_dist_fwd_multi(const PolicyDistArgs* v, int n, int B, int A, float std_min, float std_max, hipStream_t stream);
+// The policy distribution of `rows` rows read off the head GEMM's slabs (the layout policy_dist_fwd_multi reads), without a
+// sample: loc, scale_diag, mode and -- with `act` [rows][A] -- log pi(act | s) (sac.py:71-91).  Any output may be nullptr; logp
+// needs act.  A row with an action component |a| >= 1 under the tanh squash gets a non-finite logp (not clamped).
+struct PolicyStatsArgs {
+  const float* slabs; int S;   // [mean | log_std][S K-splits][rows][A]; kPolUniform: [mean] alone, bias_ls = log_stds
+  const float *bias_mean, *bias_ls, *act;
+  float *mean, *std, *mode_out, *logp;   // [rows][A] x 3, [rows]
+  int rows, A; float std_min, std_max;
+  int mode;   // kPol*
+};
+int policy_stats(const PolicyStatsArgs& v, hipStream_t stream);
 // proprio branch: y = tanh(LN(state W + b)) with W [S][64] (encoding.py:55-70), one wave per row
 struct ProprioArgs {
   const float* state; const float *W, *b, *gamma, *beta;
@@ -136,6 +147,8 @@ struct AdamArgs {
   float info_w, inv_eb;
 };
 int adam_ema(const AdamArgs& a, hipStream_t stream);
+// the info rider of `a` alone (info_mode, scalars, alpha, info_acc, ...): no parameter, moment or target is read or written
+int adam_info_only(const AdamArgs& a, hipStream_t stream);
 // optax.adam(lr) alone over a trainable slice theta[0, nt) (no schedule, clip or target), at update number `step` (1-based).
 // m / v hold nt + 1 floats: the last is the temperature slot adam_ema keeps at P - 1, never touched (g = m = v = 0).
 inline AdamArgs adam_slice(float* theta, long nt, const float* g, float* m, float* v, float lr, int64_t step) {

@@ -1624,6 +1624,64 @@ int policy_dist_fwd_multi(const PolicyDistArgs* vs, int n, int B, int A, float s
   return SERL_OK;
 }
 
+// =============================================================================================
+// The policy distribution itself, for inspection (forward_policy(obs, train=False), sac.py:71-91): no sample is drawn.
+//   mean = loc (pre-squash);  std = scale_diag, by the expressions of policy_dist_fwd_kernel (same bits);  mode = tanh(mean), or
+//   mean with kPolNoTanh;  logp[row] = log pi(act[row] | s) when `act` is given:
+//     kPolNoTanh:  sum_j log N(a_j; mean_j, std_j)
+//     else (distrax Transformed.log_prob under the Tanh bijector):  u = atanh(a) = (log1p(a) - log1p(-a)) / 2,
+//                  sum_j [log N(u_j; mean_j, std_j) - 2 (log 2 - u_j - softplus(-2 u_j))]
+//   softplus(-2u) = max(-2u, 0) + log1p(exp(-|2u|)): the exponent is never positive, nothing overflows at any finite u.
+// An action component with |a_j| >= 1 has no finite pre-image: u_j = +-inf (or NaN beyond) and the row's logp is not finite, as
+// the reference's is -- it is NOT clamped (stored gripper commands of exactly +-1 are common: clip them before asking).
+// One wave owns one row and lane j holds action column j (A <= 64; a lane past A reads column 0 and contributes 0), so the sum
+// over the row is the xor butterfly of wave_sum2: a fixed order that depends on neither the grid nor the row count.  Loads are
+// issued together on clamped addresses before any store; no LDS, no scratch.
+// =============================================================================================
+template <int MODE>
+__global__ __launch_bounds__(256) void policy_stats_kernel(PolicyStatsArgs v) {
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (row >= v.rows) return;   // (uniform over the wave)
+  const int A = v.A;
+  const bool live = lane < A;
+  const int j = live ? lane : 0;
+  const long e = (long)row * A + j;
+  float mean = v.bias_mean[j], ls = v.bias_ls[j];
+  const float a = v.act ? v.act[e] : 0.f;
+  for (int sp = 0; sp < v.S; ++sp) {   // K-split slabs of the head GEMM, [mean | log_std][split][rows][A], added in index order
+    mean += v.slabs[((long)sp * v.rows) * A + e];
+    if ((MODE & kPolStdMask) != kPolUniform) ls += v.slabs[(((long)v.S + sp) * v.rows) * A + e];
+  }
+  const float sd = fminf(fmaxf(policy_std_raw<MODE>(ls), v.std_min), v.std_max);
+  float lp = 0.f;
+  if (v.logp) {   // (uniform: a launch argument)
+    float u = a;
+    if (!(MODE & kPolNoTanh)) u = 0.5f * (log1pf(a) - log1pf(-a));
+    const float z = (u - mean) / sd;
+    lp = -0.5f * z * z - logf(sd) - 0.91893853320467274f;
+    if (!(MODE & kPolNoTanh)) lp -= 2.f * (0.69314718055994531f - u - softplusf(-2.f * u));
+    lp = live ? lp : 0.f;
+    float unused = 0.f;
+    wave_sum2(lp, unused);
+  }
+  if (live) {
+    if (v.mean) v.mean[e] = mean;
+    if (v.std) v.std[e] = sd;
+    if (v.mode_out) v.mode_out[e] = (MODE & kPolNoTanh) ? mean : tanhf(mean);
+  }
+  if (v.logp && lane == 0) v.logp[row] = lp;
+}
+
+int policy_stats(const PolicyStatsArgs& v, hipStream_t stream) {
+  SERL_REQUIRE(v.rows >= 1 && v.A >= 1 && v.A <= 64, "policy statistics: %d rows x %d action columns (one lane per column: at most 64)", v.rows, v.A);
+  SERL_REQUIRE(!v.logp || v.act, "policy statistics: a log-density needs the actions it is the density of");
+#define SERL_X(M) SERL_LAUNCH_CHAIN(policy_stats_kernel<M>, dim3(cdiv(v.rows, 4)), dim3(256), 0, stream, v)
+  SERL_POLICY_MODE_SWITCH(v.mode, SERL_X, SERL_REQUIRE(false, "bad policy distribution mode %d", v.mode))
+#undef SERL_X
+  SERL_HIP(hipGetLastError());
+  return SERL_OK;
+}
+
 
 // proprio branch (encoding.py:55-70): y = tanh(LayerNorm_1e-6(state W + b)), W [S][64]; one wave per row,
 // lane = output feature.  Replaces a GEMM + LN launch pair for this tiny layer.
@@ -1912,6 +1970,22 @@ int adam_ema(const AdamArgs& a, hipStream_t stream) {
   v.vec_ok = a.Pc >= 4 && a.Pa1 - a.Pa0 >= 4 && al16(a.theta) && al16(a.theta_target) && al16(a.g_critic) && al16(a.m_c) &&
              al16(a.v_c) && a.g_critic && a.g_actor && a.m_a && a.v_a;
   SERL_LAUNCH_CHAIN(adam_ema_kernel, dim3(cdiv(cdiv(a.P + v.n_frozen_live, 4), 256)), dim3(256), 0, stream, v);
+  SERL_HIP(hipGetLastError());
+  return SERL_OK;
+}
+
+// The info rider of adam_ema_kernel alone: one workgroup of that kernel over an EMPTY index space (P = 0, no frozen leaves), so
+// thread 0 forms the info scalars with the instructions an update forms them with -- the same bits -- and no thread reaches a
+// parameter, a moment or a target (serl_agent_eval_losses).
+int adam_info_only(const AdamArgs& a, hipStream_t stream) {
+  AdamArgs v = a;
+  v.P = v.Pc = v.Pa0 = v.Pa1 = 0;
+  v.n_frozen = v.n_frozen_live = 0;
+  v.vec_ok = 0;
+  v.critic_on = v.actor_on = v.temp_on = v.ema_on = 0;
+  v.clip_c = v.clip_a = v.clip_t = 0.f;
+  SERL_REQUIRE(v.info_mode != 0 && v.info_acc && v.scalars, "the info rider needs its mode, its scalars and a place for the result");
+  SERL_LAUNCH_CHAIN(adam_ema_kernel, dim3(1), dim3(256), 0, stream, v);
   SERL_HIP(hipGetLastError());
   return SERL_OK;
 }
