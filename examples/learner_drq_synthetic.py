@@ -74,24 +74,32 @@ def main():
     ap.add_argument("--eval-every", dest="eval_every", type=int, default=0,
                     help="every K steps print the ensemble's mean Q on a demo batch and the mean log-prob of its actions "
                          "(agent.evaluate_batch: read-only for the agent; the extra sample advances the demo store's sampler)")
+    ap.add_argument("--weight_decay", type=float, default=None,
+                    help="weight_decay of all three optimizers (optax.adamw).  It decays the whole tree, the pretrained ResNet-10 "
+                         "included, as in the reference -- not a recommendation: the agent then runs with a live trunk "
+                         "(agent.live_trunk: a third trunk pass, re-packed weights per step, no prefetch overlap)")
     a = ap.parse_args()
     assert a.run_dir or not (a.save_every or a.resume), "--save_every / --resume need --run_dir"
 
     env = _Env()
     sample_obs = {"front": np.zeros((1, H, W, 3), np.uint8), "wrist": np.zeros((1, H, W, 3), np.uint8),
                   "state": np.zeros((1, S), np.float32)}
-    if a.hidden == 256 and a.activation == "tanh":
+    if a.hidden == 256 and a.activation == "tanh" and a.weight_decay is None:
         agent = make_drq_agent(seed=42, sample_obs=sample_obs, sample_action=np.zeros((A,), np.float32), image_keys=KEYS,
                                encoder_type="resnet-pretrained", batch_size=a.batch_size)
     else:
-        # make_drq_agent has no width or activation argument (launcher.py:79-116 writes hidden_dims and nn.tanh into the call):
-        # other ones go to create_drq as they do in the reference, with the launcher's other hyper-parameters
+        # make_drq_agent has no width, activation or optimizer argument (launcher.py:79-116 writes hidden_dims and nn.tanh into
+        # the call): other ones go to create_drq as they do in the reference, with the launcher's other hyper-parameters
+        opt = {} if a.weight_decay is None else {f"{tx}_optimizer_kwargs": {"weight_decay": a.weight_decay}
+                                                 for tx in ("actor", "critic", "temperature")}
         mlp = {"activations": a.activation, "use_layer_norm": True, "hidden_dims": [a.hidden, a.hidden]}
         agent = DrQAgent.create_drq(
             42, sample_obs, np.zeros((A,), np.float32), encoder_type="resnet-pretrained", use_proprio=True, image_keys=KEYS,
             policy_kwargs={"tanh_squash_distribution": True, "std_parameterization": "exp", "std_min": 1e-5, "std_max": 5},
             critic_network_kwargs=mlp, policy_network_kwargs=dict(mlp), temperature_init=1e-2, discount=0.96,
-            backup_entropy=False, critic_ensemble_size=10, critic_subsample_size=2, batch_size=a.batch_size)
+            backup_entropy=False, critic_ensemble_size=10, critic_subsample_size=2, batch_size=a.batch_size, **opt)
+        if a.weight_decay is not None:
+            print(f"weight_decay {a.weight_decay:g} in all three optimizers: live trunk {agent.live_trunk}", flush=True)
     replay_buffer = make_replay_buffer(env, capacity=200000, type="memory_efficient_replay_buffer", image_keys=KEYS)
     demo_buffer = make_replay_buffer(env, capacity=10000, type="memory_efficient_replay_buffer", image_keys=KEYS)
     stores, update_steps = {"replay": replay_buffer, "demo": demo_buffer}, 0

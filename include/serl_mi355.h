@@ -235,8 +235,8 @@ typedef struct serl_agent_cfg {
    *   tx_warmup       >= 0: warm-up steps of this optimizer, given as steps + 1 (0 = use warmup_steps / temp_warmup_steps)
    *   tx_cosine_steps  > 0: warmup_cosine_decay_schedule(0, lr, warmup, decay_steps = this, end 0) (optimizers.py:14-21)
    *   tx_weight_decay_on != 0: optax.adamw with tx_weight_decay (optimizers.py:39-42); it decays the WHOLE tree, as the
-   *                    reference's tx.update(grads, state, params) does.  State-only agents (n_cam == 0) only: on a
-   *                    pixel agent it would decay the frozen pretrained trunk (SERL_ERR_UNSUPPORTED)
+   *                    reference's tx.update(grads, state, params) does -- on an agent with the pretrained ResNet-10 that
+   *                    tree holds the "frozen" trunk too: see LIVE TRUNK at serl_agent_create
    *   tx_clip_norm     > 0: optax.clip_by_global_norm on this optimizer's gradient tree (optimizers.py:36-37) */
   float tx_lr[3];
   int tx_warmup[3];
@@ -271,7 +271,21 @@ typedef struct serl_agent_cfg {
 #define SERL_TX_CRITIC 1
 #define SERL_TX_TEMPERATURE 2
 
+/* LIVE TRUNK.  An agent with SERL_ENCODER_RESNET_PRETRAINED and any tx_weight_decay_on is created in live-trunk mode, because that
+ * is what the reference computes (not a recommendation: decaying a pretrained trunk is rarely what a user wants).  Every
+ * optimizer step then multiplies every trunk leaf by 1 - sum_t lr_t(count) * wd_t over all three optimizers, whichever networks
+ * the step updates, and the target copy follows by the EMA on critic steps only: the online and the target trunk differ from
+ * the second step on.  The target critic's encoder reads next-frame features of the TARGET trunk (sac.py:143-147), everything
+ * else the online trunk's, and the features are recomputed after every step that changed the trunk: per minibatch inside
+ * serl_agent_update_high_utd, and once more before its actor phase.  In this mode the trunk passes run on the stream of the
+ * phase that needs them (serl_agent_critic_grads / serl_agent_actor_grads compute what is missing or stale); serl_agent_encode_slot
+ * only binds the batch, so a pass cannot run ahead of the step before it, and one slot is all a caller can use.
+ * serl_agent_bind_slot / serl_agent_slot_features (features from another GPU) are SERL_ERR_UNSUPPORTED, and reward labels
+ * always come from the classifier's own trunk (SERL_LABEL_FRAMES).  Agents without weight decay, and agents without the
+ * pretrained trunk (SERL_ENCODER_SMALL, state-only: their decay is the ordinary path of their leaves), are not in this mode and
+ * launch what they always did. */
 int serl_agent_create(const serl_agent_cfg* cfg, serl_agent** out);
+int serl_agent_live_trunk(serl_agent* a);   /* 1: live-trunk mode (above), 0: not, -1: NULL */
 /* serl_agent_create with another policy distribution (actor_critic_nets.py:167-227).  serl_agent_create is this function with
  * (SERL_STD_EXP, 0): exp + tanh, what utils/launcher.py configures -- serl_agent_cfg itself is unchanged and describes the agent it
  * always did.  Any other value of the two arguments is SERL_ERR_INVALID, the message naming the argument and the value.

@@ -72,6 +72,7 @@ SIGNATURES = {
     "serl_agent_create_policy": [P(SerlAgentCfg), i32, i32, P(vp)],   # std_param (SERL_STD_*), no_tanh
     "serl_agent_create_mlp": [P(SerlAgentCfg), i32, i32, i32, i32, P(vp)],   # ... critic_act, policy_act (SERL_ACT_*)
     "serl_agent_destroy": [vp],
+    "serl_agent_live_trunk": [vp],
     "serl_agent_num_leaves": [vp],
     "serl_agent_leaf_info": [vp, i32, C.c_char_p, i32, P(i64)],
     "serl_agent_set": [vp, C.c_char_p, C.c_char_p, vp, i64],

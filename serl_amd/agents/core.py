@@ -27,6 +27,8 @@ class AgentCore(Handle):
                  tanh_squash_distribution=True, critic_activation="tanh", policy_activation="tanh"):
         """optimizers: optional {"actor"|"critic"|"temperature": make_optimizer kwargs (common/optimizers.py:6-13:
         learning_rate, warmup_steps, cosine_decay_steps, weight_decay, clip_grad_norm)} overriding lr / warmup_steps.
+        weight_decay decays every leaf of the tree, as optax.adamw does with the params the reference hands it -- with
+        encoder_type="resnet-pretrained" the pretrained trunk too (`live_trunk`): the reference's behaviour, not a recommendation.
         num_stack: T, frames per observation (SmallEncoder only); state_dim is then the flattened width T * S.
         std_parameterization / tanh_squash_distribution: the policy distribution (Policy's kwargs of the same names).
         critic_activation / policy_activation: one of MLP_ACTIVATIONS each (MLP's `activations`, utils.init.mlp_activations)."""
@@ -96,6 +98,14 @@ class AgentCore(Handle):
     def load_flat(self, section: str, tree: Dict[str, np.ndarray]):
         for k, v in tree.items():
             self.set(section, k, v)
+
+    @property
+    def live_trunk(self) -> bool:
+        """True for the pretrained ResNet-10 under a non-zero weight_decay in any optimizer: adamw decays the whole tree, the
+        "frozen" trunk included (common/optimizers.py:39-42), so the online and the target trunk move at every step and the
+        library recomputes the features after each (serl_mi355.h, LIVE TRUNK).  Such a core computes its trunk passes inside the
+        update phases: encode_slot only binds the batch, one slot is all a schedule can use, bind_slot is refused."""
+        return int(self.L.serl_agent_live_trunk(self._h)) == 1
 
     @property
     def step(self):

@@ -188,6 +188,11 @@ class DrQAgent:
         ChunkingWrapper(obs_horizon=T) produces them; EncodingWrapper(enable_stacking=True) folds them into the channels and the
         proprio width (common/encoding.py:39-44,58-64).  T in 1..4 with encoder_type="small"; the pretrained ResNet-10 cannot take
         a stack (its conv_init kernel has 3 input channels).
+        {actor,critic,temperature}_optimizer_kwargs: make_optimizer's (common/optimizers.py:6-13).  weight_decay selects
+        optax.adamw, which decays EVERY leaf of the tree it is given (optimizers.py:39-42) -- with encoder_type="resnet-pretrained"
+        that includes the pretrained trunk, which then shrinks by sum_t lr_t * wd_t per optimizer step while its target copy
+        follows by the EMA (`agent.live_trunk`; costs a third trunk pass, re-packed weights per step and the prefetch overlap:
+        DESIGN.md section 7).  That is what the reference computes, and it is reproduced for parity -- not a recommendation.
         param_init: "numpy" (default) draws the trainable leaves from host NumPy streams seeded by `rng`; "reference" draws them
         as the reference's model_def.init(init_rng) does (utils/init_ref.py); the frozen trunk is the same either way."""
         if encoder_type not in ("resnet-pretrained", "small"):
@@ -265,6 +270,13 @@ class DrQAgent:
         from .snapshot import take_snapshot
         return take_snapshot(self, sections, slots)
 
+    @property
+    def live_trunk(self) -> bool:
+        """True when an optimizer's weight_decay reaches the pretrained trunk (AgentCore.live_trunk): the trunk then decays at
+        every optimizer step, its target copy follows by the EMA, every step is followed by fresh trunk passes on the update
+        stream, `prefetch` has no effect, and an attached reward classifier labels from its own trunk ("frames")."""
+        return self.core.live_trunk
+
     def lr_at(self, count, tx="critic"):
         """optimizers.py:14-30: warm-up -> constant, or warm-up -> cosine decay."""
         return lr_schedule(self._opts[tx], count)
@@ -301,7 +313,9 @@ class DrQAgent:
         image_keys: the agent camera each classifier camera reads, by name, in the classifier's camera order (default: the
         classifier's own image_keys) -- a subset of the agent's, in any order.
         The classifier's head runs on the frozen-trunk features the update already holds when both trunks are bit-identical
-        (reward_label_mode "features", compared here), else its own trunk runs on the augmented next frames ("frames").  Setting a
+        (reward_label_mode "features", compared here), else its own trunk runs on the augmented next frames ("frames"; always with
+        a live trunk, which is the classifier's only until the first optimizer step; the optimizer's own changes of it never
+        make the attachment stale).  Setting a
         trunk leaf on either side afterwards (load_trunk_params) makes the next labelled update raise until this is called again.
         Train the classifier with its train_step between updates, on the stream the updates run on."""
         if classifier is None:
@@ -435,8 +449,9 @@ class DrQAgent:
         return tuple((id(b), id(ix)) for b, ix in batch.parts)
 
     def _can_prefetch(self, batch, crops):
-        # (only the FROZEN trunk can run ahead of the update: a trainable encoder depends on the parameters)
-        return (self.prefetch and crops is None and isinstance(batch, LazyBatch) and self.core.cfg.n_cam > 0
+        # (only the FROZEN trunk can run ahead of the update: a trainable encoder depends on the parameters, and so does a live
+        #  trunk -- a pass of batch i+1 under the update of batch i would read the weights from before that update's apply)
+        return (self.prefetch and not self.live_trunk and crops is None and isinstance(batch, LazyBatch) and self.core.cfg.n_cam > 0
                 and self.core.cfg.encoder_type == 0 and batch.batch_size <= self.core.cfg.batch)
 
     def _slot_batch(self, slot, B):

@@ -7,6 +7,8 @@
 // The frozen trunk is evaluated twice per update (augmented obs, augmented next_obs); the reference
 // evaluates it a third time with target_params, whose trunk leaves equal the online ones up to
 // EMA round-off (<= 1e-6 relative) -- the target copy is still maintained for export.
+// LIVE TRUNK (serl_mi355.h at serl_agent_create): with adamw on an agent that has the pretrained trunk the optimizers decay the
+// trunk at every step, the two copies differ, and that third evaluation is real: live_features below.
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -92,6 +94,17 @@ struct serl_agent {
   TrunkWorkspace tws{};
   TrunkPacked tpk{};
   int trunk_mode = 1;  // 0: exact fp32 MFMA convs, 1: split-fp16 (f16x3) convs for the blocks
+  // Live trunk: the pretrained trunk under adamw.  The target copy has its own weights view and packed planes (re-derived by
+  // trunk_forward when an apply marked them dirty), and every slot a buffer [n_cam][batch] of next-frame features of the target
+  // trunk.  trunk_ver / trunk_t_ver count the changes of either copy; feats_on / feats_tg say which rows of the selected batch
+  // hold features of which version (live_features computes what a phase lacks).  All of it unused, and nothing allocated, otherwise.
+  bool live = false;
+  TrunkWeights tw_t{};
+  TrunkPacked tpk_t{};
+  float* feats_t = nullptr;   // current slot
+  float* feats_t_slot[4] = {nullptr, nullptr, nullptr, nullptr};
+  int64_t trunk_ver = 0, trunk_t_ver = 0;
+  struct FeatRows { int64_t ver = -1; int lo = 0, hi = 0; } feats_on, feats_tg;
   // last-arriver fusion of the update chain (heads.hip): slab reductions / the tanh-Gaussian head run inside the GEMM
   // launches that feed them, the critic loss rides on the LayerNorm backward that consumes dQ, noise is hashed where it is used.
   // SERL_CHAIN_FUSE=0 restores one launch per operation (A/B timing; the fused path is bit-identical on identical noise).
@@ -122,7 +135,7 @@ struct serl_agent {
   serl_batch cur{};
   bool has_batch = false;
   // The target copy of the FROZEN trunk takes an EMA step per critic update like every other leaf (common.py:124-134), but no
-  // gradient or weight decay ever reaches those leaves (adamw is refused on pixel agents), so the steps are only counted here
+  // gradient or weight decay ever reaches those leaves (with adamw the trunk is `live` and never takes this path), so the steps are only counted here
   // and applied in one pass (frozen_ema: the same rounding sequence) when somebody reads or overwrites the trunk's target
   // leaves -- 59 MB less HBM traffic per critic step.
   int64_t trunk_ema_pending = 0;
@@ -312,6 +325,13 @@ size_t carve(serl_agent* a, void* base) {
     if (base) trunk_workspace_bind(a->tws, tmem, nimg, c.H, c.W);
     void* pmem = b.take<uint8_t>(trunk_packed_bytes());
     if (base) trunk_packed_bind(a->tpk, pmem);
+    if (a->live) {   // the target copy's planes and, per slot, its features of the next frames
+      static_assert(sizeof(a->feats_t_slot) / sizeof(a->feats_t_slot[0]) == serl_agent::kSlots + 1, "one target-feature buffer per slot");
+      void* pmem_t = b.take<uint8_t>(trunk_packed_bytes());
+      if (base) trunk_packed_bind(a->tpk_t, pmem_t);
+      for (int k = 0; k <= serl_agent::kSlots; ++k) a->feats_t_slot[k] = b.take<float>((long)c.n_cam * B * a->HW * 512);
+      a->feats_t = a->feats_t_slot[0];
+    }
   }
   (void)persistent;
   return b.off;
@@ -341,6 +361,7 @@ struct EncJob {
   int gen_mask = 0;            // fused chain, mask == nullptr: 1 = hash the Dropout keep-mask inside the SLE kernel from mask_seed,
   uint64_t mask_seed = 0;      // 2 = jax.random.bernoulli(tf_key[camera], keep, (tf_rows, D)) rows tf_row0.. (serl_noise key_mask_*)
   const uint32_t* tf_key = nullptr; long tf_rows = 0, tf_row0 = 0;
+  const float* x = nullptr;    // trunk features [n_cam][cfg.batch] to read instead of side `which` of the slot (live trunk: the target copy's)
 };
 // The tensors of the two encoder layers in one EncodingWrapper pass: every camera reads its own block of f and writes its
 // columns of the code; the proprio branch reads `state` and writes the columns behind the cameras'.
@@ -374,7 +395,7 @@ int encode_multi(serl_agent* a, const EncJob* jobs, int n, int off, int cnt, hip
     const EncJob& j = jobs[i];
     EncBuf& e = *j.e;
     sv[i] = SleFwdArgs{};
-    sv[i].x = a->feats + (((long)j.which * c.n_cam) * c.batch + off) * a->HW * 512;
+    sv[i].x = (j.x ? j.x : a->feats + ((long)j.which * c.n_cam) * c.batch * a->HW * 512) + (long)off * a->HW * 512;
     sv[i].K = j.P + o.enc0;
     sv[i].mask = j.mask ? j.mask + (long)off * a->D : nullptr;
     sv[i].f = e.f;
@@ -848,14 +869,12 @@ int serl_agent_create_mlp(const serl_agent_cfg* cfg, int std_param, int no_tanh,
   SERL_REQUIRE(policy_act >= 0 && policy_act < kActCount, "policy_act %d: served are SERL_ACT_TANH (0), SERL_ACT_RELU (1) and SERL_ACT_SWISH (2)", policy_act);
   SERL_REQUIRE(cfg->state_dim % num_stack == 0, "state_dim %d is not num_stack %d proprio vectors (state_dim is the flattened width T * S)",
                cfg->state_dim, num_stack);
+  bool any_wd = false;
   for (int t = 0; t < 3; ++t) {
-    // adamw decays EVERY leaf of the tree the optimizer is given (common.py:142-147 passes the full params), i.e. it
-    // would un-freeze the pretrained trunk and make the online and target trunks differ, which the two-pass trunk
-    // evaluation relies on being equal: supported for the state-only agent only
-    if (cfg->tx_weight_decay_on[t] && cfg->n_cam > 0) {
-      set_error("weight_decay on a pixel agent would decay the frozen pretrained trunk (optimizers.py:39-42 over the full tree): unsupported");
-      return SERL_ERR_UNSUPPORTED;
-    }
+    // adamw decays EVERY leaf of the tree the optimizer is given (common.py:142-147 passes the full params): with the pretrained
+    // trunk in that tree the agent runs in live-trunk mode (below)
+    // (a decay of exactly 0 moves no leaf: such an agent keeps the frozen-trunk path, bit for bit)
+    any_wd = any_wd || (cfg->tx_weight_decay_on[t] && cfg->tx_weight_decay[t] != 0.f);
     SERL_REQUIRE(cfg->tx_lr[t] >= 0.f && cfg->tx_warmup[t] >= 0 && cfg->tx_cosine_steps[t] >= 0 && cfg->tx_clip_norm[t] >= 0.f,
                  "bad optimizer options for optimizer %d", t);
   }
@@ -867,15 +886,19 @@ int serl_agent_create_mlp(const serl_agent_cfg* cfg, int std_param, int no_tanh,
   a->critic_act = critic_act; a->policy_act = policy_act;
   { const char* e = getenv("SERL_CHAIN_FUSE"); a->fuse = !(e && e[0] == '0'); }
   build_layout(a);
+  a->live = any_wd && a->trunk_count > 0;
   if (int rc = alloc_zeroed(&a->arena, carve(a, nullptr), "agent arena")) {
     delete a;
     return rc;
   }
   carve(a, a->arena);
   if (!a->state_only && !a->small) a->tw = trunk_weights(a->trunk, a->to);
+  if (a->live) a->tw_t = trunk_weights(a->trunk_t, a->to);
   *out = a;
   return SERL_OK;
 }
+
+int serl_agent_live_trunk(serl_agent* a) { return a ? (a->live ? 1 : 0) : -1; }
 
 int serl_agent_destroy(serl_agent* a) {
   if (!a) return SERL_OK;
@@ -969,6 +992,7 @@ int serl_agent_set(serl_agent* a, const char* section, const char* leaf, const f
   RC(leaf_copy(p, host, n, hipMemcpyHostToDevice, section, leaf, kOutsideSupport));
   if (p && std::strncmp(leaf, "trunk/", 6) == 0) {
     a->tpk.dirty = true;
+    if (a->live) { a->tpk_t.dirty = true; a->trunk_ver += 1; a->trunk_t_ver += 1; }   // (either copy: both are re-packed and re-evaluated)
     a->trunk_gen += 1;   // (a reward classifier attached on equal trunks is stale now: check_label_fresh)
   }
   return SERL_OK;
@@ -1040,6 +1064,7 @@ int serl_agent_encode_slot_range(serl_agent* a, const serl_batch* batch, int slo
   hipStream_t st = (hipStream_t)stream;
   a->cur_slot[slot] = *batch;
   a->slot_valid[slot] = true;
+  if (a->live) return SERL_OK;   // the phases compute their features themselves, behind the apply in front of them (live_features)
   return trunk_pass(a, batch, a->feats_slot[slot], stage_begin, stage_end, st);
 }
 
@@ -1061,10 +1086,53 @@ static int trunk_pass(serl_agent* a, const serl_batch* batch, float* feats, int 
   return SERL_OK;
 }
 
+// Live trunk.  Rows [off, off + cnt) of the sides [w0, w1) of `batch` (0 = observations, 1 = next observations) through the trunk
+// copy (w, pk) into `feats`, laid out [w1 - w0][n_cam][cfg.batch] feature maps: the whole run of images in one pass where it is
+// contiguous on both ends, else one pass per (side, camera) as in trunk_pass.
+static int trunk_rows(serl_agent* a, const TrunkWeights& w, TrunkPacked& pk, const serl_batch* batch, int w0, int w1, int off, int cnt,
+                      float* feats, hipStream_t st) {
+  const serl_agent_cfg& c = a->cfg;
+  const int B = batch->batch;
+  const size_t fbytes = (size_t)c.H * c.W * 3;
+  const long fmap = (long)a->HW * 512;
+  SERL_REQUIRE(off >= 0 && cnt >= 1 && off + cnt <= B && B <= c.batch, "trunk rows [%d, %d) outside a batch of %d", off, off + cnt, B);
+  TrunkPacked* packed = a->trunk_mode ? &pk : nullptr;
+  if (off == 0 && cnt == B && B == c.batch)
+    return trunk_forward(w, a->tws, batch->frames + (size_t)w0 * c.n_cam * B * fbytes, (w1 - w0) * c.n_cam * B, feats, st, packed);
+  for (int s = w0; s < w1; ++s)
+    for (int k = 0; k < c.n_cam; ++k)
+      RC(trunk_forward(w, a->tws, batch->frames + ((size_t)(s * c.n_cam + k) * B + off) * fbytes, cnt,
+                       feats + (((long)(s - w0) * c.n_cam + k) * c.batch + off) * fmap, st, packed));
+  return SERL_OK;
+}
+
+// Live trunk: what the phase about to run on rows [off, off + cnt) of the selected batch reads -- both sides through the online
+// trunk and, with `target`, the next frames through the target copy (sac.py:143-147 with target_params) -- is computed here, on the
+// phase's stream and therefore behind every apply enqueued so far, unless the slot already holds it for the current version of
+// that copy.  update_high_utd thus runs a pass per minibatch (each apply moved the trunk) and one over the whole batch in front of
+// its actor phase; update() with all three networks runs one, shared by its phases.
+static int live_features(serl_agent* a, int off, int cnt, bool target, hipStream_t st) {
+  if (!a->live) return SERL_OK;
+  auto stale = [&](const serl_agent::FeatRows& h, int64_t ver) { return h.ver != ver || off < h.lo || off + cnt > h.hi; };
+  if (stale(a->feats_on, a->trunk_ver)) {
+    RC(trunk_rows(a, a->tw, a->tpk, &a->cur, 0, 2, off, cnt, a->feats, st));
+    a->feats_on.ver = a->trunk_ver; a->feats_on.lo = off; a->feats_on.hi = off + cnt;
+  }
+  if (target && stale(a->feats_tg, a->trunk_t_ver)) {
+    RC(trunk_rows(a, a->tw_t, a->tpk_t, &a->cur, 1, 2, off, cnt, a->feats_t, st));
+    a->feats_tg.ver = a->trunk_t_ver; a->feats_tg.lo = off; a->feats_tg.hi = off + cnt;
+  }
+  return SERL_OK;
+}
+
+static constexpr const char* kLiveNoRemote =
+    "this agent's trunk is live (weight decay on the pretrained trunk): features computed elsewhere would be those of another trunk";
+
 int serl_agent_slot_features(serl_agent* a, int slot, float** dev_out, int64_t* count_out) {
   SERL_REQUIRE(a && dev_out && count_out, "NULL argument");
   SERL_REQUIRE(slot >= 0 && slot < serl_agent::kSlots, "slot must be 0..%d", serl_agent::kSlots - 1);
   SERL_REQUIRE(!a->state_only && !a->small, "this agent has no frozen-trunk features");
+  if (a->live) { set_error("%s", kLiveNoRemote); return SERL_ERR_UNSUPPORTED; }
   *dev_out = a->feats_slot[slot];
   *count_out = 2LL * a->cfg.n_cam * a->cfg.batch * a->HW * 512;
   return SERL_OK;
@@ -1076,6 +1144,7 @@ int serl_agent_bind_slot(serl_agent* a, const serl_batch* batch, int slot) {
   int rc = check_batch(a, batch);
   if (rc) return rc;
   SERL_REQUIRE(batch->batch == a->cfg.batch, "externally computed features cover a full-size batch");
+  if (a->live) { set_error("%s", kLiveNoRemote); return SERL_ERR_UNSUPPORTED; }
   a->cur_slot[slot] = *batch;
   a->slot_valid[slot] = true;
   return SERL_OK;
@@ -1085,6 +1154,8 @@ int serl_agent_select_slot(serl_agent* a, int slot) {
   SERL_REQUIRE(a, "NULL agent");
   SERL_REQUIRE(slot >= 0 && slot < serl_agent::kSlots && a->slot_valid[slot], "slot %d holds no encoded batch", slot);
   a->feats = a->feats_slot[slot];
+  a->feats_t = a->feats_t_slot[slot];
+  a->feats_on = a->feats_tg = serl_agent::FeatRows{};   // (live trunk: nothing of this batch is computed yet)
   a->cur = a->cur_slot[slot];
   a->has_batch = true;
   a->labelled = a->label_exempt = false;   // this batch's rewards are its own until serl_agent_label_rewards runs
@@ -1149,7 +1220,8 @@ int serl_agent_set_reward_classifier(serl_agent* a, serl_classifier* cls, const 
   SERL_REQUIRE(v.cfg.max_batch >= c.batch, "classifier max_batch %d is below the agent's batch %d", v.cfg.max_batch, c.batch);
   SERL_HIP(hipSetDevice(c.device));
   int mode = SERL_LABEL_FRAMES;
-  if (!a->small && v.trunk_count == a->trunk_count) {   // shared features only where every trunk leaf is bit-identical
+  // (a live trunk is the classifier's only until the first optimizer step: always the classifier's own pass)
+  if (!a->small && !a->live && v.trunk_count == a->trunk_count) {   // shared features only where every trunk leaf is bit-identical
     SERL_HIP(hipDeviceSynchronize());
     std::vector<float> mine(a->trunk_count), theirs(a->trunk_count);
     SERL_HIP(hipMemcpy(mine.data(), a->trunk, sizeof(float) * mine.size(), hipMemcpyDeviceToHost));
@@ -1258,12 +1330,14 @@ int serl_agent_critic_grads_bucketed(serl_agent* a, int off, int cnt, int global
                              noise && noise->key_eps_next ? noise->key_eps_next + 2 * redq_row : nullptr,
                              noise && noise->key_mask_next ? noise->key_mask_next + 2 * c.n_cam * redq_row : nullptr);
   RC(materialise_noise(a, &nz, 1, off, cnt, global_count, st));
+  RC(live_features(a, off, cnt, true, st));
   // the three encoder passes of the critic loss in one set of launches: online policy input at next_obs
   // (dropout), target-critic input at next_obs (target_params, train=False), online-critic input at obs
   // (train=False; the batch's actions ride along into [enc | action])
   EncJob ej[3] = {{a->theta, 1, nullptr, &a->encP, nullptr, nullptr},
                   {a->theta_t, 1, nullptr, &a->encT, nullptr, nullptr},
                   {a->theta, 0, nullptr, &a->encO, a->cur.action + (long)off * A, a->crit.x + a->E}};
+  if (a->live) ej[1].x = a->feats_t;   // target_params hold the target trunk too
   // backup_entropy (sac.py:174-176) needs alpha = softplus(lagrange) of the online parameters next to the per-sample log-probs
   PolJob pj{a->theta, &a->pol, a->encP.enc, a->encP.ld, nullptr, a->critT.x + a->E, a->XA, nullptr,
             c.backup_entropy ? a->aux + X_ALPHA : nullptr};
@@ -1300,6 +1374,7 @@ int serl_agent_actor_grads(serl_agent* a, int global_count, const serl_noise* no
                       draw_noise(a, noise ? noise->eps_temp : nullptr, noise ? noise->mask_next_temp : nullptr, 2,
                                  noise ? noise->key_eps_temp : nullptr, noise ? noise->key_mask_next_temp : nullptr)};
   RC(materialise_noise(a, nz, 2, 0, cnt, global_count, st));
+  RC(live_features(a, 0, cnt, false, st));
   // encoder passes of the actor step in one set of launches: temperature loss input (next_obs, dropout;
   // sac.py:223-234), critic-side encoding of obs (train=False), policy input at obs (dropout; sac.py:193-221)
   EncJob ej[3] = {{a->theta, 1, nullptr, &a->encT, nullptr, nullptr},
@@ -1373,8 +1448,7 @@ int serl_agent_apply(serl_agent* a, int which, float info_weight, void* stream) 
   ad.tau = c.tau; ad.target_entropy = c.target_entropy;
   ad.inv_batch = a->last_global > 0 ? 1.0f / (float)a->last_global : 0.f;
   ad.frozen = a->trunk; ad.frozen_target = a->trunk_t; ad.n_frozen = a->trunk_count;  // common.py:124-134 covers every leaf
-  const bool any_wd = c.tx_weight_decay_on[SERL_TX_ACTOR] || c.tx_weight_decay_on[SERL_TX_CRITIC] || c.tx_weight_decay_on[SERL_TX_TEMPERATURE];
-  if (!any_wd && a->trunk_count > 0) {   // frozen leaves only ever see the EMA: count the step, apply it lazily (flush_trunk_ema)
+  if (!a->live && a->trunk_count > 0) {   // frozen leaves only ever see the EMA: count the step, apply it lazily (flush_trunk_ema)
     ad.n_frozen = 0;
     if (crit) a->trunk_ema_pending += 1;
   }
@@ -1392,6 +1466,10 @@ int serl_agent_apply(serl_agent* a, int which, float info_weight, void* stream) 
   ad.info_w = info_weight;
   ad.inv_eb = a->last_global > 0 ? 1.0f / ((float)c.ensemble * (float)a->last_global) : 0.f;
   RC(adam_ema(ad, st));
+  if (a->live) {   // the step decayed the online trunk and, with the EMA, moved the target copy: planes and features are stale
+    a->tpk.dirty = true; a->trunk_ver += 1;
+    if (crit) { a->tpk_t.dirty = true; a->trunk_t_ver += 1; }
+  }
   a->step += 1;
   a->lr_last[SERL_TX_ACTOR] = ad.lr_a; a->lr_last[SERL_TX_CRITIC] = ad.lr_c; a->lr_last[SERL_TX_TEMPERATURE] = ad.lr_t;
   return SERL_OK;
@@ -1469,14 +1547,18 @@ int serl_agent_read_info(serl_agent* a, serl_info* out, void* stream) {
 struct EvalScope {
   serl_agent* a;
   serl_batch cur; bool has_batch, labelled, label_exempt; float* feats; int last_global; uint64_t noise_ctr;
+  float* feats_t; serl_agent::FeatRows feats_on, feats_tg;   // live trunk: the scratch slot starts empty, the update's slot keeps what it holds
   explicit EvalScope(serl_agent* a_)
       : a(a_), cur(a_->cur), has_batch(a_->has_batch), labelled(a_->labelled), label_exempt(a_->label_exempt), feats(a_->feats),
-        last_global(a_->last_global), noise_ctr(a_->noise_ctr) {
+        last_global(a_->last_global), noise_ctr(a_->noise_ctr), feats_t(a_->feats_t), feats_on(a_->feats_on), feats_tg(a_->feats_tg) {
     a->feats = a->feats_slot[serl_agent::kSlots];
+    a->feats_t = a->feats_t_slot[serl_agent::kSlots];
+    a->feats_on = a->feats_tg = serl_agent::FeatRows{};
   }
   ~EvalScope() {
     a->cur = cur; a->has_batch = has_batch; a->labelled = labelled; a->label_exempt = label_exempt; a->feats = feats;
     a->last_global = last_global; a->noise_ctr = noise_ctr;
+    a->feats_t = feats_t; a->feats_on = feats_on; a->feats_tg = feats_tg;
     a->pg_ncs = a->pg_nwg = 0;
   }
 };
@@ -1497,9 +1579,13 @@ static int eval_encode(serl_agent* a, const uint8_t* dev_frames, const float* de
                        const float* act_src, float* act_dst, hipStream_t st) {
   const serl_agent_cfg& c = a->cfg;
   const size_t fbytes = (size_t)c.H * c.W * 3;
+  // (live trunk: target_params hold their own trunk copy -- forward_target_critic runs it)
+  const bool tgt = a->live && P == a->theta_t;
+  const TrunkWeights& w = tgt ? a->tw_t : a->tw;
+  TrunkPacked& pk = tgt ? a->tpk_t : a->tpk;
   for (int k = 0; k < c.n_cam && !a->small; ++k)
-    RC(trunk_forward(a->tw, a->tws, dev_frames + (size_t)k * n * fbytes, n, a->feats + ((long)k * c.batch) * a->HW * 512, st,
-                     a->trunk_mode ? &a->tpk : nullptr));
+    RC(trunk_forward(w, a->tws, dev_frames + (size_t)k * n * fbytes, n, a->feats + ((long)k * c.batch) * a->HW * 512, st,
+                     a->trunk_mode ? &pk : nullptr));
   a->cur = serl_batch{};
   a->cur.batch = n;
   a->cur.state = const_cast<float*>(dev_state);
@@ -1582,7 +1668,7 @@ int serl_agent_eval_losses(serl_agent* a, const serl_batch* batch, const serl_no
   SERL_HIP(hipSetDevice(c.device));
   EvalScope scope(a);
   // serl_agent_update's encode without a slot: both sides of the batch through the trunk into the scratch slot, no binding
-  RC(trunk_pass(a, batch, a->feats, -1, kTrunkStages - 1, st));
+  if (!a->live) RC(trunk_pass(a, batch, a->feats, -1, kTrunkStages - 1, st));   // (live trunk: the phases below compute theirs)
   a->cur = *batch;
   a->has_batch = true;
   a->labelled = false; a->label_exempt = true;   // SACAgent.update keeps the stored rewards

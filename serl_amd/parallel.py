@@ -174,6 +174,12 @@ class DataParallelLearner:
         self.all_reduce = all_reduce
         self.ensemble = ensemble
         self.sched = schedule or SerialSchedule()
+        # A live trunk (AgentCore.live_trunk: weight decay on the pretrained trunk) changes at every optimizer step, so no pass
+        # can run ahead of the update before it: the core computes its passes inside the update phases, on the update stream, and
+        # only a one-slot schedule describes that.  The decay is the same arithmetic on every rank: nothing more to all-reduce.
+        if getattr(core, "live_trunk", False) and self.sched.slots != 1:
+            raise ValueError(f"the core's trunk is live (weight_decay on the pretrained trunk): its passes follow each optimizer step "
+                             f"and cannot be pipelined over {self.sched.slots} slots; use the serial schedule (schedule=None)")
         self._rng = J.create_rng(seed)   # the reference's random stream, identical on all ranks (same seed)
         self._keys = None            # keys of the call in progress
         self.image_keys = tuple(image_keys) if image_keys is not None else None
@@ -359,6 +365,10 @@ class TrunkFarmLearner(DataParallelLearner):
 
     def __init__(self, core, gather, buffers, batch_sizes, rank=0, world=2, send=None, recv=None, seed=0, ensemble=10,
                  schedule=None, image_keys=None, device_noise="hash", role=None, n_workers=None, chain_budget=None):
+        if getattr(core, "live_trunk", False):
+            # (the farm rests on features that depend on the pixels only; a live trunk's depend on every optimizer step so far)
+            raise NotImplementedError("the trunk farm needs a frozen trunk: this core's is live (weight_decay on the pretrained "
+                                      "trunk); use DataParallelLearner with the serial schedule")
         super().__init__(core, gather, buffers, batch_sizes, 0, 1, all_reduce=None, seed=seed, ensemble=ensemble,
                          schedule=schedule, image_keys=image_keys, device_noise=device_noise)
         assert world >= 2 or role is not None, "a trunk farm needs an updater and at least one worker"
