@@ -47,7 +47,7 @@ def theta_flax_paths(cfg):
     """oracle leaf name -> flax path of the reference's parameter tree (the product's export mapping: using it here also
     checks serl_amd/agents/flax_tree.py against the tree the reference really builds)."""
     from serl_amd.agents.flax_tree import theta_paths
-    prod = theta_paths(cfg.image_keys, encoder_type=cfg.encoder_type)
+    prod = theta_paths(cfg.image_keys, encoder_type=cfg.encoder_type, std_parameterization=cfg.std_parameterization)
     return {k: prod[_product_name(k, cfg.image_keys)][0] for k in O.trainable_param_shapes(cfg)}
 
 
@@ -249,20 +249,22 @@ def synth_flat_batch(cfg, B, seed):
 
 
 def run_reference(cfg: O.Config, B: int, schedule, param_seed=42, batch_seed=100, float64=True, theta_transform=None,
-                  batch_transform=None, target_transform=None):
+                  batch_transform=None, target_transform=None, leaves=None):
     """schedule: list of ("critics",), ("high_utd", utd_ratio) or ("update", (network names...)) -- the last one is
     SACAgent.update on an un-augmented batch.  cfg.image_keys == (): the state-only agent of make_sac_agent.
     theta_transform(theta, cfg) -> theta: applied to O.init_params' leaves before they are patched into the reference agent
     (params and target_params); target_transform(theta, cfg) -> theta: the target copy, from the transformed leaves;
     batch_transform(pb, step) -> pb: applied to the synthetic sample of schedule item `step`.  All three default to None = the
-    run every update_*.npz was recorded from.
+    run every update_*.npz was recorded from.  leaves: (trunk, theta) to start from in place of O.init_params' (theta is read
+    once the reference's agent exists).  The policy distribution and the MLP activations do not reach the reference through cfg:
+    a generator overrides them in the kwargs of the reference's factories and passes the launcher's Config.
     Returns dict(steps=[...], final=...)."""
     assert R.reference_available(), "/root/reference is not present"
     jax = R.install(float64)
     import jax.numpy as jnp
     from flax.core.frozen_dict import freeze
 
-    trunk, theta = O.init_params(cfg, param_seed)
+    trunk, theta = O.init_params(cfg, param_seed) if leaves is None else leaves
     if theta_transform is not None:
         theta = theta_transform(theta, cfg)
     agent = _make_reference_agent(jax, jnp, cfg, trunk)
@@ -376,3 +378,27 @@ def oracle_batch_and_noise(cfg, step, dtype):
          "action": torch.tensor(pb["action"], dtype=dtype), "reward": torch.tensor(pb["reward"], dtype=dtype),
          "mask": torch.tensor(pb["mask"], dtype=dtype)}
     return b, O.noise_to_torch(n, dtype)
+
+
+def run_step(st, step, batch, noise):
+    """One schedule item -- {"kind": "critics" | "high_utd" | "update", "utd", "nets"} as run_reference records it -- through the
+    oracle's update of that kind, on an oracle batch and torch noise -> (info, aux); aux is None for "update"."""
+    if step["kind"] == "critics":
+        return O.update_critics(st, batch, noise)
+    if step["kind"] == "high_utd":
+        return O.update_high_utd(st, batch, noise, step["utd"])
+    return O.update(st, batch, noise, step["nets"]), None
+
+
+def run_steps(st, steps, dtype, on_info=None, inputs=oracle_batch_and_noise):
+    """A recorded schedule (the "steps" of run_reference / golden_update.unpack) through the oracle, from the TrainState given
+    -> the info dict of every step.  on_info(i, step, info) is called after each step; inputs(cfg, step, dtype) -> (batch, noise)
+    for recordings whose batches are laid out otherwise."""
+    infos = []
+    for i, step in enumerate(steps):
+        b, n = inputs(st.cfg, step, dtype)
+        info, _ = run_step(st, step, b, n)
+        if on_info is not None:
+            on_info(i, step, info)
+        infos.append(info)
+    return infos

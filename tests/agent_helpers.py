@@ -32,9 +32,8 @@ def chain_fuse(fuse):
             os.environ.update(SERL_CHAIN_FUSE=old)
 
 
-def make_core(cfg: O.Config, B, *, fuse=None, trunk_mode=None, agent_seed=0, **agent_kwargs):
-    """-> the AgentCore of an oracle Config; agent_kwargs: what a Config does not hold (std_parameterization,
-    tanh_squash_distribution, critic_activation, policy_activation).  fuse: see chain_fuse."""
+def make_core(cfg: O.Config, B, *, fuse=None, trunk_mode=None, agent_seed=0):
+    """-> the AgentCore of an oracle Config, its optimizer kwargs, policy distribution and MLP activations included.  fuse: see chain_fuse."""
     from serl_amd.agents.core import AgentCore
     with chain_fuse(fuse):
         core = AgentCore(encoder_type=cfg.encoder_type, n_cam=cfg.n_cam, H=cfg.H, W=cfg.W, state_dim=cfg.S, act_dim=cfg.A, batch=B,
@@ -42,7 +41,9 @@ def make_core(cfg: O.Config, B, *, fuse=None, trunk_mode=None, agent_seed=0, **a
                          warmup_steps=cfg.warmup, dropout=cfg.dropout, std_min=cfg.std_min, std_max=cfg.std_max,
                          target_entropy=cfg.target_entropy, seed=agent_seed,
                          temp_warmup_steps=-1 if cfg.temp_warmup is None else cfg.temp_warmup,
-                         critic_subsample_size=cfg.subsample, backup_entropy=cfg.backup_entropy, **agent_kwargs)
+                         critic_subsample_size=cfg.subsample, backup_entropy=cfg.backup_entropy, optimizers=cfg.opt,
+                         std_parameterization=cfg.std_parameterization, tanh_squash_distribution=cfg.tanh_squash,
+                         critic_activation=cfg.critic_activation, policy_activation=cfg.policy_activation)
     if trunk_mode is not None:
         core.set_trunk_mode(trunk_mode)
     return core

@@ -49,13 +49,14 @@ def reference_answers(name):
     assert R.reference_available(), "the reference checkout is not present"
     jax = R.install(True)
     import jax.numpy as jnp
-    trunk, theta, target = EO.leaves(cfg, std)
+    assert (cfg.std_parameterization, cfg.tanh_squash) == (std, squash)
+    trunk, theta, target = EO.leaves(cfg)
     launcher = (std, squash) == PM.DEFAULT_MODE
     over = contextlib.nullcontext() if launcher else \
         VR.reference_create_overrides({"policy_kwargs": {"std_parameterization": std, "tanh_squash_distribution": squash}})
     with over:
         agent = RR._make_reference_agent(jax, jnp, cfg, trunk)
-    paths = RR.theta_flax_paths(cfg) if launcher else PM.flax_paths(cfg, std)
+    paths = RR.theta_flax_paths(cfg)
     assert set(paths) == set(theta) == set(target), (sorted(paths), sorted(theta))
 
     def patched(leaves):

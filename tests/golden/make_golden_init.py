@@ -206,7 +206,7 @@ def run_agent_case(cfg, B, sched):
     patch_standins()
     captured, meta = {}, {}
     trunk = product_trunk(cfg)
-    orig_make, orig_init = RR._make_reference_agent, O.init_params
+    orig_make = RR._make_reference_agent
 
     def make(jax_, jnp, cfg_, trunk_):
         jax_._core.set_float_dtype(torch.float32)           # the networks are built in float32, as JAX does
@@ -217,11 +217,11 @@ def run_agent_case(cfg, B, sched):
         captured.update(reference_leaves(agent.state.params, RR.theta_flax_paths(cfg_)))
         meta["rng"] = [int(v) & 0xFFFFFFFF for v in np.asarray(agent.state.rng).reshape(-1)]
         return agent
-    RR._make_reference_agent, O.init_params = make, lambda cfg_, seed: (trunk, captured)
+    RR._make_reference_agent = make
     try:
-        res = RR.run_reference(cfg, B, sched, SEED, BATCH_SEED)
+        res = RR.run_reference(cfg, B, sched, SEED, BATCH_SEED, leaves=(trunk, captured))
     finally:
-        RR._make_reference_agent, O.init_params = orig_make, orig_init
+        RR._make_reference_agent = orig_make
     res["prng"] = "threefry"
     rec = G.pack(res, SEED, BATCH_SEED, n_sample=N_SAMPLE)
     for name, v in captured.items():

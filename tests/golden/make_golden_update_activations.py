@@ -8,7 +8,7 @@ The launcher factories write their own network kwargs into create_states / creat
 functions are wrapped AT RUN TIME, as make_golden_update_policy.py wraps them for policy_kwargs: the wrapper overrides `activations`
 in the critic_network_kwargs / policy_network_kwargs the factory passes.  What it passes is a callable (mlp.py:19-21 takes one as it
 is) that reports every tensor it is applied to -- the pre-activations -- to a tests/mlp_activations.Recorder and then calls the
-shim's own jax.nn function of that name.  Nothing under oracle/ changes.
+shim's own jax.nn function of that name.  The run itself is given the launcher's Config: that is the cfg record of the files.
 
   act_update_sac_state_{swish,relu,mixed}.npz   S = 10, A = 5, 72 rows; high_utd 2, update, high_utd 1; mixed = critic relu, policy swish
   act_trained_sac_state_swish.npz               the same schedule from trained_regime.trained_like leaves: |pre-activation| of tens
@@ -27,6 +27,7 @@ do not start with "update_": tests/test_reference_update.py and tests/test_golde
 launcher's tanh.  tests/test_mlp_activations_{cpu,gpu}.py read these files.
 """
 import contextlib
+import dataclasses
 import os
 import sys
 
@@ -95,7 +96,9 @@ def main():
             recs = {"critic": MA.Recorder(), "policy": MA.Recorder()}
             try:
                 with reference_activations(critic, policy, recs, {w: MA.KINK_MIN for w in relu}):
-                    res = RR.run_reference(cfg, B, sched, GR.PARAM_SEED, batch_seed,
+                    assert (cfg.critic_activation, cfg.policy_activation) == (critic, policy)
+                    res = RR.run_reference(dataclasses.replace(cfg, critic_activation="tanh", policy_activation="tanh"), B, sched,
+                                           GR.PARAM_SEED, batch_seed,
                                            theta_transform=lambda th, c: MA.act_theta(th, c, regime))
             except MA.Kink as e:      # this seed is out at its first evaluation inside the margin: the next one
                 tried.append((batch_seed, e.args[0]))

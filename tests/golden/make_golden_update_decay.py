@@ -13,8 +13,8 @@ trunk leaf by 1 - sum_t lr_t * wd_t, the target copy follows by the EMA, and for
 
 Every file holds, beside what oracle.golden_update.pack records, the final online and target trunk/conv_init of the run
 (`trunk_conv_init`, `trunk_conv_init_target`; absent for the SmallEncoder).  The file names do not start with "update_":
-tests/test_reference_update.py runs every update_*.npz through the unmodified oracle, whose target critic shares the online
-trunk's features.  tests/test_pixel_weight_decay_{cpu,gpu}.py read these files.
+the fixtures of a variant family are kept apart from the update_*.npz sweep.  tests/test_pixel_weight_decay_{cpu,gpu}.py read
+these files.
 """
 import os
 import sys
@@ -25,6 +25,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.dirname(HERE))
+from oracle import drq_oracle as O  # noqa: E402
 from oracle import ref_update_runner as RR  # noqa: E402
 import golden_replay as GR  # noqa: E402
 import pixel_weight_decay as PW  # noqa: E402
@@ -41,7 +42,7 @@ def main():
         res = RR.run_reference(cfg, B, sched, GR.PARAM_SEED, GR.BATCH_SEED)
         extra, meta = {}, {"decay": PW.DECAY}
         if not cfg.small:
-            trunk, _ = PW.O.init_params(cfg, GR.PARAM_SEED)
+            trunk, _ = O.init_params(cfg, GR.PARAM_SEED)
             p0 = trunk["trunk/conv_init"].astype(np.float64).reshape(-1)
             extra = {"trunk_conv_init": res["final"]["trunk_conv_init"], "trunk_conv_init_target": res["final"]["trunk_conv_init_target"]}
             big = np.abs(p0) > 1e-3 * np.abs(p0).max()

@@ -5,9 +5,10 @@ with a policy distribution other than the launcher's ("exp" + tanh).  Run in the
 
 The launcher factories write their own policy_kwargs into create_states / create_drq (utils/launcher.py:50-116), so the two create
 functions are wrapped AT RUN TIME, as make_golden_update_widths.py wraps them for hidden_dims: the wrapper overrides
-std_parameterization / tanh_squash_distribution in the `policy_kwargs` the factory passes.  For "uniform" the run's leaf table
-(oracle.ref_update_runner.theta_flax_paths, looked up at run time) is replaced by tests/policy_modes.flax_paths: no
-modules_actor/Dense_1, and ("modules_actor", "log_stds") instead.  Nothing under oracle/ changes.
+std_parameterization / tanh_squash_distribution in the `policy_kwargs` the factory passes.  The run itself is given the launcher's
+Config (its recipes start from the launcher's leaves, and that is the cfg record of the files); the run's leaf table
+(oracle.ref_update_runner.theta_flax_paths, looked up at run time) is the one of the mode's Config: for "uniform" no
+modules_actor/Dense_1, and ("modules_actor", "log_stds") instead.
 
   policy_update_sac_state_{softplus,gauss,uniform,uniform_gauss}.npz   S = 10, A = 5, 72 rows; high_utd 2, update, high_utd 1
   policy_update_drq_uniform.npz                                        one camera 64x64, S = 5, A = 3, 6 rows; critics, high_utd 2
@@ -23,6 +24,7 @@ The file names do not start with "update_": tests/test_reference_update.py and t
 update_*.npz through the launcher's distribution.  tests/test_policy_modes_{cpu,gpu}.py read these files.
 """
 import contextlib
+import dataclasses
 import os
 import sys
 
@@ -32,6 +34,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.dirname(HERE))
+from oracle import drq_oracle as O  # noqa: E402
 from oracle import ref_update_runner as RR  # noqa: E402
 import golden_replay as GR  # noqa: E402
 import policy_modes as PM  # noqa: E402
@@ -55,7 +58,7 @@ def reference_policy(cfg, std, squash, stddevs):
             return dist
         SACAgent.forward_policy = forward_policy
         paths = RR.theta_flax_paths
-        RR.theta_flax_paths = lambda c: PM.flax_paths(c, std)
+        RR.theta_flax_paths = lambda c: paths(cfg)
         try:
             yield
         finally:
@@ -91,10 +94,11 @@ def main():
         os.environ.pop("SERL_JAXSHIM_PRNG", None)
         stddevs = []
         with reference_policy(cfg, std, squash, stddevs):
-            res = RR.run_reference(cfg, B, sched, GR.PARAM_SEED, GR.BATCH_SEED,
-                                   theta_transform=lambda th, c: PM.mode_theta(th, c, std, regime))
+            res = RR.run_reference(dataclasses.replace(cfg, std_parameterization="exp", tanh_squash=True), B, sched, GR.PARAM_SEED,
+                                   GR.BATCH_SEED, theta_transform=lambda th, c: PM.mode_theta(th, c, std, regime))
         holds = check_tree(res["final"]["param_tree"], std)
-        assert set(res["final"]["params"]) == set(PM.leaf_names(cfg, std))
+        assert (cfg.std_parameterization, cfg.tanh_squash) == (std, squash)
+        assert set(res["final"]["params"]) == set(O.trainable_param_shapes(cfg))
         assert stddevs and all(s.shape[-1] == cfg.A for s in stddevs)
         meta = {"std_parameterization": std, "tanh_squash_distribution": squash, "regime": regime, "std_leaves": holds,
                 "transform": "policy_modes.mode_theta", "log_stds_seed": PM.LOG_STDS_SEED, "clip_cycle": list(PM.CLIP_CYCLE),

@@ -4,6 +4,7 @@ act_*): the agent built as the reference's create functions were called, the ref
 function, and the loader of a variant file.
 Tolerance: the north star's 1e-4 (info scalars; Adam moments = running gradient averages, per leaf relative to the leaf's max;
 parameters: 99.9th percentile within 1e-4 and every element within the Adam sign-flip bound)."""
+import dataclasses
 import os
 
 import numpy as np
@@ -29,15 +30,24 @@ def variant_path(prefix, name):
 
 
 def load_variant(prefix, name):
-    """-> (G.unpack of tests/golden/<prefix>_<name>.npz, its meta, the npz)"""
+    """-> (G.unpack of tests/golden/<prefix>_<name>.npz, its meta, the npz).  The files' own cfg record is the launcher's; the
+    mode a variant was recorded in stands in its meta block (meta["policy"], meta["activations"]) and is laid over g["cfg"] here,
+    so that the oracle and AH.make_core read it from the Config like every other option."""
     z = np.load(variant_path(prefix, name))
     g = G.unpack(z)
-    return g, g["meta"], z
+    meta, mode = g["meta"], {}
+    if "policy" in meta:
+        mode.update(std_parameterization=meta["policy"]["std_parameterization"], tanh_squash=meta["policy"]["tanh_squash_distribution"])
+    if "activations" in meta:
+        mode.update(critic_activation=meta["activations"]["critic"], policy_activation=meta["activations"]["policy"])
+    g["cfg"] = dataclasses.replace(g["cfg"], **mode)
+    return g, meta, z
 
 
 def initial_leaves(cfg, transform):
-    """-> (trunk, theta) a variant fixture's run started from, oracle names; transform(theta, cfg): the family's"""
-    trunk, theta = O.init_params(cfg, PARAM_SEED)
+    """-> (trunk, theta) a variant fixture's run started from, oracle names; transform(theta, cfg): the family's recipe, which
+    takes the leaves of the launcher's policy (the log-std Dense is there whatever cfg.std_parameterization says)"""
+    trunk, theta = O.init_params(dataclasses.replace(cfg, std_parameterization="exp"), PARAM_SEED)
     return trunk, transform(theta, cfg)
 
 
@@ -99,15 +109,13 @@ def check_draws(agent, cfg, B, step, want, want_crops):
                 assert np.array_equal(nb[name][ci].cpu().numpy(), np.asarray(want[name][cam], np.uint8)), (name, cam)
 
 
-def replay(agent, g, *, leaf_names=None, seed_only=False, label):
+def replay(agent, g, *, seed_only=False, label):
     """The recorded schedule of a reference golden (G.unpack) through an agent that holds the run's initial parameters, then the
-    final state against the recorded one.  leaf_names: the trainable leaves to compare, oracle names (default: those of the
-    Config; a "uniform" policy has others).  seed_only: a golden recorded under the reference's own threefry stream -- nothing is
-    injected, the agent runs FROM THE SEED and must draw what the reference drew: integers bit for bit, normals to the float32
+    final state against the recorded one, over the trainable leaves of the Config (a "uniform" policy has its own).  seed_only: a
+    golden recorded under the reference's own threefry stream -- nothing is injected, the agent runs FROM THE SEED and must draw what the reference drew: integers bit for bit, normals to the float32
     erf_inv formula's 1e-5; otherwise the recorded crop offsets / eps / dropout masks / REDQ indices are injected."""
     cfg, B, meta = g["cfg"], g["B"], g["meta"]
-    if leaf_names is None:
-        leaf_names = list(O.trainable_param_shapes(cfg))
+    leaf_names = list(O.trainable_param_shapes(cfg))
     if seed_only:
         assert agent.rng_impl == "threefry"
         assert [int(v) for v in agent.state.rng] == meta["rng0"], "state.rng after create differs from the reference's"

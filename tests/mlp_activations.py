@@ -1,10 +1,8 @@
 """Shared by tests/test_mlp_activations_cpu.py, tests/test_mlp_activations_gpu.py and tests/golden/make_golden_update_activations.py:
 the activations of the critic's and the policy's MLP beside the launcher's tanh (networks/mlp.py:19-31; the critic_act / policy_act
-arguments of serl_agent_create_mlp), the table of the act_*.npz fixtures, the parameters each fixture's run starts from, and a
-float64 restatement of the two MLPs that takes the activation as a parameter: oracle.drq_oracle's policy_head and critic_forward,
-replaced at run time (`oracle_activations`), so that the oracle's own update code -- and autograd for the backward -- runs on it."""
-import contextlib
-
+arguments of serl_agent_create_mlp), the table of the act_*.npz fixtures, the parameters each fixture's run starts from, and the
+Recorder of pre-activations behind the relu kink condition.  The activations themselves are stated in oracle/drq_oracle.py
+(Config.critic_activation / policy_activation, ACTIVATIONS); a Recorder sees them through O.observe_preactivations."""
 import numpy as np
 import torch
 
@@ -15,7 +13,6 @@ import trained_regime as TR
 KINK_MIN = 1e-4        # the smallest |pre-activation| a relu comparison may contain (see `Recorder`)
 KINK_SEEDS = 10
 
-TORCH_ACT = {"tanh": torch.tanh, "relu": torch.relu, "swish": lambda x: x * torch.sigmoid(x)}
 NEW_ACTS = ("swish", "relu")
 
 
@@ -24,15 +21,19 @@ def network_kwargs(act, h=256):
     return {"activations": act, "use_layer_norm": True, "hidden_dims": [h, h]}
 
 
-# name -> (oracle Config, rows, schedule, (critic activation, policy activation), regime, sampled elements per large leaf).
-# State-only: golden_replay's shared shape.
+def _row(critic, policy, rows, sched, regime, **kw):
+    return O.Config(critic_activation=critic, policy_activation=policy, **kw), rows, sched, (critic, policy), regime, 1024
+
+
+# name -> (oracle Config, rows, schedule, (critic activation, policy activation), regime, sampled elements per large leaf).  The
+# Config carries the activations; the pair repeats them for the check against a file's meta block.  State-only: golden_replay's
+# shared shape.
 GOLDEN = {
-    "update_sac_state_swish": (O.Config(warmup=2000, **GR.STATE), 72, GR.STATE_SCHED, ("swish", "swish"), "init", 1024),
-    "update_sac_state_relu": (O.Config(warmup=2000, **GR.STATE), 72, GR.STATE_SCHED, ("relu", "relu"), "kink_margin", 1024),
-    "update_sac_state_mixed": (O.Config(warmup=2000, **GR.STATE), 72, GR.STATE_SCHED, ("relu", "swish"), "kink_margin", 1024),
-    "trained_sac_state_swish": (O.Config(warmup=4, **GR.STATE), 72, GR.STATE_SCHED, ("swish", "swish"), "trained", 1024),
-    "update_drq_swish": (O.Config(image_keys=("image",), H=64, W=64, S=5, A=3), 6, [("critics",), ("high_utd", 2)],
-                         ("swish", "swish"), "init", 1024),
+    "update_sac_state_swish": _row("swish", "swish", 72, GR.STATE_SCHED, "init", warmup=2000, **GR.STATE),
+    "update_sac_state_relu": _row("relu", "relu", 72, GR.STATE_SCHED, "kink_margin", warmup=2000, **GR.STATE),
+    "update_sac_state_mixed": _row("relu", "swish", 72, GR.STATE_SCHED, "kink_margin", warmup=2000, **GR.STATE),
+    "trained_sac_state_swish": _row("swish", "swish", 72, GR.STATE_SCHED, "trained", warmup=4, **GR.STATE),
+    "update_drq_swish": _row("swish", "swish", 6, [("critics",), ("high_utd", 2)], "init", image_keys=("image",), H=64, W=64, S=5, A=3),
 }
 
 
@@ -128,56 +129,3 @@ class Recorder:
     @property
     def kink_free(self):
         return bool(self.min_abs) and min(self.min_abs) >= KINK_MIN
-
-
-# ---- float64 restatement of the two MLPs -----------------------------------------------------------------------------------------
-def policy_features(th, enc, act):
-    """the policy's two LayerNorm + activation layers -> h2 (mlp.py:19-31)"""
-    h = act(O.layer_norm(enc @ th["actor/w1"] + th["actor/b1"], th["actor/ln1/scale"], th["actor/ln1/bias"]))
-    return act(O.layer_norm(h @ th["actor/w2"] + th["actor/b2"], th["actor/ln2/scale"], th["actor/ln2/bias"]))
-
-
-def policy_head(th, cfg, enc, act):
-    """O.policy_head (exp std, the launcher's) with the MLP's activation given -> (mean, clipped std)"""
-    h = policy_features(th, enc, act)
-    mean = h @ th["actor/mean/kernel"] + th["actor/mean/bias"]
-    log_std = h @ th["actor/logstd/kernel"] + th["actor/logstd/bias"]
-    return mean, torch.clamp(torch.exp(log_std), cfg.std_min, cfg.std_max)
-
-
-def critic_forward(th, cfg, enc, action, act):
-    """O.critic_forward with the MLP's activation given -> Q [ensemble, B]"""
-    x = torch.cat([enc, action], dim=-1)
-    h = torch.einsum("bi,eio->ebo", x, th["critic/w1"]) + th["critic/b1"][:, None, :]
-    h = act(O.layer_norm(h, th["critic/ln1/scale"][:, None, :], th["critic/ln1/bias"][:, None, :]))
-    h = torch.einsum("ebi,eio->ebo", h, th["critic/w2"]) + th["critic/b2"][:, None, :]
-    h = act(O.layer_norm(h, th["critic/ln2/scale"][:, None, :], th["critic/ln2/bias"][:, None, :]))
-    if cfg.state_only:
-        return torch.einsum("ebi,eio->ebo", h, th["critic/head/kernel"]).squeeze(-1) + th["critic/head/bias"][:, None]
-    return (h @ th["critic/head/kernel"]).squeeze(-1) + th["critic/head/bias"]
-
-
-def recorded(name, rec):
-    """TORCH_ACT[name] reporting every pre-activation tensor to the Recorder"""
-    fn = TORCH_ACT[name]
-
-    def act(x):
-        rec.see(x)
-        return fn(x)
-    return act
-
-
-@contextlib.contextmanager
-def oracle_activations(critic, policy, recs=None):
-    """oracle.drq_oracle with the critic's MLP on activation `critic` and the policy's on `policy` (names of TORCH_ACT): its
-    policy_head / critic_forward replaced for the duration, so update_critics / update_high_utd / update run on them.
-    recs: {"critic": Recorder, "policy": Recorder} that see every pre-activation of their network."""
-    ca = recorded(critic, recs["critic"]) if recs else TORCH_ACT[critic]
-    pa = recorded(policy, recs["policy"]) if recs else TORCH_ACT[policy]
-    saved = O.policy_head, O.critic_forward
-    O.policy_head = lambda th, cfg, enc: policy_head(th, cfg, enc, pa)
-    O.critic_forward = lambda th, cfg, enc, action: critic_forward(th, cfg, enc, action, ca)
-    try:
-        yield
-    finally:
-        O.policy_head, O.critic_forward = saved

@@ -14,6 +14,8 @@ gradients and its preset first moment share one sign (sign_pattern), so b1*mu + 
 roundings of that expression stay three roundings of the result; a preset nu is exactly zero only where mu is and where the
 element's gradients are exact zeros too (the state of an element that never saw a gradient), so that no second moment is a
 float32 denormal other than an exact zero."""
+import dataclasses
+
 import numpy as np
 import torch
 
@@ -24,7 +26,7 @@ STATE = dict(image_keys=(), discount=0.99)
 PIX = dict(H=32, W=32)
 LOG_STDS_SEED = 17
 
-# (id, oracle Config kwargs, AgentCore kwargs beyond the Config's).  B = 4 everywhere; no update runs.
+# (id, oracle Config kwargs, those of them that leave the launcher's policy).  B = 4 everywhere; no update runs.
 LAYOUTS = [
     ("state_w64_A1_S3_E3", dict(STATE, S=3, A=1, hidden=64, ensemble=3), {}),
     ("state_w64_A4_S4_E4", dict(STATE, S=4, A=4, hidden=64, ensemble=4), {}),
@@ -45,29 +47,15 @@ BOUNDARIES = ("Pc", "Pa0", "Pa1", "P-1")
 
 
 def layout_config(case):
-    """-> (oracle Config, AgentCore kwargs)"""
+    """-> (oracle Config, the case's third entry)"""
     _, ckw, akw = case
-    akw = dict(akw)
-    cfg = O.Config(**ckw)
-    if cfg.opt:
-        akw["optimizers"] = cfg.opt
-    return cfg, akw
+    return O.Config(**ckw, **akw), dict(akw)
 
 
 def layout_shapes(case):
     """{leaf (oracle name): shape} in arena order, from O.trainable_param_shapes alone (a "uniform" policy has actor/log_stds
     [A] where the others have the log-std Dense: actor_critic_nets.py:205-214)"""
-    cfg, akw = layout_config(case)
-    sh = dict(O.trainable_param_shapes(cfg))
-    if akw.get("std_parameterization") == "uniform":
-        out = {}
-        for k, v in sh.items():
-            if k == "actor/logstd/kernel":
-                out["actor/log_stds"] = (cfg.A,)
-            elif k != "actor/logstd/bias":
-                out[k] = v
-        sh = out
-    return sh
+    return dict(O.trainable_param_shapes(layout_config(case)[0]))
 
 
 def slices_of(shapes):
@@ -113,12 +101,10 @@ def support(shapes):
 def layout_theta(case, seed):
     """-> (trunk, theta) float32, oracle names: O.init_params at `seed` (unit-sized LayerNorm scales, small kernels, perturbed
     biases), actor/log_stds for a uniform policy"""
-    cfg, akw = layout_config(case)
+    cfg, _ = layout_config(case)
     trunk, theta = O.init_params(cfg, seed)
-    if akw.get("std_parameterization") == "uniform":
-        theta = {k: v for k, v in theta.items() if not k.startswith("actor/logstd/")}
+    if "actor/log_stds" in theta:      # (the reference's zeros would leave std = 1 in every column)
         theta["actor/log_stds"] = np.random.default_rng(LOG_STDS_SEED + seed).uniform(-1.5, 0.5, cfg.A).astype(np.float32)
-        theta = {k: theta[k] for k in layout_shapes(case)}
     return trunk, theta
 
 
@@ -161,13 +147,7 @@ class Pair:
 
     def __init__(self, case, B=4, presets=True, seed=42, cfg_override=None):
         self.case = case
-        self.cfg, akw = layout_config(case)
-        if cfg_override:
-            for k, v in cfg_override.items():
-                setattr(self.cfg, k, v)
-            if self.cfg.opt:
-                akw["optimizers"] = self.cfg.opt
-        cfg = self.cfg
+        self.cfg = cfg = dataclasses.replace(layout_config(case)[0], **(cfg_override or {}))
         self.shapes = layout_shapes(case)
         self.sl, self.P = slices_of(self.shapes)
         self.b = boundaries(self.shapes)
@@ -177,7 +157,7 @@ class Pair:
         _, target = layout_theta(case, seed + 1)
         self.st = O.TrainState(cfg, trunk, theta)
         self.st.target = O.to_torch(target, torch.float64)
-        self.core = AH.make_core(cfg, B, **akw)
+        self.core = AH.make_core(cfg, B)
         AH.load_leaves(self.core, cfg, trunk, theta, target)
         self.sign = sign_pattern(self.P)
         self.zero, self.tiny = zero_pattern(self.P)

@@ -1,14 +1,11 @@
 """Shared by tests/test_policy_modes_cpu.py, tests/test_policy_modes_gpu.py and tests/golden/make_golden_update_policy.py: the
 policy distributions beside the launcher's (std_parameterization "exp" / "softplus" / "uniform" x tanh_squash_distribution True /
-False; the std_param / no_tanh arguments of serl_agent_create_policy), the table of the policy_*.npz fixtures, the parameters each fixture's run starts from,
-and a float64 restatement of the policy head (actor_critic_nets.py:189-227, distrax MultivariateNormalDiag [+ Tanh])."""
-import math
-
+False; the std_param / no_tanh arguments of serl_agent_create_policy), the table of the policy_*.npz fixtures and the parameters each
+fixture's run starts from.  The distributions themselves are stated in oracle/drq_oracle.py (Config.std_parameterization /
+tanh_squash: policy_head, sample_and_log_prob, trainable_param_shapes)."""
 import numpy as np
-import torch
 
 from oracle import drq_oracle as O
-import agent_helpers as AH
 import golden_replay as GR
 import trained_regime as TR
 
@@ -31,23 +28,31 @@ def policy_kwargs(std, squash):
 # by a few tenths: the bias decides.
 CLIP_CYCLE = (-14.0, -3.0, 0.5, 7.0)
 
-# name -> (oracle Config, rows, schedule, (std, squash), regime, sampled elements per large leaf).  State-only: golden_replay's
-# shared shape.  The pixel case is create_drq's own default pair.
+def mode_config(std, squash, **kw):
+    return O.Config(std_parameterization=std, tanh_squash=squash, **kw)
+
+
+def _row(std, squash, rows, sched, regime, **kw):
+    return mode_config(std, squash, **kw), rows, sched, (std, squash), regime, 1024
+
+
+# name -> (oracle Config, rows, schedule, (std, squash), regime, sampled elements per large leaf).  The Config carries the mode; the
+# pair repeats it for the check against a file's meta block.  State-only: golden_replay's shared shape.  The pixel case is
+# create_drq's own default pair.
 GOLDEN = {
-    "update_sac_state_softplus": (O.Config(warmup=2000, **GR.STATE), 72, GR.STATE_SCHED, ("softplus", True), "init", 1024),
-    "update_sac_state_gauss": (O.Config(warmup=2000, **GR.STATE), 72, GR.STATE_SCHED, ("exp", False), "init", 1024),
-    "update_sac_state_uniform": (O.Config(warmup=2000, **GR.STATE), 72, GR.STATE_SCHED, ("uniform", True), "init", 1024),
-    "update_sac_state_uniform_gauss": (O.Config(warmup=2000, **GR.STATE), 72, GR.STATE_SCHED, ("uniform", False), "init", 1024),
-    "update_drq_uniform": (O.Config(image_keys=("image",), H=64, W=64, S=5, A=3), 6, [("critics",), ("high_utd", 2)],
-                           ("uniform", True), "init", 1024),
-    "trained_sac_state_softplus": (O.Config(warmup=4, **GR.STATE), 72, GR.STATE_SCHED, ("softplus", True), "trained", 1024),
-    "trained_sac_state_uniform": (O.Config(warmup=4, **GR.STATE), 72, GR.STATE_SCHED, ("uniform", True), "trained", 1024),
+    "update_sac_state_softplus": _row("softplus", True, 72, GR.STATE_SCHED, "init", warmup=2000, **GR.STATE),
+    "update_sac_state_gauss": _row("exp", False, 72, GR.STATE_SCHED, "init", warmup=2000, **GR.STATE),
+    "update_sac_state_uniform": _row("uniform", True, 72, GR.STATE_SCHED, "init", warmup=2000, **GR.STATE),
+    "update_sac_state_uniform_gauss": _row("uniform", False, 72, GR.STATE_SCHED, "init", warmup=2000, **GR.STATE),
+    "update_drq_uniform": _row("uniform", True, 6, [("critics",), ("high_utd", 2)], "init", image_keys=("image",), H=64, W=64, S=5, A=3),
+    "trained_sac_state_softplus": _row("softplus", True, 72, GR.STATE_SCHED, "trained", warmup=4, **GR.STATE),
+    "trained_sac_state_uniform": _row("uniform", True, 72, GR.STATE_SCHED, "trained", warmup=4, **GR.STATE),
 }
 STD_DENSE = ("actor/logstd/kernel", "actor/logstd/bias")
 
 
 def mode_theta(theta, cfg, std, regime):
-    """O.init_params' leaves -> the leaves a fixture's run starts from (oracle names), float32.  "trained": trained_regime.trained_like
+    """O.init_params' leaves of the launcher's ("exp") policy -> the leaves a fixture's run starts from (oracle names), float32.  "trained": trained_regime.trained_like
     (lagrange 0.5) with CLIP_CYCLE on the log-std bias.  "uniform": no log-std Dense; actor/log_stds = CLIP_CYCLE ("trained"), or
     seeded values in [-1.5, 0.5) ("init": the reference's zeros would leave std = 1 in every column)."""
     out = {k: np.array(v, np.float32) for k, v in theta.items()}
@@ -65,22 +70,6 @@ def mode_theta(theta, cfg, std, regime):
     return out
 
 
-def leaf_names(cfg, std):
-    """the trainable leaves (oracle names) of an agent with this std parameterisation, in arena order"""
-    names = [k for k in O.trainable_param_shapes(cfg)]
-    if std == "uniform":
-        i = names.index(STD_DENSE[0])
-        names[i:i + 2] = ["actor/log_stds"]
-    return names
-
-
-def flax_paths(cfg, std):
-    """oracle leaf name -> flax path, from the product's mapping (what oracle.ref_update_runner.theta_flax_paths does for "exp")"""
-    from serl_amd.agents.flax_tree import theta_paths
-    prod = theta_paths(cfg.image_keys, encoder_type=cfg.encoder_type, std_parameterization=std)
-    return {k: prod[AH.product_name(k, cfg.image_keys)][0] for k in leaf_names(cfg, std)}
-
-
 def initial_leaves(name):
     """-> (trunk, theta) the run of fixture `name` started from, oracle names"""
     cfg, _, _, (std, _), regime, _ = GOLDEN[name]
@@ -93,31 +82,3 @@ def tree_has(tree, path):
             return False
         tree = tree[k]
     return True
-
-
-# ---- float64 restatement of the head ------------------------------------------------------------------------------------------
-def mlp_features(th, cfg, enc):
-    """the policy's two LayerNorm + tanh layers -> h2"""
-    h = torch.tanh(O.layer_norm(enc @ th["actor/w1"] + th["actor/b1"], th["actor/ln1/scale"], th["actor/ln1/bias"]))
-    return torch.tanh(O.layer_norm(h @ th["actor/w2"] + th["actor/b2"], th["actor/ln2/scale"], th["actor/ln2/bias"]))
-
-
-def head(th, cfg, enc, std):
-    """-> (mean, clipped std) [B, A] in the dtype of th"""
-    h = mlp_features(th, cfg, enc)
-    mean = h @ th["actor/mean/kernel"] + th["actor/mean/bias"]
-    if std == "uniform":
-        raw = torch.exp(th["actor/log_stds"]).expand_as(mean)
-    else:
-        pre = h @ th["actor/logstd/kernel"] + th["actor/logstd/bias"]
-        raw = torch.nn.functional.softplus(pre) if std == "softplus" else torch.exp(pre)
-    return mean, torch.clamp(raw, cfg.std_min, cfg.std_max)
-
-
-def sample_and_log_prob(mean, sd, eps, squash):
-    """-> (action, log pi): a = tanh(u) or u, u = mean + sd eps; the tanh's log-determinant only when squashed"""
-    u = mean + sd * eps
-    lp = (-0.5 * eps * eps - torch.log(sd) - 0.5 * math.log(2.0 * math.pi)).sum(-1)
-    if not squash:
-        return u, lp
-    return torch.tanh(u), lp - (2.0 * (math.log(2.0) - u - torch.nn.functional.softplus(-2.0 * u))).sum(-1)

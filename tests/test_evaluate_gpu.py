@@ -20,6 +20,7 @@ std 4.3e-7, mode 6.6e-7; log_prob 1.3e-6 per row (softplus + tanh, A = 1, n = 64
 the worst fp32 yardstick of any case is 1.8e-6, so the bound is its floor of 1e-4 everywhere.  Against the goldens: q 1.9e-7,
 q_target 1.3e-7, mean / std / mode 1.1e-7, log_prob 2.1e-7.  evaluate_losses against the oracle: worst 1.0e-6 (entropy, one camera)."""
 import ctypes as C
+import dataclasses
 import itertools
 
 import numpy as np
@@ -45,22 +46,21 @@ def _dev(a):
     return torch.tensor(np.ascontiguousarray(a), device="cuda")
 
 
-def _state_cfg(A, hidden, ensemble):
-    return O.Config(image_keys=(), S=10, A=A, ensemble=ensemble, discount=0.99, hidden=hidden, warmup=4, temp_warmup=0)
+def _state_cfg(A, hidden, ensemble, std="exp", squash=True):
+    return PM.mode_config(std, squash, image_keys=(), S=10, A=A, ensemble=ensemble, discount=0.99, hidden=hidden, warmup=4, temp_warmup=0)
 
 
-def _leaves(cfg, std, regime):
+def _leaves(cfg, regime):
     """-> (trunk, theta, target): "init" = O.init_params (std in its usual range, nothing clips), "trained" = whole std columns on
     both clips (trained_regime.clip_columns); the target copy differs in both"""
-    trunk, theta = O.init_params(cfg, 42)
-    theta = PM.mode_theta(theta, cfg, std, regime)       # "trained": policy_modes.CLIP_CYCLE clips exp and softplus on both sides
+    trunk, theta = O.init_params(dataclasses.replace(cfg, std_parameterization="exp"), 42)
+    theta = PM.mode_theta(theta, cfg, cfg.std_parameterization, regime)       # "trained": policy_modes.CLIP_CYCLE clips exp and softplus on both sides
     return trunk, theta, TR.perturb_target(theta, cfg)
 
 
-def _core(cfg, B, std, squash, leaves, fuse=None):
+def _core(cfg, B, leaves, fuse=None):
     trunk, theta, target = leaves
-    core = AH.make_core(cfg, B, fuse=fuse, std_parameterization=std, tanh_squash_distribution=squash)
-    return AH.load_leaves(core, cfg, trunk, theta, target)
+    return AH.load_leaves(AH.make_core(cfg, B, fuse=fuse), cfg, trunk, theta, target)
 
 
 def _check(label, got, ref64, err32):
@@ -98,13 +98,13 @@ SWEEP = [
 @pytest.mark.parametrize("case", SWEEP, ids=[c[0] for c in SWEEP])
 def test_state_only_against_the_restatement(gpu, case):
     name, A, ens, hidden, std, squash, regime = case
-    cfg, B = _state_cfg(A, hidden, ens), 72
-    lv = _leaves(cfg, std, regime)
-    core = _core(cfg, B, std, squash, lv)
+    cfg, B = _state_cfg(A, hidden, ens, std, squash), 72
+    lv = _leaves(cfg, regime)
+    core = _core(cfg, B, lv)
     rng = np.random.default_rng(5)
     state = rng.standard_normal((B, cfg.S)).astype(np.float32)
     act = EO.scaled_actions(rng.uniform(-1, 1, (B, A)))
-    ref64, err32 = EO.log_prob_yardstick(cfg, *lv, {}, state, act, std, squash)       # once, for all row counts (rows are independent)
+    ref64, err32 = EO.log_prob_yardstick(cfg, *lv, {}, state, act)       # once, for all row counts (rows are independent)
     if regime == "trained":
         lo, _, hi = TR.clip_columns(cfg)
         assert (ref64["std"][:, lo] == cfg.std_min).all() and (ref64["std"][:, hi] == cfg.std_max).all() and len(lo) and len(hi)
@@ -117,18 +117,18 @@ def test_state_only_against_the_restatement(gpu, case):
         a1 = act[:5].copy()
         a1[2, 0], a1[4, A - 1] = 1.0, -1.0
         got = core.eval_policy(None, _dev(state[:5]), _dev(a1))["log_prob"].cpu().numpy()
-        ref = EO.evaluate(cfg, *lv, {}, state[:5], a1, torch.float64, std, squash)["log_prob"]
+        ref = EO.evaluate(cfg, *lv, {}, state[:5], a1, torch.float64)["log_prob"]
         assert (~np.isfinite(got)).tolist() == (~np.isfinite(ref)).tolist() == [False, False, True, False, True]
 
 
 def test_one_camera_resnet_against_the_restatement(gpu):
     name = "drq_one_cam"
-    cfg, B, (std, squash) = EO.GOLDEN[name]
-    lv = EO.leaves(cfg, std)
-    core = _core(cfg, B, std, squash, lv)
+    cfg, B, _ = EO.GOLDEN[name]
+    lv = EO.leaves(cfg)
+    core = _core(cfg, B, lv)
     pb = EO.golden_inputs(name)
     frames = {k: v[:, 0] for k, v in pb["frames"].items()}
-    ref64, err32 = EO.log_prob_yardstick(cfg, *lv, frames, pb["state"][:, 0], pb["action"], std, squash)
+    ref64, err32 = EO.log_prob_yardstick(cfg, *lv, frames, pb["state"][:, 0], pb["action"])
     f = _dev(np.stack([frames[k] for k in cfg.image_keys]))
     for n in (B, 1, 5):
         got = _core_eval(core, f[:, :n].contiguous(), _dev(pb["state"][:n, 0]), _dev(pb["action"][:n]))
@@ -147,7 +147,7 @@ def test_small_encoder_stack_of_two_against_the_restatement(gpu):
     frames = rng.integers(0, 256, (B, T, cfg.H, cfg.W, 3), dtype=np.uint8)
     state = rng.standard_normal((B, cfg.S)).astype(np.float32)
     act = EO.scaled_actions(rng.uniform(-1, 1, (B, cfg.A)))
-    ref64, err32 = EO.log_prob_yardstick(cfg, {}, theta, target, {"wrist": SO.fold(frames)}, state, act, "exp", True)
+    ref64, err32 = EO.log_prob_yardstick(cfg, {}, theta, target, {"wrist": SO.fold(frames)}, state, act)
     for n in (B, 3):
         got = _core_eval(core, _dev(frames[None, :n]), _dev(state[:n]), _dev(act[:n]))
         _check(f"small T=2 n={n}", got, {k: (v[:, :n] if k in ("q", "q_target") else v[:n]) for k, v in ref64.items()}, err32)
@@ -157,7 +157,7 @@ def test_small_encoder_stack_of_two_against_the_restatement(gpu):
 def _golden_agent(name, B=None):
     cfg, rows, (std, squash) = EO.GOLDEN[name]
     agent = GR.reference_agent(cfg, B or rows, policy_kwargs=PM.policy_kwargs(std, squash))
-    AH.load_leaves(agent.core, cfg, *EO.leaves(cfg, std))
+    AH.load_leaves(agent.core, cfg, *EO.leaves(cfg))
     return cfg, agent
 
 
@@ -197,9 +197,9 @@ def test_mode_is_the_argmax_action_bit_for_bit(gpu, name):
 
 @pytest.mark.parametrize("std,squash", [("exp", True), ("softplus", False), ("uniform", True)])
 def test_std_is_the_std_of_an_update_on_the_same_rows_bit_for_bit(gpu, std, squash):
-    cfg, B = _state_cfg(5, 256, 2), 9
-    lv = _leaves(cfg, std, "trained")
-    core = _core(cfg, B, std, squash, lv)
+    cfg, B = _state_cfg(5, 256, 2, std, squash), 9
+    lv = _leaves(cfg, "trained")
+    core = _core(cfg, B, lv)
     b = AH.synth_batch(cfg, B, seed=2)
     db = AH.batch_to_device(cfg, b)
     mine = core.eval_policy(None, db.state[0], None)["std"].cpu().numpy()
@@ -415,7 +415,7 @@ def test_refusals(gpu):
     from serl_amd import _lib
     from serl_amd._lib import SerlError
     cfg, B = _state_cfg(4, 256, 2), 8
-    core = _core(cfg, B, "exp", True, _leaves(cfg, "exp", "init"))
+    core = _core(cfg, B, _leaves(cfg, "init"))
     s, a = torch.zeros((B + 1, cfg.S), device="cuda"), torch.zeros((B + 1, cfg.A), device="cuda")
     with pytest.raises(SerlError, match=r"n 9 not in \[1,8\]"):
         core.eval_q(None, s, a)
@@ -441,8 +441,8 @@ def test_c_abi_with_raw_device_pointers(gpu):
     from serl_amd import _lib
     from serl_amd._lib_agent import SerlInfo
     cfg, B, n = _state_cfg(4, 256, 2), 8, 5
-    lv = _leaves(cfg, "exp", "init")
-    core = _core(cfg, B, "exp", True, lv)
+    lv = _leaves(cfg, "init")
+    core = _core(cfg, B, lv)
     L, h = _lib.lib(), core._h
     b = AH.synth_batch(cfg, B, seed=1)
     b["action"] = EO.scaled_actions(b["action"])

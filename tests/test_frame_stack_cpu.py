@@ -16,6 +16,7 @@ import pytest
 import torch
 
 from oracle import drq_oracle as O
+from oracle import ref_update_runner as RR
 import stacked_oracle as SO
 from test_reference_update import F64_TOL
 
@@ -43,19 +44,16 @@ def test_fp64_restatement_reproduces_the_reference_at_num_stack_2(golden):
     g = golden
     cfg, T = g["cfg"], g["T"]
     st = SO.train_state(cfg, T, g["meta"]["param_seed"])
-    for i, step in enumerate(g["steps"]):
+    def folded(cfg, step, dtype):      # channel-folded frames, cropped with the step's B*T offsets per stream
         n = step["noise"]
         fr = SO.cropped(cfg, T, step["batch"], n.get("crop_obs"), n.get("crop_next"))
-        b, tn = SO.oracle_batch(cfg, T, step["batch"], fr), O.noise_to_torch(n, torch.float64)
-        if step["kind"] == "critics":
-            info, _ = O.update_critics(st, b, tn)
-        elif step["kind"] == "high_utd":
-            info, _ = O.update_high_utd(st, b, tn, step["utd"])
-        else:
-            info = O.update(st, b, tn, step["nets"])
+        return SO.oracle_batch(cfg, T, step["batch"], fr), O.noise_to_torch(n, dtype)
+
+    def check(i, step, info):
         for k, v in info.items():
             r = step["info"][k]
             assert abs(v - r) <= F64_TOL * max(1.0, abs(r)), (i, k, v, r)
+    RR.run_steps(st, g["steps"], torch.float64, on_info=check, inputs=folded)
     assert st.step == g["meta"]["final_step"] == 6
     secs = {"params": st.params, "target": st.target}
     for tx in O.TX_NAMES:

@@ -12,10 +12,11 @@ import torch
 
 from helpers import make_spaces
 from oracle import drq_oracle as O
+from oracle import ref_update_runner as RR
 from oracle.replay_oracle import ReplayOracle
 import agent_helpers as AH
 import stacked_oracle as SO
-from test_small_encoder_gpu import TOL, _compare_state
+from test_small_encoder_gpu import ALL_NETS, TOL, _compare_state
 
 pytestmark = pytest.mark.gpu
 KEYS = ("front", "wrist")
@@ -179,8 +180,8 @@ def test_updates_match_the_fp64_restatement_at_num_stack_2(gpu):
         fr = SO.cropped(cfg, T, pb, noise["crop_obs"], noise["crop_next"])
         tb, tn = SO.oracle_batch(cfg, T, pb, fr), O.noise_to_torch(noise, torch.float64)
         db, dn = SO.device_batch(cfg, T, pb, fr), AH.noise_to_device(cfg, noise)
+        info, aux = RR.run_step(st, {"kind": kind, "utd": utd, "nets": ALL_NETS}, tb, tn)
         if kind == "critics":
-            info, aux = O.update_critics(st, tb, tn)
             core.update_critics(db, dn)
             if it == 0:
                 q = core.debug("q", cfg.ensemble * B).reshape(cfg.ensemble, B)
@@ -191,12 +192,10 @@ def test_updates_match_the_fp64_restatement_at_num_stack_2(gpu):
                 assert "enc/front/conv0/kernel" in aux["grads"] and "enc/proprio/dense/kernel" in aux["grads"]
                 SO.check_grads(cfg, T, core, aux["grads"], "g_critic", 0, TOL)
         elif kind == "high_utd":
-            info, aux = O.update_high_utd(st, tb, tn, utd)
             core.update_high_utd(db, utd, dn)
             SO.check_grads(cfg, T, core, aux["g_actor"], "g_actor", sl["enc/proprio/dense/kernel"][0], TOL)
         else:
-            info = O.update(st, tb, tn)
-            core.update(db, ("actor", "critic", "temperature"), dn)
+            core.update(db, ALL_NETS, dn)
         got = core.read_info()
         for k, v in info.items():
             assert abs(got[k] - v) < 2 * TOL * max(1.0, abs(v)), (it, kind, k, got[k], v)

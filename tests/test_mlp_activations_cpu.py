@@ -2,10 +2,9 @@
 (networks/mlp.py:19-31; tests/mlp_activations.py).
 
 * tests/golden/act_*.npz were produced by tests/golden/make_golden_update_activations.py from the reference's own update code with
-  `activations` overridden in the kwargs its factories pass; the float64 restatement of the two MLPs (oracle.drq_oracle's
-  policy_head / critic_forward replaced at run time, activation as a parameter, autograd for the backward) reproduces them within
-  F64_TOL of tests/test_reference_update.py, the bound of every oracle-against-golden test here.  That pins the restatement the GPU
-  tests compare with at other widths.
+  `activations` overridden in the kwargs its factories pass; the oracle (oracle.drq_oracle's policy_head / critic_forward with
+  the Config's activations, autograd for the backward) reproduces them within F64_TOL of tests/test_reference_update.py, the bound
+  of every oracle-against-golden test here.  That pins the statement the GPU tests compare with at other widths.
 * utils.init.mlp_activations reads the two kwargs as the reference's MLP would and refuses the rest from the arguments alone.
 * serl_agent_create_mlp is declared, exported and bound; the entries it generalises are still there.
 
@@ -15,6 +14,7 @@ meets it (8e6 relu pre-activations per run of density 0.4 at 0: over the seeds 1
 and 1.0e-6), so their runs start from mlp_activations.kink_margin's leaves: four live columns per LayerNorm vector, off in 40 % of
 the rows, every other column on in all rows or off in all rows.  The generator's seed search then ended at batch seed 1780 (106
 seeds tried) and 1460 (86 tried); smallest |pre-activation| 1.0022e-4 and 1.0005e-4."""
+import dataclasses
 import json
 import os
 import re
@@ -48,7 +48,7 @@ def test_restated_mlps_reproduce_the_reference_golden(name):
     g, meta, z = GR.load_variant("act", name)
     act = meta["activations"]
     assert (act["critic"], act["policy"], act["regime"]) == (critic, policy, regime) and int(z["act_n_sample"]) == n_sample
-    assert g["B"] == B and [s["kind"] for s in g["steps"]] == [s[0] for s in sched] and g["meta"]["batch_seed"] == act["batch_seed"]
+    assert g["cfg"] == cfg and g["B"] == B and [s["kind"] for s in g["steps"]] == [s[0] for s in sched] and g["meta"]["batch_seed"] == act["batch_seed"]
     if "relu" in (critic, policy):      # the fixture's condition, as the generator recorded it; and the kink was crossed
         assert act["relu_min_abs_pre"] >= MA.KINK_MIN and regime == "kink_margin" and act["margin_seed"] == MA.MARGIN_SEED, act
         assert all(0.2 < f < 0.6 for f in act["relu_off_fraction"].values()) and set(act["relu_off_fraction"]) == \
@@ -58,19 +58,13 @@ def test_restated_mlps_reproduce_the_reference_golden(name):
     trunk, theta = MA.initial_leaves(name)
     st = O.TrainState(g["cfg"], trunk, theta, torch.float64)
     recs = {"critic": MA.Recorder(), "policy": MA.Recorder()}
-    with MA.oracle_activations(critic, policy, recs):
-        for i, step in enumerate(g["steps"]):
-            b, n = RR.oracle_batch_and_noise(g["cfg"], step, torch.float64)
-            if step["kind"] == "critics":
-                info, _ = O.update_critics(st, b, n)
-            elif step["kind"] == "high_utd":
-                info, _ = O.update_high_utd(st, b, n, step["utd"])
-            else:
-                info = O.update(st, b, n, step["nets"])
-            for k, v in info.items():
-                r = step["info"][k]
-                assert abs(v - r) <= F64_TOL * max(1.0, abs(r)), (i, k, v, r)
-    assert O.policy_head.__module__ == "oracle.drq_oracle" and O.critic_forward.__module__ == "oracle.drq_oracle"   # put back
+    def check(i, step, info):
+        for k, v in info.items():
+            r = step["info"][k]
+            assert abs(v - r) <= F64_TOL * max(1.0, abs(r)), (i, k, v, r)
+    with O.observe_preactivations(recs):
+        RR.run_steps(st, g["steps"], torch.float64, on_info=check)
+    assert not O.OBSERVERS      # nothing observes once the block is left
     assert st.step == g["meta"]["final_step"]
     # the restatement saw the pre-activations the reference's activation saw
     for w, rec in recs.items():
@@ -90,32 +84,41 @@ def test_restated_mlps_reproduce_the_reference_golden(name):
 
 @pytest.mark.parametrize("name", [n for n in MA.GOLDEN if os.path.exists(GR.variant_path("act", n))])
 def test_golden_differs_from_the_tanh_run(name):
-    """the activation took effect in the reference: the oracle's own tanh MLPs do NOT reproduce the first step's critic loss
-    (a missing fixture fails in the test above)"""
+    """the activation took effect in the reference: the oracle with the launcher's tanh MLPs does NOT reproduce the first step's
+    critic loss (a missing fixture fails in the test above)"""
     g = GR.load_variant("act", name)[0]
     trunk, theta = MA.initial_leaves(name)
-    st = O.TrainState(g["cfg"], trunk, theta, torch.float64)
-    step = g["steps"][0]
-    b, n = RR.oracle_batch_and_noise(g["cfg"], step, torch.float64)
-    info = O.update_critics(st, b, n)[0] if step["kind"] == "critics" else O.update_high_utd(st, b, n, step["utd"])[0]
-    r = step["info"]["critic_loss"]
+    cfg = dataclasses.replace(g["cfg"], critic_activation="tanh", policy_activation="tanh")
+    st = O.TrainState(cfg, trunk, theta, torch.float64)
+    (info,) = RR.run_steps(st, g["steps"][:1], torch.float64)
+    r = g["steps"][0]["info"]["critic_loss"]
     assert abs(info["critic_loss"] - r) > 1e-3 * abs(r), (info["critic_loss"], r)
 
 
 def test_restatement_with_tanh_is_the_oracle():
+    """The default Config is the launcher's tanh and observing changes no value: the two MLPs under Recorders, bit for bit.  (The
+    oracle's update code against what the per-option restatements it replaced computed was compared once, over every policy_*,
+    act_* and wd_* fixture, when they were folded into it: every info scalar, leaf and moment np.array_equal.)"""
     cfg = O.Config(image_keys=(), S=10, A=5)
+    assert (cfg.critic_activation, cfg.policy_activation, cfg.std_parameterization, cfg.tanh_squash) == ("tanh", "tanh", "exp", True)
     th = O.to_torch(O.init_params(cfg, 3)[1], torch.float64)
     enc, a = torch.randn(7, cfg.S, dtype=torch.float64), torch.randn(7, cfg.A, dtype=torch.float64)
     want = O.policy_head(th, cfg, enc), O.critic_forward(th, cfg, enc, a)
-    with MA.oracle_activations("tanh", "tanh"):
+    recs = {"critic": MA.Recorder(), "policy": MA.Recorder()}
+    with O.observe_preactivations(recs):
         got = O.policy_head(th, cfg, enc), O.critic_forward(th, cfg, enc, a)
     assert torch.equal(got[0][0], want[0][0]) and torch.equal(got[0][1], want[0][1]) and torch.equal(got[1], want[1])
+    assert len(recs["critic"].min_abs) == len(recs["policy"].min_abs) == 2 and not O.OBSERVERS
+    with pytest.raises(MA.Kink):      # an observer's exception leaves the hook empty too
+        with O.observe_preactivations({"policy": MA.Recorder(floor=1e9)}):
+            O.policy_head(th, cfg, enc)
+    assert not O.OBSERVERS
     # relu's gradient at exactly 0 is 0 (jax.nn.relu's choice), and swish is x * sigmoid(x)
     x = torch.zeros(3, dtype=torch.float64, requires_grad=True)
-    MA.TORCH_ACT["relu"](x).sum().backward()
+    O.ACTIVATIONS["relu"](x).sum().backward()
     assert not x.grad.any()
     v = torch.tensor([-30.0, -1.0, 0.0, 2.0], dtype=torch.float64)
-    assert torch.allclose(MA.TORCH_ACT["swish"](v), torch.nn.functional.silu(v), rtol=1e-15, atol=0)
+    assert torch.allclose(O.ACTIVATIONS["swish"](v), torch.nn.functional.silu(v), rtol=1e-15, atol=0)
 
 
 # ---- reading the kwargs ----------------------------------------------------------------------------------------------------------

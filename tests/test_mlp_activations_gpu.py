@@ -3,8 +3,8 @@ field of LnFwdArgs / LnBwdArgs in serl_amd/csrc/heads.hip: ln_activate, ln_act_g
 
 * the reference's own update code with another activation (tests/golden/act_*.npz, injected noise) through
   tests/golden_replay.py::replay: its comparisons, its TOL;
-* the three row layouts (width 64, blocked 256, strided 2..16 columns per lane) against the restated oracle of
-  tests/mlp_activations.py: swish and relu at hidden 64, 192, 256 and 1024, 8 rows x 10 members, and 72 rows at 192 -- one
+* the three row layouts (width 64, blocked 256, strided 2..16 columns per lane) against the oracle with the Config's
+  activations: swish and relu at hidden 64, 192, 256 and 1024, 8 rows x 10 members, and 72 rows at 192 -- one
   update_critics and one update_high_utd(1) each, every gradient leaf, the info scalars, the state;
 * sample_actions of a swish agent, mode and seeded;
 * a tanh agent made by serl_agent_create_mlp(.., 0, 0) against one made by serl_agent_create, bit for bit;
@@ -18,6 +18,7 @@ fixtures, from mlp_activations.kink_margin's leaves: ROW_LIVE live columns per L
 row, all others on in every row or off in every row, their scale following the width (mlp_activations.safe_scale).  Every
 case then finds its seed among the ten (asserted in tests/test_mlp_activations_cpu.py, which needs no GPU): nothing skips."""
 import ctypes as C
+import dataclasses
 import functools
 
 import numpy as np
@@ -43,7 +44,7 @@ def test_hip_update_matches_the_reference_golden_with_activation(gpu, name):
     g, meta, _ = GR.load_variant("act", name)
     cfg, B = g["cfg"], g["B"]
     critic, policy = meta["activations"]["critic"], meta["activations"]["policy"]
-    assert (critic, policy) == MA.GOLDEN[name][3] and B == MA.GOLDEN[name][1]
+    assert (critic, policy) == MA.GOLDEN[name][3] and B == MA.GOLDEN[name][1] and cfg == MA.GOLDEN[name][0]
     agent = GR.reference_agent(cfg, B, critic_network_kwargs=MA.network_kwargs(critic, cfg.hidden),
                                policy_network_kwargs=MA.network_kwargs(policy, cfg.hidden))
     assert (agent.config["critic_activation"], agent.config["policy_activation"]) == (critic, policy)
@@ -63,13 +64,13 @@ ROW_LIVE = {8: 8, 72: 2}      # live columns per LayerNorm vector by rows: about
 PAIRS = [("swish", "swish"), ("relu", "relu"), ("relu", "swish"), ("swish", "relu")]      # (critic, policy)
 
 
-def _row_cfg(hidden):
-    return O.Config(image_keys=(), S=10, A=3, discount=0.99, hidden=hidden, ensemble=10)
+def _row_cfg(hidden, critic="tanh", policy="tanh"):
+    return O.Config(image_keys=(), S=10, A=3, discount=0.99, hidden=hidden, ensemble=10, critic_activation=critic, policy_activation=policy)
 
 
-def _core(cfg, B, critic, policy, theta):
-    """AgentCore with these activations holding `theta` (oracle names) in params and target_params"""
-    return AH.load_leaves(AH.make_core(cfg, B, critic_activation=critic, policy_activation=policy), cfg, None, theta)
+def _core(cfg, B, theta):
+    """AgentCore of the Config (its activations) holding `theta` (oracle names) in params and target_params"""
+    return AH.load_leaves(AH.make_core(cfg, B), cfg, None, theta)
 
 
 @functools.lru_cache(maxsize=None)
@@ -77,7 +78,7 @@ def _oracle_side(hidden, B, critic, policy, margin):
     """the fp64 side of a row case, once per case: update_critics on batch 3 + 16 k, then update_high_utd(1) on batch 4 + 16 k, for
     the first k < KINK_SEEDS whose relu pre-activations all stay `margin` away from 0 (k = 0 without a relu network)
     -> (k, what the comparison needs), or (None, [(k, the |pre-activation| that put seed k out) ...])"""
-    cfg = _row_cfg(hidden)
+    cfg = _row_cfg(hidden, critic, policy)
     relu = "relu" in (critic, policy)
     tried = []
     trunk, theta = O.init_params(cfg, 42)
@@ -89,7 +90,7 @@ def _oracle_side(hidden, B, critic, policy, margin):
         n1, n2 = O.make_noise(cfg, B, seed=7), O.make_noise(cfg, B, seed=8, utd_ratio=1)
         recs = {w: MA.Recorder(floor=margin if a == "relu" else None) for w, a in (("critic", critic), ("policy", policy))}
         try:
-            with MA.oracle_activations(critic, policy, recs):
+            with O.observe_preactivations(recs):
                 info1, aux1 = O.update_critics(st, AH.batch_to_torch(b1, torch.float64), O.noise_to_torch(n1, torch.float64))
                 info2, aux2 = O.update_high_utd(st, AH.batch_to_torch(b2, torch.float64), O.noise_to_torch(n2, torch.float64), 1)
         except MA.Kink as e:      # this seed is out at its first evaluation inside the margin
@@ -101,13 +102,13 @@ def _oracle_side(hidden, B, critic, policy, margin):
 
 def _compare_rows(case, critic, policy, margin):
     label, hidden, B = case
-    cfg = _row_cfg(hidden)
+    cfg = _row_cfg(hidden, critic, policy)
     k, side = _oracle_side(hidden, B, critic, policy, margin)
     if k is None:
         pytest.skip(f"{label} {critic}/{policy}: no batch seed among {MA.KINK_SEEDS} keeps every relu pre-activation {margin:g} away from 0 "
                     f"(seed index, the first evaluation's minimum inside the margin): {[(i, float(f'{m:.2g}')) for i, m in side]}")
-    core = _core(cfg, B, critic, policy, side["theta"])
-    assert core.cfg.hidden == hidden
+    core = _core(cfg, B, side["theta"])
+    assert core.cfg.hidden == hidden and (core.critic_activation, core.policy_activation) == (critic, policy)
     fig = _Figures(f"{label} critic={critic} policy={policy} seed {k}")
     core.update_critics(AH.batch_to_device(cfg, side["b1"]), AH.noise_to_device(cfg, side["n1"]))
     _info(fig, core.read_info(), side["info1"], ("critic_loss", "predicted_qs", "target_qs"))
@@ -137,7 +138,7 @@ def test_a_tanh_row_case_fails_against_the_swish_oracle(gpu):
     label, hidden, B = ROWS[0]
     cfg = _row_cfg(hidden)
     _, side = _oracle_side(hidden, B, "swish", "swish", MA.KINK_MIN)
-    core = _core(cfg, B, "tanh", "tanh", side["theta"])
+    core = _core(cfg, B, side["theta"])
     core.update_critics(AH.batch_to_device(cfg, side["b1"]), AH.noise_to_device(cfg, side["n1"]))
     assert AH.rel_err(core.debug("q", cfg.ensemble * B).reshape(cfg.ensemble, B), side["aux1"]["q"].numpy()) > 100 * TOL
 
@@ -148,12 +149,12 @@ def test_sample_actions_of_a_swish_agent_match_the_restated_policy(gpu, hidden):
     S, A, B = 10, 5, 72
     agent = MW.sac_agent(hidden, seed=3, B=B, S=S, A=A, critic_network_kwargs=MA.network_kwargs("relu", hidden),
                          policy_network_kwargs=MA.network_kwargs("swish", hidden))
-    cfg = O.Config(image_keys=(), S=S, A=A, discount=0.99, hidden=hidden)
+    cfg = O.Config(image_keys=(), S=S, A=A, discount=0.99, hidden=hidden, critic_activation="relu", policy_activation="swish")
     theta = MA.act_theta(O.init_params(cfg, GR.PARAM_SEED)[1], cfg, "trained")      # (LayerNorm scales up to 3: swish is not near-linear)
     AH.load_leaves(agent.core, cfg, None, theta)
     state = np.random.default_rng(6).standard_normal((B, S)).astype(np.float32)
     th = O.to_torch(theta, torch.float64)
-    mean, sd = MA.policy_head(th, cfg, torch.tensor(state, dtype=torch.float64), MA.TORCH_ACT["swish"])
+    mean, sd = O.policy_head(th, cfg, torch.tensor(state, dtype=torch.float64))
     mode = agent.sample_actions(state, argmax=True)
     e_mode = AH.rel_err(mode, torch.tanh(mean).numpy())
     seed = np.array([0, 11], np.uint32)
@@ -161,7 +162,7 @@ def test_sample_actions_of_a_swish_agent_match_the_restated_policy(gpu, hidden):
     eps = agent._action_noise(seed, B).cpu().numpy().astype(np.float64)        # the draws that seed stands for
     want, _ = O.sample_and_log_prob(mean, sd, torch.tensor(eps))
     e_sample = AH.rel_err(got, want.numpy())
-    tanh_mean, _ = O.policy_head(th, cfg, torch.tensor(state, dtype=torch.float64))
+    tanh_mean, _ = O.policy_head(th, dataclasses.replace(cfg, policy_activation="tanh"), torch.tensor(state, dtype=torch.float64))
     print(f"sample_actions swish w{hidden}: mode {e_mode:.2e}, sample {e_sample:.2e}; "
           f"the tanh policy's mode is {AH.rel_err(torch.tanh(tanh_mean).numpy(), torch.tanh(mean).numpy()):.2e} away")
     assert e_mode < TOL and e_sample < TOL

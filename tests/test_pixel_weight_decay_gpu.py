@@ -7,7 +7,7 @@ after every step.
 * the reference's own runs (tests/golden/wd_*.npz) through tests/golden_replay.py::replay at its TOL, the pretrained ones in both
   trunk modes, and once on an agent whose batch capacity exceeds the rows (every pass then takes the partial-batch path; at
   capacity == rows update_critics and the actor phase take the contiguous pass, the 3-row minibatches the partial one);
-* every trunk leaf, online and target, after the schedule against the float64 restatement of tests/pixel_weight_decay.py,
+* every trunk leaf, online and target, after the schedule against the float64 oracle (TrainState.live_trunk),
   element by element: |got - ref| <= 1e-4 |p0 - ref| + 2 n ulp(p0) -- tests/test_optimizer_layouts_gpu.py's bound for one step
   (optimizer_cases.STEP_REL of the step, 2 ulp of the parameter), summed over the n steps of a monotone decay; a target element
   is an average of online values with weights that sum to 1 and rounds twice more per EMA step: 2 n_ema ulp(p0) on top;
@@ -33,6 +33,8 @@ import golden_replay as GR
 import mlp_widths as MW
 import optimizer_cases as OC
 import pixel_weight_decay as PW
+from test_agent_gpu import _compare_state
+from test_mlp_widths_gpu import _Figures, _grads, _info
 from test_pixel_weight_decay_cpu import _restated
 
 pytestmark = pytest.mark.gpu
@@ -103,7 +105,12 @@ def test_every_trunk_leaf_matches_the_restatement(gpu, name, trunk_mode, capacit
     g, _, st, _ = _restated(name)
     core = _replayed(name, trunk_mode, capacity).core
     trunk0, _ = O.init_params(g["cfg"], g["meta"]["param_seed"])
-    steps = PW.optimizer_steps(PW.GOLDEN[name][2])
+    _check_trunk_leaves(core, st, trunk0, PW.optimizer_steps(PW.GOLDEN[name][2]), f"wd_{name} {trunk_mode} capacity {capacity}")
+
+
+def _check_trunk_leaves(core, st, trunk0, steps, label):
+    """every trunk leaf of the agent, online and target, against the oracle's after `steps` (PW.optimizer_steps), element by
+    element, with the bound of the module docstring"""
     n, n_ema = len(steps), sum(steps)
     worst = {"params": 0.0, "target_params": 0.0}
     for k, v0 in trunk0.items():
@@ -120,8 +127,7 @@ def test_every_trunk_leaf_matches_the_restatement(gpu, name, trunk_mode, capacit
             worst[sec] = max(worst[sec], float((err[nz] / bound[nz]).max()) if nz.any() else 0.0)
             assert (err <= bound).all(), (sec, k, i, got[nz][i], ref[nz][i], err[nz][i], bound[nz][i])
         assert (np.abs(core.get("params", k)) <= 0.95 * np.abs(v0.reshape(-1))).all(), k      # the trunk did decay
-    print(f"wd_{name} {trunk_mode} capacity {capacity}: trunk leaves, worst err / bound: online {worst['params']:.3f}, "
-          f"target {worst['target_params']:.3f}")
+    print(f"{label}: trunk leaves, worst err / bound: online {worst['params']:.3f}, target {worst['target_params']:.3f}")
 
 
 @pytest.mark.parametrize("name,trunk_mode,capacity", PRETRAINED[:2], ids=[f"{n}-{m}-{c}" for n, m, c in PRETRAINED[:2]])
@@ -140,9 +146,9 @@ def test_read_paths_use_the_right_trunk(gpu, name, trunk_mode, capacity):
     with torch.no_grad():
         q = {}
         for which, params, target in (("target", st.target, True), ("online", st.params, False), ("target on online trunk", st.target, False)):
-            q[which] = O.critic_forward(params, cfg, O.encode(params, cfg, PW.features(st, ft, target=target), s64), a64).numpy()
-        mean, _ = O.policy_head(st.params, cfg, O.encode(st.params, cfg, PW.features(st, ft), s64))
-        mean_t, _ = O.policy_head(st.params, cfg, O.encode(st.params, cfg, PW.features(st, ft, target=True), s64))
+            q[which] = O.critic_forward(params, cfg, O.encode(params, cfg, O.features(st, ft, target=target), s64), a64).numpy()
+        mean, _ = O.policy_head(st.params, cfg, O.encode(st.params, cfg, O.features(st, ft), s64))
+        mean_t, _ = O.policy_head(st.params, cfg, O.encode(st.params, cfg, O.features(st, ft, target=True), s64))
     e_t = AH.rel_err(agent.q_values(obs, action, target=True), q["target"])
     e_o = AH.rel_err(agent.q_values(obs, action), q["online"])
     e_m = AH.rel_err(agent.sample_actions(obs, argmax=True), torch.tanh(mean).numpy())
@@ -151,6 +157,40 @@ def test_read_paths_use_the_right_trunk(gpu, name, trunk_mode, capacity):
           f"{apart_q:.2e} (Q) and {apart_m:.2e} (mode) away")
     assert apart_q > 100 * TOL and apart_m > 100 * TOL      # (a condition on the fixture: the comparison can tell the trunks apart)
     assert e_t < TOL and e_o < TOL and e_m < TOL
+
+
+# ---- every option at once -------------------------------------------------------------------------------------------------------
+def test_all_options_at_once_match_the_oracle(gpu):
+    """PW.COMPOSED -- softplus std, swish in both MLPs, the decay on a pretrained trunk -- in one serl_agent_create_mlp call against
+    the one oracle: update_critics (6 rows = the agent's capacity) then update_high_utd(2) (3-row minibatches: the partial-batch
+    path), with the comparisons and bounds of tests/test_mlp_activations_gpu.py::_compare_rows and, for the trunk leaves, of
+    test_every_trunk_leaf_matches_the_restatement"""
+    cfg, B = PW.COMPOSED, PW.COMPOSED_ROWS
+    trunk0, theta = O.init_params(cfg, GR.PARAM_SEED)
+    st = O.TrainState(cfg, trunk0, theta, torch.float64)
+    core = AH.load_leaves(AH.make_core(cfg, B), cfg, trunk0, theta)
+    assert st.live_trunk and core.live_trunk and core.std_parameterization == "softplus"
+    assert (core.critic_activation, core.policy_activation) == ("swish", "swish")
+    b1, n1 = AH.synth_batch(cfg, B, seed=3), O.make_noise(cfg, B, seed=7)
+    b2, n2 = AH.synth_batch(cfg, B, seed=4), O.make_noise(cfg, B, seed=8, utd_ratio=2)
+    info1, aux1 = O.update_critics(st, AH.batch_to_torch(b1, torch.float64), O.noise_to_torch(n1, torch.float64))
+    info2, aux2 = O.update_high_utd(st, AH.batch_to_torch(b2, torch.float64), O.noise_to_torch(n2, torch.float64), 2)
+    fig = _Figures("composed softplus / swish / decay")
+    core.update_critics(AH.batch_to_device(cfg, b1), AH.noise_to_device(cfg, n1))
+    _info(fig, core.read_info(), info1, ("critic_loss", "predicted_qs", "target_qs"))
+    fig.add("q", AH.rel_err(core.debug("q", cfg.ensemble * B).reshape(cfg.ensemble, B), aux1["q"].numpy()))
+    fig.add("target_q", AH.rel_err(core.debug("target_q", B), aux1["target_q"].numpy()))
+    fig.add("next logp", AH.rel_err(core.debug("logp", B), aux1["next_logp"].numpy()))
+    _grads(fig, cfg, core, aux1["grads"], "g_critic")
+    core.update_high_utd(AH.batch_to_device(cfg, b2), 2, AH.noise_to_device(cfg, n2))
+    _info(fig, core.read_info(), info2,
+          ("critic_loss", "predicted_qs", "target_qs", "actor_loss", "temperature", "entropy", "temperature_loss"))
+    _grads(fig, cfg, core, aux2["g_actor"], "g_actor")
+    fig.check()
+    _compare_state(cfg, st, core, steps=4)
+    assert core.step == st.step == 4
+    _check_trunk_leaves(core, st, trunk0, PW.optimizer_steps([("critics",), ("high_utd", 2)]), "composed")
+    assert core.debug("ctr_nonzero", 1)[0] == 0
 
 
 # ---- checkpoints -----------------------------------------------------------------------------------------------------------------

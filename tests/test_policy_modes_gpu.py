@@ -4,12 +4,13 @@ Gaussian (serl_agent_create_policy's std_param / no_tanh; the MODE template para
 * the reference's own update code in every new mode (tests/golden/policy_*.npz, injected noise) with the comparisons and bounds of
   tests/golden_replay.py::replay, walked over the agent's own leaves (a uniform agent has actor/log_stds and no
   log-std Dense), at 72 rows (two head tiles, the second ragged) and A = 5; two of them in the regime where whole std columns clip;
-* sample_actions, mode and injected noise, against the float64 restatement of tests/policy_modes.py;
+* sample_actions, mode and injected noise, against the float64 head of oracle/drq_oracle.py;
 * the fused chain against the one-launch-per-operation chain bit for bit at hidden = 192, 65 rows, and a uniform agent's launch count
   against the exp agent's;
 * the checkpoint round trip of a uniform agent, and the refusal of an exp state;
 * the C ABI: serl_agent_create and its struct build the agent they always did, serl_agent_create_policy range-checks its arguments."""
 import ctypes as C
+import dataclasses
 
 import numpy as np
 import pytest
@@ -33,19 +34,19 @@ def test_hip_update_matches_the_reference_golden_in_mode(gpu, name):
     g, meta, _ = GR.load_variant("policy", name)
     cfg, B = g["cfg"], g["B"]
     std, squash = meta["policy"]["std_parameterization"], meta["policy"]["tanh_squash_distribution"]
-    assert (std, squash) == PM.GOLDEN[name][3] and B == PM.GOLDEN[name][1]
+    assert (std, squash) == PM.GOLDEN[name][3] and B == PM.GOLDEN[name][1] and cfg == PM.GOLDEN[name][0]
     agent = GR.reference_agent(cfg, B, policy_kwargs=PM.policy_kwargs(std, squash))
     assert ("actor/log_stds" in agent.core.leaves) == (std == "uniform") == ("actor/logstd/kernel" not in agent.core.leaves)
     AH.load_leaves(agent.core, cfg, *PM.initial_leaves(name))
-    GR.replay(agent, g, leaf_names=PM.leaf_names(cfg, std), label=f"policy_{name}")
+    GR.replay(agent, g, label=f"policy_{name}")
     assert agent.core.debug("ctr_nonzero", 1)[0] == 0
 
 
 # ---- sample_actions ------------------------------------------------------------------------------------------------------------
 def _core(cfg, B, std, squash, theta, trunk=None, fuse=None):
     """AgentCore of this distribution holding `theta` (oracle names) in params and target_params"""
-    core = AH.make_core(cfg, B, fuse=fuse, std_parameterization=std, tanh_squash_distribution=squash)
-    return AH.load_leaves(core, cfg, trunk, theta)
+    cfg = dataclasses.replace(cfg, std_parameterization=std, tanh_squash=squash)
+    return AH.load_leaves(AH.make_core(cfg, B, fuse=fuse), cfg, trunk, theta)
 
 
 @pytest.mark.parametrize("std,squash", [PM.DEFAULT_MODE] + PM.NEW_MODES, ids=["exp"] + PM.MODE_IDS)
@@ -57,13 +58,13 @@ def test_sample_actions_match_the_float64_head_in_mode(gpu, std, squash):
     state = rng.standard_normal((B, cfg.S)).astype(np.float32)
     eps = (2.0 * rng.standard_normal((B, cfg.A))).astype(np.float32)      # (wide enough that unsquashed samples leave [-1, 1])
     th = O.to_torch(theta, torch.float64)
-    mean, sd = PM.head(th, cfg, torch.tensor(state, dtype=torch.float64), std)
+    mean, sd = O.policy_head(th, dataclasses.replace(cfg, std_parameterization=std), torch.tensor(state, dtype=torch.float64))
     dstate = torch.tensor(state, device="cuda")
     mode = core.sample_actions(None, dstate, None).cpu().numpy()
     want_mode = (torch.tanh(mean) if squash else mean).numpy()
     e_mode = AH.rel_err(mode, want_mode)
     got = core.sample_actions(None, dstate, torch.tensor(eps, device="cuda")).cpu().numpy()
-    want, _ = PM.sample_and_log_prob(mean, sd, torch.tensor(eps, dtype=torch.float64), squash)
+    want, _ = O.sample_and_log_prob(mean, sd, torch.tensor(eps, dtype=torch.float64), squash)
     e_sample = AH.rel_err(got, want.numpy())
     print(f"sample_actions {std} squash={squash}: mode {e_mode:.2e}, sample {e_sample:.2e}, max |a| {np.abs(got).max():.3f}")
     assert e_mode < TOL and e_sample < TOL

@@ -28,17 +28,7 @@ F64_TOL = 1e-9
 def _run_oracle(cfg, steps, param_seed):
     trunk, theta = O.init_params(cfg, param_seed)
     st = O.TrainState(cfg, trunk, theta, torch.float64)
-    infos = []
-    for step in steps:
-        b, n = RR.oracle_batch_and_noise(cfg, step, torch.float64)
-        if step["kind"] == "critics":
-            info, _ = O.update_critics(st, b, n)
-        elif step["kind"] == "high_utd":
-            info, _ = O.update_high_utd(st, b, n, step["utd"])
-        else:
-            info = O.update(st, b, n, step["nets"])
-        infos.append(info)
-    return st, infos
+    return st, RR.run_steps(st, steps, torch.float64)
 
 
 def _oracle_sections(st):

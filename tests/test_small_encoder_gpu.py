@@ -7,10 +7,12 @@ import pytest
 import torch
 
 from oracle import drq_oracle as O
+from oracle import ref_update_runner as RR
 import agent_helpers as AH
 from test_agent_gpu import TOL, _check_grads, _compare_state
 
 pytestmark = pytest.mark.gpu
+ALL_NETS = ("actor", "critic", "temperature")
 
 
 def _cfg(H=64, W=64, keys=("front", "wrist"), S=5, A=3):
@@ -51,16 +53,14 @@ def test_small_encoder_sequence(gpu):
         noise = O.make_noise(cfg, B, seed=50 + it, utd_ratio=utd)
         tb, tn = AH.batch_to_torch(b, torch.float64), O.noise_to_torch(noise, torch.float64)
         db, dn = AH.batch_to_device(cfg, b), AH.noise_to_device(cfg, noise)
+        info, aux = RR.run_step(st, {"kind": kind, "utd": utd, "nets": ALL_NETS}, tb, tn)
         if kind == "critics":
-            info, _ = O.update_critics(st, tb, tn)
             core.update_critics(db, dn)
         elif kind == "high_utd":
-            info, aux = O.update_high_utd(st, tb, tn, utd)
             core.update_high_utd(db, utd, dn)
             _check_grads(cfg, core, aux["g_actor"], "g_actor", sl["enc/proprio/dense/kernel"][0])
         else:
-            info = O.update(st, tb, tn)
-            core.update(db, ("actor", "critic", "temperature"), dn)
+            core.update(db, ALL_NETS, dn)
         got = core.read_info()
         for k, v in info.items():
             assert abs(got[k] - v) < 2 * TOL * max(1.0, abs(v)), (it, kind, k, got[k], v)

@@ -88,17 +88,7 @@ def _run_oracle(g, theta, target, trunk):
     cfg = g["cfg"]
     st = O.TrainState(cfg, trunk, theta, torch.float64)
     st.target = O.to_torch(target, torch.float64)
-    infos = []
-    for step in g["steps"]:
-        b, n = RR.oracle_batch_and_noise(cfg, step, torch.float64)
-        if step["kind"] == "critics":
-            info, _ = O.update_critics(st, b, n)
-        elif step["kind"] == "high_utd":
-            info, _ = O.update_high_utd(st, b, n, step["utd"])
-        else:
-            info = O.update(st, b, n, step["nets"])
-        infos.append(info)
-    return st, infos
+    return st, RR.run_steps(st, g["steps"], torch.float64)
 
 
 @pytest.mark.parametrize("name", TR.UPDATE_GOLDEN)

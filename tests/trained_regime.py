@@ -181,8 +181,7 @@ def policy_pre(st, b, noise, side, mask_name):
         enc = O.encode(st.params, cfg, feats, b["state" if side == "obs" else "next_state"], drop_masks=noise[mask_name],
                        stop_gradient=True)
         th = st.params
-        h = torch.tanh(O.layer_norm(enc @ th["actor/w1"] + th["actor/b1"], th["actor/ln1/scale"], th["actor/ln1/bias"]))
-        h = torch.tanh(O.layer_norm(h @ th["actor/w2"] + th["actor/b2"], th["actor/ln2/scale"], th["actor/ln2/bias"]))
+        h = O.policy_mlp(th, cfg, enc)
         return h @ th["actor/mean/kernel"] + th["actor/mean/bias"], h @ th["actor/logstd/kernel"] + th["actor/logstd/bias"]
 
 
