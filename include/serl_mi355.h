@@ -305,6 +305,19 @@ int serl_agent_create_policy(const serl_agent_cfg* cfg, int std_param, int no_ta
  *   SERL_ACT_RELU   y = max(p, 0), gradient 0 at p = 0 (jax.nn.relu)
  *   SERL_ACT_SWISH  y = p * sigmoid(p) (flax.linen.swish = silu, mlp.py's own default) */
 int serl_agent_create_mlp(const serl_agent_cfg* cfg, int std_param, int no_tanh, int critic_act, int policy_act, serl_agent** out);
+/* serl_agent_create_mlp with Dropout in the critic's and the policy's MLP (networks/mlp.py:27-28: Dense -> Dropout(dropout_rate) ->
+ * LayerNorm -> activation in both hidden layers; agents/continuous/sac.py:137-176,197-207 run every loss with train=True).  A
+ * positive critic rate is Dropout-Q.  serl_agent_create_mlp is this function with (0, 0): such an agent launches the kernels it
+ * always launched.  Rates outside [0, 1) are SERL_ERR_INVALID.  The rates are doubles, as the reference's are: the keep
+ * probability is float32(1.0 - rate), rounded once -- what jax.random.bernoulli compares with and the kept elements are divided by.  Dropout owns no parameter: leaves, optimizer state and checkpoints are the same at every rate.
+ *   - a kept element of the Dense output (bias included) is divided by 1 - rate, a dropped one is 0; the LayerNorm's statistics
+ *     are those of the masked row;
+ *   - all ensemble members of one critic forward drop the SAME elements (ensemblize splits only the params stream): one keep-mask
+ *     [rows][hidden] per (forward, layer);
+ *   - the update's six MLP evaluations draw (serl_mlp_noise below); serl_agent_sample_actions, serl_agent_eval_q and
+ *     serl_agent_eval_policy are train=False and ignore the rates. */
+int serl_agent_create_dropout(const serl_agent_cfg* cfg, int std_param, int no_tanh, int critic_act, int policy_act,
+                              double critic_dropout, double policy_dropout, serl_agent** out);
 int serl_agent_destroy(serl_agent* a);
 
 /* Parameter tree access (flat leaf names, see DESIGN.md "parameter arena"; the Python shim maps
@@ -399,6 +412,35 @@ typedef struct serl_noise {
   const uint32_t* key_eps_temp;
   const uint32_t* key_mask_next_temp;
 } serl_noise;
+
+/* The MLP Dropout draws of an agent made by serl_agent_create_dropout (mlp.py:27-28; sac.py:137-176,197-207).  serl_noise is
+ * unchanged; this struct is BOUND to the agent and consumed by the next update / phase / dry-run call (serl_agent_update*,
+ * serl_agent_critic_grads*, serl_agent_actor_grads, serl_agent_eval_losses): that call reads it -- an update reads it in all of
+ * its phases -- and the binding is gone when it returns.  Six evaluations ("sites") draw, each in both hidden layers:
+ *   SERL_SITE_PI_NEXT   policy at next_obs inside the critic loss      (policy rate; one draw per critic update)
+ *   SERL_SITE_Q_TARGET  target critic at next_obs                      (critic rate; one draw per critic update)
+ *   SERL_SITE_Q_ONLINE  online critic at obs                           (critic rate; one draw per critic update)
+ *   SERL_SITE_PI        policy at obs inside the actor loss            (policy rate)
+ *   SERL_SITE_Q_ACTOR   critic at obs inside the actor loss            (critic rate)
+ *   SERL_SITE_PI_TEMP   policy at next_obs inside the temperature loss (policy rate)
+ * Per site, in this order of preference:
+ *   mask[site]  DEVICE u8 keep-masks [2 layers][batch][hidden], 1 = keep, batch = the rows of the call's batch; the critic-loss
+ *               sites of minibatch i of a high-UTD update read the rows of that minibatch.
+ *   key[site]   HOST uint32 words: per layer the key of jax.random.bernoulli(key, 1 - rate, (global minibatch rows, hidden)), drawn
+ *               inside the LayerNorm rows (a data-parallel rank draws its rows of it, serl_agent_set_shard) -- flax's make_rng at
+ *               the Dropout layer's scope path.  Critic-loss sites: [utd][2 layers][2], indexed by redq_row; the others [2 layers][2].
+ *   neither     hashed on the device from cfg.seed, a stream per (site, layer) indexed by the global row: the ranks of a
+ *               data-parallel job agree.  The hash gives the target and the online critic independent masks also where the
+ *               reference, with critic_subsample_size None, would give them the same one.
+ * A site whose network has rate 0 reads nothing.  serl_agent_set_mlp_noise(a, NULL) clears a binding. */
+enum { SERL_SITE_PI_NEXT = 0, SERL_SITE_Q_TARGET = 1, SERL_SITE_Q_ONLINE = 2, SERL_SITE_PI = 3, SERL_SITE_Q_ACTOR = 4, SERL_SITE_PI_TEMP = 5,
+       SERL_MLP_SITES = 6 };
+typedef struct serl_mlp_noise {
+  const uint8_t* mask[SERL_MLP_SITES];
+  const uint32_t* key[SERL_MLP_SITES];
+  int32_t mask_rows;   /* `batch` of the mask tensors: a call on a batch of another size is refused (SERL_ERR_INVALID) */
+} serl_mlp_noise;
+int serl_agent_set_mlp_noise(serl_agent* a, const serl_mlp_noise* noise);
 
 /* sac.py:185-189,215-219,234,291-297 */
 typedef struct serl_info {
@@ -696,6 +738,20 @@ typedef struct serl_jax_update_keys_t {
   uint32_t k_policy[2], k_sample[2], k_temp[2];
 } serl_jax_update_keys_t;
 int serl_jax_update_keys(const uint32_t rng[2], int drq_aug, int n_critic, int has_actor_temp, int combined, serl_jax_update_keys_t* out);
+/* serl_jax_update_keys, and the rngs the critic forwards of the same call run under (mlp.py:27-28 draws its Dropout masks from
+ * them; sac.py:137-176,197-207):
+ *   k_q_target[u]  c of `c, k_next_action = split(r_critic)`: forward_target_critic's rng                    (sac.py:137,143-147)
+ *   k_q_online[u]  split(c)[0], what sac.py:151 leaves in `rng` for forward_critic (sac.py:174-176) -- or c itself with
+ *                  subsample_none != 0 (critic_subsample_size None: no re-split, target and online forwards share rng and masks)
+ *   k_q_actor      critic_rng, the fourth key of split(r_actor, 4)                                          (sac.py:197,203-207)
+ * `keys` is filled exactly as serl_jax_update_keys fills it. */
+typedef struct serl_jax_dropout_keys_t {
+  uint32_t k_q_target[SERL_JAX_MAX_UTD][2];
+  uint32_t k_q_online[SERL_JAX_MAX_UTD][2];
+  uint32_t k_q_actor[2];
+} serl_jax_dropout_keys_t;
+int serl_jax_update_keys_dropout(const uint32_t rng[2], int drq_aug, int n_critic, int has_actor_temp, int combined, int subsample_none,
+                                 serl_jax_update_keys_t* keys, serl_jax_dropout_keys_t* out);
 /* Device draws: job i writes elements [first, first + count) of the flat array a JAX call of `n_total` elements returns
  * (a rank of a data-parallel job, or a minibatch window, fills its rows only):
  *   SERL_JAX_NORMAL       f32  jax.random.normal(key, shape)             SERL_JAX_BERNOULLI_U8  u8  jax.random.bernoulli(key, p, shape)

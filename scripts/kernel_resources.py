@@ -49,6 +49,8 @@ CHAIN = [
     ("ln_bwd_kernel<0, false>", 80),
     ("ln_bwd_one_kernel<4, true>", 80),
     ("ln_bwd_one_kernel<1, false>", 80),
+    ("ln_fwd_drop_kernel<4, true>", 80),      # the same rows with MLP Dropout (launches of a Dropout agent only)
+    ("ln_bwd_drop_kernel<0, false>", 80),
     ("policy_dist_fwd_kernel<0>", 80),
     ("policy_dist_bwd_kernel<0>", 80),
     ("critic_loss_kernel", 80),

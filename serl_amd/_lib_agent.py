@@ -53,6 +53,15 @@ class SerlNoise(C.Structure):
     ]
 
 
+MLP_SITES = ("pi_next", "q_target", "q_online", "pi", "q_actor", "pi_temp")   # SERL_SITE_*, in code order
+MLP_CRITIC_LOSS_SITES = MLP_SITES[:3]      # one draw per critic update of a call
+MLP_SITE_NETWORK = {"pi_next": "policy", "q_target": "critic", "q_online": "critic", "pi": "policy", "q_actor": "critic", "pi_temp": "policy"}
+
+
+class SerlMlpNoise(C.Structure):      # serl_mlp_noise
+    _fields_ = [("mask", C.c_void_p * len(MLP_SITES)), ("key", C.c_void_p * len(MLP_SITES)), ("mask_rows", C.c_int32)]
+
+
 class SerlInfo(C.Structure):
     _fields_ = [(n, C.c_float) for n in (
         "critic_loss", "predicted_qs", "target_qs", "actor_loss", "temperature", "entropy",
@@ -71,6 +80,8 @@ SIGNATURES = {
     "serl_agent_create": [P(SerlAgentCfg), P(vp)],
     "serl_agent_create_policy": [P(SerlAgentCfg), i32, i32, P(vp)],   # std_param (SERL_STD_*), no_tanh
     "serl_agent_create_mlp": [P(SerlAgentCfg), i32, i32, i32, i32, P(vp)],   # ... critic_act, policy_act (SERL_ACT_*)
+    "serl_agent_create_dropout": [P(SerlAgentCfg), i32, i32, i32, i32, C.c_double, C.c_double, P(vp)],   # ... critic_dropout, policy_dropout
+    "serl_agent_set_mlp_noise": [vp, P(SerlMlpNoise)],
     "serl_agent_destroy": [vp],
     "serl_agent_live_trunk": [vp],
     "serl_agent_num_leaves": [vp],

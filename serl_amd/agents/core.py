@@ -9,7 +9,8 @@ import torch
 
 from .. import _lib
 from .._handle import Handle
-from .._lib_agent import APPLY_ACTOR_TEMP, APPLY_CRITIC, NET_BITS, TX_INDEX, SerlAgentCfg, SerlInfo, SerlNoise  # noqa: F401
+from .._lib_agent import (APPLY_ACTOR_TEMP, APPLY_CRITIC, MLP_SITES, NET_BITS, TX_INDEX, SerlAgentCfg, SerlInfo,  # noqa: F401
+                          SerlMlpNoise, SerlNoise)
 
 from ..utils.init import MLP_ACTIVATIONS, STD_PARAMETERIZATIONS
 
@@ -24,14 +25,17 @@ class AgentCore(Handle):
                  tau=0.005, lr=3e-4, dropout=0.1, std_min=1e-5, std_max=5.0, target_entropy=None,
                  seed=0, temp_warmup_steps=-1, optimizers=None, encoder_type="resnet-pretrained",
                  critic_subsample_size=2, backup_entropy=False, num_stack=1, std_parameterization="exp",
-                 tanh_squash_distribution=True, critic_activation="tanh", policy_activation="tanh"):
+                 tanh_squash_distribution=True, critic_activation="tanh", policy_activation="tanh",
+                 critic_dropout=0.0, policy_dropout=0.0):
         """optimizers: optional {"actor"|"critic"|"temperature": make_optimizer kwargs (common/optimizers.py:6-13:
         learning_rate, warmup_steps, cosine_decay_steps, weight_decay, clip_grad_norm)} overriding lr / warmup_steps.
         weight_decay decays every leaf of the tree, as optax.adamw does with the params the reference hands it -- with
         encoder_type="resnet-pretrained" the pretrained trunk too (`live_trunk`): the reference's behaviour, not a recommendation.
         num_stack: T, frames per observation (SmallEncoder only); state_dim is then the flattened width T * S.
         std_parameterization / tanh_squash_distribution: the policy distribution (Policy's kwargs of the same names).
-        critic_activation / policy_activation: one of MLP_ACTIVATIONS each (MLP's `activations`, utils.init.mlp_activations)."""
+        critic_activation / policy_activation: one of MLP_ACTIVATIONS each (MLP's `activations`, utils.init.mlp_activations).
+        critic_dropout / policy_dropout: MLP's `dropout_rate` in [0, 1) (mlp.py:27-28, utils.init.mlp_dropout_rates); the update's
+        losses draw, the evaluation calls (sample_actions, eval_q, eval_policy) never do."""
         if target_entropy is None:
             target_entropy = -act_dim / 2
         self.cfg = SerlAgentCfg(device, n_cam, H, W, state_dim, act_dim, batch, ensemble, hidden,
@@ -51,6 +55,8 @@ class AgentCore(Handle):
         # ... nor are the MLP activations: serl_agent_create_mlp
         self.critic_activation, self.policy_activation = critic_activation, policy_activation
         self._acts = (MLP_ACTIVATIONS.index(critic_activation), MLP_ACTIVATIONS.index(policy_activation))
+        # ... nor the MLPs' Dropout rates: serl_agent_create_dropout
+        self.critic_dropout, self.policy_dropout = float(critic_dropout), float(policy_dropout)
         for name, kw in (optimizers or {}).items():
             i = TX_INDEX[name]
             bad = set(kw) - {"learning_rate", "warmup_steps", "cosine_decay_steps", "weight_decay", "clip_grad_norm"}
@@ -78,8 +84,8 @@ class AgentCore(Handle):
         super().__del__()
 
     def _create(self, cfg):
-        return self.L.serl_agent_create_mlp(C.byref(cfg), self._std_param, 0 if self.tanh_squash_distribution else 1, *self._acts,
-                                            C.byref(self._h))
+        return self.L.serl_agent_create_dropout(C.byref(cfg), self._std_param, 0 if self.tanh_squash_distribution else 1, *self._acts,
+                                                self.critic_dropout, self.policy_dropout, C.byref(self._h))
 
     # ---- parameters ------------------------------------------------------------------------
     @property
@@ -118,11 +124,32 @@ class AgentCore(Handle):
     # ---- updates ---------------------------------------------------------------------------
     def _noise(self, noise: Optional[dict]):
         """noise: dict of torch device tensors (eps_*, mask_*), np.int32 redq_idx and / or jax.random keys (key_eps_* uint32[..., 2],
-        key_mask_* uint32[..., n_cam, 2]: draws made inside the consuming kernels where the tensor is absent), or None."""
+        key_mask_* uint32[..., n_cam, 2]: draws made inside the consuming kernels where the tensor is absent), or None.
+        The MLPs' Dropout draws ride in the same dict, per site of _lib_agent.MLP_SITES: drop_mask_<site> device u8[2, batch, hidden]
+        keep-masks or drop_key_<site> uint32[(update,) 2, 2] keys; they are bound to the agent here, for the call this noise is
+        built for (serl_agent_set_mlp_noise)."""
         if noise is None:
             self._keep = None
             return None
         keep = []
+        m = None
+        if any(k.startswith("drop_") for k in noise):
+            m = SerlMlpNoise()
+            for i, site in enumerate(MLP_SITES):
+                t, k = noise.get("drop_mask_" + site), noise.get("drop_key_" + site)
+                if t is not None:
+                    t = t.to(device=self.device, dtype=torch.uint8).contiguous()
+                    rows = m.mask_rows if m.mask_rows else int(t.shape[1]) if t.dim() == 3 else -1
+                    if tuple(t.shape) != (2, rows, self.cfg.hidden):
+                        raise ValueError(f"drop_mask_{site}: expected u8[2, batch, {self.cfg.hidden}], the same batch at every site, "
+                                         f"got {tuple(t.shape)}")
+                    m.mask_rows = rows
+                    keep.append(t)
+                    m.mask[i] = t.data_ptr()
+                if k is not None:
+                    k = np.ascontiguousarray(k, dtype=np.uint32)
+                    keep.append(k)
+                    m.key[i] = k.ctypes.data
 
         def dev(name, dtype):
             t = noise.get(name)
@@ -151,7 +178,10 @@ class AgentCore(Handle):
                       dev("eps_temp", torch.float32), dev("mask_next_temp", torch.uint8),
                       key("key_eps_next"), key("key_mask_next"), key("key_eps_pi"), key("key_mask_obs_pi"),
                       key("key_eps_temp"), key("key_mask_next_temp"))
-        self._keep = (keep, n)
+        self._keep = (keep, n, m)
+        # bound last, once nothing above can raise any more: the call this noise goes to consumes the binding
+        if m is not None:
+            _lib.check(self.L.serl_agent_set_mlp_noise(self._h, C.byref(m)))
         return C.byref(n)
 
     def update_critics(self, batch, noise=None):

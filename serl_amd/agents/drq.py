@@ -174,13 +174,15 @@ class DrQAgent:
                    target_entropy: Optional[float] = None, backup_entropy: bool = False,
                    batch_size: int = 256, device: int = 0, learning_rate: float = 3e-4,
                    actor_optimizer_kwargs: dict = None, critic_optimizer_kwargs: dict = None,
-                   temperature_optimizer_kwargs: dict = None, param_init: str = "numpy", **kwargs):
+                   temperature_optimizer_kwargs: dict = None, param_init: str = "numpy", mlp_dropout: bool = False, **kwargs):
         """drq.py:104-242.  Only the configuration the reference's examples run is built natively:
         encoder_type="resnet-pretrained", use_proprio=True, REDQ subsample 2, tanh-squashed
         exp-parameterised policy, LayerNorm+tanh MLPs (utils/launcher.py:79-116) -- 256x256 there; critic_network_kwargs /
         policy_network_kwargs may give hidden_dims=[h, h], h a multiple of 64 in [64, 1024], the same in both, and
         activations "tanh" (when absent), "relu" or "swish" / "silu", by name or as a callable of that name, chosen per network
-        (mlp.py:19-31); other activations and a positive dropout_rate are refused.
+        (mlp.py:19-31); other activations and a positive dropout_rate are refused.  mlp_dropout=True switches MLP Dropout on: a
+        dropout_rate (a number below 1) in either network kwargs then puts Dropout in front of that MLP's two LayerNorms
+        (mlp.py:27-28; the critic's is DroQ) -- the update's losses draw, acting and evaluation never do.
         policy_kwargs: std_parameterization "exp", "softplus" or "uniform" (one trainable log_stds vector, no Dense_1) and
         tanh_squash_distribution True or False all run in the head kernels; "fixed" is refused.  A key that is absent, or
         policy_kwargs=None, means the launcher's value ("exp", True).
@@ -203,7 +205,8 @@ class DrQAgent:
         pk = policy_kwargs or {}
         std_param, squash = pinit.policy_mode(pk)
         hidden = pinit.mlp_hidden_width(critic_network_kwargs, policy_network_kwargs)
-        critic_act, policy_act = pinit.mlp_activations(critic_network_kwargs, policy_network_kwargs)
+        critic_act, policy_act = pinit.mlp_activations(critic_network_kwargs, policy_network_kwargs, mlp_dropout)
+        critic_drop, policy_drop = pinit.mlp_dropout_rates(critic_network_kwargs, policy_network_kwargs) if mlp_dropout else (0.0, 0.0)
         seed = int(np.asarray(rng).reshape(-1)[-1]) if not isinstance(rng, int) else rng
         image_keys = tuple(image_keys)
         img = np.asarray(observations[image_keys[0]])
@@ -234,7 +237,8 @@ class DrQAgent:
                          optimizers={k: {"warmup_steps": 0, **v} for k, v in opts.items()}, encoder_type=encoder_type,
                          critic_subsample_size=critic_subsample_size, backup_entropy=backup_entropy, num_stack=T,
                          hidden=hidden, std_parameterization=std_param, tanh_squash_distribution=squash,
-                         critic_activation=critic_act, policy_activation=policy_act)
+                         critic_activation=critic_act, policy_activation=policy_act,
+                         critic_dropout=critic_drop, policy_dropout=policy_drop)
         if init_ref.check_param_init(param_init):
             theta = init_ref.theta_reference(image_keys, H, W, S, A, rng, ensemble=critic_ensemble_size, encoder_type=encoder_type,
                                              temperature_init=temperature_init, device=device, num_stack=T, hidden=hidden,
@@ -250,7 +254,8 @@ class DrQAgent:
         config = dict(critic_ensemble_size=critic_ensemble_size, critic_subsample_size=critic_subsample_size,
                       discount=discount, soft_target_update_rate=soft_target_update_rate,
                       target_entropy=target_entropy, backup_entropy=backup_entropy, image_keys=image_keys,
-                      critic_activation=critic_act, policy_activation=policy_act)
+                      critic_activation=critic_act, policy_activation=policy_act,
+                      critic_dropout_rate=critic_drop, policy_dropout_rate=policy_drop)
         agent = cls(core, image_keys, config, seed)
         agent._opts = {k: {"warmup_steps": 0, **v} for k, v in opts.items()}
         if param_init == "reference":
@@ -375,7 +380,16 @@ class DrQAgent:
         """Keys of the learner call about to run, derived from state.rng (None when the device-hashed stream is selected)."""
         if self.rng_impl != "threefry":
             return None
-        return J.UpdateKeys(self._rng_key, self._DRQ_AUG if drq_aug is None else drq_aug, n_critic, has_actor_temp, combined)
+        return J.UpdateKeys(self._rng_key, self._DRQ_AUG if drq_aug is None else drq_aug, n_critic, has_actor_temp, combined,
+                            self._subsample_none)
+
+    @property
+    def _subsample_none(self):
+        """UpdateKeys' last argument: None without MLP Dropout (the keys the agent always derived), else whether
+        critic_subsample_size is None -- the online critic's Dropout rng then equals the target critic's (sac.py:143-176)"""
+        if self.core.critic_dropout <= 0 and self.core.policy_dropout <= 0:
+            return None
+        return int(self.core.cfg.critic_subsample_size) < 0
 
     @property
     def _noise_bufs(self):
@@ -700,7 +714,7 @@ class DrQAgent:
         self._sync_side_stream()
         if noise is None and self.rng_impl == "threefry":
             key = self._rng_key if rng is None else np.asarray(rng, np.uint32)
-            keys = J.UpdateKeys(key, False, 1, True, True)       # the split of update() with all three networks
+            keys = J.UpdateKeys(key, False, 1, True, True, self._subsample_none)       # the split of update() with all three networks
             drawn = dict(self.last_draws)     # (last_draws records what the last UPDATE drew: put back below)
             noise = self._call_noise.build(keys, db.batch, self.noise_form, want_critic=True, want_actor=True)
             self.last_draws.clear()

@@ -33,17 +33,20 @@ class SACAgent(DrQAgent):
                       target_entropy: Optional[float] = None, backup_entropy: bool = False,
                       actor_optimizer_kwargs: dict = None, critic_optimizer_kwargs: dict = None,
                       temperature_optimizer_kwargs: dict = None, batch_size: int = 256, device: int = 0, param_init: str = "numpy",
+                      mlp_dropout: bool = False,
                       **kwargs):
         """sac.py:486-542 -> create (:323-400).  Built natively: the configuration of utils/launcher.py:50-76
         (REDQ subsample 2, tanh-squashed exp-parameterised policy, LayerNorm+tanh 256x256 MLPs); hidden_dims=[h, h] in both
         network kwargs selects another width h, a multiple of 64 in [64, 1024], and activations "tanh" (when absent), "relu" or
-        "swish" / "silu" the activation of each network (mlp.py:19-31; others and a positive dropout_rate are refused).  policy_kwargs: std_parameterization "exp",
+        "swish" / "silu" the activation of each network (mlp.py:19-31; others and a positive dropout_rate are refused -- unless mlp_dropout=True: a dropout_rate below 1 then puts
+        Dropout in front of that network's two LayerNorms, mlp.py:27-28, DroQ in the critic).  policy_kwargs: std_parameterization "exp",
         "softplus" or "uniform" and tanh_squash_distribution True or False run in the head kernels ("fixed" is refused).
         param_init: "numpy" (default) or "reference" (the reference's own initialisers and keys, utils/init_ref.py)."""
         pk = policy_kwargs or {}
         std_param, squash = pinit.policy_mode(pk)
         hidden = pinit.mlp_hidden_width(critic_network_kwargs, policy_network_kwargs)
-        critic_act, policy_act = pinit.mlp_activations(critic_network_kwargs, policy_network_kwargs)
+        critic_act, policy_act = pinit.mlp_activations(critic_network_kwargs, policy_network_kwargs, mlp_dropout)
+        critic_drop, policy_drop = pinit.mlp_dropout_rates(critic_network_kwargs, policy_network_kwargs) if mlp_dropout else (0.0, 0.0)
         ao = {"learning_rate": 3e-4, "warmup_steps": 2000, **(actor_optimizer_kwargs or {})}     # sac.py:333-336
         co = {"learning_rate": 3e-4, "warmup_steps": 2000, **(critic_optimizer_kwargs or {})}    # sac.py:337-340
         to = {"learning_rate": 3e-4, **(temperature_optimizer_kwargs or {})}                     # sac.py:341-343
@@ -60,7 +63,8 @@ class SACAgent(DrQAgent):
                          optimizers={"actor": ao, "critic": co, "temperature": {"warmup_steps": 0, **to}},
                          critic_subsample_size=critic_subsample_size, backup_entropy=backup_entropy, hidden=hidden,
                          std_parameterization=std_param, tanh_squash_distribution=squash,
-                         critic_activation=critic_act, policy_activation=policy_act)
+                         critic_activation=critic_act, policy_activation=policy_act,
+                         critic_dropout=critic_drop, policy_dropout=policy_drop)
         if init_ref.check_param_init(param_init):
             theta = init_ref.theta_reference((), 0, 0, S, A, rng, ensemble=critic_ensemble_size, temperature_init=temperature_init,
                                              device=device, hidden=hidden, std_parameterization=std_param)
@@ -72,7 +76,8 @@ class SACAgent(DrQAgent):
         config = dict(critic_ensemble_size=critic_ensemble_size, critic_subsample_size=critic_subsample_size,
                       discount=discount, soft_target_update_rate=soft_target_update_rate,
                       target_entropy=target_entropy, backup_entropy=backup_entropy,
-                      critic_activation=critic_act, policy_activation=policy_act)
+                      critic_activation=critic_act, policy_activation=policy_act,
+                      critic_dropout_rate=critic_drop, policy_dropout_rate=policy_drop)
         agent = cls(core, (), config, seed)
         agent._opts = {"actor": ao, "critic": co, "temperature": {"warmup_steps": 0, **to}}
         if param_init == "reference":

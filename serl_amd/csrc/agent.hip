@@ -76,6 +76,12 @@ struct serl_agent {
   int pol_mode = kPolExp;            // ... as the head kernels take them
   int head_groups = 2;               // Dense layers of the policy head: (mean, log_std), or the mean alone with kPolUniform
   int critic_act = kActTanh, policy_act = kActTanh;   // serl_agent_create_mlp: the activation of each MLP's two LayerNorm rows (kAct*)
+  // serl_agent_create_dropout: the rate of the Dropout in front of each MLP's two LayerNorm rows (mlp.py:27-28); 0 = none.
+  // mlp_bound: what serl_agent_set_mlp_noise left for the next update / phase / dry-run call; mlp_cur: what the call in progress
+  // (mlp_depth > 0: its outermost entry point took the binding) reads.  MlpNoiseScope, below.
+  double critic_drop = 0.0, policy_drop = 0.0;
+  serl_mlp_noise mlp_bound{}, mlp_cur{};
+  int mlp_depth = 0;
   SmallWorkspace sws{};
   Offs o{};
   std::vector<Leaf> theta_leaves, trunk_leaves;
@@ -205,8 +211,8 @@ void build_layout(serl_agent* a) {
     }
   });
   o.enc0 = ch.first; o.cam_stride = ch.stride; o.cam = ch.dense;
-  o.c1 = add_dense_ln_leaves(L, off, "critic/w1", "critic/b1", "critic/ln1", N, a->XA, Hd, a->critic_act);
-  o.c2 = add_dense_ln_leaves(L, off, "critic/w2", "critic/b2", "critic/ln2", N, Hd, Hd, a->critic_act);
+  o.c1 = add_dense_ln_leaves(L, off, "critic/w1", "critic/b1", "critic/ln1", N, a->XA, Hd, a->critic_act, a->critic_drop);
+  o.c2 = add_dense_ln_leaves(L, off, "critic/w2", "critic/b2", "critic/ln2", N, Hd, Hd, a->critic_act, a->critic_drop);
   // DrQ: one Dense(1) head shared by the ensemble (drq.py:201-207); state-only SAC: ensemblize vmaps the whole
   // Critic, so every member has its own head (actor_critic_nets.py:49-73,156-164)
   o.c_hw = add_leaf(L, off, "critic/head/kernel", a->state_only ? N * Hd : Hd);
@@ -217,8 +223,8 @@ void build_layout(serl_agent* a) {
                                  c.proprio_dim, kActTanh);
   }
   o.Pc = off;
-  o.a1 = add_dense_ln_leaves(L, off, "actor/w1", "actor/b1", "actor/ln1", 1, a->E, Hd, a->policy_act);
-  o.a2 = add_dense_ln_leaves(L, off, "actor/w2", "actor/b2", "actor/ln2", 1, Hd, Hd, a->policy_act);
+  o.a1 = add_dense_ln_leaves(L, off, "actor/w1", "actor/b1", "actor/ln1", 1, a->E, Hd, a->policy_act, a->policy_drop);
+  o.a2 = add_dense_ln_leaves(L, off, "actor/w2", "actor/b2", "actor/ln2", 1, Hd, Hd, a->policy_act, a->policy_drop);
   o.a_Wm = add_leaf(L, off, "actor/mean/kernel", Hd * A);
   o.a_bm = add_leaf(L, off, "actor/mean/bias", A);
   a->pol_mode = a->std_param | (a->no_tanh ? kPolNoTanh : 0);
@@ -457,7 +463,7 @@ DenseLnGrad mlp_grad(const DenseLn& L, const GradBuf& s, int rows, bool dy_here 
 // Layer L forward on `rows` rows per group for n independent instances of identical shape (instance i: parameters and tensors of
 // job i, split-K scratch slabs_lane[i]): one grouped GEMM launch, K-split `smax` deep at the most, and one LayerNorm launch.
 struct RowDot { const float *w, *b; float* out; long w_gs, b_gs; };   // rider of the LayerNorm launch: out[row] = y . w + b (critic head); *_gs: per-group heads, 0 = shared
-struct LayerJob { const float* P; DenseLnIo t; RowDot dot; };
+struct LayerJob { const float* P; DenseLnIo t; RowDot dot; DenseLnDrop drop; };   // drop: the evaluation's Dropout site (zero: train=False)
 int dense_ln_multi(serl_agent* a, const DenseLn& L, const LayerJob* jobs, int n, int rows, int smax, hipStream_t st) {
   SERL_REQUIRE(n >= 1 && n <= 3, "bad dense instance count");
   const int splitk = split_for(a->split_budget, rows, L.N, L.groups * n, smax);
@@ -469,7 +475,7 @@ int dense_ln_multi(serl_agent* a, const DenseLn& L, const LayerJob* jobs, int n,
   for (int i = 0; i < n; ++i) {
     const LayerJob& j = jobs[i];
     gd[i] = layer_fwd(L, j.P, j.t, rows, a->slabs_lane[i], splitk);
-    lv[i] = layer_ln_fwd(L, j.P, j.t, rows, gd[i]);
+    lv[i] = layer_ln_fwd(L, j.P, j.t, rows, gd[i], j.drop);
     lv[i].dot_w = j.dot.w; lv[i].dot_b = j.dot.b; lv[i].dot_out = j.dot.out;
     lv[i].dot_gstride = j.dot.w_gs; lv[i].dot_b_gstride = j.dot.b_gs;
   }
@@ -488,6 +494,7 @@ struct PolJob {
   // fused chain, eps == nullptr: the draws are hashed inside the head kernel from (eps_seed, global row) and kept in eps_out
   float* eps_out = nullptr; uint64_t eps_seed = 0; long eps_row0 = 0;
   const uint32_t* tf_key = nullptr; long tf_rows = 0, tf_row0 = 0;   // jax.random.normal(tf_key, (tf_rows, A)) rows tf_row0.. (serl_noise key_eps_*)
+  DenseLnDrop drop[2] = {};   // the Dropout sites of the two MLP layers (zero: train=False)
 };
 int policy_fwd_multi(serl_agent* a, const PolJob* jobs, int n, int cnt, hipStream_t st) {
   const serl_agent_cfg& c = a->cfg;
@@ -501,8 +508,8 @@ int policy_fwd_multi(serl_agent* a, const PolJob* jobs, int n, int cnt, hipStrea
     const PolJob& j = jobs[i];
     const float* P = j.P;
     PolBuf& pb = *j.pb;
-    d1[i] = LayerJob{P, mlp_io(o.a1, j.enc, j.ld_enc, pb.m.l1, cnt), {}};
-    d2[i] = LayerJob{P, mlp_io(o.a2, pb.m.l1, pb.m.l2, cnt), {}};
+    d1[i] = LayerJob{P, mlp_io(o.a1, j.enc, j.ld_enc, pb.m.l1, cnt), {}, j.drop[0]};
+    d2[i] = LayerJob{P, mlp_io(o.a2, pb.m.l1, pb.m.l2, cnt), {}, j.drop[1]};
     // The head is no layer of the six (no LayerNorm): (mean, log_std) as two groups of one GEMM, the mean alone when log_stds is
     // a parameter vector (the stride is then unused)
     gd[i] = gemm_fwd(pb.m.l2.h, Hd, 0, P + o.a_Wm, o.a_bs - o.a_bm, a->slabs_lane[i], a->head_groups, cnt, A, Hd, 4);
@@ -543,7 +550,7 @@ int policy_fwd_multi(serl_agent* a, const PolJob* jobs, int n, int cnt, hipStrea
 
 // Critic ensemble forward on x = [enc | action] (actor_critic_nets.py:56-73, drq.py:201-207) for n independent
 // (parameters, input) pairs; the shared Q head is fused into the LN kernel of layer 2
-struct CritJob { const float* P; CritBuf* cb; };
+struct CritJob { const float* P; CritBuf* cb; DenseLnDrop drop[2]; };   // drop: the Dropout sites of the two layers (zero: train=False)
 int critic_fwd_multi(serl_agent* a, const CritJob* jobs, int n, int cnt, hipStream_t st) {
   const serl_agent_cfg& c = a->cfg;
   const Offs& o = a->o;
@@ -552,9 +559,9 @@ int critic_fwd_multi(serl_agent* a, const CritJob* jobs, int n, int cnt, hipStre
   for (int i = 0; i < n; ++i) {
     const float* P = jobs[i].P;
     CritBuf& cb = *jobs[i].cb;
-    d1[i] = LayerJob{P, mlp_io(o.c1, cb.x, a->XA, cb.m.l1, cnt), {}};
+    d1[i] = LayerJob{P, mlp_io(o.c1, cb.x, a->XA, cb.m.l1, cnt), {}, jobs[i].drop[0]};
     d2[i] = LayerJob{P, mlp_io(o.c2, cb.m.l1, cb.m.l2, cnt),
-                     RowDot{P + o.c_hw, P + o.c_hb, cb.q, a->state_only ? c.hidden : 0, a->state_only ? 1 : 0}};
+                     RowDot{P + o.c_hw, P + o.c_hb, cb.q, a->state_only ? c.hidden : 0, a->state_only ? 1 : 0}, jobs[i].drop[1]};
   }
   RC(dense_ln_multi(a, o.c1, d1, n, cnt, 4, st));
   return dense_ln_multi(a, o.c2, d2, n, cnt, 2, st);
@@ -582,8 +589,8 @@ struct HeadDq {   // dy[row][col] = dq[row] * w[col] formed in the launch (rank-
   const float* dq; const float* w; float dq_const; long w_gs; const LossArgs* loss;
 };
 int dense_ln_bwd(serl_agent* a, const DenseLn& L, const float* P, const DenseLnIo& t, const DenseLnGrad& d, int rows, float* G,
-                 hipStream_t st, const HeadDq* head = nullptr) {
-  LnBwdArgs l = layer_ln_bwd(L, P, t, d, rows);
+                 hipStream_t st, const HeadDq* head = nullptr, const DenseLnDrop& site = DenseLnDrop{}) {
+  LnBwdArgs l = layer_ln_bwd(L, P, t, d, rows, site);
   if (head) { l.dq = head->dq; l.dq_w = head->w; l.dq_const = head->dq_const; l.dq_w_gstride = head->w_gs; }
   if (head && head->loss) {   // the critic loss rides on this launch and every row derives its dQ from the loss arguments (no critic_loss launch)
     l.dq_inline = 1;
@@ -671,7 +678,9 @@ int head_bias_grad(serl_agent* a, int cnt, float* out, long out_gstride, hipStre
 
 // Critic backward down to dx [cnt][E+A]; parameter grads into Gc when `pg`.  The gradient wrt Q [ens][cnt] is the dq of the
 // critic loss `loss` (critic phase), or the constant `dq_const` for every element (actor loss, loss == nullptr).
-int critic_bwd(serl_agent* a, const float* P, CritBuf& cb, int cnt, bool pg, hipStream_t st, const LossArgs* loss, float dq_const) {
+// `sites`: the two layers' Dropout sites of the forward pass whose activations `cb` holds.
+int critic_bwd(serl_agent* a, const float* P, CritBuf& cb, int cnt, bool pg, hipStream_t st, const LossArgs* loss, float dq_const,
+               const DenseLnDrop* sites) {
   const serl_agent_cfg& c = a->cfg;
   const Offs& o = a->o;
   float* G = pg ? a->Gc : nullptr;
@@ -681,9 +690,9 @@ int critic_bwd(serl_agent* a, const float* P, CritBuf& cb, int cnt, bool pg, hip
   const DenseLnGrad d2 = mlp_grad(o.c2, a->s2, cnt, false), d1 = mlp_grad(o.c1, a->s1, cnt);
   // layer 2: the gradient through the head dh2 = dq (x) w is formed inside the LN backward kernel (rank-1 mode)
   const HeadDq head{loss ? loss->dq : nullptr, P + o.c_hw, dq_const, a->state_only ? c.hidden : 0, rider};
-  RC(dense_ln_bwd(a, o.c2, P, mlp_io(o.c2, cb.m.l1, cb.m.l2, cnt), d2, cnt, G, st, &head));
+  RC(dense_ln_bwd(a, o.c2, P, mlp_io(o.c2, cb.m.l1, cb.m.l2, cnt), d2, cnt, G, st, &head, sites[1]));
   RC(gemm_f32(layer_igrad(o.c2, P, d2, cnt, d1), st));
-  RC(dense_ln_bwd(a, o.c1, P, mlp_io(o.c1, cb.x, a->XA, cb.m.l1, cnt), d1, cnt, G, st));
+  RC(dense_ln_bwd(a, o.c1, P, mlp_io(o.c1, cb.x, a->XA, cb.m.l1, cnt), d1, cnt, G, st, nullptr, sites[0]));
   // dx = sum_e da1[e] * W1[e]^T
   return igrad_sum(a, layer_igrad(o.c1, P, d1, cnt, nullptr, 0, 0), a->dx, a->XA, st);
 }
@@ -814,6 +823,42 @@ void set_noise(const serl_agent* a, EncJob& e, PolJob& p, const PhaseNoise& z, l
   p.tf_key = z.tf_eps; p.tf_rows = global_count; p.tf_row0 = tf_row0;
 }
 
+// The Dropout sites of the two layers of MLP evaluation `site` (SERL_SITE_*) on rows [off, off + cnt) of the selected batch, at
+// rate `rate` (0: nothing is read and the agent's noise stream does not move -- a rate-0 agent draws what it always drew).  Each
+// layer: the bound mask, else the bound key (`key_row`: the critic update of a high-UTD call, for the critic-loss sites), else a
+// seed of the agent's own stream, one per (site, layer) in call order, which every rank of a data-parallel job takes alike.
+void mlp_sites(serl_agent* a, int site, double rate, int off, int cnt, long global_count, int key_row, DenseLnDrop (&out)[2]) {
+  out[0] = out[1] = DenseLnDrop{};
+  if (!(rate > 0.0)) return;
+  const serl_mlp_noise& z = a->mlp_cur;
+  const long Hd = a->cfg.hidden;
+  for (int l = 0; l < 2; ++l) {
+    DenseLnDrop& d = out[l];
+    d.train = 1;
+    if (z.mask[site]) d.mask = z.mask[site] + ((long)l * a->cur.batch + off) * Hd;
+    else if (z.key[site]) { d.key = z.key[site] + ((long)key_row * 2 + l) * 2; d.key_rows = global_count; d.key_row0 = tf_row0_of(a, cnt); }
+    else { d.seed = a->cfg.seed ^ (0xD0D0ull + 15485863ull * (++a->noise_ctr)); d.hash_row0 = a->shard_off + off; }
+  }
+}
+// the bound mask tensors are laid out for the rows of the selected batch
+int mlp_masks_fit(const serl_agent* a) {
+  for (int s = 0; s < SERL_MLP_SITES; ++s)
+    SERL_REQUIRE(!a->mlp_cur.mask[s] || a->mlp_cur.mask_rows == a->cur.batch,
+                 "serl_mlp_noise: the masks of site %d hold %d rows per layer, the batch has %d", s, a->mlp_cur.mask_rows, a->cur.batch);
+  return SERL_OK;
+}
+// The outermost update / phase / dry-run entry point takes the serl_agent_set_mlp_noise binding; the entry points it calls read
+// the same one; when it returns, on every path, the binding is gone.
+struct MlpNoiseScope {
+  serl_agent* a;
+  explicit MlpNoiseScope(serl_agent* a_) : a(a_) {
+    if (a && a->mlp_depth++ == 0) { a->mlp_cur = a->mlp_bound; a->mlp_bound = serl_mlp_noise{}; }
+  }
+  ~MlpNoiseScope() {
+    if (a && --a->mlp_depth == 0) a->mlp_cur = serl_mlp_noise{};
+  }
+};
+
 // learning rate of optimizer `tx` at `count` (optimizers.py:14-30): warm-up -> constant, or warm-up -> cosine decay
 float lr_at(const serl_agent_cfg& c, int64_t count, int tx) {
   const float peak = (c.tx_lr_set[tx] || c.tx_lr[tx] > 0.f) ? c.tx_lr[tx] : c.lr;
@@ -841,7 +886,17 @@ int serl_agent_create_policy(const serl_agent_cfg* cfg, int std_param, int no_ta
 // mlp.py:19-31: MLP applies `activations` (a callable, or the name of one in flax.linen) behind every LayerNorm; the critic and the
 // policy get theirs from two separate kwargs dicts, so the two codes are independent.
 int serl_agent_create_mlp(const serl_agent_cfg* cfg, int std_param, int no_tanh, int critic_act, int policy_act, serl_agent** out) {
+  return serl_agent_create_dropout(cfg, std_param, no_tanh, critic_act, policy_act, 0.0, 0.0, out);
+}
+
+// mlp.py:27-28: Dense -> Dropout(dropout_rate) -> LayerNorm -> activation in both hidden layers of each MLP, the rate from the
+// network's own kwargs dict; sac.py:137-176,197-207: every loss runs its forwards with train=True.
+int serl_agent_create_dropout(const serl_agent_cfg* cfg, int std_param, int no_tanh, int critic_act, int policy_act, double critic_dropout,
+                              double policy_dropout, serl_agent** out) {
   SERL_REQUIRE(cfg && out, "NULL argument");
+  // (the keep probability float32(1 - rate) must itself lie below 1 and above 0)
+  SERL_REQUIRE(critic_dropout >= 0.0 && (float)(1.0 - critic_dropout) > 0.f, "critic_dropout %g: a Dropout rate lies in [0, 1)", critic_dropout);
+  SERL_REQUIRE(policy_dropout >= 0.0 && (float)(1.0 - policy_dropout) > 0.f, "policy_dropout %g: a Dropout rate lies in [0, 1)", policy_dropout);
   SERL_REQUIRE(cfg->n_cam >= 0 && cfg->n_cam <= SERL_MAX_CAMS, "n_cam %d not in [0,%d]", cfg->n_cam, SERL_MAX_CAMS);
   SERL_REQUIRE(cfg->n_cam == 0 || (cfg->H >= 32 && cfg->W >= 32), "images must be at least 32x32");
   SERL_REQUIRE(cfg->encoder_type == SERL_ENCODER_RESNET_PRETRAINED || cfg->encoder_type == SERL_ENCODER_SMALL,
@@ -884,6 +939,7 @@ int serl_agent_create_mlp(const serl_agent_cfg* cfg, int std_param, int no_tanh,
   a->cfg.num_stack = num_stack;
   a->std_param = std_param; a->no_tanh = no_tanh;
   a->critic_act = critic_act; a->policy_act = policy_act;
+  a->critic_drop = critic_dropout; a->policy_drop = policy_dropout;
   { const char* e = getenv("SERL_CHAIN_FUSE"); a->fuse = !(e && e[0] == '0'); }
   build_layout(a);
   a->live = any_wd && a->trunk_count > 0;
@@ -1175,6 +1231,14 @@ int serl_agent_begin_update(serl_agent* a, void* stream) {
   return SERL_OK;
 }
 
+// mlp.py:27-28; sac.py:137-176,197-207: the Dropout draws of the next update / phase / dry-run call (serl_mi355.h)
+int serl_agent_set_mlp_noise(serl_agent* a, const serl_mlp_noise* noise) {
+  SERL_REQUIRE(a, "NULL agent");
+  SERL_REQUIRE(a->mlp_depth == 0, "serl_agent_set_mlp_noise inside an update");
+  a->mlp_bound = noise ? *noise : serl_mlp_noise{};
+  return SERL_OK;
+}
+
 int serl_agent_set_shard(serl_agent* a, int64_t global_offset, int64_t global_batch) {
   SERL_REQUIRE(a, "NULL agent");
   SERL_REQUIRE(global_batch == 0 || (global_offset >= 0 && global_offset < global_batch), "bad shard [%lld of %lld]",
@@ -1296,8 +1360,10 @@ int serl_agent_grad_bucket(serl_agent* a, int bucket, float** dev_ptr, int64_t* 
 
 int serl_agent_critic_grads_bucketed(serl_agent* a, int off, int cnt, int global_count, const serl_noise* noise,
                                      int redq_row, void* stream, void* event_bucket0) {
+  MlpNoiseScope mlp_scope(a);
   SERL_REQUIRE(a && a->has_batch, "serl_agent_encode must run first");
   SERL_REQUIRE(off >= 0 && cnt >= 1 && off + cnt <= a->cur.batch && global_count >= cnt, "bad minibatch range");
+  RC(mlp_masks_fit(a));
   if (a->cls && !a->labelled && !a->label_exempt) {
     set_error("a reward classifier is attached: serl_agent_label_rewards must follow serl_agent_select_slot (vice.py:594)");
     return SERL_ERR_STATE;
@@ -1342,16 +1408,20 @@ int serl_agent_critic_grads_bucketed(serl_agent* a, int off, int cnt, int global
   PolJob pj{a->theta, &a->pol, a->encP.enc, a->encP.ld, nullptr, a->critT.x + a->E, a->XA, nullptr,
             c.backup_entropy ? a->aux + X_ALPHA : nullptr};
   set_noise(a, ej[0], pj, nz, off, cnt, global_count);
+  // the MLPs' Dropout in the reference's draw order (sac.py:137-176): policy at next_obs, target critic, online critic
+  CritJob cj[2] = {{a->theta_t, &a->critT, {}}, {a->theta, &a->crit, {}}};  // target and online ensembles together
+  mlp_sites(a, SERL_SITE_PI_NEXT, a->policy_drop, off, cnt, global_count, redq_row, pj.drop);
+  mlp_sites(a, SERL_SITE_Q_TARGET, a->critic_drop, off, cnt, global_count, redq_row, cj[0].drop);
+  mlp_sites(a, SERL_SITE_Q_ONLINE, a->critic_drop, off, cnt, global_count, redq_row, cj[1].drop);
   RC(encode_multi(a, ej, 3, off, cnt, st));
   RC(policy_fwd_multi(a, &pj, 1, cnt, st));
-  const CritJob cj[2] = {{a->theta_t, &a->critT}, {a->theta, &a->crit}};  // target and online ensembles together
   RC(critic_fwd_multi(a, cj, 2, cnt, st));
   const float* reward = a->labelled ? a->labels : a->cur.reward;   // vice.py:594: the labels stand in for the stored rewards
   const LossArgs L{1, a->critT.q, a->crit.q, reward + off, a->cur.mask + off, sel, c.ensemble, cnt, c.discount,
                    1.0f / ((float)c.ensemble * (float)global_count), a->ytgt, a->dq, a->SC, a->Gc + o.c_hb, a->state_only ? 1 : 0,
                    c.backup_entropy ? a->pol.logp : nullptr, c.backup_entropy ? a->aux + X_ALPHA : nullptr};
   SERL_REQUIRE(!a->state_only || c.ensemble <= 16, "per-member head bias supports ensembles of at most 16");
-  RC(critic_bwd(a, a->theta, a->crit, cnt, true, st, &L, 0.f));
+  RC(critic_bwd(a, a->theta, a->crit, cnt, true, st, &L, 0.f, cj[1].drop));
   RC(enc_bwd_critic(a, a->theta, a->encO, off, cnt, st, event_bucket0));
   RC(flush_param_grads(a, st));
   a->last_global = global_count;
@@ -1359,6 +1429,7 @@ int serl_agent_critic_grads_bucketed(serl_agent* a, int off, int cnt, int global
 }
 
 int serl_agent_actor_grads(serl_agent* a, int global_count, const serl_noise* noise, void* stream) {
+  MlpNoiseScope mlp_scope(a);
   SERL_REQUIRE(a && a->has_batch, "serl_agent_encode must run first");
   const serl_agent_cfg& c = a->cfg;
   const Offs& o = a->o;
@@ -1366,6 +1437,7 @@ int serl_agent_actor_grads(serl_agent* a, int global_count, const serl_noise* no
   SERL_HIP(hipSetDevice(c.device));
   const int cnt = a->cur.batch, A = c.act_dim, Hd = c.hidden;
   SERL_REQUIRE(global_count >= cnt, "global_count < local batch");
+  RC(mlp_masks_fit(a));
   a->pg_ncs = a->pg_nwg = 0;
   a->pg_defer = true;
   enum { PI = 0, TEMP = 1 };   // noise of the policy loss (slot 1) and of the temperature loss (slot 2), drawn in this order
@@ -1384,12 +1456,16 @@ int serl_agent_actor_grads(serl_agent* a, int global_count, const serl_noise* no
                   {a->theta, &a->pol, a->encP.enc, a->encP.ld, nullptr, a->crit.x + a->E, a->XA, a->SC + S_LOGP, nullptr}};
   set_noise(a, ej[0], pj[0], nz[TEMP], 0, cnt, global_count);
   set_noise(a, ej[2], pj[1], nz[PI], 0, cnt, global_count);
+  // the MLPs' Dropout (sac.py:197-207,222-227): policy at obs, the critic inside the actor loss, policy at next_obs
+  CritJob cj{a->theta, &a->crit, {}};
+  mlp_sites(a, SERL_SITE_PI, a->policy_drop, 0, cnt, global_count, 0, pj[1].drop);
+  mlp_sites(a, SERL_SITE_Q_ACTOR, a->critic_drop, 0, cnt, global_count, 0, cj.drop);
+  mlp_sites(a, SERL_SITE_PI_TEMP, a->policy_drop, 0, cnt, global_count, 0, pj[0].drop);
   RC(encode_multi(a, ej, 3, 0, cnt, st));
   RC(policy_fwd_multi(a, pj, 2, cnt, st));
   const float* eps_pi = nz[PI].eps ? nz[PI].eps : nz[PI].eps_out;   // (the backward reads the draws the head used)
-  const CritJob cj{a->theta, &a->crit};
   RC(critic_fwd_multi(a, &cj, 1, cnt, st));
-  RC(critic_bwd(a, a->theta, a->crit, cnt, false, st, nullptr, -1.0f / ((float)c.ensemble * (float)global_count)));
+  RC(critic_bwd(a, a->theta, a->crit, cnt, false, st, nullptr, -1.0f / ((float)c.ensemble * (float)global_count), cj.drop));
   RC(policy_dist_bwd(a->dx + a->E, a->XA, a->crit.x + a->E, a->XA, a->pol.pre, a->pol.std, eps_pi, a->aux + X_ALPHA,
                      1.0f / (float)global_count, cnt, A, c.std_min, c.std_max, a->dpre, a->crit.q, c.ensemble,
                      a->SC + S_QPI, st, a->pol_mode));
@@ -1406,9 +1482,9 @@ int serl_agent_actor_grads(serl_agent* a, int global_count, const serl_noise* no
   RC(head_bias_grad(a, cnt, Ga + o.a_bm, hs, st));
   // dh2 = dmean W_mean^T + dlog_std W_logstd^T (no second term when the log-std has no Dense)
   RC(igrad_sum(a, gemm_igrad(a->dpre, A, (long)cnt * A, P + o.a_Wm, A, hs, nullptr, 0, 0, hg, cnt, Hd, A), d2.dy, d2.ld_dy, st));
-  RC(dense_ln_bwd(a, o.a2, P, t2, d2, cnt, Ga, st));
+  RC(dense_ln_bwd(a, o.a2, P, t2, d2, cnt, Ga, st, nullptr, pj[1].drop[1]));
   RC(gemm_f32(layer_igrad(o.a2, P, d2, cnt, d1), st));
-  RC(dense_ln_bwd(a, o.a1, P, t1, d1, cnt, Ga, st));
+  RC(dense_ln_bwd(a, o.a1, P, t1, d1, cnt, Ga, st, nullptr, pj[1].drop[0]));
   // image codes are stop-gradiented (encoding.py:48-49); only the proprio slice of d_enc is needed: the rows of W1 that the
   // proprio columns multiply, a slice of layer 1's kernel and therefore written out
   if (!a->state_only) {
@@ -1487,6 +1563,7 @@ int serl_agent_grad_view(serl_agent* a, int which, float** dev_ptr, int64_t* cou
 }
 
 int serl_agent_update(serl_agent* a, const serl_batch* batch, int nets, const serl_noise* noise, void* stream) {
+  MlpNoiseScope mlp_scope(a);
   SERL_REQUIRE(a && batch, "NULL argument");
   SERL_REQUIRE(nets >= 1 && nets <= 7, "Invalid gradient steps: %d", nets);   // sac.py:272-274
   RC(serl_agent_begin_update(a, stream));
@@ -1498,6 +1575,7 @@ int serl_agent_update(serl_agent* a, const serl_batch* batch, int nets, const se
 }
 
 int serl_agent_update_critics(serl_agent* a, const serl_batch* batch, const serl_noise* noise, void* stream) {
+  MlpNoiseScope mlp_scope(a);
   SERL_REQUIRE(a, "NULL agent");
   RC(check_label_fresh(a));
   RC(serl_agent_begin_update(a, stream));
@@ -1509,6 +1587,7 @@ int serl_agent_update_critics(serl_agent* a, const serl_batch* batch, const serl
 
 int serl_agent_update_high_utd(serl_agent* a, const serl_batch* batch, int utd_ratio, const serl_noise* noise,
                                void* stream) {
+  MlpNoiseScope mlp_scope(a);
   SERL_REQUIRE(a && batch, "NULL argument");
   SERL_REQUIRE(utd_ratio >= 1 && batch->batch % utd_ratio == 0,
                "Batch size %d must be divisible by UTD ratio %d", batch->batch, utd_ratio);  // sac.py:561-563
@@ -1625,7 +1704,7 @@ int serl_agent_eval_q(serl_agent* a, const uint8_t* dev_frames, const float* dev
   const float* P = target ? a->theta_t : a->theta;
   CritBuf& cb = target ? a->critT : a->crit;
   RC(eval_encode(a, dev_frames, dev_state, n, P, target ? &a->encT : &a->encO, dev_actions, cb.x + a->E, st));
-  const CritJob cj{P, &cb};
+  const CritJob cj{P, &cb, {}};   // train=False: no Dropout
   RC(critic_fwd_multi(a, &cj, 1, n, st));
   SERL_HIP(hipMemcpyAsync(dev_q_out, cb.q, sizeof(float) * c.ensemble * n, hipMemcpyDeviceToDevice, st));   // [ensemble][n]
   return SERL_OK;
@@ -1646,7 +1725,7 @@ int serl_agent_eval_policy(serl_agent* a, const uint8_t* dev_frames, const float
   // the policy MLP as policy_fwd_multi runs it; the head always as a plain K-split GEMM whose slabs policy_stats_kernel reads
   // (whatever a->fuse says: the fused epilogue samples, and this call draws nothing)
   PolBuf& pb = a->pol;
-  const LayerJob d1{P, mlp_io(o.a1, a->encP.enc, a->encP.ld, pb.m.l1, n), {}}, d2{P, mlp_io(o.a2, pb.m.l1, pb.m.l2, n), {}};
+  const LayerJob d1{P, mlp_io(o.a1, a->encP.enc, a->encP.ld, pb.m.l1, n), {}, {}}, d2{P, mlp_io(o.a2, pb.m.l1, pb.m.l2, n), {}, {}};
   RC(dense_ln_multi(a, o.a1, &d1, 1, n, 8, st));
   RC(dense_ln_multi(a, o.a2, &d2, 1, n, 4, st));
   const GemmDesc g = gemm_fwd(pb.m.l2.h, c.hidden, 0, P + o.a_Wm, o.a_bs - o.a_bm, a->slabs_lane[0], a->head_groups, n, c.act_dim,
@@ -1661,6 +1740,7 @@ int serl_agent_eval_policy(serl_agent* a, const uint8_t* dev_frames, const float
 }
 
 int serl_agent_eval_losses(serl_agent* a, const serl_batch* batch, const serl_noise* noise, serl_info* host_out, void* stream) {
+  MlpNoiseScope mlp_scope(a);
   SERL_REQUIRE(a && batch && host_out, "NULL argument");
   RC(check_batch(a, batch));
   const serl_agent_cfg& c = a->cfg;
@@ -1747,6 +1827,17 @@ int serl_agent_debug_get(serl_agent* a, const char* what, float* host_out, int64
   else if (w == "logp") { p = a->pol.logp; n = c.batch; }
   else if (w == "std") { p = a->pol.std; n = (long)c.batch * c.act_dim; }   // clipped std [rows][A] of the last policy evaluation in `pol`
   else if (w == "dx") { p = a->dx; n = (long)c.batch * a->XA; }
+  // the MLP rows as the last phase left them: the normalised LayerNorm input of layer 1 / 2 of an MLP buffer ([rows][hidden], the
+  // critics' rows member-major), and the gradient wrt the Dense output of the layer-1 / layer-2 backward that ran last
+  else if (w.rfind("mlp_xhat/", 0) == 0 && w.size() == 16 && (w[15] == '1' || w[15] == '2')) {
+    const std::string buf = w.substr(9, 5);
+    const MlpBuf* m = buf == "pol__" ? &a->pol.m : buf == "polT_" ? &a->polT.m : buf == "crit_" ? &a->crit.m : buf == "critT" ? &a->critT.m : nullptr;
+    if (!m) { set_error("unknown debug tap '%s'", what); return SERL_ERR_INVALID; }
+    p = (w[15] == '1' ? m->l1 : m->l2).xhat;
+    n = (long)(buf[0] == 'c' ? c.ensemble : 1) * c.batch * c.hidden;
+  }
+  else if (w == "mlp_dpre/1") { p = a->s1.dpre; n = (long)c.ensemble * c.batch * c.hidden; }
+  else if (w == "mlp_dpre/2") { p = a->s2.dpre; n = (long)c.ensemble * c.batch * c.hidden; }
   // SmallEncoder layer 0's ReLU output of the LAST encoder pass, [n_cam][images of that pass][h1][w1][32]
   else if (w == "small_act0" && a->small) { p = a->sws.act[0]; n = (long)c.n_cam * c.batch * a->sws.d.h[1] * a->sws.d.w[1] * kSmallFeat[1]; }
   else { set_error("unknown debug tap '%s'", what); return SERL_ERR_INVALID; }

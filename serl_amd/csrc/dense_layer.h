@@ -12,17 +12,39 @@ struct DenseLn {
   long W, b, g, be;      // group 0's kernel [K][N], bias, LayerNorm scale and LayerNorm bias: offsets into a parameter vector
   long w_gs, p_gs;       // floats from one group's kernel, and from one group's three vectors, to the next group's
   int groups, K, N, act; // act: kAct*
+  float keep;            // Dropout between Dense and LayerNorm (mlp.py:27-28): float32(1 - rate), the rate a double in (0, 1) as the
+                         // reference's keep_prob = 1.0 - rate is one -- what its bernoulli compares with and its division divides by; 0: none
 };
+// Where the keep decisions of ONE evaluation (a "site") of a Dropout layer come from, in this order of preference:
+struct DenseLnDrop {   // (of a layer with keep > 0)
+  int train;               // 0: train=False, no Dropout in this evaluation (the zero-initialised site)
+  const uint8_t* mask;     // a device keep-mask u8 [rows][N] of the evaluation's rows (one mask for every group), or
+  const uint32_t* key;     // a host jax.random key: bernoulli(key, keep, (key_rows, N)), rows key_row0.., or
+  uint64_t seed;           // the hash stream `seed`, indexed by the global row: local row 0 is row hash_row0
+  long key_rows, key_row0, hash_row0;
+};
+// the layer's Dropout as the LayerNorm rows take it (forward and backward alike); a layer without Dropout ignores the site, and
+// a train=False evaluation drops nothing
+inline LnDrop layer_drop(const DenseLn& L, const DenseLnDrop& s) {
+  LnDrop d{};
+  if (!(L.keep > 0.f) || !s.train) return d;
+  d.keep = L.keep;
+  if (s.mask) { d.mode = kLnDropMask; d.mask = s.mask; }
+  else if (s.key) { d.mode = kLnDropKey; d.key[0] = s.key[0]; d.key[1] = s.key[1]; d.total_rows = s.key_rows; d.row0 = s.key_row0; }
+  else { d.mode = kLnDropHash; d.seed = s.seed; d.row0 = s.hash_row0; }
+  return d;
+}
 // Appends the layer's four leaves -- `groups` kernels, biases, scales and shifts back to back in each -- at `off`, which moves
 // behind them.
 inline DenseLn add_dense_ln_leaves(std::vector<Leaf>& v, long& off, const std::string& kernel, const std::string& bias,
-                                   const std::string& ln, int groups, int K, int N, int act) {
+                                   const std::string& ln, int groups, int K, int N, int act, double drop = 0.0) {
   DenseLn l{};
   l.W = add_leaf(v, off, kernel, (long)groups * K * N);
   l.b = add_leaf(v, off, bias, (long)groups * N);
   l.g = add_leaf(v, off, ln + "/scale", (long)groups * N);
   l.be = add_leaf(v, off, ln + "/bias", (long)groups * N);
   l.w_gs = groups > 1 ? (long)K * N : 0; l.p_gs = groups > 1 ? N : 0; l.groups = groups; l.K = K; l.N = N; l.act = act;
+  l.keep = drop > 0.0 ? (float)(1.0 - drop) : 0.f;
   return l;
 }
 
@@ -41,26 +63,31 @@ inline GemmDesc layer_fwd(const DenseLn& L, const float* P, const DenseLnIo& t, 
   return gemm_fwd(t.x, t.ldx, t.x_gs, P + L.W, L.w_gs, slabs, L.groups, rows, L.N, L.K, splitk);
 }
 // the LayerNorm + activation launch that sums the slabs of `g` = layer_fwd(...)
-inline LnFwdArgs layer_ln_fwd(const DenseLn& L, const float* P, const DenseLnIo& t, int rows, const GemmDesc& g) {
+inline LnFwdArgs layer_ln_fwd(const DenseLn& L, const float* P, const DenseLnIo& t, int rows, const GemmDesc& g,
+                              const DenseLnDrop& site = DenseLnDrop{}) {
   LnFwdArgs l{};
   l.slabs = g.C; l.S = g.splitk; l.slab_stride = g.sCz;
   l.bias = P + L.b; l.gamma = P + L.g; l.beta = P + L.be; l.pstride = L.p_gs;
   l.rows = L.groups * rows; l.rows_per_group = rows;
   l.y = t.y; l.ld_y = t.ld_y; l.y_goff = t.y_goff;
   l.xhat = t.xhat; l.rstd = t.rstd; l.act = L.act;
+  l.drop = layer_drop(L, site);
   return l;
 }
 // The proprio branch runs its forward as one row kernel, without a GEMM (riders of the launch: the caller's)
 inline ProprioArgs layer_row_fwd(const DenseLn& L, const float* P, const DenseLnIo& t) {
   return ProprioArgs{t.x, P + L.W, P + L.b, P + L.g, P + L.be, t.y, t.ld_y, t.xhat, t.rstd, nullptr, 0, nullptr, 0, 0};
 }
-inline LnBwdArgs layer_ln_bwd(const DenseLn& L, const float* P, const DenseLnIo& t, const DenseLnGrad& d, int rows) {
+// (site: the one the forward pass of these activations was given)
+inline LnBwdArgs layer_ln_bwd(const DenseLn& L, const float* P, const DenseLnIo& t, const DenseLnGrad& d, int rows,
+                              const DenseLnDrop& site = DenseLnDrop{}) {
   LnBwdArgs l{};
   l.dy = d.dy; l.ld_dy = d.ld_dy; l.dy_goff = d.dy_goff;
   l.y = t.y; l.ld_y = t.ld_y; l.y_goff = t.y_goff;
   l.xhat = t.xhat; l.rstd = t.rstd; l.gamma = P + L.g; l.beta = P + L.be; l.pstride = L.p_gs;
   l.rows = L.groups * rows; l.rows_per_group = rows; l.D = L.N;
   l.dx = d.dpre; l.dg = d.dg; l.act = L.act;
+  l.drop = layer_drop(L, site);
   return l;
 }
 // Gradients of the scale, shift and bias into G, a gradient vector indexed like the parameter vector

@@ -50,6 +50,7 @@ struct LnBwdArgs {
   const float* beta;  // kActSwish only: the forward's beta (addressed like gamma), to recompute pre = gamma*xhat + beta
   int D;          // the row width, a multiple of 64 in [64, 1024]
   int dq_inline;  // rank-1 mode: dq[row] = 2 (q - y) inv_norm computed from the LossArgs of the launch
+  LnDrop drop;    // the forward row's Dropout, stated again: dx = keep-decision ? dx / keep : 0 (zero-initialised: none)
 };
 // up to kMaxMulti LayerNorm backward passes in one launch (+ the critic-loss rider when loss.on).  Widths 64 and 256 may share a
 // launch (the encoder heads); any other width (an MLP layer at hidden != 256) must be the width of every instance.  One

@@ -281,8 +281,32 @@ __device__ __forceinline__ void ln_gather(const LnFwdArgs& a, long base, long pb
     }
   }
 }
-// Returns the fused row-dot (dot_out's value, in every lane; 0 without one).
+// Dropout on a lane's VPL values of local row `lrow` (LnDrop, internal.h; mlp.py:27-28): kept elements are divided by keep as
+// flax does (inputs / keep_prob), dropped ones are exactly 0.  The forward row applies it to the gathered Dense output, the
+// backward row to dx; both state the element's index as (row0 + lrow) * D + column, whatever the lane layout.  Called under a
+// wave-uniform branch on d.mode != kLnDropNone; the mode is uniform too.
 template <int VPL, bool BLOCKED>
+__device__ __forceinline__ void ln_dropout(const LnDrop& d, long lrow, int c0, float (&v)[VPL]) {
+  constexpr int D = 64 * VPL, kStep = kLnStep<BLOCKED>;
+  const uint32_t thr = (uint32_t)(d.keep * 16777216.f);
+#pragma unroll
+  for (int j = 0; j < VPL; ++j) {
+    const int col = c0 + kStep * j;
+    bool keep;
+    if (d.mode == kLnDropMask) {
+      keep = d.mask[lrow * D + col] != 0;
+    } else {
+      const uint64_t e = (uint64_t)(d.row0 + lrow) * (uint64_t)D + (uint64_t)col;
+      if (d.mode == kLnDropKey) keep = bits_to_unit(random_bits_at(d.key[0], d.key[1], (uint64_t)d.total_rows * (uint64_t)D, e)) < d.keep;
+      else keep = (uint32_t)(mix64(d.seed ^ mix64(e)) & 0xFFFFFFull) < thr;
+    }
+    v[j] = keep ? v[j] / d.keep : 0.f;
+  }
+}
+// Returns the fused row-dot (dot_out's value, in every lane; 0 without one).
+// DROP: the instantiation of the launches that carry an instance with Dropout (ln_fwd_drop_kernel); the rows of every other launch
+// are the DROP = false instantiation, whose text -- and therefore whose contraction into fused multiply-adds -- is what it was.
+template <int VPL, bool BLOCKED, bool DROP = false>
 __device__ __forceinline__ float ln_row(const LnFwdArgs& a, int row, int lane) {
   constexpr int D = 64 * VPL, kStep = kLnStep<BLOCKED>;
   const int grp = row / a.rows_per_group;
@@ -292,6 +316,9 @@ __device__ __forceinline__ float ln_row(const LnFwdArgs& a, int row, int lane) {
   const long pb = (long)grp * a.pstride + c0;
   float v[VPL];
   ln_gather<VPL, BLOCKED>(a, base, pb, v);
+  if constexpr (DROP) {
+    if (a.drop.mode != kLnDropNone) ln_dropout<VPL, BLOCKED>(a.drop, lrow, c0, v);   // (uniform: the launch's instance)
+  }
   float s1 = 0.f, s2 = 0.f;
 #pragma unroll
   for (int j = 0; j < VPL; ++j) { s1 += v[j]; s2 += v[j] * v[j]; }
@@ -947,6 +974,14 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(Multi<LnFwdArgs> mv) {
   if (row >= a.rows) return;
   ln_row<VPL, BLOCKED>(a, row, lane);
 }
+// ... of a launch in which an instance has Dropout (mlp.py:27-28): the same rows with the mask in front of the statistics
+template <int VPL, bool BLOCKED>
+__global__ __launch_bounds__(256) void ln_fwd_drop_kernel(Multi<LnFwdArgs> mv) {
+  const LnFwdArgs& a = mv.v[blockIdx.y];
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (row >= a.rows) return;
+  ln_row<VPL, BLOCKED, true>(a, row, lane);
+}
 
 // The reward classifier's head closed for labelling (vice.py:546,594: rewards = (sigmoid(classifier(next_obs)) >= 0.5) * 1.0): the
 // LayerNorm -> ReLU -> Dense(1) row of ln_row at width 256 (one row per wave; the logit goes to a.dot_out as in the train=False
@@ -986,6 +1021,15 @@ int label_rows(const LnFwdArgs& a, float* label, float* mean, int* ctr, hipStrea
 // and K256 at 256 (the encoder's proprio and bottleneck LayerNorms, and the MLPs at the default width), the strided K<D / 64, false>
 // at every other.
 #define SERL_LN_WIDTH_OK(D) ((D) >= 64 && (D) <= 1024 && (D) % 64 == 0)
+// a launch's Dropout description: none, or a keep probability in (0, 1] with the mask tensor / the window of `rows` rows inside
+// the array the key draws
+static bool ln_drop_ok(const LnDrop& d, long rows) {
+  if (d.mode == kLnDropNone) return true;
+  if (!(d.keep > 0.f && d.keep <= 1.f)) return false;
+  if (d.mode == kLnDropMask) return d.mask != nullptr;
+  if (d.mode == kLnDropKey) return d.row0 >= 0 && d.row0 + rows <= d.total_rows;
+  return d.mode == kLnDropHash && d.row0 >= 0;
+}
 #define SERL_LN_CASE(V, K, ...) case V: SERL_LAUNCH_CHAIN(K, __VA_ARGS__); break;
 #define SERL_LN_STRIDED(V, K, ...) SERL_LN_CASE(V, (K<V, false>), __VA_ARGS__)
 #define SERL_LN_LAUNCH(D, K64, K256, K, ...)                                                                              \
@@ -1004,13 +1048,17 @@ int ln_fwd_multi(const LnFwdArgs* as, int n, int D, hipStream_t stream) {
   SERL_REQUIRE(n >= 1 && n <= kMaxMulti, "bad instance count %d", n);
   Multi<LnFwdArgs> mv{};
   int rows = 0;
+  bool drop = false;
   for (int i = 0; i < n; ++i) {
     SERL_REQUIRE(as[i].act >= 0 && as[i].act < kActCount, "LayerNorm row: activation code %d is not tanh (0), relu (1) or swish (2)", as[i].act);
+    SERL_REQUIRE(ln_drop_ok(as[i].drop, as[i].rows_per_group), "LayerNorm row: bad Dropout description (mode %d, keep %g)", as[i].drop.mode, as[i].drop.keep);
     mv.v[i] = as[i];
     rows = std::max(rows, as[i].rows);
+    drop = drop || as[i].drop.mode != kLnDropNone;
   }
   dim3 grid(cdiv(rows, 4), n);
-  SERL_LN_LAUNCH(D, (ln_fwd_kernel<1, false>), (ln_fwd_kernel<4, true>), ln_fwd_kernel, grid, dim3(256), 0, stream, mv)
+  if (drop) SERL_LN_LAUNCH(D, (ln_fwd_drop_kernel<1, false>), (ln_fwd_drop_kernel<4, true>), ln_fwd_drop_kernel, grid, dim3(256), 0, stream, mv)
+  else SERL_LN_LAUNCH(D, (ln_fwd_kernel<1, false>), (ln_fwd_kernel<4, true>), ln_fwd_kernel, grid, dim3(256), 0, stream, mv)
   SERL_HIP(hipGetLastError());
   return SERL_OK;
 }
@@ -1087,7 +1135,7 @@ __device__ void critic_loss_body(const LossArgs& L, float (*red)[256]) {
 // backward of ONE row of y = act(gamma*xhat + beta), xhat = (x-mean)*rstd, by one wave, in the lane-to-column layout of ln_row:
 //   dg = dy*act'(pre) (ln_act_grad; tanh: dy*(1-y^2));  dxhat = dg*gamma;  dx = rstd*(dxhat - mean(dxhat) - xhat*mean(dxhat*xhat))
 // a lane sums its columns in ascending order, then the xor butterfly.  L: the launch's critic loss, read by a dq_inline row alone.
-template <int VPL, bool BLOCKED>
+template <int VPL, bool BLOCKED, bool DROP = false>
 __device__ __forceinline__ void ln_bwd_row(const LnBwdArgs& a, const LossArgs& L, int row, int lane) {
   const int grp = row / a.rows_per_group;
   constexpr int D = VPL * 64;
@@ -1114,11 +1162,23 @@ __device__ __forceinline__ void ln_bwd_row(const LnBwdArgs& a, const LossArgs& L
   }
   wave_sum2(s1, s2);
   const float m1 = s1 * (1.0f / D), m2 = s2 * (1.0f / D), rstd = a.rstd[row];
+  if constexpr (!DROP) {
 #pragma unroll
-  for (int j = 0; j < VPL; ++j) {
-    const int col = c0 + kLnStep<BLOCKED> * j;
-    a.dx[(long)row * D + col] = rstd * (dxh[j] - m1 - xh[j] * m2);
-    a.dg[(long)row * D + col] = dg[j];
+    for (int j = 0; j < VPL; ++j) {
+      const int col = c0 + kLnStep<BLOCKED> * j;
+      a.dx[(long)row * D + col] = rstd * (dxh[j] - m1 - xh[j] * m2);
+      a.dg[(long)row * D + col] = dg[j];
+    }
+  } else {   // dx wrt the LayerNorm's input, then -- the forward's keep decision stated again -- wrt the Dense output in front of the Dropout
+#pragma unroll
+    for (int j = 0; j < VPL; ++j) dxh[j] = rstd * (dxh[j] - m1 - xh[j] * m2);
+    if (a.drop.mode != kLnDropNone) ln_dropout<VPL, BLOCKED>(a.drop, lr, c0, dxh);
+#pragma unroll
+    for (int j = 0; j < VPL; ++j) {
+      const int col = c0 + kLnStep<BLOCKED> * j;
+      a.dx[(long)row * D + col] = dxh[j];
+      a.dg[(long)row * D + col] = dg[j];
+    }
   }
 }
 
@@ -1139,6 +1199,19 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(Multi<LnBwdArgs> mv, LossAr
   else ln_bwd_row<1, false>(a, loss, row, lane);
 }
 
+// ... of a launch in which an instance has Dropout: the rows mask dx as the forward masked the Dense output
+template <int VPL, bool BLOCKED>
+__global__ __launch_bounds__(256) void ln_bwd_drop_kernel(Multi<LnBwdArgs> mv, LossArgs loss) {
+  __shared__ float red[4][256];
+  if (loss.on && blockIdx.y == 0 && blockIdx.x == gridDim.x - 1) { critic_loss_body(loss, red); return; }
+  const LnBwdArgs& a = mv.v[blockIdx.y];
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (row >= a.rows) return;
+  if constexpr (VPL != kLnMixed) ln_bwd_row<VPL, BLOCKED, true>(a, loss, row, lane);
+  else if (a.D == 256) ln_bwd_row<4, true, true>(a, loss, row, lane);
+  else ln_bwd_row<1, false, true>(a, loss, row, lane);
+}
+
 // One instance of a default width without a rider (most LayerNorm backward launches of the default agent, BC, the classifier):
 // the same row behind a launch that carries one LnBwdArgs (ln_bwd_kernel's arguments are four of them and the loss).  Measured:
 // with ln_bwd_kernel in its place the update step is 0.36 % slower (profiles/README.md).
@@ -1153,6 +1226,7 @@ int ln_bwd_multi(const LnBwdArgs* as, int n, const LossArgs& loss, hipStream_t s
   SERL_REQUIRE(n >= 1 && n <= kMaxMulti, "bad instance count %d", n);
   Multi<LnBwdArgs> mv{};
   int rows = 0;
+  bool drop = false;
   const auto mixes = [](int D) { return D == 64 || D == 256; };
   for (int i = 0; i < n; ++i) {
     SERL_REQUIRE(SERL_LN_WIDTH_OK(as[i].D), "LayerNorm width %d unsupported (a multiple of 64 in [64, 1024])", as[i].D);
@@ -1161,14 +1235,17 @@ int ln_bwd_multi(const LnBwdArgs* as, int n, const LossArgs& loss, hipStream_t s
     // (the swish backward recomputes its pre-activation: it reads beta where the forward did)
     SERL_REQUIRE(as[i].act >= 0 && as[i].act < kActCount && (as[i].act != kActSwish || as[i].beta),
                  "LayerNorm backward: activation code %d is not tanh (0), relu (1) or swish (2), or swish without beta", as[i].act);
+    SERL_REQUIRE(ln_drop_ok(as[i].drop, as[i].rows_per_group), "LayerNorm backward: bad Dropout description (mode %d, keep %g)", as[i].drop.mode, as[i].drop.keep);
     mv.v[i] = as[i];
     rows = std::max(rows, as[i].rows);
+    drop = drop || as[i].drop.mode != kLnDropNone;
     // (64 and 256 may share a launch -- the encoder heads; any other width comes from one MLP layer and is alone)
     SERL_REQUIRE(as[i].D == as[0].D || (mixes(as[i].D) && mixes(as[0].D)),
                  "LayerNorm widths %d and %d in one launch: widths other than 64 and 256 do not mix", as[0].D, as[i].D);
   }
   const dim3 grid(cdiv(rows, 4) + (loss.on ? 1 : 0), n);
-  if (n == 1 && !loss.on && as[0].D == 256) SERL_LAUNCH_CHAIN((ln_bwd_one_kernel<4, true>), grid, dim3(256), 0, stream, as[0]);
+  if (drop) SERL_LN_LAUNCH(as[0].D, (ln_bwd_drop_kernel<kLnMixed, false>), (ln_bwd_drop_kernel<kLnMixed, false>), ln_bwd_drop_kernel, grid, dim3(256), 0, stream, mv, loss)
+  else if (n == 1 && !loss.on && as[0].D == 256) SERL_LAUNCH_CHAIN((ln_bwd_one_kernel<4, true>), grid, dim3(256), 0, stream, as[0]);
   else if (n == 1 && !loss.on && as[0].D == 64) SERL_LAUNCH_CHAIN((ln_bwd_one_kernel<1, false>), grid, dim3(256), 0, stream, as[0]);
   else SERL_LN_LAUNCH(as[0].D, (ln_bwd_kernel<kLnMixed, false>), (ln_bwd_kernel<kLnMixed, false>), ln_bwd_kernel, grid, dim3(256), 0, stream, mv, loss)
   SERL_HIP(hipGetLastError());

@@ -110,6 +110,22 @@ int trunk_forward(const TrunkWeights& w, TrunkWorkspace& ws, const uint8_t* fram
 // --------------------------------------------------------------------------------------------
 // rows are grouped (group g = row / rows_per_group) and every group has its own bias/gamma/beta at
 // `pstride` floats apart; the pre-activation is bias + sum of S GEMM slabs laid out [g*S + s][local row][D]
+// Dropout between the Dense and the LayerNorm of a row (mlp.py:27-28: x = Dense(x); x = Dropout(rate)(x); x = LayerNorm(x)):
+// element (local row r of its group, column c) of the Dense output -- bias included -- is kept and scaled by 1 / keep, or set to
+// 0, before the row's statistics are taken.  The keep decision is a function of (r, c) alone, so every group (ensemble member) of
+// a launch drops the same elements, as the reference's vmapped critic does (ensemblize splits the params stream only).  The
+// backward row states the same decision again and applies it to dx.  mode kLnDropNone: no Dropout -- the rows execute what they
+// always did (a wave-uniform branch on this field).
+enum { kLnDropNone = 0, kLnDropMask = 1, kLnDropKey = 2, kLnDropHash = 3 };
+struct LnDrop {
+  int mode;
+  float keep;            // 1 - rate, in (0, 1]
+  const uint8_t* mask;   // kLnDropMask: u8 [rows_per_group][D], 1 = keep
+  // kLnDropKey: jax.random.bernoulli(key, keep, (total_rows, D))[row0 + r][c] (jaxrng.h).  kLnDropHash: the low 24 bits of
+  // mix64(seed ^ mix64((row0 + r) * D + c)) against keep * 2^24; row0 = the GLOBAL row of local row 0 (serl_agent_set_shard).
+  uint32_t key[2]; uint64_t seed;
+  long total_rows, row0;
+};
 struct LnFwdArgs {
   const float* slabs; int S; long slab_stride;
   const float *bias, *gamma, *beta; long pstride;
@@ -121,6 +137,7 @@ struct LnFwdArgs {
   const float* dot_w; const float* dot_b; float* dot_out;
   long dot_gstride, dot_b_gstride;  // 0: one head shared by all groups (DrQ critic); else per-group heads (ensemblized Critic)
   int act;               // kAct*: the row's activation, per instance (one launch may mix them) and uniform over a wave
+  LnDrop drop;           // Dropout on the gathered row, in front of the statistics (zero-initialised: none)
 };
 // The activation behind a LayerNorm row (mlp.py:19-31: `activations`, a callable or the name of one in flax.linen).  tanh: the MLPs
 // as utils/launcher.py configures them, and always the encoder heads; ReLU: also the BinaryClassifier (reward_classifier.py:24-26);

@@ -139,11 +139,14 @@ int serl_jax_crop_offsets(const uint32_t key[2], int frames, int padding, int32_
   return SERL_OK;
 }
 
-int serl_jax_update_keys(const uint32_t rng[2], int drq_aug, int n_critic, int has_actor_temp, int combined, serl_jax_update_keys_t* out) {
+// the key schedule of one learner call; `dk` (optional) also takes the rngs of its critic forwards (serl_jax_update_keys_dropout)
+static int update_keys(const uint32_t rng[2], int drq_aug, int n_critic, int has_actor_temp, int combined, int subsample_none,
+                       serl_jax_update_keys_t* out, serl_jax_dropout_keys_t* dk) {
   SERL_REQUIRE(rng && out && n_critic >= 0 && n_critic <= SERL_JAX_MAX_UTD && (n_critic > 0 || has_actor_temp), "bad argument");
   SERL_REQUIRE(!combined || (n_critic == 1 && has_actor_temp), "a combined update is one critic + actor + temperature step");
   uint32_t r[2] = {rng[0], rng[1]};
   *out = serl_jax_update_keys_t{};
+  if (dk) *dk = serl_jax_dropout_keys_t{};
   if (drq_aug) {   // drq.py:276-277 / :307-308: rng, obs_rng, next_obs_rng = split(rng, 3); state.rng = rng
     uint32_t k[6];
     serl::split_host(r, 3, k);
@@ -165,12 +168,17 @@ int serl_jax_update_keys(const uint32_t rng[2], int drq_aug, int n_critic, int h
       uint32_t s[4];
       serl::split_host(c, 2, s);                  // sac.py:151: rng, subsample_key = split(rng)
       out->k_subsample[u][0] = s[2]; out->k_subsample[u][1] = s[3];
+      if (dk) {   // sac.py:143-147 runs the target critic under c; sac.py:174-176 the online one under what :151 left of it
+        dk->k_q_target[u][0] = c[0]; dk->k_q_target[u][1] = c[1];
+        dk->k_q_online[u][0] = subsample_none ? c[0] : s[0]; dk->k_q_online[u][1] = subsample_none ? c[1] : s[1];
+      }
     }
     if (combined || u >= n_critic) {
       uint32_t p[8];
       serl::split_host(r_actor, 4, p);            // sac.py:197: rng, policy_rng, sample_rng, critic_rng = split(rng, 4)
       out->k_policy[0] = p[2]; out->k_policy[1] = p[3];
       out->k_sample[0] = p[4]; out->k_sample[1] = p[5];
+      if (dk) { dk->k_q_actor[0] = p[6]; dk->k_q_actor[1] = p[7]; }
       uint32_t t[4];
       serl::split_host(r_temp, 2, t);             // sac.py:222: rng, next_action_sample_key = split(rng)
       out->k_temp[0] = t[2]; out->k_temp[1] = t[3];
@@ -182,6 +190,17 @@ int serl_jax_update_keys(const uint32_t rng[2], int drq_aug, int n_critic, int h
   out->rng_out[0] = r[0]; out->rng_out[1] = r[1];
   out->n_critic = n_critic;
   return SERL_OK;
+}
+
+int serl_jax_update_keys(const uint32_t rng[2], int drq_aug, int n_critic, int has_actor_temp, int combined, serl_jax_update_keys_t* out) {
+  return update_keys(rng, drq_aug, n_critic, has_actor_temp, combined, 0, out, nullptr);
+}
+
+// mlp.py:27-28; sac.py:137-176,197-207: the rngs forward_target_critic / forward_critic hand their MLP's Dropout layers
+int serl_jax_update_keys_dropout(const uint32_t rng[2], int drq_aug, int n_critic, int has_actor_temp, int combined, int subsample_none,
+                                 serl_jax_update_keys_t* keys, serl_jax_dropout_keys_t* out) {
+  SERL_REQUIRE(out, "NULL argument");
+  return update_keys(rng, drq_aug, n_critic, has_actor_temp, combined, subsample_none, keys, out);
 }
 
 int serl_jax_fill(int device, const serl_jax_job* jobs, int n, void* stream) {

@@ -25,6 +25,10 @@ class _UpdateKeys(C.Structure):
                 ("k_policy", C.c_uint32 * 2), ("k_sample", C.c_uint32 * 2), ("k_temp", C.c_uint32 * 2)]
 
 
+class _DropoutKeys(C.Structure):      # serl_jax_dropout_keys_t
+    _fields_ = [("k_q_target", (C.c_uint32 * 2) * MAX_UTD), ("k_q_online", (C.c_uint32 * 2) * MAX_UTD), ("k_q_actor", C.c_uint32 * 2)]
+
+
 class _Job(C.Structure):
     _fields_ = [("key", C.c_uint32 * 2), ("kind", C.c_int32), ("p", C.c_float), ("n_total", C.c_int64), ("first", C.c_int64),
                 ("count", C.c_int64), ("out", C.c_void_p)]
@@ -115,7 +119,11 @@ def crop_pair(rng, frames: int):
 class UpdateKeys:
     """Every key one learner call derives from state.rng (serl_jax_update_keys; order documented in the header)."""
 
-    def __init__(self, rng, drq_aug: bool, n_critic: int, has_actor_temp: bool, combined: bool = False):
+    def __init__(self, rng, drq_aug: bool, n_critic: int, has_actor_temp: bool, combined: bool = False, subsample_none=None):
+        """subsample_none: None = an agent without MLP Dropout, the keys it always had.  True / False (critic_subsample_size is /
+        is not None) = also the rngs of the call's critic forwards, which only their Dropout layers read (mlp.py:27-28):
+        k_q_target[i] (sac.py:143-147), k_q_online[i] (sac.py:174-176: split(k_q_target[i])[0] behind sac.py:151's re-split, the
+        same key without it) and k_q_actor (critic_rng, sac.py:197,203-207)."""
         # The C struct holds SERL_JAX_MAX_UTD critic slots; the schedule is a chain (every update derives its keys from the running
         # rng and advances it), so a larger utd_ratio -- the reference accepts any divisor of the batch (sac.py:544-596) -- is the
         # same call made on consecutive windows of <= MAX_UTD critic updates, the actor/temperature update riding on the last one.
@@ -123,13 +131,24 @@ class UpdateKeys:
         a = lambda f: np.array(list(f), np.uint32)
         self.rng_in = k.copy()
         self.k_next_action, self.k_subsample = [], []
+        if subsample_none is not None:
+            self.k_q_target, self.k_q_online = [], []
         done, first, cur = 0, True, k
         while True:
             n = min(n_critic - done, MAX_UTD)
             last = done + n == n_critic
             s = _UpdateKeys()
-            _lib.check(_lib.lib().serl_jax_update_keys(_kp(cur), int(bool(drq_aug) and first), int(n), int(bool(has_actor_temp) and last),
-                                                       int(bool(combined)), C.byref(s)))
+            if subsample_none is None:
+                _lib.check(_lib.lib().serl_jax_update_keys(_kp(cur), int(bool(drq_aug) and first), int(n), int(bool(has_actor_temp) and last),
+                                                           int(bool(combined)), C.byref(s)))
+            else:
+                d = _DropoutKeys()
+                _lib.check(_lib.lib().serl_jax_update_keys_dropout(_kp(cur), int(bool(drq_aug) and first), int(n),
+                                                                   int(bool(has_actor_temp) and last), int(bool(combined)),
+                                                                   int(bool(subsample_none)), C.byref(s), C.byref(d)))
+                self.k_q_target += [a(d.k_q_target[i]) for i in range(n)]
+                self.k_q_online += [a(d.k_q_online[i]) for i in range(n)]
+                self.k_q_actor = a(d.k_q_actor)
             if first:
                 self.k_obs, self.k_next = a(s.k_obs), a(s.k_next)
             self.k_next_action += [a(s.k_next_action[i]) for i in range(n)]
@@ -161,6 +180,14 @@ def dropout_path(image_key: str) -> tuple:
     """Scope path of the Dropout layer behind a camera's SpatialLearnedEmbeddings in the POLICY's encoder (the only Dropout that
     is ever active: vision/resnet_v1.py:352, networks/actor_critic_nets.py:185, agents/continuous/drq.py:155-199)."""
     return ("modules_actor", "encoder", f"encoder_{image_key}", "Dropout_0")
+
+
+def mlp_dropout_path(network: str, layer: int) -> tuple:
+    """Scope path of Dropout layer `layer` (0, 1) of the MLP of `network` ("policy" / "critic"): mlp.py:27-28 under
+    actor_critic_nets.py's `network` field under the agent's modules_actor / modules_critic.  The critic's MLP sits inside
+    ensemblize's nn.vmap, which splits the params stream only: every member reads this one path (DESIGN.md section 7 on what of
+    this could be pinned here)."""
+    return ({"policy": "modules_actor", "critic": "modules_critic"}[network], "network", f"Dropout_{int(layer)}")
 
 
 def job(kind: int, key, n_total: int, out_ptr: int, first: int = 0, count: int | None = None, p: float = 0.0) -> _Job:

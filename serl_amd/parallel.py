@@ -31,6 +31,13 @@ from ._lib_agent import APPLY_ACTOR_TEMP, APPLY_CRITIC  # noqa: F401
 from .call_noise import CallNoise
 
 
+def _subsample_none(core):
+    """jaxrng.UpdateKeys' last argument for `core`: None without MLP Dropout, else whether critic_subsample_size is None"""
+    if getattr(core, "critic_dropout", 0.0) <= 0 and getattr(core, "policy_dropout", 0.0) <= 0:
+        return None
+    return int(core.cfg.critic_subsample_size) < 0
+
+
 def shard_parts(parts: Sequence[Tuple[object, np.ndarray]], rank: int, world: int):
     """parts: [(buffer, idx[n_i])] in concat order (global batch = sum n_i).  Returns this rank's
     slice as parts plus the (lo, hi) global sample range."""
@@ -319,7 +326,7 @@ class DataParallelLearner:
 
     def update_critics(self):
         """DrQAgent.update_critics over the global batch (one grad-step)."""
-        self._keys = J.UpdateKeys(self._rng, True, 1, False)
+        self._keys = J.UpdateKeys(self._rng, True, 1, False, False, _subsample_none(self.core))
         with self.sched.main():
             slot = self._acquire()
             self._critic()
@@ -328,7 +335,7 @@ class DataParallelLearner:
 
     def update_high_utd(self):
         """DrQAgent.update_high_utd(utd_ratio=1): critic step, then actor+temperature on the same batch."""
-        self._keys = J.UpdateKeys(self._rng, True, 1, True)
+        self._keys = J.UpdateKeys(self._rng, True, 1, True, False, _subsample_none(self.core))
         with self.sched.main():
             slot = self._acquire()
             self._critic()
@@ -435,7 +442,7 @@ class TrunkFarmLearner(DataParallelLearner):
 
     def _worker_step(self, has_actor):
         """a worker's share of one learner call: the key bookkeeping of the call and, if it owns the batch, its pass"""
-        self._keys = J.UpdateKeys(self._rng, True, 1, has_actor)
+        self._keys = J.UpdateKeys(self._rng, True, 1, has_actor, False, _subsample_none(self.core))
         slot = self._pending if self._pending is not None else self._produce(self._keys.rng_in)
         self._pending = None
         if self.sched.slots > 1:

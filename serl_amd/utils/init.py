@@ -76,12 +76,13 @@ MLP_ACTIVATIONS = ("tanh", "relu", "swish")   # serl_agent_create_mlp's critic_a
 _ACTIVATION_NAMES = {"tanh": "tanh", "relu": "relu", "swish": "swish", "silu": "swish"}   # flax.linen.silu is swish
 
 
-def mlp_activations(critic_network_kwargs=None, policy_network_kwargs=None):
+def mlp_activations(critic_network_kwargs=None, policy_network_kwargs=None, mlp_dropout=False):
     """(critic, policy): the `activations` of the reference's MLP (networks/mlp.py:19-31) from its two network kwargs, each one
     of MLP_ACTIVATIONS.  Accepted: the strings "tanh", "relu", "swish", "silu" (mlp.py resolves a string as getattr(nn, name)) and
     any callable whose __name__ is one of them (nn.tanh, jax.nn.relu, ...).  An absent key means what utils/launcher.py writes,
-    tanh -- not mlp.py's own default, swish: pass it to get it.  Anything else, and a positive dropout_rate (mlp.py:28-31: not
-    built in the MLP rows), raises NotImplementedError from the arguments alone."""
+    tanh -- not mlp.py's own default, swish: pass it to get it.  Anything else, and a positive dropout_rate, raises
+    NotImplementedError from the arguments alone -- unless the caller has switched MLP Dropout on (mlp_dropout=True, the
+    argument of the same name of create_states / create_drq): the rates are then mlp_dropout_rates' to read and to refuse."""
     served = 'served: activations "tanh", "relu", "swish" (= "silu") by name or as a callable of that __name__, dropout_rate None or 0'
     out = []
     for which, nk in (("critic_network_kwargs", critic_network_kwargs or {}), ("policy_network_kwargs", policy_network_kwargs or {})):
@@ -90,9 +91,32 @@ def mlp_activations(critic_network_kwargs=None, policy_network_kwargs=None):
         if not isinstance(name, str) or name not in _ACTIVATION_NAMES:
             raise NotImplementedError(f"{which}: activations={act!r} ({served})")
         rate = nk.get("dropout_rate")
-        if rate is not None and not (isinstance(rate, (int, float)) and rate <= 0):
-            raise NotImplementedError(f"{which}: dropout_rate={rate!r} ({served})")
+        if not mlp_dropout and rate is not None and not (isinstance(rate, (int, float)) and rate <= 0):
+            raise NotImplementedError(f"{which}: dropout_rate={rate!r} ({served}; a positive rate below 1 with mlp_dropout=True)")
         out.append(_ACTIVATION_NAMES[name])
+    return tuple(out)
+
+
+def _dropout_rate_ok(rate):
+    return rate is None or (not isinstance(rate, bool) and isinstance(rate, (int, float, np.integer, np.floating)) and bool(rate < 1))
+
+
+def mlp_dropout_rates(critic_network_kwargs=None, policy_network_kwargs=None):
+    """What create_states / create_drq read with mlp_dropout=True (without it a positive rate is refused by mlp_activations, as it
+    always was).  (critic, policy): the `dropout_rate` of the reference's MLP (networks/mlp.py:27-28: Dense -> Dropout -> LayerNorm ->
+    activation in both hidden layers) from its two network kwargs, as floats: serl_agent_create_dropout's two rates.  None, an
+    absent key and anything <= 0 mean 0, as mlp.py reads them (`dropout_rate is not None and dropout_rate > 0`).  A rate >= 1 or
+    a value that is no number raises NotImplementedError from the arguments alone."""
+    served = "served: dropout_rate None or a number below 1 (<= 0 means no Dropout)"
+    out = []
+    for which, nk in (("critic_network_kwargs", critic_network_kwargs or {}), ("policy_network_kwargs", policy_network_kwargs or {})):
+        rate = nk.get("dropout_rate")
+        if rate is None:
+            out.append(0.0)
+            continue
+        if not _dropout_rate_ok(rate):
+            raise NotImplementedError(f"{which}: dropout_rate={rate!r} ({served})")
+        out.append(max(float(rate), 0.0))
     return tuple(out)
 
 
