@@ -67,6 +67,11 @@ def main():
     ap.add_argument("--resume", action="store_true", help="continue from the latest run state in --run_dir")
     ap.add_argument("--hidden", type=int, default=256,
                     help="width h of the critic's and the policy's MLPs (hidden_dims=[h, h]): a multiple of 64 in [64, 1024]")
+    ap.add_argument("--critic_dims", type=int, nargs="+", default=None,
+                    help="hidden_dims of the critic's MLP, 1 to 4 widths (multiples of 64 in [64, 1024]), e.g. 512 512 512: the critic "
+                         "never leaves the learner; default [hidden, hidden]")
+    ap.add_argument("--policy_dims", type=int, nargs="+", default=None,
+                    help="hidden_dims of the policy's MLP, the network that is published to the actor; default [hidden, hidden]")
     ap.add_argument("--publish", choices=["sync", "snapshot"], default="sync",
                     help="sync: publish_network(agent.state.params) on the training thread; snapshot: publish_network(agent.snapshot)")
     ap.add_argument("--activation", choices=["tanh", "relu", "swish"], default="tanh",
@@ -84,7 +89,8 @@ def main():
     env = _Env()
     sample_obs = {"front": np.zeros((1, H, W, 3), np.uint8), "wrist": np.zeros((1, H, W, 3), np.uint8),
                   "state": np.zeros((1, S), np.float32)}
-    if a.hidden == 256 and a.activation == "tanh" and a.weight_decay is None:
+    shapes = a.critic_dims is not None or a.policy_dims is not None
+    if a.hidden == 256 and a.activation == "tanh" and a.weight_decay is None and not shapes:
         agent = make_drq_agent(seed=42, sample_obs=sample_obs, sample_action=np.zeros((A,), np.float32), image_keys=KEYS,
                                encoder_type="resnet-pretrained", batch_size=a.batch_size)
     else:
@@ -93,11 +99,14 @@ def main():
         opt = {} if a.weight_decay is None else {f"{tx}_optimizer_kwargs": {"weight_decay": a.weight_decay}
                                                  for tx in ("actor", "critic", "temperature")}
         mlp = {"activations": a.activation, "use_layer_norm": True, "hidden_dims": [a.hidden, a.hidden]}
+        critic_mlp, policy_mlp = dict(mlp, hidden_dims=a.critic_dims or mlp["hidden_dims"]), dict(mlp, hidden_dims=a.policy_dims or mlp["hidden_dims"])
         agent = DrQAgent.create_drq(
             42, sample_obs, np.zeros((A,), np.float32), encoder_type="resnet-pretrained", use_proprio=True, image_keys=KEYS,
             policy_kwargs={"tanh_squash_distribution": True, "std_parameterization": "exp", "std_min": 1e-5, "std_max": 5},
-            critic_network_kwargs=mlp, policy_network_kwargs=dict(mlp), temperature_init=1e-2, discount=0.96,
-            backup_entropy=False, critic_ensemble_size=10, critic_subsample_size=2, batch_size=a.batch_size, **opt)
+            critic_network_kwargs=critic_mlp, policy_network_kwargs=policy_mlp, temperature_init=1e-2, discount=0.96,
+            backup_entropy=False, critic_ensemble_size=10, critic_subsample_size=2, batch_size=a.batch_size, mlp_shapes=shapes, **opt)
+        if shapes:
+            print(f"critic hidden_dims {list(agent.core.critic_dims)}, policy hidden_dims {list(agent.core.policy_dims)}", flush=True)
         if a.weight_decay is not None:
             print(f"weight_decay {a.weight_decay:g} in all three optimizers: live trunk {agent.live_trunk}", flush=True)
     replay_buffer = make_replay_buffer(env, capacity=200000, type="memory_efficient_replay_buffer", image_keys=KEYS)

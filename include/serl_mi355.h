@@ -318,6 +318,20 @@ int serl_agent_create_mlp(const serl_agent_cfg* cfg, int std_param, int no_tanh,
  *     serl_agent_eval_policy are train=False and ignore the rates. */
 int serl_agent_create_dropout(const serl_agent_cfg* cfg, int std_param, int no_tanh, int critic_act, int policy_act,
                               double critic_dropout, double policy_dropout, serl_agent** out);
+/* serl_agent_create_mlp with critic and policy MLPs of their own depth and per-layer widths (networks/mlp.py:19-31 loops over
+ * `hidden_dims` of any length; agents/continuous/sac.py:516-524 and drq.py:188-207 build the two networks from separate kwargs, so
+ * the lists are independent).  Each list holds 1 to SERL_MAX_MLP_LAYERS widths, every width a multiple of 64 in [64, 1024]; anything
+ * else, or a NULL list, is SERL_ERR_INVALID, the message naming the network, the layer and the value.  cfg->hidden is not read.
+ * serl_agent_create_mlp is this function with {cfg->hidden, cfg->hidden} twice: such an agent launches the kernels it always
+ * launched.  Leaves: critic/w<j>, critic/b<j>, critic/ln<j>/{scale,bias}, j = 1..n_critic, and the same under actor/, layer by
+ * layer; critic/head/kernel follows the critic's last width, actor/mean/kernel and actor/logstd/kernel the policy's.  No Dropout
+ * in these MLPs: serl_agent_create_dropout keeps its two layers of one width. */
+#define SERL_MAX_MLP_LAYERS 4
+int serl_agent_create_shapes(const serl_agent_cfg* cfg, int std_param, int no_tanh, int critic_act, int policy_act,
+                             const int* critic_dims, int n_critic, const int* policy_dims, int n_policy, serl_agent** out);
+/* The hidden widths of one MLP of any agent (networks/mlp.py:19-31; sac.py:516-524, drq.py:188-207): network 0 = critic,
+ * 1 = policy.  Returns the layer count and fills dims[0 .. count); -1 on a NULL argument or another network code. */
+int serl_agent_mlp_dims(serl_agent* a, int network /* 0 critic, 1 policy */, int dims[SERL_MAX_MLP_LAYERS]);  /* -> layer count */
 int serl_agent_destroy(serl_agent* a);
 
 /* Parameter tree access (flat leaf names, see DESIGN.md "parameter arena"; the Python shim maps

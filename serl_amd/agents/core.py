@@ -12,7 +12,7 @@ from .._handle import Handle
 from .._lib_agent import (APPLY_ACTOR_TEMP, APPLY_CRITIC, MLP_SITES, NET_BITS, TX_INDEX, SerlAgentCfg, SerlInfo,  # noqa: F401
                           SerlMlpNoise, SerlNoise)
 
-from ..utils.init import MLP_ACTIVATIONS, STD_PARAMETERIZATIONS
+from ..utils.init import MLP_ACTIVATIONS, STD_PARAMETERIZATIONS, check_shapes_dropout, resolve_mlp_dims
 
 TX_NAMES = ("actor", "critic", "temperature")
 
@@ -26,7 +26,7 @@ class AgentCore(Handle):
                  seed=0, temp_warmup_steps=-1, optimizers=None, encoder_type="resnet-pretrained",
                  critic_subsample_size=2, backup_entropy=False, num_stack=1, std_parameterization="exp",
                  tanh_squash_distribution=True, critic_activation="tanh", policy_activation="tanh",
-                 critic_dropout=0.0, policy_dropout=0.0):
+                 critic_dropout=0.0, policy_dropout=0.0, critic_dims=None, policy_dims=None):
         """optimizers: optional {"actor"|"critic"|"temperature": make_optimizer kwargs (common/optimizers.py:6-13:
         learning_rate, warmup_steps, cosine_decay_steps, weight_decay, clip_grad_norm)} overriding lr / warmup_steps.
         weight_decay decays every leaf of the tree, as optax.adamw does with the params the reference hands it -- with
@@ -35,7 +35,10 @@ class AgentCore(Handle):
         std_parameterization / tanh_squash_distribution: the policy distribution (Policy's kwargs of the same names).
         critic_activation / policy_activation: one of MLP_ACTIVATIONS each (MLP's `activations`, utils.init.mlp_activations).
         critic_dropout / policy_dropout: MLP's `dropout_rate` in [0, 1) (mlp.py:27-28, utils.init.mlp_dropout_rates); the update's
-        losses draw, the evaluation calls (sample_actions, eval_q, eval_policy) never do."""
+        losses draw, the evaluation calls (sample_actions, eval_q, eval_policy) never do.
+        critic_dims / policy_dims: MLP's `hidden_dims` of each network, 1 to MAX_MLP_LAYERS widths (utils.init.mlp_layer_dims);
+        with either given the agent comes from serl_agent_create_shapes and `hidden` stands only for a list left out.  The
+        attributes of the same names read (hidden, hidden) on a core made without them."""
         if target_entropy is None:
             target_entropy = -act_dim / 2
         self.cfg = SerlAgentCfg(device, n_cam, H, W, state_dim, act_dim, batch, ensemble, hidden,
@@ -57,6 +60,11 @@ class AgentCore(Handle):
         self._acts = (MLP_ACTIVATIONS.index(critic_activation), MLP_ACTIVATIONS.index(policy_activation))
         # ... nor the MLPs' Dropout rates: serl_agent_create_dropout
         self.critic_dropout, self.policy_dropout = float(critic_dropout), float(policy_dropout)
+        # ... nor the MLPs' per-layer widths: serl_agent_create_shapes
+        self._shapes = critic_dims is not None or policy_dims is not None
+        self.critic_dims, self.policy_dims = resolve_mlp_dims(hidden, critic_dims, policy_dims)
+        if self._shapes:
+            check_shapes_dropout(self.critic_dims, self.policy_dims, self.critic_dropout, self.policy_dropout)
         for name, kw in (optimizers or {}).items():
             i = TX_INDEX[name]
             bad = set(kw) - {"learning_rate", "warmup_steps", "cosine_decay_steps", "weight_decay", "clip_grad_norm"}
@@ -84,6 +92,11 @@ class AgentCore(Handle):
         super().__del__()
 
     def _create(self, cfg):
+        if self._shapes and not (self.critic_dropout > 0 or self.policy_dropout > 0):
+            cd, pd = (C.c_int32 * len(self.critic_dims))(*self.critic_dims), (C.c_int32 * len(self.policy_dims))(*self.policy_dims)
+            return self.L.serl_agent_create_shapes(C.byref(cfg), self._std_param, 0 if self.tanh_squash_distribution else 1, *self._acts,
+                                                   cd, len(self.critic_dims), pd, len(self.policy_dims), C.byref(self._h))
+        # (Dropout keeps its own entry point: two layers of one width, cfg.hidden -- check_shapes_dropout saw to that)
         return self.L.serl_agent_create_dropout(C.byref(cfg), self._std_param, 0 if self.tanh_squash_distribution else 1, *self._acts,
                                                 self.critic_dropout, self.policy_dropout, C.byref(self._h))
 

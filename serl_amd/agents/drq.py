@@ -174,7 +174,7 @@ class DrQAgent:
                    target_entropy: Optional[float] = None, backup_entropy: bool = False,
                    batch_size: int = 256, device: int = 0, learning_rate: float = 3e-4,
                    actor_optimizer_kwargs: dict = None, critic_optimizer_kwargs: dict = None,
-                   temperature_optimizer_kwargs: dict = None, param_init: str = "numpy", mlp_dropout: bool = False, **kwargs):
+                   temperature_optimizer_kwargs: dict = None, param_init: str = "numpy", mlp_dropout: bool = False, mlp_shapes: bool = False, **kwargs):
         """drq.py:104-242.  Only the configuration the reference's examples run is built natively:
         encoder_type="resnet-pretrained", use_proprio=True, REDQ subsample 2, tanh-squashed
         exp-parameterised policy, LayerNorm+tanh MLPs (utils/launcher.py:79-116) -- 256x256 there; critic_network_kwargs /
@@ -183,6 +183,9 @@ class DrQAgent:
         (mlp.py:19-31); other activations and a positive dropout_rate are refused.  mlp_dropout=True switches MLP Dropout on: a
         dropout_rate (a number below 1) in either network kwargs then puts Dropout in front of that MLP's two LayerNorms
         (mlp.py:27-28; the critic's is DroQ) -- the update's losses draw, acting and evaluation never do.
+        mlp_shapes=True reads each network's own hidden_dims instead: 1 to 4 layers, every width a multiple of 64 in [64, 1024], the
+        critic's list independent of the policy's (utils.init.mlp_layer_dims; [h, h] in both gives the same agent as without the
+        switch; with a positive dropout_rate under mlp_dropout=True only one [h, h] is served).
         policy_kwargs: std_parameterization "exp", "softplus" or "uniform" (one trainable log_stds vector, no Dense_1) and
         tanh_squash_distribution True or False all run in the head kernels; "fixed" is refused.  A key that is absent, or
         policy_kwargs=None, means the launcher's value ("exp", True).
@@ -204,9 +207,16 @@ class DrQAgent:
             raise NotImplementedError("only use_proprio=True")
         pk = policy_kwargs or {}
         std_param, squash = pinit.policy_mode(pk)
-        hidden = pinit.mlp_hidden_width(critic_network_kwargs, policy_network_kwargs)
+        # mlp_shapes=True: each network's own depth and per-layer widths (mlp.py:19-31); else the one width of [h, h], as always
+        dims = pinit.mlp_layer_dims(critic_network_kwargs, policy_network_kwargs) if mlp_shapes else None
+        hidden = dims[0][0] if mlp_shapes else pinit.mlp_hidden_width(critic_network_kwargs, policy_network_kwargs)
         critic_act, policy_act = pinit.mlp_activations(critic_network_kwargs, policy_network_kwargs, mlp_dropout)
         critic_drop, policy_drop = pinit.mlp_dropout_rates(critic_network_kwargs, policy_network_kwargs) if mlp_dropout else (0.0, 0.0)
+        if mlp_shapes:
+            pinit.check_shapes_dropout(dims[0], dims[1], critic_drop, policy_drop)
+            if dims[0] == dims[1] and len(dims[0]) == 2 and dims[0][0] == dims[0][1]:
+                dims = None    # [h, h] twice: the very agent the call without the switch makes
+        shape_kw = {} if dims is None else {"critic_dims": dims[0], "policy_dims": dims[1]}
         seed = int(np.asarray(rng).reshape(-1)[-1]) if not isinstance(rng, int) else rng
         image_keys = tuple(image_keys)
         img = np.asarray(observations[image_keys[0]])
@@ -238,15 +248,15 @@ class DrQAgent:
                          critic_subsample_size=critic_subsample_size, backup_entropy=backup_entropy, num_stack=T,
                          hidden=hidden, std_parameterization=std_param, tanh_squash_distribution=squash,
                          critic_activation=critic_act, policy_activation=policy_act,
-                         critic_dropout=critic_drop, policy_dropout=policy_drop)
+                         critic_dropout=critic_drop, policy_dropout=policy_drop, **shape_kw)
         if init_ref.check_param_init(param_init):
             theta = init_ref.theta_reference(image_keys, H, W, S, A, rng, ensemble=critic_ensemble_size, encoder_type=encoder_type,
                                              temperature_init=temperature_init, device=device, num_stack=T, hidden=hidden,
-                                             std_parameterization=std_param)
+                                             std_parameterization=std_param, **shape_kw)
         else:
             theta = pinit.init_theta(len(image_keys), H, W, S, A, seed=seed, temperature_init=temperature_init,
                                      ensemble=critic_ensemble_size, encoder_type=encoder_type, num_stack=T, hidden=hidden,
-                                     std_parameterization=std_param)
+                                     std_parameterization=std_param, **shape_kw)
         trunk = pinit.init_trunk(seed=seed) if encoder_type == "resnet-pretrained" else {}
         for sec in ("params", "target_params"):  # JaxRLTrainState.create(target_params=params)
             core.load_flat(sec, theta)

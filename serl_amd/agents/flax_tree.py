@@ -143,14 +143,33 @@ def std_parameterization_of(core) -> str:
     return getattr(core, "std_parameterization", "exp")
 
 
-def theta_paths(image_keys, critic_mlp_name="network", encoder_type="resnet-pretrained", std_parameterization="exp"):
-    """flat trainable leaf -> list of flax paths (aliases)."""
+def mlp_dims_of(core):
+    """(critic, policy) hidden widths of an AgentCore; a core that only has cfg.hidden is the (hidden, hidden) agent"""
+    cd, pd = getattr(core, "critic_dims", None), getattr(core, "policy_dims", None)
+    h = int(getattr(core.cfg, "hidden", 256))
+    return (tuple(cd) if cd is not None else (h, h), tuple(pd) if pd is not None else (h, h))
+
+
+def _mlp_paths(m, pre, base, n_layers):
+    """layer j = 1..n of MLP `pre` -> Dense_{j-1} / LayerNorm_{j-1} below `base` (mlp.py:19-31 names them in loop order)"""
+    for j in range(1, n_layers + 1):
+        m[f"{pre}/w{j}"] = [base + (f"Dense_{j - 1}", "kernel")]
+        m[f"{pre}/b{j}"] = [base + (f"Dense_{j - 1}", "bias")]
+        m[f"{pre}/ln{j}/scale"] = [base + (f"LayerNorm_{j - 1}", "scale")]
+        m[f"{pre}/ln{j}/bias"] = [base + (f"LayerNorm_{j - 1}", "bias")]
+
+
+def theta_paths(image_keys, critic_mlp_name="network", encoder_type="resnet-pretrained", std_parameterization="exp",
+                critic_dims=None, policy_dims=None):
+    """flat trainable leaf -> list of flax paths (aliases).  critic_dims / policy_dims: the hidden widths of each MLP (only their
+    count matters here; None: two layers)."""
     enc = ("modules_actor", "encoder")
     m = {}
+    nc, na = (2 if critic_dims is None else len(critic_dims)), (2 if policy_dims is None else len(policy_dims))
     if len(image_keys) == 0:
         # SACAgent.create_states: Policy(encoder=None, network=MLP) and ensemblize(Critic(encoder=None, network=MLP))
         # -- the vmapped Critic keeps its module names, every leaf gains a leading ensemble axis (sac.py:516-524)
-        return _state_paths(std_parameterization)
+        return _state_paths(std_parameterization, nc, na)
     for i, k in enumerate(image_keys):
         e = enc + (f"encoder_{k}",)
         if encoder_type == "small":   # SmallEncoder (small_encoders.py:9-55): Conv_0..3 {kernel, bias}
@@ -167,20 +186,10 @@ def theta_paths(image_keys, critic_mlp_name="network", encoder_type="resnet-pret
     m["enc/proprio/dense/bias"] = [enc + ("Dense_0", "bias")]
     m["enc/proprio/ln/scale"] = [enc + ("LayerNorm_0", "scale")]
     m["enc/proprio/ln/bias"] = [enc + ("LayerNorm_0", "bias")]
-    c = ("modules_critic", critic_mlp_name)
-    for j, n in ((1, 0), (2, 1)):
-        m[f"critic/w{j}"] = [c + (f"Dense_{n}", "kernel")]
-        m[f"critic/b{j}"] = [c + (f"Dense_{n}", "bias")]
-        m[f"critic/ln{j}/scale"] = [c + (f"LayerNorm_{n}", "scale")]
-        m[f"critic/ln{j}/bias"] = [c + (f"LayerNorm_{n}", "bias")]
+    _mlp_paths(m, "critic", ("modules_critic", critic_mlp_name), nc)
     m["critic/head/kernel"] = [("modules_critic", "Dense_0", "kernel")]
     m["critic/head/bias"] = [("modules_critic", "Dense_0", "bias")]
-    a = ("modules_actor", "network")
-    for j, n in ((1, 0), (2, 1)):
-        m[f"actor/w{j}"] = [a + (f"Dense_{n}", "kernel")]
-        m[f"actor/b{j}"] = [a + (f"Dense_{n}", "bias")]
-        m[f"actor/ln{j}/scale"] = [a + (f"LayerNorm_{n}", "scale")]
-        m[f"actor/ln{j}/bias"] = [a + (f"LayerNorm_{n}", "bias")]
+    _mlp_paths(m, "actor", ("modules_actor", "network"), na)
     m["actor/mean/kernel"] = [("modules_actor", "Dense_0", "kernel")]
     m["actor/mean/bias"] = [("modules_actor", "Dense_0", "bias")]
     m.update(_policy_std_paths(std_parameterization))
@@ -188,14 +197,10 @@ def theta_paths(image_keys, critic_mlp_name="network", encoder_type="resnet-pret
     return m
 
 
-def _state_paths(std_parameterization="exp"):
+def _state_paths(std_parameterization="exp", n_critic=2, n_policy=2):
     m = {}
-    for mod, pre in (("modules_critic", "critic"), ("modules_actor", "actor")):
-        for j, n in ((1, 0), (2, 1)):
-            m[f"{pre}/w{j}"] = [(mod, "network", f"Dense_{n}", "kernel")]
-            m[f"{pre}/b{j}"] = [(mod, "network", f"Dense_{n}", "bias")]
-            m[f"{pre}/ln{j}/scale"] = [(mod, "network", f"LayerNorm_{n}", "scale")]
-            m[f"{pre}/ln{j}/bias"] = [(mod, "network", f"LayerNorm_{n}", "bias")]
+    for mod, pre, n in (("modules_critic", "critic", n_critic), ("modules_actor", "actor", n_policy)):
+        _mlp_paths(m, pre, (mod, "network"), n)
     m["critic/head/kernel"] = [("modules_critic", "Dense_0", "kernel")]
     m["critic/head/bias"] = [("modules_critic", "Dense_0", "bias")]
     m["actor/mean/kernel"] = [("modules_actor", "Dense_0", "kernel")]
@@ -267,10 +272,12 @@ def export_tree(core, section: str, image_keys, duplicate_encoder_under_critic: 
     get = core.get if get is None else get
     cfg = core.cfg
     etype = "small" if cfg.encoder_type == 1 else "resnet-pretrained"
+    cd, pd = mlp_dims_of(core)
     shapes = theta_shapes(cfg.n_cam, cfg.H, cfg.W, cfg.state_dim, cfg.act_dim, ensemble=cfg.ensemble, hidden=cfg.hidden,
-                          encoder_type=etype, num_stack=max(cfg.num_stack, 1), std_parameterization=std_parameterization_of(core))
+                          encoder_type=etype, num_stack=max(cfg.num_stack, 1), std_parameterization=std_parameterization_of(core),
+                          critic_dims=cd, policy_dims=pd)
     shapes.update(trunk_shapes())
-    paths = theta_paths(image_keys, critic_mlp_name, etype, std_parameterization_of(core))
+    paths = theta_paths(image_keys, critic_mlp_name, etype, std_parameterization_of(core), cd, pd)
     if cfg.n_cam and etype != "small":
         # ONE frozen trunk: drq.py:165-176 passes the same `pretrained_encoder` module to every camera's
         # PreTrainedResNetEncoder, flax adopts a shared module once -- under the first camera in sorted-key order --

@@ -33,7 +33,7 @@ class SACAgent(DrQAgent):
                       target_entropy: Optional[float] = None, backup_entropy: bool = False,
                       actor_optimizer_kwargs: dict = None, critic_optimizer_kwargs: dict = None,
                       temperature_optimizer_kwargs: dict = None, batch_size: int = 256, device: int = 0, param_init: str = "numpy",
-                      mlp_dropout: bool = False,
+                      mlp_dropout: bool = False, mlp_shapes: bool = False,
                       **kwargs):
         """sac.py:486-542 -> create (:323-400).  Built natively: the configuration of utils/launcher.py:50-76
         (REDQ subsample 2, tanh-squashed exp-parameterised policy, LayerNorm+tanh 256x256 MLPs); hidden_dims=[h, h] in both
@@ -41,12 +41,21 @@ class SACAgent(DrQAgent):
         "swish" / "silu" the activation of each network (mlp.py:19-31; others and a positive dropout_rate are refused -- unless mlp_dropout=True: a dropout_rate below 1 then puts
         Dropout in front of that network's two LayerNorms, mlp.py:27-28, DroQ in the critic).  policy_kwargs: std_parameterization "exp",
         "softplus" or "uniform" and tanh_squash_distribution True or False run in the head kernels ("fixed" is refused).
+        mlp_shapes=True reads each network's own hidden_dims instead: 1 to 4 layers, every width a multiple of 64 in [64, 1024], the
+        critic's list independent of the policy's (utils.init.mlp_layer_dims; create_drq's docstring).
         param_init: "numpy" (default) or "reference" (the reference's own initialisers and keys, utils/init_ref.py)."""
         pk = policy_kwargs or {}
         std_param, squash = pinit.policy_mode(pk)
-        hidden = pinit.mlp_hidden_width(critic_network_kwargs, policy_network_kwargs)
+        # mlp_shapes=True: each network's own depth and per-layer widths (mlp.py:19-31); else the one width of [h, h], as always
+        dims = pinit.mlp_layer_dims(critic_network_kwargs, policy_network_kwargs) if mlp_shapes else None
+        hidden = dims[0][0] if mlp_shapes else pinit.mlp_hidden_width(critic_network_kwargs, policy_network_kwargs)
         critic_act, policy_act = pinit.mlp_activations(critic_network_kwargs, policy_network_kwargs, mlp_dropout)
         critic_drop, policy_drop = pinit.mlp_dropout_rates(critic_network_kwargs, policy_network_kwargs) if mlp_dropout else (0.0, 0.0)
+        if mlp_shapes:
+            pinit.check_shapes_dropout(dims[0], dims[1], critic_drop, policy_drop)
+            if dims[0] == dims[1] and len(dims[0]) == 2 and dims[0][0] == dims[0][1]:
+                dims = None    # [h, h] twice: the very agent the call without the switch makes
+        shape_kw = {} if dims is None else {"critic_dims": dims[0], "policy_dims": dims[1]}
         ao = {"learning_rate": 3e-4, "warmup_steps": 2000, **(actor_optimizer_kwargs or {})}     # sac.py:333-336
         co = {"learning_rate": 3e-4, "warmup_steps": 2000, **(critic_optimizer_kwargs or {})}    # sac.py:337-340
         to = {"learning_rate": 3e-4, **(temperature_optimizer_kwargs or {})}                     # sac.py:341-343
@@ -64,13 +73,13 @@ class SACAgent(DrQAgent):
                          critic_subsample_size=critic_subsample_size, backup_entropy=backup_entropy, hidden=hidden,
                          std_parameterization=std_param, tanh_squash_distribution=squash,
                          critic_activation=critic_act, policy_activation=policy_act,
-                         critic_dropout=critic_drop, policy_dropout=policy_drop)
+                         critic_dropout=critic_drop, policy_dropout=policy_drop, **shape_kw)
         if init_ref.check_param_init(param_init):
             theta = init_ref.theta_reference((), 0, 0, S, A, rng, ensemble=critic_ensemble_size, temperature_init=temperature_init,
-                                             device=device, hidden=hidden, std_parameterization=std_param)
+                                             device=device, hidden=hidden, std_parameterization=std_param, **shape_kw)
         else:
             theta = pinit.init_theta(0, 0, 0, S, A, seed=seed, temperature_init=temperature_init, ensemble=critic_ensemble_size,
-                                     hidden=hidden, std_parameterization=std_param)
+                                     hidden=hidden, std_parameterization=std_param, **shape_kw)
         for sec in ("params", "target_params"):
             core.load_flat(sec, theta)
         config = dict(critic_ensemble_size=critic_ensemble_size, critic_subsample_size=critic_subsample_size,

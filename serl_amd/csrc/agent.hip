@@ -23,9 +23,16 @@ using namespace serl;
 
 namespace {
 
+constexpr int kL = SERL_MAX_MLP_LAYERS;
+// K-split depth of an MLP layer's forward GEMM: the layer on the network's input is the deepest (it has the longest K)
+inline int critic_smax(int layer) { return layer == 0 ? 4 : 2; }
+inline int policy_smax(int layer) { return layer == 0 ? 8 : 4; }
+
 struct Offs {
   long enc0, cam_stride;   // camera 0's first leaf (SpatialLearnedEmbeddings kernel, or the SmallEncoder's first conv); camera k's sit k * cam_stride further
-  DenseLn cam, prop, c1, c2, a1, a2;   // the Dense -> LayerNorm -> activation layers: camera bottleneck, proprio branch, critic and policy MLPs
+  DenseLn cam, prop;       // the Dense -> LayerNorm -> activation layers: camera bottleneck, proprio branch,
+  DenseLn c[kL], a[kL];    // ... and the nc layers of the critic's MLP, the na layers of the policy's (mlp.py:19-31), input side first
+  int nc, na;
   long c_hw, c_hb;
   long a_Wm, a_bm, a_Ws, a_bs;   // kPolUniform: a_bs = actor/log_stds, no a_Ws
   long lam;
@@ -41,8 +48,8 @@ struct EncBuf {     // activations of one EncodingWrapper forward
   float* enc;       // [B][ld] output slice base
   long ld;
 };
-struct LayerBuf { float *h, *xhat, *rstd; };   // a layer's output [rows][hidden], normalised pre-activation and 1/std [rows]
-struct MlpBuf { LayerBuf l1, l2; };             // 2-layer MLP activations (ensemble: rows = E*B)
+struct LayerBuf { float *h, *xhat, *rstd; };   // a layer's output [rows][width], normalised pre-activation and 1/std [rows]
+struct MlpBuf { LayerBuf l[kL]; };              // an MLP's activations, one LayerBuf per layer of that layer's width (ensemble: rows = E*B)
 struct GradBuf { float *dy, *dpre, *dg; };      // a layer's backward scratch: DenseLnGrad's three tensors
 struct CritBuf {
   float* x;  // [B][E+A]
@@ -75,7 +82,11 @@ struct serl_agent {
   int std_param = SERL_STD_EXP, no_tanh = 0;   // the arguments of serl_agent_create_policy
   int pol_mode = kPolExp;            // ... as the head kernels take them
   int head_groups = 2;               // Dense layers of the policy head: (mean, log_std), or the mean alone with kPolUniform
-  int critic_act = kActTanh, policy_act = kActTanh;   // serl_agent_create_mlp: the activation of each MLP's two LayerNorm rows (kAct*)
+  int critic_act = kActTanh, policy_act = kActTanh;   // serl_agent_create_mlp: the activation of each MLP's LayerNorm rows (kAct*)
+  // serl_agent_create_shapes: the hidden widths of the critic's and the policy's MLP; {cfg.hidden, cfg.hidden} twice from every
+  // other entry point.  Nothing below reads cfg.hidden.
+  int critic_dims[kL] = {0, 0, 0, 0}, policy_dims[kL] = {0, 0, 0, 0};
+  int n_critic = 0, n_policy = 0;
   // serl_agent_create_dropout: the rate of the Dropout in front of each MLP's two LayerNorm rows (mlp.py:27-28); 0 = none.
   // mlp_bound: what serl_agent_set_mlp_noise left for the next update / phase / dry-run call; mlp_cur: what the call in progress
   // (mlp_depth > 0: its outermost entry point took the binding) reads.  MlpNoiseScope, below.
@@ -132,7 +143,9 @@ struct serl_agent {
   float* slabs = nullptr; long slabs_cap = 0;  // GEMM split-K scratch (== slabs_lane[0])
   float* slabs_lane[3] = {nullptr, nullptr, nullptr};  // one per instance of a multi-instance launch
   float *dq = nullptr, *ytgt = nullptr;
-  GradBuf s2{}, s1{}, scam{}, sprop{};   // MLP layers 2 and 1 (critic and policy in turn), camera bottleneck (dy lies in dx), proprio branch
+  // MLP layer j (critic and policy in turn; the deferred gradient jobs of a phase read dpre / dg at its end: no two layers share),
+  // camera bottleneck (dy lies in dx), proprio branch
+  GradBuf s[kL]{}, scam{}, sprop{};
   float *dx = nullptr, *df = nullptr, *sle_part = nullptr, *dpre = nullptr;
   float *eps_buf[3] = {nullptr, nullptr, nullptr};
   uint8_t* mask_buf[3] = {nullptr, nullptr, nullptr};
@@ -200,8 +213,15 @@ void build_layout(serl_agent* a) {
   long off = 0;
   Offs& o = a->o;
   std::vector<Leaf>& L = a->theta_leaves;
-  const int Hd = c.hidden, N = c.ensemble;
+  const int N = c.ensemble;
   const long A = c.act_dim;
+  const int Hc = a->critic_dims[a->n_critic - 1], Hp = a->policy_dims[a->n_policy - 1];   // the widths the heads read
+  const auto mlp_leaves = [&](DenseLn* layers, const std::string& net, const int* dims, int n, int groups, int in, int act, double drop) {
+    for (int j = 0; j < n; ++j) {
+      const std::string k = std::to_string(j + 1);
+      layers[j] = add_dense_ln_leaves(L, off, net + "/w" + k, net + "/b" + k, net + "/ln" + k, groups, j ? dims[j - 1] : in, dims[j], act, drop);
+    }
+  };
   const CamHeadOffsets ch = add_cam_head_leaves(L, off, c.n_cam, a->D, c.bottleneck, [&](const std::string& p) {
     if (!a->small) { add_leaf(L, off, p + "sle", (long)a->HW * 512 * c.sle_features); return; }
     for (int l = 0; l < kSmallLayers; ++l) {   // per layer [9*cin + 1][cout]: kernel (HWIO) immediately followed by the bias (small_encoder.hip)
@@ -211,11 +231,11 @@ void build_layout(serl_agent* a) {
     }
   });
   o.enc0 = ch.first; o.cam_stride = ch.stride; o.cam = ch.dense;
-  o.c1 = add_dense_ln_leaves(L, off, "critic/w1", "critic/b1", "critic/ln1", N, a->XA, Hd, a->critic_act, a->critic_drop);
-  o.c2 = add_dense_ln_leaves(L, off, "critic/w2", "critic/b2", "critic/ln2", N, Hd, Hd, a->critic_act, a->critic_drop);
+  o.nc = a->n_critic; o.na = a->n_policy;
+  mlp_leaves(o.c, "critic", a->critic_dims, o.nc, N, a->XA, a->critic_act, a->critic_drop);
   // DrQ: one Dense(1) head shared by the ensemble (drq.py:201-207); state-only SAC: ensemblize vmaps the whole
   // Critic, so every member has its own head (actor_critic_nets.py:49-73,156-164)
-  o.c_hw = add_leaf(L, off, "critic/head/kernel", a->state_only ? N * Hd : Hd);
+  o.c_hw = add_leaf(L, off, "critic/head/kernel", a->state_only ? N * Hc : Hc);
   o.c_hb = add_leaf(L, off, "critic/head/bias", a->state_only ? N : 1);
   o.Pa0 = off;
   if (!a->state_only) {
@@ -223,9 +243,8 @@ void build_layout(serl_agent* a) {
                                  c.proprio_dim, kActTanh);
   }
   o.Pc = off;
-  o.a1 = add_dense_ln_leaves(L, off, "actor/w1", "actor/b1", "actor/ln1", 1, a->E, Hd, a->policy_act, a->policy_drop);
-  o.a2 = add_dense_ln_leaves(L, off, "actor/w2", "actor/b2", "actor/ln2", 1, Hd, Hd, a->policy_act, a->policy_drop);
-  o.a_Wm = add_leaf(L, off, "actor/mean/kernel", Hd * A);
+  mlp_leaves(o.a, "actor", a->policy_dims, o.na, 1, a->E, a->policy_act, a->policy_drop);
+  o.a_Wm = add_leaf(L, off, "actor/mean/kernel", Hp * A);
   o.a_bm = add_leaf(L, off, "actor/mean/bias", A);
   a->pol_mode = a->std_param | (a->no_tanh ? kPolNoTanh : 0);
   a->head_groups = a->std_param == SERL_STD_UNIFORM ? 1 : 2;
@@ -233,7 +252,7 @@ void build_layout(serl_agent* a) {
     o.a_Ws = -1;
     o.a_bs = add_leaf(L, off, "actor/log_stds", A);
   } else {
-    o.a_Ws = add_leaf(L, off, "actor/logstd/kernel", Hd * A);
+    o.a_Ws = add_leaf(L, off, "actor/logstd/kernel", Hp * A);
     o.a_bs = add_leaf(L, off, "actor/logstd/bias", A);
   }
   o.Pa1 = off;
@@ -250,8 +269,12 @@ void build_layout(serl_agent* a) {
 // carve everything (pass 1 with base == nullptr measures)
 size_t carve(serl_agent* a, void* base) {
   const serl_agent_cfg& c = a->cfg;
-  const long B = c.batch, N = c.ensemble, Hd = c.hidden, A = c.act_dim;
+  const long B = c.batch, N = c.ensemble, A = c.act_dim;
   const Offs& o = a->o;
+  // the widest layer of either MLP (shared scratch is sized by it) and the critic's last (the head gradient's width)
+  const long Wc = *std::max_element(a->critic_dims, a->critic_dims + a->n_critic);
+  const long Wp = *std::max_element(a->policy_dims, a->policy_dims + a->n_policy);
+  const long Hc = a->critic_dims[a->n_critic - 1];
   Bump b(base);
   a->trunk = b.take<float>(a->trunk_count);
   a->trunk_t = b.take<float>(a->trunk_count);
@@ -280,32 +303,40 @@ size_t carve(serl_agent* a, void* base) {
   enc(a->encP); enc(a->encT); enc(a->encO);
   float* encP_out = b.take<float>(B * a->E);
   a->encP.enc = encP_out; a->encP.ld = a->E;
-  auto mlp = [&](MlpBuf& m, long rows) {
-    for (LayerBuf* l : {&m.l1, &m.l2}) { l->h = b.take<float>(rows * Hd); l->xhat = b.take<float>(rows * Hd); l->rstd = b.take<float>(rows); }
+  auto mlp = [&](MlpBuf& m, long rows, const int* dims, int n) {
+    for (int j = 0; j < n; ++j) {
+      LayerBuf* l = &m.l[j];
+      l->h = b.take<float>(rows * dims[j]); l->xhat = b.take<float>(rows * dims[j]); l->rstd = b.take<float>(rows);
+    }
   };
   auto crit = [&](CritBuf& cb) {
     cb.x = b.take<float>(B * a->XA);
-    mlp(cb.m, N * B);
+    mlp(cb.m, N * B, a->critic_dims, a->n_critic);
     cb.q = b.take<float>(N * B);
   };
   crit(a->critT); crit(a->crit);
   a->encT.enc = a->critT.x; a->encT.ld = a->XA;
   a->encO.enc = a->crit.x; a->encO.ld = a->XA;
   for (PolBuf* pbuf : {&a->pol, &a->polT}) {
-    mlp(pbuf->m, B);
+    mlp(pbuf->m, B, a->policy_dims, a->n_policy);
     pbuf->pre = b.take<float>(2 * B * A); pbuf->std = b.take<float>(B * A); pbuf->logp = b.take<float>(B);
   }
   // (fused epilogues keep whole 64x64 slab tiles: rows and columns padded to 64).  The terms, in order: the camera heads' K-split
   // (32 slices), the critic's input gradient summed over members, a policy layer (K-split <= 8), a critic layer (K-split <= 4 per
   // member) and the shared head's gradient (K-split 8, 64 padded rows); every user checks its own need against slabs_cap with the
-  // numbers in the message (hidden = 1024 x 16 members x 65 rows: tests/test_mlp_widths_gpu.py)
+  // numbers in the message (hidden = 1024 x 16 members x 65 rows: tests/test_mlp_widths_gpu.py).  The lanes are shared by all
+  // layers: the policy's and the critic's terms take the widest layer of their MLP, the head gradient the critic's last width.
   const long Bp = pad64(B);
-  long cap = std::max<long>({(long)c.n_cam * 32 * Bp * c.bottleneck, N * Bp * pad64(a->XA), 8 * Bp * Hd, 4 * N * Bp * Hd, 16L * 64 * Hd});
+  long cap = std::max<long>({(long)c.n_cam * 32 * Bp * c.bottleneck, N * Bp * pad64(a->XA), 8 * Bp * Wp, 4 * N * Bp * Wc, 16L * 64 * Hc});
   a->slabs_cap = cap;
   for (int k = 0; k < 3; ++k) a->slabs_lane[k] = b.take<float>(cap);
   a->slabs = a->slabs_lane[0];
   a->dq = b.take<float>(N * B); a->ytgt = b.take<float>(B);
-  for (GradBuf* s : {&a->s2, &a->s1}) { s->dy = b.take<float>(N * B * Hd); s->dpre = b.take<float>(N * B * Hd); s->dg = b.take<float>(N * B * Hd); }
+  for (int j = std::max(a->n_critic, a->n_policy) - 1; j >= 0; --j) {   // layer j's scratch holds the critic's layer j or the policy's, whichever is larger
+    const long n = std::max<long>(j < a->n_critic ? N * B * a->critic_dims[j] : 0, j < a->n_policy ? B * a->policy_dims[j] : 0);
+    GradBuf* s = &a->s[j];
+    s->dy = b.take<float>(n); s->dpre = b.take<float>(n); s->dg = b.take<float>(n);
+  }
   a->dx = b.take<float>(B * a->XA);
   a->scam.dpre = b.take<float>((long)c.n_cam * B * c.bottleneck);
   a->scam.dg = b.take<float>((long)c.n_cam * B * c.bottleneck);
@@ -494,33 +525,43 @@ struct PolJob {
   // fused chain, eps == nullptr: the draws are hashed inside the head kernel from (eps_seed, global row) and kept in eps_out
   float* eps_out = nullptr; uint64_t eps_seed = 0; long eps_row0 = 0;
   const uint32_t* tf_key = nullptr; long tf_rows = 0, tf_row0 = 0;   // jax.random.normal(tf_key, (tf_rows, A)) rows tf_row0.. (serl_noise key_eps_*)
-  DenseLnDrop drop[2] = {};   // the Dropout sites of the two MLP layers (zero: train=False)
+  DenseLnDrop drop[kL] = {};   // the Dropout sites of the MLP's layers (zero: train=False)
 };
+// the policy MLP of n instances, layer by layer (a GEMM and a LayerNorm launch each), into every job's buffers
+int policy_mlp_multi(serl_agent* a, const PolJob* jobs, int n, int cnt, hipStream_t st) {
+  const Offs& o = a->o;
+  for (int l = 0; l < o.na; ++l) {
+    LayerJob d[3];
+    for (int i = 0; i < n; ++i) {
+      const PolJob& j = jobs[i];
+      MlpBuf& m = j.pb->m;
+      d[i] = LayerJob{j.P, l ? mlp_io(o.a[l], m.l[l - 1], m.l[l], cnt) : mlp_io(o.a[0], j.enc, j.ld_enc, m.l[0], cnt), {}, j.drop[l]};
+    }
+    RC(dense_ln_multi(a, o.a[l], d, n, cnt, policy_smax(l), st));
+  }
+  return SERL_OK;
+}
 int policy_fwd_multi(serl_agent* a, const PolJob* jobs, int n, int cnt, hipStream_t st) {
   const serl_agent_cfg& c = a->cfg;
   const Offs& o = a->o;
-  const int Hd = c.hidden, A = c.act_dim;
+  const int Hd = o.a[o.na - 1].N, A = c.act_dim;   // the head reads the last layer
   SERL_REQUIRE(n >= 1 && n <= 3, "bad policy instance count");
-  LayerJob d1[3], d2[3];
   GemmDesc gd[3];
   PolicyDistArgs pv[3];
   for (int i = 0; i < n; ++i) {
     const PolJob& j = jobs[i];
     const float* P = j.P;
     PolBuf& pb = *j.pb;
-    d1[i] = LayerJob{P, mlp_io(o.a1, j.enc, j.ld_enc, pb.m.l1, cnt), {}, j.drop[0]};
-    d2[i] = LayerJob{P, mlp_io(o.a2, pb.m.l1, pb.m.l2, cnt), {}, j.drop[1]};
-    // The head is no layer of the six (no LayerNorm): (mean, log_std) as two groups of one GEMM, the mean alone when log_stds is
+    // The head is no Dense -> LayerNorm layer (no LayerNorm): (mean, log_std) as two groups of one GEMM, the mean alone when log_stds is
     // a parameter vector (the stride is then unused)
-    gd[i] = gemm_fwd(pb.m.l2.h, Hd, 0, P + o.a_Wm, o.a_bs - o.a_bm, a->slabs_lane[i], a->head_groups, cnt, A, Hd, 4);
+    gd[i] = gemm_fwd(pb.m.l[o.na - 1].h, Hd, 0, P + o.a_Wm, o.a_bs - o.a_bm, a->slabs_lane[i], a->head_groups, cnt, A, Hd, 4);
     pv[i] = PolicyDistArgs{};
     pv[i].mode = a->pol_mode;
     pv[i].slabs = a->slabs_lane[i]; pv[i].S = 4; pv[i].bias_mean = P + o.a_bm; pv[i].bias_ls = P + o.a_bs; pv[i].pre = pb.pre;
     pv[i].eps = j.eps; pv[i].act = j.act_out; pv[i].ld_act = j.ld_act; pv[i].logp = pb.logp; pv[i].std_out = pb.std;
     pv[i].sum_logp = j.sum_logp; pv[i].lam = P + o.lam; pv[i].alpha_out = j.alpha_out;
   }
-  RC(dense_ln_multi(a, o.a1, d1, n, cnt, 8, st));
-  RC(dense_ln_multi(a, o.a2, d2, n, cnt, 4, st));
+  RC(policy_mlp_multi(a, jobs, n, cnt, st));
   if (a->fuse) {   // the tanh-Gaussian head inside the head GEMM: last arriver of every 64-row tile (heads.hip, kEpiPolicy)
     SERL_REQUIRE(A <= 64, "the fused policy-head epilogue holds one 64-wide slab row per sample (act_dim %d)", A);
     SERL_REQUIRE(cdiv(cnt, 64) <= kCtrPerLane && 8 * pad64(cnt) * 64 <= a->slabs_cap, "policy head exceeds the fused epilogue's scratch");
@@ -549,22 +590,23 @@ int policy_fwd_multi(serl_agent* a, const PolJob* jobs, int n, int cnt, hipStrea
 }
 
 // Critic ensemble forward on x = [enc | action] (actor_critic_nets.py:56-73, drq.py:201-207) for n independent
-// (parameters, input) pairs; the shared Q head is fused into the LN kernel of layer 2
-struct CritJob { const float* P; CritBuf* cb; DenseLnDrop drop[2]; };   // drop: the Dropout sites of the two layers (zero: train=False)
+// (parameters, input) pairs; the shared Q head is fused into the LN kernel of the last layer
+struct CritJob { const float* P; CritBuf* cb; DenseLnDrop drop[kL]; };   // drop: the Dropout sites of the layers (zero: train=False)
 int critic_fwd_multi(serl_agent* a, const CritJob* jobs, int n, int cnt, hipStream_t st) {
-  const serl_agent_cfg& c = a->cfg;
   const Offs& o = a->o;
   SERL_REQUIRE(n >= 1 && n <= 3, "bad critic instance count");
-  LayerJob d1[3], d2[3];
-  for (int i = 0; i < n; ++i) {
-    const float* P = jobs[i].P;
-    CritBuf& cb = *jobs[i].cb;
-    d1[i] = LayerJob{P, mlp_io(o.c1, cb.x, a->XA, cb.m.l1, cnt), {}, jobs[i].drop[0]};
-    d2[i] = LayerJob{P, mlp_io(o.c2, cb.m.l1, cb.m.l2, cnt),
-                     RowDot{P + o.c_hw, P + o.c_hb, cb.q, a->state_only ? c.hidden : 0, a->state_only ? 1 : 0}, jobs[i].drop[1]};
+  for (int l = 0; l < o.nc; ++l) {
+    LayerJob d[3];
+    for (int i = 0; i < n; ++i) {
+      const float* P = jobs[i].P;
+      CritBuf& cb = *jobs[i].cb;
+      d[i] = LayerJob{P, l ? mlp_io(o.c[l], cb.m.l[l - 1], cb.m.l[l], cnt) : mlp_io(o.c[0], cb.x, a->XA, cb.m.l[0], cnt), {}, jobs[i].drop[l]};
+      if (l == o.nc - 1)   // Q = h . w + b rides on the last layer's LayerNorm launch (a one-layer critic: on its only one)
+        d[i].dot = RowDot{P + o.c_hw, P + o.c_hb, cb.q, a->state_only ? o.c[l].N : 0, a->state_only ? 1 : 0};
+    }
+    RC(dense_ln_multi(a, o.c[l], d, n, cnt, critic_smax(l), st));
   }
-  RC(dense_ln_multi(a, o.c1, d1, n, cnt, 4, st));
-  return dense_ln_multi(a, o.c2, d2, n, cnt, 2, st);
+  return SERL_OK;
 }
 
 int flush_param_grads(serl_agent* a, hipStream_t st) {
@@ -631,12 +673,12 @@ int igrad_sum(serl_agent* a, GemmDesc g, float* out, long ldo, hipStream_t st) {
 // one head per member (state-only SAC): dq as one row [1][K] times h2.  A K above 1024 is split.  Fused: a deferred GEMM whose
 // slabs the last arriver sums.  Else: the GEMM now, then reduce_slabs.  (M = 1: hand-filled, sAm is the schedule's own.)
 int head_kernel_grad(serl_agent* a, CritBuf& cb, int cnt, hipStream_t st) {
-  const int Hd = a->cfg.hidden, N = a->cfg.ensemble;
+  const int Hd = a->o.c[a->o.nc - 1].N, N = a->cfg.ensemble;   // the head reads the last layer
   const int groups = a->state_only ? N : 1, K = a->state_only ? cnt : N * cnt, split = K <= 1024 ? 1 : (a->state_only ? 4 : 8);
   float* out = a->Gc + a->o.c_hw;
   GemmDesc g{};
   g.A = a->dq; g.sAm = a->fuse ? 1 : 0; g.sAk = 1; g.sAb = a->state_only ? cnt : 0;
-  g.B = cb.m.l2.h; g.sBk = Hd; g.sBn = 1; g.sBb = a->state_only ? (long)cnt * Hd : 0;
+  g.B = cb.m.l[a->o.nc - 1].h; g.sBk = Hd; g.sBn = 1; g.sBb = a->state_only ? (long)cnt * Hd : 0;
   g.C = split == 1 ? out : a->slabs; g.ldc = Hd; g.sCz = Hd;   // (short K: written in place)
   g.M = 1; g.N = Hd; g.K = K; g.nbatch = groups; g.splitk = split;
   if (!a->fuse) {
@@ -678,23 +720,26 @@ int head_bias_grad(serl_agent* a, int cnt, float* out, long out_gstride, hipStre
 
 // Critic backward down to dx [cnt][E+A]; parameter grads into Gc when `pg`.  The gradient wrt Q [ens][cnt] is the dq of the
 // critic loss `loss` (critic phase), or the constant `dq_const` for every element (actor loss, loss == nullptr).
-// `sites`: the two layers' Dropout sites of the forward pass whose activations `cb` holds.
+// `sites`: the layers' Dropout sites of the forward pass whose activations `cb` holds.
 int critic_bwd(serl_agent* a, const float* P, CritBuf& cb, int cnt, bool pg, hipStream_t st, const LossArgs* loss, float dq_const,
                const DenseLnDrop* sites) {
-  const serl_agent_cfg& c = a->cfg;
   const Offs& o = a->o;
   float* G = pg ? a->Gc : nullptr;
   const LossArgs* rider = nullptr;
   if (loss) RC(critic_loss_or_rider(a, *loss, st, &rider));
   if (pg) RC(head_kernel_grad(a, cb, cnt, st));
-  const DenseLnGrad d2 = mlp_grad(o.c2, a->s2, cnt, false), d1 = mlp_grad(o.c1, a->s1, cnt);
-  // layer 2: the gradient through the head dh2 = dq (x) w is formed inside the LN backward kernel (rank-1 mode)
-  const HeadDq head{loss ? loss->dq : nullptr, P + o.c_hw, dq_const, a->state_only ? c.hidden : 0, rider};
-  RC(dense_ln_bwd(a, o.c2, P, mlp_io(o.c2, cb.m.l1, cb.m.l2, cnt), d2, cnt, G, st, &head, sites[1]));
-  RC(gemm_f32(layer_igrad(o.c2, P, d2, cnt, d1), st));
-  RC(dense_ln_bwd(a, o.c1, P, mlp_io(o.c1, cb.x, a->XA, cb.m.l1, cnt), d1, cnt, G, st, nullptr, sites[0]));
-  // dx = sum_e da1[e] * W1[e]^T
-  return igrad_sum(a, layer_igrad(o.c1, P, d1, cnt, nullptr, 0, 0), a->dx, a->XA, st);
+  const int top = o.nc - 1;
+  // the last layer: the gradient through the head dh = dq (x) w is formed inside the LN backward kernel (rank-1 mode), with the
+  // critic-loss rider on the same launch; a one-layer critic has both on the layer that also feeds dx
+  const HeadDq head{loss ? loss->dq : nullptr, P + o.c_hw, dq_const, a->state_only ? o.c[top].N : 0, rider};
+  for (int l = top; l >= 0; --l) {
+    const DenseLnGrad d = mlp_grad(o.c[l], a->s[l], cnt, l != top);
+    const DenseLnIo t = l ? mlp_io(o.c[l], cb.m.l[l - 1], cb.m.l[l], cnt) : mlp_io(o.c[0], cb.x, a->XA, cb.m.l[0], cnt);
+    RC(dense_ln_bwd(a, o.c[l], P, t, d, cnt, G, st, l == top ? &head : nullptr, sites[l]));
+    if (l) RC(gemm_f32(layer_igrad(o.c[l], P, d, cnt, mlp_grad(o.c[l - 1], a->s[l - 1], cnt)), st));
+    else return igrad_sum(a, layer_igrad(o.c[0], P, d, cnt, nullptr, 0, 0), a->dx, a->XA, st);   // dx = sum_e da1[e] * W1[e]^T
+  }
+  return SERL_OK;
 }
 
 // The critic path's backward below dx: d_enc = dx[:, :E] -> the proprio branch and the camera heads (LayerNorm, Dense, SLE
@@ -823,20 +868,23 @@ void set_noise(const serl_agent* a, EncJob& e, PolJob& p, const PhaseNoise& z, l
   p.tf_key = z.tf_eps; p.tf_rows = global_count; p.tf_row0 = tf_row0;
 }
 
-// The Dropout sites of the two layers of MLP evaluation `site` (SERL_SITE_*) on rows [off, off + cnt) of the selected batch, at
+// The Dropout sites of the layers of MLP evaluation `site` (SERL_SITE_*) on rows [off, off + cnt) of the selected batch, at
 // rate `rate` (0: nothing is read and the agent's noise stream does not move -- a rate-0 agent draws what it always drew).  Each
 // layer: the bound mask, else the bound key (`key_row`: the critic update of a high-UTD call, for the critic-loss sites), else a
 // seed of the agent's own stream, one per (site, layer) in call order, which every rank of a data-parallel job takes alike.
-void mlp_sites(serl_agent* a, int site, double rate, int off, int cnt, long global_count, int key_row, DenseLnDrop (&out)[2]) {
-  out[0] = out[1] = DenseLnDrop{};
+void mlp_sites(serl_agent* a, int site, double rate, int off, int cnt, long global_count, int key_row, DenseLnDrop (&out)[kL]) {
+  for (DenseLnDrop& d : out) d = DenseLnDrop{};
   if (!(rate > 0.0)) return;
   const serl_mlp_noise& z = a->mlp_cur;
-  const long Hd = a->cfg.hidden;
-  for (int l = 0; l < 2; ++l) {
+  const bool critic = site == SERL_SITE_Q_TARGET || site == SERL_SITE_Q_ONLINE || site == SERL_SITE_Q_ACTOR;
+  const int* dims = critic ? a->critic_dims : a->policy_dims;
+  const int n = critic ? a->n_critic : a->n_policy;
+  long below = 0;   // mask elements per batch row of the layers in front of layer l
+  for (int l = 0; l < n; below += dims[l], ++l) {
     DenseLnDrop& d = out[l];
     d.train = 1;
-    if (z.mask[site]) d.mask = z.mask[site] + ((long)l * a->cur.batch + off) * Hd;
-    else if (z.key[site]) { d.key = z.key[site] + ((long)key_row * 2 + l) * 2; d.key_rows = global_count; d.key_row0 = tf_row0_of(a, cnt); }
+    if (z.mask[site]) d.mask = z.mask[site] + below * a->cur.batch + (long)off * dims[l];
+    else if (z.key[site]) { d.key = z.key[site] + ((long)key_row * n + l) * 2; d.key_rows = global_count; d.key_row0 = tf_row0_of(a, cnt); }
     else { d.seed = a->cfg.seed ^ (0xD0D0ull + 15485863ull * (++a->noise_ctr)); d.hash_row0 = a->shard_off + off; }
   }
 }
@@ -885,8 +933,31 @@ int serl_agent_create_policy(const serl_agent_cfg* cfg, int std_param, int no_ta
 
 // mlp.py:19-31: MLP applies `activations` (a callable, or the name of one in flax.linen) behind every LayerNorm; the critic and the
 // policy get theirs from two separate kwargs dicts, so the two codes are independent.
+// (= serl_agent_create_shapes with {hidden, hidden} twice: both reach create_agent with those lists and no Dropout)
 int serl_agent_create_mlp(const serl_agent_cfg* cfg, int std_param, int no_tanh, int critic_act, int policy_act, serl_agent** out) {
   return serl_agent_create_dropout(cfg, std_param, no_tanh, critic_act, policy_act, 0.0, 0.0, out);
+}
+
+static int create_agent(const serl_agent_cfg* cfg, int std_param, int no_tanh, int critic_act, int policy_act, double critic_dropout,
+                        double policy_dropout, const int* critic_dims, int n_critic, const int* policy_dims, int n_policy, bool shapes,
+                        serl_agent** out);
+
+// mlp.py:19-31: MLP loops over hidden_dims of any length; sac.py:516-524, drq.py:188-207: the critic and the policy are built
+// from separate kwargs, so the two lists are independent.  The heads follow the last width of their network.
+int serl_agent_create_shapes(const serl_agent_cfg* cfg, int std_param, int no_tanh, int critic_act, int policy_act,
+                             const int* critic_dims, int n_critic, const int* policy_dims, int n_policy, serl_agent** out) {
+  SERL_REQUIRE(cfg && out, "NULL argument");
+  SERL_REQUIRE(critic_dims && policy_dims, "%s is NULL: the hidden widths of the %s's MLP, 1 to %d of them",
+               critic_dims ? "policy_dims" : "critic_dims", critic_dims ? "policy" : "critic", SERL_MAX_MLP_LAYERS);
+  return create_agent(cfg, std_param, no_tanh, critic_act, policy_act, 0.0, 0.0, critic_dims, n_critic, policy_dims, n_policy, true, out);
+}
+
+// mlp.py:19-31; sac.py:516-524, drq.py:188-207: the hidden widths an agent was created with
+int serl_agent_mlp_dims(serl_agent* a, int network, int dims[SERL_MAX_MLP_LAYERS]) {
+  if (!a || !dims || (network != 0 && network != 1)) return -1;
+  const int n = network ? a->n_policy : a->n_critic;
+  for (int j = 0; j < n; ++j) dims[j] = (network ? a->policy_dims : a->critic_dims)[j];
+  return n;
 }
 
 // mlp.py:27-28: Dense -> Dropout(dropout_rate) -> LayerNorm -> activation in both hidden layers of each MLP, the rate from the
@@ -894,6 +965,15 @@ int serl_agent_create_mlp(const serl_agent_cfg* cfg, int std_param, int no_tanh,
 int serl_agent_create_dropout(const serl_agent_cfg* cfg, int std_param, int no_tanh, int critic_act, int policy_act, double critic_dropout,
                               double policy_dropout, serl_agent** out) {
   SERL_REQUIRE(cfg && out, "NULL argument");
+  const int dims[2] = {cfg->hidden, cfg->hidden};
+  return create_agent(cfg, std_param, no_tanh, critic_act, policy_act, critic_dropout, policy_dropout, dims, 2, dims, 2, false, out);
+}
+
+// every entry point's agent.  `shapes`: the lists are the caller's (serl_agent_create_shapes) and are checked one by one; else
+// they repeat cfg->hidden, which is checked as it always was.
+static int create_agent(const serl_agent_cfg* cfg, int std_param, int no_tanh, int critic_act, int policy_act, double critic_dropout,
+                        double policy_dropout, const int* critic_dims, int n_critic, const int* policy_dims, int n_policy, bool shapes,
+                        serl_agent** out) {
   // (the keep probability float32(1 - rate) must itself lie below 1 and above 0)
   SERL_REQUIRE(critic_dropout >= 0.0 && (float)(1.0 - critic_dropout) > 0.f, "critic_dropout %g: a Dropout rate lies in [0, 1)", critic_dropout);
   SERL_REQUIRE(policy_dropout >= 0.0 && (float)(1.0 - policy_dropout) > 0.f, "policy_dropout %g: a Dropout rate lies in [0, 1)", policy_dropout);
@@ -903,8 +983,20 @@ int serl_agent_create_dropout(const serl_agent_cfg* cfg, int std_param, int no_t
                "Unknown encoder type: %d", cfg->encoder_type);
   SERL_REQUIRE(cfg->n_cam > 0 || cfg->ensemble <= 16, "state-only SAC supports ensembles of at most 16");
   // one wave owns a LayerNorm row and a lane holds hidden / 64 of its columns, 16 at the most (heads.hip)
-  SERL_REQUIRE(cfg->hidden >= 64 && cfg->hidden <= 1024 && cfg->hidden % 64 == 0,
-               "hidden must be a multiple of 64 in [64, 1024] (got %d): the width of the critic's and the policy's two MLP layers", cfg->hidden);
+  if (!shapes)
+    SERL_REQUIRE(cfg->hidden >= 64 && cfg->hidden <= 1024 && cfg->hidden % 64 == 0,
+                 "hidden must be a multiple of 64 in [64, 1024] (got %d): the width of the critic's and the policy's two MLP layers", cfg->hidden);
+  for (int net = 0; net < 2 && shapes; ++net) {
+    const int* dims = net ? policy_dims : critic_dims;
+    const int n = net ? n_policy : n_critic;
+    const char* name = net ? "policy" : "critic";
+    SERL_REQUIRE(n >= 1 && n <= SERL_MAX_MLP_LAYERS, "%s MLP: %d hidden layers (served: 1 to %d layers, each a multiple of 64 in [64, 1024] wide)",
+                 name, n, SERL_MAX_MLP_LAYERS);
+    for (int j = 0; j < n; ++j)
+      SERL_REQUIRE(dims[j] >= 64 && dims[j] <= 1024 && dims[j] % 64 == 0,
+                   "%s MLP: layer %d has width %d (served: 1 to %d layers, each a multiple of 64 in [64, 1024] wide)", name, j + 1, dims[j],
+                   SERL_MAX_MLP_LAYERS);
+  }
   SERL_REQUIRE(cfg->bottleneck == 256, "bottleneck must be 256 (got %d): the reference fixes bottleneck_dim=256 in create_drq", cfg->bottleneck);
   SERL_REQUIRE(cfg->proprio_dim == 64, "proprio_dim must be 64");
   SERL_REQUIRE(cfg->sle_features == 8, "sle_features must be 8");
@@ -940,6 +1032,9 @@ int serl_agent_create_dropout(const serl_agent_cfg* cfg, int std_param, int no_t
   a->std_param = std_param; a->no_tanh = no_tanh;
   a->critic_act = critic_act; a->policy_act = policy_act;
   a->critic_drop = critic_dropout; a->policy_drop = policy_dropout;
+  a->n_critic = n_critic; a->n_policy = n_policy;
+  for (int j = 0; j < n_critic; ++j) a->critic_dims[j] = critic_dims[j];
+  for (int j = 0; j < n_policy; ++j) a->policy_dims[j] = policy_dims[j];
   { const char* e = getenv("SERL_CHAIN_FUSE"); a->fuse = !(e && e[0] == '0'); }
   build_layout(a);
   a->live = any_wd && a->trunk_count > 0;
@@ -1353,8 +1448,8 @@ int serl_agent_grad_bucket(serl_agent* a, int bucket, float** dev_ptr, int64_t* 
   SERL_REQUIRE(a && dev_ptr && count, "NULL argument");
   SERL_REQUIRE(bucket == 0 || bucket == 1, "bucket must be 0 or 1");
   const Offs& o = a->o;
-  if (bucket == 0) { *dev_ptr = a->Gc + o.c1.W; *count = (o.Pc - o.c1.W) + kScalars; }
-  else { *dev_ptr = a->Gc; *count = o.c1.W; }
+  if (bucket == 0) { *dev_ptr = a->Gc + o.c[0].W; *count = (o.Pc - o.c[0].W) + kScalars; }
+  else { *dev_ptr = a->Gc; *count = o.c[0].W; }
   return SERL_OK;
 }
 
@@ -1435,7 +1530,7 @@ int serl_agent_actor_grads(serl_agent* a, int global_count, const serl_noise* no
   const Offs& o = a->o;
   hipStream_t st = (hipStream_t)stream;
   SERL_HIP(hipSetDevice(c.device));
-  const int cnt = a->cur.batch, A = c.act_dim, Hd = c.hidden;
+  const int cnt = a->cur.batch, A = c.act_dim, top = o.na - 1, Hd = o.a[top].N;   // the head reads the policy's last layer
   SERL_REQUIRE(global_count >= cnt, "global_count < local batch");
   RC(mlp_masks_fit(a));
   a->pg_ncs = a->pg_nwg = 0;
@@ -1475,22 +1570,25 @@ int serl_agent_actor_grads(serl_agent* a, int global_count, const serl_noise* no
   const int hg = a->head_groups;
   float* Ga = a->Ga - o.Pa0;   // Ga[o] = gradient of the actor-tx leaf at parameter offset o
   const float* P = a->theta;
-  const DenseLnIo t2 = mlp_io(o.a2, a->pol.m.l1, a->pol.m.l2, cnt), t1 = mlp_io(o.a1, a->encP.enc, a->encP.ld, a->pol.m.l1, cnt);
-  const DenseLnGrad d2 = mlp_grad(o.a2, a->s2, cnt), d1 = mlp_grad(o.a1, a->s1, cnt);
-  // (the head is no layer of the six -- no LayerNorm, mean and log_std as groups: its three GEMM forms are written out)
-  RC(wgrad(a, gemm_wgrad(t2.y, Hd, 0, a->dpre, A, (long)cnt * A, Ga + o.a_Wm, A, hs, hg, Hd, A, cnt), st));
+  const MlpBuf& pm = a->pol.m;
+  const auto io = [&](int l) { return l ? mlp_io(o.a[l], pm.l[l - 1], pm.l[l], cnt) : mlp_io(o.a[0], a->encP.enc, a->encP.ld, pm.l[0], cnt); };
+  const DenseLnGrad dtop = mlp_grad(o.a[top], a->s[top], cnt), d1 = mlp_grad(o.a[0], a->s[0], cnt);
+  // (the head is no Dense -> LayerNorm layer -- no LayerNorm, mean and log_std as groups: its three GEMM forms are written out)
+  RC(wgrad(a, gemm_wgrad(pm.l[top].h, Hd, 0, a->dpre, A, (long)cnt * A, Ga + o.a_Wm, A, hs, hg, Hd, A, cnt), st));
   RC(head_bias_grad(a, cnt, Ga + o.a_bm, hs, st));
-  // dh2 = dmean W_mean^T + dlog_std W_logstd^T (no second term when the log-std has no Dense)
-  RC(igrad_sum(a, gemm_igrad(a->dpre, A, (long)cnt * A, P + o.a_Wm, A, hs, nullptr, 0, 0, hg, cnt, Hd, A), d2.dy, d2.ld_dy, st));
-  RC(dense_ln_bwd(a, o.a2, P, t2, d2, cnt, Ga, st, nullptr, pj[1].drop[1]));
-  RC(gemm_f32(layer_igrad(o.a2, P, d2, cnt, d1), st));
-  RC(dense_ln_bwd(a, o.a1, P, t1, d1, cnt, Ga, st, nullptr, pj[1].drop[0]));
+  // dh = dmean W_mean^T + dlog_std W_logstd^T (no second term when the log-std has no Dense)
+  RC(igrad_sum(a, gemm_igrad(a->dpre, A, (long)cnt * A, P + o.a_Wm, A, hs, nullptr, 0, 0, hg, cnt, Hd, A), dtop.dy, dtop.ld_dy, st));
+  for (int l = top; l >= 0; --l) {
+    const DenseLnGrad d = mlp_grad(o.a[l], a->s[l], cnt);
+    RC(dense_ln_bwd(a, o.a[l], P, io(l), d, cnt, Ga, st, nullptr, pj[1].drop[l]));
+    if (l) RC(gemm_f32(layer_igrad(o.a[l], P, d, cnt, mlp_grad(o.a[l - 1], a->s[l - 1], cnt)), st));
+  }
   // image codes are stop-gradiented (encoding.py:48-49); only the proprio slice of d_enc is needed: the rows of W1 that the
   // proprio columns multiply, a slice of layer 1's kernel and therefore written out
   if (!a->state_only) {
     const DenseLnGrad dp{a->sprop.dy, o.prop.N, 0, a->sprop.dpre, a->sprop.dg};
-    RC(gemm_f32(gemm_igrad(d1.dpre, o.a1.N, 0, P + o.a1.W + (long)c.n_cam * o.cam.N * o.a1.N, o.a1.N, 0, dp.dy, dp.ld_dy, 0, 1, cnt,
-                           o.prop.N, o.a1.N), st));
+    RC(gemm_f32(gemm_igrad(d1.dpre, o.a[0].N, 0, P + o.a[0].W + (long)c.n_cam * o.cam.N * o.a[0].N, o.a[0].N, 0, dp.dy, dp.ld_dy, 0, 1, cnt,
+                           o.prop.N, o.a[0].N), st));
     RC(dense_ln_bwd(a, o.prop, P, prop_io(a, a->encP, a->cur.state), dp, cnt, Ga, st));
   }
   RC(flush_param_grads(a, st));
@@ -1725,11 +1823,12 @@ int serl_agent_eval_policy(serl_agent* a, const uint8_t* dev_frames, const float
   // the policy MLP as policy_fwd_multi runs it; the head always as a plain K-split GEMM whose slabs policy_stats_kernel reads
   // (whatever a->fuse says: the fused epilogue samples, and this call draws nothing)
   PolBuf& pb = a->pol;
-  const LayerJob d1{P, mlp_io(o.a1, a->encP.enc, a->encP.ld, pb.m.l1, n), {}, {}}, d2{P, mlp_io(o.a2, pb.m.l1, pb.m.l2, n), {}, {}};
-  RC(dense_ln_multi(a, o.a1, &d1, 1, n, 8, st));
-  RC(dense_ln_multi(a, o.a2, &d2, 1, n, 4, st));
-  const GemmDesc g = gemm_fwd(pb.m.l2.h, c.hidden, 0, P + o.a_Wm, o.a_bs - o.a_bm, a->slabs_lane[0], a->head_groups, n, c.act_dim,
-                              c.hidden, 4);
+  PolJob pj{};   // train=False: no Dropout site
+  pj.P = P; pj.pb = &pb; pj.enc = a->encP.enc; pj.ld_enc = a->encP.ld;
+  RC(policy_mlp_multi(a, &pj, 1, n, st));
+  const int Hd = o.a[o.na - 1].N;
+  const GemmDesc g = gemm_fwd(pb.m.l[o.na - 1].h, Hd, 0, P + o.a_Wm, o.a_bs - o.a_bm, a->slabs_lane[0], a->head_groups, n, c.act_dim,
+                              Hd, 4);
   SERL_REQUIRE((long)a->head_groups * 4 * n * c.act_dim <= a->slabs_cap, "policy head exceeds the slab scratch");
   RC(gemm_f32_multi(&g, 1, st));
   PolicyStatsArgs v{};
@@ -1827,17 +1926,22 @@ int serl_agent_debug_get(serl_agent* a, const char* what, float* host_out, int64
   else if (w == "logp") { p = a->pol.logp; n = c.batch; }
   else if (w == "std") { p = a->pol.std; n = (long)c.batch * c.act_dim; }   // clipped std [rows][A] of the last policy evaluation in `pol`
   else if (w == "dx") { p = a->dx; n = (long)c.batch * a->XA; }
-  // the MLP rows as the last phase left them: the normalised LayerNorm input of layer 1 / 2 of an MLP buffer ([rows][hidden], the
-  // critics' rows member-major), and the gradient wrt the Dense output of the layer-1 / layer-2 backward that ran last
-  else if (w.rfind("mlp_xhat/", 0) == 0 && w.size() == 16 && (w[15] == '1' || w[15] == '2')) {
+  // the MLP rows as the last phase left them: the normalised LayerNorm input of layer l = 1.. of an MLP buffer ([rows][that
+  // layer's width], the critics' rows member-major), and the gradient wrt the Dense output of the layer-l backward that ran last
+  // (the critic's layer l or the policy's: the scratch holds the larger of the two)
+  else if (w.rfind("mlp_xhat/", 0) == 0 && w.size() == 16 && w[15] >= '1' && w[15] < '1' + kL) {
     const std::string buf = w.substr(9, 5);
     const MlpBuf* m = buf == "pol__" ? &a->pol.m : buf == "polT_" ? &a->polT.m : buf == "crit_" ? &a->crit.m : buf == "critT" ? &a->critT.m : nullptr;
-    if (!m) { set_error("unknown debug tap '%s'", what); return SERL_ERR_INVALID; }
-    p = (w[15] == '1' ? m->l1 : m->l2).xhat;
-    n = (long)(buf[0] == 'c' ? c.ensemble : 1) * c.batch * c.hidden;
+    const int l = w[15] - '1';
+    if (!m || l >= (buf[0] == 'c' ? a->n_critic : a->n_policy)) { set_error("unknown debug tap '%s'", what); return SERL_ERR_INVALID; }
+    p = m->l[l].xhat;
+    n = (long)(buf[0] == 'c' ? c.ensemble : 1) * c.batch * (buf[0] == 'c' ? a->critic_dims : a->policy_dims)[l];
   }
-  else if (w == "mlp_dpre/1") { p = a->s1.dpre; n = (long)c.ensemble * c.batch * c.hidden; }
-  else if (w == "mlp_dpre/2") { p = a->s2.dpre; n = (long)c.ensemble * c.batch * c.hidden; }
+  else if (w.rfind("mlp_dpre/", 0) == 0 && w.size() == 10 && w[9] >= '1' && w[9] - '1' < std::max(a->n_critic, a->n_policy)) {
+    const int l = w[9] - '1';
+    p = a->s[l].dpre;
+    n = std::max<long>(l < a->n_critic ? (long)c.ensemble * c.batch * a->critic_dims[l] : 0, l < a->n_policy ? (long)c.batch * a->policy_dims[l] : 0);
+  }
   // SmallEncoder layer 0's ReLU output of the LAST encoder pass, [n_cam][images of that pass][h1][w1][32]
   else if (w == "small_act0" && a->small) { p = a->sws.act[0]; n = (long)c.n_cam * c.batch * a->sws.d.h[1] * a->sws.d.w[1] * kSmallFeat[1]; }
   else { set_error("unknown debug tap '%s'", what); return SERL_ERR_INVALID; }

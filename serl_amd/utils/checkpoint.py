@@ -21,7 +21,7 @@ import msgpack
 import numpy as np
 
 from ..agents.core import TX_NAMES
-from ..agents.flax_tree import leaves_from_tree, std_parameterization_of, theta_paths, trunk_owner, _trunk_paths
+from ..agents.flax_tree import leaves_from_tree, mlp_dims_of, std_parameterization_of, theta_paths, trunk_owner, _trunk_paths
 
 _EXT_NDARRAY = 1
 
@@ -160,22 +160,40 @@ def load_state_dict(agent, sd: dict, restore_rng: bool = False):
         return agent
     core, keys = agent.core, agent.image_keys
     etype = "small" if core.cfg.encoder_type == 1 else "resnet-pretrained"
-    tp = theta_paths(keys, encoder_type=etype, std_parameterization=std_parameterization_of(core))
+    cd, pd = mlp_dims_of(core)
+    tp = theta_paths(keys, encoder_type=etype, std_parameterization=std_parameterization_of(core), critic_dims=cd, policy_dims=pd)
+    # the leaves whose PRESENCE is geometry: the policy's std leaves (std_parameterization "uniform": log_stds, else Dense_1) and
+    # the MLPs' layers (hidden_dims of any length: Dense_j / LayerNorm_j below each `network`)
+    mlp_leaves = tuple(leaf for leaf in tp if re.fullmatch(r"(critic|actor)/(w|b|ln)\d+(/scale|/bias)?", leaf))
+    optional = STD_LEAVES + mlp_leaves
+    mlp_modules = {net: (tp[f"{net}/w1"][0][:-2], n) for net, n in (("critic", len(cd)), ("actor", len(pd)))}
     trunk = _trunk_paths() if (keys and etype != "small") else {}   # state-only / SmallEncoder agents have no frozen trunk
     todo = []      # (section, leaf, array): everything is sized against the agent's leaves before the first one is written
 
-    def leaves_of(tree):
-        # The policy's std leaves are the ones whose PRESENCE is geometry (std_parameterization "uniform": log_stds, else
-        # Dense_1): a tree of the other kind holds nothing at their paths, which the size check below reports as 0 elements
-        for leaf in STD_LEAVES:
+    def leaves_of(tree, section):
+        # a tree of another kind holds nothing at the paths of such a leaf, which the size check below reports as 0 elements ...
+        for leaf in optional:
             if leaf in tp and _absent(tree, tp[leaf][0]):
                 yield leaf, np.zeros((0,), np.float32)
-        yield from leaves_from_tree({leaf: p for leaf, p in tp.items() if leaf not in STD_LEAVES or not _absent(tree, p[0])}, tree)
+        # ... and a layer the tree holds and this agent lacks is refused here: no leaf of the agent would ever meet it
+        for net, (mod, n) in mlp_modules.items():
+            if _absent(tree, mod):
+                continue
+            d = tree
+            for k in mod:
+                d = d[k]
+            for name in sorted(d):
+                m = re.fullmatch(r"(Dense|LayerNorm)_(\d+)", name)
+                if m and int(m.group(2)) >= n:
+                    got = sum(int(np.size(v)) for v in d[name].values()) if isinstance(d[name], dict) else int(np.size(d[name]))
+                    raise ValueError(f"{section}: '{'/'.join(mod + (name,))}' holds {got} elements in the state, this agent's {net} MLP "
+                                     f"has {n} layers and 0 elements there; nothing was loaded")
+        yield from leaves_from_tree({leaf: p for leaf, p in tp.items() if leaf not in optional or not _absent(tree, p[0])}, tree)
     for section in ("params", "target_params"):
         tree = sd.get(section)
         if tree is None:
             continue
-        todo += [(section, leaf, v) for leaf, v in leaves_of(tree)]
+        todo += [(section, leaf, v) for leaf, v in leaves_of(tree, section)]
         if trunk:
             # Where flax puts the ONE shared frozen trunk is derived from its adoption rule (first camera in sorted-key
             # order) and unverified against a real flax install: accept it under any camera, like
@@ -193,7 +211,7 @@ def load_state_dict(agent, sd: dict, restore_rng: bool = False):
                 raise KeyError(f"opt_states['{tx}'] holds no ScaleByAdamState (mu / nu)")
             for mom in ("mu", "nu"):
                 # leaves outside the optimizer's support are exact zeros; the C ABI accepts (and checks) them
-                todo += [(f"opt/{tx}/{mom}", leaf, np.asarray(v, np.float32)) for leaf, v in leaves_of(adam[mom])]
+                todo += [(f"opt/{tx}/{mom}", leaf, np.asarray(v, np.float32)) for leaf, v in leaves_of(adam[mom], f"opt_states/{tx}/{mom}")]
     # A state saved by an agent of another geometry (MLP width, ensemble, action or state dimension, std leaves) is refused whole: a leaf
     # that does not depend on the differing dimension would otherwise be overwritten before the first mismatch is met
     counts = getattr(core, "leaves", {})

@@ -12,6 +12,7 @@ threefry stream under flax's per-module keys (utils/init_ref.py); the trunk come
 from __future__ import annotations
 
 import math
+import re
 
 import numpy as np
 
@@ -70,6 +71,62 @@ def mlp_hidden_width(critic_network_kwargs=None, policy_network_kwargs=None) -> 
     if widths[0] != widths[1]:
         raise NotImplementedError(f"critic width {widths[0]} and policy width {widths[1]} differ ({served})")
     return widths[0]
+
+
+MAX_MLP_LAYERS = 4   # SERL_MAX_MLP_LAYERS
+
+
+def mlp_layer_dims(critic_network_kwargs=None, policy_network_kwargs=None):
+    """(critic, policy): the `hidden_dims` of the reference's MLP (networks/mlp.py:19-31 loops over a list of any length) from its
+    two network kwargs, as tuples of ints: what create_states / create_drq read with mlp_shapes=True (without the switch
+    mlp_hidden_width reads and refuses as it always did).  Default [256, 256].  Served: 1 to MAX_MLP_LAYERS layers per network,
+    every width a multiple of 64 in [64, 1024], the two lists independent, LayerNorm on; anything else raises NotImplementedError
+    from the arguments alone."""
+    served = (f"served: hidden_dims of 1 to {MAX_MLP_LAYERS} layers with LayerNorm, every width a multiple of 64 in [64, 1024], "
+              "the critic's list independent of the policy's")
+    out = []
+    for which, nk in (("critic_network_kwargs", critic_network_kwargs or {}), ("policy_network_kwargs", policy_network_kwargs or {})):
+        if not nk.get("use_layer_norm", True):
+            raise NotImplementedError(f"{which}: use_layer_norm=False ({served})")
+        dims = nk.get("hidden_dims", [256, 256])
+        dims = list(dims) if isinstance(dims, (list, tuple, np.ndarray)) else [dims]
+        if not 1 <= len(dims) <= MAX_MLP_LAYERS:
+            raise NotImplementedError(f"{which}: hidden_dims={dims} has {len(dims)} layers ({served})")
+        for d in dims:
+            if isinstance(d, bool) or not isinstance(d, (int, np.integer)):
+                raise NotImplementedError(f"{which}: width {d!r} in hidden_dims={dims} is no integer ({served})")
+            if int(d) not in HIDDEN_WIDTHS:
+                raise NotImplementedError(f"{which}: width {int(d)} in hidden_dims={dims} is off the grid ({served})")
+        out.append(tuple(int(d) for d in dims))
+    return tuple(out)
+
+
+def check_shapes_dropout(critic_dims, policy_dims, critic_dropout, policy_dropout):
+    """mlp_shapes=True together with a positive dropout_rate under mlp_dropout=True: served only where both lists are one [h, h]
+    (the Dropout masks and per-layer keys of serl_mlp_noise are laid out for two layers of one width)."""
+    if (critic_dropout > 0 or policy_dropout > 0) and not (len(critic_dims) == 2 and critic_dims[0] == critic_dims[1]
+                                                          and tuple(critic_dims) == tuple(policy_dims)):
+        raise NotImplementedError(
+            f"mlp_shapes=True with mlp_dropout=True and a positive dropout_rate: critic hidden_dims={list(critic_dims)}, policy "
+            f"hidden_dims={list(policy_dims)} (served with Dropout: hidden_dims=[h, h], the same in both networks)")
+
+
+def resolve_mlp_dims(hidden=256, critic_dims=None, policy_dims=None):
+    """(critic, policy) width tuples from the defaulted parameters every shape helper takes: None means (hidden, hidden)."""
+    return (tuple(int(d) for d in critic_dims) if critic_dims is not None else (int(hidden), int(hidden)),
+            tuple(int(d) for d in policy_dims) if policy_dims is not None else (int(hidden), int(hidden)))
+
+
+def _mlp_shapes(net, lead, fan_in, dims):
+    """{leaf: shape} of one MLP, layer by layer as the arena lays them out; lead: () or (ensemble,)."""
+    sh = {}
+    for j, d in enumerate(dims, 1):
+        sh[f"{net}/w{j}"] = (*lead, fan_in, d)
+        sh[f"{net}/b{j}"] = (*lead, d)
+        sh[f"{net}/ln{j}/scale"] = (*lead, d)
+        sh[f"{net}/ln{j}/bias"] = (*lead, d)
+        fan_in = d
+    return sh
 
 
 MLP_ACTIVATIONS = ("tanh", "relu", "swish")   # serl_agent_create_mlp's critic_act / policy_act (SERL_ACT_*), in code order
@@ -147,20 +204,20 @@ def _policy_std_shapes(Hd, A, std_parameterization):
 
 
 def theta_shapes(n_cam, H, W, S, A, ensemble=10, hidden=256, bottleneck=256, sle_features=8, proprio_dim=64,
-                 encoder_type="resnet-pretrained", num_stack=1, std_parameterization="exp"):
-    """S: the proprio Dense's input width -- T * S for a stack of T = num_stack frames, which EncodingWrapper folds into the
+                 encoder_type="resnet-pretrained", num_stack=1, std_parameterization="exp", critic_dims=None, policy_dims=None):
+    """critic_dims / policy_dims: the hidden widths of each MLP, layer by layer (None: (hidden, hidden)); the heads follow the last.
+    S: the proprio Dense's input width -- T * S for a stack of T = num_stack frames, which EncodingWrapper folds into the
     channels ("B T H W C -> B H W (T C)", common/encoding.py:39-44): the SmallEncoder's first kernel is then (3,3,3T,32).
     std_parameterization="uniform": actor/log_stds (A,) in place of actor/logstd/{kernel,bias}."""
+    cd, pd = resolve_mlp_dims(hidden, critic_dims, policy_dims)
     if n_cam == 0:   # state-only SAC (SACAgent.create_states, sac.py:486-542): no encoder, per-member Q heads
-        N, Hd = ensemble, hidden
+        N = ensemble
         return {
-            "critic/w1": (N, S + A, Hd), "critic/b1": (N, Hd), "critic/ln1/scale": (N, Hd), "critic/ln1/bias": (N, Hd),
-            "critic/w2": (N, Hd, Hd), "critic/b2": (N, Hd), "critic/ln2/scale": (N, Hd), "critic/ln2/bias": (N, Hd),
-            "critic/head/kernel": (N, Hd, 1), "critic/head/bias": (N, 1),   # vmapped Dense(1): one bias per member
-            "actor/w1": (S, Hd), "actor/b1": (Hd,), "actor/ln1/scale": (Hd,), "actor/ln1/bias": (Hd,),
-            "actor/w2": (Hd, Hd), "actor/b2": (Hd,), "actor/ln2/scale": (Hd,), "actor/ln2/bias": (Hd,),
-            "actor/mean/kernel": (Hd, A), "actor/mean/bias": (A,),
-            **_policy_std_shapes(Hd, A, std_parameterization),
+            **_mlp_shapes("critic", (N,), S + A, cd),
+            "critic/head/kernel": (N, cd[-1], 1), "critic/head/bias": (N, 1),   # vmapped Dense(1): one bias per member
+            **_mlp_shapes("actor", (), S, pd),
+            "actor/mean/kernel": (pd[-1], A), "actor/mean/bias": (A,),
+            **_policy_std_shapes(pd[-1], A, std_parameterization),
             "temp/lagrange": (),
         }
     fh, fw = feat_hw(H, W)
@@ -178,20 +235,21 @@ def theta_shapes(n_cam, H, W, S, A, ensemble=10, hidden=256, bottleneck=256, sle
         sh[f"enc/{k}/dense/bias"] = (bottleneck,)
         sh[f"enc/{k}/ln/scale"] = (bottleneck,)
         sh[f"enc/{k}/ln/bias"] = (bottleneck,)
-    N, Hd = ensemble, hidden
+    N = ensemble
     sh.update({
-        "critic/w1": (N, E + A, Hd), "critic/b1": (N, Hd), "critic/ln1/scale": (N, Hd), "critic/ln1/bias": (N, Hd),
-        "critic/w2": (N, Hd, Hd), "critic/b2": (N, Hd), "critic/ln2/scale": (N, Hd), "critic/ln2/bias": (N, Hd),
-        "critic/head/kernel": (Hd, 1), "critic/head/bias": (1,),
+        **_mlp_shapes("critic", (N,), E + A, cd),
+        "critic/head/kernel": (cd[-1], 1), "critic/head/bias": (1,),
         "enc/proprio/dense/kernel": (S, proprio_dim), "enc/proprio/dense/bias": (proprio_dim,),
         "enc/proprio/ln/scale": (proprio_dim,), "enc/proprio/ln/bias": (proprio_dim,),
-        "actor/w1": (E, Hd), "actor/b1": (Hd,), "actor/ln1/scale": (Hd,), "actor/ln1/bias": (Hd,),
-        "actor/w2": (Hd, Hd), "actor/b2": (Hd,), "actor/ln2/scale": (Hd,), "actor/ln2/bias": (Hd,),
-        "actor/mean/kernel": (Hd, A), "actor/mean/bias": (A,),
-        **_policy_std_shapes(Hd, A, std_parameterization),
+        **_mlp_shapes("actor", (), E, pd),
+        "actor/mean/kernel": (pd[-1], A), "actor/mean/bias": (A,),
+        **_policy_std_shapes(pd[-1], A, std_parameterization),
         "temp/lagrange": (),
     })
     return sh
+
+
+_MLP_KERNEL = re.compile(r"(critic|actor)/w[1-9]")     # the Dense kernels of the two MLPs
 
 
 def init_trunk(seed=42):
@@ -217,11 +275,11 @@ def init_theta(n_cam, H, W, S, A, seed=42, temperature_init=1e-2, **kw):
             out[name] = (rng.standard_normal(shp) / math.sqrt(shp[0] * shp[1] * shp[2])).astype(np.float32)
         elif name.startswith("enc/") and name.endswith("dense/kernel") and "proprio" not in name:
             out[name] = (rng.standard_normal(shp) / math.sqrt(shp[0])).astype(np.float32)  # nn.Dense default
-        elif name in ("critic/w1", "critic/w2") or (name == "critic/head/kernel" and len(shp) == 3):
+        elif _MLP_KERNEL.fullmatch(name) and name.startswith("critic/") or (name == "critic/head/kernel" and len(shp) == 3):
             # default_init = xavier_uniform, vmapped per member
             a = math.sqrt(6.0 / (shp[1] + shp[2]))
             out[name] = rng.uniform(-a, a, shp).astype(np.float32)
-        elif name.endswith("kernel") or name in ("actor/w1", "actor/w2"):
+        elif name.endswith("kernel") or _MLP_KERNEL.fullmatch(name):
             a = math.sqrt(6.0 / (shp[0] + shp[1]))
             out[name] = rng.uniform(-a, a, shp).astype(np.float32)
         elif name.endswith("scale"):

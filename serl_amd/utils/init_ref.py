@@ -83,15 +83,18 @@ def _init_of(name, shape):
 
 
 def theta_leaves(image_keys: Sequence[str], H, W, S, A, ensemble=10, encoder_type="resnet-pretrained", num_stack=1,
-                 hidden=256, std_parameterization="exp") -> List[Leaf]:
+                 hidden=256, std_parameterization="exp", critic_dims=None, policy_dims=None) -> List[Leaf]:
     """The trainable leaves of DrQAgent.create_drq (image_keys non-empty) or SACAgent.create_states (image_keys empty);
-    hidden: the MLPs' width (hidden_dims=[hidden, hidden]).  std_parameterization="uniform": the zero-initialised log_stds
+    hidden: the MLPs' width (hidden_dims=[hidden, hidden]), or critic_dims / policy_dims: each MLP's own widths, layer by layer
+    (Dense_2 / LayerNorm_2 and up take their keys from their paths like every other leaf).  std_parameterization="uniform": the zero-initialised log_stds
     vector in place of Dense_1; every other leaf keeps its key (a flax key depends on the module's path and the scope's own
     counter, not on its siblings), so the rest of the tree is bit-identical to the "exp" agent's."""
     from ..agents.flax_tree import theta_paths
     shapes = theta_shapes(len(image_keys), H, W, S, A, ensemble=ensemble, hidden=hidden, encoder_type=encoder_type,
-                          num_stack=num_stack, std_parameterization=std_parameterization)
-    paths = theta_paths(tuple(image_keys), encoder_type=encoder_type, std_parameterization=std_parameterization)
+                          num_stack=num_stack, std_parameterization=std_parameterization, critic_dims=critic_dims,
+                          policy_dims=policy_dims)
+    paths = theta_paths(tuple(image_keys), encoder_type=encoder_type, std_parameterization=std_parameterization,
+                        critic_dims=critic_dims, policy_dims=policy_dims)
     # the vmapped module: DrQ ensemblizes the critic's MLP (drq.py:206-209), state SAC the whole Critic (sac.py:516-517)
     vm = ("modules_critic", "network") if image_keys else ("modules_critic",)
     out = []
@@ -216,11 +219,13 @@ def draw_flat(leaves: Sequence[Leaf], init_rng, device: Optional[int] = 0, tempe
 
 
 def theta_reference(image_keys, H, W, S, A, rng, ensemble=10, encoder_type="resnet-pretrained", temperature_init=1.0,
-                    device: Optional[int] = 0, num_stack=1, hidden=256, std_parameterization="exp") -> Dict[str, np.ndarray]:
+                    device: Optional[int] = 0, num_stack=1, hidden=256, std_parameterization="exp", critic_dims=None,
+                    policy_dims=None) -> Dict[str, np.ndarray]:
     """init_theta's leaves as the reference's DrQ / state-SAC create path draws them from `rng` (drq.py:69, sac.py:368).
     S is the flattened proprio width T * S of a stack of T = num_stack frames; the widened leaves draw with their real fan-in.
     hidden: the MLPs' width; its leaves draw with the fans of that width."""
-    return draw_flat(theta_leaves(image_keys, H, W, S, A, ensemble, encoder_type, num_stack, hidden, std_parameterization),
+    return draw_flat(theta_leaves(image_keys, H, W, S, A, ensemble, encoder_type, num_stack, hidden, std_parameterization,
+                                  critic_dims, policy_dims),
                      init_rng_of(reference_key(rng)),
                      device, temperature_init)
 
