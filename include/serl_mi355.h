@@ -332,6 +332,20 @@ int serl_agent_create_shapes(const serl_agent_cfg* cfg, int std_param, int no_ta
 /* The hidden widths of one MLP of any agent (networks/mlp.py:19-31; sac.py:516-524, drq.py:188-207): network 0 = critic,
  * 1 = policy.  Returns the layer count and fills dims[0 .. count); -1 on a NULL argument or another network code. */
 int serl_agent_mlp_dims(serl_agent* a, int network /* 0 critic, 1 policy */, int dims[SERL_MAX_MLP_LAYERS]);  /* -> layer count */
+/* serl_agent_create_shapes with the LayerNorm of the critic's and of the policy's MLP switched per network (networks/mlp.py:29-30:
+ * `if self.use_layer_norm: x = nn.LayerNorm()(x)` in every hidden layer; mlp.py's own default, plain SAC and REDQ are without it;
+ * the two networks take the flag from separate kwargs, so the two are independent).  serl_agent_create_shapes is this function
+ * with (1, 1): such an agent launches the kernels it always launched.  Any other flag value than 0 / 1 is SERL_ERR_INVALID.
+ * A layer of a network with flag 0 is y = act(Dense(x) + b) and owns critic/w<j> and critic/b<j> (actor/...) alone: no
+ * ln<j>/{scale,bias} leaf, optimizer moment, target copy or checkpoint entry exists for it.  Every activation, depth and width of
+ * serl_agent_create_shapes applies; a plain layer takes the place of its LayerNorm launch one for one.  The encoder's bottleneck
+ * and proprio rows keep their LayerNorm (resnet_v1.py:371-374, encoding.py:66-68).  No Dropout in these MLPs. */
+int serl_agent_create_layer_norm(const serl_agent_cfg* cfg, int std_param, int no_tanh, int critic_act, int policy_act,
+                                 const int* critic_dims, int n_critic, const int* policy_dims, int n_policy, int critic_layer_norm,
+                                 int policy_layer_norm, serl_agent** out);
+/* Whether the layers of one MLP of any agent have their LayerNorm (networks/mlp.py:29-30): network 0 = critic, 1 = policy.
+ * Returns 1 or 0; -1 on a NULL agent or another network code. */
+int serl_agent_mlp_layer_norm(serl_agent* a, int network /* 0 critic, 1 policy */);
 int serl_agent_destroy(serl_agent* a);
 
 /* Parameter tree access (flat leaf names, see DESIGN.md "parameter arena"; the Python shim maps

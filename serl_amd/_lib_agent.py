@@ -83,6 +83,8 @@ SIGNATURES = {
     "serl_agent_create_dropout": [P(SerlAgentCfg), i32, i32, i32, i32, C.c_double, C.c_double, P(vp)],   # ... critic_dropout, policy_dropout
     # ... critic_dims, n_critic, policy_dims, n_policy (hidden_dims of each network; no Dropout)
     "serl_agent_create_shapes": [P(SerlAgentCfg), i32, i32, i32, i32, P(i32), i32, P(i32), i32, P(vp)],
+    "serl_agent_create_layer_norm": [P(SerlAgentCfg), i32, i32, i32, i32, P(i32), i32, P(i32), i32, i32, i32, P(vp)],   # ... critic_layer_norm, policy_layer_norm
+    "serl_agent_mlp_layer_norm": [vp, i32],   # network (0 critic, 1 policy) -> 1 / 0
     "serl_agent_mlp_dims": [vp, i32, P(i32)],   # network (0 critic, 1 policy), dims[SERL_MAX_MLP_LAYERS] -> layer count
     "serl_agent_set_mlp_noise": [vp, P(SerlMlpNoise)],
     "serl_agent_destroy": [vp],

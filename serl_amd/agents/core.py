@@ -12,7 +12,7 @@ from .._handle import Handle
 from .._lib_agent import (APPLY_ACTOR_TEMP, APPLY_CRITIC, MLP_SITES, NET_BITS, TX_INDEX, SerlAgentCfg, SerlInfo,  # noqa: F401
                           SerlMlpNoise, SerlNoise)
 
-from ..utils.init import MLP_ACTIVATIONS, STD_PARAMETERIZATIONS, check_shapes_dropout, resolve_mlp_dims
+from ..utils.init import MLP_ACTIVATIONS, STD_PARAMETERIZATIONS, check_plain_dropout, check_shapes_dropout, resolve_mlp_dims
 
 TX_NAMES = ("actor", "critic", "temperature")
 
@@ -26,7 +26,8 @@ class AgentCore(Handle):
                  seed=0, temp_warmup_steps=-1, optimizers=None, encoder_type="resnet-pretrained",
                  critic_subsample_size=2, backup_entropy=False, num_stack=1, std_parameterization="exp",
                  tanh_squash_distribution=True, critic_activation="tanh", policy_activation="tanh",
-                 critic_dropout=0.0, policy_dropout=0.0, critic_dims=None, policy_dims=None):
+                 critic_dropout=0.0, policy_dropout=0.0, critic_dims=None, policy_dims=None, critic_layer_norm=True,
+                 policy_layer_norm=True):
         """optimizers: optional {"actor"|"critic"|"temperature": make_optimizer kwargs (common/optimizers.py:6-13:
         learning_rate, warmup_steps, cosine_decay_steps, weight_decay, clip_grad_norm)} overriding lr / warmup_steps.
         weight_decay decays every leaf of the tree, as optax.adamw does with the params the reference hands it -- with
@@ -38,7 +39,9 @@ class AgentCore(Handle):
         losses draw, the evaluation calls (sample_actions, eval_q, eval_policy) never do.
         critic_dims / policy_dims: MLP's `hidden_dims` of each network, 1 to MAX_MLP_LAYERS widths (utils.init.mlp_layer_dims);
         with either given the agent comes from serl_agent_create_shapes and `hidden` stands only for a list left out.  The
-        attributes of the same names read (hidden, hidden) on a core made without them."""
+        attributes of the same names read (hidden, hidden) on a core made without them.
+        critic_layer_norm / policy_layer_norm: MLP's `use_layer_norm` of each network (mlp.py:29-30, utils.init.mlp_layer_norms); with
+        either False the agent comes from serl_agent_create_layer_norm, and no Dropout rate may be positive."""
         if target_entropy is None:
             target_entropy = -act_dim / 2
         self.cfg = SerlAgentCfg(device, n_cam, H, W, state_dim, act_dim, batch, ensemble, hidden,
@@ -63,6 +66,12 @@ class AgentCore(Handle):
         # ... nor the MLPs' per-layer widths: serl_agent_create_shapes
         self._shapes = critic_dims is not None or policy_dims is not None
         self.critic_dims, self.policy_dims = resolve_mlp_dims(hidden, critic_dims, policy_dims)
+        # ... nor whether the MLPs have their LayerNorm: serl_agent_create_layer_norm
+        for name, flag in (("critic_layer_norm", critic_layer_norm), ("policy_layer_norm", policy_layer_norm)):
+            if not isinstance(flag, (bool, np.bool_)):
+                raise TypeError(f"{name} must be a bool (got {flag!r})")
+        self.critic_layer_norm, self.policy_layer_norm = bool(critic_layer_norm), bool(policy_layer_norm)
+        check_plain_dropout(self.critic_layer_norm, self.policy_layer_norm, self.critic_dropout, self.policy_dropout)
         if self._shapes:
             check_shapes_dropout(self.critic_dims, self.policy_dims, self.critic_dropout, self.policy_dropout)
         for name, kw in (optimizers or {}).items():
@@ -92,6 +101,11 @@ class AgentCore(Handle):
         super().__del__()
 
     def _create(self, cfg):
+        if not (self.critic_layer_norm and self.policy_layer_norm):
+            cd, pd = (C.c_int32 * len(self.critic_dims))(*self.critic_dims), (C.c_int32 * len(self.policy_dims))(*self.policy_dims)
+            return self.L.serl_agent_create_layer_norm(C.byref(cfg), self._std_param, 0 if self.tanh_squash_distribution else 1, *self._acts,
+                                                       cd, len(self.critic_dims), pd, len(self.policy_dims),
+                                                       int(self.critic_layer_norm), int(self.policy_layer_norm), C.byref(self._h))
         if self._shapes and not (self.critic_dropout > 0 or self.policy_dropout > 0):
             cd, pd = (C.c_int32 * len(self.critic_dims))(*self.critic_dims), (C.c_int32 * len(self.policy_dims))(*self.policy_dims)
             return self.L.serl_agent_create_shapes(C.byref(cfg), self._std_param, 0 if self.tanh_squash_distribution else 1, *self._acts,

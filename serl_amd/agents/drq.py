@@ -174,7 +174,7 @@ class DrQAgent:
                    target_entropy: Optional[float] = None, backup_entropy: bool = False,
                    batch_size: int = 256, device: int = 0, learning_rate: float = 3e-4,
                    actor_optimizer_kwargs: dict = None, critic_optimizer_kwargs: dict = None,
-                   temperature_optimizer_kwargs: dict = None, param_init: str = "numpy", mlp_dropout: bool = False, mlp_shapes: bool = False, **kwargs):
+                   temperature_optimizer_kwargs: dict = None, param_init: str = "numpy", mlp_dropout: bool = False, mlp_shapes: bool = False, mlp_plain: bool = False, **kwargs):
         """drq.py:104-242.  Only the configuration the reference's examples run is built natively:
         encoder_type="resnet-pretrained", use_proprio=True, REDQ subsample 2, tanh-squashed
         exp-parameterised policy, LayerNorm+tanh MLPs (utils/launcher.py:79-116) -- 256x256 there; critic_network_kwargs /
@@ -186,6 +186,11 @@ class DrQAgent:
         mlp_shapes=True reads each network's own hidden_dims instead: 1 to 4 layers, every width a multiple of 64 in [64, 1024], the
         critic's list independent of the policy's (utils.init.mlp_layer_dims; [h, h] in both gives the same agent as without the
         switch; with a positive dropout_rate under mlp_dropout=True only one [h, h] is served).
+        mlp_plain=True reads each network's own use_layer_norm (mlp.py:29-30; utils.init.mlp_layer_norms): a network with False has
+        no LayerNorm in its MLP -- y = act(Dense(x) + b) per layer, the leaves w<j> and b<j> alone, no LayerNorm_<j> in the flax tree --
+        at every activation, depth and width served, with or without mlp_shapes.  An absent key means True, and True in both gives the
+        same agent as without the switch.  The encoder's bottleneck and proprio layers keep their LayerNorm.  Together with a
+        positive dropout_rate under mlp_dropout=True it is refused.
         policy_kwargs: std_parameterization "exp", "softplus" or "uniform" (one trainable log_stds vector, no Dense_1) and
         tanh_squash_distribution True or False all run in the head kernels; "fixed" is refused.  A key that is absent, or
         policy_kwargs=None, means the launcher's value ("exp", True).
@@ -208,15 +213,20 @@ class DrQAgent:
         pk = policy_kwargs or {}
         std_param, squash = pinit.policy_mode(pk)
         # mlp_shapes=True: each network's own depth and per-layer widths (mlp.py:19-31); else the one width of [h, h], as always
-        dims = pinit.mlp_layer_dims(critic_network_kwargs, policy_network_kwargs) if mlp_shapes else None
-        hidden = dims[0][0] if mlp_shapes else pinit.mlp_hidden_width(critic_network_kwargs, policy_network_kwargs)
+        dims = pinit.mlp_layer_dims(critic_network_kwargs, policy_network_kwargs, mlp_plain) if mlp_shapes else None
+        hidden = dims[0][0] if mlp_shapes else pinit.mlp_hidden_width(critic_network_kwargs, policy_network_kwargs, mlp_plain)
+        # mlp_plain=True: each network's own use_layer_norm (mlp.py:29-30); else LayerNorm in both, as always
+        lns = pinit.mlp_layer_norms(critic_network_kwargs, policy_network_kwargs) if mlp_plain else (True, True)
         critic_act, policy_act = pinit.mlp_activations(critic_network_kwargs, policy_network_kwargs, mlp_dropout)
         critic_drop, policy_drop = pinit.mlp_dropout_rates(critic_network_kwargs, policy_network_kwargs) if mlp_dropout else (0.0, 0.0)
         if mlp_shapes:
             pinit.check_shapes_dropout(dims[0], dims[1], critic_drop, policy_drop)
             if dims[0] == dims[1] and len(dims[0]) == 2 and dims[0][0] == dims[0][1]:
                 dims = None    # [h, h] twice: the very agent the call without the switch makes
+        pinit.check_plain_dropout(*lns, critic_drop, policy_drop)
         shape_kw = {} if dims is None else {"critic_dims": dims[0], "policy_dims": dims[1]}
+        if lns != (True, True):    # (True, True): the very agent the call without the switch makes
+            shape_kw.update(critic_layer_norm=lns[0], policy_layer_norm=lns[1])
         seed = int(np.asarray(rng).reshape(-1)[-1]) if not isinstance(rng, int) else rng
         image_keys = tuple(image_keys)
         img = np.asarray(observations[image_keys[0]])
@@ -265,7 +275,8 @@ class DrQAgent:
                       discount=discount, soft_target_update_rate=soft_target_update_rate,
                       target_entropy=target_entropy, backup_entropy=backup_entropy, image_keys=image_keys,
                       critic_activation=critic_act, policy_activation=policy_act,
-                      critic_dropout_rate=critic_drop, policy_dropout_rate=policy_drop)
+                      critic_dropout_rate=critic_drop, policy_dropout_rate=policy_drop,
+                      **({} if lns == (True, True) else {"critic_use_layer_norm": lns[0], "policy_use_layer_norm": lns[1]}))
         agent = cls(core, image_keys, config, seed)
         agent._opts = {k: {"warmup_steps": 0, **v} for k, v in opts.items()}
         if param_init == "reference":

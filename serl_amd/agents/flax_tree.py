@@ -150,26 +150,33 @@ def mlp_dims_of(core):
     return (tuple(cd) if cd is not None else (h, h), tuple(pd) if pd is not None else (h, h))
 
 
-def _mlp_paths(m, pre, base, n_layers):
-    """layer j = 1..n of MLP `pre` -> Dense_{j-1} / LayerNorm_{j-1} below `base` (mlp.py:19-31 names them in loop order)"""
+def layer_norms_of(core):
+    """(critic, policy): whether each MLP of an AgentCore has its LayerNorm; a core without the attributes has both"""
+    return bool(getattr(core, "critic_layer_norm", True)), bool(getattr(core, "policy_layer_norm", True))
+
+
+def _mlp_paths(m, pre, base, n_layers, layer_norm=True):
+    """layer j = 1..n of MLP `pre` -> Dense_{j-1} / LayerNorm_{j-1} below `base` (mlp.py:19-31 names them in loop order); with
+    use_layer_norm=False (mlp.py:29-30) no LayerNorm module is made and the tree holds none"""
     for j in range(1, n_layers + 1):
         m[f"{pre}/w{j}"] = [base + (f"Dense_{j - 1}", "kernel")]
         m[f"{pre}/b{j}"] = [base + (f"Dense_{j - 1}", "bias")]
-        m[f"{pre}/ln{j}/scale"] = [base + (f"LayerNorm_{j - 1}", "scale")]
-        m[f"{pre}/ln{j}/bias"] = [base + (f"LayerNorm_{j - 1}", "bias")]
+        if layer_norm:
+            m[f"{pre}/ln{j}/scale"] = [base + (f"LayerNorm_{j - 1}", "scale")]
+            m[f"{pre}/ln{j}/bias"] = [base + (f"LayerNorm_{j - 1}", "bias")]
 
 
 def theta_paths(image_keys, critic_mlp_name="network", encoder_type="resnet-pretrained", std_parameterization="exp",
-                critic_dims=None, policy_dims=None):
+                critic_dims=None, policy_dims=None, critic_layer_norm=True, policy_layer_norm=True):
     """flat trainable leaf -> list of flax paths (aliases).  critic_dims / policy_dims: the hidden widths of each MLP (only their
-    count matters here; None: two layers)."""
+    count matters here; None: two layers).  critic_layer_norm / policy_layer_norm False: no LayerNorm_<j> under that network."""
     enc = ("modules_actor", "encoder")
     m = {}
     nc, na = (2 if critic_dims is None else len(critic_dims)), (2 if policy_dims is None else len(policy_dims))
     if len(image_keys) == 0:
         # SACAgent.create_states: Policy(encoder=None, network=MLP) and ensemblize(Critic(encoder=None, network=MLP))
         # -- the vmapped Critic keeps its module names, every leaf gains a leading ensemble axis (sac.py:516-524)
-        return _state_paths(std_parameterization, nc, na)
+        return _state_paths(std_parameterization, nc, na, critic_layer_norm, policy_layer_norm)
     for i, k in enumerate(image_keys):
         e = enc + (f"encoder_{k}",)
         if encoder_type == "small":   # SmallEncoder (small_encoders.py:9-55): Conv_0..3 {kernel, bias}
@@ -186,10 +193,10 @@ def theta_paths(image_keys, critic_mlp_name="network", encoder_type="resnet-pret
     m["enc/proprio/dense/bias"] = [enc + ("Dense_0", "bias")]
     m["enc/proprio/ln/scale"] = [enc + ("LayerNorm_0", "scale")]
     m["enc/proprio/ln/bias"] = [enc + ("LayerNorm_0", "bias")]
-    _mlp_paths(m, "critic", ("modules_critic", critic_mlp_name), nc)
+    _mlp_paths(m, "critic", ("modules_critic", critic_mlp_name), nc, critic_layer_norm)
     m["critic/head/kernel"] = [("modules_critic", "Dense_0", "kernel")]
     m["critic/head/bias"] = [("modules_critic", "Dense_0", "bias")]
-    _mlp_paths(m, "actor", ("modules_actor", "network"), na)
+    _mlp_paths(m, "actor", ("modules_actor", "network"), na, policy_layer_norm)
     m["actor/mean/kernel"] = [("modules_actor", "Dense_0", "kernel")]
     m["actor/mean/bias"] = [("modules_actor", "Dense_0", "bias")]
     m.update(_policy_std_paths(std_parameterization))
@@ -197,10 +204,10 @@ def theta_paths(image_keys, critic_mlp_name="network", encoder_type="resnet-pret
     return m
 
 
-def _state_paths(std_parameterization="exp", n_critic=2, n_policy=2):
+def _state_paths(std_parameterization="exp", n_critic=2, n_policy=2, critic_layer_norm=True, policy_layer_norm=True):
     m = {}
-    for mod, pre, n in (("modules_critic", "critic", n_critic), ("modules_actor", "actor", n_policy)):
-        _mlp_paths(m, pre, (mod, "network"), n)
+    for mod, pre, n, ln in (("modules_critic", "critic", n_critic, critic_layer_norm), ("modules_actor", "actor", n_policy, policy_layer_norm)):
+        _mlp_paths(m, pre, (mod, "network"), n, ln)
     m["critic/head/kernel"] = [("modules_critic", "Dense_0", "kernel")]
     m["critic/head/bias"] = [("modules_critic", "Dense_0", "bias")]
     m["actor/mean/kernel"] = [("modules_actor", "Dense_0", "kernel")]
@@ -273,11 +280,12 @@ def export_tree(core, section: str, image_keys, duplicate_encoder_under_critic: 
     cfg = core.cfg
     etype = "small" if cfg.encoder_type == 1 else "resnet-pretrained"
     cd, pd = mlp_dims_of(core)
+    cln, pln = layer_norms_of(core)
     shapes = theta_shapes(cfg.n_cam, cfg.H, cfg.W, cfg.state_dim, cfg.act_dim, ensemble=cfg.ensemble, hidden=cfg.hidden,
                           encoder_type=etype, num_stack=max(cfg.num_stack, 1), std_parameterization=std_parameterization_of(core),
-                          critic_dims=cd, policy_dims=pd)
+                          critic_dims=cd, policy_dims=pd, critic_layer_norm=cln, policy_layer_norm=pln)
     shapes.update(trunk_shapes())
-    paths = theta_paths(image_keys, critic_mlp_name, etype, std_parameterization_of(core), cd, pd)
+    paths = theta_paths(image_keys, critic_mlp_name, etype, std_parameterization_of(core), cd, pd, cln, pln)
     if cfg.n_cam and etype != "small":
         # ONE frozen trunk: drq.py:165-176 passes the same `pretrained_encoder` module to every camera's
         # PreTrainedResNetEncoder, flax adopts a shared module once -- under the first camera in sorted-key order --

@@ -33,7 +33,7 @@ class SACAgent(DrQAgent):
                       target_entropy: Optional[float] = None, backup_entropy: bool = False,
                       actor_optimizer_kwargs: dict = None, critic_optimizer_kwargs: dict = None,
                       temperature_optimizer_kwargs: dict = None, batch_size: int = 256, device: int = 0, param_init: str = "numpy",
-                      mlp_dropout: bool = False, mlp_shapes: bool = False,
+                      mlp_dropout: bool = False, mlp_shapes: bool = False, mlp_plain: bool = False,
                       **kwargs):
         """sac.py:486-542 -> create (:323-400).  Built natively: the configuration of utils/launcher.py:50-76
         (REDQ subsample 2, tanh-squashed exp-parameterised policy, LayerNorm+tanh 256x256 MLPs); hidden_dims=[h, h] in both
@@ -43,19 +43,26 @@ class SACAgent(DrQAgent):
         "softplus" or "uniform" and tanh_squash_distribution True or False run in the head kernels ("fixed" is refused).
         mlp_shapes=True reads each network's own hidden_dims instead: 1 to 4 layers, every width a multiple of 64 in [64, 1024], the
         critic's list independent of the policy's (utils.init.mlp_layer_dims; create_drq's docstring).
+        mlp_plain=True reads each network's own use_layer_norm (absent: True): a network with False has no LayerNorm in its MLP
+        (utils.init.mlp_layer_norms; create_drq's docstring).
         param_init: "numpy" (default) or "reference" (the reference's own initialisers and keys, utils/init_ref.py)."""
         pk = policy_kwargs or {}
         std_param, squash = pinit.policy_mode(pk)
         # mlp_shapes=True: each network's own depth and per-layer widths (mlp.py:19-31); else the one width of [h, h], as always
-        dims = pinit.mlp_layer_dims(critic_network_kwargs, policy_network_kwargs) if mlp_shapes else None
-        hidden = dims[0][0] if mlp_shapes else pinit.mlp_hidden_width(critic_network_kwargs, policy_network_kwargs)
+        dims = pinit.mlp_layer_dims(critic_network_kwargs, policy_network_kwargs, mlp_plain) if mlp_shapes else None
+        hidden = dims[0][0] if mlp_shapes else pinit.mlp_hidden_width(critic_network_kwargs, policy_network_kwargs, mlp_plain)
+        # mlp_plain=True: each network's own use_layer_norm (mlp.py:29-30); else LayerNorm in both, as always
+        lns = pinit.mlp_layer_norms(critic_network_kwargs, policy_network_kwargs) if mlp_plain else (True, True)
         critic_act, policy_act = pinit.mlp_activations(critic_network_kwargs, policy_network_kwargs, mlp_dropout)
         critic_drop, policy_drop = pinit.mlp_dropout_rates(critic_network_kwargs, policy_network_kwargs) if mlp_dropout else (0.0, 0.0)
         if mlp_shapes:
             pinit.check_shapes_dropout(dims[0], dims[1], critic_drop, policy_drop)
             if dims[0] == dims[1] and len(dims[0]) == 2 and dims[0][0] == dims[0][1]:
                 dims = None    # [h, h] twice: the very agent the call without the switch makes
+        pinit.check_plain_dropout(*lns, critic_drop, policy_drop)
         shape_kw = {} if dims is None else {"critic_dims": dims[0], "policy_dims": dims[1]}
+        if lns != (True, True):    # (True, True): the very agent the call without the switch makes
+            shape_kw.update(critic_layer_norm=lns[0], policy_layer_norm=lns[1])
         ao = {"learning_rate": 3e-4, "warmup_steps": 2000, **(actor_optimizer_kwargs or {})}     # sac.py:333-336
         co = {"learning_rate": 3e-4, "warmup_steps": 2000, **(critic_optimizer_kwargs or {})}    # sac.py:337-340
         to = {"learning_rate": 3e-4, **(temperature_optimizer_kwargs or {})}                     # sac.py:341-343
@@ -86,7 +93,8 @@ class SACAgent(DrQAgent):
                       discount=discount, soft_target_update_rate=soft_target_update_rate,
                       target_entropy=target_entropy, backup_entropy=backup_entropy,
                       critic_activation=critic_act, policy_activation=policy_act,
-                      critic_dropout_rate=critic_drop, policy_dropout_rate=policy_drop)
+                      critic_dropout_rate=critic_drop, policy_dropout_rate=policy_drop,
+                      **({} if lns == (True, True) else {"critic_use_layer_norm": lns[0], "policy_use_layer_norm": lns[1]}))
         agent = cls(core, (), config, seed)
         agent._opts = {"actor": ao, "critic": co, "temperature": {"warmup_steps": 0, **to}}
         if param_init == "reference":

@@ -87,6 +87,9 @@ struct serl_agent {
   // other entry point.  Nothing below reads cfg.hidden.
   int critic_dims[kL] = {0, 0, 0, 0}, policy_dims[kL] = {0, 0, 0, 0};
   int n_critic = 0, n_policy = 0;
+  // serl_agent_create_layer_norm: whether each MLP's layers have their LayerNorm (mlp.py:29-30, use_layer_norm); true from every
+  // other entry point.  Read by build_layout alone: the layers carry it from there (DenseLn::ln).
+  bool critic_ln = true, policy_ln = true;
   // serl_agent_create_dropout: the rate of the Dropout in front of each MLP's two LayerNorm rows (mlp.py:27-28); 0 = none.
   // mlp_bound: what serl_agent_set_mlp_noise left for the next update / phase / dry-run call; mlp_cur: what the call in progress
   // (mlp_depth > 0: its outermost entry point took the binding) reads.  MlpNoiseScope, below.
@@ -216,10 +219,10 @@ void build_layout(serl_agent* a) {
   const int N = c.ensemble;
   const long A = c.act_dim;
   const int Hc = a->critic_dims[a->n_critic - 1], Hp = a->policy_dims[a->n_policy - 1];   // the widths the heads read
-  const auto mlp_leaves = [&](DenseLn* layers, const std::string& net, const int* dims, int n, int groups, int in, int act, double drop) {
+  const auto mlp_leaves = [&](DenseLn* layers, const std::string& net, const int* dims, int n, int groups, int in, int act, double drop, bool ln) {
     for (int j = 0; j < n; ++j) {
       const std::string k = std::to_string(j + 1);
-      layers[j] = add_dense_ln_leaves(L, off, net + "/w" + k, net + "/b" + k, net + "/ln" + k, groups, j ? dims[j - 1] : in, dims[j], act, drop);
+      layers[j] = add_dense_ln_leaves(L, off, net + "/w" + k, net + "/b" + k, net + "/ln" + k, groups, j ? dims[j - 1] : in, dims[j], act, drop, ln);
     }
   };
   const CamHeadOffsets ch = add_cam_head_leaves(L, off, c.n_cam, a->D, c.bottleneck, [&](const std::string& p) {
@@ -232,7 +235,7 @@ void build_layout(serl_agent* a) {
   });
   o.enc0 = ch.first; o.cam_stride = ch.stride; o.cam = ch.dense;
   o.nc = a->n_critic; o.na = a->n_policy;
-  mlp_leaves(o.c, "critic", a->critic_dims, o.nc, N, a->XA, a->critic_act, a->critic_drop);
+  mlp_leaves(o.c, "critic", a->critic_dims, o.nc, N, a->XA, a->critic_act, a->critic_drop, a->critic_ln);
   // DrQ: one Dense(1) head shared by the ensemble (drq.py:201-207); state-only SAC: ensemblize vmaps the whole
   // Critic, so every member has its own head (actor_critic_nets.py:49-73,156-164)
   o.c_hw = add_leaf(L, off, "critic/head/kernel", a->state_only ? N * Hc : Hc);
@@ -243,7 +246,7 @@ void build_layout(serl_agent* a) {
                                  c.proprio_dim, kActTanh);
   }
   o.Pc = off;
-  mlp_leaves(o.a, "actor", a->policy_dims, o.na, 1, a->E, a->policy_act, a->policy_drop);
+  mlp_leaves(o.a, "actor", a->policy_dims, o.na, 1, a->E, a->policy_act, a->policy_drop, a->policy_ln);
   o.a_Wm = add_leaf(L, off, "actor/mean/kernel", Hp * A);
   o.a_bm = add_leaf(L, off, "actor/mean/bias", A);
   a->pol_mode = a->std_param | (a->no_tanh ? kPolNoTanh : 0);
@@ -940,16 +943,33 @@ int serl_agent_create_mlp(const serl_agent_cfg* cfg, int std_param, int no_tanh,
 
 static int create_agent(const serl_agent_cfg* cfg, int std_param, int no_tanh, int critic_act, int policy_act, double critic_dropout,
                         double policy_dropout, const int* critic_dims, int n_critic, const int* policy_dims, int n_policy, bool shapes,
-                        serl_agent** out);
+                        int critic_layer_norm, int policy_layer_norm, serl_agent** out);
 
 // mlp.py:19-31: MLP loops over hidden_dims of any length; sac.py:516-524, drq.py:188-207: the critic and the policy are built
 // from separate kwargs, so the two lists are independent.  The heads follow the last width of their network.
+// (= serl_agent_create_layer_norm with (1, 1))
 int serl_agent_create_shapes(const serl_agent_cfg* cfg, int std_param, int no_tanh, int critic_act, int policy_act,
                              const int* critic_dims, int n_critic, const int* policy_dims, int n_policy, serl_agent** out) {
+  return serl_agent_create_layer_norm(cfg, std_param, no_tanh, critic_act, policy_act, critic_dims, n_critic, policy_dims, n_policy, 1, 1, out);
+}
+
+// mlp.py:29-30: `if self.use_layer_norm: x = nn.LayerNorm()(x)` in every hidden layer; sac.py:516-524, drq.py:188-207: the critic
+// and the policy are built from separate kwargs, so the two flags are independent.  A layer without it is y = act(Dense(x) + b)
+// with the leaves w<j> and b<j> alone.  The encoder's bottleneck and proprio layers keep theirs (resnet_v1.py:371-374, encoding.py:66-68).
+int serl_agent_create_layer_norm(const serl_agent_cfg* cfg, int std_param, int no_tanh, int critic_act, int policy_act,
+                                 const int* critic_dims, int n_critic, const int* policy_dims, int n_policy, int critic_layer_norm,
+                                 int policy_layer_norm, serl_agent** out) {
   SERL_REQUIRE(cfg && out, "NULL argument");
   SERL_REQUIRE(critic_dims && policy_dims, "%s is NULL: the hidden widths of the %s's MLP, 1 to %d of them",
                critic_dims ? "policy_dims" : "critic_dims", critic_dims ? "policy" : "critic", SERL_MAX_MLP_LAYERS);
-  return create_agent(cfg, std_param, no_tanh, critic_act, policy_act, 0.0, 0.0, critic_dims, n_critic, policy_dims, n_policy, true, out);
+  return create_agent(cfg, std_param, no_tanh, critic_act, policy_act, 0.0, 0.0, critic_dims, n_critic, policy_dims, n_policy, true,
+                      critic_layer_norm, policy_layer_norm, out);
+}
+
+// mlp.py:29-30: whether the layers of an agent's critic (network 0) or policy (1) MLP have their LayerNorm
+int serl_agent_mlp_layer_norm(serl_agent* a, int network) {
+  if (!a || (network != 0 && network != 1)) return -1;
+  return (network ? a->policy_ln : a->critic_ln) ? 1 : 0;
 }
 
 // mlp.py:19-31; sac.py:516-524, drq.py:188-207: the hidden widths an agent was created with
@@ -966,14 +986,18 @@ int serl_agent_create_dropout(const serl_agent_cfg* cfg, int std_param, int no_t
                               double policy_dropout, serl_agent** out) {
   SERL_REQUIRE(cfg && out, "NULL argument");
   const int dims[2] = {cfg->hidden, cfg->hidden};
-  return create_agent(cfg, std_param, no_tanh, critic_act, policy_act, critic_dropout, policy_dropout, dims, 2, dims, 2, false, out);
+  return create_agent(cfg, std_param, no_tanh, critic_act, policy_act, critic_dropout, policy_dropout, dims, 2, dims, 2, false, 1, 1, out);
 }
 
 // every entry point's agent.  `shapes`: the lists are the caller's (serl_agent_create_shapes) and are checked one by one; else
 // they repeat cfg->hidden, which is checked as it always was.
 static int create_agent(const serl_agent_cfg* cfg, int std_param, int no_tanh, int critic_act, int policy_act, double critic_dropout,
                         double policy_dropout, const int* critic_dims, int n_critic, const int* policy_dims, int n_policy, bool shapes,
-                        serl_agent** out) {
+                        int critic_layer_norm, int policy_layer_norm, serl_agent** out) {
+  SERL_REQUIRE(critic_layer_norm == 0 || critic_layer_norm == 1, "critic_layer_norm %d is not 0 (no LayerNorm) or 1", critic_layer_norm);
+  SERL_REQUIRE(policy_layer_norm == 0 || policy_layer_norm == 1, "policy_layer_norm %d is not 0 (no LayerNorm) or 1", policy_layer_norm);
+  SERL_REQUIRE((critic_layer_norm || !(critic_dropout > 0.0)) && (policy_layer_norm || !(policy_dropout > 0.0)),
+               "Dropout in an MLP without LayerNorm is not served");
   // (the keep probability float32(1 - rate) must itself lie below 1 and above 0)
   SERL_REQUIRE(critic_dropout >= 0.0 && (float)(1.0 - critic_dropout) > 0.f, "critic_dropout %g: a Dropout rate lies in [0, 1)", critic_dropout);
   SERL_REQUIRE(policy_dropout >= 0.0 && (float)(1.0 - policy_dropout) > 0.f, "policy_dropout %g: a Dropout rate lies in [0, 1)", policy_dropout);
@@ -1033,6 +1057,7 @@ static int create_agent(const serl_agent_cfg* cfg, int std_param, int no_tanh, i
   a->critic_act = critic_act; a->policy_act = policy_act;
   a->critic_drop = critic_dropout; a->policy_drop = policy_dropout;
   a->n_critic = n_critic; a->n_policy = n_policy;
+  a->critic_ln = critic_layer_norm != 0; a->policy_ln = policy_layer_norm != 0;
   for (int j = 0; j < n_critic; ++j) a->critic_dims[j] = critic_dims[j];
   for (int j = 0; j < n_policy; ++j) a->policy_dims[j] = policy_dims[j];
   { const char* e = getenv("SERL_CHAIN_FUSE"); a->fuse = !(e && e[0] == '0'); }

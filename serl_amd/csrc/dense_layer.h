@@ -3,6 +3,8 @@
 // describes the layer (DenseLn), a carve the tensors of one evaluation (DenseLnIo) and of one backward pass (DenseLnGrad); the
 // functions below derive the arguments of every launch that touches the layer, so that no caller writes one of its strides.
 // Fields that only group index 0 multiplies (one group) are filled like any other; `beta` is always passed (the swish backward reads it).
+// A layer of an MLP with use_layer_norm=False (mlp.py:29-30) is the same layer without the LayerNorm ("plain", DenseLn::ln == 0):
+// y = act(Dense(x) + b), two leaves, and the same launches one for one -- the row launches take its arguments without gamma and beta.
 #pragma once
 #include "heads.h"
 
@@ -12,6 +14,7 @@ struct DenseLn {
   long W, b, g, be;      // group 0's kernel [K][N], bias, LayerNorm scale and LayerNorm bias: offsets into a parameter vector
   long w_gs, p_gs;       // floats from one group's kernel, and from one group's three vectors, to the next group's
   int groups, K, N, act; // act: kAct*
+  int ln;                // 1: LayerNorm between Dense and activation; 0: none (mlp.py:29-30) -- g and be are then -1, no leaves
   float keep;            // Dropout between Dense and LayerNorm (mlp.py:27-28): float32(1 - rate), the rate a double in (0, 1) as the
                          // reference's keep_prob = 1.0 - rate is one -- what its bernoulli compares with and its division divides by; 0: none
 };
@@ -35,14 +38,15 @@ inline LnDrop layer_drop(const DenseLn& L, const DenseLnDrop& s) {
   return d;
 }
 // Appends the layer's four leaves -- `groups` kernels, biases, scales and shifts back to back in each -- at `off`, which moves
-// behind them.
+// behind them.  layer_norm false: the kernels and biases alone.
 inline DenseLn add_dense_ln_leaves(std::vector<Leaf>& v, long& off, const std::string& kernel, const std::string& bias,
-                                   const std::string& ln, int groups, int K, int N, int act, double drop = 0.0) {
+                                   const std::string& ln, int groups, int K, int N, int act, double drop = 0.0, bool layer_norm = true) {
   DenseLn l{};
   l.W = add_leaf(v, off, kernel, (long)groups * K * N);
   l.b = add_leaf(v, off, bias, (long)groups * N);
-  l.g = add_leaf(v, off, ln + "/scale", (long)groups * N);
-  l.be = add_leaf(v, off, ln + "/bias", (long)groups * N);
+  l.ln = layer_norm ? 1 : 0;
+  l.g = layer_norm ? add_leaf(v, off, ln + "/scale", (long)groups * N) : -1;
+  l.be = layer_norm ? add_leaf(v, off, ln + "/bias", (long)groups * N) : -1;
   l.w_gs = groups > 1 ? (long)K * N : 0; l.p_gs = groups > 1 ? N : 0; l.groups = groups; l.K = K; l.N = N; l.act = act;
   l.keep = drop > 0.0 ? (float)(1.0 - drop) : 0.f;
   return l;
@@ -51,11 +55,13 @@ inline DenseLn add_dense_ln_leaves(std::vector<Leaf>& v, long& off, const std::s
 struct DenseLnIo {   // one evaluation on `rows` rows per group
   const float* x; long ldx, x_gs;   // input [rows][K] (row stride ldx); group g's at x + g * x_gs (0: one input for all)
   float* y; long ld_y, y_goff;      // y[row * ld_y + g * y_goff + col]: column slices of a wider row, or one block per group
-  float *xhat, *rstd;               // [groups * rows][N], [groups * rows]: what a backward pass reads, or nullptr
+  float *xhat, *rstd;               // [groups * rows][N], [groups * rows]: what a backward pass reads, or nullptr (a plain layer keeps
+                                    // its pre-activation in xhat and leaves rstd alone)
 };
 struct DenseLnGrad {   // one backward pass
   float* dy; long ld_dy, dy_goff;   // gradient wrt y, addressed like y (nullptr: the rank-1 form through the critic head)
-  float *dpre, *dg;                 // [groups * rows][N] each: gradient wrt the Dense output, and dy * act'
+  float *dpre, *dg;                 // [groups * rows][N] each: gradient wrt the Dense output, and dy * act' (a plain layer: the two
+                                    // coincide, dpre alone is written and read)
 };
 
 // Y = X W as `splitk` K-split slabs behind `slabs` ([group][split][rows][N])
@@ -67,7 +73,8 @@ inline LnFwdArgs layer_ln_fwd(const DenseLn& L, const float* P, const DenseLnIo&
                               const DenseLnDrop& site = DenseLnDrop{}) {
   LnFwdArgs l{};
   l.slabs = g.C; l.S = g.splitk; l.slab_stride = g.sCz;
-  l.bias = P + L.b; l.gamma = P + L.g; l.beta = P + L.be; l.pstride = L.p_gs;
+  l.bias = P + L.b; l.pstride = L.p_gs;
+  if (L.ln) { l.gamma = P + L.g; l.beta = P + L.be; }   // (else nullptr: the plain row)
   l.rows = L.groups * rows; l.rows_per_group = rows;
   l.y = t.y; l.ld_y = t.ld_y; l.y_goff = t.y_goff;
   l.xhat = t.xhat; l.rstd = t.rstd; l.act = L.act;
@@ -84,14 +91,17 @@ inline LnBwdArgs layer_ln_bwd(const DenseLn& L, const float* P, const DenseLnIo&
   LnBwdArgs l{};
   l.dy = d.dy; l.ld_dy = d.ld_dy; l.dy_goff = d.dy_goff;
   l.y = t.y; l.ld_y = t.ld_y; l.y_goff = t.y_goff;
-  l.xhat = t.xhat; l.rstd = t.rstd; l.gamma = P + L.g; l.beta = P + L.be; l.pstride = L.p_gs;
+  l.xhat = t.xhat; l.rstd = t.rstd; l.pstride = L.p_gs;
+  if (L.ln) { l.gamma = P + L.g; l.beta = P + L.be; }   // (else nullptr: the plain row, which writes dx alone)
   l.rows = L.groups * rows; l.rows_per_group = rows; l.D = L.N;
   l.dx = d.dpre; l.dg = d.dg; l.act = L.act;
   l.drop = layer_drop(L, site);
   return l;
 }
-// Gradients of the scale, shift and bias into G, a gradient vector indexed like the parameter vector
+// Gradients of the scale, shift and bias into G, a gradient vector indexed like the parameter vector.  A plain layer has the
+// bias alone, the column sum of dpre (Colsum3Args mode 1): no dg or xhat is read, no scale or shift slot written.
 inline Colsum3Args layer_colsum(const DenseLn& L, const DenseLnIo& t, const DenseLnGrad& d, int rows, float* G) {
+  if (!L.ln) return Colsum3Args{d.dpre, nullptr, nullptr, L.groups, rows, L.N, nullptr, G + L.b, nullptr, L.p_gs, 1};
   return Colsum3Args{d.dg, t.xhat, d.dpre, L.groups, rows, L.N, G + L.g, G + L.be, G + L.b, L.p_gs, 0};
 }
 // Gradient of the kernel, written in place into G

@@ -22,6 +22,8 @@ int reduce_slabs(const float* slabs, int S, long slab_stride, int groups, int ro
                  hipStream_t stream, float scale = 1.0f);
 
 // D: the row width of every instance, a multiple of 64 in [64, 1024] (one wave per row, D / 64 columns per lane)
+// Instances without gamma and beta are LayerNorm-free MLP layers (mlp.py:29-30; plain_row): y = act(bias + slabs), the same riders,
+// the pre-activation in xhat, rstd not written.  All instances of a launch are plain or none is; plain ones carry no Dropout.
 int ln_fwd_multi(const LnFwdArgs* a, int n, int D, hipStream_t stream);
 // One width-256 ReLU instance with a row-dot (the reward classifier's head), closed for reward labelling: dot_out = logits,
 // label[row] = sigmoid(logit) >= 0.5, mean[0] = the labels' mean, summed in a fixed order inside the launch (ctr: one zeroed
@@ -55,6 +57,9 @@ struct LnBwdArgs {
 // up to kMaxMulti LayerNorm backward passes in one launch (+ the critic-loss rider when loss.on).  Widths 64 and 256 may share a
 // launch (the encoder heads); any other width (an MLP layer at hidden != 256) must be the width of every instance.  One
 // instance of width 64 or 256 without a rider takes a launch of its own kind with one LnBwdArgs for arguments.
+// Instances without gamma are LayerNorm-free MLP layers (mlp.py:29-30, use_layer_norm=False; plain_bwd_row): dx = dy * act'(.) from y
+// and, for swish, the pre-activation the forward row kept in xhat; rstd, beta and dg are not touched (dg == dx).  All instances
+// of a launch are plain or none is; plain ones share one width and carry no Dropout.
 int ln_bwd_multi(const LnBwdArgs* a, int n, const LossArgs& loss, hipStream_t stream);
 inline int ln_bwd(const LnBwdArgs& a, hipStream_t stream) { return ln_bwd_multi(&a, 1, LossArgs{}, stream); }
 

@@ -349,6 +349,43 @@ __device__ __forceinline__ float ln_row(const LnFwdArgs& a, int row, int lane) {
   return d;
 }
 
+// The LayerNorm-free ("plain") row of an MLP layer with use_layer_norm=False (mlp.py:23-31: y = act(Dense(x) + b)), in ln_row's
+// lane-to-column layouts and with its gather: bias first, then the slabs in index order.  No statistics, so the row itself
+// needs no exchange between lanes; the dot_out rider (the critic's Q head on its last layer) keeps ln_row's: a lane's columns in
+// ascending order, then the xor butterfly.  What the backward reads: y (tanh and relu differentiate from it) and, for swish, the
+// pre-activation, which goes to the layer's xhat buffer (a plain layer has no normalised row to keep there); rstd is not written.
+// A launch is plain when its instances carry no gamma (LnFwdArgs); a row kernel of its own, so that ln_row's text stays what it is.
+template <int VPL, bool BLOCKED>
+__device__ __forceinline__ float plain_row(const LnFwdArgs& a, int row, int lane) {
+  constexpr int D = 64 * VPL, kStep = kLnStep<BLOCKED>;
+  const int grp = row / a.rows_per_group;
+  const long lrow = row - grp * a.rows_per_group;
+  const int c0 = ln_col0<VPL, BLOCKED>(lane);
+  const long base = (long)grp * a.S * a.slab_stride + lrow * D + c0;
+  const long pb = (long)grp * a.pstride + c0;
+  float v[VPL];
+  ln_gather<VPL, BLOCKED>(a, base, pb, v);
+  if (a.xhat) {
+#pragma unroll
+    for (int j = 0; j < VPL; ++j) a.xhat[(long)row * D + c0 + kStep * j] = v[j];
+  }
+  ln_activate(a.act, v);
+  float d = 0.f;
+#pragma unroll
+  for (int j = 0; j < VPL; ++j) {
+    const int col = c0 + kStep * j;
+    a.y[lrow * a.ld_y + (long)grp * a.y_goff + col] = v[j];
+    if (a.dot_out) d += v[j] * a.dot_w[(long)grp * a.dot_gstride + col];
+  }
+  if (a.dot_out) {
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) d += __shfl_xor(d, off);
+    d += a.dot_b[(long)grp * a.dot_b_gstride];
+    if (lane == 0) a.dot_out[row] = d;
+  }
+  return d;
+}
+
 // The raw standard deviation of a std parameterisation (actor_critic_nets.py:196-211) before the clip to [std_min, std_max]
 template <int MODE>
 __device__ __forceinline__ float policy_std_raw(float ls) {
@@ -982,6 +1019,14 @@ __global__ __launch_bounds__(256) void ln_fwd_drop_kernel(Multi<LnFwdArgs> mv) {
   if (row >= a.rows) return;
   ln_row<VPL, BLOCKED, true>(a, row, lane);
 }
+// ... of a launch whose instances are LayerNorm-free layers (mlp.py:29-30, use_layer_norm=False): plain_row in the same grid
+template <int VPL, bool BLOCKED>
+__global__ __launch_bounds__(256) void plain_fwd_kernel(Multi<LnFwdArgs> mv) {
+  const LnFwdArgs& a = mv.v[blockIdx.y];
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (row >= a.rows) return;
+  plain_row<VPL, BLOCKED>(a, row, lane);
+}
 
 // The reward classifier's head closed for labelling (vice.py:546,594: rewards = (sigmoid(classifier(next_obs)) >= 0.5) * 1.0): the
 // LayerNorm -> ReLU -> Dense(1) row of ln_row at width 256 (one row per wave; the logit goes to a.dot_out as in the train=False
@@ -1055,9 +1100,16 @@ int ln_fwd_multi(const LnFwdArgs* as, int n, int D, hipStream_t stream) {
     mv.v[i] = as[i];
     rows = std::max(rows, as[i].rows);
     drop = drop || as[i].drop.mode != kLnDropNone;
+    // (the instances of a launch are evaluations of ONE layer: all of them have a LayerNorm, or none has)
+    SERL_REQUIRE((as[i].gamma == nullptr) == (as[0].gamma == nullptr) && (as[i].gamma == nullptr) == (as[i].beta == nullptr),
+                 "LayerNorm row: instance %d %s a LayerNorm and instance 0 %s; plain and LayerNorm rows do not share a launch", i,
+                 as[i].gamma ? "has" : "lacks", as[0].gamma ? "has" : "lacks");
   }
   dim3 grid(cdiv(rows, 4), n);
-  if (drop) SERL_LN_LAUNCH(D, (ln_fwd_drop_kernel<1, false>), (ln_fwd_drop_kernel<4, true>), ln_fwd_drop_kernel, grid, dim3(256), 0, stream, mv)
+  if (!as[0].gamma) {
+    SERL_REQUIRE(!drop, "plain row (no LayerNorm) with Dropout: not served");
+    SERL_LN_LAUNCH(D, (plain_fwd_kernel<1, false>), (plain_fwd_kernel<4, true>), plain_fwd_kernel, grid, dim3(256), 0, stream, mv)
+  } else if (drop) SERL_LN_LAUNCH(D, (ln_fwd_drop_kernel<1, false>), (ln_fwd_drop_kernel<4, true>), ln_fwd_drop_kernel, grid, dim3(256), 0, stream, mv)
   else SERL_LN_LAUNCH(D, (ln_fwd_kernel<1, false>), (ln_fwd_kernel<4, true>), ln_fwd_kernel, grid, dim3(256), 0, stream, mv)
   SERL_HIP(hipGetLastError());
   return SERL_OK;
@@ -1182,6 +1234,43 @@ __device__ __forceinline__ void ln_bwd_row(const LnBwdArgs& a, const LossArgs& L
   }
 }
 
+// backward of ONE plain row y = act(pre) (plain_row) by one wave, in the same layout: dpre = dy * act'.  tanh: 1 - y^2; ReLU: y > 0
+// (0 at 0, as jax.nn.relu's); swish: sigma(pre) + y (1 - sigma(pre)) with the pre-activation the forward row kept in xhat (read on
+// this path alone).  dy in ln_bwd_row's three forms: a tensor, the rank-1 dq (x) w, and dq derived inline from the launch's loss.
+// No row statistics, no exchange between lanes.  dg and dpre coincide: the row writes dx alone, and the bias's column sum and the
+// weight and input gradients all read it (layer_colsum, dense_layer.h); a.dg, a.rstd, a.gamma and a.beta are not touched.
+template <int VPL, bool BLOCKED>
+__device__ __forceinline__ void plain_bwd_row(const LnBwdArgs& a, const LossArgs& L, int row, int lane) {
+  const int grp = row / a.rows_per_group;
+  constexpr int D = VPL * 64, kStep = kLnStep<BLOCKED>;
+  float dg[VPL], y[VPL];
+  const long lr = row - grp * a.rows_per_group;
+  const int c0 = ln_col0<VPL, BLOCKED>(lane);
+  float dqr = 0.f;
+  if (a.dq_w) dqr = a.dq_inline ? 2.f * (L.q[row] - redq_target(L, (int)lr)) * L.inv_norm : (a.dq ? a.dq[row] : a.dq_const);
+#pragma unroll
+  for (int j = 0; j < VPL; ++j) {
+    const int col = c0 + kStep * j;
+    y[j] = a.y[lr * a.ld_y + (long)grp * a.y_goff + col];
+    dg[j] = a.dq_w ? dqr * a.dq_w[(long)grp * a.dq_w_gstride + col] : a.dy[lr * a.ld_dy + (long)grp * a.dy_goff + col];
+  }
+  if (a.act == kActTanh) {
+#pragma unroll
+    for (int j = 0; j < VPL; ++j) dg[j] *= 1.f - y[j] * y[j];
+  } else if (a.act == kActRelu) {
+#pragma unroll
+    for (int j = 0; j < VPL; ++j) dg[j] = y[j] > 0.f ? dg[j] : 0.f;
+  } else {
+#pragma unroll
+    for (int j = 0; j < VPL; ++j) {
+      const float sg = sigmoid_stable(a.xhat[(long)row * D + c0 + kStep * j]);
+      dg[j] *= sg + y[j] * (1.f - sg);
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < VPL; ++j) a.dx[(long)row * D + c0 + kStep * j] = dg[j];
+}
+
 // A LayerNorm-backward launch: blockIdx.y = instance, one wave per row, four rows per workgroup; the LAST workgroup of instance 0
 // is the critic-loss rider when loss.on.  VPL > 0: every instance has the width 64 * VPL (the MLP layers at a hidden width other
 // than 256).  VPL == 0: instances of width 256 or 64, each its own (the encoder heads: the cameras' bottleneck and the proprio
@@ -1212,6 +1301,18 @@ __global__ __launch_bounds__(256) void ln_bwd_drop_kernel(Multi<LnBwdArgs> mv, L
   else ln_bwd_row<1, false, true>(a, loss, row, lane);
 }
 
+// ... of a launch whose instances are LayerNorm-free layers, all of the width 64 * VPL (an MLP layer is alone in its launch):
+// plain_bwd_row in the same grid, the critic-loss rider in the same place
+template <int VPL, bool BLOCKED>
+__global__ __launch_bounds__(256) void plain_bwd_kernel(Multi<LnBwdArgs> mv, LossArgs loss) {
+  __shared__ float red[4][256];
+  if (loss.on && blockIdx.y == 0 && blockIdx.x == gridDim.x - 1) { critic_loss_body(loss, red); return; }
+  const LnBwdArgs& a = mv.v[blockIdx.y];
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (row >= a.rows) return;
+  plain_bwd_row<VPL, BLOCKED>(a, loss, row, lane);
+}
+
 // One instance of a default width without a rider (most LayerNorm backward launches of the default agent, BC, the classifier):
 // the same row behind a launch that carries one LnBwdArgs (ln_bwd_kernel's arguments are four of them and the loss).  Measured:
 // with ln_bwd_kernel in its place the update step is 0.36 % slower (profiles/README.md).
@@ -1233,8 +1334,12 @@ int ln_bwd_multi(const LnBwdArgs* as, int n, const LossArgs& loss, hipStream_t s
     SERL_REQUIRE(!as[i].dq_inline || (loss.on && as[i].dq_w && as[i].rows == loss.E * loss.B && as[i].rows_per_group == loss.B),
                  "inline dQ needs the loss arguments of the launch");
     // (the swish backward recomputes its pre-activation: it reads beta where the forward did)
-    SERL_REQUIRE(as[i].act >= 0 && as[i].act < kActCount && (as[i].act != kActSwish || as[i].beta),
+    // (... and a plain row reads the pre-activation its forward kept in xhat)
+    SERL_REQUIRE(as[i].act >= 0 && as[i].act < kActCount && (as[i].act != kActSwish || (as[i].gamma ? as[i].beta : as[i].xhat)),
                  "LayerNorm backward: activation code %d is not tanh (0), relu (1) or swish (2), or swish without beta", as[i].act);
+    // (the instances of a plain launch are evaluations of one MLP layer: no LayerNorm in any, one width, no Dropout)
+    SERL_REQUIRE((as[i].gamma == nullptr) == (as[0].gamma == nullptr) && (as[i].gamma || (as[i].D == as[0].D && as[i].drop.mode == kLnDropNone)),
+                 "LayerNorm backward: plain and LayerNorm rows in one launch, or plain rows of widths %d and %d, or with Dropout", as[0].D, as[i].D);
     SERL_REQUIRE(ln_drop_ok(as[i].drop, as[i].rows_per_group), "LayerNorm backward: bad Dropout description (mode %d, keep %g)", as[i].drop.mode, as[i].drop.keep);
     mv.v[i] = as[i];
     rows = std::max(rows, as[i].rows);
@@ -1244,7 +1349,8 @@ int ln_bwd_multi(const LnBwdArgs* as, int n, const LossArgs& loss, hipStream_t s
                  "LayerNorm widths %d and %d in one launch: widths other than 64 and 256 do not mix", as[0].D, as[i].D);
   }
   const dim3 grid(cdiv(rows, 4) + (loss.on ? 1 : 0), n);
-  if (drop) SERL_LN_LAUNCH(as[0].D, (ln_bwd_drop_kernel<kLnMixed, false>), (ln_bwd_drop_kernel<kLnMixed, false>), ln_bwd_drop_kernel, grid, dim3(256), 0, stream, mv, loss)
+  if (!as[0].gamma) SERL_LN_LAUNCH(as[0].D, (plain_bwd_kernel<1, false>), (plain_bwd_kernel<4, true>), plain_bwd_kernel, grid, dim3(256), 0, stream, mv, loss)
+  else if (drop) SERL_LN_LAUNCH(as[0].D, (ln_bwd_drop_kernel<kLnMixed, false>), (ln_bwd_drop_kernel<kLnMixed, false>), ln_bwd_drop_kernel, grid, dim3(256), 0, stream, mv, loss)
   else if (n == 1 && !loss.on && as[0].D == 256) SERL_LAUNCH_CHAIN((ln_bwd_one_kernel<4, true>), grid, dim3(256), 0, stream, as[0]);
   else if (n == 1 && !loss.on && as[0].D == 64) SERL_LAUNCH_CHAIN((ln_bwd_one_kernel<1, false>), grid, dim3(256), 0, stream, as[0]);
   else SERL_LN_LAUNCH(as[0].D, (ln_bwd_kernel<kLnMixed, false>), (ln_bwd_kernel<kLnMixed, false>), ln_bwd_kernel, grid, dim3(256), 0, stream, mv, loss)

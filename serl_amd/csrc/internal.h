@@ -128,7 +128,7 @@ struct LnDrop {
 };
 struct LnFwdArgs {
   const float* slabs; int S; long slab_stride;
-  const float *bias, *gamma, *beta; long pstride;
+  const float *bias, *gamma, *beta; long pstride;   // gamma == beta == nullptr: a plain row, no LayerNorm (ln_fwd_multi, heads.h)
   int rows, rows_per_group;
   float* y; long ld_y; long y_goff;  // y[local_row*ld_y + group*y_goff + col] (column slices / group blocks)
   float* xhat;           // [rows][D] or nullptr

@@ -21,7 +21,7 @@ import msgpack
 import numpy as np
 
 from ..agents.core import TX_NAMES
-from ..agents.flax_tree import leaves_from_tree, mlp_dims_of, std_parameterization_of, theta_paths, trunk_owner, _trunk_paths
+from ..agents.flax_tree import layer_norms_of, leaves_from_tree, mlp_dims_of, std_parameterization_of, theta_paths, trunk_owner, _trunk_paths
 
 _EXT_NDARRAY = 1
 
@@ -161,7 +161,9 @@ def load_state_dict(agent, sd: dict, restore_rng: bool = False):
     core, keys = agent.core, agent.image_keys
     etype = "small" if core.cfg.encoder_type == 1 else "resnet-pretrained"
     cd, pd = mlp_dims_of(core)
-    tp = theta_paths(keys, encoder_type=etype, std_parameterization=std_parameterization_of(core), critic_dims=cd, policy_dims=pd)
+    lns = dict(zip(("critic", "actor"), layer_norms_of(core)))
+    tp = theta_paths(keys, encoder_type=etype, std_parameterization=std_parameterization_of(core), critic_dims=cd, policy_dims=pd,
+                     critic_layer_norm=lns["critic"], policy_layer_norm=lns["actor"])
     # the leaves whose PRESENCE is geometry: the policy's std leaves (std_parameterization "uniform": log_stds, else Dense_1) and
     # the MLPs' layers (hidden_dims of any length: Dense_j / LayerNorm_j below each `network`)
     mlp_leaves = tuple(leaf for leaf in tp if re.fullmatch(r"(critic|actor)/(w|b|ln)\d+(/scale|/bias)?", leaf))
@@ -174,6 +176,10 @@ def load_state_dict(agent, sd: dict, restore_rng: bool = False):
         # a tree of another kind holds nothing at the paths of such a leaf, which the size check below reports as 0 elements ...
         for leaf in optional:
             if leaf in tp and _absent(tree, tp[leaf][0]):
+                if re.fullmatch(r"(critic|actor)/ln1/scale", leaf) and not _absent(tree, tp[leaf.split("/")[0] + "/w1"][0]):
+                    net = leaf.split("/")[0]
+                    raise ValueError(f"{section}: the state's {net} MLP has no LayerNorm ('{'/'.join(tp[leaf][0][:-1])}' is absent: "
+                                     f"use_layer_norm=False), this agent's {net} MLP has one; nothing was loaded")
                 yield leaf, np.zeros((0,), np.float32)
         # ... and a layer the tree holds and this agent lacks is refused here: no leaf of the agent would ever meet it
         for net, (mod, n) in mlp_modules.items():
@@ -184,6 +190,9 @@ def load_state_dict(agent, sd: dict, restore_rng: bool = False):
                 d = d[k]
             for name in sorted(d):
                 m = re.fullmatch(r"(Dense|LayerNorm)_(\d+)", name)
+                if m and m.group(1) == "LayerNorm" and not lns[net]:
+                    raise ValueError(f"{section}: '{'/'.join(mod + (name,))}' is a LayerNorm in the state, this agent's {net} MLP has "
+                                     f"none (use_layer_norm=False); nothing was loaded")
                 if m and int(m.group(2)) >= n:
                     got = sum(int(np.size(v)) for v in d[name].values()) if isinstance(d[name], dict) else int(np.size(d[name]))
                     raise ValueError(f"{section}: '{'/'.join(mod + (name,))}' holds {got} elements in the state, this agent's {net} MLP "

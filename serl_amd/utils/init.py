@@ -51,15 +51,19 @@ SMALL_FEATURES = (3, 32, 64, 128, 256)   # SmallEncoder(features=(32, 64, 128, 2
 HIDDEN_WIDTHS = tuple(range(64, 1025, 64))   # serl_agent_cfg.hidden: one wave per LayerNorm row, hidden / 64 columns per lane
 
 
-def mlp_hidden_width(critic_network_kwargs=None, policy_network_kwargs=None) -> int:
+_PLAIN_HINT = "; without LayerNorm with mlp_plain=True"
+
+
+def mlp_hidden_width(critic_network_kwargs=None, policy_network_kwargs=None, mlp_plain=False) -> int:
     """The one width h of the critic's and the policy's MLPs from the reference's `critic_network_kwargs` /
     `policy_network_kwargs` (hidden_dims=[h, h], LayerNorm, default [256, 256]).  Served: two layers of the same width, the same
-    in both networks, a multiple of 64 from 64 to 1024; anything else raises NotImplementedError."""
+    in both networks, a multiple of 64 from 64 to 1024; anything else raises NotImplementedError.  mlp_plain=True (the argument
+    of the same name of create_states / create_drq): use_layer_norm is mlp_layer_norms' to read."""
     served = "served: hidden_dims=[h, h] with LayerNorm, h a multiple of 64 in [64, 1024], the same h for critic and policy"
     widths = []
     for which, nk in (("critic_network_kwargs", critic_network_kwargs or {}), ("policy_network_kwargs", policy_network_kwargs or {})):
-        if not nk.get("use_layer_norm", True):
-            raise NotImplementedError(f"{which}: use_layer_norm=False ({served})")
+        if not mlp_plain and not nk.get("use_layer_norm", True):
+            raise NotImplementedError(f"{which}: use_layer_norm=False ({served}{_PLAIN_HINT})")
         dims = [int(d) for d in nk.get("hidden_dims", [256, 256])]
         if len(dims) != 2:
             raise NotImplementedError(f"{which}: hidden_dims={dims} has {len(dims)} layers ({served})")
@@ -76,18 +80,18 @@ def mlp_hidden_width(critic_network_kwargs=None, policy_network_kwargs=None) -> 
 MAX_MLP_LAYERS = 4   # SERL_MAX_MLP_LAYERS
 
 
-def mlp_layer_dims(critic_network_kwargs=None, policy_network_kwargs=None):
+def mlp_layer_dims(critic_network_kwargs=None, policy_network_kwargs=None, mlp_plain=False):
     """(critic, policy): the `hidden_dims` of the reference's MLP (networks/mlp.py:19-31 loops over a list of any length) from its
     two network kwargs, as tuples of ints: what create_states / create_drq read with mlp_shapes=True (without the switch
     mlp_hidden_width reads and refuses as it always did).  Default [256, 256].  Served: 1 to MAX_MLP_LAYERS layers per network,
     every width a multiple of 64 in [64, 1024], the two lists independent, LayerNorm on; anything else raises NotImplementedError
-    from the arguments alone."""
+    from the arguments alone.  mlp_plain=True: use_layer_norm is mlp_layer_norms' to read."""
     served = (f"served: hidden_dims of 1 to {MAX_MLP_LAYERS} layers with LayerNorm, every width a multiple of 64 in [64, 1024], "
               "the critic's list independent of the policy's")
     out = []
     for which, nk in (("critic_network_kwargs", critic_network_kwargs or {}), ("policy_network_kwargs", policy_network_kwargs or {})):
-        if not nk.get("use_layer_norm", True):
-            raise NotImplementedError(f"{which}: use_layer_norm=False ({served})")
+        if not mlp_plain and not nk.get("use_layer_norm", True):
+            raise NotImplementedError(f"{which}: use_layer_norm=False ({served}{_PLAIN_HINT})")
         dims = nk.get("hidden_dims", [256, 256])
         dims = list(dims) if isinstance(dims, (list, tuple, np.ndarray)) else [dims]
         if not 1 <= len(dims) <= MAX_MLP_LAYERS:
@@ -117,14 +121,16 @@ def resolve_mlp_dims(hidden=256, critic_dims=None, policy_dims=None):
             tuple(int(d) for d in policy_dims) if policy_dims is not None else (int(hidden), int(hidden)))
 
 
-def _mlp_shapes(net, lead, fan_in, dims):
-    """{leaf: shape} of one MLP, layer by layer as the arena lays them out; lead: () or (ensemble,)."""
+def _mlp_shapes(net, lead, fan_in, dims, layer_norm=True):
+    """{leaf: shape} of one MLP, layer by layer as the arena lays them out; lead: () or (ensemble,).  layer_norm False
+    (mlp.py:29-30, use_layer_norm=False): the kernels and biases alone."""
     sh = {}
     for j, d in enumerate(dims, 1):
         sh[f"{net}/w{j}"] = (*lead, fan_in, d)
         sh[f"{net}/b{j}"] = (*lead, d)
-        sh[f"{net}/ln{j}/scale"] = (*lead, d)
-        sh[f"{net}/ln{j}/bias"] = (*lead, d)
+        if layer_norm:
+            sh[f"{net}/ln{j}/scale"] = (*lead, d)
+            sh[f"{net}/ln{j}/bias"] = (*lead, d)
         fan_in = d
     return sh
 
@@ -152,6 +158,37 @@ def mlp_activations(critic_network_kwargs=None, policy_network_kwargs=None, mlp_
             raise NotImplementedError(f"{which}: dropout_rate={rate!r} ({served}; a positive rate below 1 with mlp_dropout=True)")
         out.append(_ACTIVATION_NAMES[name])
     return tuple(out)
+
+
+def mlp_layer_norms(critic_network_kwargs=None, policy_network_kwargs=None):
+    """What create_states / create_drq read with mlp_plain=True (without it use_layer_norm=False is refused by mlp_hidden_width /
+    mlp_layer_dims, as it always was).  (critic, policy): the `use_layer_norm` of the reference's MLP (networks/mlp.py:29-30) from its
+    two network kwargs, as bools: serl_agent_create_layer_norm's two flags.  An absent key means what utils/launcher.py writes and
+    this library has always meant, True -- not mlp.py's own default, False: pass it to get it.  Anything that is not a bool raises
+    NotImplementedError from the arguments alone."""
+    out = []
+    for which, nk in (("critic_network_kwargs", critic_network_kwargs or {}), ("policy_network_kwargs", policy_network_kwargs or {})):
+        flag = nk.get("use_layer_norm", True)
+        if not isinstance(flag, (bool, np.bool_)):
+            raise NotImplementedError(f"{which}: use_layer_norm={flag!r} (served: True or False)")
+        out.append(bool(flag))
+    return tuple(out)
+
+
+def check_plain_dropout(critic_layer_norm, policy_layer_norm, critic_dropout, policy_dropout):
+    """mlp_plain=True together with a positive dropout_rate under mlp_dropout=True in a network that has use_layer_norm=False:
+    not served (the LayerNorm-free rows carry no Dropout).  Nor is Dropout in a LayerNorm network beside a plain one:
+    serl_agent_create_layer_norm, the one entry point that makes a plain network, takes no rates."""
+    nets = (("critic_network_kwargs", critic_layer_norm, critic_dropout), ("policy_network_kwargs", policy_layer_norm, policy_dropout))
+    for which, ln, rate in nets:
+        if not ln and rate > 0:
+            raise NotImplementedError(f"{which}: use_layer_norm=False under mlp_plain=True with dropout_rate={rate!r} under "
+                                      "mlp_dropout=True (served: Dropout in agents whose two networks have their LayerNorm)")
+    if not (critic_layer_norm and policy_layer_norm):
+        for which, ln, rate in nets:
+            if rate > 0:
+                raise NotImplementedError(f"{which}: dropout_rate={rate!r} under mlp_dropout=True beside a network with use_layer_norm=False "
+                                          "under mlp_plain=True (served: Dropout in agents whose two networks have their LayerNorm)")
 
 
 def _dropout_rate_ok(rate):
@@ -204,8 +241,10 @@ def _policy_std_shapes(Hd, A, std_parameterization):
 
 
 def theta_shapes(n_cam, H, W, S, A, ensemble=10, hidden=256, bottleneck=256, sle_features=8, proprio_dim=64,
-                 encoder_type="resnet-pretrained", num_stack=1, std_parameterization="exp", critic_dims=None, policy_dims=None):
+                 encoder_type="resnet-pretrained", num_stack=1, std_parameterization="exp", critic_dims=None, policy_dims=None, critic_layer_norm=True,
+                 policy_layer_norm=True):
     """critic_dims / policy_dims: the hidden widths of each MLP, layer by layer (None: (hidden, hidden)); the heads follow the last.
+    critic_layer_norm / policy_layer_norm False: that MLP's layers own w<j> and b<j> alone (mlp.py:29-30, use_layer_norm=False).
     S: the proprio Dense's input width -- T * S for a stack of T = num_stack frames, which EncodingWrapper folds into the
     channels ("B T H W C -> B H W (T C)", common/encoding.py:39-44): the SmallEncoder's first kernel is then (3,3,3T,32).
     std_parameterization="uniform": actor/log_stds (A,) in place of actor/logstd/{kernel,bias}."""
@@ -213,9 +252,9 @@ def theta_shapes(n_cam, H, W, S, A, ensemble=10, hidden=256, bottleneck=256, sle
     if n_cam == 0:   # state-only SAC (SACAgent.create_states, sac.py:486-542): no encoder, per-member Q heads
         N = ensemble
         return {
-            **_mlp_shapes("critic", (N,), S + A, cd),
+            **_mlp_shapes("critic", (N,), S + A, cd, critic_layer_norm),
             "critic/head/kernel": (N, cd[-1], 1), "critic/head/bias": (N, 1),   # vmapped Dense(1): one bias per member
-            **_mlp_shapes("actor", (), S, pd),
+            **_mlp_shapes("actor", (), S, pd, policy_layer_norm),
             "actor/mean/kernel": (pd[-1], A), "actor/mean/bias": (A,),
             **_policy_std_shapes(pd[-1], A, std_parameterization),
             "temp/lagrange": (),
@@ -237,11 +276,11 @@ def theta_shapes(n_cam, H, W, S, A, ensemble=10, hidden=256, bottleneck=256, sle
         sh[f"enc/{k}/ln/bias"] = (bottleneck,)
     N = ensemble
     sh.update({
-        **_mlp_shapes("critic", (N,), E + A, cd),
+        **_mlp_shapes("critic", (N,), E + A, cd, critic_layer_norm),
         "critic/head/kernel": (cd[-1], 1), "critic/head/bias": (1,),
         "enc/proprio/dense/kernel": (S, proprio_dim), "enc/proprio/dense/bias": (proprio_dim,),
         "enc/proprio/ln/scale": (proprio_dim,), "enc/proprio/ln/bias": (proprio_dim,),
-        **_mlp_shapes("actor", (), E, pd),
+        **_mlp_shapes("actor", (), E, pd, policy_layer_norm),
         "actor/mean/kernel": (pd[-1], A), "actor/mean/bias": (A,),
         **_policy_std_shapes(pd[-1], A, std_parameterization),
         "temp/lagrange": (),

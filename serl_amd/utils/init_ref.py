@@ -83,18 +83,22 @@ def _init_of(name, shape):
 
 
 def theta_leaves(image_keys: Sequence[str], H, W, S, A, ensemble=10, encoder_type="resnet-pretrained", num_stack=1,
-                 hidden=256, std_parameterization="exp", critic_dims=None, policy_dims=None) -> List[Leaf]:
+                 hidden=256, std_parameterization="exp", critic_dims=None, policy_dims=None, critic_layer_norm=True,
+                 policy_layer_norm=True) -> List[Leaf]:
     """The trainable leaves of DrQAgent.create_drq (image_keys non-empty) or SACAgent.create_states (image_keys empty);
     hidden: the MLPs' width (hidden_dims=[hidden, hidden]), or critic_dims / policy_dims: each MLP's own widths, layer by layer
     (Dense_2 / LayerNorm_2 and up take their keys from their paths like every other leaf).  std_parameterization="uniform": the zero-initialised log_stds
     vector in place of Dense_1; every other leaf keeps its key (a flax key depends on the module's path and the scope's own
-    counter, not on its siblings), so the rest of the tree is bit-identical to the "exp" agent's."""
+    counter, not on its siblings), so the rest of the tree is bit-identical to the "exp" agent's.
+    critic_layer_norm / policy_layer_norm False (mlp.py:29-30): that MLP has no LayerNorm leaves; a LayerNorm draws nothing, so the
+    Dense leaves keep their keys and values."""
     from ..agents.flax_tree import theta_paths
     shapes = theta_shapes(len(image_keys), H, W, S, A, ensemble=ensemble, hidden=hidden, encoder_type=encoder_type,
                           num_stack=num_stack, std_parameterization=std_parameterization, critic_dims=critic_dims,
-                          policy_dims=policy_dims)
+                          policy_dims=policy_dims, critic_layer_norm=critic_layer_norm, policy_layer_norm=policy_layer_norm)
     paths = theta_paths(tuple(image_keys), encoder_type=encoder_type, std_parameterization=std_parameterization,
-                        critic_dims=critic_dims, policy_dims=policy_dims)
+                        critic_dims=critic_dims, policy_dims=policy_dims, critic_layer_norm=critic_layer_norm,
+                        policy_layer_norm=policy_layer_norm)
     # the vmapped module: DrQ ensemblizes the critic's MLP (drq.py:206-209), state SAC the whole Critic (sac.py:516-517)
     vm = ("modules_critic", "network") if image_keys else ("modules_critic",)
     out = []
@@ -220,12 +224,12 @@ def draw_flat(leaves: Sequence[Leaf], init_rng, device: Optional[int] = 0, tempe
 
 def theta_reference(image_keys, H, W, S, A, rng, ensemble=10, encoder_type="resnet-pretrained", temperature_init=1.0,
                     device: Optional[int] = 0, num_stack=1, hidden=256, std_parameterization="exp", critic_dims=None,
-                    policy_dims=None) -> Dict[str, np.ndarray]:
+                    policy_dims=None, critic_layer_norm=True, policy_layer_norm=True) -> Dict[str, np.ndarray]:
     """init_theta's leaves as the reference's DrQ / state-SAC create path draws them from `rng` (drq.py:69, sac.py:368).
     S is the flattened proprio width T * S of a stack of T = num_stack frames; the widened leaves draw with their real fan-in.
     hidden: the MLPs' width; its leaves draw with the fans of that width."""
     return draw_flat(theta_leaves(image_keys, H, W, S, A, ensemble, encoder_type, num_stack, hidden, std_parameterization,
-                                  critic_dims, policy_dims),
+                                  critic_dims, policy_dims, critic_layer_norm, policy_layer_norm),
                      init_rng_of(reference_key(rng)),
                      device, temperature_init)
 
