@@ -262,6 +262,7 @@ typedef struct serl_agent_cfg {
 #define SERL_STD_EXP 0
 #define SERL_STD_SOFTPLUS 1
 #define SERL_STD_UNIFORM 2
+#define SERL_STD_FIXED 3   /* serl_agent_create_fixed_std alone */
 #define SERL_ACT_TANH 0
 #define SERL_ACT_RELU 1
 #define SERL_ACT_SWISH 2
@@ -346,6 +347,23 @@ int serl_agent_create_layer_norm(const serl_agent_cfg* cfg, int std_param, int n
 /* Whether the layers of one MLP of any agent have their LayerNorm (networks/mlp.py:29-30): network 0 = critic, 1 = policy.
  * Returns 1 or 0; -1 on a NULL agent or another network code. */
 int serl_agent_mlp_layer_norm(serl_agent* a, int network /* 0 critic, 1 policy */);
+/* serl_agent_create_layer_norm with the fourth std parameterisation (actor_critic_nets.py:189-192,212: `fixed_std`, how the
+ * reference writes TD3): std_param == SERL_STD_FIXED and fixed_std = act_dim floats (host memory, copied), each finite and > 0:
+ *   std = clip(fixed_std, std_min, std_max), the same for every row, in float32 inside the head kernels (temperature 1).
+ * The head then has NO std parameter: the leaf table holds neither actor/logstd/{kernel,bias} nor actor/log_stds, the head GEMMs
+ * have one group (the mean), and no gradient, optimizer moment, target copy or checkpoint entry exists for a std.  The vector is
+ * a constant of the agent: device memory of its own outside the parameter arena, never stepped, averaged or all-reduced, and
+ * not part of serl_agent_get / serl_agent_set (serl_agent_fixed_std reads it back).  With the tanh bijector log pi still depends
+ * on the mean through the log-determinant; with no_tanh == 1 it depends on no parameter and the actor gradient is dL/da alone.
+ * fixed_std is NULL unless std_param == SERL_STD_FIXED and not NULL when it is: either mismatch, or an entry that is not a
+ * finite positive number, is SERL_ERR_INVALID with a message.  serl_agent_create_layer_norm is this function with NULL: it
+ * keeps refusing std_param 3 by its own range check, and every agent of the other three modes launches what it launched. */
+int serl_agent_create_fixed_std(const serl_agent_cfg* cfg, int std_param, int no_tanh, int critic_act, int policy_act,
+                                const int* critic_dims, int n_critic, const int* policy_dims, int n_policy, int critic_layer_norm,
+                                int policy_layer_norm, const float* fixed_std, serl_agent** out);
+/* The fixed_std vector of an agent made with SERL_STD_FIXED, as passed (before the clip): out = act_dim floats (host).
+ * SERL_ERR_INVALID on a NULL argument or an agent of another std parameterisation. */
+int serl_agent_fixed_std(serl_agent* a, float* out);
 int serl_agent_destroy(serl_agent* a);
 
 /* Parameter tree access (flat leaf names, see DESIGN.md "parameter arena"; the Python shim maps

@@ -59,6 +59,8 @@ CHAIN = [
     # read-only evaluation (serl_agent_eval_policy): launched on the update stream, possibly beside a prefetching trunk pass
     ("policy_stats_kernel<0>", 80),
     ("policy_stats_kernel<1>", 80),
+    ("policy_stats_fixed_kernel<false>", 80),   # ... of a fixed-std agent (serl_agent_create_fixed_std)
+    ("policy_stats_fixed_kernel<true>", 80),
 ]
 
 

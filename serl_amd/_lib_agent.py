@@ -85,6 +85,9 @@ SIGNATURES = {
     "serl_agent_create_shapes": [P(SerlAgentCfg), i32, i32, i32, i32, P(i32), i32, P(i32), i32, P(vp)],
     "serl_agent_create_layer_norm": [P(SerlAgentCfg), i32, i32, i32, i32, P(i32), i32, P(i32), i32, i32, i32, P(vp)],   # ... critic_layer_norm, policy_layer_norm
     "serl_agent_mlp_layer_norm": [vp, i32],   # network (0 critic, 1 policy) -> 1 / 0
+    # serl_agent_create_layer_norm's arguments, then fixed_std: act_dim floats with std_param SERL_STD_FIXED (3), NULL otherwise
+    "serl_agent_create_fixed_std": [P(SerlAgentCfg), i32, i32, i32, i32, P(i32), i32, P(i32), i32, i32, i32, P(C.c_float), P(vp)],
+    "serl_agent_fixed_std": [vp, P(C.c_float)],   # out: act_dim floats, the vector as passed
     "serl_agent_mlp_dims": [vp, i32, P(i32)],   # network (0 critic, 1 policy), dims[SERL_MAX_MLP_LAYERS] -> layer count
     "serl_agent_set_mlp_noise": [vp, P(SerlMlpNoise)],
     "serl_agent_destroy": [vp],

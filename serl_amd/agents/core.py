@@ -12,7 +12,8 @@ from .._handle import Handle
 from .._lib_agent import (APPLY_ACTOR_TEMP, APPLY_CRITIC, MLP_SITES, NET_BITS, TX_INDEX, SerlAgentCfg, SerlInfo,  # noqa: F401
                           SerlMlpNoise, SerlNoise)
 
-from ..utils.init import MLP_ACTIVATIONS, STD_PARAMETERIZATIONS, check_plain_dropout, check_shapes_dropout, resolve_mlp_dims
+from ..utils.init import (FIXED_STD, MLP_ACTIVATIONS, STD_PARAMETERIZATIONS, check_fixed_dropout, check_plain_dropout, check_shapes_dropout,
+                          resolve_mlp_dims)
 
 TX_NAMES = ("actor", "critic", "temperature")
 
@@ -27,7 +28,7 @@ class AgentCore(Handle):
                  critic_subsample_size=2, backup_entropy=False, num_stack=1, std_parameterization="exp",
                  tanh_squash_distribution=True, critic_activation="tanh", policy_activation="tanh",
                  critic_dropout=0.0, policy_dropout=0.0, critic_dims=None, policy_dims=None, critic_layer_norm=True,
-                 policy_layer_norm=True):
+                 policy_layer_norm=True, fixed_std=None):
         """optimizers: optional {"actor"|"critic"|"temperature": make_optimizer kwargs (common/optimizers.py:6-13:
         learning_rate, warmup_steps, cosine_decay_steps, weight_decay, clip_grad_norm)} overriding lr / warmup_steps.
         weight_decay decays every leaf of the tree, as optax.adamw does with the params the reference hands it -- with
@@ -41,7 +42,10 @@ class AgentCore(Handle):
         with either given the agent comes from serl_agent_create_shapes and `hidden` stands only for a list left out.  The
         attributes of the same names read (hidden, hidden) on a core made without them.
         critic_layer_norm / policy_layer_norm: MLP's `use_layer_norm` of each network (mlp.py:29-30, utils.init.mlp_layer_norms); with
-        either False the agent comes from serl_agent_create_layer_norm, and no Dropout rate may be positive."""
+        either False the agent comes from serl_agent_create_layer_norm, and no Dropout rate may be positive.
+        fixed_std: with std_parameterization="fixed" (and only then) the float32 vector of act_dim finite positive entries that
+        utils.init.policy_mode_fixed returns; the agent then comes from serl_agent_create_fixed_std, its head has no std leaf, and no
+        Dropout rate may be positive.  The attribute of the same name reads it back from the library (None for another mode)."""
         if target_entropy is None:
             target_entropy = -act_dim / 2
         self.cfg = SerlAgentCfg(device, n_cam, H, W, state_dim, act_dim, batch, ensemble, hidden,
@@ -57,7 +61,14 @@ class AgentCore(Handle):
         # the policy distribution is no field of serl_agent_cfg: it goes to serl_agent_create_policy (_create)
         self.std_parameterization = std_parameterization
         self.tanh_squash_distribution = bool(tanh_squash_distribution)
-        self._std_param = STD_PARAMETERIZATIONS.index(std_parameterization)
+        if (std_parameterization == FIXED_STD) != (fixed_std is not None):
+            raise ValueError(f"std_parameterization={std_parameterization!r} with fixed_std={fixed_std!r}: 'fixed' and fixed_std go together")
+        self._fixed_std = None
+        if fixed_std is not None:
+            self._fixed_std = np.ascontiguousarray(np.asarray(fixed_std, np.float32).reshape(-1))
+            if self._fixed_std.shape != (act_dim,) or not (np.isfinite(self._fixed_std).all() and (self._fixed_std > 0).all()):
+                raise ValueError(f"fixed_std must be {act_dim} finite positive numbers (got {fixed_std!r})")
+        self._std_param = 3 if fixed_std is not None else STD_PARAMETERIZATIONS.index(std_parameterization)   # SERL_STD_FIXED = 3
         # ... nor are the MLP activations: serl_agent_create_mlp
         self.critic_activation, self.policy_activation = critic_activation, policy_activation
         self._acts = (MLP_ACTIVATIONS.index(critic_activation), MLP_ACTIVATIONS.index(policy_activation))
@@ -72,6 +83,7 @@ class AgentCore(Handle):
                 raise TypeError(f"{name} must be a bool (got {flag!r})")
         self.critic_layer_norm, self.policy_layer_norm = bool(critic_layer_norm), bool(policy_layer_norm)
         check_plain_dropout(self.critic_layer_norm, self.policy_layer_norm, self.critic_dropout, self.policy_dropout)
+        check_fixed_dropout(self._fixed_std, self.critic_dropout, self.policy_dropout)
         if self._shapes:
             check_shapes_dropout(self.critic_dims, self.policy_dims, self.critic_dropout, self.policy_dropout)
         for name, kw in (optimizers or {}).items():
@@ -101,6 +113,12 @@ class AgentCore(Handle):
         super().__del__()
 
     def _create(self, cfg):
+        if self._fixed_std is not None:
+            cd, pd = (C.c_int32 * len(self.critic_dims))(*self.critic_dims), (C.c_int32 * len(self.policy_dims))(*self.policy_dims)
+            fs = (C.c_float * len(self._fixed_std))(*self._fixed_std.tolist())
+            return self.L.serl_agent_create_fixed_std(C.byref(cfg), self._std_param, 0 if self.tanh_squash_distribution else 1, *self._acts,
+                                                      cd, len(self.critic_dims), pd, len(self.policy_dims),
+                                                      int(self.critic_layer_norm), int(self.policy_layer_norm), fs, C.byref(self._h))
         if not (self.critic_layer_norm and self.policy_layer_norm):
             cd, pd = (C.c_int32 * len(self.critic_dims))(*self.critic_dims), (C.c_int32 * len(self.policy_dims))(*self.policy_dims)
             return self.L.serl_agent_create_layer_norm(C.byref(cfg), self._std_param, 0 if self.tanh_squash_distribution else 1, *self._acts,
@@ -119,6 +137,16 @@ class AgentCore(Handle):
     def leaves(self) -> Dict[str, int]:
         """{leaf: element count}"""
         return self._counts
+
+    @property
+    def fixed_std(self) -> Optional[np.ndarray]:
+        """float32[act_dim]: the fixed_std of a std_parameterization="fixed" agent as the library holds it (before the clip to
+        [std_min, std_max], which the head kernels apply); None for an agent of another std parameterisation."""
+        if self._fixed_std is None:
+            return None
+        out = np.zeros(self.cfg.act_dim, np.float32)
+        _lib.check(self.L.serl_agent_fixed_std(self._h, out.ctypes.data_as(C.POINTER(C.c_float))))
+        return out
 
     def set_trunk_mode(self, mode: str):
         """'f32' = exact fp32 MFMA convs, 'f16x3' = split-fp16 convs (default)."""

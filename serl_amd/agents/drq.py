@@ -174,7 +174,8 @@ class DrQAgent:
                    target_entropy: Optional[float] = None, backup_entropy: bool = False,
                    batch_size: int = 256, device: int = 0, learning_rate: float = 3e-4,
                    actor_optimizer_kwargs: dict = None, critic_optimizer_kwargs: dict = None,
-                   temperature_optimizer_kwargs: dict = None, param_init: str = "numpy", mlp_dropout: bool = False, mlp_shapes: bool = False, mlp_plain: bool = False, **kwargs):
+                   temperature_optimizer_kwargs: dict = None, param_init: str = "numpy", mlp_dropout: bool = False, mlp_shapes: bool = False, mlp_plain: bool = False,
+                   policy_fixed: bool = False, **kwargs):
         """drq.py:104-242.  Only the configuration the reference's examples run is built natively:
         encoder_type="resnet-pretrained", use_proprio=True, REDQ subsample 2, tanh-squashed
         exp-parameterised policy, LayerNorm+tanh MLPs (utils/launcher.py:79-116) -- 256x256 there; critic_network_kwargs /
@@ -194,6 +195,14 @@ class DrQAgent:
         policy_kwargs: std_parameterization "exp", "softplus" or "uniform" (one trainable log_stds vector, no Dense_1) and
         tanh_squash_distribution True or False all run in the head kernels; "fixed" is refused.  A key that is absent, or
         policy_kwargs=None, means the launcher's value ("exp", True).
+        policy_fixed=True also reads std_parameterization="fixed" with fixed_std (utils.init.policy_mode_fixed), how the reference
+        writes TD3 (sac.py:23-28): fixed_std is a scalar, broadcast, or action_dim numbers, each finite and positive, and
+        stds = clip(fixed_std, std_min, std_max) in every row.  The head then has no std parameter at all -- no Dense_1 and no
+        log_stds in the flax tree, the optimizer state or a checkpoint; agent.config["fixed_std"] holds the vector, which a
+        checkpoint does not carry.  fixed_std beside another std_parameterization, "fixed" without fixed_std (ValueError, as in the
+        reference), another length and a non-finite or non-positive entry are refused from the arguments alone; so is a
+        positive dropout_rate under mlp_dropout=True beside it.  Any other mode under the switch gives the agent the call
+        without the switch gives.
         Frame stacks: the sample observation carries T = observations[image_key].shape[0] frames and a (T, S) state, as
         ChunkingWrapper(obs_horizon=T) produces them; EncodingWrapper(enable_stacking=True) folds them into the channels and the
         proprio width (common/encoding.py:39-44,58-64).  T in 1..4 with encoder_type="small"; the pretrained ResNet-10 cannot take
@@ -211,7 +220,9 @@ class DrQAgent:
         if not use_proprio:
             raise NotImplementedError("only use_proprio=True")
         pk = policy_kwargs or {}
-        std_param, squash = pinit.policy_mode(pk)
+        # policy_fixed=True: "fixed" / fixed_std are read (actor_critic_nets.py:189-192); else refused, as always
+        A = int(np.asarray(actions).shape[-1])
+        std_param, squash, fixed = pinit.policy_mode_fixed(pk, A) if policy_fixed else (*pinit.policy_mode(pk), None)
         # mlp_shapes=True: each network's own depth and per-layer widths (mlp.py:19-31); else the one width of [h, h], as always
         dims = pinit.mlp_layer_dims(critic_network_kwargs, policy_network_kwargs, mlp_plain) if mlp_shapes else None
         hidden = dims[0][0] if mlp_shapes else pinit.mlp_hidden_width(critic_network_kwargs, policy_network_kwargs, mlp_plain)
@@ -224,9 +235,11 @@ class DrQAgent:
             if dims[0] == dims[1] and len(dims[0]) == 2 and dims[0][0] == dims[0][1]:
                 dims = None    # [h, h] twice: the very agent the call without the switch makes
         pinit.check_plain_dropout(*lns, critic_drop, policy_drop)
+        pinit.check_fixed_dropout(fixed, critic_drop, policy_drop)
         shape_kw = {} if dims is None else {"critic_dims": dims[0], "policy_dims": dims[1]}
         if lns != (True, True):    # (True, True): the very agent the call without the switch makes
             shape_kw.update(critic_layer_norm=lns[0], policy_layer_norm=lns[1])
+        core_kw = {} if fixed is None else {"fixed_std": fixed}
         seed = int(np.asarray(rng).reshape(-1)[-1]) if not isinstance(rng, int) else rng
         image_keys = tuple(image_keys)
         img = np.asarray(observations[image_keys[0]])
@@ -243,7 +256,6 @@ class DrQAgent:
                     "(common/encoding.py:39-44) and the pretrained ResNet-10's conv_init kernel (7,7,3,64) takes 3; "
                     "use encoder_type='small'")
         S = int(st0.shape[-1]) * T      # the proprio Dense's input: "B T S -> B (T S)" (common/encoding.py:58-64)
-        A = int(np.asarray(actions).shape[-1])
         if target_entropy is None:
             target_entropy = -A / 2  # drq.py:88-89
         # drq.py:35-43: each optimizer = make_optimizer(learning_rate=3e-4) unless overridden (optimizers.py:6-13)
@@ -258,7 +270,7 @@ class DrQAgent:
                          critic_subsample_size=critic_subsample_size, backup_entropy=backup_entropy, num_stack=T,
                          hidden=hidden, std_parameterization=std_param, tanh_squash_distribution=squash,
                          critic_activation=critic_act, policy_activation=policy_act,
-                         critic_dropout=critic_drop, policy_dropout=policy_drop, **shape_kw)
+                         critic_dropout=critic_drop, policy_dropout=policy_drop, **shape_kw, **core_kw)
         if init_ref.check_param_init(param_init):
             theta = init_ref.theta_reference(image_keys, H, W, S, A, rng, ensemble=critic_ensemble_size, encoder_type=encoder_type,
                                              temperature_init=temperature_init, device=device, num_stack=T, hidden=hidden,
@@ -276,6 +288,7 @@ class DrQAgent:
                       target_entropy=target_entropy, backup_entropy=backup_entropy, image_keys=image_keys,
                       critic_activation=critic_act, policy_activation=policy_act,
                       critic_dropout_rate=critic_drop, policy_dropout_rate=policy_drop,
+                      **({} if fixed is None else {"fixed_std": tuple(float(x) for x in fixed)}),
                       **({} if lns == (True, True) else {"critic_use_layer_norm": lns[0], "policy_use_layer_norm": lns[1]}))
         agent = cls(core, image_keys, config, seed)
         agent._opts = {k: {"warmup_steps": 0, **v} for k, v in opts.items()}

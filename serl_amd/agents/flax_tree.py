@@ -132,7 +132,10 @@ def _trunk_paths():
 
 def _policy_std_paths(std_parameterization):
     """the leaves behind the policy's mean head: Dense_1, or Policy's own `log_stds` parameter with "uniform"
-    (actor_critic_nets.py:199-201: self.param("log_stds", zeros, (action_dim,)))"""
+    (actor_critic_nets.py:199-201: self.param("log_stds", zeros, (action_dim,))); nothing with "fixed" (:190-192: fixed_std is a
+    constant of the module, modules_actor holds the encoder, the MLP and Dense_0 alone)"""
+    if std_parameterization == "fixed":
+        return {}
     if std_parameterization == "uniform":
         return {"actor/log_stds": [("modules_actor", "log_stds")]}
     return {"actor/logstd/kernel": [("modules_actor", "Dense_1", "kernel")], "actor/logstd/bias": [("modules_actor", "Dense_1", "bias")]}

@@ -34,7 +34,7 @@ class SACAgent(DrQAgent):
                       actor_optimizer_kwargs: dict = None, critic_optimizer_kwargs: dict = None,
                       temperature_optimizer_kwargs: dict = None, batch_size: int = 256, device: int = 0, param_init: str = "numpy",
                       mlp_dropout: bool = False, mlp_shapes: bool = False, mlp_plain: bool = False,
-                      **kwargs):
+                      policy_fixed: bool = False, **kwargs):
         """sac.py:486-542 -> create (:323-400).  Built natively: the configuration of utils/launcher.py:50-76
         (REDQ subsample 2, tanh-squashed exp-parameterised policy, LayerNorm+tanh 256x256 MLPs); hidden_dims=[h, h] in both
         network kwargs selects another width h, a multiple of 64 in [64, 1024], and activations "tanh" (when absent), "relu" or
@@ -45,9 +45,13 @@ class SACAgent(DrQAgent):
         critic's list independent of the policy's (utils.init.mlp_layer_dims; create_drq's docstring).
         mlp_plain=True reads each network's own use_layer_norm (absent: True): a network with False has no LayerNorm in its MLP
         (utils.init.mlp_layer_norms; create_drq's docstring).
+        policy_fixed=True also reads std_parameterization="fixed" with fixed_std, a scalar or action_dim numbers -- how the
+        reference writes TD3 (utils.init.policy_mode_fixed; create_drq's docstring).
         param_init: "numpy" (default) or "reference" (the reference's own initialisers and keys, utils/init_ref.py)."""
         pk = policy_kwargs or {}
-        std_param, squash = pinit.policy_mode(pk)
+        # policy_fixed=True: "fixed" / fixed_std are read (actor_critic_nets.py:189-192); else refused, as always
+        A = int(np.asarray(actions).shape[-1])
+        std_param, squash, fixed = pinit.policy_mode_fixed(pk, A) if policy_fixed else (*pinit.policy_mode(pk), None)
         # mlp_shapes=True: each network's own depth and per-layer widths (mlp.py:19-31); else the one width of [h, h], as always
         dims = pinit.mlp_layer_dims(critic_network_kwargs, policy_network_kwargs, mlp_plain) if mlp_shapes else None
         hidden = dims[0][0] if mlp_shapes else pinit.mlp_hidden_width(critic_network_kwargs, policy_network_kwargs, mlp_plain)
@@ -60,15 +64,16 @@ class SACAgent(DrQAgent):
             if dims[0] == dims[1] and len(dims[0]) == 2 and dims[0][0] == dims[0][1]:
                 dims = None    # [h, h] twice: the very agent the call without the switch makes
         pinit.check_plain_dropout(*lns, critic_drop, policy_drop)
+        pinit.check_fixed_dropout(fixed, critic_drop, policy_drop)
         shape_kw = {} if dims is None else {"critic_dims": dims[0], "policy_dims": dims[1]}
         if lns != (True, True):    # (True, True): the very agent the call without the switch makes
             shape_kw.update(critic_layer_norm=lns[0], policy_layer_norm=lns[1])
+        core_kw = {} if fixed is None else {"fixed_std": fixed}
         ao = {"learning_rate": 3e-4, "warmup_steps": 2000, **(actor_optimizer_kwargs or {})}     # sac.py:333-336
         co = {"learning_rate": 3e-4, "warmup_steps": 2000, **(critic_optimizer_kwargs or {})}    # sac.py:337-340
         to = {"learning_rate": 3e-4, **(temperature_optimizer_kwargs or {})}                     # sac.py:341-343
         seed = int(np.asarray(rng).reshape(-1)[-1]) if not isinstance(rng, int) else rng
         S = int(np.asarray(observations).shape[-1])
-        A = int(np.asarray(actions).shape[-1])
         if target_entropy is None:
             target_entropy = -A / 2   # sac.py:387-388
         core = AgentCore(device=device, n_cam=0, H=0, W=0, state_dim=S, act_dim=A, batch=batch_size,
@@ -80,7 +85,7 @@ class SACAgent(DrQAgent):
                          critic_subsample_size=critic_subsample_size, backup_entropy=backup_entropy, hidden=hidden,
                          std_parameterization=std_param, tanh_squash_distribution=squash,
                          critic_activation=critic_act, policy_activation=policy_act,
-                         critic_dropout=critic_drop, policy_dropout=policy_drop, **shape_kw)
+                         critic_dropout=critic_drop, policy_dropout=policy_drop, **shape_kw, **core_kw)
         if init_ref.check_param_init(param_init):
             theta = init_ref.theta_reference((), 0, 0, S, A, rng, ensemble=critic_ensemble_size, temperature_init=temperature_init,
                                              device=device, hidden=hidden, std_parameterization=std_param, **shape_kw)
@@ -94,6 +99,7 @@ class SACAgent(DrQAgent):
                       target_entropy=target_entropy, backup_entropy=backup_entropy,
                       critic_activation=critic_act, policy_activation=policy_act,
                       critic_dropout_rate=critic_drop, policy_dropout_rate=policy_drop,
+                      **({} if fixed is None else {"fixed_std": tuple(float(x) for x in fixed)}),
                       **({} if lns == (True, True) else {"critic_use_layer_norm": lns[0], "policy_use_layer_norm": lns[1]}))
         agent = cls(core, (), config, seed)
         agent._opts = {"actor": ao, "critic": co, "temperature": {"warmup_steps": 0, **to}}

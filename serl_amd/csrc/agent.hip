@@ -34,7 +34,7 @@ struct Offs {
   DenseLn c[kL], a[kL];    // ... and the nc layers of the critic's MLP, the na layers of the policy's (mlp.py:19-31), input side first
   int nc, na;
   long c_hw, c_hb;
-  long a_Wm, a_bm, a_Ws, a_bs;   // kPolUniform: a_bs = actor/log_stds, no a_Ws
+  long a_Wm, a_bm, a_Ws, a_bs;   // kPolUniform: a_bs = actor/log_stds, no a_Ws; kPolFixed: neither (both -1)
   long lam;
   long P, Pc, Pa0, Pa1;
 };
@@ -81,7 +81,11 @@ struct serl_agent {
   bool small = false;                // encoder_type == "small": trainable SmallEncoder instead of the frozen trunk
   int std_param = SERL_STD_EXP, no_tanh = 0;   // the arguments of serl_agent_create_policy
   int pol_mode = kPolExp;            // ... as the head kernels take them
-  int head_groups = 2;               // Dense layers of the policy head: (mean, log_std), or the mean alone with kPolUniform
+  int head_groups = 2;               // Dense layers of the policy head: (mean, log_std), or the mean alone with kPolUniform / kPolFixed
+  // serl_agent_create_fixed_std: the constant std vector of a kPolFixed agent as it was passed, [act_dim]; the device copy is an
+  // allocation of its own outside the arena (no leaf, no moments, no target copy, never all-reduced).  Empty / nullptr otherwise.
+  std::vector<float> fixed_std;
+  float* fixed_std_dev = nullptr;
   int critic_act = kActTanh, policy_act = kActTanh;   // serl_agent_create_mlp: the activation of each MLP's LayerNorm rows (kAct*)
   // serl_agent_create_shapes: the hidden widths of the critic's and the policy's MLP; {cfg.hidden, cfg.hidden} twice from every
   // other entry point.  Nothing below reads cfg.hidden.
@@ -250,8 +254,10 @@ void build_layout(serl_agent* a) {
   o.a_Wm = add_leaf(L, off, "actor/mean/kernel", Hp * A);
   o.a_bm = add_leaf(L, off, "actor/mean/bias", A);
   a->pol_mode = a->std_param | (a->no_tanh ? kPolNoTanh : 0);
-  a->head_groups = a->std_param == SERL_STD_UNIFORM ? 1 : 2;
-  if (a->head_groups == 1) {   // one log-std vector shared by all rows (actor_critic_nets.py:199-201), directly behind the mean's bias
+  a->head_groups = (a->std_param == SERL_STD_UNIFORM || a->std_param == SERL_STD_FIXED) ? 1 : 2;
+  if (a->std_param == SERL_STD_FIXED) {   // no std parameter at all (actor_critic_nets.py:190-192): the head ends with the mean's bias
+    o.a_Ws = o.a_bs = -1;
+  } else if (a->head_groups == 1) {   // one log-std vector shared by all rows (actor_critic_nets.py:199-201), directly behind the mean's bias
     o.a_Ws = -1;
     o.a_bs = add_leaf(L, off, "actor/log_stds", A);
   } else {
@@ -544,6 +550,11 @@ int policy_mlp_multi(serl_agent* a, const PolJob* jobs, int n, int cnt, hipStrea
   }
   return SERL_OK;
 }
+// The distance between the groups of the policy head's GEMMs (mean -> log_std, bias to bias); unused with one group, where it is
+// A: the distance from the mean's bias to log_stds when there is such a leaf
+inline long head_stride(const serl_agent* a) { return a->o.a_bs >= 0 ? a->o.a_bs - a->o.a_bm : a->cfg.act_dim; }
+// What the head kernels read as `bias_ls` in the parameter vector P: the log-std bias, log_stds, or the agent's fixed_std
+inline const float* head_bias_ls(const serl_agent* a, const float* P) { return a->o.a_bs >= 0 ? P + a->o.a_bs : a->fixed_std_dev; }
 int policy_fwd_multi(serl_agent* a, const PolJob* jobs, int n, int cnt, hipStream_t st) {
   const serl_agent_cfg& c = a->cfg;
   const Offs& o = a->o;
@@ -557,10 +568,10 @@ int policy_fwd_multi(serl_agent* a, const PolJob* jobs, int n, int cnt, hipStrea
     PolBuf& pb = *j.pb;
     // The head is no Dense -> LayerNorm layer (no LayerNorm): (mean, log_std) as two groups of one GEMM, the mean alone when log_stds is
     // a parameter vector (the stride is then unused)
-    gd[i] = gemm_fwd(pb.m.l[o.na - 1].h, Hd, 0, P + o.a_Wm, o.a_bs - o.a_bm, a->slabs_lane[i], a->head_groups, cnt, A, Hd, 4);
+    gd[i] = gemm_fwd(pb.m.l[o.na - 1].h, Hd, 0, P + o.a_Wm, head_stride(a), a->slabs_lane[i], a->head_groups, cnt, A, Hd, 4);
     pv[i] = PolicyDistArgs{};
     pv[i].mode = a->pol_mode;
-    pv[i].slabs = a->slabs_lane[i]; pv[i].S = 4; pv[i].bias_mean = P + o.a_bm; pv[i].bias_ls = P + o.a_bs; pv[i].pre = pb.pre;
+    pv[i].slabs = a->slabs_lane[i]; pv[i].S = 4; pv[i].bias_mean = P + o.a_bm; pv[i].bias_ls = head_bias_ls(a, P); pv[i].pre = pb.pre;
     pv[i].eps = j.eps; pv[i].act = j.act_out; pv[i].ld_act = j.ld_act; pv[i].logp = pb.logp; pv[i].std_out = pb.std;
     pv[i].sum_logp = j.sum_logp; pv[i].lam = P + o.lam; pv[i].alpha_out = j.alpha_out;
   }
@@ -712,12 +723,13 @@ int critic_loss_or_rider(serl_agent* a, const LossArgs& L, hipStream_t st, const
 // Gradient of the policy's head biases (mean, log_std): the column sums of dpre.  Fused: a job of the phase's deferred
 // column-sum launch.  Else: a colsum launch.
 // (kPolUniform: the second slab of dpre is the per-row gradient of the shared log_stds, whose leaf sits out_gstride = A behind
-// the mean's bias: the same two column sums.)
+// the mean's bias: the same two column sums.  kPolFixed: dpre has no second slab and the std no leaf: the mean's sum alone.)
 int head_bias_grad(serl_agent* a, int cnt, float* out, long out_gstride, hipStream_t st) {
   const int A = a->cfg.act_dim;
-  if (!a->fuse) return colsum(a->dpre, nullptr, 2, cnt, A, out, out_gstride, false, st);
+  const int groups = a->std_param == SERL_STD_FIXED ? 1 : 2;
+  if (!a->fuse) return colsum(a->dpre, nullptr, groups, cnt, A, out, out_gstride, false, st);
   SERL_REQUIRE(a->pg_ncs < kMaxColsum, "no room for the head-bias gradient job");
-  a->pg_cs[a->pg_ncs++] = Colsum3Args{a->dpre, nullptr, nullptr, 2, cnt, A, nullptr, out, nullptr, out_gstride, 1};
+  a->pg_cs[a->pg_ncs++] = Colsum3Args{a->dpre, nullptr, nullptr, groups, cnt, A, nullptr, out, nullptr, out_gstride, 1};
   return SERL_OK;
 }
 
@@ -943,7 +955,8 @@ int serl_agent_create_mlp(const serl_agent_cfg* cfg, int std_param, int no_tanh,
 
 static int create_agent(const serl_agent_cfg* cfg, int std_param, int no_tanh, int critic_act, int policy_act, double critic_dropout,
                         double policy_dropout, const int* critic_dims, int n_critic, const int* policy_dims, int n_policy, bool shapes,
-                        int critic_layer_norm, int policy_layer_norm, serl_agent** out);
+                        int critic_layer_norm, int policy_layer_norm, serl_agent** out, const float* fixed_std = nullptr,
+                        bool fixed_abi = false);
 
 // mlp.py:19-31: MLP loops over hidden_dims of any length; sac.py:516-524, drq.py:188-207: the critic and the policy are built
 // from separate kwargs, so the two lists are independent.  The heads follow the last width of their network.
@@ -967,6 +980,26 @@ int serl_agent_create_layer_norm(const serl_agent_cfg* cfg, int std_param, int n
 }
 
 // mlp.py:29-30: whether the layers of an agent's critic (network 0) or policy (1) MLP have their LayerNorm
+// actor_critic_nets.py:189-192,212: `fixed_std` -- stds = clip(fixed_std, std_min, std_max), no Dense_1 and no log_stds.
+// serl_agent_create_layer_norm is this function with NULL (its own range check keeps refusing SERL_STD_FIXED).
+int serl_agent_create_fixed_std(const serl_agent_cfg* cfg, int std_param, int no_tanh, int critic_act, int policy_act,
+                                const int* critic_dims, int n_critic, const int* policy_dims, int n_policy, int critic_layer_norm,
+                                int policy_layer_norm, const float* fixed_std, serl_agent** out) {
+  SERL_REQUIRE(cfg && out, "NULL argument");
+  SERL_REQUIRE(critic_dims && policy_dims, "%s is NULL: the hidden widths of the %s's MLP, 1 to %d of them",
+               critic_dims ? "policy_dims" : "critic_dims", critic_dims ? "policy" : "critic", SERL_MAX_MLP_LAYERS);
+  return create_agent(cfg, std_param, no_tanh, critic_act, policy_act, 0.0, 0.0, critic_dims, n_critic, policy_dims, n_policy, true,
+                      critic_layer_norm, policy_layer_norm, out, fixed_std, true);
+}
+
+// the vector serl_agent_create_fixed_std was given (before the clip)
+int serl_agent_fixed_std(serl_agent* a, float* out) {
+  SERL_REQUIRE(a && out, "NULL argument");
+  SERL_REQUIRE(a->std_param == SERL_STD_FIXED, "the agent's std parameterisation is %d, not SERL_STD_FIXED (3): it has no fixed_std", a->std_param);
+  for (size_t j = 0; j < a->fixed_std.size(); ++j) out[j] = a->fixed_std[j];
+  return SERL_OK;
+}
+
 int serl_agent_mlp_layer_norm(serl_agent* a, int network) {
   if (!a || (network != 0 && network != 1)) return -1;
   return (network ? a->policy_ln : a->critic_ln) ? 1 : 0;
@@ -993,7 +1026,7 @@ int serl_agent_create_dropout(const serl_agent_cfg* cfg, int std_param, int no_t
 // they repeat cfg->hidden, which is checked as it always was.
 static int create_agent(const serl_agent_cfg* cfg, int std_param, int no_tanh, int critic_act, int policy_act, double critic_dropout,
                         double policy_dropout, const int* critic_dims, int n_critic, const int* policy_dims, int n_policy, bool shapes,
-                        int critic_layer_norm, int policy_layer_norm, serl_agent** out) {
+                        int critic_layer_norm, int policy_layer_norm, serl_agent** out, const float* fixed_std, bool fixed_abi) {
   SERL_REQUIRE(critic_layer_norm == 0 || critic_layer_norm == 1, "critic_layer_norm %d is not 0 (no LayerNorm) or 1", critic_layer_norm);
   SERL_REQUIRE(policy_layer_norm == 0 || policy_layer_norm == 1, "policy_layer_norm %d is not 0 (no LayerNorm) or 1", policy_layer_norm);
   SERL_REQUIRE((critic_layer_norm || !(critic_dropout > 0.0)) && (policy_layer_norm || !(policy_dropout > 0.0)),
@@ -1033,8 +1066,17 @@ static int create_agent(const serl_agent_cfg* cfg, int std_param, int no_tanh, i
     return SERL_ERR_UNSUPPORTED;
   }
   SERL_REQUIRE(num_stack == 1 || cfg->n_cam > 0, "num_stack %d on a state-only agent: its state path has no stacking wrapper", num_stack);
-  SERL_REQUIRE(std_param >= SERL_STD_EXP && std_param <= SERL_STD_UNIFORM,
-               "std_param %d is not SERL_STD_EXP (0), SERL_STD_SOFTPLUS (1) or SERL_STD_UNIFORM (2)", std_param);
+  if (!fixed_abi) {
+    SERL_REQUIRE(std_param >= SERL_STD_EXP && std_param <= SERL_STD_UNIFORM,
+                 "std_param %d is not SERL_STD_EXP (0), SERL_STD_SOFTPLUS (1) or SERL_STD_UNIFORM (2)", std_param);
+  } else {
+    SERL_REQUIRE(std_param >= SERL_STD_EXP && std_param <= SERL_STD_FIXED,
+                 "std_param %d is not SERL_STD_EXP (0), SERL_STD_SOFTPLUS (1), SERL_STD_UNIFORM (2) or SERL_STD_FIXED (3)", std_param);
+    SERL_REQUIRE(std_param != SERL_STD_FIXED || fixed_std, "std_param SERL_STD_FIXED (3) needs fixed_std: act_dim floats, got NULL");
+    SERL_REQUIRE(std_param == SERL_STD_FIXED || !fixed_std, "fixed_std is given with std_param %d: it goes with SERL_STD_FIXED (3) alone", std_param);
+    for (int j = 0; fixed_std && j < cfg->act_dim; ++j)
+      SERL_REQUIRE(std::isfinite(fixed_std[j]) && fixed_std[j] > 0.f, "fixed_std[%d] = %g is not a finite positive number", j, (double)fixed_std[j]);
+  }
   SERL_REQUIRE(no_tanh == 0 || no_tanh == 1, "no_tanh %d is not 0 (tanh-squashed) or 1 (plain Gaussian)", no_tanh);
   SERL_REQUIRE(critic_act >= 0 && critic_act < kActCount, "critic_act %d: served are SERL_ACT_TANH (0), SERL_ACT_RELU (1) and SERL_ACT_SWISH (2)", critic_act);
   SERL_REQUIRE(policy_act >= 0 && policy_act < kActCount, "policy_act %d: served are SERL_ACT_TANH (0), SERL_ACT_RELU (1) and SERL_ACT_SWISH (2)", policy_act);
@@ -1068,6 +1110,18 @@ static int create_agent(const serl_agent_cfg* cfg, int std_param, int no_tanh, i
     return rc;
   }
   carve(a, a->arena);
+  if (fixed_std) {   // a constant of the agent, outside the arena: nothing that walks the parameters meets it
+    a->fixed_std.assign(fixed_std, fixed_std + cfg->act_dim);
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&a->fixed_std_dev), sizeof(float) * cfg->act_dim);
+    if (e == hipSuccess) e = hipMemcpy(a->fixed_std_dev, fixed_std, sizeof(float) * cfg->act_dim, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+      set_error("fixed_std: %s", hipGetErrorString(e));
+      if (a->fixed_std_dev) (void)hipFree(a->fixed_std_dev);
+      (void)hipFree(a->arena);
+      delete a;
+      return SERL_ERR_HIP;
+    }
+  }
   if (!a->state_only && !a->small) a->tw = trunk_weights(a->trunk, a->to);
   if (a->live) a->tw_t = trunk_weights(a->trunk_t, a->to);
   *out = a;
@@ -1085,6 +1139,7 @@ int serl_agent_destroy(serl_agent* a) {
   (void)hipSetDevice(a->cfg.device);
   (void)hipDeviceSynchronize();
   if (a->arena) (void)hipFree(a->arena);
+  if (a->fixed_std_dev) (void)hipFree(a->fixed_std_dev);
   delete a;
   return SERL_OK;
 }
@@ -1590,8 +1645,9 @@ int serl_agent_actor_grads(serl_agent* a, int global_count, const serl_noise* no
                      1.0f / (float)global_count, cnt, A, c.std_min, c.std_max, a->dpre, a->crit.q, c.ensemble,
                      a->SC + S_QPI, st, a->pol_mode));
   // policy heads (mean, log_std): two groups with uniform stride; parameter gradients off the critical chain.  kPolUniform: one
-  // group, and hs = A is the distance from the mean's bias to log_stds
-  const long hs = o.a_bs - o.a_bm;
+  // group, and hs = A is the distance from the mean's bias to log_stds.  kPolFixed: one group and no std leaf -- dpre is the
+  // mean's slab alone, so neither the second group's weight gradient nor the log_stds column sum exists
+  const long hs = head_stride(a);
   const int hg = a->head_groups;
   float* Ga = a->Ga - o.Pa0;   // Ga[o] = gradient of the actor-tx leaf at parameter offset o
   const float* P = a->theta;
@@ -1852,12 +1908,12 @@ int serl_agent_eval_policy(serl_agent* a, const uint8_t* dev_frames, const float
   pj.P = P; pj.pb = &pb; pj.enc = a->encP.enc; pj.ld_enc = a->encP.ld;
   RC(policy_mlp_multi(a, &pj, 1, n, st));
   const int Hd = o.a[o.na - 1].N;
-  const GemmDesc g = gemm_fwd(pb.m.l[o.na - 1].h, Hd, 0, P + o.a_Wm, o.a_bs - o.a_bm, a->slabs_lane[0], a->head_groups, n, c.act_dim,
+  const GemmDesc g = gemm_fwd(pb.m.l[o.na - 1].h, Hd, 0, P + o.a_Wm, head_stride(a), a->slabs_lane[0], a->head_groups, n, c.act_dim,
                               Hd, 4);
   SERL_REQUIRE((long)a->head_groups * 4 * n * c.act_dim <= a->slabs_cap, "policy head exceeds the slab scratch");
   RC(gemm_f32_multi(&g, 1, st));
   PolicyStatsArgs v{};
-  v.slabs = a->slabs_lane[0]; v.S = 4; v.bias_mean = P + o.a_bm; v.bias_ls = P + o.a_bs; v.act = dev_actions;
+  v.slabs = a->slabs_lane[0]; v.S = 4; v.bias_mean = P + o.a_bm; v.bias_ls = head_bias_ls(a, P); v.act = dev_actions;
   v.mean = dev_mean_out; v.std = dev_std_out; v.mode_out = dev_mode_out; v.logp = dev_logp_out;
   v.rows = n; v.A = c.act_dim; v.std_min = c.std_min; v.std_max = c.std_max; v.mode = a->pol_mode;
   return policy_stats(v, st);

@@ -106,7 +106,8 @@ int policy_dist_fwd_multi(const PolicyDistArgs* v, int n, int B, int A, float st
 // sample: loc, scale_diag, mode and -- with `act` [rows][A] -- log pi(act | s) (sac.py:71-91).  Any output may be nullptr; logp
 // needs act.  A row with an action component |a| >= 1 under the tanh squash gets a non-finite logp (not clamped).
 struct PolicyStatsArgs {
-  const float* slabs; int S;   // [mean | log_std][S K-splits][rows][A]; kPolUniform: [mean] alone, bias_ls = log_stds
+  const float* slabs; int S;   // [mean | log_std][S K-splits][rows][A]; kPolUniform: [mean] alone, bias_ls = log_stds;
+                               // kPolFixed: [mean] alone, bias_ls = fixed_std
   const float *bias_mean, *bias_ls, *act;
   float *mean, *std, *mode_out, *logp;   // [rows][A] x 3, [rows]
   int rows, A; float std_min, std_max;

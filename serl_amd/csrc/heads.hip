@@ -391,10 +391,24 @@ template <int MODE>
 __device__ __forceinline__ float policy_std_raw(float ls) {
   return (MODE & kPolStdMask) == kPolSoftplus ? softplusf(ls) : expf(ls);
 }
+// kPolFixed (actor_critic_nets.py:190-192,212): the head owns no std parameter.  What the other modes call `ls` is then the
+// agent's constant fixed_std vector itself, std = clip(fixed_std[j], std_min, std_max) in float32, policy_std_raw has no meaning,
+// the head GEMM has one group and the second half of `pre` is neither written nor read.
+template <int MODE>
+__device__ __forceinline__ constexpr bool policy_fixed() { return (MODE & kPolStdMask) == kPolFixed; }
+// whether the head GEMM has the log-std group behind the mean's
+template <int MODE>
+__device__ __forceinline__ constexpr bool policy_ls_group() { return (MODE & kPolStdMask) != kPolUniform && !policy_fixed<MODE>(); }
+// std of one element from `ls` (the log-std, the softplus argument, or with kPolFixed the fixed std)
+template <int MODE>
+__device__ __forceinline__ float policy_std(float ls, float std_min, float std_max) {
+  if (policy_fixed<MODE>()) return fminf(fmaxf(ls, std_min), std_max);
+  return fminf(fmaxf(policy_std_raw<MODE>(ls), std_min), std_max);
+}
 
 // Gaussian head of rows [r0, r1) from the head GEMM's slabs (actor_critic_nets.py:179-272): one thread per (row, action).
 // MODE (internal.h, kPol*): the std parameterisation, and whether the sample goes through tanh.  kPolUniform: the head GEMM has
-// no log-std group -- `ls` is the shared log_stds vector (bias_ls) alone and no second slab is read.
+// no log-std group -- `ls` is the shared log_stds vector (bias_ls) alone and no second slab is read.  kPolFixed: see policy_fixed.
 template <bool LIVE, int MODE>
 __device__ __forceinline__ void policy_dist_rows(const PolicyDistArgs& v, int r0, int r1, int tid, int nthreads) {
   const int A = v.A, B = v.B;
@@ -405,7 +419,7 @@ __device__ __forceinline__ void policy_dist_rows(const PolicyDistArgs& v, int r0
     for (int sp = 0; sp < v.S; ++sp) {   // K-split slabs of the head GEMM: [mean | log_std][split][rows][ld]
       const long o0 = (long)sp * v.slab_stride + (long)b * v.slab_ld + j, o1 = o0 + (long)v.S * v.slab_stride;
       mean += LIVE ? ld1_sc1(rs, o0) : v.slabs[o0];
-      if ((MODE & kPolStdMask) != kPolUniform) ls += LIVE ? ld1_sc1(rs, o1) : v.slabs[o1];
+      if (policy_ls_group<MODE>()) ls += LIVE ? ld1_sc1(rs, o1) : v.slabs[o1];
     }
     float ep;
     if (v.eps) ep = v.eps[(long)b * A + j];
@@ -416,8 +430,8 @@ __device__ __forceinline__ void policy_dist_rows(const PolicyDistArgs& v, int r0
       v.eps_out[(long)b * A + j] = ep;
     }
     v.pre[(long)b * A + j] = mean;
-    v.pre[((long)B + b) * A + j] = ls;
-    const float sd = fminf(fmaxf(policy_std_raw<MODE>(ls), v.std_min), v.std_max);
+    if (!policy_fixed<MODE>()) v.pre[((long)B + b) * A + j] = ls;
+    const float sd = policy_std<MODE>(ls, v.std_min, v.std_max);
     const float u = mean + sd * ep;
     v.act[(long)b * v.ld_act + j] = (MODE & kPolNoTanh) ? u : tanhf(u);
     v.std_out[(long)b * A + j] = sd;
@@ -448,15 +462,20 @@ __device__ __forceinline__ void policy_tile(const PolicyDistArgs& v, int r0, int
   __syncthreads();   // (this workgroup's own global writes of pre / std / eps, read back below)
   policy_logp_rows<MODE>(v, r0, r1, tid, 256);
 }
-// X(MODE) for the compile-time constant equal to `mode`; `bad` for a value that is no mode
-#define SERL_POLICY_MODE_SWITCH(mode, X, bad)                                  \
-  switch (mode) {                                                              \
+// X(MODE) for the compile-time constant equal to `mode`; `bad` for a value that is no mode.  SERL_POLICY_PARAM_CASES: the six modes
+// whose std has a parameter; SERL_POLICY_MODE_SWITCH: those and the two kPolFixed ones.
+#define SERL_POLICY_PARAM_CASES(X)                                             \
     case kPolExp: X(kPolExp); break;                                           \
     case kPolSoftplus: X(kPolSoftplus); break;                                 \
     case kPolUniform: X(kPolUniform); break;                                   \
     case kPolExp | kPolNoTanh: X(kPolExp | kPolNoTanh); break;                 \
     case kPolSoftplus | kPolNoTanh: X(kPolSoftplus | kPolNoTanh); break;       \
-    case kPolUniform | kPolNoTanh: X(kPolUniform | kPolNoTanh); break;         \
+    case kPolUniform | kPolNoTanh: X(kPolUniform | kPolNoTanh); break;
+#define SERL_POLICY_MODE_SWITCH(mode, X, bad)                                  \
+  switch (mode) {                                                              \
+    SERL_POLICY_PARAM_CASES(X)                                                 \
+    case kPolFixed: X(kPolFixed); break;                                       \
+    case kPolFixed | kPolNoTanh: X(kPolFixed | kPolNoTanh); break;             \
     default: bad;                                                              \
   }
 
@@ -1755,7 +1774,8 @@ int critic_loss(const float* qt, const float* q, const float* reward, const floa
 //   std = clip(exp(log_std), std_min, std_max); u = mean + std*eps; a = tanh(u)
 //   logp = sum_j(-eps^2/2 - log std - log(2pi)/2) - sum_j 2(log2 - u - softplus(-2u))
 // pre: [2][B][A] (mean slab, log_std slab; biases already added).  MODE: see policy_dist_rows (kPolSoftplus: std from
-// softplus; kPolUniform: log_std = bias_ls for every row, one slab group; kPolNoTanh: a = u and no second sum)
+// softplus; kPolUniform: log_std = bias_ls for every row, one slab group; kPolFixed: std = clip(bias_ls), one slab group, pre is
+// [1][B][A]; kPolNoTanh: a = u and no second sum)
 // =============================================================================================
 template <int MODE>
 __global__ void policy_dist_fwd_kernel(Multi<PolicyDistArgs> mv, int B, int A, float std_min, float std_max) {
@@ -1768,12 +1788,12 @@ __global__ void policy_dist_fwd_kernel(Multi<PolicyDistArgs> mv, int B, int A, f
       float mean = v.bias_mean[j], ls = v.bias_ls[j];
       for (int sp = 0; sp < v.S; ++sp) {  // K-split slabs of the head GEMM: [mean | log_std][split][B][A]
         mean += v.slabs[((long)sp * B + b) * A + j];
-        if ((MODE & kPolStdMask) != kPolUniform) ls += v.slabs[(((long)v.S + sp) * B + b) * A + j];
+        if (policy_ls_group<MODE>()) ls += v.slabs[(((long)v.S + sp) * B + b) * A + j];
       }
       const float e = v.eps[(long)b * A + j];
       v.pre[(long)b * A + j] = mean;
-      v.pre[((long)B + b) * A + j] = ls;
-      const float sd = fminf(fmaxf(policy_std_raw<MODE>(ls), std_min), std_max);
+      if (!policy_fixed<MODE>()) v.pre[((long)B + b) * A + j] = ls;
+      const float sd = policy_std<MODE>(ls, std_min, std_max);
       const float u = mean + sd * e;
       v.act[(long)b * v.ld_act + j] = (MODE & kPolNoTanh) ? u : tanhf(u);
       v.std_out[(long)b * A + j] = sd;
@@ -1854,12 +1874,50 @@ __global__ __launch_bounds__(256) void policy_stats_kernel(PolicyStatsArgs v) {
   }
   if (v.logp && lane == 0) v.logp[row] = lp;
 }
+// kPolFixed: the same row with std = clip(fixed_std[j]) -- bias_ls is the agent's fixed_std vector, read like the biases (a lane past A
+// reads column 0) and before any store; one slab group, no exp.  Kernels of their own: the six above keep their text.
+template <bool NOTANH>
+__global__ __launch_bounds__(256) void policy_stats_fixed_kernel(PolicyStatsArgs v) {
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (row >= v.rows) return;   // (uniform over the wave)
+  const int A = v.A;
+  const bool live = lane < A;
+  const int j = live ? lane : 0;
+  const long e = (long)row * A + j;
+  float mean = v.bias_mean[j];
+  const float fixed = v.bias_ls[j];
+  const float a = v.act ? v.act[e] : 0.f;
+  for (int sp = 0; sp < v.S; ++sp) mean += v.slabs[((long)sp * v.rows) * A + e];   // K-split slabs of the mean's group, in index order
+  const float sd = policy_std<kPolFixed>(fixed, v.std_min, v.std_max);
+  float lp = 0.f;
+  if (v.logp) {   // (uniform: a launch argument)
+    float u = a;
+    if (!NOTANH) u = 0.5f * (log1pf(a) - log1pf(-a));
+    const float z = (u - mean) / sd;
+    lp = -0.5f * z * z - logf(sd) - 0.91893853320467274f;
+    if (!NOTANH) lp -= 2.f * (0.69314718055994531f - u - softplusf(-2.f * u));
+    lp = live ? lp : 0.f;
+    float unused = 0.f;
+    wave_sum2(lp, unused);
+  }
+  if (live) {
+    if (v.mean) v.mean[e] = mean;
+    if (v.std) v.std[e] = sd;
+    if (v.mode_out) v.mode_out[e] = NOTANH ? mean : tanhf(mean);
+  }
+  if (v.logp && lane == 0) v.logp[row] = lp;
+}
 
 int policy_stats(const PolicyStatsArgs& v, hipStream_t stream) {
   SERL_REQUIRE(v.rows >= 1 && v.A >= 1 && v.A <= 64, "policy statistics: %d rows x %d action columns (one lane per column: at most 64)", v.rows, v.A);
   SERL_REQUIRE(!v.logp || v.act, "policy statistics: a log-density needs the actions it is the density of");
 #define SERL_X(M) SERL_LAUNCH_CHAIN(policy_stats_kernel<M>, dim3(cdiv(v.rows, 4)), dim3(256), 0, stream, v)
-  SERL_POLICY_MODE_SWITCH(v.mode, SERL_X, SERL_REQUIRE(false, "bad policy distribution mode %d", v.mode))
+  switch (v.mode) {
+    SERL_POLICY_PARAM_CASES(SERL_X)
+    case kPolFixed: SERL_LAUNCH_CHAIN(policy_stats_fixed_kernel<false>, dim3(cdiv(v.rows, 4)), dim3(256), 0, stream, v); break;
+    case kPolFixed | kPolNoTanh: SERL_LAUNCH_CHAIN(policy_stats_fixed_kernel<true>, dim3(cdiv(v.rows, 4)), dim3(256), 0, stream, v); break;
+    default: SERL_REQUIRE(false, "bad policy distribution mode %d", v.mode);
+  }
 #undef SERL_X
   SERL_HIP(hipGetLastError());
   return SERL_OK;
@@ -1892,7 +1950,8 @@ int proprio_fwd_multi(const ProprioArgs* vs, int n, int S, int rows, hipStream_t
 // dpre: [2][B][A].  c_lp = dL/dlogp (device scalar *alpha times coef).
 // MODE (see policy_dist_rows): kPolNoTanh: G_u = dL/da; kPolSoftplus: dlog_std = dstd * sigmoid(ls) under the same gate on
 // softplus(ls); kPolUniform: ls is the shared log_stds vector (as the forward left it in pre) and the column sums of the second
-// slab -- the sums that make the log-std bias gradient -- are the gradient of log_stds.
+// slab -- the sums that make the log-std bias gradient -- are the gradient of log_stds.  kPolFixed: the std has no parameter:
+// dpre is [1][B][A] = G_u alone, and pre's second half, stdv and eps are not read.
 template <int MODE>
 __global__ void policy_dist_bwd_kernel(const float* da, long ld_da, const float* act, long ld_act,
                                        const float* pre, const float* stdv, const float* eps,
@@ -1923,6 +1982,10 @@ __global__ void policy_dist_bwd_kernel(const float* da, long ld_da, const float*
   if (!(MODE & kPolNoTanh)) {
     const float a = act[(long)b * ld_act + j];
     gu = gu * (1.f - a * a) + c_lp * 2.f * a;
+  }
+  if (policy_fixed<MODE>()) {
+    dpre[e] = gu;
+    return;
   }
   const float sd = stdv[e];
   const float ls = pre[((long)B + b) * A + j];

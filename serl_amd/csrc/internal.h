@@ -145,10 +145,12 @@ struct LnFwdArgs {
 enum { kActTanh = 0, kActRelu = 1, kActSwish = 2, kActCount = 3 };
 // The policy distribution of an agent (serl_agent_create_policy's std_param / no_tanh) as the head kernels take it, a template parameter:
 // the std parameterisation in the low bits, kPolNoTanh on top.  kPolExp (0) is the tanh-Gaussian with std = exp(log_std).
-enum { kPolExp = 0, kPolSoftplus = 1, kPolUniform = 2, kPolStdMask = 3, kPolNoTanh = 4 };
+// kPolFixed (serl_agent_create_fixed_std): the head has no std parameter; std = clip(fixed_std) of a constant vector.
+enum { kPolExp = 0, kPolSoftplus = 1, kPolUniform = 2, kPolFixed = 3, kPolStdMask = 3, kPolNoTanh = 4 };
 // tanh-Gaussian policy head: slabs = raw head GEMM outputs (mean, log_std); biases added here, result kept in `pre`
 struct PolicyDistArgs {
   const float* slabs; int S;  // head GEMM output [mean | log_std][S K-splits][B][A]; kPolUniform: [mean] alone, bias_ls = log_stds
+                              // kPolFixed: [mean] alone, bias_ls = the agent's fixed_std vector (the std itself, not its log)
   const float* bias_mean; const float* bias_ls; float* pre; const float* eps;
   float* act; long ld_act; float* logp; float* std_out; float* sum_logp;
   const float* lam; float* alpha_out;  // optional rider: alpha_out[0] = softplus(lam[0])

@@ -172,7 +172,21 @@ def load_state_dict(agent, sd: dict, restore_rng: bool = False):
     trunk = _trunk_paths() if (keys and etype != "small") else {}   # state-only / SmallEncoder agents have no frozen trunk
     todo = []      # (section, leaf, array): everything is sized against the agent's leaves before the first one is written
 
+    std_mode = std_parameterization_of(core)
+    std_modules = {"Dense_1": "actor/logstd", "log_stds": "actor/log_stds"}   # what Policy keeps its std in, below modules_actor
+
     def leaves_of(tree, section):
+        # std_parameterization="fixed" against a state with std leaves, either way round: said in those words, before any size
+        actor = tree.get("modules_actor") if isinstance(tree, dict) else None
+        if isinstance(actor, dict):
+            held = [m for m in std_modules if m in actor]
+            if std_mode == "fixed" and held:
+                raise ValueError(f"{section}: the state holds the policy's std leaves ('modules_actor/{held[0]}'), this agent's head has "
+                                 "a fixed std and no std leaf (std_parameterization='fixed'); nothing was loaded")
+            if std_mode != "fixed" and not held and not _absent(tree, tp["actor/mean/kernel"][0]):
+                raise ValueError(f"{section}: the state holds no std leaf of the policy (neither 'modules_actor/Dense_1' nor "
+                                 "'modules_actor/log_stds': written by a std_parameterization='fixed' agent), this agent's head has "
+                                 f"'{std_modules['log_stds' if std_mode == 'uniform' else 'Dense_1']}'; nothing was loaded")
         # a tree of another kind holds nothing at the paths of such a leaf, which the size check below reports as 0 elements ...
         for leaf in optional:
             if leaf in tp and _absent(tree, tp[leaf][0]):

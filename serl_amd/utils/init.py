@@ -230,9 +230,53 @@ def policy_mode(policy_kwargs=None):
     return std, bool(pk.get("tanh_squash_distribution", True))
 
 
+FIXED_STD = "fixed"   # serl_agent_create_fixed_std's SERL_STD_FIXED: read by policy_mode_fixed alone (policy_fixed=True)
+
+
+def policy_mode_fixed(policy_kwargs, A):
+    """What create_states / create_drq read with policy_fixed=True (without it policy_mode reads and refuses as it always did).
+    (std_parameterization, tanh_squash_distribution, fixed): std is "exp", "softplus", "uniform" or "fixed"; fixed is None, or
+    with "fixed" a float32 vector of A entries -- `fixed_std`, a scalar (how sac.py's docstring writes TD3: fixed_std=0.1)
+    broadcast to A or a sequence of A numbers.  The reference (actor_critic_nets.py:189-192,212-215) then builds neither Dense_1
+    nor log_stds and uses stds = clip(fixed_std, std_min, std_max).  Refused from the arguments alone: fixed_std beside another
+    std_parameterization (the reference asserts), "fixed" without fixed_std (ValueError, the reference's own "Invalid
+    std_parameterization"), a length other than 1 or A, an entry that is not a finite positive number."""
+    pk = policy_kwargs or {}
+    std = pk.get("std_parameterization", "exp")
+    fixed = pk.get("fixed_std")
+    if std != FIXED_STD:
+        if fixed is not None:
+            raise NotImplementedError(f"policy_kwargs['fixed_std'] with std_parameterization={std!r}: fixed_std goes with "
+                                      "std_parameterization='fixed' alone (actor_critic_nets.py:191 asserts it)")
+        return (*policy_mode(pk), None)
+    if fixed is None:
+        raise ValueError("Invalid std_parameterization: 'fixed' without policy_kwargs['fixed_std'] (actor_critic_nets.py:209-210)")
+    try:
+        v = np.asarray(fixed, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(f"policy_kwargs['fixed_std']={fixed!r} is not a number or a sequence of {A} numbers") from None
+    if v.ndim > 1 or v.size not in (1, A):
+        raise ValueError(f"policy_kwargs['fixed_std'] has shape {v.shape}: served are a scalar and a vector of action_dim = {A} entries")
+    with np.errstate(over="ignore"):     # (a double past float32's range becomes inf, and is refused below)
+        v = np.broadcast_to(v.reshape(-1), (A,)).astype(np.float32)
+    if not (np.isfinite(v).all() and (v > 0).all()):
+        raise ValueError(f"policy_kwargs['fixed_std']={fixed!r}: every entry must be a finite positive number (as float32: {v.tolist()})")
+    return FIXED_STD, bool(pk.get("tanh_squash_distribution", True)), v.copy()
+
+
+def check_fixed_dropout(fixed, critic_dropout, policy_dropout):
+    """policy_fixed=True with std_parameterization="fixed" together with a positive dropout_rate under mlp_dropout=True: not served
+    (serl_agent_create_fixed_std, the one entry point that makes a fixed-std head, takes no rates)."""
+    if fixed is not None and (critic_dropout > 0 or policy_dropout > 0):
+        raise NotImplementedError(f"std_parameterization='fixed' under policy_fixed=True with dropout_rate critic {critic_dropout!r} / "
+                                  f"policy {policy_dropout!r} under mlp_dropout=True (served: Dropout in agents whose policy head has std leaves)")
+
+
 def _policy_std_shapes(Hd, A, std_parameterization):
     """The leaves behind the policy's mean head: Dense_1 (log-std or softplus pre-activation), or with "uniform" the one
-    `log_stds` vector shared by all rows (actor_critic_nets.py:199-201)."""
+    `log_stds` vector shared by all rows (actor_critic_nets.py:199-201); none with "fixed" (:190-192: no std parameter)."""
+    if std_parameterization == FIXED_STD:
+        return {}
     if std_parameterization not in STD_PARAMETERIZATIONS:
         raise NotImplementedError(f"std_parameterization={std_parameterization!r}")
     if std_parameterization == "uniform":
@@ -247,7 +291,7 @@ def theta_shapes(n_cam, H, W, S, A, ensemble=10, hidden=256, bottleneck=256, sle
     critic_layer_norm / policy_layer_norm False: that MLP's layers own w<j> and b<j> alone (mlp.py:29-30, use_layer_norm=False).
     S: the proprio Dense's input width -- T * S for a stack of T = num_stack frames, which EncodingWrapper folds into the
     channels ("B T H W C -> B H W (T C)", common/encoding.py:39-44): the SmallEncoder's first kernel is then (3,3,3T,32).
-    std_parameterization="uniform": actor/log_stds (A,) in place of actor/logstd/{kernel,bias}."""
+    std_parameterization="uniform": actor/log_stds (A,) in place of actor/logstd/{kernel,bias}; "fixed": neither."""
     cd, pd = resolve_mlp_dims(hidden, critic_dims, policy_dims)
     if n_cam == 0:   # state-only SAC (SACAgent.create_states, sac.py:486-542): no encoder, per-member Q heads
         N = ensemble

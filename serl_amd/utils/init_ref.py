@@ -89,7 +89,8 @@ def theta_leaves(image_keys: Sequence[str], H, W, S, A, ensemble=10, encoder_typ
     hidden: the MLPs' width (hidden_dims=[hidden, hidden]), or critic_dims / policy_dims: each MLP's own widths, layer by layer
     (Dense_2 / LayerNorm_2 and up take their keys from their paths like every other leaf).  std_parameterization="uniform": the zero-initialised log_stds
     vector in place of Dense_1; every other leaf keeps its key (a flax key depends on the module's path and the scope's own
-    counter, not on its siblings), so the rest of the tree is bit-identical to the "exp" agent's.
+    counter, not on its siblings), so the rest of the tree is bit-identical to the "exp" agent's.  "fixed"
+    (actor_critic_nets.py:189-192): no std leaf at all, the rest as for "exp" by the same argument.
     critic_layer_norm / policy_layer_norm False (mlp.py:29-30): that MLP has no LayerNorm leaves; a LayerNorm draws nothing, so the
     Dense leaves keep their keys and values."""
     from ..agents.flax_tree import theta_paths
