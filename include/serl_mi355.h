@@ -236,7 +236,7 @@ typedef struct serl_agent_cfg {
    *   tx_cosine_steps  > 0: warmup_cosine_decay_schedule(0, lr, warmup, decay_steps = this, end 0) (optimizers.py:14-21)
    *   tx_weight_decay_on != 0: optax.adamw with tx_weight_decay (optimizers.py:39-42); it decays the WHOLE tree, as the
    *                    reference's tx.update(grads, state, params) does -- on an agent with the pretrained ResNet-10 that
-   *                    tree holds the "frozen" trunk too: see LIVE TRUNK at serl_agent_create
+   *                    tree holds the "frozen" trunk too: see LIVE TRUNK at serl_agent_create_opts
    *   tx_clip_norm     > 0: optax.clip_by_global_norm on this optimizer's gradient tree (optimizers.py:36-37) */
   float tx_lr[3];
   int tx_warmup[3];
@@ -262,7 +262,7 @@ typedef struct serl_agent_cfg {
 #define SERL_STD_EXP 0
 #define SERL_STD_SOFTPLUS 1
 #define SERL_STD_UNIFORM 2
-#define SERL_STD_FIXED 3   /* serl_agent_create_fixed_std alone */
+#define SERL_STD_FIXED 3   /* serl_agent_create_opts and serl_agent_create_fixed_std alone */
 #define SERL_ACT_TANH 0
 #define SERL_ACT_RELU 1
 #define SERL_ACT_SWISH 2
@@ -285,82 +285,88 @@ typedef struct serl_agent_cfg {
  * always come from the classifier's own trunk (SERL_LABEL_FRAMES).  Agents without weight decay, and agents without the
  * pretrained trunk (SERL_ENCODER_SMALL, state-only: their decay is the ordinary path of their leaves), are not in this mode and
  * launch what they always did. */
-int serl_agent_create(const serl_agent_cfg* cfg, serl_agent** out);
+/* NETWORK OPTIONS.  What the critic's and the policy's networks are, beyond serl_agent_cfg, stated once.  Every field is chosen so
+ * that 0 means what utils/launcher.py configures: an all-zero serl_agent_opts is serl_agent_create(cfg), and such an agent
+ * launches the kernels it always launched.  A value outside what is listed is SERL_ERR_INVALID, the message naming the field and
+ * the value.  No option owns a parameter of its own except where said: leaves, optimizer state and checkpoints are otherwise alike.
+ * serl_mlp_opts, one per network (networks/mlp.py:19-31; sac.py:516-524 and drq.py:188-207 build the two from separate kwargs, so
+ * the two are independent):
+ *   act            `activations`, behind every layer: SERL_ACT_TANH y = tanh(p); SERL_ACT_RELU y = max(p, 0), gradient 0 at p = 0
+ *                  (jax.nn.relu); SERL_ACT_SWISH y = p * sigmoid(p) (flax.linen.swish = silu, mlp.py's own default).  The encoder's
+ *                  bottleneck and proprio rows keep tanh and their LayerNorm (resnet_v1.py:371-374, encoding.py:66-68).
+ *   n_layers, dims `hidden_dims`: 1 to SERL_MAX_MLP_LAYERS widths, each a multiple of 64 in [64, 1024]; n_layers == 0 means two
+ *                  layers of cfg->hidden, which is read for such a network alone.  Leaves: critic/w<j>, critic/b<j>,
+ *                  critic/ln<j>/{scale,bias}, j = 1..n_layers, and the same under actor/; critic/head/kernel follows the critic's
+ *                  last width, actor/mean/kernel and actor/logstd/kernel the policy's.
+ *   no_layer_norm  1 = `use_layer_norm=False` (mlp.py:29-30; mlp.py's own default, plain SAC and REDQ): every layer is
+ *                  y = act(Dense(x) + b) and owns w<j> and b<j> alone -- no ln<j>/{scale,bias} leaf, moment, target copy or
+ *                  checkpoint entry; a plain layer takes the place of its LayerNorm launch one for one.
+ *   dropout        `dropout_rate` in [0, 1) (mlp.py:27-28: Dense -> Dropout -> LayerNorm -> activation; sac.py:137-176,197-207 run
+ *                  every loss with train=True; a positive critic rate is Dropout-Q).  A double, as the reference's is: the keep
+ *                  probability is float32(1.0 - rate), rounded once.  A kept element of the Dense output (bias included) is divided
+ *                  by it, a dropped one is 0, and the LayerNorm's statistics are those of the masked row; all ensemble members of
+ *                  one critic forward drop the SAME elements (one keep-mask [rows][hidden] per (forward, layer)).  The update's
+ *                  six MLP evaluations draw (serl_mlp_noise below); serl_agent_sample_actions, serl_agent_eval_q and
+ *                  serl_agent_eval_policy are train=False and ignore the rates.  Served with a positive rate in either network:
+ *                  n_layers == 0 and no_layer_norm == 0 in BOTH networks (the masks are laid out for two layers of cfg->hidden)
+ *                  and a std_param other than SERL_STD_FIXED.
+ * serl_agent_opts (actor_critic_nets.py:167-227):
+ *   std_param      SERL_STD_EXP      std = clip(exp(Dense_1(h)), std_min, std_max)
+ *                  SERL_STD_SOFTPLUS std = clip(softplus(Dense_1(h)), std_min, std_max)
+ *                  SERL_STD_UNIFORM  std = clip(exp(log_stds), std_min, std_max): one trainable vector of act_dim floats shared by
+ *                                    all rows, leaf actor/log_stds in place of actor/logstd/{kernel,bias} (create_drq's own default)
+ *                  SERL_STD_FIXED    std = clip(fixed_std, std_min, std_max), the same for every row, in float32 inside the head
+ *                                    kernels (:189-192,212, how the reference writes TD3).  The head then has NO std parameter: no
+ *                                    actor/logstd/{kernel,bias} and no actor/log_stds leaf, one head GEMM group (the mean), and no
+ *                                    gradient, moment, target copy or checkpoint entry for a std.  With the tanh bijector log pi
+ *                                    still depends on the mean through the log-determinant; with no_tanh == 1 it depends on no
+ *                                    parameter and the actor gradient is dL/da alone.
+ *   no_tanh        0 = distrax Tanh bijector on the Gaussian; 1 = tanh_squash_distribution=False: the plain Gaussian -- actions are
+ *                  unbounded, log pi has no log-det term, and the mode is the mean
+ *   fixed_std      act_dim floats (host memory, copied), each finite and > 0, with SERL_STD_FIXED; NULL with every other
+ *                  std_param.  A constant of the agent: device memory of its own outside the parameter arena, never stepped,
+ *                  averaged or all-reduced, and not part of serl_agent_get / serl_agent_set (serl_agent_fixed_std reads it back). */
+#define SERL_MAX_MLP_LAYERS 4
+typedef struct serl_mlp_opts {
+  int act;
+  int n_layers;
+  int dims[SERL_MAX_MLP_LAYERS];
+  int no_layer_norm;
+  double dropout;
+} serl_mlp_opts;
+typedef struct serl_agent_opts {
+  int std_param;
+  int no_tanh;
+  serl_mlp_opts critic, policy;
+  const float* fixed_std;
+} serl_agent_opts;
+int serl_agent_create_opts(const serl_agent_cfg* cfg, const serl_agent_opts* opts, serl_agent** out);
 int serl_agent_live_trunk(serl_agent* a);   /* 1: live-trunk mode (above), 0: not, -1: NULL */
-/* serl_agent_create with another policy distribution (actor_critic_nets.py:167-227).  serl_agent_create is this function with
- * (SERL_STD_EXP, 0): exp + tanh, what utils/launcher.py configures -- serl_agent_cfg itself is unchanged and describes the agent it
- * always did.  Any other value of the two arguments is SERL_ERR_INVALID, the message naming the argument and the value.
- *   std_param: SERL_STD_EXP      std = clip(exp(Dense_1(h)), std_min, std_max)
- *              SERL_STD_SOFTPLUS std = clip(softplus(Dense_1(h)), std_min, std_max)
- *              SERL_STD_UNIFORM  std = clip(exp(log_stds), std_min, std_max): one trainable vector of act_dim floats shared by
- *                                all rows, leaf actor/log_stds in place of actor/logstd/{kernel,bias} (create_drq's own default)
- *   no_tanh:   0 = distrax Tanh bijector on the Gaussian; 1 = tanh_squash_distribution=False: the plain Gaussian -- actions are
- *              unbounded, log pi has no log-det term, and the mode is the mean */
-int serl_agent_create_policy(const serl_agent_cfg* cfg, int std_param, int no_tanh, serl_agent** out);
-/* serl_agent_create_policy with another activation in the critic's and the policy's MLP (networks/mlp.py:19-31: `activations`
- * behind every LayerNorm; the two networks take theirs from separate kwargs, so the codes are independent).  serl_agent_create_policy
- * is this function with (SERL_ACT_TANH, SERL_ACT_TANH), what utils/launcher.py writes.  Any other code is SERL_ERR_INVALID, the
- * message naming the served set.  An activation owns no parameter: leaves, optimizer state and checkpoints are the same for all.
- * The encoder's bottleneck and proprio rows keep tanh (resnet_v1.py:371-374, encoding.py:66-68).
- *   SERL_ACT_TANH   y = tanh(p)
- *   SERL_ACT_RELU   y = max(p, 0), gradient 0 at p = 0 (jax.nn.relu)
- *   SERL_ACT_SWISH  y = p * sigmoid(p) (flax.linen.swish = silu, mlp.py's own default) */
-int serl_agent_create_mlp(const serl_agent_cfg* cfg, int std_param, int no_tanh, int critic_act, int policy_act, serl_agent** out);
-/* serl_agent_create_mlp with Dropout in the critic's and the policy's MLP (networks/mlp.py:27-28: Dense -> Dropout(dropout_rate) ->
- * LayerNorm -> activation in both hidden layers; agents/continuous/sac.py:137-176,197-207 run every loss with train=True).  A
- * positive critic rate is Dropout-Q.  serl_agent_create_mlp is this function with (0, 0): such an agent launches the kernels it
- * always launched.  Rates outside [0, 1) are SERL_ERR_INVALID.  The rates are doubles, as the reference's are: the keep
- * probability is float32(1.0 - rate), rounded once -- what jax.random.bernoulli compares with and the kept elements are divided by.  Dropout owns no parameter: leaves, optimizer state and checkpoints are the same at every rate.
- *   - a kept element of the Dense output (bias included) is divided by 1 - rate, a dropped one is 0; the LayerNorm's statistics
- *     are those of the masked row;
- *   - all ensemble members of one critic forward drop the SAME elements (ensemblize splits only the params stream): one keep-mask
- *     [rows][hidden] per (forward, layer);
- *   - the update's six MLP evaluations draw (serl_mlp_noise below); serl_agent_sample_actions, serl_agent_eval_q and
- *     serl_agent_eval_policy are train=False and ignore the rates. */
+/* The entry points from before serl_agent_opts: each sets the fields its arguments name and leaves the others 0.  The three that
+ * take the width lists refuse a NULL list and never read cfg->hidden; all but serl_agent_create_fixed_std refuse SERL_STD_FIXED. */
+int serl_agent_create(const serl_agent_cfg* cfg, serl_agent** out);   /* no field: the all-zero opts */
+int serl_agent_create_policy(const serl_agent_cfg* cfg, int std_param, int no_tanh, serl_agent** out);   /* std_param, no_tanh */
+int serl_agent_create_mlp(const serl_agent_cfg* cfg, int std_param, int no_tanh, int critic_act, int policy_act, serl_agent** out);   /* ... and both act */
+/* ... and both dropout */
 int serl_agent_create_dropout(const serl_agent_cfg* cfg, int std_param, int no_tanh, int critic_act, int policy_act,
                               double critic_dropout, double policy_dropout, serl_agent** out);
-/* serl_agent_create_mlp with critic and policy MLPs of their own depth and per-layer widths (networks/mlp.py:19-31 loops over
- * `hidden_dims` of any length; agents/continuous/sac.py:516-524 and drq.py:188-207 build the two networks from separate kwargs, so
- * the lists are independent).  Each list holds 1 to SERL_MAX_MLP_LAYERS widths, every width a multiple of 64 in [64, 1024]; anything
- * else, or a NULL list, is SERL_ERR_INVALID, the message naming the network, the layer and the value.  cfg->hidden is not read.
- * serl_agent_create_mlp is this function with {cfg->hidden, cfg->hidden} twice: such an agent launches the kernels it always
- * launched.  Leaves: critic/w<j>, critic/b<j>, critic/ln<j>/{scale,bias}, j = 1..n_critic, and the same under actor/, layer by
- * layer; critic/head/kernel follows the critic's last width, actor/mean/kernel and actor/logstd/kernel the policy's.  No Dropout
- * in these MLPs: serl_agent_create_dropout keeps its two layers of one width. */
-#define SERL_MAX_MLP_LAYERS 4
+/* serl_agent_create_mlp's fields and both n_layers / dims */
 int serl_agent_create_shapes(const serl_agent_cfg* cfg, int std_param, int no_tanh, int critic_act, int policy_act,
                              const int* critic_dims, int n_critic, const int* policy_dims, int n_policy, serl_agent** out);
-/* The hidden widths of one MLP of any agent (networks/mlp.py:19-31; sac.py:516-524, drq.py:188-207): network 0 = critic,
- * 1 = policy.  Returns the layer count and fills dims[0 .. count); -1 on a NULL argument or another network code. */
-int serl_agent_mlp_dims(serl_agent* a, int network /* 0 critic, 1 policy */, int dims[SERL_MAX_MLP_LAYERS]);  /* -> layer count */
-/* serl_agent_create_shapes with the LayerNorm of the critic's and of the policy's MLP switched per network (networks/mlp.py:29-30:
- * `if self.use_layer_norm: x = nn.LayerNorm()(x)` in every hidden layer; mlp.py's own default, plain SAC and REDQ are without it;
- * the two networks take the flag from separate kwargs, so the two are independent).  serl_agent_create_shapes is this function
- * with (1, 1): such an agent launches the kernels it always launched.  Any other flag value than 0 / 1 is SERL_ERR_INVALID.
- * A layer of a network with flag 0 is y = act(Dense(x) + b) and owns critic/w<j> and critic/b<j> (actor/...) alone: no
- * ln<j>/{scale,bias} leaf, optimizer moment, target copy or checkpoint entry exists for it.  Every activation, depth and width of
- * serl_agent_create_shapes applies; a plain layer takes the place of its LayerNorm launch one for one.  The encoder's bottleneck
- * and proprio rows keep their LayerNorm (resnet_v1.py:371-374, encoding.py:66-68).  No Dropout in these MLPs. */
+/* ... and both no_layer_norm, as its complement: critic_layer_norm / policy_layer_norm 1 = LayerNorm, 0 = none */
 int serl_agent_create_layer_norm(const serl_agent_cfg* cfg, int std_param, int no_tanh, int critic_act, int policy_act,
                                  const int* critic_dims, int n_critic, const int* policy_dims, int n_policy, int critic_layer_norm,
                                  int policy_layer_norm, serl_agent** out);
-/* Whether the layers of one MLP of any agent have their LayerNorm (networks/mlp.py:29-30): network 0 = critic, 1 = policy.
- * Returns 1 or 0; -1 on a NULL agent or another network code. */
-int serl_agent_mlp_layer_norm(serl_agent* a, int network /* 0 critic, 1 policy */);
-/* serl_agent_create_layer_norm with the fourth std parameterisation (actor_critic_nets.py:189-192,212: `fixed_std`, how the
- * reference writes TD3): std_param == SERL_STD_FIXED and fixed_std = act_dim floats (host memory, copied), each finite and > 0:
- *   std = clip(fixed_std, std_min, std_max), the same for every row, in float32 inside the head kernels (temperature 1).
- * The head then has NO std parameter: the leaf table holds neither actor/logstd/{kernel,bias} nor actor/log_stds, the head GEMMs
- * have one group (the mean), and no gradient, optimizer moment, target copy or checkpoint entry exists for a std.  The vector is
- * a constant of the agent: device memory of its own outside the parameter arena, never stepped, averaged or all-reduced, and
- * not part of serl_agent_get / serl_agent_set (serl_agent_fixed_std reads it back).  With the tanh bijector log pi still depends
- * on the mean through the log-determinant; with no_tanh == 1 it depends on no parameter and the actor gradient is dL/da alone.
- * fixed_std is NULL unless std_param == SERL_STD_FIXED and not NULL when it is: either mismatch, or an entry that is not a
- * finite positive number, is SERL_ERR_INVALID with a message.  serl_agent_create_layer_norm is this function with NULL: it
- * keeps refusing std_param 3 by its own range check, and every agent of the other three modes launches what it launched. */
+/* ... and fixed_std, with std_param up to SERL_STD_FIXED */
 int serl_agent_create_fixed_std(const serl_agent_cfg* cfg, int std_param, int no_tanh, int critic_act, int policy_act,
                                 const int* critic_dims, int n_critic, const int* policy_dims, int n_policy, int critic_layer_norm,
                                 int policy_layer_norm, const float* fixed_std, serl_agent** out);
+/* The hidden widths of one MLP of any agent (networks/mlp.py:19-31; sac.py:516-524, drq.py:188-207): network 0 = critic,
+ * 1 = policy.  Returns the layer count and fills dims[0 .. count); -1 on a NULL argument or another network code. */
+int serl_agent_mlp_dims(serl_agent* a, int network /* 0 critic, 1 policy */, int dims[SERL_MAX_MLP_LAYERS]);  /* -> layer count */
+/* Whether the layers of one MLP of any agent have their LayerNorm (networks/mlp.py:29-30): network 0 = critic, 1 = policy.
+ * Returns 1 or 0; -1 on a NULL agent or another network code. */
+int serl_agent_mlp_layer_norm(serl_agent* a, int network /* 0 critic, 1 policy */);
 /* The fixed_std vector of an agent made with SERL_STD_FIXED, as passed (before the clip): out = act_dim floats (host).
  * SERL_ERR_INVALID on a NULL argument or an agent of another std parameterisation. */
 int serl_agent_fixed_std(serl_agent* a, float* out);

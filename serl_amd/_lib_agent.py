@@ -3,6 +3,7 @@ handles.  _lib.lib() applies SIGNATURES / RESTYPES once, when it loads the libra
 import ctypes as C
 
 from ._lib import P, SerlBatch, f32, i32, i64, vp
+from .utils.init import MAX_MLP_LAYERS
 
 
 class SerlAgentCfg(C.Structure):
@@ -23,6 +24,16 @@ class SerlAgentCfg(C.Structure):
         ("tx_lr_set", C.c_int * 3),   # != 0: tx_lr[t] given explicitly (0.0 is a valid optax learning rate)
         ("num_stack", C.c_int),   # T, frames per observation (0 = 1); state_dim is then the flattened width T * S
     ]
+
+
+class SerlMlpOpts(C.Structure):      # serl_mlp_opts: one network's MLP; all zero = two LayerNorm+tanh layers of cfg.hidden, no Dropout
+    _fields_ = [("act", C.c_int), ("n_layers", C.c_int), ("dims", C.c_int * MAX_MLP_LAYERS), ("no_layer_norm", C.c_int),
+                ("dropout", C.c_double)]
+
+
+class SerlAgentOpts(C.Structure):    # serl_agent_opts (utils.init.NetSpec.to_c fills it); all zero = serl_agent_create(cfg)
+    _fields_ = [("std_param", C.c_int), ("no_tanh", C.c_int), ("critic", SerlMlpOpts), ("policy", SerlMlpOpts),
+                ("fixed_std", P(C.c_float))]
 
 
 TX_INDEX = {"actor": 0, "critic": 1, "temperature": 2}   # SERL_TX_*
@@ -77,6 +88,7 @@ SNAP_BITS = {"params": 1, "target_params": 2, "opt_states": 4}   # SERL_SNAP_*, 
 
 # function -> argtypes (int status unless RESTYPES says otherwise)
 SIGNATURES = {
+    "serl_agent_create_opts": [P(SerlAgentCfg), P(SerlAgentOpts), P(vp)],   # what AgentCore calls; the older entry points follow
     "serl_agent_create": [P(SerlAgentCfg), P(vp)],
     "serl_agent_create_policy": [P(SerlAgentCfg), i32, i32, P(vp)],   # std_param (SERL_STD_*), no_tanh
     "serl_agent_create_mlp": [P(SerlAgentCfg), i32, i32, i32, i32, P(vp)],   # ... critic_act, policy_act (SERL_ACT_*)

@@ -2,6 +2,7 @@
 from __future__ import annotations
 
 import ctypes as C
+import dataclasses
 from typing import Dict, Optional
 
 import numpy as np
@@ -12,8 +13,7 @@ from .._handle import Handle
 from .._lib_agent import (APPLY_ACTOR_TEMP, APPLY_CRITIC, MLP_SITES, NET_BITS, TX_INDEX, SerlAgentCfg, SerlInfo,  # noqa: F401
                           SerlMlpNoise, SerlNoise)
 
-from ..utils.init import (FIXED_STD, MLP_ACTIVATIONS, STD_PARAMETERIZATIONS, check_fixed_dropout, check_plain_dropout, check_shapes_dropout,
-                          resolve_mlp_dims)
+from ..utils.init import FIXED_STD, NetSpec
 
 TX_NAMES = ("actor", "critic", "temperature")
 
@@ -39,13 +39,14 @@ class AgentCore(Handle):
         critic_dropout / policy_dropout: MLP's `dropout_rate` in [0, 1) (mlp.py:27-28, utils.init.mlp_dropout_rates); the update's
         losses draw, the evaluation calls (sample_actions, eval_q, eval_policy) never do.
         critic_dims / policy_dims: MLP's `hidden_dims` of each network, 1 to MAX_MLP_LAYERS widths (utils.init.mlp_layer_dims);
-        with either given the agent comes from serl_agent_create_shapes and `hidden` stands only for a list left out.  The
-        attributes of the same names read (hidden, hidden) on a core made without them.
-        critic_layer_norm / policy_layer_norm: MLP's `use_layer_norm` of each network (mlp.py:29-30, utils.init.mlp_layer_norms); with
-        either False the agent comes from serl_agent_create_layer_norm, and no Dropout rate may be positive.
+        with either given `hidden` stands only for a list left out.  The attributes of the same names read (hidden, hidden) on a
+        core made without them.
+        critic_layer_norm / policy_layer_norm: MLP's `use_layer_norm` of each network (mlp.py:29-30, utils.init.mlp_layer_norms).
         fixed_std: with std_parameterization="fixed" (and only then) the float32 vector of act_dim finite positive entries that
-        utils.init.policy_mode_fixed returns; the agent then comes from serl_agent_create_fixed_std, its head has no std leaf, and no
-        Dropout rate may be positive.  The attribute of the same name reads it back from the library (None for another mode)."""
+        utils.init.policy_mode_fixed returns; the head then has no std leaf.  The attribute of the same name reads it back from the
+        library (None for another mode).
+        These network options are no fields of serl_agent_cfg: they make one utils.init.NetSpec (`spec`), whose check() says where
+        a positive Dropout rate is served, and go to serl_agent_create_opts as one struct (_create)."""
         if target_entropy is None:
             target_entropy = -act_dim / 2
         self.cfg = SerlAgentCfg(device, n_cam, H, W, state_dim, act_dim, batch, ensemble, hidden,
@@ -58,34 +59,28 @@ class AgentCore(Handle):
         self.cfg.critic_subsample_size = -1 if critic_subsample_size is None else int(critic_subsample_size)
         self.cfg.backup_entropy = 1 if backup_entropy else 0
         self.cfg.num_stack = int(num_stack)
-        # the policy distribution is no field of serl_agent_cfg: it goes to serl_agent_create_policy (_create)
-        self.std_parameterization = std_parameterization
-        self.tanh_squash_distribution = bool(tanh_squash_distribution)
         if (std_parameterization == FIXED_STD) != (fixed_std is not None):
             raise ValueError(f"std_parameterization={std_parameterization!r} with fixed_std={fixed_std!r}: 'fixed' and fixed_std go together")
-        self._fixed_std = None
         if fixed_std is not None:
-            self._fixed_std = np.ascontiguousarray(np.asarray(fixed_std, np.float32).reshape(-1))
-            if self._fixed_std.shape != (act_dim,) or not (np.isfinite(self._fixed_std).all() and (self._fixed_std > 0).all()):
+            v = np.asarray(fixed_std, np.float32).reshape(-1)
+            if v.shape != (act_dim,) or not (np.isfinite(v).all() and (v > 0).all()):
                 raise ValueError(f"fixed_std must be {act_dim} finite positive numbers (got {fixed_std!r})")
-        self._std_param = 3 if fixed_std is not None else STD_PARAMETERIZATIONS.index(std_parameterization)   # SERL_STD_FIXED = 3
-        # ... nor are the MLP activations: serl_agent_create_mlp
-        self.critic_activation, self.policy_activation = critic_activation, policy_activation
-        self._acts = (MLP_ACTIVATIONS.index(critic_activation), MLP_ACTIVATIONS.index(policy_activation))
-        # ... nor the MLPs' Dropout rates: serl_agent_create_dropout
-        self.critic_dropout, self.policy_dropout = float(critic_dropout), float(policy_dropout)
-        # ... nor the MLPs' per-layer widths: serl_agent_create_shapes
-        self._shapes = critic_dims is not None or policy_dims is not None
-        self.critic_dims, self.policy_dims = resolve_mlp_dims(hidden, critic_dims, policy_dims)
-        # ... nor whether the MLPs have their LayerNorm: serl_agent_create_layer_norm
+            fixed_std = tuple(float(x) for x in v)
         for name, flag in (("critic_layer_norm", critic_layer_norm), ("policy_layer_norm", policy_layer_norm)):
             if not isinstance(flag, (bool, np.bool_)):
                 raise TypeError(f"{name} must be a bool (got {flag!r})")
-        self.critic_layer_norm, self.policy_layer_norm = bool(critic_layer_norm), bool(policy_layer_norm)
-        check_plain_dropout(self.critic_layer_norm, self.policy_layer_norm, self.critic_dropout, self.policy_dropout)
-        check_fixed_dropout(self._fixed_std, self.critic_dropout, self.policy_dropout)
-        if self._shapes:
-            check_shapes_dropout(self.critic_dims, self.policy_dims, self.critic_dropout, self.policy_dropout)
+        self.spec = NetSpec(std_parameterization, bool(tanh_squash_distribution), fixed_std, critic_activation, policy_activation,
+                            float(critic_dropout), float(policy_dropout), int(hidden),
+                            None if critic_dims is None else tuple(int(d) for d in critic_dims),
+                            None if policy_dims is None else tuple(int(d) for d in policy_dims),
+                            bool(critic_layer_norm), bool(policy_layer_norm))
+        opts = self.spec.to_c()      # (an unknown std_parameterization or activation name raises here)
+        self.spec.check()
+        for f in dataclasses.fields(self.spec):      # the options as public attributes, under the constructor's names ...
+            if f.name not in ("hidden", "fixed_std", "critic_dims", "policy_dims"):
+                setattr(self, f.name, getattr(self.spec, f.name))
+        self.critic_dims, self.policy_dims = self.spec.dims      # ... the two lists resolved
+        self._std_param, self._acts = opts.std_param, (opts.critic.act, opts.policy.act)      # SERL_STD_* / SERL_ACT_* codes
         for name, kw in (optimizers or {}).items():
             i = TX_INDEX[name]
             bad = set(kw) - {"learning_rate", "warmup_steps", "cosine_decay_steps", "weight_decay", "clip_grad_norm"}
@@ -113,24 +108,7 @@ class AgentCore(Handle):
         super().__del__()
 
     def _create(self, cfg):
-        if self._fixed_std is not None:
-            cd, pd = (C.c_int32 * len(self.critic_dims))(*self.critic_dims), (C.c_int32 * len(self.policy_dims))(*self.policy_dims)
-            fs = (C.c_float * len(self._fixed_std))(*self._fixed_std.tolist())
-            return self.L.serl_agent_create_fixed_std(C.byref(cfg), self._std_param, 0 if self.tanh_squash_distribution else 1, *self._acts,
-                                                      cd, len(self.critic_dims), pd, len(self.policy_dims),
-                                                      int(self.critic_layer_norm), int(self.policy_layer_norm), fs, C.byref(self._h))
-        if not (self.critic_layer_norm and self.policy_layer_norm):
-            cd, pd = (C.c_int32 * len(self.critic_dims))(*self.critic_dims), (C.c_int32 * len(self.policy_dims))(*self.policy_dims)
-            return self.L.serl_agent_create_layer_norm(C.byref(cfg), self._std_param, 0 if self.tanh_squash_distribution else 1, *self._acts,
-                                                       cd, len(self.critic_dims), pd, len(self.policy_dims),
-                                                       int(self.critic_layer_norm), int(self.policy_layer_norm), C.byref(self._h))
-        if self._shapes and not (self.critic_dropout > 0 or self.policy_dropout > 0):
-            cd, pd = (C.c_int32 * len(self.critic_dims))(*self.critic_dims), (C.c_int32 * len(self.policy_dims))(*self.policy_dims)
-            return self.L.serl_agent_create_shapes(C.byref(cfg), self._std_param, 0 if self.tanh_squash_distribution else 1, *self._acts,
-                                                   cd, len(self.critic_dims), pd, len(self.policy_dims), C.byref(self._h))
-        # (Dropout keeps its own entry point: two layers of one width, cfg.hidden -- check_shapes_dropout saw to that)
-        return self.L.serl_agent_create_dropout(C.byref(cfg), self._std_param, 0 if self.tanh_squash_distribution else 1, *self._acts,
-                                                self.critic_dropout, self.policy_dropout, C.byref(self._h))
+        return self.L.serl_agent_create_opts(C.byref(cfg), C.byref(self.spec.to_c()), C.byref(self._h))
 
     # ---- parameters ------------------------------------------------------------------------
     @property
@@ -142,7 +120,7 @@ class AgentCore(Handle):
     def fixed_std(self) -> Optional[np.ndarray]:
         """float32[act_dim]: the fixed_std of a std_parameterization="fixed" agent as the library holds it (before the clip to
         [std_min, std_max], which the head kernels apply); None for an agent of another std parameterisation."""
-        if self._fixed_std is None:
+        if self.spec.fixed_std is None:
             return None
         out = np.zeros(self.cfg.act_dim, np.float32)
         _lib.check(self.L.serl_agent_fixed_std(self._h, out.ctypes.data_as(C.POINTER(C.c_float))))

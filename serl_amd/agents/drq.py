@@ -220,26 +220,9 @@ class DrQAgent:
         if not use_proprio:
             raise NotImplementedError("only use_proprio=True")
         pk = policy_kwargs or {}
-        # policy_fixed=True: "fixed" / fixed_std are read (actor_critic_nets.py:189-192); else refused, as always
         A = int(np.asarray(actions).shape[-1])
-        std_param, squash, fixed = pinit.policy_mode_fixed(pk, A) if policy_fixed else (*pinit.policy_mode(pk), None)
-        # mlp_shapes=True: each network's own depth and per-layer widths (mlp.py:19-31); else the one width of [h, h], as always
-        dims = pinit.mlp_layer_dims(critic_network_kwargs, policy_network_kwargs, mlp_plain) if mlp_shapes else None
-        hidden = dims[0][0] if mlp_shapes else pinit.mlp_hidden_width(critic_network_kwargs, policy_network_kwargs, mlp_plain)
-        # mlp_plain=True: each network's own use_layer_norm (mlp.py:29-30); else LayerNorm in both, as always
-        lns = pinit.mlp_layer_norms(critic_network_kwargs, policy_network_kwargs) if mlp_plain else (True, True)
-        critic_act, policy_act = pinit.mlp_activations(critic_network_kwargs, policy_network_kwargs, mlp_dropout)
-        critic_drop, policy_drop = pinit.mlp_dropout_rates(critic_network_kwargs, policy_network_kwargs) if mlp_dropout else (0.0, 0.0)
-        if mlp_shapes:
-            pinit.check_shapes_dropout(dims[0], dims[1], critic_drop, policy_drop)
-            if dims[0] == dims[1] and len(dims[0]) == 2 and dims[0][0] == dims[0][1]:
-                dims = None    # [h, h] twice: the very agent the call without the switch makes
-        pinit.check_plain_dropout(*lns, critic_drop, policy_drop)
-        pinit.check_fixed_dropout(fixed, critic_drop, policy_drop)
-        shape_kw = {} if dims is None else {"critic_dims": dims[0], "policy_dims": dims[1]}
-        if lns != (True, True):    # (True, True): the very agent the call without the switch makes
-            shape_kw.update(critic_layer_norm=lns[0], policy_layer_norm=lns[1])
-        core_kw = {} if fixed is None else {"fixed_std": fixed}
+        spec = pinit.network_spec(critic_network_kwargs, policy_network_kwargs, pk, A, mlp_dropout=mlp_dropout, mlp_shapes=mlp_shapes,
+                                  mlp_plain=mlp_plain, policy_fixed=policy_fixed)
         seed = int(np.asarray(rng).reshape(-1)[-1]) if not isinstance(rng, int) else rng
         image_keys = tuple(image_keys)
         img = np.asarray(observations[image_keys[0]])
@@ -268,28 +251,20 @@ class DrQAgent:
                          std_max=pk.get("std_max", 10.0), target_entropy=target_entropy, seed=seed,
                          optimizers={k: {"warmup_steps": 0, **v} for k, v in opts.items()}, encoder_type=encoder_type,
                          critic_subsample_size=critic_subsample_size, backup_entropy=backup_entropy, num_stack=T,
-                         hidden=hidden, std_parameterization=std_param, tanh_squash_distribution=squash,
-                         critic_activation=critic_act, policy_activation=policy_act,
-                         critic_dropout=critic_drop, policy_dropout=policy_drop, **shape_kw, **core_kw)
+                         **spec.core_kwargs())
         if init_ref.check_param_init(param_init):
             theta = init_ref.theta_reference(image_keys, H, W, S, A, rng, ensemble=critic_ensemble_size, encoder_type=encoder_type,
-                                             temperature_init=temperature_init, device=device, num_stack=T, hidden=hidden,
-                                             std_parameterization=std_param, **shape_kw)
+                                             temperature_init=temperature_init, device=device, num_stack=T, **spec.leaf_kwargs())
         else:
             theta = pinit.init_theta(len(image_keys), H, W, S, A, seed=seed, temperature_init=temperature_init,
-                                     ensemble=critic_ensemble_size, encoder_type=encoder_type, num_stack=T, hidden=hidden,
-                                     std_parameterization=std_param, **shape_kw)
+                                     ensemble=critic_ensemble_size, encoder_type=encoder_type, num_stack=T, **spec.leaf_kwargs())
         trunk = pinit.init_trunk(seed=seed) if encoder_type == "resnet-pretrained" else {}
         for sec in ("params", "target_params"):  # JaxRLTrainState.create(target_params=params)
             core.load_flat(sec, theta)
             core.load_flat(sec, trunk)
         config = dict(critic_ensemble_size=critic_ensemble_size, critic_subsample_size=critic_subsample_size,
                       discount=discount, soft_target_update_rate=soft_target_update_rate,
-                      target_entropy=target_entropy, backup_entropy=backup_entropy, image_keys=image_keys,
-                      critic_activation=critic_act, policy_activation=policy_act,
-                      critic_dropout_rate=critic_drop, policy_dropout_rate=policy_drop,
-                      **({} if fixed is None else {"fixed_std": tuple(float(x) for x in fixed)}),
-                      **({} if lns == (True, True) else {"critic_use_layer_norm": lns[0], "policy_use_layer_norm": lns[1]}))
+                      target_entropy=target_entropy, backup_entropy=backup_entropy, image_keys=image_keys, **spec.config_entries())
         agent = cls(core, image_keys, config, seed)
         agent._opts = {k: {"warmup_steps": 0, **v} for k, v in opts.items()}
         if param_init == "reference":

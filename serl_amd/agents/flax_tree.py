@@ -17,7 +17,7 @@ from typing import Dict
 
 import numpy as np
 
-from ..utils.init import STAGES, theta_shapes, trunk_shapes
+from ..utils.init import STAGES, NetSpec, theta_shapes, trunk_shapes
 
 
 # optax.adam's state (optax/_src/transform.py ScaleByAdamState; base.EmptyState of scale_by_learning_rate)
@@ -141,21 +141,11 @@ def _policy_std_paths(std_parameterization):
     return {"actor/logstd/kernel": [("modules_actor", "Dense_1", "kernel")], "actor/logstd/bias": [("modules_actor", "Dense_1", "bias")]}
 
 
-def std_parameterization_of(core) -> str:
-    """the std parameterisation an AgentCore was created with (a handle without the attribute is the "exp" agent)"""
-    return getattr(core, "std_parameterization", "exp")
-
-
-def mlp_dims_of(core):
-    """(critic, policy) hidden widths of an AgentCore; a core that only has cfg.hidden is the (hidden, hidden) agent"""
-    cd, pd = getattr(core, "critic_dims", None), getattr(core, "policy_dims", None)
-    h = int(getattr(core.cfg, "hidden", 256))
-    return (tuple(cd) if cd is not None else (h, h), tuple(pd) if pd is not None else (h, h))
-
-
-def layer_norms_of(core):
-    """(critic, policy): whether each MLP of an AgentCore has its LayerNorm; a core without the attributes has both"""
-    return bool(getattr(core, "critic_layer_norm", True)), bool(getattr(core, "policy_layer_norm", True))
+def net_spec_of(core) -> NetSpec:
+    """the network options of an AgentCore, as far as the leaf tables depend on them (NetSpec.leaf_kwargs); an attribute the handle
+    does not have is the default's: a core that only has cfg.hidden is the (hidden, hidden), LayerNorm, "exp" agent"""
+    names = ("std_parameterization", "critic_dims", "policy_dims", "critic_layer_norm", "policy_layer_norm")
+    return NetSpec(hidden=int(getattr(core.cfg, "hidden", 256)), **{n: getattr(core, n) for n in names if hasattr(core, n)})
 
 
 def _mlp_paths(m, pre, base, n_layers, layer_norm=True):
@@ -282,13 +272,11 @@ def export_tree(core, section: str, image_keys, duplicate_encoder_under_critic: 
     get = core.get if get is None else get
     cfg = core.cfg
     etype = "small" if cfg.encoder_type == 1 else "resnet-pretrained"
-    cd, pd = mlp_dims_of(core)
-    cln, pln = layer_norms_of(core)
-    shapes = theta_shapes(cfg.n_cam, cfg.H, cfg.W, cfg.state_dim, cfg.act_dim, ensemble=cfg.ensemble, hidden=cfg.hidden,
-                          encoder_type=etype, num_stack=max(cfg.num_stack, 1), std_parameterization=std_parameterization_of(core),
-                          critic_dims=cd, policy_dims=pd, critic_layer_norm=cln, policy_layer_norm=pln)
+    net = net_spec_of(core).leaf_kwargs()
+    shapes = theta_shapes(cfg.n_cam, cfg.H, cfg.W, cfg.state_dim, cfg.act_dim, ensemble=cfg.ensemble, encoder_type=etype,
+                          num_stack=max(cfg.num_stack, 1), **net)
     shapes.update(trunk_shapes())
-    paths = theta_paths(image_keys, critic_mlp_name, etype, std_parameterization_of(core), cd, pd, cln, pln)
+    paths = theta_paths(image_keys, critic_mlp_name, etype, **net)
     if cfg.n_cam and etype != "small":
         # ONE frozen trunk: drq.py:165-176 passes the same `pretrained_encoder` module to every camera's
         # PreTrainedResNetEncoder, flax adopts a shared module once -- under the first camera in sorted-key order --

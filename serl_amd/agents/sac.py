@@ -49,26 +49,9 @@ class SACAgent(DrQAgent):
         reference writes TD3 (utils.init.policy_mode_fixed; create_drq's docstring).
         param_init: "numpy" (default) or "reference" (the reference's own initialisers and keys, utils/init_ref.py)."""
         pk = policy_kwargs or {}
-        # policy_fixed=True: "fixed" / fixed_std are read (actor_critic_nets.py:189-192); else refused, as always
         A = int(np.asarray(actions).shape[-1])
-        std_param, squash, fixed = pinit.policy_mode_fixed(pk, A) if policy_fixed else (*pinit.policy_mode(pk), None)
-        # mlp_shapes=True: each network's own depth and per-layer widths (mlp.py:19-31); else the one width of [h, h], as always
-        dims = pinit.mlp_layer_dims(critic_network_kwargs, policy_network_kwargs, mlp_plain) if mlp_shapes else None
-        hidden = dims[0][0] if mlp_shapes else pinit.mlp_hidden_width(critic_network_kwargs, policy_network_kwargs, mlp_plain)
-        # mlp_plain=True: each network's own use_layer_norm (mlp.py:29-30); else LayerNorm in both, as always
-        lns = pinit.mlp_layer_norms(critic_network_kwargs, policy_network_kwargs) if mlp_plain else (True, True)
-        critic_act, policy_act = pinit.mlp_activations(critic_network_kwargs, policy_network_kwargs, mlp_dropout)
-        critic_drop, policy_drop = pinit.mlp_dropout_rates(critic_network_kwargs, policy_network_kwargs) if mlp_dropout else (0.0, 0.0)
-        if mlp_shapes:
-            pinit.check_shapes_dropout(dims[0], dims[1], critic_drop, policy_drop)
-            if dims[0] == dims[1] and len(dims[0]) == 2 and dims[0][0] == dims[0][1]:
-                dims = None    # [h, h] twice: the very agent the call without the switch makes
-        pinit.check_plain_dropout(*lns, critic_drop, policy_drop)
-        pinit.check_fixed_dropout(fixed, critic_drop, policy_drop)
-        shape_kw = {} if dims is None else {"critic_dims": dims[0], "policy_dims": dims[1]}
-        if lns != (True, True):    # (True, True): the very agent the call without the switch makes
-            shape_kw.update(critic_layer_norm=lns[0], policy_layer_norm=lns[1])
-        core_kw = {} if fixed is None else {"fixed_std": fixed}
+        spec = pinit.network_spec(critic_network_kwargs, policy_network_kwargs, pk, A, mlp_dropout=mlp_dropout, mlp_shapes=mlp_shapes,
+                                  mlp_plain=mlp_plain, policy_fixed=policy_fixed)
         ao = {"learning_rate": 3e-4, "warmup_steps": 2000, **(actor_optimizer_kwargs or {})}     # sac.py:333-336
         co = {"learning_rate": 3e-4, "warmup_steps": 2000, **(critic_optimizer_kwargs or {})}    # sac.py:337-340
         to = {"learning_rate": 3e-4, **(temperature_optimizer_kwargs or {})}                     # sac.py:341-343
@@ -82,25 +65,18 @@ class SACAgent(DrQAgent):
                          temp_warmup_steps=int(to.get("warmup_steps", 0)), std_min=pk.get("std_min", 1e-5),
                          std_max=pk.get("std_max", 10.0), target_entropy=target_entropy, seed=seed,
                          optimizers={"actor": ao, "critic": co, "temperature": {"warmup_steps": 0, **to}},
-                         critic_subsample_size=critic_subsample_size, backup_entropy=backup_entropy, hidden=hidden,
-                         std_parameterization=std_param, tanh_squash_distribution=squash,
-                         critic_activation=critic_act, policy_activation=policy_act,
-                         critic_dropout=critic_drop, policy_dropout=policy_drop, **shape_kw, **core_kw)
+                         critic_subsample_size=critic_subsample_size, backup_entropy=backup_entropy, **spec.core_kwargs())
         if init_ref.check_param_init(param_init):
             theta = init_ref.theta_reference((), 0, 0, S, A, rng, ensemble=critic_ensemble_size, temperature_init=temperature_init,
-                                             device=device, hidden=hidden, std_parameterization=std_param, **shape_kw)
+                                             device=device, **spec.leaf_kwargs())
         else:
             theta = pinit.init_theta(0, 0, 0, S, A, seed=seed, temperature_init=temperature_init, ensemble=critic_ensemble_size,
-                                     hidden=hidden, std_parameterization=std_param, **shape_kw)
+                                     **spec.leaf_kwargs())
         for sec in ("params", "target_params"):
             core.load_flat(sec, theta)
         config = dict(critic_ensemble_size=critic_ensemble_size, critic_subsample_size=critic_subsample_size,
                       discount=discount, soft_target_update_rate=soft_target_update_rate,
-                      target_entropy=target_entropy, backup_entropy=backup_entropy,
-                      critic_activation=critic_act, policy_activation=policy_act,
-                      critic_dropout_rate=critic_drop, policy_dropout_rate=policy_drop,
-                      **({} if fixed is None else {"fixed_std": tuple(float(x) for x in fixed)}),
-                      **({} if lns == (True, True) else {"critic_use_layer_norm": lns[0], "policy_use_layer_norm": lns[1]}))
+                      target_entropy=target_entropy, backup_entropy=backup_entropy, **spec.config_entries())
         agent = cls(core, (), config, seed)
         agent._opts = {"actor": ao, "critic": co, "temperature": {"warmup_steps": 0, **to}}
         if param_init == "reference":

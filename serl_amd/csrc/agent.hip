@@ -79,25 +79,19 @@ struct serl_agent {
   int E = 0, D = 0, HW = 0, XA = 0;  // enc dim, sle dim, feature pixels, E + A
   bool state_only = false;           // n_cam == 0: SACAgent.create_states
   bool small = false;                // encoder_type == "small": trainable SmallEncoder instead of the frozen trunk
-  int std_param = SERL_STD_EXP, no_tanh = 0;   // the arguments of serl_agent_create_policy
-  int pol_mode = kPolExp;            // ... as the head kernels take them
+  // The network options the agent was created with (serl_mi355.h, NETWORK OPTIONS), normalised by create_agent: both networks have
+  // n_layers >= 1 and their dims filled ({cfg.hidden, cfg.hidden} where 0 layers were given: nothing below reads cfg.hidden), and
+  // fixed_std points into the vector below.  act is a kAct* code; no_layer_norm is read by build_layout alone, the layers carry it
+  // from there (DenseLn::ln).
+  serl_agent_opts opts{};
+  int pol_mode = kPolExp;            // opts.std_param / no_tanh as the head kernels take them
   int head_groups = 2;               // Dense layers of the policy head: (mean, log_std), or the mean alone with kPolUniform / kPolFixed
-  // serl_agent_create_fixed_std: the constant std vector of a kPolFixed agent as it was passed, [act_dim]; the device copy is an
+  // SERL_STD_FIXED: the constant std vector of a kPolFixed agent as it was passed, [act_dim]; the device copy is an
   // allocation of its own outside the arena (no leaf, no moments, no target copy, never all-reduced).  Empty / nullptr otherwise.
   std::vector<float> fixed_std;
   float* fixed_std_dev = nullptr;
-  int critic_act = kActTanh, policy_act = kActTanh;   // serl_agent_create_mlp: the activation of each MLP's LayerNorm rows (kAct*)
-  // serl_agent_create_shapes: the hidden widths of the critic's and the policy's MLP; {cfg.hidden, cfg.hidden} twice from every
-  // other entry point.  Nothing below reads cfg.hidden.
-  int critic_dims[kL] = {0, 0, 0, 0}, policy_dims[kL] = {0, 0, 0, 0};
-  int n_critic = 0, n_policy = 0;
-  // serl_agent_create_layer_norm: whether each MLP's layers have their LayerNorm (mlp.py:29-30, use_layer_norm); true from every
-  // other entry point.  Read by build_layout alone: the layers carry it from there (DenseLn::ln).
-  bool critic_ln = true, policy_ln = true;
-  // serl_agent_create_dropout: the rate of the Dropout in front of each MLP's two LayerNorm rows (mlp.py:27-28); 0 = none.
   // mlp_bound: what serl_agent_set_mlp_noise left for the next update / phase / dry-run call; mlp_cur: what the call in progress
   // (mlp_depth > 0: its outermost entry point took the binding) reads.  MlpNoiseScope, below.
-  double critic_drop = 0.0, policy_drop = 0.0;
   serl_mlp_noise mlp_bound{}, mlp_cur{};
   int mlp_depth = 0;
   SmallWorkspace sws{};
@@ -222,11 +216,13 @@ void build_layout(serl_agent* a) {
   std::vector<Leaf>& L = a->theta_leaves;
   const int N = c.ensemble;
   const long A = c.act_dim;
-  const int Hc = a->critic_dims[a->n_critic - 1], Hp = a->policy_dims[a->n_policy - 1];   // the widths the heads read
-  const auto mlp_leaves = [&](DenseLn* layers, const std::string& net, const int* dims, int n, int groups, int in, int act, double drop, bool ln) {
-    for (int j = 0; j < n; ++j) {
+  const serl_mlp_opts &critic = a->opts.critic, &policy = a->opts.policy;
+  const int Hc = critic.dims[critic.n_layers - 1], Hp = policy.dims[policy.n_layers - 1];   // the widths the heads read
+  const auto mlp_leaves = [&](DenseLn* layers, const std::string& name, const serl_mlp_opts& net, int groups, int in) {
+    for (int j = 0; j < net.n_layers; ++j) {
       const std::string k = std::to_string(j + 1);
-      layers[j] = add_dense_ln_leaves(L, off, net + "/w" + k, net + "/b" + k, net + "/ln" + k, groups, j ? dims[j - 1] : in, dims[j], act, drop, ln);
+      layers[j] = add_dense_ln_leaves(L, off, name + "/w" + k, name + "/b" + k, name + "/ln" + k, groups, j ? net.dims[j - 1] : in, net.dims[j],
+                                      net.act, net.dropout, !net.no_layer_norm);
     }
   };
   const CamHeadOffsets ch = add_cam_head_leaves(L, off, c.n_cam, a->D, c.bottleneck, [&](const std::string& p) {
@@ -238,8 +234,8 @@ void build_layout(serl_agent* a) {
     }
   });
   o.enc0 = ch.first; o.cam_stride = ch.stride; o.cam = ch.dense;
-  o.nc = a->n_critic; o.na = a->n_policy;
-  mlp_leaves(o.c, "critic", a->critic_dims, o.nc, N, a->XA, a->critic_act, a->critic_drop, a->critic_ln);
+  o.nc = critic.n_layers; o.na = policy.n_layers;
+  mlp_leaves(o.c, "critic", critic, N, a->XA);
   // DrQ: one Dense(1) head shared by the ensemble (drq.py:201-207); state-only SAC: ensemblize vmaps the whole
   // Critic, so every member has its own head (actor_critic_nets.py:49-73,156-164)
   o.c_hw = add_leaf(L, off, "critic/head/kernel", a->state_only ? N * Hc : Hc);
@@ -250,12 +246,13 @@ void build_layout(serl_agent* a) {
                                  c.proprio_dim, kActTanh);
   }
   o.Pc = off;
-  mlp_leaves(o.a, "actor", a->policy_dims, o.na, 1, a->E, a->policy_act, a->policy_drop, a->policy_ln);
+  mlp_leaves(o.a, "actor", policy, 1, a->E);
   o.a_Wm = add_leaf(L, off, "actor/mean/kernel", Hp * A);
   o.a_bm = add_leaf(L, off, "actor/mean/bias", A);
-  a->pol_mode = a->std_param | (a->no_tanh ? kPolNoTanh : 0);
-  a->head_groups = (a->std_param == SERL_STD_UNIFORM || a->std_param == SERL_STD_FIXED) ? 1 : 2;
-  if (a->std_param == SERL_STD_FIXED) {   // no std parameter at all (actor_critic_nets.py:190-192): the head ends with the mean's bias
+  const int std_param = a->opts.std_param;
+  a->pol_mode = std_param | (a->opts.no_tanh ? kPolNoTanh : 0);
+  a->head_groups = (std_param == SERL_STD_UNIFORM || std_param == SERL_STD_FIXED) ? 1 : 2;
+  if (std_param == SERL_STD_FIXED) {   // no std parameter at all (actor_critic_nets.py:190-192): the head ends with the mean's bias
     o.a_Ws = o.a_bs = -1;
   } else if (a->head_groups == 1) {   // one log-std vector shared by all rows (actor_critic_nets.py:199-201), directly behind the mean's bias
     o.a_Ws = -1;
@@ -281,9 +278,10 @@ size_t carve(serl_agent* a, void* base) {
   const long B = c.batch, N = c.ensemble, A = c.act_dim;
   const Offs& o = a->o;
   // the widest layer of either MLP (shared scratch is sized by it) and the critic's last (the head gradient's width)
-  const long Wc = *std::max_element(a->critic_dims, a->critic_dims + a->n_critic);
-  const long Wp = *std::max_element(a->policy_dims, a->policy_dims + a->n_policy);
-  const long Hc = a->critic_dims[a->n_critic - 1];
+  const serl_mlp_opts &critic = a->opts.critic, &policy = a->opts.policy;
+  const long Wc = *std::max_element(critic.dims, critic.dims + critic.n_layers);
+  const long Wp = *std::max_element(policy.dims, policy.dims + policy.n_layers);
+  const long Hc = critic.dims[critic.n_layers - 1];
   Bump b(base);
   a->trunk = b.take<float>(a->trunk_count);
   a->trunk_t = b.take<float>(a->trunk_count);
@@ -312,22 +310,22 @@ size_t carve(serl_agent* a, void* base) {
   enc(a->encP); enc(a->encT); enc(a->encO);
   float* encP_out = b.take<float>(B * a->E);
   a->encP.enc = encP_out; a->encP.ld = a->E;
-  auto mlp = [&](MlpBuf& m, long rows, const int* dims, int n) {
-    for (int j = 0; j < n; ++j) {
+  auto mlp = [&](MlpBuf& m, long rows, const serl_mlp_opts& net) {
+    for (int j = 0; j < net.n_layers; ++j) {
       LayerBuf* l = &m.l[j];
-      l->h = b.take<float>(rows * dims[j]); l->xhat = b.take<float>(rows * dims[j]); l->rstd = b.take<float>(rows);
+      l->h = b.take<float>(rows * net.dims[j]); l->xhat = b.take<float>(rows * net.dims[j]); l->rstd = b.take<float>(rows);
     }
   };
   auto crit = [&](CritBuf& cb) {
     cb.x = b.take<float>(B * a->XA);
-    mlp(cb.m, N * B, a->critic_dims, a->n_critic);
+    mlp(cb.m, N * B, critic);
     cb.q = b.take<float>(N * B);
   };
   crit(a->critT); crit(a->crit);
   a->encT.enc = a->critT.x; a->encT.ld = a->XA;
   a->encO.enc = a->crit.x; a->encO.ld = a->XA;
   for (PolBuf* pbuf : {&a->pol, &a->polT}) {
-    mlp(pbuf->m, B, a->policy_dims, a->n_policy);
+    mlp(pbuf->m, B, policy);
     pbuf->pre = b.take<float>(2 * B * A); pbuf->std = b.take<float>(B * A); pbuf->logp = b.take<float>(B);
   }
   // (fused epilogues keep whole 64x64 slab tiles: rows and columns padded to 64).  The terms, in order: the camera heads' K-split
@@ -341,8 +339,8 @@ size_t carve(serl_agent* a, void* base) {
   for (int k = 0; k < 3; ++k) a->slabs_lane[k] = b.take<float>(cap);
   a->slabs = a->slabs_lane[0];
   a->dq = b.take<float>(N * B); a->ytgt = b.take<float>(B);
-  for (int j = std::max(a->n_critic, a->n_policy) - 1; j >= 0; --j) {   // layer j's scratch holds the critic's layer j or the policy's, whichever is larger
-    const long n = std::max<long>(j < a->n_critic ? N * B * a->critic_dims[j] : 0, j < a->n_policy ? B * a->policy_dims[j] : 0);
+  for (int j = std::max(critic.n_layers, policy.n_layers) - 1; j >= 0; --j) {   // layer j's scratch holds the critic's layer j or the policy's, whichever is larger
+    const long n = std::max<long>(j < critic.n_layers ? N * B * critic.dims[j] : 0, j < policy.n_layers ? B * policy.dims[j] : 0);
     GradBuf* s = &a->s[j];
     s->dy = b.take<float>(n); s->dpre = b.take<float>(n); s->dg = b.take<float>(n);
   }
@@ -726,7 +724,7 @@ int critic_loss_or_rider(serl_agent* a, const LossArgs& L, hipStream_t st, const
 // the mean's bias: the same two column sums.  kPolFixed: dpre has no second slab and the std no leaf: the mean's sum alone.)
 int head_bias_grad(serl_agent* a, int cnt, float* out, long out_gstride, hipStream_t st) {
   const int A = a->cfg.act_dim;
-  const int groups = a->std_param == SERL_STD_FIXED ? 1 : 2;
+  const int groups = a->opts.std_param == SERL_STD_FIXED ? 1 : 2;
   if (!a->fuse) return colsum(a->dpre, nullptr, groups, cnt, A, out, out_gstride, false, st);
   SERL_REQUIRE(a->pg_ncs < kMaxColsum, "no room for the head-bias gradient job");
   a->pg_cs[a->pg_ncs++] = Colsum3Args{a->dpre, nullptr, nullptr, groups, cnt, A, nullptr, out, nullptr, out_gstride, 1};
@@ -892,8 +890,9 @@ void mlp_sites(serl_agent* a, int site, double rate, int off, int cnt, long glob
   if (!(rate > 0.0)) return;
   const serl_mlp_noise& z = a->mlp_cur;
   const bool critic = site == SERL_SITE_Q_TARGET || site == SERL_SITE_Q_ONLINE || site == SERL_SITE_Q_ACTOR;
-  const int* dims = critic ? a->critic_dims : a->policy_dims;
-  const int n = critic ? a->n_critic : a->n_policy;
+  const serl_mlp_opts& net = critic ? a->opts.critic : a->opts.policy;
+  const int* dims = net.dims;
+  const int n = net.n_layers;
   long below = 0;   // mask elements per batch row of the layers in front of layer l
   for (int l = 0; l < n; below += dims[l], ++l) {
     DenseLnDrop& d = out[l];
@@ -940,118 +939,144 @@ float lr_at(const serl_agent_cfg& c, int64_t count, int tx) {
 
 extern "C" {
 
+static int create_agent(const serl_agent_cfg* cfg, const serl_agent_opts* opts, serl_agent** out);
+
+int serl_agent_create_opts(const serl_agent_cfg* cfg, const serl_agent_opts* opts, serl_agent** out) {
+  SERL_REQUIRE(cfg && opts && out, "NULL argument");
+  return create_agent(cfg, opts, out);
+}
+
+// The entry points from before serl_agent_opts: each states its argument list as opts, the fields it has no argument for left 0.
+// SERL_STD_FIXED came with serl_agent_create_fixed_std: the older ones keep refusing it, in the words they always used.
+static int three_std_params(int std_param) {
+  SERL_REQUIRE(std_param >= SERL_STD_EXP && std_param <= SERL_STD_UNIFORM,
+               "std_param %d is not SERL_STD_EXP (0), SERL_STD_SOFTPLUS (1) or SERL_STD_UNIFORM (2)", std_param);
+  return SERL_OK;
+}
+
 int serl_agent_create(const serl_agent_cfg* cfg, serl_agent** out) { return serl_agent_create_policy(cfg, SERL_STD_EXP, 0, out); }
 
 int serl_agent_create_policy(const serl_agent_cfg* cfg, int std_param, int no_tanh, serl_agent** out) {
   return serl_agent_create_mlp(cfg, std_param, no_tanh, SERL_ACT_TANH, SERL_ACT_TANH, out);
 }
 
-// mlp.py:19-31: MLP applies `activations` (a callable, or the name of one in flax.linen) behind every LayerNorm; the critic and the
-// policy get theirs from two separate kwargs dicts, so the two codes are independent.
-// (= serl_agent_create_shapes with {hidden, hidden} twice: both reach create_agent with those lists and no Dropout)
 int serl_agent_create_mlp(const serl_agent_cfg* cfg, int std_param, int no_tanh, int critic_act, int policy_act, serl_agent** out) {
   return serl_agent_create_dropout(cfg, std_param, no_tanh, critic_act, policy_act, 0.0, 0.0, out);
 }
 
-static int create_agent(const serl_agent_cfg* cfg, int std_param, int no_tanh, int critic_act, int policy_act, double critic_dropout,
-                        double policy_dropout, const int* critic_dims, int n_critic, const int* policy_dims, int n_policy, bool shapes,
-                        int critic_layer_norm, int policy_layer_norm, serl_agent** out, const float* fixed_std = nullptr,
-                        bool fixed_abi = false);
+int serl_agent_create_dropout(const serl_agent_cfg* cfg, int std_param, int no_tanh, int critic_act, int policy_act, double critic_dropout,
+                              double policy_dropout, serl_agent** out) {
+  SERL_REQUIRE(cfg && out, "NULL argument");
+  if (int rc = three_std_params(std_param)) return rc;
+  serl_agent_opts o{};
+  o.std_param = std_param; o.no_tanh = no_tanh;
+  o.critic.act = critic_act; o.policy.act = policy_act;
+  o.critic.dropout = critic_dropout; o.policy.dropout = policy_dropout;
+  return create_agent(cfg, &o, out);
+}
 
-// mlp.py:19-31: MLP loops over hidden_dims of any length; sac.py:516-524, drq.py:188-207: the critic and the policy are built
-// from separate kwargs, so the two lists are independent.  The heads follow the last width of their network.
-// (= serl_agent_create_layer_norm with (1, 1))
 int serl_agent_create_shapes(const serl_agent_cfg* cfg, int std_param, int no_tanh, int critic_act, int policy_act,
                              const int* critic_dims, int n_critic, const int* policy_dims, int n_policy, serl_agent** out) {
   return serl_agent_create_layer_norm(cfg, std_param, no_tanh, critic_act, policy_act, critic_dims, n_critic, policy_dims, n_policy, 1, 1, out);
 }
 
-// mlp.py:29-30: `if self.use_layer_norm: x = nn.LayerNorm()(x)` in every hidden layer; sac.py:516-524, drq.py:188-207: the critic
-// and the policy are built from separate kwargs, so the two flags are independent.  A layer without it is y = act(Dense(x) + b)
-// with the leaves w<j> and b<j> alone.  The encoder's bottleneck and proprio layers keep theirs (resnet_v1.py:371-374, encoding.py:66-68).
 int serl_agent_create_layer_norm(const serl_agent_cfg* cfg, int std_param, int no_tanh, int critic_act, int policy_act,
                                  const int* critic_dims, int n_critic, const int* policy_dims, int n_policy, int critic_layer_norm,
                                  int policy_layer_norm, serl_agent** out) {
-  SERL_REQUIRE(cfg && out, "NULL argument");
-  SERL_REQUIRE(critic_dims && policy_dims, "%s is NULL: the hidden widths of the %s's MLP, 1 to %d of them",
-               critic_dims ? "policy_dims" : "critic_dims", critic_dims ? "policy" : "critic", SERL_MAX_MLP_LAYERS);
-  return create_agent(cfg, std_param, no_tanh, critic_act, policy_act, 0.0, 0.0, critic_dims, n_critic, policy_dims, n_policy, true,
-                      critic_layer_norm, policy_layer_norm, out);
+  if (int rc = three_std_params(std_param)) return rc;
+  return serl_agent_create_fixed_std(cfg, std_param, no_tanh, critic_act, policy_act, critic_dims, n_critic, policy_dims, n_policy,
+                                     critic_layer_norm, policy_layer_norm, nullptr, out);
 }
 
-// mlp.py:29-30: whether the layers of an agent's critic (network 0) or policy (1) MLP have their LayerNorm
-// actor_critic_nets.py:189-192,212: `fixed_std` -- stds = clip(fixed_std, std_min, std_max), no Dense_1 and no log_stds.
-// serl_agent_create_layer_norm is this function with NULL (its own range check keeps refusing SERL_STD_FIXED).
 int serl_agent_create_fixed_std(const serl_agent_cfg* cfg, int std_param, int no_tanh, int critic_act, int policy_act,
                                 const int* critic_dims, int n_critic, const int* policy_dims, int n_policy, int critic_layer_norm,
                                 int policy_layer_norm, const float* fixed_std, serl_agent** out) {
   SERL_REQUIRE(cfg && out, "NULL argument");
   SERL_REQUIRE(critic_dims && policy_dims, "%s is NULL: the hidden widths of the %s's MLP, 1 to %d of them",
                critic_dims ? "policy_dims" : "critic_dims", critic_dims ? "policy" : "critic", SERL_MAX_MLP_LAYERS);
-  return create_agent(cfg, std_param, no_tanh, critic_act, policy_act, 0.0, 0.0, critic_dims, n_critic, policy_dims, n_policy, true,
-                      critic_layer_norm, policy_layer_norm, out, fixed_std, true);
+  SERL_REQUIRE(critic_layer_norm == 0 || critic_layer_norm == 1, "critic_layer_norm %d is not 0 (no LayerNorm) or 1", critic_layer_norm);
+  SERL_REQUIRE(policy_layer_norm == 0 || policy_layer_norm == 1, "policy_layer_norm %d is not 0 (no LayerNorm) or 1", policy_layer_norm);
+  serl_agent_opts o{};
+  o.std_param = std_param; o.no_tanh = no_tanh;
+  o.critic.act = critic_act; o.policy.act = policy_act;
+  o.fixed_std = fixed_std;
+  for (int k = 0; k < 2; ++k) {
+    serl_mlp_opts& net = k ? o.policy : o.critic;
+    const int n = k ? n_policy : n_critic;
+    // checked HERE, before anything is copied into dims[]; a caller's 0 is refused as 0 layers, it never becomes "use cfg->hidden"
+    SERL_REQUIRE(n >= 1 && n <= SERL_MAX_MLP_LAYERS, "%s MLP: %d hidden layers (served: 1 to %d layers, each a multiple of 64 in [64, 1024] wide)",
+                 k ? "policy" : "critic", n, SERL_MAX_MLP_LAYERS);
+    net.n_layers = n;
+    std::copy_n(k ? policy_dims : critic_dims, n, net.dims);
+    net.no_layer_norm = !(k ? policy_layer_norm : critic_layer_norm);
+  }
+  return create_agent(cfg, &o, out);
 }
 
-// the vector serl_agent_create_fixed_std was given (before the clip)
+// the vector the agent was given with SERL_STD_FIXED (before the clip)
 int serl_agent_fixed_std(serl_agent* a, float* out) {
   SERL_REQUIRE(a && out, "NULL argument");
-  SERL_REQUIRE(a->std_param == SERL_STD_FIXED, "the agent's std parameterisation is %d, not SERL_STD_FIXED (3): it has no fixed_std", a->std_param);
-  for (size_t j = 0; j < a->fixed_std.size(); ++j) out[j] = a->fixed_std[j];
+  SERL_REQUIRE(a->opts.std_param == SERL_STD_FIXED, "the agent's std parameterisation is %d, not SERL_STD_FIXED (3): it has no fixed_std", a->opts.std_param);
+  std::copy(a->fixed_std.begin(), a->fixed_std.end(), out);
   return SERL_OK;
 }
 
+// mlp.py:29-30: whether the layers of an agent's critic (network 0) or policy (1) MLP have their LayerNorm
 int serl_agent_mlp_layer_norm(serl_agent* a, int network) {
   if (!a || (network != 0 && network != 1)) return -1;
-  return (network ? a->policy_ln : a->critic_ln) ? 1 : 0;
+  return (network ? a->opts.policy : a->opts.critic).no_layer_norm ? 0 : 1;
 }
 
 // mlp.py:19-31; sac.py:516-524, drq.py:188-207: the hidden widths an agent was created with
 int serl_agent_mlp_dims(serl_agent* a, int network, int dims[SERL_MAX_MLP_LAYERS]) {
   if (!a || !dims || (network != 0 && network != 1)) return -1;
-  const int n = network ? a->n_policy : a->n_critic;
-  for (int j = 0; j < n; ++j) dims[j] = (network ? a->policy_dims : a->critic_dims)[j];
-  return n;
+  const serl_mlp_opts& net = network ? a->opts.policy : a->opts.critic;
+  std::copy_n(net.dims, net.n_layers, dims);
+  return net.n_layers;
 }
 
-// mlp.py:27-28: Dense -> Dropout(dropout_rate) -> LayerNorm -> activation in both hidden layers of each MLP, the rate from the
-// network's own kwargs dict; sac.py:137-176,197-207: every loss runs its forwards with train=True.
-int serl_agent_create_dropout(const serl_agent_cfg* cfg, int std_param, int no_tanh, int critic_act, int policy_act, double critic_dropout,
-                              double policy_dropout, serl_agent** out) {
-  SERL_REQUIRE(cfg && out, "NULL argument");
-  const int dims[2] = {cfg->hidden, cfg->hidden};
-  return create_agent(cfg, std_param, no_tanh, critic_act, policy_act, critic_dropout, policy_dropout, dims, 2, dims, 2, false, 1, 1, out);
-}
-
-// every entry point's agent.  `shapes`: the lists are the caller's (serl_agent_create_shapes) and are checked one by one; else
-// they repeat cfg->hidden, which is checked as it always was.
-static int create_agent(const serl_agent_cfg* cfg, int std_param, int no_tanh, int critic_act, int policy_act, double critic_dropout,
-                        double policy_dropout, const int* critic_dims, int n_critic, const int* policy_dims, int n_policy, bool shapes,
-                        int critic_layer_norm, int policy_layer_norm, serl_agent** out, const float* fixed_std, bool fixed_abi) {
-  SERL_REQUIRE(critic_layer_norm == 0 || critic_layer_norm == 1, "critic_layer_norm %d is not 0 (no LayerNorm) or 1", critic_layer_norm);
-  SERL_REQUIRE(policy_layer_norm == 0 || policy_layer_norm == 1, "policy_layer_norm %d is not 0 (no LayerNorm) or 1", policy_layer_norm);
-  SERL_REQUIRE((critic_layer_norm || !(critic_dropout > 0.0)) && (policy_layer_norm || !(policy_dropout > 0.0)),
+// Every entry point's agent (serl_mi355.h, NETWORK OPTIONS).  The two networks are built from separate kwargs (sac.py:516-524,
+// drq.py:188-207), so their options are independent: mlp.py:19-31 applies `activations` behind every layer and loops over
+// hidden_dims of any length, :27-28 puts Dropout in front of the LayerNorm, :29-30 makes the LayerNorm optional;
+// actor_critic_nets.py:189-192,212: with fixed_std, stds = clip(fixed_std, std_min, std_max), no Dense_1 and no log_stds.
+static int create_agent(const serl_agent_cfg* cfg, const serl_agent_opts* opts, serl_agent** out) {
+  const serl_mlp_opts &critic = opts->critic, &policy = opts->policy;
+  const int std_param = opts->std_param;
+  const float* fixed_std = opts->fixed_std;
+  SERL_REQUIRE(critic.no_layer_norm == 0 || critic.no_layer_norm == 1, "critic no_layer_norm %d is not 0 (LayerNorm) or 1 (none)", critic.no_layer_norm);
+  SERL_REQUIRE(policy.no_layer_norm == 0 || policy.no_layer_norm == 1, "policy no_layer_norm %d is not 0 (LayerNorm) or 1 (none)", policy.no_layer_norm);
+  SERL_REQUIRE((!critic.no_layer_norm || !(critic.dropout > 0.0)) && (!policy.no_layer_norm || !(policy.dropout > 0.0)),
                "Dropout in an MLP without LayerNorm is not served");
   // (the keep probability float32(1 - rate) must itself lie below 1 and above 0)
-  SERL_REQUIRE(critic_dropout >= 0.0 && (float)(1.0 - critic_dropout) > 0.f, "critic_dropout %g: a Dropout rate lies in [0, 1)", critic_dropout);
-  SERL_REQUIRE(policy_dropout >= 0.0 && (float)(1.0 - policy_dropout) > 0.f, "policy_dropout %g: a Dropout rate lies in [0, 1)", policy_dropout);
+  SERL_REQUIRE(critic.dropout >= 0.0 && (float)(1.0 - critic.dropout) > 0.f, "critic_dropout %g: a Dropout rate lies in [0, 1)", critic.dropout);
+  SERL_REQUIRE(policy.dropout >= 0.0 && (float)(1.0 - policy.dropout) > 0.f, "policy_dropout %g: a Dropout rate lies in [0, 1)", policy.dropout);
+  // what the argument lists could not say and opts can: Dropout is served where it always was
+  if (critic.dropout > 0.0 || policy.dropout > 0.0) {
+    // (the keep-masks and per-layer keys of serl_mlp_noise are laid out for two layers of cfg->hidden)
+    SERL_REQUIRE(critic.n_layers == 0 && policy.n_layers == 0, "dropout %g / %g with n_layers %d / %d (critic / policy): Dropout is served with "
+                 "n_layers 0 in both networks, two layers of cfg->hidden", critic.dropout, policy.dropout, critic.n_layers, policy.n_layers);
+    SERL_REQUIRE(!critic.no_layer_norm && !policy.no_layer_norm, "dropout %g / %g with no_layer_norm %d / %d (critic / policy): Dropout is "
+                 "served in agents whose two networks have their LayerNorm", critic.dropout, policy.dropout, critic.no_layer_norm, policy.no_layer_norm);
+    SERL_REQUIRE(std_param != SERL_STD_FIXED, "dropout %g / %g (critic / policy) with std_param SERL_STD_FIXED (3): Dropout is served in "
+                 "agents whose policy head has std leaves", critic.dropout, policy.dropout);
+  }
   SERL_REQUIRE(cfg->n_cam >= 0 && cfg->n_cam <= SERL_MAX_CAMS, "n_cam %d not in [0,%d]", cfg->n_cam, SERL_MAX_CAMS);
   SERL_REQUIRE(cfg->n_cam == 0 || (cfg->H >= 32 && cfg->W >= 32), "images must be at least 32x32");
   SERL_REQUIRE(cfg->encoder_type == SERL_ENCODER_RESNET_PRETRAINED || cfg->encoder_type == SERL_ENCODER_SMALL,
                "Unknown encoder type: %d", cfg->encoder_type);
   SERL_REQUIRE(cfg->n_cam > 0 || cfg->ensemble <= 16, "state-only SAC supports ensembles of at most 16");
   // one wave owns a LayerNorm row and a lane holds hidden / 64 of its columns, 16 at the most (heads.hip)
-  if (!shapes)
+  if (critic.n_layers == 0 || policy.n_layers == 0)
     SERL_REQUIRE(cfg->hidden >= 64 && cfg->hidden <= 1024 && cfg->hidden % 64 == 0,
                  "hidden must be a multiple of 64 in [64, 1024] (got %d): the width of the critic's and the policy's two MLP layers", cfg->hidden);
-  for (int net = 0; net < 2 && shapes; ++net) {
-    const int* dims = net ? policy_dims : critic_dims;
-    const int n = net ? n_policy : n_critic;
-    const char* name = net ? "policy" : "critic";
-    SERL_REQUIRE(n >= 1 && n <= SERL_MAX_MLP_LAYERS, "%s MLP: %d hidden layers (served: 1 to %d layers, each a multiple of 64 in [64, 1024] wide)",
-                 name, n, SERL_MAX_MLP_LAYERS);
-    for (int j = 0; j < n; ++j)
-      SERL_REQUIRE(dims[j] >= 64 && dims[j] <= 1024 && dims[j] % 64 == 0,
-                   "%s MLP: layer %d has width %d (served: 1 to %d layers, each a multiple of 64 in [64, 1024] wide)", name, j + 1, dims[j],
+  for (const serl_mlp_opts* net : {&critic, &policy}) {
+    if (net->n_layers == 0) continue;   // two layers of cfg->hidden, checked above
+    const char* name = net == &critic ? "critic" : "policy";
+    SERL_REQUIRE(net->n_layers >= 1 && net->n_layers <= SERL_MAX_MLP_LAYERS,
+                 "%s MLP: %d hidden layers (served: 1 to %d layers, each a multiple of 64 in [64, 1024] wide)", name, net->n_layers, SERL_MAX_MLP_LAYERS);
+    for (int j = 0; j < net->n_layers; ++j)
+      SERL_REQUIRE(net->dims[j] >= 64 && net->dims[j] <= 1024 && net->dims[j] % 64 == 0,
+                   "%s MLP: layer %d has width %d (served: 1 to %d layers, each a multiple of 64 in [64, 1024] wide)", name, j + 1, net->dims[j],
                    SERL_MAX_MLP_LAYERS);
   }
   SERL_REQUIRE(cfg->bottleneck == 256, "bottleneck must be 256 (got %d): the reference fixes bottleneck_dim=256 in create_drq", cfg->bottleneck);
@@ -1066,20 +1091,15 @@ static int create_agent(const serl_agent_cfg* cfg, int std_param, int no_tanh, i
     return SERL_ERR_UNSUPPORTED;
   }
   SERL_REQUIRE(num_stack == 1 || cfg->n_cam > 0, "num_stack %d on a state-only agent: its state path has no stacking wrapper", num_stack);
-  if (!fixed_abi) {
-    SERL_REQUIRE(std_param >= SERL_STD_EXP && std_param <= SERL_STD_UNIFORM,
-                 "std_param %d is not SERL_STD_EXP (0), SERL_STD_SOFTPLUS (1) or SERL_STD_UNIFORM (2)", std_param);
-  } else {
-    SERL_REQUIRE(std_param >= SERL_STD_EXP && std_param <= SERL_STD_FIXED,
-                 "std_param %d is not SERL_STD_EXP (0), SERL_STD_SOFTPLUS (1), SERL_STD_UNIFORM (2) or SERL_STD_FIXED (3)", std_param);
-    SERL_REQUIRE(std_param != SERL_STD_FIXED || fixed_std, "std_param SERL_STD_FIXED (3) needs fixed_std: act_dim floats, got NULL");
-    SERL_REQUIRE(std_param == SERL_STD_FIXED || !fixed_std, "fixed_std is given with std_param %d: it goes with SERL_STD_FIXED (3) alone", std_param);
-    for (int j = 0; fixed_std && j < cfg->act_dim; ++j)
-      SERL_REQUIRE(std::isfinite(fixed_std[j]) && fixed_std[j] > 0.f, "fixed_std[%d] = %g is not a finite positive number", j, (double)fixed_std[j]);
-  }
-  SERL_REQUIRE(no_tanh == 0 || no_tanh == 1, "no_tanh %d is not 0 (tanh-squashed) or 1 (plain Gaussian)", no_tanh);
-  SERL_REQUIRE(critic_act >= 0 && critic_act < kActCount, "critic_act %d: served are SERL_ACT_TANH (0), SERL_ACT_RELU (1) and SERL_ACT_SWISH (2)", critic_act);
-  SERL_REQUIRE(policy_act >= 0 && policy_act < kActCount, "policy_act %d: served are SERL_ACT_TANH (0), SERL_ACT_RELU (1) and SERL_ACT_SWISH (2)", policy_act);
+  SERL_REQUIRE(std_param >= SERL_STD_EXP && std_param <= SERL_STD_FIXED,
+               "std_param %d is not SERL_STD_EXP (0), SERL_STD_SOFTPLUS (1), SERL_STD_UNIFORM (2) or SERL_STD_FIXED (3)", std_param);
+  SERL_REQUIRE(std_param != SERL_STD_FIXED || fixed_std, "std_param SERL_STD_FIXED (3) needs fixed_std: act_dim floats, got NULL");
+  SERL_REQUIRE(std_param == SERL_STD_FIXED || !fixed_std, "fixed_std is given with std_param %d: it goes with SERL_STD_FIXED (3) alone", std_param);
+  for (int j = 0; fixed_std && j < cfg->act_dim; ++j)
+    SERL_REQUIRE(std::isfinite(fixed_std[j]) && fixed_std[j] > 0.f, "fixed_std[%d] = %g is not a finite positive number", j, (double)fixed_std[j]);
+  SERL_REQUIRE(opts->no_tanh == 0 || opts->no_tanh == 1, "no_tanh %d is not 0 (tanh-squashed) or 1 (plain Gaussian)", opts->no_tanh);
+  SERL_REQUIRE(critic.act >= 0 && critic.act < kActCount, "critic_act %d: served are SERL_ACT_TANH (0), SERL_ACT_RELU (1) and SERL_ACT_SWISH (2)", critic.act);
+  SERL_REQUIRE(policy.act >= 0 && policy.act < kActCount, "policy_act %d: served are SERL_ACT_TANH (0), SERL_ACT_RELU (1) and SERL_ACT_SWISH (2)", policy.act);
   SERL_REQUIRE(cfg->state_dim % num_stack == 0, "state_dim %d is not num_stack %d proprio vectors (state_dim is the flattened width T * S)",
                cfg->state_dim, num_stack);
   bool any_wd = false;
@@ -1095,13 +1115,13 @@ static int create_agent(const serl_agent_cfg* cfg, int std_param, int no_tanh, i
   serl_agent* a = new serl_agent();
   a->cfg = *cfg;
   a->cfg.num_stack = num_stack;
-  a->std_param = std_param; a->no_tanh = no_tanh;
-  a->critic_act = critic_act; a->policy_act = policy_act;
-  a->critic_drop = critic_dropout; a->policy_drop = policy_dropout;
-  a->n_critic = n_critic; a->n_policy = n_policy;
-  a->critic_ln = critic_layer_norm != 0; a->policy_ln = policy_layer_norm != 0;
-  for (int j = 0; j < n_critic; ++j) a->critic_dims[j] = critic_dims[j];
-  for (int j = 0; j < n_policy; ++j) a->policy_dims[j] = policy_dims[j];
+  a->opts = *opts;
+  for (serl_mlp_opts* net : {&a->opts.critic, &a->opts.policy}) {
+    if (net->n_layers == 0) { net->n_layers = 2; net->dims[0] = net->dims[1] = cfg->hidden; }
+    std::fill(net->dims + net->n_layers, net->dims + kL, 0);
+  }
+  if (fixed_std) a->fixed_std.assign(fixed_std, fixed_std + cfg->act_dim);
+  a->opts.fixed_std = fixed_std ? a->fixed_std.data() : nullptr;   // the caller's pointer is not kept
   { const char* e = getenv("SERL_CHAIN_FUSE"); a->fuse = !(e && e[0] == '0'); }
   build_layout(a);
   a->live = any_wd && a->trunk_count > 0;
@@ -1111,7 +1131,6 @@ static int create_agent(const serl_agent_cfg* cfg, int std_param, int no_tanh, i
   }
   carve(a, a->arena);
   if (fixed_std) {   // a constant of the agent, outside the arena: nothing that walks the parameters meets it
-    a->fixed_std.assign(fixed_std, fixed_std + cfg->act_dim);
     hipError_t e = hipMalloc(reinterpret_cast<void**>(&a->fixed_std_dev), sizeof(float) * cfg->act_dim);
     if (e == hipSuccess) e = hipMemcpy(a->fixed_std_dev, fixed_std, sizeof(float) * cfg->act_dim, hipMemcpyHostToDevice);
     if (e != hipSuccess) {
@@ -1585,9 +1604,9 @@ int serl_agent_critic_grads_bucketed(serl_agent* a, int off, int cnt, int global
   set_noise(a, ej[0], pj, nz, off, cnt, global_count);
   // the MLPs' Dropout in the reference's draw order (sac.py:137-176): policy at next_obs, target critic, online critic
   CritJob cj[2] = {{a->theta_t, &a->critT, {}}, {a->theta, &a->crit, {}}};  // target and online ensembles together
-  mlp_sites(a, SERL_SITE_PI_NEXT, a->policy_drop, off, cnt, global_count, redq_row, pj.drop);
-  mlp_sites(a, SERL_SITE_Q_TARGET, a->critic_drop, off, cnt, global_count, redq_row, cj[0].drop);
-  mlp_sites(a, SERL_SITE_Q_ONLINE, a->critic_drop, off, cnt, global_count, redq_row, cj[1].drop);
+  mlp_sites(a, SERL_SITE_PI_NEXT, a->opts.policy.dropout, off, cnt, global_count, redq_row, pj.drop);
+  mlp_sites(a, SERL_SITE_Q_TARGET, a->opts.critic.dropout, off, cnt, global_count, redq_row, cj[0].drop);
+  mlp_sites(a, SERL_SITE_Q_ONLINE, a->opts.critic.dropout, off, cnt, global_count, redq_row, cj[1].drop);
   RC(encode_multi(a, ej, 3, off, cnt, st));
   RC(policy_fwd_multi(a, &pj, 1, cnt, st));
   RC(critic_fwd_multi(a, cj, 2, cnt, st));
@@ -1633,9 +1652,9 @@ int serl_agent_actor_grads(serl_agent* a, int global_count, const serl_noise* no
   set_noise(a, ej[2], pj[1], nz[PI], 0, cnt, global_count);
   // the MLPs' Dropout (sac.py:197-207,222-227): policy at obs, the critic inside the actor loss, policy at next_obs
   CritJob cj{a->theta, &a->crit, {}};
-  mlp_sites(a, SERL_SITE_PI, a->policy_drop, 0, cnt, global_count, 0, pj[1].drop);
-  mlp_sites(a, SERL_SITE_Q_ACTOR, a->critic_drop, 0, cnt, global_count, 0, cj.drop);
-  mlp_sites(a, SERL_SITE_PI_TEMP, a->policy_drop, 0, cnt, global_count, 0, pj[0].drop);
+  mlp_sites(a, SERL_SITE_PI, a->opts.policy.dropout, 0, cnt, global_count, 0, pj[1].drop);
+  mlp_sites(a, SERL_SITE_Q_ACTOR, a->opts.critic.dropout, 0, cnt, global_count, 0, cj.drop);
+  mlp_sites(a, SERL_SITE_PI_TEMP, a->opts.policy.dropout, 0, cnt, global_count, 0, pj[0].drop);
   RC(encode_multi(a, ej, 3, 0, cnt, st));
   RC(policy_fwd_multi(a, pj, 2, cnt, st));
   const float* eps_pi = nz[PI].eps ? nz[PI].eps : nz[PI].eps_out;   // (the backward reads the draws the head used)
@@ -2014,14 +2033,16 @@ int serl_agent_debug_get(serl_agent* a, const char* what, float* host_out, int64
     const std::string buf = w.substr(9, 5);
     const MlpBuf* m = buf == "pol__" ? &a->pol.m : buf == "polT_" ? &a->polT.m : buf == "crit_" ? &a->crit.m : buf == "critT" ? &a->critT.m : nullptr;
     const int l = w[15] - '1';
-    if (!m || l >= (buf[0] == 'c' ? a->n_critic : a->n_policy)) { set_error("unknown debug tap '%s'", what); return SERL_ERR_INVALID; }
+    const serl_mlp_opts& net = buf[0] == 'c' ? a->opts.critic : a->opts.policy;
+    if (!m || l >= net.n_layers) { set_error("unknown debug tap '%s'", what); return SERL_ERR_INVALID; }
     p = m->l[l].xhat;
-    n = (long)(buf[0] == 'c' ? c.ensemble : 1) * c.batch * (buf[0] == 'c' ? a->critic_dims : a->policy_dims)[l];
+    n = (long)(buf[0] == 'c' ? c.ensemble : 1) * c.batch * net.dims[l];
   }
-  else if (w.rfind("mlp_dpre/", 0) == 0 && w.size() == 10 && w[9] >= '1' && w[9] - '1' < std::max(a->n_critic, a->n_policy)) {
+  else if (w.rfind("mlp_dpre/", 0) == 0 && w.size() == 10 && w[9] >= '1' && w[9] - '1' < std::max(a->opts.critic.n_layers, a->opts.policy.n_layers)) {
+    const serl_mlp_opts &critic = a->opts.critic, &policy = a->opts.policy;
     const int l = w[9] - '1';
     p = a->s[l].dpre;
-    n = std::max<long>(l < a->n_critic ? (long)c.ensemble * c.batch * a->critic_dims[l] : 0, l < a->n_policy ? (long)c.batch * a->policy_dims[l] : 0);
+    n = std::max<long>(l < critic.n_layers ? (long)c.ensemble * c.batch * critic.dims[l] : 0, l < policy.n_layers ? (long)c.batch * policy.dims[l] : 0);
   }
   // SmallEncoder layer 0's ReLU output of the LAST encoder pass, [n_cam][images of that pass][h1][w1][32]
   else if (w == "small_act0" && a->small) { p = a->sws.act[0]; n = (long)c.n_cam * c.batch * a->sws.d.h[1] * a->sws.d.w[1] * kSmallFeat[1]; }

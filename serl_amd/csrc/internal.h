@@ -141,11 +141,11 @@ struct LnFwdArgs {
 };
 // The activation behind a LayerNorm row (mlp.py:19-31: `activations`, a callable or the name of one in flax.linen).  tanh: the MLPs
 // as utils/launcher.py configures them, and always the encoder heads; ReLU: also the BinaryClassifier (reward_classifier.py:24-26);
-// swish = silu: x * sigmoid(x), mlp.py's own default.  The values are serl_agent_create_mlp's critic_act / policy_act.
+// swish = silu: x * sigmoid(x), mlp.py's own default.  The values are serl_mlp_opts' act.
 enum { kActTanh = 0, kActRelu = 1, kActSwish = 2, kActCount = 3 };
-// The policy distribution of an agent (serl_agent_create_policy's std_param / no_tanh) as the head kernels take it, a template parameter:
+// The policy distribution of an agent (serl_agent_opts' std_param / no_tanh) as the head kernels take it, a template parameter:
 // the std parameterisation in the low bits, kPolNoTanh on top.  kPolExp (0) is the tanh-Gaussian with std = exp(log_std).
-// kPolFixed (serl_agent_create_fixed_std): the head has no std parameter; std = clip(fixed_std) of a constant vector.
+// kPolFixed (SERL_STD_FIXED): the head has no std parameter; std = clip(fixed_std) of a constant vector.
 enum { kPolExp = 0, kPolSoftplus = 1, kPolUniform = 2, kPolFixed = 3, kPolStdMask = 3, kPolNoTanh = 4 };
 // tanh-Gaussian policy head: slabs = raw head GEMM outputs (mean, log_std); biases added here, result kept in `pre`
 struct PolicyDistArgs {

@@ -21,7 +21,7 @@ import msgpack
 import numpy as np
 
 from ..agents.core import TX_NAMES
-from ..agents.flax_tree import layer_norms_of, leaves_from_tree, mlp_dims_of, std_parameterization_of, theta_paths, trunk_owner, _trunk_paths
+from ..agents.flax_tree import leaves_from_tree, net_spec_of, theta_paths, trunk_owner, _trunk_paths
 
 _EXT_NDARRAY = 1
 
@@ -160,10 +160,10 @@ def load_state_dict(agent, sd: dict, restore_rng: bool = False):
         return agent
     core, keys = agent.core, agent.image_keys
     etype = "small" if core.cfg.encoder_type == 1 else "resnet-pretrained"
-    cd, pd = mlp_dims_of(core)
-    lns = dict(zip(("critic", "actor"), layer_norms_of(core)))
-    tp = theta_paths(keys, encoder_type=etype, std_parameterization=std_parameterization_of(core), critic_dims=cd, policy_dims=pd,
-                     critic_layer_norm=lns["critic"], policy_layer_norm=lns["actor"])
+    spec = net_spec_of(core)
+    cd, pd = spec.dims
+    lns = {"critic": spec.critic_layer_norm, "actor": spec.policy_layer_norm}
+    tp = theta_paths(keys, encoder_type=etype, **spec.leaf_kwargs())
     # the leaves whose PRESENCE is geometry: the policy's std leaves (std_parameterization "uniform": log_stds, else Dense_1) and
     # the MLPs' layers (hidden_dims of any length: Dense_j / LayerNorm_j below each `network`)
     mlp_leaves = tuple(leaf for leaf in tp if re.fullmatch(r"(critic|actor)/(w|b|ln)\d+(/scale|/bias)?", leaf))
@@ -172,7 +172,7 @@ def load_state_dict(agent, sd: dict, restore_rng: bool = False):
     trunk = _trunk_paths() if (keys and etype != "small") else {}   # state-only / SmallEncoder agents have no frozen trunk
     todo = []      # (section, leaf, array): everything is sized against the agent's leaves before the first one is written
 
-    std_mode = std_parameterization_of(core)
+    std_mode = spec.std_parameterization
     std_modules = {"Dense_1": "actor/logstd", "log_stds": "actor/log_stds"}   # what Policy keeps its std in, below modules_actor
 
     def leaves_of(tree, section):

@@ -11,8 +11,11 @@ threefry stream under flax's per-module keys (utils/init_ref.py); the trunk come
 """
 from __future__ import annotations
 
+import ctypes
+import dataclasses
 import math
 import re
+from typing import Optional, Tuple
 
 import numpy as np
 
@@ -105,16 +108,6 @@ def mlp_layer_dims(critic_network_kwargs=None, policy_network_kwargs=None, mlp_p
     return tuple(out)
 
 
-def check_shapes_dropout(critic_dims, policy_dims, critic_dropout, policy_dropout):
-    """mlp_shapes=True together with a positive dropout_rate under mlp_dropout=True: served only where both lists are one [h, h]
-    (the Dropout masks and per-layer keys of serl_mlp_noise are laid out for two layers of one width)."""
-    if (critic_dropout > 0 or policy_dropout > 0) and not (len(critic_dims) == 2 and critic_dims[0] == critic_dims[1]
-                                                          and tuple(critic_dims) == tuple(policy_dims)):
-        raise NotImplementedError(
-            f"mlp_shapes=True with mlp_dropout=True and a positive dropout_rate: critic hidden_dims={list(critic_dims)}, policy "
-            f"hidden_dims={list(policy_dims)} (served with Dropout: hidden_dims=[h, h], the same in both networks)")
-
-
 def resolve_mlp_dims(hidden=256, critic_dims=None, policy_dims=None):
     """(critic, policy) width tuples from the defaulted parameters every shape helper takes: None means (hidden, hidden)."""
     return (tuple(int(d) for d in critic_dims) if critic_dims is not None else (int(hidden), int(hidden)),
@@ -175,22 +168,6 @@ def mlp_layer_norms(critic_network_kwargs=None, policy_network_kwargs=None):
     return tuple(out)
 
 
-def check_plain_dropout(critic_layer_norm, policy_layer_norm, critic_dropout, policy_dropout):
-    """mlp_plain=True together with a positive dropout_rate under mlp_dropout=True in a network that has use_layer_norm=False:
-    not served (the LayerNorm-free rows carry no Dropout).  Nor is Dropout in a LayerNorm network beside a plain one:
-    serl_agent_create_layer_norm, the one entry point that makes a plain network, takes no rates."""
-    nets = (("critic_network_kwargs", critic_layer_norm, critic_dropout), ("policy_network_kwargs", policy_layer_norm, policy_dropout))
-    for which, ln, rate in nets:
-        if not ln and rate > 0:
-            raise NotImplementedError(f"{which}: use_layer_norm=False under mlp_plain=True with dropout_rate={rate!r} under "
-                                      "mlp_dropout=True (served: Dropout in agents whose two networks have their LayerNorm)")
-    if not (critic_layer_norm and policy_layer_norm):
-        for which, ln, rate in nets:
-            if rate > 0:
-                raise NotImplementedError(f"{which}: dropout_rate={rate!r} under mlp_dropout=True beside a network with use_layer_norm=False "
-                                          "under mlp_plain=True (served: Dropout in agents whose two networks have their LayerNorm)")
-
-
 def _dropout_rate_ok(rate):
     return rate is None or (not isinstance(rate, bool) and isinstance(rate, (int, float, np.integer, np.floating)) and bool(rate < 1))
 
@@ -230,7 +207,7 @@ def policy_mode(policy_kwargs=None):
     return std, bool(pk.get("tanh_squash_distribution", True))
 
 
-FIXED_STD = "fixed"   # serl_agent_create_fixed_std's SERL_STD_FIXED: read by policy_mode_fixed alone (policy_fixed=True)
+FIXED_STD = "fixed"   # SERL_STD_FIXED: read by policy_mode_fixed alone (policy_fixed=True)
 
 
 def policy_mode_fixed(policy_kwargs, A):
@@ -264,12 +241,110 @@ def policy_mode_fixed(policy_kwargs, A):
     return FIXED_STD, bool(pk.get("tanh_squash_distribution", True)), v.copy()
 
 
-def check_fixed_dropout(fixed, critic_dropout, policy_dropout):
-    """policy_fixed=True with std_parameterization="fixed" together with a positive dropout_rate under mlp_dropout=True: not served
-    (serl_agent_create_fixed_std, the one entry point that makes a fixed-std head, takes no rates)."""
-    if fixed is not None and (critic_dropout > 0 or policy_dropout > 0):
-        raise NotImplementedError(f"std_parameterization='fixed' under policy_fixed=True with dropout_rate critic {critic_dropout!r} / "
-                                  f"policy {policy_dropout!r} under mlp_dropout=True (served: Dropout in agents whose policy head has std leaves)")
+@dataclasses.dataclass(frozen=True)
+class NetSpec:
+    """The options of an agent's critic and policy networks, stated once: what network_spec reads from the reference's kwargs, what
+    AgentCore takes as keywords and hands to serl_agent_create_opts (to_c), and what the leaf tables are built from (leaf_kwargs).
+    The defaults are what utils/launcher.py configures, and the all-zero serl_agent_opts.
+    critic_dims / policy_dims: None means (hidden, hidden); with both None the library is sent n_layers = 0, "two layers of
+    cfg.hidden", the agent every call without mlp_shapes makes.  fixed_std: None, or with "fixed" act_dim float32 values as floats."""
+    std_parameterization: str = "exp"
+    tanh_squash_distribution: bool = True
+    fixed_std: Optional[Tuple[float, ...]] = None
+    critic_activation: str = "tanh"
+    policy_activation: str = "tanh"
+    critic_dropout: float = 0.0
+    policy_dropout: float = 0.0
+    hidden: int = 256
+    critic_dims: Optional[Tuple[int, ...]] = None
+    policy_dims: Optional[Tuple[int, ...]] = None
+    critic_layer_norm: bool = True
+    policy_layer_norm: bool = True
+
+    @property
+    def dims(self):
+        """(critic, policy) width tuples, a list left out resolved"""
+        return resolve_mlp_dims(self.hidden, self.critic_dims, self.policy_dims)
+
+    def check(self):
+        """A positive dropout_rate (mlp_dropout=True) is served in two LayerNorm MLPs of one [h, h] under a policy head with std
+        leaves: the Dropout masks and per-layer keys of serl_mlp_noise are laid out for two layers of one width, the LayerNorm-free
+        rows carry no Dropout, and the library serves none beside a fixed std.  Anything else raises NotImplementedError."""
+        rates = (self.critic_dropout, self.policy_dropout)
+        if not any(r > 0 for r in rates):
+            return self
+        cd, pd = self.dims
+        if not (len(cd) == 2 and cd[0] == cd[1] and cd == pd):
+            raise NotImplementedError(
+                f"mlp_shapes=True with mlp_dropout=True and a positive dropout_rate: critic hidden_dims={list(cd)}, policy "
+                f"hidden_dims={list(pd)} (served with Dropout: hidden_dims=[h, h], the same in both networks)")
+        nets = (("critic_network_kwargs", self.critic_layer_norm, rates[0]), ("policy_network_kwargs", self.policy_layer_norm, rates[1]))
+        for which, ln, rate in nets:
+            if not ln and rate > 0:
+                raise NotImplementedError(f"{which}: use_layer_norm=False under mlp_plain=True with dropout_rate={rate!r} under "
+                                          "mlp_dropout=True (served: Dropout in agents whose two networks have their LayerNorm)")
+        if not (self.critic_layer_norm and self.policy_layer_norm):
+            which, _, rate = next(n for n in nets if n[2] > 0)
+            raise NotImplementedError(f"{which}: dropout_rate={rate!r} under mlp_dropout=True beside a network with use_layer_norm=False "
+                                      "under mlp_plain=True (served: Dropout in agents whose two networks have their LayerNorm)")
+        if self.fixed_std is not None:
+            raise NotImplementedError(f"std_parameterization='fixed' under policy_fixed=True with dropout_rate critic {rates[0]!r} / "
+                                      f"policy {rates[1]!r} under mlp_dropout=True (served: Dropout in agents whose policy head has std leaves)")
+        return self
+
+    def core_kwargs(self):
+        """AgentCore's keywords of these options"""
+        return dataclasses.asdict(self)
+
+    def leaf_kwargs(self):
+        """what the leaf tables depend on, as theta_shapes, init_theta, flax_tree.theta_paths and init_ref.theta_leaves /
+        theta_reference all take it"""
+        cd, pd = self.dims
+        return dict(std_parameterization=self.std_parameterization, critic_dims=cd, policy_dims=pd,
+                    critic_layer_norm=self.critic_layer_norm, policy_layer_norm=self.policy_layer_norm)
+
+    def config_entries(self):
+        """the network entries of agent.config; fixed_std and the use_layer_norm pair only where they say something"""
+        return dict(critic_activation=self.critic_activation, policy_activation=self.policy_activation,
+                    critic_dropout_rate=self.critic_dropout, policy_dropout_rate=self.policy_dropout,
+                    **({} if self.fixed_std is None else {"fixed_std": self.fixed_std}),
+                    **({} if self.critic_layer_norm and self.policy_layer_norm else
+                       {"critic_use_layer_norm": self.critic_layer_norm, "policy_use_layer_norm": self.policy_layer_norm}))
+
+    def to_c(self):
+        """-> _lib_agent.SerlAgentOpts (serl_agent_opts); no device is touched.  (ctypes keeps the fixed_std buffer alive with the struct.)"""
+        from .._lib_agent import SerlAgentOpts
+        o = SerlAgentOpts()
+        o.std_param = 3 if self.fixed_std is not None else STD_PARAMETERIZATIONS.index(self.std_parameterization)   # SERL_STD_FIXED = 3
+        o.no_tanh = 0 if self.tanh_squash_distribution else 1
+        given = self.critic_dims is not None or self.policy_dims is not None
+        for net, act, dims, ln, rate in zip((o.critic, o.policy), (self.critic_activation, self.policy_activation), self.dims,
+                                            (self.critic_layer_norm, self.policy_layer_norm), (self.critic_dropout, self.policy_dropout)):
+            net.act = MLP_ACTIVATIONS.index(act)
+            if given:
+                net.n_layers, net.dims[:len(dims)] = len(dims), dims
+            net.no_layer_norm, net.dropout = 0 if ln else 1, rate
+        if self.fixed_std is not None:
+            o.fixed_std = (ctypes.c_float * len(self.fixed_std))(*self.fixed_std)
+        return o
+
+
+def network_spec(critic_network_kwargs, policy_network_kwargs, policy_kwargs, act_dim, *, mlp_dropout=False, mlp_shapes=False,
+                 mlp_plain=False, policy_fixed=False) -> NetSpec:
+    """The checked NetSpec of create_states' / create_drq's three kwargs dicts under their four switches; every refusal is raised
+    from the arguments alone, in the order of the lines below."""
+    # policy_fixed=True: "fixed" / fixed_std are read (actor_critic_nets.py:189-192); else refused, as always
+    std_param, squash, fixed = policy_mode_fixed(policy_kwargs, act_dim) if policy_fixed else (*policy_mode(policy_kwargs), None)
+    # mlp_shapes=True: each network's own depth and per-layer widths (mlp.py:19-31); else the one width of [h, h], as always
+    dims = mlp_layer_dims(critic_network_kwargs, policy_network_kwargs, mlp_plain) if mlp_shapes else (None, None)
+    hidden = dims[0][0] if mlp_shapes else mlp_hidden_width(critic_network_kwargs, policy_network_kwargs, mlp_plain)
+    # mlp_plain=True: each network's own use_layer_norm (mlp.py:29-30); else LayerNorm in both, as always
+    lns = mlp_layer_norms(critic_network_kwargs, policy_network_kwargs) if mlp_plain else (True, True)
+    acts = mlp_activations(critic_network_kwargs, policy_network_kwargs, mlp_dropout)
+    rates = mlp_dropout_rates(critic_network_kwargs, policy_network_kwargs) if mlp_dropout else (0.0, 0.0)
+    if dims == ((hidden, hidden), (hidden, hidden)):
+        dims = (None, None)    # [h, h] twice: the very agent the call without the switch makes
+    return NetSpec(std_param, squash, None if fixed is None else tuple(float(x) for x in fixed), *acts, *rates, hidden, *dims, *lns).check()
 
 
 def _policy_std_shapes(Hd, A, std_parameterization):

@@ -33,8 +33,11 @@ def chain_fuse(fuse):
 
 
 def make_core(cfg: O.Config, B, *, fuse=None, trunk_mode=None, agent_seed=0):
-    """-> the AgentCore of an oracle Config, its optimizer kwargs, policy distribution and MLP activations included.  fuse: see chain_fuse."""
+    """-> the AgentCore of an oracle Config, its optimizer kwargs, policy distribution and MLP activations included; and of the Configs
+    that carry more (mlp_shapes.ShapeConfig, mlp_plain.PlainConfig, policy_fixed.FixedConfig) their width lists, LayerNorm flags and
+    fixed_std -- a fixed_std makes the "fixed" agent, whatever mode the Config has the oracle run.  fuse: see chain_fuse."""
     from serl_amd.agents.core import AgentCore
+    fixed = getattr(cfg, "fixed_std", None)
     with chain_fuse(fuse):
         core = AgentCore(encoder_type=cfg.encoder_type, n_cam=cfg.n_cam, H=cfg.H, W=cfg.W, state_dim=cfg.S, act_dim=cfg.A, batch=B,
                          ensemble=cfg.ensemble, hidden=cfg.hidden, discount=cfg.discount, tau=cfg.tau, lr=cfg.lr,
@@ -42,8 +45,11 @@ def make_core(cfg: O.Config, B, *, fuse=None, trunk_mode=None, agent_seed=0):
                          target_entropy=cfg.target_entropy, seed=agent_seed,
                          temp_warmup_steps=-1 if cfg.temp_warmup is None else cfg.temp_warmup,
                          critic_subsample_size=cfg.subsample, backup_entropy=cfg.backup_entropy, optimizers=cfg.opt,
-                         std_parameterization=cfg.std_parameterization, tanh_squash_distribution=cfg.tanh_squash,
-                         critic_activation=cfg.critic_activation, policy_activation=cfg.policy_activation)
+                         std_parameterization=cfg.std_parameterization if fixed is None else "fixed",
+                         fixed_std=None if fixed is None else np.asarray(fixed, np.float32), tanh_squash_distribution=cfg.tanh_squash,
+                         critic_activation=cfg.critic_activation, policy_activation=cfg.policy_activation,
+                         critic_dims=getattr(cfg, "critic_dims", None), policy_dims=getattr(cfg, "policy_dims", None),
+                         critic_layer_norm=getattr(cfg, "critic_layer_norm", True), policy_layer_norm=getattr(cfg, "policy_layer_norm", True))
     if trunk_mode is not None:
         core.set_trunk_mode(trunk_mode)
     return core

@@ -206,29 +206,10 @@ def case_config(case):
     return config(kind, cd, pd, ensemble, ca, pa), B, utd
 
 
-def make_core(cfg, B, *, fuse=None, trunk_mode=None, agent_seed=0):
-    """agent_helpers.make_core with AgentCore(critic_dims=..., policy_dims=...)"""
-    from serl_amd.agents.core import AgentCore
-    cd, pd = dims_of(cfg)
-    with AH.chain_fuse(fuse):
-        core = AgentCore(encoder_type=cfg.encoder_type, n_cam=cfg.n_cam, H=cfg.H, W=cfg.W, state_dim=cfg.S, act_dim=cfg.A, batch=B,
-                         ensemble=cfg.ensemble, hidden=cfg.hidden, discount=cfg.discount, tau=cfg.tau, lr=cfg.lr,
-                         warmup_steps=cfg.warmup, dropout=cfg.dropout, std_min=cfg.std_min, std_max=cfg.std_max,
-                         target_entropy=cfg.target_entropy, seed=agent_seed,
-                         temp_warmup_steps=-1 if cfg.temp_warmup is None else cfg.temp_warmup,
-                         critic_subsample_size=cfg.subsample, backup_entropy=cfg.backup_entropy, optimizers=cfg.opt,
-                         std_parameterization=cfg.std_parameterization, tanh_squash_distribution=cfg.tanh_squash,
-                         critic_activation=cfg.critic_activation, policy_activation=cfg.policy_activation,
-                         critic_dims=cd, policy_dims=pd)
-    if trunk_mode is not None:
-        core.set_trunk_mode(trunk_mode)
-    return core
-
-
 def make_pair(cfg, B, dtype=torch.float64, seed=42, agent_seed=0, trunk_mode=None, fuse=None):
     """-> (oracle TrainState, AgentCore) holding identical parameters; inside installed()"""
     trunk, theta = init_params(cfg, seed)
-    core = make_core(cfg, B, fuse=fuse, trunk_mode=trunk_mode, agent_seed=agent_seed)
+    core = AH.make_core(cfg, B, fuse=fuse, trunk_mode=trunk_mode, agent_seed=agent_seed)
     return O.TrainState(cfg, trunk, theta, dtype), AH.load_leaves(core, cfg, trunk, theta)
 
 

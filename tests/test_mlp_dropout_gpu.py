@@ -238,6 +238,35 @@ def test_rate_zero_through_create_dropout_is_create_mlp_bit_for_bit(gpu):
         _same_bits(_bits(new), _bits(old), f"hidden {hidden}")
 
 
+def test_positive_rates_through_create_dropout_are_create_opts_bit_for_bit(gpu):
+    """the same comparison at rate 0.5 in both networks: serl_agent_create_dropout fills the struct AgentCore hands to
+    serl_agent_create_opts.  Explicit keep-masks, so both agents see the same draws."""
+    from serl_amd.agents.core import AgentCore
+
+    class OldEntry(AgentCore):
+        def _create(self, cfg):
+            return self.L.serl_agent_create_dropout(C.byref(cfg), self._std_param, 0 if self.tanh_squash_distribution else 1, *self._acts,
+                                                    self.critic_dropout, self.policy_dropout, C.byref(self._h))
+    cfg, B, rates = O.Config(image_keys=(), S=10, A=4, discount=0.99, hidden=64, ensemble=2), 8, (0.5, 0.5)
+    _, theta = O.init_params(cfg, 42)
+    kw = dict(encoder_type=cfg.encoder_type, n_cam=0, H=0, W=0, state_dim=cfg.S, act_dim=cfg.A, batch=B, ensemble=cfg.ensemble,
+              hidden=cfg.hidden, discount=cfg.discount, tau=cfg.tau, lr=cfg.lr, warmup_steps=cfg.warmup, dropout=cfg.dropout,
+              std_min=cfg.std_min, std_max=cfg.std_max, target_entropy=cfg.target_entropy, seed=5, temp_warmup_steps=-1,
+              critic_dropout=rates[0], policy_dropout=rates[1])
+    old, new = OldEntry(**kw), AgentCore(**kw)
+    assert list(old.leaves.items()) == list(new.leaves.items())
+    b = AH.synth_batch(cfg, B, seed=5)
+    n1, n2 = O.make_noise(cfg, B, seed=8), O.make_noise(cfg, B, seed=9, utd_ratio=2)
+    m1, m2 = MD.random_masks(rates, "critics", 1, (), B, cfg.hidden, seed=11), MD.random_masks(rates, "high_utd", 2, (), B, cfg.hidden, seed=12)
+    assert set(m2) == set(MD.MLP_SITES)
+    for core in (old, new):
+        AH.load_leaves(core, cfg, None, theta)
+        core.update_critics(AH.batch_to_device(cfg, b), {**AH.noise_to_device(cfg, n1), **MD.device_noise(m1)})
+        core.update_high_utd(AH.batch_to_device(cfg, b), 2, {**AH.noise_to_device(cfg, n2), **MD.device_noise(m2)})
+    assert old.step == new.step > 0 and old.read_info() == new.read_info()
+    _same_bits(_bits(new), _bits(old), "rates 0.5")
+
+
 def test_c_abi_refuses_rates_outside_the_unit_interval(gpu):
     from serl_amd import _lib
     from serl_amd._lib_agent import SerlAgentCfg

@@ -57,8 +57,8 @@ def test_dropout_beside_a_plain_network_is_refused_naming_both_switches(create):
         with pytest.raises(NotImplementedError, match=where) as e:
             create(policy_kwargs=dict(MS.POLICY_KWARGS), mlp_plain=True, mlp_dropout=True, critic_network_kwargs=ck, policy_network_kwargs=pk)
         assert "mlp_plain=True" in str(e.value) and "mlp_dropout=True" in str(e.value)
-    pinit.check_plain_dropout(True, True, 0.1, 0.2)          # LayerNorm in both: Dropout's own business
-    pinit.check_plain_dropout(False, False, 0.0, 0.0)        # no positive rate: served
+    pinit.NetSpec(critic_dropout=0.1, policy_dropout=0.2).check()                      # LayerNorm in both: Dropout's own business
+    pinit.NetSpec(critic_layer_norm=False, policy_layer_norm=False).check()            # no positive rate: served
 
 
 @CREATE
@@ -127,7 +127,8 @@ def test_both_flags_true_return_what_they_return_today():
         assert FT.theta_paths(keys) == FT.theta_paths(keys, critic_layer_norm=True, policy_layer_norm=True)
     assert [lf for lf in IR.theta_leaves((), 0, 0, 7, 3, hidden=128)] == \
         [lf for lf in IR.theta_leaves((), 0, 0, 7, 3, hidden=128, critic_layer_norm=True, policy_layer_norm=True)]
-    assert FT.layer_norms_of(SimpleNamespace()) == (True, True)          # a core made before the flags existed
+    bare = FT.net_spec_of(SimpleNamespace(cfg=SimpleNamespace()))        # a core made before the flags existed
+    assert (bare.critic_layer_norm, bare.policy_layer_norm) == (True, True)
 
 
 # ---- the general oracle at both flags True is the mlp_shapes oracle ------------------------------------------------------------

@@ -42,7 +42,7 @@ def _core_of(run, fuse):
     """a fresh agent holding the parameters the case's oracle run started from"""
     cfg = run["cfg"]
     trunk, theta = MP.init_params(cfg, run["seed"])
-    return AH.load_leaves(MP.make_core(cfg, run["B"], fuse=fuse), cfg, trunk, theta)
+    return AH.load_leaves(AH.make_core(cfg, run["B"], fuse=fuse), cfg, trunk, theta)
 
 
 # ---- oracle parity -----------------------------------------------------------------------------------------------------------

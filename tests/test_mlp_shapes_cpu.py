@@ -102,8 +102,8 @@ def test_dropout_with_other_shapes_is_refused(create):
             create(policy_kwargs=dict(MS.POLICY_KWARGS), mlp_shapes=True, mlp_dropout=True,
                    critic_network_kwargs=MS.mlp_kwargs(cd, dropout_rate=0.1), policy_network_kwargs=MS.mlp_kwargs(pd))
         assert "hidden_dims=[h, h], the same in both networks" in str(e.value)
-    pinit.check_shapes_dropout((128, 128), (128, 128), 0.1, 0.0)      # one [h, h]: served
-    pinit.check_shapes_dropout((128, 256, 64), (64,), 0.0, 0.0)       # no positive rate: served
+    pinit.NetSpec(critic_dims=(128, 128), policy_dims=(128, 128), critic_dropout=0.1).check()      # one [h, h]: served
+    pinit.NetSpec(critic_dims=(128, 256, 64), policy_dims=(64,)).check()                           # no positive rate: served
 
 
 # ---- shapes, paths and the exported tree against the tree the reference built ----------------------------------------------------

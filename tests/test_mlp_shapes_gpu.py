@@ -116,7 +116,9 @@ def test_shapes_entry_point_at_h_h_is_the_create_mlp_agent(gpu):
     old_cfg = O.Config(image_keys=("wrist",), H=64, W=64, S=5, A=3, hidden=192)
     B = 6
     new, old = MS.make_pair(cfg, B)[1], AH.make_pair(old_cfg, B)[1]
-    assert new._shapes and not old._shapes and old.critic_dims == old.policy_dims == (192, 192)
+    # (the new core sends its two lists, the old one n_layers = 0: two layers of cfg.hidden)
+    assert (new.spec.to_c().critic.n_layers, new.spec.to_c().policy.n_layers) == (2, 2)
+    assert (old.spec.to_c().critic.n_layers, old.spec.to_c().policy.n_layers) == (0, 0) and old.critic_dims == old.policy_dims == (192, 192)
     assert list(new.leaves.items()) == list(old.leaves.items())
     n = {}
     for it in range(2):

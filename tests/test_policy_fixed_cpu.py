@@ -112,8 +112,8 @@ def test_dropout_beside_a_fixed_head_is_refused_naming_both_switches(create):
             create(policy_kwargs=_pk(std_parameterization="fixed", fixed_std=0.1), policy_fixed=True, mlp_dropout=True,
                    critic_network_kwargs=ck, policy_network_kwargs=pk)
         assert "policy_fixed=True" in str(e.value) and "mlp_dropout=True" in str(e.value)
-    pinit.check_fixed_dropout(None, 0.1, 0.2)                              # no fixed head: Dropout's own business
-    pinit.check_fixed_dropout(np.ones(3, np.float32), 0.0, 0.0)            # no positive rate: served
+    pinit.NetSpec(critic_dropout=0.1, policy_dropout=0.2).check()                              # no fixed head: Dropout's own business
+    pinit.NetSpec(std_parameterization="fixed", fixed_std=(1.0, 1.0, 1.0)).check()             # no positive rate: served
 
 
 # ---- shapes and trees ------------------------------------------------------------------------------------------------------------

@@ -44,7 +44,7 @@ def _core_of(run, fuse):
     """a fresh fixed agent holding the parameters the case's oracle run started from"""
     cfg = run["cfg"]
     trunk, theta = PF.init_params(cfg, PF.PARAM_SEED)
-    return AH.load_leaves(PF.make_core(cfg, run["B"], fuse=fuse), cfg, trunk, theta)
+    return AH.load_leaves(AH.make_core(cfg, run["B"], fuse=fuse), cfg, trunk, theta)
 
 
 def _spans(cfg):
@@ -165,7 +165,7 @@ def _twin_cores(squash, fuse=None):
     assert uni.std_min <= 1.0 <= uni.std_max and (fix.std_min, fix.std_max) == (uni.std_min, uni.std_max)
     theta = O.init_params(uni, PF.PARAM_SEED)[1]
     assert not theta[PF.LEAF].any()
-    a = AH.load_leaves(PF.make_core(fix, TWIN_ROWS, fuse=fuse), fix, None, PF.unpinned(theta))
+    a = AH.load_leaves(AH.make_core(fix, TWIN_ROWS, fuse=fuse), fix, None, PF.unpinned(theta))
     b = AH.load_leaves(AH.make_core(uni, TWIN_ROWS, fuse=fuse), uni, None, theta)
     return fix, uni, a, b
 
@@ -327,6 +327,41 @@ def test_fixed_std_reads_back_and_a_scalar_is_its_vector(gpu):
         assert _bits_equal(v, want[key]), key
 
 
+def test_create_fixed_std_is_the_create_opts_agent_bit_for_bit(gpu):
+    """serl_agent_create_fixed_std fills the struct AgentCore hands to serl_agent_create_opts: the same leaf table, and the same
+    params, target and optimizer bits after one update_critics and one update_high_utd(2)"""
+    import ctypes as C
+    import types
+    from serl_amd.agents.core import AgentCore
+
+    class OldEntry(AgentCore):
+        def _create(self, cfg):
+            cd, pd = (C.c_int32 * len(self.critic_dims))(*self.critic_dims), (C.c_int32 * len(self.policy_dims))(*self.policy_dims)
+            fs = (C.c_float * cfg.act_dim)(*self.spec.fixed_std)
+            return self.L.serl_agent_create_fixed_std(C.byref(cfg), self._std_param, 0 if self.tanh_squash_distribution else 1, *self._acts,
+                                                      cd, len(cd), pd, len(pd), int(self.critic_layer_norm), int(self.policy_layer_norm), fs,
+                                                      C.byref(self._h))
+    B = 8
+    cfg = PF.config("state", 10, 4, (0.1, 0.3, 1.0, 0.7), ensemble=2, critic_dims=(64, 64), policy_dims=(64, 64))
+    theta = PF.unpinned(O.init_params(PF.pinned_config(cfg), PF.PARAM_SEED)[1])
+    kw = dict(encoder_type=cfg.encoder_type, n_cam=0, H=0, W=0, state_dim=cfg.S, act_dim=cfg.A, batch=B, ensemble=cfg.ensemble, hidden=cfg.hidden,
+              discount=cfg.discount, tau=cfg.tau, lr=cfg.lr, warmup_steps=cfg.warmup, dropout=cfg.dropout, std_min=cfg.std_min,
+              std_max=cfg.std_max, target_entropy=cfg.target_entropy, seed=5, temp_warmup_steps=-1, std_parameterization="fixed",
+              fixed_std=np.asarray(cfg.fixed_std, np.float32), critic_dims=cfg.critic_dims, policy_dims=cfg.policy_dims)
+    old, new = OldEntry(**kw), AgentCore(**kw)
+    assert list(old.leaves.items()) == list(new.leaves.items()) and np.array_equal(old.fixed_std, new.fixed_std)
+    b = AH.synth_batch(cfg, B, seed=5)
+    n1, n2 = O.make_noise(cfg, B, seed=8), O.make_noise(cfg, B, seed=9, utd_ratio=2)
+    for core in (old, new):
+        AH.load_leaves(core, cfg, None, theta)
+        core.update_critics(AH.batch_to_device(cfg, b), AH.noise_to_device(cfg, n1))
+        core.update_high_utd(AH.batch_to_device(cfg, b), 2, AH.noise_to_device(cfg, n2))
+    assert old.step == new.step > 0 and old.read_info() == new.read_info()
+    want = _all_bits(types.SimpleNamespace(core=old))
+    for key, v in _all_bits(types.SimpleNamespace(core=new)).items():
+        assert _bits_equal(v, want[key]), key
+
+
 def test_checkpoint_roundtrip_and_both_refusals(gpu, tmp_path):
     """tests/test_policy_modes_gpu.py::test_checkpoint_roundtrip_of_a_uniform_agent for a fixed agent: every leaf back and an
     identical next update (the checkpoint carries no fixed_std: the fresh agent is created with it); a uniform and an exp agent's
@@ -384,7 +419,7 @@ def test_two_shards_of_a_batch_equal_the_full_batch(gpu):
     _, pc, pa0, pa1 = _spans(cfg)
 
     def run(rows, shard):
-        core = AH.load_leaves(PF.make_core(cfg, rows, agent_seed=7), cfg, None, theta)
+        core = AH.load_leaves(AH.make_core(cfg, rows, agent_seed=7), cfg, None, theta)
         lo = 0 if shard is None else shard * rows
         if shard is not None:
             core.set_shard(lo, B)
