@@ -294,7 +294,8 @@ typedef struct serl_agent_cfg {
  *   act            `activations`, behind every layer: SERL_ACT_TANH y = tanh(p); SERL_ACT_RELU y = max(p, 0), gradient 0 at p = 0
  *                  (jax.nn.relu); SERL_ACT_SWISH y = p * sigmoid(p) (flax.linen.swish = silu, mlp.py's own default).  The encoder's
  *                  bottleneck and proprio rows keep tanh and their LayerNorm (resnet_v1.py:371-374, encoding.py:66-68).
- *   n_layers, dims `hidden_dims`: 1 to SERL_MAX_MLP_LAYERS widths, each a multiple of 64 in [64, 1024]; n_layers == 0 means two
+ *   n_layers, dims `hidden_dims`: 1 to SERL_MAX_MLP_LAYERS widths, each a multiple of 64 in [64, 1024] (any integer in [1, 1024] with
+ *                  serl_agent_opts.ragged_widths, below, which holds for cfg->hidden too); n_layers == 0 means two
  *                  layers of cfg->hidden, which is read for such a network alone.  Leaves: critic/w<j>, critic/b<j>,
  *                  critic/ln<j>/{scale,bias}, j = 1..n_layers, and the same under actor/; critic/head/kernel follows the critic's
  *                  last width, actor/mean/kernel and actor/logstd/kernel the policy's.
@@ -325,7 +326,19 @@ typedef struct serl_agent_cfg {
  *                  unbounded, log pi has no log-det term, and the mode is the mean
  *   fixed_std      act_dim floats (host memory, copied), each finite and > 0, with SERL_STD_FIXED; NULL with every other
  *                  std_param.  A constant of the agent: device memory of its own outside the parameter arena, never stepped,
- *                  averaged or all-reduced, and not part of serl_agent_get / serl_agent_set (serl_agent_fixed_std reads it back). */
+ *                  averaged or all-reduced, and not part of serl_agent_get / serl_agent_set (serl_agent_fixed_std reads it back).
+ *   ragged_widths  0: every MLP width (dims[], cfg->hidden) is a multiple of 64 in [64, 1024], checked and refused as always.
+ *                  1: every width is any integer in [1, 1024] (mlp.py:19-31 takes any list; TD3's and DDPG's published [400, 300]).
+ *                  A layer of true width d is STORED dp = 64 * ceil(d / 64) wide: the columns [d, dp) of w<j>, b<j> and
+ *                  ln<j>/{scale,bias}, and the rows [d, dp) of the kernel that reads the layer (w<j+1>, critic/head/kernel,
+ *                  actor/mean/kernel, actor/logstd/kernel) are padding, exactly 0.0f in the parameters, the target parameters, the
+ *                  Adam moments and the gradients, after any sequence of calls (debug tap "pad_max_abs").  The update launches
+ *                  what the agent of widths dp launches; only the LayerNorm rows of a layer off the grid are instantiations of
+ *                  their own, which divide by d.  serl_agent_leaf_info, serl_agent_set, serl_agent_get and serl_agent_mlp_dims
+ *                  speak of true extents alone and never touch padding; what exposes storage says so below
+ *                  (serl_agent_leaf_layout).  An agent whose widths all lie on the grid is the agent of ragged_widths 0, bit for
+ *                  bit.  A positive dropout beside any width off the grid is refused (the keep-masks are laid out for widths on
+ *                  the grid).  The entry points from before serl_agent_opts leave it 0. */
 #define SERL_MAX_MLP_LAYERS 4
 typedef struct serl_mlp_opts {
   int act;
@@ -339,6 +352,7 @@ typedef struct serl_agent_opts {
   int no_tanh;
   serl_mlp_opts critic, policy;
   const float* fixed_std;
+  int ragged_widths;
 } serl_agent_opts;
 int serl_agent_create_opts(const serl_agent_cfg* cfg, const serl_agent_opts* opts, serl_agent** out);
 int serl_agent_live_trunk(serl_agent* a);   /* 1: live-trunk mode (above), 0: not, -1: NULL */
@@ -379,6 +393,13 @@ int serl_agent_num_leaves(serl_agent* a);
 int serl_agent_leaf_info(serl_agent* a, int i, char* name_out, int name_cap, int64_t* count);
 int serl_agent_set(serl_agent* a, const char* section, const char* leaf, const float* host, int64_t count);
 int serl_agent_get(serl_agent* a, const char* section, const char* leaf, float* host_out, int64_t count);
+/* How a leaf is stored (ragged_widths above): out = {n, rows, cols, rows_p, ld}.  The leaf is n blocks of rows x cols elements --
+ * n * rows * cols is serl_agent_leaf_info's count, and the order of serl_agent_get's elements -- inside n blocks of rows_p x ld
+ * floats: element (i, r, c) is float (i * rows_p + r) * ld + c of the leaf's storage, and every other float of the n * rows_p * ld
+ * is padding, exactly 0.  A leaf without padding reports rows_p == rows and ld == cols, or {1, 1, count, 1, count}.  For readers
+ * of what exposes storage: serl_agent_grad_view and serl_agent_grad_bucket (the gradient of a leaf lies where the leaf lies, padding
+ * included; an all-reduce over the whole range keeps the padding zero) and serl_snapshot_leaf (which returns the storage). */
+int serl_agent_leaf_layout(serl_agent* a, const char* leaf, int64_t out[5]);
 int serl_agent_set_step(serl_agent* a, int64_t step); /* JaxRLTrainState.step and the Adam counts */
 /* Arithmetic of the frozen trunk's 3x3/1x1 convs: 0 = exact fp32 MFMA, 1 (default) = split-fp16
  * ("f16x3": x = hi + 2^-11 lo', three fp16 MFMA products per fp32 product, fp32 accumulate; error per
@@ -433,6 +454,8 @@ int serl_snapshot_wait(serl_snapshot* s, int slot);
 int serl_snapshot_info(serl_snapshot* s, int slot, serl_snapshot_meta* out);
 /* async_drq_sim.py:229,295-307.  *host_out points INTO the slot's pinned buffer (read-only for the caller; shared zeros for a
  * moment outside its optimizer's support) and is valid until serl_snapshot_release; refused before the copy is complete. */
+/* The pack kernel copies contiguous runs: a leaf stored with padding (serl_agent_leaf_layout) arrives as its storage, *count is
+ * n * rows_p * ld, and the caller cuts the leaf's own elements out of it. */
 int serl_snapshot_leaf(serl_snapshot* s, int slot, const char* section, const char* leaf, const float** host_out, int64_t* count);
 /* async_drq_sim.py:295-307.  The slot may be taken again (once its copy, if still running, has ended). */
 int serl_snapshot_release(serl_snapshot* s, int slot);
@@ -608,6 +631,13 @@ int serl_agent_eval_losses(serl_agent* a, const serl_batch* batch, const serl_no
 
 /* Debug / test taps (device->host copies of internal activations). */
 int serl_agent_trunk_forward(serl_agent* a, const uint8_t* dev_frames, int n, float* dev_feats_out, void* stream);
+/* "pad_max_abs" (one value, read-only): the largest |value| over all padding of the ragged layout (ragged_widths).  Covered: every
+ * leaf whose storage is larger than its element count (serl_agent_leaf_layout: n * rows_p * ld > n * rows * cols) -- pad columns
+ * [cols, ld) of every row and pad rows [rows, rows_p) of every block, those of the one-block kernels actor/mean/kernel,
+ * actor/logstd/kernel and actor/w<j> included -- in the parameters, the target parameters, both Adam moments of the critic's and
+ * of the actor's optimizer and both gradient buffers.  Not covered: the temperature's moments and the trunk (neither has
+ * padding).  The layout's invariant is that it reads exactly 0 (NaN reads as infinity; 0 for an agent without padding).  The MLP taps
+ * ("mlp_xhat/...", "mlp_dpre/...") hold rows of the storage width. */
 int serl_agent_debug_get(serl_agent* a, const char* what, float* host_out, int64_t count);
 /* inject gradients / scalars ("g_critic", "g_actor", "scalars") before serl_agent_apply: optimizer tests */
 int serl_agent_debug_set(serl_agent* a, const char* what, const float* host, int64_t count);

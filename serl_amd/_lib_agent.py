@@ -33,7 +33,7 @@ class SerlMlpOpts(C.Structure):      # serl_mlp_opts: one network's MLP; all zer
 
 class SerlAgentOpts(C.Structure):    # serl_agent_opts (utils.init.NetSpec.to_c fills it); all zero = serl_agent_create(cfg)
     _fields_ = [("std_param", C.c_int), ("no_tanh", C.c_int), ("critic", SerlMlpOpts), ("policy", SerlMlpOpts),
-                ("fixed_std", P(C.c_float))]
+                ("fixed_std", P(C.c_float)), ("ragged_widths", C.c_int)]
 
 
 TX_INDEX = {"actor": 0, "critic": 1, "temperature": 2}   # SERL_TX_*
@@ -106,6 +106,7 @@ SIGNATURES = {
     "serl_agent_live_trunk": [vp],
     "serl_agent_num_leaves": [vp],
     "serl_agent_leaf_info": [vp, i32, C.c_char_p, i32, P(i64)],
+    "serl_agent_leaf_layout": [vp, C.c_char_p, P(i64)],   # out[5] = n, rows, cols, rows_p, ld (serl_mi355.h)
     "serl_agent_set": [vp, C.c_char_p, C.c_char_p, vp, i64],
     "serl_agent_get": [vp, C.c_char_p, C.c_char_p, vp, i64],
     "serl_agent_set_step": [vp, i64],

@@ -28,7 +28,7 @@ class AgentCore(Handle):
                  critic_subsample_size=2, backup_entropy=False, num_stack=1, std_parameterization="exp",
                  tanh_squash_distribution=True, critic_activation="tanh", policy_activation="tanh",
                  critic_dropout=0.0, policy_dropout=0.0, critic_dims=None, policy_dims=None, critic_layer_norm=True,
-                 policy_layer_norm=True, fixed_std=None):
+                 policy_layer_norm=True, fixed_std=None, ragged=False):
         """optimizers: optional {"actor"|"critic"|"temperature": make_optimizer kwargs (common/optimizers.py:6-13:
         learning_rate, warmup_steps, cosine_decay_steps, weight_decay, clip_grad_norm)} overriding lr / warmup_steps.
         weight_decay decays every leaf of the tree, as optax.adamw does with the params the reference hands it -- with
@@ -45,6 +45,9 @@ class AgentCore(Handle):
         fixed_std: with std_parameterization="fixed" (and only then) the float32 vector of act_dim finite positive entries that
         utils.init.policy_mode_fixed returns; the head then has no std leaf.  The attribute of the same name reads it back from the
         library (None for another mode).
+        ragged: serl_agent_opts.ragged_widths -- hidden and the entries of critic_dims / policy_dims are any integers in [1, 1024];
+        a layer off the 64 grid is stored zero padded to the next multiple of 64 (include/serl_mi355.h), and every leaf this handle
+        gets, sets or counts has its true shape.
         These network options are no fields of serl_agent_cfg: they make one utils.init.NetSpec (`spec`), whose check() says where
         a positive Dropout rate is served, and go to serl_agent_create_opts as one struct (_create)."""
         if target_entropy is None:
@@ -73,7 +76,7 @@ class AgentCore(Handle):
                             float(critic_dropout), float(policy_dropout), int(hidden),
                             None if critic_dims is None else tuple(int(d) for d in critic_dims),
                             None if policy_dims is None else tuple(int(d) for d in policy_dims),
-                            bool(critic_layer_norm), bool(policy_layer_norm))
+                            bool(critic_layer_norm), bool(policy_layer_norm), bool(ragged))
         opts = self.spec.to_c()      # (an unknown std_parameterization or activation name raises here)
         self.spec.check()
         for f in dataclasses.fields(self.spec):      # the options as public attributes, under the constructor's names ...
@@ -100,6 +103,7 @@ class AgentCore(Handle):
         super().__init__(self.cfg)
         self._keep = None
         self._snapshots = {}    # (SERL_SNAP_* mask, slots) -> agents/snapshot.py SnapshotHandle
+        self._layouts = {}      # leaf -> serl_agent_leaf_layout's five numbers (leaf_layout)
 
     def __del__(self):
         # the library refuses to destroy an agent that has live snapshot handles
@@ -115,6 +119,23 @@ class AgentCore(Handle):
     def leaves(self) -> Dict[str, int]:
         """{leaf: element count}"""
         return self._counts
+
+    def leaf_layout(self, leaf: str):
+        """(n, rows, cols, rows_p, ld) of serl_agent_leaf_layout: the leaf is n blocks of rows x cols elements inside n blocks of
+        rows_p x ld floats of storage, what serl_agent_grad_view and a snapshot expose; the floats outside the box are zero."""
+        if leaf not in self._layouts:      # fixed at creation: asked for once per leaf
+            out = (C.c_int64 * 5)()
+            _lib.check(self.L.serl_agent_leaf_layout(self._h, leaf.encode(), out))
+            self._layouts[leaf] = tuple(int(x) for x in out)
+        return self._layouts[leaf]
+
+    @property
+    def pad_max_abs(self) -> float:
+        """the largest |value| in the padding of the ragged layout over parameters, target parameters, Adam moments and gradients
+        (debug tap "pad_max_abs"): exactly 0.0 at every quiescent point"""
+        out = np.zeros(1, np.float32)
+        _lib.check(self.L.serl_agent_debug_get(self._h, b"pad_max_abs", out.ctypes.data_as(C.POINTER(C.c_float)), 1))
+        return float(out[0])
 
     @property
     def fixed_std(self) -> Optional[np.ndarray]:

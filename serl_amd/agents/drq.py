@@ -175,7 +175,7 @@ class DrQAgent:
                    batch_size: int = 256, device: int = 0, learning_rate: float = 3e-4,
                    actor_optimizer_kwargs: dict = None, critic_optimizer_kwargs: dict = None,
                    temperature_optimizer_kwargs: dict = None, param_init: str = "numpy", mlp_dropout: bool = False, mlp_shapes: bool = False, mlp_plain: bool = False,
-                   policy_fixed: bool = False, **kwargs):
+                   policy_fixed: bool = False, mlp_ragged: bool = False, **kwargs):
         """drq.py:104-242.  Only the configuration the reference's examples run is built natively:
         encoder_type="resnet-pretrained", use_proprio=True, REDQ subsample 2, tanh-squashed
         exp-parameterised policy, LayerNorm+tanh MLPs (utils/launcher.py:79-116) -- 256x256 there; critic_network_kwargs /
@@ -203,6 +203,11 @@ class DrQAgent:
         reference), another length and a non-finite or non-positive entry are refused from the arguments alone; so is a
         positive dropout_rate under mlp_dropout=True beside it.  Any other mode under the switch gives the agent the call
         without the switch gives.
+        mlp_ragged=True: every width that hidden_dims carries, with or without mlp_shapes, is any integer in [1, 1024] (mlp.py:19-31
+        takes any list; TD3's and DDPG's published [400, 300]) at every depth, activation and use_layer_norm served.  A layer off the
+        64 grid is stored zero padded to the next multiple of 64 on the device; params, target_params, opt_states, checkpoints and
+        snapshots have the true shapes.  Widths on the grid give the agent the call without the switch gives.  A positive
+        dropout_rate under mlp_dropout=True beside a width off the grid is refused.
         Frame stacks: the sample observation carries T = observations[image_key].shape[0] frames and a (T, S) state, as
         ChunkingWrapper(obs_horizon=T) produces them; EncodingWrapper(enable_stacking=True) folds them into the channels and the
         proprio width (common/encoding.py:39-44,58-64).  T in 1..4 with encoder_type="small"; the pretrained ResNet-10 cannot take
@@ -222,7 +227,7 @@ class DrQAgent:
         pk = policy_kwargs or {}
         A = int(np.asarray(actions).shape[-1])
         spec = pinit.network_spec(critic_network_kwargs, policy_network_kwargs, pk, A, mlp_dropout=mlp_dropout, mlp_shapes=mlp_shapes,
-                                  mlp_plain=mlp_plain, policy_fixed=policy_fixed)
+                                  mlp_plain=mlp_plain, policy_fixed=policy_fixed, mlp_ragged=mlp_ragged)
         seed = int(np.asarray(rng).reshape(-1)[-1]) if not isinstance(rng, int) else rng
         image_keys = tuple(image_keys)
         img = np.asarray(observations[image_keys[0]])

@@ -34,7 +34,7 @@ class SACAgent(DrQAgent):
                       actor_optimizer_kwargs: dict = None, critic_optimizer_kwargs: dict = None,
                       temperature_optimizer_kwargs: dict = None, batch_size: int = 256, device: int = 0, param_init: str = "numpy",
                       mlp_dropout: bool = False, mlp_shapes: bool = False, mlp_plain: bool = False,
-                      policy_fixed: bool = False, **kwargs):
+                      policy_fixed: bool = False, mlp_ragged: bool = False, **kwargs):
         """sac.py:486-542 -> create (:323-400).  Built natively: the configuration of utils/launcher.py:50-76
         (REDQ subsample 2, tanh-squashed exp-parameterised policy, LayerNorm+tanh 256x256 MLPs); hidden_dims=[h, h] in both
         network kwargs selects another width h, a multiple of 64 in [64, 1024], and activations "tanh" (when absent), "relu" or
@@ -47,11 +47,12 @@ class SACAgent(DrQAgent):
         (utils.init.mlp_layer_norms; create_drq's docstring).
         policy_fixed=True also reads std_parameterization="fixed" with fixed_std, a scalar or action_dim numbers -- how the
         reference writes TD3 (utils.init.policy_mode_fixed; create_drq's docstring).
+        mlp_ragged=True admits any width in [1, 1024] wherever hidden_dims is read, e.g. TD3's [400, 300] (create_drq's docstring).
         param_init: "numpy" (default) or "reference" (the reference's own initialisers and keys, utils/init_ref.py)."""
         pk = policy_kwargs or {}
         A = int(np.asarray(actions).shape[-1])
         spec = pinit.network_spec(critic_network_kwargs, policy_network_kwargs, pk, A, mlp_dropout=mlp_dropout, mlp_shapes=mlp_shapes,
-                                  mlp_plain=mlp_plain, policy_fixed=policy_fixed)
+                                  mlp_plain=mlp_plain, policy_fixed=policy_fixed, mlp_ragged=mlp_ragged)
         ao = {"learning_rate": 3e-4, "warmup_steps": 2000, **(actor_optimizer_kwargs or {})}     # sac.py:333-336
         co = {"learning_rate": 3e-4, "warmup_steps": 2000, **(critic_optimizer_kwargs or {})}    # sac.py:337-340
         to = {"learning_rate": 3e-4, **(temperature_optimizer_kwargs or {})}                     # sac.py:341-343

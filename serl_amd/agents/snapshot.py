@@ -71,10 +71,15 @@ class SnapshotHandle:
         return m
 
     def leaf(self, slot, section, leaf, owner) -> np.ndarray:
-        """a read-only view; `owner` (the AgentCore that owns this handle) stays alive as long as the view does"""
+        """a read-only view; `owner` (the AgentCore that owns this handle) stays alive as long as the view does.  The leaf of a
+        ragged MLP layer is a NON-CONTIGUOUS view of shape (blocks, rows, cols) into its padded storage: a caller that needs flat
+        data copies it (np.ascontiguousarray, or the reshape to the leaf's shape that export_tree does)."""
         p, n = C.POINTER(C.c_float)(), C.c_int64()
         _lib.check(self.L.serl_snapshot_leaf(self._h, slot, section.encode(), leaf.encode(), C.byref(p), C.byref(n)))
-        return np.asarray(_Pinned(C.addressof(p.contents), n.value, owner))
+        v = np.asarray(_Pinned(C.addressof(p.contents), n.value, owner))
+        # a leaf of a ragged MLP layer arrives as its zero-padded storage (serl_agent_leaf_layout): the view of its own elements
+        blocks, rows, cols, rows_p, ld = owner.leaf_layout(leaf)
+        return v if v.size == blocks * rows * cols else v.reshape(blocks, rows_p, ld)[:, :rows, :cols]
 
     def release(self, slot):
         if self._h:

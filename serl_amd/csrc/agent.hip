@@ -84,6 +84,10 @@ struct serl_agent {
   // fixed_std points into the vector below.  act is a kAct* code; no_layer_norm is read by build_layout alone, the layers carry it
   // from there (DenseLn::ln).
   serl_agent_opts opts{};
+  // opts.ragged_widths: the dims above are the STORAGE widths, 64 ceil(d / 64), and everything that launches reads them as it
+  // always did; the widths the agent was created with are true_dims[network][layer] (equal to the dims without the option).  A
+  // layer off the grid keeps its leaves as boxes in zero padding (param_arena.h) and its LayerNorm rows divide by the true width.
+  int true_dims[2][SERL_MAX_MLP_LAYERS] = {};
   int pol_mode = kPolExp;            // opts.std_param / no_tanh as the head kernels take them
   int head_groups = 2;               // Dense layers of the policy head: (mean, log_std), or the mean alone with kPolUniform / kPolFixed
   // SERL_STD_FIXED: the constant std vector of a kPolFixed agent as it was passed, [act_dim]; the device copy is an
@@ -218,11 +222,13 @@ void build_layout(serl_agent* a) {
   const long A = c.act_dim;
   const serl_mlp_opts &critic = a->opts.critic, &policy = a->opts.policy;
   const int Hc = critic.dims[critic.n_layers - 1], Hp = policy.dims[policy.n_layers - 1];   // the widths the heads read
+  const int Hct = a->true_dims[0][critic.n_layers - 1], Hpt = a->true_dims[1][policy.n_layers - 1];   // ... and their live rows
   const auto mlp_leaves = [&](DenseLn* layers, const std::string& name, const serl_mlp_opts& net, int groups, int in) {
+    const int* td = a->true_dims[&net == &policy];
     for (int j = 0; j < net.n_layers; ++j) {
       const std::string k = std::to_string(j + 1);
       layers[j] = add_dense_ln_leaves(L, off, name + "/w" + k, name + "/b" + k, name + "/ln" + k, groups, j ? net.dims[j - 1] : in, net.dims[j],
-                                      net.act, net.dropout, !net.no_layer_norm);
+                                      net.act, net.dropout, !net.no_layer_norm, j ? td[j - 1] : in, td[j]);
     }
   };
   const CamHeadOffsets ch = add_cam_head_leaves(L, off, c.n_cam, a->D, c.bottleneck, [&](const std::string& p) {
@@ -238,7 +244,8 @@ void build_layout(serl_agent* a) {
   mlp_leaves(o.c, "critic", critic, N, a->XA);
   // DrQ: one Dense(1) head shared by the ensemble (drq.py:201-207); state-only SAC: ensemblize vmaps the whole
   // Critic, so every member has its own head (actor_critic_nets.py:49-73,156-164)
-  o.c_hw = add_leaf(L, off, "critic/head/kernel", a->state_only ? N * Hc : Hc);
+  // (the heads read the last layer's storage width: the rows of their kernels behind the true width are zero padding)
+  o.c_hw = add_leaf_box(L, off, "critic/head/kernel", a->state_only ? N : 1, 1, Hct, 1, Hc);
   o.c_hb = add_leaf(L, off, "critic/head/bias", a->state_only ? N : 1);
   o.Pa0 = off;
   if (!a->state_only) {
@@ -247,7 +254,7 @@ void build_layout(serl_agent* a) {
   }
   o.Pc = off;
   mlp_leaves(o.a, "actor", policy, 1, a->E);
-  o.a_Wm = add_leaf(L, off, "actor/mean/kernel", Hp * A);
+  o.a_Wm = add_leaf_box(L, off, "actor/mean/kernel", 1, Hpt, A, Hp, A);
   o.a_bm = add_leaf(L, off, "actor/mean/bias", A);
   const int std_param = a->opts.std_param;
   a->pol_mode = std_param | (a->opts.no_tanh ? kPolNoTanh : 0);
@@ -258,7 +265,7 @@ void build_layout(serl_agent* a) {
     o.a_Ws = -1;
     o.a_bs = add_leaf(L, off, "actor/log_stds", A);
   } else {
-    o.a_Ws = add_leaf(L, off, "actor/logstd/kernel", Hp * A);
+    o.a_Ws = add_leaf_box(L, off, "actor/logstd/kernel", 1, Hpt, A, Hp, A);
     o.a_bs = add_leaf(L, off, "actor/logstd/bias", A);
   }
   o.Pa1 = off;
@@ -1031,7 +1038,7 @@ int serl_agent_mlp_layer_norm(serl_agent* a, int network) {
 int serl_agent_mlp_dims(serl_agent* a, int network, int dims[SERL_MAX_MLP_LAYERS]) {
   if (!a || !dims || (network != 0 && network != 1)) return -1;
   const serl_mlp_opts& net = network ? a->opts.policy : a->opts.critic;
-  std::copy_n(net.dims, net.n_layers, dims);
+  std::copy_n(a->true_dims[network], net.n_layers, dims);   // (net.dims: the storage widths)
   return net.n_layers;
 }
 
@@ -1065,20 +1072,34 @@ static int create_agent(const serl_agent_cfg* cfg, const serl_agent_opts* opts, 
   SERL_REQUIRE(cfg->encoder_type == SERL_ENCODER_RESNET_PRETRAINED || cfg->encoder_type == SERL_ENCODER_SMALL,
                "Unknown encoder type: %d", cfg->encoder_type);
   SERL_REQUIRE(cfg->n_cam > 0 || cfg->ensemble <= 16, "state-only SAC supports ensembles of at most 16");
-  // one wave owns a LayerNorm row and a lane holds hidden / 64 of its columns, 16 at the most (heads.hip)
-  if (critic.n_layers == 0 || policy.n_layers == 0)
-    SERL_REQUIRE(cfg->hidden >= 64 && cfg->hidden <= 1024 && cfg->hidden % 64 == 0,
-                 "hidden must be a multiple of 64 in [64, 1024] (got %d): the width of the critic's and the policy's two MLP layers", cfg->hidden);
+  SERL_REQUIRE(opts->ragged_widths == 0 || opts->ragged_widths == 1, "ragged_widths %d is not 0 (widths on the 64 grid) or 1 (any width in [1, 1024])",
+               opts->ragged_widths);
+  // one wave owns a LayerNorm row and a lane holds hidden / 64 of its columns, 16 at the most (heads.hip).  ragged_widths 1: any
+  // width in [1, 1024], a layer off the grid being stored 64 ceil(d / 64) wide in zero padding
+  const bool ragged = opts->ragged_widths == 1;
+  const auto width_ok = [&](int d) { return d <= 1024 && (ragged ? d >= 1 : d >= 64 && d % 64 == 0); };
+  const char* served = ragged ? "served with ragged_widths 1: 1 to %d layers, each in [1, 1024] wide"
+                              : "served: 1 to %d layers, each a multiple of 64 in [64, 1024] wide";
+  bool off_grid = false;
+  if (critic.n_layers == 0 || policy.n_layers == 0) {
+    SERL_REQUIRE(width_ok(cfg->hidden), ragged ? "hidden must lie in [1, 1024] with ragged_widths 1 (got %d): the width of the critic's and the policy's two MLP layers"
+                                               : "hidden must be a multiple of 64 in [64, 1024] (got %d): the width of the critic's and the policy's two MLP layers",
+                 cfg->hidden);
+    off_grid = cfg->hidden % 64 != 0;
+  }
   for (const serl_mlp_opts* net : {&critic, &policy}) {
     if (net->n_layers == 0) continue;   // two layers of cfg->hidden, checked above
-    const char* name = net == &critic ? "critic" : "policy";
-    SERL_REQUIRE(net->n_layers >= 1 && net->n_layers <= SERL_MAX_MLP_LAYERS,
-                 "%s MLP: %d hidden layers (served: 1 to %d layers, each a multiple of 64 in [64, 1024] wide)", name, net->n_layers, SERL_MAX_MLP_LAYERS);
-    for (int j = 0; j < net->n_layers; ++j)
-      SERL_REQUIRE(net->dims[j] >= 64 && net->dims[j] <= 1024 && net->dims[j] % 64 == 0,
-                   "%s MLP: layer %d has width %d (served: 1 to %d layers, each a multiple of 64 in [64, 1024] wide)", name, j + 1, net->dims[j],
-                   SERL_MAX_MLP_LAYERS);
+    const std::string name = net == &critic ? "critic" : "policy";
+    SERL_REQUIRE(net->n_layers >= 1 && net->n_layers <= SERL_MAX_MLP_LAYERS, (name + " MLP: %d hidden layers (" + served + ")").c_str(), net->n_layers,
+                 SERL_MAX_MLP_LAYERS);
+    for (int j = 0; j < net->n_layers; ++j) {
+      SERL_REQUIRE(width_ok(net->dims[j]), (name + " MLP: layer %d has width %d (" + served + ")").c_str(), j + 1, net->dims[j], SERL_MAX_MLP_LAYERS);
+      off_grid = off_grid || net->dims[j] % 64 != 0;
+    }
   }
+  // (the jax-keyed keep-masks are laid out for [rows][h] with h on the grid; off_grid implies ragged here)
+  SERL_REQUIRE(!off_grid || !(critic.dropout > 0.0 || policy.dropout > 0.0), "dropout %g / %g (critic / policy) beside an MLP width off the 64 grid "
+               "under ragged_widths 1: Dropout is served at widths that are multiples of 64", critic.dropout, policy.dropout);
   SERL_REQUIRE(cfg->bottleneck == 256, "bottleneck must be 256 (got %d): the reference fixes bottleneck_dim=256 in create_drq", cfg->bottleneck);
   SERL_REQUIRE(cfg->proprio_dim == 64, "proprio_dim must be 64");
   SERL_REQUIRE(cfg->sle_features == 8, "sle_features must be 8");
@@ -1119,6 +1140,8 @@ static int create_agent(const serl_agent_cfg* cfg, const serl_agent_opts* opts, 
   for (serl_mlp_opts* net : {&a->opts.critic, &a->opts.policy}) {
     if (net->n_layers == 0) { net->n_layers = 2; net->dims[0] = net->dims[1] = cfg->hidden; }
     std::fill(net->dims + net->n_layers, net->dims + kL, 0);
+    int* td = a->true_dims[net == &a->opts.policy];
+    for (int j = 0; j < kL; ++j) { td[j] = net->dims[j]; net->dims[j] = (int)pad64(td[j]); }   // (on the grid: the same number twice)
   }
   if (fixed_std) a->fixed_std.assign(fixed_std, fixed_std + cfg->act_dim);
   a->opts.fixed_std = fixed_std ? a->fixed_std.data() : nullptr;   // the caller's pointer is not kept
@@ -1177,6 +1200,16 @@ int serl_agent_leaf_info(serl_agent* a, int i, char* name_out, int name_cap, int
   return SERL_OK;
 }
 
+int serl_agent_leaf_layout(serl_agent* a, const char* leaf, int64_t out[5]) {
+  SERL_REQUIRE(a && leaf && out, "NULL argument");
+  const Leaf* t = find(a->trunk_leaves, leaf);
+  const Leaf* l = t ? t : find(a->theta_leaves, leaf);
+  SERL_REQUIRE(l != nullptr, "unknown leaf '%s'", leaf);
+  if (l->cols == 0) { out[0] = out[1] = out[3] = 1; out[2] = out[4] = l->count; }   // contiguous: one row of count columns
+  else { out[0] = l->n; out[1] = l->rows; out[2] = l->cols; out[3] = l->rows_p; out[4] = l->ld; }
+  return SERL_OK;
+}
+
 static int flush_trunk_ema(serl_agent* a) {
   if (a->trunk_ema_pending > 0 && a->trunk_count > 0) {
     RC(frozen_ema(a->trunk, a->trunk_t, a->trunk_count, a->cfg.tau, a->trunk_ema_pending, nullptr));
@@ -1187,11 +1220,12 @@ static int flush_trunk_ema(serl_agent* a) {
 }
 
 // resolves (section, leaf) -> device pointer (nullptr = outside that optimizer's support: exact zeros, as the gradient there)
-static int resolve(serl_agent* a, const char* section, const char* leaf, float** ptr, long* count) {
+// *lp: the leaf, whose storage behind *ptr may be a box (param_arena.h)
+static int resolve(serl_agent* a, const char* section, const char* leaf, float** ptr, const Leaf** lp) {
   const Leaf* t = find(a->trunk_leaves, leaf);
   const Leaf* l = t ? t : find(a->theta_leaves, leaf);
   SERL_REQUIRE(l != nullptr, "unknown leaf '%s'", leaf);
-  *count = l->count;
+  *lp = l;
   const std::string s(section);
   const Offs& o = a->o;
   if (s == "params") { *ptr = (t ? a->trunk : a->theta) + l->off; return SERL_OK; }
@@ -1218,7 +1252,13 @@ static int resolve(serl_agent* a, const char* section, const char* leaf, float**
 }  // extern "C"
 // ---- the agent as a snapshot handle sees it (internal.h; snapshot.hip) ----
 namespace serl {
-int agent_resolve(serl_agent* a, const char* section, const char* leaf, float** ptr, long* count) { return resolve(a, section, leaf, ptr, count); }
+// (*count: the leaf's STORAGE, padding included -- what a contiguous copy of the leaf has to cover)
+int agent_resolve(serl_agent* a, const char* section, const char* leaf, float** ptr, long* count) {
+  const Leaf* l;
+  RC(resolve(a, section, leaf, ptr, &l));
+  *count = l->span();
+  return SERL_OK;
+}
 int agent_device(const serl_agent* a) { return a->cfg.device; }
 int64_t agent_trunk_gen(const serl_agent* a) { return a->trunk_gen; }
 void agent_snapshot_count(serl_agent* a, int delta) { a->snapshots += delta; }
@@ -1235,11 +1275,11 @@ static constexpr const char* kOutsideSupport = "'%s' of '%s' lies outside the op
 int serl_agent_set(serl_agent* a, const char* section, const char* leaf, const float* host, int64_t count) {
   SERL_REQUIRE(a && section && leaf && host, "NULL argument");
   SERL_HIP(hipSetDevice(a->cfg.device));
-  float* p; long n;
-  RC(resolve(a, section, leaf, &p, &n));
-  SERL_REQUIRE(n == count, "leaf '%s' has %ld elements, got %lld", leaf, n, (long long)count);
+  float* p; const Leaf* l;
+  RC(resolve(a, section, leaf, &p, &l));
+  SERL_REQUIRE(l->count == count, "leaf '%s' has %ld elements, got %lld", leaf, l->count, (long long)count);
   if (std::strncmp(leaf, "trunk/", 6) == 0) { SERL_HIP(hipDeviceSynchronize()); RC(flush_trunk_ema(a)); }   // pending EMA steps belong to the old values
-  RC(leaf_copy(p, host, n, hipMemcpyHostToDevice, section, leaf, kOutsideSupport));
+  RC(leaf_copy(p, nullptr, host, *l, hipMemcpyHostToDevice, section, kOutsideSupport));
   if (p && std::strncmp(leaf, "trunk/", 6) == 0) {
     a->tpk.dirty = true;
     if (a->live) { a->tpk_t.dirty = true; a->trunk_ver += 1; a->trunk_t_ver += 1; }   // (either copy: both are re-packed and re-evaluated)
@@ -1251,14 +1291,14 @@ int serl_agent_set(serl_agent* a, const char* section, const char* leaf, const f
 int serl_agent_get(serl_agent* a, const char* section, const char* leaf, float* host_out, int64_t count) {
   SERL_REQUIRE(a && section && leaf && host_out, "NULL argument");
   SERL_HIP(hipSetDevice(a->cfg.device));
-  float* p; long n;
-  RC(resolve(a, section, leaf, &p, &n));
-  SERL_REQUIRE(n == count, "leaf '%s' has %ld elements, got %lld", leaf, n, (long long)count);
+  float* p; const Leaf* l;
+  RC(resolve(a, section, leaf, &p, &l));
+  SERL_REQUIRE(l->count == count, "leaf '%s' has %ld elements, got %lld", leaf, l->count, (long long)count);
   if (p) {
     SERL_HIP(hipDeviceSynchronize());
     if (std::strncmp(leaf, "trunk/", 6) == 0 && std::strcmp(section, "target_params") == 0) RC(flush_trunk_ema(a));
   }
-  return leaf_copy(host_out, p, n, hipMemcpyDeviceToHost, section, leaf, kOutsideSupport);
+  return leaf_copy(p, host_out, nullptr, *l, hipMemcpyDeviceToHost, section, kOutsideSupport);
 }
 
 int serl_agent_set_trunk_mode(serl_agent* a, int mode) {
@@ -2012,6 +2052,34 @@ int serl_agent_debug_get(serl_agent* a, const char* what, float* host_out, int64
     long nz = 0;
     for (int v : h) nz += v != 0;
     host_out[0] = (float)nz;
+    return SERL_OK;
+  }
+  if (w == "pad_max_abs") {
+    // The invariant of the ragged layout: every float of a box leaf's storage outside its box is exactly 0 in
+    // the parameters, the target parameters, both Adam moments of the critic's and the actor's optimizer and both gradient
+    // buffers.  host_out[0] = the largest |value| found there after a device synchronise (NaN counts as infinity); 0 without a box.
+    SERL_REQUIRE(count == 1, "tap 'pad_max_abs' holds one value");
+    SERL_HIP(hipDeviceSynchronize());
+    float worst = 0.f;
+    std::vector<float> h;
+    const auto scan = [&](const float* dev, long lo, long hi) -> int {   // dev[i - lo] holds parameter index i of [lo, hi)
+      h.resize((size_t)(hi - lo));
+      if (hi > lo) SERL_HIP(hipMemcpy(h.data(), dev, sizeof(float) * h.size(), hipMemcpyDeviceToHost));
+      for (const Leaf& l : a->theta_leaves) {
+        if (l.cols == 0 || l.span() == l.count || l.off < lo || l.off >= hi) continue;   // (any padding at all, pad ROWS of a one-block leaf included)
+        for (long i = 0; i < l.n; ++i)
+          for (long r = 0; r < l.rows_p; ++r)
+            for (long cc = (r < l.rows ? l.cols : 0); cc < l.ld; ++cc) {
+              const float v = std::fabs(h[(size_t)(l.off - lo + (i * l.rows_p + r) * l.ld + cc)]);
+              worst = std::isnan(v) ? INFINITY : std::max(worst, v);
+            }
+      }
+      return SERL_OK;
+    };
+    RC(scan(a->theta, 0, o.P)); RC(scan(a->theta_t, 0, o.P));
+    RC(scan(a->m_c, 0, o.Pc)); RC(scan(a->v_c, 0, o.Pc)); RC(scan(a->Gc, 0, o.Pc));
+    RC(scan(a->m_a, o.Pa0, o.Pa1)); RC(scan(a->v_a, o.Pa0, o.Pa1)); RC(scan(a->Ga, o.Pa0, o.Pa1));
+    host_out[0] = worst;
     return SERL_OK;
   }
   if (w == "g_critic") { p = a->Gc; n = o.Pc; }

@@ -14,6 +14,8 @@ struct DenseLn {
   long W, b, g, be;      // group 0's kernel [K][N], bias, LayerNorm scale and LayerNorm bias: offsets into a parameter vector
   long w_gs, p_gs;       // floats from one group's kernel, and from one group's three vectors, to the next group's
   int groups, K, N, act; // act: kAct*
+  int Nt;                // the layer's true width, Nt <= N.  Nt < N: a ragged layer stored N = 64 ceil(Nt / 64) wide, columns [Nt, N)
+                         // of its kernel and vectors zero (and rows [Kt, K) of its kernel, where its input is ragged too)
   int ln;                // 1: LayerNorm between Dense and activation; 0: none (mlp.py:29-30) -- g and be are then -1, no leaves
   float keep;            // Dropout between Dense and LayerNorm (mlp.py:27-28): float32(1 - rate), the rate a double in (0, 1) as the
                          // reference's keep_prob = 1.0 - rate is one -- what its bernoulli compares with and its division divides by; 0: none
@@ -38,15 +40,21 @@ inline LnDrop layer_drop(const DenseLn& L, const DenseLnDrop& s) {
   return d;
 }
 // Appends the layer's four leaves -- `groups` kernels, biases, scales and shifts back to back in each -- at `off`, which moves
-// behind them.  layer_norm false: the kernels and biases alone.
+// behind them.  layer_norm false: the kernels and biases alone.  Kt / Nt (0: K / N): the true extents of a ragged layer, whose
+// leaves are boxes [Kt][Nt] and [Nt] inside the storage [K][N] and [N] (param_arena.h).
 inline DenseLn add_dense_ln_leaves(std::vector<Leaf>& v, long& off, const std::string& kernel, const std::string& bias,
-                                   const std::string& ln, int groups, int K, int N, int act, double drop = 0.0, bool layer_norm = true) {
+                                   const std::string& ln, int groups, int K, int N, int act, double drop = 0.0, bool layer_norm = true,
+                                   int Kt = 0, int Nt = 0) {
   DenseLn l{};
-  l.W = add_leaf(v, off, kernel, (long)groups * K * N);
-  l.b = add_leaf(v, off, bias, (long)groups * N);
+  if (!Kt) Kt = K;
+  if (!Nt) Nt = N;
+  l.Nt = Nt;
+  const auto vec = [&](const std::string& name) { return add_leaf_box(v, off, name, groups, 1, Nt, 1, N); };
+  l.W = add_leaf_box(v, off, kernel, groups, Kt, Nt, K, N);
+  l.b = vec(bias);
   l.ln = layer_norm ? 1 : 0;
-  l.g = layer_norm ? add_leaf(v, off, ln + "/scale", (long)groups * N) : -1;
-  l.be = layer_norm ? add_leaf(v, off, ln + "/bias", (long)groups * N) : -1;
+  l.g = layer_norm ? vec(ln + "/scale") : -1;
+  l.be = layer_norm ? vec(ln + "/bias") : -1;
   l.w_gs = groups > 1 ? (long)K * N : 0; l.p_gs = groups > 1 ? N : 0; l.groups = groups; l.K = K; l.N = N; l.act = act;
   l.keep = drop > 0.0 ? (float)(1.0 - drop) : 0.f;
   return l;
@@ -78,6 +86,7 @@ inline LnFwdArgs layer_ln_fwd(const DenseLn& L, const float* P, const DenseLnIo&
   l.rows = L.groups * rows; l.rows_per_group = rows;
   l.y = t.y; l.ld_y = t.ld_y; l.y_goff = t.y_goff;
   l.xhat = t.xhat; l.rstd = t.rstd; l.act = L.act;
+  l.d = L.Nt < L.N ? L.Nt : 0;
   l.drop = layer_drop(L, site);
   return l;
 }
@@ -95,6 +104,7 @@ inline LnBwdArgs layer_ln_bwd(const DenseLn& L, const float* P, const DenseLnIo&
   if (L.ln) { l.gamma = P + L.g; l.beta = P + L.be; }   // (else nullptr: the plain row, which writes dx alone)
   l.rows = L.groups * rows; l.rows_per_group = rows; l.D = L.N;
   l.dx = d.dpre; l.dg = d.dg; l.act = L.act;
+  l.d = L.Nt < L.N ? L.Nt : 0;
   l.drop = layer_drop(L, site);
   return l;
 }

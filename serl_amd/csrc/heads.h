@@ -22,6 +22,10 @@ int reduce_slabs(const float* slabs, int S, long slab_stride, int groups, int ro
                  hipStream_t stream, float scale = 1.0f);
 
 // D: the row width of every instance, a multiple of 64 in [64, 1024] (one wave per row, D / 64 columns per lane)
+// RAGGED rows (an instance's d != 0; all instances of a launch or none): the row's true width is d < D and columns [d, D) are zero
+// padding -- of the bias, scale, shift and of the kernel's columns, hence of the slabs.  The statistics divide by d; everything else
+// is the on-grid row, which leaves y == 0 in the pads (gamma == beta == 0 and act(0) == 0).  The backward divides by d and writes
+// dx = 0 in the pads (the on-grid row would leave rstd * (-m1 - xhat * m2) there).  Plain rows need neither.  No Dropout.
 // Instances without gamma and beta are LayerNorm-free MLP layers (mlp.py:29-30; plain_row): y = act(bias + slabs), the same riders,
 // the pre-activation in xhat, rstd not written.  All instances of a launch are plain or none is; plain ones carry no Dropout.
 int ln_fwd_multi(const LnFwdArgs* a, int n, int D, hipStream_t stream);
@@ -49,6 +53,7 @@ struct LnBwdArgs {
   float* dx;  // [rows][D] gradient wrt the pre-activation
   float* dg;  // [rows][D] dy * act'(pre): dy*(1-y^2) for tanh  (-> dbeta = colsum(dg), dgamma = colsum(dg*xhat))
   int act;            // kAct* of the forward row (per instance, uniform over a wave)
+  int d;              // as LnFwdArgs::d: 0, or the true width of a zero-padded row (in the hole behind act)
   const float* beta;  // kActSwish only: the forward's beta (addressed like gamma), to recompute pre = gamma*xhat + beta
   int D;          // the row width, a multiple of 64 in [64, 1024]
   int dq_inline;  // rank-1 mode: dq[row] = 2 (q - y) inv_norm computed from the LossArgs of the launch

@@ -306,7 +306,9 @@ __device__ __forceinline__ void ln_dropout(const LnDrop& d, long lrow, int c0, f
 // Returns the fused row-dot (dot_out's value, in every lane; 0 without one).
 // DROP: the instantiation of the launches that carry an instance with Dropout (ln_fwd_drop_kernel); the rows of every other launch
 // are the DROP = false instantiation, whose text -- and therefore whose contraction into fused multiply-adds -- is what it was.
-template <int VPL, bool BLOCKED, bool DROP = false>
+// RAGGED: the instantiation of a zero-padded row of true width a.d < D (heads.h): the statistics divide by a.d.  Nothing else
+// differs: the pads of the bias and of the slabs are 0 and add nothing to the sums, and gamma == beta == 0 there gives y == act(0) == 0.
+template <int VPL, bool BLOCKED, bool DROP = false, bool RAGGED = false>
 __device__ __forceinline__ float ln_row(const LnFwdArgs& a, int row, int lane) {
   constexpr int D = 64 * VPL, kStep = kLnStep<BLOCKED>;
   const int grp = row / a.rows_per_group;
@@ -324,7 +326,8 @@ __device__ __forceinline__ float ln_row(const LnFwdArgs& a, int row, int lane) {
   for (int j = 0; j < VPL; ++j) { s1 += v[j]; s2 += v[j] * v[j]; }
   wave_sum2(s1, s2);
   float mean, rstd;
-  ln_mean_rstd<D>(s1, s2, mean, rstd);
+  if constexpr (RAGGED) ln_mean_rstd_n(s1, s2, a.d, mean, rstd);
+  else ln_mean_rstd<D>(s1, s2, mean, rstd);
   float d = 0.f;
 #pragma unroll
   for (int j = 0; j < VPL; ++j) {   // v: the row's values, then its pre-activations, then y
@@ -1038,6 +1041,14 @@ __global__ __launch_bounds__(256) void ln_fwd_drop_kernel(Multi<LnFwdArgs> mv) {
   if (row >= a.rows) return;
   ln_row<VPL, BLOCKED, true>(a, row, lane);
 }
+// ... of a launch whose instances are zero-padded rows of a true width off the 64 grid (LnFwdArgs::d)
+template <int VPL, bool BLOCKED>
+__global__ __launch_bounds__(256) void ln_fwd_ragged_kernel(Multi<LnFwdArgs> mv) {
+  const LnFwdArgs& a = mv.v[blockIdx.y];
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (row >= a.rows) return;
+  ln_row<VPL, BLOCKED, false, true>(a, row, lane);
+}
 // ... of a launch whose instances are LayerNorm-free layers (mlp.py:29-30, use_layer_norm=False): plain_row in the same grid
 template <int VPL, bool BLOCKED>
 __global__ __launch_bounds__(256) void plain_fwd_kernel(Multi<LnFwdArgs> mv) {
@@ -1114,6 +1125,9 @@ int ln_fwd_multi(const LnFwdArgs* as, int n, int D, hipStream_t stream) {
   int rows = 0;
   bool drop = false;
   for (int i = 0; i < n; ++i) {
+    // (the instances of a launch are evaluations of ONE layer: all of them are ragged, at one true width, or none is)
+    SERL_REQUIRE(as[i].d == as[0].d && as[i].d >= 0 && as[i].d < D, "LayerNorm row: instance %d has the true width %d, instance 0 %d, in rows of %d",
+                 i, as[i].d, as[0].d, D);
     SERL_REQUIRE(as[i].act >= 0 && as[i].act < kActCount, "LayerNorm row: activation code %d is not tanh (0), relu (1) or swish (2)", as[i].act);
     SERL_REQUIRE(ln_drop_ok(as[i].drop, as[i].rows_per_group), "LayerNorm row: bad Dropout description (mode %d, keep %g)", as[i].drop.mode, as[i].drop.keep);
     mv.v[i] = as[i];
@@ -1128,6 +1142,9 @@ int ln_fwd_multi(const LnFwdArgs* as, int n, int D, hipStream_t stream) {
   if (!as[0].gamma) {
     SERL_REQUIRE(!drop, "plain row (no LayerNorm) with Dropout: not served");
     SERL_LN_LAUNCH(D, (plain_fwd_kernel<1, false>), (plain_fwd_kernel<4, true>), plain_fwd_kernel, grid, dim3(256), 0, stream, mv)
+  } else if (as[0].d) {
+    SERL_REQUIRE(!drop, "ragged LayerNorm row (true width %d in %d) with Dropout: not served", as[0].d, D);
+    SERL_LN_LAUNCH(D, (ln_fwd_ragged_kernel<1, false>), (ln_fwd_ragged_kernel<4, true>), ln_fwd_ragged_kernel, grid, dim3(256), 0, stream, mv)
   } else if (drop) SERL_LN_LAUNCH(D, (ln_fwd_drop_kernel<1, false>), (ln_fwd_drop_kernel<4, true>), ln_fwd_drop_kernel, grid, dim3(256), 0, stream, mv)
   else SERL_LN_LAUNCH(D, (ln_fwd_kernel<1, false>), (ln_fwd_kernel<4, true>), ln_fwd_kernel, grid, dim3(256), 0, stream, mv)
   SERL_HIP(hipGetLastError());
@@ -1206,7 +1223,9 @@ __device__ void critic_loss_body(const LossArgs& L, float (*red)[256]) {
 // backward of ONE row of y = act(gamma*xhat + beta), xhat = (x-mean)*rstd, by one wave, in the lane-to-column layout of ln_row:
 //   dg = dy*act'(pre) (ln_act_grad; tanh: dy*(1-y^2));  dxhat = dg*gamma;  dx = rstd*(dxhat - mean(dxhat) - xhat*mean(dxhat*xhat))
 // a lane sums its columns in ascending order, then the xor butterfly.  L: the launch's critic loss, read by a dq_inline row alone.
-template <int VPL, bool BLOCKED, bool DROP = false>
+// RAGGED: a zero-padded row of true width a.d < D (heads.h).  dy is 0 in the pads (the rows of the consumer's kernel are), so dg,
+// dxhat and both sums are what the d live columns give; the means divide by a.d, and dx is 0 in the pads.
+template <int VPL, bool BLOCKED, bool DROP = false, bool RAGGED = false>
 __device__ __forceinline__ void ln_bwd_row(const LnBwdArgs& a, const LossArgs& L, int row, int lane) {
   const int grp = row / a.rows_per_group;
   constexpr int D = VPL * 64;
@@ -1232,8 +1251,19 @@ __device__ __forceinline__ void ln_bwd_row(const LnBwdArgs& a, const LossArgs& L
     s2 += dxh[j] * xh[j];
   }
   wave_sum2(s1, s2);
-  const float m1 = s1 * (1.0f / D), m2 = s2 * (1.0f / D), rstd = a.rstd[row];
-  if constexpr (!DROP) {
+  float m1, m2;
+  if constexpr (RAGGED) { const float inv = 1.0f / (float)a.d; m1 = s1 * inv; m2 = s2 * inv; }
+  else { m1 = s1 * (1.0f / D); m2 = s2 * (1.0f / D); }
+  const float rstd = a.rstd[row];
+  if constexpr (RAGGED) {
+    static_assert(!DROP, "a ragged row carries no Dropout");
+#pragma unroll
+    for (int j = 0; j < VPL; ++j) {
+      const int col = c0 + kLnStep<BLOCKED> * j;
+      a.dx[(long)row * D + col] = col < a.d ? rstd * (dxh[j] - m1 - xh[j] * m2) : 0.f;
+      a.dg[(long)row * D + col] = dg[j];
+    }
+  } else if constexpr (!DROP) {
 #pragma unroll
     for (int j = 0; j < VPL; ++j) {
       const int col = c0 + kLnStep<BLOCKED> * j;
@@ -1320,6 +1350,18 @@ __global__ __launch_bounds__(256) void ln_bwd_drop_kernel(Multi<LnBwdArgs> mv, L
   else ln_bwd_row<1, false, true>(a, loss, row, lane);
 }
 
+// ... of a launch whose instances are zero-padded rows of one true width off the 64 grid (LnBwdArgs::d), all of them stored
+// 64 * VPL wide (an MLP layer is alone in its launch: no mixed widths); the critic-loss rider in the same place
+template <int VPL, bool BLOCKED>
+__global__ __launch_bounds__(256) void ln_bwd_ragged_kernel(Multi<LnBwdArgs> mv, LossArgs loss) {
+  __shared__ float red[4][256];
+  if (loss.on && blockIdx.y == 0 && blockIdx.x == gridDim.x - 1) { critic_loss_body(loss, red); return; }
+  const LnBwdArgs& a = mv.v[blockIdx.y];
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (row >= a.rows) return;
+  ln_bwd_row<VPL, BLOCKED, false, true>(a, loss, row, lane);
+}
+
 // ... of a launch whose instances are LayerNorm-free layers, all of the width 64 * VPL (an MLP layer is alone in its launch):
 // plain_bwd_row in the same grid, the critic-loss rider in the same place
 template <int VPL, bool BLOCKED>
@@ -1350,6 +1392,10 @@ int ln_bwd_multi(const LnBwdArgs* as, int n, const LossArgs& loss, hipStream_t s
   const auto mixes = [](int D) { return D == 64 || D == 256; };
   for (int i = 0; i < n; ++i) {
     SERL_REQUIRE(SERL_LN_WIDTH_OK(as[i].D), "LayerNorm width %d unsupported (a multiple of 64 in [64, 1024])", as[i].D);
+    // (a ragged launch is one MLP layer: one storage width, one true width, no Dropout)
+    SERL_REQUIRE(as[i].d >= 0 && as[i].d < as[i].D && as[i].d == as[0].d && (!as[i].d || (as[i].D == as[0].D && as[i].drop.mode == kLnDropNone)),
+                 "LayerNorm backward: instance %d has the true width %d in rows of %d, instance 0 %d in rows of %d; or a ragged row with Dropout",
+                 i, as[i].d, as[i].D, as[0].d, as[0].D);
     SERL_REQUIRE(!as[i].dq_inline || (loss.on && as[i].dq_w && as[i].rows == loss.E * loss.B && as[i].rows_per_group == loss.B),
                  "inline dQ needs the loss arguments of the launch");
     // (the swish backward recomputes its pre-activation: it reads beta where the forward did)
@@ -1369,6 +1415,7 @@ int ln_bwd_multi(const LnBwdArgs* as, int n, const LossArgs& loss, hipStream_t s
   }
   const dim3 grid(cdiv(rows, 4) + (loss.on ? 1 : 0), n);
   if (!as[0].gamma) SERL_LN_LAUNCH(as[0].D, (plain_bwd_kernel<1, false>), (plain_bwd_kernel<4, true>), plain_bwd_kernel, grid, dim3(256), 0, stream, mv, loss)
+  else if (as[0].d) SERL_LN_LAUNCH(as[0].D, (ln_bwd_ragged_kernel<1, false>), (ln_bwd_ragged_kernel<4, true>), ln_bwd_ragged_kernel, grid, dim3(256), 0, stream, mv, loss)
   else if (drop) SERL_LN_LAUNCH(as[0].D, (ln_bwd_drop_kernel<kLnMixed, false>), (ln_bwd_drop_kernel<kLnMixed, false>), ln_bwd_drop_kernel, grid, dim3(256), 0, stream, mv, loss)
   else if (n == 1 && !loss.on && as[0].D == 256) SERL_LAUNCH_CHAIN((ln_bwd_one_kernel<4, true>), grid, dim3(256), 0, stream, as[0]);
   else if (n == 1 && !loss.on && as[0].D == 64) SERL_LAUNCH_CHAIN((ln_bwd_one_kernel<1, false>), grid, dim3(256), 0, stream, as[0]);

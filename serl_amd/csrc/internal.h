@@ -137,6 +137,8 @@ struct LnFwdArgs {
   const float* dot_w; const float* dot_b; float* dot_out;
   long dot_gstride, dot_b_gstride;  // 0: one head shared by all groups (DrQ critic); else per-group heads (ensemblized Critic)
   int act;               // kAct*: the row's activation, per instance (one launch may mix them) and uniform over a wave
+  int d;                 // 0: every column of the row is live.  Else the row's true width, 1 <= d < D: columns [d, D) are zero padding
+                         // (a ragged MLP layer, heads.h); read by the ragged instantiations alone.  (Lies in the hole behind act.)
   LnDrop drop;           // Dropout on the gathered row, in front of the statistics (zero-initialised: none)
 };
 // The activation behind a LayerNorm row (mlp.py:19-31: `activations`, a callable or the name of one in flax.linen).  tanh: the MLPs

@@ -19,4 +19,13 @@ __device__ __forceinline__ void ln_mean_rstd(float s1, float s2, float& mean, fl
   rstd = rsqrtf(var + 1e-6f);
 }
 
+// ... of a row whose `d` live values lie in a wider, zero-padded row: the pads add nothing to s1 and s2, the divisor is d
+__device__ __forceinline__ void ln_mean_rstd_n(float s1, float s2, int d, float& mean, float& rstd) {
+  const float inv = 1.0f / (float)d;
+  mean = s1 * inv;
+  const float mean2 = s2 * inv;
+  const float var = fmaxf(mean2 - mean * mean, 0.f);
+  rstd = rsqrtf(var + 1e-6f);
+}
+
 }  // namespace serl

@@ -8,10 +8,18 @@
 
 namespace serl {
 
-// A named slice [off, off + count) of a flat float parameter vector.
+// A named slice of a flat float parameter vector that starts at `off`.  `count` is the number of the leaf's own elements.  Most
+// leaves are the contiguous [off, off + count).  A BOX leaf (a ragged MLP layer) is `n` blocks of `rows` x
+// `cols` elements stored inside n blocks of rows_p x ld floats: element (i, r, c) lies at off + (i * rows_p + r) * ld + c, and the
+// floats of the storage outside the box are padding that is zero and stays zero.  span() is the storage, what `off` advances by.
 struct Leaf {
   std::string name;
   long off, count;
+  long n = 1, rows = 1, cols = 0, rows_p = 1, ld = 0;   // cols == 0: contiguous, the box fields say nothing
+  // whether a copy of the leaf has to be strided: padding BEHIND the last row of a one-block leaf (rows_p > rows with ld == cols)
+  // leaves the leaf's elements one contiguous run; span() != count is the test for "has padding"
+  bool boxed() const { return cols != 0 && (ld != cols || (n > 1 && rows_p != rows)); }
+  long span() const { return cols == 0 ? count : n * rows_p * ld; }
 };
 
 // Appends a leaf of `count` floats at `off` and moves `off` behind it; returns the leaf's offset.
@@ -19,6 +27,15 @@ inline long add_leaf(std::vector<Leaf>& v, long& off, std::string name, long cou
   v.push_back({std::move(name), off, count});
   off += count;
   return off - count;
+}
+
+// Appends a box leaf (Leaf, above) and moves `off` behind its storage; returns the leaf's offset.
+inline long add_leaf_box(std::vector<Leaf>& v, long& off, std::string name, long n, long rows, long cols, long rows_p, long ld) {
+  Leaf l{std::move(name), off, n * rows * cols};
+  l.n = n; l.rows = rows; l.cols = cols; l.rows_p = rows_p; l.ld = ld;
+  v.push_back(l);
+  off += l.span();
+  return l.off;
 }
 
 inline const Leaf* find(const std::vector<Leaf>& v, const char* name) {
@@ -82,6 +99,23 @@ inline int leaf_copy(float* dst, const float* src, long n, hipMemcpyKind kind, c
     return SERL_OK;
   }
   SERL_HIP(hipMemcpy(dst, src, (size_t)n * sizeof(float), kind));
+  return SERL_OK;
+}
+
+// ... of a leaf `l` whose device side `dev` (nullptr: as above) may be a box: the host side is the leaf's count elements, dense,
+// in (block, row, column) order; the padding of the storage is neither read nor written.
+inline int leaf_copy(float* dev, float* host_out, const float* host_in, const Leaf& l, hipMemcpyKind kind, const char* section,
+                     const char* nonzero_fmt) {
+  const bool up = kind == hipMemcpyHostToDevice;
+  if (!dev || !l.boxed())
+    return up ? leaf_copy(dev, host_in, l.count, kind, section, l.name.c_str(), nonzero_fmt)
+              : leaf_copy(host_out, dev, l.count, kind, section, l.name.c_str(), nonzero_fmt);
+  for (long i = 0; i < l.n; ++i) {
+    float* d = dev + i * l.rows_p * l.ld;
+    const long h = i * l.rows * l.cols;
+    if (up) SERL_HIP(hipMemcpy2D(d, l.ld * sizeof(float), host_in + h, l.cols * sizeof(float), l.cols * sizeof(float), l.rows, kind));
+    else SERL_HIP(hipMemcpy2D(host_out + h, l.cols * sizeof(float), d, l.ld * sizeof(float), l.cols * sizeof(float), l.rows, kind));
+  }
   return SERL_OK;
 }
 

@@ -54,26 +54,38 @@ SMALL_FEATURES = (3, 32, 64, 128, 256)   # SmallEncoder(features=(32, 64, 128, 2
 HIDDEN_WIDTHS = tuple(range(64, 1025, 64))   # serl_agent_cfg.hidden: one wave per LayerNorm row, hidden / 64 columns per lane
 
 
+RAGGED_WIDTHS = range(1, 1025)   # ... with serl_agent_opts.ragged_widths: a layer off the grid is stored 64 ceil(d / 64) wide, zero padded
+
+
 _PLAIN_HINT = "; without LayerNorm with mlp_plain=True"
 
 
-def mlp_hidden_width(critic_network_kwargs=None, policy_network_kwargs=None, mlp_plain=False) -> int:
+def _is_width(d):
+    return not isinstance(d, bool) and isinstance(d, (int, np.integer))
+
+
+def mlp_hidden_width(critic_network_kwargs=None, policy_network_kwargs=None, mlp_plain=False, mlp_ragged=False) -> int:
     """The one width h of the critic's and the policy's MLPs from the reference's `critic_network_kwargs` /
     `policy_network_kwargs` (hidden_dims=[h, h], LayerNorm, default [256, 256]).  Served: two layers of the same width, the same
     in both networks, a multiple of 64 from 64 to 1024; anything else raises NotImplementedError.  mlp_plain=True (the argument
-    of the same name of create_states / create_drq): use_layer_norm is mlp_layer_norms' to read."""
-    served = "served: hidden_dims=[h, h] with LayerNorm, h a multiple of 64 in [64, 1024], the same h for critic and policy"
+    of the same name of create_states / create_drq): use_layer_norm is mlp_layer_norms' to read.  mlp_ragged=True (likewise): h is
+    any integer in [1, 1024]; 0, a negative, 1025 and a width that is no integer are refused."""
+    grid = "any integer in [1, 1024] under mlp_ragged=True" if mlp_ragged else "a multiple of 64 in [64, 1024]"
+    served = f"served: hidden_dims=[h, h] with LayerNorm, h {grid}, the same h for critic and policy"
     widths = []
     for which, nk in (("critic_network_kwargs", critic_network_kwargs or {}), ("policy_network_kwargs", policy_network_kwargs or {})):
         if not mlp_plain and not nk.get("use_layer_norm", True):
             raise NotImplementedError(f"{which}: use_layer_norm=False ({served}{_PLAIN_HINT})")
-        dims = [int(d) for d in nk.get("hidden_dims", [256, 256])]
+        dims = list(nk.get("hidden_dims", [256, 256]))
+        if mlp_ragged and not all(_is_width(d) for d in dims):
+            raise NotImplementedError(f"{which}: hidden_dims={dims} holds a width that is no integer ({served})")
+        dims = [int(d) for d in dims]
         if len(dims) != 2:
             raise NotImplementedError(f"{which}: hidden_dims={dims} has {len(dims)} layers ({served})")
         if dims[0] != dims[1]:
             raise NotImplementedError(f"{which}: hidden_dims={dims} has two different layer widths ({served})")
-        if dims[0] not in HIDDEN_WIDTHS:
-            raise NotImplementedError(f"{which}: width {dims[0]} is off the grid ({served})")
+        if dims[0] not in (RAGGED_WIDTHS if mlp_ragged else HIDDEN_WIDTHS):
+            raise NotImplementedError(f"{which}: width {dims[0]} is {'outside [1, 1024]' if mlp_ragged else 'off the grid'} ({served})")
         widths.append(dims[0])
     if widths[0] != widths[1]:
         raise NotImplementedError(f"critic width {widths[0]} and policy width {widths[1]} differ ({served})")
@@ -83,13 +95,15 @@ def mlp_hidden_width(critic_network_kwargs=None, policy_network_kwargs=None, mlp
 MAX_MLP_LAYERS = 4   # SERL_MAX_MLP_LAYERS
 
 
-def mlp_layer_dims(critic_network_kwargs=None, policy_network_kwargs=None, mlp_plain=False):
+def mlp_layer_dims(critic_network_kwargs=None, policy_network_kwargs=None, mlp_plain=False, mlp_ragged=False):
     """(critic, policy): the `hidden_dims` of the reference's MLP (networks/mlp.py:19-31 loops over a list of any length) from its
     two network kwargs, as tuples of ints: what create_states / create_drq read with mlp_shapes=True (without the switch
     mlp_hidden_width reads and refuses as it always did).  Default [256, 256].  Served: 1 to MAX_MLP_LAYERS layers per network,
     every width a multiple of 64 in [64, 1024], the two lists independent, LayerNorm on; anything else raises NotImplementedError
-    from the arguments alone.  mlp_plain=True: use_layer_norm is mlp_layer_norms' to read."""
-    served = (f"served: hidden_dims of 1 to {MAX_MLP_LAYERS} layers with LayerNorm, every width a multiple of 64 in [64, 1024], "
+    from the arguments alone.  mlp_plain=True: use_layer_norm is mlp_layer_norms' to read.  mlp_ragged=True: every width is any
+    integer in [1, 1024]."""
+    grid = "any integer in [1, 1024] under mlp_ragged=True" if mlp_ragged else "a multiple of 64 in [64, 1024]"
+    served = (f"served: hidden_dims of 1 to {MAX_MLP_LAYERS} layers with LayerNorm, every width {grid}, "
               "the critic's list independent of the policy's")
     out = []
     for which, nk in (("critic_network_kwargs", critic_network_kwargs or {}), ("policy_network_kwargs", policy_network_kwargs or {})):
@@ -100,10 +114,11 @@ def mlp_layer_dims(critic_network_kwargs=None, policy_network_kwargs=None, mlp_p
         if not 1 <= len(dims) <= MAX_MLP_LAYERS:
             raise NotImplementedError(f"{which}: hidden_dims={dims} has {len(dims)} layers ({served})")
         for d in dims:
-            if isinstance(d, bool) or not isinstance(d, (int, np.integer)):
+            if not _is_width(d):
                 raise NotImplementedError(f"{which}: width {d!r} in hidden_dims={dims} is no integer ({served})")
-            if int(d) not in HIDDEN_WIDTHS:
-                raise NotImplementedError(f"{which}: width {int(d)} in hidden_dims={dims} is off the grid ({served})")
+            if int(d) not in (RAGGED_WIDTHS if mlp_ragged else HIDDEN_WIDTHS):
+                raise NotImplementedError(f"{which}: width {int(d)} in hidden_dims={dims} is "
+                                          f"{'outside [1, 1024]' if mlp_ragged else 'off the grid'} ({served})")
         out.append(tuple(int(d) for d in dims))
     return tuple(out)
 
@@ -247,7 +262,9 @@ class NetSpec:
     AgentCore takes as keywords and hands to serl_agent_create_opts (to_c), and what the leaf tables are built from (leaf_kwargs).
     The defaults are what utils/launcher.py configures, and the all-zero serl_agent_opts.
     critic_dims / policy_dims: None means (hidden, hidden); with both None the library is sent n_layers = 0, "two layers of
-    cfg.hidden", the agent every call without mlp_shapes makes.  fixed_std: None, or with "fixed" act_dim float32 values as floats."""
+    cfg.hidden", the agent every call without mlp_shapes makes.  fixed_std: None, or with "fixed" act_dim float32 values as floats.
+    ragged: serl_agent_opts.ragged_widths -- the widths are any integers in [1, 1024]; network_spec sets it where a width is off the
+    64 grid and nowhere else, so that widths on the grid through mlp_ragged=True give the NetSpec, and the agent, of the call without."""
     std_parameterization: str = "exp"
     tanh_squash_distribution: bool = True
     fixed_std: Optional[Tuple[float, ...]] = None
@@ -260,11 +277,17 @@ class NetSpec:
     policy_dims: Optional[Tuple[int, ...]] = None
     critic_layer_norm: bool = True
     policy_layer_norm: bool = True
+    ragged: bool = False
 
     @property
     def dims(self):
         """(critic, policy) width tuples, a list left out resolved"""
         return resolve_mlp_dims(self.hidden, self.critic_dims, self.policy_dims)
+
+    @property
+    def off_grid(self):
+        """whether a width of either network is no multiple of 64"""
+        return any(d % 64 for net in self.dims for d in net)
 
     def check(self):
         """A positive dropout_rate (mlp_dropout=True) is served in two LayerNorm MLPs of one [h, h] under a policy head with std
@@ -274,6 +297,11 @@ class NetSpec:
         if not any(r > 0 for r in rates):
             return self
         cd, pd = self.dims
+        if self.ragged and self.off_grid:
+            raise NotImplementedError(
+                f"mlp_ragged=True with mlp_dropout=True and a positive dropout_rate (critic {rates[0]!r} / policy {rates[1]!r}): critic "
+                f"hidden_dims={list(cd)}, policy hidden_dims={list(pd)} (served with Dropout: widths that are multiples of 64; the "
+                "keep-masks are laid out for rows of such a width)")
         if not (len(cd) == 2 and cd[0] == cd[1] and cd == pd):
             raise NotImplementedError(
                 f"mlp_shapes=True with mlp_dropout=True and a positive dropout_rate: critic hidden_dims={list(cd)}, policy "
@@ -326,25 +354,28 @@ class NetSpec:
             net.no_layer_norm, net.dropout = 0 if ln else 1, rate
         if self.fixed_std is not None:
             o.fixed_std = (ctypes.c_float * len(self.fixed_std))(*self.fixed_std)
+        o.ragged_widths = 1 if self.ragged else 0
         return o
 
 
 def network_spec(critic_network_kwargs, policy_network_kwargs, policy_kwargs, act_dim, *, mlp_dropout=False, mlp_shapes=False,
-                 mlp_plain=False, policy_fixed=False) -> NetSpec:
-    """The checked NetSpec of create_states' / create_drq's three kwargs dicts under their four switches; every refusal is raised
-    from the arguments alone, in the order of the lines below."""
+                 mlp_plain=False, policy_fixed=False, mlp_ragged=False) -> NetSpec:
+    """The checked NetSpec of create_states' / create_drq's three kwargs dicts under their five switches; every refusal is raised
+    from the arguments alone, in the order of the lines below.  mlp_ragged=True: every width read below is any integer in
+    [1, 1024] (mlp.py:19-31 takes any list); without it the 64 grid, as always."""
     # policy_fixed=True: "fixed" / fixed_std are read (actor_critic_nets.py:189-192); else refused, as always
     std_param, squash, fixed = policy_mode_fixed(policy_kwargs, act_dim) if policy_fixed else (*policy_mode(policy_kwargs), None)
     # mlp_shapes=True: each network's own depth and per-layer widths (mlp.py:19-31); else the one width of [h, h], as always
-    dims = mlp_layer_dims(critic_network_kwargs, policy_network_kwargs, mlp_plain) if mlp_shapes else (None, None)
-    hidden = dims[0][0] if mlp_shapes else mlp_hidden_width(critic_network_kwargs, policy_network_kwargs, mlp_plain)
+    dims = mlp_layer_dims(critic_network_kwargs, policy_network_kwargs, mlp_plain, mlp_ragged) if mlp_shapes else (None, None)
+    hidden = dims[0][0] if mlp_shapes else mlp_hidden_width(critic_network_kwargs, policy_network_kwargs, mlp_plain, mlp_ragged)
     # mlp_plain=True: each network's own use_layer_norm (mlp.py:29-30); else LayerNorm in both, as always
     lns = mlp_layer_norms(critic_network_kwargs, policy_network_kwargs) if mlp_plain else (True, True)
     acts = mlp_activations(critic_network_kwargs, policy_network_kwargs, mlp_dropout)
     rates = mlp_dropout_rates(critic_network_kwargs, policy_network_kwargs) if mlp_dropout else (0.0, 0.0)
     if dims == ((hidden, hidden), (hidden, hidden)):
         dims = (None, None)    # [h, h] twice: the very agent the call without the switch makes
-    return NetSpec(std_param, squash, None if fixed is None else tuple(float(x) for x in fixed), *acts, *rates, hidden, *dims, *lns).check()
+    spec = NetSpec(std_param, squash, None if fixed is None else tuple(float(x) for x in fixed), *acts, *rates, hidden, *dims, *lns)
+    return dataclasses.replace(spec, ragged=bool(mlp_ragged) and spec.off_grid).check()
 
 
 def _policy_std_shapes(Hd, A, std_parameterization):
