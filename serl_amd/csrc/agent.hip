@@ -2054,6 +2054,14 @@ int serl_agent_debug_get(serl_agent* a, const char* what, float* host_out, int64
     host_out[0] = (float)nz;
     return SERL_OK;
   }
+  if (w == "small_plan") {
+    // The launch plan of the SmallEncoder's last backward pass, kept on the host: [row chunks of layer 0's weight gradient, K-split
+    // of the weight-gradient GEMM of layers 1, 2, 3], as launched; zeros before the first backward pass.
+    SERL_REQUIRE(a->small, "tap 'small_plan' belongs to the SmallEncoder");
+    SERL_REQUIRE(count == kSmallLayers, "tap 'small_plan' holds %d values", kSmallLayers);
+    for (int l = 0; l < kSmallLayers; ++l) host_out[l] = (float)a->sws.last_plan[l];
+    return SERL_OK;
+  }
   if (w == "pad_max_abs") {
     // The invariant of the ragged layout: every float of a box leaf's storage outside its box is exactly 0 in
     // the parameters, the target parameters, both Adam moments of the critic's and the actor's optimizer and both gradient
@@ -2112,8 +2120,12 @@ int serl_agent_debug_get(serl_agent* a, const char* what, float* host_out, int64
     p = a->s[l].dpre;
     n = std::max<long>(l < critic.n_layers ? (long)c.ensemble * c.batch * critic.dims[l] : 0, l < policy.n_layers ? (long)c.batch * policy.dims[l] : 0);
   }
-  // SmallEncoder layer 0's ReLU output of the LAST encoder pass, [n_cam][images of that pass][h1][w1][32]
-  else if (w == "small_act0" && a->small) { p = a->sws.act[0]; n = (long)c.n_cam * c.batch * a->sws.d.h[1] * a->sws.d.w[1] * kSmallFeat[1]; }
+  // SmallEncoder layer l's ReLU output of the LAST encoder pass, [n_cam][images of that pass][h_{l+1}][w_{l+1}][cout_l]
+  else if (w.rfind("small_act", 0) == 0 && w.size() == 10 && w[9] >= '0' && w[9] < '0' + kSmallLayers && a->small) {
+    const int l = w[9] - '0';
+    p = a->sws.act[l];
+    n = (long)c.n_cam * c.batch * a->sws.d.h[l + 1] * a->sws.d.w[l + 1] * kSmallFeat[l + 1];
+  }
   else { set_error("unknown debug tap '%s'", what); return SERL_ERR_INVALID; }
   SERL_REQUIRE(count <= n && count > 0, "tap '%s' holds %ld floats, asked for %lld", what, n, (long long)count);
   SERL_HIP(hipDeviceSynchronize());

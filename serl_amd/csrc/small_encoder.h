@@ -36,6 +36,9 @@ struct SmallWorkspace {
   // layer 0 runs directly on the u8 frames (no im2col matrix): the backward pass re-reads the frames of the last forward pass
   const uint8_t* last_frames = nullptr;
   long last_frame_cam_stride = 0;
+  // the launch plan of the last small_backward, for the debug tap small_plan: layer 0's row chunks, then the K-split of the
+  // weight-gradient GEMMs of layers 1..3 as launched (after the halving against slabs_cap); 0 before the first backward pass
+  int last_plan[kSmallLayers] = {0, 0, 0, 0};
   size_t bytes = 0;
 };
 size_t small_workspace_bytes(int max_images, int H, int W, int T = 1);

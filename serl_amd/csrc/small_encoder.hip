@@ -527,6 +527,7 @@ int small_backward(SmallWorkspace& ws, const float* P, long conv_off, long cam_s
       SERL_REQUIRE(ws.last_frames != nullptr, "small_backward without a forward pass");
       const int chunks = (int)std::min<long>(kConv0Chunks, std::max<long>(1, rows_cam / 256));   // one workgroup per chunk (latency-bound: many)
       const int n_elem = (27 * ws.T + 1) * 32;
+      ws.last_plan[0] = chunks;
       ProfScope prof0("small_conv0_wgrad", stream);   // (inside small_encoder_bwd: layer 0's two launches)
       SERL_REQUIRE((long)chunks * n_cam * n_elem <= ws.slabs_cap, "SmallEncoder: layer 0's partials exceed the workspace");
 #define SERL_CONV0_STACK_WGRAD(TT)                                                                                                 \
@@ -553,6 +554,7 @@ int small_backward(SmallWorkspace& ws, const float* P, long conv_off, long cam_s
       // (deeper splits -- 512 or 256 rows per workgroup instead of 2048 -- were measured neutral in round 4: 5.84 / 5.87 / 5.89 ms)
       int S = (int)std::min<long>(64, std::max<long>(1, rows_cam / 2048));
       while (S > 1 && (long)S * n_cam * K * cout > ws.slabs_cap) S >>= 1;
+      ws.last_plan[l] = S;
       GemmDesc g{};
       {   // col_l^T gathered from the layer's input activations (still in the workspace)
         g.A = ws.act[l - 1]; g.sAm = 1; g.sAk = 0; g.sAb = 0;
