@@ -338,7 +338,19 @@ typedef struct serl_agent_cfg {
  *                  speak of true extents alone and never touch padding; what exposes storage says so below
  *                  (serl_agent_leaf_layout).  An agent whose widths all lie on the grid is the agent of ragged_widths 0, bit for
  *                  bit.  A positive dropout beside any width off the grid is refused (the keep-masks are laid out for widths on
- *                  the grid).  The entry points from before serl_agent_opts leave it 0. */
+ *                  the grid).  The entry points from before serl_agent_opts leave it 0.
+ *   no_proprio     0: EncodingWrapper(use_proprio=True), the agent as it always was.  1: use_proprio=False (common/encoding.py:53-72;
+ *                  the reference's own default in create_drq): the code is the concatenated camera codes alone, E = bottleneck *
+ *                  n_cam, critic/w1 has E + act_dim rows and actor/w1 E.  There is NO enc/proprio/... leaf, moment, target copy,
+ *                  gradient, snapshot or checkpoint entry, and no proprio scratch.  The state is never read: serl_batch.state and
+ *                  every dev_state argument may be NULL; cfg->state_dim is validated (>= 1) and matched against serl_batch as
+ *                  always, and otherwise unused; cfg->proprio_dim must still be 64 and is ignored.  An update launches no proprio
+ *                  rows and no kernel that does proprio work only; the actions rider of the encoder pass (the batch's actions into
+ *                  the critic input [enc | action]) rides on the SpatialLearnedEmbeddings launch as trailing workgroups where that
+ *                  launch carried the proprio rows, and is one column-copy launch where the proprio rows were a launch of their
+ *                  own.  n_cam == 0 with no_proprio 1 is SERL_ERR_INVALID (a state-only agent has no EncodingWrapper); a positive
+ *                  dropout in either MLP beside no_proprio 1 is SERL_ERR_UNSUPPORTED.  Any other value is SERL_ERR_INVALID.  The
+ *                  entry points from before serl_agent_opts leave it 0. */
 #define SERL_MAX_MLP_LAYERS 4
 typedef struct serl_mlp_opts {
   int act;
@@ -353,9 +365,11 @@ typedef struct serl_agent_opts {
   serl_mlp_opts critic, policy;
   const float* fixed_std;
   int ragged_widths;
+  int no_proprio;
 } serl_agent_opts;
 int serl_agent_create_opts(const serl_agent_cfg* cfg, const serl_agent_opts* opts, serl_agent** out);
 int serl_agent_live_trunk(serl_agent* a);   /* 1: live-trunk mode (above), 0: not, -1: NULL */
+int serl_agent_use_proprio(serl_agent* a);  /* 1: the agent has the proprio branch, 0: no_proprio (above), -1: NULL */
 /* The entry points from before serl_agent_opts: each sets the fields its arguments name and leaves the others 0.  The three that
  * take the width lists refuse a NULL list and never read cfg->hidden; all but serl_agent_create_fixed_std refuse SERL_STD_FIXED. */
 int serl_agent_create(const serl_agent_cfg* cfg, serl_agent** out);   /* no field: the all-zero opts */
@@ -758,7 +772,17 @@ typedef struct {
   float dropout;            /* Dropout rate behind SpatialLearnedEmbeddings (resnet_v1.py:351) */
   float std_min, std_max;   /* launcher.py:41-42 */
 } serl_bc_cfg;
-int serl_bc_create(const serl_bc_cfg* cfg, serl_bc** out);   /* BCAgent.create (bc.py:118-204) */
+int serl_bc_create(const serl_bc_cfg* cfg, serl_bc** out);   /* BCAgent.create (bc.py:118-204); the all-zero serl_bc_opts */
+/* no_proprio 1: EncodingWrapper(use_proprio=False), BCAgent.create's own default (bc.py:126).  The code is the camera codes alone:
+ * actor/w1 is (256 * n_cam, 256), there is no enc/proprio/... leaf or moment, the forward pass launches SpatialLearnedEmbeddings
+ * without proprio rows, and the update has no proprio input-gradient GEMM, LayerNorm backward, column sum or weight-gradient
+ * entry: the two MLP layers and the two heads alone train.  The state is never read: serl_batch.state and dev_state may be NULL
+ * (state_dim is validated and matched as always).  Any value but 0 and 1 is SERL_ERR_INVALID. */
+typedef struct serl_bc_opts {
+  int no_proprio;
+} serl_bc_opts;
+int serl_bc_create_opts(const serl_bc_cfg* cfg, const serl_bc_opts* opts, serl_bc** out);
+int serl_bc_use_proprio(serl_bc* c);   /* 1: proprio branch, 0: no_proprio, -1: NULL */
 int serl_bc_destroy(serl_bc* c);
 int serl_bc_num_leaves(serl_bc* c);
 int serl_bc_leaf_info(serl_bc* c, int i, char* name_out, int name_cap, int64_t* count, int* trainable);

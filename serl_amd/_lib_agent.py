@@ -33,7 +33,7 @@ class SerlMlpOpts(C.Structure):      # serl_mlp_opts: one network's MLP; all zer
 
 class SerlAgentOpts(C.Structure):    # serl_agent_opts (utils.init.NetSpec.to_c fills it); all zero = serl_agent_create(cfg)
     _fields_ = [("std_param", C.c_int), ("no_tanh", C.c_int), ("critic", SerlMlpOpts), ("policy", SerlMlpOpts),
-                ("fixed_std", P(C.c_float)), ("ragged_widths", C.c_int)]
+                ("fixed_std", P(C.c_float)), ("ragged_widths", C.c_int), ("no_proprio", C.c_int)]
 
 
 TX_INDEX = {"actor": 0, "critic": 1, "temperature": 2}   # SERL_TX_*
@@ -47,6 +47,10 @@ class SerlBcCfg(C.Structure):
         ("act_dim", C.c_int), ("max_batch", C.c_int),
         ("lr", C.c_float), ("dropout", C.c_float), ("std_min", C.c_float), ("std_max", C.c_float),
     ]
+
+
+class SerlBcOpts(C.Structure):       # serl_bc_opts; all zero = serl_bc_create(cfg)
+    _fields_ = [("no_proprio", C.c_int)]
 
 
 class SerlClassifierCfg(C.Structure):
@@ -104,6 +108,7 @@ SIGNATURES = {
     "serl_agent_set_mlp_noise": [vp, P(SerlMlpNoise)],
     "serl_agent_destroy": [vp],
     "serl_agent_live_trunk": [vp],
+    "serl_agent_use_proprio": [vp],   # 1 / 0 (serl_agent_opts.no_proprio) / -1
     "serl_agent_num_leaves": [vp],
     "serl_agent_leaf_info": [vp, i32, C.c_char_p, i32, P(i64)],
     "serl_agent_leaf_layout": [vp, C.c_char_p, P(i64)],   # out[5] = n, rows, cols, rows_p, ld (serl_mi355.h)
@@ -152,6 +157,8 @@ SIGNATURES = {
     "serl_snapshot_destroy": [vp],
     # behaviour cloning (csrc/bc.hip, serl_amd/agents/bc.py)
     "serl_bc_create": [P(SerlBcCfg), P(vp)],
+    "serl_bc_create_opts": [P(SerlBcCfg), P(SerlBcOpts), P(vp)],
+    "serl_bc_use_proprio": [vp],
     "serl_bc_destroy": [vp],
     "serl_bc_num_leaves": [vp],
     "serl_bc_leaf_info": [vp, i32, C.c_char_p, i32, P(i64), P(i32)],

@@ -21,7 +21,7 @@ import torch
 from .. import _lib
 from .. import jaxrng as J
 from .._handle import Handle, LazyInfo
-from .._lib_agent import SerlBcCfg
+from .._lib_agent import SerlBcCfg, SerlBcOpts
 from ..data.data_store import LazyBatch, gather_crop
 from .batch import DeviceBatch
 from .flax_tree import AdamTrainState, bc_paths, bc_shapes, leaves_from_tree, trunk_from_flax, tree_from_leaves
@@ -69,12 +69,18 @@ class BCTrainState(AdamTrainState):
 
     def _export(self, section):
         a = self._a
-        return tree_from_leaves(bc_paths(a.image_keys), bc_shapes(a.image_keys, a.H, a.W, a.S, a.A),
-                                lambda leaf: a.get(section, leaf))
+        shapes = bc_shapes(a.image_keys, a.H, a.W, a.S, a.A, use_proprio=a.use_proprio)
+        return tree_from_leaves(bc_paths(a.image_keys, a.use_proprio), shapes, lambda leaf: a.get(section, leaf))
 
     def _import(self, tree, section):
         a = self._a
-        paths = bc_paths(a.image_keys)
+        paths = bc_paths(a.image_keys, a.use_proprio)
+        # a state of the other kind (with / without the proprio branch under `encoder`) is refused whole, before any leaf is written
+        enc = tree.get("modules_actor", {}).get("encoder") if isinstance(tree, dict) else None
+        if isinstance(enc, dict) and ("Dense_0" in enc or "LayerNorm_0" in enc) != a.use_proprio:
+            raise ValueError(f"{section}: the state was written by a BC agent with use_proprio={not a.use_proprio} ('modules_actor/encoder/"
+                             f"Dense_0' is {'present' if not a.use_proprio else 'absent'}), this agent has use_proprio={a.use_proprio}; "
+                             "nothing was loaded")
         for leaf, v in leaves_from_tree(paths, tree):
             v = np.asarray(v, np.float32)
             if section != "params" and not a._trainable[leaf]:
@@ -103,15 +109,21 @@ class BCAgent(Handle):
     prefix = "serl_bc"
 
     def __init__(self, image_keys, H, W, state_dim, act_dim, *, seed_key, max_batch=256, learning_rate=3e-4, device=0,
-                 dropout=0.1, std_min=1e-5, std_max=5.0):
+                 dropout=0.1, std_min=1e-5, std_max=5.0, use_proprio=True):
+        if not isinstance(use_proprio, (bool, np.bool_)):
+            raise TypeError(f"use_proprio must be a bool (got {use_proprio!r})")
+        self.use_proprio = bool(use_proprio)     # False: serl_bc_opts.no_proprio, the image codes alone; the state is never read
         self.image_keys = tuple(image_keys)
         self.H, self.W, self.S, self.A, self.max_batch, self.device = H, W, state_dim, act_dim, max_batch, device
-        self.config = {"image_keys": self.image_keys}
+        self.config = {"image_keys": self.image_keys, "use_proprio": self.use_proprio}
         super().__init__(SerlBcCfg(device, len(self.image_keys), H, W, state_dim, act_dim, max_batch, learning_rate, dropout,
                                    std_min, std_max))
         self._rng_key = J.create_rng(seed_key)    # BCAgent.create (bc.py:194-202)
         self._db: Optional[DeviceBatch] = None
         self.state = BCTrainState(self)
+
+    def _create(self, cfg):
+        return self.L.serl_bc_create_opts(C.byref(cfg), C.byref(SerlBcOpts(0 if self.use_proprio else 1)), C.byref(self._h))
 
     # ------------------------------------------------------------------ construction (bc.py:118-204)
     @classmethod
@@ -123,13 +135,17 @@ class BCAgent(Handle):
         As for DrQAgent.create_drq, the trunk keeps its initialiser's values until the caller runs
         utils.train_utils.load_resnet10_params(agent, image_keys) (the reference calls it at the end of create, bc.py:200-203,
         and downloads the pickle when it is absent; there is no download here).
+        use_proprio: False (the reference's default, bc.py:126) is EncodingWrapper(use_proprio=False): the policy reads the
+        concatenated camera codes alone, `encoder` holds no Dense_0 / LayerNorm_0, network/Dense_0's kernel is (256 * n_cam, 256),
+        and only the two MLP layers and the two heads train.  observations["state"] is still required (the stores carry it); its
+        values are never read.  True adds the proprio branch (what make_bc_agent builds).
         param_init: "numpy" (default) or "reference" (the reference's own initialisers and keys from `rng`, utils/init_ref.py)."""
         from ..utils import init_ref
         reference = init_ref.check_param_init(param_init)
         if encoder_type != "resnet-pretrained":
             raise ValueError(f"encoder_type {encoder_type!r}: only 'resnet-pretrained' is implemented for BC on this library")
-        if not use_proprio:
-            raise ValueError("use_proprio=False is not implemented for BC on this library (make_bc_agent passes True)")
+        if not isinstance(use_proprio, (bool, np.bool_)):
+            raise ValueError(f"use_proprio={use_proprio!r}: True or False")
         nk = dict(network_kwargs or {"hidden_dims": [256, 256]})
         if list(nk.get("hidden_dims", [256, 256])) != [256, 256] or nk.get("use_layer_norm", False) or \
                 nk.get("activations", "tanh") not in ("tanh", None) and getattr(nk.get("activations"), "__name__", "") != "tanh":
@@ -144,14 +160,14 @@ class BCAgent(Handle):
         S = int(np.asarray(observations["state"]).shape[-1])
         A = int(np.asarray(actions).shape[-1])
         agent = cls(image_keys, H, W, S, A, seed_key=key, max_batch=batch_size, learning_rate=learning_rate, device=device,
-                    std_min=float(pk.get("std_min", 1e-5)), std_max=float(pk.get("std_max", 10.0)))
+                    std_min=float(pk.get("std_min", 1e-5)), std_max=float(pk.get("std_max", 10.0)), use_proprio=bool(use_proprio))
         from ..utils.init import init_theta, init_trunk
         seed = int(key[1]) if param_seed is None else param_seed
         agent.load_flat(init_trunk(seed))
         if reference:
-            theta = init_ref.bc_reference(image_keys, H, W, S, A, key, device=device)
+            theta = init_ref.bc_reference(image_keys, H, W, S, A, key, device=device, use_proprio=agent.use_proprio)
         else:
-            theta = init_theta(len(image_keys), H, W, S, A, seed=seed)
+            theta = init_theta(len(image_keys), H, W, S, A, seed=seed, use_proprio=agent.use_proprio)
         agent.load_flat({k: v for k, v in theta.items() if k in agent._counts})
         return agent
 
@@ -288,12 +304,12 @@ class BCAgent(Handle):
 
 
 def make_bc_agent(seed, sample_obs, sample_action, image_keys=("image",), encoder_type="resnet-pretrained",
-                  batch_size=256, device=0, param_init="numpy"):
+                  batch_size=256, device=0, param_init="numpy", use_proprio=True):
     """launcher.py:26-47 (hyper-parameters copied from there).  The reference's default encoder_type "small" raises at this
     reference commit; only "resnet-pretrained" is served here."""
     return BCAgent.create(
         J.prngkey(seed), sample_obs, sample_action,
         network_kwargs={"activations": "tanh", "use_layer_norm": False, "hidden_dims": [256, 256]},
         policy_kwargs={"tanh_squash_distribution": False, "std_parameterization": "exp", "std_min": 1e-5, "std_max": 5},
-        use_proprio=True, encoder_type=encoder_type, image_keys=image_keys, batch_size=batch_size, device=device,
+        use_proprio=use_proprio, encoder_type=encoder_type, image_keys=image_keys, batch_size=batch_size, device=device,
         param_init=param_init)

@@ -28,7 +28,7 @@ class AgentCore(Handle):
                  critic_subsample_size=2, backup_entropy=False, num_stack=1, std_parameterization="exp",
                  tanh_squash_distribution=True, critic_activation="tanh", policy_activation="tanh",
                  critic_dropout=0.0, policy_dropout=0.0, critic_dims=None, policy_dims=None, critic_layer_norm=True,
-                 policy_layer_norm=True, fixed_std=None, ragged=False):
+                 policy_layer_norm=True, fixed_std=None, ragged=False, use_proprio=True):
         """optimizers: optional {"actor"|"critic"|"temperature": make_optimizer kwargs (common/optimizers.py:6-13:
         learning_rate, warmup_steps, cosine_decay_steps, weight_decay, clip_grad_norm)} overriding lr / warmup_steps.
         weight_decay decays every leaf of the tree, as optax.adamw does with the params the reference hands it -- with
@@ -48,6 +48,9 @@ class AgentCore(Handle):
         ragged: serl_agent_opts.ragged_widths -- hidden and the entries of critic_dims / policy_dims are any integers in [1, 1024];
         a layer off the 64 grid is stored zero padded to the next multiple of 64 (include/serl_mi355.h), and every leaf this handle
         gets, sets or counts has its true shape.
+        use_proprio: False is serl_agent_opts.no_proprio (pixel agents alone): EncodingWrapper(use_proprio=False), the image codes
+        alone -- no enc/proprio/* leaf, and no call of this handle reads a state: the state tensors of a batch and of
+        sample_actions / q_values / policy_stats are accepted and never dereferenced.
         These network options are no fields of serl_agent_cfg: they make one utils.init.NetSpec (`spec`), whose check() says where
         a positive Dropout rate is served, and go to serl_agent_create_opts as one struct (_create)."""
         if target_entropy is None:
@@ -72,11 +75,14 @@ class AgentCore(Handle):
         for name, flag in (("critic_layer_norm", critic_layer_norm), ("policy_layer_norm", policy_layer_norm)):
             if not isinstance(flag, (bool, np.bool_)):
                 raise TypeError(f"{name} must be a bool (got {flag!r})")
+        if not isinstance(use_proprio, (bool, np.bool_)):
+            raise TypeError(f"use_proprio must be a bool (got {use_proprio!r})")
+        use_proprio = bool(use_proprio)
         self.spec = NetSpec(std_parameterization, bool(tanh_squash_distribution), fixed_std, critic_activation, policy_activation,
                             float(critic_dropout), float(policy_dropout), int(hidden),
                             None if critic_dims is None else tuple(int(d) for d in critic_dims),
                             None if policy_dims is None else tuple(int(d) for d in policy_dims),
-                            bool(critic_layer_norm), bool(policy_layer_norm), bool(ragged))
+                            bool(critic_layer_norm), bool(policy_layer_norm), bool(ragged), use_proprio)
         opts = self.spec.to_c()      # (an unknown std_parameterization or activation name raises here)
         self.spec.check()
         for f in dataclasses.fields(self.spec):      # the options as public attributes, under the constructor's names ...
@@ -319,7 +325,7 @@ class AgentCore(Handle):
                                                   redq_row, self._stream()))
 
     def critic_grads_bucketed(self, offset, count, global_count, noise=None, redq_row=0, event=None):
-        """critic_grads with bucket 0 ([ensemble | head | proprio | scalars]) published early: `event` (torch.cuda.Event) is
+        """critic_grads with bucket 0 ([ensemble | head | proprio (none in an image-only agent) | scalars]) published early: `event` (torch.cuda.Event) is
         recorded on the current stream once that bucket is final, before the encoder-head backward is issued."""
         ev = None
         if event is not None:

@@ -175,7 +175,7 @@ class DrQAgent:
                    batch_size: int = 256, device: int = 0, learning_rate: float = 3e-4,
                    actor_optimizer_kwargs: dict = None, critic_optimizer_kwargs: dict = None,
                    temperature_optimizer_kwargs: dict = None, param_init: str = "numpy", mlp_dropout: bool = False, mlp_shapes: bool = False, mlp_plain: bool = False,
-                   policy_fixed: bool = False, mlp_ragged: bool = False, **kwargs):
+                   policy_fixed: bool = False, mlp_ragged: bool = False, image_only: bool = False, **kwargs):
         """drq.py:104-242.  Only the configuration the reference's examples run is built natively:
         encoder_type="resnet-pretrained", use_proprio=True, REDQ subsample 2, tanh-squashed
         exp-parameterised policy, LayerNorm+tanh MLPs (utils/launcher.py:79-116) -- 256x256 there; critic_network_kwargs /
@@ -217,17 +217,29 @@ class DrQAgent:
         that includes the pretrained trunk, which then shrinks by sum_t lr_t * wd_t per optimizer step while its target copy
         follows by the EMA (`agent.live_trunk`; costs a third trunk pass, re-packed weights per step and the prefetch overlap:
         DESIGN.md section 7).  That is what the reference computes, and it is reproduced for parity -- not a recommendation.
+        image_only=True reads use_proprio as given (without the switch use_proprio=False, the reference's own default, is refused as
+        it always was).  False builds EncodingWrapper(use_proprio=False) (common/encoding.py:53-72): the code is the concatenated
+        camera codes, there is no Dense_0 / LayerNorm_0 under either `encoder` in the flax tree, the first kernels of the critic
+        and the policy have 256 * n_cam (+ action_dim) rows, and the update launches no proprio work.  observations["state"] is still
+        required in the sample observation and in every batch, because the replay stores carry it; its values are never read.
+        True gives the agent the call without the switch gives.  A use_proprio that is no bool, and a positive dropout_rate under
+        mlp_dropout=True beside use_proprio=False, are refused from the arguments alone.  agent.config holds "use_proprio": False
+        for such an agent (no entry otherwise).
         param_init: "numpy" (default) draws the trainable leaves from host NumPy streams seeded by `rng`; "reference" draws them
         as the reference's model_def.init(init_rng) does (utils/init_ref.py); the frozen trunk is the same either way."""
         if encoder_type not in ("resnet-pretrained", "small"):
             # drq.py:155-167 also has "resnet" (trainable ResNet-10, never selected by an example: not built)
             raise NotImplementedError(f"Unknown encoder type: {encoder_type}")
-        if not use_proprio:
-            raise NotImplementedError("only use_proprio=True")
+        if image_only:
+            if not isinstance(use_proprio, (bool, np.bool_)):
+                raise NotImplementedError(f"use_proprio={use_proprio!r} under image_only=True (served: True or False)")
+        elif not use_proprio:
+            raise NotImplementedError("only use_proprio=True; the image-only agent (use_proprio=False) with image_only=True")
         pk = policy_kwargs or {}
         A = int(np.asarray(actions).shape[-1])
         spec = pinit.network_spec(critic_network_kwargs, policy_network_kwargs, pk, A, mlp_dropout=mlp_dropout, mlp_shapes=mlp_shapes,
-                                  mlp_plain=mlp_plain, policy_fixed=policy_fixed, mlp_ragged=mlp_ragged)
+                                  mlp_plain=mlp_plain, policy_fixed=policy_fixed, mlp_ragged=mlp_ragged,
+                                  use_proprio=bool(use_proprio) if image_only else True)
         seed = int(np.asarray(rng).reshape(-1)[-1]) if not isinstance(rng, int) else rng
         image_keys = tuple(image_keys)
         img = np.asarray(observations[image_keys[0]])

@@ -145,7 +145,12 @@ def net_spec_of(core) -> NetSpec:
     """the network options of an AgentCore, as far as the leaf tables depend on them (NetSpec.leaf_kwargs); an attribute the handle
     does not have is the default's: a core that only has cfg.hidden is the (hidden, hidden), LayerNorm, "exp" agent"""
     names = ("std_parameterization", "critic_dims", "policy_dims", "critic_layer_norm", "policy_layer_norm")
-    return NetSpec(hidden=int(getattr(core.cfg, "hidden", 256)), **{n: getattr(core, n) for n in names if hasattr(core, n)})
+    kw = {n: getattr(core, n) for n in names if hasattr(core, n)}
+    if getattr(core, "_h", None) is not None and hasattr(core, "L"):      # whether the library's agent has its proprio branch
+        kw["use_proprio"] = int(core.L.serl_agent_use_proprio(core._h)) != 0
+    elif hasattr(core, "use_proprio"):
+        kw["use_proprio"] = bool(core.use_proprio)
+    return NetSpec(hidden=int(getattr(core.cfg, "hidden", 256)), **kw)
 
 
 def _mlp_paths(m, pre, base, n_layers, layer_norm=True):
@@ -160,8 +165,9 @@ def _mlp_paths(m, pre, base, n_layers, layer_norm=True):
 
 
 def theta_paths(image_keys, critic_mlp_name="network", encoder_type="resnet-pretrained", std_parameterization="exp",
-                critic_dims=None, policy_dims=None, critic_layer_norm=True, policy_layer_norm=True):
-    """flat trainable leaf -> list of flax paths (aliases).  critic_dims / policy_dims: the hidden widths of each MLP (only their
+                critic_dims=None, policy_dims=None, critic_layer_norm=True, policy_layer_norm=True, use_proprio=True):
+    """flat trainable leaf -> list of flax paths (aliases).  use_proprio False: `encoder` holds the cameras' `encoder_<key>` alone,
+    no Dense_0 or LayerNorm_0 (common/encoding.py:53-72).  critic_dims / policy_dims: the hidden widths of each MLP (only their
     count matters here; None: two layers).  critic_layer_norm / policy_layer_norm False: no LayerNorm_<j> under that network."""
     enc = ("modules_actor", "encoder")
     m = {}
@@ -182,10 +188,11 @@ def theta_paths(image_keys, critic_mlp_name="network", encoder_type="resnet-pret
         m[f"enc/{i}/dense/bias"] = [e + ("Dense_0", "bias")]
         m[f"enc/{i}/ln/scale"] = [e + ("LayerNorm_0", "scale")]
         m[f"enc/{i}/ln/bias"] = [e + ("LayerNorm_0", "bias")]
-    m["enc/proprio/dense/kernel"] = [enc + ("Dense_0", "kernel")]
-    m["enc/proprio/dense/bias"] = [enc + ("Dense_0", "bias")]
-    m["enc/proprio/ln/scale"] = [enc + ("LayerNorm_0", "scale")]
-    m["enc/proprio/ln/bias"] = [enc + ("LayerNorm_0", "bias")]
+    if use_proprio:
+        m["enc/proprio/dense/kernel"] = [enc + ("Dense_0", "kernel")]
+        m["enc/proprio/dense/bias"] = [enc + ("Dense_0", "bias")]
+        m["enc/proprio/ln/scale"] = [enc + ("LayerNorm_0", "scale")]
+        m["enc/proprio/ln/bias"] = [enc + ("LayerNorm_0", "bias")]
     _mlp_paths(m, "critic", ("modules_critic", critic_mlp_name), nc, critic_layer_norm)
     m["critic/head/kernel"] = [("modules_critic", "Dense_0", "kernel")]
     m["critic/head/bias"] = [("modules_critic", "Dense_0", "bias")]
@@ -210,11 +217,12 @@ def _state_paths(std_parameterization="exp", n_critic=2, n_policy=2, critic_laye
     return m
 
 
-def bc_paths(image_keys):
+def bc_paths(image_keys, use_proprio=True):
     """flat BC leaf (csrc/bc.hip) -> flax path in BCAgent.state.params (bc.py:118-204): Policy is `modules_actor`, its
     EncodingWrapper `encoder` (per camera `encoder_<key>`, the proprio Dense_0 / LayerNorm_0), its MLP `network`
     (Dense_0, Dense_1 -- no LayerNorm), the heads Dense_0 (mean) and Dense_1 (log_std); the shared frozen trunk sits under
-    the first camera in sorted-key order, as in DrQ."""
+    the first camera in sorted-key order, as in DrQ.  use_proprio False (BCAgent.create's own default): no Dense_0 / LayerNorm_0
+    under `encoder`."""
     enc = ("modules_actor", "encoder")
     m = {}
     for leaf, sub in _trunk_paths().items():
@@ -222,10 +230,11 @@ def bc_paths(image_keys):
     for i, k in enumerate(image_keys):
         for leaf, sub in CAM_PATHS.items():
             m[f"enc/{i}/{leaf}"] = enc + (f"encoder_{k}",) + sub
-    m["enc/proprio/dense/kernel"] = enc + ("Dense_0", "kernel")
-    m["enc/proprio/dense/bias"] = enc + ("Dense_0", "bias")
-    m["enc/proprio/ln/scale"] = enc + ("LayerNorm_0", "scale")
-    m["enc/proprio/ln/bias"] = enc + ("LayerNorm_0", "bias")
+    if use_proprio:
+        m["enc/proprio/dense/kernel"] = enc + ("Dense_0", "kernel")
+        m["enc/proprio/dense/bias"] = enc + ("Dense_0", "bias")
+        m["enc/proprio/ln/scale"] = enc + ("LayerNorm_0", "scale")
+        m["enc/proprio/ln/bias"] = enc + ("LayerNorm_0", "bias")
     for j in (0, 1):
         m[f"actor/w{j + 1}"] = ("modules_actor", "network", f"Dense_{j}", "kernel")
         m[f"actor/b{j + 1}"] = ("modules_actor", "network", f"Dense_{j}", "bias")
@@ -248,12 +257,13 @@ def _camera_shapes(n_cam, H, W, bottleneck):
     return sh
 
 
-def bc_shapes(image_keys, H, W, S, A, hidden=256, bottleneck=256, proprio_dim=64):
-    """flat BC leaf -> flax shape"""
+def bc_shapes(image_keys, H, W, S, A, hidden=256, bottleneck=256, proprio_dim=64, use_proprio=True):
+    """flat BC leaf -> flax shape; use_proprio False: no enc/proprio leaves, actor/w1 (bottleneck * n_cam, hidden)"""
     sh = dict(trunk_shapes(), **_camera_shapes(len(image_keys), H, W, bottleneck))
-    sh["enc/proprio/dense/kernel"] = (S, proprio_dim)
-    sh["enc/proprio/dense/bias"] = sh["enc/proprio/ln/scale"] = sh["enc/proprio/ln/bias"] = (proprio_dim,)
-    sh["actor/w1"], sh["actor/b1"] = (bottleneck * len(image_keys) + proprio_dim, hidden), (hidden,)
+    if use_proprio:
+        sh["enc/proprio/dense/kernel"] = (S, proprio_dim)
+        sh["enc/proprio/dense/bias"] = sh["enc/proprio/ln/scale"] = sh["enc/proprio/ln/bias"] = (proprio_dim,)
+    sh["actor/w1"], sh["actor/b1"] = (bottleneck * len(image_keys) + (proprio_dim if use_proprio else 0), hidden), (hidden,)
     sh["actor/w2"], sh["actor/b2"] = (hidden, hidden), (hidden,)
     sh["actor/mean/kernel"], sh["actor/mean/bias"] = (hidden, A), (A,)
     sh["actor/logstd/kernel"], sh["actor/logstd/bias"] = (hidden, A), (A,)

@@ -79,6 +79,7 @@ struct serl_agent {
   int E = 0, D = 0, HW = 0, XA = 0;  // enc dim, sle dim, feature pixels, E + A
   bool state_only = false;           // n_cam == 0: SACAgent.create_states
   bool small = false;                // encoder_type == "small": trainable SmallEncoder instead of the frozen trunk
+  bool prop = false;                 // the EncodingWrapper has its proprio branch (cameras and opts.no_proprio == 0); else nothing reads cur.state
   // The network options the agent was created with (serl_mi355.h, NETWORK OPTIONS), normalised by create_agent: both networks have
   // n_layers >= 1 and their dims filled ({cfg.hidden, cfg.hidden} where 0 layers were given: nothing below reads cfg.hidden), and
   // fixed_std points into the vector below.  act is a kAct* code; no_layer_norm is read by build_layout alone, the layers carry it
@@ -213,7 +214,8 @@ void build_layout(serl_agent* a) {
   a->small = !a->state_only && c.encoder_type == SERL_ENCODER_SMALL;
   a->HW = (a->state_only || a->small) ? 0 : d.h[5] * d.w[5];
   a->D = a->state_only ? 0 : (a->small ? kSmallFeat[kSmallLayers] : 512 * c.sle_features);
-  a->E = a->state_only ? c.state_dim : c.bottleneck * c.n_cam + c.proprio_dim;
+  a->prop = !a->state_only && !a->opts.no_proprio;
+  a->E = a->state_only ? c.state_dim : c.bottleneck * c.n_cam + (a->prop ? c.proprio_dim : 0);
   a->XA = a->E + c.act_dim;
   long off = 0;
   Offs& o = a->o;
@@ -248,7 +250,7 @@ void build_layout(serl_agent* a) {
   o.c_hw = add_leaf_box(L, off, "critic/head/kernel", a->state_only ? N : 1, 1, Hct, 1, Hc);
   o.c_hb = add_leaf(L, off, "critic/head/bias", a->state_only ? N : 1);
   o.Pa0 = off;
-  if (!a->state_only) {
+  if (a->prop) {
     o.prop = add_dense_ln_leaves(L, off, "enc/proprio/dense/kernel", "enc/proprio/dense/bias", "enc/proprio/ln", 1, c.state_dim,
                                  c.proprio_dim, kActTanh);
   }
@@ -310,8 +312,8 @@ size_t carve(serl_agent* a, void* base) {
     e.f = b.take<float>((long)c.n_cam * B * a->D);
     e.xhat = b.take<float>((long)c.n_cam * B * c.bottleneck);
     e.rstd = b.take<float>((long)c.n_cam * B);
-    e.pxhat = b.take<float>(B * c.proprio_dim);
-    e.prstd = b.take<float>(B);
+    e.pxhat = a->opts.no_proprio ? nullptr : b.take<float>(B * c.proprio_dim);   // (no proprio scratch without the branch)
+    e.prstd = a->opts.no_proprio ? nullptr : b.take<float>(B);
     e.enc = nullptr; e.ld = 0;
   };
   enc(a->encP); enc(a->encT); enc(a->encO);
@@ -356,8 +358,9 @@ size_t carve(serl_agent* a, void* base) {
   a->scam.dg = b.take<float>((long)c.n_cam * B * c.bottleneck);
   a->df = b.take<float>((long)c.n_cam * B * a->D);
   a->sle_part = b.take<float>((long)c.n_cam * kSleSplit * a->HW * 512 * c.sle_features);
-  a->sprop.dpre = b.take<float>(B * c.proprio_dim); a->sprop.dg = b.take<float>(B * c.proprio_dim);
-  a->dpre = b.take<float>(2 * B * A); a->sprop.dy = b.take<float>(B * c.proprio_dim);
+  const long Bprop = a->opts.no_proprio ? 0 : B * c.proprio_dim;
+  a->sprop.dpre = b.take<float>(Bprop); a->sprop.dg = b.take<float>(Bprop);
+  a->dpre = b.take<float>(2 * B * A); a->sprop.dy = b.take<float>(Bprop);
   for (int k = 0; k < 3; ++k) {
     a->eps_buf[k] = b.take<float>(B * A);
     a->mask_buf[k] = b.take<uint8_t>((long)c.n_cam * B * a->D);
@@ -441,6 +444,7 @@ int encode_multi(serl_agent* a, const EncJob* jobs, int n, int off, int cnt, hip
   GemmDesc gd[3];
   LnFwdArgs lv[3];
   ProprioArgs pv[3];
+  bool any_rider = false;   // image-only agents: some instance carries the actions rider
   const int S = split_for(a->split_budget, cnt, c.bottleneck, c.n_cam * n, 32);  // K = 4096: up to 32 slices of 128
   for (int i = 0; i < n; ++i) {
     const EncJob& j = jobs[i];
@@ -453,7 +457,9 @@ int encode_multi(serl_agent* a, const EncJob* jobs, int n, int off, int cnt, hip
     gd[i] = layer_fwd(o.cam, j.P, cam_io(a, e), cnt, a->slabs_lane[i], S);
     lv[i] = layer_ln_fwd(o.cam, j.P, cam_io(a, e), cnt, gd[i]);
     ProprioArgs& pr = pv[i];
-    pr = layer_row_fwd(o.prop, j.P, prop_io(a, e, a->cur.state + ((long)j.which * Bfull + off) * c.state_dim));
+    pr = ProprioArgs{};   // (without the proprio branch: the rider's fields alone, and the state is not touched)
+    if (a->prop) pr = layer_row_fwd(o.prop, j.P, prop_io(a, e, a->cur.state + ((long)j.which * Bfull + off) * c.state_dim));
+    else any_rider = any_rider || j.act_dst;
     if (j.act_dst) {
       pr.copy_src = j.act_src; pr.ld_copy_src = c.act_dim; pr.copy_dst = j.act_dst; pr.ld_copy_dst = a->XA;
       pr.copy_cols = c.act_dim;
@@ -481,7 +487,8 @@ int encode_multi(serl_agent* a, const EncJob* jobs, int n, int off, int cnt, hip
       RC(small_forward(a->sws, j.P, o.enc0, o.cam_stride, fr, Bfull, c.n_cam, cnt, j.e->f, (long)c.batch * a->D, st));
     }
   } else if (a->fuse) {   // channel-blocked SLE (+ hashed Dropout mask) with the proprio branch as extra workgroups of the launch
-    RC(sle_proprio_fwd_multi(sv, pv, n, 1.0f - c.dropout, cnt, a->HW, 512, c.n_cam, (long)c.batch * a->HW * 512, o.cam_stride,
+    // (an image-only agent: no proprio rows; the rider's rows alone behind the SLE workgroups, and none without a rider)
+    RC(sle_proprio_fwd_multi(sv, a->prop || any_rider ? pv : nullptr, n, 1.0f - c.dropout, cnt, a->HW, 512, c.n_cam, (long)c.batch * a->HW * 512, o.cam_stride,
                              Bfull * a->D, (long)c.batch * a->D, c.state_dim, st));
   } else {
     RC(sle_fwd_multi(sv, n, 1.0f / (1.0f - c.dropout), cnt, a->HW, 512, c.n_cam, (long)c.batch * a->HW * 512, o.cam_stride,
@@ -490,7 +497,13 @@ int encode_multi(serl_agent* a, const EncJob* jobs, int n, int off, int cnt, hip
   RC(gemm_f32_multi(gd, n, st));
   RC(ln_fwd_multi(lv, n, c.bottleneck, st));
   if (a->fuse && !a->small) return SERL_OK;   // (the proprio branch rode on the SLE launch)
-  return proprio_fwd_multi(pv, n, c.state_dim, cnt, st);
+  if (a->prop) return proprio_fwd_multi(pv, n, c.state_dim, cnt, st);
+  // image-only: where the proprio rows are a launch of their own, the rider is a column copy in its place (none without a rider)
+  CopyJob cj[kMaxMulti];
+  int m = 0;
+  for (int i = 0; i < n; ++i)
+    if (jobs[i].act_dst) cj[m++] = CopyJob{jobs[i].act_src, c.act_dim, jobs[i].act_dst, a->XA, c.act_dim};
+  return m ? copy_cols_multi(cj, m, cnt, st) : SERL_OK;
 }
 
 // The tensors of an MLP layer on `rows` rows per group: output and statistics in `b`, one [rows][N] block per group ...
@@ -771,10 +784,16 @@ int enc_bwd_critic(serl_agent* a, const float* P, EncBuf& e, int off, int cnt, h
   const serl_agent_cfg& c = a->cfg;
   const Offs& o = a->o;
   // both layers read their dy where the critic's backward left it: the cameras' column slices of dx, the proprio columns behind
-  const DenseLnIo tc = cam_io(a, e), tp = prop_io(a, e, a->cur.state + (long)off * c.state_dim);
+  const DenseLnIo tc = cam_io(a, e), tp = a->prop || a->state_only ? prop_io(a, e, a->cur.state + (long)off * c.state_dim) : DenseLnIo{};
   const DenseLnGrad dc{a->dx, a->XA, o.cam.N, a->scam.dpre, a->scam.dg};
-  const DenseLnGrad dp{a->dx + (long)c.n_cam * o.cam.N, a->XA, 0, a->sprop.dpre, a->sprop.dg};
-  if (a->fuse && !a->state_only) {
+  const DenseLnGrad dp{a->dx + (long)c.n_cam * o.cam.N, a->XA, 0, a->sprop.dpre, a->sprop.dg};   // (unused without the proprio branch)
+  if (!a->prop && !a->state_only) {   // image-only: the camera heads' LayerNorm backward alone, nothing of a proprio branch deferred
+    if (a->fuse) {
+      RC(ln_bwd(layer_ln_bwd(o.cam, P, tc, dc, cnt), st));
+      SERL_REQUIRE(a->pg_defer && a->pg_ncs + 1 <= kMaxColsum, "no room for the deferred LayerNorm gradients");
+      a->pg_cs[a->pg_ncs++] = layer_colsum(o.cam, tc, dc, cnt, a->Gc);
+    }   // (un-fused: nothing in front of the event; the camera heads' dense_ln_bwd below runs their LayerNorm backward)
+  } else if (a->fuse && !a->state_only) {
     LnBwdArgs lb[2] = {layer_ln_bwd(o.cam, P, tc, dc, cnt), layer_ln_bwd(o.prop, P, tp, dp, cnt)};
     RC(ln_bwd_multi(lb, 2, LossArgs{}, st));
     SERL_REQUIRE(a->pg_defer && a->pg_ncs + 2 <= kMaxColsum, "no room for the deferred LayerNorm gradients");
@@ -784,7 +803,7 @@ int enc_bwd_critic(serl_agent* a, const float* P, EncBuf& e, int off, int cnt, h
   } else if (!a->state_only) {
     RC(dense_ln_bwd(a, o.prop, P, tp, dp, cnt, a->Gc, st));
   }
-  if (event_bucket0) {   // bucket 0 (ensemble | head | proprio | scalars) is final once the jobs deferred so far have run
+  if (event_bucket0) {   // bucket 0 (ensemble | head | proprio, where the agent has the branch | scalars) is final once the jobs deferred so far have run
     RC(flush_param_grads(a, st));
     SERL_HIP(hipEventRecord((hipEvent_t)event_bucket0, st));
   }
@@ -1068,6 +1087,13 @@ static int create_agent(const serl_agent_cfg* cfg, const serl_agent_opts* opts, 
                  "agents whose policy head has std leaves", critic.dropout, policy.dropout);
   }
   SERL_REQUIRE(cfg->n_cam >= 0 && cfg->n_cam <= SERL_MAX_CAMS, "n_cam %d not in [0,%d]", cfg->n_cam, SERL_MAX_CAMS);
+  SERL_REQUIRE(opts->no_proprio == 0 || opts->no_proprio == 1, "no_proprio %d is not 0 (the proprio branch) or 1 (image codes alone)", opts->no_proprio);
+  SERL_REQUIRE(!opts->no_proprio || cfg->n_cam > 0, "no_proprio 1 with n_cam 0: a state-only agent has no EncodingWrapper, its input is the state");
+  if (opts->no_proprio && (critic.dropout > 0.0 || policy.dropout > 0.0)) {
+    set_error("dropout %g / %g (critic / policy) with no_proprio 1: Dropout in the MLPs is served in agents with the proprio branch",
+              critic.dropout, policy.dropout);
+    return SERL_ERR_UNSUPPORTED;
+  }
   SERL_REQUIRE(cfg->n_cam == 0 || (cfg->H >= 32 && cfg->W >= 32), "images must be at least 32x32");
   SERL_REQUIRE(cfg->encoder_type == SERL_ENCODER_RESNET_PRETRAINED || cfg->encoder_type == SERL_ENCODER_SMALL,
                "Unknown encoder type: %d", cfg->encoder_type);
@@ -1171,6 +1197,7 @@ static int create_agent(const serl_agent_cfg* cfg, const serl_agent_opts* opts, 
 }
 
 int serl_agent_live_trunk(serl_agent* a) { return a ? (a->live ? 1 : 0) : -1; }
+int serl_agent_use_proprio(serl_agent* a) { return a ? (a->opts.no_proprio ? 0 : 1) : -1; }
 
 int serl_agent_destroy(serl_agent* a) {
   if (!a) return SERL_OK;
@@ -1329,7 +1356,8 @@ int serl_agent_trunk_forward(serl_agent* a, const uint8_t* dev_frames, int n, fl
 
 static int check_batch(serl_agent* a, const serl_batch* b) {
   const serl_agent_cfg& c = a->cfg;
-  SERL_REQUIRE(b && (b->frames || c.n_cam == 0) && b->state && b->action && b->reward && b->mask, "serl_batch has NULL members");
+  // (an agent without the proprio branch never reads the state: NULL is accepted)
+  SERL_REQUIRE(b && (b->frames || c.n_cam == 0) && (b->state || a->opts.no_proprio) && b->action && b->reward && b->mask, "serl_batch has NULL members");
   SERL_REQUIRE(b->batch >= 1 && b->batch <= c.batch, "batch %d not in [1,%d]", b->batch, c.batch);
   SERL_REQUIRE(b->n_cam == c.n_cam && (c.n_cam == 0 || (b->H == c.H && b->W == c.W && b->C == 3)) &&
                    b->state_dim == c.state_dim && b->act_dim == c.act_dim, "serl_batch shape does not match the agent");
@@ -1725,7 +1753,7 @@ int serl_agent_actor_grads(serl_agent* a, int global_count, const serl_noise* no
   }
   // image codes are stop-gradiented (encoding.py:48-49); only the proprio slice of d_enc is needed: the rows of W1 that the
   // proprio columns multiply, a slice of layer 1's kernel and therefore written out
-  if (!a->state_only) {
+  if (a->prop) {   // (an image-only policy has no trainable input: its backward ends at layer 1)
     const DenseLnGrad dp{a->sprop.dy, o.prop.N, 0, a->sprop.dpre, a->sprop.dg};
     RC(gemm_f32(gemm_igrad(d1.dpre, o.a[0].N, 0, P + o.a[0].W + (long)c.n_cam * o.cam.N * o.a[0].N, o.a[0].N, 0, dp.dy, dp.ld_dy, 0, 1, cnt,
                            o.prop.N, o.a[0].N), st));
@@ -1885,7 +1913,7 @@ static int eval_check(serl_agent* a, const uint8_t* dev_frames, const float* dev
   const serl_agent_cfg& c = a->cfg;
   SERL_REQUIRE(n >= 1 && n <= c.batch, "n %d not in [1,%d]", n, c.batch);
   SERL_REQUIRE(dev_frames || c.n_cam == 0, "dev_frames is NULL on an agent with %d camera(s)", c.n_cam);
-  SERL_REQUIRE(dev_state, "dev_state is NULL");
+  SERL_REQUIRE(dev_state || a->opts.no_proprio, "dev_state is NULL");
   return SERL_OK;
 }
 
@@ -1913,7 +1941,7 @@ static int eval_encode(serl_agent* a, const uint8_t* dev_frames, const float* de
 
 int serl_agent_sample_actions(serl_agent* a, const uint8_t* dev_frames, const float* dev_state, int n,
                               const float* dev_eps, float* dev_out_actions, void* stream) {
-  SERL_REQUIRE(a && dev_state && dev_out_actions, "NULL argument");
+  SERL_REQUIRE(a && (dev_state || a->opts.no_proprio) && dev_out_actions, "NULL argument");
   const serl_agent_cfg& c = a->cfg;
   SERL_REQUIRE(dev_frames || c.n_cam == 0, "NULL frames");
   SERL_REQUIRE(n >= 1 && n <= c.batch, "n %d not in [1,%d]", n, c.batch);

@@ -9,6 +9,8 @@
 // forever (Adam with g = m = v = 0 leaves a parameter unchanged) and are produced on read instead of stored.
 // Reuses the trunk (trunk_f16x3.hip) and the encoder-head / GEMM / Adam kernels (heads.hip); new here: the bias + tanh slab
 // reduction of a plain Dense -> tanh layer, its backward, and the diagonal-Gaussian NLL head.
+// serl_bc_opts.no_proprio: EncodingWrapper(use_proprio=False), BCAgent.create's own default -- the code is the image codes alone,
+// no proprio leaves or launches, and only the two MLP layers and the two heads train.
 #include <cmath>
 #include <string>
 #include <vector>
@@ -24,6 +26,7 @@ constexpr int kHidden = 256, kBottleneck = 256, kSleFeatures = 8, kProprio = 64,
 
 struct serl_bc {
   serl_bc_cfg cfg{};
+  bool has_prop = true;   // the proprio branch (serl_bc_opts.no_proprio == 0); else the state is never read
   int HW = 0, D = 0, Eimg = 0, E = 0;
   std::vector<Leaf> leaves;    // trunk, cameras (frozen), then the trainable slice [t0, t0 + nt)
   long n_params = 0, t0 = 0, nt = 0;
@@ -51,7 +54,7 @@ void layout(serl_bc* c) {
   c->HW = d.h[5] * d.w[5];
   c->D = 512 * kSleFeatures;
   c->Eimg = kBottleneck * g.n_cam;
-  c->E = c->Eimg + kProprio;
+  c->E = c->Eimg + (c->has_prop ? kProprio : 0);
   std::vector<Leaf>& L = c->leaves;
   long off = 0;
   c->to = add_trunk_leaves(L, off);
@@ -59,7 +62,7 @@ void layout(serl_bc* c) {
   off = (off + 3) & ~3L;   // (16-byte aligned trainable slice)
   c->t0 = off;
   const long A = g.act_dim;
-  c->prop = add_dense_ln_leaves(L, off, "enc/proprio/dense/kernel", "enc/proprio/dense/bias", "enc/proprio/ln", 1, g.state_dim, kProprio, kActTanh);
+  if (c->has_prop) c->prop = add_dense_ln_leaves(L, off, "enc/proprio/dense/kernel", "enc/proprio/dense/bias", "enc/proprio/ln", 1, g.state_dim, kProprio, kActTanh);
   c->o_w1 = add_leaf(L, off, "actor/w1", (long)c->E * kHidden);
   c->o_b1 = add_leaf(L, off, "actor/b1", kHidden);
   c->o_w2 = add_leaf(L, off, "actor/w2", (long)kHidden * kHidden);
@@ -75,7 +78,7 @@ void layout(serl_bc* c) {
 size_t carve(serl_bc* c, uint8_t* base) {
   const serl_bc_cfg& g = c->cfg;
   Bump b(base);
-  const long n = g.max_batch, A = g.act_dim;
+  const long n = g.max_batch, A = g.act_dim, np = c->has_prop ? n : 0;   // np: rows of proprio scratch
   c->params = b.take<float>(c->n_params + 1);
   c->opt.carve(b, c->t0, c->nt);
   c->info = b.take<float>(2);
@@ -86,17 +89,17 @@ size_t carve(serl_bc* c, uint8_t* base) {
   c->slabs_cap = (long)std::max(32 * g.n_cam, 8) * n * kBottleneck;
   c->slabs = b.take<float>(c->slabs_cap);
   c->enc = b.take<float>(n * c->E);
-  c->pxhat = b.take<float>(n * kProprio);
-  c->prstd = b.take<float>(n);
+  c->pxhat = b.take<float>(np * kProprio);
+  c->prstd = b.take<float>(np);
   c->h1 = b.take<float>(n * kHidden);
   c->h2 = b.take<float>(n * kHidden);
   c->mu = b.take<float>(n * A);
   c->dhead = b.take<float>(2 * n * A);
   c->dpre1 = b.take<float>(n * kHidden);
   c->dpre2 = b.take<float>(n * kHidden);
-  c->dprop = b.take<float>(n * kProprio);
-  c->dpp = b.take<float>(n * kProprio);
-  c->dgp = b.take<float>(n * kProprio);
+  c->dprop = b.take<float>(np * kProprio);
+  c->dpp = b.take<float>(np * kProprio);
+  c->dgp = b.take<float>(np * kProprio);
   if (base) {
     trunk_packed_bind(c->tpk, pk);
     trunk_workspace_bind(c->tws, ws, g.n_cam * g.max_batch, g.H, g.W);
@@ -234,8 +237,9 @@ int forward(serl_bc* c, const uint8_t* frames, const float* state, int n, const 
   SleFwdArgs sv{};
   sv.x = c->feats; sv.K = P + c->cam.first; sv.mask = mask; sv.f = c->f;
   if (!mask && mask_keys) sle_tf_masks(sv, mask_keys, g.n_cam, n, 0);
-  const ProprioArgs pv = layer_row_fwd(c->prop, P, prop_io(c, state));
-  RC(sle_proprio_fwd_multi(&sv, &pv, 1, 1.0f - g.dropout, n, c->HW, 512, g.n_cam, (long)n * c->HW * 512, c->cam.stride,
+  ProprioArgs pv{};
+  if (c->has_prop) pv = layer_row_fwd(c->prop, P, prop_io(c, state));
+  RC(sle_proprio_fwd_multi(&sv, c->has_prop ? &pv : nullptr, 1, 1.0f - g.dropout, n, c->HW, 512, g.n_cam, (long)n * c->HW * 512, c->cam.stride,
                            (long)n * c->D, (long)n * c->D, g.state_dim, st));
   // bottleneck Dense (K-split) -> LayerNorm -> tanh per camera, side by side in enc
   const int S0 = split_under(n, kBottleneck, g.n_cam, 32);
@@ -277,7 +281,7 @@ int launch_head(const BcHeadArgs& h, hipStream_t st) {
 
 int check_batch(serl_bc* c, const serl_batch* b) {
   const serl_bc_cfg& g = c->cfg;
-  SERL_REQUIRE(b && b->frames && b->state && b->action, "serl_batch has NULL members");
+  SERL_REQUIRE(b && b->frames && (b->state || !c->has_prop) && b->action, "serl_batch has NULL members");
   SERL_REQUIRE(b->batch >= 1 && b->batch <= g.max_batch, "batch %d not in [1,%d]", b->batch, g.max_batch);
   SERL_REQUIRE(b->n_cam == g.n_cam && b->H == g.H && b->W == g.W && b->C == 3 && b->state_dim == g.state_dim &&
                    b->act_dim == g.act_dim, "serl_batch shape does not match the BC agent");
@@ -300,7 +304,15 @@ int resolve(serl_bc* c, const char* section, const char* leaf, float** ptr, long
 extern "C" {
 
 int serl_bc_create(const serl_bc_cfg* cfg, serl_bc** out) {
-  SERL_REQUIRE(cfg && out, "NULL argument");
+  const serl_bc_opts opts{};
+  return serl_bc_create_opts(cfg, &opts, out);
+}
+
+int serl_bc_use_proprio(serl_bc* c) { return c ? (c->has_prop ? 1 : 0) : -1; }
+
+int serl_bc_create_opts(const serl_bc_cfg* cfg, const serl_bc_opts* opts, serl_bc** out) {
+  SERL_REQUIRE(cfg && opts && out, "NULL argument");
+  SERL_REQUIRE(opts->no_proprio == 0 || opts->no_proprio == 1, "no_proprio %d is not 0 (the proprio branch) or 1 (image codes alone)", opts->no_proprio);
   SERL_REQUIRE(cfg->n_cam >= 1 && cfg->n_cam <= SERL_MAX_CAMS, "n_cam %d not in [1,%d]", cfg->n_cam, SERL_MAX_CAMS);
   SERL_REQUIRE(cfg->H >= 32 && cfg->W >= 32 && cfg->max_batch >= 1, "bad BC shape");
   SERL_REQUIRE(cfg->state_dim >= 1 && cfg->act_dim >= 1 && cfg->act_dim <= kMaxAct, "state_dim %d / act_dim %d unsupported",
@@ -309,6 +321,7 @@ int serl_bc_create(const serl_bc_cfg* cfg, serl_bc** out) {
   SERL_HIP(hipSetDevice(cfg->device));
   serl_bc* c = new serl_bc();
   c->cfg = *cfg;
+  c->has_prop = !opts->no_proprio;
   layout(c);
   if (int rc = alloc_zeroed(&c->arena, carve(c, nullptr), "BC arena")) {
     delete c;
@@ -394,11 +407,15 @@ int serl_bc_update(serl_bc* c, const serl_batch* batch, const uint8_t* dev_masks
   RC(gemm_f32_multi(&gd, 1, st));
   RC(dense_tanh_bwd(c->slabs, S2, gd.sCz, c->h1, c->dpre1, n, kHidden, st));
   // gradient of the proprio code only (the image codes are behind stop_gradient): dpre1 W1[Eimg:E]^T
-  const GemmDesc gp = gemm_igrad(c->dpre1, kHidden, 0, P + c->o_w1 + (long)c->Eimg * kHidden, kHidden, 0, c->dprop, kProprio, 0, 1, n, kProprio, kHidden);
-  RC(gemm_f32_multi(&gp, 1, st));
-  const DenseLnIo tp = prop_io(c, batch->state);
+  // (without the proprio branch the policy has no trainable input: no such GEMM, LayerNorm backward or gradient entry)
+  const int np = c->has_prop ? 5 : 4;   // entries of the two gradient launches
+  const DenseLnIo tp = c->has_prop ? prop_io(c, batch->state) : DenseLnIo{};
   const DenseLnGrad dp{c->dprop, kProprio, 0, c->dpp, c->dgp};
-  RC(ln_bwd(layer_ln_bwd(c->prop, P, tp, dp, n), st));
+  if (c->has_prop) {
+    const GemmDesc gp = gemm_igrad(c->dpre1, kHidden, 0, P + c->o_w1 + (long)c->Eimg * kHidden, kHidden, 0, c->dprop, kProprio, 0, 1, n, kProprio, kHidden);
+    RC(gemm_f32_multi(&gp, 1, st));
+    RC(ln_bwd(layer_ln_bwd(c->prop, P, tp, dp, n), st));
+  }
   // every parameter gradient: one column-sum launch and one grouped weight-gradient GEMM
   const float* dmu = c->dhead;
   const float* dls = c->dhead + (long)n * A;
@@ -407,9 +424,9 @@ int serl_bc_update(serl_bc* c, const serl_batch* batch, const uint8_t* dev_masks
       {c->dpre2, nullptr, nullptr, 1, n, kHidden, nullptr, G + c->o_b2, nullptr, 0, 1},
       {dmu, nullptr, nullptr, 1, n, A, nullptr, G + c->o_bm, nullptr, 0, 1},
       {dls, nullptr, nullptr, 1, n, A, nullptr, G + c->o_bs, nullptr, 0, 1},
-      layer_colsum(c->prop, tp, dp, n, G),
+      c->has_prop ? layer_colsum(c->prop, tp, dp, n, G) : Colsum3Args{},
   };
-  RC(colsum3_multi(cs, 5, st));
+  RC(colsum3_multi(cs, np, st));
   auto wg = [&](const float* X, long ldx, const float* dY, long ldy, float* out, int Mx, int Ny) {
     return gemm_wgrad(X, ldx, 0, dY, ldy, 0, out, Ny, 0, 1, Mx, Ny, n);
   };
@@ -418,9 +435,9 @@ int serl_bc_update(serl_bc* c, const serl_batch* batch, const uint8_t* dev_masks
       wg(c->h1, kHidden, c->dpre2, kHidden, G + c->o_w2, kHidden, kHidden),
       wg(c->h2, kHidden, dmu, A, G + c->o_Wm, kHidden, A),
       wg(c->h2, kHidden, dls, A, G + c->o_Ws, kHidden, A),
-      layer_wgrad(c->prop, tp, dp, n, G),
+      c->has_prop ? layer_wgrad(c->prop, tp, dp, n, G) : GemmDesc{},
   };
-  RC(gemm_f32_multi(wgs, 5, st));
+  RC(gemm_f32_multi(wgs, np, st));
   // optax.adam(lr) over the trainable slice (bc.py:139 via common.py:170-220); one count, no schedule, no clip
   return c->opt.apply(c->params, g.lr, st);
 }
@@ -434,7 +451,7 @@ int serl_bc_read_info(serl_bc* c, float out[2], void* stream) {
 
 int serl_bc_sample_actions(serl_bc* c, const uint8_t* dev_frames, const float* dev_state, int n, const float* dev_eps,
                            const uint32_t* host_key, float temperature, int argmax, float* dev_actions_out, void* stream) {
-  SERL_REQUIRE(c && dev_frames && dev_state && dev_actions_out, "NULL argument");
+  SERL_REQUIRE(c && dev_frames && (dev_state || !c->has_prop) && dev_actions_out, "NULL argument");
   SERL_REQUIRE(n >= 1 && n <= c->cfg.max_batch, "n = %d not in [1, max_batch = %d]", n, c->cfg.max_batch);
   SERL_REQUIRE(argmax || dev_eps || host_key, "sampling needs eps or a jax.random key");
   SERL_REQUIRE(temperature >= 0.f, "negative temperature");

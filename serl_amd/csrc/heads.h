@@ -88,7 +88,9 @@ struct SleFwdArgs {
   uint32_t tf_key[4][2]; long tf_rows, tf_row0;
 };
 // SpatialLearnedEmbeddings channel-blocked (a workgroup = 256 channels x 8 samples: the kernel K is read once per workgroup,
-// not once per sample) + inline Dropout mask + the proprio branch as extra workgroups of the same launch (pv == nullptr: none)
+// not once per sample) + inline Dropout mask + the proprio branch as extra workgroups of the same launch (pv == nullptr: none).
+// pv whose instances have no `state` (an agent without the proprio branch): the extra workgroups carry the instances' column-copy
+// riders alone -- all instances of a launch have a state or none has; the caller passes nullptr where no instance has a rider
 struct ProprioArgs;
 int sle_proprio_fwd_multi(const SleFwdArgs* v, const ProprioArgs* pv, int n, float keep, int N, int HW, int Cc, int groups, long x_gs,
                           long k_gs, long mask_gs, long f_gs, int state_dim, hipStream_t stream);

@@ -1578,6 +1578,11 @@ int sle_fwd_multi(const SleFwdArgs* vs, int n, float keep_scale, int N, int HW, 
 }
 
 
+// optional column copy riding along (the batch's actions into the critic input [enc | action]): ONE row by one wave, lane = column
+__device__ __forceinline__ void copy_rider_row(const ProprioArgs& a, int row, int lane) {
+  if (a.copy_dst && lane < a.copy_cols) a.copy_dst[(long)row * a.ld_copy_dst + lane] = a.copy_src[(long)row * a.ld_copy_src + lane];
+}
+
 // proprio branch (encoding.py:55-70) of ONE row by one wave, lane = output feature (also the body of proprio_fwd_kernel)
 __device__ __forceinline__ void proprio_row(const ProprioArgs& a, int S, int row, int lane) {
   float v = a.b[lane];
@@ -1602,8 +1607,7 @@ __device__ __forceinline__ void proprio_row(const ProprioArgs& a, int S, int row
   a.y[(long)row * a.ld_y + lane] = tanhf(xh * a.gamma[lane] + a.beta[lane]);
   if (a.xhat) a.xhat[(long)row * 64 + lane] = xh;
   if (a.rstd && lane == 0) a.rstd[row] = rstd;
-  // optional column copy riding along (the batch's actions into the critic input [enc | action])
-  if (a.copy_dst && lane < a.copy_cols) a.copy_dst[(long)row * a.ld_copy_dst + lane] = a.copy_src[(long)row * a.ld_copy_src + lane];
+  copy_rider_row(a, row, lane);
 }
 
 // SpatialLearnedEmbeddings, channel-blocked: a workgroup = 256 channels x kSleNb samples.  The embedding kernel K
@@ -1612,7 +1616,8 @@ __device__ __forceinline__ void proprio_row(const ProprioArgs& a, int S, int row
 // sample's 8 outputs stay in registers across the pixel loop (same hw-ascending sum as before: bit-identical).  The Dropout(0.1)
 // keep-mask (resnet_v1.py:351), when not supplied, is hashed from (seed, camera, GLOBAL sample, channel): three 64-bit hashes
 // give the eight 24-bit uniforms of a thread's eight outputs -- no mask tensor, no gen_noise launch.  Workgroups past the SLE
-// range run the proprio branch of the same instance (camera 0 only): one launch instead of two.
+// range run the proprio branch of the same instance (camera 0 only): one launch instead of two.  has_proprio == 2 (an agent
+// without the proprio branch, use_proprio=False): those workgroups carry the instance's column-copy rider alone.
 // kSleNb samples per workgroup; a rank's share of a data-parallel batch (<= 64 samples) takes 2 samples x 4 pixels (64 VGPRs), which
 // keeps more workgroups in flight (96 workgroups of 8 samples each took 64 us next to the trunk pass at 32 samples).  Larger
 // batches take 4 samples x 2 pixels: 32 sums + 16 embedding values + 8 pixels = 62 VGPRs, so a wave fits into the 80 registers per
@@ -1625,7 +1630,9 @@ __global__ __launch_bounds__(256) void sle_proprio_fwd_kernel(Multi<SleFwdArgs> 
   if ((int)blockIdx.x >= nb_sle) {
     if (!has_proprio || blockIdx.y != 0) return;
     const int row = ((int)blockIdx.x - nb_sle) * 4 + (threadIdx.x >> 6);
-    if (row < N) proprio_row(pv.v[blockIdx.z], S, row, threadIdx.x & 63);
+    if (row >= N) return;
+    if (has_proprio == 2) copy_rider_row(pv.v[blockIdx.z], row, threadIdx.x & 63);
+    else proprio_row(pv.v[blockIdx.z], S, row, threadIdx.x & 63);
     return;
   }
   const SleFwdArgs& v = mv.v[blockIdx.z];  // blockIdx.z = instance, blockIdx.y = camera
@@ -1708,11 +1715,14 @@ int sle_proprio_fwd_multi(const SleFwdArgs* vs, const ProprioArgs* ps, int n, fl
   // (block sizes: see the kernel; tests/test_sle_block_gpu.py holds its row counts to the 4)
   const int nb = N <= 64 ? 2 : 4;
   const int nb_sle = cdiv(Cc, 256) * cdiv(N, nb), nb_prop = ps ? cdiv(N, 4) : 0;
+  // ps without a state: no proprio rows, the trailing workgroups carry the riders alone (the caller passes none without a rider)
+  const int has_prop = !ps ? 0 : (ps[0].state ? 1 : 2);
+  for (int i = 0; ps && i < n; ++i) SERL_REQUIRE((ps[i].state != nullptr) == (has_prop == 1), "proprio rows in some instances of a launch and not in others");
   if (nb == 2)
-    SERL_LAUNCH_CHAIN((sle_proprio_fwd_kernel<2, 4>), dim3(nb_sle + nb_prop, groups, n), dim3(256), 0, stream, mv, pv, ps ? 1 : 0,
+    SERL_LAUNCH_CHAIN((sle_proprio_fwd_kernel<2, 4>), dim3(nb_sle + nb_prop, groups, n), dim3(256), 0, stream, mv, pv, has_prop,
                       1.0f / keep, (unsigned)(keep * 16777216.0f), keep, N, HW, Cc, x_gs, k_gs, mask_gs, f_gs, state_dim, nb_sle);
   else
-    SERL_LAUNCH_CHAIN((sle_proprio_fwd_kernel<4, 2>), dim3(nb_sle + nb_prop, groups, n), dim3(256), 0, stream, mv, pv, ps ? 1 : 0,
+    SERL_LAUNCH_CHAIN((sle_proprio_fwd_kernel<4, 2>), dim3(nb_sle + nb_prop, groups, n), dim3(256), 0, stream, mv, pv, has_prop,
                       1.0f / keep, (unsigned)(keep * 16777216.0f), keep, N, HW, Cc, x_gs, k_gs, mask_gs, f_gs, state_dim, nb_sle);
   SERL_HIP(hipGetLastError());
   return SERL_OK;

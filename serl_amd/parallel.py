@@ -206,7 +206,7 @@ class DataParallelLearner:
         if self.sched.slots > 1 and self.Bl >= 128 and hasattr(core, "set_chain_budget"):
             core.set_chain_budget(256)
         # overlap_reduce=True: bucketed, overlapped gradient all-reduce (DDP-style): the critic phase publishes [ensemble | head |
-        # proprio | scalars] before it starts the encoder-head backward; that bucket is reduced on a communication stream while
+        # proprio (none in an image-only agent) | scalars] before it starts the encoder-head backward; that bucket is reduced on a communication stream while
         # the encoder heads' weight gradients are still being computed, the second bucket follows, and only `apply` waits.
         # OPT-IN since round 3's measurement (profiles/README.md): a dependency that crosses HIP streams costs 60-100 us on this
         # stack, the update stream crosses twice per critic update (comm waits for the bucket event, `apply` waits for comm),
@@ -376,6 +376,9 @@ class TrunkFarmLearner(DataParallelLearner):
             # (the farm rests on features that depend on the pixels only; a live trunk's depend on every optimizer step so far)
             raise NotImplementedError("the trunk farm needs a frozen trunk: this core's is live (weight_decay on the pretrained "
                                       "trunk); use DataParallelLearner with the serial schedule")
+        if not getattr(core, "use_proprio", True):
+            raise NotImplementedError("the trunk farm serves agents with the proprio branch: this core is image-only "
+                                      "(use_proprio=False); use DataParallelLearner")
         super().__init__(core, gather, buffers, batch_sizes, 0, 1, all_reduce=None, seed=seed, ensemble=ensemble,
                          schedule=schedule, image_keys=image_keys, device_noise=device_noise)
         assert world >= 2 or role is not None, "a trunk farm needs an updater and at least one worker"

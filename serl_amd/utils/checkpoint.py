@@ -187,6 +187,17 @@ def load_state_dict(agent, sd: dict, restore_rng: bool = False):
                 raise ValueError(f"{section}: the state holds no std leaf of the policy (neither 'modules_actor/Dense_1' nor "
                                  "'modules_actor/log_stds': written by a std_parameterization='fixed' agent), this agent's head has "
                                  f"'{std_modules['log_stds' if std_mode == 'uniform' else 'Dense_1']}'; nothing was loaded")
+        # an image-only state (use_proprio=False: `encoder` holds the cameras alone) against an agent with the proprio branch, either
+        # way round: said in those words, before any size
+        enc = ("modules_actor", "encoder")
+        if keys and not _absent(tree, enc):
+            held = not _absent(tree, enc + ("Dense_0",)) or not _absent(tree, enc + ("LayerNorm_0",))
+            if held and not spec.use_proprio:
+                raise ValueError(f"{section}: the state holds the proprio branch ('modules_actor/encoder/Dense_0': written by a "
+                                 "use_proprio=True agent), this agent is image-only (use_proprio=False) and has no such leaf; nothing was loaded")
+            if not held and spec.use_proprio:
+                raise ValueError(f"{section}: the state holds no proprio branch ('modules_actor/encoder/Dense_0' is absent: written by an "
+                                 "image-only agent, use_proprio=False), this agent has one (use_proprio=True); nothing was loaded")
         # a tree of another kind holds nothing at the paths of such a leaf, which the size check below reports as 0 elements ...
         for leaf in optional:
             if leaf in tp and _absent(tree, tp[leaf][0]):

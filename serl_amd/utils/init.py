@@ -264,7 +264,10 @@ class NetSpec:
     critic_dims / policy_dims: None means (hidden, hidden); with both None the library is sent n_layers = 0, "two layers of
     cfg.hidden", the agent every call without mlp_shapes makes.  fixed_std: None, or with "fixed" act_dim float32 values as floats.
     ragged: serl_agent_opts.ragged_widths -- the widths are any integers in [1, 1024]; network_spec sets it where a width is off the
-    64 grid and nowhere else, so that widths on the grid through mlp_ragged=True give the NetSpec, and the agent, of the call without."""
+    64 grid and nowhere else, so that widths on the grid through mlp_ragged=True give the NetSpec, and the agent, of the call without.
+    use_proprio: False is serl_agent_opts.no_proprio -- EncodingWrapper(use_proprio=False) (common/encoding.py:53-72), the image codes
+    alone: no enc/proprio/* leaf, and the first kernels of both MLPs lose the 64 proprio rows.  network_spec sets it from
+    create_drq's use_proprio under image_only=True and nowhere else."""
     std_parameterization: str = "exp"
     tanh_squash_distribution: bool = True
     fixed_std: Optional[Tuple[float, ...]] = None
@@ -278,6 +281,7 @@ class NetSpec:
     critic_layer_norm: bool = True
     policy_layer_norm: bool = True
     ragged: bool = False
+    use_proprio: bool = True
 
     @property
     def dims(self):
@@ -296,6 +300,10 @@ class NetSpec:
         rates = (self.critic_dropout, self.policy_dropout)
         if not any(r > 0 for r in rates):
             return self
+        if not self.use_proprio:
+            raise NotImplementedError(
+                f"use_proprio=False under image_only=True with mlp_dropout=True and a positive dropout_rate (critic {rates[0]!r} / policy "
+                f"{rates[1]!r}) (served: Dropout in the MLPs of agents with the proprio branch)")
         cd, pd = self.dims
         if self.ragged and self.off_grid:
             raise NotImplementedError(
@@ -329,11 +337,14 @@ class NetSpec:
         theta_reference all take it"""
         cd, pd = self.dims
         return dict(std_parameterization=self.std_parameterization, critic_dims=cd, policy_dims=pd,
-                    critic_layer_norm=self.critic_layer_norm, policy_layer_norm=self.policy_layer_norm)
+                    critic_layer_norm=self.critic_layer_norm, policy_layer_norm=self.policy_layer_norm,
+                    **({} if self.use_proprio else {"use_proprio": False}))
 
     def config_entries(self):
-        """the network entries of agent.config; fixed_std and the use_layer_norm pair only where they say something"""
-        return dict(critic_activation=self.critic_activation, policy_activation=self.policy_activation,
+        """the network entries of agent.config; fixed_std, the use_layer_norm pair and use_proprio (False: the image-only agent)
+        only where they say something"""
+        return dict(**({} if self.use_proprio else {"use_proprio": False}),
+                    critic_activation=self.critic_activation, policy_activation=self.policy_activation,
                     critic_dropout_rate=self.critic_dropout, policy_dropout_rate=self.policy_dropout,
                     **({} if self.fixed_std is None else {"fixed_std": self.fixed_std}),
                     **({} if self.critic_layer_norm and self.policy_layer_norm else
@@ -355,14 +366,16 @@ class NetSpec:
         if self.fixed_std is not None:
             o.fixed_std = (ctypes.c_float * len(self.fixed_std))(*self.fixed_std)
         o.ragged_widths = 1 if self.ragged else 0
+        o.no_proprio = 0 if self.use_proprio else 1
         return o
 
 
 def network_spec(critic_network_kwargs, policy_network_kwargs, policy_kwargs, act_dim, *, mlp_dropout=False, mlp_shapes=False,
-                 mlp_plain=False, policy_fixed=False, mlp_ragged=False) -> NetSpec:
+                 mlp_plain=False, policy_fixed=False, mlp_ragged=False, use_proprio=True) -> NetSpec:
     """The checked NetSpec of create_states' / create_drq's three kwargs dicts under their five switches; every refusal is raised
     from the arguments alone, in the order of the lines below.  mlp_ragged=True: every width read below is any integer in
-    [1, 1024] (mlp.py:19-31 takes any list); without it the 64 grid, as always."""
+    [1, 1024] (mlp.py:19-31 takes any list); without it the 64 grid, as always.  use_proprio: create_drq's, already checked to be
+    a bool and read under image_only=True alone."""
     # policy_fixed=True: "fixed" / fixed_std are read (actor_critic_nets.py:189-192); else refused, as always
     std_param, squash, fixed = policy_mode_fixed(policy_kwargs, act_dim) if policy_fixed else (*policy_mode(policy_kwargs), None)
     # mlp_shapes=True: each network's own depth and per-layer widths (mlp.py:19-31); else the one width of [h, h], as always
@@ -375,7 +388,7 @@ def network_spec(critic_network_kwargs, policy_network_kwargs, policy_kwargs, ac
     if dims == ((hidden, hidden), (hidden, hidden)):
         dims = (None, None)    # [h, h] twice: the very agent the call without the switch makes
     spec = NetSpec(std_param, squash, None if fixed is None else tuple(float(x) for x in fixed), *acts, *rates, hidden, *dims, *lns)
-    return dataclasses.replace(spec, ragged=bool(mlp_ragged) and spec.off_grid).check()
+    return dataclasses.replace(spec, ragged=bool(mlp_ragged) and spec.off_grid, use_proprio=bool(use_proprio)).check()
 
 
 def _policy_std_shapes(Hd, A, std_parameterization):
@@ -392,8 +405,9 @@ def _policy_std_shapes(Hd, A, std_parameterization):
 
 def theta_shapes(n_cam, H, W, S, A, ensemble=10, hidden=256, bottleneck=256, sle_features=8, proprio_dim=64,
                  encoder_type="resnet-pretrained", num_stack=1, std_parameterization="exp", critic_dims=None, policy_dims=None, critic_layer_norm=True,
-                 policy_layer_norm=True):
-    """critic_dims / policy_dims: the hidden widths of each MLP, layer by layer (None: (hidden, hidden)); the heads follow the last.
+                 policy_layer_norm=True, use_proprio=True):
+    """use_proprio False (pixel agents): no enc/proprio/* leaf, and E = bottleneck * n_cam.
+    critic_dims / policy_dims: the hidden widths of each MLP, layer by layer (None: (hidden, hidden)); the heads follow the last.
     critic_layer_norm / policy_layer_norm False: that MLP's layers own w<j> and b<j> alone (mlp.py:29-30, use_layer_norm=False).
     S: the proprio Dense's input width -- T * S for a stack of T = num_stack frames, which EncodingWrapper folds into the
     channels ("B T H W C -> B H W (T C)", common/encoding.py:39-44): the SmallEncoder's first kernel is then (3,3,3T,32).
@@ -410,7 +424,7 @@ def theta_shapes(n_cam, H, W, S, A, ensemble=10, hidden=256, bottleneck=256, sle
             "temp/lagrange": (),
         }
     fh, fw = feat_hw(H, W)
-    E = bottleneck * n_cam + proprio_dim
+    E = bottleneck * n_cam + (proprio_dim if use_proprio else 0)
     sh = {}
     for k in range(n_cam):
         if encoder_type == "small":    # 4 x Conv(3x3, stride 2, VALID) with bias, then mean-pool -> Dense(256)
@@ -428,8 +442,8 @@ def theta_shapes(n_cam, H, W, S, A, ensemble=10, hidden=256, bottleneck=256, sle
     sh.update({
         **_mlp_shapes("critic", (N,), E + A, cd, critic_layer_norm),
         "critic/head/kernel": (cd[-1], 1), "critic/head/bias": (1,),
-        "enc/proprio/dense/kernel": (S, proprio_dim), "enc/proprio/dense/bias": (proprio_dim,),
-        "enc/proprio/ln/scale": (proprio_dim,), "enc/proprio/ln/bias": (proprio_dim,),
+        **({"enc/proprio/dense/kernel": (S, proprio_dim), "enc/proprio/dense/bias": (proprio_dim,),
+            "enc/proprio/ln/scale": (proprio_dim,), "enc/proprio/ln/bias": (proprio_dim,)} if use_proprio else {}),
         **_mlp_shapes("actor", (), E, pd, policy_layer_norm),
         "actor/mean/kernel": (pd[-1], A), "actor/mean/bias": (A,),
         **_policy_std_shapes(pd[-1], A, std_parameterization),
@@ -455,6 +469,23 @@ def init_trunk(seed=42):
 
 
 def init_theta(n_cam, H, W, S, A, seed=42, temperature_init=1e-2, **kw):
+    if not kw.get("use_proprio", True) and n_cam > 0:
+        # The image-only agent: the draw of the proprio agent of the same seed, so that every leaf the two share keeps its values;
+        # enc/proprio/* is dropped, and the two first kernels lose the rows of the 64 proprio columns (the last of the code) and
+        # are rescaled to the xavier-uniform bound of their new fan-in.
+        full = init_theta(n_cam, H, W, S, A, seed=seed, temperature_init=temperature_init, **{**kw, "use_proprio": True})
+        out = {}
+        Eimg = kw.get("bottleneck", 256) * n_cam      # the code's width; the proprio columns were [Eimg, Eimg + proprio_dim)
+        Efull = Eimg + kw.get("proprio_dim", 64)
+        for name, shp in theta_shapes(n_cam, H, W, S, A, **kw).items():
+            v = full[name]
+            if name in ("critic/w1", "actor/w1"):     # (N, E + A, d) and (E, d): the rows [Eimg, Efull) leave
+                keep = np.r_[0:Eimg, Efull:v.shape[-2]]
+                scale = math.sqrt((v.shape[-2] + v.shape[-1]) / (shp[-2] + shp[-1]))
+                v = (np.take(v, keep, axis=-2).astype(np.float64) * scale).astype(np.float32)
+            assert v.shape == tuple(shp), (name, v.shape, shp)
+            out[name] = v
+        return out
     rng = np.random.Generator(np.random.PCG64(np.random.SeedSequence([seed, 2])))
     out = {}
     for name, shp in theta_shapes(n_cam, H, W, S, A, **kw).items():

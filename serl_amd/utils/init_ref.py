@@ -84,7 +84,7 @@ def _init_of(name, shape):
 
 def theta_leaves(image_keys: Sequence[str], H, W, S, A, ensemble=10, encoder_type="resnet-pretrained", num_stack=1,
                  hidden=256, std_parameterization="exp", critic_dims=None, policy_dims=None, critic_layer_norm=True,
-                 policy_layer_norm=True) -> List[Leaf]:
+                 policy_layer_norm=True, use_proprio=True) -> List[Leaf]:
     """The trainable leaves of DrQAgent.create_drq (image_keys non-empty) or SACAgent.create_states (image_keys empty);
     hidden: the MLPs' width (hidden_dims=[hidden, hidden]), or critic_dims / policy_dims: each MLP's own widths, layer by layer
     (Dense_2 / LayerNorm_2 and up take their keys from their paths like every other leaf).  std_parameterization="uniform": the zero-initialised log_stds
@@ -92,14 +92,17 @@ def theta_leaves(image_keys: Sequence[str], H, W, S, A, ensemble=10, encoder_typ
     counter, not on its siblings), so the rest of the tree is bit-identical to the "exp" agent's.  "fixed"
     (actor_critic_nets.py:189-192): no std leaf at all, the rest as for "exp" by the same argument.
     critic_layer_norm / policy_layer_norm False (mlp.py:29-30): that MLP has no LayerNorm leaves; a LayerNorm draws nothing, so the
-    Dense leaves keep their keys and values."""
+    Dense leaves keep their keys and values.
+    use_proprio False (common/encoding.py:53-72): `encoder` has no Dense_0 / LayerNorm_0; the camera heads keep their keys by the
+    same argument, and the two first kernels draw with the fan-in of the image codes alone."""
     from ..agents.flax_tree import theta_paths
     shapes = theta_shapes(len(image_keys), H, W, S, A, ensemble=ensemble, hidden=hidden, encoder_type=encoder_type,
                           num_stack=num_stack, std_parameterization=std_parameterization, critic_dims=critic_dims,
-                          policy_dims=policy_dims, critic_layer_norm=critic_layer_norm, policy_layer_norm=policy_layer_norm)
+                          policy_dims=policy_dims, critic_layer_norm=critic_layer_norm, policy_layer_norm=policy_layer_norm,
+                          use_proprio=use_proprio)
     paths = theta_paths(tuple(image_keys), encoder_type=encoder_type, std_parameterization=std_parameterization,
                         critic_dims=critic_dims, policy_dims=policy_dims, critic_layer_norm=critic_layer_norm,
-                        policy_layer_norm=policy_layer_norm)
+                        policy_layer_norm=policy_layer_norm, use_proprio=use_proprio)
     # the vmapped module: DrQ ensemblizes the critic's MLP (drq.py:206-209), state SAC the whole Critic (sac.py:516-517)
     vm = ("modules_critic", "network") if image_keys else ("modules_critic",)
     out = []
@@ -110,11 +113,11 @@ def theta_leaves(image_keys: Sequence[str], H, W, S, A, ensemble=10, encoder_typ
     return out
 
 
-def bc_leaves(image_keys: Sequence[str], H, W, S, A) -> List[Leaf]:
-    """The trainable leaves of BCAgent.create (no LayerNorm in the policy MLP)."""
+def bc_leaves(image_keys: Sequence[str], H, W, S, A, use_proprio=True) -> List[Leaf]:
+    """The trainable leaves of BCAgent.create (no LayerNorm in the policy MLP); use_proprio False: without the proprio branch."""
     from ..agents.flax_tree import bc_paths, bc_shapes
     from .init import trunk_shapes
-    shapes, paths = bc_shapes(tuple(image_keys), H, W, S, A), bc_paths(tuple(image_keys))
+    shapes, paths = bc_shapes(tuple(image_keys), H, W, S, A, use_proprio=use_proprio), bc_paths(tuple(image_keys), use_proprio)
     out = []
     for name, shp in shapes.items():
         if name in trunk_shapes():
@@ -225,19 +228,19 @@ def draw_flat(leaves: Sequence[Leaf], init_rng, device: Optional[int] = 0, tempe
 
 def theta_reference(image_keys, H, W, S, A, rng, ensemble=10, encoder_type="resnet-pretrained", temperature_init=1.0,
                     device: Optional[int] = 0, num_stack=1, hidden=256, std_parameterization="exp", critic_dims=None,
-                    policy_dims=None, critic_layer_norm=True, policy_layer_norm=True) -> Dict[str, np.ndarray]:
+                    policy_dims=None, critic_layer_norm=True, policy_layer_norm=True, use_proprio=True) -> Dict[str, np.ndarray]:
     """init_theta's leaves as the reference's DrQ / state-SAC create path draws them from `rng` (drq.py:69, sac.py:368).
     S is the flattened proprio width T * S of a stack of T = num_stack frames; the widened leaves draw with their real fan-in.
     hidden: the MLPs' width; its leaves draw with the fans of that width."""
     return draw_flat(theta_leaves(image_keys, H, W, S, A, ensemble, encoder_type, num_stack, hidden, std_parameterization,
-                                  critic_dims, policy_dims, critic_layer_norm, policy_layer_norm),
+                                  critic_dims, policy_dims, critic_layer_norm, policy_layer_norm, use_proprio),
                      init_rng_of(reference_key(rng)),
                      device, temperature_init)
 
 
-def bc_reference(image_keys, H, W, S, A, rng, device: Optional[int] = 0) -> Dict[str, np.ndarray]:
+def bc_reference(image_keys, H, W, S, A, rng, device: Optional[int] = 0, use_proprio=True) -> Dict[str, np.ndarray]:
     """BCAgent.create's trainable leaves from `rng` (bc.py: rng, init_rng = split(rng))."""
-    return draw_flat(bc_leaves(image_keys, H, W, S, A), init_rng_of(reference_key(rng)), device)
+    return draw_flat(bc_leaves(image_keys, H, W, S, A, use_proprio), init_rng_of(reference_key(rng)), device)
 
 
 def classifier_reference(image_keys, H, W, key, device: Optional[int] = 0) -> Dict[str, np.ndarray]:
