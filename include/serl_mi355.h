@@ -614,12 +614,12 @@ int serl_agent_sample_actions(serl_agent* a, const uint8_t* dev_frames, const fl
                               const float* dev_eps, float* dev_out_actions, void* stream);
 
 /* ---- Read-only evaluation: what the trained networks think, without a step -------------------------------------------------
- * The three entries below read the parameters and leave every piece of training state as it was: no byte of the online or
+ * The four entries below read the parameters and leave every piece of training state as it was: no byte of the online or
  * target parameters, the Adam moments, the step counter, the agent's noise counter, the reward-label state, or the three
  * pipeline slots (their trunk features and batch bindings) is written.  They use the scratch feature slot of
  * serl_agent_sample_actions, the activations, the gradient scratch and an info accumulator of their own; the next update
  * starts with serl_agent_begin_update as always.  They share the trunk workspace with serl_agent_encode_slot: order them
- * behind a trunk pass in flight on another stream, as for serl_agent_sample_actions.  No Dropout (train=False) in the first two.
+ * behind a trunk pass in flight on another stream, as for serl_agent_sample_actions.  No Dropout (train=False) in the first three.
  * Refused with SERL_ERR_INVALID, the message naming the argument and the value: n outside [1, cfg.batch]; dev_logp_out without
  * dev_actions; NULL dev_frames on an agent with cameras (a state-only agent, n_cam == 0, takes NULL). */
 /* forward_critic(obs, actions, train=False) (sac.py:33-55); target != 0: with target_params (sac.py:57-69).
@@ -627,6 +627,14 @@ int serl_agent_sample_actions(serl_agent* a, const uint8_t* dev_frames, const fl
  * q_out f32[ensemble][n] device. */
 int serl_agent_eval_q(serl_agent* a, const uint8_t* dev_frames, const float* dev_state, const float* dev_actions,
                       int n, int target, float* dev_q_out, void* stream);
+/* The same on n_actions candidate actions per observation (multiple_action_q_function, actor_critic_nets.py:33-46: actions of
+ * three dimensions): actions f32[n][n_actions][A] device, q_out f32[ensemble][n][n_actions] device -- entry [e][b][j] is what
+ * serl_agent_eval_q gives for observation b with action [b][j], up to the order of the first layer's sums.  The encoder runs
+ * once over the n observations, and so does the observation's share of the critic's first layer; the candidates fan out behind
+ * it.  The rows of the critic's activations are n * n_actions: refused with SERL_ERR_INVALID when n * n_actions lies outside
+ * [1, cfg.batch], n_actions < 1, or dev_actions / dev_q_out is NULL (and what serl_agent_eval_q refuses). */
+int serl_agent_eval_q_actions(serl_agent* a, const uint8_t* dev_frames, const float* dev_state, const float* dev_actions, int n,
+                              int n_actions, int target, float* dev_q_out, void* stream);
 /* forward_policy(obs, train=False) (sac.py:71-91): loc, scale_diag, mode, and log_prob(dev_actions) when given.
  * Any output pointer may be NULL; dev_logp_out requires dev_actions.  mean, std, mode f32[n][A], logp f32[n], device.
  * Under the tanh squash log_prob follows distrax's Transformed.log_prob with the Tanh bijector: u = atanh(a),

@@ -61,6 +61,8 @@ CHAIN = [
     ("policy_stats_kernel<1>", 80),
     ("policy_stats_fixed_kernel<false>", 80),   # ... of a fixed-std agent (serl_agent_create_fixed_std)
     ("policy_stats_fixed_kernel<true>", 80),
+    # ... (serl_agent_eval_q_actions): the critic's first layer fanned out over the candidates, at the default width; 16 KB of LDS
+    ("critic_fanout_kernel<4>", 80),
 ]
 
 

@@ -139,6 +139,7 @@ SIGNATURES = {
     "serl_agent_sample_actions": [vp, vp, vp, i32, vp, vp, vp],
     # read-only evaluation: forward_critic / forward_target_critic, forward_policy, loss_fns without the step
     "serl_agent_eval_q": [vp, vp, vp, vp, i32, i32, vp, vp],
+    "serl_agent_eval_q_actions": [vp, vp, vp, vp, i32, i32, i32, vp, vp],
     "serl_agent_eval_policy": [vp, vp, vp, vp, i32, vp, vp, vp, vp, vp],
     "serl_agent_eval_losses": [vp, P(SerlBatch), P(SerlNoise), P(SerlInfo), vp],
     "serl_agent_trunk_forward": [vp, vp, i32, vp, vp],

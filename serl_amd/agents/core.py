@@ -382,10 +382,20 @@ class AgentCore(Handle):
 
     def eval_q(self, frames_u8, state, actions, target=False) -> torch.Tensor:
         """forward_critic(obs, actions, train=False), or with target_params -> f32[ensemble, n] (device).  frames_u8
-        u8[n_cam, n, (T,) H, W, 3] or None (state-only), state f32[n, T*S], actions f32[n, A]: device tensors, n <= cfg.batch."""
+        u8[n_cam, n, (T,) H, W, 3] or None (state-only), state f32[n, T*S], actions f32[n, A]: device tensors, n <= cfg.batch.
+        actions f32[n, N, A] (three dimensions, as multiple_action_q_function reads them): N candidate actions per observation
+        -> f32[ensemble, n, N] from serl_agent_eval_q_actions, one encoder pass over the n observations; n * N <= cfg.batch."""
         n = state.shape[0]
-        out = torch.empty((self.cfg.ensemble, n), dtype=torch.float32, device=self.device)
         keep = [None if frames_u8 is None else frames_u8.contiguous(), state.contiguous(), actions.contiguous()]
+        if actions.dim() == 3:
+            if actions.shape[0] != n:
+                raise ValueError(f"actions {tuple(actions.shape)}: the leading axis must be the {n} observations")
+            N = actions.shape[1]
+            out = torch.empty((self.cfg.ensemble, n, N), dtype=torch.float32, device=self.device)
+            _lib.check(self.L.serl_agent_eval_q_actions(self._h, self._ptr(keep[0]), keep[1].data_ptr(), keep[2].data_ptr(), n, N,
+                                                        1 if target else 0, out.data_ptr(), self._stream()))
+            return out
+        out = torch.empty((self.cfg.ensemble, n), dtype=torch.float32, device=self.device)
         _lib.check(self.L.serl_agent_eval_q(self._h, self._ptr(keep[0]), keep[1].data_ptr(), keep[2].data_ptr(), n,
                                             1 if target else 0, out.data_ptr(), self._stream()))
         return out

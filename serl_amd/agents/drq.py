@@ -676,14 +676,26 @@ class DrQAgent:
         a = np.asarray(actions, np.float32).reshape(n, self.core.cfg.act_dim)
         return torch.from_numpy(a).to(self.core.device)
 
-    def _chunks(self, n):
-        """n > cfg.batch is served in chunks of cfg.batch rows"""
-        B = int(self.core.cfg.batch)
+    def _eval_candidates(self, actions, n):
+        """actions [n, N, A]: N candidate actions for each of the n observations -> device tensor"""
+        c = self.core.cfg
+        a = np.asarray(actions, np.float32)
+        if a.shape[0] != n or a.shape[2] != c.act_dim:
+            raise ValueError(f"actions of shape {a.shape}: three dimensions are [n, N, A] with n = {n} observations and A = {c.act_dim}")
+        if not 1 <= a.shape[1] <= c.batch:
+            raise ValueError(f"{a.shape[1]} candidate actions per observation: one observation's candidates are rows of one call, "
+                             f"1 to batch_size = {c.batch}")
+        return torch.from_numpy(np.ascontiguousarray(a)).to(self.core.device)
+
+    def _chunks(self, n, per_row=1):
+        """n > cfg.batch is served in chunks of cfg.batch rows; with per_row candidate actions per observation in chunks of
+        cfg.batch // per_row observations"""
+        B = int(self.core.cfg.batch) // per_row
         return [(lo, min(lo + B, n)) for lo in range(0, n, B)]
 
     def _q_dev(self, f, s, a, target):
         return torch.cat([self.core.eval_q(None if f is None else f[:, lo:hi], s[lo:hi], a[lo:hi], target)
-                          for lo, hi in self._chunks(s.shape[0])], dim=1)
+                          for lo, hi in self._chunks(s.shape[0], a.shape[1] if a.dim() == 3 else 1)], dim=1)
 
     def _policy_dev(self, f, s, a):
         parts = [self.core.eval_policy(None if f is None else f[:, lo:hi], s[lo:hi], None if a is None else a[lo:hi])
@@ -692,10 +704,13 @@ class DrQAgent:
 
     def q_values(self, observations, actions, *, target: bool = False) -> np.ndarray:
         """forward_critic(observations, actions, train=False) -- with target=True forward_target_critic -> f32[ensemble, n]
-        (n = 1 for a single observation)."""
+        (n = 1 for a single observation).  Actions of three dimensions, [n, N, A], are N candidate actions per observation, as in
+        the reference's multiple_action_q_function (actor_critic_nets.py:33-46) -> f32[ensemble, n, N]: every observation is
+        encoded once, whatever N is.  n must be the number of observations and N at most batch_size."""
         self._sync_side_stream()
         f, s, n, _ = self._eval_obs(observations)
-        return self._q_dev(f, s, self._eval_actions(actions, n), target).cpu().numpy()
+        a = self._eval_candidates(actions, n) if np.ndim(actions) == 3 else self._eval_actions(actions, n)
+        return self._q_dev(f, s, a, target).cpu().numpy()
 
     def policy_stats(self, observations, actions=None) -> dict:
         """forward_policy(observations, train=False) -> {"mean": .distribution.loc, "std": .scale_diag, "mode": .mode()} [n, A]

@@ -109,7 +109,9 @@ class SACAgent(DrQAgent):
         raise AttributeError("SACAgent has no update_critics (drq.py:296-328 is DrQ-only); use update(networks_to_update={'critic'})")
 
     def _eval_obs(self, observations):
-        """flat observations, (S,) or (n, S), as sample_actions takes them -> (None, state f32[n, S] device, n, batched)"""
+        """flat observations, (S,) or (n, S), as sample_actions takes them -> (None, state f32[n, S] device, n, batched).
+        q_values / policy_stats / evaluate_batch are DrQAgent's over this view: q_values with actions [n, N, A] scores N candidate
+        actions per state in one call (serl_agent_eval_q_actions), the state's share of the first critic layer computed once."""
         st = np.asarray(observations, np.float32)
         batched = st.ndim == 2
         n = st.shape[0] if batched else 1

@@ -624,10 +624,11 @@ int policy_fwd_multi(serl_agent* a, const PolJob* jobs, int n, int cnt, hipStrea
 // Critic ensemble forward on x = [enc | action] (actor_critic_nets.py:56-73, drq.py:201-207) for n independent
 // (parameters, input) pairs; the shared Q head is fused into the LN kernel of the last layer
 struct CritJob { const float* P; CritBuf* cb; DenseLnDrop drop[kL]; };   // drop: the Dropout sites of the layers (zero: train=False)
-int critic_fwd_multi(serl_agent* a, const CritJob* jobs, int n, int cnt, hipStream_t st) {
+// (first > 0: layers first .. nc - 1 alone, on what another launch left in layer first - 1's buffer: serl_agent_eval_q_actions)
+int critic_fwd_multi(serl_agent* a, const CritJob* jobs, int n, int cnt, hipStream_t st, int first = 0) {
   const Offs& o = a->o;
   SERL_REQUIRE(n >= 1 && n <= 3, "bad critic instance count");
-  for (int l = 0; l < o.nc; ++l) {
+  for (int l = first; l < o.nc; ++l) {
     LayerJob d[3];
     for (int i = 0; i < n; ++i) {
       const float* P = jobs[i].P;
@@ -1973,6 +1974,49 @@ int serl_agent_eval_q(serl_agent* a, const uint8_t* dev_frames, const float* dev
   const CritJob cj{P, &cb, {}};   // train=False: no Dropout
   RC(critic_fwd_multi(a, &cj, 1, n, st));
   SERL_HIP(hipMemcpyAsync(dev_q_out, cb.q, sizeof(float) * c.ensemble * n, hipMemcpyDeviceToDevice, st));   // [ensemble][n]
+  return SERL_OK;
+}
+
+int serl_agent_eval_q_actions(serl_agent* a, const uint8_t* dev_frames, const float* dev_state, const float* dev_actions, int n,
+                              int n_actions, int target, float* dev_q_out, void* stream) {
+  SERL_REQUIRE(a, "NULL agent");
+  const serl_agent_cfg& c = a->cfg;
+  SERL_REQUIRE(n_actions >= 1, "n_actions %d is not positive", n_actions);
+  SERL_REQUIRE(n >= 1 && (long)n * n_actions <= c.batch, "n * n_actions = %d * %d not in [1,%d]", n, n_actions, c.batch);
+  RC(eval_check(a, dev_frames, dev_state, n));
+  SERL_REQUIRE(dev_actions && dev_q_out, "dev_actions or dev_q_out is NULL");
+  hipStream_t st = (hipStream_t)stream;
+  SERL_HIP(hipSetDevice(c.device));
+  EvalScope scope(a);
+  const Offs& o = a->o;
+  const float* P = target ? a->theta_t : a->theta;
+  CritBuf& cb = target ? a->critT : a->crit;
+  // one encoder pass over the n observations, no actions rider: columns [0, E) of cb.x
+  RC(eval_encode(a, dev_frames, dev_state, n, P, target ? &a->encT : &a->encO, nullptr, nullptr, st));
+  // Layer 1.  The observation's share of the Dense, enc . W[0:E], on n rows per member: the layer's forward GEMM cut at K = E (the
+  // kernel leaf as it lies, same leading dimension).  Then the fan-out rows: n * n_actions per member into the layer's buffer,
+  // ordered (member, observation, candidate) -- the block per member that the layers behind read as rows = n * n_actions.
+  const DenseLn& L = o.c[0];
+  const int rows = n * n_actions;
+  const DenseLnIo io{cb.x, a->XA, 0, cb.m.l[0].h, L.N, (long)rows * L.N, nullptr, nullptr};
+  const int splitk = split_for(a->split_budget, n, L.N, L.groups, critic_smax(0));
+  SERL_REQUIRE((long)L.groups * splitk * n * L.N <= a->slabs_cap, "Dense layer: %d groups x %d K-splits x %d rows x width %d exceeds the slab scratch of %ld floats",
+               L.groups, splitk, n, L.N, a->slabs_cap);
+  GemmDesc g = layer_fwd(L, P, io, n, a->slabs, splitk);
+  g.K = a->E;
+  FanoutArgs f{};
+  f.l = layer_ln_fwd(L, P, io, n, g);
+  if (o.nc == 1) {   // a one-layer critic: the Q head rides on the fan-out rows (critic_fwd_multi's rider)
+    f.l.dot_w = P + o.c_hw; f.l.dot_b = P + o.c_hb; f.l.dot_out = cb.q;
+    f.l.dot_gstride = a->state_only ? L.N : 0; f.l.dot_b_gstride = a->state_only ? 1 : 0;
+  }
+  f.w_act = P + L.W + (long)a->E * L.N; f.w_gstride = L.w_gs;
+  f.actions = dev_actions; f.N = n_actions; f.A = c.act_dim;
+  RC(gemm_f32(g, st));
+  RC(critic_fanout_fwd(f, L.N, st));
+  const CritJob cj{P, &cb, {}};   // train=False: no Dropout
+  RC(critic_fwd_multi(a, &cj, 1, rows, st, 1));   // layers 2 .. and the Q head on n * n_actions rows per member (none: one layer)
+  SERL_HIP(hipMemcpyAsync(dev_q_out, cb.q, sizeof(float) * c.ensemble * rows, hipMemcpyDeviceToDevice, st));   // [ensemble][n][n_actions]
   return SERL_OK;
 }
 

@@ -29,6 +29,19 @@ int reduce_slabs(const float* slabs, int S, long slab_stride, int groups, int ro
 // Instances without gamma and beta are LayerNorm-free MLP layers (mlp.py:29-30; plain_row): y = act(bias + slabs), the same riders,
 // the pre-activation in xhat, rstd not written.  All instances of a launch are plain or none is; plain ones carry no Dropout.
 int ln_fwd_multi(const LnFwdArgs* a, int n, int D, hipStream_t stream);
+// The critic's first layer on N candidate actions per observation (multiple_action_q_function, actor_critic_nets.py:33-46): the
+// rows of `l` are the n observations per group -- slabs of the K-split GEMM of the encodings with the kernel's first E rows, bias,
+// gamma / beta (or neither: a plain layer), act, d and the dot rider as ln_fwd_multi takes them -- and every row becomes N rows,
+//   y[(g n + b) N + j][:] = act(LN(base[g][b] + actions[b][j] . w_act[g]))      (y [groups n N][D]; dot_out [groups n N])
+// w_act: group 0's action block, the kernel's rows E .. E + A ([A][D], row stride D), group g's w_gstride floats further.
+// train=False: no Dropout, and xhat / rstd are not written (no backward pass reads this layer).  ld_y and y_goff are not read.
+struct FanoutArgs {
+  LnFwdArgs l;
+  const float* w_act; long w_gstride;
+  const float* actions;   // [n][N][A]
+  int N, A;               // A <= 64
+};
+int critic_fanout_fwd(const FanoutArgs& f, int D, hipStream_t stream);
 // One width-256 ReLU instance with a row-dot (the reward classifier's head), closed for reward labelling: dot_out = logits,
 // label[row] = sigmoid(logit) >= 0.5, mean[0] = the labels' mean, summed in a fixed order inside the launch (ctr: one zeroed
 // arrival counter)

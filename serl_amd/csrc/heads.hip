@@ -1151,6 +1151,125 @@ int ln_fwd_multi(const LnFwdArgs* as, int n, int D, hipStream_t stream) {
   return SERL_OK;
 }
 
+// =============================================================================================
+// The critic's first layer fanned out over N candidate actions per observation (critic_fanout_fwd, heads.h)
+//   pre[g][b][j][:] = bias[g] + sum_s slab[g][s][b][:] + sum_k act[b][j][k] * Wact[g][k][:],   y[g][b][j] = act(LayerNorm(pre)) or act(pre)
+// =============================================================================================
+// Work split.  A workgroup is one ensemble member g and four observations, one per wave: the wave sums the slabs of its (g, b)
+// ONCE into the strided row layout of ln_row (lane l holds columns l + 64 i) and keeps that base row in registers while it loops
+// over the observation's candidates, kFanCj<VPL> of them at a time in registers.  The action block Wact[g] ([A][D], at most 64 x
+// 1024 floats) goes through LDS in chunks of kFanLds / D kernel rows that the four waves share.  A block that is one chunk -- A * D
+// <= kFanLds, every robot arm at the default width -- is staged once per workgroup, before the first candidate; a larger block is
+// staged once per register batch of candidates.  A candidate's A action values are uniform over the wave: lane k of one coalesced
+// load holds act[b][j][k], and the FMA loop reads value k from that register with v_readlane (a scalar operand), never per lane.
+// A candidate's sum starts from the base row and adds the action terms in ascending k: two equal candidates give equal bits,
+// wherever they stand.
+constexpr int kFanLds = 4096;   // floats of the action block in LDS at a time: 16 KB, the chain kernels' LDS budget
+template <int VPL>
+constexpr int kFanCj = VPL <= 4 ? 8 : (VPL <= 8 ? 16 / VPL : 1);   // candidates whose rows a wave accumulates at once: 8, or what 16 registers hold
+
+// The epilogue of one candidate row held in v (the arithmetic of ln_row / plain_row at this width: statistics over the true width
+// of a ragged row, whose pads stay exactly zero as there), written as row `row` of y [rows][D] and of the Q-head rider.
+template <int VPL>
+__device__ __forceinline__ void fanout_row(const LnFwdArgs& a, float (&v)[VPL], long row, int grp, int lane, long pb) {
+  constexpr int D = 64 * VPL;
+  if (a.gamma) {   // (uniform over the launch)
+    float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+    for (int i = 0; i < VPL; ++i) { s1 += v[i]; s2 += v[i] * v[i]; }
+    wave_sum2(s1, s2);
+    float mean, rstd;
+    ln_mean_rstd_n(s1, s2, a.d ? a.d : D, mean, rstd);
+#pragma unroll
+    for (int i = 0; i < VPL; ++i) v[i] = (v[i] - mean) * rstd * a.gamma[pb + 64 * i] + a.beta[pb + 64 * i];
+  }
+  ln_activate(a.act, v);
+  float d = 0.f;
+#pragma unroll
+  for (int i = 0; i < VPL; ++i) {
+    const int col = lane + 64 * i;
+    a.y[row * D + col] = v[i];
+    if (a.dot_out) d += v[i] * a.dot_w[(long)grp * a.dot_gstride + col];
+  }
+  if (a.dot_out) {
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) d += __shfl_xor(d, off);
+    d += a.dot_b[(long)grp * a.dot_b_gstride];
+    if (lane == 0) a.dot_out[row] = d;
+  }
+}
+
+template <int VPL>
+__global__ __launch_bounds__(256) void critic_fanout_kernel(FanoutArgs f) {
+  constexpr int D = 64 * VPL, KC = kFanLds / D, CJ = kFanCj<VPL>;
+  __shared__ float wl[kFanLds];
+  const LnFwdArgs& a = f.l;
+  const int tid = threadIdx.x, lane = tid & 63, grp = blockIdx.y, n = a.rows_per_group, N = f.N, A = f.A;
+  // a wave past the last observation stages and waits with the others on the last observation's addresses and stores nothing
+  const int bw = blockIdx.x * 4 + (tid >> 6);
+  const bool live = bw < n;
+  const int b = __builtin_amdgcn_readfirstlane(live ? bw : n - 1);
+  const long pb = (long)grp * a.pstride + lane;
+  float base[VPL];
+  ln_gather<VPL, false>(a, (long)grp * a.S * a.slab_stride + (long)b * D + lane, pb, base);
+  const float* wsrc = f.w_act + (long)grp * f.w_gstride;
+  const float* arow = f.actions + (long)b * N * A;
+  const int nchunks = (A + KC - 1) / KC;
+  for (int j0 = 0; j0 < N; j0 += CJ) {
+    float av[CJ], acc[CJ][VPL];
+#pragma unroll
+    for (int c = 0; c < CJ; ++c) {   // (a batch past the last candidate repeats the last one and is not written)
+      av[c] = lane < A ? arow[(long)min(j0 + c, N - 1) * A + lane] : 0.f;
+#pragma unroll
+      for (int i = 0; i < VPL; ++i) acc[c][i] = base[i];
+    }
+    for (int ch = 0; ch < nchunks; ++ch) {
+      const int k0 = ch * KC, kc = min(KC, A - k0);
+      if (nchunks > 1 || j0 == 0) {   // (uniform over the workgroup)
+        __syncthreads();              // the rows of the chunk before are read
+        for (int i = tid; i < kc * D; i += 256) wl[i] = wsrc[(long)k0 * D + i];
+        __syncthreads();
+      }
+      for (int k = 0; k < kc; ++k) {
+        float w[VPL];
+#pragma unroll
+        for (int i = 0; i < VPL; ++i) w[i] = wl[k * D + lane + 64 * i];
+#pragma unroll
+        for (int c = 0; c < CJ; ++c) {
+          const float s = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, av[c]), k0 + k));
+#pragma unroll
+          for (int i = 0; i < VPL; ++i) acc[c][i] = fmaf(s, w[i], acc[c][i]);
+        }
+      }
+    }
+    if (live) {   // (uniform over the wave)
+#pragma unroll
+      for (int c = 0; c < CJ; ++c)
+        if (j0 + c < N) fanout_row<VPL>(a, acc[c], ((long)grp * n + b) * N + j0 + c, grp, lane, pb);
+    }
+  }
+}
+
+int critic_fanout_fwd(const FanoutArgs& f, int D, hipStream_t stream) {
+  const LnFwdArgs& a = f.l;
+  SERL_REQUIRE(SERL_LN_WIDTH_OK(D), "fanned-out critic layer: width %d unsupported (a multiple of 64 in [64, 1024])", D);
+  SERL_REQUIRE(f.A >= 1 && f.A <= 64, "fanned-out critic layer: %d action columns; a wave holds one candidate's actions, 1 to 64", f.A);
+  SERL_REQUIRE(f.N >= 1 && a.rows_per_group >= 1 && a.rows >= a.rows_per_group && a.rows % a.rows_per_group == 0 && a.S >= 1,
+               "fanned-out critic layer: bad shape (%d candidates, %d rows, %d per group, %d slabs)", f.N, a.rows, a.rows_per_group, a.S);
+  SERL_REQUIRE(a.slabs && a.y && f.w_act && f.actions && (a.gamma == nullptr) == (a.beta == nullptr), "fanned-out critic layer: NULL tensor");
+  SERL_REQUIRE(a.d >= 0 && a.d < D && a.act >= 0 && a.act < kActCount && a.drop.mode == kLnDropNone,
+               "fanned-out critic layer: true width %d in %d, activation code %d, Dropout mode %d", a.d, D, a.act, a.drop.mode);
+  const dim3 grid(cdiv(a.rows_per_group, 4), a.rows / a.rows_per_group);
+#define SERL_FAN_CASE(V) case V: SERL_LAUNCH_CHAIN(critic_fanout_kernel<V>, grid, dim3(256), 0, stream, f); break;
+  switch (D / 64) {
+    SERL_FAN_CASE(1) SERL_FAN_CASE(2) SERL_FAN_CASE(3) SERL_FAN_CASE(4) SERL_FAN_CASE(5) SERL_FAN_CASE(6) SERL_FAN_CASE(7) SERL_FAN_CASE(8)
+    SERL_FAN_CASE(9) SERL_FAN_CASE(10) SERL_FAN_CASE(11) SERL_FAN_CASE(12) SERL_FAN_CASE(13) SERL_FAN_CASE(14) SERL_FAN_CASE(15) SERL_FAN_CASE(16)
+  }
+#undef SERL_FAN_CASE
+  SERL_HIP(hipGetLastError());
+  return SERL_OK;
+}
+
 // REDQ target of sample b (sac.py:150-176): y = r + discount * mask * min over the selected (or all) target members
 // [- alpha * log pi(a'|s') with backup_entropy, outside the discount as the reference has it]
 __device__ __forceinline__ float redq_target(const LossArgs& L, int b) {
