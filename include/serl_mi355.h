@@ -614,12 +614,12 @@ int serl_agent_sample_actions(serl_agent* a, const uint8_t* dev_frames, const fl
                               const float* dev_eps, float* dev_out_actions, void* stream);
 
 /* ---- Read-only evaluation: what the trained networks think, without a step -------------------------------------------------
- * The four entries below read the parameters and leave every piece of training state as it was: no byte of the online or
+ * The six entries below read the parameters and leave every piece of training state as it was: no byte of the online or
  * target parameters, the Adam moments, the step counter, the agent's noise counter, the reward-label state, or the three
  * pipeline slots (their trunk features and batch bindings) is written.  They use the scratch feature slot of
  * serl_agent_sample_actions, the activations, the gradient scratch and an info accumulator of their own; the next update
  * starts with serl_agent_begin_update as always.  They share the trunk workspace with serl_agent_encode_slot: order them
- * behind a trunk pass in flight on another stream, as for serl_agent_sample_actions.  No Dropout (train=False) in the first three.
+ * behind a trunk pass in flight on another stream, as for serl_agent_sample_actions.  No Dropout (train=False) in all but the last.
  * Refused with SERL_ERR_INVALID, the message naming the argument and the value: n outside [1, cfg.batch]; dev_logp_out without
  * dev_actions; NULL dev_frames on an agent with cameras (a state-only agent, n_cam == 0, takes NULL). */
 /* forward_critic(obs, actions, train=False) (sac.py:33-55); target != 0: with target_params (sac.py:57-69).
@@ -644,6 +644,25 @@ int serl_agent_eval_q_actions(serl_agent* a, const uint8_t* dev_frames, const fl
 int serl_agent_eval_policy(serl_agent* a, const uint8_t* dev_frames, const float* dev_state, const float* dev_actions,
                            int n, float* dev_mean_out, float* dev_std_out, float* dev_mode_out, float* dev_logp_out,
                            void* stream);
+/* n_cand samples of forward_policy(obs, train=False) per observation (SACAgent.sample_actions, sac.py:301-320, with the sample
+ * shape that multiple_action_q_function, actor_critic_nets.py:33-46, scores): eps f32[n_cand][n][A] device, laid out as distrax
+ * draws jax.random.normal(seed, (n_cand, n, A)); actions_out f32[n][n_cand][A] device, entry [b][j] = tanh(loc + scale * eps[j][b])
+ * (no tanh without the squash) -- with n_cand == 1 the bits of serl_agent_sample_actions.  logp_out f32[n][n_cand] device or
+ * NULL: the log-density of every sample, formed from the pre-squash value as distrax's sample_and_log_prob does, finite where
+ * tanh rounds to +-1.  One encoder and one policy pass over the n observations.  Refused with SERL_ERR_INVALID: n_cand < 1,
+ * n * n_cand outside [1, cfg.batch], NULL dev_eps or dev_actions_out (and what serl_agent_eval_policy refuses). */
+int serl_agent_sample_candidates(serl_agent* a, const uint8_t* dev_frames, const float* dev_state, int n, int n_cand,
+                                 const float* dev_eps, float* dev_actions_out, float* dev_logp_out, void* stream);
+/* Acting on the critic: the candidates above, the ONLINE critic's Q of each (serl_agent_eval_q_actions on them), and per
+ * observation the candidate whose score over the ensemble -- reduce = SERL_RANK_MIN: the members' minimum, the reading SAC's
+ * target uses; SERL_RANK_MEAN: their mean -- is largest, ties to the lowest candidate.  The trunk / SmallEncoder and the
+ * EncodingWrapper run once for both networks.  action_out f32[n][A]: a copy of the chosen candidate; optional outputs (NULL:
+ * not wanted): index_out i32[n], score_out f32[n], actions_out f32[n][n_cand][A], q_out f32[ensemble][n][n_cand].  No buffer
+ * scales with n_cand.  Refused as serl_agent_sample_candidates, and: NULL dev_action_out, an unknown reduce. */
+enum { SERL_RANK_MIN = 0, SERL_RANK_MEAN = 1 };
+int serl_agent_sample_best(serl_agent* a, const uint8_t* dev_frames, const float* dev_state, int n, int n_cand, const float* dev_eps,
+                           int reduce, float* dev_action_out, int* dev_index_out, float* dev_score_out, float* dev_actions_out,
+                           float* dev_q_out, void* stream);
 /* loss_fns(batch) evaluated, not applied (sac.py:134-241): the critic, actor and temperature phases of
  * serl_agent_update on `batch` with `noise`, WITHOUT serl_agent_apply.  host_out gets the seven loss scalars and the
  * three learning rates an update at the current step would report (synchronises `stream`).  The scalars are bit for bit those

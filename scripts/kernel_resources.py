@@ -63,6 +63,11 @@ CHAIN = [
     ("policy_stats_fixed_kernel<true>", 80),
     # ... (serl_agent_eval_q_actions): the critic's first layer fanned out over the candidates, at the default width; 16 KB of LDS
     ("critic_fanout_kernel<4>", 80),
+    # ... (serl_agent_sample_candidates / serl_agent_sample_best): N policy samples per row, and the best of them under the ensemble
+    ("policy_fanout_kernel<0>", 80),
+    ("policy_fanout_kernel<1>", 80),
+    ("policy_fanout_kernel<3>", 80),
+    ("q_rank_kernel", 80),
 ]
 
 

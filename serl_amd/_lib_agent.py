@@ -141,6 +141,9 @@ SIGNATURES = {
     "serl_agent_eval_q": [vp, vp, vp, vp, i32, i32, vp, vp],
     "serl_agent_eval_q_actions": [vp, vp, vp, vp, i32, i32, i32, vp, vp],
     "serl_agent_eval_policy": [vp, vp, vp, vp, i32, vp, vp, vp, vp, vp],
+    # acting on the critic: N policy samples per observation, and the best of them under the ensemble
+    "serl_agent_sample_candidates": [vp, vp, vp, i32, i32, vp, vp, vp, vp],
+    "serl_agent_sample_best": [vp, vp, vp, i32, i32, vp, i32, vp, vp, vp, vp, vp, vp],
     "serl_agent_eval_losses": [vp, P(SerlBatch), P(SerlNoise), P(SerlInfo), vp],
     "serl_agent_trunk_forward": [vp, vp, i32, vp, vp],
     "serl_agent_debug_get": [vp, C.c_char_p, vp, i64],

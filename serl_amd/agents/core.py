@@ -16,6 +16,7 @@ from .._lib_agent import (APPLY_ACTOR_TEMP, APPLY_CRITIC, MLP_SITES, NET_BITS, T
 from ..utils.init import FIXED_STD, NetSpec
 
 TX_NAMES = ("actor", "critic", "temperature")
+RANKS = {"min": 0, "mean": 1}   # SERL_RANK_*: how serl_agent_sample_best reads the ensemble
 
 
 class AgentCore(Handle):
@@ -413,6 +414,43 @@ class AgentCore(Handle):
                                                  out["mean"].data_ptr(), out["std"].data_ptr(), out["mode"].data_ptr(),
                                                  self._ptr(out.get("log_prob")), self._stream()))
         return out
+
+    def sample_candidates(self, frames_u8, state, eps, log_prob=True) -> Dict[str, torch.Tensor]:
+        """N samples of forward_policy(obs, train=False) per observation from eps f32[N, n, A] (jax.random.normal(seed, (N, n, A))
+        as it lies) -> {"actions": f32[n, N, A], "log_prob": f32[n, N]} (device): serl_agent_sample_candidates, one encoder and one
+        policy pass; n * N <= cfg.batch.  log_prob is the density of each sample from its pre-squash value (finite at tanh = +-1)."""
+        n, (N, _, A) = state.shape[0], self._eps_shape(eps, state)
+        out = {"actions": torch.empty((n, N, A), dtype=torch.float32, device=self.device)}
+        if log_prob:
+            out["log_prob"] = torch.empty((n, N), dtype=torch.float32, device=self.device)
+        keep = [None if frames_u8 is None else frames_u8.contiguous(), state.contiguous(), eps.contiguous()]
+        _lib.check(self.L.serl_agent_sample_candidates(self._h, self._ptr(keep[0]), keep[1].data_ptr(), n, N, keep[2].data_ptr(),
+                                                       out["actions"].data_ptr(), self._ptr(out.get("log_prob")), self._stream()))
+        return out
+
+    def sample_best(self, frames_u8, state, eps, rank="min", info=True) -> Dict[str, torch.Tensor]:
+        """The candidates of sample_candidates, the online critic's Q of each and, per observation, the candidate whose score over
+        the ensemble (rank "min": the members' minimum; "mean") is largest -> {"action": f32[n, A]} and, with info, "index" i32[n],
+        "score" f32[n], "actions" f32[n, N, A], "q" f32[ensemble, n, N] (device): serl_agent_sample_best, ONE encoder pass for the
+        policy and the critic; n * N <= cfg.batch."""
+        if rank not in RANKS:
+            raise ValueError(f"rank must be one of {sorted(RANKS)} (got {rank!r})")
+        n, (N, _, A) = state.shape[0], self._eps_shape(eps, state)
+        f32 = dict(dtype=torch.float32, device=self.device)
+        out = {"action": torch.empty((n, A), **f32)}
+        if info:
+            out.update(index=torch.empty((n,), dtype=torch.int32, device=self.device), score=torch.empty((n,), **f32),
+                       actions=torch.empty((n, N, A), **f32), q=torch.empty((self.cfg.ensemble, n, N), **f32))
+        keep = [None if frames_u8 is None else frames_u8.contiguous(), state.contiguous(), eps.contiguous()]
+        _lib.check(self.L.serl_agent_sample_best(self._h, self._ptr(keep[0]), keep[1].data_ptr(), n, N, keep[2].data_ptr(), RANKS[rank],
+                                                 out["action"].data_ptr(), *(self._ptr(out.get(k)) for k in ("index", "score", "actions", "q")),
+                                                 self._stream()))
+        return out
+
+    def _eps_shape(self, eps, state):
+        if eps.dim() != 3 or eps.shape[1] != state.shape[0] or eps.shape[2] != self.cfg.act_dim:
+            raise ValueError(f"eps {tuple(eps.shape)}: [N, n, A] with n = {state.shape[0]} observations and A = {self.cfg.act_dim}")
+        return tuple(eps.shape)
 
     def eval_losses(self, batch, noise=None) -> dict:
         """loss_fns(batch) evaluated, not applied: the scalars and learning rates update(batch, noise=noise) would report."""

@@ -24,7 +24,7 @@ from .. import jaxrng as J
 from .._handle import LazyInfo
 from ..call_noise import CallNoise
 from .batch import DeviceBatch
-from .core import APPLY_ACTOR_TEMP, APPLY_CRITIC, TX_NAMES, AgentCore
+from .core import APPLY_ACTOR_TEMP, APPLY_CRITIC, RANKS, TX_NAMES, AgentCore
 from .flax_tree import export_tree
 
 
@@ -637,9 +637,17 @@ class DrQAgent:
                               lambda noise: self.core.update(db, tuple(networks_to_update), noise), want_critic=crit, want_actor=act)
 
     # ------------------------------------------------------------------ acting
-    def sample_actions(self, observations, *, seed=None, argmax: bool = False, **kwargs):
+    def sample_actions(self, observations, *, seed=None, argmax: bool = False, num_candidates=None, rank: str = "min",
+                       return_info: bool = False, **kwargs):
         """sac.py:301-320: policy forward with train=False; sample (external seed) or mode.  Observations are (T, H, W, 3) frames
-        and a (T, S) state per sample (T = num_stack; the T axis of a single-frame agent may be missing), batched or not."""
+        and a (T, S) state per sample (T = num_stack; the T axis of a single-frame agent may be missing), batched or not.
+        num_candidates=N: act on the critic -- N samples per observation from `seed` (policy_samples' for that seed), ranked by
+        the online critic as multiple_action_q_function scores them (actor_critic_nets.py:33-46): the one whose `rank` over the
+        ensemble ("min", SAC's conservative reading, or "mean") is largest is returned, [n, A]; with return_info=True
+        (action, {"index": [n], "score": [n], "actions": [n, N, A], "q": [ensemble, n, N]}).  One encoder pass serves both
+        networks (serl_agent_sample_best); more than batch_size // N observations go in chunks.  N = 1 is the plain sample."""
+        if num_candidates is not None:
+            return self._sample_best(observations, seed, argmax, num_candidates, rank, return_info)
         if argmax:
             assert seed is None, "Cannot specify seed when sampling deterministically"
         c = self.core.cfg
@@ -723,6 +731,45 @@ class DrQAgent:
         out = {k: v.cpu().numpy() for k, v in out.items()}
         return out if batched else {k: v[0] for k, v in out.items()}
 
+    def _num_candidates(self, num):
+        N = int(num)
+        if not 1 <= N <= self.core.cfg.batch:
+            raise ValueError(f"{num} candidates per observation: one observation's candidates are rows of one call, 1 to batch_size = "
+                             f"{self.core.cfg.batch}")
+        return N
+
+    def _candidates_dev(self, call, f, s, eps):
+        """call(frames, state, eps) of AgentCore on chunks of batch_size // N observations, each with its slice of eps [N, n, A];
+        the parts joined along the observation axis (the second of "q", the first of everything else)"""
+        parts = [call(None if f is None else f[:, lo:hi], s[lo:hi], eps[:, lo:hi].contiguous())
+                 for lo, hi in self._chunks(s.shape[0], eps.shape[0])]
+        return {k: torch.cat([p[k] for p in parts], dim=1 if k == "q" else 0).cpu().numpy() for k in parts[0]}
+
+    def policy_samples(self, observations, *, seed, num_samples) -> dict:
+        """forward_policy(observations, train=False).sample_and_log_prob(seed=seed, sample_shape=num_samples), the candidate axis
+        behind the observations' -> {"actions": [n, N, A], "log_prob": [n, N]} (without the leading axis for a single
+        observation).  The noise is jax.random.normal(seed, (N, n, A)) as distrax draws it; the log-density is formed from the
+        pre-squash sample, so it is finite where tanh rounds to +-1."""
+        N = self._num_candidates(num_samples)
+        self._sync_side_stream()
+        f, s, n, batched = self._eval_obs(observations)
+        out = self._candidates_dev(self.core.sample_candidates, f, s, self._action_noise(seed, n, N))
+        return out if batched else {k: v[0] for k, v in out.items()}
+
+    def _sample_best(self, observations, seed, argmax, num_candidates, rank, return_info):
+        if argmax:
+            raise ValueError("argmax=True draws nothing: it cannot be combined with num_candidates")
+        if rank not in RANKS:
+            raise ValueError(f"rank must be one of {sorted(RANKS)} (got {rank!r})")
+        N = self._num_candidates(num_candidates)
+        self._sync_side_stream()
+        f, s, n, batched = self._eval_obs(observations)
+        out = self._candidates_dev(lambda *a: self.core.sample_best(*a, rank=rank, info=return_info), f, s, self._action_noise(seed, n, N))
+        if not batched:
+            out = {k: v[:, 0] if k == "q" else v[0] for k, v in out.items()}
+        action = out.pop("action")
+        return (action, out) if return_info else action
+
     def evaluate_batch(self, batch, *, side: str = "observations") -> dict:
         """The four questions on a replay batch (what `update` takes: a host dict, a DeviceBatch or a LazyBatch of the store --
         gathered in HBM, never through the host) -> {"q", "q_target": [ensemble, B], "mean", "std", "mode": [B, A], "log_prob":
@@ -767,13 +814,15 @@ class DrQAgent:
         out.update({f"{n}_lr": r[f"{n}_lr"] for n in TX_NAMES})
         return out
 
-    def _action_noise(self, seed, n):
-        """dist.sample(seed=seed) of sac.py:316-320: distrax draws jax.random.normal(seed, (1,) + batch + (A,))."""
+    def _action_noise(self, seed, n, num=None):
+        """dist.sample(seed=seed) of sac.py:316-320: distrax draws jax.random.normal(seed, (1,) + batch + (A,)) -> [n, A]; with
+        num = N the draws of a sample shape, jax.random.normal(seed, (N,) + batch + (A,)) -> [N, n, A] (N = 1: the same numbers)."""
         assert seed is not None, "Must specify rng when sampling"
         c = self.core.cfg
-        eps = torch.empty((n, c.act_dim), dtype=torch.float32, device=self.core.device)
+        shape = (n, c.act_dim) if num is None else (num, n, c.act_dim)
+        eps = torch.empty(shape, dtype=torch.float32, device=self.core.device)
         if self.rng_impl == "threefry" and J.is_key(seed):
-            J.fill(c.device, [J.job(J.NORMAL, seed, n * c.act_dim, eps.data_ptr())], self.core._stream())
+            J.fill(c.device, [J.job(J.NORMAL, seed, eps.numel(), eps.data_ptr())], self.core._stream())
             return eps
         g = np.random.Generator(np.random.PCG64(np.random.SeedSequence(np.asarray(seed).reshape(-1).tolist())))
-        return torch.from_numpy(g.standard_normal((n, c.act_dim)).astype(np.float32)).to(self.core.device)
+        return torch.from_numpy(g.standard_normal(shape).astype(np.float32)).to(self.core.device)

@@ -117,8 +117,11 @@ class SACAgent(DrQAgent):
         n = st.shape[0] if batched else 1
         return None, torch.from_numpy(st.reshape(n, -1)).to(self.core.device), n, batched
 
-    def sample_actions(self, observations, *, seed=None, argmax: bool = False, **kwargs):
-        """sac.py:301-320."""
+    def sample_actions(self, observations, *, seed=None, argmax: bool = False, num_candidates=None, rank: str = "min",
+                       return_info: bool = False, **kwargs):
+        """sac.py:301-320.  num_candidates / rank / return_info: DrQAgent.sample_actions' (the best of N samples under the critic)."""
+        if num_candidates is not None:
+            return self._sample_best(observations, seed, argmax, num_candidates, rank, return_info)
         if argmax:
             assert seed is None, "Cannot specify seed when sampling deterministically"
         c = self.core.cfg

@@ -1977,22 +1977,11 @@ int serl_agent_eval_q(serl_agent* a, const uint8_t* dev_frames, const float* dev
   return SERL_OK;
 }
 
-int serl_agent_eval_q_actions(serl_agent* a, const uint8_t* dev_frames, const float* dev_state, const float* dev_actions, int n,
-                              int n_actions, int target, float* dev_q_out, void* stream) {
-  SERL_REQUIRE(a, "NULL agent");
+// The critic with parameters P on n_actions candidate actions for each of the n observations whose encodings lie in columns
+// [0, E) of cb.x: Q into cb.q, [ensemble][n][n_actions].  Inside an EvalScope.
+static int critic_on_candidates(serl_agent* a, const float* P, CritBuf& cb, const float* dev_actions, int n, int n_actions, hipStream_t st) {
   const serl_agent_cfg& c = a->cfg;
-  SERL_REQUIRE(n_actions >= 1, "n_actions %d is not positive", n_actions);
-  SERL_REQUIRE(n >= 1 && (long)n * n_actions <= c.batch, "n * n_actions = %d * %d not in [1,%d]", n, n_actions, c.batch);
-  RC(eval_check(a, dev_frames, dev_state, n));
-  SERL_REQUIRE(dev_actions && dev_q_out, "dev_actions or dev_q_out is NULL");
-  hipStream_t st = (hipStream_t)stream;
-  SERL_HIP(hipSetDevice(c.device));
-  EvalScope scope(a);
   const Offs& o = a->o;
-  const float* P = target ? a->theta_t : a->theta;
-  CritBuf& cb = target ? a->critT : a->crit;
-  // one encoder pass over the n observations, no actions rider: columns [0, E) of cb.x
-  RC(eval_encode(a, dev_frames, dev_state, n, P, target ? &a->encT : &a->encO, nullptr, nullptr, st));
   // Layer 1.  The observation's share of the Dense, enc . W[0:E], on n rows per member: the layer's forward GEMM cut at K = E (the
   // kernel leaf as it lies, same leading dimension).  Then the fan-out rows: n * n_actions per member into the layer's buffer,
   // ordered (member, observation, candidate) -- the block per member that the layers behind read as rows = n * n_actions.
@@ -2015,8 +2004,97 @@ int serl_agent_eval_q_actions(serl_agent* a, const uint8_t* dev_frames, const fl
   RC(gemm_f32(g, st));
   RC(critic_fanout_fwd(f, L.N, st));
   const CritJob cj{P, &cb, {}};   // train=False: no Dropout
-  RC(critic_fwd_multi(a, &cj, 1, rows, st, 1));   // layers 2 .. and the Q head on n * n_actions rows per member (none: one layer)
-  SERL_HIP(hipMemcpyAsync(dev_q_out, cb.q, sizeof(float) * c.ensemble * rows, hipMemcpyDeviceToDevice, st));   // [ensemble][n][n_actions]
+  return critic_fwd_multi(a, &cj, 1, rows, st, 1);   // layers 2 .. and the Q head on n * n_actions rows per member (none: one layer)
+}
+
+int serl_agent_eval_q_actions(serl_agent* a, const uint8_t* dev_frames, const float* dev_state, const float* dev_actions, int n,
+                              int n_actions, int target, float* dev_q_out, void* stream) {
+  SERL_REQUIRE(a, "NULL agent");
+  const serl_agent_cfg& c = a->cfg;
+  SERL_REQUIRE(n_actions >= 1, "n_actions %d is not positive", n_actions);
+  SERL_REQUIRE(n >= 1 && (long)n * n_actions <= c.batch, "n * n_actions = %d * %d not in [1,%d]", n, n_actions, c.batch);
+  RC(eval_check(a, dev_frames, dev_state, n));
+  SERL_REQUIRE(dev_actions && dev_q_out, "dev_actions or dev_q_out is NULL");
+  hipStream_t st = (hipStream_t)stream;
+  SERL_HIP(hipSetDevice(c.device));
+  EvalScope scope(a);
+  const float* P = target ? a->theta_t : a->theta;
+  CritBuf& cb = target ? a->critT : a->crit;
+  // one encoder pass over the n observations, no actions rider: columns [0, E) of cb.x
+  RC(eval_encode(a, dev_frames, dev_state, n, P, target ? &a->encT : &a->encO, nullptr, nullptr, st));
+  RC(critic_on_candidates(a, P, cb, dev_actions, n, n_actions, st));
+  SERL_HIP(hipMemcpyAsync(dev_q_out, cb.q, sizeof(float) * c.ensemble * n * n_actions, hipMemcpyDeviceToDevice, st));   // [ensemble][n][n_actions]
+  return SERL_OK;
+}
+
+// The policy with the online parameters on n encodings `enc` (row stride ld): the MLP as policy_fwd_multi runs it, the head as a
+// plain K-split GEMM (serl_agent_eval_policy's, same slabs), and n_cand samples per row from them.  Inside an EvalScope.
+static int policy_candidates(serl_agent* a, const float* enc, long ld, int n, int n_cand, const float* dev_eps, float* actions,
+                             float* logp, hipStream_t st) {
+  const serl_agent_cfg& c = a->cfg;
+  const Offs& o = a->o;
+  const float* P = a->theta;
+  PolBuf& pb = a->pol;
+  PolJob pj{};   // train=False: no Dropout site
+  pj.P = P; pj.pb = &pb; pj.enc = enc; pj.ld_enc = ld;
+  RC(policy_mlp_multi(a, &pj, 1, n, st));
+  const int Hd = o.a[o.na - 1].N;
+  const GemmDesc g = gemm_fwd(pb.m.l[o.na - 1].h, Hd, 0, P + o.a_Wm, head_stride(a), a->slabs_lane[0], a->head_groups, n, c.act_dim,
+                              Hd, 4);
+  SERL_REQUIRE((long)a->head_groups * 4 * n * c.act_dim <= a->slabs_cap, "policy head exceeds the slab scratch");
+  RC(gemm_f32_multi(&g, 1, st));
+  PolicyFanoutArgs v{};
+  v.slabs = a->slabs_lane[0]; v.S = 4; v.bias_mean = P + o.a_bm; v.bias_ls = head_bias_ls(a, P);
+  v.eps = dev_eps; v.actions = actions; v.logp = logp;
+  v.rows = n; v.N = n_cand; v.A = c.act_dim; v.std_min = c.std_min; v.std_max = c.std_max; v.mode = a->pol_mode;
+  return policy_fanout(v, st);
+}
+
+// what the two candidate entries refuse alike
+static int candidates_check(serl_agent* a, const uint8_t* dev_frames, const float* dev_state, int n, int n_cand, const float* dev_eps) {
+  SERL_REQUIRE(a, "NULL agent");
+  SERL_REQUIRE(n_cand >= 1, "n_cand %d is not positive", n_cand);
+  SERL_REQUIRE(n >= 1 && (long)n * n_cand <= a->cfg.batch, "n * n_cand = %d * %d not in [1,%d]", n, n_cand, a->cfg.batch);
+  RC(eval_check(a, dev_frames, dev_state, n));
+  SERL_REQUIRE(dev_eps, "dev_eps is NULL");
+  return SERL_OK;
+}
+
+int serl_agent_sample_candidates(serl_agent* a, const uint8_t* dev_frames, const float* dev_state, int n, int n_cand,
+                                 const float* dev_eps, float* dev_actions_out, float* dev_logp_out, void* stream) {
+  RC(candidates_check(a, dev_frames, dev_state, n, n_cand, dev_eps));
+  SERL_REQUIRE(dev_actions_out, "dev_actions_out is NULL");
+  hipStream_t st = (hipStream_t)stream;
+  SERL_HIP(hipSetDevice(a->cfg.device));
+  EvalScope scope(a);
+  RC(eval_encode(a, dev_frames, dev_state, n, a->theta, &a->encP, nullptr, nullptr, st));
+  return policy_candidates(a, a->encP.enc, a->encP.ld, n, n_cand, dev_eps, dev_actions_out, dev_logp_out, st);
+}
+
+int serl_agent_sample_best(serl_agent* a, const uint8_t* dev_frames, const float* dev_state, int n, int n_cand, const float* dev_eps,
+                           int reduce, float* dev_action_out, int* dev_index_out, float* dev_score_out, float* dev_actions_out,
+                           float* dev_q_out, void* stream) {
+  RC(candidates_check(a, dev_frames, dev_state, n, n_cand, dev_eps));
+  SERL_REQUIRE(dev_action_out, "dev_action_out is NULL");
+  SERL_REQUIRE(reduce == SERL_RANK_MIN || reduce == SERL_RANK_MEAN, "reduce %d is neither SERL_RANK_MIN nor SERL_RANK_MEAN", reduce);
+  const serl_agent_cfg& c = a->cfg;
+  hipStream_t st = (hipStream_t)stream;
+  SERL_HIP(hipSetDevice(c.device));
+  EvalScope scope(a);
+  // ONE trunk / SmallEncoder pass and ONE EncodingWrapper pass serve both networks: the actor and the critic share the encoder's
+  // leaves (one enc0 in theta), and without Dropout their encodings of an observation are the same numbers.  They go where the
+  // critic reads them, columns [0, E) of crit.x; the policy's first layer reads the same columns at that row stride.
+  RC(eval_encode(a, dev_frames, dev_state, n, a->theta, &a->encO, nullptr, nullptr, st));
+  // candidates and Q the caller did not ask for live in scratch that n * n_cand <= cfg.batch rows always fit: act_tmp, crit.q
+  float* cand = dev_actions_out ? dev_actions_out : a->act_tmp;
+  RC(policy_candidates(a, a->encO.enc, a->encO.ld, n, n_cand, dev_eps, cand, nullptr, st));
+  RC(critic_on_candidates(a, a->theta, a->crit, cand, n, n_cand, st));
+  QRankArgs r{};
+  r.q = a->crit.q; r.actions = cand; r.action_out = dev_action_out; r.index = dev_index_out; r.score = dev_score_out;
+  r.E = c.ensemble; r.n = n; r.N = n_cand; r.A = c.act_dim; r.mean = reduce == SERL_RANK_MEAN;
+  RC(q_rank(r, st));
+  if (dev_q_out)
+    SERL_HIP(hipMemcpyAsync(dev_q_out, a->crit.q, sizeof(float) * c.ensemble * n * n_cand, hipMemcpyDeviceToDevice, st));   // [ensemble][n][n_cand]
   return SERL_OK;
 }
 

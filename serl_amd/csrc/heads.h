@@ -134,6 +134,34 @@ struct PolicyStatsArgs {
   int mode;   // kPol*
 };
 int policy_stats(const PolicyStatsArgs& v, hipStream_t stream);
+// The sampling sibling of policy_stats: N samples of every row's distribution from the same slabs (sac.py:301-320 with a sample
+// shape).  mean and std as policy_stats forms them (same bits), then per candidate j
+//   u = mean + std * eps[j][row][:],   actions[row][j][:] = tanh(u) (u itself with kPolNoTanh),
+//   logp[row][j] = sum_k [-eps^2/2 - log std - log(2 pi)/2 - 2 (log 2 - u - softplus(-2u))]   (no last term with kPolNoTanh)
+// -- the density of the sample from u, what distrax's sample_and_log_prob returns: finite where tanh(u) rounds to +-1.
+// eps is jax.random.normal(seed, (N, rows, A)) as it lies, the candidate axis outermost; logp may be nullptr.
+struct PolicyFanoutArgs {
+  const float* slabs; int S;   // the layout of PolicyStatsArgs
+  const float *bias_mean, *bias_ls;
+  const float* eps;            // [N][rows][A]
+  float* actions;              // [rows][N][A]
+  float* logp;                 // [rows][N] or nullptr
+  int rows, N, A; float std_min, std_max;
+  int mode;   // kPol*
+};
+int policy_fanout(const PolicyFanoutArgs& v, hipStream_t stream);
+// The best of N candidates per observation under the critic ensemble (one wave per observation): score[b][j] = min over the
+// members of q[e][b][j] (mean != 0: their mean), members in ascending order; index[b] = the argmax over j, ties to the lowest
+// j; action_out[b][:] = actions[b][index[b]][:], a copy.  index and score may be nullptr.
+struct QRankArgs {
+  const float* q;         // [E][n][N]
+  const float* actions;   // [n][N][A]
+  float* action_out;      // [n][A]
+  int* index;             // [n]
+  float* score;           // [n]
+  int E, n, N, A, mean;   // A <= 64
+};
+int q_rank(const QRankArgs& v, hipStream_t stream);
 // proprio branch: y = tanh(LN(state W + b)) with W [S][64] (encoding.py:55-70), one wave per row
 struct ProprioArgs {
   const float* state; const float *W, *b, *gamma, *beta;

@@ -2099,6 +2099,133 @@ int policy_stats(const PolicyStatsArgs& v, hipStream_t stream) {
   return SERL_OK;
 }
 
+// =============================================================================================
+// N samples per row of the policy distribution (policy_fanout, heads.h; SACAgent.sample_actions, sac.py:301-320, with the
+// candidates that multiple_action_q_function, actor_critic_nets.py:33-46, scores)
+// =============================================================================================
+// Work split.  As in policy_stats_kernel one wave owns one row and lane k holds action column k (a lane past A sits on column 0
+// and contributes 0).  The wave sums the head GEMM's K-split slabs ONCE, in index order on top of the bias, forms mean and std by
+// the expressions of policy_dist_rows and policy_stats_kernel (same bits) and keeps mean, std and log std in three registers
+// while it loops over the row's N candidates -- the slab sum is the expensive operand here, as the base row is in
+// critic_fanout_kernel.  Nothing but eps is read inside the loop, and a candidate is one dependent load -> FMA -> tanh -> store
+// with a six-step butterfly behind it, so the loop is bound by latency, not by bytes: the wave takes kPfCj candidates per pass
+// (their loads are issued together, their butterflies interleave), and the eps of the NEXT pass are fetched before the current
+// one is computed, so that a pass's loads fly under the pass before.  eps is read where jax.random.normal(seed, (N, rows, A))
+// put it: candidate j of this row lies j * rows * A floats behind candidate 0, A contiguous floats per load.  A pass past the
+// last candidate repeats the last one's address and stores nothing.  A pass's log-densities leave in one store: after the
+// butterfly every lane holds every sum and lane c keeps candidate c's.  No LDS, no scratch.
+constexpr int kPfCj = 8;   // candidates per pass over the registers: 2 x 8 eps registers, 8 sums in flight
+template <int MODE>
+__global__ __launch_bounds__(256) void policy_fanout_kernel(PolicyFanoutArgs v) {
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (row >= v.rows) return;   // (uniform over the wave)
+  const int A = v.A, N = v.N;
+  const bool live = lane < A;
+  const int k = live ? lane : 0;
+  const long e = (long)row * A + k;
+  float mean = v.bias_mean[k], ls = v.bias_ls[k];
+  // K-split slabs of the head GEMM, [mean | log_std][split][rows][A], added in index order; a loop per group (scalar adds)
+  for (int sp = 0; sp < v.S; ++sp) mean += v.slabs[((long)sp * v.rows) * A + e];
+  if (policy_ls_group<MODE>())
+    for (int sp = 0; sp < v.S; ++sp) ls += v.slabs[(((long)v.S + sp) * v.rows) * A + e];
+  const float sd = policy_std<MODE>(ls, v.std_min, v.std_max);
+  const float lsd = logf(sd);
+  const long cstride = (long)v.rows * A;   // from a candidate's eps to the next one's
+  const float* ep = v.eps + e;
+  float* out = v.actions + (long)row * N * A + k;
+  float cur[kPfCj], nxt[kPfCj];
+#pragma unroll
+  for (int c = 0; c < kPfCj; ++c) { cur[c] = ep[(long)min(c, N - 1) * cstride]; nxt[c] = 0.f; }
+  for (int j0 = 0; j0 < N; j0 += kPfCj) {
+    if (j0 + kPfCj < N) {   // (uniform over the wave)
+#pragma unroll
+      for (int c = 0; c < kPfCj; ++c) nxt[c] = ep[(long)min(j0 + kPfCj + c, N - 1) * cstride];
+    }
+    float lp[kPfCj];
+#pragma unroll
+    for (int c = 0; c < kPfCj; ++c) {
+      const float z = cur[c];
+      const float u = mean + sd * z;
+      if (live && j0 + c < N) out[(long)(j0 + c) * A] = (MODE & kPolNoTanh) ? u : tanhf(u);
+      float t = -0.5f * z * z - lsd - 0.91893853320467274f;
+      if (!(MODE & kPolNoTanh)) t -= 2.f * (0.69314718055994531f - u - softplusf(-2.f * u));
+      lp[c] = live ? t : 0.f;
+    }
+    if (v.logp) {   // (uniform: a launch argument)
+      float mine = 0.f;
+#pragma unroll
+      for (int off = 1; off < 64; off <<= 1) {
+#pragma unroll
+        for (int c = 0; c < kPfCj; ++c) lp[c] += __shfl_xor(lp[c], off);
+      }
+#pragma unroll
+      for (int c = 0; c < kPfCj; ++c) mine = lane == c ? lp[c] : mine;
+      if (lane < kPfCj && j0 + lane < N) v.logp[(long)row * N + j0 + lane] = mine;
+    }
+#pragma unroll
+    for (int c = 0; c < kPfCj; ++c) cur[c] = nxt[c];
+  }
+}
+
+int policy_fanout(const PolicyFanoutArgs& v, hipStream_t stream) {
+  SERL_REQUIRE(v.rows >= 1 && v.N >= 1 && v.A >= 1 && v.A <= 64 && v.S >= 1,
+               "policy fan-out: %d rows x %d candidates x %d action columns (one lane per column: at most 64), %d slabs", v.rows, v.N, v.A, v.S);
+  SERL_REQUIRE(v.slabs && v.bias_mean && v.bias_ls && v.eps && v.actions, "policy fan-out: NULL tensor");
+#define SERL_X(M) SERL_LAUNCH_CHAIN(policy_fanout_kernel<M>, dim3(cdiv(v.rows, 4)), dim3(256), 0, stream, v)
+  SERL_POLICY_MODE_SWITCH(v.mode, SERL_X, SERL_REQUIRE(false, "bad policy distribution mode %d", v.mode))
+#undef SERL_X
+  SERL_HIP(hipGetLastError());
+  return SERL_OK;
+}
+
+// The best candidate of every observation under the ensemble (q_rank, heads.h).  One wave per observation b; lanes stride over
+// the candidates j (N may exceed 64).  A lane reduces q[0..E)[b][j] over the members in ascending order -- min, or the sum
+// divided by E -- so a score's bits depend on neither the grid nor the lane that formed it, and keeps the best (score, j) of its
+// own candidates: j ascends, and only a strictly greater score replaces, so ties stay with the lowest j.  The wave's maximum
+// is an xor butterfly on the pair with the same tie rule; a lane without a candidate holds (-inf, INT_MAX) and never wins
+// against lane 0, which always has one, so the index is a candidate's whatever the scores are (NaN included: comparisons with
+// it are false).  Then the copy of the chosen action, one lane per column.  No LDS, no scratch.
+__global__ __launch_bounds__(256) void q_rank_kernel(QRankArgs v) {
+  const int b = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (b >= v.n) return;   // (uniform over the wave)
+  const int N = v.N, E = v.E;
+  const long mstride = (long)v.n * N;
+  const float* q = v.q + (long)b * N;
+  float best = -INFINITY;
+  int bi = INT_MAX;
+  for (int j = lane; j < N; j += 64) {
+    float s = q[j];
+    for (int m = 1; m < E; ++m) {
+      const float x = q[m * mstride + j];
+      s = v.mean ? s + x : fminf(s, x);
+    }
+    if (v.mean) s /= (float)E;
+    if (bi == INT_MAX || s > best) { best = s; bi = j; }
+  }
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    const float ob = __shfl_xor(best, off);
+    const int oi = __shfl_xor(bi, off);
+    if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
+  }
+  const int pick = min(__builtin_amdgcn_readfirstlane(bi), N - 1);
+  best = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, best)));
+  if (lane < v.A) v.action_out[(long)b * v.A + lane] = v.actions[((long)b * N + pick) * v.A + lane];
+  if (lane == 0) {
+    if (v.index) v.index[b] = pick;
+    if (v.score) v.score[b] = best;
+  }
+}
+
+int q_rank(const QRankArgs& v, hipStream_t stream) {
+  SERL_REQUIRE(v.E >= 1 && v.n >= 1 && v.N >= 1 && v.A >= 1 && v.A <= 64,
+               "candidate ranking: %d members x %d observations x %d candidates x %d action columns (one lane per column: at most 64)", v.E, v.n, v.N, v.A);
+  SERL_REQUIRE(v.q && v.actions && v.action_out, "candidate ranking: NULL tensor");
+  SERL_LAUNCH_CHAIN(q_rank_kernel, dim3(cdiv(v.n, 4)), dim3(256), 0, stream, v);
+  SERL_HIP(hipGetLastError());
+  return SERL_OK;
+}
+
 
 // proprio branch (encoding.py:55-70): y = tanh(LayerNorm_1e-6(state W + b)), W [S][64]; one wave per row,
 // lane = output feature.  Replaces a GEMM + LN launch pair for this tiny layer.
