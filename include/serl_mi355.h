@@ -350,7 +350,18 @@ typedef struct serl_agent_cfg {
  *                  launch carried the proprio rows, and is one column-copy launch where the proprio rows were a launch of their
  *                  own.  n_cam == 0 with no_proprio 1 is SERL_ERR_INVALID (a state-only agent has no EncodingWrapper); a positive
  *                  dropout in either MLP beside no_proprio 1 is SERL_ERR_UNSUPPORTED.  Any other value is SERL_ERR_INVALID.  The
- *                  entry points from before serl_agent_opts leave it 0. */
+ *                  entry points from before serl_agent_opts leave it 0.
+ *   wide_widths    0: every MLP width ends at 1024; every check, message and launch is what it was.  1: every MLP width (dims[],
+ *                  cfg->hidden) is a multiple of 64 in [64, 4096], and with ragged_widths 1 any integer in [1, 4096] (stored
+ *                  64 * ceil(d / 64) wide, as above).  A layer stored wider than 1024 takes the place of its LayerNorm (or plain)
+ *                  launches one for one, forward and backward, with rows that one workgroup of four waves owns (csrc/ln_wide.h);
+ *                  layers up to 1024 launch what they always did, so an agent without such a layer is the agent of wide_widths 0,
+ *                  bit for bit.  Leaves, optimizer state, snapshots and checkpoints follow the widths like any others.  Refused:
+ *                  a positive dropout beside any width above 1024 (SERL_ERR_INVALID; the masks are laid out for the narrow rows);
+ *                  serl_agent_eval_q_actions and serl_agent_sample_best when the critic's FIRST layer is stored wider than 1024
+ *                  (SERL_ERR_UNSUPPORTED: the fan-out rows hold a whole row per wave) -- a policy wider than 1024 beside a
+ *                  narrower first critic layer is served.  Any other value is SERL_ERR_INVALID.  serl_agent_wide_widths reads it
+ *                  back.  The entry points from before serl_agent_opts leave it 0. */
 #define SERL_MAX_MLP_LAYERS 4
 typedef struct serl_mlp_opts {
   int act;
@@ -365,6 +376,7 @@ typedef struct serl_agent_opts {
   serl_mlp_opts critic, policy;
   const float* fixed_std;
   int ragged_widths;
+  int wide_widths;   /* (beside the other width switch; no_proprio stays the last field) */
   int no_proprio;
 } serl_agent_opts;
 int serl_agent_create_opts(const serl_agent_cfg* cfg, const serl_agent_opts* opts, serl_agent** out);
@@ -392,6 +404,7 @@ int serl_agent_create_fixed_std(const serl_agent_cfg* cfg, int std_param, int no
 /* The hidden widths of one MLP of any agent (networks/mlp.py:19-31; sac.py:516-524, drq.py:188-207): network 0 = critic,
  * 1 = policy.  Returns the layer count and fills dims[0 .. count); -1 on a NULL argument or another network code. */
 int serl_agent_mlp_dims(serl_agent* a, int network /* 0 critic, 1 policy */, int dims[SERL_MAX_MLP_LAYERS]);  /* -> layer count */
+int serl_agent_wide_widths(serl_agent* a);  /* serl_agent_opts.wide_widths of any agent: 1 or 0; -1 on a NULL agent */
 /* Whether the layers of one MLP of any agent have their LayerNorm (networks/mlp.py:29-30): network 0 = critic, 1 = policy.
  * Returns 1 or 0; -1 on a NULL agent or another network code. */
 int serl_agent_mlp_layer_norm(serl_agent* a, int network /* 0 critic, 1 policy */);

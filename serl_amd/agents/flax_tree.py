@@ -150,6 +150,10 @@ def net_spec_of(core) -> NetSpec:
         kw["use_proprio"] = int(core.L.serl_agent_use_proprio(core._h)) != 0
     elif hasattr(core, "use_proprio"):
         kw["use_proprio"] = bool(core.use_proprio)
+    if getattr(core, "_h", None) is not None and hasattr(core, "L"):      # ... and whether its widths end at 4096
+        kw["wide"] = int(core.L.serl_agent_wide_widths(core._h)) == 1
+    elif hasattr(core, "wide"):
+        kw["wide"] = bool(core.wide)
     return NetSpec(hidden=int(getattr(core.cfg, "hidden", 256)), **kw)
 
 

@@ -1062,6 +1062,9 @@ int serl_agent_mlp_dims(serl_agent* a, int network, int dims[SERL_MAX_MLP_LAYERS
   return net.n_layers;
 }
 
+// serl_agent_opts.wide_widths as the agent was created with it
+int serl_agent_wide_widths(serl_agent* a) { return a ? a->opts.wide_widths : -1; }
+
 // Every entry point's agent (serl_mi355.h, NETWORK OPTIONS).  The two networks are built from separate kwargs (sac.py:516-524,
 // drq.py:188-207), so their options are independent: mlp.py:19-31 applies `activations` behind every layer and loops over
 // hidden_dims of any length, :27-28 puts Dropout in front of the LayerNorm, :29-30 makes the LayerNorm optional;
@@ -1104,15 +1107,25 @@ static int create_agent(const serl_agent_cfg* cfg, const serl_agent_opts* opts, 
   // one wave owns a LayerNorm row and a lane holds hidden / 64 of its columns, 16 at the most (heads.hip).  ragged_widths 1: any
   // width in [1, 1024], a layer off the grid being stored 64 ceil(d / 64) wide in zero padding
   const bool ragged = opts->ragged_widths == 1;
-  const auto width_ok = [&](int d) { return d <= 1024 && (ragged ? d >= 1 : d >= 64 && d % 64 == 0); };
-  const char* served = ragged ? "served with ragged_widths 1: 1 to %d layers, each in [1, 1024] wide"
-                              : "served: 1 to %d layers, each a multiple of 64 in [64, 1024] wide";
+  // wide_widths 1: up to 4096, where one workgroup of four waves owns a LayerNorm row (ln_wide.h); 0: every check and message below
+  // is what it was
+  SERL_REQUIRE(opts->wide_widths == 0 || opts->wide_widths == 1, "wide_widths %d is not 0 (widths up to 1024) or 1 (up to 4096)", opts->wide_widths);
+  const bool wide = opts->wide_widths == 1;
+  const auto width_ok = [&](int d) { return d <= (wide ? 4096 : 1024) && (ragged ? d >= 1 : d >= 64 && d % 64 == 0); };
+  const char* served = wide ? (ragged ? "served with wide_widths 1 and ragged_widths 1: 1 to %d layers, each in [1, 4096] wide"
+                                      : "served with wide_widths 1: 1 to %d layers, each a multiple of 64 in [64, 4096] wide")
+                            : (ragged ? "served with ragged_widths 1: 1 to %d layers, each in [1, 1024] wide"
+                                      : "served: 1 to %d layers, each a multiple of 64 in [64, 1024] wide");
   bool off_grid = false;
+  int widest = 0;
   if (critic.n_layers == 0 || policy.n_layers == 0) {
-    SERL_REQUIRE(width_ok(cfg->hidden), ragged ? "hidden must lie in [1, 1024] with ragged_widths 1 (got %d): the width of the critic's and the policy's two MLP layers"
-                                               : "hidden must be a multiple of 64 in [64, 1024] (got %d): the width of the critic's and the policy's two MLP layers",
-                 cfg->hidden);
+    const char* hidden_msg = wide ? (ragged ? "hidden must lie in [1, 4096] with wide_widths 1 and ragged_widths 1 (got %d): the width of the critic's and the policy's two MLP layers"
+                                            : "hidden must be a multiple of 64 in [64, 4096] with wide_widths 1 (got %d): the width of the critic's and the policy's two MLP layers")
+                                  : (ragged ? "hidden must lie in [1, 1024] with ragged_widths 1 (got %d): the width of the critic's and the policy's two MLP layers"
+                                            : "hidden must be a multiple of 64 in [64, 1024] (got %d): the width of the critic's and the policy's two MLP layers");
+    SERL_REQUIRE(width_ok(cfg->hidden), hidden_msg, cfg->hidden);
     off_grid = cfg->hidden % 64 != 0;
+    widest = cfg->hidden;
   }
   for (const serl_mlp_opts* net : {&critic, &policy}) {
     if (net->n_layers == 0) continue;   // two layers of cfg->hidden, checked above
@@ -1122,8 +1135,12 @@ static int create_agent(const serl_agent_cfg* cfg, const serl_agent_opts* opts, 
     for (int j = 0; j < net->n_layers; ++j) {
       SERL_REQUIRE(width_ok(net->dims[j]), (name + " MLP: layer %d has width %d (" + served + ")").c_str(), j + 1, net->dims[j], SERL_MAX_MLP_LAYERS);
       off_grid = off_grid || net->dims[j] % 64 != 0;
+      widest = std::max(widest, net->dims[j]);
     }
   }
+  // (the keep-masks and the Dropout rows are those of the one-wave rows; widest > 1024 implies wide here)
+  SERL_REQUIRE(widest <= 1024 || !(critic.dropout > 0.0 || policy.dropout > 0.0), "dropout %g / %g (critic / policy) beside an MLP width of %d "
+               "under wide_widths 1: Dropout is served at widths up to 1024", critic.dropout, policy.dropout, widest);
   // (the jax-keyed keep-masks are laid out for [rows][h] with h on the grid; off_grid implies ragged here)
   SERL_REQUIRE(!off_grid || !(critic.dropout > 0.0 || policy.dropout > 0.0), "dropout %g / %g (critic / policy) beside an MLP width off the 64 grid "
                "under ragged_widths 1: Dropout is served at widths that are multiples of 64", critic.dropout, policy.dropout);
@@ -2007,9 +2024,20 @@ static int critic_on_candidates(serl_agent* a, const float* P, CritBuf& cb, cons
   return critic_fwd_multi(a, &cj, 1, rows, st, 1);   // layers 2 .. and the Q head on n * n_actions rows per member (none: one layer)
 }
 
+// The fan-out rows hold a whole row of the critic's first layer per wave: a layer wider than 1024 (wide_widths) has none.  `what`:
+// the call as its caller knows it.
+static int fanout_width_check(const serl_agent* a, const char* what) {
+  const int w = a->o.c[0].N;
+  if (w <= 1024) return SERL_OK;
+  set_error("%s: the critic's first layer is %d wide under wide_widths 1; candidate actions are served up to a first critic width of 1024",
+            what, a->true_dims[0][0]);
+  return SERL_ERR_UNSUPPORTED;
+}
+
 int serl_agent_eval_q_actions(serl_agent* a, const uint8_t* dev_frames, const float* dev_state, const float* dev_actions, int n,
                               int n_actions, int target, float* dev_q_out, void* stream) {
   SERL_REQUIRE(a, "NULL agent");
+  RC(fanout_width_check(a, "Q of candidate actions (q_values with [n, N, A] actions)"));
   const serl_agent_cfg& c = a->cfg;
   SERL_REQUIRE(n_actions >= 1, "n_actions %d is not positive", n_actions);
   SERL_REQUIRE(n >= 1 && (long)n * n_actions <= c.batch, "n * n_actions = %d * %d not in [1,%d]", n, n_actions, c.batch);
@@ -2075,6 +2103,7 @@ int serl_agent_sample_best(serl_agent* a, const uint8_t* dev_frames, const float
                            int reduce, float* dev_action_out, int* dev_index_out, float* dev_score_out, float* dev_actions_out,
                            float* dev_q_out, void* stream) {
   RC(candidates_check(a, dev_frames, dev_state, n, n_cand, dev_eps));
+  RC(fanout_width_check(a, "the best of N policy samples (sample_actions with num_candidates > 1)"));
   SERL_REQUIRE(dev_action_out, "dev_action_out is NULL");
   SERL_REQUIRE(reduce == SERL_RANK_MIN || reduce == SERL_RANK_MEAN, "reduce %d is neither SERL_RANK_MIN nor SERL_RANK_MEAN", reduce);
   const serl_agent_cfg& c = a->cfg;

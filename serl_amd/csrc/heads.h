@@ -21,7 +21,8 @@ int reduce_slabs(const float* slabs, int S, long slab_stride, int groups, int ro
                  long bias_gstride, float* out, long ld_out, long out_gstride, bool accumulate,
                  hipStream_t stream, float scale = 1.0f);
 
-// D: the row width of every instance, a multiple of 64 in [64, 1024] (one wave per row, D / 64 columns per lane)
+// D: the row width of every instance, a multiple of 64 in [64, 4096] (up to 1024 one wave per row, D / 64 columns per lane; above,
+// one workgroup of four waves per row, ln_wide.h: every form below except Dropout, in the same launch count)
 // RAGGED rows (an instance's d != 0; all instances of a launch or none): the row's true width is d < D and columns [d, D) are zero
 // padding -- of the bias, scale, shift and of the kernel's columns, hence of the slabs.  The statistics divide by d; everything else
 // is the on-grid row, which leaves y == 0 in the pads (gamma == beta == 0 and act(0) == 0).  The backward divides by d and writes
@@ -68,7 +69,7 @@ struct LnBwdArgs {
   int act;            // kAct* of the forward row (per instance, uniform over a wave)
   int d;              // as LnFwdArgs::d: 0, or the true width of a zero-padded row (in the hole behind act)
   const float* beta;  // kActSwish only: the forward's beta (addressed like gamma), to recompute pre = gamma*xhat + beta
-  int D;          // the row width, a multiple of 64 in [64, 1024]
+  int D;          // the row width, a multiple of 64 in [64, 4096]
   int dq_inline;  // rank-1 mode: dq[row] = 2 (q - y) inv_norm computed from the LossArgs of the launch
   LnDrop drop;    // the forward row's Dropout, stated again: dx = keep-decision ? dx / keep : 0 (zero-initialised: none)
 };

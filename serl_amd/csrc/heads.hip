@@ -1094,8 +1094,11 @@ int label_rows(const LnFwdArgs& a, float* label, float* mean, int* ctr, hipStrea
 
 // The widths the LayerNorm rows serve: one wave per row, D / 64 columns per lane, at most 16.  The launch of a width: K64 at 64
 // and K256 at 256 (the encoder's proprio and bottleneck LayerNorms, and the MLPs at the default width), the strided K<D / 64, false>
-// at every other.
-#define SERL_LN_WIDTH_OK(D) ((D) >= 64 && (D) <= 1024 && (D) % 64 == 0)
+// at every other.  Above 1024 one workgroup of four waves owns a row (ln_wide.h, included below): ln_fwd_multi and ln_bwd_multi hand
+// such a launch over, one for one.
+#define SERL_LN_WIDTH_OK(D) ((D) >= 64 && (D) <= 4096 && (D) % 64 == 0)
+int ln_wide_fwd(const Multi<LnFwdArgs>& mv, int n, int rows, int D, bool plain, hipStream_t stream);
+int ln_wide_bwd(const Multi<LnBwdArgs>& mv, int n, int rows, int D, bool plain, const LossArgs& loss, hipStream_t stream);
 // a launch's Dropout description: none, or a keep probability in (0, 1] with the mask tensor / the window of `rows` rows inside
 // the array the key draws
 static bool ln_drop_ok(const LnDrop& d, long rows) {
@@ -1119,7 +1122,7 @@ static bool ln_drop_ok(const LnDrop& d, long rows) {
   }
 
 int ln_fwd_multi(const LnFwdArgs* as, int n, int D, hipStream_t stream) {
-  SERL_REQUIRE(SERL_LN_WIDTH_OK(D), "LayerNorm width %d unsupported (a multiple of 64 in [64, 1024])", D);
+  SERL_REQUIRE(SERL_LN_WIDTH_OK(D), "LayerNorm width %d unsupported (a multiple of 64 in [64, 4096])", D);
   SERL_REQUIRE(n >= 1 && n <= kMaxMulti, "bad instance count %d", n);
   Multi<LnFwdArgs> mv{};
   int rows = 0;
@@ -1137,6 +1140,10 @@ int ln_fwd_multi(const LnFwdArgs* as, int n, int D, hipStream_t stream) {
     SERL_REQUIRE((as[i].gamma == nullptr) == (as[0].gamma == nullptr) && (as[i].gamma == nullptr) == (as[i].beta == nullptr),
                  "LayerNorm row: instance %d %s a LayerNorm and instance 0 %s; plain and LayerNorm rows do not share a launch", i,
                  as[i].gamma ? "has" : "lacks", as[0].gamma ? "has" : "lacks");
+  }
+  if (D > 1024) {   // one workgroup per row (ln_wide.h)
+    SERL_REQUIRE(!drop, "LayerNorm row of width %d with Dropout: served up to 1024", D);
+    return ln_wide_fwd(mv, n, rows, D, !as[0].gamma, stream);
   }
   dim3 grid(cdiv(rows, 4), n);
   if (!as[0].gamma) {
@@ -1252,7 +1259,7 @@ __global__ __launch_bounds__(256) void critic_fanout_kernel(FanoutArgs f) {
 
 int critic_fanout_fwd(const FanoutArgs& f, int D, hipStream_t stream) {
   const LnFwdArgs& a = f.l;
-  SERL_REQUIRE(SERL_LN_WIDTH_OK(D), "fanned-out critic layer: width %d unsupported (a multiple of 64 in [64, 1024])", D);
+  SERL_REQUIRE(SERL_LN_WIDTH_OK(D) && D <= 1024, "fanned-out critic layer: width %d unsupported (a multiple of 64 in [64, 1024])", D);
   SERL_REQUIRE(f.A >= 1 && f.A <= 64, "fanned-out critic layer: %d action columns; a wave holds one candidate's actions, 1 to 64", f.A);
   SERL_REQUIRE(f.N >= 1 && a.rows_per_group >= 1 && a.rows >= a.rows_per_group && a.rows % a.rows_per_group == 0 && a.S >= 1,
                "fanned-out critic layer: bad shape (%d candidates, %d rows, %d per group, %d slabs)", f.N, a.rows, a.rows_per_group, a.S);
@@ -1287,6 +1294,11 @@ __device__ __forceinline__ float redq_target(const LossArgs& L, int b) {
 }
 
 // critic loss by ONE workgroup of 256 threads (deterministic reductions); the body of critic_loss_kernel
+// (The attribute: the wide rows' kernels, ln_wide.h, are built without packed fp32 instructions and can inline only a callee that
+// asks for no more than they have; inlined into any other kernel the body is built with that kernel's features, as it always was.)
+#if defined(__HIP_DEVICE_COMPILE__)
+__attribute__((target("no-packed-fp32-ops")))
+#endif
 __device__ void critic_loss_body(const LossArgs& L, float (*red)[256]) {
   float s_d2 = 0.f, s_q = 0.f, s_y = 0.f, s_dq = 0.f;
   float s_e[16];  // per-member sums of dQ (per_member: E <= 16)
@@ -1503,6 +1515,8 @@ __global__ __launch_bounds__(256) void ln_bwd_one_kernel(LnBwdArgs a) {
   ln_bwd_row<VPL, BLOCKED>(a, LossArgs{}, row, lane);   // (no dq_inline without a loss: ln_bwd_multi checks)
 }
 
+#include "ln_wide.h"
+
 int ln_bwd_multi(const LnBwdArgs* as, int n, const LossArgs& loss, hipStream_t stream) {
   SERL_REQUIRE(n >= 1 && n <= kMaxMulti, "bad instance count %d", n);
   Multi<LnBwdArgs> mv{};
@@ -1510,7 +1524,7 @@ int ln_bwd_multi(const LnBwdArgs* as, int n, const LossArgs& loss, hipStream_t s
   bool drop = false;
   const auto mixes = [](int D) { return D == 64 || D == 256; };
   for (int i = 0; i < n; ++i) {
-    SERL_REQUIRE(SERL_LN_WIDTH_OK(as[i].D), "LayerNorm width %d unsupported (a multiple of 64 in [64, 1024])", as[i].D);
+    SERL_REQUIRE(SERL_LN_WIDTH_OK(as[i].D), "LayerNorm width %d unsupported (a multiple of 64 in [64, 4096])", as[i].D);
     // (a ragged launch is one MLP layer: one storage width, one true width, no Dropout)
     SERL_REQUIRE(as[i].d >= 0 && as[i].d < as[i].D && as[i].d == as[0].d && (!as[i].d || (as[i].D == as[0].D && as[i].drop.mode == kLnDropNone)),
                  "LayerNorm backward: instance %d has the true width %d in rows of %d, instance 0 %d in rows of %d; or a ragged row with Dropout",
@@ -1531,6 +1545,10 @@ int ln_bwd_multi(const LnBwdArgs* as, int n, const LossArgs& loss, hipStream_t s
     // (64 and 256 may share a launch -- the encoder heads; any other width comes from one MLP layer and is alone)
     SERL_REQUIRE(as[i].D == as[0].D || (mixes(as[i].D) && mixes(as[0].D)),
                  "LayerNorm widths %d and %d in one launch: widths other than 64 and 256 do not mix", as[0].D, as[i].D);
+  }
+  if (as[0].D > 1024) {   // one workgroup per row (ln_wide.h); such a width comes from one MLP layer and is every instance's
+    SERL_REQUIRE(!drop, "LayerNorm backward of width %d with Dropout: served up to 1024", as[0].D);
+    return ln_wide_bwd(mv, n, rows, as[0].D, !as[0].gamma, loss, stream);
   }
   const dim3 grid(cdiv(rows, 4) + (loss.on ? 1 : 0), n);
   if (!as[0].gamma) SERL_LN_LAUNCH(as[0].D, (plain_bwd_kernel<1, false>), (plain_bwd_kernel<4, true>), plain_bwd_kernel, grid, dim3(256), 0, stream, mv, loss)

@@ -57,6 +57,21 @@ HIDDEN_WIDTHS = tuple(range(64, 1025, 64))   # serl_agent_cfg.hidden: one wave p
 RAGGED_WIDTHS = range(1, 1025)   # ... with serl_agent_opts.ragged_widths: a layer off the grid is stored 64 ceil(d / 64) wide, zero padded
 
 
+WIDE_MAX = 4096   # ... with serl_agent_opts.wide_widths: above 1024 one workgroup of four waves owns a LayerNorm row (csrc/ln_wide.h)
+
+
+def _served_widths(mlp_ragged, mlp_wide):
+    """(the widths served under the two switches, how a message names them, how it names a width outside them); without mlp_wide
+    the sets and the words of always"""
+    if not mlp_wide:
+        return ((RAGGED_WIDTHS, "any integer in [1, 1024] under mlp_ragged=True", "outside [1, 1024]") if mlp_ragged
+                else (HIDDEN_WIDTHS, "a multiple of 64 in [64, 1024]", "off the grid"))
+    if mlp_ragged:
+        return range(1, WIDE_MAX + 1), f"any integer in [1, {WIDE_MAX}] under mlp_ragged=True and mlp_wide=True", f"outside [1, {WIDE_MAX}]"
+    return (range(64, WIDE_MAX + 1, 64), f"a multiple of 64 in [64, {WIDE_MAX}] under mlp_wide=True",
+            f"no multiple of 64 in [64, {WIDE_MAX}] under mlp_wide=True")
+
+
 _PLAIN_HINT = "; without LayerNorm with mlp_plain=True"
 
 
@@ -64,13 +79,14 @@ def _is_width(d):
     return not isinstance(d, bool) and isinstance(d, (int, np.integer))
 
 
-def mlp_hidden_width(critic_network_kwargs=None, policy_network_kwargs=None, mlp_plain=False, mlp_ragged=False) -> int:
+def mlp_hidden_width(critic_network_kwargs=None, policy_network_kwargs=None, mlp_plain=False, mlp_ragged=False, mlp_wide=False) -> int:
     """The one width h of the critic's and the policy's MLPs from the reference's `critic_network_kwargs` /
     `policy_network_kwargs` (hidden_dims=[h, h], LayerNorm, default [256, 256]).  Served: two layers of the same width, the same
     in both networks, a multiple of 64 from 64 to 1024; anything else raises NotImplementedError.  mlp_plain=True (the argument
     of the same name of create_states / create_drq): use_layer_norm is mlp_layer_norms' to read.  mlp_ragged=True (likewise): h is
-    any integer in [1, 1024]; 0, a negative, 1025 and a width that is no integer are refused."""
-    grid = "any integer in [1, 1024] under mlp_ragged=True" if mlp_ragged else "a multiple of 64 in [64, 1024]"
+    any integer in [1, 1024]; 0, a negative, 1025 and a width that is no integer are refused.  mlp_wide=True (likewise): the
+    widths end at 4096 instead of 1024."""
+    widths_served, grid, outside = _served_widths(mlp_ragged, mlp_wide)
     served = f"served: hidden_dims=[h, h] with LayerNorm, h {grid}, the same h for critic and policy"
     widths = []
     for which, nk in (("critic_network_kwargs", critic_network_kwargs or {}), ("policy_network_kwargs", policy_network_kwargs or {})):
@@ -84,8 +100,8 @@ def mlp_hidden_width(critic_network_kwargs=None, policy_network_kwargs=None, mlp
             raise NotImplementedError(f"{which}: hidden_dims={dims} has {len(dims)} layers ({served})")
         if dims[0] != dims[1]:
             raise NotImplementedError(f"{which}: hidden_dims={dims} has two different layer widths ({served})")
-        if dims[0] not in (RAGGED_WIDTHS if mlp_ragged else HIDDEN_WIDTHS):
-            raise NotImplementedError(f"{which}: width {dims[0]} is {'outside [1, 1024]' if mlp_ragged else 'off the grid'} ({served})")
+        if dims[0] not in widths_served:
+            raise NotImplementedError(f"{which}: width {dims[0]} is {outside} ({served})")
         widths.append(dims[0])
     if widths[0] != widths[1]:
         raise NotImplementedError(f"critic width {widths[0]} and policy width {widths[1]} differ ({served})")
@@ -95,14 +111,14 @@ def mlp_hidden_width(critic_network_kwargs=None, policy_network_kwargs=None, mlp
 MAX_MLP_LAYERS = 4   # SERL_MAX_MLP_LAYERS
 
 
-def mlp_layer_dims(critic_network_kwargs=None, policy_network_kwargs=None, mlp_plain=False, mlp_ragged=False):
+def mlp_layer_dims(critic_network_kwargs=None, policy_network_kwargs=None, mlp_plain=False, mlp_ragged=False, mlp_wide=False):
     """(critic, policy): the `hidden_dims` of the reference's MLP (networks/mlp.py:19-31 loops over a list of any length) from its
     two network kwargs, as tuples of ints: what create_states / create_drq read with mlp_shapes=True (without the switch
     mlp_hidden_width reads and refuses as it always did).  Default [256, 256].  Served: 1 to MAX_MLP_LAYERS layers per network,
     every width a multiple of 64 in [64, 1024], the two lists independent, LayerNorm on; anything else raises NotImplementedError
     from the arguments alone.  mlp_plain=True: use_layer_norm is mlp_layer_norms' to read.  mlp_ragged=True: every width is any
-    integer in [1, 1024]."""
-    grid = "any integer in [1, 1024] under mlp_ragged=True" if mlp_ragged else "a multiple of 64 in [64, 1024]"
+    integer in [1, 1024].  mlp_wide=True: the widths end at 4096 instead of 1024."""
+    widths_served, grid, outside = _served_widths(mlp_ragged, mlp_wide)
     served = (f"served: hidden_dims of 1 to {MAX_MLP_LAYERS} layers with LayerNorm, every width {grid}, "
               "the critic's list independent of the policy's")
     out = []
@@ -116,9 +132,8 @@ def mlp_layer_dims(critic_network_kwargs=None, policy_network_kwargs=None, mlp_p
         for d in dims:
             if not _is_width(d):
                 raise NotImplementedError(f"{which}: width {d!r} in hidden_dims={dims} is no integer ({served})")
-            if int(d) not in (RAGGED_WIDTHS if mlp_ragged else HIDDEN_WIDTHS):
-                raise NotImplementedError(f"{which}: width {int(d)} in hidden_dims={dims} is "
-                                          f"{'outside [1, 1024]' if mlp_ragged else 'off the grid'} ({served})")
+            if int(d) not in widths_served:
+                raise NotImplementedError(f"{which}: width {int(d)} in hidden_dims={dims} is {outside} ({served})")
         out.append(tuple(int(d) for d in dims))
     return tuple(out)
 
@@ -267,7 +282,9 @@ class NetSpec:
     64 grid and nowhere else, so that widths on the grid through mlp_ragged=True give the NetSpec, and the agent, of the call without.
     use_proprio: False is serl_agent_opts.no_proprio -- EncodingWrapper(use_proprio=False) (common/encoding.py:53-72), the image codes
     alone: no enc/proprio/* leaf, and the first kernels of both MLPs lose the 64 proprio rows.  network_spec sets it from
-    create_drq's use_proprio under image_only=True and nowhere else."""
+    create_drq's use_proprio under image_only=True and nowhere else.
+    wide: serl_agent_opts.wide_widths -- the widths end at 4096 instead of 1024; network_spec sets it where a width is above 1024 and
+    nowhere else, so that widths up to 1024 through mlp_wide=True give the NetSpec, and the agent, of the call without."""
     std_parameterization: str = "exp"
     tanh_squash_distribution: bool = True
     fixed_std: Optional[Tuple[float, ...]] = None
@@ -282,6 +299,7 @@ class NetSpec:
     policy_layer_norm: bool = True
     ragged: bool = False
     use_proprio: bool = True
+    wide: bool = False
 
     @property
     def dims(self):
@@ -305,6 +323,12 @@ class NetSpec:
                 f"use_proprio=False under image_only=True with mlp_dropout=True and a positive dropout_rate (critic {rates[0]!r} / policy "
                 f"{rates[1]!r}) (served: Dropout in the MLPs of agents with the proprio branch)")
         cd, pd = self.dims
+        widest = max(cd + pd)
+        if widest > 1024:
+            raise NotImplementedError(
+                f"mlp_wide=True with mlp_dropout=True and a positive dropout_rate (critic {rates[0]!r} / policy {rates[1]!r}) beside the "
+                f"width {widest}: critic hidden_dims={list(cd)}, policy hidden_dims={list(pd)} (served with Dropout: widths up to 1024; the "
+                "keep-masks are laid out for the rows one wave owns)")
         if self.ragged and self.off_grid:
             raise NotImplementedError(
                 f"mlp_ragged=True with mlp_dropout=True and a positive dropout_rate (critic {rates[0]!r} / policy {rates[1]!r}): critic "
@@ -367,20 +391,22 @@ class NetSpec:
             o.fixed_std = (ctypes.c_float * len(self.fixed_std))(*self.fixed_std)
         o.ragged_widths = 1 if self.ragged else 0
         o.no_proprio = 0 if self.use_proprio else 1
+        o.wide_widths = 1 if self.wide else 0
         return o
 
 
 def network_spec(critic_network_kwargs, policy_network_kwargs, policy_kwargs, act_dim, *, mlp_dropout=False, mlp_shapes=False,
-                 mlp_plain=False, policy_fixed=False, mlp_ragged=False, use_proprio=True) -> NetSpec:
+                 mlp_plain=False, policy_fixed=False, mlp_ragged=False, use_proprio=True, mlp_wide=False) -> NetSpec:
     """The checked NetSpec of create_states' / create_drq's three kwargs dicts under their five switches; every refusal is raised
     from the arguments alone, in the order of the lines below.  mlp_ragged=True: every width read below is any integer in
     [1, 1024] (mlp.py:19-31 takes any list); without it the 64 grid, as always.  use_proprio: create_drq's, already checked to be
-    a bool and read under image_only=True alone."""
+    a bool and read under image_only=True alone.  mlp_wide=True: every width read below ends at 4096 instead of 1024 (one
+    workgroup per LayerNorm row above 1024); a positive dropout_rate beside such a width is NetSpec.check's to refuse."""
     # policy_fixed=True: "fixed" / fixed_std are read (actor_critic_nets.py:189-192); else refused, as always
     std_param, squash, fixed = policy_mode_fixed(policy_kwargs, act_dim) if policy_fixed else (*policy_mode(policy_kwargs), None)
     # mlp_shapes=True: each network's own depth and per-layer widths (mlp.py:19-31); else the one width of [h, h], as always
-    dims = mlp_layer_dims(critic_network_kwargs, policy_network_kwargs, mlp_plain, mlp_ragged) if mlp_shapes else (None, None)
-    hidden = dims[0][0] if mlp_shapes else mlp_hidden_width(critic_network_kwargs, policy_network_kwargs, mlp_plain, mlp_ragged)
+    dims = mlp_layer_dims(critic_network_kwargs, policy_network_kwargs, mlp_plain, mlp_ragged, mlp_wide) if mlp_shapes else (None, None)
+    hidden = dims[0][0] if mlp_shapes else mlp_hidden_width(critic_network_kwargs, policy_network_kwargs, mlp_plain, mlp_ragged, mlp_wide)
     # mlp_plain=True: each network's own use_layer_norm (mlp.py:29-30); else LayerNorm in both, as always
     lns = mlp_layer_norms(critic_network_kwargs, policy_network_kwargs) if mlp_plain else (True, True)
     acts = mlp_activations(critic_network_kwargs, policy_network_kwargs, mlp_dropout)
@@ -388,7 +414,8 @@ def network_spec(critic_network_kwargs, policy_network_kwargs, policy_kwargs, ac
     if dims == ((hidden, hidden), (hidden, hidden)):
         dims = (None, None)    # [h, h] twice: the very agent the call without the switch makes
     spec = NetSpec(std_param, squash, None if fixed is None else tuple(float(x) for x in fixed), *acts, *rates, hidden, *dims, *lns)
-    return dataclasses.replace(spec, ragged=bool(mlp_ragged) and spec.off_grid, use_proprio=bool(use_proprio)).check()
+    wide = bool(mlp_wide) and max(max(net) for net in spec.dims) > 1024
+    return dataclasses.replace(spec, ragged=bool(mlp_ragged) and spec.off_grid, use_proprio=bool(use_proprio), wide=wide).check()
 
 
 def _policy_std_shapes(Hd, A, std_parameterization):
