@@ -361,7 +361,17 @@ typedef struct serl_agent_cfg {
  *                  serl_agent_eval_q_actions and serl_agent_sample_best when the critic's FIRST layer is stored wider than 1024
  *                  (SERL_ERR_UNSUPPORTED: the fan-out rows hold a whole row per wave) -- a policy wider than 1024 beside a
  *                  narrower first critic layer is served.  Any other value is SERL_ERR_INVALID.  serl_agent_wide_widths reads it
- *                  back.  The entry points from before serl_agent_opts leave it 0. */
+ *                  back.  The entry points from before serl_agent_opts leave it 0.
+ *   wide_actions   0: cfg->act_dim ends at 64 ("bad dims" above it); every check, message and launch is what it was.  1: act_dim
+ *                  is any integer in [1, 256] (a flattened action chunk, both arms of a bimanual setup).  Above 64 every kernel
+ *                  that touches an action vector runs the wide head rows (csrc/head_wide.h): one wave per sample row, lane l on
+ *                  columns l + 64 j, row sums per lane in j order and then the wave's butterfly, so a row's bits do not depend
+ *                  on the row count.  The policy head is then its own launch behind the head GEMM in BOTH schedules of the
+ *                  chain, one launch for all instances of a phase (the fused schedule loses the head GEMM's sampling epilogue:
+ *                  one launch more in the critic phase and one in the actor phase), and the actions rider of a pixel agent's encoder
+ *                  pass is one column-copy launch.  act_dim <= 64 launches what it always did: such an agent is the agent of
+ *                  wide_actions 0, bit for bit.  act_dim above 256 and any other value of the switch are SERL_ERR_INVALID.
+ *                  serl_agent_wide_actions reads it back.  The entry points from before serl_agent_opts leave it 0. */
 #define SERL_MAX_MLP_LAYERS 4
 typedef struct serl_mlp_opts {
   int act;
@@ -377,6 +387,7 @@ typedef struct serl_agent_opts {
   const float* fixed_std;
   int ragged_widths;
   int wide_widths;   /* (beside the other width switch; no_proprio stays the last field) */
+  int wide_actions;  /* (likewise) */
   int no_proprio;
 } serl_agent_opts;
 int serl_agent_create_opts(const serl_agent_cfg* cfg, const serl_agent_opts* opts, serl_agent** out);
@@ -405,6 +416,7 @@ int serl_agent_create_fixed_std(const serl_agent_cfg* cfg, int std_param, int no
  * 1 = policy.  Returns the layer count and fills dims[0 .. count); -1 on a NULL argument or another network code. */
 int serl_agent_mlp_dims(serl_agent* a, int network /* 0 critic, 1 policy */, int dims[SERL_MAX_MLP_LAYERS]);  /* -> layer count */
 int serl_agent_wide_widths(serl_agent* a);  /* serl_agent_opts.wide_widths of any agent: 1 or 0; -1 on a NULL agent */
+int serl_agent_wide_actions(serl_agent* a); /* serl_agent_opts.wide_actions of any agent: 1 or 0; -1 on a NULL agent */
 /* Whether the layers of one MLP of any agent have their LayerNorm (networks/mlp.py:29-30): network 0 = critic, 1 = policy.
  * Returns 1 or 0; -1 on a NULL agent or another network code. */
 int serl_agent_mlp_layer_norm(serl_agent* a, int network /* 0 critic, 1 policy */);
@@ -822,6 +834,11 @@ typedef struct serl_bc_opts {
   int no_proprio;
 } serl_bc_opts;
 int serl_bc_create_opts(const serl_bc_cfg* cfg, const serl_bc_opts* opts, serl_bc** out);
+/* serl_bc_create_opts with wide_actions (serl_agent_opts.wide_actions for the BC agent; an argument, because serl_bc_opts keeps its
+ * one field): 1 lets act_dim be any integer in [1, 256] instead of [1, 64].  The BC head kernel loops over the action columns per
+ * sample and every buffer is sized from act_dim, so no launch changes: act_dim <= 64 gives the agent of wide_actions 0, bit for
+ * bit.  act_dim above 256 and any value but 0 and 1 are SERL_ERR_INVALID.  serl_bc_create_opts is this call with 0. */
+int serl_bc_create_wide(const serl_bc_cfg* cfg, const serl_bc_opts* opts, int wide_actions, serl_bc** out);
 int serl_bc_use_proprio(serl_bc* c);   /* 1: proprio branch, 0: no_proprio, -1: NULL */
 int serl_bc_destroy(serl_bc* c);
 int serl_bc_num_leaves(serl_bc* c);

@@ -68,6 +68,21 @@ CHAIN = [
     ("policy_fanout_kernel<1>", 80),
     ("policy_fanout_kernel<3>", 80),
     ("q_rank_kernel", 80),
+    # the wide head rows (csrc/head_wide.h, serl_agent_opts.wide_actions: 65 to 256 action columns, up to 4 per lane): the head
+    # forward and backward of an update, and the read-only calls, a fixed-std instantiation of each; the fan-out at the default critic
+    # width, 16 KB of LDS (like its narrow twin it leaves the budget at the widest critic rows: DESIGN.md section 7, WIDE ACTIONS; --all)
+    ("policy_head_wide_kernel<0>", 80),
+    ("policy_head_wide_kernel<1>", 80),
+    ("policy_head_wide_kernel<3>", 80),
+    ("policy_head_wide_bwd_kernel<0>", 80),
+    ("policy_head_wide_bwd_kernel<1>", 80),
+    ("policy_head_wide_bwd_kernel<3>", 80),
+    ("policy_stats_wide_kernel<0>", 80),
+    ("policy_stats_wide_kernel<3>", 80),
+    ("policy_fanout_wide_kernel<0>", 80),
+    ("policy_fanout_wide_kernel<3>", 80),
+    ("critic_fanout_wide_kernel<4>", 80),
+    ("q_rank_wide_kernel", 80),
 ]
 
 

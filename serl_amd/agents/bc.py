@@ -109,10 +109,12 @@ class BCAgent(Handle):
     prefix = "serl_bc"
 
     def __init__(self, image_keys, H, W, state_dim, act_dim, *, seed_key, max_batch=256, learning_rate=3e-4, device=0,
-                 dropout=0.1, std_min=1e-5, std_max=5.0, use_proprio=True):
+                 dropout=0.1, std_min=1e-5, std_max=5.0, use_proprio=True, wide_actions=False):
         if not isinstance(use_proprio, (bool, np.bool_)):
             raise TypeError(f"use_proprio must be a bool (got {use_proprio!r})")
         self.use_proprio = bool(use_proprio)     # False: serl_bc_opts.no_proprio, the image codes alone; the state is never read
+        from ..utils.init import act_dim_served
+        self.wide_actions = act_dim_served(act_dim, wide_actions)     # serl_bc_create_wide: act_dim above 64, up to 256
         self.image_keys = tuple(image_keys)
         self.H, self.W, self.S, self.A, self.max_batch, self.device = H, W, state_dim, act_dim, max_batch, device
         self.config = {"image_keys": self.image_keys, "use_proprio": self.use_proprio}
@@ -123,14 +125,15 @@ class BCAgent(Handle):
         self.state = BCTrainState(self)
 
     def _create(self, cfg):
-        return self.L.serl_bc_create_opts(C.byref(cfg), C.byref(SerlBcOpts(0 if self.use_proprio else 1)), C.byref(self._h))
+        return self.L.serl_bc_create_wide(C.byref(cfg), C.byref(SerlBcOpts(0 if self.use_proprio else 1)), 1 if self.wide_actions else 0,
+                                          C.byref(self._h))
 
     # ------------------------------------------------------------------ construction (bc.py:118-204)
     @classmethod
     def create(cls, rng, observations, actions, encoder_type: str = "small", image_keys: Iterable[str] = ("image",),
                use_proprio: bool = False, network_kwargs: dict = None, policy_kwargs: dict = None,
                learning_rate: float = 3e-4, batch_size: int = 256, device: int = 0, param_seed: Optional[int] = None,
-               param_init: str = "numpy"):
+               param_init: str = "numpy", wide_actions: bool = False):
         """`rng`: a jax.random key (uint32[2]) or an int seed.  Only the frozen pretrained ResNet-10 encoder is served.
         As for DrQAgent.create_drq, the trunk keeps its initialiser's values until the caller runs
         utils.train_utils.load_resnet10_params(agent, image_keys) (the reference calls it at the end of create, bc.py:200-203,
@@ -139,6 +142,8 @@ class BCAgent(Handle):
         concatenated camera codes alone, `encoder` holds no Dense_0 / LayerNorm_0, network/Dense_0's kernel is (256 * n_cam, 256),
         and only the two MLP layers and the two heads train.  observations["state"] is still required (the stores carry it); its
         values are never read.  True adds the proprio branch (what make_bc_agent builds).
+        wide_actions=True: actions.shape[-1] is any integer in [1, 256] instead of [1, 64] (serl_bc_create_wide; the head kernel
+        loops over the action columns, so no launch changes); without it a width above 64 is refused by the library, as always.
         param_init: "numpy" (default) or "reference" (the reference's own initialisers and keys from `rng`, utils/init_ref.py)."""
         from ..utils import init_ref
         reference = init_ref.check_param_init(param_init)
@@ -160,7 +165,7 @@ class BCAgent(Handle):
         S = int(np.asarray(observations["state"]).shape[-1])
         A = int(np.asarray(actions).shape[-1])
         agent = cls(image_keys, H, W, S, A, seed_key=key, max_batch=batch_size, learning_rate=learning_rate, device=device,
-                    std_min=float(pk.get("std_min", 1e-5)), std_max=float(pk.get("std_max", 10.0)), use_proprio=bool(use_proprio))
+                    std_min=float(pk.get("std_min", 1e-5)), std_max=float(pk.get("std_max", 10.0)), use_proprio=bool(use_proprio), wide_actions=wide_actions)
         from ..utils.init import init_theta, init_trunk
         seed = int(key[1]) if param_seed is None else param_seed
         agent.load_flat(init_trunk(seed))

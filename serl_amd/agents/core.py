@@ -29,7 +29,7 @@ class AgentCore(Handle):
                  critic_subsample_size=2, backup_entropy=False, num_stack=1, std_parameterization="exp",
                  tanh_squash_distribution=True, critic_activation="tanh", policy_activation="tanh",
                  critic_dropout=0.0, policy_dropout=0.0, critic_dims=None, policy_dims=None, critic_layer_norm=True,
-                 policy_layer_norm=True, fixed_std=None, ragged=False, use_proprio=True, wide=False):
+                 policy_layer_norm=True, fixed_std=None, ragged=False, use_proprio=True, wide=False, wide_actions=False):
         """optimizers: optional {"actor"|"critic"|"temperature": make_optimizer kwargs (common/optimizers.py:6-13:
         learning_rate, warmup_steps, cosine_decay_steps, weight_decay, clip_grad_norm)} overriding lr / warmup_steps.
         weight_decay decays every leaf of the tree, as optax.adamw does with the params the reference hands it -- with
@@ -55,6 +55,8 @@ class AgentCore(Handle):
         wide: serl_agent_opts.wide_widths -- hidden and the entries of critic_dims / policy_dims end at 4096 instead of 1024; a
         layer above 1024 runs the LayerNorm rows that one workgroup owns (include/serl_mi355.h), and a critic whose first layer is
         one refuses q_values with [n, N, A] actions and sample_actions(num_candidates > 1).
+        wide_actions: serl_agent_opts.wide_actions -- act_dim ends at 256 instead of 64; above 64 every kernel that touches an action
+        vector runs the wide head rows (include/serl_mi355.h), up to 64 the agent is the one without the switch, bit for bit.
         These network options are no fields of serl_agent_cfg: they make one utils.init.NetSpec (`spec`), whose check() says where
         a positive Dropout rate is served, and go to serl_agent_create_opts as one struct (_create)."""
         if target_entropy is None:
@@ -86,7 +88,7 @@ class AgentCore(Handle):
                             float(critic_dropout), float(policy_dropout), int(hidden),
                             None if critic_dims is None else tuple(int(d) for d in critic_dims),
                             None if policy_dims is None else tuple(int(d) for d in policy_dims),
-                            bool(critic_layer_norm), bool(policy_layer_norm), bool(ragged), use_proprio, bool(wide))
+                            bool(critic_layer_norm), bool(policy_layer_norm), bool(ragged), use_proprio, bool(wide), bool(wide_actions))
         opts = self.spec.to_c()      # (an unknown std_parameterization or activation name raises here)
         self.spec.check()
         for f in dataclasses.fields(self.spec):      # the options as public attributes, under the constructor's names ...

@@ -175,7 +175,7 @@ class DrQAgent:
                    batch_size: int = 256, device: int = 0, learning_rate: float = 3e-4,
                    actor_optimizer_kwargs: dict = None, critic_optimizer_kwargs: dict = None,
                    temperature_optimizer_kwargs: dict = None, param_init: str = "numpy", mlp_dropout: bool = False, mlp_shapes: bool = False, mlp_plain: bool = False,
-                   policy_fixed: bool = False, mlp_ragged: bool = False, image_only: bool = False, mlp_wide: bool = False, **kwargs):
+                   policy_fixed: bool = False, mlp_ragged: bool = False, image_only: bool = False, mlp_wide: bool = False, wide_actions: bool = False, **kwargs):
         """drq.py:104-242.  Only the configuration the reference's examples run is built natively:
         encoder_type="resnet-pretrained", use_proprio=True, REDQ subsample 2, tanh-squashed
         exp-parameterised policy, LayerNorm+tanh MLPs (utils/launcher.py:79-116) -- 256x256 there; critic_network_kwargs /
@@ -213,6 +213,11 @@ class DrQAgent:
         of four waves owns a LayerNorm row (csrc/ln_wide.h); widths up to 1024 give the agent the call without the switch gives.
         Refused beside a width above 1024: a positive dropout_rate under mlp_dropout=True, from the arguments alone; and, where
         the critic's first layer is that wide, q_values with [n, N, A] actions and sample_actions(num_candidates > 1), by the library.
+        wide_actions=True: the action width, actions.shape[-1], is any integer in [1, 256] instead of [1, 64] -- a flattened action
+        chunk, both arms of a bimanual setup.  Above 64 every kernel that touches an action vector runs the wide head rows
+        (csrc/head_wide.h: one wave per sample, up to 4 columns per lane) and the policy head is a launch of its own behind the head
+        GEMM; up to 64 the call gives the agent the call without the switch gives.  Without it a width above 64 is refused by the
+        library, as always; 257 and a switch that is no bool are refused from the arguments alone.
         Frame stacks: the sample observation carries T = observations[image_key].shape[0] frames and a (T, S) state, as
         ChunkingWrapper(obs_horizon=T) produces them; EncodingWrapper(enable_stacking=True) folds them into the channels and the
         proprio width (common/encoding.py:39-44,58-64).  T in 1..4 with encoder_type="small"; the pretrained ResNet-10 cannot take
@@ -244,7 +249,7 @@ class DrQAgent:
         A = int(np.asarray(actions).shape[-1])
         spec = pinit.network_spec(critic_network_kwargs, policy_network_kwargs, pk, A, mlp_dropout=mlp_dropout, mlp_shapes=mlp_shapes,
                                   mlp_plain=mlp_plain, policy_fixed=policy_fixed, mlp_ragged=mlp_ragged,
-                                  use_proprio=bool(use_proprio) if image_only else True, mlp_wide=mlp_wide)
+                                  use_proprio=bool(use_proprio) if image_only else True, mlp_wide=mlp_wide, wide_actions=wide_actions)
         seed = int(np.asarray(rng).reshape(-1)[-1]) if not isinstance(rng, int) else rng
         image_keys = tuple(image_keys)
         img = np.asarray(observations[image_keys[0]])

@@ -154,6 +154,10 @@ def net_spec_of(core) -> NetSpec:
         kw["wide"] = int(core.L.serl_agent_wide_widths(core._h)) == 1
     elif hasattr(core, "wide"):
         kw["wide"] = bool(core.wide)
+    if getattr(core, "_h", None) is not None and hasattr(core, "L"):      # ... and whether its action width ends at 256
+        kw["wide_actions"] = int(core.L.serl_agent_wide_actions(core._h)) == 1
+    elif hasattr(core, "wide_actions"):
+        kw["wide_actions"] = bool(core.wide_actions)
     return NetSpec(hidden=int(getattr(core.cfg, "hidden", 256)), **kw)
 
 

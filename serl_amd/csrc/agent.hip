@@ -343,7 +343,8 @@ size_t carve(serl_agent* a, void* base) {
   // numbers in the message (hidden = 1024 x 16 members x 65 rows: tests/test_mlp_widths_gpu.py).  The lanes are shared by all
   // layers: the policy's and the critic's terms take the widest layer of their MLP, the head gradient the critic's last width.
   const long Bp = pad64(B);
-  long cap = std::max<long>({(long)c.n_cam * 32 * Bp * c.bottleneck, N * Bp * pad64(a->XA), 8 * Bp * Wp, 4 * N * Bp * Wc, 16L * 64 * Hc});
+  // (the policy head's slabs, two groups K-split 4: at most the policy-layer term up to 64 action columns, a term of their own above)
+  long cap = std::max<long>({(long)c.n_cam * 32 * Bp * c.bottleneck, N * Bp * pad64(a->XA), 8 * Bp * Wp, 4 * N * Bp * Wc, 16L * 64 * Hc, 8 * Bp * A});
   a->slabs_cap = cap;
   for (int k = 0; k < 3; ++k) a->slabs_lane[k] = b.take<float>(cap);
   a->slabs = a->slabs_lane[0];
@@ -445,6 +446,16 @@ int encode_multi(serl_agent* a, const EncJob* jobs, int n, int off, int cnt, hip
   LnFwdArgs lv[3];
   ProprioArgs pv[3];
   bool any_rider = false;   // image-only agents: some instance carries the actions rider
+  // wide_actions: the proprio rows' rider holds one action column per lane; above 64 columns the riders of the pass are one
+  // column-copy launch of their own, up front (they read the batch alone)
+  const bool wide_rider = c.act_dim > 64;
+  if (wide_rider) {
+    CopyJob cj[kMaxMulti];
+    int m = 0;
+    for (int i = 0; i < n; ++i)
+      if (jobs[i].act_dst) cj[m++] = CopyJob{jobs[i].act_src, c.act_dim, jobs[i].act_dst, a->XA, c.act_dim};
+    if (m) RC(copy_cols_multi(cj, m, cnt, st));
+  }
   const int S = split_for(a->split_budget, cnt, c.bottleneck, c.n_cam * n, 32);  // K = 4096: up to 32 slices of 128
   for (int i = 0; i < n; ++i) {
     const EncJob& j = jobs[i];
@@ -459,8 +470,8 @@ int encode_multi(serl_agent* a, const EncJob* jobs, int n, int off, int cnt, hip
     ProprioArgs& pr = pv[i];
     pr = ProprioArgs{};   // (without the proprio branch: the rider's fields alone, and the state is not touched)
     if (a->prop) pr = layer_row_fwd(o.prop, j.P, prop_io(a, e, a->cur.state + ((long)j.which * Bfull + off) * c.state_dim));
-    else any_rider = any_rider || j.act_dst;
-    if (j.act_dst) {
+    else any_rider = any_rider || (j.act_dst && !wide_rider);
+    if (j.act_dst && !wide_rider) {
       pr.copy_src = j.act_src; pr.ld_copy_src = c.act_dim; pr.copy_dst = j.act_dst; pr.ld_copy_dst = a->XA;
       pr.copy_cols = c.act_dim;
     }
@@ -502,7 +513,7 @@ int encode_multi(serl_agent* a, const EncJob* jobs, int n, int off, int cnt, hip
   CopyJob cj[kMaxMulti];
   int m = 0;
   for (int i = 0; i < n; ++i)
-    if (jobs[i].act_dst) cj[m++] = CopyJob{jobs[i].act_src, c.act_dim, jobs[i].act_dst, a->XA, c.act_dim};
+    if (jobs[i].act_dst && !wide_rider) cj[m++] = CopyJob{jobs[i].act_src, c.act_dim, jobs[i].act_dst, a->XA, c.act_dim};
   return m ? copy_cols_multi(cj, m, cnt, st) : SERL_OK;
 }
 
@@ -594,6 +605,28 @@ int policy_fwd_multi(serl_agent* a, const PolJob* jobs, int n, int cnt, hipStrea
     pv[i].sum_logp = j.sum_logp; pv[i].lam = P + o.lam; pv[i].alpha_out = j.alpha_out;
   }
   RC(policy_mlp_multi(a, jobs, n, cnt, st));
+  if (A > 64) {   // wide_actions: the head rows as ONE launch of their own behind the head GEMM, in both schedules (head_wide.h)
+    SERL_REQUIRE((long)a->head_groups * 4 * cnt * A <= a->slabs_cap, "policy head: %d groups x 4 K-splits x %d rows x %d action columns exceeds the slab scratch of %ld floats",
+                 a->head_groups, cnt, A, a->slabs_cap);
+    Colsum3Args now[3];
+    int nnow = 0;
+    for (int i = 0; i < n; ++i) {
+      const PolJob& j = jobs[i];
+      PolicyDistArgs& v = pv[i];
+      // (eps == nullptr, the fused schedule: the rows draw as the epilogue does, from the key or the seed, and keep the draws in eps_out)
+      v.eps_out = j.eps_out; v.seed = j.eps_seed; v.row_offset = j.eps_row0;
+      v.tf = j.tf_key ? 1 : 0;
+      if (j.tf_key) { v.tf_key[0] = j.tf_key[0]; v.tf_key[1] = j.tf_key[1]; v.tf_rows = j.tf_rows; v.tf_row0 = j.tf_row0; }
+      if (!j.sum_logp) continue;
+      // sum_b log pi: a vector-sum job of the phase's deferred column-sum launch where there is one, else of a launch behind the rows
+      const Colsum3Args cs{j.pb->logp, nullptr, nullptr, 1, cnt, 1, nullptr, j.sum_logp, nullptr, 0, 2};
+      if (a->pg_defer && a->pg_ncs < kMaxColsum) a->pg_cs[a->pg_ncs++] = cs;
+      else now[nnow++] = cs;
+    }
+    RC(gemm_f32_multi(gd, n, st));
+    RC(policy_dist_fwd_multi(pv, n, cnt, A, c.std_min, c.std_max, st));
+    return nnow ? colsum3_multi(now, nnow, st) : SERL_OK;
+  }
   if (a->fuse) {   // the tanh-Gaussian head inside the head GEMM: last arriver of every 64-row tile (heads.hip, kEpiPolicy)
     SERL_REQUIRE(A <= 64, "the fused policy-head epilogue holds one 64-wide slab row per sample (act_dim %d)", A);
     SERL_REQUIRE(cdiv(cnt, 64) <= kCtrPerLane && 8 * pad64(cnt) * 64 <= a->slabs_cap, "policy head exceeds the fused epilogue's scratch");
@@ -1064,6 +1097,7 @@ int serl_agent_mlp_dims(serl_agent* a, int network, int dims[SERL_MAX_MLP_LAYERS
 
 // serl_agent_opts.wide_widths as the agent was created with it
 int serl_agent_wide_widths(serl_agent* a) { return a ? a->opts.wide_widths : -1; }
+int serl_agent_wide_actions(serl_agent* a) { return a ? a->opts.wide_actions : -1; }
 
 // Every entry point's agent (serl_mi355.h, NETWORK OPTIONS).  The two networks are built from separate kwargs (sac.py:516-524,
 // drq.py:188-207), so their options are independent: mlp.py:19-31 applies `activations` behind every layer and loops over
@@ -1147,7 +1181,10 @@ static int create_agent(const serl_agent_cfg* cfg, const serl_agent_opts* opts, 
   SERL_REQUIRE(cfg->bottleneck == 256, "bottleneck must be 256 (got %d): the reference fixes bottleneck_dim=256 in create_drq", cfg->bottleneck);
   SERL_REQUIRE(cfg->proprio_dim == 64, "proprio_dim must be 64");
   SERL_REQUIRE(cfg->sle_features == 8, "sle_features must be 8");
-  SERL_REQUIRE(cfg->batch >= 1 && cfg->ensemble >= 2 && cfg->state_dim >= 1 && cfg->act_dim >= 1 && cfg->act_dim <= 64, "bad dims");
+  // wide_actions 1: act_dim up to 256, above 64 on the wide head rows (head_wide.h); 0: "bad dims" above 64, as always
+  SERL_REQUIRE(opts->wide_actions == 0 || opts->wide_actions == 1, "wide_actions %d is not 0 (act_dim up to 64) or 1 (up to 256)", opts->wide_actions);
+  SERL_REQUIRE(!opts->wide_actions || cfg->act_dim <= 256, "act_dim %d with wide_actions 1: served are 1 to 256 action columns", cfg->act_dim);
+  SERL_REQUIRE(cfg->batch >= 1 && cfg->ensemble >= 2 && cfg->state_dim >= 1 && cfg->act_dim >= 1 && (cfg->act_dim <= 64 || opts->wide_actions), "bad dims");
   const int num_stack = cfg->num_stack > 0 ? cfg->num_stack : 1;   // 0 = 1: a zero-initialised field keeps its meaning
   SERL_REQUIRE(cfg->num_stack >= 0 && num_stack <= kSmallMaxStack, "num_stack %d not in [1,%d]", cfg->num_stack, kSmallMaxStack);
   if (num_stack > 1 && cfg->n_cam > 0 && cfg->encoder_type == SERL_ENCODER_RESNET_PRETRAINED) {

@@ -22,6 +22,7 @@ using namespace serl;
 
 namespace {
 constexpr int kHidden = 256, kBottleneck = 256, kSleFeatures = 8, kProprio = 64, kMaxAct = 64;
+constexpr int kMaxActWide = 256;   // serl_bc_create_wide: the head kernel loops over A per sample; every buffer is sized from A
 }  // namespace
 
 struct serl_bc {
@@ -86,6 +87,7 @@ size_t carve(serl_bc* c, uint8_t* base) {
   uint8_t* ws = b.take<uint8_t>(trunk_workspace_bytes(g.n_cam * g.max_batch, g.H, g.W));
   c->feats = b.take<float>((size_t)g.n_cam * n * c->HW * 512);
   c->f = b.take<float>((size_t)g.n_cam * n * c->D);
+  static_assert(8 * kBottleneck >= 2 * 4 * kMaxActWide, "the head GEMM's slabs (2 groups x K-split 4 x act_dim columns per row) fit the scratch");
   c->slabs_cap = (long)std::max(32 * g.n_cam, 8) * n * kBottleneck;
   c->slabs = b.take<float>(c->slabs_cap);
   c->enc = b.take<float>(n * c->E);
@@ -311,11 +313,19 @@ int serl_bc_create(const serl_bc_cfg* cfg, serl_bc** out) {
 int serl_bc_use_proprio(serl_bc* c) { return c ? (c->has_prop ? 1 : 0) : -1; }
 
 int serl_bc_create_opts(const serl_bc_cfg* cfg, const serl_bc_opts* opts, serl_bc** out) {
+  return serl_bc_create_wide(cfg, opts, 0, out);
+}
+
+// wide_actions 1: act_dim up to kMaxActWide.  An argument of an entry point of its own, not a field: serl_bc_opts is the struct it was.
+int serl_bc_create_wide(const serl_bc_cfg* cfg, const serl_bc_opts* opts, int wide_actions, serl_bc** out) {
   SERL_REQUIRE(cfg && opts && out, "NULL argument");
+  SERL_REQUIRE(wide_actions == 0 || wide_actions == 1, "wide_actions %d is not 0 (act_dim up to %d) or 1 (up to %d)", wide_actions, kMaxAct, kMaxActWide);
+  SERL_REQUIRE(!wide_actions || cfg->act_dim <= kMaxActWide, "act_dim %d with wide_actions 1: served are 1 to %d action columns", cfg->act_dim,
+               kMaxActWide);
   SERL_REQUIRE(opts->no_proprio == 0 || opts->no_proprio == 1, "no_proprio %d is not 0 (the proprio branch) or 1 (image codes alone)", opts->no_proprio);
   SERL_REQUIRE(cfg->n_cam >= 1 && cfg->n_cam <= SERL_MAX_CAMS, "n_cam %d not in [1,%d]", cfg->n_cam, SERL_MAX_CAMS);
   SERL_REQUIRE(cfg->H >= 32 && cfg->W >= 32 && cfg->max_batch >= 1, "bad BC shape");
-  SERL_REQUIRE(cfg->state_dim >= 1 && cfg->act_dim >= 1 && cfg->act_dim <= kMaxAct, "state_dim %d / act_dim %d unsupported",
+  SERL_REQUIRE(cfg->state_dim >= 1 && cfg->act_dim >= 1 && (cfg->act_dim <= kMaxAct || wide_actions), "state_dim %d / act_dim %d unsupported",
                cfg->state_dim, cfg->act_dim);
   SERL_REQUIRE(cfg->dropout >= 0.f && cfg->dropout < 1.f && cfg->std_min > 0.f && cfg->std_max > cfg->std_min, "bad BC hyper-parameters");
   SERL_HIP(hipSetDevice(cfg->device));

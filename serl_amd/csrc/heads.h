@@ -40,7 +40,7 @@ struct FanoutArgs {
   LnFwdArgs l;
   const float* w_act; long w_gstride;
   const float* actions;   // [n][N][A]
-  int N, A;               // A <= 64
+  int N, A;               // A <= 256 (above 64: action blocks of 64 columns, head_wide.h)
 };
 int critic_fanout_fwd(const FanoutArgs& f, int D, hipStream_t stream);
 // One width-256 ReLU instance with a row-dot (the reward classifier's head), closed for reward labelling: dot_out = logits,
@@ -160,7 +160,7 @@ struct QRankArgs {
   float* action_out;      // [n][A]
   int* index;             // [n]
   float* score;           // [n]
-  int E, n, N, A, mean;   // A <= 64
+  int E, n, N, A, mean;   // A <= 256 (above 64: the copy over up to 4 columns per lane, head_wide.h)
 };
 int q_rank(const QRankArgs& v, hipStream_t stream);
 // proprio branch: y = tanh(LN(state W + b)) with W [S][64] (encoding.py:55-70), one wave per row

@@ -1257,16 +1257,20 @@ __global__ __launch_bounds__(256) void critic_fanout_kernel(FanoutArgs f) {
   }
 }
 
+#include "head_wide.h"
+
 int critic_fanout_fwd(const FanoutArgs& f, int D, hipStream_t stream) {
   const LnFwdArgs& a = f.l;
   SERL_REQUIRE(SERL_LN_WIDTH_OK(D) && D <= 1024, "fanned-out critic layer: width %d unsupported (a multiple of 64 in [64, 1024])", D);
-  SERL_REQUIRE(f.A >= 1 && f.A <= 64, "fanned-out critic layer: %d action columns; a wave holds one candidate's actions, 1 to 64", f.A);
+  SERL_REQUIRE(f.A >= 1 && f.A <= kHeadWideMax, "fanned-out critic layer: %d action columns; a wave holds one candidate's actions in blocks of 64, 1 to %d",
+               f.A, kHeadWideMax);
   SERL_REQUIRE(f.N >= 1 && a.rows_per_group >= 1 && a.rows >= a.rows_per_group && a.rows % a.rows_per_group == 0 && a.S >= 1,
                "fanned-out critic layer: bad shape (%d candidates, %d rows, %d per group, %d slabs)", f.N, a.rows, a.rows_per_group, a.S);
   SERL_REQUIRE(a.slabs && a.y && f.w_act && f.actions && (a.gamma == nullptr) == (a.beta == nullptr), "fanned-out critic layer: NULL tensor");
   SERL_REQUIRE(a.d >= 0 && a.d < D && a.act >= 0 && a.act < kActCount && a.drop.mode == kLnDropNone,
                "fanned-out critic layer: true width %d in %d, activation code %d, Dropout mode %d", a.d, D, a.act, a.drop.mode);
   const dim3 grid(cdiv(a.rows_per_group, 4), a.rows / a.rows_per_group);
+  if (f.A > 64) return critic_fanout_wide(f, D, grid, stream);   // action blocks of 64 columns (head_wide.h)
 #define SERL_FAN_CASE(V) case V: SERL_LAUNCH_CHAIN(critic_fanout_kernel<V>, grid, dim3(256), 0, stream, f); break;
   switch (D / 64) {
     SERL_FAN_CASE(1) SERL_FAN_CASE(2) SERL_FAN_CASE(3) SERL_FAN_CASE(4) SERL_FAN_CASE(5) SERL_FAN_CASE(6) SERL_FAN_CASE(7) SERL_FAN_CASE(8)
@@ -2014,6 +2018,15 @@ int policy_dist_fwd_multi(const PolicyDistArgs* vs, int n, int B, int A, float s
     mv.v[i] = vs[i];
     SERL_REQUIRE(vs[i].mode == vs[0].mode, "the policy heads of one launch share a distribution mode");
   }
+  if (A > 64) {   // the wide head rows (head_wide.h): one launch for all instances, the slabs as the head GEMM leaves them
+    SERL_REQUIRE(A <= kHeadWideMax, "policy head: %d action columns; the wide head rows serve 65 to %d", A, kHeadWideMax);
+    for (int i = 0; i < n; ++i) {
+      PolicyDistArgs& v = mv.v[i];
+      SERL_REQUIRE(v.eps || v.eps_out, "policy noise: neither draws nor a buffer for drawn ones");
+      v.B = B; v.A = A; v.std_min = std_min; v.std_max = std_max; v.slab_ld = A; v.slab_stride = (long)B * A;
+    }
+    return policy_head_wide_fwd(mv, n, B, stream);
+  }
 #define SERL_X(M) SERL_LAUNCH_CHAIN(policy_dist_fwd_kernel<M>, dim3(n), dim3(256), 0, stream, mv, B, A, std_min, std_max)
   SERL_POLICY_MODE_SWITCH(vs[0].mode, SERL_X, SERL_REQUIRE(false, "bad policy distribution mode %d", vs[0].mode))
 #undef SERL_X
@@ -2103,8 +2116,9 @@ __global__ __launch_bounds__(256) void policy_stats_fixed_kernel(PolicyStatsArgs
 }
 
 int policy_stats(const PolicyStatsArgs& v, hipStream_t stream) {
-  SERL_REQUIRE(v.rows >= 1 && v.A >= 1 && v.A <= 64, "policy statistics: %d rows x %d action columns (one lane per column: at most 64)", v.rows, v.A);
+  SERL_REQUIRE(v.rows >= 1 && v.A >= 1 && v.A <= kHeadWideMax, "policy statistics: %d rows x %d action columns (at most %d)", v.rows, v.A, kHeadWideMax);
   SERL_REQUIRE(!v.logp || v.act, "policy statistics: a log-density needs the actions it is the density of");
+  if (v.A > 64) return policy_stats_wide(v, stream);   // up to 4 columns per lane (head_wide.h)
 #define SERL_X(M) SERL_LAUNCH_CHAIN(policy_stats_kernel<M>, dim3(cdiv(v.rows, 4)), dim3(256), 0, stream, v)
   switch (v.mode) {
     SERL_POLICY_PARAM_CASES(SERL_X)
@@ -2186,9 +2200,10 @@ __global__ __launch_bounds__(256) void policy_fanout_kernel(PolicyFanoutArgs v) 
 }
 
 int policy_fanout(const PolicyFanoutArgs& v, hipStream_t stream) {
-  SERL_REQUIRE(v.rows >= 1 && v.N >= 1 && v.A >= 1 && v.A <= 64 && v.S >= 1,
-               "policy fan-out: %d rows x %d candidates x %d action columns (one lane per column: at most 64), %d slabs", v.rows, v.N, v.A, v.S);
+  SERL_REQUIRE(v.rows >= 1 && v.N >= 1 && v.A >= 1 && v.A <= kHeadWideMax && v.S >= 1,
+               "policy fan-out: %d rows x %d candidates x %d action columns (at most %d), %d slabs", v.rows, v.N, v.A, kHeadWideMax, v.S);
   SERL_REQUIRE(v.slabs && v.bias_mean && v.bias_ls && v.eps && v.actions, "policy fan-out: NULL tensor");
+  if (v.A > 64) return policy_fanout_wide(v, stream);   // up to 4 columns per lane (head_wide.h)
 #define SERL_X(M) SERL_LAUNCH_CHAIN(policy_fanout_kernel<M>, dim3(cdiv(v.rows, 4)), dim3(256), 0, stream, v)
   SERL_POLICY_MODE_SWITCH(v.mode, SERL_X, SERL_REQUIRE(false, "bad policy distribution mode %d", v.mode))
 #undef SERL_X
@@ -2236,9 +2251,10 @@ __global__ __launch_bounds__(256) void q_rank_kernel(QRankArgs v) {
 }
 
 int q_rank(const QRankArgs& v, hipStream_t stream) {
-  SERL_REQUIRE(v.E >= 1 && v.n >= 1 && v.N >= 1 && v.A >= 1 && v.A <= 64,
-               "candidate ranking: %d members x %d observations x %d candidates x %d action columns (one lane per column: at most 64)", v.E, v.n, v.N, v.A);
+  SERL_REQUIRE(v.E >= 1 && v.n >= 1 && v.N >= 1 && v.A >= 1 && v.A <= kHeadWideMax,
+               "candidate ranking: %d members x %d observations x %d candidates x %d action columns (at most %d)", v.E, v.n, v.N, v.A, kHeadWideMax);
   SERL_REQUIRE(v.q && v.actions && v.action_out, "candidate ranking: NULL tensor");
+  if (v.A > 64) return q_rank_wide(v, stream);   // the winner's copy over up to 4 columns per lane (head_wide.h)
   SERL_LAUNCH_CHAIN(q_rank_kernel, dim3(cdiv(v.n, 4)), dim3(256), 0, stream, v);
   SERL_HIP(hipGetLastError());
   return SERL_OK;
@@ -2321,6 +2337,11 @@ int policy_dist_bwd(const float* da, long ld_da, const float* act, long ld_act, 
                     const float* stdv, const float* eps, const float* alpha, float coef, int B, int A,
                     float std_min, float std_max, float* dpre, const float* q, int E, float* qmean_out,
                     hipStream_t stream, int mode) {
+  if (A > 64) {   // a wave per row, up to 4 columns per lane (head_wide.h)
+    SERL_REQUIRE(A <= kHeadWideMax, "policy head backward: %d action columns; the wide head rows serve 65 to %d", A, kHeadWideMax);
+    return policy_head_wide_bwd(HeadBwdArgs{da, ld_da, act, ld_act, pre, stdv, eps, alpha, coef, B, A, std_min, std_max, dpre, q, E, qmean_out},
+                                mode, stream);
+  }
 #define SERL_X(M)                                                                                                            \
   SERL_LAUNCH_CHAIN(policy_dist_bwd_kernel<M>, dim3(cdiv(B * A, 256) + 1), dim3(256), 0, stream, da, ld_da, act, ld_act, pre, \
                     stdv, eps, alpha, coef, B, A, std_min, std_max, dpre, q, E, qmean_out)

@@ -72,6 +72,22 @@ def _served_widths(mlp_ragged, mlp_wide):
             f"no multiple of 64 in [64, {WIDE_MAX}] under mlp_wide=True")
 
 
+ACT_DIM_MAX = 64         # serl_agent_cfg.act_dim: one lane of a wave per action column ...
+ACT_DIM_WIDE_MAX = 256   # ... with serl_agent_opts.wide_actions: up to 4 columns per lane (csrc/head_wide.h)
+
+
+def act_dim_served(act_dim, wide_actions):
+    """The argument check of wide_actions=True (create_states, create_drq, BCAgent.create): the switch is a bool, and under it the
+    action width ends at ACT_DIM_WIDE_MAX.  Without the switch nothing is refused here: an act_dim above 64 is the library's
+    "bad dims", as always.  -> whether the library is to be sent wide_actions = 1 (act_dim above 64 under the switch)."""
+    if not isinstance(wide_actions, (bool, np.bool_)):
+        raise TypeError(f"wide_actions must be a bool (got {wide_actions!r})")
+    if wide_actions and not 1 <= int(act_dim) <= ACT_DIM_WIDE_MAX:
+        raise NotImplementedError(f"action_dim {int(act_dim)} under wide_actions=True (served: 1 to {ACT_DIM_WIDE_MAX} action columns; "
+                                  f"without wide_actions=True 1 to {ACT_DIM_MAX})")
+    return bool(wide_actions) and int(act_dim) > ACT_DIM_MAX
+
+
 _PLAIN_HINT = "; without LayerNorm with mlp_plain=True"
 
 
@@ -284,7 +300,9 @@ class NetSpec:
     alone: no enc/proprio/* leaf, and the first kernels of both MLPs lose the 64 proprio rows.  network_spec sets it from
     create_drq's use_proprio under image_only=True and nowhere else.
     wide: serl_agent_opts.wide_widths -- the widths end at 4096 instead of 1024; network_spec sets it where a width is above 1024 and
-    nowhere else, so that widths up to 1024 through mlp_wide=True give the NetSpec, and the agent, of the call without."""
+    nowhere else, so that widths up to 1024 through mlp_wide=True give the NetSpec, and the agent, of the call without.
+    wide_actions: serl_agent_opts.wide_actions -- act_dim ends at 256 instead of 64, above 64 on the wide head rows
+    (csrc/head_wide.h); network_spec sets it where act_dim is above 64 and nowhere else, to the same end."""
     std_parameterization: str = "exp"
     tanh_squash_distribution: bool = True
     fixed_std: Optional[Tuple[float, ...]] = None
@@ -300,6 +318,7 @@ class NetSpec:
     ragged: bool = False
     use_proprio: bool = True
     wide: bool = False
+    wide_actions: bool = False
 
     @property
     def dims(self):
@@ -392,16 +411,19 @@ class NetSpec:
         o.ragged_widths = 1 if self.ragged else 0
         o.no_proprio = 0 if self.use_proprio else 1
         o.wide_widths = 1 if self.wide else 0
+        o.wide_actions = 1 if self.wide_actions else 0
         return o
 
 
 def network_spec(critic_network_kwargs, policy_network_kwargs, policy_kwargs, act_dim, *, mlp_dropout=False, mlp_shapes=False,
-                 mlp_plain=False, policy_fixed=False, mlp_ragged=False, use_proprio=True, mlp_wide=False) -> NetSpec:
+                 mlp_plain=False, policy_fixed=False, mlp_ragged=False, use_proprio=True, mlp_wide=False, wide_actions=False) -> NetSpec:
     """The checked NetSpec of create_states' / create_drq's three kwargs dicts under their five switches; every refusal is raised
     from the arguments alone, in the order of the lines below.  mlp_ragged=True: every width read below is any integer in
     [1, 1024] (mlp.py:19-31 takes any list); without it the 64 grid, as always.  use_proprio: create_drq's, already checked to be
     a bool and read under image_only=True alone.  mlp_wide=True: every width read below ends at 4096 instead of 1024 (one
-    workgroup per LayerNorm row above 1024); a positive dropout_rate beside such a width is NetSpec.check's to refuse."""
+    workgroup per LayerNorm row above 1024); a positive dropout_rate beside such a width is NetSpec.check's to refuse.
+    wide_actions=True: act_dim is any integer in [1, 256]; without it an act_dim above 64 is the library's to refuse, as always."""
+    send_wide_actions = act_dim_served(act_dim, wide_actions)
     # policy_fixed=True: "fixed" / fixed_std are read (actor_critic_nets.py:189-192); else refused, as always
     std_param, squash, fixed = policy_mode_fixed(policy_kwargs, act_dim) if policy_fixed else (*policy_mode(policy_kwargs), None)
     # mlp_shapes=True: each network's own depth and per-layer widths (mlp.py:19-31); else the one width of [h, h], as always
@@ -415,7 +437,8 @@ def network_spec(critic_network_kwargs, policy_network_kwargs, policy_kwargs, ac
         dims = (None, None)    # [h, h] twice: the very agent the call without the switch makes
     spec = NetSpec(std_param, squash, None if fixed is None else tuple(float(x) for x in fixed), *acts, *rates, hidden, *dims, *lns)
     wide = bool(mlp_wide) and max(max(net) for net in spec.dims) > 1024
-    return dataclasses.replace(spec, ragged=bool(mlp_ragged) and spec.off_grid, use_proprio=bool(use_proprio), wide=wide).check()
+    return dataclasses.replace(spec, ragged=bool(mlp_ragged) and spec.off_grid, use_proprio=bool(use_proprio), wide=wide,
+                               wide_actions=send_wide_actions).check()
 
 
 def _policy_std_shapes(Hd, A, std_parameterization):
