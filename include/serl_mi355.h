@@ -371,7 +371,18 @@ typedef struct serl_agent_cfg {
  *                  one launch more in the critic phase and one in the actor phase), and the actions rider of a pixel agent's encoder
  *                  pass is one column-copy launch.  act_dim <= 64 launches what it always did: such an agent is the agent of
  *                  wide_actions 0, bit for bit.  act_dim above 256 and any other value of the switch are SERL_ERR_INVALID.
- *                  serl_agent_wide_actions reads it back.  The entry points from before serl_agent_opts leave it 0. */
+ *                  serl_agent_wide_actions reads it back.  The entry points from before serl_agent_opts leave it 0.
+ *   dropout_any    0: a positive dropout is served where it always was (two LayerNorm layers of cfg->hidden on the 64 grid, with the
+ *                  proprio branch); every check, message and launch is what it was.  1: a positive dropout in either network is
+ *                  served beside any n_layers / dims, no_layer_norm 1, ragged_widths, wide_widths and no_proprio: the refusals
+ *                  "dropout ... beside/with" those five are skipped, the rate range checks and the SERL_STD_FIXED refusal stay.
+ *                  A layer with Dropout takes the place of its launch one for one, with the DROP rows of its family: a plain
+ *                  layer is y = act(Dropout(Dense(x) + b)), a ragged or wide layer masks in front of its statistics.  The masks
+ *                  and the keys' arrays follow TRUE widths d_l: under mask[site] layer l starts batch * sum_{j<l} d_j bytes in and
+ *                  holds u8 [batch][d_l]; key[site] holds n_layers keys per critic update, layer l's drawing bernoulli(key, keep,
+ *                  (rows, d_l)); padding columns draw nothing.  For two layers of one width on the grid this is the layout above,
+ *                  byte for byte, and the agent is the agent of dropout_any 0.  Any other value is SERL_ERR_INVALID.
+ *                  serl_agent_dropout_any reads it back.  The entry points from before serl_agent_opts leave it 0. */
 #define SERL_MAX_MLP_LAYERS 4
 typedef struct serl_mlp_opts {
   int act;
@@ -388,6 +399,7 @@ typedef struct serl_agent_opts {
   int ragged_widths;
   int wide_widths;   /* (beside the other width switch; no_proprio stays the last field) */
   int wide_actions;  /* (likewise) */
+  int dropout_any;   /* (likewise) */
   int no_proprio;
 } serl_agent_opts;
 int serl_agent_create_opts(const serl_agent_cfg* cfg, const serl_agent_opts* opts, serl_agent** out);
@@ -417,6 +429,7 @@ int serl_agent_create_fixed_std(const serl_agent_cfg* cfg, int std_param, int no
 int serl_agent_mlp_dims(serl_agent* a, int network /* 0 critic, 1 policy */, int dims[SERL_MAX_MLP_LAYERS]);  /* -> layer count */
 int serl_agent_wide_widths(serl_agent* a);  /* serl_agent_opts.wide_widths of any agent: 1 or 0; -1 on a NULL agent */
 int serl_agent_wide_actions(serl_agent* a); /* serl_agent_opts.wide_actions of any agent: 1 or 0; -1 on a NULL agent */
+int serl_agent_dropout_any(serl_agent* a);  /* serl_agent_opts.dropout_any of any agent: 1 or 0; -1 on a NULL agent */
 /* Whether the layers of one MLP of any agent have their LayerNorm (networks/mlp.py:29-30): network 0 = critic, 1 = policy.
  * Returns 1 or 0; -1 on a NULL agent or another network code. */
 int serl_agent_mlp_layer_norm(serl_agent* a, int network /* 0 critic, 1 policy */);

@@ -33,7 +33,7 @@ class SerlMlpOpts(C.Structure):      # serl_mlp_opts: one network's MLP; all zer
 
 class SerlAgentOpts(C.Structure):    # serl_agent_opts (utils.init.NetSpec.to_c fills it); all zero = serl_agent_create(cfg)
     _fields_ = [("std_param", C.c_int), ("no_tanh", C.c_int), ("critic", SerlMlpOpts), ("policy", SerlMlpOpts),
-                ("fixed_std", P(C.c_float)), ("ragged_widths", C.c_int), ("wide_widths", C.c_int), ("wide_actions", C.c_int), ("no_proprio", C.c_int)]
+                ("fixed_std", P(C.c_float)), ("ragged_widths", C.c_int), ("wide_widths", C.c_int), ("wide_actions", C.c_int), ("dropout_any", C.c_int), ("no_proprio", C.c_int)]
 
 
 TX_INDEX = {"actor": 0, "critic": 1, "temperature": 2}   # SERL_TX_*
@@ -107,6 +107,7 @@ SIGNATURES = {
     "serl_agent_mlp_dims": [vp, i32, P(i32)],   # network (0 critic, 1 policy), dims[SERL_MAX_MLP_LAYERS] -> layer count
     "serl_agent_wide_widths": [vp],   # 1 / 0 (serl_agent_opts.wide_widths) / -1
     "serl_agent_wide_actions": [vp],  # 1 / 0 (serl_agent_opts.wide_actions) / -1
+    "serl_agent_dropout_any": [vp],   # 1 / 0 (serl_agent_opts.dropout_any) / -1
     "serl_agent_set_mlp_noise": [vp, P(SerlMlpNoise)],
     "serl_agent_destroy": [vp],
     "serl_agent_live_trunk": [vp],

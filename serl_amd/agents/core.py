@@ -10,7 +10,7 @@ import torch
 
 from .. import _lib
 from .._handle import Handle
-from .._lib_agent import (APPLY_ACTOR_TEMP, APPLY_CRITIC, MLP_SITES, NET_BITS, TX_INDEX, SerlAgentCfg, SerlInfo,  # noqa: F401
+from .._lib_agent import (APPLY_ACTOR_TEMP, APPLY_CRITIC, MLP_SITE_NETWORK, MLP_SITES, NET_BITS, TX_INDEX, SerlAgentCfg, SerlInfo,  # noqa: F401
                           SerlMlpNoise, SerlNoise)
 
 from ..utils.init import FIXED_STD, NetSpec
@@ -29,7 +29,8 @@ class AgentCore(Handle):
                  critic_subsample_size=2, backup_entropy=False, num_stack=1, std_parameterization="exp",
                  tanh_squash_distribution=True, critic_activation="tanh", policy_activation="tanh",
                  critic_dropout=0.0, policy_dropout=0.0, critic_dims=None, policy_dims=None, critic_layer_norm=True,
-                 policy_layer_norm=True, fixed_std=None, ragged=False, use_proprio=True, wide=False, wide_actions=False):
+                 policy_layer_norm=True, fixed_std=None, ragged=False, use_proprio=True, wide=False, wide_actions=False,
+                 dropout_any=False):
         """optimizers: optional {"actor"|"critic"|"temperature": make_optimizer kwargs (common/optimizers.py:6-13:
         learning_rate, warmup_steps, cosine_decay_steps, weight_decay, clip_grad_norm)} overriding lr / warmup_steps.
         weight_decay decays every leaf of the tree, as optax.adamw does with the params the reference hands it -- with
@@ -57,6 +58,9 @@ class AgentCore(Handle):
         one refuses q_values with [n, N, A] actions and sample_actions(num_candidates > 1).
         wide_actions: serl_agent_opts.wide_actions -- act_dim ends at 256 instead of 64; above 64 every kernel that touches an action
         vector runs the wide head rows (include/serl_mi355.h), up to 64 the agent is the one without the switch, bit for bit.
+        dropout_any: serl_agent_opts.dropout_any -- a positive critic_dropout / policy_dropout is served beside any depth and widths,
+        LayerNorm-free networks, ragged and wide widths and use_proprio=False (the DROP rows of every family); the masks of an
+        update's noise then follow the true widths (_noise).
         These network options are no fields of serl_agent_cfg: they make one utils.init.NetSpec (`spec`), whose check() says where
         a positive Dropout rate is served, and go to serl_agent_create_opts as one struct (_create)."""
         if target_entropy is None:
@@ -88,7 +92,7 @@ class AgentCore(Handle):
                             float(critic_dropout), float(policy_dropout), int(hidden),
                             None if critic_dims is None else tuple(int(d) for d in critic_dims),
                             None if policy_dims is None else tuple(int(d) for d in policy_dims),
-                            bool(critic_layer_norm), bool(policy_layer_norm), bool(ragged), use_proprio, bool(wide), bool(wide_actions))
+                            bool(critic_layer_norm), bool(policy_layer_norm), bool(ragged), use_proprio, bool(wide), bool(wide_actions), bool(dropout_any))
         opts = self.spec.to_c()      # (an unknown std_parameterization or activation name raises here)
         self.spec.check()
         for f in dataclasses.fields(self.spec):      # the options as public attributes, under the constructor's names ...
@@ -193,7 +197,9 @@ class AgentCore(Handle):
         key_mask_* uint32[..., n_cam, 2]: draws made inside the consuming kernels where the tensor is absent), or None.
         The MLPs' Dropout draws ride in the same dict, per site of _lib_agent.MLP_SITES: drop_mask_<site> device u8[2, batch, hidden]
         keep-masks or drop_key_<site> uint32[(update,) 2, 2] keys; they are bound to the agent here, for the call this noise is
-        built for (serl_agent_set_mlp_noise)."""
+        built for (serl_agent_set_mlp_noise).  With dropout_any a site's masks follow its network's true widths d_l: a list of one
+        u8[batch, d_l] per layer, or those concatenated flat, or u8[n_layers, batch, d] where every width is d; keys are
+        uint32[(update,) n_layers, 2]."""
         if noise is None:
             self._keep = None
             return None
@@ -204,9 +210,12 @@ class AgentCore(Handle):
             for i, site in enumerate(MLP_SITES):
                 t, k = noise.get("drop_mask_" + site), noise.get("drop_key_" + site)
                 if t is not None:
+                    if self.spec.dropout_any:
+                        t, rows = self._site_masks(site, t, m.mask_rows)
+                    else:
+                        rows = m.mask_rows if m.mask_rows else int(t.shape[1]) if t.dim() == 3 else -1
                     t = t.to(device=self.device, dtype=torch.uint8).contiguous()
-                    rows = m.mask_rows if m.mask_rows else int(t.shape[1]) if t.dim() == 3 else -1
-                    if tuple(t.shape) != (2, rows, self.cfg.hidden):
+                    if not self.spec.dropout_any and tuple(t.shape) != (2, rows, self.cfg.hidden):
                         raise ValueError(f"drop_mask_{site}: expected u8[2, batch, {self.cfg.hidden}], the same batch at every site, "
                                          f"got {tuple(t.shape)}")
                     m.mask_rows = rows
@@ -249,6 +258,22 @@ class AgentCore(Handle):
         if m is not None:
             _lib.check(self.L.serl_agent_set_mlp_noise(self._h, C.byref(m)))
         return C.byref(n)
+
+    def _site_masks(self, site, t, rows):
+        """dropout_any: the masks of one site in one of _noise's three forms -> (the flat u8 tensor serl_mlp_noise takes -- layer l
+        at batch * sum_{j<l} d_j, rows of d_l bytes -- and its batch)"""
+        dims = self.critic_dims if MLP_SITE_NETWORK[site] == "critic" else self.policy_dims
+        if isinstance(t, (list, tuple)):
+            rows = rows or int(t[0].shape[0])
+            if [tuple(x.shape) for x in t] != [(rows, d) for d in dims]:
+                raise ValueError(f"drop_mask_{site}: expected one u8[batch, width] per layer of widths {list(dims)}, the same batch at every "
+                                 f"site, got {[tuple(x.shape) for x in t]}")
+            return torch.cat([x.to(device=self.device, dtype=torch.uint8).reshape(-1) for x in t]), rows
+        rows = rows or (int(t.shape[1]) if t.dim() == 3 else t.numel() // sum(dims))
+        if tuple(t.shape) not in ((rows * sum(dims),), (len(dims), rows, dims[0])) or t.numel() != rows * sum(dims):
+            raise ValueError(f"drop_mask_{site}: expected {rows * sum(dims)} bytes, one u8[batch, width] per layer of widths {list(dims)} "
+                             f"flat or stacked, got {tuple(t.shape)}")
+        return t.reshape(-1), rows
 
     def update_critics(self, batch, noise=None):
         _lib.check(self.L.serl_agent_update_critics(self._h, C.byref(batch.cstruct), self._noise(noise), self._stream()))

@@ -218,6 +218,11 @@ class DrQAgent:
         (csrc/head_wide.h: one wave per sample, up to 4 columns per lane) and the policy head is a launch of its own behind the head
         GEMM; up to 64 the call gives the agent the call without the switch gives.  Without it a width above 64 is refused by the
         library, as always; 257 and a switch that is no bool are refused from the arguments alone.
+        mlp_dropout="any": the rates are read as with True and served beside every switch above -- mlp_shapes, mlp_plain (a plain
+        layer is act(Dropout(Dense(x) + b))), mlp_ragged, mlp_wide and use_proprio=False under image_only=True -- on the Dropout
+        rows of each family (serl_agent_opts.dropout_any); beside std_parameterization="fixed" it stays refused.  An injected
+        drop_mask_<site> is then one u8[batch, width] per layer of that network (AgentCore._noise).  Another value than False,
+        True or "any" is a ValueError.
         Frame stacks: the sample observation carries T = observations[image_key].shape[0] frames and a (T, S) state, as
         ChunkingWrapper(obs_horizon=T) produces them; EncodingWrapper(enable_stacking=True) folds them into the channels and the
         proprio width (common/encoding.py:39-44,58-64).  T in 1..4 with encoder_type="small"; the pretrained ResNet-10 cannot take

@@ -158,6 +158,10 @@ def net_spec_of(core) -> NetSpec:
         kw["wide_actions"] = int(core.L.serl_agent_wide_actions(core._h)) == 1
     elif hasattr(core, "wide_actions"):
         kw["wide_actions"] = bool(core.wide_actions)
+    if getattr(core, "_h", None) is not None and hasattr(core, "L"):      # ... and whether Dropout is served at every shape
+        kw["dropout_any"] = int(core.L.serl_agent_dropout_any(core._h)) == 1
+    elif hasattr(core, "dropout_any"):
+        kw["dropout_any"] = bool(core.dropout_any)
     return NetSpec(hidden=int(getattr(core.cfg, "hidden", 256)), **kw)
 
 

@@ -50,6 +50,8 @@ class SACAgent(DrQAgent):
         mlp_ragged=True admits any width in [1, 1024] wherever hidden_dims is read, e.g. TD3's [400, 300] (create_drq's docstring).
         mlp_wide=True ends every width at 4096 instead of 1024, e.g. a REDQ critic of [2048, 2048] (create_drq's docstring).
         wide_actions=True ends the action width at 256 instead of 64, e.g. 7 joints x 10 steps of an action chunk (create_drq's docstring).
+        mlp_dropout="any" reads the rates as True does and serves them beside every other switch above but policy_fixed's "fixed":
+        any depth and widths, LayerNorm-free networks, ragged and wide widths (create_drq's docstring).
         param_init: "numpy" (default) or "reference" (the reference's own initialisers and keys, utils/init_ref.py)."""
         pk = policy_kwargs or {}
         A = int(np.asarray(actions).shape[-1])

@@ -44,8 +44,13 @@ class CallNoise:
                 out.update(q_actor=keys.k_q_actor)
         return {site: k for site, k in out.items() if rates[MLP_SITE_NETWORK[site]] > 0}
 
+    def _site_dims(self, site):
+        """the true widths of the layers of the site's network ((hidden, hidden) for a core without the lists)"""
+        dims = getattr(self.core, MLP_SITE_NETWORK[site] + "_dims", None)
+        return tuple(dims) if dims else (int(self.core.cfg.hidden),) * 2
+
     def _layer_keys(self, site, rng):
-        return np.stack([J.flax_make_rng(rng, self.mlp_dropout_path(MLP_SITE_NETWORK[site], l), 1) for l in (0, 1)])
+        return np.stack([J.flax_make_rng(rng, self.mlp_dropout_path(MLP_SITE_NETWORK[site], l), 1) for l in range(len(self._site_dims(site)))])
 
     def _buffers(self, rows, A, D, n_cam):
         if rows not in self.bufs:
@@ -106,15 +111,19 @@ class CallNoise:
                 noise[mask] = nb[mask]
 
         def mlp_draws(site, rng, row0=0, n=rows):
-            """the site's two keep-masks u8[2, rows, hidden]: local rows [row0, row0 + n) <- rows [lo, lo + n) of each layer's draw"""
-            name, h = "drop_mask_" + site, int(cfg.hidden)
+            """the site's keep-masks, layer l a u8[rows, d_l] at rows * sum_{j<l} d_j (u8[layers, rows, d] where every width is d):
+            local rows [row0, row0 + n) <- rows [lo, lo + n) of each layer's draw"""
+            name, dims = "drop_mask_" + site, self._site_dims(site)
             if name not in nb:
                 import torch
-                nb[name] = torch.empty((2, rows, h), dtype=torch.uint8, device=self.core.device)
+                shape = (len(dims), rows, dims[0]) if len(set(dims)) == 1 else (rows * sum(dims),)
+                nb[name] = torch.empty(shape, dtype=torch.uint8, device=self.core.device)
             g = n if shard is None else shard[1]
             p = 1.0 - self.mlp_rates()[MLP_SITE_NETWORK[site]]
-            for l, k in enumerate(self._layer_keys(site, rng)):
-                jobs.append(J.job(J.BERNOULLI_U8, k, g * h, nb[name].data_ptr() + (l * rows + row0) * h, first=lo * h, count=n * h, p=p))
+            below = 0
+            for h, k in zip(dims, self._layer_keys(site, rng)):
+                jobs.append(J.job(J.BERNOULLI_U8, k, g * h, nb[name].data_ptr() + below + row0 * h, first=lo * h, count=n * h, p=p))
+                below += rows * h
             noise[name] = nb[name]
 
         if want_critic:

@@ -951,7 +951,9 @@ void mlp_sites(serl_agent* a, int site, double rate, int off, int cnt, long glob
   const serl_mlp_noise& z = a->mlp_cur;
   const bool critic = site == SERL_SITE_Q_TARGET || site == SERL_SITE_Q_ONLINE || site == SERL_SITE_Q_ACTOR;
   const serl_mlp_opts& net = critic ? a->opts.critic : a->opts.policy;
-  const int* dims = net.dims;
+  // the masks and the keys' arrays are laid out by TRUE widths: layer l holds rows of true_dims[l] bytes, what the reference's
+  // bernoulli(key, keep, (rows, width)) draws (net.dims: the storage widths; equal on the 64 grid)
+  const int* dims = a->true_dims[critic ? 0 : 1];
   const int n = net.n_layers;
   long below = 0;   // mask elements per batch row of the layers in front of layer l
   for (int l = 0; l < n; below += dims[l], ++l) {
@@ -1098,6 +1100,7 @@ int serl_agent_mlp_dims(serl_agent* a, int network, int dims[SERL_MAX_MLP_LAYERS
 // serl_agent_opts.wide_widths as the agent was created with it
 int serl_agent_wide_widths(serl_agent* a) { return a ? a->opts.wide_widths : -1; }
 int serl_agent_wide_actions(serl_agent* a) { return a ? a->opts.wide_actions : -1; }
+int serl_agent_dropout_any(serl_agent* a) { return a ? a->opts.dropout_any : -1; }
 
 // Every entry point's agent (serl_mi355.h, NETWORK OPTIONS).  The two networks are built from separate kwargs (sac.py:516-524,
 // drq.py:188-207), so their options are independent: mlp.py:19-31 applies `activations` behind every layer and loops over
@@ -1109,7 +1112,13 @@ static int create_agent(const serl_agent_cfg* cfg, const serl_agent_opts* opts, 
   const float* fixed_std = opts->fixed_std;
   SERL_REQUIRE(critic.no_layer_norm == 0 || critic.no_layer_norm == 1, "critic no_layer_norm %d is not 0 (LayerNorm) or 1 (none)", critic.no_layer_norm);
   SERL_REQUIRE(policy.no_layer_norm == 0 || policy.no_layer_norm == 1, "policy no_layer_norm %d is not 0 (LayerNorm) or 1 (none)", policy.no_layer_norm);
-  SERL_REQUIRE((!critic.no_layer_norm || !(critic.dropout > 0.0)) && (!policy.no_layer_norm || !(policy.dropout > 0.0)),
+  // dropout_any 1: Dropout at every served shape -- the DROP rows of the plain, ragged and wide families (heads.hip, ln_wide.h) and
+  // masks laid out by true widths (mlp_sites); only the Dropout-beside-X requirements below are skipped.  0: every check and
+  // message is what it was
+  SERL_REQUIRE(opts->dropout_any == 0 || opts->dropout_any == 1, "dropout_any %d is not 0 (Dropout in two LayerNorm layers of one width on "
+               "the 64 grid) or 1 (at every served shape)", opts->dropout_any);
+  const bool any = opts->dropout_any == 1;
+  SERL_REQUIRE(any || ((!critic.no_layer_norm || !(critic.dropout > 0.0)) && (!policy.no_layer_norm || !(policy.dropout > 0.0))),
                "Dropout in an MLP without LayerNorm is not served");
   // (the keep probability float32(1 - rate) must itself lie below 1 and above 0)
   SERL_REQUIRE(critic.dropout >= 0.0 && (float)(1.0 - critic.dropout) > 0.f, "critic_dropout %g: a Dropout rate lies in [0, 1)", critic.dropout);
@@ -1117,9 +1126,9 @@ static int create_agent(const serl_agent_cfg* cfg, const serl_agent_opts* opts, 
   // what the argument lists could not say and opts can: Dropout is served where it always was
   if (critic.dropout > 0.0 || policy.dropout > 0.0) {
     // (the keep-masks and per-layer keys of serl_mlp_noise are laid out for two layers of cfg->hidden)
-    SERL_REQUIRE(critic.n_layers == 0 && policy.n_layers == 0, "dropout %g / %g with n_layers %d / %d (critic / policy): Dropout is served with "
+    SERL_REQUIRE(any || (critic.n_layers == 0 && policy.n_layers == 0), "dropout %g / %g with n_layers %d / %d (critic / policy): Dropout is served with "
                  "n_layers 0 in both networks, two layers of cfg->hidden", critic.dropout, policy.dropout, critic.n_layers, policy.n_layers);
-    SERL_REQUIRE(!critic.no_layer_norm && !policy.no_layer_norm, "dropout %g / %g with no_layer_norm %d / %d (critic / policy): Dropout is "
+    SERL_REQUIRE(any || (!critic.no_layer_norm && !policy.no_layer_norm), "dropout %g / %g with no_layer_norm %d / %d (critic / policy): Dropout is "
                  "served in agents whose two networks have their LayerNorm", critic.dropout, policy.dropout, critic.no_layer_norm, policy.no_layer_norm);
     SERL_REQUIRE(std_param != SERL_STD_FIXED, "dropout %g / %g (critic / policy) with std_param SERL_STD_FIXED (3): Dropout is served in "
                  "agents whose policy head has std leaves", critic.dropout, policy.dropout);
@@ -1127,7 +1136,7 @@ static int create_agent(const serl_agent_cfg* cfg, const serl_agent_opts* opts, 
   SERL_REQUIRE(cfg->n_cam >= 0 && cfg->n_cam <= SERL_MAX_CAMS, "n_cam %d not in [0,%d]", cfg->n_cam, SERL_MAX_CAMS);
   SERL_REQUIRE(opts->no_proprio == 0 || opts->no_proprio == 1, "no_proprio %d is not 0 (the proprio branch) or 1 (image codes alone)", opts->no_proprio);
   SERL_REQUIRE(!opts->no_proprio || cfg->n_cam > 0, "no_proprio 1 with n_cam 0: a state-only agent has no EncodingWrapper, its input is the state");
-  if (opts->no_proprio && (critic.dropout > 0.0 || policy.dropout > 0.0)) {
+  if (!any && opts->no_proprio && (critic.dropout > 0.0 || policy.dropout > 0.0)) {
     set_error("dropout %g / %g (critic / policy) with no_proprio 1: Dropout in the MLPs is served in agents with the proprio branch",
               critic.dropout, policy.dropout);
     return SERL_ERR_UNSUPPORTED;
@@ -1173,10 +1182,10 @@ static int create_agent(const serl_agent_cfg* cfg, const serl_agent_opts* opts, 
     }
   }
   // (the keep-masks and the Dropout rows are those of the one-wave rows; widest > 1024 implies wide here)
-  SERL_REQUIRE(widest <= 1024 || !(critic.dropout > 0.0 || policy.dropout > 0.0), "dropout %g / %g (critic / policy) beside an MLP width of %d "
+  SERL_REQUIRE(any || widest <= 1024 || !(critic.dropout > 0.0 || policy.dropout > 0.0), "dropout %g / %g (critic / policy) beside an MLP width of %d "
                "under wide_widths 1: Dropout is served at widths up to 1024", critic.dropout, policy.dropout, widest);
   // (the jax-keyed keep-masks are laid out for [rows][h] with h on the grid; off_grid implies ragged here)
-  SERL_REQUIRE(!off_grid || !(critic.dropout > 0.0 || policy.dropout > 0.0), "dropout %g / %g (critic / policy) beside an MLP width off the 64 grid "
+  SERL_REQUIRE(any || !off_grid || !(critic.dropout > 0.0 || policy.dropout > 0.0), "dropout %g / %g (critic / policy) beside an MLP width off the 64 grid "
                "under ragged_widths 1: Dropout is served at widths that are multiples of 64", critic.dropout, policy.dropout);
   SERL_REQUIRE(cfg->bottleneck == 256, "bottleneck must be 256 (got %d): the reference fixes bottleneck_dim=256 in create_drq", cfg->bottleneck);
   SERL_REQUIRE(cfg->proprio_dim == 64, "proprio_dim must be 64");

@@ -303,11 +303,47 @@ __device__ __forceinline__ void ln_dropout(const LnDrop& d, long lrow, int c0, f
     v[j] = keep ? v[j] / d.keep : 0.f;
   }
 }
+// One keep decision at flat element index `idx` of the launch's instance, from its mask, its key or its hash stream (uniform mode).
+// `n`: the elements of the whole array the key draws; `e`: idx's place in that array and in the hash stream.
+__device__ __forceinline__ bool ln_keep_at(const LnDrop& d, long idx, uint64_t n, uint64_t e, uint32_t thr) {
+  if (d.mode == kLnDropMask) return d.mask[idx] != 0;
+  if (d.mode == kLnDropKey) return bits_to_unit(random_bits_at(d.key[0], d.key[1], n, e)) < d.keep;
+  return (uint32_t)(mix64(d.seed ^ mix64(e)) & 0xFFFFFFull) < thr;
+}
+// Dropout at a TRUE width Nt <= D read at run time: the ragged LayerNorm rows and the plain rows (ln_row<.., DROP, RAGGED>,
+// plain_row<.., DROP>).  Element (row r, true column c) is decision r * Nt + c -- the shape bernoulli(key, keep, (rows, Nt)) draws,
+// and the layout of the u8 mask; with Nt == D these are ln_dropout's decisions.  A padding column [Nt, D) draws nothing and reads
+// no mask byte: its address is clamped to the row's last true column, the load is unconditional and the value is selected to 0
+// afterwards.  The key's decisions are taken one column after the other in a loop that is not unrolled and
+// kept as bits: one Threefry state in registers whatever VPL is.
+template <int VPL, bool BLOCKED>
+__device__ __forceinline__ void ln_dropout_n(const LnDrop& d, long lrow, int c0, int Nt, float (&v)[VPL]) {
+  constexpr int kStep = kLnStep<BLOCKED>;
+  const uint32_t thr = (uint32_t)(d.keep * 16777216.f);
+  const uint64_t n = (uint64_t)d.total_rows * (uint64_t)Nt, e0 = (uint64_t)(d.row0 + lrow) * (uint64_t)Nt;
+  uint32_t bits = 0;
+  if (d.mode == kLnDropKey) {
+#pragma unroll 1
+    for (int j = 0; j < VPL; ++j) {
+      const int cc = min(c0 + kStep * j, Nt - 1);
+      bits |= (ln_keep_at(d, 0, n, e0 + (uint64_t)cc, thr) ? 1u : 0u) << j;
+    }
+  } else {
+#pragma unroll
+    for (int j = 0; j < VPL; ++j) {
+      const int cc = min(c0 + kStep * j, Nt - 1);
+      bits |= (ln_keep_at(d, lrow * Nt + cc, n, e0 + (uint64_t)cc, thr) ? 1u : 0u) << j;
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < VPL; ++j) v[j] = ((bits >> j) & 1u) && c0 + kStep * j < Nt ? v[j] / d.keep : 0.f;
+}
 // Returns the fused row-dot (dot_out's value, in every lane; 0 without one).
 // DROP: the instantiation of the launches that carry an instance with Dropout (ln_fwd_drop_kernel); the rows of every other launch
 // are the DROP = false instantiation, whose text -- and therefore whose contraction into fused multiply-adds -- is what it was.
 // RAGGED: the instantiation of a zero-padded row of true width a.d < D (heads.h): the statistics divide by a.d.  Nothing else
 // differs: the pads of the bias and of the slabs are 0 and add nothing to the sums, and gamma == beta == 0 there gives y == act(0) == 0.
+// DROP and RAGGED (ln_fwd_ragged_drop_kernel): the decisions of ln_dropout_n, indexed by the true width; xhat is kept 0 in the pads.
 template <int VPL, bool BLOCKED, bool DROP = false, bool RAGGED = false>
 __device__ __forceinline__ float ln_row(const LnFwdArgs& a, int row, int lane) {
   constexpr int D = 64 * VPL, kStep = kLnStep<BLOCKED>;
@@ -319,7 +355,10 @@ __device__ __forceinline__ float ln_row(const LnFwdArgs& a, int row, int lane) {
   float v[VPL];
   ln_gather<VPL, BLOCKED>(a, base, pb, v);
   if constexpr (DROP) {
-    if (a.drop.mode != kLnDropNone) ln_dropout<VPL, BLOCKED>(a.drop, lrow, c0, v);   // (uniform: the launch's instance)
+    if (a.drop.mode != kLnDropNone) {   // (uniform: the launch's instance)
+      if constexpr (RAGGED) ln_dropout_n<VPL, BLOCKED>(a.drop, lrow, c0, a.d, v);
+      else ln_dropout<VPL, BLOCKED>(a.drop, lrow, c0, v);
+    }
   }
   float s1 = 0.f, s2 = 0.f;
 #pragma unroll
@@ -331,7 +370,8 @@ __device__ __forceinline__ float ln_row(const LnFwdArgs& a, int row, int lane) {
   float d = 0.f;
 #pragma unroll
   for (int j = 0; j < VPL; ++j) {   // v: the row's values, then its pre-activations, then y
-    const float xh = (v[j] - mean) * rstd;
+    float xh = (v[j] - mean) * rstd;
+    if constexpr (DROP && RAGGED) xh = c0 + kStep * j < a.d ? xh : 0.f;
     v[j] = xh * a.gamma[pb + kStep * j] + a.beta[pb + kStep * j];
     if (a.xhat) a.xhat[(long)row * D + c0 + kStep * j] = xh;
   }
@@ -358,7 +398,9 @@ __device__ __forceinline__ float ln_row(const LnFwdArgs& a, int row, int lane) {
 // ascending order, then the xor butterfly.  What the backward reads: y (tanh and relu differentiate from it) and, for swish, the
 // pre-activation, which goes to the layer's xhat buffer (a plain layer has no normalised row to keep there); rstd is not written.
 // A launch is plain when its instances carry no gamma (LnFwdArgs); a row kernel of its own, so that ln_row's text stays what it is.
-template <int VPL, bool BLOCKED>
+// DROP (plain_fwd_drop_kernel; mlp.py:27-31 without the LayerNorm: y = act(Dropout(Dense(x) + b))): the decisions of ln_dropout_n at
+// the row's true width, in front of everything else -- xhat keeps the MASKED pre-activation, and the rider reads the masked row.
+template <int VPL, bool BLOCKED, bool DROP = false>
 __device__ __forceinline__ float plain_row(const LnFwdArgs& a, int row, int lane) {
   constexpr int D = 64 * VPL, kStep = kLnStep<BLOCKED>;
   const int grp = row / a.rows_per_group;
@@ -368,6 +410,9 @@ __device__ __forceinline__ float plain_row(const LnFwdArgs& a, int row, int lane
   const long pb = (long)grp * a.pstride + c0;
   float v[VPL];
   ln_gather<VPL, BLOCKED>(a, base, pb, v);
+  if constexpr (DROP) {
+    if (a.drop.mode != kLnDropNone) ln_dropout_n<VPL, BLOCKED>(a.drop, lrow, c0, a.d ? a.d : D, v);   // (uniform: the launch's instance)
+  }
   if (a.xhat) {
 #pragma unroll
     for (int j = 0; j < VPL; ++j) a.xhat[(long)row * D + c0 + kStep * j] = v[j];
@@ -1058,6 +1103,22 @@ __global__ __launch_bounds__(256) void plain_fwd_kernel(Multi<LnFwdArgs> mv) {
   plain_row<VPL, BLOCKED>(a, row, lane);
 }
 
+// ... ragged rows / plain rows of a launch in which an instance has Dropout
+template <int VPL, bool BLOCKED>
+__global__ __launch_bounds__(256) void ln_fwd_ragged_drop_kernel(Multi<LnFwdArgs> mv) {
+  const LnFwdArgs& a = mv.v[blockIdx.y];
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (row >= a.rows) return;
+  ln_row<VPL, BLOCKED, true, true>(a, row, lane);
+}
+template <int VPL, bool BLOCKED>
+__global__ __launch_bounds__(256) void plain_fwd_drop_kernel(Multi<LnFwdArgs> mv) {
+  const LnFwdArgs& a = mv.v[blockIdx.y];
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (row >= a.rows) return;
+  plain_row<VPL, BLOCKED, true>(a, row, lane);
+}
+
 // The reward classifier's head closed for labelling (vice.py:546,594: rewards = (sigmoid(classifier(next_obs)) >= 0.5) * 1.0): the
 // LayerNorm -> ReLU -> Dense(1) row of ln_row at width 256 (one row per wave; the logit goes to a.dot_out as in the train=False
 // forward), then p = 1 / (1 + expf(-logit)) in fp32 (as jax.nn.sigmoid: a logit just below zero may round to 0.5) and
@@ -1097,8 +1158,8 @@ int label_rows(const LnFwdArgs& a, float* label, float* mean, int* ctr, hipStrea
 // at every other.  Above 1024 one workgroup of four waves owns a row (ln_wide.h, included below): ln_fwd_multi and ln_bwd_multi hand
 // such a launch over, one for one.
 #define SERL_LN_WIDTH_OK(D) ((D) >= 64 && (D) <= 4096 && (D) % 64 == 0)
-int ln_wide_fwd(const Multi<LnFwdArgs>& mv, int n, int rows, int D, bool plain, hipStream_t stream);
-int ln_wide_bwd(const Multi<LnBwdArgs>& mv, int n, int rows, int D, bool plain, const LossArgs& loss, hipStream_t stream);
+int ln_wide_fwd(const Multi<LnFwdArgs>& mv, int n, int rows, int D, bool plain, bool drop, hipStream_t stream);
+int ln_wide_bwd(const Multi<LnBwdArgs>& mv, int n, int rows, int D, bool plain, bool drop, const LossArgs& loss, hipStream_t stream);
 // a launch's Dropout description: none, or a keep probability in (0, 1] with the mask tensor / the window of `rows` rows inside
 // the array the key draws
 static bool ln_drop_ok(const LnDrop& d, long rows) {
@@ -1141,17 +1202,15 @@ int ln_fwd_multi(const LnFwdArgs* as, int n, int D, hipStream_t stream) {
                  "LayerNorm row: instance %d %s a LayerNorm and instance 0 %s; plain and LayerNorm rows do not share a launch", i,
                  as[i].gamma ? "has" : "lacks", as[0].gamma ? "has" : "lacks");
   }
-  if (D > 1024) {   // one workgroup per row (ln_wide.h)
-    SERL_REQUIRE(!drop, "LayerNorm row of width %d with Dropout: served up to 1024", D);
-    return ln_wide_fwd(mv, n, rows, D, !as[0].gamma, stream);
-  }
+  if (D > 1024) return ln_wide_fwd(mv, n, rows, D, !as[0].gamma, drop, stream);   // one workgroup per row (ln_wide.h)
   dim3 grid(cdiv(rows, 4), n);
+  // (a launch in which an instance carries Dropout is the DROP instantiation of its family; every other launch is what it was)
   if (!as[0].gamma) {
-    SERL_REQUIRE(!drop, "plain row (no LayerNorm) with Dropout: not served");
-    SERL_LN_LAUNCH(D, (plain_fwd_kernel<1, false>), (plain_fwd_kernel<4, true>), plain_fwd_kernel, grid, dim3(256), 0, stream, mv)
+    if (drop) SERL_LN_LAUNCH(D, (plain_fwd_drop_kernel<1, false>), (plain_fwd_drop_kernel<4, true>), plain_fwd_drop_kernel, grid, dim3(256), 0, stream, mv)
+    else SERL_LN_LAUNCH(D, (plain_fwd_kernel<1, false>), (plain_fwd_kernel<4, true>), plain_fwd_kernel, grid, dim3(256), 0, stream, mv)
   } else if (as[0].d) {
-    SERL_REQUIRE(!drop, "ragged LayerNorm row (true width %d in %d) with Dropout: not served", as[0].d, D);
-    SERL_LN_LAUNCH(D, (ln_fwd_ragged_kernel<1, false>), (ln_fwd_ragged_kernel<4, true>), ln_fwd_ragged_kernel, grid, dim3(256), 0, stream, mv)
+    if (drop) SERL_LN_LAUNCH(D, (ln_fwd_ragged_drop_kernel<1, false>), (ln_fwd_ragged_drop_kernel<4, true>), ln_fwd_ragged_drop_kernel, grid, dim3(256), 0, stream, mv)
+    else SERL_LN_LAUNCH(D, (ln_fwd_ragged_kernel<1, false>), (ln_fwd_ragged_kernel<4, true>), ln_fwd_ragged_kernel, grid, dim3(256), 0, stream, mv)
   } else if (drop) SERL_LN_LAUNCH(D, (ln_fwd_drop_kernel<1, false>), (ln_fwd_drop_kernel<4, true>), ln_fwd_drop_kernel, grid, dim3(256), 0, stream, mv)
   else SERL_LN_LAUNCH(D, (ln_fwd_kernel<1, false>), (ln_fwd_kernel<4, true>), ln_fwd_kernel, grid, dim3(256), 0, stream, mv)
   SERL_HIP(hipGetLastError());
@@ -1390,8 +1449,17 @@ __device__ __forceinline__ void ln_bwd_row(const LnBwdArgs& a, const LossArgs& L
   if constexpr (RAGGED) { const float inv = 1.0f / (float)a.d; m1 = s1 * inv; m2 = s2 * inv; }
   else { m1 = s1 * (1.0f / D); m2 = s2 * (1.0f / D); }
   const float rstd = a.rstd[row];
-  if constexpr (RAGGED) {
-    static_assert(!DROP, "a ragged row carries no Dropout");
+  if constexpr (RAGGED && DROP) {   // ... the forward's decision by the true width (ln_dropout_n, which leaves the pads 0)
+#pragma unroll
+    for (int j = 0; j < VPL; ++j) dxh[j] = rstd * (dxh[j] - m1 - xh[j] * m2);
+    if (a.drop.mode != kLnDropNone) ln_dropout_n<VPL, BLOCKED>(a.drop, lr, c0, a.d, dxh);
+#pragma unroll
+    for (int j = 0; j < VPL; ++j) {
+      const int col = c0 + kLnStep<BLOCKED> * j;
+      a.dx[(long)row * D + col] = col < a.d ? dxh[j] : 0.f;
+      a.dg[(long)row * D + col] = dg[j];
+    }
+  } else if constexpr (RAGGED) {
 #pragma unroll
     for (int j = 0; j < VPL; ++j) {
       const int col = c0 + kLnStep<BLOCKED> * j;
@@ -1423,7 +1491,9 @@ __device__ __forceinline__ void ln_bwd_row(const LnBwdArgs& a, const LossArgs& L
 // this path alone).  dy in ln_bwd_row's three forms: a tensor, the rank-1 dq (x) w, and dq derived inline from the launch's loss.
 // No row statistics, no exchange between lanes.  dg and dpre coincide: the row writes dx alone, and the bias's column sum and the
 // weight and input gradients all read it (layer_colsum, dense_layer.h); a.dg, a.rstd, a.gamma and a.beta are not touched.
-template <int VPL, bool BLOCKED>
+// DROP (plain_bwd_drop_kernel): y and xhat are those of the masked pre-activation, and dpre = dy act'(masked pre) (kept ? 1 / keep : 0),
+// the forward's decision stated again, in all three forms of dy.
+template <int VPL, bool BLOCKED, bool DROP = false>
 __device__ __forceinline__ void plain_bwd_row(const LnBwdArgs& a, const LossArgs& L, int row, int lane) {
   const int grp = row / a.rows_per_group;
   constexpr int D = VPL * 64, kStep = kLnStep<BLOCKED>;
@@ -1450,6 +1520,9 @@ __device__ __forceinline__ void plain_bwd_row(const LnBwdArgs& a, const LossArgs
       const float sg = sigmoid_stable(a.xhat[(long)row * D + c0 + kStep * j]);
       dg[j] *= sg + y[j] * (1.f - sg);
     }
+  }
+  if constexpr (DROP) {
+    if (a.drop.mode != kLnDropNone) ln_dropout_n<VPL, BLOCKED>(a.drop, lr, c0, a.d ? a.d : D, dg);
   }
 #pragma unroll
   for (int j = 0; j < VPL; ++j) a.dx[(long)row * D + c0 + kStep * j] = dg[j];
@@ -1509,6 +1582,26 @@ __global__ __launch_bounds__(256) void plain_bwd_kernel(Multi<LnBwdArgs> mv, Los
   plain_bwd_row<VPL, BLOCKED>(a, loss, row, lane);
 }
 
+// ... ragged rows / plain rows of a launch in which an instance has Dropout; the critic-loss rider in the same place
+template <int VPL, bool BLOCKED>
+__global__ __launch_bounds__(256) void ln_bwd_ragged_drop_kernel(Multi<LnBwdArgs> mv, LossArgs loss) {
+  __shared__ float red[4][256];
+  if (loss.on && blockIdx.y == 0 && blockIdx.x == gridDim.x - 1) { critic_loss_body(loss, red); return; }
+  const LnBwdArgs& a = mv.v[blockIdx.y];
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (row >= a.rows) return;
+  ln_bwd_row<VPL, BLOCKED, true, true>(a, loss, row, lane);
+}
+template <int VPL, bool BLOCKED>
+__global__ __launch_bounds__(256) void plain_bwd_drop_kernel(Multi<LnBwdArgs> mv, LossArgs loss) {
+  __shared__ float red[4][256];
+  if (loss.on && blockIdx.y == 0 && blockIdx.x == gridDim.x - 1) { critic_loss_body(loss, red); return; }
+  const LnBwdArgs& a = mv.v[blockIdx.y];
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (row >= a.rows) return;
+  plain_bwd_row<VPL, BLOCKED, true>(a, loss, row, lane);
+}
+
 // One instance of a default width without a rider (most LayerNorm backward launches of the default agent, BC, the classifier):
 // the same row behind a launch that carries one LnBwdArgs (ln_bwd_kernel's arguments are four of them and the loss).  Measured:
 // with ln_bwd_kernel in its place the update step is 0.36 % slower (profiles/README.md).
@@ -1529,9 +1622,9 @@ int ln_bwd_multi(const LnBwdArgs* as, int n, const LossArgs& loss, hipStream_t s
   const auto mixes = [](int D) { return D == 64 || D == 256; };
   for (int i = 0; i < n; ++i) {
     SERL_REQUIRE(SERL_LN_WIDTH_OK(as[i].D), "LayerNorm width %d unsupported (a multiple of 64 in [64, 4096])", as[i].D);
-    // (a ragged launch is one MLP layer: one storage width, one true width, no Dropout)
-    SERL_REQUIRE(as[i].d >= 0 && as[i].d < as[i].D && as[i].d == as[0].d && (!as[i].d || (as[i].D == as[0].D && as[i].drop.mode == kLnDropNone)),
-                 "LayerNorm backward: instance %d has the true width %d in rows of %d, instance 0 %d in rows of %d; or a ragged row with Dropout",
+    // (a ragged launch is one MLP layer: one storage width, one true width)
+    SERL_REQUIRE(as[i].d >= 0 && as[i].d < as[i].D && as[i].d == as[0].d && (!as[i].d || as[i].D == as[0].D),
+                 "LayerNorm backward: instance %d has the true width %d in rows of %d, instance 0 %d in rows of %d",
                  i, as[i].d, as[i].D, as[0].d, as[0].D);
     SERL_REQUIRE(!as[i].dq_inline || (loss.on && as[i].dq_w && as[i].rows == loss.E * loss.B && as[i].rows_per_group == loss.B),
                  "inline dQ needs the loss arguments of the launch");
@@ -1539,9 +1632,9 @@ int ln_bwd_multi(const LnBwdArgs* as, int n, const LossArgs& loss, hipStream_t s
     // (... and a plain row reads the pre-activation its forward kept in xhat)
     SERL_REQUIRE(as[i].act >= 0 && as[i].act < kActCount && (as[i].act != kActSwish || (as[i].gamma ? as[i].beta : as[i].xhat)),
                  "LayerNorm backward: activation code %d is not tanh (0), relu (1) or swish (2), or swish without beta", as[i].act);
-    // (the instances of a plain launch are evaluations of one MLP layer: no LayerNorm in any, one width, no Dropout)
-    SERL_REQUIRE((as[i].gamma == nullptr) == (as[0].gamma == nullptr) && (as[i].gamma || (as[i].D == as[0].D && as[i].drop.mode == kLnDropNone)),
-                 "LayerNorm backward: plain and LayerNorm rows in one launch, or plain rows of widths %d and %d, or with Dropout", as[0].D, as[i].D);
+    // (the instances of a plain launch are evaluations of one MLP layer: no LayerNorm in any, one width)
+    SERL_REQUIRE((as[i].gamma == nullptr) == (as[0].gamma == nullptr) && (as[i].gamma || as[i].D == as[0].D),
+                 "LayerNorm backward: plain and LayerNorm rows in one launch, or plain rows of widths %d and %d", as[0].D, as[i].D);
     SERL_REQUIRE(ln_drop_ok(as[i].drop, as[i].rows_per_group), "LayerNorm backward: bad Dropout description (mode %d, keep %g)", as[i].drop.mode, as[i].drop.keep);
     mv.v[i] = as[i];
     rows = std::max(rows, as[i].rows);
@@ -1550,12 +1643,12 @@ int ln_bwd_multi(const LnBwdArgs* as, int n, const LossArgs& loss, hipStream_t s
     SERL_REQUIRE(as[i].D == as[0].D || (mixes(as[i].D) && mixes(as[0].D)),
                  "LayerNorm widths %d and %d in one launch: widths other than 64 and 256 do not mix", as[0].D, as[i].D);
   }
-  if (as[0].D > 1024) {   // one workgroup per row (ln_wide.h); such a width comes from one MLP layer and is every instance's
-    SERL_REQUIRE(!drop, "LayerNorm backward of width %d with Dropout: served up to 1024", as[0].D);
-    return ln_wide_bwd(mv, n, rows, as[0].D, !as[0].gamma, loss, stream);
-  }
+  // one workgroup per row (ln_wide.h); such a width comes from one MLP layer and is every instance's
+  if (as[0].D > 1024) return ln_wide_bwd(mv, n, rows, as[0].D, !as[0].gamma, drop, loss, stream);
   const dim3 grid(cdiv(rows, 4) + (loss.on ? 1 : 0), n);
-  if (!as[0].gamma) SERL_LN_LAUNCH(as[0].D, (plain_bwd_kernel<1, false>), (plain_bwd_kernel<4, true>), plain_bwd_kernel, grid, dim3(256), 0, stream, mv, loss)
+  if (!as[0].gamma && drop) SERL_LN_LAUNCH(as[0].D, (plain_bwd_drop_kernel<1, false>), (plain_bwd_drop_kernel<4, true>), plain_bwd_drop_kernel, grid, dim3(256), 0, stream, mv, loss)
+  else if (!as[0].gamma) SERL_LN_LAUNCH(as[0].D, (plain_bwd_kernel<1, false>), (plain_bwd_kernel<4, true>), plain_bwd_kernel, grid, dim3(256), 0, stream, mv, loss)
+  else if (as[0].d && drop) SERL_LN_LAUNCH(as[0].D, (ln_bwd_ragged_drop_kernel<1, false>), (ln_bwd_ragged_drop_kernel<4, true>), ln_bwd_ragged_drop_kernel, grid, dim3(256), 0, stream, mv, loss)
   else if (as[0].d) SERL_LN_LAUNCH(as[0].D, (ln_bwd_ragged_kernel<1, false>), (ln_bwd_ragged_kernel<4, true>), ln_bwd_ragged_kernel, grid, dim3(256), 0, stream, mv, loss)
   else if (drop) SERL_LN_LAUNCH(as[0].D, (ln_bwd_drop_kernel<kLnMixed, false>), (ln_bwd_drop_kernel<kLnMixed, false>), ln_bwd_drop_kernel, grid, dim3(256), 0, stream, mv, loss)
   else if (n == 1 && !loss.on && as[0].D == 256) SERL_LAUNCH_CHAIN((ln_bwd_one_kernel<4, true>), grid, dim3(256), 0, stream, as[0]);

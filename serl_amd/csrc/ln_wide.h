@@ -22,7 +22,13 @@
 // Forms: LayerNorm and plain (LN), ragged by a.d (the statistics divide by the true width, the pads stay exactly 0 -- a.d is read
 // at run time: a row of D live columns divides by D through the same instruction), tanh / relu / swish, xhat / rstd / the plain
 // pre-activation as the backward reads them, ln_gather's arithmetic per column (bias first, then the slabs in index order),
-// dy as a tensor, as the rank-1 dq (x) w and as dq_inline beside the critic-loss rider.  No Dropout: refused by the launchers.
+// dy as a tensor, as the rank-1 dq (x) w and as dq_inline beside the critic-loss rider.
+// Dropout (the DROP instantiations, launched when an instance of the launch carries a mask; every other launch runs the kernels it
+// always ran): a wave applies the keep decisions to the chunks it was dealt BEFORE the row sums go through LDS -- the forward row to
+// the gathered Dense output, the backward rows to dx, stating the forward's decision again.  Element (row r, true column c) is
+// decision r * Nt + c, Nt = a.d or D (ln_dropout_n of heads.hip); the tail chunk's and the pads' addresses are clamped, the load
+// is unconditional and the value selected afterwards.  A decision depends on (r, c) alone and the exchange is unchanged: a row's
+// bits still depend on D alone.  The key's decisions are taken in column order in a loop that is not unrolled.
 // The kernels are built without packed fp32 instructions (v_pk_*_f32).
 #pragma once
 
@@ -47,8 +53,34 @@ __device__ __forceinline__ void wide_sum2(float& s1, float& s2, float* x, int wa
   s2 = ((x[1] + x[3]) + x[5]) + x[7];
 }
 
-// The forward row (ln_row / plain_row of heads.hip at these widths).  x: 12 floats of LDS.
-template <int CPW, bool LN>
+// Dropout on a lane's CPW values of local row `lrow` (wide_col's columns; v's tail is 0 where the wave has no tail chunk)
+template <int CPW>
+__device__ __forceinline__ void wide_dropout(const LnDrop& d, long lrow, int c0, bool tail_ok, int Nt, float (&v)[CPW]) {
+  const uint32_t thr = (uint32_t)(d.keep * 16777216.f);
+  const uint64_t n = (uint64_t)d.total_rows * (uint64_t)Nt, e0 = (uint64_t)(d.row0 + lrow) * (uint64_t)Nt;
+  uint32_t bits = 0;
+  if (d.mode == kLnDropKey) {
+#pragma unroll 1
+    for (int j = 0; j < CPW; ++j) {
+      const int cc = min(wide_col<CPW>(j, c0, tail_ok), Nt - 1);
+      bits |= (ln_keep_at(d, 0, n, e0 + (uint64_t)cc, thr) ? 1u : 0u) << j;
+    }
+  } else {
+#pragma unroll
+    for (int j = 0; j < CPW; ++j) {
+      const int cc = min(wide_col<CPW>(j, c0, tail_ok), Nt - 1);
+      bits |= (ln_keep_at(d, lrow * Nt + cc, n, e0 + (uint64_t)cc, thr) ? 1u : 0u) << j;
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < CPW; ++j) {
+    const bool live = (j < CPW - 1 || tail_ok) && c0 + 256 * j < Nt;
+    v[j] = ((bits >> j) & 1u) && live ? v[j] / d.keep : 0.f;
+  }
+}
+
+// The forward row (ln_row / plain_row of heads.hip at these widths).  x: 12 floats of LDS.  DROP: see above.
+template <int CPW, bool LN, bool DROP = false>
 __device__ __forceinline__ void wide_row(const LnFwdArgs& a, int D, int row, int wave, int lane, float* x) {
   const bool tail_ok = wave + 4 * (CPW - 1) < (D >> 6);
   const int c0 = 64 * wave + lane;
@@ -66,6 +98,9 @@ __device__ __forceinline__ void wide_row(const LnFwdArgs& a, int D, int row, int
     for (int j = 0; j < CPW; ++j) v[j] += a.slabs[o + wide_col<CPW>(j, c0, tail_ok)];
   }
   v[CPW - 1] = tail_ok ? v[CPW - 1] : 0.f;
+  if constexpr (DROP) {
+    if (a.drop.mode != kLnDropNone) wide_dropout<CPW>(a.drop, lrow, c0, tail_ok, a.d ? a.d : D, v);   // (uniform: the launch's instance)
+  }
   float rstd = 0.f;
   if constexpr (LN) {
     float s1 = 0.f, s2 = 0.f;
@@ -77,7 +112,8 @@ __device__ __forceinline__ void wide_row(const LnFwdArgs& a, int D, int row, int
 #pragma unroll
     for (int j = 0; j < CPW; ++j) {   // v: the row's values, then its pre-activations, then y
       const int col = wide_col<CPW>(j, c0, tail_ok);
-      const float xh = (v[j] - mean) * rstd;
+      float xh = (v[j] - mean) * rstd;
+      if constexpr (DROP) xh = col < (a.d ? a.d : D) ? xh : 0.f;   // (xhat is kept 0 in a ragged row's pads)
       v[j] = xh * a.gamma[pb + col] + a.beta[pb + col];
       if (a.xhat && (j < CPW - 1 || tail_ok)) a.xhat[(long)row * D + col] = xh;
     }
@@ -116,6 +152,14 @@ SERL_WIDE_KERNEL void ln_wide_fwd_kernel(Multi<LnFwdArgs> mv, int D) {
   if ((int)blockIdx.x >= a.rows) return;   // (the whole workgroup)
   wide_row<CPW, LN>(a, D, blockIdx.x, threadIdx.x >> 6, threadIdx.x & 63, x);
 }
+// ... of a launch in which an instance has Dropout
+template <int CPW, bool LN>
+SERL_WIDE_KERNEL void ln_wide_fwd_drop_kernel(Multi<LnFwdArgs> mv, int D) {
+  __shared__ float x[12];
+  const LnFwdArgs& a = mv.v[blockIdx.y];
+  if ((int)blockIdx.x >= a.rows) return;
+  wide_row<CPW, LN, true>(a, D, blockIdx.x, threadIdx.x >> 6, threadIdx.x & 63, x);
+}
 
 // dy of a lane's column in the three forms of ln_bwd_row
 __device__ __forceinline__ float wide_dq(const LnBwdArgs& a, const LossArgs& L, int row, long lr) {
@@ -123,8 +167,9 @@ __device__ __forceinline__ float wide_dq(const LnBwdArgs& a, const LossArgs& L, 
   return a.dq_inline ? 2.f * (L.q[row] - redq_target(L, (int)lr)) * L.inv_norm : (a.dq ? a.dq[row] : a.dq_const);
 }
 
-// The backward LayerNorm row (ln_bwd_row of heads.hip at these widths; ragged by a.d).  x: 8 floats of LDS.
-template <int CPW>
+// The backward LayerNorm row (ln_bwd_row of heads.hip at these widths; ragged by a.d).  x: 8 floats of LDS.  DROP: dx wrt the
+// LayerNorm's input, then wrt the Dense output in front of the Dropout.
+template <int CPW, bool DROP = false>
 __device__ __forceinline__ void wide_bwd_row(const LnBwdArgs& a, const LossArgs& L, int row, int wave, int lane, float* x) {
   const int D = a.D, live = a.d ? a.d : D;
   const bool tail_ok = wave + 4 * (CPW - 1) < (D >> 6);
@@ -167,6 +212,20 @@ __device__ __forceinline__ void wide_bwd_row(const LnBwdArgs& a, const LossArgs&
   wide_sum2(s1, s2, x, wave, lane);
   const float inv = 1.0f / (float)live, m1 = s1 * inv, m2 = s2 * inv;
   const float rstd = a.rstd[row];
+  if constexpr (DROP) {
+#pragma unroll
+    for (int j = 0; j < CPW; ++j) dxh[j] = rstd * (dxh[j] - m1 - xh[j] * m2);
+    if (a.drop.mode != kLnDropNone) wide_dropout<CPW>(a.drop, lr, c0, tail_ok, live, dxh);
+#pragma unroll
+    for (int j = 0; j < CPW; ++j) {
+      const int col = wide_col<CPW>(j, c0, tail_ok);
+      if (j < CPW - 1 || tail_ok) {
+        a.dx[(long)row * D + col] = col < live ? dxh[j] : 0.f;
+        a.dg[(long)row * D + col] = dg[j];
+      }
+    }
+    return;
+  }
 #pragma unroll
   for (int j = 0; j < CPW; ++j) {
     const int col = wide_col<CPW>(j, c0, tail_ok);
@@ -178,7 +237,7 @@ __device__ __forceinline__ void wide_bwd_row(const LnBwdArgs& a, const LossArgs&
 }
 
 // The backward plain row (plain_bwd_row of heads.hip at these widths): no statistics, no exchange; dx alone is written.
-template <int CPW>
+template <int CPW, bool DROP = false>
 __device__ __forceinline__ void wide_plain_bwd_row(const LnBwdArgs& a, const LossArgs& L, int row, int wave, int lane) {
   const int D = a.D;
   const bool tail_ok = wave + 4 * (CPW - 1) < (D >> 6);
@@ -206,6 +265,9 @@ __device__ __forceinline__ void wide_plain_bwd_row(const LnBwdArgs& a, const Los
       dg[j] *= sg + y[j] * (1.f - sg);
     }
   }
+  if constexpr (DROP) {
+    if (a.drop.mode != kLnDropNone) wide_dropout<CPW>(a.drop, lr, c0, tail_ok, a.d ? a.d : D, dg);
+  }
 #pragma unroll
   for (int j = 0; j < CPW; ++j)
     if (j < CPW - 1 || tail_ok) a.dx[(long)row * D + wide_col<CPW>(j, c0, tail_ok)] = dg[j];
@@ -223,6 +285,17 @@ SERL_WIDE_KERNEL void ln_wide_bwd_kernel(Multi<LnBwdArgs> mv, LossArgs loss) {
   else wide_plain_bwd_row<CPW>(a, loss, blockIdx.x, threadIdx.x >> 6, threadIdx.x & 63);
 }
 
+// ... of a launch in which an instance has Dropout
+template <int CPW, bool LN>
+SERL_WIDE_KERNEL void ln_wide_bwd_drop_kernel(Multi<LnBwdArgs> mv, LossArgs loss) {
+  __shared__ float red[4][256];
+  if (loss.on && blockIdx.y == 0 && blockIdx.x == gridDim.x - 1) { critic_loss_body(loss, red); return; }
+  const LnBwdArgs& a = mv.v[blockIdx.y];
+  if ((int)blockIdx.x >= a.rows) return;
+  if constexpr (LN) wide_bwd_row<CPW, true>(a, loss, blockIdx.x, threadIdx.x >> 6, threadIdx.x & 63, &red[0][0]);
+  else wide_plain_bwd_row<CPW, true>(a, loss, blockIdx.x, threadIdx.x >> 6, threadIdx.x & 63);
+}
+
 // The launch of a width: K<ceil(D / 256), LN>
 #define SERL_WIDE_CASE(V, K, LN, ...) case V: SERL_LAUNCH_CHAIN((K<V, LN>), __VA_ARGS__); break;
 #define SERL_WIDE_CASES(K, LN, ...)                                                                                              \
@@ -236,21 +309,26 @@ SERL_WIDE_KERNEL void ln_wide_bwd_kernel(Multi<LnBwdArgs> mv, LossArgs loss) {
     default: serl::set_error("wide LayerNorm width %d has no kernel", (int)(D)); return SERL_ERR_INVALID;                        \
   }
 
-// mv, rows (the most of any instance), D, plain as ln_fwd_multi validated them; one workgroup per row and instance
-int ln_wide_fwd(const Multi<LnFwdArgs>& mv, int n, int rows, int D, bool plain, hipStream_t stream) {
+// mv, rows (the most of any instance), D, plain, drop (an instance carries Dropout) as ln_fwd_multi validated them; one workgroup
+// per row and instance
+int ln_wide_fwd(const Multi<LnFwdArgs>& mv, int n, int rows, int D, bool plain, bool drop, hipStream_t stream) {
   SERL_REQUIRE(D > 1024 && D <= kWideMax && D % 64 == 0 && rows >= 1, "wide LayerNorm row: width %d, %d rows", D, rows);
   const dim3 grid(rows, n);
-  if (plain) SERL_WIDE_LAUNCH(D, ln_wide_fwd_kernel, false, grid, dim3(256), 0, stream, mv, D)
+  if (plain && drop) SERL_WIDE_LAUNCH(D, ln_wide_fwd_drop_kernel, false, grid, dim3(256), 0, stream, mv, D)
+  else if (drop) SERL_WIDE_LAUNCH(D, ln_wide_fwd_drop_kernel, true, grid, dim3(256), 0, stream, mv, D)
+  else if (plain) SERL_WIDE_LAUNCH(D, ln_wide_fwd_kernel, false, grid, dim3(256), 0, stream, mv, D)
   else SERL_WIDE_LAUNCH(D, ln_wide_fwd_kernel, true, grid, dim3(256), 0, stream, mv, D)
   SERL_HIP(hipGetLastError());
   return SERL_OK;
 }
 
 // ... as ln_bwd_multi validated them (every instance D wide); the rider workgroup behind the rows when loss.on
-int ln_wide_bwd(const Multi<LnBwdArgs>& mv, int n, int rows, int D, bool plain, const LossArgs& loss, hipStream_t stream) {
+int ln_wide_bwd(const Multi<LnBwdArgs>& mv, int n, int rows, int D, bool plain, bool drop, const LossArgs& loss, hipStream_t stream) {
   SERL_REQUIRE(D > 1024 && D <= kWideMax && D % 64 == 0 && rows >= 1, "wide LayerNorm backward: width %d, %d rows", D, rows);
   const dim3 grid(rows + (loss.on ? 1 : 0), n);
-  if (plain) SERL_WIDE_LAUNCH(D, ln_wide_bwd_kernel, false, grid, dim3(256), 0, stream, mv, loss)
+  if (plain && drop) SERL_WIDE_LAUNCH(D, ln_wide_bwd_drop_kernel, false, grid, dim3(256), 0, stream, mv, loss)
+  else if (drop) SERL_WIDE_LAUNCH(D, ln_wide_bwd_drop_kernel, true, grid, dim3(256), 0, stream, mv, loss)
+  else if (plain) SERL_WIDE_LAUNCH(D, ln_wide_bwd_kernel, false, grid, dim3(256), 0, stream, mv, loss)
   else SERL_WIDE_LAUNCH(D, ln_wide_bwd_kernel, true, grid, dim3(256), 0, stream, mv, loss)
   SERL_HIP(hipGetLastError());
   return SERL_OK;

@@ -302,7 +302,10 @@ class NetSpec:
     wide: serl_agent_opts.wide_widths -- the widths end at 4096 instead of 1024; network_spec sets it where a width is above 1024 and
     nowhere else, so that widths up to 1024 through mlp_wide=True give the NetSpec, and the agent, of the call without.
     wide_actions: serl_agent_opts.wide_actions -- act_dim ends at 256 instead of 64, above 64 on the wide head rows
-    (csrc/head_wide.h); network_spec sets it where act_dim is above 64 and nowhere else, to the same end."""
+    (csrc/head_wide.h); network_spec sets it where act_dim is above 64 and nowhere else, to the same end.
+    dropout_any: serl_agent_opts.dropout_any -- a positive dropout_rate is served beside every other option but a fixed std
+    (mlp_dropout="any"); network_spec sets it where a rate is positive and nowhere else.  Two LayerNorm layers of one width on the
+    grid launch under it what they launch without."""
     std_parameterization: str = "exp"
     tanh_squash_distribution: bool = True
     fixed_std: Optional[Tuple[float, ...]] = None
@@ -319,6 +322,7 @@ class NetSpec:
     use_proprio: bool = True
     wide: bool = False
     wide_actions: bool = False
+    dropout_any: bool = False
 
     @property
     def dims(self):
@@ -333,10 +337,14 @@ class NetSpec:
     def check(self):
         """A positive dropout_rate (mlp_dropout=True) is served in two LayerNorm MLPs of one [h, h] under a policy head with std
         leaves: the Dropout masks and per-layer keys of serl_mlp_noise are laid out for two layers of one width, the LayerNorm-free
-        rows carry no Dropout, and the library serves none beside a fixed std.  Anything else raises NotImplementedError."""
+        rows carry no Dropout, and the library serves none beside a fixed std.  Anything else raises NotImplementedError.
+        With dropout_any (mlp_dropout="any") the rows of every family carry Dropout and the masks follow the true widths: only the
+        fixed std is refused."""
         rates = (self.critic_dropout, self.policy_dropout)
         if not any(r > 0 for r in rates):
             return self
+        if self.dropout_any:
+            return self._check_fixed(rates)
         if not self.use_proprio:
             raise NotImplementedError(
                 f"use_proprio=False under image_only=True with mlp_dropout=True and a positive dropout_rate (critic {rates[0]!r} / policy "
@@ -366,6 +374,9 @@ class NetSpec:
             which, _, rate = next(n for n in nets if n[2] > 0)
             raise NotImplementedError(f"{which}: dropout_rate={rate!r} under mlp_dropout=True beside a network with use_layer_norm=False "
                                       "under mlp_plain=True (served: Dropout in agents whose two networks have their LayerNorm)")
+        return self._check_fixed(rates)
+
+    def _check_fixed(self, rates):
         if self.fixed_std is not None:
             raise NotImplementedError(f"std_parameterization='fixed' under policy_fixed=True with dropout_rate critic {rates[0]!r} / "
                                       f"policy {rates[1]!r} under mlp_dropout=True (served: Dropout in agents whose policy head has std leaves)")
@@ -389,6 +400,7 @@ class NetSpec:
         return dict(**({} if self.use_proprio else {"use_proprio": False}),
                     critic_activation=self.critic_activation, policy_activation=self.policy_activation,
                     critic_dropout_rate=self.critic_dropout, policy_dropout_rate=self.policy_dropout,
+                    **({"dropout_any": True} if self.dropout_any else {}),
                     **({} if self.fixed_std is None else {"fixed_std": self.fixed_std}),
                     **({} if self.critic_layer_norm and self.policy_layer_norm else
                        {"critic_use_layer_norm": self.critic_layer_norm, "policy_use_layer_norm": self.policy_layer_norm}))
@@ -412,6 +424,7 @@ class NetSpec:
         o.no_proprio = 0 if self.use_proprio else 1
         o.wide_widths = 1 if self.wide else 0
         o.wide_actions = 1 if self.wide_actions else 0
+        o.dropout_any = 1 if self.dropout_any else 0
         return o
 
 
@@ -422,7 +435,12 @@ def network_spec(critic_network_kwargs, policy_network_kwargs, policy_kwargs, ac
     [1, 1024] (mlp.py:19-31 takes any list); without it the 64 grid, as always.  use_proprio: create_drq's, already checked to be
     a bool and read under image_only=True alone.  mlp_wide=True: every width read below ends at 4096 instead of 1024 (one
     workgroup per LayerNorm row above 1024); a positive dropout_rate beside such a width is NetSpec.check's to refuse.
-    wide_actions=True: act_dim is any integer in [1, 256]; without it an act_dim above 64 is the library's to refuse, as always."""
+    wide_actions=True: act_dim is any integer in [1, 256]; without it an act_dim above 64 is the library's to refuse, as always.
+    mlp_dropout="any": the rates are read as with True, and served beside every shape, LayerNorm choice and use_proprio=False
+    (NetSpec.dropout_any); True and False are what they were, any other value is a ValueError."""
+    if not (isinstance(mlp_dropout, (bool, np.bool_)) or (isinstance(mlp_dropout, str) and mlp_dropout == "any")):
+        raise ValueError(f"mlp_dropout must be False, True or 'any' (got {mlp_dropout!r})")
+    any_shape = isinstance(mlp_dropout, str)
     send_wide_actions = act_dim_served(act_dim, wide_actions)
     # policy_fixed=True: "fixed" / fixed_std are read (actor_critic_nets.py:189-192); else refused, as always
     std_param, squash, fixed = policy_mode_fixed(policy_kwargs, act_dim) if policy_fixed else (*policy_mode(policy_kwargs), None)
@@ -438,7 +456,7 @@ def network_spec(critic_network_kwargs, policy_network_kwargs, policy_kwargs, ac
     spec = NetSpec(std_param, squash, None if fixed is None else tuple(float(x) for x in fixed), *acts, *rates, hidden, *dims, *lns)
     wide = bool(mlp_wide) and max(max(net) for net in spec.dims) > 1024
     return dataclasses.replace(spec, ragged=bool(mlp_ragged) and spec.off_grid, use_proprio=bool(use_proprio), wide=wide,
-                               wide_actions=send_wide_actions).check()
+                               wide_actions=send_wide_actions, dropout_any=any_shape and any(r > 0 for r in rates)).check()
 
 
 def _policy_std_shapes(Hd, A, std_parameterization):
