@@ -45,12 +45,12 @@ CHAIN = [
     ("gemm_bf16x3_kernel<false, false, 16, false, false>", 80),
     ("gemm_bf16x3_kernel<true, false, 16, false, false>", 80),
     ("gemm_bf16x3_kernel<true, true, 16, false, false>", 80),
-    ("ln_fwd_kernel<4, true>", 80),
-    ("ln_bwd_kernel<0, false>", 80),
+    ("ln_fwd_kernel<4, true, true, false, false>", 80),      # <VPL, BLOCKED, LN, RAGGED, DROP>
+    ("ln_bwd_kernel<0, false, true, false, false>", 80),
     ("ln_bwd_one_kernel<4, true>", 80),
     ("ln_bwd_one_kernel<1, false>", 80),
-    ("ln_fwd_drop_kernel<4, true>", 80),      # the same rows with MLP Dropout (launches of a Dropout agent only)
-    ("ln_bwd_drop_kernel<0, false>", 80),
+    ("ln_fwd_kernel<4, true, true, false, true>", 80),      # the same rows with MLP Dropout (launches of a Dropout agent only)
+    ("ln_bwd_kernel<0, false, true, false, true>", 80),
     ("policy_dist_fwd_kernel<0>", 80),
     ("policy_dist_bwd_kernel<0>", 80),
     ("critic_loss_kernel", 80),

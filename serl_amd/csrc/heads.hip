@@ -4,6 +4,7 @@
 // Reference semantics are cited per kernel (paths relative to serl_launcher/serl_launcher/).
 #include <algorithm>
 #include <cstdlib>
+#include <type_traits>
 
 #include "heads.h"
 #include "jaxrng.h"
@@ -216,11 +217,15 @@ __device__ __forceinline__ void ln_activate(int act, float (&v)[N]) {   // in pl
   }
 }
 // dg[j] = dy[j] * act'(pre[j]) in place (dg holds dy on entry).  tanh: 1 - y^2.  ReLU: y > 0 -- the gradient AT 0 is 0, as
-// jax.nn.relu's.  swish: sigma(p) + y (1 - sigma(p)) with p = gam * xh + beta recomputed (pbeta: the lane's first beta, its
-// columns BSTRIDE floats apart: beta + boff; beta is nullptr on the other paths, so the pointer is formed on this one alone).
-template <int N, int BSTRIDE>
-__device__ __forceinline__ void ln_act_grad(int act, float (&dg)[N], const float (&y)[N], const float (&xh)[N], const float (&gam)[N],
-                                            const float* beta, long boff) {
+// jax.nn.relu's.  swish: sigma(p) + y (1 - sigma(p)) with p = pre(j), the pre-activation of the lane's column j, which every
+// backward row states for itself: gamma * xhat + beta recomputed by a LayerNorm row, the xhat buffer's value by a plain row (its
+// forward kept the pre-activation there).  pre is called on the swish path alone: beta and a plain row's xhat are read nowhere else.
+// A lambda of the rows (a column map, a pre-activation): inlined with the __forceinline__ functions around it, in front of every other
+// pass, so that a row comes out as if written in one piece -- and inlined into the wide kernels (ln_wide.h) at all, which are built
+// without a target feature the call operator would ask for (critic_loss_body has the same matter).
+#define SERL_LAMBDA_INLINE __attribute__((always_inline))
+template <int N, class Pre>
+__device__ __forceinline__ void ln_act_grad(int act, float (&dg)[N], const float (&y)[N], Pre pre) {
   if (act == kActTanh) {
 #pragma unroll
     for (int j = 0; j < N; ++j) dg[j] *= 1.f - y[j] * y[j];
@@ -228,10 +233,9 @@ __device__ __forceinline__ void ln_act_grad(int act, float (&dg)[N], const float
 #pragma unroll
     for (int j = 0; j < N; ++j) dg[j] = y[j] > 0.f ? dg[j] : 0.f;
   } else {
-    const float* pbeta = beta + boff;
 #pragma unroll
     for (int j = 0; j < N; ++j) {
-      const float sg = sigmoid_stable(xh[j] * gam[j] + pbeta[j * BSTRIDE]);
+      const float sg = sigmoid_stable(pre(j));
       dg[j] *= sg + y[j] * (1.f - sg);
     }
   }
@@ -285,6 +289,10 @@ __device__ __forceinline__ void ln_gather(const LnFwdArgs& a, long base, long pb
 // flax does (inputs / keep_prob), dropped ones are exactly 0.  The forward row applies it to the gathered Dense output, the
 // backward row to dx; both state the element's index as (row0 + lrow) * D + column, whatever the lane layout.  Called under a
 // wave-uniform branch on d.mode != kLnDropNone; the mode is uniform too.
+// This is the FULL-WIDTH form (every column of the row is a true column, D a constant), unrolled over the lane's columns in all
+// three modes -- the form the budget-listed <4, true> Dropout kernels run (scripts/kernel_resources.py).  Its unroll policy differs
+// from ln_dropout_n's on purpose (that one keeps one Threefry state in registers at up to 16 columns per lane), so the two are
+// not one function; every row that is not a full-width LayerNorm row takes ln_dropout_n, and nothing else restates this one.
 template <int VPL, bool BLOCKED>
 __device__ __forceinline__ void ln_dropout(const LnDrop& d, long lrow, int c0, float (&v)[VPL]) {
   constexpr int D = 64 * VPL, kStep = kLnStep<BLOCKED>;
@@ -310,41 +318,51 @@ __device__ __forceinline__ bool ln_keep_at(const LnDrop& d, long idx, uint64_t n
   if (d.mode == kLnDropKey) return bits_to_unit(random_bits_at(d.key[0], d.key[1], n, e)) < d.keep;
   return (uint32_t)(mix64(d.seed ^ mix64(e)) & 0xFFFFFFull) < thr;
 }
-// Dropout at a TRUE width Nt <= D read at run time: the ragged LayerNorm rows and the plain rows (ln_row<.., DROP, RAGGED>,
-// plain_row<.., DROP>).  Element (row r, true column c) is decision r * Nt + c -- the shape bernoulli(key, keep, (rows, Nt)) draws,
-// and the layout of the u8 mask; with Nt == D these are ln_dropout's decisions.  A padding column [Nt, D) draws nothing and reads
-// no mask byte: its address is clamped to the row's last true column, the load is unconditional and the value is selected to 0
+// Dropout at a TRUE width Nt <= D read at run time, on the N values a lane holds in any row layout: the ragged LayerNorm rows, the
+// plain rows and the wide rows (ln_wide.h).  The layout is a column map: col(j) is the column of value j -- some column of the row
+// where the lane has none -- and live(j) says whether value j is a true column of the row (it exists and lies below Nt).
+// Element (row r, true column c) is decision r * Nt + c -- the shape bernoulli(key, keep, (rows, Nt)) draws, and the layout of
+// the u8 mask; with Nt == D these are ln_dropout's decisions.  A value that is not live draws nothing and reads no mask byte of
+// its own: its address is clamped to the row's last true column, the load is unconditional and the value is selected to 0
 // afterwards.  The key's decisions are taken one column after the other in a loop that is not unrolled and
-// kept as bits: one Threefry state in registers whatever VPL is.
-template <int VPL, bool BLOCKED>
-__device__ __forceinline__ void ln_dropout_n(const LnDrop& d, long lrow, int c0, int Nt, float (&v)[VPL]) {
-  constexpr int kStep = kLnStep<BLOCKED>;
+// kept as bits: one Threefry state in registers whatever N is.
+template <int N, class Col, class Live>
+__device__ __forceinline__ void ln_dropout_n(const LnDrop& d, long lrow, int Nt, float (&v)[N], Col col, Live live) {
   const uint32_t thr = (uint32_t)(d.keep * 16777216.f);
   const uint64_t n = (uint64_t)d.total_rows * (uint64_t)Nt, e0 = (uint64_t)(d.row0 + lrow) * (uint64_t)Nt;
   uint32_t bits = 0;
   if (d.mode == kLnDropKey) {
 #pragma unroll 1
-    for (int j = 0; j < VPL; ++j) {
-      const int cc = min(c0 + kStep * j, Nt - 1);
+    for (int j = 0; j < N; ++j) {
+      const int cc = min(col(j), Nt - 1);
       bits |= (ln_keep_at(d, 0, n, e0 + (uint64_t)cc, thr) ? 1u : 0u) << j;
     }
   } else {
 #pragma unroll
-    for (int j = 0; j < VPL; ++j) {
-      const int cc = min(c0 + kStep * j, Nt - 1);
+    for (int j = 0; j < N; ++j) {
+      const int cc = min(col(j), Nt - 1);
       bits |= (ln_keep_at(d, lrow * Nt + cc, n, e0 + (uint64_t)cc, thr) ? 1u : 0u) << j;
     }
   }
 #pragma unroll
-  for (int j = 0; j < VPL; ++j) v[j] = ((bits >> j) & 1u) && c0 + kStep * j < Nt ? v[j] / d.keep : 0.f;
+  for (int j = 0; j < N; ++j) v[j] = ((bits >> j) & 1u) && live(j) ? v[j] / d.keep : 0.f;
+}
+// A narrow row's Dropout (under the row's uniform branch on d.mode): a LayerNorm row of D true columns takes ln_dropout, every
+// other row ln_dropout_n at its true width Nt in the narrow column map.
+template <int VPL, bool BLOCKED, bool FULL>
+__device__ __forceinline__ void ln_row_dropout(const LnDrop& d, long lrow, int c0, int Nt, float (&v)[VPL]) {
+  if constexpr (FULL) ln_dropout<VPL, BLOCKED>(d, lrow, c0, v);
+  else ln_dropout_n(d, lrow, Nt, v, [&](int j) SERL_LAMBDA_INLINE { return c0 + kLnStep<BLOCKED> * j; },
+                    [&](int j) SERL_LAMBDA_INLINE { return c0 + kLnStep<BLOCKED> * j < Nt; });
 }
 // Returns the fused row-dot (dot_out's value, in every lane; 0 without one).
-// DROP: the instantiation of the launches that carry an instance with Dropout (ln_fwd_drop_kernel); the rows of every other launch
-// are the DROP = false instantiation, whose text -- and therefore whose contraction into fused multiply-adds -- is what it was.
-// RAGGED: the instantiation of a zero-padded row of true width a.d < D (heads.h): the statistics divide by a.d.  Nothing else
-// differs: the pads of the bias and of the slabs are 0 and add nothing to the sums, and gamma == beta == 0 there gives y == act(0) == 0.
-// DROP and RAGGED (ln_fwd_ragged_drop_kernel): the decisions of ln_dropout_n, indexed by the true width; xhat is kept 0 in the pads.
-template <int VPL, bool BLOCKED, bool DROP = false, bool RAGGED = false>
+// One body for every family of LayerNorm row; a family is an instantiation, and the rows of the default launches are the
+// <!RAGGED, !DROP> one, whose text -- and therefore whose contraction into fused multiply-adds -- is what it was.
+// RAGGED: a zero-padded row of true width a.d < D (heads.h): the statistics divide by a.d.  Nothing else differs: the pads of the
+// bias and of the slabs are 0 and add nothing to the sums, and gamma == beta == 0 there gives y == act(0) == 0.
+// DROP: the rows of a launch in which an instance carries Dropout (mlp.py:27-31: y = act(LayerNorm(Dropout(Dense(x) + b)))): the
+// keep decisions in front of the statistics, indexed by the true width (ln_row_dropout).  DROP and RAGGED: xhat is kept 0 in the pads.
+template <int VPL, bool BLOCKED, bool RAGGED = false, bool DROP = false>
 __device__ __forceinline__ float ln_row(const LnFwdArgs& a, int row, int lane) {
   constexpr int D = 64 * VPL, kStep = kLnStep<BLOCKED>;
   const int grp = row / a.rows_per_group;
@@ -355,10 +373,7 @@ __device__ __forceinline__ float ln_row(const LnFwdArgs& a, int row, int lane) {
   float v[VPL];
   ln_gather<VPL, BLOCKED>(a, base, pb, v);
   if constexpr (DROP) {
-    if (a.drop.mode != kLnDropNone) {   // (uniform: the launch's instance)
-      if constexpr (RAGGED) ln_dropout_n<VPL, BLOCKED>(a.drop, lrow, c0, a.d, v);
-      else ln_dropout<VPL, BLOCKED>(a.drop, lrow, c0, v);
-    }
+    if (a.drop.mode != kLnDropNone) ln_row_dropout<VPL, BLOCKED, !RAGGED>(a.drop, lrow, c0, RAGGED ? a.d : D, v);   // (uniform: the launch's instance)
   }
   float s1 = 0.f, s2 = 0.f;
 #pragma unroll
@@ -383,7 +398,7 @@ __device__ __forceinline__ float ln_row(const LnFwdArgs& a, int row, int lane) {
     if (a.dot_out) d += v[j] * a.dot_w[(long)grp * a.dot_gstride + col];
   }
   if (a.rstd && lane == 0) a.rstd[row] = rstd;
-  if (a.dot_out) {
+  if (a.dot_out) {   // the Q-head row-dot rider: the lane's columns in ascending order (above), the butterfly, + dot_b, lane 0 stores
 #pragma unroll
     for (int off = 1; off < 64; off <<= 1) d += __shfl_xor(d, off);
     d += a.dot_b[(long)grp * a.dot_b_gstride];
@@ -397,8 +412,9 @@ __device__ __forceinline__ float ln_row(const LnFwdArgs& a, int row, int lane) {
 // needs no exchange between lanes; the dot_out rider (the critic's Q head on its last layer) keeps ln_row's: a lane's columns in
 // ascending order, then the xor butterfly.  What the backward reads: y (tanh and relu differentiate from it) and, for swish, the
 // pre-activation, which goes to the layer's xhat buffer (a plain layer has no normalised row to keep there); rstd is not written.
-// A launch is plain when its instances carry no gamma (LnFwdArgs); a row kernel of its own, so that ln_row's text stays what it is.
-// DROP (plain_fwd_drop_kernel; mlp.py:27-31 without the LayerNorm: y = act(Dropout(Dense(x) + b))): the decisions of ln_dropout_n at
+// A launch is plain when its instances carry no gamma (LnFwdArgs); a row body of its own: folded into ln_row the plain kernels come out
+// with other instructions, and a plain Dropout update step measured slower (profiles/README.md).
+// DROP ( mlp.py:27-31 without the LayerNorm: y = act(Dropout(Dense(x) + b))): the decisions of ln_dropout_n at
 // the row's true width, in front of everything else -- xhat keeps the MASKED pre-activation, and the rider reads the masked row.
 template <int VPL, bool BLOCKED, bool DROP = false>
 __device__ __forceinline__ float plain_row(const LnFwdArgs& a, int row, int lane) {
@@ -411,7 +427,7 @@ __device__ __forceinline__ float plain_row(const LnFwdArgs& a, int row, int lane
   float v[VPL];
   ln_gather<VPL, BLOCKED>(a, base, pb, v);
   if constexpr (DROP) {
-    if (a.drop.mode != kLnDropNone) ln_dropout_n<VPL, BLOCKED>(a.drop, lrow, c0, a.d ? a.d : D, v);   // (uniform: the launch's instance)
+    if (a.drop.mode != kLnDropNone) ln_row_dropout<VPL, BLOCKED, false>(a.drop, lrow, c0, a.d ? a.d : D, v);   // (uniform: the launch's instance)
   }
   if (a.xhat) {
 #pragma unroll
@@ -1071,52 +1087,16 @@ int reduce_slabs(const float* slabs, int S, long slab_stride, int groups, int ro
 // =============================================================================================
 // LayerNorm(eps 1e-6, fast variance) + activation, one wave per row (ln_row), four rows per workgroup.
 // =============================================================================================
-template <int VPL, bool BLOCKED>
+// The family of a launch's rows is the kernel's instantiation (ln_row's LN, RAGGED and DROP; ln_for_family below): LayerNorm or
+// LayerNorm-free layers (mlp.py:29-30, use_layer_norm=False), zero-padded rows of a true width off the 64 grid (LnFwdArgs::d), and
+// a launch in which an instance has Dropout (mlp.py:27-28).
+template <int VPL, bool BLOCKED, bool LN = true, bool RAGGED = false, bool DROP = false>
 __global__ __launch_bounds__(256) void ln_fwd_kernel(Multi<LnFwdArgs> mv) {
   const LnFwdArgs& a = mv.v[blockIdx.y];  // blockIdx.y = independent instance (variant)
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (row >= a.rows) return;
-  ln_row<VPL, BLOCKED>(a, row, lane);
-}
-// ... of a launch in which an instance has Dropout (mlp.py:27-28): the same rows with the mask in front of the statistics
-template <int VPL, bool BLOCKED>
-__global__ __launch_bounds__(256) void ln_fwd_drop_kernel(Multi<LnFwdArgs> mv) {
-  const LnFwdArgs& a = mv.v[blockIdx.y];
-  const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-  if (row >= a.rows) return;
-  ln_row<VPL, BLOCKED, true>(a, row, lane);
-}
-// ... of a launch whose instances are zero-padded rows of a true width off the 64 grid (LnFwdArgs::d)
-template <int VPL, bool BLOCKED>
-__global__ __launch_bounds__(256) void ln_fwd_ragged_kernel(Multi<LnFwdArgs> mv) {
-  const LnFwdArgs& a = mv.v[blockIdx.y];
-  const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-  if (row >= a.rows) return;
-  ln_row<VPL, BLOCKED, false, true>(a, row, lane);
-}
-// ... of a launch whose instances are LayerNorm-free layers (mlp.py:29-30, use_layer_norm=False): plain_row in the same grid
-template <int VPL, bool BLOCKED>
-__global__ __launch_bounds__(256) void plain_fwd_kernel(Multi<LnFwdArgs> mv) {
-  const LnFwdArgs& a = mv.v[blockIdx.y];
-  const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-  if (row >= a.rows) return;
-  plain_row<VPL, BLOCKED>(a, row, lane);
-}
-
-// ... ragged rows / plain rows of a launch in which an instance has Dropout
-template <int VPL, bool BLOCKED>
-__global__ __launch_bounds__(256) void ln_fwd_ragged_drop_kernel(Multi<LnFwdArgs> mv) {
-  const LnFwdArgs& a = mv.v[blockIdx.y];
-  const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-  if (row >= a.rows) return;
-  ln_row<VPL, BLOCKED, true, true>(a, row, lane);
-}
-template <int VPL, bool BLOCKED>
-__global__ __launch_bounds__(256) void plain_fwd_drop_kernel(Multi<LnFwdArgs> mv) {
-  const LnFwdArgs& a = mv.v[blockIdx.y];
-  const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-  if (row >= a.rows) return;
-  plain_row<VPL, BLOCKED, true>(a, row, lane);
+  if constexpr (LN) ln_row<VPL, BLOCKED, RAGGED, DROP>(a, row, lane);
+  else plain_row<VPL, BLOCKED, DROP>(a, row, lane);
 }
 
 // The reward classifier's head closed for labelling (vice.py:546,594: rewards = (sigmoid(classifier(next_obs)) >= 0.5) * 1.0): the
@@ -1169,18 +1149,36 @@ static bool ln_drop_ok(const LnDrop& d, long rows) {
   if (d.mode == kLnDropKey) return d.row0 >= 0 && d.row0 + rows <= d.total_rows;
   return d.mode == kLnDropHash && d.row0 >= 0;
 }
-#define SERL_LN_CASE(V, K, ...) case V: SERL_LAUNCH_CHAIN(K, __VA_ARGS__); break;
-#define SERL_LN_STRIDED(V, K, ...) SERL_LN_CASE(V, (K<V, false>), __VA_ARGS__)
-#define SERL_LN_LAUNCH(D, K64, K256, K, ...)                                                                              \
-  switch ((D) / 64) {                                                                                                     \
-    SERL_LN_CASE(1, K64, __VA_ARGS__) SERL_LN_CASE(4, K256, __VA_ARGS__)                                                  \
-    SERL_LN_STRIDED(2, K, __VA_ARGS__) SERL_LN_STRIDED(3, K, __VA_ARGS__) SERL_LN_STRIDED(5, K, __VA_ARGS__)              \
-    SERL_LN_STRIDED(6, K, __VA_ARGS__) SERL_LN_STRIDED(7, K, __VA_ARGS__) SERL_LN_STRIDED(8, K, __VA_ARGS__)              \
-    SERL_LN_STRIDED(9, K, __VA_ARGS__) SERL_LN_STRIDED(10, K, __VA_ARGS__) SERL_LN_STRIDED(11, K, __VA_ARGS__)            \
-    SERL_LN_STRIDED(12, K, __VA_ARGS__) SERL_LN_STRIDED(13, K, __VA_ARGS__) SERL_LN_STRIDED(14, K, __VA_ARGS__)           \
-    SERL_LN_STRIDED(15, K, __VA_ARGS__) SERL_LN_STRIDED(16, K, __VA_ARGS__)                                               \
-    default: serl::set_error("LayerNorm width %d has no kernel", (int)(D)); return SERL_ERR_INVALID;                      \
+// The dispatch of a row launch, each mapping written once; `launch` is a generic lambda that names the kernel template and is
+// called with the template arguments as std::integral_constant values.
+template <int V> using IntC = std::integral_constant<int, V>;
+template <bool B> using BoolC = std::integral_constant<bool, B>;
+#define SERL_C(x) decltype(x)::value   // the constant such an argument carries
+// family -> launch(LN, RAGGED, DROP).  plain: the instances carry no gamma; ragged: a true width a.d off the 64 grid, an
+// instantiation of its own for the narrow LayerNorm rows alone (a plain row and a wide row read a.d at run time); drop: an
+// instance of the launch carries Dropout -- every other launch is the instantiation it always was.
+template <class F>
+static int ln_for_family(bool plain, bool ragged, bool drop, F&& launch) {
+  if (plain) return drop ? launch(BoolC<false>{}, BoolC<false>{}, BoolC<true>{}) : launch(BoolC<false>{}, BoolC<false>{}, BoolC<false>{});
+  if (ragged) return drop ? launch(BoolC<true>{}, BoolC<true>{}, BoolC<true>{}) : launch(BoolC<true>{}, BoolC<true>{}, BoolC<false>{});
+  return drop ? launch(BoolC<true>{}, BoolC<false>{}, BoolC<true>{}) : launch(BoolC<true>{}, BoolC<false>{}, BoolC<false>{});
+}
+// narrow width -> launch(VPL, BLOCKED): <1, false> at 64, <4, true> at 256, the strided <D / 64, false> at every other.  MIXES: a
+// backward launch whose instances may be 64 and 256 wide side by side (kLnMixed below): both widths are <kLnMixed, false>.
+constexpr int kLnMixed = 0;
+template <bool MIXES, class F>
+static int ln_for_width(int D, F&& launch) {
+  switch (D / 64) {
+    case 1: launch(IntC<MIXES ? kLnMixed : 1>{}, BoolC<false>{}); break;
+    case 4: launch(IntC<MIXES ? kLnMixed : 4>{}, BoolC<!MIXES>{}); break;
+#define SERL_LN_STRIDED(V) case V: launch(IntC<V>{}, BoolC<false>{}); break;
+    SERL_LN_STRIDED(2) SERL_LN_STRIDED(3) SERL_LN_STRIDED(5) SERL_LN_STRIDED(6) SERL_LN_STRIDED(7) SERL_LN_STRIDED(8) SERL_LN_STRIDED(9)
+    SERL_LN_STRIDED(10) SERL_LN_STRIDED(11) SERL_LN_STRIDED(12) SERL_LN_STRIDED(13) SERL_LN_STRIDED(14) SERL_LN_STRIDED(15) SERL_LN_STRIDED(16)
+#undef SERL_LN_STRIDED
+    default: serl::set_error("LayerNorm width %d has no kernel", D); return SERL_ERR_INVALID;
   }
+  return SERL_OK;
+}
 
 int ln_fwd_multi(const LnFwdArgs* as, int n, int D, hipStream_t stream) {
   SERL_REQUIRE(SERL_LN_WIDTH_OK(D), "LayerNorm width %d unsupported (a multiple of 64 in [64, 4096])", D);
@@ -1204,15 +1202,12 @@ int ln_fwd_multi(const LnFwdArgs* as, int n, int D, hipStream_t stream) {
   }
   if (D > 1024) return ln_wide_fwd(mv, n, rows, D, !as[0].gamma, drop, stream);   // one workgroup per row (ln_wide.h)
   dim3 grid(cdiv(rows, 4), n);
-  // (a launch in which an instance carries Dropout is the DROP instantiation of its family; every other launch is what it was)
-  if (!as[0].gamma) {
-    if (drop) SERL_LN_LAUNCH(D, (plain_fwd_drop_kernel<1, false>), (plain_fwd_drop_kernel<4, true>), plain_fwd_drop_kernel, grid, dim3(256), 0, stream, mv)
-    else SERL_LN_LAUNCH(D, (plain_fwd_kernel<1, false>), (plain_fwd_kernel<4, true>), plain_fwd_kernel, grid, dim3(256), 0, stream, mv)
-  } else if (as[0].d) {
-    if (drop) SERL_LN_LAUNCH(D, (ln_fwd_ragged_drop_kernel<1, false>), (ln_fwd_ragged_drop_kernel<4, true>), ln_fwd_ragged_drop_kernel, grid, dim3(256), 0, stream, mv)
-    else SERL_LN_LAUNCH(D, (ln_fwd_ragged_kernel<1, false>), (ln_fwd_ragged_kernel<4, true>), ln_fwd_ragged_kernel, grid, dim3(256), 0, stream, mv)
-  } else if (drop) SERL_LN_LAUNCH(D, (ln_fwd_drop_kernel<1, false>), (ln_fwd_drop_kernel<4, true>), ln_fwd_drop_kernel, grid, dim3(256), 0, stream, mv)
-  else SERL_LN_LAUNCH(D, (ln_fwd_kernel<1, false>), (ln_fwd_kernel<4, true>), ln_fwd_kernel, grid, dim3(256), 0, stream, mv)
+  const int rc = ln_for_family(!as[0].gamma, as[0].gamma && as[0].d, drop, [&](auto ln, auto ragged, auto dr) {
+    return ln_for_width<false>(D, [&](auto vpl, auto blocked) {
+      SERL_LAUNCH_CHAIN((ln_fwd_kernel<SERL_C(vpl), SERL_C(blocked), SERL_C(ln), SERL_C(ragged), SERL_C(dr)>), grid, dim3(256), 0, stream, mv);
+    });
+  });
+  if (rc != SERL_OK) return rc;
   SERL_HIP(hipGetLastError());
   return SERL_OK;
 }
@@ -1234,7 +1229,7 @@ constexpr int kFanLds = 4096;   // floats of the action block in LDS at a time: 
 template <int VPL>
 constexpr int kFanCj = VPL <= 4 ? 8 : (VPL <= 8 ? 16 / VPL : 1);   // candidates whose rows a wave accumulates at once: 8, or what 16 registers hold
 
-// The epilogue of one candidate row held in v (the arithmetic of ln_row / plain_row at this width: statistics over the true width
+// The epilogue of one candidate row held in v (the arithmetic of ln_row at this width, LayerNorm or plain: statistics over the true width
 // of a ragged row, whose pads stay exactly zero as there), written as row `row` of y [rows][D] and of the Q-head rider.
 template <int VPL>
 __device__ __forceinline__ void fanout_row(const LnFwdArgs& a, float (&v)[VPL], long row, int grp, int lane, long pb) {
@@ -1355,6 +1350,12 @@ __device__ __forceinline__ float redq_target(const LossArgs& L, int b) {
   if (L.logp_next) y -= L.alpha[0] * L.logp_next[b];
   return y;
 }
+// dq of a backward row whose dy is the rank-1 dq (x) dq_w (0 where dy is a tensor), in its three forms: derived inline from the
+// launch's loss L (dq_inline, beside the critic-loss rider), read from a tensor, or a constant.  lr: the row inside its group.
+__device__ __forceinline__ float row_dq(const LnBwdArgs& a, const LossArgs& L, int row, long lr) {
+  if (!a.dq_w) return 0.f;
+  return a.dq_inline ? 2.f * (L.q[row] - redq_target(L, (int)lr)) * L.inv_norm : (a.dq ? a.dq[row] : a.dq_const);
+}
 
 // critic loss by ONE workgroup of 256 threads (deterministic reductions); the body of critic_loss_kernel
 // (The attribute: the wide rows' kernels, ln_wide.h, are built without packed fp32 instructions and can inline only a callee that
@@ -1419,25 +1420,27 @@ __device__ void critic_loss_body(const LossArgs& L, float (*red)[256]) {
 // a lane sums its columns in ascending order, then the xor butterfly.  L: the launch's critic loss, read by a dq_inline row alone.
 // RAGGED: a zero-padded row of true width a.d < D (heads.h).  dy is 0 in the pads (the rows of the consumer's kernel are), so dg,
 // dxhat and both sums are what the d live columns give; the means divide by a.d, and dx is 0 in the pads.
-template <int VPL, bool BLOCKED, bool DROP = false, bool RAGGED = false>
+// DROP: dx wrt the LayerNorm's input, then -- the forward's keep decision stated again, by the true width (ln_row_dropout) -- wrt
+// the Dense output in front of the Dropout.
+template <int VPL, bool BLOCKED, bool RAGGED = false, bool DROP = false>
 __device__ __forceinline__ void ln_bwd_row(const LnBwdArgs& a, const LossArgs& L, int row, int lane) {
   const int grp = row / a.rows_per_group;
-  constexpr int D = VPL * 64;
+  constexpr int D = VPL * 64, kStep = kLnStep<BLOCKED>;
   float dg[VPL], dxh[VPL], xh[VPL], y[VPL], gam[VPL];
-  float s1 = 0.f, s2 = 0.f;
   const long lr = row - grp * a.rows_per_group;
   const int c0 = ln_col0<VPL, BLOCKED>(lane);
-  float dqr = 0.f;
-  if (a.dq_w) dqr = a.dq_inline ? 2.f * (L.q[row] - redq_target(L, (int)lr)) * L.inv_norm : (a.dq ? a.dq[row] : a.dq_const);
+  const float dqr = row_dq(a, L, row, lr);
 #pragma unroll
   for (int j = 0; j < VPL; ++j) {
-    const int col = c0 + kLnStep<BLOCKED> * j;
+    const int col = c0 + kStep * j;
     y[j] = a.y[lr * a.ld_y + (long)grp * a.y_goff + col];
     dg[j] = a.dq_w ? dqr * a.dq_w[(long)grp * a.dq_w_gstride + col] : a.dy[lr * a.ld_dy + (long)grp * a.dy_goff + col];
     xh[j] = a.xhat[(long)row * D + col];
     gam[j] = a.gamma[(long)grp * a.pstride + col];
   }
-  ln_act_grad<VPL, BLOCKED ? 1 : 64>(a.act, dg, y, xh, gam, a.beta, (long)grp * a.pstride + c0);
+  const long pb = (long)grp * a.pstride + c0;
+  ln_act_grad(a.act, dg, y, [&](int j) SERL_LAMBDA_INLINE { return xh[j] * gam[j] + (a.beta + pb)[kStep * j]; });
+  float s1 = 0.f, s2 = 0.f;
 #pragma unroll
   for (int j = 0; j < VPL; ++j) {
     dxh[j] = dg[j] * gam[j];
@@ -1449,40 +1452,24 @@ __device__ __forceinline__ void ln_bwd_row(const LnBwdArgs& a, const LossArgs& L
   if constexpr (RAGGED) { const float inv = 1.0f / (float)a.d; m1 = s1 * inv; m2 = s2 * inv; }
   else { m1 = s1 * (1.0f / D); m2 = s2 * (1.0f / D); }
   const float rstd = a.rstd[row];
-  if constexpr (RAGGED && DROP) {   // ... the forward's decision by the true width (ln_dropout_n, which leaves the pads 0)
+  // 1. dx of the lane's column j: ONE expression, whose contraction into fused multiply-adds is the same wherever it is
+  // evaluated -- a row without Dropout evaluates it at its store, as it always did
+  const auto dx_at = [&](int j) SERL_LAMBDA_INLINE { return rstd * (dxh[j] - m1 - xh[j] * m2); };
+  float dx[VPL];
+  if constexpr (DROP) {   // 2. dx wrt the Dense output in front of the Dropout (the pads of a ragged row come out 0)
 #pragma unroll
-    for (int j = 0; j < VPL; ++j) dxh[j] = rstd * (dxh[j] - m1 - xh[j] * m2);
-    if (a.drop.mode != kLnDropNone) ln_dropout_n<VPL, BLOCKED>(a.drop, lr, c0, a.d, dxh);
+    for (int j = 0; j < VPL; ++j) dx[j] = dx_at(j);
+    if (a.drop.mode != kLnDropNone) ln_row_dropout<VPL, BLOCKED, !RAGGED>(a.drop, lr, c0, RAGGED ? a.d : D, dx);
+  }
 #pragma unroll
-    for (int j = 0; j < VPL; ++j) {
-      const int col = c0 + kLnStep<BLOCKED> * j;
-      a.dx[(long)row * D + col] = col < a.d ? dxh[j] : 0.f;
-      a.dg[(long)row * D + col] = dg[j];
-    }
-  } else if constexpr (RAGGED) {
-#pragma unroll
-    for (int j = 0; j < VPL; ++j) {
-      const int col = c0 + kLnStep<BLOCKED> * j;
-      a.dx[(long)row * D + col] = col < a.d ? rstd * (dxh[j] - m1 - xh[j] * m2) : 0.f;
-      a.dg[(long)row * D + col] = dg[j];
-    }
-  } else if constexpr (!DROP) {
-#pragma unroll
-    for (int j = 0; j < VPL; ++j) {
-      const int col = c0 + kLnStep<BLOCKED> * j;
-      a.dx[(long)row * D + col] = rstd * (dxh[j] - m1 - xh[j] * m2);
-      a.dg[(long)row * D + col] = dg[j];
-    }
-  } else {   // dx wrt the LayerNorm's input, then -- the forward's keep decision stated again -- wrt the Dense output in front of the Dropout
-#pragma unroll
-    for (int j = 0; j < VPL; ++j) dxh[j] = rstd * (dxh[j] - m1 - xh[j] * m2);
-    if (a.drop.mode != kLnDropNone) ln_dropout<VPL, BLOCKED>(a.drop, lr, c0, dxh);
-#pragma unroll
-    for (int j = 0; j < VPL; ++j) {
-      const int col = c0 + kLnStep<BLOCKED> * j;
-      a.dx[(long)row * D + col] = dxh[j];
-      a.dg[(long)row * D + col] = dg[j];
-    }
+  for (int j = 0; j < VPL; ++j) {   // 3. the stores; dx is 0 in the pads of a ragged row
+    const int col = c0 + kStep * j;
+    float v;
+    if constexpr (DROP) v = dx[j];
+    else v = dx_at(j);
+    if constexpr (RAGGED) v = col < a.d ? v : 0.f;
+    a.dx[(long)row * D + col] = v;
+    a.dg[(long)row * D + col] = dg[j];
   }
 }
 
@@ -1491,7 +1478,7 @@ __device__ __forceinline__ void ln_bwd_row(const LnBwdArgs& a, const LossArgs& L
 // this path alone).  dy in ln_bwd_row's three forms: a tensor, the rank-1 dq (x) w, and dq derived inline from the launch's loss.
 // No row statistics, no exchange between lanes.  dg and dpre coincide: the row writes dx alone, and the bias's column sum and the
 // weight and input gradients all read it (layer_colsum, dense_layer.h); a.dg, a.rstd, a.gamma and a.beta are not touched.
-// DROP (plain_bwd_drop_kernel): y and xhat are those of the masked pre-activation, and dpre = dy act'(masked pre) (kept ? 1 / keep : 0),
+// DROP: y and xhat are those of the masked pre-activation, and dpre = dy act'(masked pre) (kept ? 1 / keep : 0),
 // the forward's decision stated again, in all three forms of dy.
 template <int VPL, bool BLOCKED, bool DROP = false>
 __device__ __forceinline__ void plain_bwd_row(const LnBwdArgs& a, const LossArgs& L, int row, int lane) {
@@ -1500,8 +1487,7 @@ __device__ __forceinline__ void plain_bwd_row(const LnBwdArgs& a, const LossArgs
   float dg[VPL], y[VPL];
   const long lr = row - grp * a.rows_per_group;
   const int c0 = ln_col0<VPL, BLOCKED>(lane);
-  float dqr = 0.f;
-  if (a.dq_w) dqr = a.dq_inline ? 2.f * (L.q[row] - redq_target(L, (int)lr)) * L.inv_norm : (a.dq ? a.dq[row] : a.dq_const);
+  const float dqr = row_dq(a, L, row, lr);
 #pragma unroll
   for (int j = 0; j < VPL; ++j) {
     const int col = c0 + kStep * j;
@@ -1522,84 +1508,29 @@ __device__ __forceinline__ void plain_bwd_row(const LnBwdArgs& a, const LossArgs
     }
   }
   if constexpr (DROP) {
-    if (a.drop.mode != kLnDropNone) ln_dropout_n<VPL, BLOCKED>(a.drop, lr, c0, a.d ? a.d : D, dg);
+    if (a.drop.mode != kLnDropNone) ln_row_dropout<VPL, BLOCKED, false>(a.drop, lr, c0, a.d ? a.d : D, dg);
   }
 #pragma unroll
   for (int j = 0; j < VPL; ++j) a.dx[(long)row * D + c0 + kStep * j] = dg[j];
 }
 
 // A LayerNorm-backward launch: blockIdx.y = instance, one wave per row, four rows per workgroup; the LAST workgroup of instance 0
-// is the critic-loss rider when loss.on.  VPL > 0: every instance has the width 64 * VPL (the MLP layers at a hidden width other
-// than 256).  VPL == 0: instances of width 256 or 64, each its own (the encoder heads: the cameras' bottleneck and the proprio
-// branch in one launch; and the MLP layers at the default width).
-constexpr int kLnMixed = 0;
-template <int VPL, bool BLOCKED>
+// is the critic-loss rider when loss.on.  The family of the rows is the instantiation, as in ln_fwd_kernel.  VPL > 0: every
+// instance has the width 64 * VPL (an MLP layer at a hidden width other than 256, ragged, plain: such a layer is alone in its
+// launch).  VPL == kLnMixed: LayerNorm instances of width 256 or 64, each its own (the encoder heads: the cameras' bottleneck and
+// the proprio branch in one launch; and the MLP layers at the default width).
+template <int VPL, bool BLOCKED, bool LN = true, bool RAGGED = false, bool DROP = false>
 __global__ __launch_bounds__(256) void ln_bwd_kernel(Multi<LnBwdArgs> mv, LossArgs loss) {
+  static_assert(VPL != kLnMixed || (LN && !RAGGED && !BLOCKED), "widths mix in a launch of full-width LayerNorm rows alone");
   __shared__ float red[4][256];
   if (loss.on && blockIdx.y == 0 && blockIdx.x == gridDim.x - 1) { critic_loss_body(loss, red); return; }
   const LnBwdArgs& a = mv.v[blockIdx.y];
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (row >= a.rows) return;
-  if constexpr (VPL != kLnMixed) ln_bwd_row<VPL, BLOCKED>(a, loss, row, lane);
-  else if (a.D == 256) ln_bwd_row<4, true>(a, loss, row, lane);
-  else ln_bwd_row<1, false>(a, loss, row, lane);
-}
-
-// ... of a launch in which an instance has Dropout: the rows mask dx as the forward masked the Dense output
-template <int VPL, bool BLOCKED>
-__global__ __launch_bounds__(256) void ln_bwd_drop_kernel(Multi<LnBwdArgs> mv, LossArgs loss) {
-  __shared__ float red[4][256];
-  if (loss.on && blockIdx.y == 0 && blockIdx.x == gridDim.x - 1) { critic_loss_body(loss, red); return; }
-  const LnBwdArgs& a = mv.v[blockIdx.y];
-  const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-  if (row >= a.rows) return;
-  if constexpr (VPL != kLnMixed) ln_bwd_row<VPL, BLOCKED, true>(a, loss, row, lane);
-  else if (a.D == 256) ln_bwd_row<4, true, true>(a, loss, row, lane);
-  else ln_bwd_row<1, false, true>(a, loss, row, lane);
-}
-
-// ... of a launch whose instances are zero-padded rows of one true width off the 64 grid (LnBwdArgs::d), all of them stored
-// 64 * VPL wide (an MLP layer is alone in its launch: no mixed widths); the critic-loss rider in the same place
-template <int VPL, bool BLOCKED>
-__global__ __launch_bounds__(256) void ln_bwd_ragged_kernel(Multi<LnBwdArgs> mv, LossArgs loss) {
-  __shared__ float red[4][256];
-  if (loss.on && blockIdx.y == 0 && blockIdx.x == gridDim.x - 1) { critic_loss_body(loss, red); return; }
-  const LnBwdArgs& a = mv.v[blockIdx.y];
-  const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-  if (row >= a.rows) return;
-  ln_bwd_row<VPL, BLOCKED, false, true>(a, loss, row, lane);
-}
-
-// ... of a launch whose instances are LayerNorm-free layers, all of the width 64 * VPL (an MLP layer is alone in its launch):
-// plain_bwd_row in the same grid, the critic-loss rider in the same place
-template <int VPL, bool BLOCKED>
-__global__ __launch_bounds__(256) void plain_bwd_kernel(Multi<LnBwdArgs> mv, LossArgs loss) {
-  __shared__ float red[4][256];
-  if (loss.on && blockIdx.y == 0 && blockIdx.x == gridDim.x - 1) { critic_loss_body(loss, red); return; }
-  const LnBwdArgs& a = mv.v[blockIdx.y];
-  const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-  if (row >= a.rows) return;
-  plain_bwd_row<VPL, BLOCKED>(a, loss, row, lane);
-}
-
-// ... ragged rows / plain rows of a launch in which an instance has Dropout; the critic-loss rider in the same place
-template <int VPL, bool BLOCKED>
-__global__ __launch_bounds__(256) void ln_bwd_ragged_drop_kernel(Multi<LnBwdArgs> mv, LossArgs loss) {
-  __shared__ float red[4][256];
-  if (loss.on && blockIdx.y == 0 && blockIdx.x == gridDim.x - 1) { critic_loss_body(loss, red); return; }
-  const LnBwdArgs& a = mv.v[blockIdx.y];
-  const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-  if (row >= a.rows) return;
-  ln_bwd_row<VPL, BLOCKED, true, true>(a, loss, row, lane);
-}
-template <int VPL, bool BLOCKED>
-__global__ __launch_bounds__(256) void plain_bwd_drop_kernel(Multi<LnBwdArgs> mv, LossArgs loss) {
-  __shared__ float red[4][256];
-  if (loss.on && blockIdx.y == 0 && blockIdx.x == gridDim.x - 1) { critic_loss_body(loss, red); return; }
-  const LnBwdArgs& a = mv.v[blockIdx.y];
-  const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-  if (row >= a.rows) return;
-  plain_bwd_row<VPL, BLOCKED, true>(a, loss, row, lane);
+  if constexpr (!LN) plain_bwd_row<VPL, BLOCKED, DROP>(a, loss, row, lane);
+  else if constexpr (VPL != kLnMixed) ln_bwd_row<VPL, BLOCKED, RAGGED, DROP>(a, loss, row, lane);
+  else if (a.D == 256) ln_bwd_row<4, true, false, DROP>(a, loss, row, lane);
+  else ln_bwd_row<1, false, false, DROP>(a, loss, row, lane);
 }
 
 // One instance of a default width without a rider (most LayerNorm backward launches of the default agent, BC, the classifier):
@@ -1646,17 +1577,22 @@ int ln_bwd_multi(const LnBwdArgs* as, int n, const LossArgs& loss, hipStream_t s
   // one workgroup per row (ln_wide.h); such a width comes from one MLP layer and is every instance's
   if (as[0].D > 1024) return ln_wide_bwd(mv, n, rows, as[0].D, !as[0].gamma, drop, loss, stream);
   const dim3 grid(cdiv(rows, 4) + (loss.on ? 1 : 0), n);
-  if (!as[0].gamma && drop) SERL_LN_LAUNCH(as[0].D, (plain_bwd_drop_kernel<1, false>), (plain_bwd_drop_kernel<4, true>), plain_bwd_drop_kernel, grid, dim3(256), 0, stream, mv, loss)
-  else if (!as[0].gamma) SERL_LN_LAUNCH(as[0].D, (plain_bwd_kernel<1, false>), (plain_bwd_kernel<4, true>), plain_bwd_kernel, grid, dim3(256), 0, stream, mv, loss)
-  else if (as[0].d && drop) SERL_LN_LAUNCH(as[0].D, (ln_bwd_ragged_drop_kernel<1, false>), (ln_bwd_ragged_drop_kernel<4, true>), ln_bwd_ragged_drop_kernel, grid, dim3(256), 0, stream, mv, loss)
-  else if (as[0].d) SERL_LN_LAUNCH(as[0].D, (ln_bwd_ragged_kernel<1, false>), (ln_bwd_ragged_kernel<4, true>), ln_bwd_ragged_kernel, grid, dim3(256), 0, stream, mv, loss)
-  else if (drop) SERL_LN_LAUNCH(as[0].D, (ln_bwd_drop_kernel<kLnMixed, false>), (ln_bwd_drop_kernel<kLnMixed, false>), ln_bwd_drop_kernel, grid, dim3(256), 0, stream, mv, loss)
-  else if (n == 1 && !loss.on && as[0].D == 256) SERL_LAUNCH_CHAIN((ln_bwd_one_kernel<4, true>), grid, dim3(256), 0, stream, as[0]);
-  else if (n == 1 && !loss.on && as[0].D == 64) SERL_LAUNCH_CHAIN((ln_bwd_one_kernel<1, false>), grid, dim3(256), 0, stream, as[0]);
-  else SERL_LN_LAUNCH(as[0].D, (ln_bwd_kernel<kLnMixed, false>), (ln_bwd_kernel<kLnMixed, false>), ln_bwd_kernel, grid, dim3(256), 0, stream, mv, loss)
+  const int rc = ln_for_family(!as[0].gamma, as[0].gamma && as[0].d, drop, [&](auto ln, auto ragged, auto dr) {
+    // (64 and 256 mix in the launches of full-width LayerNorm rows)
+    return ln_for_width<SERL_C(ln) && !SERL_C(ragged)>(as[0].D, [&](auto vpl, auto blocked) {
+      if constexpr (SERL_C(vpl) == kLnMixed && !SERL_C(dr)) {   // one default-width instance, no rider, no Dropout: ln_bwd_one_kernel
+        if (n == 1 && !loss.on && as[0].D == 256) { SERL_LAUNCH_CHAIN((ln_bwd_one_kernel<4, true>), grid, dim3(256), 0, stream, as[0]); return; }
+        if (n == 1 && !loss.on) { SERL_LAUNCH_CHAIN((ln_bwd_one_kernel<1, false>), grid, dim3(256), 0, stream, as[0]); return; }
+      }
+      SERL_LAUNCH_CHAIN((ln_bwd_kernel<SERL_C(vpl), SERL_C(blocked), SERL_C(ln), SERL_C(ragged), SERL_C(dr)>), grid, dim3(256), 0, stream, mv, loss);
+    });
+  });
+  if (rc != SERL_OK) return rc;
   SERL_HIP(hipGetLastError());
   return SERL_OK;
 }
+#undef SERL_C
+#undef SERL_LAMBDA_INLINE
 
 // out[g][col] (+)= sum_{r in group g} X[r][col] * (Y ? Y[r][col] : 1)     (bias / LN-param grads)
 __global__ __launch_bounds__(256) void colsum_kernel(const float* X, const float* Y, int rows_per_group,

@@ -1,7 +1,7 @@
 // The WIDE rows of an MLP layer: storage widths D, a multiple of 64 with 1024 < D <= 4096, where ONE WORKGROUP OF FOUR WAVES owns
 // one row (the narrow rows of heads.hip: one wave per row, D <= 1024).  Device code and its two launchers; included once by
-// heads.hip, inside namespace serl, behind the narrow rows whose helpers it shares (ln_activate, sigmoid_stable, redq_target,
-// critic_loss_body).  Nothing of the narrow rows is changed: ln_fwd_multi / ln_bwd_multi hand a launch over when D > 1024.
+// heads.hip, inside namespace serl, behind the narrow rows whose helpers it shares (ln_activate, ln_dropout_n, row_dq,
+// critic_loss_body, ln_for_family).  ln_fwd_multi / ln_bwd_multi hand a launch over when D > 1024.
 //
 // Work split.  The row is D / 64 chunks of 64 columns, 17 to 64 of them, dealt to the four waves in turn: chunk c belongs to wave
 // c & 3, so wave w holds chunks w, w + 4, w + 8, ... and lane l of it the columns 64 (w + 4 j) + l -- the strided layout of the
@@ -53,34 +53,16 @@ __device__ __forceinline__ void wide_sum2(float& s1, float& s2, float* x, int wa
   s2 = ((x[1] + x[3]) + x[5]) + x[7];
 }
 
-// Dropout on a lane's CPW values of local row `lrow` (wide_col's columns; v's tail is 0 where the wave has no tail chunk)
+// Dropout on a lane's CPW values of local row `lrow`: ln_dropout_n (heads.hip) in the wide column map -- wide_col's columns; the
+// tail of a wave that has no tail chunk is not live
 template <int CPW>
 __device__ __forceinline__ void wide_dropout(const LnDrop& d, long lrow, int c0, bool tail_ok, int Nt, float (&v)[CPW]) {
-  const uint32_t thr = (uint32_t)(d.keep * 16777216.f);
-  const uint64_t n = (uint64_t)d.total_rows * (uint64_t)Nt, e0 = (uint64_t)(d.row0 + lrow) * (uint64_t)Nt;
-  uint32_t bits = 0;
-  if (d.mode == kLnDropKey) {
-#pragma unroll 1
-    for (int j = 0; j < CPW; ++j) {
-      const int cc = min(wide_col<CPW>(j, c0, tail_ok), Nt - 1);
-      bits |= (ln_keep_at(d, 0, n, e0 + (uint64_t)cc, thr) ? 1u : 0u) << j;
-    }
-  } else {
-#pragma unroll
-    for (int j = 0; j < CPW; ++j) {
-      const int cc = min(wide_col<CPW>(j, c0, tail_ok), Nt - 1);
-      bits |= (ln_keep_at(d, lrow * Nt + cc, n, e0 + (uint64_t)cc, thr) ? 1u : 0u) << j;
-    }
-  }
-#pragma unroll
-  for (int j = 0; j < CPW; ++j) {
-    const bool live = (j < CPW - 1 || tail_ok) && c0 + 256 * j < Nt;
-    v[j] = ((bits >> j) & 1u) && live ? v[j] / d.keep : 0.f;
-  }
+  ln_dropout_n(d, lrow, Nt, v, [&](int j) SERL_LAMBDA_INLINE { return wide_col<CPW>(j, c0, tail_ok); },
+               [&](int j) SERL_LAMBDA_INLINE { return (j < CPW - 1 || tail_ok) && c0 + 256 * j < Nt; });
 }
 
 // The forward row (ln_row / plain_row of heads.hip at these widths).  x: 12 floats of LDS.  DROP: see above.
-template <int CPW, bool LN, bool DROP = false>
+template <int CPW, bool LN, bool DROP>
 __device__ __forceinline__ void wide_row(const LnFwdArgs& a, int D, int row, int wave, int lane, float* x) {
   const bool tail_ok = wave + 4 * (CPW - 1) < (D >> 6);
   const int c0 = 64 * wave + lane;
@@ -145,26 +127,13 @@ __device__ __forceinline__ void wide_row(const LnFwdArgs& a, int D, int row, int
   }
 }
 
-template <int CPW, bool LN>
+// LN: LayerNorm or plain rows; DROP: a launch in which an instance has Dropout
+template <int CPW, bool LN, bool DROP>
 SERL_WIDE_KERNEL void ln_wide_fwd_kernel(Multi<LnFwdArgs> mv, int D) {
   __shared__ float x[12];
   const LnFwdArgs& a = mv.v[blockIdx.y];   // blockIdx.y = instance, blockIdx.x = row
   if ((int)blockIdx.x >= a.rows) return;   // (the whole workgroup)
-  wide_row<CPW, LN>(a, D, blockIdx.x, threadIdx.x >> 6, threadIdx.x & 63, x);
-}
-// ... of a launch in which an instance has Dropout
-template <int CPW, bool LN>
-SERL_WIDE_KERNEL void ln_wide_fwd_drop_kernel(Multi<LnFwdArgs> mv, int D) {
-  __shared__ float x[12];
-  const LnFwdArgs& a = mv.v[blockIdx.y];
-  if ((int)blockIdx.x >= a.rows) return;
-  wide_row<CPW, LN, true>(a, D, blockIdx.x, threadIdx.x >> 6, threadIdx.x & 63, x);
-}
-
-// dy of a lane's column in the three forms of ln_bwd_row
-__device__ __forceinline__ float wide_dq(const LnBwdArgs& a, const LossArgs& L, int row, long lr) {
-  if (!a.dq_w) return 0.f;
-  return a.dq_inline ? 2.f * (L.q[row] - redq_target(L, (int)lr)) * L.inv_norm : (a.dq ? a.dq[row] : a.dq_const);
+  wide_row<CPW, LN, DROP>(a, D, blockIdx.x, threadIdx.x >> 6, threadIdx.x & 63, x);
 }
 
 // The backward LayerNorm row (ln_bwd_row of heads.hip at these widths; ragged by a.d).  x: 8 floats of LDS.  DROP: dx wrt the
@@ -177,7 +146,7 @@ __device__ __forceinline__ void wide_bwd_row(const LnBwdArgs& a, const LossArgs&
   const int grp = row / a.rows_per_group;
   const long lr = row - grp * a.rows_per_group;
   const long pb = (long)grp * a.pstride;
-  const float dqr = wide_dq(a, L, row, lr);
+  const float dqr = row_dq(a, L, row, lr);
   float dg[CPW], dxh[CPW], xh[CPW], y[CPW], gam[CPW];
 #pragma unroll
   for (int j = 0; j < CPW; ++j) {
@@ -244,7 +213,7 @@ __device__ __forceinline__ void wide_plain_bwd_row(const LnBwdArgs& a, const Los
   const int c0 = 64 * wave + lane;
   const int grp = row / a.rows_per_group;
   const long lr = row - grp * a.rows_per_group;
-  const float dqr = wide_dq(a, L, row, lr);
+  const float dqr = row_dq(a, L, row, lr);
   float dg[CPW], y[CPW];
 #pragma unroll
   for (int j = 0; j < CPW; ++j) {
@@ -274,50 +243,42 @@ __device__ __forceinline__ void wide_plain_bwd_row(const LnBwdArgs& a, const Los
 }
 
 // blockIdx.y = instance, blockIdx.x = row; the LAST workgroup of instance 0 is the critic-loss rider when loss.on, as in the
-// narrow launches
-template <int CPW, bool LN>
+// narrow launches.  LN, DROP: as in ln_wide_fwd_kernel.
+template <int CPW, bool LN, bool DROP>
 SERL_WIDE_KERNEL void ln_wide_bwd_kernel(Multi<LnBwdArgs> mv, LossArgs loss) {
   __shared__ float red[4][256];
   if (loss.on && blockIdx.y == 0 && blockIdx.x == gridDim.x - 1) { critic_loss_body(loss, red); return; }
   const LnBwdArgs& a = mv.v[blockIdx.y];
   if ((int)blockIdx.x >= a.rows) return;   // (the whole workgroup)
-  if constexpr (LN) wide_bwd_row<CPW>(a, loss, blockIdx.x, threadIdx.x >> 6, threadIdx.x & 63, &red[0][0]);
-  else wide_plain_bwd_row<CPW>(a, loss, blockIdx.x, threadIdx.x >> 6, threadIdx.x & 63);
+  if constexpr (LN) wide_bwd_row<CPW, DROP>(a, loss, blockIdx.x, threadIdx.x >> 6, threadIdx.x & 63, &red[0][0]);
+  else wide_plain_bwd_row<CPW, DROP>(a, loss, blockIdx.x, threadIdx.x >> 6, threadIdx.x & 63);
 }
 
-// ... of a launch in which an instance has Dropout
-template <int CPW, bool LN>
-SERL_WIDE_KERNEL void ln_wide_bwd_drop_kernel(Multi<LnBwdArgs> mv, LossArgs loss) {
-  __shared__ float red[4][256];
-  if (loss.on && blockIdx.y == 0 && blockIdx.x == gridDim.x - 1) { critic_loss_body(loss, red); return; }
-  const LnBwdArgs& a = mv.v[blockIdx.y];
-  if ((int)blockIdx.x >= a.rows) return;
-  if constexpr (LN) wide_bwd_row<CPW, true>(a, loss, blockIdx.x, threadIdx.x >> 6, threadIdx.x & 63, &red[0][0]);
-  else wide_plain_bwd_row<CPW, true>(a, loss, blockIdx.x, threadIdx.x >> 6, threadIdx.x & 63);
-}
-
-// The launch of a width: K<ceil(D / 256), LN>
-#define SERL_WIDE_CASE(V, K, LN, ...) case V: SERL_LAUNCH_CHAIN((K<V, LN>), __VA_ARGS__); break;
-#define SERL_WIDE_CASES(K, LN, ...)                                                                                              \
-    SERL_WIDE_CASE(5, K, LN, __VA_ARGS__) SERL_WIDE_CASE(6, K, LN, __VA_ARGS__) SERL_WIDE_CASE(7, K, LN, __VA_ARGS__)             \
-    SERL_WIDE_CASE(8, K, LN, __VA_ARGS__) SERL_WIDE_CASE(9, K, LN, __VA_ARGS__) SERL_WIDE_CASE(10, K, LN, __VA_ARGS__)            \
-    SERL_WIDE_CASE(11, K, LN, __VA_ARGS__) SERL_WIDE_CASE(12, K, LN, __VA_ARGS__) SERL_WIDE_CASE(13, K, LN, __VA_ARGS__)          \
-    SERL_WIDE_CASE(14, K, LN, __VA_ARGS__) SERL_WIDE_CASE(15, K, LN, __VA_ARGS__) SERL_WIDE_CASE(16, K, LN, __VA_ARGS__)
-#define SERL_WIDE_LAUNCH(D, K, LN, ...)                                                                                          \
-  switch (cdiv((D) / 64, 4)) {                                                                                                   \
-    SERL_WIDE_CASES(K, LN, __VA_ARGS__)                                                                                           \
-    default: serl::set_error("wide LayerNorm width %d has no kernel", (int)(D)); return SERL_ERR_INVALID;                        \
+// wide width -> launch(CPW), CPW = ceil(D / 256); the family comes from ln_for_family (heads.hip), whose RAGGED these rows do not
+// read: they are ragged by a.d at run time
+template <class F>
+static int wide_for_width(int D, F&& launch) {
+  switch (cdiv(D / 64, 4)) {
+#define SERL_WIDE_CASE(V) case V: launch(IntC<V>{}); break;
+    SERL_WIDE_CASE(5) SERL_WIDE_CASE(6) SERL_WIDE_CASE(7) SERL_WIDE_CASE(8) SERL_WIDE_CASE(9) SERL_WIDE_CASE(10)
+    SERL_WIDE_CASE(11) SERL_WIDE_CASE(12) SERL_WIDE_CASE(13) SERL_WIDE_CASE(14) SERL_WIDE_CASE(15) SERL_WIDE_CASE(16)
+#undef SERL_WIDE_CASE
+    default: serl::set_error("wide LayerNorm width %d has no kernel", D); return SERL_ERR_INVALID;
   }
+  return SERL_OK;
+}
 
 // mv, rows (the most of any instance), D, plain, drop (an instance carries Dropout) as ln_fwd_multi validated them; one workgroup
 // per row and instance
 int ln_wide_fwd(const Multi<LnFwdArgs>& mv, int n, int rows, int D, bool plain, bool drop, hipStream_t stream) {
   SERL_REQUIRE(D > 1024 && D <= kWideMax && D % 64 == 0 && rows >= 1, "wide LayerNorm row: width %d, %d rows", D, rows);
   const dim3 grid(rows, n);
-  if (plain && drop) SERL_WIDE_LAUNCH(D, ln_wide_fwd_drop_kernel, false, grid, dim3(256), 0, stream, mv, D)
-  else if (drop) SERL_WIDE_LAUNCH(D, ln_wide_fwd_drop_kernel, true, grid, dim3(256), 0, stream, mv, D)
-  else if (plain) SERL_WIDE_LAUNCH(D, ln_wide_fwd_kernel, false, grid, dim3(256), 0, stream, mv, D)
-  else SERL_WIDE_LAUNCH(D, ln_wide_fwd_kernel, true, grid, dim3(256), 0, stream, mv, D)
+  const int rc = ln_for_family(plain, false, drop, [&](auto ln, auto, auto dr) {
+    return wide_for_width(D, [&](auto cpw) {
+      SERL_LAUNCH_CHAIN((ln_wide_fwd_kernel<SERL_C(cpw), SERL_C(ln), SERL_C(dr)>), grid, dim3(256), 0, stream, mv, D);
+    });
+  });
+  if (rc != SERL_OK) return rc;
   SERL_HIP(hipGetLastError());
   return SERL_OK;
 }
@@ -326,10 +287,12 @@ int ln_wide_fwd(const Multi<LnFwdArgs>& mv, int n, int rows, int D, bool plain, 
 int ln_wide_bwd(const Multi<LnBwdArgs>& mv, int n, int rows, int D, bool plain, bool drop, const LossArgs& loss, hipStream_t stream) {
   SERL_REQUIRE(D > 1024 && D <= kWideMax && D % 64 == 0 && rows >= 1, "wide LayerNorm backward: width %d, %d rows", D, rows);
   const dim3 grid(rows + (loss.on ? 1 : 0), n);
-  if (plain && drop) SERL_WIDE_LAUNCH(D, ln_wide_bwd_drop_kernel, false, grid, dim3(256), 0, stream, mv, loss)
-  else if (drop) SERL_WIDE_LAUNCH(D, ln_wide_bwd_drop_kernel, true, grid, dim3(256), 0, stream, mv, loss)
-  else if (plain) SERL_WIDE_LAUNCH(D, ln_wide_bwd_kernel, false, grid, dim3(256), 0, stream, mv, loss)
-  else SERL_WIDE_LAUNCH(D, ln_wide_bwd_kernel, true, grid, dim3(256), 0, stream, mv, loss)
+  const int rc = ln_for_family(plain, false, drop, [&](auto ln, auto, auto dr) {
+    return wide_for_width(D, [&](auto cpw) {
+      SERL_LAUNCH_CHAIN((ln_wide_bwd_kernel<SERL_C(cpw), SERL_C(ln), SERL_C(dr)>), grid, dim3(256), 0, stream, mv, loss);
+    });
+  });
+  if (rc != SERL_OK) return rc;
   SERL_HIP(hipGetLastError());
   return SERL_OK;
 }
